@@ -1,6 +1,7 @@
 """bench.py — dynamic-embedding hot path on MI355X (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config m1b|c3|c2|c4|c5] [--slots S] [--keys N_KEYS] [--batch B]
+                  [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic ids.  Configurations (BASELINE.json `configs`):
 
@@ -20,7 +21,16 @@ One "step" = one pass of the hot path over one batch of synthetic ids.  Configur
   c5  configs[4]: 26 tables, dims {16,32,64,128}, fused FTRL.  `--config c5` on one GPU: the local multi-table drivers
       (tfra_multi_step_prefetch ...) plus the N = 1 point of the routed form; `--config c5 --gpus N`: every table hash-sharded over
       the N ranks, one tfra_route per table on one shared transport (MultiTableRoutedStep), per-GPU batch B per table.
-  The default invocation at N=1 prints m1b as the top-level line and c3 / c2 / c4 / c5 (routed, small tables) under "secondary".
+  The default invocation at N=1 prints m1b as the top-level line; with `--full`, c3 / c2 / c4 / c5 (routed, small tables) under
+  "secondary".
+
+Without `--full` a run on the bounded table (m1b, c3) does only what `value` needs: set-up, W warm-up steps and the K timed steps of
+the one driver the rule below names, the dump of `--dump-outputs`, the line.  `--full` adds everything else this file measures or
+checks: the other drivers and op-surface variants, per-kernel timings and the roofline, the untimed verification, the live traffic
+passes, the growth measurement, the secondary workloads and the CPU baseline.
+`--dump-outputs DIR`: after the timed steps, the rows the timed driver's LAST step returned to its caller (its lookup of one batch)
+go to DIR/rows.npy in float32 (beyond DUMP_LIMIT bytes, a fixed seeded sample of the rows); every input is generated from fixed
+seeds, so two builds run with the same arguments can be compared output for output.
 
 `value` = ids looked up AND written back per second (lookup+insert pairs/s), whole job.  On the assign workloads (m1b, c3) the
 faster of the table's two step drivers, both reported (`faster_driver` names it):
@@ -36,10 +46,11 @@ on the gradient workloads (c2, c4) the look-ahead driver with the fused optimize
                       exactly what the TF shim (tf_ops/mi355x_table_ops.h) issues; `value_op_surface_find_first`: round 3's order;
   `value_op_surface_table_ops_only` Find(B) + Insert(U) with the unique keys prepared beforehand;
   `value_accum`       bp_v2: Find(B) + insert_or_accum of the U unique keys.
-Timing: after W warm-up steps, R = 5 back-to-back windows of exactly K steps each, every window bracketed by
-barrier + torch.cuda.synchronize() (max over ranks); `value` / `ms_per_step` are the MEDIAN window, min / max are in
-config.timing.  Inputs (id batches, values, gradients) are generated on the device and resident in HBM before the timed
-region; an untimed verification pass checks the table against the values written (config.verified).
+Timing: on the bounded table, `value` / `ms_per_step` come from ONE window of exactly K steps after W warm-up steps, bracketed by
+torch.cuda.synchronize().  Every other number (the `--full` variants, and the other configurations) is timed as R = 5 back-to-back
+windows of exactly K steps each after W warm-up steps, every window bracketed by barrier + torch.cuda.synchronize() (max over
+ranks), and reports the MEDIAN window, min / max in config.timing.  Inputs (id batches, values, gradients) are generated on the device and resident in HBM before the timed
+region; with `--full`, an untimed verification pass checks the table against the values written (config.verified).
 N>1: one process per GPU.  Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -162,9 +173,12 @@ class IdFactory:
     self.n_new = int(round(batch * new_ratio))
     self.pos = (torch.arange(self.n_new, device=dev, dtype=torch.float64) * (batch / max(1, self.n_new))).to(torch.int64)
 
-  def ranks(self, nbatch):
+  def keys(self, nbatch, out=None):
+    """[nbatch, B] keys, into `out` when given.  Drawn and scrambled 64 batches at a time straight into the result: full-size
+    temporaries would take several times the ids' own memory beside a table that fills the device."""
     t = self.torch
-    out = []
+    if out is None:
+      out = t.empty((nbatch, self.B), dtype=t.int64, device=self.dev)
     for lo in range(0, nbatch, 64):   # bounded scratch: 64 batches per draw
       m = min(64, nbatch - lo)
       r = zipf_bounded_torch(t, self.gen, m * self.B, self.n, self.dev).reshape(m, self.B)
@@ -172,11 +186,8 @@ class IdFactory:
         fresh = self.fresh + t.arange(m * self.n_new, device=self.dev, dtype=t.int64).reshape(m, self.n_new)
         r[:, self.pos] = fresh
         self.fresh += m * self.n_new
-      out.append(r)
-    return t.cat(out) if len(out) > 1 else out[0]
-
-  def keys(self, nbatch):
-    return keys_of_ranks_torch(self.torch, self.ranks(nbatch))
+      out[lo:lo + m] = keys_of_ranks_torch(t, r)
+    return out
 
 
 # ------------------------------------------------------------------ CPU baseline (reference engine)
@@ -450,6 +461,23 @@ def timing_note(secs, K):
           "ms_per_step_by_window": [round(x / K * 1e3, 5) for x in secs]}
 
 
+DUMP_LIMIT = 48 << 20   # bytes of float32 rows --dump-outputs writes at most
+
+
+def dump_output(path, name, t):
+  """--dump-outputs: the [n, dim] tensor `t` as path/<name>.npy in float32 — beyond DUMP_LIMIT bytes a fixed, seeded sample of its rows
+  (in row order), the same rows in every run with the same arguments"""
+  import torch
+  a = t.float()
+  if a.numel() * 4 > DUMP_LIMIT:
+    keep = DUMP_LIMIT // (4 * a[0].numel())
+    idx = np.sort(np.random.default_rng(SEED).choice(a.shape[0], keep, replace=False))
+    a = a[torch.from_numpy(idx).to(a.device)]
+  os.makedirs(path, exist_ok=True)
+  np.save(os.path.join(path, name + ".npy"), a.cpu().numpy())
+  note("outputs: %s/%s.npy %s float32" % (path, name, list(a.shape)))
+
+
 def profile_summary():
   """the newest committed rocprofv3 summary (profiles/rNN_summary.json, made by scripts/run_profile_round.sh: separate --pmc FETCH_SIZE /
   WRITE_SIZE passes, corrected as MI355X_MICROARCH.md prescribes) — `roofline.traffic` is READ from it, not measured by this run:
@@ -467,7 +495,7 @@ def profile_summary():
 
 def live_traffic(args):
   """`roofline.traffic` measured BY THIS RUN when rocprofv3 is here: two short child runs of the headline workload alone
-  (`--config m1b --no-secondary --no-cpu-baseline --steps 10 --warmup 5`), one per counter as MI355X_MICROARCH.md prescribes
+  (`--config m1b --full --no-secondary --no-cpu-baseline --steps 10 --warmup 5`), one per counter as MI355X_MICROARCH.md prescribes
   (`rocprofv3 --pmc FETCH_SIZE --kernel-trace`, then `--pmc WRITE_SIZE --kernel-trace`: PMC passes on their own, never with API
   tracing), BEFORE this process touches the GPU (the table takes 273 of the 288 GB).  Per launch of the step kernel:
   (2 x FETCH_SIZE + WRITE_SIZE) KiB — gfx950 reports half of the wide coalesced reads.  Returns {"step_k": bytes, "source": ...} or None
@@ -493,7 +521,7 @@ def live_traffic(args):
     for c in ("FETCH_SIZE", "WRITE_SIZE"):
       d = os.path.join(tmp, c)
       cmd = [exe, "--pmc", c, "--kernel-trace", "--output-format", "csv", "-d", d, "-o", "live", "--", sys.executable, os.path.abspath(__file__),
-             "--config", "m1b", "--no-secondary", "--no-cpu-baseline", "--steps", "10", "--warmup", "5", "--slots", str(args.slots),
+             "--config", "m1b", "--full", "--no-secondary", "--no-cpu-baseline", "--steps", "10", "--warmup", "5", "--slots", str(args.slots),
              "--batch", str(args.batch)]
       t0 = time.perf_counter()
       pr = subprocess.Popen(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
@@ -594,8 +622,38 @@ def last_occurrence_rows(torch, ids, values):
   return values[lp][inv]
 
 
-def run_bounded(args, torch, de, dev, cfg):
-  """cfg 'm1b': dim 64 fp32, `--new-key-ratio` (default 0) never-seen ids;  'c3': dim 128 fp16, 50 % never-seen ids."""
+def time_headline(torch, de, dev, table, idf, values, K, W, overlapped):
+  """The headline driver on fresh batches: W warm-up steps, then ONE window of exactly K steps, one host call per step.  Returns
+  (window seconds, host seconds of its enqueue loop, the rows its last step returned); its ids and step arrays go with it."""
+  ids = idf.keys(W + K + 3)
+  if overlapped:
+    drv = de.OverlapAssignStep(table).prime(ids[0])
+    for i in range(W):
+      drv.step(values, ids[i + 1], ids[i + 2])
+    outs = [torch.empty_like(values) for _ in range(2)]
+    runs = [drv.make_run([ids[W + c]], [values], [outs[c % 2]], ids_after=ids[W + c + 1], values_before=values if (W + c) else None,
+                         ids_after2=ids[W + c + 2]) for c in range(K)]
+    (secs,), _, host_s = timed_windows(torch, None, 1, dev, K, lambda i: runs[i - W](), first=W, windows=1)
+    rows = outs[(K - 1) % 2]
+    drv.flush()
+  else:
+    drv = de.PrefetchAssignStep(table).prime(ids[0])
+    for i in range(W):
+      drv.step(values, ids[i + 1])
+    last = [None]
+
+    def step(i):
+      last[0] = drv.step(values, ids[i + 1])
+
+    (secs,), _, host_s = timed_windows(torch, None, 1, dev, K, step, first=W, windows=1)
+    rows = last[0]
+  torch.cuda.synchronize()
+  return secs, host_s, rows
+
+
+def run_bounded(args, torch, de, dev, cfg, dump=None):
+  """cfg 'm1b': dim 64 fp32, `--new-key-ratio` (default 0) never-seen ids;  'c3': dim 128 fp16, 50 % never-seen ids.
+  dump: the --dump-outputs directory of the run's top-level workload (None: write nothing)."""
   import ctypes
   from tfra_amd import _capi
   from tfra_amd.dynamic_embedding.table_ops import _ptr, _stream
@@ -606,7 +664,7 @@ def run_bounded(args, torch, de, dev, cfg):
   Rb = dim * (2 if dtype == torch.float16 else 4)
   want = args.slots
   growth = None
-  if cfg == "c3":   # (the default invocation measures it FIRST, on a fresh device: right behind the release of another 273-GB table the
+  if cfg == "c3" and args.full:   # (the default invocation measures it FIRST, on a fresh device: right behind the release of another 273-GB table the
     growth = getattr(args, "_growth", None) or measure_growth(torch, de, dev, dim, dtype, want // 4)   # driver is still reclaiming memory, 6 s instead of 18 ms)
   table, failures = None, []
   for slots in [want] + [int(want * f) for f in (0.9, 0.8, 0.7, 0.6, 0.5, 0.4, 0.25)]:
@@ -654,7 +712,44 @@ def run_bounded(args, torch, de, dev, cfg):
     del wids
   torch.cuda.synchronize()
 
-  # ---- driver 1 (`value`): the overlapped step — ONE launch per step: lookup of batch i+1 (ids of batch i served from the rows
+  # ---- the headline (`value`, `ms_per_step`): ONE driver per workload, chosen by RULE (de.assign_step_driver_for: the stream's share of
+  # never-seen ids), not by result — the overlapped step for streams that mostly revisit resident keys (the metric's), the look-ahead
+  # driver when more than a tenth of a batch are never-seen ids (configs[2]: the write-back with its evictions is the long pole and runs
+  # faster as kernels of its own).  W warm-up steps, then ONE window of exactly K steps, one host call per step, fresh batches.
+  best_is_overlapped = de.assign_step_driver_for(new_ratio) == "overlapped_step"
+  head_s, head_host_s, head_rows = time_headline(torch, de, dev, table, idf, values, K, W, best_is_overlapped)
+  if dump:
+    dump_output(dump, "rows", head_rows)
+  del head_rows
+  ms = head_s / K * 1e3
+  value = B * K / head_s
+  note("%s: headline timed (%.2f us/step)" % (cfg, ms * 1e3))
+  driver = "overlapped_step" if best_is_overlapped else "look_ahead"
+  driver_rule = ("de.assign_step_driver_for(new_key_ratio): overlapped_step when <= 10 %% of a batch are never-seen ids, else look_ahead "
+                 "(new_key_ratio here: %.2f)" % new_ratio)
+  cfg_name = "2" if cfg == "c3" else "metric (dim 64 fp32, 1 B keys, Zipf-1.2)"
+  metric = ("embedding lookup+insert pairs/s (%s, %d-slot bounded table, %d %% never-seen ids per batch: lookup + insert_or_assign with "
+            "score-based eviction)" % ("dim=128 fp16" if cfg == "c3" else "dim=64 fp32", capacity, round(100 * new_ratio)))
+  workload = ("BASELINE configs[%s]: bounded Hkv (LRU) table, %d slots (%.1f GB in HBM: key line + score line + 15 rows per "
+              "4 KiB bucket block), pre-filled with %d unique keys -> %d resident, %s rows, batch=%d = %d %% Zipf-1.2 over "
+              "the %d ranks + %d %% never-seen ranks; step = lookup(B) + insert_or_assign(B, last occurrence "
+              "wins) with eviction%s" % (cfg_name, capacity, capacity / 15 * (256 + 15 * Rb) / 1e9, n_res, resident,
+                                          "dim=128 fp16" if cfg == "c3" else "dim=64 fp32", B, round(100 * (1 - new_ratio)), n_res,
+                                          round(100 * new_ratio),
+                                          "; the export sweep of configs[2] ('every 1000 steps') is outside the timed region, see config.export"
+                                          if (cfg == "c3" and args.full) else ""))
+  head_timing = {"windows": 1, "steps": K, "warmup_steps": W, "ms_per_step": round(ms, 5)}
+  if not args.full:
+    res = {"metric": metric, "value": value, "unit": "pairs/s", "n_gpus": 1, "steps": K, "warmup": W, "ms_per_step": ms,
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16" if dtype == torch.float16 else "f32",
+           "data": "synthetic", "driver": driver, "driver_rule": driver_rule,
+           "config": {"workload": workload, "slots": capacity, "requested_slots": want, "alloc_failures": failures,
+                      "resident_after_prefill": resident, "new_key_ratio": new_ratio, "global_batch": B, "prefill_s": round(t_fill, 2),
+                      "state_warm_steps_before_any_timing": state_warm_steps, "steps_per_host_call": 1,
+                      "host_enqueue_ms_per_step": round(1e3 * head_host_s / K, 4), "timing": {"value": head_timing}}}
+    return res
+
+  # ---- driver 1: the overlapped step — ONE launch per step: lookup of batch i+1 (ids of batch i served from the rows
   # being written: store-to-load forwarding through batch i's plan), write-back of batch i, its left-over keys and the output
   # corrections (tail), and the plans of the next two batches (built over two launches, without atomics); D steps per host call
   # (tfra_table_steps_overlap), one stream, nothing waits on the host.  Lookup outputs: a ring of D buffers.
@@ -828,7 +923,7 @@ def run_bounded(args, torch, de, dev, cfg):
   fus = [(tbl._h, ws, B, P(ids[i]), P(out_buf), None, P(dflt_row), 0, P(ubuf), P(ibuf), cpin_p, st) for i in range(nsteps)]
   # (every variant on batches of its own — new never-seen ids where the workload has them: the argument blocks point into `ids`, which is
   # refilled in place)
-  ids.copy_(idf.keys(nsteps))
+  idf.keys(nsteps, out=ids)
   for i in range(W):
     op_surface_fused(i)
   secs_opfu, med_opfu, _ = timed_windows(torch, None, 1, dev, K, op_surface_fused, first=W)
@@ -836,12 +931,12 @@ def run_bounded(args, torch, de, dev, cfg):
   u = int(cpin[0])
   got, ex = table.lookup(ubuf[:u], return_exists=True)
   verified["op_surface_fused_ops_last_batch"] = bool(ex.all()) and bool(torch.equal(got, values[:u]))
-  ids.copy_(idf.keys(nsteps))
+  idf.keys(nsteps, out=ids)
   for i in range(W):
     op_surface(i)
   secs_ops, med_ops, _ = timed_windows(torch, None, 1, dev, K, op_surface, first=W)
   torch.cuda.synchronize()
-  ids.copy_(idf.keys(nsteps))
+  idf.keys(nsteps, out=ids)
   for i in range(W):
     op_surface_sync(i)
   secs_ops_sync, med_ops_sync, _ = timed_windows(torch, None, 1, dev, K, op_surface_sync, first=W)
@@ -944,14 +1039,7 @@ def run_bounded(args, torch, de, dev, cfg):
   bad = [k for k, v in verified.items() if v is False]
   assert not bad, "bench verification failed: %s (overlapped step: %s)" % (bad, ovl_stats)
 
-  # `value` = ONE driver per workload, chosen by RULE (de.assign_step_driver_for: the stream's share of never-seen ids), not by
-  # result: the overlapped step for streams that mostly revisit resident keys (the metric's), the look-ahead driver when more than
-  # a tenth of a batch are never-seen ids (configs[2]: the write-back with its evictions is the long pole and runs faster as
-  # kernels of its own).  The other driver's number is reported beside it.
-  best_is_overlapped = de.assign_step_driver_for(new_ratio) == "overlapped_step"
-  med_best = med if best_is_overlapped else med_pf
-  ms = med_best / K * 1e3
-  value = B * K / med_best
+  # `value` / `ms` are the headline's (above); both drivers' median windows are reported beside it
   lookup_bytes = B * (8 + 2 * Rb)                      # key + row read + row written out
   upsert_bytes = U * (8 + Rb + Rb + 8)                 # per unique key: key, value row read, row written, key stored
   step_bytes = step_bytes_ = lookup_bytes + upsert_bytes
@@ -977,20 +1065,16 @@ def run_bounded(args, torch, de, dev, cfg):
   }
   on_step = list(kernels)[:1] if best_is_overlapped else list(kernels)[1:3]   # the launches of the `value` step
   dom = max(on_step, key=lambda k: kernels[k]["avg_launch_us"])
-  cfg_name = "2" if cfg == "c3" else "metric (dim 64 fp32, 1 B keys, Zipf-1.2)"
   res = {
-      "metric": "embedding lookup+insert pairs/s (%s, %d-slot bounded table, %d %% never-seen ids per batch: lookup + "
-                "insert_or_assign with score-based eviction)" % ("dim=128 fp16" if cfg == "c3" else "dim=64 fp32", capacity,
-                                                                 round(100 * new_ratio)),
+      "metric": metric,
       "value": value, "unit": "pairs/s", "n_gpus": 1, "steps": K, "warmup": W, "ms_per_step": ms,
       "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16" if dtype == torch.float16 else "f32",
       "data": "synthetic",
       "value_overlapped_step": B * K / med, "ms_per_step_overlapped_step": med / K * 1e3,
       "value_overlapped_step_4_steps_per_host_call": B * K / med_d4, "ms_per_step_overlapped_step_4_steps_per_host_call": med_d4 / K * 1e3,
       "value_look_ahead_driver": B * K / med_pf, "ms_per_step_look_ahead_driver": med_pf / K * 1e3,
-      "driver": "overlapped_step" if best_is_overlapped else "look_ahead",
-      "driver_rule": "de.assign_step_driver_for(new_key_ratio): overlapped_step when <= 10 %% of a batch are never-seen ids, else look_ahead "
-                     "(new_key_ratio here: %.2f)" % new_ratio,
+      "driver": driver,
+      "driver_rule": driver_rule,
       "routed_local": None if routed_local is None else (routed_local if "error" in routed_local else {
           "value": B * K / routed_local["med"], "ms_per_step": routed_local["med"] / K * 1e3, "owner_launch_us": routed_local["owner_launch_us"],
           "host_enqueue_ms_per_step": round(1e3 * routed_local["host_s"] / K, 4), "served_ids_per_step": routed_local["served_ids"],
@@ -1003,31 +1087,26 @@ def run_bounded(args, torch, de, dev, cfg):
       "value_accum": B * K / med_acc, "ms_per_step_accum": med_acc / K * 1e3,
       "value_op_surface_table_ops_only": B * K / med_tops, "ms_per_step_op_surface_table_ops_only": med_tops / K * 1e3,
       "config": {
-          "workload": "BASELINE configs[%s]: bounded Hkv (LRU) table, %d slots (%.1f GB in HBM: key line + score line + 15 rows per "
-                      "4 KiB bucket block), pre-filled with %d unique keys -> %d resident, %s rows, batch=%d = %d %% Zipf-1.2 over "
-                      "the %d ranks + %d %% never-seen ranks; step = lookup(B) + insert_or_assign(B, last occurrence "
-                      "wins) with eviction%s" % (cfg_name, capacity, capacity / 15 * (256 + 15 * Rb) / 1e9, n_res, resident,
-                                                  "dim=128 fp16" if cfg == "c3" else "dim=64 fp32", B, round(100 * (1 - new_ratio)), n_res,
-                                                  round(100 * new_ratio),
-                                                  "; the export sweep of configs[2] ('every 1000 steps') is outside the timed region, see config.export" if cfg == "c3" else ""),
+          "workload": workload,
           "slots": capacity, "requested_slots": want, "alloc_failures": failures, "growth_in_place": growth,
           "resident_after_prefill": resident,
           "resident_after_timed_steps": size_after, "new_key_ratio": new_ratio, "global_batch": B,
           "unique_ratio": round(uniq_ratio, 4), "unique_keys_per_batch": U, "prefill_s": round(t_fill, 2),
           "state_warm_steps_before_any_timing": state_warm_steps,
-          "table_ops_per_s": (B + U) * K / med_best,
+          "table_ops_per_s": (B + U) * K / head_s,
           "table_ops_per_s_counts": "B lookups + U row writes (the distinct keys of the batch) per step",
-          "host_enqueue_ms_per_step": round(1e3 * (host_s if best_is_overlapped else host_pf) / K, 4), "steps_per_host_call": 1,
+          "host_enqueue_ms_per_step": round(1e3 * head_host_s / K, 4), "steps_per_host_call": 1,
           "host_enqueue_ms_per_step_overlapped_step": round(1e3 * host_s / K, 4),
           "host_enqueue_ms_per_step_overlapped_step_4_steps_per_host_call": round(1e3 * host_d4 / K, 4),
           "host_enqueue_ms_per_step_look_ahead_driver": round(1e3 * host_pf / K, 4),
           "overlapped_step_stats": ovl_stats,
-          "timing": {"value_overlapped_step": timing_note(secs, K), "value_overlapped_step_4_steps_per_host_call": timing_note(secs_d4, K), "value_look_ahead_driver": timing_note(secs_pf, K), "value_plain_call": timing_note(secs_plain, K),
+          "timing": {"value": head_timing, "value_overlapped_step": timing_note(secs, K), "value_overlapped_step_4_steps_per_host_call": timing_note(secs_d4, K), "value_look_ahead_driver": timing_note(secs_pf, K), "value_plain_call": timing_note(secs_plain, K),
                      "value_op_surface": timing_note(secs_ops, K), "value_op_surface_fused_ops": timing_note(secs_opfu, K), "value_op_surface_find_first": timing_note(secs_opf, K), "value_op_surface_host_read_first": timing_note(secs_ops_sync, K),
                      "value_accum": timing_note(secs_acc, K), "value_op_surface_table_ops_only": timing_note(secs_tops, K)},
           "verified": verified,
           "drivers": {
-              "value": "= value_overlapped_step" if best_is_overlapped else "= value_look_ahead_driver",
+              "value": "the driver of value_%s, timed on fresh batches of its own: W warm-up steps, then ONE window of the K steps"
+                       % ("overlapped_step" if best_is_overlapped else "look_ahead_driver"),
               "value_overlapped_step": "tfra_table_steps_overlap (csrc/tfra_step_impl.h): ONE launch per step on one stream = lookup of batch i+1 (ids of "
                        "batch i served from the rows being written: store-to-load forwarding through batch i's plan) + ownership "
                        "write-back of batch i + its left-over keys and the output corrections (tail blocks of the same launch) + the "
@@ -1824,8 +1903,9 @@ def compact_line(res, detail_path=None):
     for k, v in ((rr.get("config") or {}).get("verified") or {}).items():
       flags["%s.%s" % (name, k)] = v
   bools = [v for v in flags.values() if isinstance(v, bool)]
-  line["verified"] = bool(bools) and all(bools)
-  line["verified_flags"] = len(bools)
+  if "verified" in cfg or res.get("secondary"):   # (a run without --full checks nothing and says nothing about it)
+    line["verified"] = bool(bools) and all(bools)
+    line["verified_flags"] = len(bools)
   r = _pick(rf, ("bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_source", "traffic_profile_summary", "algorithmic_bytes_per_launch",
                  "avg_launch_us", "step_frac", "step_algorithmic_bytes"))
   if r.get("traffic_profile_summary") is None:
@@ -1835,7 +1915,8 @@ def compact_line(res, detail_path=None):
   r["kernel"] = _short(rf.get("kernel"), 150)
   if r.get("traffic") is not None and r.get("algorithmic_bytes_per_launch"):
     r["traffic_over_algorithmic"] = _num(r["traffic"] / r["algorithmic_bytes_per_launch"], 3)
-  line["roofline"] = r
+  if rf:
+    line["roofline"] = r
   if cb is not None:
     b = _pick(cb, ("value", "unit", "cores", "kind", "resident_keys", "table_ops_only_pairs_per_s", "host_cores",
                    "prefill_keys_per_s_init_size_8192_growth_included", "small_table_legs_keys"))
@@ -1923,7 +2004,16 @@ def main():
   ap.add_argument("--new-key-ratio", type=float, default=None, help="c2 / m1b: share of never-seen keys per batch")
   ap.add_argument("--no-cpu-baseline", action="store_true")
   ap.add_argument("--no-secondary", action="store_true", help="skip the secondary c3 / c2 / c4 measurements of the default invocation")
+  ap.add_argument("--full", action="store_true",
+                  help="measure and check everything besides the headline: the other drivers and variants, per-kernel timings and "
+                       "roofline, verification, live traffic passes, growth, the secondary workloads and the CPU baseline")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="after the timed steps, write the rows the timed driver's last step returned to DIR/rows.npy (float32)")
   args = ap.parse_args()
+  if args.dump_outputs and (args.config or "m1b") not in ("m1b", "c3"):
+    ap.error("--dump-outputs: the timed path of --config %s keeps no outputs (m1b and c3 do)" % args.config)
+  if args.dump_outputs and args.gpus > 1:
+    ap.error("--dump-outputs: one GPU only")
 
   if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
     # `python bench.py --gpus N` without a launcher: become one — re-run this command line under torch.distributed.run, one process per
@@ -1941,7 +2031,7 @@ def main():
     env.setdefault("OMP_NUM_THREADS", "8")
     sys.exit(subprocess.call(cmd, env=env))
 
-  if args.config is None and args.gpus == 1 and "WORLD_SIZE" not in os.environ and os.environ.get("TFRA_BENCH_FORCE_A2A") != "1":
+  if args.full and args.config is None and args.gpus == 1 and "WORLD_SIZE" not in os.environ and os.environ.get("TFRA_BENCH_FORCE_A2A") != "1":
     args._live_traffic = live_traffic(args)   # (before this process allocates anything on the GPU)
 
   import torch
@@ -1974,10 +2064,10 @@ def main():
     res.update({"higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic"})
   elif cfg in ("c3", "m1b"):
     assert world == 1, "%s is a single-GPU configuration" % cfg
-    if args.config is None and not args.no_secondary:
+    if args.full and args.config is None and not args.no_secondary:
       args._growth = measure_growth(torch, de, dev, 128, torch.float16, args.slots // 4)   # reported under secondary.c3
-    res = run_bounded(args, torch, de, dev, cfg)
-    if not args.no_secondary and args.config is None:
+    res = run_bounded(args, torch, de, dev, cfg, dump=args.dump_outputs)
+    if args.full and not args.no_secondary and args.config is None:
       keep = ("metric", "value", "value_overlapped_step", "value_overlapped_step_4_steps_per_host_call", "value_look_ahead_driver", "driver", "driver_rule", "value_op_surface_fused_ops", "value_op_surface_host_read_first", "value_plain_call", "value_op_surface", "value_op_surface_find_first", "value_accum",
               "value_op_surface_table_ops_only", "ms_per_step",
               "ms_per_step_plain_call", "ms_per_step_op_surface", "config", "roofline")
@@ -2027,7 +2117,7 @@ def main():
   else:
     res = run_sharded(args, torch, dist, de, dev, world, rank, "c4")
   if rank == 0:
-    if not args.no_cpu_baseline and world == 1:   # (the CPU leg belongs to the one-GPU line: at N > 1 the other ranks would sit in the final barrier for its 45 s)
+    if args.full and not args.no_cpu_baseline and world == 1:   # (the CPU leg belongs to the one-GPU line: at N > 1 the other ranks would sit in the final barrier for its 45 s)
       res["cpu_baseline"] = cpu_baseline(args.batch)
     emit(res)
   if dist.is_initialized():

@@ -10,7 +10,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp TFRA_BENCH_SKIP_ROUTED_LOCAL=1   # (m1b's trace holds the headline's step launches only; m1s = the routed step at one rank, its own workload)
 for WS in $WORKLOADS; do
   W=${WS%%:*}; SET=${WS##*:}
-  ARGS="--config $W --no-secondary --no-cpu-baseline"
+  ARGS="--config $W --full --no-secondary --no-cpu-baseline"
   timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${W}_trace -o $TAG -- python /root/repo/bench.py $ARGS --steps 40 --warmup 10 > $OUT/${W}_bench_trace.log 2>&1
   CS=("FETCH_SIZE" "WRITE_SIZE")
   if [ "$SET" = "full" ]; then CS+=("TCC_HIT_sum TCC_MISS_sum" "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM"); fi

@@ -21,7 +21,7 @@ KERNELS = ["find_kernel", "upsert_own_kernel", "upsert_rest_kernel", "setplan_ke
            "plan_dest_keys_kernel", "part_scatter_kernel", "accum_kernel", "step_k", "routeplan_insert_kernel", "routeplan_emit_kernel",
            "gather_rows16_kernel", "move_rows_kernel"]
 WORKLOADS = ("m1b", "m1s", "c3", "c2", "c4")
-COMMANDS = {w: "python bench.py --config %s --no-secondary --no-cpu-baseline" % w for w in WORKLOADS}
+COMMANDS = {w: "python bench.py --config %s --full --no-secondary --no-cpu-baseline" % w for w in WORKLOADS}
 SRC_NAMES = {"0": "plan", "1": "direct", "2": "set"}   # upsert_own_kernel<G, SIMPLE, SRC> / upsert_rest_kernel<G, SRC>: where the keys come from
 
 

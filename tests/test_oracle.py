@@ -4,9 +4,16 @@ import numpy as np
 import pytest
 
 import oracle
-from tests import kats
+from tests import kats, ref_engine
 
 KINDS = ["port"] + (["reference"] if oracle.available("reference") or True else [])
+
+
+@pytest.fixture(autouse=True)
+def _reference_engine(request):
+  """kind="reference": the engine built from the reference tree, or where that tree is absent its recorded answers (tests/ref_engine.py)"""
+  with ref_engine.installed(request.node.name):
+    yield
 
 
 def factory(kind):
