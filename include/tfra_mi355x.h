@@ -273,6 +273,17 @@ int tfra_table_apply_planned(tfra_table_t* t, const tfra_opt_params* p, const tf
                              const float* grads, const float* param_default_row, tfra_stream_t stream);
 int tfra_table_upsert_planned(tfra_table_t* t, const tfra_sparse_plan_t* plan, const void* values,
                               const uint64_t* scores, tfra_stream_t stream);
+/* The write-back of an embedding_lookup_sparse (gradient with respect to its combined output): the contract of
+ * tfra_table_apply_planned, with `plan` built over the ENTRY ids (the sparse input's values, repeats included) and the
+ * gradient of plan position e = the combiner's backward of entry e, formed from grad_out[n_rows, dim] in registers
+ * (never written out): g_e = (grad_out[seg[e]] / den) * w_e, den = 1 (sum) | sum of the row's weights (mean) |
+ * sqrt(sum of their squares) (sqrtn), 0 when that sum is 0 (see tfra_sparse_segment_combine_backprop).  seg[nnz]
+ * ascending, weights[nnz] or NULL (=> 1), combiner 0 sum, 1 mean, 2 sqrtn.  Bit-identical to
+ * tfra_table_apply_sparse(ids, tfra_sparse_segment_combine_backprop(grad_out, ...)).  float32 tables, dim % 4 == 0,
+ * dim <= 256, grad_out / default row 16-B aligned. */
+int tfra_table_apply_planned_combined(tfra_table_t* t, const tfra_opt_params* p, const tfra_sparse_plan_t* plan,
+                                      const float* grad_out, const int64_t* seg, const float* weights, int combiner,
+                                      size_t n_rows, const float* param_default_row, tfra_stream_t stream);
 /* Introspection (tests, tools): counts[6] = {keys with > 8 occurrences, other keys, partial sums, 512-entry bins,
  * entries of the other keys, build errors}; when keys != NULL also the CSR itself, keys with > 8 occurrences first:
  * keys[i], cnt[i], and positions[] = the batch positions of key 0, of key 1, ... each ascending (cap = length of
@@ -485,6 +496,14 @@ int tfra_gather_rows(size_t n, size_t row_bytes, const void* rows, const int32_t
 int tfra_sparse_segment_combine(tfra_workspace_t* ws, size_t nnz, int dim, const float* rows,
                                 const int32_t* idx, const int64_t* seg, const float* weights, int combiner,
                                 size_t n_rows, float* out, tfra_stream_t stream);
+/* Its backward (TF's SparseSegment{Sum,Mean,SqrtN}Grad together with the weights multiply, PY/dynamic_embedding_ops.py:
+ * 218-291): entry_grads_out[e,:] = (grad_out[seg[e],:] / den) * w[e] in fp32, in that order, den = 1 (sum) |
+ * sum_{seg==r} w (mean) | sqrt(sum_{seg==r} w^2) (sqrtn); a row whose weight sum is 0 gives 0 (as the forward), an
+ * entry whose row lies outside [0, n_rows) gives 0.  seg ascending, weights NULL => 1, n_rows >= 1 when nnz > 0.
+ * Chained with tfra_segment_sum(idx) it is the gradient of the lookup's unique rows. */
+int tfra_sparse_segment_combine_backprop(tfra_workspace_t* ws, size_t nnz, int dim, const float* grad_out,
+                                         const int64_t* seg, const float* weights, int combiner, size_t n_rows,
+                                         float* entry_grads_out, tfra_stream_t stream);
 
 /* default_partition_fn (PY/dynamic_embedding_variable.py:165-197) + dynamic_partition in one
  * pass: owner[i] = mode 0: (key & 0x7fffffff) % num_shards (CUDA-build branch)

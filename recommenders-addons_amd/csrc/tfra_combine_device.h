@@ -1,0 +1,51 @@
+// The backward of the sparse segment combiner of embedding_lookup_sparse (PY/dynamic_embedding_ops.py:218-291: gather,
+// *= weights, segment_sum, then / sum w (mean) or / sqrt(sum w^2) (sqrtn)).  For entry e of row r = seg[e] with weight w_e
+// (1 without weights) and incoming gradient G[r,:]:
+//   g_e = (G[r] / den_r) * w_e,   den_r = 1 (sum) | sum_{seg = r} w (mean) | sqrt(sum_{seg = r} w^2) (sqrtn)
+// in fp32 and in TF's order: the divide's gradient first, then the multiply's (G / 1 == G exactly, so sum needs no branch).
+// A row whose weight sum is 0 gives g_e = 0, the forward's convention (seg_combine_kernel, tfra_frontend.hip).
+//
+// Every kernel that forms g_e — tfra_sparse_segment_combine_backprop (written out) and the combined write-back of
+// tfra_table_apply_planned_combined (formed in registers from grad_out, tfra_csr.hip) — reads the same per-entry record and
+// calls comb_grad4, so the two routes agree bit for bit.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "tfra_device.h"
+
+namespace tfra {
+
+// one 16-B load per entry: the grad_out row, its denominator, the entry's weight
+struct CombEnt {
+  unsigned row;
+  float den;
+  float w;
+  unsigned pad;
+};
+
+// kernel argument of the combined write-back: position e of the plan has gradient comb_grad4(grads[ent[e].row], ent[e].den, ent[e].w)
+struct CombRows {
+  const CombEnt* ent;
+};
+
+// den_r over the row's members [b, e) in input order (the same adds as seg_combine_kernel's weight sum)
+__device__ __forceinline__ float comb_den(const float* __restrict__ w, int b, int e, int combiner) {
+  if (combiner == 0) return 1.f;
+  float s = 0.f;
+  for (int p = b; p < e; ++p) { const float x = w ? w[p] : 1.f; s += combiner == 2 ? x * x : x; }
+  return combiner == 2 ? sqrtf(s) : s;
+}
+
+__device__ __forceinline__ float comb_grad(float g, float den, float w) { return den != 0.f ? (g / den) * w : 0.f; }
+
+__device__ __forceinline__ float4 comb_grad4(float4 g, float den, float w) {
+  return make_float4(comb_grad(g.x, den, w), comb_grad(g.y, den, w), comb_grad(g.z, den, w), comb_grad(g.w, den, w));
+}
+
+// The per-entry records of one batch (tfra_frontend.hip): ent[e] = {seg[e], den_{seg[e]}, w_e}; an entry whose row lies outside
+// [0, n_rows) gets {0, 0, w} (gradient 0, as the forward ignores it).  seg ascending; se: scratch of 2 n_rows ints, den: of
+// n_rows floats.  n_rows >= 1.
+int comb_entries(hipStream_t s, size_t nnz, const int64_t* seg, const float* weights, int combiner, size_t n_rows, int* se,
+                 float* den, CombEnt* ent);
+
+}  // namespace tfra

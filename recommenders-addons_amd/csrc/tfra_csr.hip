@@ -59,6 +59,7 @@
 #include <vector>
 
 #include "../../include/tfra_mi355x.h"
+#include "tfra_combine_device.h"
 #include "tfra_device.h"
 #include "tfra_host.h"
 #include "tfra_optim_device.h"
@@ -566,12 +567,22 @@ __global__ __launch_bounds__(NTA) void csr_scatter_kernel(const unsigned* __rest
 // none: the group loads its 16 entry words with one coalesced read, puts all 16 gradient rows in flight at once
 // (unconditional loads, padding clamped to the item's first row), adds them in entry order, and the group holding the
 // run's first item then adds the sums of the run's following items in item order (LDS) and writes the partial row.
-template <int NCH>
+// CS = CombRows (tfra_table_apply_planned_combined): the gradient of position e is formed from grads = grad_out and the entry's
+// record (tfra_combine_device.h) — each lane loads the record of its own entry, the group shares it by shuffles; none: grads[e].
+template <class... CS>
+__device__ __forceinline__ const CombEnt* comb_ent(const CS&... cs) {
+  const CombEnt* p = nullptr;
+  ((p = cs.ent), ...);
+  return p;
+}
+
+template <int NCH, class... CS>
 __global__ __launch_bounds__(NTA) void hot_sums_kernel(const float* __restrict__ grads, int dim,
                                                        const unsigned* __restrict__ hent, const unsigned* __restrict__ hout,
                                                        const unsigned* __restrict__ binmap,
                                                        const unsigned* __restrict__ d_counts, float* __restrict__ partial,
-                                                       unsigned* progress, unsigned progress_val) {
+                                                       unsigned* progress, unsigned progress_val, const CS... cs) {
+  constexpr bool COMB = sizeof...(CS) > 0;
   constexpr int NG = NTA / 16;
   __shared__ float s_sum[NG][64];
   __shared__ unsigned char s_kind[NG + 1];   // 0 = item continues the run of the item before, 1 = first item of a run, 2 = empty item
@@ -591,10 +602,19 @@ __global__ __launch_bounds__(NTA) void hot_sums_kernel(const float* __restrict__
     if (sub == 0) s_kind[g] = empty ? 2 : (first ? 1 : 0);
     if (threadIdx.x == 0) s_kind[NG] = 1;
     unsigned rows[16];   // element offset of each row (< 2^18 * 256)
+    float cden = 0.f, cw = 0.f;   // COMB: denominator and weight of this lane's entry
+    if constexpr (COMB) {
+      const CombEnt ce = comb_ent(cs...)[((e & E_SKIP) ? e0 : e) & E_POS];   // (padding: the item's first row, as below)
+      cden = ce.den;
+      cw = ce.w;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) rows[j] = (unsigned)__shfl((int)ce.row, gshift + j) * (unsigned)dim;
+    } else {
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
       const unsigned ej = (unsigned)__shfl((int)e, gshift + j);
       rows[j] = (((live >> j) & 1u) ? (ej & E_POS) : (e0 & E_POS)) * (unsigned)dim;
+    }
     }
     for (int k = 0; k < NCH; ++k) {
       const int col = k * 64 + sub * 4;
@@ -610,6 +630,10 @@ __global__ __launch_bounds__(NTA) void hot_sums_kernel(const float* __restrict__
 #pragma unroll
         for (int j = 0; j < 8; ++j) x[j] = *reinterpret_cast<const float4*>(grads + rows[h * 8 + j] + cc);
         keep_live(x[0], x[1], x[2], x[3]); keep_live(x[4], x[5], x[6], x[7]);
+        if constexpr (COMB) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) x[j] = comb_grad4(x[j], __shfl(cden, gshift + h * 8 + j), __shfl(cw, gshift + h * 8 + j));
+        }
 #pragma unroll
         for (int j = 0; j < 8; ++j)
           if ((live >> (h * 8 + j)) & 1u) { acc.x += x[j].x; acc.y += x[j].y; acc.z += x[j].z; acc.w += x[j].w; }
@@ -620,6 +644,10 @@ __global__ __launch_bounds__(NTA) void hot_sums_kernel(const float* __restrict__
       for (int j = 0; j < 16; ++j) x[j] = *reinterpret_cast<const float4*>(grads + rows[j] + cc);   // 16 rows in flight
       keep_live(x[0], x[1], x[2], x[3]); keep_live(x[4], x[5], x[6], x[7]);
       keep_live(x[8], x[9], x[10], x[11]); keep_live(x[12], x[13], x[14], x[15]);
+      if constexpr (COMB) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) x[j] = comb_grad4(x[j], __shfl(cden, gshift + j), __shfl(cw, gshift + j));
+      }
 #pragma unroll
       for (int j = 0; j < 16; ++j)
         if ((live >> j) & 1u) { acc.x += x[j].x; acc.y += x[j].y; acc.z += x[j].z; acc.w += x[j].w; }
@@ -721,9 +749,12 @@ __device__ __forceinline__ unsigned load_record(const CsrKeys& ks, unsigned g, i
 // of the group holds word i: EVERY lane of the group must be here); a key with many lists consecutive rows of the partial
 // sums.  The addresses are formed here, from the record word, not kept in an array across the kernel: with 8 pointers and
 // 8 rows held per lane the update kernel needed 145 registers (3 waves per SIMD); this form needs 125 (Adam) / 109 (SGD).
-template <int NB>
+// COMB (combined write-back): lanes 4.. of a key with few occurrences hold grad_out rows instead of batch positions, and the
+// denominator / weight of their entry in cden / cw; each gradient row is scaled by comb_grad4 before it is added.
+template <int NB, bool COMB = false>
 __device__ __forceinline__ void add_rows(float4& acc, const float* __restrict__ grads, const float* __restrict__ partial, bool hot,
-                                         unsigned w, unsigned first, unsigned nsrc, unsigned j0, int dim, int c, int gshift) {
+                                         unsigned w, unsigned first, unsigned nsrc, unsigned j0, int dim, int c, int gshift,
+                                         float cden = 0.f, float cw = 0.f) {
   float4 x[NB];
 #pragma unroll
   for (int j = 0; j < NB; ++j) {
@@ -733,6 +764,13 @@ __device__ __forceinline__ void add_rows(float4& acc, const float* __restrict__ 
     x[j] = *reinterpret_cast<const float4*>(q + c);
   }
   if (NB == 4) keep_live(x[0], x[1], x[2], x[3]);
+  if (COMB && !hot) {
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      const int src = gshift + 4 + (int)min(min(j0 + (unsigned)j, nsrc - 1), 7u);
+      x[j] = comb_grad4(x[j], __shfl(cden, src), __shfl(cw, src));
+    }
+  }
 #pragma unroll
   for (int j = 0; j < NB; ++j)
     if (j0 + (unsigned)j < nsrc) { acc.x += x[j].x; acc.y += x[j].y; acc.z += x[j].z; acc.w += x[j].w; }
@@ -740,16 +778,18 @@ __device__ __forceinline__ void add_rows(float4& acc, const float* __restrict__ 
 
 // the whole sum of a key; wmax = the largest list length (capped at 8) among the wave's four keys: the trip count of the
 // common part is uniform across the wave, the few keys with more than 8 partial rows go on alone
+template <bool COMB = false>
 __device__ __forceinline__ float4 sum_rows(const float* __restrict__ grads, const float* __restrict__ partial, bool hot, unsigned w,
-                                           unsigned first, unsigned nsrc, unsigned wmax, int dim, int c, int gshift) {
+                                           unsigned first, unsigned nsrc, unsigned wmax, int dim, int c, int gshift,
+                                           float cden = 0.f, float cw = 0.f) {
   float4 gg = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (wmax <= 1) add_rows<1>(gg, grads, partial, hot, w, first, nsrc, 0, dim, c, gshift);
-  else if (wmax <= 2) add_rows<2>(gg, grads, partial, hot, w, first, nsrc, 0, dim, c, gshift);
+  if (wmax <= 1) add_rows<1, COMB>(gg, grads, partial, hot, w, first, nsrc, 0, dim, c, gshift, cden, cw);
+  else if (wmax <= 2) add_rows<2, COMB>(gg, grads, partial, hot, w, first, nsrc, 0, dim, c, gshift, cden, cw);
   else {
-    add_rows<4>(gg, grads, partial, hot, w, first, nsrc, 0, dim, c, gshift);
-    if (wmax > 4) add_rows<4>(gg, grads, partial, hot, w, first, nsrc, 4, dim, c, gshift);
+    add_rows<4, COMB>(gg, grads, partial, hot, w, first, nsrc, 0, dim, c, gshift, cden, cw);
+    if (wmax > 4) add_rows<4, COMB>(gg, grads, partial, hot, w, first, nsrc, 4, dim, c, gshift, cden, cw);
   }
-  for (unsigned j0 = 8; j0 < nsrc; j0 += 4) add_rows<4>(gg, grads, partial, hot, w, first, nsrc, j0, dim, c, gshift);
+  for (unsigned j0 = 8; j0 < nsrc; j0 += 4) add_rows<4, COMB>(gg, grads, partial, hot, w, first, nsrc, j0, dim, c, gshift, cden, cw);
   return gg;
 }
 
@@ -764,12 +804,14 @@ __device__ __forceinline__ float4 sum_rows(const float* __restrict__ grads, cons
 // Without the pointer arrays — add_rows — it is 125 registers, 4 waves per SIMD, no spills: 28.7 us, step 57.2 instead of 59.9 us.
 // Round 4: amdgpu_waves_per_eu(5, 5) on that form — 96 registers, 18 spilled for Adam: gradient half 28.7 -> 37.3 us, the step of
 // configs[1] 55.4 -> 62.3 us (A/B on one box, twice).  Five waves need a kernel that NEEDS 96 registers, not one that spills to them.)
-template <int KIND, bool PHASE2>
+// CS = CombRows: the combined write-back (see hot_sums_kernel).
+template <int KIND, bool PHASE2, class... CS>
 __global__ __launch_bounds__(256) void apply_csr_kernel(TableView v, OptP o, int dim, const float* __restrict__ grads,
                                                         const float* __restrict__ partial, CsrKeys ks,
                                                         const float* __restrict__ default_row, float aux0, float aux1,
                                                         ScoreP sp, uint8_t* __restrict__ dflag, unsigned* any_deferred,
-                                                        unsigned use_gen) {
+                                                        unsigned use_gen, const CS... cs) {
+  constexpr bool COMB = sizeof...(CS) > 0;
   if (PHASE2 && *any_deferred != use_gen) return;   // phase 1 of this use deferred nothing
   constexpr int S = NSlots<KIND>::v;
   const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
@@ -796,6 +838,15 @@ __global__ __launch_bounds__(256) void apply_csr_kernel(TableView v, OptP o, int
     const unsigned cnt = (unsigned)__shfl((int)w, gshift + 2);
     const unsigned first = (unsigned)__shfl((int)w, gshift + 3);             // keys with many occurrences: first partial row
     const unsigned nsrc = hot ? (unsigned)__shfl((int)w, gshift + 4) : cnt;
+    // COMB: lane 4 + j of a key with few occurrences swaps batch position j for that entry's grad_out row (+ denominator, weight)
+    unsigned wsrc = w;
+    float cden = 0.f, cw = 0.f;
+    if constexpr (COMB) {
+      if (!hot && sub >= 4 && (unsigned)(sub - 4) < cnt) {
+        const CombEnt ce = comb_ent(cs...)[w];
+        wsrc = ce.row; cden = ce.den; cw = ce.w;
+      }
+    }
     // wave-uniform batch width: 1 / 2 / 4 rows in flight (most keys of a Zipf batch occur once)
     unsigned wmax = min(nsrc, 8u);
     for (int o2 = 32; o2 >= 16; o2 >>= 1) wmax = max(wmax, (unsigned)__shfl_xor((int)wmax, o2));
@@ -831,7 +882,7 @@ __global__ __launch_bounds__(256) void apply_csr_kernel(TableView v, OptP o, int
       float4 p = *reinterpret_cast<const float4*>((is_new ? default_row : pr) + c);
       float4 s1 = *reinterpret_cast<const float4*>(pr + (S >= 1 ? dim : 0) + c);
       float4 s2 = *reinterpret_cast<const float4*>(pr + (S >= 2 ? 2 * dim : 0) + c);
-      float4 gg = sum_rows(grads, partial, hot, w, first, nsrc, wmax, dim, c, gshift);
+      float4 gg = sum_rows<COMB>(grads, partial, hot, COMB ? wsrc : w, first, nsrc, wmax, dim, c, gshift, cden, cw);
       float4 dummy = p;
       keep_live(dummy, p, s1, s2);
       if (is_new || S < 1) s1 = make_float4(aux0, aux0, aux0, aux0);
@@ -2199,9 +2250,9 @@ static CsrKeys keys_of(const tfra_sparse_plan* pl) {
   return CsrKeys{pl->keymap, pl->dkeys, pl->out.crec, pl->out.hrec, pl->out.hent, pl->d_counts, nullptr, nullptr, nullptr};
 }
 
-template <int KIND>
+template <int KIND, class... CS>
 static void launch_apply_csr(Table* t, hipStream_t s, const tfra_sparse_plan* pl, const OptP& o, const float* grads,
-                             const float* default_row, unsigned key_blocks, const ScoreP& sp) {
+                             const float* default_row, unsigned key_blocks, const ScoreP& sp, const CS&... cs) {
   TableView v = t->view_of(t->cur);
   const float a0 = t->opts.aux_init[0], a1 = t->opts.aux_init[1];
   const unsigned gen = ++pl->use_gen;
@@ -2210,14 +2261,39 @@ static void launch_apply_csr(Table* t, hipStream_t s, const tfra_sparse_plan* pl
   static const unsigned grid_cap = [] { const char* e = getenv("TFRA_APPLY_GRID_CAP"); return e ? (unsigned)atoi(e) : 1024u; }();
   if (grid_cap) key_blocks = std::min(key_blocks, grid_cap);
   apply_csr_kernel<KIND, false><<<key_blocks, 256, 0, s>>>(v, o, pl->dim, grads, pl->partial, keys_of(pl), default_row, a0, a1, sp,
-                                                           pl->dflag, pl->any_deferred, gen);
+                                                           pl->dflag, pl->any_deferred, gen, cs...);
   if (sp.bounded)
     apply_csr_kernel<KIND, true><<<key_blocks, 256, 0, s>>>(v, o, pl->dim, grads, pl->partial, keys_of(pl), default_row, a0, a1, sp,
-                                                            pl->dflag, pl->any_deferred, gen);
+                                                            pl->dflag, pl->any_deferred, gen, cs...);
 }
 
+template <class... CS>
+static void launch_hot_sums(hipStream_t s, const tfra_sparse_plan* pl, const float* grads, unsigned bin_blocks, unsigned* progress,
+                            unsigned progress_val, const CS&... cs) {
+  const int dim = pl->dim;
+  switch ((dim + 63) / 64) {
+    case 1: hot_sums_kernel<1><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, progress, progress_val, cs...); break;
+    case 2: hot_sums_kernel<2><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, progress, progress_val, cs...); break;
+    case 3: hot_sums_kernel<3><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, progress, progress_val, cs...); break;
+    default: hot_sums_kernel<4><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, progress, progress_val, cs...); break;
+  }
+}
+
+template <class... CS>
+static void launch_apply(Table* t, hipStream_t s, const tfra_sparse_plan* pl, int kind, const OptP& o, const float* grads,
+                         const float* default_row, unsigned key_blocks, const ScoreP& sp, const CS&... cs) {
+  switch (kind) {
+    case TFRA_OPT_SGD: launch_apply_csr<TFRA_OPT_SGD>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
+    case TFRA_OPT_ADAM: launch_apply_csr<TFRA_OPT_ADAM>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
+    case TFRA_OPT_ADAGRAD: launch_apply_csr<TFRA_OPT_ADAGRAD>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
+    default: launch_apply_csr<TFRA_OPT_FTRL>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
+  }
+}
+
+// comb != nullptr (tfra_table_apply_planned_combined): grads is grad_out, position e's gradient is formed from comb[e]
 static int apply_planned_impl(tfra_table_t* tp, const tfra_opt_params* p, const tfra_sparse_plan_t* pl, const float* grads,
-                              const float* param_default_row, tfra_stream_t stream, unsigned* progress, unsigned progress_val) {
+                              const float* param_default_row, tfra_stream_t stream, unsigned* progress, unsigned progress_val,
+                              const CombEnt* comb = nullptr) {
   // caller holds t->mu
   Table* t = reinterpret_cast<Table*>(tp);
   if (!t || !p || !pl) return set_error(TFRA_ERR_INVALID, "apply_planned: null argument");
@@ -2236,27 +2312,17 @@ static int apply_planned_impl(tfra_table_t* tp, const tfra_opt_params* p, const 
     return set_error(TFRA_ERR_UNSUPPORTED, "apply_planned: gradient / default buffers must be 16-B aligned");
   rc = t->prepare_insert(pl->n, s);
   if (rc) return rc;
-  const int dim = pl->dim;
   unsigned key_blocks, bin_blocks;
   plan_grids(pl, &key_blocks, &bin_blocks);
-  const int nch = (dim + 63) / 64;
-  switch (nch) {
-    case 1: hot_sums_kernel<1><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, progress, progress_val); break;
-    case 2: hot_sums_kernel<2><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, progress, progress_val); break;
-    case 3: hot_sums_kernel<3><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, progress, progress_val); break;
-    default: hot_sums_kernel<4><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, progress, progress_val); break;
-  }
+  if (comb) launch_hot_sums(s, pl, grads, bin_blocks, progress, progress_val, CombRows{comb});
+  else launch_hot_sums(s, pl, grads, bin_blocks, progress, progress_val);
   uint8_t* bounded_now;
   rc = t->bounded_flags(1, s, &bounded_now);
   if (rc) return rc;
   const ScoreP sp{t->opts.strategy, t->global_epoch, bounded_now ? (t->dense ? 2 : 1) : 0};
   OptP o{p->kind, p->lr, p->beta1, p->beta2, p->eps, p->l1, p->l2, p->lr_power, p->d_lr};
-  switch (p->kind) {
-    case TFRA_OPT_SGD: launch_apply_csr<TFRA_OPT_SGD>(t, s, pl, o, grads, param_default_row, key_blocks, sp); break;
-    case TFRA_OPT_ADAM: launch_apply_csr<TFRA_OPT_ADAM>(t, s, pl, o, grads, param_default_row, key_blocks, sp); break;
-    case TFRA_OPT_ADAGRAD: launch_apply_csr<TFRA_OPT_ADAGRAD>(t, s, pl, o, grads, param_default_row, key_blocks, sp); break;
-    default: launch_apply_csr<TFRA_OPT_FTRL>(t, s, pl, o, grads, param_default_row, key_blocks, sp); break;
-  }
+  if (comb) launch_apply(t, s, pl, p->kind, o, grads, param_default_row, key_blocks, sp, CombRows{comb});
+  else launch_apply(t, s, pl, p->kind, o, grads, param_default_row, key_blocks, sp);
   if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "apply_planned: launch failed");
   step_epoch_public(t);
   return TFRA_OK;
@@ -2268,6 +2334,45 @@ extern "C" int tfra_table_apply_planned(tfra_table_t* tp, const tfra_opt_params*
   if (!t) return set_error(TFRA_ERR_INVALID, "apply_planned: null table");
   std::lock_guard<std::mutex> lock(t->mu);
   return apply_planned_impl(tp, p, pl, grads, param_default_row, stream, nullptr, 0);
+}
+
+// The write-back of an embedding_lookup_sparse: plan over the entry ids, gradient of position e = the combiner's backward
+// (tfra_combine_device.h) formed from grad_out in registers — apply_planned's kernels, reading grad_out through one more
+// indirection instead of an expanded [nnz, dim] gradient.
+extern "C" int tfra_table_apply_planned_combined(tfra_table_t* tp, const tfra_opt_params* p, const tfra_sparse_plan_t* pl,
+                                                 const float* grad_out, const int64_t* seg, const float* weights, int combiner,
+                                                 size_t n_rows, const float* param_default_row, tfra_stream_t stream) {
+  Table* t = reinterpret_cast<Table*>(tp);
+  if (!t || !p || !pl) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: null argument");
+  if (combiner < 0 || combiner > 2) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: combiner must be 0 (sum), 1 (mean) or 2 (sqrtn)");
+  std::lock_guard<std::mutex> lock(t->mu);
+  hipStream_t s = (hipStream_t)stream;
+  int rc = t->enter(s);   // the scratch below was last used on the table's previous stream
+  if (rc) return rc;
+  if (pl->kind != 0 || pl->dim != t->opts.dim) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: the plan was built for another dim");
+  if (t->opts.device != pl->device && t->opts.device >= 0) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: plan and table live on different devices");
+  const size_t nnz = pl->n;
+  if (nnz == 0) return TFRA_OK;
+  if (!grad_out || !seg || !param_default_row) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: null buffer");
+  if (n_rows == 0 || n_rows >= (1ULL << 30)) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: need 1 <= n_rows < 2^30");
+  if ((((uintptr_t)grad_out | (uintptr_t)param_default_row) & 15) || ((uintptr_t)seg & 7) || ((uintptr_t)weights & 3))
+    return set_error(TFRA_ERR_UNSUPPORTED, "apply_planned_combined: grad_out / default buffers must be 16-B aligned");
+  if (!t->comb_ws) {
+    tfra_workspace_t* w = nullptr;
+    rc = tfra_workspace_create(t->device, &w);
+    if (rc) return rc;
+    t->comb_ws = w;
+  }
+  tfra_workspace_t* ws = reinterpret_cast<tfra_workspace_t*>(t->comb_ws);
+  auto al = [](size_t x) { return (x + 255) / 256 * 256; };
+  const size_t se_b = al(2 * n_rows * sizeof(int)), den_b = al(n_rows * sizeof(float));
+  rc = ws->ensure(se_b + den_b + al(nnz * sizeof(CombEnt)), s);
+  if (rc) return rc;
+  unsigned char* b = (unsigned char*)ws->buf;
+  CombEnt* ent = reinterpret_cast<CombEnt*>(b + se_b + den_b);
+  rc = comb_entries(s, nnz, seg, weights, combiner, n_rows, reinterpret_cast<int*>(b), reinterpret_cast<float*>(b + se_b), ent);
+  if (rc) return rc;
+  return apply_planned_impl(tp, p, pl, grad_out, param_default_row, stream, nullptr, 0, ent);
 }
 
 // ---- launch of the ownership write-back (plan keys or a caller's unique keys) --------------------------------
@@ -2578,6 +2683,7 @@ static int own_plan(Table* t, tfra_sparse_plan** out) {
 namespace tfra {
 void destroy_own_plan(Table* t) {
   if (t->big_ws) { tfra_workspace_destroy(reinterpret_cast<tfra_workspace_t*>(t->big_ws)); t->big_ws = nullptr; }
+  if (t->comb_ws) { tfra_workspace_destroy(reinterpret_cast<tfra_workspace_t*>(t->comb_ws)); t->comb_ws = nullptr; }
   if (t->own_plan) { tfra_sparse_plan_destroy(reinterpret_cast<tfra_sparse_plan*>(t->own_plan)); t->own_plan = nullptr; }
 }
 }  // namespace tfra

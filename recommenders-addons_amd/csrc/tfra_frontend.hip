@@ -15,6 +15,7 @@
 #include <string>
 
 #include "../../include/tfra_mi355x.h"
+#include "tfra_combine_device.h"
 #include "tfra_device.h"
 #include "tfra_host.h"
 
@@ -529,6 +530,40 @@ __global__ __launch_bounds__(256) void seg_combine_kernel(size_t n_rows, int dim
   }
 }
 
+// ------------------------------------ combiner backward (tfra_combine_device.h) -----------------
+__global__ void comb_den_kernel(size_t n_rows, const int* __restrict__ start_end, const float* __restrict__ w, int combiner,
+                                float* __restrict__ den) {
+  const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < n_rows) den[r] = comb_den(w, start_end[r], start_end[n_rows + r], combiner);
+}
+
+__global__ void comb_ent_kernel(size_t nnz, const i64* __restrict__ seg, const float* __restrict__ w, const float* __restrict__ den,
+                                size_t n_rows, CombEnt* __restrict__ ent) {
+  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= nnz) return;
+  const i64 s = seg[p];
+  const bool ok = s >= 0 && (size_t)s < n_rows;
+  ent[p] = CombEnt{ok ? (unsigned)s : 0u, ok ? den[s] : 0.f, w ? w[p] : 1.f, 0u};
+}
+
+// entry_grads[e, :] = comb_grad(grad_out[row_e, :], den_e, w_e); VEC4: one float4 per thread
+template <bool VEC4>
+__global__ __launch_bounds__(256) void comb_backprop_kernel(size_t nnz, int dim, const float* __restrict__ g,
+                                                            const CombEnt* __restrict__ ent, float* __restrict__ out) {
+  const size_t per = VEC4 ? (size_t)(dim / 4) : (size_t)dim;
+  const size_t total = nnz * per;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t e = i / per, c = i - e * per;
+    const CombEnt ce = ent[e];
+    if (VEC4) {
+      const float4 x = *reinterpret_cast<const float4*>(g + (size_t)ce.row * dim + c * 4);
+      *reinterpret_cast<float4*>(out + e * dim + c * 4) = comb_grad4(x, ce.den, ce.w);
+    } else {
+      out[e * dim + c] = comb_grad(g[(size_t)ce.row * dim + c], ce.den, ce.w);
+    }
+  }
+}
+
 // ------------------------------------ partition ------------------------------------------------
 __device__ __forceinline__ int owner_of(i64 key, int num, int mode) {
   if (mode == 0) return (int)(key & 0x7fffffff) % num;
@@ -817,6 +852,36 @@ int tfra_sparse_segment_combine(tfra_workspace_t* ws, size_t nnz, int dim, const
   return TFRA_OK;
 }
 
+int tfra_sparse_segment_combine_backprop(tfra_workspace_t* ws, size_t nnz, int dim, const float* grad_out, const int64_t* seg,
+                                         const float* weights, int combiner, size_t n_rows, float* entry_grads_out,
+                                         tfra_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!ws || dim <= 0 || combiner < 0 || combiner > 2) return set_error(TFRA_ERR_INVALID, "segment_combine_backprop: bad argument");
+  { int cur_ = -1; if (hipGetDevice(&cur_) != hipSuccess || cur_ != ws->device) HIP_TRY(hipSetDevice(ws->device)); }
+  if (nnz == 0) return TFRA_OK;
+  if (!grad_out || !seg || !entry_grads_out) return set_error(TFRA_ERR_INVALID, "segment_combine_backprop: null buffer");
+  if (n_rows == 0) return set_error(TFRA_ERR_INVALID, "segment_combine_backprop: entries but no rows");
+  if (nnz >= (1ULL << 31) || n_rows >= (1ULL << 30)) return set_error(TFRA_ERR_INVALID, "segment_combine_backprop: too large");
+  if (((uintptr_t)seg & 7) || ((uintptr_t)weights & 3) || (((uintptr_t)grad_out | (uintptr_t)entry_grads_out) & 3))
+    return set_error(TFRA_ERR_UNSUPPORTED, "segment_combine_backprop: misaligned buffer");
+  const size_t se_b = align_up(2 * n_rows * sizeof(int)), den_b = align_up(n_rows * sizeof(float));
+  int rc = ws->ensure(se_b + den_b + align_up(nnz * sizeof(CombEnt)), s);
+  if (rc) return rc;
+  Carver c{(unsigned char*)ws->buf};
+  int* se = c.take<int>(2 * n_rows);
+  float* den = c.take<float>(n_rows);
+  CombEnt* ent = c.take<CombEnt>(nnz);
+  rc = comb_entries(s, nnz, seg, weights, combiner, n_rows, se, den, ent);
+  if (rc) return rc;
+  const bool vec4 = dim % 4 == 0 && (((uintptr_t)grad_out | (uintptr_t)entry_grads_out) & 15) == 0;
+  const size_t work = nnz * (size_t)(vec4 ? dim / 4 : dim);
+  const unsigned grid = (unsigned)std::min<size_t>((work + 255) / 256, 8192);
+  if (vec4) comb_backprop_kernel<true><<<grid, 256, 0, s>>>(nnz, dim, grad_out, ent, entry_grads_out);
+  else comb_backprop_kernel<false><<<grid, 256, 0, s>>>(nnz, dim, grad_out, ent, entry_grads_out);
+  HIP_TRY(hipGetLastError());
+  return TFRA_OK;
+}
+
 int tfra_partition(tfra_workspace_t* ws, size_t n, const int64_t* d_n, const int64_t* keys, int num_shards, int mode,
                    int64_t* keys_out, int32_t* perm_out, int64_t* d_counts, tfra_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
@@ -890,3 +955,15 @@ int tfra_select_lowest(tfra_workspace_t* ws, size_t n, const int64_t* keys, cons
 }
 
 }  // extern "C"
+
+namespace tfra {
+int comb_entries(hipStream_t s, size_t nnz, const int64_t* seg, const float* weights, int combiner, size_t n_rows, int* se,
+                 float* den, CombEnt* ent) {
+  HIP_TRY(hipMemsetAsync(se, 0, 2 * n_rows * sizeof(int), s));  // empty rows: start = end = 0
+  seg64_bounds_kernel<<<(unsigned)((nnz + 255) / 256), 256, 0, s>>>(nnz, (const i64*)seg, se, n_rows);
+  comb_den_kernel<<<(unsigned)((n_rows + 255) / 256), 256, 0, s>>>(n_rows, se, weights, combiner, den);
+  comb_ent_kernel<<<(unsigned)((nnz + 255) / 256), 256, 0, s>>>(nnz, (const i64*)seg, weights, den, n_rows, ent);
+  HIP_TRY(hipGetLastError());
+  return TFRA_OK;
+}
+}  // namespace tfra

@@ -128,6 +128,7 @@ _SIGS = {
     "tfra_sparse_plan_destroy": [_P],
     "tfra_sparse_plan_build": [_P, _SZ, _P, _I, _P],
     "tfra_table_apply_planned": [_P, ctypes.POINTER(OptParams), _P, _P, _P, _P],
+    "tfra_table_apply_planned_combined": [_P, ctypes.POINTER(OptParams), _P, _P, _P, _P, _I, _SZ, _P, _P],
     "tfra_table_step_prefetch": [_P, ctypes.POINTER(OptParams), _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P],
     "tfra_table_step_prefetch_assign": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P],
     "tfra_step_driver_create": [_P, ctypes.POINTER(_P)],
@@ -153,6 +154,7 @@ _SIGS = {
     "tfra_keys_widen_i32": [_SZ, _P, _P, _P],
     "tfra_keys_narrow_i32": [_SZ, _P, _P, _P, _P],
     "tfra_sparse_segment_combine": [_P, _SZ, _I, _P, _P, _P, _P, _I, _SZ, _P, _P],
+    "tfra_sparse_segment_combine_backprop": [_P, _SZ, _I, _P, _P, _P, _I, _SZ, _P, _P],
     "tfra_partition": [_P, _SZ, _P, _P, _I, _I, _P, _P, _P, _P],
     "tfra_partition_by_owner": [_P, _SZ, _P, _I, _P, _P, _P],
     "tfra_scatter_rows": [_SZ, _SZ, _P, _P, _P, _P],

@@ -8,7 +8,7 @@ from .restrict_policies import FrequencyRestrictPolicy, RestrictPolicy, Timestam
 from .table_ops import (SparsePlan, CuckooHashTable, HkvEvictStrategy, HkvHashTable, KHkvHashTableInitCapacity,
                         KHkvHashTableMaxCapacity, KHkvHashTableMaxHbmForValuesByBytes)
 from .variable import (CuckooHashTableConfig, CuckooHashTableCreator, HkvHashTableConfig, HkvHashTableCreator,
-                       KVCreator, TrainableWrapper, Variable, default_partition_fn, embedding_lookup,
+                       KVCreator, SparseTrainableWrapper, TrainableWrapper, Variable, default_partition_fn, embedding_lookup,
                        embedding_lookup_sparse, embedding_lookup_unique, get_variable,
                        safe_embedding_lookup_sparse)
 

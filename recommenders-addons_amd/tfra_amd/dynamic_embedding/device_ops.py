@@ -221,3 +221,26 @@ def sparse_segment_combine(rows, idx, seg, weights, combiner, n_rows):
   _capi.call("tfra_sparse_segment_combine", _workspace(rows.device), idx.numel(), dim, _ptr(rows), _ptr(idx), _ptr(seg),
              _ptr(w), COMBINERS[combiner], n_rows, _ptr(out), _stream(rows.device))
   return out
+
+
+def sparse_segment_combine_backprop(grad_out, seg, weights, combiner):
+  """The backward of `sparse_segment_combine` (TF's SparseSegment{Sum,Mean,SqrtN}Grad with the weights multiply):
+  entry_grads[e] = (grad_out[seg[e]] / den) * weights[e], den = 1 (sum) | the row's weight sum (mean) | sqrt of the sum of
+  its squared weights (sqrtn), 0 for a row whose weight sum is 0.  grad_out [n_rows, dim] float32, seg [nnz] ascending.
+  Returns [nnz, dim]."""
+  seg = seg.to(torch.int64).contiguous().reshape(-1)
+  dev = seg.device
+  grad_out = grad_out.to(dev, torch.float32).contiguous()
+  if grad_out.dim() != 2:
+    raise ValueError("grad_out must be [n_rows, dim], got %s" % (list(grad_out.shape),))
+  n_rows, dim = grad_out.shape
+  nnz = seg.numel()
+  if weights is not None and torch.as_tensor(weights).numel() != nnz:
+    raise ValueError("weights must have one element per entry")
+  if nnz and n_rows == 0:
+    raise ValueError("entries but no rows")
+  w = None if weights is None else torch.as_tensor(weights, device=dev).to(torch.float32).contiguous().reshape(-1)
+  out = torch.empty((nnz, dim), dtype=torch.float32, device=dev)
+  _capi.call("tfra_sparse_segment_combine_backprop", _workspace(dev), nnz, dim, _ptr(grad_out), _ptr(seg), _ptr(w),
+             COMBINERS[combiner], n_rows, _ptr(out), _stream(dev))
+  return out

@@ -19,7 +19,7 @@ import torch
 
 from .. import _capi
 from . import device_ops
-from .variable import TrainableWrapper, Variable
+from .variable import SparseTrainableWrapper, TrainableWrapper, Variable
 
 
 class _Opt:
@@ -258,6 +258,53 @@ class DynamicEmbeddingOptimizer:
         if plan is not None:
           from .variable import _release_plan
           _release_plan(tw.params, plan)
+
+  def apply_combined_gradients(self, grads_and_vars, name=None):
+    """grads_and_vars: iterable of (grad_out, SparseTrainableWrapper) — grad_out is the gradient of the RESULT of
+    embedding_lookup_sparse / safe_embedding_lookup_sparse (its shape, leading dims included); one global step for all
+    pairs.  One shard, float32 rows, a fused rule and a plannable batch: the write-back forms every entry's gradient from
+    grad_out inside its kernels (tfra_table_apply_planned_combined, with the plan built at lookup time when there is one);
+    otherwise the entry gradients are written out (device_ops.sparse_segment_combine_backprop) and go through apply_sparse."""
+    pairs = []
+    for grad_out, tw in grads_and_vars:
+      if not isinstance(tw, SparseTrainableWrapper):
+        raise TypeError("apply_combined_gradients expects the SparseTrainableWrapper returned by embedding_lookup_sparse / "
+                        "safe_embedding_lookup_sparse(..., return_trainable=True); use apply_gradients for embedding_lookup")
+      if tw.max_norm is not None:
+        raise ValueError("apply_combined_gradients: lookups with max_norm are not supported (the gradient through the clip "
+                         "by norm is not implemented)")
+      pairs.append((tw.check_grad_out(grad_out), tw))
+    p = self.begin_step()
+    for g, tw in pairs:
+      var = tw.params
+      self._check(var)
+      n = tw.entry_ids.numel()
+      plan = tw.take_entry_plan()
+      fused = (self.opt.kind is not None and not self.exact_order and not var.bp_v2 and n > 0 and self.can_plan(var, n))
+      if not fused:
+        if plan is not None:
+          from .variable import _release_plan
+          _release_plan(var, plan)
+        eg = device_ops.sparse_segment_combine_backprop(g, tw.seg, tw.weights, tw.combiner)
+        self.apply_sparse(var, tw.entry_ids, eg, p)
+        continue
+      from .table_ops import SparsePlan
+      from .variable import _pool_plan, _release_plan
+      pooled = True
+      if plan is None:
+        plan = _pool_plan(var)
+        if plan is None:
+          plan, pooled = SparsePlan(var._primary, var.dim), False
+        plan.build(tw.entry_ids)
+      try:
+        if getattr(var, "restrict_policy", None) is not None:
+          var.restrict_policy.apply_update(tw.entry_ids)
+        t = var._tables[0]
+        t._table.apply_planned_combined(p, plan, g, tw.seg, tw.weights, device_ops.COMBINERS[tw.combiner],
+                                        t._default_value.to(torch.float32))
+      finally:
+        if pooled:
+          _release_plan(var, plan)
 
   def _apply_generic(self, var, ids, grad):
     """The reference's write-back sequence for an arbitrary rule (`Generic`)."""

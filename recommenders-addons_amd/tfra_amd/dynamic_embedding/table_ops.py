@@ -516,6 +516,34 @@ def _apply_planned(self, params, plan, grads, default_row, sync=True):
 _DeviceTable.apply_planned = _apply_planned
 
 
+def _apply_planned_combined(self, params, plan, grad_out, seg, weights, combiner, default_row, sync=True):
+  """apply_planned for an embedding_lookup_sparse (tfra_table_apply_planned_combined): `plan` built over the entry ids,
+  grad_out [n_rows, dim] the gradient of the combined result, seg [nnz] its row ids (ascending), weights [nnz] or None,
+  combiner 0 sum / 1 mean / 2 sqrtn.  Entry e's gradient is formed from grad_out inside the write-back kernels."""
+  if plan._dim != self._dim or plan._device != self._device:
+    raise ValueError("the plan was built for dim %d on %s" % (plan._dim, plan._device))
+  grad_out = grad_out.to(self._device, torch.float32).contiguous()
+  if grad_out.dim() != 2 or grad_out.shape[1] != self._dim:
+    raise ValueError("Expected grad_out of shape [n_rows, %d], got %s" % (self._dim, list(grad_out.shape)))
+  seg = seg.to(self._device, torch.int64).contiguous()
+  if seg.numel() != plan.n or (weights is not None and weights.numel() != plan.n):
+    raise ValueError("seg / weights need one element per plan entry (%d)" % plan.n)
+  w = None if weights is None else weights.to(self._device, torch.float32).contiguous()
+  d = default_row.to(self._device, torch.float32).contiguous()
+  stream = torch.cuda.current_stream(self._device)
+  if sync:
+    stream.wait_event(plan._built)
+  _capi.call("tfra_table_apply_planned_combined", self._h, ctypes.byref(params), plan._h, _ptr(grad_out), _ptr(seg), _ptr(w),
+             int(combiner), grad_out.shape[0], _ptr(d), _stream(self._device))
+  if sync:
+    if plan._used is None:
+      plan._used = torch.cuda.Event()
+    plan._used.record(stream)
+
+
+_DeviceTable.apply_planned_combined = _apply_planned_combined
+
+
 def _upsert_sparse(self, ids, values, scores=None):
   """insert_or_assign of a batch whose keys may repeat: the LAST occurrence wins (the reference's sequential
   order), de-duplicated on the device — also on a bounded table at max_capacity."""

@@ -397,14 +397,10 @@ def _plan_at_lookup(params, ids):
   n = ids.numel()
   if n < PLAN_AT_LOOKUP_MIN_IDS or params.bp_v2 or not DynamicEmbeddingOptimizer.can_plan(params, n) or not ids.is_cuda:
     return None
-  pool = params.__dict__.setdefault("_plan_pool", {"free": [], "made": 0, "stream": None})
-  if pool["free"]:
-    plan = pool["free"].pop()
-  elif pool["made"] < PLAN_POOL_MAX:
-    plan = SparsePlan(params._primary, params.dim)
-    pool["made"] += 1
-  else:
+  plan = _pool_plan(params)
+  if plan is None:
     return None   # more lookups in flight than plans: this one takes the one-call write-back
+  pool = params._plan_pool
   if pool["stream"] is None:
     pool["stream"] = torch.cuda.Stream(device=params._primary)
   side = pool["stream"]
@@ -412,6 +408,18 @@ def _plan_at_lookup(params, ids):
   with torch.cuda.stream(side):
     plan.build(ids)
   return plan
+
+
+def _pool_plan(params):
+  """A free plan of the Variable's pool (a new one while fewer than PLAN_POOL_MAX exist), or None."""
+  from .table_ops import SparsePlan
+  pool = params.__dict__.setdefault("_plan_pool", {"free": [], "made": 0, "stream": None})
+  if pool["free"]:
+    return pool["free"].pop()
+  if pool["made"] < PLAN_POOL_MAX:
+    pool["made"] += 1
+    return SparsePlan(params._primary, params.dim)
+  return None
 
 
 def _release_plan(params, plan):
@@ -477,6 +485,58 @@ class TrainableWrapper:
     self._values = new_values
 
 
+class SparseTrainableWrapper(TrainableWrapper):
+  """The TrainableWrapper of an embedding_lookup_sparse / safe_embedding_lookup_sparse.  `ids` (the lookup's unique ids),
+  `read_value`, `update_op` and `apply_gradients` with a [n_unique, dim] gradient are those of TrainableWrapper; it also
+  keeps what the combiner's backward needs — the entry ids, their rows (`seg`, ascending), weights, the combiner, the
+  number of rows and the shape of the result — so that the gradient of the RESULT can be applied
+  (`DynamicEmbeddingOptimizer.apply_combined_gradients`) or turned into the rows' gradient (`grad_of`).
+
+  The entry list follows the reference's safe_embedding_lookup_sparse (PY/dynamic_embedding_ops.py:374-408): entries pruned
+  for their weight are not in it, and every row left empty adds one entry (row, default_id or 0, weight 1) — with
+  default_id=None that entry's gradient is zero (the reference's `where`), but its key still reaches the write-back."""
+
+  def __init__(self, params, ids, idx, n_unique, seg, weights, combiner, n_rows, out_shape, entry_ids, entry_seg,
+               entry_weights, max_norm=None, plan_writeback=False):
+    super().__init__(params, ids, max_norm=max_norm)
+    self.combiner = combiner
+    self.n_rows = int(n_rows)
+    self.out_shape = tuple(out_shape)
+    self._idx, self._n_unique, self._seg, self._weights = idx, n_unique, seg, weights   # the lookup's own entries (grad_of)
+    self.entry_ids, self.seg, self.weights = entry_ids, entry_seg, entry_weights
+    self.entry_plan = _plan_at_lookup(params, entry_ids) if plan_writeback else None
+
+  def take_entry_plan(self):
+    """The write-back plan over the entry ids started at lookup time (or None); handed back to the pool after its use."""
+    plan, self.entry_plan = self.entry_plan, None
+    return plan
+
+  def __del__(self):
+    try:
+      if self.entry_plan is not None:
+        _release_plan(self.params, self.take_entry_plan())
+    except Exception:
+      pass
+    super().__del__()
+
+  def check_grad_out(self, grad_out):
+    """grad_out as [n_rows, dim] float32; ValueError unless it has the shape of the lookup's result."""
+    grad_out = torch.as_tensor(grad_out, device=self.params._primary)
+    if tuple(grad_out.shape) != self.out_shape:
+      raise ValueError("the gradient of a sparse lookup must have the shape of its result %s, got %s" %
+                       (list(self.out_shape), list(grad_out.shape)))
+    return grad_out.reshape(self.n_rows, self.params.dim).to(torch.float32).contiguous()
+
+  def grad_of(self, grad_out):
+    """The gradient with respect to the trainable's rows, [n_unique, dim] in the order of `ids`, from the gradient of the
+    lookup's result: the combiner's backward of every looked-up entry, summed per unique id (no host sync).  (Entries that
+    safe_embedding_lookup_sparse adds for empty rows are not rows of this lookup; apply_combined_gradients writes them.)"""
+    g = self.check_grad_out(grad_out)
+    eg = device_ops.sparse_segment_combine_backprop(g, self._seg, self._weights, self.combiner)
+    n = self.ids.numel()
+    return device_ops.segment_sum(eg, self._idx, self._n_unique, n)
+
+
 def embedding_lookup(params, ids, partition_strategy=None, name=None, validate_indices=None, max_norm=None,
                      return_trainable=False, plan_writeback=False):
   """PY/dynamic_embedding_variable.py:1362-1530.  A miss returns the initializer row and does NOT
@@ -505,28 +565,40 @@ def embedding_lookup_unique(params, ids, partition_strategy=None, name=None, val
 
 
 def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=None, name="embedding_lookup_sparse",
-                            combiner="mean", max_norm=None, return_trainable=False, num_rows=None):
+                            combiner="mean", max_norm=None, return_trainable=False, num_rows=None, plan_writeback=False,
+                            _entries=None, _out_shape=None):
   """PY/dynamic_embedding_ops.py:120-293.  `sp_ids` = (indices[nnz,2] or row_ids[nnz], values[nnz]);
-  `sp_weights` = matching weight values or None.  Segment combine sum / mean / sqrtn over rows."""
+  `sp_weights` = matching weight values or None.  Segment combine sum / mean / sqrtn over rows.
+
+  return_trainable: also returns a SparseTrainableWrapper; `DynamicEmbeddingOptimizer.apply_combined_gradients` applies the
+  gradient of the result through it.  plan_writeback (with return_trainable): build the write-back plan over the entry ids
+  at lookup time, on the Variable's second stream (as embedding_lookup's plan_writeback)."""
   if combiner not in ("mean", "sqrtn", "sum"):
     raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
   indices, ids = sp_ids
   indices = torch.as_tensor(indices, device=params._primary)
   seg = (indices[:, 0] if indices.dim() == 2 else indices).to(torch.int64)
   ids = torch.as_tensor(ids, device=params._primary)
-  uniq, idx, _ = device_ops.unique(ids)
-  r = embedding_lookup(params, uniq, max_norm=max_norm, return_trainable=return_trainable)
-  ue, tw = r if return_trainable else (r, None)
+  uniq, idx, cnt = device_ops.unique(ids)
+  w = sp_weights if sp_weights is None else torch.as_tensor(sp_weights, dtype=torch.float32, device=params._primary)
   n = int(seg.max().item()) + 1 if num_rows is None else num_rows
+  if return_trainable:
+    e_ids, e_seg, e_w = _entries if _entries is not None else (ids.reshape(-1).to(torch.int64), seg, w)
+    tw = SparseTrainableWrapper(params, uniq.reshape(-1), idx, cnt, seg, w, combiner, n,
+                                _out_shape if _out_shape is not None else (n, params.dim), e_ids, e_seg, e_w,
+                                max_norm=max_norm, plan_writeback=plan_writeback)
+    ue = tw.read_value()
+  else:
+    tw = None
+    ue = embedding_lookup(params, uniq, max_norm=max_norm)
   # gather + weights + segment combine fused in one kernel (reads the unique rows through idx)
-  out = device_ops.sparse_segment_combine(ue, idx, seg, sp_weights if sp_weights is None else torch.as_tensor(
-      sp_weights, dtype=torch.float32, device=ue.device), combiner, n)
+  out = device_ops.sparse_segment_combine(ue, idx, seg, w, combiner, n)
   return (out, tw) if return_trainable else out
 
 
 def safe_embedding_lookup_sparse(params, sp_ids, sparse_weights=None, combiner="mean", default_id=None,
                                  name="safe_embedding_lookup_sparse", partition_strategy=None, max_norm=None,
-                                 return_trainable=False, num_rows=None):
+                                 return_trainable=False, num_rows=None, plan_writeback=False):
   """PY/dynamic_embedding_ops.py:296-430.  `sp_ids` = (indices[nnz, R], values[nnz][, dense_shape[R]]) — a
   SparseTensor of rank R >= 2 (or row ids [nnz] for rank 2).  Semantics of the reference, NOT of
   `tf.nn.safe_embedding_lookup_sparse`: ids are never pruned (any int64 is a legal key, negative ones too,
@@ -571,8 +643,27 @@ def safe_embedding_lookup_sparse(params, sp_ids, sparse_weights=None, combiner="
       keep = w > 0
   if keep is not None:
     rows, ids, w = rows[keep], ids[keep], w[keep]
+  entries = None
+  if return_trainable:
+    # the trainable's entries (sparse_fill_empty_rows, :379-391): one (row, default_id or 0, weight 1) per empty row, merged
+    # into row order; with default_id=None the reference's `where` zeroes that entry's gradient — weight 0 does the same here
+    # (a row whose weight sum is 0 has gradient 0, and a sum combiner multiplies by the weight)
+    has = torch.zeros(n, dtype=torch.bool, device=params._primary)
+    has[rows] = True
+    er = torch.nonzero(~has).reshape(-1)
+    all_rows = torch.cat([rows.to(torch.int64), er])
+    all_ids = torch.cat([ids.reshape(-1).to(torch.int64),
+                         torch.full_like(er, 0 if default_id is None else int(default_id))])
+    ew = 0.0 if default_id is None else 1.0
+    all_w = torch.cat([torch.ones(rows.numel(), dtype=torch.float32, device=er.device) if w is None else w,
+                       torch.full((er.numel(),), ew, dtype=torch.float32, device=er.device)])
+    order = torch.sort(all_rows, stable=True).indices
+    entries = (all_ids[order].contiguous(), all_rows[order].contiguous(),
+               None if (w is None and default_id is not None) else all_w[order].contiguous())
+  out_shape = (tuple(lead) if lead is not None else (n,)) + (params.dim,)
   out = embedding_lookup_sparse(params, (rows, ids), w, combiner=combiner, max_norm=max_norm,
-                                return_trainable=return_trainable, num_rows=n)
+                                return_trainable=return_trainable, num_rows=n, plan_writeback=plan_writeback,
+                                _entries=entries, _out_shape=out_shape)
   res, tw = out if return_trainable else (out, None)
   if default_id is not None and n:
     empty = torch.ones(n, dtype=torch.bool, device=res.device)
