@@ -7,11 +7,14 @@ import numpy as np
 
 def default_partition_fn(keys, shard_num, gpu_mode=True):
   """PY/dynamic_embedding_variable.py:165-197.  int64 keys on CUDA builds:
-  ``int32(key & 0x7fffffff) % N``; otherwise ``key % N`` (floor mod, like tf.math.mod)."""
-  keys = np.asarray(keys, dtype=np.int64)
+  ``int32(key & 0x7fffffff) % N``; otherwise — int32 keys, or any keys on a CPU build — ``key % N`` (floor mod, like
+  tf.math.mod).  The key dtype is read before the keys are widened: a Python list or an int64 array is int64."""
+  keys = np.asarray(keys)
+  is_int64 = keys.dtype == np.int64
+  keys = keys.astype(np.int64)
   if shard_num <= 1:
     return np.zeros(keys.shape, dtype=np.int32)
-  if gpu_mode:
+  if gpu_mode and is_int64:
     return ((keys & 0x7FFFFFFF).astype(np.int32) % np.int32(shard_num)).astype(np.int32)
   return np.mod(keys, shard_num).astype(np.int32)
 

@@ -5,7 +5,7 @@ import ctypes
 import torch
 
 from .. import _capi
-from .table_ops import _ptr, _stream
+from .table_ops import _narrow_keys, _ptr, _stream, _wide_keys
 
 _WS = {}
 
@@ -23,14 +23,15 @@ def _workspace(device):
 
 
 def unique(ids, ordered=True):
-  """tf.unique (first-occurrence order): returns (unique[U], idx[n] int32, num_unique device scalar).
+  """tf.unique (first-occurrence order): returns (unique[U], idx[n] int32, num_unique device scalar).  `unique` has the dtype of
+  `ids` (int64 or int32, as tf.unique's output has its input's; tfra_unique reads int64 ids, so int32 ids are widened in front of
+  it and the uniques narrowed back).
 
   `unique` is returned as a length-n buffer view trimmed with ONE host read of the count — the
   same sync TF's `tf.unique` output-shape inference imposes (PY/dynamic_embedding_ops.py:99).
   ordered=False: the distinct ids in no particular order (tfra_unique_unordered, two launches instead of three; up to 2^18 ids)
   — all embedding_lookup needs: the order of tf.unique's output is not observable behind the gather."""
-  ids = ids.contiguous()
-  flat = ids.reshape(-1)
+  flat = _wide_keys(ids.reshape(-1))
   n = flat.numel()
   dev = flat.device
   uniq = torch.empty(n, dtype=torch.int64, device=dev)
@@ -39,19 +40,19 @@ def unique(ids, ordered=True):
   fn = "tfra_unique" if (ordered or n > (1 << 18)) else "tfra_unique_unordered"
   _capi.call(fn, _workspace(dev), n, _ptr(flat), _ptr(uniq), _ptr(idx), _ptr(cnt), _stream(dev))
   u = int(cnt.item())
-  return uniq[:u], idx, cnt
+  return _narrow_keys(uniq[:u], ids.dtype), idx, cnt
 
 
 def unique_no_sync(ids):
-  """Like `unique` but never reads the count on the host: returns the full-length buffer."""
-  flat = ids.contiguous().reshape(-1)
+  """Like `unique` but never reads the count on the host: returns the full-length buffer (in the dtype of `ids`)."""
+  flat = _wide_keys(ids.reshape(-1))
   n = flat.numel()
   dev = flat.device
   uniq = torch.empty(n, dtype=torch.int64, device=dev)
   idx = torch.empty(n, dtype=torch.int32, device=dev)
   cnt = torch.zeros((), dtype=torch.int64, device=dev)
   _capi.call("tfra_unique", _workspace(dev), n, _ptr(flat), _ptr(uniq), _ptr(idx), _ptr(cnt), _stream(dev))
-  return uniq, idx, cnt
+  return _narrow_keys(uniq, ids.dtype), idx, cnt
 
 
 def gather_rows(rows, idx):
@@ -92,31 +93,38 @@ def segment_sum(grads, idx, num_segments_dev, max_segments):
 
 def reduce_by_key(ids, rows):
   """unique + unsorted_segment_sum, parallel per key (hot ids do not serialise) and bit-reproducible.
-  Returns (keys[n] buffer, sums[n,dim] buffer, count device scalar): the first `count` entries are valid,
+  Returns (keys[n] buffer in the dtype of `ids`, sums[n,dim] buffer, count device scalar): the first `count` entries are valid,
   in a deterministic but unspecified key order."""
-  ids = ids.contiguous().reshape(-1)
+  wide = _wide_keys(ids.reshape(-1))
   rows = rows.to(torch.float32).contiguous()
-  n, dim = ids.numel(), rows.shape[-1]
-  dev = ids.device
+  n, dim = wide.numel(), rows.shape[-1]
+  dev = wide.device
   keys = torch.empty(n, dtype=torch.int64, device=dev)
   sums = torch.empty((n, dim), dtype=torch.float32, device=dev)
   cnt = torch.zeros((), dtype=torch.int64, device=dev)
-  _capi.call("tfra_reduce_by_key", _workspace(dev), n, _ptr(ids), dim, _ptr(rows), _ptr(keys), _ptr(sums), _ptr(cnt),
+  _capi.call("tfra_reduce_by_key", _workspace(dev), n, _ptr(wide), dim, _ptr(rows), _ptr(keys), _ptr(sums), _ptr(cnt),
              _stream(dev))
-  return keys, sums, cnt
+  return _narrow_keys(keys, ids.dtype), sums, cnt
 
 
-PARTITION_MASK_MOD = 0  # int32(key & 0x7fffffff) % N   (CUDA-build branch of default_partition_fn)
-PARTITION_FLOOR_MOD = 1  # key % N                       (CPU-build branch)
+PARTITION_MASK_MOD = 0  # int32(key & 0x7fffffff) % N   (int64 keys on a GPU build: default_partition_fn's first branch)
+PARTITION_FLOOR_MOD = 1  # key % N, floor mod            (every other case: int32 keys, CPU builds)
 PARTITION_HASH = 2  # fmix64(key) % N               (opt-in, Zipf-balanced)
+
+
+def default_partition_mode(key_dtype):
+  """The mode of default_partition_fn for keys of `key_dtype` on a GPU build (PY/dynamic_embedding_variable.py:182-196): mask-mod
+  for int64 keys only; int32 keys take `math_ops.mod(keys, shard_num)`, floor mod.  The two differ for negative keys whenever
+  the shard count is not a power of two."""
+  return PARTITION_FLOOR_MOD if key_dtype == torch.int32 else PARTITION_MASK_MOD
 
 
 def partition(keys, num_shards, mode=PARTITION_MASK_MOD, n_dev=None):
   """default_partition_fn + dynamic_partition in one pass (PY/dynamic_embedding_variable.py:131-197).
-  Returns owner-major keys, perm (original index of each output element) and device counts[num_shards].
+  Returns owner-major keys (in the dtype of `keys`), perm (original index of each output element) and device counts[num_shards].
   n_dev: optional device int64 scalar — only the first min(n, n_dev) keys are partitioned (the buffers
   keep length n; entries past sum(counts) are unspecified)."""
-  flat = keys.contiguous().reshape(-1)
+  flat = _wide_keys(keys.reshape(-1))
   n = flat.numel()
   dev = flat.device
   keys_out = torch.empty(n, dtype=torch.int64, device=dev)
@@ -124,7 +132,7 @@ def partition(keys, num_shards, mode=PARTITION_MASK_MOD, n_dev=None):
   counts = torch.zeros(num_shards, dtype=torch.int64, device=dev)
   _capi.call("tfra_partition", _workspace(dev), n, None if n_dev is None else _ptr(n_dev), _ptr(flat), num_shards, mode,
              _ptr(keys_out), _ptr(perm), _ptr(counts), _stream(dev))
-  return keys_out, perm, counts
+  return _narrow_keys(keys_out, keys.dtype), perm, counts
 
 
 def partition_by_owner(owner, num_shards):
@@ -189,8 +197,10 @@ def dynamic_stitch(indices, data):
 
 
 def select_lowest(keys, status, k):
-  """The k keys with the lowest status (int32/int64), ties in input order (restrict policies)."""
-  keys = keys.reshape(-1).to(torch.int64).contiguous()
+  """The k keys with the lowest status (int32/int64), ties in input order (restrict policies).  The keys come back in the
+  dtype of `keys` (int64 or int32)."""
+  key_dtype = keys.dtype
+  keys = _wide_keys(keys.reshape(-1))
   status = status.reshape(-1).contiguous()
   if status.dtype not in (torch.int32, torch.int64):
     raise TypeError("status must be int32 or int64")
@@ -200,7 +210,7 @@ def select_lowest(keys, status, k):
   out = torch.empty(k, dtype=torch.int64, device=keys.device)
   _capi.call("tfra_select_lowest", _workspace(keys.device), n, _ptr(keys), _ptr(status),
              4 if status.dtype == torch.int32 else 5, k, _ptr(out), _stream(keys.device))
-  return out
+  return _narrow_keys(out, key_dtype)
 
 
 COMBINERS = {"sum": 0, "mean": 1, "sqrtn": 2}

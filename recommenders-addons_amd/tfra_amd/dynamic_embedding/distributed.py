@@ -21,6 +21,15 @@ import torch
 import torch.distributed as dist
 
 
+def _partition_mode(partition_mode, key_dtype):
+  """An explicit partition mode as given; None = default_partition_fn's rule for the table's key dtype (mask-mod for int64 keys,
+  floor mod for int32 keys: PY/dynamic_embedding_variable.py:182-196)."""
+  if partition_mode is not None:
+    return int(partition_mode)
+  from .device_ops import default_partition_mode
+  return default_partition_mode(key_dtype)
+
+
 class _DeviceOps:
   """Default: the HIP front-end kernels."""
 
@@ -61,12 +70,12 @@ class AllToAllEmbedding:
   read per lookup is the pair of split-size vectors that alltoallv needs (as `hvd.alltoall(ids, splits)`).
   """
 
-  def __init__(self, local, group=None, partition_mode=0, ops=None, dedup=True, force_collectives=False):
+  def __init__(self, local, group=None, partition_mode=None, ops=None, dedup=True, force_collectives=False):
     self.local = local
     self.group = group
     self.world = dist.get_world_size(group) if dist.is_initialized() else 1
     self.rank = dist.get_rank(group) if dist.is_initialized() else 0
-    self.mode = partition_mode
+    self.mode = _partition_mode(partition_mode, getattr(local, "key_dtype", torch.int64))
     self.ops = ops if ops is not None else _DeviceOps()
     self.dedup = dedup
     # world == 1 normally short-circuits; `force_collectives` keeps the full route (used to exercise the
@@ -203,14 +212,14 @@ class RoutedPrefetchStep:
   """
   NSLOTS = 4
 
-  def __init__(self, var, optimizer, group=None, partition_mode=0, force_collectives=False):
+  def __init__(self, var, optimizer, group=None, partition_mode=None, force_collectives=False):
     from .optimizer import DynamicEmbeddingOptimizer
     from .table_ops import SparsePlan
     if var.shard_num != 1 or not DynamicEmbeddingOptimizer.can_plan(var, 1):
       raise ValueError("RoutedPrefetchStep needs a single-shard fp32 local Variable with dim % 4 == 0, dim <= 256")
     optimizer._check(var)
     self.var, self.deo = var, optimizer
-    self.group, self.mode = group, partition_mode
+    self.group, self.mode = group, _partition_mode(partition_mode, var.key_dtype)
     self.world = dist.get_world_size(group) if dist.is_initialized() else 1
     self.rank = dist.get_rank(group) if dist.is_initialized() else 0
     self.collectives = dist.is_initialized() and (self.world > 1 or force_collectives)
@@ -244,8 +253,9 @@ class RoutedPrefetchStep:
     current stream (the second stream then waits for it)."""
     if self.fed >= self.NSLOTS - 1:
       raise RuntimeError("RoutedPrefetchStep: %d batches are fed ahead already" % self.fed)
+    from .table_ops import _driver_ids
     sl = self.slots[self.tail]
-    ids = torch.as_tensor(ids, device=self.dev).reshape(-1).to(torch.int64).contiguous()
+    ids = _driver_ids(self.table, ids, self.dev, widen=False)   # int32-key tables: the ids stay int32 along the route
     if not ids_ready:
       self.side.wait_stream(torch.cuda.current_stream(self.dev))
     if sl.get("done") is not None:
@@ -275,7 +285,7 @@ class RoutedPrefetchStep:
     send, recv = [int(x) for x in hc[0]], [int(x) for x in hc[1]]
     u = sum(send)
     with torch.cuda.stream(self.side):
-      remote_ids = torch.empty(sum(recv), dtype=torch.int64, device=self.dev)
+      remote_ids = torch.empty(sum(recv), dtype=sl["ids"].dtype, device=self.dev)
       self._a2a(remote_ids, sl["owner_major"][:u].contiguous(), recv, send)
       # position -> row of the owner-major block: inverse of perm (owner-major j holds distinct id perm[j]), through idx —
       # two row moves of 4-byte rows (a scatter and a gather) instead of four framework ops
@@ -451,7 +461,7 @@ class NativeRoutedStep:
   transport: "rccl" (default when torch.distributed runs on nccl), "staged" (host-staged through the group; tests),
   None (single rank, device copies).  Reference: PY/shadow_embedding_ops.py:397-447."""
 
-  def __init__(self, var, optimizer, group=None, partition_mode=0, force_collectives=False, transport="auto", max_batch=1 << 18,
+  def __init__(self, var, optimizer, group=None, partition_mode=None, force_collectives=False, transport="auto", max_batch=1 << 18,
                threaded=True, share_transport_of=None):
     import ctypes
     from .. import _capi
@@ -491,7 +501,7 @@ class NativeRoutedStep:
       raise ValueError("transport: 'auto', 'rccl', 'staged' or None")
     self._threaded = bool(threaded)
     self._h = ctypes.c_void_p()
-    _capi.call("tfra_route_create", self.table._h, tr, int(partition_mode), int(max_batch),
+    _capi.call("tfra_route_create", self.table._h, tr, _partition_mode(partition_mode, self.table.key_dtype), int(max_batch),
                0 if threaded else _capi.ROUTE_NO_THREAD, ctypes.byref(self._h))
     self.default = self.t._default_value.to(device=self.dev, dtype=torch.float32).contiguous()
     self._ids = []     # fed batches, oldest first (kept alive until applied)
@@ -510,7 +520,10 @@ class NativeRoutedStep:
     return self._ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(self.dev.index or 0))
 
   def feed(self, ids, ids_ready=True):
-    ids = torch.as_tensor(ids, device=self.dev).reshape(-1).to(torch.int64).contiguous()
+    from .table_ops import _driver_ids
+    ids = _driver_ids(self.table, ids, self.dev)
+    if self.table.key_dtype == torch.int32:
+      ids_ready = False   # widened on the current stream just now: the driver's stream must wait for that
     self._call("tfra_route_feed", self._h, ids.numel(), self._ctypes.c_void_p(ids.data_ptr()), 1 if ids_ready else 0, self._stream())
     self._ids.append(ids)
 
@@ -544,7 +557,8 @@ class NativeRoutedStep:
         torch.cuda.current_stream(self.dev).synchronize()   # the ids arrived on the driver's second stream
         if _hip().hipMemcpy(served.data_ptr(), ptr, nr * 8, 3) != 0:
           raise RuntimeError("NativeRoutedStep: copy of the served ids failed")
-        self.var.restrict_policy.apply_update(served)
+        from .table_ops import _narrow_keys
+        self.var.restrict_policy.apply_update(_narrow_keys(served, self.table.key_dtype))
     self._call("tfra_route_apply", self._h, self._ctypes.byref(p), self._ctypes.c_void_p(g.data_ptr()),
                self._ctypes.c_void_p(self.default.data_ptr()), self._stream())
     self._ids.pop(0)
@@ -576,7 +590,7 @@ class MultiTableRoutedStep:
   PY/shadow_embedding_ops.py:397-447 + the optimizer's sparse apply); every rank calls with the tables in the same order, so the
   collectives of all tables interleave identically everywhere.  One optimizer step (`begin_step`) covers all tables of an apply."""
 
-  def __init__(self, variables, optimizer, group=None, partition_mode=0, force_collectives=False, transport="auto", max_batch=1 << 18,
+  def __init__(self, variables, optimizer, group=None, partition_mode=None, force_collectives=False, transport="auto", max_batch=1 << 18,
                threaded=False):
     self.deo = optimizer
     self.steps = []
@@ -628,7 +642,7 @@ class RoutedAssignStep:
   transport: "auto" | "rccl" | "staged" (tests) | "local" (one rank THROUGH the route driver, device copies where the alltoalls
   would be: what the route itself costs)."""
 
-  def __init__(self, table, group=None, partition_mode=0, transport="auto", max_batch=1 << 18):
+  def __init__(self, table, group=None, partition_mode=None, transport="auto", max_batch=1 << 18):
     import ctypes
     from .. import _capi
     self.t = table
@@ -665,7 +679,8 @@ class RoutedAssignStep:
     elif self.world != 1:
       raise ValueError("RoutedAssignStep: transport='local' needs a single rank")
     self._h = ctypes.c_void_p()
-    _capi.call("tfra_assign_route_create", self.table._h, tr, int(partition_mode), int(max_batch), ctypes.byref(self._h))
+    _capi.call("tfra_assign_route_create", self.table._h, tr, _partition_mode(partition_mode, self.table.key_dtype), int(max_batch),
+               ctypes.byref(self._h))
 
   def _call(self, name, *args):
     try:
@@ -680,14 +695,15 @@ class RoutedAssignStep:
     return self._ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(self.dev.index or 0))
 
   def _as_ids(self, ids):
-    if torch.is_tensor(ids) and ids.dtype == torch.int64 and ids.dim() == 1 and ids.is_contiguous() and ids.device == self.dev:
-      return ids
-    return torch.as_tensor(ids, device=self.dev).reshape(-1).to(torch.int64).contiguous()
+    from .table_ops import _driver_ids
+    return _driver_ids(self.table, ids, self.dev)
 
   def feed(self, ids, ids_ready=False):
     """ids_ready=False (default): the ids may still be in flight on the current stream — the driver's own stream waits for them (one
     event); True: they are complete (a host synchronisation lies between their producer and this call)."""
     ids = self._as_ids(ids)
+    if self.table.key_dtype == torch.int32:
+      ids_ready = False   # widened on the current stream just now: the driver's stream must wait for that
     if not self.identity:
       self._call("tfra_assign_route_feed", self._h, ids.numel(), self._ctypes.c_void_p(ids.data_ptr()), 1 if ids_ready else 0, self._stream())
     self._fed.append(ids)

@@ -19,6 +19,7 @@ import torch
 
 from .. import _capi
 from . import device_ops
+from .table_ops import _driver_ids, _narrow_keys
 from .variable import SparseTrainableWrapper, TrainableWrapper, Variable
 
 
@@ -358,7 +359,7 @@ class DynamicEmbeddingOptimizer:
       return self._apply_generic(var, ids, grad)
     if plan is not None:
       if getattr(var, "restrict_policy", None) is not None:
-        var.restrict_policy.apply_update(plan.ids)
+        var.restrict_policy.apply_update(plan.ids if ids is None else ids)   # (plan.ids are int64: the caller's keep the key dtype)
       t = var._tables[0]
       t._table.apply_planned(p, plan, grad.reshape(-1, var.dim), t._default_value.to(torch.float32))
       return
@@ -499,7 +500,7 @@ class PrefetchStep:
 
   def prime(self, ids):
     """Stage the first batch: its plan is built on the current stream."""
-    ids = torch.as_tensor(ids, device=self.dev).reshape(-1).to(torch.int64).contiguous()
+    ids = _driver_ids(self.table, ids, self.dev)
     self.plans[self.cur].build(ids, sync=False)
     self.ids[self.cur] = ids
     return self
@@ -514,24 +515,21 @@ class PrefetchStep:
     nxt_slot = (cur + 1) % self.NPLANS
     ids = self.ids[cur]
     n = ids.numel()
+    nxt = None if next_ids is None else _driver_ids(self.table, next_ids, self.dev)
     self.deo.iterations += 1
     p = self.deo.opt.params(self.deo.iterations)
     grads = grads.reshape(n, self.var.dim)
     if grads.dtype != torch.float32 or not grads.is_contiguous():
       grads = grads.to(torch.float32).contiguous()
     if getattr(self.var, "restrict_policy", None) is not None and n:   # PY/embedding_weights.py:441-442
-      self.var.restrict_policy.apply_update(ids)
+      self.var.restrict_policy.apply_update(_narrow_keys(ids, self.table.key_dtype))
     out = torch.empty((n, self.var.dim), dtype=torch.float32, device=self.dev)
-    nxt = None
-    if next_ids is not None:
-      nxt = next_ids
-      if not (torch.is_tensor(nxt) and nxt.dtype == torch.int64 and nxt.dim() == 1 and nxt.is_contiguous() and
-              nxt.device == self.dev):
-        nxt = torch.as_tensor(next_ids, device=self.dev).reshape(-1).to(torch.int64).contiguous()
+    if nxt is not None:
       nxt.record_stream(self.side)
       self.ids[nxt_slot] = nxt                      # kept alive until its step has run
     main = torch.cuda.current_stream(self.dev)
-    if nxt is not None and not next_ids_ready:
+    # an int32 table's next ids were just widened on `main` (_driver_ids): the plan build on the second stream must follow that
+    if nxt is not None and (not next_ids_ready or self.table.key_dtype == torch.int32):
       self.side.wait_stream(main)
     _capi.call("tfra_table_step_prefetch", self.table._h, ctypes.byref(p), self.plans[cur]._h, _ptr(ids), _ptr(out),
                _ptr(self.default), _ptr(grads), _ptr(self.default), self.plans[nxt_slot]._h if nxt is not None else None,
@@ -585,7 +583,7 @@ class MultiTablePrefetchStep:
 
   def prime(self, ids_list):
     for i, ids in enumerate(ids_list):
-      ids = torch.as_tensor(ids, device=self.dev).reshape(-1).to(torch.int64).contiguous()
+      ids = _driver_ids(self.tables[i], ids, self.dev)
       self.plans[i][self.cur].build(ids, sync=False)
       self.ids[i][self.cur] = ids
     torch.cuda.current_stream(self.dev).synchronize()   # the plans were built on the current stream, the steps run on others
@@ -606,11 +604,10 @@ class MultiTablePrefetchStep:
         g = g.to(torch.float32).contiguous()
       out = torch.empty((n, v.dim), dtype=torch.float32, device=self.dev)
       nxt = None if next_ids_list is None else next_ids_list[i]
-      if nxt is not None and not (torch.is_tensor(nxt) and nxt.dtype == torch.int64 and nxt.dim() == 1 and nxt.is_contiguous() and
-                                  nxt.device == self.dev):
-        nxt = torch.as_tensor(nxt, device=self.dev).reshape(-1).to(torch.int64).contiguous()
+      if nxt is not None:
+        nxt = _driver_ids(self.tables[i], nxt, self.dev)
       if getattr(v, "restrict_policy", None) is not None and n:
-        v.restrict_policy.apply_update(ids)
+        v.restrict_policy.apply_update(_narrow_keys(ids, self.tables[i].key_dtype))
       d = self.descs[i]
       d.opt = ctypes.addressof(p)
       d.plan_cur = self.plans[i][cur]._h
@@ -677,7 +674,7 @@ class PrefetchAssignStep:
     self._main = None
 
   def prime(self, ids):
-    ids = torch.as_tensor(ids, device=self.dev).reshape(-1).to(torch.int64).contiguous()
+    ids = _driver_ids(self.table, ids, self.dev)
     self.plans[self.cur].build(ids, sync=False)
     self.ids[self.cur] = ids
     return self
@@ -704,12 +701,10 @@ class PrefetchAssignStep:
       main = torch.cuda.current_stream(dev)
       self._main, self._main_h = main, ctypes.c_void_p(main.cuda_stream)
     if next_ids is not None:
-      nxt = next_ids
-      if not (torch.is_tensor(nxt) and nxt.dtype == torch.int64 and nxt.dim() == 1 and nxt.is_contiguous() and nxt.device == dev):
-        nxt = torch.as_tensor(next_ids, device=dev).reshape(-1).to(torch.int64).contiguous()
+      nxt = _driver_ids(self.table, next_ids, dev)
       nxt.record_stream(self.side)
       self.ids[nxt_slot] = nxt
-      if not next_ids_ready:
+      if not next_ids_ready or self.table.key_dtype == torch.int32:   # (int32 tables: widened on the main stream just now)
         self.side.wait_stream(self._main)
     sp = None
     if scores is not None:
@@ -806,9 +801,7 @@ class OverlapAssignStep:
       pass
 
   def _as_ids(self, ids):
-    if torch.is_tensor(ids) and ids.dtype == torch.int64 and ids.dim() == 1 and ids.is_contiguous() and ids.device == self.dev:
-      return ids
-    return torch.as_tensor(ids, device=self.dev).reshape(-1).to(torch.int64).contiguous()
+    return _driver_ids(self.table, ids, self.dev)
 
   def prime(self, ids):
     self._ids = self._as_ids(ids)
@@ -891,8 +884,12 @@ class OverlapAssignStep:
     """Pre-builds the argument array of `tfra_table_steps_overlap` for the steps (ids_list[k], values_list[k]) -> outs[k]:
     returns a callable that enqueues all of them with ONE host call.  values_before = the values of the batch pending when
     the run starts (None: nothing pending); ids_after / ids_after2 = the ids of the two steps behind the run (their plans are
-    built / started by the run's last launches).  The caller keeps every tensor alive and unchanged until the run has executed."""
+    built / started by the run's last launches).  The caller keeps every tensor alive and unchanged until the run has executed.
+    Ids that are not already the engine's int64 ids (those of an int32-key table) are converted here, when the run is made."""
     from .table_ops import _stream
+    ids_list = [self._as_ids(x) for x in ids_list]
+    ids_after = None if ids_after is None else self._as_ids(ids_after)
+    ids_after2 = None if ids_after2 is None else self._as_ids(ids_after2)
     m = len(ids_list)
     arr = (_capi.OverlapStep * m)()
     for k in range(m):

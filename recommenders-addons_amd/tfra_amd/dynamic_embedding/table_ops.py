@@ -63,6 +63,46 @@ def _ptr(t):
   return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _wide_keys(keys):
+  """`keys` as the engine's int64 keys, for a C function that reads `const int64_t*`: int64 keys as they are, int32 keys widened on
+  the device (tfra_keys_widen_i32).  Any other dtype raises TypeError before a launch."""
+  if keys.dtype == torch.int64:
+    return keys.contiguous()
+  if keys.dtype != torch.int32:
+    raise TypeError("keys must be torch.int64 or torch.int32, got %s" % keys.dtype)
+  keys = keys.contiguous()
+  wide = torch.empty(keys.shape, dtype=torch.int64, device=keys.device)
+  if keys.numel():
+    _capi.call("tfra_keys_widen_i32", keys.numel(), _ptr(keys), _ptr(wide), _stream(keys.device))
+  return wide
+
+
+def _narrow_keys(keys, dtype):
+  """Engine int64 keys back in the caller's key dtype: int32 keys narrowed on the device (tfra_keys_narrow_i32), int64 as they
+  are.  Only keys that came from int32 keys are narrowed, so none can overflow."""
+  if dtype == torch.int64:
+    return keys
+  narrow = torch.empty(keys.shape, dtype=torch.int32, device=keys.device)
+  if keys.numel():
+    _capi.call("tfra_keys_narrow_i32", keys.numel(), _ptr(keys.contiguous()), _ptr(narrow), None, _stream(keys.device))
+  return narrow
+
+
+def _driver_ids(table, ids, device, widen=True):
+  """The ids of a step or route driver, as the int64 buffer its C calls read.  An int32-key table takes int32 ids only — int64 ids
+  raise TypeError before any launch, as the table's own ops do, so that no key above 2^31 can enter it — and widens them (or,
+  widen=False, keeps them as they are); an int64-key table casts whatever integer ids it is given, as it always has."""
+  if table.key_dtype == torch.int32:
+    ids = torch.as_tensor(ids, device=device) if not torch.is_tensor(ids) else ids
+    if ids.dtype != torch.int32:
+      raise TypeError("Signature mismatch. Keys must be dtype %s, got %s." % (torch.int32, ids.dtype))
+    ids = ids.to(device).reshape(-1).contiguous()
+    return _wide_keys(ids) if widen else ids
+  if torch.is_tensor(ids) and ids.dtype == torch.int64 and ids.dim() == 1 and ids.is_contiguous() and ids.device == device:
+    return ids
+  return torch.as_tensor(ids, device=device).reshape(-1).to(torch.int64).contiguous()
+
+
 def _as_device(device):
   if device is None or device == "" or device == []:
     device = "cuda:0"
@@ -161,12 +201,7 @@ class _DeviceTable:
     keys = torch.as_tensor(keys, device=self._device) if not torch.is_tensor(keys) else keys
     if keys.dtype != self._key_dtype:
       raise TypeError("Signature mismatch. Keys must be dtype %s, got %s." % (self._key_dtype, keys.dtype))
-    keys = keys.to(self._device).contiguous()
-    if self._key_dtype == torch.int32:   # the engine's keys are int64
-      wide = torch.empty(keys.shape, dtype=torch.int64, device=self._device)
-      _capi.call("tfra_keys_widen_i32", keys.numel(), _ptr(keys), _ptr(wide), _stream(self._device))
-      return wide
-    return keys
+    return _wide_keys(keys.to(self._device))   # the engine's keys are int64
 
   def _values_for(self, keys, values, what="values"):
     values = torch.as_tensor(values, device=self._device) if not torch.is_tensor(values) else values
@@ -225,6 +260,7 @@ class _DeviceTable:
     cnt = torch.zeros((), dtype=torch.int64, device=self._device)
     _capi.call("tfra_table_find_unique", self._h, _workspace(self._device), n, _ptr(keys), _ptr(out), _ptr(exists), _ptr(d), full,
                _ptr(uniq), _ptr(idx), _ptr(cnt), _stream(self._device))
+    uniq = _narrow_keys(uniq, self._key_dtype)   # the table's key dtype, so that `unique` goes back into upsert / erase
     return (out, uniq, idx, cnt, exists) if return_exists else (out, uniq, idx, cnt)
 
   def upsert(self, keys, values, scores=None, unique_keys=False, field=0):
@@ -354,11 +390,7 @@ class _DeviceTable:
     got = int(counter.item())
     if got != n:
       raise RuntimeError("export: table changed during export (%d vs %d)" % (got, n))
-    if self._key_dtype == torch.int32:
-      narrow = torch.empty(n, dtype=torch.int32, device=self._device)
-      _capi.call("tfra_keys_narrow_i32", n, _ptr(keys), _ptr(narrow), None, _stream(self._device))
-      keys = narrow
-    return keys, vals, scores
+    return _narrow_keys(keys, self._key_dtype), vals, scores
 
   def save(self, prefix, buffer_size=4194304, append_to_file=False, field=0):
     """field > 0: the co-located state vector `field` (an optimizer slot) in the same file format."""

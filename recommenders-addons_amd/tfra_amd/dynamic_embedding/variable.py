@@ -19,12 +19,14 @@ from .table_ops import CuckooHashTable, HkvHashTable, HkvEvictStrategy, _as_devi
 
 
 def default_partition_fn(keys, shard_num):
-  """PY/dynamic_embedding_variable.py:165-197 (int64 keys, accelerator build):
-  ``int32(key & 0x7fffffff) % shard_num``.  Kept as a python callable for API parity; the
-  Variable recognises it and runs the fused device partition instead."""
+  """PY/dynamic_embedding_variable.py:165-197 on an accelerator build: int64 keys go to ``int32(key & 0x7fffffff) % shard_num``
+  (:182-190), keys of any other dtype — int32 — to ``math_ops.mod(keys, shard_num)``, floor mod (:191-196).  Kept as a python
+  callable for API parity; the Variable recognises it and runs the fused device partition instead."""
   if shard_num <= 1:
     return torch.zeros(keys.shape, dtype=torch.int32, device=keys.device)
-  return ((keys & 0x7FFFFFFF).to(torch.int32) % shard_num).to(torch.int32)
+  if keys.dtype == torch.int64:
+    return ((keys & 0x7FFFFFFF).to(torch.int32) % shard_num).to(torch.int32)
+  return torch.remainder(keys, shard_num).to(torch.int32)    # floor mod: the sign of the divisor, as tf.math.mod
 
 
 class KVCreator:
@@ -151,11 +153,9 @@ class Variable:
     if self.shard_num <= 1:
       return [flat], None, [flat.numel()]
     if self.partition_fn is default_partition_fn:
-      if flat.dtype == torch.int32:   # the partition kernel reads int64 keys; sign extension keeps (key & 0x7fffffff) % n
-        owner_major, perm, counts = device_ops.partition(flat.to(torch.int64), self.shard_num, device_ops.PARTITION_MASK_MOD)
-        owner_major = owner_major.to(torch.int32)
-      else:
-        owner_major, perm, counts = device_ops.partition(flat, self.shard_num, device_ops.PARTITION_MASK_MOD)
+      # default_partition_fn's rule follows the key dtype: mask-mod for int64 keys, floor mod for int32 keys
+      # (PY/dynamic_embedding_variable.py:182-196; they differ for negative keys when shard_num is not a power of two)
+      owner_major, perm, counts = device_ops.partition(flat, self.shard_num, device_ops.default_partition_mode(flat.dtype))
     else:
       owner = self.partition_fn(flat, self.shard_num)
       perm, counts = device_ops.partition_by_owner(owner, self.shard_num)
@@ -337,14 +337,15 @@ class Variable:
             t._table.load(p, buffer_size, field=f)
       return
     self.clear()
+    key_np = np.int32 if self.key_dtype == torch.int32 else np.int64   # the key files hold raw keys of the key dtype
     for fn in files:
-      keys = np.fromfile(os.path.join(dirpath, fn + "-keys"), dtype=np.int64)
+      keys = np.fromfile(os.path.join(dirpath, fn + "-keys"), dtype=key_np)
       vals = torch.from_numpy(np.fromfile(os.path.join(dirpath, fn + "-values"), dtype=np.uint8)).view(
           self.value_dtype).reshape(-1, self.dim)
       self.upsert(torch.from_numpy(keys).to(self._primary), vals.to(self._primary))
     for f, base in slots.items():   # re-sharded restore of the state vectors: through the same partitioner
       for fn in slot_files(base):
-        keys = torch.from_numpy(np.fromfile(os.path.join(dirpath, fn + "-keys"), dtype=np.int64)).to(self._primary)
+        keys = torch.from_numpy(np.fromfile(os.path.join(dirpath, fn + "-keys"), dtype=key_np)).to(self._primary)
         vals = torch.from_numpy(np.fromfile(os.path.join(dirpath, fn + "-values"), dtype=np.uint8)).view(
             self.value_dtype).reshape(-1, self.dim).to(self._primary)
         kp, perm, counts = self._partition(keys)
@@ -583,7 +584,7 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=
   w = sp_weights if sp_weights is None else torch.as_tensor(sp_weights, dtype=torch.float32, device=params._primary)
   n = int(seg.max().item()) + 1 if num_rows is None else num_rows
   if return_trainable:
-    e_ids, e_seg, e_w = _entries if _entries is not None else (ids.reshape(-1).to(torch.int64), seg, w)
+    e_ids, e_seg, e_w = _entries if _entries is not None else (ids.reshape(-1), seg, w)   # ids keep their key dtype
     tw = SparseTrainableWrapper(params, uniq.reshape(-1), idx, cnt, seg, w, combiner, n,
                                 _out_shape if _out_shape is not None else (n, params.dim), e_ids, e_seg, e_w,
                                 max_norm=max_norm, plan_writeback=plan_writeback)
@@ -652,8 +653,8 @@ def safe_embedding_lookup_sparse(params, sp_ids, sparse_weights=None, combiner="
     has[rows] = True
     er = torch.nonzero(~has).reshape(-1)
     all_rows = torch.cat([rows.to(torch.int64), er])
-    all_ids = torch.cat([ids.reshape(-1).to(torch.int64),
-                         torch.full_like(er, 0 if default_id is None else int(default_id))])
+    all_ids = torch.cat([ids.reshape(-1),
+                         torch.full(er.shape, 0 if default_id is None else int(default_id), dtype=ids.dtype, device=er.device)])
     ew = 0.0 if default_id is None else 1.0
     all_w = torch.cat([torch.ones(rows.numel(), dtype=torch.float32, device=er.device) if w is None else w,
                        torch.full((er.numel(),), ew, dtype=torch.float32, device=er.device)])
@@ -668,7 +669,7 @@ def safe_embedding_lookup_sparse(params, sp_ids, sparse_weights=None, combiner="
   if default_id is not None and n:
     empty = torch.ones(n, dtype=torch.bool, device=res.device)
     empty[rows] = False
-    d = embedding_lookup(params, torch.tensor([default_id], dtype=torch.int64, device=params._primary),
+    d = embedding_lookup(params, torch.tensor([default_id], dtype=params.key_dtype, device=params._primary),
                          max_norm=max_norm).to(torch.float32)
     res = torch.where(empty[:, None], d, res)
   if lead is not None:

@@ -22,7 +22,8 @@ DIM = 6
 
 
 class _CpuOps:
-  """numpy stand-ins with the signatures of tfra_amd.dynamic_embedding.device_ops."""
+  """numpy stand-ins with the signatures of tfra_amd.dynamic_embedding.device_ops (keys come back in the dtype of the ids, as
+  the device ops return them)."""
 
   def __init__(self, use_reduce=True):
     self.use_reduce = use_reduce
@@ -33,17 +34,18 @@ class _CpuOps:
     n_all = k.size
     if n_dev is not None:
       k = k[:int(n_dev)]
-    owner = ofe.default_partition_fn(k, world, gpu_mode=(mode == 0))
+    # mode 0 = mask-mod (the CUDA-build rule for int64 keys) whatever the key dtype, 1 = floor mod: as tfra_partition's modes
+    owner = ofe.default_partition_fn(k.astype(np.int64), world, gpu_mode=(mode == 0))
     perm = np.concatenate([np.nonzero(owner == r)[0] for r in range(world)]).astype(np.int32)
     counts = np.array([(owner == r).sum() for r in range(world)], dtype=np.int64)
-    pad = np.zeros(n_all - k.size, dtype=np.int64)     # the device op returns length-n buffers
+    pad = np.zeros(n_all - k.size, dtype=k.dtype)      # the device op returns length-n buffers
     return (torch.from_numpy(np.concatenate([k[perm], pad])), torch.from_numpy(np.concatenate([perm, pad.astype(np.int32)])),
             torch.from_numpy(counts))
 
   def unique_no_sync(self, ids):
     from oracle import frontends as ofe
     u, idx = ofe.unique(ids.numpy())
-    buf = np.zeros(ids.numel(), dtype=np.int64)
+    buf = np.zeros(ids.numel(), dtype=ids.numpy().dtype)
     buf[:u.size] = u
     return torch.from_numpy(buf), torch.from_numpy(idx.astype(np.int32)), torch.tensor(u.size, dtype=torch.int64)
 
@@ -63,7 +65,7 @@ class _CpuOps:
     u, g, _ = oopt.segment_sum_by_key(ids.numpy().reshape(-1), grads.numpy())
     order = np.argsort(-u, kind="stable")
     n = ids.numel()
-    kb = np.zeros(n, dtype=np.int64); kb[:u.size] = u[order]
+    kb = np.zeros(n, dtype=ids.numpy().dtype); kb[:u.size] = u[order]
     gb = np.zeros((n, grads.shape[-1]), dtype=np.float32); gb[:u.size] = g[order]
     return torch.from_numpy(kb), torch.from_numpy(gb), torch.tensor(u.size, dtype=torch.int64)
 
@@ -267,3 +269,99 @@ def test_routed_assign_step_world2_equals_one_table():
   np.testing.assert_array_equal(gv[o], ev)
   for r in range(world):
     assert np.all(ofe.default_partition_fn(res[r][1], world) == r)
+
+
+# ---- int32 keys: the route's default partition rule follows the key dtype ------------------------------------------------------
+I32 = np.iinfo(np.int32)
+
+
+def _i32_keys():
+  """INT32_MIN, INT32_MAX, -1, 0, a dense run of negative keys and random keys over the whole int32 range."""
+  rng = np.random.default_rng(77)
+  k = np.concatenate([[I32.min, I32.max, -1, 0, I32.min + 1, I32.max - 1], np.arange(-600, 0),
+                      rng.integers(I32.min, I32.max, size=400, endpoint=True)]).astype(np.int32)
+  return np.unique(k)
+
+
+def _i32_ids(rank):
+  rng = np.random.default_rng(300 + rank)
+  miss = np.array([-100000 - rank, 123456789], np.int32)
+  return rng.choice(np.concatenate([_i32_keys(), miss]), size=(7, 41 + 13 * rank)).astype(np.int32)
+
+
+class _I32Shard(_OracleShard):
+  """An int32-key shard: the route must hand it int32 ids, and take its key dtype for the partition rule."""
+  key_dtype = torch.int32
+
+  def lookup(self, ids):
+    assert ids.dtype == torch.int32, ids.dtype
+    return super().lookup(ids)
+
+
+def _i32_worker(rank, world, port, q):
+  os.environ["MASTER_ADDR"] = "127.0.0.1"
+  os.environ["MASTER_PORT"] = str(port)
+  dist.init_process_group("gloo", rank=rank, world_size=world)
+  from tfra_amd.dynamic_embedding.distributed import AllToAllEmbedding
+  shard = _I32Shard(DIM)
+  keys = _i32_keys()
+  mine = keys[np.mod(keys, world) == rank]          # the reference's rule for int32 keys: math_ops.mod, floor mod
+  shard.t.insert(mine.astype(np.int64), np.tile(mine[:, None].astype(np.float32), (1, DIM)))
+  emb = AllToAllEmbedding(shard, ops=_CpuOps())     # partition_mode left at its default
+  ids = torch.from_numpy(_i32_ids(rank))
+  out = emb.lookup(ids)
+  emb.apply_gradients(_SgdOpt(0.1), torch.from_numpy(_grads(rank, ids.numel())))
+  dist.barrier()
+  k, v = shard.t.export_sorted()
+  q.put((rank, emb.mode, out.numpy(), k, v))
+  dist.barrier()
+  dist.destroy_process_group()
+
+
+def test_alltoall_int32_keys_floor_mod_world3():
+  """AllToAllEmbedding over int32 keys at world 3 (negative keys: mask-mod and floor mod disagree): with partition_mode left at its
+  default every rank owns the keys with np.mod(k, 3) == rank (PY/dynamic_embedding_variable.py:191-196), the lookups equal ONE
+  oracle table, and the SGD write-back lands on the owner (the sum of every rank's gradients of a key)."""
+  import oracle
+  from oracle import optimizers as oopt
+  import socket
+  with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as so:   # a free port from the OS
+    so.bind(("127.0.0.1", 0))
+    port = so.getsockname()[1]
+  world = 3
+  ctx = mp.get_context("spawn")
+  q = ctx.Queue()
+  procs = [ctx.Process(target=_i32_worker, args=(r, world, port, q)) for r in range(world)]
+  for p in procs:
+    p.start()
+  res = {}
+  for _ in range(world):
+    r, mode, out, k, v = q.get(timeout=120)
+    res[r] = (mode, out, k, v)
+  for p in procs:
+    p.join(timeout=60)
+    assert p.exitcode == 0
+  keys = _i32_keys()
+  assert np.any((keys < 0) & (np.mod(keys, world) != ((keys.astype(np.int64) & 0x7FFFFFFF) % world)))   # the rules differ here
+  tab = oracle.CpuTable(DIM)
+  tab.insert(keys.astype(np.int64), np.tile(keys[:, None].astype(np.float32), (1, DIM)))
+  ids = [_i32_ids(r) for r in range(world)]
+  for r in range(world):
+    assert res[r][0] == 1                            # PARTITION_FLOOR_MOD
+    want = tab.find(ids[r].reshape(-1).astype(np.int64), np.full(DIM, -1.0, np.float32))
+    np.testing.assert_array_equal(res[r][1].reshape(-1, DIM), want, err_msg="rank %d" % r)
+  # the single-table write-back: per source, its repeats summed; at the owner, the sources in rank order
+  ks, gs = [], []
+  for src in range(world):
+    k_src, g_src, _ = oopt.segment_sum_by_key(ids[src].reshape(-1), _grads(src, ids[src].size))
+    ks.append(k_src); gs.append(g_src)
+  uniq, gsum, _ = oopt.segment_sum_by_key(np.concatenate(ks), np.concatenate(gs))
+  tab.insert(uniq, oopt.sgd(tab.find(uniq, np.full(DIM, -1.0, np.float32)), gsum, 0.1))
+  ek, ev = tab.export_sorted()
+  gk = np.concatenate([res[r][2] for r in range(world)])
+  gv = np.concatenate([res[r][3] for r in range(world)])
+  o = np.argsort(gk)
+  np.testing.assert_array_equal(gk[o], ek)           # every key on exactly one shard
+  np.testing.assert_allclose(gv[o], ev, rtol=1e-6, atol=1e-6)
+  for r in range(world):
+    assert np.all(np.mod(res[r][2], world) == r), "rank %d holds keys of another owner" % r
