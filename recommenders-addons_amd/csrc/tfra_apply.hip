@@ -1,0 +1,737 @@
+// GRADIENT HALF of a write-back whose ids may repeat (tfra_table_apply_planned, over a CSR plan of tfra_csr.hip): the hot sums,
+// then one fused optimizer update per unique key; the same sums written out instead (tfra_reduce_by_key, tfra_plan_reduce_to);
+// the one-call and the two-stream forms (tfra_table_apply_sparse, tfra_table_step_prefetch[_assign]).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/tfra_mi355x.h"
+#include "tfra_combine_device.h"
+#include "tfra_device.h"
+#include "tfra_host.h"
+#include "tfra_optim_device.h"
+#include "tfra_plan.h"
+#include "tfra_reduce_device.h"
+
+using namespace tfra;
+using namespace tfra::red;
+
+namespace {
+
+#ifndef TFRA_HOT_SUMS_HALVES
+#define TFRA_HOT_SUMS_HALVES 1   // hot_sums_kernel: 8 rows in flight, twice (0: 16 at once, the form of rounds 2-5; A/B)
+#endif
+
+// ---------------------------------------------------------------------------------------------
+// gradient half, kernel 1: one block per bin of 512 entries = 32 items of 16 entries, one 16-lane group per item.
+// Runs are item-aligned (csr_bucket_kernel pads every run to whole items), so an item belongs to exactly one run or to
+// none: the group loads its 16 entry words with one coalesced read, puts all 16 gradient rows in flight at once
+// (unconditional loads, padding clamped to the item's first row), adds them in entry order, and the group holding the
+// run's first item then adds the sums of the run's following items in item order (LDS) and writes the partial row.
+// CS = CombRows (tfra_table_apply_planned_combined): the gradient of position e is formed from grads = grad_out and the entry's
+// record (tfra_combine_device.h) — each lane loads the record of its own entry, the group shares it by shuffles; none: grads[e].
+template <class... CS>
+__device__ __forceinline__ const CombEnt* comb_ent(const CS&... cs) {
+  const CombEnt* p = nullptr;
+  ((p = cs.ent), ...);
+  return p;
+}
+
+template <int NCH, class... CS>
+__global__ __launch_bounds__(NTA) void hot_sums_kernel(const float* __restrict__ grads, int dim,
+                                                       const unsigned* __restrict__ hent, const unsigned* __restrict__ hout,
+                                                       const unsigned* __restrict__ binmap,
+                                                       const unsigned* __restrict__ d_counts, float* __restrict__ partial,
+                                                       unsigned* progress, unsigned progress_val, const CS... cs) {
+  constexpr bool COMB = sizeof...(CS) > 0;
+  constexpr int NG = NTA / 16;
+  __shared__ float s_sum[NG][64];
+  __shared__ unsigned char s_kind[NG + 1];   // 0 = item continues the run of the item before, 1 = first item of a run, 2 = empty item
+  // tfra_table_step_prefetch: host-visible progress counter (pinned memory) — this kernel running means the
+  // lookup of step `progress_val` and every earlier step of the main stream are complete
+  if (progress && blockIdx.x == 0 && threadIdx.x == 0)
+    __hip_atomic_store(progress, progress_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48, g = threadIdx.x >> 4;
+  const unsigned nbins = d_counts[3];
+  for (unsigned ib = blockIdx.x; ib < nbins; ib += gridDim.x) {
+    const unsigned bin = binmap[ib];
+    const unsigned e = hent[(size_t)bin * SEG + threadIdx.x];          // lane `sub` holds entry `sub` of the item
+    const unsigned e0 = (unsigned)__shfl((int)e, gshift);
+    const bool empty = (e0 & E_SKIP) != 0, first = (e0 & E_HEAD) != 0;
+    const unsigned out_row = (first && !empty && sub == 0) ? hout[(size_t)bin * 32 + g] : 0u;
+    const unsigned live = (unsigned)(__ballot(!(e & E_SKIP)) >> gshift) & 0xffffu;   // entries of the item that exist
+    if (sub == 0) s_kind[g] = empty ? 2 : (first ? 1 : 0);
+    if (threadIdx.x == 0) s_kind[NG] = 1;
+    unsigned rows[16];   // element offset of each row (< 2^18 * 256)
+    float cden = 0.f, cw = 0.f;   // COMB: denominator and weight of this lane's entry
+    if constexpr (COMB) {
+      const CombEnt ce = comb_ent(cs...)[((e & E_SKIP) ? e0 : e) & E_POS];   // (padding: the item's first row, as below)
+      cden = ce.den;
+      cw = ce.w;
+#pragma unroll
+      for (int j = 0; j < 16; ++j) rows[j] = (unsigned)__shfl((int)ce.row, gshift + j) * (unsigned)dim;
+    } else {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const unsigned ej = (unsigned)__shfl((int)e, gshift + j);
+      rows[j] = (((live >> j) & 1u) ? (ej & E_POS) : (e0 & E_POS)) * (unsigned)dim;
+    }
+    }
+    for (int k = 0; k < NCH; ++k) {
+      const int col = k * 64 + sub * 4;
+      const int cc = col < dim ? col : 0;
+      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (TFRA_HOT_SUMS_HALVES && NCH == 1) {   // (rows of more than 64 floats keep 16 in flight: their kernels are at 122-128 registers either way)
+      // 8 rows in flight, twice, instead of 16 at once: 76 registers instead of 106 => 6 waves per SIMD instead of 4 => the ~680 bins of
+      // a Zipf batch (512-thread blocks) are resident in ONE round instead of two; the second batch of loads costs a trip, the second round
+      // cost more: 10.0 -> 9.2 us under rocprofv3, configs[1]'s step 56.7-57.3 -> 55.6-55.7 us (A/B on one box, twice).  Same adds, same order.
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        float4 x[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = *reinterpret_cast<const float4*>(grads + rows[h * 8 + j] + cc);
+        keep_live(x[0], x[1], x[2], x[3]); keep_live(x[4], x[5], x[6], x[7]);
+        if constexpr (COMB) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) x[j] = comb_grad4(x[j], __shfl(cden, gshift + h * 8 + j), __shfl(cw, gshift + h * 8 + j));
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if ((live >> (h * 8 + j)) & 1u) { acc.x += x[j].x; acc.y += x[j].y; acc.z += x[j].z; acc.w += x[j].w; }
+      }
+      } else {
+      float4 x[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) x[j] = *reinterpret_cast<const float4*>(grads + rows[j] + cc);   // 16 rows in flight
+      keep_live(x[0], x[1], x[2], x[3]); keep_live(x[4], x[5], x[6], x[7]);
+      keep_live(x[8], x[9], x[10], x[11]); keep_live(x[12], x[13], x[14], x[15]);
+      if constexpr (COMB) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) x[j] = comb_grad4(x[j], __shfl(cden, gshift + j), __shfl(cw, gshift + j));
+      }
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+        if ((live >> j) & 1u) { acc.x += x[j].x; acc.y += x[j].y; acc.z += x[j].z; acc.w += x[j].w; }
+      }
+      if (k) __syncthreads();   // the owners of the previous chunk have read s_sum
+      *reinterpret_cast<float4*>(&s_sum[g][sub * 4]) = acc;
+      __syncthreads();
+      if (first && !empty) {
+        for (int g2 = g + 1; s_kind[g2] == 0; ++g2) {
+          const float4 y = *reinterpret_cast<const float4*>(&s_sum[g2][sub * 4]);
+          acc.x += y.x; acc.y += y.y; acc.z += y.z; acc.w += y.w;
+        }
+        const unsigned orow = (unsigned)__shfl((int)out_row, gshift);
+        if (col < dim) *reinterpret_cast<float4*>(partial + (size_t)orow * dim + col) = acc;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// The source rows of a key's sum, NB of them in flight: rows j0 .. j0+NB-1 of its list (clamped to the last one; loads issued
+// together, adds in list order).  A key with few occurrences lists their batch positions in words 4.. of its record (lane i
+// of the group holds word i: EVERY lane of the group must be here); a key with many lists consecutive rows of the partial
+// sums.  The addresses are formed here, from the record word, not kept in an array across the kernel: with 8 pointers and
+// 8 rows held per lane the update kernel needed 145 registers (3 waves per SIMD); this form needs 125 (Adam) / 109 (SGD).
+// COMB (combined write-back): lanes 4.. of a key with few occurrences hold grad_out rows instead of batch positions, and the
+// denominator / weight of their entry in cden / cw; each gradient row is scaled by comb_grad4 before it is added.
+template <int NB, bool COMB = false>
+__device__ __forceinline__ void add_rows(float4& acc, const float* __restrict__ grads, const float* __restrict__ partial, bool hot,
+                                         unsigned w, unsigned first, unsigned nsrc, unsigned j0, int dim, int c, int gshift,
+                                         float cden = 0.f, float cw = 0.f) {
+  float4 x[NB];
+#pragma unroll
+  for (int j = 0; j < NB; ++j) {
+    const unsigned jj = min(j0 + (unsigned)j, nsrc - 1);
+    const unsigned position = (unsigned)__shfl((int)w, gshift + 4 + (int)min(jj, 7u));
+    const float* q = hot ? partial + (size_t)(first + jj) * dim : grads + (size_t)position * dim;
+    x[j] = *reinterpret_cast<const float4*>(q + c);
+  }
+  if (NB == 4) keep_live(x[0], x[1], x[2], x[3]);
+  if (COMB && !hot) {
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      const int src = gshift + 4 + (int)min(min(j0 + (unsigned)j, nsrc - 1), 7u);
+      x[j] = comb_grad4(x[j], __shfl(cden, src), __shfl(cw, src));
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NB; ++j)
+    if (j0 + (unsigned)j < nsrc) { acc.x += x[j].x; acc.y += x[j].y; acc.z += x[j].z; acc.w += x[j].w; }
+}
+
+// the whole sum of a key; wmax = the largest list length (capped at 8) among the wave's four keys: the trip count of the
+// common part is uniform across the wave, the few keys with more than 8 partial rows go on alone
+template <bool COMB = false>
+__device__ __forceinline__ float4 sum_rows(const float* __restrict__ grads, const float* __restrict__ partial, bool hot, unsigned w,
+                                           unsigned first, unsigned nsrc, unsigned wmax, int dim, int c, int gshift,
+                                           float cden = 0.f, float cw = 0.f) {
+  float4 gg = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (wmax <= 1) add_rows<1, COMB>(gg, grads, partial, hot, w, first, nsrc, 0, dim, c, gshift, cden, cw);
+  else if (wmax <= 2) add_rows<2, COMB>(gg, grads, partial, hot, w, first, nsrc, 0, dim, c, gshift, cden, cw);
+  else {
+    add_rows<4, COMB>(gg, grads, partial, hot, w, first, nsrc, 0, dim, c, gshift, cden, cw);
+    if (wmax > 4) add_rows<4, COMB>(gg, grads, partial, hot, w, first, nsrc, 4, dim, c, gshift, cden, cw);
+  }
+  for (unsigned j0 = 8; j0 < nsrc; j0 += 4) add_rows<4, COMB>(gg, grads, partial, hot, w, first, nsrc, j0, dim, c, gshift, cden, cw);
+  return gg;
+}
+
+// ---------------------------------------------------------------------------------------------
+// gradient half, kernel 2: one 16-lane group per unique key, hot keys first (their partial lists are the longest
+// chains of the kernel: started first, they finish inside the kernel's duration).
+// PHASE2: bounded (Hkv) table at max_capacity — the keys flagged in `dflag` (no free slot in phase 1; one byte per key:
+// a list appended through ONE atomic counter cost 4 ns per key, 260 us for a batch of new keys) replace the minimum-score
+// entry of their two home buckets and start from the default row / initial slot values, exactly like
+// apply_evict_kernel (tfra_optim.hip).
+// (Tried: amdgpu_waves_per_eu(4) on the 145-register form — 128 VGPRs with 7 spilled: gradient half 32.5 us instead of 31.5.
+// Without the pointer arrays — add_rows — it is 125 registers, 4 waves per SIMD, no spills: 28.7 us, step 57.2 instead of 59.9 us.
+// Round 4: amdgpu_waves_per_eu(5, 5) on that form — 96 registers, 18 spilled for Adam: gradient half 28.7 -> 37.3 us, the step of
+// configs[1] 55.4 -> 62.3 us (A/B on one box, twice).  Five waves need a kernel that NEEDS 96 registers, not one that spills to them.)
+// CS = CombRows: the combined write-back (see hot_sums_kernel).
+template <int KIND, bool PHASE2, class... CS>
+__global__ __launch_bounds__(256) void apply_csr_kernel(TableView v, OptP o, int dim, const float* __restrict__ grads,
+                                                        const float* __restrict__ partial, CsrKeys ks,
+                                                        const float* __restrict__ default_row, float aux0, float aux1,
+                                                        ScoreP sp, uint8_t* __restrict__ dflag, unsigned* any_deferred,
+                                                        unsigned use_gen, const CS... cs) {
+  constexpr bool COMB = sizeof...(CS) > 0;
+  if (PHASE2 && *any_deferred != use_gen) return;   // phase 1 of this use deferred nothing
+  constexpr int S = NSlots<KIND>::v;
+  const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
+  const unsigned total = ks.d_counts[0] + ks.d_counts[1];
+  const unsigned ngroups = (gridDim.x * blockDim.x) >> 4;
+  int fresh = 0, failed = 0;
+  if (o.d_lr) o.lr = *o.d_lr;
+  if (!PHASE2 && blockIdx.x == 0 && threadIdx.x == 0 && ks.d_counts[5]) atomicAdd(v.err_count, ks.d_counts[5]);  // plan overflow
+  // trips are uniform per wave (the batch width below is a wave-wide maximum): a group past the end re-reads the
+  // last key's records and does nothing else
+  for (unsigned wbase = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) << 2; wbase < total; wbase += ngroups) {
+    const unsigned it_raw = wbase + (unsigned)(lane >> 4);
+    const bool active = it_raw < total;
+    const unsigned g = active ? it_raw : total - 1;
+    if (PHASE2 && !__builtin_amdgcn_readfirstlane((int)(__ballot(active && dflag[g]) != 0))) continue;   // nothing deferred in this wave
+    // two chains in flight: key -> first probe line, and keymap -> record -> source rows
+    const i64 key = ks.dkeys[g];
+    u64 h;
+    const u64 b0 = bucket0(key, v.nb, h);
+    i64 k0 = 0;
+    if (!PHASE2) k0 = load_key_coherent(key_line(v, b0) + sub);
+    bool hot;
+    const unsigned w = load_record(ks, g, sub, hot);
+    const unsigned cnt = (unsigned)__shfl((int)w, gshift + 2);
+    const unsigned first = (unsigned)__shfl((int)w, gshift + 3);             // keys with many occurrences: first partial row
+    const unsigned nsrc = hot ? (unsigned)__shfl((int)w, gshift + 4) : cnt;
+    // COMB: lane 4 + j of a key with few occurrences swaps batch position j for that entry's grad_out row (+ denominator, weight)
+    unsigned wsrc = w;
+    float cden = 0.f, cw = 0.f;
+    if constexpr (COMB) {
+      if (!hot && sub >= 4 && (unsigned)(sub - 4) < cnt) {
+        const CombEnt ce = comb_ent(cs...)[w];
+        wsrc = ce.row; cden = ce.den; cw = ce.w;
+      }
+    }
+    // wave-uniform batch width: 1 / 2 / 4 rows in flight (most keys of a Zipf batch occur once)
+    unsigned wmax = min(nsrc, 8u);
+    for (int o2 = 32; o2 >= 16; o2 >>= 1) wmax = max(wmax, (unsigned)__shfl_xor((int)wmax, o2));
+    wmax = (unsigned)__builtin_amdgcn_readfirstlane((int)wmax);
+    if (!active || (PHASE2 && !dflag[g])) continue;
+    i64 row;
+    bool is_new = false;
+    u64 word = 0;
+    bool claimed_empty = false;
+    if (PHASE2) {
+      const bool lru_like = sp.strategy == TFRA_EVICT_LRU || sp.strategy == TFRA_EVICT_EPOCHLRU;
+      const u64 in_score = sp.strategy == TFRA_EVICT_EPOCHLFU ? ((sp.epoch << 32) | 1) : 1;
+      row = evict_and_lock(v, key, in_score, lru_like, sub, gshift, &word, claimed_empty);
+      is_new = true;
+    } else {
+      row = locate_or_claim_from(v, key, h, b0, k0, sub, gshift, is_new, sp.bounded);
+      if (sp.bounded && sub == 0) {
+        dflag[g] = row == NEED_EVICT;
+        if (row == NEED_EVICT) *any_deferred = use_gen;
+      }
+    }
+    if (row < 0) {
+      failed += (sub == 0 && (PHASE2 ? row == -3 : row != NEED_EVICT));
+      continue;
+    }
+    fresh += ((PHASE2 ? claimed_empty : is_new) && sub == 0);
+    float* pr = reinterpret_cast<float*>(row_ptr(v, row));
+    // (every lane of the group takes every trip — sum_rows reads the record words of the other lanes; a lane beyond the row
+    // works on column 0 and stores nothing)
+    for (int c0 = 0; c0 < dim; c0 += 64) {
+      const bool col = c0 + sub * 4 < dim;
+      const int c = col ? c0 + sub * 4 : 0;
+      float4 p = *reinterpret_cast<const float4*>((is_new ? default_row : pr) + c);
+      float4 s1 = *reinterpret_cast<const float4*>(pr + (S >= 1 ? dim : 0) + c);
+      float4 s2 = *reinterpret_cast<const float4*>(pr + (S >= 2 ? 2 * dim : 0) + c);
+      float4 gg = sum_rows<COMB>(grads, partial, hot, COMB ? wsrc : w, first, nsrc, wmax, dim, c, gshift, cden, cw);
+      float4 dummy = p;
+      keep_live(dummy, p, s1, s2);
+      if (is_new || S < 1) s1 = make_float4(aux0, aux0, aux0, aux0);
+      if (is_new || S < 2) s2 = make_float4(aux1, aux1, aux1, aux1);
+      apply_one<KIND>(o, gg.x, p.x, s1.x, s2.x);
+      apply_one<KIND>(o, gg.y, p.y, s1.y, s2.y);
+      apply_one<KIND>(o, gg.z, p.z, s1.z, s2.z);
+      apply_one<KIND>(o, gg.w, p.w, s1.w, s2.w);
+      // write-through: the rows leave L2 during the kernel, not at the boundary to the next one
+      if (col) {
+        store_wt16(pr + c, *reinterpret_cast<uint4*>(&p));
+        if (S >= 1) store_wt16(pr + dim + c, *reinterpret_cast<uint4*>(&s1));
+        if (S >= 2) store_wt16(pr + 2 * dim + c, *reinterpret_cast<uint4*>(&s2));
+      }
+    }
+    // aux fields the optimizer does not own (table created with more slots than it uses)
+    if (is_new && (int)v.n_fields - 1 > S) {
+      for (int f = S + 1; f < (int)v.n_fields; ++f)
+        for (int c = sub; c < dim; c += 16)
+          __hip_atomic_store(pr + f * dim + c, (f == 1 ? aux0 : aux1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (PHASE2) {
+      if (sub == 0) store_wt8(score_word(v, word), 0);  // the slot starts a new life
+      update_score<true>(v, row, true, sp.strategy, 1, sp.epoch, sub);
+      publish_key(v, word, key, sub);
+    } else {
+      update_score(v, row, is_new, sp.strategy, 1, sp.epoch, sub);  // one write-back = one upsert
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) { fresh += __shfl_xor(fresh, off); failed += __shfl_xor(failed, off); }
+  if (lane == 0) {
+    if (fresh) size_add(v, (blockIdx.x * blockDim.x + threadIdx.x) >> 6, fresh);
+    if (failed) atomicAdd(v.err_count, (unsigned)failed);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// tfra_reduce_by_key epilogue: the same per-key sums as apply_csr_kernel, written out instead of applied.
+// dest != nullptr (tfra_plan_reduce_to): the sum of a key goes to row dest[p], p = the key's last batch position — the
+// caller's map from batch positions to output rows (equal for all positions of a key), e.g. position -> owner-major
+// index of the multi-GPU gradient route; keys_out / d_count are not written then.
+__global__ __launch_bounds__(256) void gather_csr_kernel(int dim, const float* __restrict__ grads,
+                                                         const float* __restrict__ partial, CsrKeys ks,
+                                                         i64* __restrict__ keys_out, float* __restrict__ rows_out,
+                                                         i64* __restrict__ d_count, const int* __restrict__ dest) {
+  const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
+  const unsigned total = ks.d_counts[0] + ks.d_counts[1];
+  const unsigned ngroups = (gridDim.x * blockDim.x) >> 4;
+  if (d_count && blockIdx.x == 0 && threadIdx.x == 0) *d_count = ks.d_counts[5] ? (i64)-1 : (i64)total;
+  for (unsigned wbase = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) << 2; wbase < total; wbase += ngroups) {
+    const unsigned it_raw = wbase + (unsigned)(lane >> 4);
+    const bool active = it_raw < total;
+    const unsigned g = active ? it_raw : total - 1;
+    bool hot;
+    const unsigned w = load_record(ks, g, sub, hot);
+    const i64 key = (i64)(((u64)(unsigned)__shfl((int)w, gshift + 1) << 32) | (unsigned)__shfl((int)w, gshift));
+    const unsigned cnt = (unsigned)__shfl((int)w, gshift + 2);
+    const unsigned first = (unsigned)__shfl((int)w, gshift + 3);
+    const unsigned nsrc = hot ? (unsigned)__shfl((int)w, gshift + 4) : cnt;
+    unsigned wmax = min(nsrc, 8u);
+    for (int o2 = 32; o2 >= 16; o2 >>= 1) wmax = max(wmax, (unsigned)__shfl_xor((int)wmax, o2));
+    wmax = (unsigned)__builtin_amdgcn_readfirstlane((int)wmax);
+    if (!active) continue;
+    size_t orow = g;
+    if (dest) {
+      unsigned lastp = (unsigned)__shfl((int)w, gshift + (hot ? 5 : 3));   // few: the last position itself; many: where it is stored
+      if (hot) lastp = ks.hent[lastp];
+      orow = (size_t)dest[lastp & E_POS];
+    }
+    for (int c0 = 0; c0 < dim; c0 += 64) {   // (every lane takes every trip: see apply_csr_kernel)
+      const bool col = c0 + sub * 4 < dim;
+      const int c = col ? c0 + sub * 4 : 0;
+      const float4 gg = sum_rows(grads, partial, hot, w, first, nsrc, wmax, dim, c, gshift);
+      if (col) *reinterpret_cast<float4*>(rows_out + orow * dim + c) = gg;
+    }
+    if (keys_out && sub == 0) keys_out[g] = key;
+  }
+}
+
+}  // namespace
+
+template <int KIND, class... CS>
+static void launch_apply_csr(Table* t, hipStream_t s, const tfra_sparse_plan* pl, const OptP& o, const float* grads,
+                             const float* default_row, unsigned key_blocks, const ScoreP& sp, const CS&... cs) {
+  TableView v = t->view_of(t->cur);
+  const float a0 = t->opts.aux_init[0], a1 = t->opts.aux_init[1];
+  const unsigned gen = ++pl->use_gen;
+  // one RESIDENT grid (the kernel is grid-stride: 125 registers = 4 blocks per CU x 256 CUs): a batch's 33 K keys as 2075 blocks were two
+  // rounds of dispatch plus a third of 27 blocks; 1024 blocks looping twice: configs[1] 55.2 -> 53.7 us per step (A/B on one box, twice)
+  static const unsigned grid_cap = [] { const char* e = getenv("TFRA_APPLY_GRID_CAP"); return e ? (unsigned)atoi(e) : 1024u; }();
+  if (grid_cap) key_blocks = std::min(key_blocks, grid_cap);
+  apply_csr_kernel<KIND, false><<<key_blocks, 256, 0, s>>>(v, o, pl->dim, grads, pl->partial, keys_of(pl), default_row, a0, a1, sp,
+                                                           pl->dflag, pl->any_deferred, gen, cs...);
+  if (sp.bounded)
+    apply_csr_kernel<KIND, true><<<key_blocks, 256, 0, s>>>(v, o, pl->dim, grads, pl->partial, keys_of(pl), default_row, a0, a1, sp,
+                                                            pl->dflag, pl->any_deferred, gen, cs...);
+}
+
+template <class... CS>
+static void launch_hot_sums(hipStream_t s, const tfra_sparse_plan* pl, const float* grads, unsigned bin_blocks, unsigned* progress,
+                            unsigned progress_val, const CS&... cs) {
+  const int dim = pl->dim;
+  switch ((dim + 63) / 64) {
+    case 1: hot_sums_kernel<1><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, progress, progress_val, cs...); break;
+    case 2: hot_sums_kernel<2><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, progress, progress_val, cs...); break;
+    case 3: hot_sums_kernel<3><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, progress, progress_val, cs...); break;
+    default: hot_sums_kernel<4><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, progress, progress_val, cs...); break;
+  }
+}
+
+template <class... CS>
+static void launch_apply(Table* t, hipStream_t s, const tfra_sparse_plan* pl, int kind, const OptP& o, const float* grads,
+                         const float* default_row, unsigned key_blocks, const ScoreP& sp, const CS&... cs) {
+  switch (kind) {
+    case TFRA_OPT_SGD: launch_apply_csr<TFRA_OPT_SGD>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
+    case TFRA_OPT_ADAM: launch_apply_csr<TFRA_OPT_ADAM>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
+    case TFRA_OPT_ADAGRAD: launch_apply_csr<TFRA_OPT_ADAGRAD>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
+    default: launch_apply_csr<TFRA_OPT_FTRL>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
+  }
+}
+
+// comb != nullptr (tfra_table_apply_planned_combined): grads is grad_out, position e's gradient is formed from comb[e]
+int tfra::apply_planned_impl(tfra_table_t* tp, const tfra_opt_params* p, const tfra_sparse_plan_t* pl, const float* grads,
+                              const float* param_default_row, tfra_stream_t stream, unsigned* progress, unsigned progress_val,
+                             const CombEnt* comb) {
+  // caller holds t->mu
+  Table* t = reinterpret_cast<Table*>(tp);
+  if (!t || !p || !pl) return set_error(TFRA_ERR_INVALID, "apply_planned: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  int rc = t->enter(s);
+  if (rc) return rc;
+  if (pl->n == 0) return TFRA_OK;
+  if (!grads || !param_default_row) return set_error(TFRA_ERR_INVALID, "apply_planned: null buffer");
+  if (t->opts.value_dtype != TFRA_F32) return set_error(TFRA_ERR_UNSUPPORTED, "apply_planned: value_dtype must be float32");
+  if (p->kind < 0 || p->kind > TFRA_OPT_FTRL) return set_error(TFRA_ERR_INVALID, "apply_planned: unknown kind");
+  int need = p->kind == TFRA_OPT_SGD ? 0 : (p->kind == TFRA_OPT_ADAGRAD ? 1 : 2);
+  if (t->opts.aux_fields < need) return set_error(TFRA_ERR_INVALID, "apply_planned: table lacks optimizer slot fields");
+  if (t->opts.dim != pl->dim) return set_error(TFRA_ERR_INVALID, "apply_planned: the plan was built for another dim");
+  if (t->opts.device != pl->device && t->opts.device >= 0) return set_error(TFRA_ERR_INVALID, "apply_planned: plan and table live on different devices");
+  if ((((uintptr_t)grads | (uintptr_t)param_default_row) & 15))
+    return set_error(TFRA_ERR_UNSUPPORTED, "apply_planned: gradient / default buffers must be 16-B aligned");
+  rc = t->prepare_insert(pl->n, s);
+  if (rc) return rc;
+  unsigned key_blocks, bin_blocks;
+  plan_grids(pl, &key_blocks, &bin_blocks);
+  if (comb) launch_hot_sums(s, pl, grads, bin_blocks, progress, progress_val, CombRows{comb});
+  else launch_hot_sums(s, pl, grads, bin_blocks, progress, progress_val);
+  uint8_t* bounded_now;
+  rc = t->bounded_flags(1, s, &bounded_now);
+  if (rc) return rc;
+  const ScoreP sp{t->opts.strategy, t->global_epoch, bounded_now ? (t->dense ? 2 : 1) : 0};
+  OptP o{p->kind, p->lr, p->beta1, p->beta2, p->eps, p->l1, p->l2, p->lr_power, p->d_lr};
+  if (comb) launch_apply(t, s, pl, p->kind, o, grads, param_default_row, key_blocks, sp, CombRows{comb});
+  else launch_apply(t, s, pl, p->kind, o, grads, param_default_row, key_blocks, sp);
+  if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "apply_planned: launch failed");
+  step_epoch_public(t);
+  return TFRA_OK;
+}
+
+extern "C" int tfra_table_apply_planned(tfra_table_t* tp, const tfra_opt_params* p, const tfra_sparse_plan_t* pl,
+                                        const float* grads, const float* param_default_row, tfra_stream_t stream) {
+  Table* t = reinterpret_cast<Table*>(tp);
+  if (!t) return set_error(TFRA_ERR_INVALID, "apply_planned: null table");
+  std::lock_guard<std::mutex> lock(t->mu);
+  return apply_planned_impl(tp, p, pl, grads, param_default_row, stream, nullptr, 0);
+}
+
+// The write-back of an embedding_lookup_sparse: plan over the entry ids, gradient of position e = the combiner's backward
+// (tfra_combine_device.h) formed from grad_out in registers — apply_planned's kernels, reading grad_out through one more
+// indirection instead of an expanded [nnz, dim] gradient.
+extern "C" int tfra_table_apply_planned_combined(tfra_table_t* tp, const tfra_opt_params* p, const tfra_sparse_plan_t* pl,
+                                                 const float* grad_out, const int64_t* seg, const float* weights, int combiner,
+                                                 size_t n_rows, const float* param_default_row, tfra_stream_t stream) {
+  Table* t = reinterpret_cast<Table*>(tp);
+  if (!t || !p || !pl) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: null argument");
+  if (combiner < 0 || combiner > 2) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: combiner must be 0 (sum), 1 (mean) or 2 (sqrtn)");
+  std::lock_guard<std::mutex> lock(t->mu);
+  hipStream_t s = (hipStream_t)stream;
+  int rc = t->enter(s);   // the scratch below was last used on the table's previous stream
+  if (rc) return rc;
+  if (pl->kind != 0 || pl->dim != t->opts.dim) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: the plan was built for another dim");
+  if (t->opts.device != pl->device && t->opts.device >= 0) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: plan and table live on different devices");
+  const size_t nnz = pl->n;
+  if (nnz == 0) return TFRA_OK;
+  if (!grad_out || !seg || !param_default_row) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: null buffer");
+  if (n_rows == 0 || n_rows >= (1ULL << 30)) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: need 1 <= n_rows < 2^30");
+  if ((((uintptr_t)grad_out | (uintptr_t)param_default_row) & 15) || ((uintptr_t)seg & 7) || ((uintptr_t)weights & 3))
+    return set_error(TFRA_ERR_UNSUPPORTED, "apply_planned_combined: grad_out / default buffers must be 16-B aligned");
+  if (!t->comb_ws) {
+    tfra_workspace_t* w = nullptr;
+    rc = tfra_workspace_create(t->device, &w);
+    if (rc) return rc;
+    t->comb_ws = w;
+  }
+  tfra_workspace_t* ws = reinterpret_cast<tfra_workspace_t*>(t->comb_ws);
+  auto al = [](size_t x) { return (x + 255) / 256 * 256; };
+  const size_t se_b = al(2 * n_rows * sizeof(int)), den_b = al(n_rows * sizeof(float));
+  rc = ws->ensure(se_b + den_b + al(nnz * sizeof(CombEnt)), s);
+  if (rc) return rc;
+  unsigned char* b = (unsigned char*)ws->buf;
+  CombEnt* ent = reinterpret_cast<CombEnt*>(b + se_b + den_b);
+  rc = comb_entries(s, nnz, seg, weights, combiner, n_rows, reinterpret_cast<int*>(b), reinterpret_cast<float*>(b + se_b), ent);
+  if (rc) return rc;
+  return apply_planned_impl(tp, p, pl, grad_out, param_default_row, stream, nullptr, 0, ent);
+}
+
+// tfra_table_apply_sparse for more ids than a plan holds (2^18).  Equal ids must still meet in ONE update, whatever
+// chunk they sit in:
+//   1. per chunk of 2^18 ids: unique + per-key gradient sums (tfra_reduce_by_key) into one concatenated list — a key now
+//      occurs at most once per chunk, so even the hottest id of a Zipf batch is a handful of entries;
+//   2. the list fits a plan: one planned write-back sums a key's entries in chunk order and applies it;
+//      else the list is split by key hash (tfra_partition, mode 2) into parts that fit — a key's entries stay together,
+//      the parts are disjoint key sets — and each part is written back on its own.
+// A slow path (host reads of the counts, scratch allocated per call); results are deterministic, the association of the
+// sums is (within chunk) + (across chunks in order).
+static int apply_sparse_big(Table* t, tfra_table_t* tp, tfra_sparse_plan* pl, const tfra_opt_params* p, size_t n, const int64_t* ids,
+                            const float* grads, const float* param_default_row, tfra_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const int dim = t->opts.dim;
+  if (!t->big_ws) {
+    tfra_workspace_t* w = nullptr;
+    int rc = tfra_workspace_create(t->device, &w);
+    if (rc) return rc;
+    t->big_ws = w;
+  }
+  tfra_workspace_t* ws = reinterpret_cast<tfra_workspace_t*>(t->big_ws);
+  i64 *keys_cat = nullptr, *d_cnt = nullptr, *keys_part = nullptr, *d_counts = nullptr;
+  float *sums_cat = nullptr, *sums_part = nullptr;
+  int* perm = nullptr;
+  auto cleanup = [&](int rc) {
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(keys_cat); (void)hipFree(d_cnt); (void)hipFree(keys_part); (void)hipFree(d_counts); (void)hipFree(sums_cat);
+    (void)hipFree(sums_part); (void)hipFree(perm);
+    return rc;
+  };
+  auto oom = [&]() { return cleanup(set_error(TFRA_ERR_OOM, "apply_sparse: scratch for a batch of more than 2^18 ids")); };
+  if (hipMalloc((void**)&keys_cat, n * sizeof(i64)) != hipSuccess || hipMalloc((void**)&sums_cat, n * (size_t)dim * sizeof(float)) != hipSuccess ||
+      hipMalloc((void**)&d_cnt, sizeof(i64)) != hipSuccess)
+    return oom();
+  size_t T = 0;
+  for (size_t off = 0; off < n; off += MAX_IDS) {
+    const size_t m = std::min<size_t>(MAX_IDS, n - off);
+    int rc = tfra_reduce_by_key(ws, m, ids + off, dim, grads + off * (size_t)dim, (int64_t*)keys_cat + T, sums_cat + T * (size_t)dim,
+                                (int64_t*)d_cnt, stream);
+    if (rc) return cleanup(rc);
+    i64 c = 0;
+    if (hipMemcpyAsync(&c, d_cnt, sizeof(i64), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+      return cleanup(set_error(TFRA_ERR_HIP, "apply_sparse: count read"));
+    if (c < 0) return cleanup(set_error(TFRA_ERR_FULL, "apply_sparse: a de-duplication plan overflowed"));
+    T += (size_t)c;
+  }
+  if (T <= MAX_IDS) {
+    int rc = tfra_sparse_plan_build(pl, T, (const int64_t*)keys_cat, dim, stream);
+    if (!rc) rc = apply_planned_impl(tp, p, pl, sums_cat, param_default_row, stream, nullptr, 0);
+    return cleanup(rc);
+  }
+  if (hipMalloc((void**)&keys_part, T * sizeof(i64)) != hipSuccess || hipMalloc((void**)&perm, T * sizeof(int)) != hipSuccess ||
+      hipMalloc((void**)&sums_part, T * (size_t)dim * sizeof(float)) != hipSuccess)
+    return oom();
+  for (size_t P = (T + (MAX_IDS / 2) - 1) / (MAX_IDS / 2); P <= 2048; P *= 2) {
+    (void)hipFree(d_counts); d_counts = nullptr;
+    if (hipMalloc((void**)&d_counts, P * sizeof(i64)) != hipSuccess) return oom();
+    int rc = tfra_partition(ws, T, nullptr, (const int64_t*)keys_cat, (int)P, 2, (int64_t*)keys_part, perm, (int64_t*)d_counts, stream);
+    if (rc) return cleanup(rc);
+    std::vector<i64> counts(P);
+    if (hipMemcpyAsync(counts.data(), d_counts, P * sizeof(i64), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+      return cleanup(set_error(TFRA_ERR_HIP, "apply_sparse: count read"));
+    bool fits = true;
+    for (i64 c : counts) fits = fits && (size_t)c <= MAX_IDS;
+    if (!fits) continue;   // a part too large (skewed hash): more parts
+    rc = tfra_gather_rows(T, (size_t)dim * sizeof(float), sums_cat, perm, sums_part, stream);
+    if (rc) return cleanup(rc);
+    size_t off = 0;
+    // ONE logical write-back: the epoch / step counters of the EPOCH* strategies advance once, not once per part (the
+    // reference counts one upsert per write-back, lookup_table_op_hkv.h:528-536).  (On a bounded table at max_capacity a
+    // later part may still evict keys an earlier part of the same batch inserted.)
+    t->epoch_hold = true;
+    for (i64 c : counts) {
+      if (c > 0) {
+        rc = tfra_sparse_plan_build(pl, (size_t)c, (const int64_t*)keys_part + off, dim, stream);
+        if (!rc) rc = apply_planned_impl(tp, p, pl, sums_part + off * (size_t)dim, param_default_row, stream, nullptr, 0);
+        if (rc) { t->epoch_hold = false; return cleanup(rc); }
+      }
+      off += (size_t)c;
+    }
+    t->epoch_hold = false;
+    step_epoch_public(t);
+    return cleanup(TFRA_OK);
+  }
+  return cleanup(set_error(TFRA_ERR_UNSUPPORTED, "apply_sparse: could not split the batch into parts of 2^18 ids"));
+}
+
+extern "C" int tfra_table_apply_sparse(tfra_table_t* tp, const tfra_opt_params* p, size_t n, const int64_t* ids,
+                                       const float* grads, const float* param_default_row, tfra_stream_t stream) {
+  Table* t = reinterpret_cast<Table*>(tp);
+  if (!t || !p) return set_error(TFRA_ERR_INVALID, "apply_sparse: null argument");
+  if (n == 0) return TFRA_OK;
+  if (!ids || !grads || !param_default_row) return set_error(TFRA_ERR_INVALID, "apply_sparse: null buffer");
+  if (t->opts.value_dtype != TFRA_F32) return set_error(TFRA_ERR_UNSUPPORTED, "apply_sparse: value_dtype must be float32");
+  const int dim = t->opts.dim;
+  if (dim % 4 != 0 || dim > 64 * MAXCH || (((uintptr_t)grads | (uintptr_t)param_default_row) & 15))
+    return set_error(TFRA_ERR_UNSUPPORTED, "apply_sparse: needs dim % 4 == 0, dim <= 256 and 16-B aligned buffers "
+                                           "(use tfra_unique + tfra_segment_sum + tfra_table_apply_optimizer otherwise)");
+  tfra_sparse_plan* pl;
+  std::lock_guard<std::mutex> lock(t->mu);
+  int rc = t->enter((hipStream_t)stream);   // orders the rebuild of the table's own plan behind its previous use
+  if (rc) return rc;
+  rc = own_plan(t, &pl);
+  if (rc) return rc;
+  if (n > MAX_IDS) return apply_sparse_big(t, tp, pl, p, n, ids, grads, param_default_row, stream);
+  rc = tfra_sparse_plan_build(pl, n, ids, dim, stream);
+  if (rc) return rc;
+  return apply_planned_impl(tp, p, pl, grads, param_default_row, stream, nullptr, 0);
+}
+
+// unique + unsorted_segment_sum in one call = the plan + the hot sums + a gather (the reduction half of
+// tfra_table_apply_sparse with the same summation tree, so routing the sums elsewhere — multi-GPU gradient
+// alltoall — and applying them there gives the same bits as applying them here).
+extern "C" int tfra_reduce_by_key(tfra_workspace_t* ws, size_t n, const int64_t* ids, int dim, const float* grads,
+                                  int64_t* keys_out, float* rows_out, int64_t* d_count, tfra_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!ws || !d_count) return set_error(TFRA_ERR_INVALID, "reduce_by_key: null argument");
+  { int cur_ = -1; if (hipGetDevice(&cur_) != hipSuccess || cur_ != ws->device) { if (hipSetDevice(ws->device) != hipSuccess) return set_error(TFRA_ERR_HIP, "reduce_by_key: hipSetDevice"); } }
+  if (n == 0) {
+    if (hipMemsetAsync(d_count, 0, sizeof(int64_t), s) != hipSuccess) return set_error(TFRA_ERR_HIP, "reduce_by_key: memset");
+    return TFRA_OK;
+  }
+  if (!ids || !grads || !keys_out || !rows_out) return set_error(TFRA_ERR_INVALID, "reduce_by_key: null buffer");
+  if (dim <= 0 || dim % 4 != 0 || dim > 64 * MAXCH || (((uintptr_t)grads | (uintptr_t)rows_out) & 15))
+    return set_error(TFRA_ERR_UNSUPPORTED, "reduce_by_key: needs dim % 4 == 0, dim <= 256 and 16-B aligned buffers "
+                                           "(use tfra_unique + tfra_segment_sum otherwise)");
+  if (n > MAX_IDS) return set_error(TFRA_ERR_UNSUPPORTED, "reduce_by_key: at most 2^18 ids per call");
+  if (!ws->plan) {
+    tfra_sparse_plan* np_ = nullptr;
+    int rc = tfra_sparse_plan_create(ws->device, &np_);
+    if (rc) return rc;
+    ws->plan = np_;
+  }
+  tfra_sparse_plan* pl = reinterpret_cast<tfra_sparse_plan*>(ws->plan);
+  int rc = tfra_sparse_plan_build(pl, n, ids, dim, stream);
+  if (rc) return rc;
+  unsigned key_blocks, bin_blocks;
+  plan_grids(pl, &key_blocks, &bin_blocks);
+  launch_hot_sums(s, pl, grads, bin_blocks, nullptr, 0);   // (pl->dim == dim)
+  gather_csr_kernel<<<key_blocks, 256, 0, s>>>(dim, grads, pl->partial, keys_of(pl), (i64*)keys_out, rows_out, (i64*)d_count, nullptr);
+  if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "reduce_by_key: launch failed");
+  return TFRA_OK;
+}
+
+// The per-key gradient sums of a batch whose plan was built ahead (tfra_sparse_plan_build with the table's dim, on any
+// stream): hot sums + gather, the reduction half of tfra_reduce_by_key with the same summation tree, written to
+// rows_out[dest[p]] where p is a position of the key.  dest [n] int32: the caller's map from batch positions to output
+// rows, the same for every position of a key (e.g. position -> owner-major index of the multi-GPU gradient route, which
+// is known from the ids alone).  rows_out must have a row for every value in dest; rows no key maps to are not written.
+extern "C" int tfra_plan_reduce_to(const tfra_sparse_plan_t* pl, const float* grads, const int32_t* dest, float* rows_out,
+                                   tfra_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!pl) return set_error(TFRA_ERR_INVALID, "plan_reduce_to: null plan");
+  if (pl->kind == 1) return set_error(TFRA_ERR_UNSUPPORTED, "plan_reduce_to: needs a plan built with the table's dim");
+  if (pl->n == 0) return TFRA_OK;
+  if (!grads || !dest || !rows_out) return set_error(TFRA_ERR_INVALID, "plan_reduce_to: null buffer");
+  const int dim = pl->dim;
+  if (dim <= 0 || (((uintptr_t)grads | (uintptr_t)rows_out) & 15))
+    return set_error(TFRA_ERR_INVALID, "plan_reduce_to: the plan must have been built with the rows' dim; buffers 16-B aligned");
+  { int cur_ = -1; if (hipGetDevice(&cur_) != hipSuccess || cur_ != pl->device) { if (hipSetDevice(pl->device) != hipSuccess) return set_error(TFRA_ERR_HIP, "plan_reduce_to: hipSetDevice"); } }
+  unsigned key_blocks, bin_blocks;
+  plan_grids(pl, &key_blocks, &bin_blocks);
+  launch_hot_sums(s, pl, grads, bin_blocks, nullptr, 0);
+  gather_csr_kernel<<<key_blocks, 256, 0, s>>>(dim, grads, pl->partial, keys_of(pl), nullptr, rows_out, nullptr, (const int*)dest);
+  if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "plan_reduce_to: launch failed");
+  return TFRA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// One training step driven from C on two streams (no Python between the launches, no graph).
+//   main : lookup(ids_cur) -> write-back of batch cur (hot sums + fused update, or assign)      (plan_cur)
+//   side : build plan_next from ids_next, free-running
+// Cross-queue events cost ~5 us (stream wait) / ~7 us (record) each between two kernels of the main stream,
+// so the two streams are ordered through two host-visible counters in pinned memory instead, and the host
+// only falls back to a sync when a counter lags:
+//   * table progress: written by the first block of the write-back of step s  =>  every earlier step is done.
+//     plan_next's buffers were last read by step plan_next->last_used_step; the build is enqueued once the
+//     progress has passed it (with >= 3 plans in rotation that is always the case unless the host is far
+//     ahead of the GPU, in which case it waits here instead of in a queue);
+//   * plan built: generation + counts written by the build's last kernel.  If they already show plan_cur's
+//     generation the write-back is enqueued without any wait packet and with exact grids; otherwise — the host
+//     got ahead of the side stream — the host waits for the side stream.
+static int step_prefetch_impl(tfra_table_t* tp, const tfra_opt_params* p, tfra_sparse_plan_t* plan_cur,
+                              const int64_t* ids_cur, void* rows_out, const void* find_default, const void* grads_or_values,
+                              const float* param_default_row, const uint64_t* scores, tfra_sparse_plan_t* plan_next,
+                              const int64_t* ids_next, size_t n_next, tfra_stream_t main_stream, tfra_stream_t side_stream) {
+  Table* t = reinterpret_cast<Table*>(tp);
+  if (!t || !plan_cur) return set_error(TFRA_ERR_INVALID, "step_prefetch: null argument");
+  hipStream_t ms = (hipStream_t)main_stream, ss = (hipStream_t)side_stream;
+  if (ms == ss && plan_next) return set_error(TFRA_ERR_INVALID, "step_prefetch: needs two different streams");
+  if (plan_next == plan_cur) return set_error(TFRA_ERR_INVALID, "step_prefetch: plan_next must differ from plan_cur");
+  std::lock_guard<std::mutex> step_lock(t->step_mu);   // one driver call at a time per table
+  int rc = TFRA_OK;
+  if (!t->progress_host) {
+    if (hipHostMalloc((void**)&t->progress_host, 64, hipHostMallocDefault) != hipSuccess) { t->progress_host = nullptr; return set_error(TFRA_ERR_OOM, "step_prefetch: hipHostMalloc"); }
+    t->progress_host[0] = 0; t->progress_host[1] = 0;
+  }
+  const unsigned step = ++t->step_gen;
+  if (plan_next) {
+    if (!plan_next->host_counts) {
+      if (hipHostMalloc((void**)&plan_next->host_counts, 64, hipHostMallocDefault) != hipSuccess) { plan_next->host_counts = nullptr; return set_error(TFRA_ERR_OOM, "step_prefetch: hipHostMalloc"); }
+      for (int i = 0; i < 8; ++i) plan_next->host_counts[i] = 0;
+    }
+    if (plan_next->last_used_step) {  // the write-back that read plan_next's buffers must be over
+      const unsigned need = plan_next->last_used_step + 1;
+      volatile unsigned* prog = t->progress_host;
+      bool ok = false;
+      for (int it = 0; it < 200000 && !ok; ++it) ok = (int)(*prog - need) >= 0;   // ~ a few ms at most
+      if (!ok && hipStreamSynchronize(ms) != hipSuccess) return set_error(TFRA_ERR_HIP, "step_prefetch: sync");
+    }
+  }
+  if (plan_cur->n && rows_out) {
+    rc = tfra_table_find(tp, plan_cur->n, ids_cur, rows_out, nullptr, find_default, 0, main_stream);
+    if (rc) return rc;
+  }
+  if (plan_next) {
+    if (!p) plan_next->skip_counts_once = !(t->opts.strategy == TFRA_EVICT_LFU && !scores);   // (the next step's call passes scores or not like this one)
+    rc = tfra_sparse_plan_build(plan_next, n_next, ids_next, p ? t->opts.dim : 0, side_stream);
+    if (rc) return rc;
+    if (!plan_next->built_ev && hipEventCreateWithFlags(&plan_next->built_ev, hipEventDisableTiming) != hipSuccess) {
+      plan_next->built_ev = nullptr;
+      return set_error(TFRA_ERR_HIP, "step_prefetch: event");
+    }
+    if (hipEventRecord(plan_next->built_ev, ss) != hipSuccess) return set_error(TFRA_ERR_HIP, "step_prefetch: event record");
+    plan_next->ev_recorded = true;   // built on the side stream: the join below applies
+  }
+  if (plan_cur->ev_recorded) {  // built on the side stream by an earlier call
+    // complete = every block of the build has ended and its stores are in memory (the pinned counts alone do not say that)
+    if (hipEventQuery(plan_cur->built_ev) != hipSuccess && hipEventSynchronize(plan_cur->built_ev) != hipSuccess)   // the wait: rare
+      return set_error(TFRA_ERR_HIP, "step_prefetch: join");
+    plan_cur->ev_recorded = false;
+  }
+  plan_cur->last_used_step = step;
+  if (plan_cur->n == 0) return TFRA_OK;   // no kernel publishes this step: a later slot check falls back to a sync
+  std::lock_guard<std::mutex> lock(t->mu);
+  if (p) return apply_planned_impl(tp, p, plan_cur, (const float*)grads_or_values, param_default_row, main_stream, t->progress_host, step);
+  return upsert_planned_impl(tp, plan_cur, grads_or_values, scores, main_stream, t->progress_host, step);
+}
+
+extern "C" int tfra_table_step_prefetch(tfra_table_t* tp, const tfra_opt_params* p, tfra_sparse_plan_t* plan_cur,
+                                        const int64_t* ids_cur, void* rows_out, const void* find_default,
+                                        const float* grads, const float* param_default_row,
+                                        tfra_sparse_plan_t* plan_next, const int64_t* ids_next, size_t n_next,
+                                        tfra_stream_t main_stream, tfra_stream_t side_stream) {
+  if (!p) return set_error(TFRA_ERR_INVALID, "step_prefetch: null optimizer parameters");
+  return step_prefetch_impl(tp, p, plan_cur, ids_cur, rows_out, find_default, grads, param_default_row, nullptr, plan_next, ids_next,
+                            n_next, main_stream, side_stream);
+}
+
+extern "C" int tfra_table_step_prefetch_assign(tfra_table_t* tp, tfra_sparse_plan_t* plan_cur, const int64_t* ids_cur,
+                                               void* rows_out, const void* find_default, const void* values,
+                                               const uint64_t* scores, tfra_sparse_plan_t* plan_next,
+                                               const int64_t* ids_next, size_t n_next, tfra_stream_t main_stream,
+                                               tfra_stream_t side_stream) {
+  return step_prefetch_impl(tp, nullptr, plan_cur, ids_cur, rows_out, find_default, values, nullptr, scores, plan_next, ids_next,
+                            n_next, main_stream, side_stream);
+}

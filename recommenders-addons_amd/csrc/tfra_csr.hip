@@ -20,11 +20,11 @@
 //                            occurrences of a key fill one bin, the remainder (< 512, padded to 16) shares a bin
 //                            with other remainders, never straddling — and (key, first partial, #partials).
 //     csr_finish_kernel  publishes the counts, re-arms the cursors for the next build.
-//   GRADIENT HALF (tfra_table_apply_planned)
+//   GRADIENT HALF (tfra_table_apply_planned; tfra_apply.hip)
 //     hot_sums_kernel    one block per bin: 32 groups x 16 rows in flight, ordered add -> one partial row per run
 //     apply_csr_kernel   one 16-lane group per unique key (hot keys first): gathers its <= 8 gradient rows or
 //                        its partial rows IN ORDER, sums, locates/claims the table row, applies the optimizer.
-//   ASSIGN (tfra_table_upsert_planned): upsert_own_kernel (one pass with bucket ownership) + upsert_rest_kernel (the few
+//   ASSIGN (tfra_table_upsert_planned; tfra_own.hip): upsert_own_kernel (one pass with bucket ownership) + upsert_rest_kernel (the few
 //     keys that pass leaves over) copy the row of every key's LAST occurrence (no sums, any value dtype); the assign-only
 //     plan (setplan_kernel, dim 0) is one kernel: distinct ids with their last position.
 //
@@ -63,52 +63,13 @@
 #include "tfra_device.h"
 #include "tfra_host.h"
 #include "tfra_optim_device.h"
+#include "tfra_plan.h"
 #include "tfra_reduce_device.h"
 
 using namespace tfra;
 using namespace tfra::red;
 
 namespace {
-
-#ifndef TFRA_HOT_SUMS_HALVES
-#define TFRA_HOT_SUMS_HALVES 1   // hot_sums_kernel: 8 rows in flight, twice (0: 16 at once, the form of rounds 2-5; A/B)
-#endif
-constexpr int DIRECT = 8;                 // occurrences the update kernel gathers by itself
-constexpr int SEG = 512;                  // entries of a hot bin = rows one hot_sums block reduces
-constexpr unsigned E_SKIP = 1u << 31, E_HEAD = 1u << 30, E_POS = (1u << 18) - 1;
-constexpr unsigned TABW = 2048;           // u32 entries of the per-pass tile table (8 KB: 8 keys x 256 tiles per round)
-constexpr unsigned CTR_STRIDE = 16;       // u64 words between two counters (one 128-B line each)
-constexpr int MAXPASS_SPLIT = 64;
-// Output space is handed out by ATOMIC counters, and same-line atomics of different workgroups serialise at ~25 ns
-// each on this chip (1024 bucket blocks on ONE counter line: 25 us, measured).  So the outputs are split into NSH
-// shards with private counters and private ranges: bucket b allocates in shard b % NSH (P/NSH = 16 atomics per line),
-// and the last plan kernel publishes dense maps (keymap / binmap) over the shards for the kernels of the other half.
-constexpr unsigned NSH = 64;
-constexpr unsigned REC_WORDS = 16;        // a key record = 64 B: [0,1] key [2] count; few occurrences: [3] last position, [4..11] its batch
-                                          // positions, ascending; many: [3] first partial row [4] #partials [5] entry
-                                          // address of its last occurrence
-constexpr unsigned KM_MANY = 1u << 31;    // keymap: the record lives in `hrec`
-
-// global descriptor store: bucket b owns [b*CMAX, b*CMAX + cm); overflow list behind it
-struct CsrDesc {
-  i64* key;
-  unsigned* ord;        // tile << 18 | (count == 1: position in tile, else: run index in the tile) << 9 | (count - 1)
-  unsigned* cursor;     // [P] one per 128-B line
-  i64* ovf_key;
-  unsigned* ovf_ord;
-  unsigned* ovf_bucket;
-  unsigned* ovf_count;
-  unsigned ovf_cap;
-};
-
-struct CsrOut {
-  u64* counters;        // [NSH] one per line: few-keys | many-keys << 16 | partials << 32 | bins << 48; [NSH]: deferred keys
-  unsigned* crec;       // [NSH*cr] records of the keys with <= DIRECT occurrences
-  unsigned* hrec;       // [NSH*hr] records of the others
-  unsigned* hent;       // [NSH*br] bins of SEG entries: batch position | E_HEAD | E_SKIP
-  unsigned* hout;       // [NSH*br*32] per 16-entry item: partial row of the run starting there
-  unsigned cr, hr, pr, br;   // per-shard capacities: records, records, partial rows, bins
-};
 
 // ---------------------------------------------------------------------------------------------
 // plan kernel 1: per tile of 512 ids.
@@ -562,1099 +523,6 @@ __global__ __launch_bounds__(NTA) void csr_scatter_kernel(const unsigned* __rest
 }
 
 // ---------------------------------------------------------------------------------------------
-// gradient half, kernel 1: one block per bin of 512 entries = 32 items of 16 entries, one 16-lane group per item.
-// Runs are item-aligned (csr_bucket_kernel pads every run to whole items), so an item belongs to exactly one run or to
-// none: the group loads its 16 entry words with one coalesced read, puts all 16 gradient rows in flight at once
-// (unconditional loads, padding clamped to the item's first row), adds them in entry order, and the group holding the
-// run's first item then adds the sums of the run's following items in item order (LDS) and writes the partial row.
-// CS = CombRows (tfra_table_apply_planned_combined): the gradient of position e is formed from grads = grad_out and the entry's
-// record (tfra_combine_device.h) — each lane loads the record of its own entry, the group shares it by shuffles; none: grads[e].
-template <class... CS>
-__device__ __forceinline__ const CombEnt* comb_ent(const CS&... cs) {
-  const CombEnt* p = nullptr;
-  ((p = cs.ent), ...);
-  return p;
-}
-
-template <int NCH, class... CS>
-__global__ __launch_bounds__(NTA) void hot_sums_kernel(const float* __restrict__ grads, int dim,
-                                                       const unsigned* __restrict__ hent, const unsigned* __restrict__ hout,
-                                                       const unsigned* __restrict__ binmap,
-                                                       const unsigned* __restrict__ d_counts, float* __restrict__ partial,
-                                                       unsigned* progress, unsigned progress_val, const CS... cs) {
-  constexpr bool COMB = sizeof...(CS) > 0;
-  constexpr int NG = NTA / 16;
-  __shared__ float s_sum[NG][64];
-  __shared__ unsigned char s_kind[NG + 1];   // 0 = item continues the run of the item before, 1 = first item of a run, 2 = empty item
-  // tfra_table_step_prefetch: host-visible progress counter (pinned memory) — this kernel running means the
-  // lookup of step `progress_val` and every earlier step of the main stream are complete
-  if (progress && blockIdx.x == 0 && threadIdx.x == 0)
-    __hip_atomic_store(progress, progress_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48, g = threadIdx.x >> 4;
-  const unsigned nbins = d_counts[3];
-  for (unsigned ib = blockIdx.x; ib < nbins; ib += gridDim.x) {
-    const unsigned bin = binmap[ib];
-    const unsigned e = hent[(size_t)bin * SEG + threadIdx.x];          // lane `sub` holds entry `sub` of the item
-    const unsigned e0 = (unsigned)__shfl((int)e, gshift);
-    const bool empty = (e0 & E_SKIP) != 0, first = (e0 & E_HEAD) != 0;
-    const unsigned out_row = (first && !empty && sub == 0) ? hout[(size_t)bin * 32 + g] : 0u;
-    const unsigned live = (unsigned)(__ballot(!(e & E_SKIP)) >> gshift) & 0xffffu;   // entries of the item that exist
-    if (sub == 0) s_kind[g] = empty ? 2 : (first ? 1 : 0);
-    if (threadIdx.x == 0) s_kind[NG] = 1;
-    unsigned rows[16];   // element offset of each row (< 2^18 * 256)
-    float cden = 0.f, cw = 0.f;   // COMB: denominator and weight of this lane's entry
-    if constexpr (COMB) {
-      const CombEnt ce = comb_ent(cs...)[((e & E_SKIP) ? e0 : e) & E_POS];   // (padding: the item's first row, as below)
-      cden = ce.den;
-      cw = ce.w;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) rows[j] = (unsigned)__shfl((int)ce.row, gshift + j) * (unsigned)dim;
-    } else {
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const unsigned ej = (unsigned)__shfl((int)e, gshift + j);
-      rows[j] = (((live >> j) & 1u) ? (ej & E_POS) : (e0 & E_POS)) * (unsigned)dim;
-    }
-    }
-    for (int k = 0; k < NCH; ++k) {
-      const int col = k * 64 + sub * 4;
-      const int cc = col < dim ? col : 0;
-      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (TFRA_HOT_SUMS_HALVES && NCH == 1) {   // (rows of more than 64 floats keep 16 in flight: their kernels are at 122-128 registers either way)
-      // 8 rows in flight, twice, instead of 16 at once: 76 registers instead of 106 => 6 waves per SIMD instead of 4 => the ~680 bins of
-      // a Zipf batch (512-thread blocks) are resident in ONE round instead of two; the second batch of loads costs a trip, the second round
-      // cost more: 10.0 -> 9.2 us under rocprofv3, configs[1]'s step 56.7-57.3 -> 55.6-55.7 us (A/B on one box, twice).  Same adds, same order.
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        float4 x[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) x[j] = *reinterpret_cast<const float4*>(grads + rows[h * 8 + j] + cc);
-        keep_live(x[0], x[1], x[2], x[3]); keep_live(x[4], x[5], x[6], x[7]);
-        if constexpr (COMB) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) x[j] = comb_grad4(x[j], __shfl(cden, gshift + h * 8 + j), __shfl(cw, gshift + h * 8 + j));
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          if ((live >> (h * 8 + j)) & 1u) { acc.x += x[j].x; acc.y += x[j].y; acc.z += x[j].z; acc.w += x[j].w; }
-      }
-      } else {
-      float4 x[16];
-#pragma unroll
-      for (int j = 0; j < 16; ++j) x[j] = *reinterpret_cast<const float4*>(grads + rows[j] + cc);   // 16 rows in flight
-      keep_live(x[0], x[1], x[2], x[3]); keep_live(x[4], x[5], x[6], x[7]);
-      keep_live(x[8], x[9], x[10], x[11]); keep_live(x[12], x[13], x[14], x[15]);
-      if constexpr (COMB) {
-#pragma unroll
-        for (int j = 0; j < 16; ++j) x[j] = comb_grad4(x[j], __shfl(cden, gshift + j), __shfl(cw, gshift + j));
-      }
-#pragma unroll
-      for (int j = 0; j < 16; ++j)
-        if ((live >> j) & 1u) { acc.x += x[j].x; acc.y += x[j].y; acc.z += x[j].z; acc.w += x[j].w; }
-      }
-      if (k) __syncthreads();   // the owners of the previous chunk have read s_sum
-      *reinterpret_cast<float4*>(&s_sum[g][sub * 4]) = acc;
-      __syncthreads();
-      if (first && !empty) {
-        for (int g2 = g + 1; s_kind[g2] == 0; ++g2) {
-          const float4 y = *reinterpret_cast<const float4*>(&s_sum[g2][sub * 4]);
-          acc.x += y.x; acc.y += y.y; acc.z += y.z; acc.w += y.w;
-        }
-        const unsigned orow = (unsigned)__shfl((int)out_row, gshift);
-        if (col < dim) *reinterpret_cast<float4*>(partial + (size_t)orow * dim + col) = acc;
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-struct CsrKeys {
-  const unsigned* keymap;
-  const i64* dkeys;
-  const unsigned* crec; const unsigned* hrec;
-  const unsigned* hent;
-  const unsigned* d_counts;
-  // SET plan (assign-only, see setplan_kernel): dense distinct keys, their slots, (last position + 1, occurrences) per slot
-  const i64* ukeys;
-  const unsigned* uslot;
-  const struct SetEnt* sent;
-};
-// One slot of a SET plan's open-addressing table: 16 B, so that a probe is ONE load (the overlapped step's lookup probes the
-// previous batch's plan for every id: find_fwd_role, tfra_step_impl.h)
-struct SetEnt { i64 key; unsigned pos1, cnt; };   // key (EMPTY_KEY = free) | last position + 1 | occurrences
-__device__ __forceinline__ uint2 set_pc(const SetEnt* e) { return *reinterpret_cast<const uint2*>(&e->pos1); }
-// A SET plan's table as something to PROBE (read-only): is this key one of the batch's ids, and where is its last occurrence?
-// Probe chains stay inside a WINDOW of SET_WIN consecutive slots (home slot = hash & (m2 - 1); the slot behind the window's last
-// is its first): the overlapped step builds a plan one window per workgroup, in LDS, without atomics (tfra_step_impl.h), and
-// every other builder and every prober follows the same rule.  (m2 >= 2 n slots for n ids: a window overflows never.)
-constexpr unsigned SET_WIN = 2048, SET_WIN_LOG2 = 11;
-constexpr unsigned SEG_CAP = 32;   // pairs per (window, tile) segment of a scatter (tfra_step_impl.h); more: the overflow list
-__host__ __device__ __forceinline__ unsigned set_wmask(unsigned m2) { return (m2 < SET_WIN ? m2 : SET_WIN) - 1u; }
-__device__ __forceinline__ unsigned set_at(unsigned slot, unsigned g, unsigned wm) { return (slot & ~wm) | ((slot + g) & wm); }   // g slots on, inside the window
-struct SetProbe { const SetEnt* ent; unsigned m2; };   // m2 entries (a power of two) + the two sentinel slots + padding
-__device__ __forceinline__ unsigned set_home(const SetProbe& p, i64 key, u64 h) {   // h = fmix64(key)
-  return is_reserved_key(key) ? p.m2 + (unsigned)reserved_index(key) : (unsigned)(h >> 20) & (p.m2 - 1);
-}
-// All 16 lanes of a key group: does the table hold `key`?  Lanes 0..3 look at four consecutive entries per round (linear
-// probing, slots are never freed during a build: a match anywhere is the key, an EMPTY entry before it ends the search).
-__device__ __forceinline__ bool set_contains_group(const SetProbe& p, i64 key, int sub, int gshift) {
-  const bool resv = is_reserved_key(key);
-  unsigned slot = set_home(p, key, fmix64((u64)key));
-  const unsigned wm = set_wmask(p.m2);
-  for (int round = 0; round < 512; ++round) {
-    const unsigned e = resv ? slot + (unsigned)(sub & 3) : set_at(slot, (unsigned)(sub & 3), wm);
-    const i64 k = p.ent[e].key;
-    const bool match = resv ? ((sub & 3) == 0 && k != EMPTY_KEY) : k == key;
-    const unsigned mm = (unsigned)(__ballot(match && sub < 4) >> gshift) & 0xfu;
-    const unsigned em = (unsigned)(__ballot(k == EMPTY_KEY && sub < 4) >> gshift) & 0xfu;
-    if (mm) return true;
-    if (em || resv) return false;
-    slot = set_at(slot, 4u, wm);
-  }
-  return true;   // (a chain this long does not exist: 2 n slots for n ids; say "present", the conservative answer)
-}
-
-// The same for TWO plans at once (lanes 0..3 probe p, lanes 4..7 probe q: one round trip for both): is the key in either?
-__device__ __forceinline__ bool set_contains_either_group(const SetProbe& p, const SetProbe& q, i64 key, int sub, int gshift) {
-  const bool resv = is_reserved_key(key);
-  const SetProbe& t = (sub & 4) ? q : p;
-  unsigned slot = set_home(t, key, fmix64((u64)key));
-  const unsigned wm = set_wmask(t.m2);
-  unsigned open = 3u;   // bit 0: still looking in p, bit 1: in q
-  for (int round = 0; round < 512 && open; ++round) {
-    const unsigned e = resv ? slot + (unsigned)(sub & 3) : set_at(slot, (unsigned)(sub & 3), wm);
-    const i64 k = t.ent[e].key;
-    const bool match = resv ? ((sub & 3) == 0 && k != EMPTY_KEY) : k == key;
-    const unsigned mm = (unsigned)(__ballot(match && sub < 8) >> gshift) & 0xffu;
-    const unsigned em = (unsigned)(__ballot(k == EMPTY_KEY && sub < 8) >> gshift) & 0xffu;
-    if ((mm & 0x0fu) && (open & 1u)) return true;
-    if ((mm & 0xf0u) && (open & 2u)) return true;
-    if ((em & 0x0fu) || resv) open &= ~1u;
-    if ((em & 0xf0u) || resv) open &= ~2u;
-    slot = set_at(slot, 4u, wm);
-  }
-  return open != 0;   // (a chain this long does not exist; "present" is the conservative answer)
-}
-
-// one coalesced 64-B load per key group: lane i holds word i of the key's record
-__device__ __forceinline__ unsigned load_record(const CsrKeys& ks, unsigned g, int sub, bool& many) {
-  const unsigned km = ks.keymap[g];
-  many = (km & KM_MANY) != 0;
-  return (many ? ks.hrec : ks.crec)[(size_t)(km & ~KM_MANY) * REC_WORDS + sub];
-}
-
-// The source rows of a key's sum, NB of them in flight: rows j0 .. j0+NB-1 of its list (clamped to the last one; loads issued
-// together, adds in list order).  A key with few occurrences lists their batch positions in words 4.. of its record (lane i
-// of the group holds word i: EVERY lane of the group must be here); a key with many lists consecutive rows of the partial
-// sums.  The addresses are formed here, from the record word, not kept in an array across the kernel: with 8 pointers and
-// 8 rows held per lane the update kernel needed 145 registers (3 waves per SIMD); this form needs 125 (Adam) / 109 (SGD).
-// COMB (combined write-back): lanes 4.. of a key with few occurrences hold grad_out rows instead of batch positions, and the
-// denominator / weight of their entry in cden / cw; each gradient row is scaled by comb_grad4 before it is added.
-template <int NB, bool COMB = false>
-__device__ __forceinline__ void add_rows(float4& acc, const float* __restrict__ grads, const float* __restrict__ partial, bool hot,
-                                         unsigned w, unsigned first, unsigned nsrc, unsigned j0, int dim, int c, int gshift,
-                                         float cden = 0.f, float cw = 0.f) {
-  float4 x[NB];
-#pragma unroll
-  for (int j = 0; j < NB; ++j) {
-    const unsigned jj = min(j0 + (unsigned)j, nsrc - 1);
-    const unsigned position = (unsigned)__shfl((int)w, gshift + 4 + (int)min(jj, 7u));
-    const float* q = hot ? partial + (size_t)(first + jj) * dim : grads + (size_t)position * dim;
-    x[j] = *reinterpret_cast<const float4*>(q + c);
-  }
-  if (NB == 4) keep_live(x[0], x[1], x[2], x[3]);
-  if (COMB && !hot) {
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      const int src = gshift + 4 + (int)min(min(j0 + (unsigned)j, nsrc - 1), 7u);
-      x[j] = comb_grad4(x[j], __shfl(cden, src), __shfl(cw, src));
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < NB; ++j)
-    if (j0 + (unsigned)j < nsrc) { acc.x += x[j].x; acc.y += x[j].y; acc.z += x[j].z; acc.w += x[j].w; }
-}
-
-// the whole sum of a key; wmax = the largest list length (capped at 8) among the wave's four keys: the trip count of the
-// common part is uniform across the wave, the few keys with more than 8 partial rows go on alone
-template <bool COMB = false>
-__device__ __forceinline__ float4 sum_rows(const float* __restrict__ grads, const float* __restrict__ partial, bool hot, unsigned w,
-                                           unsigned first, unsigned nsrc, unsigned wmax, int dim, int c, int gshift,
-                                           float cden = 0.f, float cw = 0.f) {
-  float4 gg = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (wmax <= 1) add_rows<1, COMB>(gg, grads, partial, hot, w, first, nsrc, 0, dim, c, gshift, cden, cw);
-  else if (wmax <= 2) add_rows<2, COMB>(gg, grads, partial, hot, w, first, nsrc, 0, dim, c, gshift, cden, cw);
-  else {
-    add_rows<4, COMB>(gg, grads, partial, hot, w, first, nsrc, 0, dim, c, gshift, cden, cw);
-    if (wmax > 4) add_rows<4, COMB>(gg, grads, partial, hot, w, first, nsrc, 4, dim, c, gshift, cden, cw);
-  }
-  for (unsigned j0 = 8; j0 < nsrc; j0 += 4) add_rows<4, COMB>(gg, grads, partial, hot, w, first, nsrc, j0, dim, c, gshift, cden, cw);
-  return gg;
-}
-
-// ---------------------------------------------------------------------------------------------
-// gradient half, kernel 2: one 16-lane group per unique key, hot keys first (their partial lists are the longest
-// chains of the kernel: started first, they finish inside the kernel's duration).
-// PHASE2: bounded (Hkv) table at max_capacity — the keys flagged in `dflag` (no free slot in phase 1; one byte per key:
-// a list appended through ONE atomic counter cost 4 ns per key, 260 us for a batch of new keys) replace the minimum-score
-// entry of their two home buckets and start from the default row / initial slot values, exactly like
-// apply_evict_kernel (tfra_optim.hip).
-// (Tried: amdgpu_waves_per_eu(4) on the 145-register form — 128 VGPRs with 7 spilled: gradient half 32.5 us instead of 31.5.
-// Without the pointer arrays — add_rows — it is 125 registers, 4 waves per SIMD, no spills: 28.7 us, step 57.2 instead of 59.9 us.
-// Round 4: amdgpu_waves_per_eu(5, 5) on that form — 96 registers, 18 spilled for Adam: gradient half 28.7 -> 37.3 us, the step of
-// configs[1] 55.4 -> 62.3 us (A/B on one box, twice).  Five waves need a kernel that NEEDS 96 registers, not one that spills to them.)
-// CS = CombRows: the combined write-back (see hot_sums_kernel).
-template <int KIND, bool PHASE2, class... CS>
-__global__ __launch_bounds__(256) void apply_csr_kernel(TableView v, OptP o, int dim, const float* __restrict__ grads,
-                                                        const float* __restrict__ partial, CsrKeys ks,
-                                                        const float* __restrict__ default_row, float aux0, float aux1,
-                                                        ScoreP sp, uint8_t* __restrict__ dflag, unsigned* any_deferred,
-                                                        unsigned use_gen, const CS... cs) {
-  constexpr bool COMB = sizeof...(CS) > 0;
-  if (PHASE2 && *any_deferred != use_gen) return;   // phase 1 of this use deferred nothing
-  constexpr int S = NSlots<KIND>::v;
-  const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
-  const unsigned total = ks.d_counts[0] + ks.d_counts[1];
-  const unsigned ngroups = (gridDim.x * blockDim.x) >> 4;
-  int fresh = 0, failed = 0;
-  if (o.d_lr) o.lr = *o.d_lr;
-  if (!PHASE2 && blockIdx.x == 0 && threadIdx.x == 0 && ks.d_counts[5]) atomicAdd(v.err_count, ks.d_counts[5]);  // plan overflow
-  // trips are uniform per wave (the batch width below is a wave-wide maximum): a group past the end re-reads the
-  // last key's records and does nothing else
-  for (unsigned wbase = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) << 2; wbase < total; wbase += ngroups) {
-    const unsigned it_raw = wbase + (unsigned)(lane >> 4);
-    const bool active = it_raw < total;
-    const unsigned g = active ? it_raw : total - 1;
-    if (PHASE2 && !__builtin_amdgcn_readfirstlane((int)(__ballot(active && dflag[g]) != 0))) continue;   // nothing deferred in this wave
-    // two chains in flight: key -> first probe line, and keymap -> record -> source rows
-    const i64 key = ks.dkeys[g];
-    u64 h;
-    const u64 b0 = bucket0(key, v.nb, h);
-    i64 k0 = 0;
-    if (!PHASE2) k0 = load_key_coherent(key_line(v, b0) + sub);
-    bool hot;
-    const unsigned w = load_record(ks, g, sub, hot);
-    const unsigned cnt = (unsigned)__shfl((int)w, gshift + 2);
-    const unsigned first = (unsigned)__shfl((int)w, gshift + 3);             // keys with many occurrences: first partial row
-    const unsigned nsrc = hot ? (unsigned)__shfl((int)w, gshift + 4) : cnt;
-    // COMB: lane 4 + j of a key with few occurrences swaps batch position j for that entry's grad_out row (+ denominator, weight)
-    unsigned wsrc = w;
-    float cden = 0.f, cw = 0.f;
-    if constexpr (COMB) {
-      if (!hot && sub >= 4 && (unsigned)(sub - 4) < cnt) {
-        const CombEnt ce = comb_ent(cs...)[w];
-        wsrc = ce.row; cden = ce.den; cw = ce.w;
-      }
-    }
-    // wave-uniform batch width: 1 / 2 / 4 rows in flight (most keys of a Zipf batch occur once)
-    unsigned wmax = min(nsrc, 8u);
-    for (int o2 = 32; o2 >= 16; o2 >>= 1) wmax = max(wmax, (unsigned)__shfl_xor((int)wmax, o2));
-    wmax = (unsigned)__builtin_amdgcn_readfirstlane((int)wmax);
-    if (!active || (PHASE2 && !dflag[g])) continue;
-    i64 row;
-    bool is_new = false;
-    u64 word = 0;
-    bool claimed_empty = false;
-    if (PHASE2) {
-      const bool lru_like = sp.strategy == TFRA_EVICT_LRU || sp.strategy == TFRA_EVICT_EPOCHLRU;
-      const u64 in_score = sp.strategy == TFRA_EVICT_EPOCHLFU ? ((sp.epoch << 32) | 1) : 1;
-      row = evict_and_lock(v, key, in_score, lru_like, sub, gshift, &word, claimed_empty);
-      is_new = true;
-    } else {
-      row = locate_or_claim_from(v, key, h, b0, k0, sub, gshift, is_new, sp.bounded);
-      if (sp.bounded && sub == 0) {
-        dflag[g] = row == NEED_EVICT;
-        if (row == NEED_EVICT) *any_deferred = use_gen;
-      }
-    }
-    if (row < 0) {
-      failed += (sub == 0 && (PHASE2 ? row == -3 : row != NEED_EVICT));
-      continue;
-    }
-    fresh += ((PHASE2 ? claimed_empty : is_new) && sub == 0);
-    float* pr = reinterpret_cast<float*>(row_ptr(v, row));
-    // (every lane of the group takes every trip — sum_rows reads the record words of the other lanes; a lane beyond the row
-    // works on column 0 and stores nothing)
-    for (int c0 = 0; c0 < dim; c0 += 64) {
-      const bool col = c0 + sub * 4 < dim;
-      const int c = col ? c0 + sub * 4 : 0;
-      float4 p = *reinterpret_cast<const float4*>((is_new ? default_row : pr) + c);
-      float4 s1 = *reinterpret_cast<const float4*>(pr + (S >= 1 ? dim : 0) + c);
-      float4 s2 = *reinterpret_cast<const float4*>(pr + (S >= 2 ? 2 * dim : 0) + c);
-      float4 gg = sum_rows<COMB>(grads, partial, hot, COMB ? wsrc : w, first, nsrc, wmax, dim, c, gshift, cden, cw);
-      float4 dummy = p;
-      keep_live(dummy, p, s1, s2);
-      if (is_new || S < 1) s1 = make_float4(aux0, aux0, aux0, aux0);
-      if (is_new || S < 2) s2 = make_float4(aux1, aux1, aux1, aux1);
-      apply_one<KIND>(o, gg.x, p.x, s1.x, s2.x);
-      apply_one<KIND>(o, gg.y, p.y, s1.y, s2.y);
-      apply_one<KIND>(o, gg.z, p.z, s1.z, s2.z);
-      apply_one<KIND>(o, gg.w, p.w, s1.w, s2.w);
-      // write-through: the rows leave L2 during the kernel, not at the boundary to the next one
-      if (col) {
-        store_wt16(pr + c, *reinterpret_cast<uint4*>(&p));
-        if (S >= 1) store_wt16(pr + dim + c, *reinterpret_cast<uint4*>(&s1));
-        if (S >= 2) store_wt16(pr + 2 * dim + c, *reinterpret_cast<uint4*>(&s2));
-      }
-    }
-    // aux fields the optimizer does not own (table created with more slots than it uses)
-    if (is_new && (int)v.n_fields - 1 > S) {
-      for (int f = S + 1; f < (int)v.n_fields; ++f)
-        for (int c = sub; c < dim; c += 16)
-          __hip_atomic_store(pr + f * dim + c, (f == 1 ? aux0 : aux1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (PHASE2) {
-      if (sub == 0) store_wt8(score_word(v, word), 0);  // the slot starts a new life
-      update_score<true>(v, row, true, sp.strategy, 1, sp.epoch, sub);
-      publish_key(v, word, key, sub);
-    } else {
-      update_score(v, row, is_new, sp.strategy, 1, sp.epoch, sub);  // one write-back = one upsert
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1) { fresh += __shfl_xor(fresh, off); failed += __shfl_xor(failed, off); }
-  if (lane == 0) {
-    if (fresh) size_add(v, (blockIdx.x * blockDim.x + threadIdx.x) >> 6, fresh);
-    if (failed) atomicAdd(v.err_count, (unsigned)failed);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// tfra_reduce_by_key epilogue: the same per-key sums as apply_csr_kernel, written out instead of applied.
-// dest != nullptr (tfra_plan_reduce_to): the sum of a key goes to row dest[p], p = the key's last batch position — the
-// caller's map from batch positions to output rows (equal for all positions of a key), e.g. position -> owner-major
-// index of the multi-GPU gradient route; keys_out / d_count are not written then.
-__global__ __launch_bounds__(256) void gather_csr_kernel(int dim, const float* __restrict__ grads,
-                                                         const float* __restrict__ partial, CsrKeys ks,
-                                                         i64* __restrict__ keys_out, float* __restrict__ rows_out,
-                                                         i64* __restrict__ d_count, const int* __restrict__ dest) {
-  const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
-  const unsigned total = ks.d_counts[0] + ks.d_counts[1];
-  const unsigned ngroups = (gridDim.x * blockDim.x) >> 4;
-  if (d_count && blockIdx.x == 0 && threadIdx.x == 0) *d_count = ks.d_counts[5] ? (i64)-1 : (i64)total;
-  for (unsigned wbase = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) << 2; wbase < total; wbase += ngroups) {
-    const unsigned it_raw = wbase + (unsigned)(lane >> 4);
-    const bool active = it_raw < total;
-    const unsigned g = active ? it_raw : total - 1;
-    bool hot;
-    const unsigned w = load_record(ks, g, sub, hot);
-    const i64 key = (i64)(((u64)(unsigned)__shfl((int)w, gshift + 1) << 32) | (unsigned)__shfl((int)w, gshift));
-    const unsigned cnt = (unsigned)__shfl((int)w, gshift + 2);
-    const unsigned first = (unsigned)__shfl((int)w, gshift + 3);
-    const unsigned nsrc = hot ? (unsigned)__shfl((int)w, gshift + 4) : cnt;
-    unsigned wmax = min(nsrc, 8u);
-    for (int o2 = 32; o2 >= 16; o2 >>= 1) wmax = max(wmax, (unsigned)__shfl_xor((int)wmax, o2));
-    wmax = (unsigned)__builtin_amdgcn_readfirstlane((int)wmax);
-    if (!active) continue;
-    size_t orow = g;
-    if (dest) {
-      unsigned lastp = (unsigned)__shfl((int)w, gshift + (hot ? 5 : 3));   // few: the last position itself; many: where it is stored
-      if (hot) lastp = ks.hent[lastp];
-      orow = (size_t)dest[lastp & E_POS];
-    }
-    for (int c0 = 0; c0 < dim; c0 += 64) {   // (every lane takes every trip: see apply_csr_kernel)
-      const bool col = c0 + sub * 4 < dim;
-      const int c = col ? c0 + sub * 4 : 0;
-      const float4 gg = sum_rows(grads, partial, hot, w, first, nsrc, wmax, dim, c, gshift);
-      if (col) *reinterpret_cast<float4*>(rows_out + orow * dim + c) = gg;
-    }
-    if (keys_out && sub == 0) keys_out[g] = key;
-  }
-}
-
-constexpr unsigned SLOW_CAP = 8192;   // items of the left-over list of an ownership pass (more: the flags of all keys are scanned)
-
-// ---------------------------------------------------------------------------------------------
-// ASSIGN write-back, single pass with BUCKET OWNERSHIP (without owner tags — TFRA_OPTION_NO_OWNER_TAGS — every key takes the
-// locked protocol of upsert_rest_kernel).
-// Every bucket has an owner tag (one 32-bit word in a dense side array — NOT in the bucket's key line: an atomic and a
-// load issued together on the same 128-B line cost 41 us per 157 K instead of 11 us on separate lines,
-// scripts/mb/atomic_probe.hip).  Every key of the launch swaps the launch's generation into the tags of its two home
-// buckets (two atomic exchanges in flight with its line loads) and owns a bucket iff the tag it got back is from an
-// older launch.  A key that owns BOTH home buckets is the
-// only writer of the launch that can touch them — every other key of the launch whose sequence includes one of them
-// fails that claim and leaves the table alone — so it resolves hit / free slot / minimum-score eviction with plain
-// loads and stores: no CAS, no LOCKED state, no score re-read, no publish ordering, and ONE dependent round trip (the
-// four lines and the two claims are in flight together) instead of the five of the locked protocol.
-//
-// LEFT-OVER keys: a key that loses a claim (two keys of one batch sharing a home bucket: ~(2U)^2 / (2 nb) of them, 16 of
-// 23 K / 185 of 78 K on 10^9 slots) or that cannot be placed within its two home buckets appends a self-contained ITEM
-// (key, value position, input score) to the launch's list; upsert_rest_kernel takes the items afterwards with the locked
-// protocol.  A key that MAY live beyond its home buckets (both overflow flags set, ~0.1 % of the buckets of a table filled
-// to capacity) is looked for with reads in the main pass and claims the bucket it is found in.
-//
-// Round 3 measurements on the 10^9-slot table (scripts/mb_own.py, mb_sweep.py; rocprofv3 per-kernel times):
-//   * the pass costs 13 us + 0.23 us per 1000 keys: 3.0 us launch + key load, 5.5 us until the four lines AND the two
-//     claims are back (the lines alone 3.5 us — every access is a TLB miss on 273 GB), 4 us of dependent ALU / cross-lane
-//     work for ONE wave's 16 keys, 0.5 us value rows, 1 us stores;
-//   * the claims are ~5 us of 32 (78 K keys), their footprint does not matter (tags folded into 8 MB: same time);
-//   * tried and dropped: the left-over keys in two more OWNERSHIP rounds — by the last block of the pass (ticket) or by a
-//     one-block kernel behind it — 14-19 us against 10-12 us for 32 blocks of the locked protocol (one workgroup is one
-//     dependent chain per round, and the code of the rounds costs the pass registers); claim-after-look with shared /
-//     exclusive claim words in the score lines (an atomic on a line that has just been read is still a fabric
-//     read-modify-write, and it now sits behind the lines instead of beside them): 35 / 38 us against 30 / 24;
-//     the value row prefetched with the lines (direct keys): 42 us against 31 (16 more registers per lane, spills).
-
-// One left-over key with the locked protocol for every kind of write: locate or claim the key's slot, LOCK it (CAS key
-// -> LOCKED: a concurrent evictor of this pass may have taken it, then start over), or lock a victim (evict_and_lock);
-// write row and score write-through, publish the key.  With every writer of the pass holding its slot locked, an assign
-// can no longer race with the eviction of the same slot, which is what the two separate kernels (assign / claim, then
-// evict) are for when they handle a whole batch.
-// hint (a left-over key of the ownership pass that FOUND its key but had lost a claim): the slot it saw the key in — locked
-// straight away, without reading the lines again (two dependent round trips less for 15 of the 16 left-over keys of the
-// metric's batch); somebody took the slot in between: the ordinary way.
-template <int G>
-__device__ __forceinline__ void locked_upsert_kv(const TableView& v, const unsigned char* __restrict__ vals, i64 key, unsigned last,
-                                                 u64 in_score, const AuxInitPod& ai, const ScoreP& sp, int sub, int gshift,
-                                                 int& fresh, int& failed, bool hinted = false, unsigned hint_word = 0,
-                                                 i64* evicted_key = nullptr, int acc = 0, int acc_dt = 0, i64* given_back = nullptr,
-                                                 int* n_given_back = nullptr) {
-  // evicted_key (optional): set to the key this upsert replaced by eviction (untouched when it evicted nothing)
-  // acc: the reference's insert_or_accum for this key (accumrase_fn, cuckoohash_map.hh:619-633) instead of an assign —
-  //   1 (exists): present -> row += delta, one add per element; absent -> nothing.   2 (!exists): absent -> insert; present -> nothing
-  const bool lru_like = sp.strategy == TFRA_EVICT_LRU || sp.strategy == TFRA_EVICT_EPOCHLRU;
-  const u64 cmp = sp.strategy == TFRA_EVICT_EPOCHLFU ? ((sp.epoch << 32) | in_score) : in_score;
-  i64 row = -1;
-  u64 word = 0;
-  bool is_new = false, evicted = false, side = false;
-  if (hinted) {
-    i64 old = 0;
-    if (sub == 0) old = (i64)atomicCAS((u64*)key_word(v, (u64)hint_word), (u64)key, (u64)LOCKED_KEY);
-    old = shfl_i64(old, gshift);
-    if (old == key) { word = hint_word; row = (i64)((word >> 4) * SLOTS + (word & 15)); }
-  }
-  for (int attempt = 0; acc == 1 && attempt < 64 && row < 0; ++attempt) {   // accumulate: find the key (never claim a slot) and lock it
-    const i64 r = probe_find<true>(v, key, sub, gshift);
-    if (r < 0) return;                                   // absent & exists: dropped
-    if (r >= (i64)(v.nb * SLOTS)) { row = r; side = true; break; }
-    u64 rb;
-    unsigned rs;
-    split_row((u64)r, rb, rs);
-    const u64 wd = rb * 16 + rs;
-    i64 old = 0;
-    if (sub == 0) old = (i64)atomicCAS((u64*)key_word(v, wd), (u64)key, (u64)LOCKED_KEY);
-    old = shfl_i64(old, gshift);
-    if (old == key) { row = r; word = wd; }              // else: an evictor of this pass took the slot; look again
-  }
-  for (int attempt = 0; acc != 1 && attempt < 64 && row < 0; ++attempt) {
-    // This pass is one wave-lifetime of dependent round trips (~1.2 us each): both home buckets' key AND score lines
-    // travel together up front (first attempt) instead of b0 -> b1 -> score lines one after the other.
-    u64 h;
-    const u64 b0 = bucket0(key, v.nb, h);
-    const u64 b1 = bucket1(h, b0, v.nb);
-    const bool pre = attempt == 0 && has_scores(v) && sp.bounded != 0;
-    i64 kk2[2], sc2[2] = {0, 0};
-    kk2[0] = load_key_coherent(key_line(v, b0) + sub);
-    kk2[1] = pre ? load_key_coherent(key_line(v, b1) + sub) : 0;
-    if (pre) {
-      sc2[0] = (i64)__hip_atomic_load(score_line(v, b0) + sub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      sc2[1] = (i64)__hip_atomic_load(score_line(v, b1) + sub, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      keep_live(kk2[0], kk2[1], sc2[0], sc2[1]);
-    }
-    bool claimed = false;
-    i64 r = locate_or_claim_from(v, key, h, b0, kk2[0], sub, gshift, claimed, sp.bounded, pre ? &kk2[1] : nullptr);
-    if (r == NEED_EVICT) {
-      bool ce = false;
-      u64 wd = 0;
-      i64 vk = EMPTY_KEY;
-      r = evict_and_lock(v, key, cmp, lru_like, sub, gshift, &wd, ce, pre ? kk2 : nullptr, pre ? sc2 : nullptr, &vk, given_back, n_given_back);
-      if (r == -1) break;                        // not admitted (its score is below every resident one): dropped
-      if (r == -3) { failed += (sub == 0); break; }
-      row = r; word = wd; is_new = true; evicted = !ce;
-      if (evicted && evicted_key) *evicted_key = vk;
-      fresh += (ce && sub == 0);
-      break;
-    }
-    if (r < 0) { failed += (sub == 0); break; }
-    if (acc == 2 && !claimed) return;                    // present & !exists: dropped (nothing was claimed or locked)
-    fresh += (claimed && sub == 0);
-    is_new = is_new || claimed;
-    if (r >= (i64)(v.nb * SLOTS)) { row = r; side = true; break; }   // sentinel keys live in the side rows: nothing evicts there
-    u64 rb;
-    unsigned rs;
-    split_row((u64)r, rb, rs);
-    const u64 wd = rb * 16 + rs;
-    i64 old = 0;
-    if (sub == 0) old = (i64)atomicCAS((u64*)key_word(v, wd), (u64)key, (u64)LOCKED_KEY);
-    old = shfl_i64(old, gshift);
-    if (old == key) { row = r; word = wd; }   // else: an evictor of this pass took the slot; look again
-  }
-  if (row < 0) return;
-  unsigned char* pr = row_ptr(v, row);
-  if (acc == 1 && G == 16) {
-    const unsigned char* dl = vals + (size_t)last * v.field_bytes;
-    for (unsigned off = sub * 16; off < v.field_bytes; off += 256)
-      store_wt16(pr + off, add16_dt(*reinterpret_cast<const uint4*>(pr + off), *reinterpret_cast<const uint4*>(dl + off), acc_dt));
-  } else copy_bytes16_wt<G>(pr, vals + (size_t)last * v.field_bytes, v.field_bytes, sub);
-  if (is_new) {
-    for (unsigned f = 1; f < v.n_fields; ++f) {   // slot fields of the new row start at aux_init
-      const unsigned pat = ai.pattern[(f - 1) & 3];
-      unsigned char* q = pr + f * v.field_bytes;
-      if ((v.field_bytes & 3) == 0)
-        for (unsigned off = sub * 4; off < v.field_bytes; off += 64)
-          __hip_atomic_store(reinterpret_cast<unsigned*>(q + off), pat, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      else
-        for (unsigned off = sub; off < v.field_bytes; off += 16)
-          __hip_atomic_store(q + off, (unsigned char)(pat >> (8 * (off % ai.elem_bytes))), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  if (side) return;
-  if (evicted && sub == 0) store_wt8(score_word(v, word), 0);   // the slot starts a new life
-  update_score<true>(v, row, is_new, sp.strategy, in_score, sp.epoch, sub);
-  publish_key(v, word, key, sub);
-}
-
-// the same for key g of a plan: key, last position and input score come from its record
-template <int G>
-__device__ __forceinline__ void locked_upsert_one(const TableView& v, const unsigned char* __restrict__ vals,
-                                                  const u64* __restrict__ scores, const CsrKeys& ks, const AuxInitPod& ai,
-                                                  const ScoreP& sp, unsigned g, int sub, int gshift, int& fresh, int& failed) {
-  const i64 key = ks.dkeys[g];
-  bool hot;
-  const unsigned w = load_record(ks, g, sub, hot);
-  const unsigned cnt = (unsigned)__shfl((int)w, gshift + 2);
-  unsigned last = (unsigned)__shfl((int)w, gshift + (hot ? 5 : 3));
-  if (hot) last = ks.hent[last];
-  last &= E_POS;
-  const u64 in_one = scores ? scores[last] : 1;
-  const u64 in_score = sp.strategy == TFRA_EVICT_LFU ? (scores ? in_one : (u64)cnt) : in_one;
-  locked_upsert_kv<G>(v, vals, key, last, in_score, ai, sp, sub, gshift, fresh, failed);
-}
-
-// A left-over key of the ownership pass, self-contained: the remainder pass needs nothing of the plan.
-struct OwnItem {          // 32 B, written as two 16-B stores
-  i64 key;
-  unsigned last;          // batch position of the key's value row
-  unsigned g;             // index of the key in the launch (its dflag byte)
-  u64 ins;                // input score
-  unsigned hinted, word;  // hinted != 0: the pass saw the key in slot `word` (bucket * 16 + slot) and did not write it
-};
-// Counters of one use by the ownership write-back (two sets alternate, the last kernel of use k zeroes the set of
-// use k+1: nothing of use k-1 is still running by stream order).
-struct OwnCtrs { unsigned n_a, spare[3]; };
-
-// Where the keys of a launch come from:
-//   SRC_PLAN    the unique keys of a de-duplication plan (value row = the key's LAST occurrence in the batch)
-//   SRC_DIRECT  a caller's array of UNIQUE keys, value row i belongs to key i (tfra_table_insert_or_assign with
-//               TFRA_FLAG_UNIQUE_KEYS: the reference's Insert op, hkv_hashtable_op_gpu.cu.cc:253-290)
-//   SRC_SET     the distinct keys of a SET plan (assign-only: last position and count per key, no positions list)
-enum { SRC_PLAN = 0, SRC_DIRECT = 1, SRC_SET = 2, SRC_GIVEN = 3 };   // SRC_GIVEN: the caller hands key and value position (the overlapped step: from LDS)
-
-struct OwnArgs {
-  TableView v;
-  const unsigned char* vals;
-  const u64* scores;
-  CsrKeys ks;              // SRC_PLAN
-  const i64* keys;         // SRC_DIRECT
-  unsigned nkeys;          // SRC_DIRECT
-  const long long* d_nkeys;   // SRC_DIRECT, optional: the key count on the device (nkeys = the buffers' length then)
-  AuxInitPod ai;
-  ScoreP sp;
-  uint8_t* dflag;          // one byte per key of the launch: 4 = left over.  All zero between launches: only left-over keys
-                           // are flagged, and whoever takes a left-over key clears its flag
-  unsigned* tags;
-  OwnItem* items;          // [item_cap] left-over list of the launch
-  unsigned item_cap;
-  const uint8_t* exists;   // ACC (insert_or_accum of unique keys, SRC_DIRECT): the caller's exists flag per key
-  int acc_dt;              // ACC: tfra_dtype of the rows
-  SetProbe own_set;        // HF outside the step launch (SRC_SET): the launch's own SET plan, as something to probe
-  unsigned* stats_host;    // pinned (Table::own_stats_host) or null: where the remainder kernel leaves the pass's sample
-};
-// (OwnArgs stays a read-only kernel argument: a private, modified copy would live in scratch memory — its aux_init
-// pattern is indexed dynamically — and every field access of the hot loop would become a scratch load.)
-struct OwnFlags { bool with_scores, spec, lru, lru_like; };
-__device__ __forceinline__ unsigned direct_count(const OwnArgs& a) {   // keys of a SRC_DIRECT launch
-  if (!a.d_nkeys) return a.nkeys;
-  const long long dn = *a.d_nkeys;
-  return dn < 0 ? 0u : (unsigned)min((long long)a.nkeys, dn);
-}
-
-template <bool SIMPLE>
-__device__ __forceinline__ OwnFlags own_setup(const OwnArgs& a) {
-  OwnFlags fl;
-  fl.with_scores = SIMPLE || has_scores(a.v);
-  const bool dense = a.sp.bounded > 1 || (a.sp.bounded == 1 && *a.v.dense_flag);
-  fl.spec = fl.with_scores && dense;   // an eviction is likely: the score lines travel with the key lines
-  fl.lru = SIMPLE || a.sp.strategy == TFRA_EVICT_LRU;
-  fl.lru_like = fl.lru || a.sp.strategy == TFRA_EVICT_EPOCHLRU;
-  return fl;
-}
-
-// The keys the ownership pass leaves over: 32 blocks (a full grid on a small table, where they are most of the batch) of
-// the locked protocol over the item list; the flags of ALL keys when the list overflowed.
-template <int G, int SRC, bool ACC = false>
-__global__ __launch_bounds__(256) void upsert_rest_kernel(const OwnArgs a, const unsigned* slow_ctr, unsigned* zero4) {
-  // slow_ctr == nullptr: there was no ownership pass (no owner tags): EVERY key of the launch, with the locked protocol.
-  // This kernel is a chain of dependent round trips for a handful of keys: the group's first item travels together with the
-  // list's length (it is used only if the list turns out to reach that far), and the plan's key count is read only by the
-  // launches that need it.
-  const unsigned gi = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
-  uint4 f0 = make_uint4(0u, 0u, 0u, 0u), f1 = f0;
-  if (slow_ctr) {
-    const OwnItem* it = a.items + (gi < a.item_cap ? gi : 0u);
-    f0 = reinterpret_cast<const uint4*>(it)[0];
-    f1 = reinterpret_cast<const uint4*>(it)[1];
-  }
-  unsigned total = 0;
-  if (!slow_ctr) total = SRC != SRC_DIRECT ? a.ks.d_counts[0] + a.ks.d_counts[1] : direct_count(a);
-  const unsigned counted = slow_ctr ? *slow_ctr : total;
-  if ((SRC == SRC_SET || SRC == SRC_DIRECT) && !ACC && slow_ctr && a.stats_host && blockIdx.x == 0 && threadIdx.x == 0) {   // the pass's sample -> the host (launch_own)
-    __hip_atomic_store(a.stats_host, slow_ctr[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);       // not plain hits
-    __hip_atomic_store(a.stats_host + 1, slow_ctr[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // keys looked at
-  }
-  if (zero4 && blockIdx.x == 0 && threadIdx.x < 4) zero4[threadIdx.x] = 0;   // last kernel of this use: arm the next use's counters
-  if (counted == 0) return;
-  const bool listed = slow_ctr && counted <= a.item_cap;
-  if (slow_ctr && !listed) total = SRC != SRC_DIRECT ? a.ks.d_counts[0] + a.ks.d_counts[1] : direct_count(a);
-  const unsigned n = listed ? counted : total;
-  const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
-  const unsigned ngroups = (gridDim.x * blockDim.x) >> 4;
-  int fresh = 0, failed = 0;
-  for (unsigned i = gi; i < n; i += ngroups) {
-    if (listed) {
-      uint4 w0 = f0, w1 = f1;
-      if (i != gi) {
-        w0 = reinterpret_cast<const uint4*>(a.items + i)[0];
-        w1 = reinterpret_cast<const uint4*>(a.items + i)[1];
-      }
-      const i64 key = (i64)(((u64)w0.y << 32) | w0.x);
-      locked_upsert_kv<G>(a.v, a.vals, key, w0.z, ((u64)w1.y << 32) | w1.x, a.ai, a.sp, sub, gshift, fresh, failed, (w1.z & 1u) != 0, w1.w, nullptr,
-                          ACC ? ((w1.z & 2u) ? 1 : 2) : 0, a.acc_dt);
-      if (sub == 0) a.dflag[w0.w] = 0;
-    } else {
-      if (slow_ctr && a.dflag[i] != 4) continue;
-      if (SRC == SRC_PLAN) locked_upsert_one<G>(a.v, a.vals, a.scores, a.ks, a.ai, a.sp, i, sub, gshift, fresh, failed);
-      else if (SRC == SRC_SET) {
-        const uint2 pc = set_pc(a.ks.sent + a.ks.uslot[i]);
-        const u64 in_one = a.scores ? a.scores[pc.x - 1] : 1;
-        locked_upsert_kv<G>(a.v, a.vals, a.ks.ukeys[i], pc.x - 1, a.sp.strategy == TFRA_EVICT_LFU ? (a.scores ? in_one : (u64)pc.y) : in_one,
-                            a.ai, a.sp, sub, gshift, fresh, failed);
-      } else locked_upsert_kv<G>(a.v, a.vals, a.keys[i], i, a.scores ? a.scores[i] : 1, a.ai, a.sp, sub, gshift, fresh, failed, false, 0, nullptr,
-                                 ACC ? (a.exists[i] ? 1 : 2) : 0, a.acc_dt);
-      if (slow_ctr && sub == 0) a.dflag[i] = 0;
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1) { fresh += __shfl_xor(fresh, off); failed += __shfl_xor(failed, off); }
-  if (lane == 0) {
-    if (fresh) size_add(a.v, (blockIdx.x * blockDim.x + threadIdx.x) >> 6, fresh);
-    if (failed) atomicAdd(a.v.err_count, (unsigned)failed);
-  }
-}
-
-// 16-lane minimum of (score, index) pairs with DPP row rotations (row_ror 8, 4, 2, 1: every lane ends up with the row's
-// minimum; ~8 cycles per move instead of an LDS round trip per __shfl_xor — the four dependent rounds of the victim choice
-// were a fifth of the 4 us a wave spends deciding)
-__device__ __forceinline__ unsigned dpp_ror(unsigned x, int n) {
-  switch (n) {
-    case 8: return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x128, 0xf, 0xf, false);
-    case 4: return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x124, 0xf, 0xf, false);
-    case 2: return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x122, 0xf, 0xf, false);
-    default: return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x121, 0xf, 0xf, false);
-  }
-}
-// Victim choice among the 30 slots of (b0, b1), as select_victim_merged (tfra_device.h): minimum score, the lower index
-// (b0's slots before b1's) on ties, EMPTY counts as score 0, LOCKED slots are not candidates.
-__device__ __forceinline__ void select_victim_dpp(u64 b0, u64 b1, const i64 (&kk2)[2], const i64 (&sc2)[2], int sub, int gshift,
-                                                  u64& best_score, u64& best_word) {
-  u64 s0 = (u64)sc2[0], s1 = (u64)sc2[1];
-  if (kk2[0] == EMPTY_KEY) s0 = 0;
-  if (kk2[1] == EMPTY_KEY) s1 = 0;
-  if (sub >= SLOTS || kk2[0] == LOCKED_KEY) s0 = ~0ULL;
-  if (sub >= SLOTS || kk2[1] == LOCKED_KEY) s1 = ~0ULL;
-  u64 my = s0;
-  unsigned idx = (unsigned)sub;
-  if (s1 < s0) { my = s1; idx = 16u + (unsigned)sub; }
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) {
-    const u64 os = ((u64)dpp_ror((unsigned)(my >> 32), o) << 32) | dpp_ror((unsigned)my, o);
-    const unsigned oi = dpp_ror(idx, o);
-    if (os < my || (os == my && oi < idx)) { my = os; idx = oi; }
-  }
-  best_score = my;
-  best_word = (idx >= 16u ? b1 : b0) * 16 + (idx & 15u);
-}
-
-// keep_live over U in-flight values (U = 2 or 4)
-template <int U, typename T>
-__device__ __forceinline__ void keep_live_u(T (&x)[U]) {
-  if (U == 4) keep_live(x[0], x[1], x[2], x[3]);
-  else keep_live(x[0], x[U - 1], x[0], x[U - 1]);
-}
-template <int U, typename T>
-__device__ __forceinline__ void keep_live_u2(T (&x)[U][2], int k) {
-  if (U == 4) keep_live(x[0][k], x[1][k], x[2][k], x[3][k]);
-  else keep_live(x[0][k], x[U - 1][k], x[0][k], x[U - 1][k]);
-}
-
-// One batch of 16 keys of one wave.  What is scalar per key — the key word, its hash, the two ownership claims, the plan
-// record (count, last position), the input score — is done ONE LANE PER KEY (lane j of every group holds key j; group 0
-// issues the claims): one instruction stream for 16 keys.  What needs a whole line — the four bucket lines, the ballots,
-// the victim choice, the row copy — is done one 16-lane group per key, 4 keys per group in flight (the scalar results
-// reach the group by shuffle).  SIMPLE: the common shape — rows without optimizer slots, LRU scores, no caller scores —
-// with everything else compiled out.
-// ORDER (round 3, from the phase timings above): the clock is read first (s_memrealtime is slow); every cross-lane
-// broadcast is issued before the first use of any; the claims are issued BEHIND the line loads and consumed LAST — memory
-// returns in order, so a claim issued first would hold back the lines, and consumed first it would stall the decisions,
-// which do not need it.
-// gj = the lane's key: index into the plan's dense keys / the caller's key array (clamped to a valid index; `valid` says
-// whether the lane's key is real).
-// U: keys per 16-lane group in flight (the wave's batch is 4 U keys: lanes 0 .. 4U-1 of every group hold them).  2 for up
-// to a batch's worth of keys (22.7 K keys are 1420 waves of 16 keys on 1024 SIMDs: the 4 us of dependent cross-lane work
-// per wave halve, the waves double and still fit in one round), 4 beyond.
-// CF (the overlapped step, tfra_step_impl.h): the lookup of the NEXT batch runs beside this pass and reads the table rows of every key
-// that is not in this batch — an entry this pass is about to EVICT must not be one of them: `cf` = the next batch's plan; a victim
-// that is in it defers the new key to the remainder pass (which runs after that lookup and corrects its output).
-// ACC (SRC_DIRECT, 16-B granules): the reference's insert_or_accum of unique keys (accumrase_fn, cuckoohash_map.hh:619-633;
-// HkvHashTableOfTensorsGpu::Accum, K/hkv_hashtable_op_gpu.cu.cc:292-335) instead of an assign — a.exists[i] set: the key is
-// expected in the table, present => row += value row (one add per element), absent => dropped; not set: absent => insert,
-// present => dropped.  A dropped key writes nothing, whatever its claims say (the keys of a call are unique: any order of
-// them is a valid serial order).
-template <int G, bool SIMPLE, int SRC, int U, bool CF = false, bool ACC = false, bool HF = false>
-__device__ __forceinline__ void own_batch16(const OwnArgs& a, const OwnFlags fl, unsigned gj, bool valid, unsigned gen, unsigned* slow_ctr,
-                                            int lane, int& fresh, const SetProbe* cf = nullptr, unsigned* cf_stat = nullptr,
-                                            i64 kgiven = 0, unsigned lastgiven = 0, const SetProbe* own_plan = nullptr, int* not_hits = nullptr) {
-  constexpr bool hf = HF;   // (CF && HF: the overlapped step's launch; HF alone: upsert_own_kernel over a SET plan, victims checked against that plan)
-  const u64* const scores = SIMPLE ? nullptr : a.scores;
-  const TableView& v = a.v;
-  const CsrKeys& ks = a.ks;
-  const int sub = lane & 15, gshift = lane & 48, grp = lane >> 4;
-  const u64 now = fl.lru_like ? (u64)wall_clock64() : 0;   // one clock read for the 16 keys (LRU scores tie within a wave)
-  // ---- one lane per key ------------------------------------------------------------------------------------
-  i64 kreg;
-  unsigned kmreg = 0, lastreg = gj;
-  u64 insreg = 1;
-  if (SRC == SRC_PLAN) { kreg = ks.dkeys[gj]; kmreg = ks.keymap[gj]; }
-  else if (SRC == SRC_SET) { kreg = ks.ukeys[gj]; kmreg = ks.uslot[gj]; }
-  else if (SRC == SRC_GIVEN) { kreg = kgiven; lastreg = lastgiven; }
-  else kreg = a.keys[gj];
-  const unsigned exreg = ACC ? (unsigned)a.exists[gj] : 0u;
-  u64 hreg;
-  const unsigned b0reg = (unsigned)bucket0(kreg, v.nb, hreg);
-  const unsigned b1reg = (unsigned)bucket1(hreg, b0reg, v.nb);
-  const bool reserved = is_reserved_key(kreg);   // sentinel keys live in the side rows: the general path
-  // ---- one group per key: every broadcast first, then the lines of 4 keys in flight -------------------------
-  i64 key[U], kk[U][2], sc[U][2];
-  unsigned b0[U], b1[U], gk[U];
-  bool on[U];
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const int j = u * 4 + grp;
-    key[u] = shfl_i64(kreg, j);
-    b0[u] = (unsigned)__shfl((int)b0reg, j);
-    b1[u] = (unsigned)__shfl((int)b1reg, j);
-    gk[u] = (unsigned)__shfl((int)gj, j);
-    on[u] = __shfl((int)(valid && !reserved), j) != 0;
-  }
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    // plain loads: everything written before this launch is visible, and nobody else writes a bucket this key owns
-    kk[u][0] = key_line(v, b0[u])[sub];
-    kk[u][1] = key_line(v, b1[u])[sub];
-    // (HF, the step launch: 96 % of the keys are hits, which write their score word and never read a score line — the lines are fetched
-    // below, and only by the waves that hold a key in need of a victim: 5.8 MB less random reads per launch on the metric's stream)
-    sc[u][0] = (fl.spec && !hf) ? (i64)score_line(v, b0[u])[sub] : 0;
-    sc[u][1] = (fl.spec && !hf) ? (i64)score_line(v, b1[u])[sub] : 0;
-  }
-  // ---- per key again, while the lines travel: count and last position from the plan record, input score ---
-  if (SRC == SRC_PLAN) {
-    const bool hot = (kmreg & KM_MANY) != 0;
-    const unsigned* rec = (hot ? ks.hrec : ks.crec) + (size_t)(kmreg & ~KM_MANY) * REC_WORDS;
-    const uint2 cl = *reinterpret_cast<const uint2*>(rec + 2);   // (count, last position of a key with few occurrences)
-    const unsigned cnt = cl.x;
-    lastreg = cl.y;
-    if (hot) lastreg = ks.hent[rec[5]];                          // many: where it is stored
-    lastreg &= E_POS;
-    const u64 in_one = scores ? scores[lastreg] : 1;
-    insreg = a.sp.strategy == TFRA_EVICT_LFU ? (scores ? in_one : (u64)cnt) : in_one;
-  } else if (SRC == SRC_SET) {
-    const uint2 pc = set_pc(ks.sent + kmreg);   // (last position + 1, occurrences) of the key's slot in the plan's table
-    lastreg = pc.x - 1;
-    const u64 in_one = scores ? scores[lastreg] : 1;
-    insreg = a.sp.strategy == TFRA_EVICT_LFU ? (scores ? in_one : (u64)pc.y) : in_one;
-  } else if (SRC != SRC_GIVEN) {
-    insreg = scores ? scores[lastreg] : 1;
-  }
-  // the claims, behind the loads in program order (a clamped duplicate must not claim: it would lock out the real key)
-  unsigned c0 = 0, c1 = 0;
-  if (!hf && grp == 0 && valid && !reserved) {
-    c0 = atomicExch(a.tags + b0reg, gen);
-    c1 = atomicExch(a.tags + b1reg, gen);
-  }
-  keep_live_u2<U>(kk, 0);
-  keep_live_u2<U>(kk, 1);
-  if (fl.spec && !hf) {
-    keep_live_u2<U>(sc, 0);
-    keep_live_u2<U>(sc, 1);
-  }
-  // ---- what each key would do, from its lines alone (the claims are still travelling) -----------------------
-  u64 word[U], in_s[U];
-  int act[U];   // 0 nothing to write, 1 assign (hit), 2 new key in a free slot, 3 new key over an evicted entry
-  int why[U];   // 0 handled, 1 lost a claim, 2 cannot be placed within the home buckets: the locked protocol
-  bool flag_b0[U];   // the key goes to b1 although b0 never overflowed before: finds must go on to b1
-  unsigned bxc[U];   // bucket beyond the home buckets the key was found in (it must be claimed too); ~0: none
-  bool ex[U];        // ACC: the caller's exists flag
-  bool need_v[U], ovf0_u[U];   // HF: the key needs a victim (score lines fetched below); b0's overflow flag as the decision saw it
-  auto choose_victim = [&](int u, bool ovf0) {
-    u64 best_score, best_word;
-    select_victim_dpp(b0[u], b1[u], kk[u], sc[u], sub, gshift, best_score, best_word);
-    const u64 cmp = a.sp.strategy == TFRA_EVICT_EPOCHLFU ? ((a.sp.epoch << 32) | in_s[u]) : in_s[u];
-    if (fl.lru_like || cmp >= best_score) {   // else: not admitted, dropped like HKV does
-      word[u] = best_word;
-      act[u] = 3;
-      flag_b0[u] = !ovf0 && (best_word >> 4) == b1[u];
-      if (CF || HF) {
-        const int vsrc = gshift + (int)(best_word & 15u);
-        const i64 ka = shfl_i64(kk[u][0], vsrc), kb = shfl_i64(kk[u][1], vsrc);
-        const i64 vk = (best_word >> 4) == (u64)b1[u] ? kb : ka;
-        // CF: the next lookup wants it; HF: nor may it be a key of THIS batch — those are written without a claim, see below
-        bool wanted = false;
-        if (vk != EMPTY_KEY) {
-          if (CF && HF) wanted = set_contains_either_group(*cf, *own_plan, vk, sub, gshift);
-          else if (CF) wanted = set_contains_group(*cf, vk, sub, gshift);
-          else wanted = own_plan ? set_contains_group(*own_plan, vk, sub, gshift) : true;   // (no plan to ask: defer — launch_own never picks HF then)
-        }
-        if (wanted) {   // deferred to the remainder
-          act[u] = 0; why[u] = 3;
-          if (cf_stat && sub == 0) atomicAdd(cf_stat, 1u);
-        }
-      }
-    }
-  };
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    need_v[u] = false; ovf0_u[u] = false;
-    ex[u] = ACC && __shfl((int)exreg, u * 4 + grp) != 0;
-    in_s[u] = 1;
-    if (!fl.lru_like) in_s[u] = (u64)shfl_i64((i64)insreg, u * 4 + grp);   // (LRU-type scores ignore the input score)
-    act[u] = 0; why[u] = 0; word[u] = 0; flag_b0[u] = false; bxc[u] = ~0u;
-    if (!on[u]) continue;
-    const unsigned hit0 = (unsigned)(__ballot(sub < SLOTS && kk[u][0] == key[u]) >> gshift) & 0x7fffu;
-    const unsigned hit1 = (unsigned)(__ballot(sub < SLOTS && kk[u][1] == key[u]) >> gshift) & 0x7fffu;
-    const unsigned emp0 = (unsigned)(__ballot(sub < SLOTS && kk[u][0] == EMPTY_KEY) >> gshift) & 0x7fffu;
-    const unsigned emp1 = (unsigned)(__ballot(sub < SLOTS && kk[u][1] == EMPTY_KEY) >> gshift) & 0x7fffu;
-    const bool ovf0 = ((__ballot(sub == 15 && ((u64)kk[u][0] & META_OVF0)) >> gshift) & 0xffffu) != 0;
-    const bool ovf1 = ((__ballot(sub == 15 && ((u64)kk[u][1] & META_OVF1)) >> gshift) & 0xffffu) != 0;
-    if (hit0) { word[u] = (u64)b0[u] * 16 + (__ffs(hit0) - 1); act[u] = 1; }
-    else if (hit1) { word[u] = (u64)b1[u] * 16 + (__ffs(hit1) - 1); act[u] = 1; }
-    else {
-      bool absent = !(ovf0 && ovf1);   // the flags end the search at b0 / b1
-      if (!absent) {
-        // The key may live further along (placed while the table still walked): follow the flags with READS.  Found in
-        // bucket bx: it claims bx too — every key that could evict from bx has bx as a home bucket and claimed it at its
-        // start, so the exchange tells who goes first.
-        unsigned bx = b1[u];
-#pragma unroll 1
-        for (int stepn = 0; stepn < 8 && !absent && !act[u] && !why[u]; ++stepn) {
-          bx = bx + 1 == (unsigned)v.nb ? 0u : bx + 1;
-          const i64 kx = load_key_coherent(key_line(v, bx) + sub);
-          const unsigned hitx = (unsigned)(__ballot(sub < SLOTS && kx == key[u]) >> gshift) & 0x7fffu;
-          if (hitx) { word[u] = (u64)bx * 16 + (__ffs(hitx) - 1); act[u] = 1; if (bx != b0[u] && bx != b1[u]) bxc[u] = bx; }
-          else if (!((__ballot(sub == 15 && ((u64)kx & META_OVF1)) >> gshift) & 0xffffu)) absent = true;
-          else if (stepn == 7) why[u] = 2;   // a long chain (an unbounded table): the general path
-        }
-      }
-      if (absent && !(ACC && ex[u])) {   // not in the table (ACC: absent & exists is dropped)
-        if (emp0) { word[u] = (u64)b0[u] * 16 + (__ffs(emp0) - 1); act[u] = 2; }   // first empty slot in probe order
-        else if (emp1) { word[u] = (u64)b1[u] * 16 + (__ffs(emp1) - 1); act[u] = 2; flag_b0[u] = !ovf0; }
-        else if (fl.spec) {
-          // both home buckets full on a table that no longer walks: replace the minimum-score entry of the 30 slots
-          if (hf) need_v[u] = true;                   // (its score lines are not here yet: below)
-          else choose_victim(u, ovf0);
-          ovf0_u[u] = ovf0;
-        } else why[u] = 2;   // a table that still walks (not at capacity / unbounded): placed further along by the general path
-      }
-    }
-  }
-  if (hf && fl.spec) {
-    bool any_v = false;
-#pragma unroll
-    for (int u = 0; u < U; ++u) any_v = any_v || need_v[u];
-    if (__ballot(any_v)) {   // (wave-uniform) one more round trip, for the waves that hold a key in need of a victim
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        sc[u][0] = (i64)score_line(v, b0[u])[sub];
-        sc[u][1] = (i64)score_line(v, b1[u])[sub];
-      }
-      keep_live_u2<U>(sc, 0);
-      keep_live_u2<U>(sc, 1);
-#pragma unroll
-      for (int u = 0; u < U; ++u) if (need_v[u]) choose_victim(u, ovf0_u[u]);
-    }
-  }
-  // ---- now the claims -------------------------------------------------------------------------------------------
-  const unsigned lostreg = reserved ? 2u : ((c0 == gen || c1 == gen) ? 1u : 0u);   // (group 0's lanes)
-  // HF (the overlapped step): a HIT needs no claim.  It writes its own row and score word and nothing else of the bucket; the only
-  // writer that could take its slot away is an eviction, and an eviction never takes a key of this batch (the victim check above
-  // looks the victim up in the batch's own plan too).  Only the keys that CHANGE a bucket — a new key into a free slot or over a
-  // victim — claim their two home buckets, now, behind the decision: 96 % of a Zipf batch's keys issue no atomic at all, two keys of
-  // a batch sharing a home bucket no longer collide unless both are new, and the item list is empty in nearly every step.
-  bool lost_hf[U];
-#pragma unroll
-  for (int u = 0; u < U; ++u) lost_hf[u] = false;
-  if (hf) {
-    bool any = false;
-#pragma unroll
-    for (int u = 0; u < U; ++u) { lost_hf[u] = false; any = any || act[u] >= 2; }
-    if (__ballot(any)) {   // (wave-uniform: one more round trip for the waves that hold a new key)
-      unsigned cx[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        cx[u] = 0;
-        if (act[u] >= 2 && sub < 2) cx[u] = atomicExch(a.tags + (sub == 0 ? b0[u] : b1[u]), gen) == gen ? 1u : 0u;
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) lost_hf[u] = ((__ballot(cx[u] != 0) >> gshift) & 0xffffu) != 0;
-    }
-  }
-  unsigned last[U], hint[U];
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const int j = u * 4 + grp;
-    last[u] = (unsigned)__shfl((int)lastreg, j);
-    const bool real = __shfl((int)valid, j) != 0;
-    const int lost = hf ? ((real && !on[u]) ? 2 : (lost_hf[u] ? 1 : 0)) : __shfl((int)lostreg, j);   // (without HF: lane j of group 0 made the claims)
-    hint[u] = 0;
-    if (lost) {
-      if (lost == 1 && act[u] == 1 && (word[u] >> 32) == 0) hint[u] = 1;   // found, not written: the remainder pass locks this very slot
-      act[u] = 0; why[u] = lost;
-    }
-    if (!hf && bxc[u] != ~0u && act[u]) {   // (rare) found beyond its home buckets: that bucket's claim
-      unsigned cx = 0;
-      if (sub == 0) cx = atomicExch(a.tags + bxc[u], gen) == gen ? 1u : 0u;
-      if (__shfl((int)cx, gshift)) { act[u] = 0; why[u] = 1; }
-    }
-    if (!real) { act[u] = 0; why[u] = 0; }
-    if (ACC) {
-      if (act[u] == 1 && !ex[u]) act[u] = 0;                                   // present & !exists: dropped
-      if (why[u] == 1 && hint[u] && !ex[u]) { why[u] = 0; hint[u] = 0; }        // (the same, seen without the claim)
-      if (why[u] == 1 && !hint[u] && ex[u] && bxc[u] == ~0u) { }               // lost its claim, not seen: the remainder looks again
-      if (ex[u]) hint[u] |= 2u;                                                // the item carries the flag
-    }
-    if (act[u] && flag_b0[u] && sub == 15) atomicOr((u64*)(key_line(v, b0[u]) + 15), META_OVF0);   // finds go on to b1
-    if (sub == 0 && why[u]) { if (CF) __hip_atomic_store(a.dflag + gk[u], (uint8_t)4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else a.dflag[gk[u]] = 4; }
-    fresh += (act[u] == 2 && sub == 0);
-    if (not_hits) *not_hits += (real && act[u] != 1 && sub == 0);   // (a new key, an eviction, a key handed to the remainder)
-  }
-  {   // left-over keys of the wave -> the list: one atomic add for all of them
-    u64 sm[U];
-    unsigned nslow = 0;
-#pragma unroll
-    for (int u = 0; u < U; ++u) { sm[u] = __ballot(why[u] != 0 && sub == 0); nslow += (unsigned)__popcll(sm[u]); }
-    if (nslow) {
-      unsigned at = 0;
-      if (lane == 0) at = atomicAdd(slow_ctr, nslow);
-      at = (unsigned)__builtin_amdgcn_readfirstlane((int)at);
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        if (why[u] != 0 && sub < 2) {
-          const unsigned pos = at + (unsigned)__popcll(sm[u] & ((1ULL << gshift) - 1));
-          if (pos < a.item_cap) {
-            uint4 w;
-            if (sub == 0) w = make_uint4((unsigned)(u64)key[u], (unsigned)((u64)key[u] >> 32), last[u], gk[u]);
-            else w = make_uint4((unsigned)in_s[u], (unsigned)(in_s[u] >> 32), hint[u], (unsigned)word[u]);
-            if (CF) store_wt16(reinterpret_cast<unsigned char*>(a.items + pos) + sub * 16, w);   // (read by the tail role of the same launch)
-            else *reinterpret_cast<uint4*>(reinterpret_cast<unsigned char*>(a.items + pos) + sub * 16) = w;
-          }
-        }
-        at += (unsigned)__popcll(sm[u]);
-      }
-    }
-  }
-  // value rows of the 4 keys: loads together (always from a valid address), stores for the keys that write
-  typedef typename Granule<G>::T T;
-  unsigned char* dst[U];
-#pragma unroll
-  for (int u = 0; u < U; ++u) dst[u] = row_at(v, word[u] >> 4, (unsigned)word[u] & 15u);
-  for (unsigned off = sub * G; off < v.field_bytes; off += 16 * G) {
-    T tmp[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) tmp[u] = *reinterpret_cast<const T*>(a.vals + (u64)last[u] * (u64)v.field_bytes + off);
-    keep_live_u<U>(tmp);
-    if (ACC && G == 16) {   // accumulate: the rows themselves travel with the deltas (a key that only inserts adds nothing)
-      T cur[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) cur[u] = *reinterpret_cast<const T*>(dst[u] + off);
-      keep_live_u<U>(cur);
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-        if (act[u] == 1) *reinterpret_cast<uint4*>(&tmp[u]) = add16_dt(*reinterpret_cast<uint4*>(&cur[u]), *reinterpret_cast<uint4*>(&tmp[u]), a.acc_dt);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      if (!act[u]) continue;
-      // write-through: the rows leave L2 during the kernel instead of at the boundary to the next one
-      if (G == 16) store_wt16(dst[u] + off, *reinterpret_cast<uint4*>(&tmp[u]));
-      else __hip_atomic_store(reinterpret_cast<T*>(dst[u] + off), tmp[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    if (!act[u]) continue;
-    if (act[u] >= 2) {
-      if (!SIMPLE && v.n_fields > 1) {
-        for (unsigned f = 1; f < v.n_fields; ++f) {   // slot fields of a brand-new row start at aux_init
-          const unsigned pat = a.ai.pattern[(f - 1) & 3];
-          unsigned char* q = dst[u] + f * v.field_bytes;
-          if ((v.field_bytes & 3) == 0)
-            for (unsigned off = sub * 4; off < v.field_bytes; off += 64)
-              __hip_atomic_store(reinterpret_cast<unsigned*>(q + off), pat, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          else
-            for (unsigned off = sub; off < v.field_bytes; off += 16)
-              __hip_atomic_store(q + off, (unsigned char)(pat >> (8 * (off % a.ai.elem_bytes))), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-      if (sub == 0) { if (CF) store_wt8(key_word(v, word[u]), (u64)key[u]); else *key_word(v, word[u]) = key[u]; }   // owned bucket: a plain store (CF: write-through, the
-                                                                                                                   // left-over keys follow in the same launch)
-    }
-    if (!fl.with_scores) continue;
-    if (fl.lru) { if (sub == 0) { if (CF) store_wt8(score_word(v, word[u]), now); else *score_word(v, word[u]) = now; } }
-    else if (act[u] == 3 && a.sp.strategy == TFRA_EVICT_LFU) { if (sub == 0) store_wt8(score_word(v, word[u]), in_s[u]); }   // the slot starts a new life
-    else update_score<true>(v, (i64)((word[u] >> 4) * SLOTS + (word[u] & 15)), act[u] >= 2, a.sp.strategy, in_s[u], a.sp.epoch, sub);
-  }
-}
-
-// HF (SRC_SET, round 6 — what the overlapped step's write-back role has done since round 5): a HIT claims nothing and reads no score
-// line; a key that changes a bucket claims behind its decision, and a victim that is a key of this very batch (a probe of the batch's own
-// SET plan) sends the new key to the remainder.  On a Zipf batch over resident ids (96 % hits) a key then touches its two key lines, its
-// value row and its row instead of four lines, two claim words and the rows; a batch of mostly NEW keys pays one more dependent trip per
-// wave (the score lines, then the claims) — the host picks the form from a sample of the previous write-back (launch_own).
-// SAMPLE: the launch leaves the sample described below (compiled out where nobody reads it: a caller's keys on a table that evicts)
-template <int G, bool SIMPLE, int SRC, int U = 4, bool ACC = false, bool HF = false, bool SAMPLE = false>
-__global__ __launch_bounds__(256) void upsert_own_kernel(const OwnArgs a, OwnCtrs* ctr, unsigned own_gen, unsigned* progress,
-                                                         unsigned progress_val) {
-  const int lane = threadIdx.x & 63;
-  const unsigned total = SRC != SRC_DIRECT ? a.ks.d_counts[0] + a.ks.d_counts[1] : direct_count(a);
-  const unsigned nwaves = (gridDim.x * blockDim.x) >> 6;
-  const unsigned wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  int fresh = 0, not_hits = 0, looked = 0;
-  // every 128th wave tells how many of its keys were not plain hits — ONE 64-bit add per such wave (every 16th wave with two adds: ~180
-  // same-line atomics piling up at the end of a one-round kernel, 9.9 -> 12.4 us for the DIRECT pass of 22 K keys under rocprofv3)
-  const bool sampled = SAMPLE && (wave & 127u) == 0;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (progress) {   // see hot_sums_kernel; [1]: the keys of this write-back — the host sizes the next one's grid from it
-      __hip_atomic_store(progress, progress_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      __hip_atomic_store(progress + 1, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    if (SRC == SRC_PLAN && a.ks.d_counts[5]) atomicAdd(a.v.err_count, a.ks.d_counts[5]);
-  }
-  const OwnFlags fl = own_setup<SIMPLE>(a);
-  for (unsigned wbase = wave * (4 * U); wbase < total; wbase += nwaves * (4 * U)) {
-    const unsigned i = wbase + (unsigned)(lane & 15);
-    const bool valid = (lane & 15) < 4 * U && i < total;
-    own_batch16<G, SIMPLE, SRC, U, false, ACC, HF>(a, fl, min(i, total - 1), valid, own_gen, &ctr->n_a, lane, fresh, nullptr, nullptr, 0, 0,
-                                                   (HF && a.own_set.ent) ? &a.own_set : nullptr, (SAMPLE && sampled) ? &not_hits : nullptr);
-    if (SAMPLE) looked += (valid && lane < 16);
-  }
-  for (int off = 32; off > 0; off >>= 1) fresh += __shfl_xor(fresh, off);
-  if (lane == 0 && fresh) size_add(a.v, wave, fresh);
-  if (SAMPLE && sampled) {
-    for (int off = 32; off > 0; off >>= 1) { not_hits += __shfl_xor(not_hits, off); looked += __shfl_xor(looked, off); }
-    if (lane == 0 && looked)   // spare[1] (low word: keys looked at) | spare[2] (high word: not plain hits), 8-byte aligned
-      atomicAdd(reinterpret_cast<unsigned long long*>(&ctr->spare[1]), ((unsigned long long)(unsigned)not_hits << 32) | (unsigned long long)(unsigned)looked);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
 // SET plan: the id-only half of an ASSIGN write-back (tfra_sparse_plan_build with dim 0) in ONE kernel.
 // An assign needs, per distinct id, the position of its LAST occurrence (and how often it occurred: LFU scores) — not the
 // CSR of all positions the gradient sums need.  The CSR plan's three kernels take 29 us for 131 072 ids and six of the
@@ -1677,13 +545,6 @@ __global__ __launch_bounds__(256) void upsert_own_kernel(const OwnArgs a, OwnCtr
 // The two sentinel key values have slots of their own behind the table (no hashing: EMPTY_KEY is the free-slot marker).
 constexpr int SP_NT = 1024;
 constexpr unsigned SP_LDS = 2048;
-constexpr unsigned SET_PAD = 4;   // entries behind the two sentinel slots, never used: a probe reads 4 consecutive entries
-struct SetTab {   // one of the plan's two tables
-  SetEnt* ent;      // [m2 + 2 + SET_PAD]  key: EMPTY_KEY = free (the two sentinel slots [m2], [m2 + 1]: EMPTY_KEY = free, else taken)
-  i64* ukeys;       // [n] dense list: the distinct keys, in no particular order
-  unsigned* uslot;  // [n] their slots
-  unsigned* count;  // number of distinct keys of the table's current use (zero before its build)
-};
 
 // COUNTS: also count the occurrences of every id (LFU scores without caller scores; tfra_sparse_plan_read)
 // INDEX: the occurrence-count word of a key's table entry receives the key's position in the dense list instead (tfra_unique_unordered)
@@ -1895,10 +756,6 @@ __global__ __launch_bounds__(256) void unique_idx_kernel(size_t n, const i64* __
   idx_out[i] = found;
 }
 
-#define TFRA_STEP_DEVICE_PART
-#include "tfra_step_impl.h"
-#undef TFRA_STEP_DEVICE_PART
-
 __global__ void fill_setent_kernel(SetEnt* p, size_t n) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
     *reinterpret_cast<uint4*>(p + i) = make_uint4(0u, 0x80000000u, 0u, 0u);   // {EMPTY_KEY, 0, 0}
@@ -1908,74 +765,6 @@ __global__ void fill_i64_kernel(i64* p, size_t n, i64 v) {
 }
 
 }  // namespace
-
-// ---------------------------------------------------------------------------------------------
-struct tfra_sparse_plan {
-  int device = 0;
-  void* buf = nullptr;
-  size_t bytes = 0;
-  // layout of the last build
-  size_t n = 0, npad = 0, ntiles = 0;
-  unsigned P = 0, cm = 0;
-  int dim = 0;
-  unsigned* cursors = nullptr;
-  CsrDesc ds{};
-  CsrOut out{};
-  unsigned* tile_entries = nullptr;
-  unsigned short* run_start = nullptr;
-  unsigned* tile_len = nullptr;
-  uint4* drec = nullptr;
-  unsigned* keymap = nullptr;
-  i64* dkeys = nullptr;
-  unsigned* binmap = nullptr;
-  unsigned* d_counts = nullptr;
-  uint8_t* dflag = nullptr;
-  size_t dflag_len = 0;
-  OwnItem* slow_items = nullptr;   // [SLOW_CAP] left-over keys of the ownership pass of a write-back (self-contained items)
-  unsigned* any_deferred = nullptr;   // = use_gen of the last write-back that deferred a key to its eviction phase
-  mutable unsigned use_gen = 0;
-  mutable unsigned ups_uses[2] = {0, 0};   // upsert_planned uses of the CSR buffer / of the SET buffer: the parity selects the left-over
-                                           // counter set of THAT buffer (each buffer has its own two sets and its own flag bytes: a plan
-                                           // object rebuilt with dim > 0, then dim 0, then dim > 0 again must find its CSR buffer's sets
-                                           // where its last CSR use left them)
-  float* partial = nullptr;
-  int* prow_dest = nullptr;        // [partial rows] scratch of tfra_plan_positions_to
-  bool armed = false;              // cursors/counters are zero (re-armed by the last kernel of the previous build)
-  unsigned* host_counts = nullptr; // pinned: [0] generation of the last COMPLETED build, [1..6] its counts
-  unsigned gen = 0;                // generation of the last enqueued build
-  bool ev_recorded = false;        // the last build ran on a side stream (tfra_table_step_prefetch)
-  unsigned last_used_step = 0;     // last step whose write-back read this plan
-  hipEvent_t built_ev = nullptr;   // recorded behind a build on a side stream (tfra_table_step_prefetch): complete = the plan is in memory
-  // SET plan (dim 0): its own buffer; two tables alternate (setplan_kernel)
-  int kind = 0;                    // 0 CSR, 1 SET
-  void* setbuf = nullptr;
-  size_t set_cap = 0;              // ids the set buffer was sized for
-  unsigned set_m2 = 0;
-  SetTab set_tab[2]{};
-  unsigned set_parity = 0;         // table of the last build
-  unsigned* set_counts = nullptr;  // the d_counts block of the set buffer: [8] any_deferred [12..19] OwnCtrs x2; [64 + 8 (2 p + use & 1) ..]
-                                   // the key counts of table p's uses ({0, distinct keys, 0, 0, 0, 0}: what CsrKeys::d_counts shows)
-  unsigned set_use[2] = {0, 0};    // uses of each table so far
-  bool built_counts = true;        // the last build counted occurrences
-  bool skip_counts_once = false;   // the NEXT build need not count occurrences (set by the table's own drivers for tables whose
-                                   // scores do not read them; a build through the public entry point always counts)
-  uint8_t* set_dflag = nullptr;
-  OwnItem* set_items = nullptr;
-  // the overlapped step (tfra_step_impl.h) builds a SET plan in two launches without atomics: launch 1 scatters every tile's
-  // distinct (id, last position) pairs into per-window segments, launch 2 builds each window of the table from its segments
-  void* segbuf = nullptr;
-  size_t seg_cap_ids = 0;          // ids the scatter buffers were sized for
-  SetEnt* seg_pairs = nullptr;     // [windows][tiles][SEG_CAP]
-  unsigned* seg_cnt = nullptr;     // [windows][tiles]
-  SetEnt* ovf_pairs = nullptr;     // pairs that did not fit their segment (an adversarial batch): appended with an atomic
-  unsigned* ovf_cnt = nullptr;
-  unsigned* ucnt = nullptr;        // [windows <= 256] distinct keys per window of the last list-less build (the step launch's BUILD role)
-  unsigned seg_tiles = 0;          // tiles of the last scatter
-  unsigned scat_use = 0;           // scatters into this object so far (its two overflow counters alternate)
-  const int64_t* scat_ids = nullptr;   // the batch whose pairs the segments hold (nullptr: none)
-  size_t scat_n = 0;
-  unsigned char tab_state[2] = {0, 0}; // TAB_EMPTY / TAB_LISTED / TAB_LISTLESS: what each table holds (setplan_prepare)
-};
 
 extern "C" int tfra_sparse_plan_create(int device, tfra_sparse_plan_t** out) {
   if (!out) return set_error(TFRA_ERR_INVALID, "sparse_plan_create: null out");
@@ -2081,7 +870,7 @@ static int setplan_prepare(tfra_sparse_plan* pl, size_t n, hipStream_t s, bool c
 // sized by its own length had 32 windows: 32 ids per segment on average, half the segments overflowed, and the launch took 36 us
 // instead of 17: scripts/mb_owner_step.py.)
 constexpr size_t LISTLESS_MIN_IDS = 131072;
-static int setplan_prepare_listless(tfra_sparse_plan* pl, size_t n, hipStream_t s) {
+int tfra::setplan_prepare_listless(tfra_sparse_plan* pl, size_t n, hipStream_t s) {
   int rc = setplan_ensure(pl, std::max(n, LISTLESS_MIN_IDS), s);
   if (rc) return rc;
   auto al = [](size_t x) { return (x + 255) / 256 * 256; };
@@ -2103,7 +892,7 @@ static int setplan_prepare_listless(tfra_sparse_plan* pl, size_t n, hipStream_t 
   return TFRA_OK;
 }
 // ... and the bookkeeping of the build launch: the object's other table takes the build
-static SetTab setplan_take_listless(tfra_sparse_plan* pl, size_t n) {
+void tfra::setplan_take_listless(tfra_sparse_plan* pl, size_t n) {
   const unsigned p = pl->set_parity ^ 1u;
   pl->gen += 1;
   const unsigned use = ++pl->set_use[p];
@@ -2113,9 +902,8 @@ static SetTab setplan_take_listless(tfra_sparse_plan* pl, size_t n) {
   pl->set_parity = p;
   pl->d_counts = pl->set_counts; pl->dflag = pl->set_dflag; pl->slow_items = pl->set_items; pl->any_deferred = pl->set_counts + 8;
   pl->n = n; pl->dim = 0; pl->kind = 1;
-  return pl->set_tab[p];
 }
-static int setplan_build(tfra_sparse_plan* pl, size_t n, const int64_t* ids, hipStream_t s, bool counts) {
+int tfra::setplan_build(tfra_sparse_plan* pl, size_t n, const int64_t* ids, hipStream_t s, bool counts) {
   SetPlanLaunch L;
   int rc = setplan_prepare(pl, n, s, counts, &L);
   if (rc) return rc;
@@ -2124,6 +912,8 @@ static int setplan_build(tfra_sparse_plan* pl, size_t n, const int64_t* ids, hip
   if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "sparse_plan_build: launch failed");
   return TFRA_OK;
 }
+
+void tfra::setplan_fill_empty(void* ent, size_t n, hipStream_t s) { fill_setent_kernel<<<1, 64, 0, s>>>(static_cast<SetEnt*>(ent), n); }
 
 extern "C" int tfra_sparse_plan_build(tfra_sparse_plan_t* pl, size_t n, const int64_t* ids, int dim, tfra_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
@@ -2229,7 +1019,7 @@ extern "C" int tfra_sparse_plan_build(tfra_sparse_plan_t* pl, size_t n, const in
 
 // the plan's counts as the host knows them: exact when the build has completed and published them
 // (step driver), otherwise the worst case (grid-stride kernels read the real counts from device memory)
-static void plan_grids(const tfra_sparse_plan* pl, unsigned* key_blocks, unsigned* bin_blocks) {
+void tfra::plan_grids(const tfra_sparse_plan* pl, unsigned* key_blocks, unsigned* bin_blocks) {
   size_t keys = pl->n, bins = (size_t)NSH * pl->out.br;
   if (pl->host_counts && (int)(*(volatile unsigned*)pl->host_counts - pl->gen) >= 0) {
     keys = (size_t)pl->host_counts[1] + pl->host_counts[2];
@@ -2240,363 +1030,6 @@ static void plan_grids(const tfra_sparse_plan* pl, unsigned* key_blocks, unsigne
   }
   *key_blocks = (unsigned)std::max<size_t>(1, (keys * 16 + 255) / 256);
   *bin_blocks = (unsigned)std::max<size_t>(1, bins);
-}
-
-static CsrKeys keys_of(const tfra_sparse_plan* pl) {
-  if (pl->kind == 1) {
-    const SetTab& tb = pl->set_tab[pl->set_parity];
-    return CsrKeys{nullptr, nullptr, nullptr, nullptr, nullptr, tb.count - 1, tb.ukeys, tb.uslot, tb.ent};
-  }
-  return CsrKeys{pl->keymap, pl->dkeys, pl->out.crec, pl->out.hrec, pl->out.hent, pl->d_counts, nullptr, nullptr, nullptr};
-}
-
-template <int KIND, class... CS>
-static void launch_apply_csr(Table* t, hipStream_t s, const tfra_sparse_plan* pl, const OptP& o, const float* grads,
-                             const float* default_row, unsigned key_blocks, const ScoreP& sp, const CS&... cs) {
-  TableView v = t->view_of(t->cur);
-  const float a0 = t->opts.aux_init[0], a1 = t->opts.aux_init[1];
-  const unsigned gen = ++pl->use_gen;
-  // one RESIDENT grid (the kernel is grid-stride: 125 registers = 4 blocks per CU x 256 CUs): a batch's 33 K keys as 2075 blocks were two
-  // rounds of dispatch plus a third of 27 blocks; 1024 blocks looping twice: configs[1] 55.2 -> 53.7 us per step (A/B on one box, twice)
-  static const unsigned grid_cap = [] { const char* e = getenv("TFRA_APPLY_GRID_CAP"); return e ? (unsigned)atoi(e) : 1024u; }();
-  if (grid_cap) key_blocks = std::min(key_blocks, grid_cap);
-  apply_csr_kernel<KIND, false><<<key_blocks, 256, 0, s>>>(v, o, pl->dim, grads, pl->partial, keys_of(pl), default_row, a0, a1, sp,
-                                                           pl->dflag, pl->any_deferred, gen, cs...);
-  if (sp.bounded)
-    apply_csr_kernel<KIND, true><<<key_blocks, 256, 0, s>>>(v, o, pl->dim, grads, pl->partial, keys_of(pl), default_row, a0, a1, sp,
-                                                            pl->dflag, pl->any_deferred, gen, cs...);
-}
-
-template <class... CS>
-static void launch_hot_sums(hipStream_t s, const tfra_sparse_plan* pl, const float* grads, unsigned bin_blocks, unsigned* progress,
-                            unsigned progress_val, const CS&... cs) {
-  const int dim = pl->dim;
-  switch ((dim + 63) / 64) {
-    case 1: hot_sums_kernel<1><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, progress, progress_val, cs...); break;
-    case 2: hot_sums_kernel<2><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, progress, progress_val, cs...); break;
-    case 3: hot_sums_kernel<3><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, progress, progress_val, cs...); break;
-    default: hot_sums_kernel<4><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, progress, progress_val, cs...); break;
-  }
-}
-
-template <class... CS>
-static void launch_apply(Table* t, hipStream_t s, const tfra_sparse_plan* pl, int kind, const OptP& o, const float* grads,
-                         const float* default_row, unsigned key_blocks, const ScoreP& sp, const CS&... cs) {
-  switch (kind) {
-    case TFRA_OPT_SGD: launch_apply_csr<TFRA_OPT_SGD>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
-    case TFRA_OPT_ADAM: launch_apply_csr<TFRA_OPT_ADAM>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
-    case TFRA_OPT_ADAGRAD: launch_apply_csr<TFRA_OPT_ADAGRAD>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
-    default: launch_apply_csr<TFRA_OPT_FTRL>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
-  }
-}
-
-// comb != nullptr (tfra_table_apply_planned_combined): grads is grad_out, position e's gradient is formed from comb[e]
-static int apply_planned_impl(tfra_table_t* tp, const tfra_opt_params* p, const tfra_sparse_plan_t* pl, const float* grads,
-                              const float* param_default_row, tfra_stream_t stream, unsigned* progress, unsigned progress_val,
-                              const CombEnt* comb = nullptr) {
-  // caller holds t->mu
-  Table* t = reinterpret_cast<Table*>(tp);
-  if (!t || !p || !pl) return set_error(TFRA_ERR_INVALID, "apply_planned: null argument");
-  hipStream_t s = (hipStream_t)stream;
-  int rc = t->enter(s);
-  if (rc) return rc;
-  if (pl->n == 0) return TFRA_OK;
-  if (!grads || !param_default_row) return set_error(TFRA_ERR_INVALID, "apply_planned: null buffer");
-  if (t->opts.value_dtype != TFRA_F32) return set_error(TFRA_ERR_UNSUPPORTED, "apply_planned: value_dtype must be float32");
-  if (p->kind < 0 || p->kind > TFRA_OPT_FTRL) return set_error(TFRA_ERR_INVALID, "apply_planned: unknown kind");
-  int need = p->kind == TFRA_OPT_SGD ? 0 : (p->kind == TFRA_OPT_ADAGRAD ? 1 : 2);
-  if (t->opts.aux_fields < need) return set_error(TFRA_ERR_INVALID, "apply_planned: table lacks optimizer slot fields");
-  if (t->opts.dim != pl->dim) return set_error(TFRA_ERR_INVALID, "apply_planned: the plan was built for another dim");
-  if (t->opts.device != pl->device && t->opts.device >= 0) return set_error(TFRA_ERR_INVALID, "apply_planned: plan and table live on different devices");
-  if ((((uintptr_t)grads | (uintptr_t)param_default_row) & 15))
-    return set_error(TFRA_ERR_UNSUPPORTED, "apply_planned: gradient / default buffers must be 16-B aligned");
-  rc = t->prepare_insert(pl->n, s);
-  if (rc) return rc;
-  unsigned key_blocks, bin_blocks;
-  plan_grids(pl, &key_blocks, &bin_blocks);
-  if (comb) launch_hot_sums(s, pl, grads, bin_blocks, progress, progress_val, CombRows{comb});
-  else launch_hot_sums(s, pl, grads, bin_blocks, progress, progress_val);
-  uint8_t* bounded_now;
-  rc = t->bounded_flags(1, s, &bounded_now);
-  if (rc) return rc;
-  const ScoreP sp{t->opts.strategy, t->global_epoch, bounded_now ? (t->dense ? 2 : 1) : 0};
-  OptP o{p->kind, p->lr, p->beta1, p->beta2, p->eps, p->l1, p->l2, p->lr_power, p->d_lr};
-  if (comb) launch_apply(t, s, pl, p->kind, o, grads, param_default_row, key_blocks, sp, CombRows{comb});
-  else launch_apply(t, s, pl, p->kind, o, grads, param_default_row, key_blocks, sp);
-  if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "apply_planned: launch failed");
-  step_epoch_public(t);
-  return TFRA_OK;
-}
-
-extern "C" int tfra_table_apply_planned(tfra_table_t* tp, const tfra_opt_params* p, const tfra_sparse_plan_t* pl,
-                                        const float* grads, const float* param_default_row, tfra_stream_t stream) {
-  Table* t = reinterpret_cast<Table*>(tp);
-  if (!t) return set_error(TFRA_ERR_INVALID, "apply_planned: null table");
-  std::lock_guard<std::mutex> lock(t->mu);
-  return apply_planned_impl(tp, p, pl, grads, param_default_row, stream, nullptr, 0);
-}
-
-// The write-back of an embedding_lookup_sparse: plan over the entry ids, gradient of position e = the combiner's backward
-// (tfra_combine_device.h) formed from grad_out in registers — apply_planned's kernels, reading grad_out through one more
-// indirection instead of an expanded [nnz, dim] gradient.
-extern "C" int tfra_table_apply_planned_combined(tfra_table_t* tp, const tfra_opt_params* p, const tfra_sparse_plan_t* pl,
-                                                 const float* grad_out, const int64_t* seg, const float* weights, int combiner,
-                                                 size_t n_rows, const float* param_default_row, tfra_stream_t stream) {
-  Table* t = reinterpret_cast<Table*>(tp);
-  if (!t || !p || !pl) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: null argument");
-  if (combiner < 0 || combiner > 2) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: combiner must be 0 (sum), 1 (mean) or 2 (sqrtn)");
-  std::lock_guard<std::mutex> lock(t->mu);
-  hipStream_t s = (hipStream_t)stream;
-  int rc = t->enter(s);   // the scratch below was last used on the table's previous stream
-  if (rc) return rc;
-  if (pl->kind != 0 || pl->dim != t->opts.dim) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: the plan was built for another dim");
-  if (t->opts.device != pl->device && t->opts.device >= 0) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: plan and table live on different devices");
-  const size_t nnz = pl->n;
-  if (nnz == 0) return TFRA_OK;
-  if (!grad_out || !seg || !param_default_row) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: null buffer");
-  if (n_rows == 0 || n_rows >= (1ULL << 30)) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: need 1 <= n_rows < 2^30");
-  if ((((uintptr_t)grad_out | (uintptr_t)param_default_row) & 15) || ((uintptr_t)seg & 7) || ((uintptr_t)weights & 3))
-    return set_error(TFRA_ERR_UNSUPPORTED, "apply_planned_combined: grad_out / default buffers must be 16-B aligned");
-  if (!t->comb_ws) {
-    tfra_workspace_t* w = nullptr;
-    rc = tfra_workspace_create(t->device, &w);
-    if (rc) return rc;
-    t->comb_ws = w;
-  }
-  tfra_workspace_t* ws = reinterpret_cast<tfra_workspace_t*>(t->comb_ws);
-  auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-  const size_t se_b = al(2 * n_rows * sizeof(int)), den_b = al(n_rows * sizeof(float));
-  rc = ws->ensure(se_b + den_b + al(nnz * sizeof(CombEnt)), s);
-  if (rc) return rc;
-  unsigned char* b = (unsigned char*)ws->buf;
-  CombEnt* ent = reinterpret_cast<CombEnt*>(b + se_b + den_b);
-  rc = comb_entries(s, nnz, seg, weights, combiner, n_rows, reinterpret_cast<int*>(b), reinterpret_cast<float*>(b + se_b), ent);
-  if (rc) return rc;
-  return apply_planned_impl(tp, p, pl, grad_out, param_default_row, stream, nullptr, 0, ent);
-}
-
-// ---- launch of the ownership write-back (plan keys or a caller's unique keys) --------------------------------
-template <int SRC>
-static void launch_own(hipStream_t s, int g, bool simple, const OwnArgs& a, size_t nkeys, OwnCtrs* ctr, OwnCtrs* next_ctr, unsigned og,
-                       unsigned rest_blocks, unsigned* progress, unsigned progress_val) {
-  // 4 waves x 16 keys per block and pass; up to a batch's worth of keys 8 keys per wave instead (own_batch16: U): twice the
-  // waves, half the dependent work in each, 86 instead of 118 registers.  Measured on the 10^9-slot table: 22.7 K keys
-  // 13.1 -> 11.3 us (the step 42.5 -> 41.1), 78 K keys the same kernel time alone and the step 64.0 -> 60.7 us; 4 keys per
-  // wave: nothing more on 22.7 K keys (40.8 us), 64.6 us on 78 K
-  const bool half = g == 16 && nkeys <= 131072;
-  const unsigned blocks = (unsigned)std::max<size_t>(1, half ? (nkeys + 31) / 32 : (nkeys + 63) / 64);
-  // a.tags == nullptr (TFRA_OPTION_NO_OWNER_TAGS, or the tags did not allocate): the locked protocol for every key
-  const bool smp = a.stats_host != nullptr && (SRC == SRC_SET || SRC == SRC_DIRECT) && g == 16;   // somebody reads the sample
-#define TFRA_OWN(GG, SS, UU)                                                                                  \
-  if (a.tags) {                                                                                               \
-    if (GG == 16 && smp) upsert_own_kernel<GG, SS, SRC, UU, false, false, GG == 16><<<blocks, 256, 0, s>>>(a, ctr, og, progress, progress_val); \
-    else upsert_own_kernel<GG, SS, SRC, UU><<<blocks, 256, 0, s>>>(a, ctr, og, progress, progress_val);       \
-    upsert_rest_kernel<GG, SRC><<<rest_blocks, 256, 0, s>>>(a, &ctr->n_a, reinterpret_cast<unsigned*>(next_ctr)); \
-  } else {                                                                                                    \
-    upsert_rest_kernel<GG, SRC><<<(unsigned)std::max<size_t>(1, (nkeys + 15) / 16), 256, 0, s>>>(a, nullptr, nullptr); \
-  }
-  // The form of the pass (16-byte granules): HF when the last write-back that has ended was mostly plain hits — fewer than a quarter of
-  // the keys its sample looked at were new, evicting or left over — (TFRA_OWN_HF=1: always, 0: never; tuning, tests).  Where it may be
-  // taken: over a SET plan's keys (a victim is checked against the plan), and over ANY keys — a caller's unique keys included: the
-  // reference's Insert op — on a table that never evicts (unbounded: TFRA's default cuckoo flavour), where the only thing a hit's claim
-  // protected it from does not exist.
-  // (A caller's unique keys on a table that DOES evict have no plan to check a victim against.  The form in which every key in need of
-  // a victim goes to the remainder — no eviction inside the pass, so a hit still needs no claim — was measured on the metric's table,
-  // picked below one such key in 64: find + Insert of prepared keys 33.4 -> 29.4 us, but the Insert behind the lookup op 41.5 -> 43.1 us
-  // and the pair alone 16.4 -> 19.1 us.  Not taken; TFRA_OWN_HF=1 still forces it, for the tests.)
-  const char* hf_env = getenv("TFRA_OWN_HF");
-  const bool hf_forced = hf_env && *hf_env && atoi(hf_env) != 0;
-  if ((SRC == SRC_SET || SRC == SRC_DIRECT) && g == 16 && a.tags && (hf_forced || (SRC == SRC_SET && a.own_set.ent) || a.sp.bounded == 0)) {
-    const char* e = hf_env;
-    bool hf = false;
-    if (e && *e) hf = atoi(e) != 0;
-    else if (a.stats_host) {
-      const unsigned nh = reinterpret_cast<const volatile unsigned*>(a.stats_host)[0], lk = reinterpret_cast<const volatile unsigned*>(a.stats_host)[1];
-      hf = lk >= 32 && (size_t)nh * 4 < (size_t)lk;
-    }
-    if (hf) {
-#define TFRA_OWN_HF_LAUNCH(SS, UU) upsert_own_kernel<16, SS, SRC, UU, false, true, true><<<blocks, 256, 0, s>>>(a, ctr, og, progress, progress_val)
-      if (simple) { if (half) TFRA_OWN_HF_LAUNCH(true, 2); else TFRA_OWN_HF_LAUNCH(true, 4); }
-      else { if (half) TFRA_OWN_HF_LAUNCH(false, 2); else TFRA_OWN_HF_LAUNCH(false, 4); }
-#undef TFRA_OWN_HF_LAUNCH
-      upsert_rest_kernel<16, SRC><<<rest_blocks, 256, 0, s>>>(a, &ctr->n_a, reinterpret_cast<unsigned*>(next_ctr));
-      return;
-    }
-  }
-  switch (g) {
-    case 16:
-      if (simple) { if (half) { TFRA_OWN(16, true, 2); } else { TFRA_OWN(16, true, 4); } }
-      else { if (half) { TFRA_OWN(16, false, 2); } else { TFRA_OWN(16, false, 4); } }
-      break;
-    case 8: TFRA_OWN(8, false, 4); break;
-    case 4: TFRA_OWN(4, false, 4); break;
-    case 2: TFRA_OWN(2, false, 4); break;
-    default: TFRA_OWN(1, false, 4); break;
-  }
-#undef TFRA_OWN
-}
-
-// the same pair as the reference's insert_or_accum (own_batch16: ACC) over a caller's unique keys; 16-byte granules only
-static void launch_own_accum(hipStream_t s, bool simple, const OwnArgs& a, size_t nkeys, OwnCtrs* ctr, OwnCtrs* next_ctr, unsigned og,
-                             unsigned rest_blocks) {
-  const bool half = nkeys <= 131072;
-  const unsigned blocks = (unsigned)std::max<size_t>(1, half ? (nkeys + 31) / 32 : (nkeys + 63) / 64);
-#define TFRA_OWN_ACC(SS, UU) upsert_own_kernel<16, SS, SRC_DIRECT, UU, true><<<blocks, 256, 0, s>>>(a, ctr, og, nullptr, 0)
-  if (simple) { if (half) TFRA_OWN_ACC(true, 2); else TFRA_OWN_ACC(true, 4); }
-  else { if (half) TFRA_OWN_ACC(false, 2); else TFRA_OWN_ACC(false, 4); }
-#undef TFRA_OWN_ACC
-  upsert_rest_kernel<16, SRC_DIRECT, true><<<rest_blocks, 256, 0, s>>>(a, &ctr->n_a, reinterpret_cast<unsigned*>(next_ctr));
-}
-
-// Expected left-over keys of an ownership pass over `nkeys` keys: two keys sharing a home bucket, (2 n)^2 / (2 nb).
-static double expect_leftover(double nkeys, double nb) { return 2.0 * nkeys * nkeys / nb; }
-
-static unsigned next_own_gen(Table* t) {
-  if (++t->own_gen == 0) t->own_gen = 1;     // bucket-owner tag of this launch (tags start at 0; a stale equal tag after a wrap only
-  return t->own_gen;                         // sends a key to the remainder pass)
-}
-
-// Host half of an ownership write-back of a plan's keys: everything but the launches (upsert_planned_impl launches the pair
-// upsert_own_kernel + upsert_rest_kernel, the overlapped step puts the pass into its one launch).
-struct OwnLaunch {
-  OwnArgs a;
-  OwnCtrs* ctr; OwnCtrs* next_ctr;
-  unsigned og;            // bucket-owner generation of this launch (0: no owner tags)
-  unsigned key_blocks;    // the plan's keys / 16, as far as the host knows them
-  unsigned rem_blocks;    // grid of the remainder pass
-  bool simple;
-  int g;                  // copy granule
-};
-static int own_prepare(Table* t, const tfra_sparse_plan_t* pl, const void* values, const uint64_t* scores, hipStream_t s,
-                       const unsigned* progress, OwnLaunch* L) {
-  // caller holds t->mu and has called t->enter(s)
-  if (!values) return set_error(TFRA_ERR_INVALID, "upsert_planned: null values");
-  if (t->opts.device != pl->device && t->opts.device >= 0) return set_error(TFRA_ERR_INVALID, "upsert_planned: plan and table live on different devices");
-  if (pl->kind == 1 && !pl->built_counts && t->opts.strategy == TFRA_EVICT_LFU && !scores)
-    return set_error(TFRA_ERR_INVALID, "upsert_planned: this plan was built without occurrence counts (by a step driver of a table whose scores do not read them); an LFU table without caller scores needs them");
-  int rc = t->prepare_insert(pl->n, s);
-  if (rc) return rc;
-  unsigned key_blocks, bin_blocks;
-  plan_grids(pl, &key_blocks, &bin_blocks);
-  if (pl->kind == 1 && progress) {
-    // an assign-only plan does not tell the host how many distinct keys it found; the step driver's batches resemble each
-    // other: the count the last write-back that has started saw, plus a quarter (a batch with more: grid-stride)
-    const unsigned seen = reinterpret_cast<const volatile unsigned*>(progress)[1];
-    if (seen) key_blocks = (unsigned)std::max<size_t>(1, (std::min<size_t>(pl->n, (size_t)seen + seen / 4 + 1024) * 16 + 255) / 256);
-  }
-  uint8_t* bounded_now;
-  rc = t->bounded_flags(1, s, &bounded_now);
-  if (rc) return rc;
-  const ScoreP sp{t->opts.strategy, t->global_epoch, bounded_now ? (t->dense ? 2 : 1) : 0};
-  size_t x = (size_t)t->field_bytes | (size_t)(uintptr_t)values | 16;
-  int g = (int)(x & (~x + 1));
-  if (g > 16) g = 16;
-  ++pl->use_gen;
-  unsigned* tags = t->ensure_own_tags(s);    // nullptr (no owner tags): every key takes the locked protocol
-  L->og = tags ? next_own_gen(t) : 0;
-  const unsigned par = pl->ups_uses[pl->kind == 1 ? 1 : 0]++ & 1u;   // (its own count per buffer: apply_planned uses of the plan do not touch the counters)
-  L->ctr = reinterpret_cast<OwnCtrs*>(pl->d_counts + 12) + par;
-  L->next_ctr = reinterpret_cast<OwnCtrs*>(pl->d_counts + 12) + (par ^ 1u);
-  // Left-over keys of the ownership pass.  Few (a big table): the remainder kernel walks their list with a handful of
-  // blocks.  Many (a small table): full grid.
-  const double nkeys = (double)key_blocks * 16.0;   // unique keys of the plan when its counts have arrived, else the id count
-  L->rem_blocks = expect_leftover(nkeys, (double)t->cur.nb) < 2048.0 ? 32u : key_blocks;
-  L->key_blocks = key_blocks;
-  L->simple = t->opts.aux_fields == 0 && t->opts.strategy == TFRA_EVICT_LRU && !scores;
-  L->g = g;
-  OwnArgs& a = L->a;
-  a = OwnArgs{};
-  a.v = t->view_of(t->cur); a.vals = (const unsigned char*)values; a.scores = (const u64*)scores; a.ks = keys_of(pl); a.keys = nullptr; a.nkeys = 0;
-  a.ai = t->aux; a.sp = sp;
-  a.dflag = pl->dflag; a.tags = tags; a.items = pl->slow_items; a.item_cap = SLOW_CAP;
-  if (pl->kind == 1) {   // a SET plan: its table as something to probe (HF), and where the pass's sample goes
-    const SetTab& tb = pl->set_tab[pl->set_parity];
-    a.own_set = SetProbe{tb.ent, pl->set_m2};
-    a.stats_host = t->own_stats_host;
-  }
-  return TFRA_OK;
-}
-
-static int upsert_planned_impl(tfra_table_t* tp, const tfra_sparse_plan_t* pl, const void* values, const uint64_t* scores,
-                               tfra_stream_t stream, unsigned* progress, unsigned progress_val) {
-  // caller holds t->mu
-  Table* t = reinterpret_cast<Table*>(tp);
-  if (!t || !pl) return set_error(TFRA_ERR_INVALID, "upsert_planned: null argument");
-  hipStream_t s = (hipStream_t)stream;
-  int rc = t->enter(s);
-  if (rc) return rc;
-  if (pl->n == 0) return TFRA_OK;
-  OwnLaunch L;
-  rc = own_prepare(t, pl, values, scores, s, progress, &L);
-  if (rc) return rc;
-  if (pl->kind == 1) launch_own<SRC_SET>(s, L.g, L.simple, L.a, (size_t)L.key_blocks * 16, L.ctr, L.next_ctr, L.og, L.rem_blocks, progress, progress_val);
-  else launch_own<SRC_PLAN>(s, L.g, L.simple, L.a, (size_t)L.key_blocks * 16, L.ctr, L.next_ctr, L.og, L.rem_blocks, progress, progress_val);
-  if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "upsert_planned: launch failed");
-  step_epoch_public(t);
-  return TFRA_OK;
-}
-
-// tfra_table_insert_or_assign with TFRA_FLAG_UNIQUE_KEYS (the reference's Insert op hands HKV unique keys,
-// hkv_hashtable_op_gpu.cu.cc:253-290 -> lookup_table_op_hkv.h:522-537): the same single pass with bucket ownership, fed
-// with the caller's key array — value row i belongs to key i, no plan.  *taken = false: not for this call (no owner tags,
-// or so many keys for the table's size that most of them would collide on a home bucket: a bulk load) — the caller runs
-// the locked two-phase kernels.  Caller holds t->mu and has called prepare_insert.
-namespace tfra {
-int own_upsert_unique(Table* t, hipStream_t s, size_t n, const i64* keys, const void* values, const u64* scores, bool* taken,
-                      const uint8_t* accum_exists, const int64_t* d_n) {
-  // accum_exists != nullptr: insert_or_accum (tfra_table_accum_or_assign with TFRA_FLAG_UNIQUE_KEYS) instead of an assign
-  *taken = false;
-  if (accum_exists && (((size_t)t->field_bytes | (size_t)(uintptr_t)values) & 15)) return TFRA_OK;   // 16-byte granules only
-  if (n == 0 || n > (1u << 24)) return TFRA_OK;
-  const double expect = expect_leftover((double)n, (double)t->cur.nb);
-  if (expect >= 2048.0) return TFRA_OK;   // most keys would collide on a home bucket (a bulk load): the locked kernels
-  // the table's own scratch of this path: 2 counter sets | item list | one flag byte per key
-  const size_t head = 256 + (size_t)SLOW_CAP * sizeof(OwnItem);
-  const size_t need = head + ((n + 255) / 256) * 256;
-  if (t->capture_safe && (t->own_ws_bytes < need || !t->own_tags || t->own_tags_nb != t->cur.nb)) return TFRA_OK;   // no allocation while capturing
-  unsigned* tags = t->ensure_own_tags(s);
-  if (!tags) return TFRA_OK;
-  if (t->own_ws_bytes < need) {
-    if (t->own_ws) { if (hipStreamSynchronize(s) != hipSuccess) return set_error(TFRA_ERR_HIP, "insert: sync"); t->dfree(t->own_ws, s); t->own_ws = nullptr; t->own_ws_bytes = 0; }
-    const size_t want = head + std::max<size_t>(((n + 255) / 256) * 256, (size_t)1 << 18);
-    t->own_ws = t->dalloc(want, s);
-    if (!t->own_ws) { g_last_error.clear(); return TFRA_OK; }   // no scratch: the locked kernels need none
-    if (hipMemsetAsync(t->own_ws, 0, want, s) != hipSuccess) return set_error(TFRA_ERR_HIP, "insert: memset");   // counters and flags start at zero
-    t->own_ws_bytes = want;
-    t->own_ws_uses = 0;
-  }
-  uint8_t* bounded_now;
-  int rc = t->bounded_flags(1, s, &bounded_now);
-  if (rc) return rc;
-  const ScoreP sp{t->opts.strategy, t->global_epoch, bounded_now ? (t->dense ? 2 : 1) : 0};
-  size_t x = (size_t)t->field_bytes | (size_t)(uintptr_t)values | 16;
-  int g = (int)(x & (~x + 1));
-  if (g > 16) g = 16;
-  const unsigned og = next_own_gen(t);
-  const unsigned par = t->own_ws_uses++ & 1u;
-  OwnCtrs* ctr = reinterpret_cast<OwnCtrs*>(t->own_ws) + par;
-  OwnCtrs* next_ctr = reinterpret_cast<OwnCtrs*>(t->own_ws) + (par ^ 1u);
-  const bool simple = t->opts.aux_fields == 0 && t->opts.strategy == TFRA_EVICT_LRU && !scores;
-  OwnArgs a{};
-  a.v = t->view_of(t->cur); a.vals = (const unsigned char*)values; a.scores = scores; a.keys = keys; a.nkeys = (unsigned)n;
-  a.ai = t->aux; a.sp = sp; a.dflag = (uint8_t*)t->own_ws + head; a.tags = tags;
-  a.items = reinterpret_cast<OwnItem*>((unsigned char*)t->own_ws + 256); a.item_cap = SLOW_CAP;
-  a.exists = accum_exists; a.acc_dt = t->opts.value_dtype; a.d_nkeys = (const long long*)d_n;
-  a.stats_host = sp.bounded == 0 ? t->own_stats_host : nullptr;   // (a table that evicts never takes the other form for a caller's keys: nothing to sample for)
-  if (accum_exists) launch_own_accum(s, simple, a, n, ctr, next_ctr, og, 32u);
-  else launch_own<SRC_DIRECT>(s, g, simple, a, n, ctr, next_ctr, og, 32u, nullptr, 0);
-  if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "insert: launch failed");
-  *taken = true;
-  return TFRA_OK;
-}
-}  // namespace tfra
-
-extern "C" int tfra_table_upsert_planned(tfra_table_t* tp, const tfra_sparse_plan_t* pl, const void* values,
-                                         const uint64_t* scores, tfra_stream_t stream) {
-  Table* t = reinterpret_cast<Table*>(tp);
-  if (!t) return set_error(TFRA_ERR_INVALID, "upsert_planned: null table");
-  std::lock_guard<std::mutex> lock(t->mu);
-  return upsert_planned_impl(tp, pl, values, scores, stream, nullptr, 0);
 }
 
 // Introspection for tests and tools: the plan's CSR as flat arrays (copies; synchronises the stream).
@@ -2669,7 +1102,7 @@ extern "C" int tfra_sparse_plan_read(const tfra_sparse_plan_t* pl, uint32_t* cou
 
 // ---------------------------------------------------------------------------------------------
 // One-call forms: the plan is built on the caller's stream into a plan object owned by the table.
-static int own_plan(Table* t, tfra_sparse_plan** out) {
+int tfra::own_plan(Table* t, tfra_sparse_plan** out) {
   if (!t->own_plan) {
     tfra_sparse_plan* pl = nullptr;
     int rc = tfra_sparse_plan_create(t->device, &pl);
@@ -2687,212 +1120,6 @@ void destroy_own_plan(Table* t) {
   if (t->own_plan) { tfra_sparse_plan_destroy(reinterpret_cast<tfra_sparse_plan*>(t->own_plan)); t->own_plan = nullptr; }
 }
 }  // namespace tfra
-
-// tfra_table_apply_sparse for more ids than a plan holds (2^18).  Equal ids must still meet in ONE update, whatever
-// chunk they sit in:
-//   1. per chunk of 2^18 ids: unique + per-key gradient sums (tfra_reduce_by_key) into one concatenated list — a key now
-//      occurs at most once per chunk, so even the hottest id of a Zipf batch is a handful of entries;
-//   2. the list fits a plan: one planned write-back sums a key's entries in chunk order and applies it;
-//      else the list is split by key hash (tfra_partition, mode 2) into parts that fit — a key's entries stay together,
-//      the parts are disjoint key sets — and each part is written back on its own.
-// A slow path (host reads of the counts, scratch allocated per call); results are deterministic, the association of the
-// sums is (within chunk) + (across chunks in order).
-static int apply_sparse_big(Table* t, tfra_table_t* tp, tfra_sparse_plan* pl, const tfra_opt_params* p, size_t n, const int64_t* ids,
-                            const float* grads, const float* param_default_row, tfra_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const int dim = t->opts.dim;
-  if (!t->big_ws) {
-    tfra_workspace_t* w = nullptr;
-    int rc = tfra_workspace_create(t->device, &w);
-    if (rc) return rc;
-    t->big_ws = w;
-  }
-  tfra_workspace_t* ws = reinterpret_cast<tfra_workspace_t*>(t->big_ws);
-  i64 *keys_cat = nullptr, *d_cnt = nullptr, *keys_part = nullptr, *d_counts = nullptr;
-  float *sums_cat = nullptr, *sums_part = nullptr;
-  int* perm = nullptr;
-  auto cleanup = [&](int rc) {
-    (void)hipStreamSynchronize(s);
-    (void)hipFree(keys_cat); (void)hipFree(d_cnt); (void)hipFree(keys_part); (void)hipFree(d_counts); (void)hipFree(sums_cat);
-    (void)hipFree(sums_part); (void)hipFree(perm);
-    return rc;
-  };
-  auto oom = [&]() { return cleanup(set_error(TFRA_ERR_OOM, "apply_sparse: scratch for a batch of more than 2^18 ids")); };
-  if (hipMalloc((void**)&keys_cat, n * sizeof(i64)) != hipSuccess || hipMalloc((void**)&sums_cat, n * (size_t)dim * sizeof(float)) != hipSuccess ||
-      hipMalloc((void**)&d_cnt, sizeof(i64)) != hipSuccess)
-    return oom();
-  size_t T = 0;
-  for (size_t off = 0; off < n; off += MAX_IDS) {
-    const size_t m = std::min<size_t>(MAX_IDS, n - off);
-    int rc = tfra_reduce_by_key(ws, m, ids + off, dim, grads + off * (size_t)dim, (int64_t*)keys_cat + T, sums_cat + T * (size_t)dim,
-                                (int64_t*)d_cnt, stream);
-    if (rc) return cleanup(rc);
-    i64 c = 0;
-    if (hipMemcpyAsync(&c, d_cnt, sizeof(i64), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-      return cleanup(set_error(TFRA_ERR_HIP, "apply_sparse: count read"));
-    if (c < 0) return cleanup(set_error(TFRA_ERR_FULL, "apply_sparse: a de-duplication plan overflowed"));
-    T += (size_t)c;
-  }
-  if (T <= MAX_IDS) {
-    int rc = tfra_sparse_plan_build(pl, T, (const int64_t*)keys_cat, dim, stream);
-    if (!rc) rc = apply_planned_impl(tp, p, pl, sums_cat, param_default_row, stream, nullptr, 0);
-    return cleanup(rc);
-  }
-  if (hipMalloc((void**)&keys_part, T * sizeof(i64)) != hipSuccess || hipMalloc((void**)&perm, T * sizeof(int)) != hipSuccess ||
-      hipMalloc((void**)&sums_part, T * (size_t)dim * sizeof(float)) != hipSuccess)
-    return oom();
-  for (size_t P = (T + (MAX_IDS / 2) - 1) / (MAX_IDS / 2); P <= 2048; P *= 2) {
-    (void)hipFree(d_counts); d_counts = nullptr;
-    if (hipMalloc((void**)&d_counts, P * sizeof(i64)) != hipSuccess) return oom();
-    int rc = tfra_partition(ws, T, nullptr, (const int64_t*)keys_cat, (int)P, 2, (int64_t*)keys_part, perm, (int64_t*)d_counts, stream);
-    if (rc) return cleanup(rc);
-    std::vector<i64> counts(P);
-    if (hipMemcpyAsync(counts.data(), d_counts, P * sizeof(i64), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-      return cleanup(set_error(TFRA_ERR_HIP, "apply_sparse: count read"));
-    bool fits = true;
-    for (i64 c : counts) fits = fits && (size_t)c <= MAX_IDS;
-    if (!fits) continue;   // a part too large (skewed hash): more parts
-    rc = tfra_gather_rows(T, (size_t)dim * sizeof(float), sums_cat, perm, sums_part, stream);
-    if (rc) return cleanup(rc);
-    size_t off = 0;
-    // ONE logical write-back: the epoch / step counters of the EPOCH* strategies advance once, not once per part (the
-    // reference counts one upsert per write-back, lookup_table_op_hkv.h:528-536).  (On a bounded table at max_capacity a
-    // later part may still evict keys an earlier part of the same batch inserted.)
-    t->epoch_hold = true;
-    for (i64 c : counts) {
-      if (c > 0) {
-        rc = tfra_sparse_plan_build(pl, (size_t)c, (const int64_t*)keys_part + off, dim, stream);
-        if (!rc) rc = apply_planned_impl(tp, p, pl, sums_part + off * (size_t)dim, param_default_row, stream, nullptr, 0);
-        if (rc) { t->epoch_hold = false; return cleanup(rc); }
-      }
-      off += (size_t)c;
-    }
-    t->epoch_hold = false;
-    step_epoch_public(t);
-    return cleanup(TFRA_OK);
-  }
-  return cleanup(set_error(TFRA_ERR_UNSUPPORTED, "apply_sparse: could not split the batch into parts of 2^18 ids"));
-}
-
-extern "C" int tfra_table_apply_sparse(tfra_table_t* tp, const tfra_opt_params* p, size_t n, const int64_t* ids,
-                                       const float* grads, const float* param_default_row, tfra_stream_t stream) {
-  Table* t = reinterpret_cast<Table*>(tp);
-  if (!t || !p) return set_error(TFRA_ERR_INVALID, "apply_sparse: null argument");
-  if (n == 0) return TFRA_OK;
-  if (!ids || !grads || !param_default_row) return set_error(TFRA_ERR_INVALID, "apply_sparse: null buffer");
-  if (t->opts.value_dtype != TFRA_F32) return set_error(TFRA_ERR_UNSUPPORTED, "apply_sparse: value_dtype must be float32");
-  const int dim = t->opts.dim;
-  if (dim % 4 != 0 || dim > 64 * MAXCH || (((uintptr_t)grads | (uintptr_t)param_default_row) & 15))
-    return set_error(TFRA_ERR_UNSUPPORTED, "apply_sparse: needs dim % 4 == 0, dim <= 256 and 16-B aligned buffers "
-                                           "(use tfra_unique + tfra_segment_sum + tfra_table_apply_optimizer otherwise)");
-  tfra_sparse_plan* pl;
-  std::lock_guard<std::mutex> lock(t->mu);
-  int rc = t->enter((hipStream_t)stream);   // orders the rebuild of the table's own plan behind its previous use
-  if (rc) return rc;
-  rc = own_plan(t, &pl);
-  if (rc) return rc;
-  if (n > MAX_IDS) return apply_sparse_big(t, tp, pl, p, n, ids, grads, param_default_row, stream);
-  rc = tfra_sparse_plan_build(pl, n, ids, dim, stream);
-  if (rc) return rc;
-  return apply_planned_impl(tp, p, pl, grads, param_default_row, stream, nullptr, 0);
-}
-
-// insert_or_assign of a batch whose keys may repeat, last occurrence wins, dedup on the device
-extern "C" int tfra_table_upsert_sparse(tfra_table_t* tp, size_t n, const int64_t* ids, const void* values,
-                                        const uint64_t* scores, tfra_stream_t stream) {
-  Table* t = reinterpret_cast<Table*>(tp);
-  if (!t) return set_error(TFRA_ERR_INVALID, "upsert_sparse: null table");
-  if (n == 0) return TFRA_OK;
-  if (!ids || !values) return set_error(TFRA_ERR_INVALID, "upsert_sparse: null buffer");
-  tfra_sparse_plan* pl;
-  std::lock_guard<std::mutex> lock(t->mu);
-  int rc = t->enter((hipStream_t)stream);
-  if (rc) return rc;
-  rc = own_plan(t, &pl);
-  if (rc) return rc;
-  // more ids than a plan holds: chunk after chunk on the stream — a later chunk overwrites an earlier one, which is
-  // "the last occurrence wins" across chunks too
-  for (size_t off = 0; off < n; off += MAX_IDS) {
-    const size_t m = std::min<size_t>(MAX_IDS, n - off);
-    pl->skip_counts_once = !(t->opts.strategy == TFRA_EVICT_LFU && !scores);   // what reads a key's occurrence count (own_batch16)
-    rc = tfra_sparse_plan_build(pl, m, ids + off, 0, stream);
-    if (rc) return rc;
-    rc = upsert_planned_impl(tp, pl, (const unsigned char*)values + off * (size_t)t->field_bytes, scores ? scores + off : nullptr, stream,
-                             nullptr, 0);
-    if (rc) return rc;
-  }
-  return TFRA_OK;
-}
-
-// unique + unsorted_segment_sum in one call = the plan + the hot sums + a gather (the reduction half of
-// tfra_table_apply_sparse with the same summation tree, so routing the sums elsewhere — multi-GPU gradient
-// alltoall — and applying them there gives the same bits as applying them here).
-extern "C" int tfra_reduce_by_key(tfra_workspace_t* ws, size_t n, const int64_t* ids, int dim, const float* grads,
-                                  int64_t* keys_out, float* rows_out, int64_t* d_count, tfra_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!ws || !d_count) return set_error(TFRA_ERR_INVALID, "reduce_by_key: null argument");
-  { int cur_ = -1; if (hipGetDevice(&cur_) != hipSuccess || cur_ != ws->device) { if (hipSetDevice(ws->device) != hipSuccess) return set_error(TFRA_ERR_HIP, "reduce_by_key: hipSetDevice"); } }
-  if (n == 0) {
-    if (hipMemsetAsync(d_count, 0, sizeof(int64_t), s) != hipSuccess) return set_error(TFRA_ERR_HIP, "reduce_by_key: memset");
-    return TFRA_OK;
-  }
-  if (!ids || !grads || !keys_out || !rows_out) return set_error(TFRA_ERR_INVALID, "reduce_by_key: null buffer");
-  if (dim <= 0 || dim % 4 != 0 || dim > 64 * MAXCH || (((uintptr_t)grads | (uintptr_t)rows_out) & 15))
-    return set_error(TFRA_ERR_UNSUPPORTED, "reduce_by_key: needs dim % 4 == 0, dim <= 256 and 16-B aligned buffers "
-                                           "(use tfra_unique + tfra_segment_sum otherwise)");
-  if (n > MAX_IDS) return set_error(TFRA_ERR_UNSUPPORTED, "reduce_by_key: at most 2^18 ids per call");
-  if (!ws->plan) {
-    tfra_sparse_plan* np_ = nullptr;
-    int rc = tfra_sparse_plan_create(ws->device, &np_);
-    if (rc) return rc;
-    ws->plan = np_;
-  }
-  tfra_sparse_plan* pl = reinterpret_cast<tfra_sparse_plan*>(ws->plan);
-  int rc = tfra_sparse_plan_build(pl, n, ids, dim, stream);
-  if (rc) return rc;
-  unsigned key_blocks, bin_blocks;
-  plan_grids(pl, &key_blocks, &bin_blocks);
-  const int nch = (dim + 63) / 64;
-  switch (nch) {
-    case 1: hot_sums_kernel<1><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, nullptr, 0); break;
-    case 2: hot_sums_kernel<2><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, nullptr, 0); break;
-    case 3: hot_sums_kernel<3><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, nullptr, 0); break;
-    default: hot_sums_kernel<4><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, nullptr, 0); break;
-  }
-  gather_csr_kernel<<<key_blocks, 256, 0, s>>>(dim, grads, pl->partial, keys_of(pl), (i64*)keys_out, rows_out, (i64*)d_count, nullptr);
-  if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "reduce_by_key: launch failed");
-  return TFRA_OK;
-}
-
-// The per-key gradient sums of a batch whose plan was built ahead (tfra_sparse_plan_build with the table's dim, on any
-// stream): hot sums + gather, the reduction half of tfra_reduce_by_key with the same summation tree, written to
-// rows_out[dest[p]] where p is a position of the key.  dest [n] int32: the caller's map from batch positions to output
-// rows, the same for every position of a key (e.g. position -> owner-major index of the multi-GPU gradient route, which
-// is known from the ids alone).  rows_out must have a row for every value in dest; rows no key maps to are not written.
-extern "C" int tfra_plan_reduce_to(const tfra_sparse_plan_t* pl, const float* grads, const int32_t* dest, float* rows_out,
-                                   tfra_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!pl) return set_error(TFRA_ERR_INVALID, "plan_reduce_to: null plan");
-  if (pl->kind == 1) return set_error(TFRA_ERR_UNSUPPORTED, "plan_reduce_to: needs a plan built with the table's dim");
-  if (pl->n == 0) return TFRA_OK;
-  if (!grads || !dest || !rows_out) return set_error(TFRA_ERR_INVALID, "plan_reduce_to: null buffer");
-  const int dim = pl->dim;
-  if (dim <= 0 || (((uintptr_t)grads | (uintptr_t)rows_out) & 15))
-    return set_error(TFRA_ERR_INVALID, "plan_reduce_to: the plan must have been built with the rows' dim; buffers 16-B aligned");
-  { int cur_ = -1; if (hipGetDevice(&cur_) != hipSuccess || cur_ != pl->device) { if (hipSetDevice(pl->device) != hipSuccess) return set_error(TFRA_ERR_HIP, "plan_reduce_to: hipSetDevice"); } }
-  unsigned key_blocks, bin_blocks;
-  plan_grids(pl, &key_blocks, &bin_blocks);
-  const int nch = (dim + 63) / 64;
-  switch (nch) {
-    case 1: hot_sums_kernel<1><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, nullptr, 0); break;
-    case 2: hot_sums_kernel<2><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, nullptr, 0); break;
-    case 3: hot_sums_kernel<3><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, nullptr, 0); break;
-    default: hot_sums_kernel<4><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, nullptr, 0); break;
-  }
-  gather_csr_kernel<<<key_blocks, 256, 0, s>>>(dim, grads, pl->partial, keys_of(pl), nullptr, rows_out, nullptr, (const int*)dest);
-  if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "plan_reduce_to: launch failed");
-  return TFRA_OK;
-}
 
 // ---------------------------------------------------------------------------------------------
 // Route helpers: the distinct keys of a built plan stand in for tf.unique (PY/shadow_embedding_ops.py:316 does unique,
@@ -2968,96 +1195,6 @@ extern "C" int tfra_plan_positions_to(const tfra_sparse_plan_t* pl, const int32_
 namespace tfra {
 void destroy_workspace_plan(void* plan) { if (plan) tfra_sparse_plan_destroy(reinterpret_cast<tfra_sparse_plan*>(plan)); }
 }  // namespace tfra
-
-// ---------------------------------------------------------------------------------------------
-// One training step driven from C on two streams (no Python between the launches, no graph).
-//   main : lookup(ids_cur) -> write-back of batch cur (hot sums + fused update, or assign)      (plan_cur)
-//   side : build plan_next from ids_next, free-running
-// Cross-queue events cost ~5 us (stream wait) / ~7 us (record) each between two kernels of the main stream,
-// so the two streams are ordered through two host-visible counters in pinned memory instead, and the host
-// only falls back to a sync when a counter lags:
-//   * table progress: written by the first block of the write-back of step s  =>  every earlier step is done.
-//     plan_next's buffers were last read by step plan_next->last_used_step; the build is enqueued once the
-//     progress has passed it (with >= 3 plans in rotation that is always the case unless the host is far
-//     ahead of the GPU, in which case it waits here instead of in a queue);
-//   * plan built: generation + counts written by the build's last kernel.  If they already show plan_cur's
-//     generation the write-back is enqueued without any wait packet and with exact grids; otherwise — the host
-//     got ahead of the side stream — the host waits for the side stream.
-static int step_prefetch_impl(tfra_table_t* tp, const tfra_opt_params* p, tfra_sparse_plan_t* plan_cur,
-                              const int64_t* ids_cur, void* rows_out, const void* find_default, const void* grads_or_values,
-                              const float* param_default_row, const uint64_t* scores, tfra_sparse_plan_t* plan_next,
-                              const int64_t* ids_next, size_t n_next, tfra_stream_t main_stream, tfra_stream_t side_stream) {
-  Table* t = reinterpret_cast<Table*>(tp);
-  if (!t || !plan_cur) return set_error(TFRA_ERR_INVALID, "step_prefetch: null argument");
-  hipStream_t ms = (hipStream_t)main_stream, ss = (hipStream_t)side_stream;
-  if (ms == ss && plan_next) return set_error(TFRA_ERR_INVALID, "step_prefetch: needs two different streams");
-  if (plan_next == plan_cur) return set_error(TFRA_ERR_INVALID, "step_prefetch: plan_next must differ from plan_cur");
-  std::lock_guard<std::mutex> step_lock(t->step_mu);   // one driver call at a time per table
-  int rc = TFRA_OK;
-  if (!t->progress_host) {
-    if (hipHostMalloc((void**)&t->progress_host, 64, hipHostMallocDefault) != hipSuccess) { t->progress_host = nullptr; return set_error(TFRA_ERR_OOM, "step_prefetch: hipHostMalloc"); }
-    t->progress_host[0] = 0; t->progress_host[1] = 0;
-  }
-  const unsigned step = ++t->step_gen;
-  if (plan_next) {
-    if (!plan_next->host_counts) {
-      if (hipHostMalloc((void**)&plan_next->host_counts, 64, hipHostMallocDefault) != hipSuccess) { plan_next->host_counts = nullptr; return set_error(TFRA_ERR_OOM, "step_prefetch: hipHostMalloc"); }
-      for (int i = 0; i < 8; ++i) plan_next->host_counts[i] = 0;
-    }
-    if (plan_next->last_used_step) {  // the write-back that read plan_next's buffers must be over
-      const unsigned need = plan_next->last_used_step + 1;
-      volatile unsigned* prog = t->progress_host;
-      bool ok = false;
-      for (int it = 0; it < 200000 && !ok; ++it) ok = (int)(*prog - need) >= 0;   // ~ a few ms at most
-      if (!ok && hipStreamSynchronize(ms) != hipSuccess) return set_error(TFRA_ERR_HIP, "step_prefetch: sync");
-    }
-  }
-  if (plan_cur->n && rows_out) {
-    rc = tfra_table_find(tp, plan_cur->n, ids_cur, rows_out, nullptr, find_default, 0, main_stream);
-    if (rc) return rc;
-  }
-  if (plan_next) {
-    if (!p) plan_next->skip_counts_once = !(t->opts.strategy == TFRA_EVICT_LFU && !scores);   // (the next step's call passes scores or not like this one)
-    rc = tfra_sparse_plan_build(plan_next, n_next, ids_next, p ? t->opts.dim : 0, side_stream);
-    if (rc) return rc;
-    if (!plan_next->built_ev && hipEventCreateWithFlags(&plan_next->built_ev, hipEventDisableTiming) != hipSuccess) {
-      plan_next->built_ev = nullptr;
-      return set_error(TFRA_ERR_HIP, "step_prefetch: event");
-    }
-    if (hipEventRecord(plan_next->built_ev, ss) != hipSuccess) return set_error(TFRA_ERR_HIP, "step_prefetch: event record");
-    plan_next->ev_recorded = true;   // built on the side stream: the join below applies
-  }
-  if (plan_cur->ev_recorded) {  // built on the side stream by an earlier call
-    // complete = every block of the build has ended and its stores are in memory (the pinned counts alone do not say that)
-    if (hipEventQuery(plan_cur->built_ev) != hipSuccess && hipEventSynchronize(plan_cur->built_ev) != hipSuccess)   // the wait: rare
-      return set_error(TFRA_ERR_HIP, "step_prefetch: join");
-    plan_cur->ev_recorded = false;
-  }
-  plan_cur->last_used_step = step;
-  if (plan_cur->n == 0) return TFRA_OK;   // no kernel publishes this step: a later slot check falls back to a sync
-  std::lock_guard<std::mutex> lock(t->mu);
-  if (p) return apply_planned_impl(tp, p, plan_cur, (const float*)grads_or_values, param_default_row, main_stream, t->progress_host, step);
-  return upsert_planned_impl(tp, plan_cur, grads_or_values, scores, main_stream, t->progress_host, step);
-}
-
-extern "C" int tfra_table_step_prefetch(tfra_table_t* tp, const tfra_opt_params* p, tfra_sparse_plan_t* plan_cur,
-                                        const int64_t* ids_cur, void* rows_out, const void* find_default,
-                                        const float* grads, const float* param_default_row,
-                                        tfra_sparse_plan_t* plan_next, const int64_t* ids_next, size_t n_next,
-                                        tfra_stream_t main_stream, tfra_stream_t side_stream) {
-  if (!p) return set_error(TFRA_ERR_INVALID, "step_prefetch: null optimizer parameters");
-  return step_prefetch_impl(tp, p, plan_cur, ids_cur, rows_out, find_default, grads, param_default_row, nullptr, plan_next, ids_next,
-                            n_next, main_stream, side_stream);
-}
-
-extern "C" int tfra_table_step_prefetch_assign(tfra_table_t* tp, tfra_sparse_plan_t* plan_cur, const int64_t* ids_cur,
-                                               void* rows_out, const void* find_default, const void* values,
-                                               const uint64_t* scores, tfra_sparse_plan_t* plan_next,
-                                               const int64_t* ids_next, size_t n_next, tfra_stream_t main_stream,
-                                               tfra_stream_t side_stream) {
-  return step_prefetch_impl(tp, nullptr, plan_cur, ids_cur, rows_out, find_default, values, nullptr, scores, plan_next, ids_next,
-                            n_next, main_stream, side_stream);
-}
 
 // tf.unique WITHOUT the first-occurrence order (which nothing on the embedding path observes: the distinct ids feed Find / Insert,
 // the inverse index feeds the gather — PY/dynamic_embedding_ops.py:99-117, PY/shadow_embedding_ops.py:316): the SET plan of the
@@ -3147,7 +1284,3 @@ extern "C" int tfra_table_find_unique(tfra_table_t* tp, tfra_workspace_t* ws, si
   if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "find_unique: launch failed");
   return TFRA_OK;
 }
-
-#define TFRA_STEP_HOST_PART
-#include "tfra_step_impl.h"
-#undef TFRA_STEP_HOST_PART

@@ -402,8 +402,7 @@ template <bool SCATTER>
 int move_rows(size_t n, size_t row_bytes, const void* in, const int32_t* idx, void* out, hipStream_t s) {
   if (n == 0) return TFRA_OK;
   if (!in || !idx || !out) return set_error(TFRA_ERR_INVALID, "gather/scatter: null buffer");
-  size_t x = row_bytes | (size_t)(uintptr_t)in | (size_t)(uintptr_t)out | 16;
-  int g = (int)(x & (~x + 1));
+  const int g = granule_of(row_bytes, in, out);
   dim3 grid((unsigned)((n * 16 + 255) / 256)), block(256);
   const unsigned char* i8 = (const unsigned char*)in;
   unsigned char* o8 = (unsigned char*)out;
@@ -415,13 +414,7 @@ int move_rows(size_t n, size_t row_bytes, const void* in, const int32_t* idx, vo
     HIP_TRY(hipGetLastError());
     return TFRA_OK;
   }
-  switch (g) {
-    case 16: move_rows_kernel<16, SCATTER><<<grid, block, 0, s>>>(n, rb, i8, idx, o8); break;
-    case 8: move_rows_kernel<8, SCATTER><<<grid, block, 0, s>>>(n, rb, i8, idx, o8); break;
-    case 4: move_rows_kernel<4, SCATTER><<<grid, block, 0, s>>>(n, rb, i8, idx, o8); break;
-    case 2: move_rows_kernel<2, SCATTER><<<grid, block, 0, s>>>(n, rb, i8, idx, o8); break;
-    default: move_rows_kernel<1, SCATTER><<<grid, block, 0, s>>>(n, rb, i8, idx, o8); break;
-  }
+  with_granule(g, [&](auto G) { move_rows_kernel<G, SCATTER><<<grid, block, 0, s>>>(n, rb, i8, idx, o8); });
   HIP_TRY(hipGetLastError());
   return TFRA_OK;
 }

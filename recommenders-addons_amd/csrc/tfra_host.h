@@ -2,8 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/tfra_mi355x.h"
@@ -105,11 +107,31 @@ struct Table {
 };
 
 void destroy_own_plan(Table* t);   // tfra_csr.hip
-// insert_or_assign of UNIQUE keys as one ownership pass (tfra_csr.hip); *taken = false: not applicable, run the locked kernels
+// insert_or_assign of UNIQUE keys as one ownership pass (tfra_own.hip); *taken = false: not applicable, run the locked kernels
 int own_upsert_unique(Table* t, hipStream_t s, size_t n, const i64* keys, const void* values, const u64* scores, bool* taken,
                       const uint8_t* accum_exists = nullptr, const int64_t* d_n = nullptr);   // accum_exists: insert_or_accum instead of an assign
 void destroy_workspace_plan(void* plan);   // tfra_csr.hip
 void step_epoch_public(Table* t);  // tfra_optim.hip
+
+// Copy granule of rows of `bytes` bytes between two buffers: the largest power of two <= 16 that divides the row size and both
+// addresses (a null pointer divides everything).
+static inline int granule_of(size_t bytes, const void* a, const void* b) {
+  size_t x = bytes | (size_t)(uintptr_t)a | (size_t)(uintptr_t)b | 16;
+  int g = (int)(x & (~x + 1));
+  return g > 16 ? 16 : g;
+}
+// f(std::integral_constant<int, G>{}) for the granule G in {16, 8, 4, 2, 1} that g selects (anything else: 1): one launch ladder
+// for the kernels templated on their granule
+template <class F>
+static inline void with_granule(int g, F&& f) {
+  switch (g) {
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    default: f(std::integral_constant<int, 1>{}); break;
+  }
+}
 
 }  // namespace tfra
 

@@ -1,4 +1,4 @@
-// Block-level building blocks of the duplicate-id reductions (tfra_csr.hip: the CSR write-back plan and its
+// Block-level building blocks of the duplicate-id reductions (tfra_csr.hip: the CSR write-back plan; tfra_apply.hip: its
 // gradient kernels).
 #pragma once
 #include <hip/hip_runtime.h>

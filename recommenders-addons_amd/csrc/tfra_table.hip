@@ -720,12 +720,6 @@ static AuxInit make_aux_init(const tfra_table_opts& o) {
   return ai;
 }
 
-static int granule_of(size_t bytes, const void* a, const void* b) {
-  size_t x = bytes | (size_t)(uintptr_t)a | (size_t)(uintptr_t)b | 16;
-  int g = (int)(x & (~x + 1));
-  return g > 16 ? 16 : g;
-}
-
 namespace tfra {
 
 void* Table::dalloc(size_t bytes, hipStream_t s) {
@@ -1160,16 +1154,12 @@ static int find_impl(Table* t, hipStream_t s, int field, size_t n, const int64_t
   unsigned char* o = (unsigned char*)values;
   const unsigned char* d = (const unsigned char*)defaults;
   const long long* dn = (const long long*)d_n;
-  switch (g) {
-    case 16:
-      if (t->dense) find_kernel<16, U, true, true><<<grid, block, 0, s>>>(v, n, k, o, exists, d, full, fo, dn);
-      else find_kernel<16, U><<<grid, block, 0, s>>>(v, n, k, o, exists, d, full, fo, dn);
-      break;
-    case 8: find_kernel<8, U><<<grid, block, 0, s>>>(v, n, k, o, exists, d, full, fo, dn); break;
-    case 4: find_kernel<4, U><<<grid, block, 0, s>>>(v, n, k, o, exists, d, full, fo, dn); break;
-    case 2: find_kernel<2, U><<<grid, block, 0, s>>>(v, n, k, o, exists, d, full, fo, dn); break;
-    default: find_kernel<1, U><<<grid, block, 0, s>>>(v, n, k, o, exists, d, full, fo, dn); break;
-  }
+  with_granule(g, [&](auto G) {
+    if constexpr (G == 16) {   // a dense table: both home-bucket lines of a key in flight together (PF1)
+      if (t->dense) { find_kernel<16, U, true, true><<<grid, block, 0, s>>>(v, n, k, o, exists, d, full, fo, dn); return; }
+    }
+    find_kernel<G, U><<<grid, block, 0, s>>>(v, n, k, o, exists, d, full, fo, dn);
+  });
   HIP_TRY(hipGetLastError());
   return TFRA_OK;
 }
@@ -1222,22 +1212,10 @@ static int insert_impl(Table* t, hipStream_t s, int field, size_t n, const int64
     }
     TableView v = t->view_of(t->cur);
     const int bd = bounded ? (t->dense ? 2 : 1) : 0;
-    switch (g) {
-      case 16: insert_unique_kernel<16, U><<<grid, block, 0, s>>>(v, n, k, vals, sc, field, t->aux, strat, epoch, bd, deferred); break;
-      case 8: insert_unique_kernel<8, U><<<grid, block, 0, s>>>(v, n, k, vals, sc, field, t->aux, strat, epoch, bd, deferred); break;
-      case 4: insert_unique_kernel<4, U><<<grid, block, 0, s>>>(v, n, k, vals, sc, field, t->aux, strat, epoch, bd, deferred); break;
-      case 2: insert_unique_kernel<2, U><<<grid, block, 0, s>>>(v, n, k, vals, sc, field, t->aux, strat, epoch, bd, deferred); break;
-      default: insert_unique_kernel<1, U><<<grid, block, 0, s>>>(v, n, k, vals, sc, field, t->aux, strat, epoch, bd, deferred); break;
-    }
+    with_granule(g, [&](auto G) { insert_unique_kernel<G, U><<<grid, block, 0, s>>>(v, n, k, vals, sc, field, t->aux, strat, epoch, bd, deferred); });
     if (bounded) {
       dim3 grid2((unsigned)((n * 16 + 255) / 256));
-      switch (g) {
-        case 16: insert_evict_kernel<16><<<grid2, block, 0, s>>>(v, n, k, vals, sc, field, t->aux, strat, epoch, deferred); break;
-        case 8: insert_evict_kernel<8><<<grid2, block, 0, s>>>(v, n, k, vals, sc, field, t->aux, strat, epoch, deferred); break;
-        case 4: insert_evict_kernel<4><<<grid2, block, 0, s>>>(v, n, k, vals, sc, field, t->aux, strat, epoch, deferred); break;
-        case 2: insert_evict_kernel<2><<<grid2, block, 0, s>>>(v, n, k, vals, sc, field, t->aux, strat, epoch, deferred); break;
-        default: insert_evict_kernel<1><<<grid2, block, 0, s>>>(v, n, k, vals, sc, field, t->aux, strat, epoch, deferred); break;
-      }
+      with_granule(g, [&](auto G) { insert_evict_kernel<G><<<grid2, block, 0, s>>>(v, n, k, vals, sc, field, t->aux, strat, epoch, deferred); });
     }
   } else {
     rc = t->ensure_winner(s);
@@ -1249,13 +1227,7 @@ static int insert_impl(Table* t, hipStream_t s, int field, size_t n, const int64
     i64* slot_of = (i64*)t->scratch;
     insert_locate_kernel<U><<<grid, block, 0, s>>>(v, n, k, slot_of, field, t->aux);
     dim3 grid2((unsigned)((n * 16 + 255) / 256));
-    switch (g) {
-      case 16: insert_write_kernel<16><<<grid2, block, 0, s>>>(v, n, vals, sc, slot_of, field, strat, epoch); break;
-      case 8: insert_write_kernel<8><<<grid2, block, 0, s>>>(v, n, vals, sc, slot_of, field, strat, epoch); break;
-      case 4: insert_write_kernel<4><<<grid2, block, 0, s>>>(v, n, vals, sc, slot_of, field, strat, epoch); break;
-      case 2: insert_write_kernel<2><<<grid2, block, 0, s>>>(v, n, vals, sc, slot_of, field, strat, epoch); break;
-      default: insert_write_kernel<1><<<grid2, block, 0, s>>>(v, n, vals, sc, slot_of, field, strat, epoch); break;
-    }
+    with_granule(g, [&](auto G) { insert_write_kernel<G><<<grid2, block, 0, s>>>(v, n, vals, sc, slot_of, field, strat, epoch); });
     rearm_winner_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(v, n, slot_of);
   }
   HIP_TRY(hipGetLastError());
@@ -1271,23 +1243,10 @@ static void launch_accum(int g, dim3 grid, hipStream_t s, TableView v, size_t n,
                          const uint8_t* ex, const u64* sc, unsigned dim, AuxInit ai, int strat, u64 epoch,
                          const u64* sorted_keys, const unsigned* sorted_idx, uint8_t* deferred, int bmode) {
   dim3 block(256);
-  if (sorted_keys) {
-    switch (g) {
-      case 16: accum_segments_kernel<DT, 16><<<grid, block, 0, s>>>(v, n, k, vod, ex, sc, dim, ai, strat, epoch, sorted_keys, sorted_idx); break;
-      case 8: accum_segments_kernel<DT, 8><<<grid, block, 0, s>>>(v, n, k, vod, ex, sc, dim, ai, strat, epoch, sorted_keys, sorted_idx); break;
-      case 4: accum_segments_kernel<DT, 4><<<grid, block, 0, s>>>(v, n, k, vod, ex, sc, dim, ai, strat, epoch, sorted_keys, sorted_idx); break;
-      case 2: accum_segments_kernel<DT, 2><<<grid, block, 0, s>>>(v, n, k, vod, ex, sc, dim, ai, strat, epoch, sorted_keys, sorted_idx); break;
-      default: accum_segments_kernel<DT, 1><<<grid, block, 0, s>>>(v, n, k, vod, ex, sc, dim, ai, strat, epoch, sorted_keys, sorted_idx); break;
-    }
-    return;
-  }
-  switch (g) {
-    case 16: accum_kernel<DT, 16><<<grid, block, 0, s>>>(v, n, k, vod, ex, sc, dim, ai, strat, epoch, deferred, bmode); break;
-    case 8: accum_kernel<DT, 8><<<grid, block, 0, s>>>(v, n, k, vod, ex, sc, dim, ai, strat, epoch, deferred, bmode); break;
-    case 4: accum_kernel<DT, 4><<<grid, block, 0, s>>>(v, n, k, vod, ex, sc, dim, ai, strat, epoch, deferred, bmode); break;
-    case 2: accum_kernel<DT, 2><<<grid, block, 0, s>>>(v, n, k, vod, ex, sc, dim, ai, strat, epoch, deferred, bmode); break;
-    default: accum_kernel<DT, 1><<<grid, block, 0, s>>>(v, n, k, vod, ex, sc, dim, ai, strat, epoch, deferred, bmode); break;
-  }
+  with_granule(g, [&](auto G) {
+    if (sorted_keys) accum_segments_kernel<DT, G><<<grid, block, 0, s>>>(v, n, k, vod, ex, sc, dim, ai, strat, epoch, sorted_keys, sorted_idx);
+    else accum_kernel<DT, G><<<grid, block, 0, s>>>(v, n, k, vod, ex, sc, dim, ai, strat, epoch, deferred, bmode);
+  });
 }
 
 static void launch_accum_dt(int dt, int g, dim3 grid, hipStream_t s, TableView v, size_t n, const i64* k,
@@ -1468,13 +1427,7 @@ int tfra_table_accum_or_assign(tfra_table_t* tp, size_t n, const int64_t* keys, 
       const int strat = t->opts.strategy;
       const u64 epoch = t->global_epoch;
       dim3 block(256);
-      switch (g) {
-        case 16: insert_evict_kernel<16><<<grid, block, 0, s>>>(v, n, k, vals, sc, 0, t->aux, strat, epoch, deferred); break;
-        case 8: insert_evict_kernel<8><<<grid, block, 0, s>>>(v, n, k, vals, sc, 0, t->aux, strat, epoch, deferred); break;
-        case 4: insert_evict_kernel<4><<<grid, block, 0, s>>>(v, n, k, vals, sc, 0, t->aux, strat, epoch, deferred); break;
-        case 2: insert_evict_kernel<2><<<grid, block, 0, s>>>(v, n, k, vals, sc, 0, t->aux, strat, epoch, deferred); break;
-        default: insert_evict_kernel<1><<<grid, block, 0, s>>>(v, n, k, vals, sc, 0, t->aux, strat, epoch, deferred); break;
-      }
+      with_granule(g, [&](auto G) { insert_evict_kernel<G><<<grid, block, 0, s>>>(v, n, k, vals, sc, 0, t->aux, strat, epoch, deferred); });
     }
     HIP_TRY(hipGetLastError());
     return TFRA_OK;
@@ -1603,13 +1556,7 @@ int tfra_table_export_batch(tfra_table_t* tp, size_t n, size_t offset, size_t* d
     dim3 grid((unsigned)((lb - fb + 63) / 64)), block(256);
     u64* c = (u64*)d_counter;
     unsigned char* vo = (unsigned char*)values;
-    switch (g) {
-      case 16: export_kernel<16><<<grid, block, 0, s>>>(v, fb, lb, lo, hi, c, (i64*)keys, vo, (u64*)scores); break;
-      case 8: export_kernel<8><<<grid, block, 0, s>>>(v, fb, lb, lo, hi, c, (i64*)keys, vo, (u64*)scores); break;
-      case 4: export_kernel<4><<<grid, block, 0, s>>>(v, fb, lb, lo, hi, c, (i64*)keys, vo, (u64*)scores); break;
-      case 2: export_kernel<2><<<grid, block, 0, s>>>(v, fb, lb, lo, hi, c, (i64*)keys, vo, (u64*)scores); break;
-      default: export_kernel<1><<<grid, block, 0, s>>>(v, fb, lb, lo, hi, c, (i64*)keys, vo, (u64*)scores); break;
-    }
+    with_granule(g, [&](auto G) { export_kernel<G><<<grid, block, 0, s>>>(v, fb, lb, lo, hi, c, (i64*)keys, vo, (u64*)scores); });
   }
   if (hi > total)
     export_reserved_kernel<<<1, 64, 0, s>>>(v, lo, hi, (u64*)d_counter, (i64*)keys, (unsigned char*)values, (u64*)scores);

@@ -373,7 +373,7 @@ class DynamicEmbeddingOptimizer:
     if (var.shard_num == 1 and not callable(var.initializer) and var.dim % 4 == 0 and var.dim <= 256 and not self.exact_order and
         var.value_dtype == torch.float32):
       # whole backward half in two kernels (tile reduce + bucket apply): no host sync, deterministic.  (More than 2^18
-      # ids: the library reduces chunk by chunk and applies every key once — tfra_csr.hip: apply_sparse_big.)
+      # ids: the library reduces chunk by chunk and applies every key once — tfra_apply.hip: apply_sparse_big.)
       t = var._tables[0]
       t._table.apply_sparse(p, ids, grad, t._default_value.to(torch.float32))
       return

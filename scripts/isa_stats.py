@@ -1,6 +1,6 @@
 """Static instruction mix of the gfx950 kernels of one .hip source (no GPU needed): compiles the device side to
 assembly and counts, per kernel, VALU / SALU / VMEM / LDS / waitcnt / branch instructions and the register use.
-   python scripts/isa_stats.py recommenders-addons_amd/csrc/tfra_csr.hip [name-substring ...]"""
+   python scripts/isa_stats.py recommenders-addons_amd/csrc/tfra_own.hip [name-substring ...]"""
 import collections, os, re, subprocess, sys, tempfile
 
 src = sys.argv[1]

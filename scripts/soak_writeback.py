@@ -1,4 +1,4 @@
-"""Soak run of the write-back as kernels of its own (upsert_own_kernel + upsert_rest_kernel over a SET plan's keys, csrc/tfra_csr.hip) under
+"""Soak run of the write-back as kernels of its own (upsert_own_kernel + upsert_rest_kernel over a SET plan's keys, csrc/tfra_own.hip) under
 its two drivers — the look-ahead driver (PrefetchAssignStep: tfra_table_step_prefetch_assign) and plain calls (find + upsert_sparse) —
 on a bounded LRU table at capacity, with a stream whose character CHANGES every few dozen steps: batches of resident ids only (the pass
 takes the form without claims, picked from the previous write-back's sample), batches that are half never-seen ids (evictions; the form

@@ -8,7 +8,7 @@ controls.  Every key set holds INT32_MIN, INT32_MAX, -1, 0, a dense run of negat
 Each check is against a plain reference: oracle.CpuTable, numpy restatements of the reference's partition and file layout
 (K/cuckoo_hashtable_op.cc:310-391: `<prefix>-keys` = raw K[]), the numpy forward of tests/test_gpu_sparse_train.py, or an
 int64-keyed twin fed the same ids widened — a key's update depends only on its own occurrences (hot_sums_kernel / add_rows in
-tfra_csr.hip sum per key), so the twins must agree bit for bit."""
+tfra_apply.hip sum per key), so the twins must agree bit for bit."""
 import os
 import sys
 
