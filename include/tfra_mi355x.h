@@ -213,9 +213,10 @@ int tfra_table_load_field(tfra_table_t* t, int field, const char* prefix, size_t
  * (PY/dynamic_embedding_optimizer.py:165-204) with one pass over rows laid out [p|slot..].
  * keys [n] UNIQUE (use tfra_segment_sum first), grads [n,dim] fp32.  Missing keys are inserted
  * with p = param_defaults (full [n,dim] or broadcast [dim], like find) and slots = aux_init.
- * Requires aux_fields >= the optimizer's slot count.  value_dtype F32, F16 or BF16 (tfra_table_apply_optimizer; gradients
- * and defaults are float32 in every case: the rule runs in fp32 on the up-cast row and slots and the results are rounded
- * to the storage type once); the planned / sparse forms below: F32.                           */
+ * Requires aux_fields >= the optimizer's slot count.  value_dtype F32, F16 or BF16, here and in the planned / sparse forms
+ * below (gradients and defaults are float32 in every case: the rule runs in fp32 on the up-cast row and slots and the
+ * results are rounded to the storage type once, to nearest even; a new row starts from the float32 default row and
+ * aux_init values, not from their rounded images).                                            */
 typedef enum { TFRA_OPT_SGD = 0, TFRA_OPT_ADAM = 1, TFRA_OPT_ADAGRAD = 2, TFRA_OPT_FTRL = 3 } tfra_opt_kind;
 typedef struct {
   int32_t kind;     /* tfra_opt_kind */
@@ -237,7 +238,8 @@ int tfra_table_apply_optimizer(tfra_table_t* t, const tfra_opt_params* p, size_t
  * ids are summed in a fixed order (deterministic; ids occurring <= 8 times in the batch: strictly in batch order),
  * then one fused update per unique key as above.  = _resource_apply_sparse_duplicate_indices + the write-back
  * sequence (PY/dynamic_embedding_optimizer.py:165-204).  param_default_row: [dim] fp32, used for unseen keys.
- * Requires float32 values, dim % 4 == 0, dim <= 256.  More than 2^18 (262 144) ids per call take a slower path (chunk-wise
+ * Requires float32, float16 or bfloat16 values, dim % 4 == 0, dim <= 256.  On a table that is not evicting, the bytes are those of
+ * tfra_reduce_by_key + tfra_table_apply_optimizer (same summation tree, same rule, one rounding).  More than 2^18 (262 144) ids per call take a slower path (chunk-wise
  * sums, then every key once; host reads of the counts, scratch allocated per call) with the same result up to the
  * association of the sums. */
 int tfra_table_apply_sparse(tfra_table_t* t, const tfra_opt_params* p, size_t n, const int64_t* ids,
@@ -279,7 +281,7 @@ int tfra_table_upsert_planned(tfra_table_t* t, const tfra_sparse_plan_t* plan, c
  * (never written out): g_e = (grad_out[seg[e]] / den) * w_e, den = 1 (sum) | sum of the row's weights (mean) |
  * sqrt(sum of their squares) (sqrtn), 0 when that sum is 0 (see tfra_sparse_segment_combine_backprop).  seg[nnz]
  * ascending, weights[nnz] or NULL (=> 1), combiner 0 sum, 1 mean, 2 sqrtn.  Bit-identical to
- * tfra_table_apply_sparse(ids, tfra_sparse_segment_combine_backprop(grad_out, ...)).  float32 tables, dim % 4 == 0,
+ * tfra_table_apply_sparse(ids, tfra_sparse_segment_combine_backprop(grad_out, ...)).  float32 / float16 / bfloat16 tables, dim % 4 == 0,
  * dim <= 256, grad_out / default row 16-B aligned. */
 int tfra_table_apply_planned_combined(tfra_table_t* t, const tfra_opt_params* p, const tfra_sparse_plan_t* plan,
                                       const float* grad_out, const int64_t* seg, const float* weights, int combiner,
@@ -294,7 +296,8 @@ int tfra_sparse_plan_read(const tfra_sparse_plan_t* plan, uint32_t* counts, int6
 
 /* One whole training step of a single table on two streams, driven from C (what a TF executor does
  * between the ops of one session.run, without the host framework in the loop):
- *   main : rows_out = find(ids_cur) [n = plan_cur's id count; skipped when rows_out is NULL]
+ *   main : rows_out = find(ids_cur) [n = plan_cur's id count; skipped when rows_out is NULL; rows_out and find_default
+ *          have the table's value type, grads and param_default_row are float32]
  *          -> tfra_table_apply_planned(plan_cur, grads)            (tfra_table_step_prefetch)
  *          or tfra_table_upsert_planned(plan_cur, values, scores)  (tfra_table_step_prefetch_assign)
  *   side : tfra_sparse_plan_build(plan_next, ids_next), free-running; plan_next may be NULL (last step).

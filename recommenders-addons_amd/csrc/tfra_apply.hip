@@ -195,7 +195,12 @@ __device__ __forceinline__ float4 sum_rows(const float* __restrict__ grads, cons
 // Round 4: amdgpu_waves_per_eu(5, 5) on that form — 96 registers, 18 spilled for Adam: gradient half 28.7 -> 37.3 us, the step of
 // configs[1] 55.4 -> 62.3 us (A/B on one box, twice).  Five waves need a kernel that NEEDS 96 registers, not one that spills to them.)
 // CS = CombRows: the combined write-back (see hot_sums_kernel).
-template <int KIND, bool PHASE2, class... CS>
+// ST: storage type of the rows (TFRA_F32 / TFRA_F16 / TFRA_BF16).  A half / bfloat16 row is read as ONE 8-byte granule per lane
+// and field (4 stored elements; the group's 16 lanes = one 128-byte line), up-cast, updated in fp32 exactly like a float row,
+// rounded to the storage type once (to_stored) and written back as one 8-byte write-through store per field.  A new row starts
+// from the FLOAT default row and aux_init values, not from their rounded images (as apply_kernel / apply_evict_kernel do).
+// Gradients and partial sums are fp32 for every ST.  The float instantiations compile the code they always did (if constexpr).
+template <int KIND, bool PHASE2, int ST, class... CS>
 __global__ __launch_bounds__(256) void apply_csr_kernel(TableView v, OptP o, int dim, const float* __restrict__ grads,
                                                         const float* __restrict__ partial, CsrKeys ks,
                                                         const float* __restrict__ default_row, float aux0, float aux1,
@@ -266,6 +271,43 @@ __global__ __launch_bounds__(256) void apply_csr_kernel(TableView v, OptP o, int
     float* pr = reinterpret_cast<float*>(row_ptr(v, row));
     // (every lane of the group takes every trip — sum_rows reads the record words of the other lanes; a lane beyond the row
     // works on column 0 and stores nothing)
+    if constexpr (ST != TFRA_F32) {
+      typedef typename Stored<ST>::T V;
+      V* sr = reinterpret_cast<V*>(pr);   // fields of dim * 2 bytes: 8-byte aligned at every c % 4 == 0 (dim % 4 == 0, rows 16-byte aligned)
+      for (int c0 = 0; c0 < dim; c0 += 64) {
+        const bool col = c0 + sub * 4 < dim;
+        const int c = col ? c0 + sub * 4 : 0;
+        // all loads unconditional and issued together (a brand-new row reads its own not yet initialised bytes and discards them)
+        uint2 rp = *reinterpret_cast<const uint2*>(sr + c);
+        uint2 r1 = *reinterpret_cast<const uint2*>(sr + (S >= 1 ? dim : 0) + c);
+        uint2 r2 = *reinterpret_cast<const uint2*>(sr + (S >= 2 ? 2 * dim : 0) + c);
+        const float4 dflt = *reinterpret_cast<const float4*>(default_row + c);
+        float4 gg = sum_rows<COMB>(grads, partial, hot, COMB ? wsrc : w, first, nsrc, wmax, dim, c, gshift, cden, cw);
+        uint2 dummy = rp;
+        keep_live(dummy, rp, r1, r2);
+        float4 p = is_new ? dflt : load_stored4<ST>(rp);
+        float4 s1 = (is_new || S < 1) ? make_float4(aux0, aux0, aux0, aux0) : load_stored4<ST>(r1);
+        float4 s2 = (is_new || S < 2) ? make_float4(aux1, aux1, aux1, aux1) : load_stored4<ST>(r2);
+        apply_one<KIND>(o, gg.x, p.x, s1.x, s2.x);
+        apply_one<KIND>(o, gg.y, p.y, s1.y, s2.y);
+        apply_one<KIND>(o, gg.z, p.z, s1.z, s2.z);
+        apply_one<KIND>(o, gg.w, p.w, s1.w, s2.w);
+        // write-through, one rounding per element (PHASE2: in memory before publish_key)
+        if (col) {
+          store_wt8(sr + c, to_stored4<ST>(p));
+          if (S >= 1) store_wt8(sr + dim + c, to_stored4<ST>(s1));
+          if (S >= 2) store_wt8(sr + 2 * dim + c, to_stored4<ST>(s2));
+        }
+      }
+      // aux fields the optimizer does not own (table created with more slots than it uses)
+      if (is_new && (int)v.n_fields - 1 > S) {
+        for (int f = S + 1; f < (int)v.n_fields; ++f) {
+          const float a = f == 1 ? aux0 : aux1;
+          const u64 a4 = to_stored4<ST>(make_float4(a, a, a, a));
+          for (int c = sub * 4; c < dim; c += 64) store_wt8(sr + f * dim + c, a4);
+        }
+      }
+    } else {
     for (int c0 = 0; c0 < dim; c0 += 64) {
       const bool col = c0 + sub * 4 < dim;
       const int c = col ? c0 + sub * 4 : 0;
@@ -293,6 +335,7 @@ __global__ __launch_bounds__(256) void apply_csr_kernel(TableView v, OptP o, int
       for (int f = S + 1; f < (int)v.n_fields; ++f)
         for (int c = sub; c < dim; c += 16)
           __hip_atomic_store(pr + f * dim + c, (f == 1 ? aux0 : aux1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     }
     if (PHASE2) {
       if (sub == 0) store_wt8(score_word(v, word), 0);  // the slot starts a new life
@@ -354,7 +397,7 @@ __global__ __launch_bounds__(256) void gather_csr_kernel(int dim, const float* _
 
 }  // namespace
 
-template <int KIND, class... CS>
+template <int KIND, int ST, class... CS>
 static void launch_apply_csr(Table* t, hipStream_t s, const tfra_sparse_plan* pl, const OptP& o, const float* grads,
                              const float* default_row, unsigned key_blocks, const ScoreP& sp, const CS&... cs) {
   TableView v = t->view_of(t->cur);
@@ -364,10 +407,10 @@ static void launch_apply_csr(Table* t, hipStream_t s, const tfra_sparse_plan* pl
   // rounds of dispatch plus a third of 27 blocks; 1024 blocks looping twice: configs[1] 55.2 -> 53.7 us per step (A/B on one box, twice)
   static const unsigned grid_cap = [] { const char* e = getenv("TFRA_APPLY_GRID_CAP"); return e ? (unsigned)atoi(e) : 1024u; }();
   if (grid_cap) key_blocks = std::min(key_blocks, grid_cap);
-  apply_csr_kernel<KIND, false><<<key_blocks, 256, 0, s>>>(v, o, pl->dim, grads, pl->partial, keys_of(pl), default_row, a0, a1, sp,
+  apply_csr_kernel<KIND, false, ST><<<key_blocks, 256, 0, s>>>(v, o, pl->dim, grads, pl->partial, keys_of(pl), default_row, a0, a1, sp,
                                                            pl->dflag, pl->any_deferred, gen, cs...);
   if (sp.bounded)
-    apply_csr_kernel<KIND, true><<<key_blocks, 256, 0, s>>>(v, o, pl->dim, grads, pl->partial, keys_of(pl), default_row, a0, a1, sp,
+    apply_csr_kernel<KIND, true, ST><<<key_blocks, 256, 0, s>>>(v, o, pl->dim, grads, pl->partial, keys_of(pl), default_row, a0, a1, sp,
                                                             pl->dflag, pl->any_deferred, gen, cs...);
 }
 
@@ -383,14 +426,25 @@ static void launch_hot_sums(hipStream_t s, const tfra_sparse_plan* pl, const flo
   }
 }
 
+template <int ST, class... CS>
+static void launch_apply_st(Table* t, hipStream_t s, const tfra_sparse_plan* pl, int kind, const OptP& o, const float* grads,
+                            const float* default_row, unsigned key_blocks, const ScoreP& sp, const CS&... cs) {
+  switch (kind) {
+    case TFRA_OPT_SGD: launch_apply_csr<TFRA_OPT_SGD, ST>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
+    case TFRA_OPT_ADAM: launch_apply_csr<TFRA_OPT_ADAM, ST>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
+    case TFRA_OPT_ADAGRAD: launch_apply_csr<TFRA_OPT_ADAGRAD, ST>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
+    default: launch_apply_csr<TFRA_OPT_FTRL, ST>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
+  }
+}
+
+// by the rows' storage type (checked by the caller: F32, F16 or BF16)
 template <class... CS>
 static void launch_apply(Table* t, hipStream_t s, const tfra_sparse_plan* pl, int kind, const OptP& o, const float* grads,
                          const float* default_row, unsigned key_blocks, const ScoreP& sp, const CS&... cs) {
-  switch (kind) {
-    case TFRA_OPT_SGD: launch_apply_csr<TFRA_OPT_SGD>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
-    case TFRA_OPT_ADAM: launch_apply_csr<TFRA_OPT_ADAM>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
-    case TFRA_OPT_ADAGRAD: launch_apply_csr<TFRA_OPT_ADAGRAD>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
-    default: launch_apply_csr<TFRA_OPT_FTRL>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
+  switch (t->opts.value_dtype) {
+    case TFRA_F16: launch_apply_st<TFRA_F16>(t, s, pl, kind, o, grads, default_row, key_blocks, sp, cs...); break;
+    case TFRA_BF16: launch_apply_st<TFRA_BF16>(t, s, pl, kind, o, grads, default_row, key_blocks, sp, cs...); break;
+    default: launch_apply_st<TFRA_F32>(t, s, pl, kind, o, grads, default_row, key_blocks, sp, cs...); break;
   }
 }
 
@@ -406,7 +460,9 @@ int tfra::apply_planned_impl(tfra_table_t* tp, const tfra_opt_params* p, const t
   if (rc) return rc;
   if (pl->n == 0) return TFRA_OK;
   if (!grads || !param_default_row) return set_error(TFRA_ERR_INVALID, "apply_planned: null buffer");
-  if (t->opts.value_dtype != TFRA_F32) return set_error(TFRA_ERR_UNSUPPORTED, "apply_planned: value_dtype must be float32");
+  const int dt = t->opts.value_dtype;
+  if (dt != TFRA_F32 && dt != TFRA_F16 && dt != TFRA_BF16)
+    return set_error(TFRA_ERR_UNSUPPORTED, "apply_planned: value_dtype must be float32, float16 or bfloat16 (gradients and the default row are float32)");
   if (p->kind < 0 || p->kind > TFRA_OPT_FTRL) return set_error(TFRA_ERR_INVALID, "apply_planned: unknown kind");
   int need = p->kind == TFRA_OPT_SGD ? 0 : (p->kind == TFRA_OPT_ADAGRAD ? 1 : 2);
   if (t->opts.aux_fields < need) return set_error(TFRA_ERR_INVALID, "apply_planned: table lacks optimizer slot fields");
@@ -571,7 +627,9 @@ extern "C" int tfra_table_apply_sparse(tfra_table_t* tp, const tfra_opt_params* 
   if (!t || !p) return set_error(TFRA_ERR_INVALID, "apply_sparse: null argument");
   if (n == 0) return TFRA_OK;
   if (!ids || !grads || !param_default_row) return set_error(TFRA_ERR_INVALID, "apply_sparse: null buffer");
-  if (t->opts.value_dtype != TFRA_F32) return set_error(TFRA_ERR_UNSUPPORTED, "apply_sparse: value_dtype must be float32");
+  const int dt = t->opts.value_dtype;
+  if (dt != TFRA_F32 && dt != TFRA_F16 && dt != TFRA_BF16)
+    return set_error(TFRA_ERR_UNSUPPORTED, "apply_sparse: value_dtype must be float32, float16 or bfloat16 (gradients and the default row are float32)");
   const int dim = t->opts.dim;
   if (dim % 4 != 0 || dim > 64 * MAXCH || (((uintptr_t)grads | (uintptr_t)param_default_row) & 15))
     return set_error(TFRA_ERR_UNSUPPORTED, "apply_sparse: needs dim % 4 == 0, dim <= 256 and 16-B aligned buffers "

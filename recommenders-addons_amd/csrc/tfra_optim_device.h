@@ -61,6 +61,24 @@ template <> __device__ __forceinline__ unsigned short to_stored<TFRA_BF16>(float
   return (unsigned short)(u >> 16);
 }
 
+// Four stored elements of a half / bfloat16 row as one 8-byte granule (element c in the low 16 bits): the same conversions as
+// load_stored / to_stored, element by element.
+template <int ST> __device__ __forceinline__ float bits_to_float(unsigned b);
+template <> __device__ __forceinline__ float bits_to_float<TFRA_F16>(unsigned b) { return __half2float(__ushort_as_half((unsigned short)b)); }
+template <> __device__ __forceinline__ float bits_to_float<TFRA_BF16>(unsigned b) { return __uint_as_float(b << 16); }
+template <int ST> __device__ __forceinline__ unsigned float_to_bits(float x);
+template <> __device__ __forceinline__ unsigned float_to_bits<TFRA_F16>(float x) { return __half_as_ushort(to_stored<TFRA_F16>(x)); }
+template <> __device__ __forceinline__ unsigned float_to_bits<TFRA_BF16>(float x) { return to_stored<TFRA_BF16>(x); }
+template <int ST> __device__ __forceinline__ float4 load_stored4(uint2 r) {
+  return make_float4(bits_to_float<ST>(r.x & 0xffffu), bits_to_float<ST>(r.x >> 16), bits_to_float<ST>(r.y & 0xffffu),
+                     bits_to_float<ST>(r.y >> 16));
+}
+template <int ST> __device__ __forceinline__ u64 to_stored4(const float4& x) {
+  const unsigned lo = float_to_bits<ST>(x.x) | (float_to_bits<ST>(x.y) << 16);
+  const unsigned hi = float_to_bits<ST>(x.z) | (float_to_bits<ST>(x.w) << 16);
+  return ((u64)hi << 32) | lo;
+}
+
 // score strategy of the table + its current epoch (update_score)
 struct ScoreP { int strategy; u64 epoch; int bounded; };  // bounded: 0 / 1 / 2 (dense), see locate_or_claim_from
 

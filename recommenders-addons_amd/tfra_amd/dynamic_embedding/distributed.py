@@ -215,7 +215,7 @@ class RoutedPrefetchStep:
   def __init__(self, var, optimizer, group=None, partition_mode=None, force_collectives=False):
     from .optimizer import DynamicEmbeddingOptimizer
     from .table_ops import SparsePlan
-    if var.shard_num != 1 or not DynamicEmbeddingOptimizer.can_plan(var, 1):
+    if var.shard_num != 1 or not DynamicEmbeddingOptimizer.can_plan(var, 1) or var.value_dtype != torch.float32:   # (the route ships fp32 rows)
       raise ValueError("RoutedPrefetchStep needs a single-shard fp32 local Variable with dim % 4 == 0, dim <= 256")
     optimizer._check(var)
     self.var, self.deo = var, optimizer
@@ -466,7 +466,7 @@ class NativeRoutedStep:
     import ctypes
     from .. import _capi
     from .optimizer import DynamicEmbeddingOptimizer
-    if var.shard_num != 1 or not DynamicEmbeddingOptimizer.can_plan(var, 1):
+    if var.shard_num != 1 or not DynamicEmbeddingOptimizer.can_plan(var, 1) or var.value_dtype != torch.float32:   # (the route ships fp32 rows)
       raise ValueError("NativeRoutedStep needs a single-shard fp32 local Variable with dim % 4 == 0, dim <= 256")
     optimizer._check(var)
     self.var, self.deo = var, optimizer

@@ -206,6 +206,9 @@ class SlotView:
         t._table.upsert(kp[i].to(t._device), vp[i].to(t._device), field=self.field)
 
 
+PLANNED_VALUE_DTYPES = (torch.float32, torch.float16, torch.bfloat16)   # row types of tfra_table_apply_planned / _sparse
+
+
 class DynamicEmbeddingOptimizer:
   """`de.DynamicEmbeddingOptimizer(opt)` (PY/dynamic_embedding_optimizer.py:807-867)."""
 
@@ -263,7 +266,7 @@ class DynamicEmbeddingOptimizer:
   def apply_combined_gradients(self, grads_and_vars, name=None):
     """grads_and_vars: iterable of (grad_out, SparseTrainableWrapper) — grad_out is the gradient of the RESULT of
     embedding_lookup_sparse / safe_embedding_lookup_sparse (its shape, leading dims included); one global step for all
-    pairs.  One shard, float32 rows, a fused rule and a plannable batch: the write-back forms every entry's gradient from
+    pairs.  One shard, float32 / float16 / bfloat16 rows, a fused rule and a plannable batch: the write-back forms every entry's gradient from
     grad_out inside its kernels (tfra_table_apply_planned_combined, with the plan built at lookup time when there is one);
     otherwise the entry gradients are written out (device_ops.sparse_segment_combine_backprop) and go through apply_sparse."""
     pairs = []
@@ -333,9 +336,10 @@ class DynamicEmbeddingOptimizer:
 
   @staticmethod
   def can_plan(var, n):
-    """The planned / two-kernel write-back covers one shard, fp32 rows with dim % 4 == 0, dim <= 256."""
+    """The planned / two-kernel write-back covers one shard, float32 / float16 / bfloat16 rows with dim % 4 == 0, dim <= 256
+    (gradients and the default row are float32 in every case; a half row is up-cast, updated in float32 and rounded once)."""
     return (var.shard_num == 1 and not callable(var.initializer) and var.dim % 4 == 0 and var.dim <= 256 and
-            n <= (1 << 18) and var.value_dtype == torch.float32)
+            n <= (1 << 18) and var.value_dtype in PLANNED_VALUE_DTYPES)
 
   def plan(self, var, ids, plan=None):
     """Build (or rebuild) the id-only half of `apply_sparse(var, ids, ...)` on the current stream; pass the
@@ -371,14 +375,14 @@ class DynamicEmbeddingOptimizer:
     if getattr(var, "restrict_policy", None) is not None:  # PY/embedding_weights.py:441-442
       var.restrict_policy.apply_update(ids)
     if (var.shard_num == 1 and not callable(var.initializer) and var.dim % 4 == 0 and var.dim <= 256 and not self.exact_order and
-        var.value_dtype == torch.float32):
+        var.value_dtype in PLANNED_VALUE_DTYPES):
       # whole backward half in two kernels (tile reduce + bucket apply): no host sync, deterministic.  (More than 2^18
       # ids: the library reduces chunk by chunk and applies every key once — tfra_apply.hip: apply_sparse_big.)
       t = var._tables[0]
       t._table.apply_sparse(p, ids, grad, t._default_value.to(torch.float32))
       return
     if var.dim % 4 == 0 and var.dim <= 256 and n <= (1 << 18) and not self.exact_order:
-      # sharded variables / callable initializers / half and bfloat16 rows: the same parallel, order-fixed duplicate reduction
+      # sharded variables / callable initializers: the same parallel, order-fixed duplicate reduction
       # (tile reduce + bucket merge, float32 sums), then one fused update per unique key and shard — on a half / bfloat16
       # table the rule runs in float32 on the up-cast row and slots and the results are rounded to the storage type once.  (unique +
       # segment_sum walks a segment sequentially: 9 ms for a Zipf batch whose hottest id repeats 24 000 times.)
@@ -486,7 +490,7 @@ class PrefetchStep:
   def __init__(self, var, optimizer):
     from .table_ops import SparsePlan
     if var.shard_num != 1 or not DynamicEmbeddingOptimizer.can_plan(var, 1):
-      raise ValueError("PrefetchStep needs a single-shard fp32 Variable with dim % 4 == 0, dim <= 256")
+      raise ValueError("PrefetchStep needs a single-shard float32 / float16 / bfloat16 Variable with dim % 4 == 0, dim <= 256")
     optimizer._check(var)
     self.var, self.deo = var, optimizer
     self.t = var.tables[0]
@@ -495,6 +499,8 @@ class PrefetchStep:
     self.plans = [SparsePlan(self.dev, var.dim) for _ in range(self.NPLANS)]
     self.ids = [None] * self.NPLANS
     self.default = self.t._default_value.to(device=self.dev, dtype=torch.float32).contiguous()
+    # the lookup half writes rows of the table's type and takes its default row in that type; the write-back's is float32
+    self.find_default = self.t._default_value.to(device=self.dev, dtype=var.value_dtype).contiguous()
     self.side = torch.cuda.Stream(device=self.dev)
     self.cur = 0
 
@@ -523,7 +529,7 @@ class PrefetchStep:
       grads = grads.to(torch.float32).contiguous()
     if getattr(self.var, "restrict_policy", None) is not None and n:   # PY/embedding_weights.py:441-442
       self.var.restrict_policy.apply_update(_narrow_keys(ids, self.table.key_dtype))
-    out = torch.empty((n, self.var.dim), dtype=torch.float32, device=self.dev)
+    out = torch.empty((n, self.var.dim), dtype=self.var.value_dtype, device=self.dev)
     if nxt is not None:
       nxt.record_stream(self.side)
       self.ids[nxt_slot] = nxt                      # kept alive until its step has run
@@ -532,7 +538,7 @@ class PrefetchStep:
     if nxt is not None and (not next_ids_ready or self.table.key_dtype == torch.int32):
       self.side.wait_stream(main)
     _capi.call("tfra_table_step_prefetch", self.table._h, ctypes.byref(p), self.plans[cur]._h, _ptr(ids), _ptr(out),
-               _ptr(self.default), _ptr(grads), _ptr(self.default), self.plans[nxt_slot]._h if nxt is not None else None,
+               _ptr(self.find_default), _ptr(grads), _ptr(self.default), self.plans[nxt_slot]._h if nxt is not None else None,
                _ptr(nxt), 0 if nxt is None else nxt.numel(), ctypes.c_void_p(main.cuda_stream),
                ctypes.c_void_p(self.side.cuda_stream))
     self.cur = nxt_slot
@@ -558,7 +564,7 @@ class MultiTablePrefetchStep:
     self.vars, self.deo, self.workers = list(variables), optimizer, int(workers)
     for v in self.vars:
       if v.shard_num != 1 or not DynamicEmbeddingOptimizer.can_plan(v, 1):
-        raise ValueError("MultiTablePrefetchStep needs single-shard fp32 Variables with dim % 4 == 0, dim <= 256")
+        raise ValueError("MultiTablePrefetchStep needs single-shard float32 / float16 / bfloat16 Variables with dim % 4 == 0, dim <= 256")
       optimizer._check(v)
     self.tables = [v.tables[0]._table for v in self.vars]
     self.dev = self.tables[0].device
@@ -566,6 +572,7 @@ class MultiTablePrefetchStep:
     self.plans = [[SparsePlan(self.dev, v.dim) for _ in range(self.NPLANS)] for v in self.vars]
     self.ids = [[None] * self.NPLANS for _ in range(nt)]
     self.defaults = [v.tables[0]._default_value.to(device=self.dev, dtype=torch.float32).contiguous() for v in self.vars]
+    self.find_defaults = [v.tables[0]._default_value.to(device=self.dev, dtype=v.value_dtype).contiguous() for v in self.vars]
     ns = max(1, min(int(streams), nt))
     self.main = [torch.cuda.Stream(device=self.dev) for _ in range(ns)]
     self.side = [torch.cuda.Stream(device=self.dev) for _ in range(ns)]
@@ -573,7 +580,7 @@ class MultiTablePrefetchStep:
     for i, d in enumerate(self.descs):
       d.struct_size = ctypes.sizeof(_capi.StepDesc)
       d.table = self.tables[i]._h
-      d.find_default = self.defaults[i].data_ptr()
+      d.find_default = self.find_defaults[i].data_ptr()
       d.param_default_row = self.defaults[i].data_ptr()
       d.scores = None
       d.main_stream = self.main[i % ns].cuda_stream
@@ -590,7 +597,7 @@ class MultiTablePrefetchStep:
     return self
 
   def step(self, grads_list, next_ids_list=None):
-    """grads_list[i]: [n_i, dim_i] float32 gradients of table i's staged batch; next_ids_list[i]: its next batch or None at the
+    """grads_list[i]: [n_i, dim_i] float32 gradients of table i's staged batch (rows come back in the table's type); next_ids_list[i]: its next batch or None at the
     end.  Ordered against the caller's current stream both ways (inputs produced there are waited for, the returned rows are
     safe to consume there)."""
     cur, nxt_slot = self.cur, (self.cur + 1) % self.NPLANS
@@ -602,7 +609,7 @@ class MultiTablePrefetchStep:
       g = grads_list[i].reshape(n, v.dim)
       if g.dtype != torch.float32 or not g.is_contiguous():
         g = g.to(torch.float32).contiguous()
-      out = torch.empty((n, v.dim), dtype=torch.float32, device=self.dev)
+      out = torch.empty((n, v.dim), dtype=v.value_dtype, device=self.dev)
       nxt = None if next_ids_list is None else next_ids_list[i]
       if nxt is not None:
         nxt = _driver_ids(self.tables[i], nxt, self.dev)
