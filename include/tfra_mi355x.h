@@ -508,6 +508,20 @@ int tfra_sparse_segment_combine_backprop(tfra_workspace_t* ws, size_t nnz, int d
                                          const int64_t* seg, const float* weights, int combiner, size_t n_rows,
                                          float* entry_grads_out, tfra_stream_t stream);
 
+/* pooled lookup = embedding_lookup_sparse's forward (PY/dynamic_embedding_ops.py:120-293) without its intermediates:
+ * out[r,:] = combine over {p : seg[p] == r}, in input order, of w_p * (hit(ids[p]) ? row(ids[p]) : default_row), float32.
+ * seg ascending.  Entries with seg outside [0, n_rows) are ignored.  A row without entries gives zeros.
+ * mean / sqrtn: a row whose weight sum is 0 gives zeros.  weights NULL = all 1.  combiner 0 sum | 1 mean | 2 sqrtn.
+ * default_row: one row in the table's value dtype.  Never inserts.  Duplicate and reserved ids are as in tfra_table_find.
+ * Two launches (the rows' bounds, then one probe + row read per entry accumulated in registers); no unique pass, no [nnz, dim]
+ * or [U, dim] tensor, nothing read on the host.  Bit-identical to tfra_table_find(ids -> rows, default_is_full = 0) followed by
+ * tfra_sparse_segment_combine(float32(rows), idx = 0..nnz-1, seg, weights, combiner).
+ * float32 / float16 / bfloat16 tables (half rows are up-cast exactly), dim % 4 == 0, dim <= 256, out and default_row 16-byte
+ * aligned, nnz < 2^31, n_rows < 2^30: anything else returns TFRA_ERR_UNSUPPORTED and writes nothing.  nnz == 0 zero-fills out. */
+int tfra_table_find_combine(tfra_table_t* t, tfra_workspace_t* ws, size_t nnz, const int64_t* ids, const int64_t* seg,
+                            const float* weights, int combiner, size_t n_rows, const void* default_row, float* out,
+                            tfra_stream_t stream);
+
 /* default_partition_fn (PY/dynamic_embedding_variable.py:165-197) + dynamic_partition in one
  * pass: owner[i] = mode 0: (key & 0x7fffffff) % num_shards (CUDA-build branch)
  *                  mode 1: floor_mod(key, num_shards)       (CPU-build branch)

@@ -28,12 +28,37 @@ struct CombRows {
   const CombEnt* ent;
 };
 
-// den_r over the row's members [b, e) in input order (the same adds as seg_combine_kernel's weight sum)
-__device__ __forceinline__ float comb_den(const float* __restrict__ w, int b, int e, int combiner) {
-  if (combiner == 0) return 1.f;
+// the weight sum of a row's members [b, e) in input order: sum w (sum, mean) | sum w^2 (sqrtn).  ONE loop for the forward
+// (seg_combine_kernel, find_combine_kernel) and the backward (comb_den)
+__device__ __forceinline__ float comb_wsum(const float* __restrict__ w, int b, int e, int combiner) {
   float s = 0.f;
   for (int p = b; p < e; ++p) { const float x = w ? w[p] : 1.f; s += combiner == 2 ? x * x : x; }
+  return s;
+}
+
+// den_r over the row's members [b, e)
+__device__ __forceinline__ float comb_den(const float* __restrict__ w, int b, int e, int combiner) {
+  if (combiner == 0) return 1.f;
+  const float s = comb_wsum(w, b, e, combiner);
   return combiner == 2 ? sqrtf(s) : s;
+}
+
+// ---- the forward's two steps, shared by seg_combine_kernel (tfra_frontend.hip: rows from a [U, dim] tensor) and find_combine_kernel
+// (tfra_pool.hip: rows straight from the table), so that both compile the same expressions and agree bit for bit ------------------
+// one member: acc += v * x
+__device__ __forceinline__ void comb_acc(float& acc, float v, float x) { acc += v * x; }
+__device__ __forceinline__ void comb_acc4(float4& acc, float4 v, float x) {
+  comb_acc(acc.x, v.x, x); comb_acc(acc.y, v.y, x); comb_acc(acc.z, v.z, x); comb_acc(acc.w, v.w, x);
+}
+// the row's end: wsum = comb_wsum of the row; sum: acc as it is | mean: acc / wsum | sqrtn: acc / sqrt(wsum); 0 when wsum == 0
+__device__ __forceinline__ float comb_scale_of(float wsum, int combiner) { return combiner == 2 ? sqrtf(wsum) : (combiner == 1 ? wsum : 1.f); }
+__device__ __forceinline__ float comb_finish(float acc, float wsum, float scale, int combiner) {
+  if (combiner == 0) return acc;
+  return wsum != 0.f ? acc / scale : 0.f;
+}
+__device__ __forceinline__ float4 comb_finish4(float4 acc, float wsum, float scale, int combiner) {
+  return make_float4(comb_finish(acc.x, wsum, scale, combiner), comb_finish(acc.y, wsum, scale, combiner),
+                     comb_finish(acc.z, wsum, scale, combiner), comb_finish(acc.w, wsum, scale, combiner));
 }
 
 __device__ __forceinline__ float comb_grad(float g, float den, float w) { return den != 0.f ? (g / den) * w : 0.f; }
@@ -47,5 +72,9 @@ __device__ __forceinline__ float4 comb_grad4(float4 g, float den, float w) {
 // n_rows floats.  n_rows >= 1.
 int comb_entries(hipStream_t s, size_t nnz, const int64_t* seg, const float* weights, int combiner, size_t n_rows, int* se,
                  float* den, CombEnt* ent);
+
+// se[r] / se[n_rows + r] = first / one-past-last entry of row r (seg ascending; entries outside [0, n_rows) are in no row; a row
+// without entries: 0, 0).  se: 2 n_rows ints.  A memset and one launch (tfra_frontend.hip).
+int comb_bounds(hipStream_t s, size_t nnz, const int64_t* seg, size_t n_rows, int* se);
 
 }  // namespace tfra

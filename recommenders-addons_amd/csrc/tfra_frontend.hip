@@ -493,32 +493,24 @@ __global__ __launch_bounds__(256) void seg_combine_kernel(size_t n_rows, int dim
   const size_t r = (((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4);
   if (r >= n_rows) return;
   const int b = start_end[r], e = start_end[n_rows + r];
-  float wsum = 0.f;
-  for (int p = b; p < e; ++p) { float x = w ? w[p] : 1.f; wsum += combiner == 2 ? x * x : x; }
-  float scale = 1.f;
-  if (combiner == 1) scale = wsum;
-  if (combiner == 2) scale = sqrtf(wsum);
+  const float wsum = comb_wsum(w, b, e, combiner);
+  const float scale = comb_scale_of(wsum, combiner);
   float* o = out + r * (size_t)dim;
   if (VEC4) {
     for (int c = sub * 4; c < dim; c += 64) {
       float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
       for (int p = b; p < e; ++p) {
-        float x = w ? w[p] : 1.f;
-        float4 v = *reinterpret_cast<const float4*>(rows + (size_t)idx[p] * dim + c);
-        acc.x += v.x * x; acc.y += v.y * x; acc.z += v.z * x; acc.w += v.w * x;
+        const float x = w ? w[p] : 1.f;
+        const float4 v = *reinterpret_cast<const float4*>(rows + (size_t)idx[p] * dim + c);
+        comb_acc4(acc, v, x);
       }
-      if (combiner != 0) {
-        if (wsum != 0.f) { acc.x /= scale; acc.y /= scale; acc.z /= scale; acc.w /= scale; }
-        else acc = make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-      *reinterpret_cast<float4*>(o + c) = acc;
+      *reinterpret_cast<float4*>(o + c) = comb_finish4(acc, wsum, scale, combiner);
     }
   } else {
     for (int c = sub; c < dim; c += 16) {
       float acc = 0.f;
-      for (int p = b; p < e; ++p) acc += rows[(size_t)idx[p] * dim + c] * (w ? w[p] : 1.f);
-      if (combiner != 0) acc = (wsum != 0.f) ? acc / scale : 0.f;
-      o[c] = acc;
+      for (int p = b; p < e; ++p) comb_acc(acc, rows[(size_t)idx[p] * dim + c], w ? w[p] : 1.f);
+      o[c] = comb_finish(acc, wsum, scale, combiner);
     }
   }
 }
@@ -835,8 +827,8 @@ int tfra_sparse_segment_combine(tfra_workspace_t* ws, size_t nnz, int dim, const
   int rc = ws->ensure(align_up(2 * n_rows * sizeof(int)), s);
   if (rc) return rc;
   int* se = (int*)ws->buf;
-  HIP_TRY(hipMemsetAsync(se, 0, 2 * n_rows * sizeof(int), s));  // empty rows: start = end = 0
-  if (nnz) seg64_bounds_kernel<<<(unsigned)((nnz + 255) / 256), 256, 0, s>>>(nnz, (const i64*)seg, se, n_rows);
+  rc = comb_bounds(s, nnz, seg, n_rows, se);
+  if (rc) return rc;
   dim3 grid((unsigned)((n_rows * 16 + 255) / 256));
   bool vec4 = dim % 4 == 0 && (((uintptr_t)rows | (uintptr_t)out) % 16 == 0);
   if (vec4) seg_combine_kernel<true><<<grid, 256, 0, s>>>(n_rows, dim, rows, idx, weights, se, combiner, out);
@@ -950,6 +942,13 @@ int tfra_select_lowest(tfra_workspace_t* ws, size_t n, const int64_t* keys, cons
 }  // extern "C"
 
 namespace tfra {
+int comb_bounds(hipStream_t s, size_t nnz, const int64_t* seg, size_t n_rows, int* se) {
+  HIP_TRY(hipMemsetAsync(se, 0, 2 * n_rows * sizeof(int), s));  // empty rows: start = end = 0
+  if (nnz) seg64_bounds_kernel<<<(unsigned)((nnz + 255) / 256), 256, 0, s>>>(nnz, (const i64*)seg, se, n_rows);
+  HIP_TRY(hipGetLastError());
+  return TFRA_OK;
+}
+
 int comb_entries(hipStream_t s, size_t nnz, const int64_t* seg, const float* weights, int combiner, size_t n_rows, int* se,
                  float* den, CombEnt* ent) {
   HIP_TRY(hipMemsetAsync(se, 0, 2 * n_rows * sizeof(int), s));  // empty rows: start = end = 0

@@ -149,6 +149,7 @@ _SIGS = {
     "tfra_unique": [_P, _SZ, _P, _P, _P, _P, _P],
     "tfra_unique_unordered": [_P, _SZ, _P, _P, _P, _P, _P],
     "tfra_table_find_unique": [_P, _P, _SZ, _P, _P, _P, _P, _I, _P, _P, _P, _P],
+    "tfra_table_find_combine": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, _P, _P],
     "tfra_segment_sum": [_P, _SZ, _I, _P, _P, _P, _SZ, _P, _P],
     "tfra_gather_rows": [_SZ, _SZ, _P, _P, _P, _P],
     "tfra_keys_widen_i32": [_SZ, _P, _P, _P],

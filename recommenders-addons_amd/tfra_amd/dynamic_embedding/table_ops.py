@@ -263,6 +263,34 @@ class _DeviceTable:
     uniq = _narrow_keys(uniq, self._key_dtype)   # the table's key dtype, so that `unique` goes back into upsert / erase
     return (out, uniq, idx, cnt, exists) if return_exists else (out, uniq, idx, cnt)
 
+  def find_combine(self, ids, seg, weights, combiner, n_rows, default_row=None):
+    """The pooled lookup (tfra_table_find_combine): out[r] = combine over {p: seg[p] == r}, in input order, of weights[p] * (the row
+    of ids[p], or `default_row` — one row of the value dtype, the table's default when None — on a miss), float32 [n_rows, dim].
+    seg ascending int64, weights float32 or None (all 1), combiner 0 sum / 1 mean / 2 sqrtn.  float32 / float16 / bfloat16 rows,
+    dim % 4 == 0, dim <= 256 (TfraError UNSUPPORTED otherwise).  Bit-identical to find + device_ops.sparse_segment_combine over
+    idx = arange(nnz); no unique pass, nothing read on the host."""
+    from .device_ops import _workspace
+    ids = self._keys(ids).reshape(-1)
+    nnz = ids.numel()
+    seg = torch.as_tensor(seg, device=self._device).reshape(-1).to(torch.int64).contiguous()
+    if seg.numel() != nnz:
+      raise ValueError("ids and segment_ids must have the same number of elements: %d vs %d" % (nnz, seg.numel()))
+    w = None
+    if weights is not None:
+      w = torch.as_tensor(weights, device=self._device).reshape(-1).to(torch.float32).contiguous()
+      if w.numel() != nnz:
+        raise ValueError("weights must have one element per id")
+    d = self._default_value if default_row is None else torch.as_tensor(default_row, device=self._device)
+    if d.dtype != self._value_dtype:
+      raise TypeError("default values must be dtype %s, got %s" % (self._value_dtype, d.dtype))
+    if d.numel() != self._dim:
+      raise ValueError("default_row must be one row of dim=%d elements, got %d" % (self._dim, d.numel()))
+    d = d.contiguous()
+    out = torch.empty((int(n_rows), self._dim), dtype=torch.float32, device=self._device)
+    _capi.call("tfra_table_find_combine", self._h, _workspace(self._device), nnz, _ptr(ids), _ptr(seg), _ptr(w), int(combiner),
+               int(n_rows), _ptr(d), _ptr(out), _stream(self._device))
+    return out
+
   def upsert(self, keys, values, scores=None, unique_keys=False, field=0):
     keys = self._keys(keys)
     values = self._values_for(keys, values)

@@ -239,6 +239,25 @@ class Variable:
       return v, e.reshape(keys.shape)
     return v
 
+  def can_lookup_combined(self):
+    """Whether `lookup_combined` serves this variable: one shard, a static default row (no callable initializer), float32 /
+    float16 / bfloat16 rows with dim % 4 == 0 and dim <= 256 — the conditions of the planned write-back (`can_plan`)."""
+    from .optimizer import PLANNED_VALUE_DTYPES
+    return (self.shard_num == 1 and not callable(self.initializer) and self.value_dtype in PLANNED_VALUE_DTYPES and
+            self.dim % 4 == 0 and self.dim <= 256)
+
+  def lookup_combined(self, ids, seg, weights, combiner, n_rows, name=None):
+    """The forward of embedding_lookup_sparse as one pooled read (tfra_table_find_combine): [n_rows, dim] float32,
+    out[r] = combiner over the entries p with seg[p] == r, in input order, of weights[p] * (row of ids[p], the default row on a
+    miss).  seg ascending; weights None = all 1; combiner "sum" / "mean" / "sqrtn".  Bit-identical to
+    unique -> lookup -> device_ops.sparse_segment_combine, without the unique pass and its host read.  Never inserts."""
+    if not self.can_lookup_combined():
+      raise ValueError("lookup_combined needs one shard, a static default row, float32 / float16 / bfloat16 rows, dim % 4 == 0 "
+                       "and dim <= 256; use embedding_lookup_sparse")
+    t = self._tables[0]
+    ids = torch.as_tensor(ids, device=self._primary)
+    return t._table.find_combine(ids.reshape(-1), seg, weights, device_ops.COMBINERS[combiner], n_rows, t._default_value)
+
   def export(self, name=None):
     """PY/dynamic_embedding_variable.py:988-1007"""
     ks, vs = [], []
@@ -495,17 +514,37 @@ class SparseTrainableWrapper(TrainableWrapper):
 
   The entry list follows the reference's safe_embedding_lookup_sparse (PY/dynamic_embedding_ops.py:374-408): entries pruned
   for their weight are not in it, and every row left empty adds one entry (row, default_id or 0, weight 1) — with
-  default_id=None that entry's gradient is zero (the reference's `where`), but its key still reaches the write-back."""
+  default_id=None that entry's gradient is zero (the reference's `where`), but its key still reaches the write-back.
+
+  A wrapper made behind the pooled forward (`lookup_ids`: the lookup's ids as given, instead of `ids` / `idx` / `n_unique`) has
+  not de-duplicated anything yet: `ids`, `_idx`, `_n_unique`, `exists` and the rows behind `read_value()` are resolved on their
+  first access — tf.unique of the lookup's ids and a lookup of the unique ids, as the eager wrapper does at construction (the
+  rows are then those the table holds at that moment).  `apply_combined_gradients` needs none of them."""
+
+  _LAZY = ("ids", "_idx", "_n_unique", "exists", "_values")
 
   def __init__(self, params, ids, idx, n_unique, seg, weights, combiner, n_rows, out_shape, entry_ids, entry_seg,
-               entry_weights, max_norm=None, plan_writeback=False):
-    super().__init__(params, ids, max_norm=max_norm)
+               entry_weights, max_norm=None, plan_writeback=False, lookup_ids=None):
+    if lookup_ids is None:
+      super().__init__(params, ids, max_norm=max_norm)
+      self._idx, self._n_unique = idx, n_unique
+    else:
+      self.params, self.max_norm, self.plan = params, max_norm, None
+    self._lookup_ids = lookup_ids
     self.combiner = combiner
     self.n_rows = int(n_rows)
     self.out_shape = tuple(out_shape)
-    self._idx, self._n_unique, self._seg, self._weights = idx, n_unique, seg, weights   # the lookup's own entries (grad_of)
+    self._seg, self._weights = seg, weights   # the lookup's own entries (grad_of)
     self.entry_ids, self.seg, self.weights = entry_ids, entry_seg, entry_weights
     self.entry_plan = _plan_at_lookup(params, entry_ids) if plan_writeback else None
+
+  def __getattr__(self, name):   # only reached for attributes not set yet
+    if name in SparseTrainableWrapper._LAZY and self.__dict__.get("_lookup_ids") is not None:
+      uniq, self._idx, self._n_unique = device_ops.unique(self._lookup_ids)
+      self._lookup_ids, self.ids, self._values, self.exists = None, uniq.reshape(-1), None, None
+      self.prefetch_values()
+      return self.__dict__[name]
+    raise AttributeError("%s has no attribute %r" % (type(self).__name__, name))
 
   def take_entry_plan(self):
     """The write-back plan over the entry ids started at lookup time (or None); handed back to the pool after its use."""
@@ -565,6 +604,12 @@ def embedding_lookup_unique(params, ids, partition_strategy=None, name=None, val
   return (emb, tw) if return_trainable else emb
 
 
+def _pooled_forward(params, max_norm):
+  """Whether embedding_lookup_sparse reads through `Variable.lookup_combined`: the variable qualifies, nothing is clipped
+  (max_norm acts on the unique rows) and the wrapper needs no `exists` at lookup time (bp_v2)."""
+  return max_norm is None and not params.bp_v2 and params.can_lookup_combined()
+
+
 def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=None, name="embedding_lookup_sparse",
                             combiner="mean", max_norm=None, return_trainable=False, num_rows=None, plan_writeback=False,
                             _entries=None, _out_shape=None):
@@ -580,8 +625,20 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=
   indices = torch.as_tensor(indices, device=params._primary)
   seg = (indices[:, 0] if indices.dim() == 2 else indices).to(torch.int64)
   ids = torch.as_tensor(ids, device=params._primary)
-  uniq, idx, cnt = device_ops.unique(ids)
   w = sp_weights if sp_weights is None else torch.as_tensor(sp_weights, dtype=torch.float32, device=params._primary)
+  if _pooled_forward(params, max_norm):
+    # the pooled read: one probe + row read per entry, combined in registers — no unique pass, no [U, dim] rows, no host read of
+    # a count (the result is bit-identical to the chain below)
+    n = int(seg.max().item()) + 1 if num_rows is None else num_rows
+    out = params.lookup_combined(ids, seg, w, combiner, n)
+    if not return_trainable:
+      return out
+    e_ids, e_seg, e_w = _entries if _entries is not None else (ids.reshape(-1), seg, w)   # ids keep their key dtype
+    tw = SparseTrainableWrapper(params, None, None, None, seg, w, combiner, n,
+                                _out_shape if _out_shape is not None else (n, params.dim), e_ids, e_seg, e_w,
+                                max_norm=max_norm, plan_writeback=plan_writeback, lookup_ids=ids)
+    return out, tw
+  uniq, idx, cnt = device_ops.unique(ids)
   n = int(seg.max().item()) + 1 if num_rows is None else num_rows
   if return_trainable:
     e_ids, e_seg, e_w = _entries if _entries is not None else (ids.reshape(-1), seg, w)   # ids keep their key dtype

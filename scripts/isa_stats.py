@@ -17,7 +17,7 @@ for line in open(out):
     cur = None
   m = re.match(r"\s+\.name:\s+(\S+)", line)
   if m: last_name = m.group(1)
-  m = re.match(r"\s+\.(vgpr_count|sgpr_count|vgpr_spill_count|group_segment_fixed_size):\s+(\d+)", line)
+  m = re.match(r"\s+\.(vgpr_count|sgpr_count|vgpr_spill_count|group_segment_fixed_size|private_segment_fixed_size):\s+(\d+)", line)
   if m and last_name: regs.setdefault(last_name, {})[m.group(1)] = int(m.group(2))
   if cur is None: continue
   t = line.strip().split()
