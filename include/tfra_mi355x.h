@@ -73,7 +73,10 @@ typedef struct {
   int32_t reserved_key_start_bit; /* accepted for attr parity: this engine stores EVERY int64
                                      key (libcuckoo parity), nothing is reserved             */
   int32_t device;                 /* HIP device ordinal; -1 = current                        */
-  float aux_init[4];              /* initial value of aux field f for a newly inserted key   */
+  float aux_init[4];              /* initial value of every element of aux field f + 1 of a newly inserted key,
+                                     converted to value_dtype once at create: F32 as is; F16 and BF16 rounded
+                                     to nearest even; I32 and I8 truncated toward zero; I64 and F64 tables
+                                     IGNORE it: their aux fields start at 0                  */
 } tfra_table_opts;
 
 /* Allocation bridge = TFOrDefaultAllocator (lookup_table_op_hkv.h:329-426): lets the host
@@ -194,7 +197,13 @@ int tfra_table_load(tfra_table_t* t, const char* prefix, size_t buffer_keys, tfr
 
 /* Field access for tables created with aux_fields > 0: same as find / insert_or_assign but on
  * state vector `field` (0 = the embedding itself).  Lets `<param>/<opt>/<slot>` variables of
- * create_slots (PY/dynamic_embedding_optimizer.py:870-958) be views of one physical table.   */
+ * create_slots (PY/dynamic_embedding_optimizer.py:870-958) be views of one physical table.
+ * tfra_table_insert_field with field != 0: a resident key gets field `field` replaced and nothing else touched.  A key that
+ * is NOT resident is created: field `field` = the value, field 0 = zeros (the engine holds no default row to give it) and
+ * the other aux fields = aux_init.  Repeated keys without TFRA_FLAG_UNIQUE_KEYS: the last occurrence wins.  A field insert
+ * never evicts: on a bounded table at max_capacity an absent key is created where its home buckets have a free slot, and
+ * is dropped and counted (tfra_table_check_errors reports exactly these keys) where they have none; no resident row
+ * changes either way.  The flag is accepted there with or without unique keys.  (tests/test_gpu_aux_fields.py)          */
 int tfra_table_find_field(tfra_table_t* t, int field, size_t n, const int64_t* keys, void* values,
                           uint8_t* exists, const void* defaults, int default_is_full,
                           tfra_stream_t stream);
@@ -203,7 +212,8 @@ int tfra_table_insert_field(tfra_table_t* t, int field, size_t n, const int64_t*
 /* KV files of one state vector: the reference checkpoints every slot variable of create_slots as its own table
  * (`<param>/<opt>/<slot>` -> `<param>_<opt>_<slot>_mht_<i>of<N>-keys/-values`); here the slot is field `field` of the
  * parameter's rows.  Same format as tfra_table_save / _load (field 0 = the embedding itself).  Load the embedding
- * first: a key that is not resident yet is created with the parameter's default row. */
+ * first: tfra_table_load_field of an aux field creates a key that is not resident yet like tfra_table_insert_field does,
+ * with field 0 = zeros and the other aux fields = aux_init, not with the parameter's default row (the engine has none). */
 int tfra_table_save_field(tfra_table_t* t, int field, const char* prefix, size_t buffer_keys, int append,
                           tfra_stream_t stream, size_t* n_saved);
 int tfra_table_load_field(tfra_table_t* t, int field, const char* prefix, size_t buffer_keys, tfra_stream_t stream,
