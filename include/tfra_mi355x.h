@@ -532,7 +532,33 @@ int tfra_table_find_combine(tfra_table_t* t, tfra_workspace_t* ws, size_t nnz, c
                             const float* weights, int combiner, size_t n_rows, const void* default_row, float* out,
                             tfra_stream_t stream);
 
-/* default_partition_fn (PY/dynamic_embedding_variable.py:165-197) + dynamic_partition in one
+/* The pooled lookups of MANY tables in one call (a 26-table model's forward is 26 tfra_table_find_combine calls = 78 enqueues
+ * otherwise): descs[i].out is bit-identical to tfra_table_find_combine(table, ws, nnz, ids, seg, weights, combiner, n_rows,
+ * default_row, out, stream) — the same device code runs — and every rule of that call holds per descriptor (seg ascending,
+ * entries outside [0, n_rows) ignored, empty rows zeros, reserved and duplicate ids, never inserts, the dtype / dim / alignment /
+ * size limits).  n_rows == 0: the descriptor is skipped.  nnz == 0: its out is zero-filled.  n_tables == 0: TFRA_OK.
+ * All descriptors are checked BEFORE anything is enqueued: if one fails, the call returns the code the single call returns for it
+ * (TFRA_ERR_UNSUPPORTED / TFRA_ERR_INVALID; the message names the descriptor's index) and no out of any descriptor is written.
+ * A wrong struct_size, a table on another device than ws, or descs == NULL with n_tables > 0: TFRA_ERR_INVALID.
+ * The same table may appear in several descriptors (two features sharing one table); each distinct table is locked once, in
+ * address order, and ordered behind its last stream once.  The tables' storage is looked at at call time: a table that grew
+ * between two calls is read where it is now.
+ * Enqueues, whatever n_tables: one upload of the descriptors' records (from a ring of pinned slots, each guarded by an event, so
+ * that calls may follow each other with no host synchronisation; the stream is never waited for once ws has its size), one
+ * memset of all rows' bounds, one bounds launch over all descriptors' entries and one combine launch per (value dtype, NCH)
+ * class in the list — NCH = 1 for dim <= 64, 2 for dim <= 128, 4 otherwise: at most 9.  *launches_out (optional, host): the
+ * kernel launches enqueued = the bounds launch (when any nnz > 0) + the combine launches.  Not for stream capture. */
+typedef struct {
+  uint32_t struct_size;      /* = sizeof(tfra_find_combine_desc) */
+  int32_t  combiner;         /* 0 sum | 1 mean | 2 sqrtn */
+  tfra_table_t* table;
+  size_t nnz; const int64_t* ids; const int64_t* seg; const float* weights;   /* weights may be NULL */
+  size_t n_rows; const void* default_row; float* out;                         /* out [n_rows, table dim] float32 */
+} tfra_find_combine_desc;
+int tfra_multi_find_combine(tfra_workspace_t* ws, size_t n_tables, const tfra_find_combine_desc* descs,
+                            uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
+
+/* default_partition_fn(PY/dynamic_embedding_variable.py:165-197) + dynamic_partition in one
  * pass: owner[i] = mode 0: (key & 0x7fffffff) % num_shards (CUDA-build branch)
  *                  mode 1: floor_mod(key, num_shards)       (CPU-build branch)
  *                  mode 2: fmix64(key) % num_shards         (opt-in, Zipf-balanced)

@@ -720,6 +720,7 @@ int tfra_workspace_destroy(tfra_workspace_t* ws) {
   if (ws->h_err) { (void)hipDeviceSynchronize(); (void)hipHostFree(ws->h_err); }
   tfra::destroy_workspace_plan(ws->plan);
   tfra::destroy_workspace_plan(ws->uplan);
+  tfra::destroy_workspace_many(ws->many);
   delete ws;
   return TFRA_OK;
 }

@@ -111,6 +111,7 @@ void destroy_own_plan(Table* t);   // tfra_csr.hip
 int own_upsert_unique(Table* t, hipStream_t s, size_t n, const i64* keys, const void* values, const u64* scores, bool* taken,
                       const uint8_t* accum_exists = nullptr, const int64_t* d_n = nullptr);   // accum_exists: insert_or_accum instead of an assign
 void destroy_workspace_plan(void* plan);   // tfra_csr.hip
+void destroy_workspace_many(void* stage);  // tfra_pool.hip
 void step_epoch_public(Table* t);  // tfra_optim.hip
 
 // Copy granule of rows of `bytes` bytes between two buffers: the largest power of two <= 16 that divides the row size and both
@@ -151,6 +152,7 @@ struct tfra_workspace {
   hipStream_t unq_stream = nullptr;
   bool unq_stream_set = false;
   hipEvent_t unq_ev = nullptr;
+  void* many = nullptr;   // pinned staging ring of tfra_multi_find_combine's descriptor records (tfra_pool.hip)
   int ensure(size_t need, hipStream_t s) {
     if (need <= bytes) return TFRA_OK;
     if (buf) {

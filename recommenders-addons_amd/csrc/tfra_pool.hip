@@ -9,7 +9,9 @@
 // compiles, in the same order, so the result equals tfra_table_find + tfra_sparse_segment_combine bit for bit.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <string>
+#include <vector>
 
 #include "../../include/tfra_mi355x.h"
 #include "tfra_combine_device.h"
@@ -56,16 +58,16 @@ template <> struct PoolRow<TFRA_BF16> {
 // Accumulation is strictly in entry order.  Loads stay unconditional, as in find_wave: entries past the row's end are clamped to
 // its last entry (probed and read again, not accumulated), columns past dim to column 0.
 // The probe is find_kernel's (probe_find_word: plain loads), so a lookup that runs beside a write-back sees what tfra_table_find sees.
+// The body is one function with two callers — find_combine_kernel (one table per launch) and find_combine_many_kernel (a list of
+// tables per launch) — so that both compile the same expressions: r is the output row of this lane's group in ITS table.
 template <int DT, int U, int NCH>
-__global__ __launch_bounds__(256) void find_combine_kernel(TableView v, size_t n_rows, int dim, const i64* __restrict__ ids,
-                                                           const float* __restrict__ w, const int* __restrict__ start_end,
-                                                           int combiner, const unsigned char* __restrict__ default_row,
-                                                           float* __restrict__ out) {
+__device__ __forceinline__ void find_combine_row(const TableView& v, size_t n_rows, int dim, const i64* __restrict__ ids,
+                                                 const float* __restrict__ w, const int* __restrict__ start_end, int combiner,
+                                                 const unsigned char* __restrict__ default_row, float* __restrict__ out, size_t r) {
   static_assert(U == 4, "keep_live is written for U == 4");
   typedef typename PoolRow<DT>::Raw Raw;
   constexpr unsigned EB = DT == TFRA_F32 ? 4u : 2u;   // bytes per element
   const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
-  const size_t r = ((size_t)blockIdx.x * 256 + threadIdx.x) >> 4;
   if (r >= n_rows) return;
   const int b = start_end[r], e = start_end[n_rows + r];
   const float wsum = combiner == 0 ? 0.f : comb_wsum(w, b, e, combiner);
@@ -139,6 +141,139 @@ __global__ __launch_bounds__(256) void find_combine_kernel(TableView v, size_t n
     if (cok[c]) *reinterpret_cast<float4*>(o + c * 64 + sub * 4) = comb_finish4(acc[c], wsum, scale, combiner);
 }
 
+template <int DT, int U, int NCH>
+__global__ __launch_bounds__(256) void find_combine_kernel(TableView v, size_t n_rows, int dim, const i64* __restrict__ ids,
+                                                           const float* __restrict__ w, const int* __restrict__ start_end,
+                                                           int combiner, const unsigned char* __restrict__ default_row,
+                                                           float* __restrict__ out) {
+  find_combine_row<DT, U, NCH>(v, n_rows, dim, ids, w, start_end, combiner, default_row, out,
+                               ((size_t)blockIdx.x * 256 + threadIdx.x) >> 4);
+}
+
+// ---- the grouped form (tfra_multi_find_combine): the lookups of a LIST of tables in one launch per (value dtype, NCH) class ------
+// What a single-table launch takes as kernel arguments is a record in device memory here (26 tables' records do not fit the 4 KB
+// of kernel arguments: a TableView alone is 80 B).  The grid is the concatenation of the class's descriptors, descriptor d owning
+// the blocks [prefix[d], prefix[d + 1]) = ceil(n_rows * 16 / 256) blocks, so that a block never straddles two descriptors.
+struct ManyRec {
+  TableView v;
+  size_t n_rows;
+  const i64* ids;
+  const float* w;
+  const int* se;
+  const unsigned char* default_row;
+  float* out;
+  int dim;
+  int combiner;
+};
+struct BoundsRec {
+  const i64* seg;
+  int* se;
+  size_t nnz;
+  size_t n_rows;
+};
+
+// The descriptor of block `blk`: the d with prefix[d] <= blk < prefix[d + 1] (prefix[0] = 0, prefix[n] = the grid; strictly
+// ascending: no descriptor has zero blocks).  blk is blockIdx.x, so the search, the record's address and the record are
+// wave-uniform: scalar loads into scalar registers, as kernel arguments are.
+__device__ __forceinline__ unsigned many_desc_of(const unsigned* __restrict__ prefix, unsigned n, unsigned blk) {
+  unsigned lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const unsigned mid = (lo + hi) >> 1;
+    if (prefix[mid] <= blk) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+template <int DT, int U, int NCH>
+__global__ __launch_bounds__(256) void find_combine_many_kernel(const ManyRec* __restrict__ recs, const unsigned* __restrict__ prefix,
+                                                                unsigned n) {
+  const unsigned d = many_desc_of(prefix, n, blockIdx.x);
+  const ManyRec rec = recs[d];
+  find_combine_row<DT, U, NCH>(rec.v, rec.n_rows, rec.dim, rec.ids, rec.w, rec.se, rec.combiner, rec.default_row, rec.out,
+                               ((size_t)(blockIdx.x - prefix[d]) * 256 + threadIdx.x) >> 4);
+}
+
+// seg64_bounds_kernel (tfra_frontend.hip) over a list: descriptor d owns ceil(nnz / 256) blocks and p counts ITS entries, so the
+// neighbours p - 1 / p + 1 are never read across a descriptor's end.  se zeroed before (empty rows: 0, 0).
+__global__ __launch_bounds__(256) void seg64_bounds_many_kernel(const BoundsRec* __restrict__ recs, const unsigned* __restrict__ prefix,
+                                                                unsigned n) {
+  const unsigned d = many_desc_of(prefix, n, blockIdx.x);
+  const BoundsRec rec = recs[d];
+  const size_t p = (size_t)(blockIdx.x - prefix[d]) * 256 + threadIdx.x;
+  if (p >= rec.nnz) return;
+  const i64 s = rec.seg[p];
+  if (s < 0 || (size_t)s >= rec.n_rows) return;
+  if (p == 0 || rec.seg[p - 1] != s) rec.se[s] = (int)p;
+  if (p == rec.nnz - 1 || rec.seg[p + 1] != s) rec.se[rec.n_rows + s] = (int)p + 1;
+}
+
+template <int DT>
+void launch_find_combine_many(hipStream_t s, int nch, unsigned grid, const ManyRec* recs, const unsigned* prefix, unsigned n) {
+  constexpr int U = 4;
+  if (nch == 0) find_combine_many_kernel<DT, U, 1><<<grid, 256, 0, s>>>(recs, prefix, n);
+  else if (nch == 1) find_combine_many_kernel<DT, U, 2><<<grid, 256, 0, s>>>(recs, prefix, n);
+  else find_combine_many_kernel<DT, U, 4><<<grid, 256, 0, s>>>(recs, prefix, n);
+}
+
+// The records reach the device by ONE asynchronous copy per call from a pinned staging slot.  Two calls may be enqueued back to
+// back with nothing waited for in between, so a slot must not be rewritten while its copy has not run: the slots form a ring,
+// each guarded by an event recorded behind its copy.  Taking a slot waits for ITS event only — in the steady state the copy of
+// RING calls ago, long done — never for the stream.  A list that outgrows the slots waits for the pending copies and reallocates.
+struct ManyStage {
+  static constexpr int RING = 8;
+  unsigned char* host = nullptr;
+  size_t slot_bytes = 0;
+  hipEvent_t ev[RING] = {};
+  bool pending[RING] = {};
+  unsigned next = 0;
+
+  int drain() {
+    for (int i = 0; i < RING; ++i)
+      if (pending[i]) { HIP_TRY(hipEventSynchronize(ev[i])); pending[i] = false; }
+    return TFRA_OK;
+  }
+  int take(size_t need, unsigned char** out, int* slot) {
+    if (!ev[0])
+      for (int i = 0; i < RING; ++i) HIP_TRY(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
+    if (need > slot_bytes) {
+      int rc = drain();
+      if (rc) return rc;
+      if (host) { HIP_TRY(hipHostFree(host)); host = nullptr; slot_bytes = 0; }
+      const size_t want = (std::max<size_t>(need, 8192) + 4095) / 4096 * 4096;
+      HIP_TRY(hipHostMalloc((void**)&host, want * RING, hipHostMallocDefault));
+      slot_bytes = want;
+    }
+    const int i = (int)(next++ % RING);
+    if (pending[i]) { HIP_TRY(hipEventSynchronize(ev[i])); pending[i] = false; }
+    *out = host + (size_t)i * slot_bytes;
+    *slot = i;
+    return TFRA_OK;
+  }
+};
+
+// the single call's checks of one descriptor, in its order and with its codes; *active: the descriptor has rows to write
+int check_desc(const tfra_find_combine_desc& d, const tfra_workspace* ws, bool* active, std::string* msg) {
+  *active = false;
+  if (d.struct_size != sizeof(tfra_find_combine_desc)) { *msg = "descriptor size mismatch"; return TFRA_ERR_INVALID; }
+  const Table* t = reinterpret_cast<const Table*>(d.table);
+  if (!t) { *msg = "null table"; return TFRA_ERR_INVALID; }
+  if (d.combiner < 0 || d.combiner > 2) { *msg = "bad argument"; return TFRA_ERR_INVALID; }
+  if (ws->device != t->device) { *msg = "workspace and table live on different devices"; return TFRA_ERR_INVALID; }
+  const int dt = t->opts.value_dtype, dim = t->opts.dim;
+  if (dt != TFRA_F32 && dt != TFRA_F16 && dt != TFRA_BF16) { *msg = "value_dtype must be float32, float16 or bfloat16"; return TFRA_ERR_UNSUPPORTED; }
+  if (dim % 4 != 0 || dim > 256) { *msg = "needs dim % 4 == 0 and dim <= 256"; return TFRA_ERR_UNSUPPORTED; }
+  if (d.nnz >= (1ULL << 31) || d.n_rows >= (1ULL << 30)) { *msg = "too large (nnz < 2^31, n_rows < 2^30)"; return TFRA_ERR_UNSUPPORTED; }
+  if ((((uintptr_t)d.out | (uintptr_t)d.default_row) & 15) || ((uintptr_t)d.ids & 7) || ((uintptr_t)d.seg & 7) || ((uintptr_t)d.weights & 3)) {
+    *msg = "misaligned buffer (out and default_row: 16 bytes)";
+    return TFRA_ERR_UNSUPPORTED;
+  }
+  if (d.n_rows == 0) return TFRA_OK;
+  if (!d.out) { *msg = "null out"; return TFRA_ERR_INVALID; }
+  if (d.nnz && (!d.ids || !d.seg || !d.default_row)) { *msg = "null buffer"; return TFRA_ERR_INVALID; }
+  *active = true;
+  return TFRA_OK;
+}
+
 template <int DT>
 void launch_find_combine(hipStream_t s, const TableView& v, size_t n_rows, int dim, const i64* ids, const float* w, const int* se,
                          int combiner, const unsigned char* d, float* out) {
@@ -190,5 +325,166 @@ extern "C" int tfra_table_find_combine(tfra_table_t* tp, tfra_workspace_t* ws, s
   else if (dt == TFRA_F16) launch_find_combine<TFRA_F16>(s, v, n_rows, dim, k, weights, se, combiner, d, out);
   else launch_find_combine<TFRA_BF16>(s, v, n_rows, dim, k, weights, se, combiner, d, out);
   HIP_TRY(hipGetLastError());
+  return TFRA_OK;
+}
+
+namespace tfra {
+void destroy_workspace_many(void* p) {
+  ManyStage* st = reinterpret_cast<ManyStage*>(p);
+  if (!st) return;
+  for (int i = 0; i < ManyStage::RING; ++i) {
+    if (st->pending[i]) (void)hipEventSynchronize(st->ev[i]);
+    if (st->ev[i]) (void)hipEventDestroy(st->ev[i]);
+  }
+  if (st->host) (void)hipHostFree(st->host);
+  delete st;
+}
+}  // namespace tfra
+
+extern "C" int tfra_multi_find_combine(tfra_workspace_t* ws, size_t n_tables, const tfra_find_combine_desc* descs,
+                                       uint32_t* launches_out, tfra_stream_t stream) {
+  if (launches_out) *launches_out = 0;
+  if (n_tables == 0) return TFRA_OK;
+  if (!ws || !descs) return set_error(TFRA_ERR_INVALID, "multi_find_combine: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  // every descriptor is checked before anything is enqueued: one bad descriptor and no out is written
+  constexpr int NCLASS = 9;   // (float32 | float16 | bfloat16) x (NCH 1 | 2 | 4)
+  std::vector<int> cls(n_tables, -1);
+  size_t n_act = 0, n_bnd = 0, total_rows = 0;
+  for (size_t i = 0; i < n_tables; ++i) {
+    bool active = false;
+    std::string msg;
+    const int rc = check_desc(descs[i], ws, &active, &msg);
+    if (rc) return set_error(rc, "multi_find_combine: descriptor " + std::to_string(i) + ": " + msg);
+    if (!active) continue;
+    const Table* t = reinterpret_cast<const Table*>(descs[i].table);
+    const int dt = t->opts.value_dtype, dim = t->opts.dim;
+    cls[i] = (dt == TFRA_F32 ? 0 : dt == TFRA_F16 ? 1 : 2) * 3 + (dim <= 64 ? 0 : dim <= 128 ? 1 : 2);
+    ++n_act;
+    n_bnd += descs[i].nnz ? 1 : 0;
+    total_rows += descs[i].n_rows;
+  }
+  if (n_act == 0) return TFRA_OK;
+  // the records' order: class by class, input order inside a class
+  std::vector<size_t> order;
+  order.reserve(n_act);
+  size_t cls_first[NCLASS + 1];
+  u64 cls_blocks[NCLASS], bnd_blocks = 0;
+  for (int c = 0; c < NCLASS; ++c) {
+    cls_first[c] = order.size();
+    cls_blocks[c] = 0;
+    for (size_t i = 0; i < n_tables; ++i)
+      if (cls[i] == c) { order.push_back(i); cls_blocks[c] += (descs[i].n_rows * 16 + 255) / 256; }
+    if (cls_blocks[c] >= (1ULL << 31)) return set_error(TFRA_ERR_UNSUPPORTED, "multi_find_combine: too many rows in one call");
+  }
+  cls_first[NCLASS] = order.size();
+  for (size_t i = 0; i < n_tables; ++i)
+    if (cls[i] >= 0) bnd_blocks += (descs[i].nnz + 255) / 256;
+  if (bnd_blocks >= (1ULL << 31)) return set_error(TFRA_ERR_UNSUPPORTED, "multi_find_combine: too many entries in one call");
+
+  // each distinct table locked once, in one global order (by address): two threads with overlapping lists cannot deadlock
+  std::vector<Table*> tabs;
+  tabs.reserve(n_act);
+  for (size_t i : order) tabs.push_back(reinterpret_cast<Table*>(descs[i].table));
+  std::sort(tabs.begin(), tabs.end(), std::less<Table*>());
+  tabs.erase(std::unique(tabs.begin(), tabs.end()), tabs.end());
+  std::vector<std::unique_lock<std::mutex>> locks;
+  locks.reserve(tabs.size());
+  for (Table* t : tabs) locks.emplace_back(t->mu);
+  for (Table* t : tabs) {
+    const int rc = t->enter(s);
+    if (rc) return rc;
+  }
+
+  // device memory: [bounds of all rows | records | per-class block prefixes | bounds records | their block prefix]
+  const size_t se_bytes = (2 * total_rows * sizeof(int) + 255) / 256 * 256;
+  const size_t rec_off = 0, cpre_off = (n_act * sizeof(ManyRec) + 15) / 16 * 16;
+  const size_t brec_off = (cpre_off + (n_act + NCLASS) * sizeof(unsigned) + 15) / 16 * 16;
+  const size_t bpre_off = brec_off + n_bnd * sizeof(BoundsRec);
+  const size_t blob_bytes = (bpre_off + (n_bnd + 1) * sizeof(unsigned) + 255) / 256 * 256;
+  int rc = ws->ensure(se_bytes + blob_bytes, s);
+  if (rc) return rc;
+  if (!ws->many) ws->many = new ManyStage();
+  ManyStage* stage = reinterpret_cast<ManyStage*>(ws->many);
+  unsigned char* h = nullptr;
+  int slot = 0;
+  rc = stage->take(blob_bytes, &h, &slot);
+  if (rc) return rc;
+  int* se_base = (int*)ws->buf;
+  unsigned char* d_blob = (unsigned char*)ws->buf + se_bytes;
+  ManyRec* recs = reinterpret_cast<ManyRec*>(h + rec_off);
+  unsigned* cpre = reinterpret_cast<unsigned*>(h + cpre_off);
+  BoundsRec* brecs = reinterpret_cast<BoundsRec*>(h + brec_off);
+  unsigned* bpre = reinterpret_cast<unsigned*>(h + bpre_off);
+  // the views are taken here, under the locks: a table that grew since the last call has another one
+  std::vector<size_t> se_off(n_tables, 0);
+  {
+    size_t off = 0;
+    for (size_t i = 0; i < n_tables; ++i)
+      if (cls[i] >= 0) { se_off[i] = off; off += 2 * descs[i].n_rows; }
+  }
+  size_t cpre_at[NCLASS];
+  {
+    size_t k = 0, pre = 0;
+    for (int c = 0; c < NCLASS; ++c) {
+      cpre_at[c] = pre;
+      if (cls_first[c] == cls_first[c + 1]) continue;
+      unsigned blocks = 0;
+      for (size_t j = cls_first[c]; j < cls_first[c + 1]; ++j, ++k) {
+        const tfra_find_combine_desc& d = descs[order[j]];
+        Table* t = reinterpret_cast<Table*>(d.table);
+        ManyRec& r = recs[k];
+        r.v = t->view_of(t->cur);
+        r.n_rows = d.n_rows;
+        r.ids = (const i64*)d.ids;
+        r.w = d.weights;
+        r.se = se_base + se_off[order[j]];
+        r.default_row = (const unsigned char*)d.default_row;
+        r.out = d.out;
+        r.dim = t->opts.dim;
+        r.combiner = d.combiner;
+        cpre[pre++] = blocks;
+        blocks += (unsigned)((d.n_rows * 16 + 255) / 256);
+      }
+      cpre[pre++] = blocks;
+    }
+  }
+  {
+    size_t k = 0;
+    unsigned blocks = 0;
+    for (size_t i = 0; i < n_tables; ++i) {
+      if (cls[i] < 0 || descs[i].nnz == 0) continue;
+      brecs[k].seg = (const i64*)descs[i].seg;
+      brecs[k].se = se_base + se_off[i];
+      brecs[k].nnz = descs[i].nnz;
+      brecs[k].n_rows = descs[i].n_rows;
+      bpre[k++] = blocks;
+      blocks += (unsigned)((descs[i].nnz + 255) / 256);
+    }
+    bpre[k] = blocks;
+  }
+  HIP_TRY(hipMemcpyAsync(d_blob, h, blob_bytes, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipEventRecord(stage->ev[slot], s));
+  stage->pending[slot] = true;
+  HIP_TRY(hipMemsetAsync(se_base, 0, 2 * total_rows * sizeof(int), s));   // empty rows (and every row of an nnz == 0 descriptor): 0, 0
+  uint32_t launches = 0;
+  if (n_bnd) {
+    seg64_bounds_many_kernel<<<(unsigned)bnd_blocks, 256, 0, s>>>(reinterpret_cast<const BoundsRec*>(d_blob + brec_off),
+                                                                  reinterpret_cast<const unsigned*>(d_blob + bpre_off), (unsigned)n_bnd);
+    ++launches;
+  }
+  for (int c = 0; c < NCLASS; ++c) {
+    const unsigned n = (unsigned)(cls_first[c + 1] - cls_first[c]);
+    if (!n) continue;
+    const ManyRec* r = reinterpret_cast<const ManyRec*>(d_blob + rec_off) + cls_first[c];
+    const unsigned* p = reinterpret_cast<const unsigned*>(d_blob + cpre_off) + cpre_at[c];
+    const unsigned grid = (unsigned)cls_blocks[c];
+    if (c / 3 == 0) launch_find_combine_many<TFRA_F32>(s, c % 3, grid, r, p, n);
+    else if (c / 3 == 1) launch_find_combine_many<TFRA_F16>(s, c % 3, grid, r, p, n);
+    else launch_find_combine_many<TFRA_BF16>(s, c % 3, grid, r, p, n);
+    ++launches;
+  }
+  HIP_TRY(hipGetLastError());
+  if (launches_out) *launches_out = launches;
   return TFRA_OK;
 }

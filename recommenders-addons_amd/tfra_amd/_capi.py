@@ -70,6 +70,15 @@ class StepDesc(ctypes.Structure):
   ]
 
 
+class FindCombineDesc(ctypes.Structure):
+  """tfra_find_combine_desc (include/tfra_mi355x.h): one table's pooled lookup in tfra_multi_find_combine."""
+  _fields_ = [
+      ("struct_size", ctypes.c_uint32), ("combiner", ctypes.c_int32), ("table", ctypes.c_void_p), ("nnz", ctypes.c_size_t),
+      ("ids", ctypes.c_void_p), ("seg", ctypes.c_void_p), ("weights", ctypes.c_void_p), ("n_rows", ctypes.c_size_t),
+      ("default_row", ctypes.c_void_p), ("out", ctypes.c_void_p),
+  ]
+
+
 class OverlapStep(ctypes.Structure):
   """tfra_overlap_step (include/tfra_mi355x.h): one step of tfra_table_steps_overlap."""
   _fields_ = [
@@ -150,6 +159,7 @@ _SIGS = {
     "tfra_unique_unordered": [_P, _SZ, _P, _P, _P, _P, _P],
     "tfra_table_find_unique": [_P, _P, _SZ, _P, _P, _P, _P, _I, _P, _P, _P, _P],
     "tfra_table_find_combine": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, _P, _P],
+    "tfra_multi_find_combine": [_P, _SZ, _P, _P, _P],
     "tfra_segment_sum": [_P, _SZ, _I, _P, _P, _P, _SZ, _P, _P],
     "tfra_gather_rows": [_SZ, _SZ, _P, _P, _P, _P],
     "tfra_keys_widen_i32": [_SZ, _P, _P, _P],

@@ -9,7 +9,7 @@ from .table_ops import (SparsePlan, CuckooHashTable, HkvEvictStrategy, HkvHashTa
                         KHkvHashTableMaxCapacity, KHkvHashTableMaxHbmForValuesByBytes)
 from .variable import (CuckooHashTableConfig, CuckooHashTableCreator, HkvHashTableConfig, HkvHashTableCreator,
                        KVCreator, SparseTrainableWrapper, TrainableWrapper, Variable, default_partition_fn, embedding_lookup,
-                       embedding_lookup_sparse, embedding_lookup_unique, get_variable,
-                       safe_embedding_lookup_sparse)
+                       embedding_lookup_sparse, embedding_lookup_sparse_many, embedding_lookup_unique, get_variable,
+                       safe_embedding_lookup_sparse, safe_embedding_lookup_sparse_many)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -263,13 +263,9 @@ class _DeviceTable:
     uniq = _narrow_keys(uniq, self._key_dtype)   # the table's key dtype, so that `unique` goes back into upsert / erase
     return (out, uniq, idx, cnt, exists) if return_exists else (out, uniq, idx, cnt)
 
-  def find_combine(self, ids, seg, weights, combiner, n_rows, default_row=None):
-    """The pooled lookup (tfra_table_find_combine): out[r] = combine over {p: seg[p] == r}, in input order, of weights[p] * (the row
-    of ids[p], or `default_row` — one row of the value dtype, the table's default when None — on a miss), float32 [n_rows, dim].
-    seg ascending int64, weights float32 or None (all 1), combiner 0 sum / 1 mean / 2 sqrtn.  float32 / float16 / bfloat16 rows,
-    dim % 4 == 0, dim <= 256 (TfraError UNSUPPORTED otherwise).  Bit-identical to find + device_ops.sparse_segment_combine over
-    idx = arange(nnz); no unique pass, nothing read on the host."""
-    from .device_ops import _workspace
+  def _find_combine_args(self, ids, seg, weights, n_rows, default_row):
+    """The arguments of one pooled lookup as the C calls read them: (ids, seg, weights or None, default row, out), checked and on
+    the table's device (find_combine and find_combine_many share it)."""
     ids = self._keys(ids).reshape(-1)
     nnz = ids.numel()
     seg = torch.as_tensor(seg, device=self._device).reshape(-1).to(torch.int64).contiguous()
@@ -287,7 +283,17 @@ class _DeviceTable:
       raise ValueError("default_row must be one row of dim=%d elements, got %d" % (self._dim, d.numel()))
     d = d.contiguous()
     out = torch.empty((int(n_rows), self._dim), dtype=torch.float32, device=self._device)
-    _capi.call("tfra_table_find_combine", self._h, _workspace(self._device), nnz, _ptr(ids), _ptr(seg), _ptr(w), int(combiner),
+    return ids, seg, w, d, out
+
+  def find_combine(self, ids, seg, weights, combiner, n_rows, default_row=None):
+    """The pooled lookup (tfra_table_find_combine): out[r] = combine over {p: seg[p] == r}, in input order, of weights[p] * (the row
+    of ids[p], or `default_row` — one row of the value dtype, the table's default when None — on a miss), float32 [n_rows, dim].
+    seg ascending int64, weights float32 or None (all 1), combiner 0 sum / 1 mean / 2 sqrtn.  float32 / float16 / bfloat16 rows,
+    dim % 4 == 0, dim <= 256 (TfraError UNSUPPORTED otherwise).  Bit-identical to find + device_ops.sparse_segment_combine over
+    idx = arange(nnz); no unique pass, nothing read on the host."""
+    from .device_ops import _workspace
+    ids, seg, w, d, out = self._find_combine_args(ids, seg, weights, n_rows, default_row)
+    _capi.call("tfra_table_find_combine", self._h, _workspace(self._device), ids.numel(), _ptr(ids), _ptr(seg), _ptr(w), int(combiner),
                int(n_rows), _ptr(d), _ptr(out), _stream(self._device))
     return out
 
@@ -810,3 +816,39 @@ class HkvHashTable(_LookupInterfaceMirror):
     if not (isinstance(split_size, int) and split_size > 0):
       raise ValueError("split_size must be positive integer.")
     return self._table.export_all(with_scores=True, values=True, split_size=split_size)
+
+
+def find_combine_many(requests, return_launches=False):
+  """The pooled lookups of a list of tables in ONE C call (tfra_multi_find_combine).  `requests`: a list of
+  (table, ids, seg, weights, combiner, n_rows[, default_row]) — `table` a _DeviceTable (or a CuckooHashTable / HkvHashTable, whose
+  device table is taken), the other arguments those of `_DeviceTable.find_combine`, handled the same way (int32 keys widened, the
+  default row falling back to the table's).  All tables live on one device.  Returns the [n_rows, dim] float32 results in the
+  requests' order, each bit-identical to `find_combine` of its request (with return_launches: also the number of kernel launches
+  the call enqueued — it does not grow with the list)."""
+  from .device_ops import _workspace
+  n = len(requests)
+  if n == 0:
+    return ([], 0) if return_launches else []
+  descs = (_capi.FindCombineDesc * n)()
+  keep, outs, device = [], [], None
+  for i, req in enumerate(requests):
+    table, ids, seg, weights, combiner, n_rows = req[:6]
+    default_row = req[6] if len(req) > 6 else None
+    table = getattr(table, "_table", table)
+    if device is None:
+      device = table._device
+    elif table._device != device:
+      raise ValueError("find_combine_many: all tables must live on one device (%s and %s)" % (device, table._device))
+    ids, seg, w, d, out = table._find_combine_args(ids, seg, weights, n_rows, default_row)
+    keep.append((ids, seg, w, d))
+    outs.append(out)
+    e = descs[i]
+    e.struct_size = ctypes.sizeof(_capi.FindCombineDesc)
+    e.combiner = int(combiner)
+    e.table = table._h.value
+    e.nnz, e.ids, e.seg, e.weights = ids.numel(), ids.data_ptr(), seg.data_ptr(), (w.data_ptr() if w is not None else None)
+    e.n_rows, e.default_row, e.out = int(n_rows), d.data_ptr(), out.data_ptr()
+  launches = ctypes.c_uint32(0)
+  _capi.call("tfra_multi_find_combine", _workspace(device), n, ctypes.c_void_p(ctypes.addressof(descs)),
+             ctypes.c_void_p(ctypes.addressof(launches)), _stream(device))
+  return (outs, int(launches.value)) if return_launches else outs

@@ -654,18 +654,78 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=
   return (out, tw) if return_trainable else out
 
 
-def safe_embedding_lookup_sparse(params, sp_ids, sparse_weights=None, combiner="mean", default_id=None,
-                                 name="safe_embedding_lookup_sparse", partition_strategy=None, max_norm=None,
-                                 return_trainable=False, num_rows=None, plan_writeback=False):
-  """PY/dynamic_embedding_ops.py:296-430.  `sp_ids` = (indices[nnz, R], values[nnz][, dense_shape[R]]) — a
-  SparseTensor of rank R >= 2 (or row ids [nnz] for rank 2).  Semantics of the reference, NOT of
-  `tf.nn.safe_embedding_lookup_sparse`: ids are never pruned (any int64 is a legal key, negative ones too,
-  T/dynamic_embedding_ops_test.py:1007-1050); entries with weight <= 0 are dropped unless combiner == "sum"
-  (`_prune_invalid_weights`, :374-376); rows left without entries yield zeros, or the embedding of
-  `default_id` (`sparse_fill_empty_rows`, :379-408); leading dims are flattened for the lookup and restored
-  on the result (:356-367, 411-424)."""
-  if combiner not in ("mean", "sqrtn", "sum"):
-    raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+def _per_table(value, n, what):
+  """`value` as a list of n: a scalar is repeated, a list / tuple must have n entries."""
+  if isinstance(value, (list, tuple)):
+    if len(value) != n:
+      raise ValueError("%s: %d entries for %d tables" % (what, len(value), n))
+    return list(value)
+  return [value] * n
+
+
+def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None, combiner="mean", max_norm=None,
+                                 return_trainable=False, num_rows=None, plan_writeback=False, _entries_list=None,
+                                 _out_shapes=None):
+  """`embedding_lookup_sparse` of a LIST of variables (a many-table model's sparse features): result i is what
+  `embedding_lookup_sparse(params_list[i], sp_ids_list[i], sp_weights_list[i], ...)` returns, bit for bit — with return_trainable
+  the (result, SparseTrainableWrapper) pair, the wrapper built behind the pooled forward.  `combiner` and `num_rows` are scalars
+  or per-table lists.  The variables the pooled forward serves (`_pooled_forward`) are read by ONE grouped call per device
+  (`table_ops.find_combine_many`: tfra_multi_find_combine, whose launch count does not grow with the list); every other variable
+  takes `embedding_lookup_sparse` as it is, so no list is refused.  Where num_rows is absent, the grouped variables' row counts
+  come from one host read per device, not one per table."""
+  from . import table_ops
+  n_t = len(params_list)
+  if len(sp_ids_list) != n_t:
+    raise ValueError("sp_ids_list: %d entries for %d tables" % (len(sp_ids_list), n_t))
+  weights = _per_table(None if sp_weights_list is None else list(sp_weights_list), n_t, "sp_weights_list")
+  combiners = _per_table(combiner, n_t, "combiner")
+  rows = _per_table(num_rows, n_t, "num_rows")
+  entries = _per_table(None if _entries_list is None else list(_entries_list), n_t, "_entries_list")
+  shapes = _per_table(None if _out_shapes is None else list(_out_shapes), n_t, "_out_shapes")
+  for c in combiners:
+    if c not in ("mean", "sqrtn", "sum"):
+      raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+  results = [None] * n_t
+  groups = {}   # device -> [(i, ids, seg, w)]
+  for i, params in enumerate(params_list):
+    if not _pooled_forward(params, max_norm):
+      results[i] = embedding_lookup_sparse(params, sp_ids_list[i], weights[i], combiner=combiners[i], max_norm=max_norm,
+                                           return_trainable=return_trainable, num_rows=rows[i], plan_writeback=plan_writeback,
+                                           _entries=entries[i], _out_shape=shapes[i])
+      continue
+    indices, ids = sp_ids_list[i]
+    indices = torch.as_tensor(indices, device=params._primary)
+    seg = (indices[:, 0] if indices.dim() == 2 else indices).to(torch.int64)
+    ids = torch.as_tensor(ids, device=params._primary)
+    w = weights[i] if weights[i] is None else torch.as_tensor(weights[i], dtype=torch.float32, device=params._primary)
+    groups.setdefault(params._primary, []).append((i, ids, seg, w))
+  for device, members in groups.items():
+    unknown = [m for m in members if rows[m[0]] is None]
+    if unknown:   # the row counts of all of them in one host read
+      for m, top in zip(unknown, torch.stack([m[2].max() for m in unknown]).tolist()):
+        rows[m[0]] = int(top) + 1
+    reqs = []
+    for i, ids, seg, w in members:
+      t = params_list[i]._tables[0]
+      reqs.append((t._table, ids.reshape(-1), seg, w, device_ops.COMBINERS[combiners[i]], rows[i], t._default_value))
+    outs = table_ops.find_combine_many(reqs)
+    for (i, ids, seg, w), out in zip(members, outs):
+      if not return_trainable:
+        results[i] = out
+        continue
+      params, n = params_list[i], rows[i]
+      e_ids, e_seg, e_w = entries[i] if entries[i] is not None else (ids.reshape(-1), seg, w)   # ids keep their key dtype
+      tw = SparseTrainableWrapper(params, None, None, None, seg, w, combiners[i], n,
+                                  shapes[i] if shapes[i] is not None else (n, params.dim), e_ids, e_seg, e_w,
+                                  max_norm=max_norm, plan_writeback=plan_writeback, lookup_ids=ids)
+      results[i] = (out, tw)
+  return results
+
+
+def _safe_sparse_args(params, sp_ids, sparse_weights, combiner, default_id, return_trainable, num_rows):
+  """The preprocessing of safe_embedding_lookup_sparse (PY/dynamic_embedding_ops.py:356-408): pruning by weight, the rank > 2
+  flattening, the number of rows and — for a trainable — the entry list with one entry per empty row.  Returns what
+  `embedding_lookup_sparse` is then called with and what `_safe_sparse_finish` needs: (rows, ids, w, n, entries, out_shape, lead)."""
   dense_shape = None
   if len(sp_ids) == 3:
     indices, ids, dense_shape = sp_ids
@@ -719,10 +779,12 @@ def safe_embedding_lookup_sparse(params, sp_ids, sparse_weights=None, combiner="
     entries = (all_ids[order].contiguous(), all_rows[order].contiguous(),
                None if (w is None and default_id is not None) else all_w[order].contiguous())
   out_shape = (tuple(lead) if lead is not None else (n,)) + (params.dim,)
-  out = embedding_lookup_sparse(params, (rows, ids), w, combiner=combiner, max_norm=max_norm,
-                                return_trainable=return_trainable, num_rows=n, plan_writeback=plan_writeback,
-                                _entries=entries, _out_shape=out_shape)
-  res, tw = out if return_trainable else (out, None)
+  return rows, ids, w, n, entries, out_shape, lead
+
+
+def _safe_sparse_finish(params, res, rows, n, default_id, max_norm, lead):
+  """The end of safe_embedding_lookup_sparse: the embedding of `default_id` in the rows left empty (:392-408), the leading dims
+  restored (:411-424)."""
   if default_id is not None and n:
     empty = torch.ones(n, dtype=torch.bool, device=res.device)
     empty[rows] = False
@@ -731,4 +793,65 @@ def safe_embedding_lookup_sparse(params, sp_ids, sparse_weights=None, combiner="
     res = torch.where(empty[:, None], d, res)
   if lead is not None:
     res = res.reshape(tuple(lead) + (res.shape[-1],))
+  return res
+
+
+def safe_embedding_lookup_sparse(params, sp_ids, sparse_weights=None, combiner="mean", default_id=None,
+                                 name="safe_embedding_lookup_sparse", partition_strategy=None, max_norm=None,
+                                 return_trainable=False, num_rows=None, plan_writeback=False):
+  """PY/dynamic_embedding_ops.py:296-430.  `sp_ids` = (indices[nnz, R], values[nnz][, dense_shape[R]]) — a
+  SparseTensor of rank R >= 2 (or row ids [nnz] for rank 2).  Semantics of the reference, NOT of
+  `tf.nn.safe_embedding_lookup_sparse`: ids are never pruned (any int64 is a legal key, negative ones too,
+  T/dynamic_embedding_ops_test.py:1007-1050); entries with weight <= 0 are dropped unless combiner == "sum"
+  (`_prune_invalid_weights`, :374-376); rows left without entries yield zeros, or the embedding of
+  `default_id` (`sparse_fill_empty_rows`, :379-408); leading dims are flattened for the lookup and restored
+  on the result (:356-367, 411-424)."""
+  if combiner not in ("mean", "sqrtn", "sum"):
+    raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+  rows, ids, w, n, entries, out_shape, lead = _safe_sparse_args(params, sp_ids, sparse_weights, combiner, default_id,
+                                                                 return_trainable, num_rows)
+  out = embedding_lookup_sparse(params, (rows, ids), w, combiner=combiner, max_norm=max_norm,
+                                return_trainable=return_trainable, num_rows=n, plan_writeback=plan_writeback,
+                                _entries=entries, _out_shape=out_shape)
+  res, tw = out if return_trainable else (out, None)
+  res = _safe_sparse_finish(params, res, rows, n, default_id, max_norm, lead)
   return (res, tw) if return_trainable else res
+
+
+def safe_embedding_lookup_sparse_many(params_list, sp_ids_list, sparse_weights_list=None, combiner="mean", default_id=None,
+                                      max_norm=None, return_trainable=False, num_rows=None, plan_writeback=False):
+  """`safe_embedding_lookup_sparse` of a LIST of variables: result i is what the single form returns for table i, bit for bit.
+  `combiner`, `default_id` and `num_rows` are scalars or per-table lists.  The preprocessing is the single form's
+  (`_safe_sparse_args`); the lookups go through `embedding_lookup_sparse_many`, one grouped call per device for the variables
+  the pooled forward serves.  Row counts that neither a dense_shape nor num_rows gives are read in one host read per device."""
+  n_t = len(params_list)
+  if len(sp_ids_list) != n_t:
+    raise ValueError("sp_ids_list: %d entries for %d tables" % (len(sp_ids_list), n_t))
+  weights = _per_table(None if sparse_weights_list is None else list(sparse_weights_list), n_t, "sparse_weights_list")
+  combiners = _per_table(combiner, n_t, "combiner")
+  default_ids = _per_table(default_id, n_t, "default_id")
+  num = _per_table(num_rows, n_t, "num_rows")
+  for c in combiners:
+    if c not in ("mean", "sqrtn", "sum"):
+      raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+  unknown = {}   # device -> [(i, row ids)]: rank 2, no dense_shape, no num_rows, at least one entry
+  for i, params in enumerate(params_list):
+    if num[i] is None and len(sp_ids_list[i]) == 2:
+      indices = torch.as_tensor(sp_ids_list[i][0], device=params._primary)
+      if indices.numel() and (indices.dim() == 1 or indices.shape[1] <= 2):
+        unknown.setdefault(params._primary, []).append((i, indices[:, 0] if indices.dim() == 2 else indices))
+  for members in unknown.values():
+    for (i, _), top in zip(members, torch.stack([r.max() for _, r in members]).tolist()):
+      num[i] = int(top) + 1
+  args = [_safe_sparse_args(params_list[i], sp_ids_list[i], weights[i], combiners[i], default_ids[i], return_trainable, num[i])
+          for i in range(n_t)]
+  outs = embedding_lookup_sparse_many(params_list, [(a[0], a[1]) for a in args], [a[2] for a in args], combiner=combiners,
+                                      max_norm=max_norm, return_trainable=return_trainable, num_rows=[a[3] for a in args],
+                                      plan_writeback=plan_writeback, _entries_list=[a[4] for a in args],
+                                      _out_shapes=[a[5] for a in args])
+  results = []
+  for i, (rows, ids, w, n, entries, out_shape, lead) in enumerate(args):
+    res, tw = outs[i] if return_trainable else (outs[i], None)
+    res = _safe_sparse_finish(params_list[i], res, rows, n, default_ids[i], max_norm, lead)
+    results.append((res, tw) if return_trainable else res)
+  return results
