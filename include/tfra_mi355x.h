@@ -558,6 +558,44 @@ typedef struct {
 int tfra_multi_find_combine(tfra_workspace_t* ws, size_t n_tables, const tfra_find_combine_desc* descs,
                             uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
 
+/* The combined write-backs of MANY tables in one call (a 26-table model's backward is 26 tfra_table_apply_planned_combined calls =
+ * ~160 enqueues otherwise): table i ends bit-identical to tfra_table_apply_planned_combined(table, opt, plan, grad_out, seg,
+ * weights, combiner, n_rows, param_default_row, stream) — the same device code runs — and every rule of that call holds per
+ * descriptor (float32 / float16 / bfloat16 rows, dim % 4 == 0, dim <= 256, grad_out / default row 16-B aligned, the rule's slot
+ * fields, plan built over the table's ENTRY ids with the table's dim on the table's device, 1 <= n_rows < 2^30; opt->d_lr is
+ * honoured per descriptor).  A descriptor whose plan holds 0 ids is skipped.  n_tables == 0: TFRA_OK.
+ * All descriptors are checked BEFORE anything is enqueued and before any table is touched: if one fails, the call returns the code
+ * the single call returns for it (the message names the descriptor's index) and no table or slot is changed.  A wrong
+ * struct_size, descs == NULL with n_tables > 0, or a table on another device than ws: TFRA_ERR_INVALID.
+ * A table or a plan may appear in at most ONE descriptor (two descriptors on one table would be two writers of one key inside one
+ * launch): TFRA_ERR_INVALID otherwise, the message names both indices.  (tfra_multi_find_combine allows repeats: it only reads.)
+ * The tables are locked once each, in address order, and ordered behind their last stream once each; then each table's capacity
+ * is prepared as the single call prepares it (a table may grow here; this part stays per table and may enqueue its own small
+ * size reads); the tables' storage is looked at after that, and the epoch strategies count one write-back per table.
+ * Enqueues after that, whatever n_tables: one upload of the descriptors' records (the workspace's ring of pinned, event-guarded
+ * slots, shared with tfra_multi_find_combine: calls may follow each other with no host synchronisation, and the stream is never
+ * waited for once ws has its size), one memset, one bounds launch, one denominator launch and one entry-record launch over all
+ * descriptors, one sums launch per NCH class in the list (NCH = ceil(dim / 64): 1..4), one update launch per (rule, storage
+ * type) class in the list, and one eviction-phase launch per such class that holds a table at max_capacity.  The scratch of all
+ * descriptors (bounds, denominators, entry records) lives in ws; partial sums stay in each plan.
+ * *launches_out (optional, host): the kernel launches enqueued =
+ *   3 + (NCH classes present) + ((rule, storage type) classes present) + ((rule, storage type) classes with a table at max_capacity),
+ * 0 when no descriptor has ids.  26 growing float32 tables of dims 16 / 32 / 64 / 128 with one rule: 3 + 2 + 1 = 6.
+ * The plan builds (tfra_sparse_plan_build) stay per plan.  Not for stream capture. */
+typedef struct {
+  uint32_t struct_size;              /* = sizeof(tfra_apply_combined_desc) */
+  int32_t  combiner;                 /* 0 sum | 1 mean | 2 sqrtn */
+  tfra_table_t* table;
+  const tfra_opt_params* opt;        /* per descriptor; usually the same for all */
+  const tfra_sparse_plan_t* plan;    /* CSR plan built over this table's ENTRY ids (tfra_sparse_plan_build, dim = table dim) */
+  const float* grad_out;             /* [n_rows, dim] float32 */
+  const int64_t* seg; const float* weights;   /* weights may be NULL */
+  size_t n_rows;
+  const float* param_default_row;    /* [dim] float32 */
+} tfra_apply_combined_desc;
+int tfra_multi_apply_planned_combined(tfra_workspace_t* ws, size_t n_tables, const tfra_apply_combined_desc* descs,
+                                      uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
+
 /* default_partition_fn(PY/dynamic_embedding_variable.py:165-197) + dynamic_partition in one
  * pass: owner[i] = mode 0: (key & 0x7fffffff) % num_shards (CUDA-build branch)
  *                  mode 1: floor_mod(key, num_shards)       (CPU-build branch)

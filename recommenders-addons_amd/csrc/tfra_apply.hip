@@ -14,6 +14,7 @@
 #include "tfra_combine_device.h"
 #include "tfra_device.h"
 #include "tfra_host.h"
+#include "tfra_many.h"
 #include "tfra_optim_device.h"
 #include "tfra_plan.h"
 #include "tfra_reduce_device.h"
@@ -42,23 +43,25 @@ __device__ __forceinline__ const CombEnt* comb_ent(const CS&... cs) {
   return p;
 }
 
+// The body is one function with two callers — hot_sums_kernel (one plan per launch) and hot_sums_many_kernel (a list of plans per
+// launch) — so that both compile the same expressions: blk = this block's index among the nblk blocks that work on THIS plan.
 template <int NCH, class... CS>
-__global__ __launch_bounds__(NTA) void hot_sums_kernel(const float* __restrict__ grads, int dim,
-                                                       const unsigned* __restrict__ hent, const unsigned* __restrict__ hout,
-                                                       const unsigned* __restrict__ binmap,
-                                                       const unsigned* __restrict__ d_counts, float* __restrict__ partial,
-                                                       unsigned* progress, unsigned progress_val, const CS... cs) {
+__device__ __forceinline__ void hot_sums_body(const float* __restrict__ grads, int dim,
+                                              const unsigned* __restrict__ hent, const unsigned* __restrict__ hout,
+                                              const unsigned* __restrict__ binmap,
+                                              const unsigned* __restrict__ d_counts, float* __restrict__ partial,
+                                              unsigned* progress, unsigned progress_val, unsigned blk, unsigned nblk, const CS... cs) {
   constexpr bool COMB = sizeof...(CS) > 0;
   constexpr int NG = NTA / 16;
   __shared__ float s_sum[NG][64];
   __shared__ unsigned char s_kind[NG + 1];   // 0 = item continues the run of the item before, 1 = first item of a run, 2 = empty item
   // tfra_table_step_prefetch: host-visible progress counter (pinned memory) — this kernel running means the
   // lookup of step `progress_val` and every earlier step of the main stream are complete
-  if (progress && blockIdx.x == 0 && threadIdx.x == 0)
+  if (progress && blk == 0 && threadIdx.x == 0)
     __hip_atomic_store(progress, progress_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48, g = threadIdx.x >> 4;
   const unsigned nbins = d_counts[3];
-  for (unsigned ib = blockIdx.x; ib < nbins; ib += gridDim.x) {
+  for (unsigned ib = blk; ib < nbins; ib += nblk) {
     const unsigned bin = binmap[ib];
     const unsigned e = hent[(size_t)bin * SEG + threadIdx.x];          // lane `sub` holds entry `sub` of the item
     const unsigned e0 = (unsigned)__shfl((int)e, gshift);
@@ -134,6 +137,15 @@ __global__ __launch_bounds__(NTA) void hot_sums_kernel(const float* __restrict__
   }
 }
 
+template <int NCH, class... CS>
+__global__ __launch_bounds__(NTA) void hot_sums_kernel(const float* __restrict__ grads, int dim,
+                                                       const unsigned* __restrict__ hent, const unsigned* __restrict__ hout,
+                                                       const unsigned* __restrict__ binmap,
+                                                       const unsigned* __restrict__ d_counts, float* __restrict__ partial,
+                                                       unsigned* progress, unsigned progress_val, const CS... cs) {
+  hot_sums_body<NCH>(grads, dim, hent, hout, binmap, d_counts, partial, progress, progress_val, blockIdx.x, gridDim.x, cs...);
+}
+
 // The source rows of a key's sum, NB of them in flight: rows j0 .. j0+NB-1 of its list (clamped to the last one; loads issued
 // together, adds in list order).  A key with few occurrences lists their batch positions in words 4.. of its record (lane i
 // of the group holds word i: EVERY lane of the group must be here); a key with many lists consecutive rows of the partial
@@ -200,24 +212,27 @@ __device__ __forceinline__ float4 sum_rows(const float* __restrict__ grads, cons
 // rounded to the storage type once (to_stored) and written back as one 8-byte write-through store per field.  A new row starts
 // from the FLOAT default row and aux_init values, not from their rounded images (as apply_kernel / apply_evict_kernel do).
 // Gradients and partial sums are fp32 for every ST.  The float instantiations compile the code they always did (if constexpr).
+// The body is one function with two callers — apply_csr_kernel (one table per launch) and apply_csr_many_kernel (a list of tables
+// per launch): blk = this block's index among the nblk blocks that work on THIS table's plan; they stand where the block index and
+// the grid size of the launch stood, and nothing else differs.
 template <int KIND, bool PHASE2, int ST, class... CS>
-__global__ __launch_bounds__(256) void apply_csr_kernel(TableView v, OptP o, int dim, const float* __restrict__ grads,
-                                                        const float* __restrict__ partial, CsrKeys ks,
-                                                        const float* __restrict__ default_row, float aux0, float aux1,
-                                                        ScoreP sp, uint8_t* __restrict__ dflag, unsigned* any_deferred,
-                                                        unsigned use_gen, const CS... cs) {
+__device__ __forceinline__ void apply_csr_body(const TableView& v, OptP o, int dim, const float* __restrict__ grads,
+                                               const float* __restrict__ partial, const CsrKeys& ks,
+                                               const float* __restrict__ default_row, float aux0, float aux1,
+                                               const ScoreP& sp, uint8_t* __restrict__ dflag, unsigned* any_deferred,
+                                               unsigned use_gen, unsigned blk, unsigned nblk, const CS... cs) {
   constexpr bool COMB = sizeof...(CS) > 0;
   if (PHASE2 && *any_deferred != use_gen) return;   // phase 1 of this use deferred nothing
   constexpr int S = NSlots<KIND>::v;
   const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
   const unsigned total = ks.d_counts[0] + ks.d_counts[1];
-  const unsigned ngroups = (gridDim.x * blockDim.x) >> 4;
+  const unsigned ngroups = (nblk * blockDim.x) >> 4;
   int fresh = 0, failed = 0;
   if (o.d_lr) o.lr = *o.d_lr;
-  if (!PHASE2 && blockIdx.x == 0 && threadIdx.x == 0 && ks.d_counts[5]) atomicAdd(v.err_count, ks.d_counts[5]);  // plan overflow
+  if (!PHASE2 && blk == 0 && threadIdx.x == 0 && ks.d_counts[5]) atomicAdd(v.err_count, ks.d_counts[5]);  // plan overflow
   // trips are uniform per wave (the batch width below is a wave-wide maximum): a group past the end re-reads the
   // last key's records and does nothing else
-  for (unsigned wbase = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) << 2; wbase < total; wbase += ngroups) {
+  for (unsigned wbase = ((blk * blockDim.x + threadIdx.x) >> 6) << 2; wbase < total; wbase += ngroups) {
     const unsigned it_raw = wbase + (unsigned)(lane >> 4);
     const bool active = it_raw < total;
     const unsigned g = active ? it_raw : total - 1;
@@ -347,9 +362,65 @@ __global__ __launch_bounds__(256) void apply_csr_kernel(TableView v, OptP o, int
   }
   for (int off = 32; off > 0; off >>= 1) { fresh += __shfl_xor(fresh, off); failed += __shfl_xor(failed, off); }
   if (lane == 0) {
-    if (fresh) size_add(v, (blockIdx.x * blockDim.x + threadIdx.x) >> 6, fresh);
+    if (fresh) size_add(v, (blk * blockDim.x + threadIdx.x) >> 6, fresh);
     if (failed) atomicAdd(v.err_count, (unsigned)failed);
   }
+}
+
+template <int KIND, bool PHASE2, int ST, class... CS>
+__global__ __launch_bounds__(256) void apply_csr_kernel(TableView v, OptP o, int dim, const float* __restrict__ grads,
+                                                        const float* __restrict__ partial, CsrKeys ks,
+                                                        const float* __restrict__ default_row, float aux0, float aux1,
+                                                        ScoreP sp, uint8_t* __restrict__ dflag, unsigned* any_deferred,
+                                                        unsigned use_gen, const CS... cs) {
+  apply_csr_body<KIND, PHASE2, ST>(v, o, dim, grads, partial, ks, default_row, aux0, aux1, sp, dflag, any_deferred, use_gen,
+                                   blockIdx.x, gridDim.x, cs...);
+}
+
+// ---- the grouped form (tfra_multi_apply_planned_combined): the combined write-backs of a LIST of tables, one sums launch per NCH
+// class and one update launch per (rule, storage type) class.  What a single-table launch takes as kernel arguments is a record
+// in device memory here (tfra_pool.hip: 26 tables' records do not fit the 4 KB of kernel arguments).  A class is a list of record
+// indices `idx` and the blocks' prefix sums over it: the grid is the concatenation of the class's descriptors, descriptor j owning
+// the blocks [prefix[j], prefix[j + 1]), and both kernels stride by THAT count.  blockIdx.x is wave-uniform, so the search, the
+// index and the record are scalar loads into scalar registers, as kernel arguments are.
+struct ApplyManyRec {
+  TableView v;
+  OptP o;
+  ScoreP sp;
+  CsrKeys ks;                 // (ks.hent, ks.d_counts: also the sums')
+  const float* grads;         // grad_out
+  float* partial;
+  const float* default_row;
+  const unsigned* hout;
+  const unsigned* binmap;
+  uint8_t* dflag;
+  unsigned* any_deferred;
+  const CombEnt* ent;         // this descriptor's entry records
+  int dim;
+  float aux0, aux1;
+  unsigned use_gen;
+};
+
+template <int NCH>
+__global__ __launch_bounds__(NTA) void hot_sums_many_kernel(const ApplyManyRec* __restrict__ recs, const unsigned* __restrict__ prefix,
+                                                            const unsigned* __restrict__ idx, unsigned n) {
+  const unsigned d = many_desc_of(prefix, n, blockIdx.x);
+  const unsigned first = prefix[d], nblk = prefix[d + 1] - first;
+  const ApplyManyRec rec = recs[idx[d]];
+  hot_sums_body<NCH>(rec.grads, rec.dim, rec.ks.hent, rec.hout, rec.binmap, rec.ks.d_counts, rec.partial, nullptr, 0u, blockIdx.x - first,
+                     nblk, CombRows{rec.ent});
+}
+
+// PHASE2: the class's grid again; the blocks of a table that can still grow have nothing to do (the single call does not launch it)
+template <int KIND, bool PHASE2, int ST>
+__global__ __launch_bounds__(256) void apply_csr_many_kernel(const ApplyManyRec* __restrict__ recs, const unsigned* __restrict__ prefix,
+                                                             const unsigned* __restrict__ idx, unsigned n) {
+  const unsigned d = many_desc_of(prefix, n, blockIdx.x);
+  const unsigned first = prefix[d], nblk = prefix[d + 1] - first;
+  const ApplyManyRec rec = recs[idx[d]];
+  if (PHASE2 && !rec.sp.bounded) return;
+  apply_csr_body<KIND, PHASE2, ST>(rec.v, rec.o, rec.dim, rec.grads, rec.partial, rec.ks, rec.default_row, rec.aux0, rec.aux1, rec.sp,
+                                   rec.dflag, rec.any_deferred, rec.use_gen, blockIdx.x - first, nblk, CombRows{rec.ent});
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -533,6 +604,299 @@ extern "C" int tfra_table_apply_planned_combined(tfra_table_t* tp, const tfra_op
   rc = comb_entries(s, nnz, seg, weights, combiner, n_rows, reinterpret_cast<int*>(b), reinterpret_cast<float*>(b + se_b), ent);
   if (rc) return rc;
   return apply_planned_impl(tp, p, pl, grad_out, param_default_row, stream, nullptr, 0, ent);
+}
+
+// ---------------------------------------------------------------------------------------------
+// tfra_multi_apply_planned_combined: the call above for a LIST of tables, with launches that do not grow with the list.
+namespace {
+
+constexpr unsigned MANY_GRID_CAP = 1024;   // blocks of one grouped launch (see many_cap)
+
+// Blocks a descriptor may own in a class of n_in_class descriptors.  The single call caps the update's grid at 1024 blocks — one
+// resident round of the 125-register kernel, 4 blocks per CU x 256 CUs — and the plans' host-side grids are upper bounds (2048
+// key blocks, up to 1024 bin blocks for a batch whose counts the host has not seen), mostly idle for a small batch.  The cap is
+// shared: 1024 / n blocks each, so that a class of 26 descriptors is ~1014 blocks, not 26 x 1024.  A class of one descriptor has
+// the single call's grid.  Both kernels stride by the descriptor's own block count, so results do not depend on it.
+unsigned many_cap(unsigned blocks, unsigned n_in_class) {
+  return std::max(1u, std::min(blocks, MANY_GRID_CAP / std::max(1u, n_in_class)));
+}
+
+template <int KIND, int ST>
+void launch_apply_many_csr(hipStream_t s, bool phase2, unsigned grid, const ApplyManyRec* recs, const unsigned* prefix, const unsigned* idx,
+                           unsigned n) {
+  if (phase2) apply_csr_many_kernel<KIND, true, ST><<<grid, 256, 0, s>>>(recs, prefix, idx, n);
+  else apply_csr_many_kernel<KIND, false, ST><<<grid, 256, 0, s>>>(recs, prefix, idx, n);
+}
+
+template <int ST>
+void launch_apply_many_st(hipStream_t s, int kind, bool phase2, unsigned grid, const ApplyManyRec* recs, const unsigned* prefix,
+                          const unsigned* idx, unsigned n) {
+  switch (kind) {
+    case TFRA_OPT_SGD: launch_apply_many_csr<TFRA_OPT_SGD, ST>(s, phase2, grid, recs, prefix, idx, n); break;
+    case TFRA_OPT_ADAM: launch_apply_many_csr<TFRA_OPT_ADAM, ST>(s, phase2, grid, recs, prefix, idx, n); break;
+    case TFRA_OPT_ADAGRAD: launch_apply_many_csr<TFRA_OPT_ADAGRAD, ST>(s, phase2, grid, recs, prefix, idx, n); break;
+    default: launch_apply_many_csr<TFRA_OPT_FTRL, ST>(s, phase2, grid, recs, prefix, idx, n); break;
+  }
+}
+
+void launch_apply_many(hipStream_t s, int st, int kind, bool phase2, unsigned grid, const ApplyManyRec* recs, const unsigned* prefix,
+                       const unsigned* idx, unsigned n) {
+  if (st == 1) launch_apply_many_st<TFRA_F16>(s, kind, phase2, grid, recs, prefix, idx, n);
+  else if (st == 2) launch_apply_many_st<TFRA_BF16>(s, kind, phase2, grid, recs, prefix, idx, n);
+  else launch_apply_many_st<TFRA_F32>(s, kind, phase2, grid, recs, prefix, idx, n);
+}
+
+void launch_hot_sums_many(hipStream_t s, int nch, unsigned grid, const ApplyManyRec* recs, const unsigned* prefix, const unsigned* idx,
+                          unsigned n) {
+  switch (nch) {
+    case 1: hot_sums_many_kernel<1><<<grid, NTA, 0, s>>>(recs, prefix, idx, n); break;
+    case 2: hot_sums_many_kernel<2><<<grid, NTA, 0, s>>>(recs, prefix, idx, n); break;
+    case 3: hot_sums_many_kernel<3><<<grid, NTA, 0, s>>>(recs, prefix, idx, n); break;
+    default: hot_sums_many_kernel<4><<<grid, NTA, 0, s>>>(recs, prefix, idx, n); break;
+  }
+}
+
+// the checks of tfra_table_apply_planned_combined and of apply_planned_impl behind it, in their order and with their codes;
+// *active: the descriptor's plan holds ids
+int check_apply_desc(const tfra_apply_combined_desc& d, const tfra_workspace* ws, bool* active, std::string* msg) {
+  *active = false;
+  if (d.struct_size != sizeof(tfra_apply_combined_desc)) { *msg = "descriptor size mismatch"; return TFRA_ERR_INVALID; }
+  const Table* t = reinterpret_cast<const Table*>(d.table);
+  const tfra_sparse_plan* pl = d.plan;
+  if (!t || !d.opt || !pl) { *msg = "null argument"; return TFRA_ERR_INVALID; }
+  if (d.combiner < 0 || d.combiner > 2) { *msg = "combiner must be 0 (sum), 1 (mean) or 2 (sqrtn)"; return TFRA_ERR_INVALID; }
+  if (ws->device != t->device) { *msg = "workspace and table live on different devices"; return TFRA_ERR_INVALID; }
+  if (pl->n == 0) return TFRA_OK;   // skipped (a plan that holds no ids was built for no dim: tfra_sparse_plan_build)
+  if (pl->kind != 0 || pl->dim != t->opts.dim) { *msg = "the plan was built for another dim"; return TFRA_ERR_INVALID; }
+  if (t->opts.device != pl->device && t->opts.device >= 0) { *msg = "plan and table live on different devices"; return TFRA_ERR_INVALID; }
+  if (!d.grad_out || !d.seg || !d.param_default_row) { *msg = "null buffer"; return TFRA_ERR_INVALID; }
+  if (d.n_rows == 0 || d.n_rows >= (1ULL << 30)) { *msg = "need 1 <= n_rows < 2^30"; return TFRA_ERR_INVALID; }
+  if ((((uintptr_t)d.grad_out | (uintptr_t)d.param_default_row) & 15) || ((uintptr_t)d.seg & 7) || ((uintptr_t)d.weights & 3)) {
+    *msg = "grad_out / default buffers must be 16-B aligned";
+    return TFRA_ERR_UNSUPPORTED;
+  }
+  const int dt = t->opts.value_dtype, dim = t->opts.dim;
+  if (dt != TFRA_F32 && dt != TFRA_F16 && dt != TFRA_BF16) {
+    *msg = "value_dtype must be float32, float16 or bfloat16 (gradients and the default row are float32)";
+    return TFRA_ERR_UNSUPPORTED;
+  }
+  if (dim <= 0 || dim % 4 != 0 || dim > 64 * MAXCH) { *msg = "needs dim % 4 == 0 and dim <= 256"; return TFRA_ERR_UNSUPPORTED; }
+  if (d.opt->kind < 0 || d.opt->kind > TFRA_OPT_FTRL) { *msg = "unknown kind"; return TFRA_ERR_INVALID; }
+  const int need = d.opt->kind == TFRA_OPT_SGD ? 0 : (d.opt->kind == TFRA_OPT_ADAGRAD ? 1 : 2);
+  if (t->opts.aux_fields < need) { *msg = "table lacks optimizer slot fields"; return TFRA_ERR_INVALID; }
+  *active = true;
+  return TFRA_OK;
+}
+
+}  // namespace
+
+extern "C" int tfra_multi_apply_planned_combined(tfra_workspace_t* ws, size_t n_tables, const tfra_apply_combined_desc* descs,
+                                                 uint32_t* launches_out, tfra_stream_t stream) {
+  if (launches_out) *launches_out = 0;
+  if (n_tables == 0) return TFRA_OK;
+  if (!ws || !descs) return set_error(TFRA_ERR_INVALID, "multi_apply_planned_combined: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  const std::string who = "multi_apply_planned_combined: descriptor ";
+  // every descriptor is checked before anything is enqueued and before any table is touched
+  std::vector<size_t> act;   // the descriptors with work, in input order: record k belongs to descs[act[k]]
+  for (size_t i = 0; i < n_tables; ++i) {
+    bool active = false;
+    std::string msg;
+    const int rc = check_apply_desc(descs[i], ws, &active, &msg);
+    if (rc) return set_error(rc, who + std::to_string(i) + ": " + msg);
+    if (active) act.push_back(i);
+  }
+  // two descriptors on one table would be two writers of one key inside one launch; a plan's partial sums and flags are one use's
+  for (size_t i = 0; i < n_tables; ++i)
+    for (size_t j = i + 1; j < n_tables; ++j) {
+      if (descs[i].table == descs[j].table)
+        return set_error(TFRA_ERR_INVALID, who + std::to_string(i) + " and descriptor " + std::to_string(j) + " name the same table");
+      if (descs[i].plan == descs[j].plan)
+        return set_error(TFRA_ERR_INVALID, who + std::to_string(i) + " and descriptor " + std::to_string(j) + " name the same plan");
+    }
+  const size_t n_act = act.size();
+  if (n_act == 0) return TFRA_OK;
+
+  // classes: the sums by NCH (1..4), the update by (rule, storage type)
+  constexpr int NHOT = 4, NAPP = 12;
+  std::vector<int> hot_of(n_act), app_of(n_act);
+  unsigned hot_n[NHOT] = {}, app_n[NAPP] = {};
+  u64 ent_blocks = 0, den_blocks = 0;
+  size_t se_ints = 0, den_floats = 0, ent_recs = 0;
+  for (size_t k = 0; k < n_act; ++k) {
+    const tfra_apply_combined_desc& d = descs[act[k]];
+    const Table* t = reinterpret_cast<const Table*>(d.table);
+    const int dt = t->opts.value_dtype;
+    hot_of[k] = (t->opts.dim + 63) / 64 - 1;
+    app_of[k] = d.opt->kind * 3 + (dt == TFRA_F32 ? 0 : dt == TFRA_F16 ? 1 : 2);
+    ++hot_n[hot_of[k]];
+    ++app_n[app_of[k]];
+    ent_blocks += (d.plan->n + 255) / 256;
+    den_blocks += (d.n_rows + 255) / 256;
+    se_ints += (2 * d.n_rows + 63) / 64 * 64;
+    den_floats += (d.n_rows + 63) / 64 * 64;
+    ent_recs += (d.plan->n + 15) / 16 * 16;
+  }
+  if (ent_blocks >= (1ULL << 31) || den_blocks >= (1ULL << 31))
+    return set_error(TFRA_ERR_UNSUPPORTED, "multi_apply_planned_combined: too many rows in one call");
+
+  // each table locked once, in one global order (by address): two threads with overlapping lists cannot deadlock
+  std::vector<Table*> tabs;
+  tabs.reserve(n_act);
+  for (size_t i : act) tabs.push_back(reinterpret_cast<Table*>(descs[i].table));
+  std::sort(tabs.begin(), tabs.end(), std::less<Table*>());
+  std::vector<std::unique_lock<std::mutex>> locks;
+  locks.reserve(tabs.size());
+  for (Table* t : tabs) locks.emplace_back(t->mu);
+  for (Table* t : tabs) {
+    const int rc = t->enter(s);   // (also: the calling thread is on the tables' device from here on)
+    if (rc) return rc;
+  }
+  // capacity, as the single call prepares it: a table may grow here, so the views are taken afterwards
+  std::vector<int> bounded(n_act, 0);
+  for (size_t k = 0; k < n_act; ++k) {
+    Table* t = reinterpret_cast<Table*>(descs[act[k]].table);
+    int rc = t->prepare_insert(descs[act[k]].plan->n, s);
+    if (rc) return rc;
+    uint8_t* bounded_now = nullptr;
+    rc = t->bounded_flags(1, s, &bounded_now);
+    if (rc) return rc;
+    bounded[k] = bounded_now ? (t->dense ? 2 : 1) : 0;
+  }
+
+  // device memory: [bounds of all rows | denominators | entry records | blob], the blob = [update records | bounds records |
+  // entry-kernel records | unsigned pool: entry prefix, row prefix, then per class present its prefix and its record indices]
+  const size_t se_bytes = se_ints * sizeof(int), den_bytes = den_floats * sizeof(float), ent_bytes = ent_recs * sizeof(CombEnt);
+  auto al16 = [](size_t x) { return (x + 15) / 16 * 16; };
+  const size_t arec_off = 0, brec_off = al16(n_act * sizeof(ApplyManyRec));
+  const size_t crec_off = al16(brec_off + n_act * sizeof(BoundsRec));
+  const size_t pool_off = al16(crec_off + n_act * sizeof(CombManyRec));
+  const size_t pool_words = 2 * (n_act + 1) + 2 * (2 * n_act + NHOT + NAPP);
+  const size_t blob_bytes = (pool_off + pool_words * sizeof(unsigned) + 255) / 256 * 256;
+  int rc = ws->ensure(se_bytes + den_bytes + ent_bytes + blob_bytes, s);
+  if (rc) return rc;
+  ManyStage* stage = many_stage_of(ws);
+  unsigned char* h = nullptr;
+  int slot = 0;
+  rc = stage->take(blob_bytes, &h, &slot);
+  if (rc) return rc;
+  unsigned char* base = (unsigned char*)ws->buf;
+  int* se_base = reinterpret_cast<int*>(base);
+  float* den_base = reinterpret_cast<float*>(base + se_bytes);
+  CombEnt* ent_base = reinterpret_cast<CombEnt*>(base + se_bytes + den_bytes);
+  unsigned char* d_blob = base + se_bytes + den_bytes + ent_bytes;
+  ApplyManyRec* arecs = reinterpret_cast<ApplyManyRec*>(h + arec_off);
+  BoundsRec* brecs = reinterpret_cast<BoundsRec*>(h + brec_off);
+  CombManyRec* crecs = reinterpret_cast<CombManyRec*>(h + crec_off);
+  unsigned* pool = reinterpret_cast<unsigned*>(h + pool_off);
+  const unsigned* d_pool = reinterpret_cast<const unsigned*>(d_blob + pool_off);
+
+  std::vector<unsigned> key_blocks(n_act), bin_blocks(n_act);
+  unsigned* ent_pre = pool;
+  unsigned* den_pre = pool + (n_act + 1);
+  {
+    size_t se_at = 0, den_at = 0, ent_at = 0;
+    unsigned eb = 0, db = 0;
+    for (size_t k = 0; k < n_act; ++k) {
+      const tfra_apply_combined_desc& d = descs[act[k]];
+      Table* t = reinterpret_cast<Table*>(d.table);
+      const tfra_sparse_plan* pl = d.plan;
+      const tfra_opt_params* p = d.opt;
+      int* se = se_base + se_at;
+      float* den = den_base + den_at;
+      CombEnt* ent = ent_base + ent_at;
+      se_at += (2 * d.n_rows + 63) / 64 * 64;
+      den_at += (d.n_rows + 63) / 64 * 64;
+      ent_at += (pl->n + 15) / 16 * 16;
+      brecs[k] = BoundsRec{(const i64*)d.seg, se, pl->n, d.n_rows};
+      crecs[k] = CombManyRec{(const i64*)d.seg, d.weights, se, den, ent, pl->n, d.n_rows, d.combiner};
+      ent_pre[k] = eb;
+      den_pre[k] = db;
+      eb += (unsigned)((pl->n + 255) / 256);
+      db += (unsigned)((d.n_rows + 255) / 256);
+      plan_grids(pl, &key_blocks[k], &bin_blocks[k]);
+      key_blocks[k] = many_cap(key_blocks[k], app_n[app_of[k]]);
+      bin_blocks[k] = many_cap(bin_blocks[k], hot_n[hot_of[k]]);
+      ApplyManyRec& r = arecs[k];
+      r.v = t->view_of(t->cur);   // under the lock, after the capacity preparation
+      r.o = OptP{p->kind, p->lr, p->beta1, p->beta2, p->eps, p->l1, p->l2, p->lr_power, p->d_lr};
+      r.sp = ScoreP{t->opts.strategy, t->global_epoch, bounded[k]};
+      r.ks = keys_of(pl);
+      r.grads = d.grad_out;
+      r.partial = pl->partial;
+      r.default_row = d.param_default_row;
+      r.hout = pl->out.hout;
+      r.binmap = pl->binmap;
+      r.dflag = pl->dflag;
+      r.any_deferred = pl->any_deferred;
+      r.ent = ent;
+      r.dim = pl->dim;
+      r.aux0 = t->opts.aux_init[0];
+      r.aux1 = t->opts.aux_init[1];
+      r.use_gen = ++pl->use_gen;   // one use of the plan
+    }
+    ent_pre[n_act] = eb;
+    den_pre[n_act] = db;
+  }
+  // a class = [prefix (n + 1) | idx (n)] in the pool
+  struct Cls { size_t at; unsigned n, grid; bool evict; };
+  Cls hot_cls[NHOT], app_cls[NAPP];
+  size_t at = 2 * (n_act + 1);
+  auto fill = [&](Cls& c, const std::vector<int>& of, int which, const std::vector<unsigned>& blocks) {
+    c = Cls{at, 0, 0, false};
+    for (size_t k = 0; k < n_act; ++k)
+      if (of[k] == which) ++c.n;
+    if (!c.n) return;
+    unsigned* pre = pool + at;
+    unsigned* idx = pre + c.n + 1;
+    unsigned j = 0;
+    for (size_t k = 0; k < n_act; ++k) {
+      if (of[k] != which) continue;
+      pre[j] = c.grid;
+      idx[j++] = (unsigned)k;
+      c.grid += blocks[k];
+      c.evict = c.evict || bounded[k] != 0;
+    }
+    pre[j] = c.grid;
+    at += 2 * c.n + 1;
+  };
+  for (int c = 0; c < NHOT; ++c) fill(hot_cls[c], hot_of, c, bin_blocks);
+  for (int c = 0; c < NAPP; ++c) fill(app_cls[c], app_of, c, key_blocks);
+
+  if (hipMemcpyAsync(d_blob, h, blob_bytes, hipMemcpyHostToDevice, s) != hipSuccess)
+    return set_error(TFRA_ERR_HIP, "multi_apply_planned_combined: record upload");
+  rc = stage->sent(slot, s);
+  if (rc) return rc;
+  if (hipMemsetAsync(se_base, 0, se_bytes, s) != hipSuccess)   // empty rows: start = end = 0
+    return set_error(TFRA_ERR_HIP, "multi_apply_planned_combined: memset");
+  uint32_t launches = 0;
+  rc = comb_bounds_many(s, ent_pre[n_act], reinterpret_cast<const BoundsRec*>(d_blob + brec_off), d_pool, (unsigned)n_act);
+  if (rc) return rc;
+  rc = comb_den_ent_many(s, den_pre[n_act], ent_pre[n_act], reinterpret_cast<const CombManyRec*>(d_blob + crec_off), d_pool + (n_act + 1),
+                         d_pool, (unsigned)n_act);
+  if (rc) return rc;
+  launches += 3;
+  const ApplyManyRec* d_arecs = reinterpret_cast<const ApplyManyRec*>(d_blob + arec_off);
+  for (int c = 0; c < NHOT; ++c) {
+    const Cls& k = hot_cls[c];
+    if (!k.n) continue;
+    launch_hot_sums_many(s, c + 1, k.grid, d_arecs, d_pool + k.at, d_pool + k.at + k.n + 1, k.n);
+    ++launches;
+  }
+  for (int c = 0; c < NAPP; ++c) {
+    const Cls& k = app_cls[c];
+    if (!k.n) continue;
+    launch_apply_many(s, c % 3, c / 3, false, k.grid, d_arecs, d_pool + k.at, d_pool + k.at + k.n + 1, k.n);
+    ++launches;
+    if (k.evict) {   // a table at max_capacity in the class: its eviction phase
+      launch_apply_many(s, c % 3, c / 3, true, k.grid, d_arecs, d_pool + k.at, d_pool + k.at + k.n + 1, k.n);
+      ++launches;
+    }
+  }
+  if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "multi_apply_planned_combined: launch failed");
+  for (size_t i : act) step_epoch_public(reinterpret_cast<Table*>(descs[i].table));
+  if (launches_out) *launches_out = launches;
+  return TFRA_OK;
 }
 
 // tfra_table_apply_sparse for more ids than a plan holds (2^18).  Equal ids must still meet in ONE update, whatever

@@ -67,6 +67,20 @@ __device__ __forceinline__ float4 comb_grad4(float4 g, float den, float w) {
   return make_float4(comb_grad(g.x, den, w), comb_grad(g.y, den, w), comb_grad(g.z, den, w), comb_grad(g.w, den, w));
 }
 
+// The bodies of comb_den_kernel / comb_ent_kernel (tfra_frontend.hip), one function each with two callers: the single-table kernels
+// and the grouped ones (comb_den_many_kernel / comb_ent_many_kernel), which find r / p inside THEIR descriptor
+__device__ __forceinline__ void comb_den_row(size_t r, size_t n_rows, const int* __restrict__ start_end, const float* __restrict__ w,
+                                             int combiner, float* __restrict__ den) {
+  if (r < n_rows) den[r] = comb_den(w, start_end[r], start_end[n_rows + r], combiner);
+}
+__device__ __forceinline__ void comb_ent_one(size_t p, size_t nnz, const i64* __restrict__ seg, const float* __restrict__ w,
+                                             const float* __restrict__ den, size_t n_rows, CombEnt* __restrict__ ent) {
+  if (p >= nnz) return;
+  const i64 s = seg[p];
+  const bool ok = s >= 0 && (size_t)s < n_rows;
+  ent[p] = CombEnt{ok ? (unsigned)s : 0u, ok ? den[s] : 0.f, w ? w[p] : 1.f, 0u};
+}
+
 // The per-entry records of one batch (tfra_frontend.hip): ent[e] = {seg[e], den_{seg[e]}, w_e}; an entry whose row lies outside
 // [0, n_rows) gets {0, 0, w} (gradient 0, as the forward ignores it).  seg ascending; se: scratch of 2 n_rows ints, den: of
 // n_rows floats.  n_rows >= 1.

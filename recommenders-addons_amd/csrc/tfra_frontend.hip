@@ -18,6 +18,7 @@
 #include "tfra_combine_device.h"
 #include "tfra_device.h"
 #include "tfra_host.h"
+#include "tfra_many.h"
 
 using namespace tfra;
 
@@ -518,17 +519,28 @@ __global__ __launch_bounds__(256) void seg_combine_kernel(size_t n_rows, int dim
 // ------------------------------------ combiner backward (tfra_combine_device.h) -----------------
 __global__ void comb_den_kernel(size_t n_rows, const int* __restrict__ start_end, const float* __restrict__ w, int combiner,
                                 float* __restrict__ den) {
-  const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r < n_rows) den[r] = comb_den(w, start_end[r], start_end[n_rows + r], combiner);
+  comb_den_row((size_t)blockIdx.x * blockDim.x + threadIdx.x, n_rows, start_end, w, combiner, den);
 }
 
 __global__ void comb_ent_kernel(size_t nnz, const i64* __restrict__ seg, const float* __restrict__ w, const float* __restrict__ den,
                                 size_t n_rows, CombEnt* __restrict__ ent) {
-  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= nnz) return;
-  const i64 s = seg[p];
-  const bool ok = s >= 0 && (size_t)s < n_rows;
-  ent[p] = CombEnt{ok ? (unsigned)s : 0u, ok ? den[s] : 0.f, w ? w[p] : 1.f, 0u};
+  comb_ent_one((size_t)blockIdx.x * blockDim.x + threadIdx.x, nnz, seg, w, den, n_rows, ent);
+}
+
+// the two over a list (tfra_multi_apply_planned_combined): descriptor d owns ceil(n_rows / 256) blocks of the first and
+// ceil(nnz / 256) blocks of the second, and r / p count ITS rows / entries
+__global__ __launch_bounds__(256) void comb_den_many_kernel(const CombManyRec* __restrict__ recs, const unsigned* __restrict__ prefix,
+                                                            unsigned n) {
+  const unsigned d = many_desc_of(prefix, n, blockIdx.x);
+  const CombManyRec rec = recs[d];
+  comb_den_row((size_t)(blockIdx.x - prefix[d]) * 256 + threadIdx.x, rec.n_rows, rec.se, rec.w, rec.combiner, rec.den);
+}
+
+__global__ __launch_bounds__(256) void comb_ent_many_kernel(const CombManyRec* __restrict__ recs, const unsigned* __restrict__ prefix,
+                                                            unsigned n) {
+  const unsigned d = many_desc_of(prefix, n, blockIdx.x);
+  const CombManyRec rec = recs[d];
+  comb_ent_one((size_t)(blockIdx.x - prefix[d]) * 256 + threadIdx.x, rec.nnz, rec.seg, rec.w, rec.den, rec.n_rows, rec.ent);
 }
 
 // entry_grads[e, :] = comb_grad(grad_out[row_e, :], den_e, w_e); VEC4: one float4 per thread
@@ -956,6 +968,14 @@ int comb_entries(hipStream_t s, size_t nnz, const int64_t* seg, const float* wei
   seg64_bounds_kernel<<<(unsigned)((nnz + 255) / 256), 256, 0, s>>>(nnz, (const i64*)seg, se, n_rows);
   comb_den_kernel<<<(unsigned)((n_rows + 255) / 256), 256, 0, s>>>(n_rows, se, weights, combiner, den);
   comb_ent_kernel<<<(unsigned)((nnz + 255) / 256), 256, 0, s>>>(nnz, (const i64*)seg, weights, den, n_rows, ent);
+  HIP_TRY(hipGetLastError());
+  return TFRA_OK;
+}
+
+int comb_den_ent_many(hipStream_t s, unsigned den_grid, unsigned ent_grid, const CombManyRec* recs, const unsigned* den_prefix,
+                      const unsigned* ent_prefix, unsigned n) {
+  comb_den_many_kernel<<<den_grid, 256, 0, s>>>(recs, den_prefix, n);
+  comb_ent_many_kernel<<<ent_grid, 256, 0, s>>>(recs, ent_prefix, n);
   HIP_TRY(hipGetLastError());
   return TFRA_OK;
 }

@@ -17,6 +17,7 @@
 #include "tfra_combine_device.h"
 #include "tfra_device.h"
 #include "tfra_host.h"
+#include "tfra_many.h"
 
 using namespace tfra;
 
@@ -165,24 +166,7 @@ struct ManyRec {
   int dim;
   int combiner;
 };
-struct BoundsRec {
-  const i64* seg;
-  int* se;
-  size_t nnz;
-  size_t n_rows;
-};
-
-// The descriptor of block `blk`: the d with prefix[d] <= blk < prefix[d + 1] (prefix[0] = 0, prefix[n] = the grid; strictly
-// ascending: no descriptor has zero blocks).  blk is blockIdx.x, so the search, the record's address and the record are
-// wave-uniform: scalar loads into scalar registers, as kernel arguments are.
-__device__ __forceinline__ unsigned many_desc_of(const unsigned* __restrict__ prefix, unsigned n, unsigned blk) {
-  unsigned lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const unsigned mid = (lo + hi) >> 1;
-    if (prefix[mid] <= blk) lo = mid; else hi = mid;
-  }
-  return lo;
-}
+// (BoundsRec, the record of the bounds launch, and many_desc_of, the search that takes a block to its descriptor: tfra_many.h)
 
 template <int DT, int U, int NCH>
 __global__ __launch_bounds__(256) void find_combine_many_kernel(const ManyRec* __restrict__ recs, const unsigned* __restrict__ prefix,
@@ -215,41 +199,7 @@ void launch_find_combine_many(hipStream_t s, int nch, unsigned grid, const ManyR
   else find_combine_many_kernel<DT, U, 4><<<grid, 256, 0, s>>>(recs, prefix, n);
 }
 
-// The records reach the device by ONE asynchronous copy per call from a pinned staging slot.  Two calls may be enqueued back to
-// back with nothing waited for in between, so a slot must not be rewritten while its copy has not run: the slots form a ring,
-// each guarded by an event recorded behind its copy.  Taking a slot waits for ITS event only — in the steady state the copy of
-// RING calls ago, long done — never for the stream.  A list that outgrows the slots waits for the pending copies and reallocates.
-struct ManyStage {
-  static constexpr int RING = 8;
-  unsigned char* host = nullptr;
-  size_t slot_bytes = 0;
-  hipEvent_t ev[RING] = {};
-  bool pending[RING] = {};
-  unsigned next = 0;
-
-  int drain() {
-    for (int i = 0; i < RING; ++i)
-      if (pending[i]) { HIP_TRY(hipEventSynchronize(ev[i])); pending[i] = false; }
-    return TFRA_OK;
-  }
-  int take(size_t need, unsigned char** out, int* slot) {
-    if (!ev[0])
-      for (int i = 0; i < RING; ++i) HIP_TRY(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
-    if (need > slot_bytes) {
-      int rc = drain();
-      if (rc) return rc;
-      if (host) { HIP_TRY(hipHostFree(host)); host = nullptr; slot_bytes = 0; }
-      const size_t want = (std::max<size_t>(need, 8192) + 4095) / 4096 * 4096;
-      HIP_TRY(hipHostMalloc((void**)&host, want * RING, hipHostMallocDefault));
-      slot_bytes = want;
-    }
-    const int i = (int)(next++ % RING);
-    if (pending[i]) { HIP_TRY(hipEventSynchronize(ev[i])); pending[i] = false; }
-    *out = host + (size_t)i * slot_bytes;
-    *slot = i;
-    return TFRA_OK;
-  }
-};
+// (the records reach the device through the workspace's pinned staging ring: ManyStage, tfra_many.h)
 
 // the single call's checks of one descriptor, in its order and with its codes; *active: the descriptor has rows to write
 int check_desc(const tfra_find_combine_desc& d, const tfra_workspace* ws, bool* active, std::string* msg) {
@@ -329,6 +279,12 @@ extern "C" int tfra_table_find_combine(tfra_table_t* tp, tfra_workspace_t* ws, s
 }
 
 namespace tfra {
+int comb_bounds_many(hipStream_t s, unsigned grid, const BoundsRec* recs, const unsigned* prefix, unsigned n) {
+  seg64_bounds_many_kernel<<<grid, 256, 0, s>>>(recs, prefix, n);
+  HIP_TRY(hipGetLastError());
+  return TFRA_OK;
+}
+
 void destroy_workspace_many(void* p) {
   ManyStage* st = reinterpret_cast<ManyStage*>(p);
   if (!st) return;
@@ -404,8 +360,7 @@ extern "C" int tfra_multi_find_combine(tfra_workspace_t* ws, size_t n_tables, co
   const size_t blob_bytes = (bpre_off + (n_bnd + 1) * sizeof(unsigned) + 255) / 256 * 256;
   int rc = ws->ensure(se_bytes + blob_bytes, s);
   if (rc) return rc;
-  if (!ws->many) ws->many = new ManyStage();
-  ManyStage* stage = reinterpret_cast<ManyStage*>(ws->many);
+  ManyStage* stage = many_stage_of(ws);
   unsigned char* h = nullptr;
   int slot = 0;
   rc = stage->take(blob_bytes, &h, &slot);
@@ -464,8 +419,8 @@ extern "C" int tfra_multi_find_combine(tfra_workspace_t* ws, size_t n_tables, co
     bpre[k] = blocks;
   }
   HIP_TRY(hipMemcpyAsync(d_blob, h, blob_bytes, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipEventRecord(stage->ev[slot], s));
-  stage->pending[slot] = true;
+  rc = stage->sent(slot, s);
+  if (rc) return rc;
   HIP_TRY(hipMemsetAsync(se_base, 0, 2 * total_rows * sizeof(int), s));   // empty rows (and every row of an nnz == 0 descriptor): 0, 0
   uint32_t launches = 0;
   if (n_bnd) {

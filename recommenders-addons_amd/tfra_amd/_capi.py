@@ -79,6 +79,15 @@ class FindCombineDesc(ctypes.Structure):
   ]
 
 
+class ApplyCombinedDesc(ctypes.Structure):
+  """tfra_apply_combined_desc (include/tfra_mi355x.h): one table's combined write-back in tfra_multi_apply_planned_combined."""
+  _fields_ = [
+      ("struct_size", ctypes.c_uint32), ("combiner", ctypes.c_int32), ("table", ctypes.c_void_p), ("opt", ctypes.c_void_p),
+      ("plan", ctypes.c_void_p), ("grad_out", ctypes.c_void_p), ("seg", ctypes.c_void_p), ("weights", ctypes.c_void_p),
+      ("n_rows", ctypes.c_size_t), ("param_default_row", ctypes.c_void_p),
+  ]
+
+
 class OverlapStep(ctypes.Structure):
   """tfra_overlap_step (include/tfra_mi355x.h): one step of tfra_table_steps_overlap."""
   _fields_ = [
@@ -160,6 +169,7 @@ _SIGS = {
     "tfra_table_find_unique": [_P, _P, _SZ, _P, _P, _P, _P, _I, _P, _P, _P, _P],
     "tfra_table_find_combine": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, _P, _P],
     "tfra_multi_find_combine": [_P, _SZ, _P, _P, _P],
+    "tfra_multi_apply_planned_combined": [_P, _SZ, _P, _P, _P],
     "tfra_segment_sum": [_P, _SZ, _I, _P, _P, _P, _SZ, _P, _P],
     "tfra_gather_rows": [_SZ, _SZ, _P, _P, _P, _P],
     "tfra_keys_widen_i32": [_SZ, _P, _P, _P],

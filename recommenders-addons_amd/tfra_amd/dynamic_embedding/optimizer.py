@@ -310,6 +310,75 @@ class DynamicEmbeddingOptimizer:
         if pooled:
           _release_plan(var, plan)
 
+  def apply_combined_gradients_many(self, grads_and_vars, name=None):
+    """`apply_combined_gradients` for a many-table model — the wrappers `embedding_lookup_sparse_many(..., return_trainable=True)`
+    returns: one global step for all pairs, and every pair that takes the fused write-back there (one shard, float32 / float16 /
+    bfloat16 rows, a fused rule, a plannable batch) joins the group of its device, which is written back by ONE C call
+    (`table_ops.apply_planned_combined_many`: tfra_multi_apply_planned_combined, whose launch count does not grow with the list).
+    Every other pair takes `apply_combined_gradients`' path for it.  A variable that occurs a second time closes the current
+    groups first, so the order of the write-backs of one variable is the list's.  Tables and slots end bit-identical to
+    `apply_combined_gradients` over the same list."""
+    from .table_ops import SparsePlan, apply_planned_combined_many
+    from .variable import _pool_plan, _release_plan
+    pairs = []
+    for grad_out, tw in grads_and_vars:
+      if not isinstance(tw, SparseTrainableWrapper):
+        raise TypeError("apply_combined_gradients_many expects the SparseTrainableWrapper returned by embedding_lookup_sparse / "
+                        "safe_embedding_lookup_sparse(..., return_trainable=True); use apply_gradients for embedding_lookup")
+      if tw.max_norm is not None:
+        raise ValueError("apply_combined_gradients_many: lookups with max_norm are not supported (the gradient through the clip "
+                         "by norm is not implemented)")
+      pairs.append((tw.check_grad_out(grad_out), tw))
+    p = self.begin_step()
+    groups, seen = {}, set()   # device -> [(var, plan, pooled, request)]; the variables written since the last flush
+
+    def release(members):
+      for var, plan, pooled, _ in members:
+        if pooled:
+          _release_plan(var, plan)
+
+    def flush():
+      seen.clear()
+      while groups:
+        _, members = groups.popitem()
+        try:
+          apply_planned_combined_many([m[3] for m in members], p)
+        finally:
+          release(members)
+
+    try:
+      for g, tw in pairs:
+        var = tw.params
+        self._check(var)
+        if id(var) in seen:
+          flush()
+        seen.add(id(var))
+        n = tw.entry_ids.numel()
+        plan = tw.take_entry_plan()
+        fused = (self.opt.kind is not None and not self.exact_order and not var.bp_v2 and n > 0 and self.can_plan(var, n))
+        if not fused:
+          if plan is not None:
+            _release_plan(var, plan)
+          eg = device_ops.sparse_segment_combine_backprop(g, tw.seg, tw.weights, tw.combiner)
+          self.apply_sparse(var, tw.entry_ids, eg, p)
+          continue
+        pooled = True
+        if plan is None:
+          plan = _pool_plan(var)
+          if plan is None:
+            plan, pooled = SparsePlan(var._primary, var.dim), False
+          plan.build(tw.entry_ids)
+        t = var._tables[0]
+        groups.setdefault(t._device, []).append(
+            (var, plan, pooled, (t._table, plan, g, tw.seg, tw.weights, device_ops.COMBINERS[tw.combiner],
+                                 t._default_value.to(torch.float32))))
+        if getattr(var, "restrict_policy", None) is not None:
+          var.restrict_policy.apply_update(tw.entry_ids)
+      flush()
+    finally:
+      for members in groups.values():   # (only after an exception: their plans go back to their pools)
+        release(members)
+
   def _apply_generic(self, var, ids, grad):
     """The reference's write-back sequence for an arbitrary rule (`Generic`)."""
     ids = torch.as_tensor(ids, device=var._primary).reshape(-1)

@@ -852,3 +852,62 @@ def find_combine_many(requests, return_launches=False):
   _capi.call("tfra_multi_find_combine", _workspace(device), n, ctypes.c_void_p(ctypes.addressof(descs)),
              ctypes.c_void_p(ctypes.addressof(launches)), _stream(device))
   return (outs, int(launches.value)) if return_launches else outs
+
+
+def apply_planned_combined_many(requests, p_list, sync=True):
+  """The combined write-backs of a list of tables in ONE C call (tfra_multi_apply_planned_combined).  `requests`: a list of
+  (table, plan, grad_out, seg, weights, combiner, default_row) — `table` a _DeviceTable (or a CuckooHashTable / HkvHashTable,
+  whose device table is taken), the other arguments those of `_DeviceTable.apply_planned_combined`, handled the same way.
+  `p_list`: the optimizer parameters (`_capi.OptParams`) of each request, or one for all.  All tables live on one device and
+  each table and each plan occurs once.  Every table ends bit-identical to `apply_planned_combined` of its request.  Returns the
+  number of kernel launches the call enqueued — it does not grow with the list."""
+  from .device_ops import _workspace
+  n = len(requests)
+  if n == 0:
+    return 0
+  if isinstance(p_list, _capi.OptParams):
+    p_list = [p_list] * n
+  if len(p_list) != n:
+    raise ValueError("apply_planned_combined_many: %d requests but %d optimizer parameter sets" % (n, len(p_list)))
+  descs = (_capi.ApplyCombinedDesc * n)()
+  keep, plans, device = [], [], None
+  for i, req in enumerate(requests):
+    table, plan, grad_out, seg, weights, combiner, default_row = req
+    table = getattr(table, "_table", table)
+    if device is None:
+      device = table._device
+    elif table._device != device:
+      raise ValueError("apply_planned_combined_many: all tables must live on one device (%s and %s)" % (device, table._device))
+    if plan._dim != table._dim or plan._device != table._device:
+      raise ValueError("the plan was built for dim %d on %s" % (plan._dim, plan._device))
+    grad_out = grad_out.to(table._device, torch.float32).contiguous()
+    if grad_out.dim() != 2 or grad_out.shape[1] != table._dim:
+      raise ValueError("Expected grad_out of shape [n_rows, %d], got %s" % (table._dim, list(grad_out.shape)))
+    seg = seg.to(table._device, torch.int64).contiguous()
+    if seg.numel() != plan.n or (weights is not None and weights.numel() != plan.n):
+      raise ValueError("seg / weights need one element per plan entry (%d)" % plan.n)
+    w = None if weights is None else weights.to(table._device, torch.float32).contiguous()
+    d = default_row.to(table._device, torch.float32).contiguous()
+    keep.append((grad_out, seg, w, d, p_list[i]))
+    plans.append(plan)
+    e = descs[i]
+    e.struct_size = ctypes.sizeof(_capi.ApplyCombinedDesc)
+    e.combiner = int(combiner)
+    e.table = table._h.value
+    e.opt = ctypes.addressof(p_list[i])
+    e.plan = plan._h.value
+    e.grad_out, e.seg, e.weights = grad_out.data_ptr(), seg.data_ptr(), (w.data_ptr() if w is not None else None)
+    e.n_rows, e.param_default_row = grad_out.shape[0], d.data_ptr()
+  stream = torch.cuda.current_stream(device)
+  if sync:
+    for plan in plans:
+      stream.wait_event(plan._built)
+  launches = ctypes.c_uint32(0)
+  _capi.call("tfra_multi_apply_planned_combined", _workspace(device), n, ctypes.c_void_p(ctypes.addressof(descs)),
+             ctypes.c_void_p(ctypes.addressof(launches)), _stream(device))
+  if sync:
+    for plan in plans:
+      if plan._used is None:
+        plan._used = torch.cuda.Event()
+      plan._used.record(stream)
+  return int(launches.value)
