@@ -1,6 +1,9 @@
 // GRADIENT HALF of a write-back whose ids may repeat (tfra_table_apply_planned, over a CSR plan of tfra_csr.hip): the hot sums,
 // then one fused optimizer update per unique key; the same sums written out instead (tfra_reduce_by_key, tfra_plan_reduce_to);
 // the one-call and the two-stream forms (tfra_table_apply_sparse, tfra_table_step_prefetch[_assign]).
+// The grouped combined write-back (tfra_multi_apply_planned_combined) stands on the grouped-call frame of tfra_many.h.  A write-back's
+// argument checks exist once, check_apply_planned and check_apply_combined, for every entry point that makes them; the launch
+// ladders are the dispatchers of tfra_host.h (with_opt_kind, with_stored) and with_nch, for single and grouped launches.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -8,6 +11,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/tfra_mi355x.h"
@@ -468,9 +472,31 @@ __global__ __launch_bounds__(256) void gather_csr_kernel(int dim, const float* _
 
 }  // namespace
 
-template <int KIND, int ST, class... CS>
-static void launch_apply_csr(Table* t, hipStream_t s, const tfra_sparse_plan* pl, const OptP& o, const float* grads,
-                             const float* default_row, unsigned key_blocks, const ScoreP& sp, const CS&... cs) {
+// NCH of the sums, the row's chunks of 64 floats: f(std::integral_constant<int, NCH>{}) for nch in 1..4
+template <class F>
+static void with_nch(int nch, F&& f) {
+  switch (nch) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+  }
+}
+
+template <class... CS>
+static void launch_hot_sums(hipStream_t s, const tfra_sparse_plan* pl, const float* grads, unsigned bin_blocks, unsigned* progress,
+                            unsigned progress_val, const CS&... cs) {
+  const int dim = pl->dim;
+  with_nch((dim + 63) / 64, [&](auto NCH) {
+    hot_sums_kernel<NCH><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, progress,
+                                                    progress_val, cs...);
+  });
+}
+
+// by the rule and by the rows' storage type (both checked by the caller)
+template <class... CS>
+static void launch_apply(Table* t, hipStream_t s, const tfra_sparse_plan* pl, int kind, const OptP& o, const float* grads,
+                         const float* default_row, unsigned key_blocks, const ScoreP& sp, const CS&... cs) {
   TableView v = t->view_of(t->cur);
   const float a0 = t->opts.aux_init[0], a1 = t->opts.aux_init[1];
   const unsigned gen = ++pl->use_gen;
@@ -478,45 +504,36 @@ static void launch_apply_csr(Table* t, hipStream_t s, const tfra_sparse_plan* pl
   // rounds of dispatch plus a third of 27 blocks; 1024 blocks looping twice: configs[1] 55.2 -> 53.7 us per step (A/B on one box, twice)
   static const unsigned grid_cap = [] { const char* e = getenv("TFRA_APPLY_GRID_CAP"); return e ? (unsigned)atoi(e) : 1024u; }();
   if (grid_cap) key_blocks = std::min(key_blocks, grid_cap);
-  apply_csr_kernel<KIND, false, ST><<<key_blocks, 256, 0, s>>>(v, o, pl->dim, grads, pl->partial, keys_of(pl), default_row, a0, a1, sp,
-                                                           pl->dflag, pl->any_deferred, gen, cs...);
-  if (sp.bounded)
-    apply_csr_kernel<KIND, true, ST><<<key_blocks, 256, 0, s>>>(v, o, pl->dim, grads, pl->partial, keys_of(pl), default_row, a0, a1, sp,
-                                                            pl->dflag, pl->any_deferred, gen, cs...);
+  with_opt_kind(kind, [&](auto KIND) {
+    with_stored(st_index(t->opts.value_dtype), [&](auto ST) {
+      apply_csr_kernel<KIND, false, ST><<<key_blocks, 256, 0, s>>>(v, o, pl->dim, grads, pl->partial, keys_of(pl), default_row, a0, a1, sp,
+                                                                   pl->dflag, pl->any_deferred, gen, cs...);
+      if (sp.bounded)
+        apply_csr_kernel<KIND, true, ST><<<key_blocks, 256, 0, s>>>(v, o, pl->dim, grads, pl->partial, keys_of(pl), default_row, a0, a1, sp,
+                                                                    pl->dflag, pl->any_deferred, gen, cs...);
+    });
+  });
 }
 
-template <class... CS>
-static void launch_hot_sums(hipStream_t s, const tfra_sparse_plan* pl, const float* grads, unsigned bin_blocks, unsigned* progress,
-                            unsigned progress_val, const CS&... cs) {
-  const int dim = pl->dim;
-  switch ((dim + 63) / 64) {
-    case 1: hot_sums_kernel<1><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, progress, progress_val, cs...); break;
-    case 2: hot_sums_kernel<2><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, progress, progress_val, cs...); break;
-    case 3: hot_sums_kernel<3><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, progress, progress_val, cs...); break;
-    default: hot_sums_kernel<4><<<bin_blocks, NTA, 0, s>>>(grads, dim, pl->out.hent, pl->out.hout, pl->binmap, pl->d_counts, pl->partial, progress, progress_val, cs...); break;
-  }
-}
-
-template <int ST, class... CS>
-static void launch_apply_st(Table* t, hipStream_t s, const tfra_sparse_plan* pl, int kind, const OptP& o, const float* grads,
-                            const float* default_row, unsigned key_blocks, const ScoreP& sp, const CS&... cs) {
-  switch (kind) {
-    case TFRA_OPT_SGD: launch_apply_csr<TFRA_OPT_SGD, ST>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
-    case TFRA_OPT_ADAM: launch_apply_csr<TFRA_OPT_ADAM, ST>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
-    case TFRA_OPT_ADAGRAD: launch_apply_csr<TFRA_OPT_ADAGRAD, ST>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
-    default: launch_apply_csr<TFRA_OPT_FTRL, ST>(t, s, pl, o, grads, default_row, key_blocks, sp, cs...); break;
-  }
-}
-
-// by the rows' storage type (checked by the caller: F32, F16 or BF16)
-template <class... CS>
-static void launch_apply(Table* t, hipStream_t s, const tfra_sparse_plan* pl, int kind, const OptP& o, const float* grads,
-                         const float* default_row, unsigned key_blocks, const ScoreP& sp, const CS&... cs) {
-  switch (t->opts.value_dtype) {
-    case TFRA_F16: launch_apply_st<TFRA_F16>(t, s, pl, kind, o, grads, default_row, key_blocks, sp, cs...); break;
-    case TFRA_BF16: launch_apply_st<TFRA_BF16>(t, s, pl, kind, o, grads, default_row, key_blocks, sp, cs...); break;
-    default: launch_apply_st<TFRA_F32>(t, s, pl, kind, o, grads, default_row, key_blocks, sp, cs...); break;
-  }
+// The checks of a planned write-back: apply_planned_impl's, whoever calls it, and behind check_apply_combined those of a
+// descriptor of tfra_multi_apply_planned_combined.  active: the plan holds ids.
+template <class AtEntry>
+static Check check_apply_planned(const Table* t, const tfra_opt_params* p, const tfra_sparse_plan* pl, const float* grads,
+                                 const float* param_default_row, AtEntry&& at_entry) {
+  if (!t || !p || !pl) return refuse(TFRA_ERR_INVALID, "null argument");
+  if (Check e = at_entry(); e.done()) return e;
+  if (pl->n == 0) return nothing_to_do();
+  if (!grads || !param_default_row) return refuse(TFRA_ERR_INVALID, "null buffer");
+  const int dt = t->opts.value_dtype;
+  if (dt != TFRA_F32 && dt != TFRA_F16 && dt != TFRA_BF16)
+    return refuse(TFRA_ERR_UNSUPPORTED, "value_dtype must be float32, float16 or bfloat16 (gradients and the default row are float32)");
+  if (p->kind < 0 || p->kind > TFRA_OPT_FTRL) return refuse(TFRA_ERR_INVALID, "unknown kind");
+  const int need = p->kind == TFRA_OPT_SGD ? 0 : (p->kind == TFRA_OPT_ADAGRAD ? 1 : 2);
+  if (t->opts.aux_fields < need) return refuse(TFRA_ERR_INVALID, "table lacks optimizer slot fields");
+  if (t->opts.dim != pl->dim) return refuse(TFRA_ERR_INVALID, "the plan was built for another dim");
+  if (t->opts.device != pl->device && t->opts.device >= 0) return refuse(TFRA_ERR_INVALID, "plan and table live on different devices");
+  if ((((uintptr_t)grads | (uintptr_t)param_default_row) & 15)) return refuse(TFRA_ERR_UNSUPPORTED, "gradient / default buffers must be 16-B aligned");
+  return Check{};
 }
 
 // comb != nullptr (tfra_table_apply_planned_combined): grads is grad_out, position e's gradient is formed from comb[e]
@@ -525,23 +542,11 @@ int tfra::apply_planned_impl(tfra_table_t* tp, const tfra_opt_params* p, const t
                              const CombEnt* comb) {
   // caller holds t->mu
   Table* t = reinterpret_cast<Table*>(tp);
-  if (!t || !p || !pl) return set_error(TFRA_ERR_INVALID, "apply_planned: null argument");
   hipStream_t s = (hipStream_t)stream;
-  int rc = t->enter(s);
-  if (rc) return rc;
-  if (pl->n == 0) return TFRA_OK;
-  if (!grads || !param_default_row) return set_error(TFRA_ERR_INVALID, "apply_planned: null buffer");
-  const int dt = t->opts.value_dtype;
-  if (dt != TFRA_F32 && dt != TFRA_F16 && dt != TFRA_BF16)
-    return set_error(TFRA_ERR_UNSUPPORTED, "apply_planned: value_dtype must be float32, float16 or bfloat16 (gradients and the default row are float32)");
-  if (p->kind < 0 || p->kind > TFRA_OPT_FTRL) return set_error(TFRA_ERR_INVALID, "apply_planned: unknown kind");
-  int need = p->kind == TFRA_OPT_SGD ? 0 : (p->kind == TFRA_OPT_ADAGRAD ? 1 : 2);
-  if (t->opts.aux_fields < need) return set_error(TFRA_ERR_INVALID, "apply_planned: table lacks optimizer slot fields");
-  if (t->opts.dim != pl->dim) return set_error(TFRA_ERR_INVALID, "apply_planned: the plan was built for another dim");
-  if (t->opts.device != pl->device && t->opts.device >= 0) return set_error(TFRA_ERR_INVALID, "apply_planned: plan and table live on different devices");
-  if ((((uintptr_t)grads | (uintptr_t)param_default_row) & 15))
-    return set_error(TFRA_ERR_UNSUPPORTED, "apply_planned: gradient / default buffers must be 16-B aligned");
-  rc = t->prepare_insert(pl->n, s);
+  const Check c = check_apply_planned(t, p, pl, grads, param_default_row, [&] { return Check{t->enter(s)}; });
+  if (c.code) return report("apply_planned: ", c);
+  if (!c.active) return TFRA_OK;
+  int rc = t->prepare_insert(pl->n, s);
   if (rc) return rc;
   unsigned key_blocks, bin_blocks;
   plan_grids(pl, &key_blocks, &bin_blocks);
@@ -567,6 +572,25 @@ extern "C" int tfra_table_apply_planned(tfra_table_t* tp, const tfra_opt_params*
   return apply_planned_impl(tp, p, pl, grads, param_default_row, stream, nullptr, 0);
 }
 
+// The checks tfra_table_apply_planned_combined makes before it forms the entry records (apply_planned_impl's follow behind them),
+// also the first half of a descriptor's.  active: the plan holds ids.
+template <class AtEntry>
+static Check check_apply_combined(const Table* t, const tfra_opt_params* p, const tfra_sparse_plan* pl, const float* grad_out,
+                                  const int64_t* seg, const float* weights, int combiner, size_t n_rows, const float* param_default_row,
+                                  AtEntry&& at_entry) {
+  if (!t || !p || !pl) return refuse(TFRA_ERR_INVALID, "null argument");
+  if (combiner < 0 || combiner > 2) return refuse(TFRA_ERR_INVALID, "combiner must be 0 (sum), 1 (mean) or 2 (sqrtn)");
+  if (Check e = at_entry(); e.done()) return e;
+  if (pl->kind != 0 || pl->dim != t->opts.dim) return refuse(TFRA_ERR_INVALID, "the plan was built for another dim");
+  if (t->opts.device != pl->device && t->opts.device >= 0) return refuse(TFRA_ERR_INVALID, "plan and table live on different devices");
+  if (pl->n == 0) return nothing_to_do();
+  if (!grad_out || !seg || !param_default_row) return refuse(TFRA_ERR_INVALID, "null buffer");
+  if (n_rows == 0 || n_rows >= (1ULL << 30)) return refuse(TFRA_ERR_INVALID, "need 1 <= n_rows < 2^30");
+  if ((((uintptr_t)grad_out | (uintptr_t)param_default_row) & 15) || ((uintptr_t)seg & 7) || ((uintptr_t)weights & 3))
+    return refuse(TFRA_ERR_UNSUPPORTED, "grad_out / default buffers must be 16-B aligned");
+  return Check{};
+}
+
 // The write-back of an embedding_lookup_sparse: plan over the entry ids, gradient of position e = the combiner's backward
 // (tfra_combine_device.h) formed from grad_out in registers — apply_planned's kernels, reading grad_out through one more
 // indirection instead of an expanded [nnz, dim] gradient.
@@ -574,20 +598,16 @@ extern "C" int tfra_table_apply_planned_combined(tfra_table_t* tp, const tfra_op
                                                  const float* grad_out, const int64_t* seg, const float* weights, int combiner,
                                                  size_t n_rows, const float* param_default_row, tfra_stream_t stream) {
   Table* t = reinterpret_cast<Table*>(tp);
-  if (!t || !p || !pl) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: null argument");
-  if (combiner < 0 || combiner > 2) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: combiner must be 0 (sum), 1 (mean) or 2 (sqrtn)");
-  std::lock_guard<std::mutex> lock(t->mu);
   hipStream_t s = (hipStream_t)stream;
-  int rc = t->enter(s);   // the scratch below was last used on the table's previous stream
-  if (rc) return rc;
-  if (pl->kind != 0 || pl->dim != t->opts.dim) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: the plan was built for another dim");
-  if (t->opts.device != pl->device && t->opts.device >= 0) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: plan and table live on different devices");
+  std::unique_lock<std::mutex> lock;
+  const Check c = check_apply_combined(t, p, pl, grad_out, seg, weights, combiner, n_rows, param_default_row, [&] {
+    lock = std::unique_lock<std::mutex>(t->mu);
+    return Check{t->enter(s)};   // the scratch below was last used on the table's previous stream
+  });
+  if (c.code) return report("apply_planned_combined: ", c);
+  if (!c.active) return TFRA_OK;
   const size_t nnz = pl->n;
-  if (nnz == 0) return TFRA_OK;
-  if (!grad_out || !seg || !param_default_row) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: null buffer");
-  if (n_rows == 0 || n_rows >= (1ULL << 30)) return set_error(TFRA_ERR_INVALID, "apply_planned_combined: need 1 <= n_rows < 2^30");
-  if ((((uintptr_t)grad_out | (uintptr_t)param_default_row) & 15) || ((uintptr_t)seg & 7) || ((uintptr_t)weights & 3))
-    return set_error(TFRA_ERR_UNSUPPORTED, "apply_planned_combined: grad_out / default buffers must be 16-B aligned");
+  int rc;
   if (!t->comb_ws) {
     tfra_workspace_t* w = nullptr;
     rc = tfra_workspace_create(t->device, &w);
@@ -621,71 +641,37 @@ unsigned many_cap(unsigned blocks, unsigned n_in_class) {
   return std::max(1u, std::min(blocks, MANY_GRID_CAP / std::max(1u, n_in_class)));
 }
 
-template <int KIND, int ST>
-void launch_apply_many_csr(hipStream_t s, bool phase2, unsigned grid, const ApplyManyRec* recs, const unsigned* prefix, const unsigned* idx,
-                           unsigned n) {
-  if (phase2) apply_csr_many_kernel<KIND, true, ST><<<grid, 256, 0, s>>>(recs, prefix, idx, n);
-  else apply_csr_many_kernel<KIND, false, ST><<<grid, 256, 0, s>>>(recs, prefix, idx, n);
-}
-
-template <int ST>
-void launch_apply_many_st(hipStream_t s, int kind, bool phase2, unsigned grid, const ApplyManyRec* recs, const unsigned* prefix,
-                          const unsigned* idx, unsigned n) {
-  switch (kind) {
-    case TFRA_OPT_SGD: launch_apply_many_csr<TFRA_OPT_SGD, ST>(s, phase2, grid, recs, prefix, idx, n); break;
-    case TFRA_OPT_ADAM: launch_apply_many_csr<TFRA_OPT_ADAM, ST>(s, phase2, grid, recs, prefix, idx, n); break;
-    case TFRA_OPT_ADAGRAD: launch_apply_many_csr<TFRA_OPT_ADAGRAD, ST>(s, phase2, grid, recs, prefix, idx, n); break;
-    default: launch_apply_many_csr<TFRA_OPT_FTRL, ST>(s, phase2, grid, recs, prefix, idx, n); break;
-  }
-}
-
 void launch_apply_many(hipStream_t s, int st, int kind, bool phase2, unsigned grid, const ApplyManyRec* recs, const unsigned* prefix,
                        const unsigned* idx, unsigned n) {
-  if (st == 1) launch_apply_many_st<TFRA_F16>(s, kind, phase2, grid, recs, prefix, idx, n);
-  else if (st == 2) launch_apply_many_st<TFRA_BF16>(s, kind, phase2, grid, recs, prefix, idx, n);
-  else launch_apply_many_st<TFRA_F32>(s, kind, phase2, grid, recs, prefix, idx, n);
+  with_opt_kind(kind, [&](auto KIND) {
+    with_stored(st, [&](auto ST) {
+      if (phase2) apply_csr_many_kernel<KIND, true, ST><<<grid, 256, 0, s>>>(recs, prefix, idx, n);
+      else apply_csr_many_kernel<KIND, false, ST><<<grid, 256, 0, s>>>(recs, prefix, idx, n);
+    });
+  });
 }
 
 void launch_hot_sums_many(hipStream_t s, int nch, unsigned grid, const ApplyManyRec* recs, const unsigned* prefix, const unsigned* idx,
                           unsigned n) {
-  switch (nch) {
-    case 1: hot_sums_many_kernel<1><<<grid, NTA, 0, s>>>(recs, prefix, idx, n); break;
-    case 2: hot_sums_many_kernel<2><<<grid, NTA, 0, s>>>(recs, prefix, idx, n); break;
-    case 3: hot_sums_many_kernel<3><<<grid, NTA, 0, s>>>(recs, prefix, idx, n); break;
-    default: hot_sums_many_kernel<4><<<grid, NTA, 0, s>>>(recs, prefix, idx, n); break;
-  }
+  with_nch(nch, [&](auto NCH) { hot_sums_many_kernel<NCH><<<grid, NTA, 0, s>>>(recs, prefix, idx, n); });
 }
 
-// the checks of tfra_table_apply_planned_combined and of apply_planned_impl behind it, in their order and with their codes;
-// *active: the descriptor's plan holds ids
-int check_apply_desc(const tfra_apply_combined_desc& d, const tfra_workspace* ws, bool* active, std::string* msg) {
-  *active = false;
-  if (d.struct_size != sizeof(tfra_apply_combined_desc)) { *msg = "descriptor size mismatch"; return TFRA_ERR_INVALID; }
+// A descriptor's checks: the single call's (check_apply_combined, then check_apply_planned), with what only a descriptor can get
+// wrong where the single call enters its table.  A plan that holds no ids is skipped there: it was built for no dim
+// (tfra_sparse_plan_build), and the single call is not made with one.
+Check check_apply_desc(const tfra_apply_combined_desc& d, const tfra_workspace* ws) {
+  if (d.struct_size != sizeof(tfra_apply_combined_desc)) return refuse(TFRA_ERR_INVALID, "descriptor size mismatch");
   const Table* t = reinterpret_cast<const Table*>(d.table);
-  const tfra_sparse_plan* pl = d.plan;
-  if (!t || !d.opt || !pl) { *msg = "null argument"; return TFRA_ERR_INVALID; }
-  if (d.combiner < 0 || d.combiner > 2) { *msg = "combiner must be 0 (sum), 1 (mean) or 2 (sqrtn)"; return TFRA_ERR_INVALID; }
-  if (ws->device != t->device) { *msg = "workspace and table live on different devices"; return TFRA_ERR_INVALID; }
-  if (pl->n == 0) return TFRA_OK;   // skipped (a plan that holds no ids was built for no dim: tfra_sparse_plan_build)
-  if (pl->kind != 0 || pl->dim != t->opts.dim) { *msg = "the plan was built for another dim"; return TFRA_ERR_INVALID; }
-  if (t->opts.device != pl->device && t->opts.device >= 0) { *msg = "plan and table live on different devices"; return TFRA_ERR_INVALID; }
-  if (!d.grad_out || !d.seg || !d.param_default_row) { *msg = "null buffer"; return TFRA_ERR_INVALID; }
-  if (d.n_rows == 0 || d.n_rows >= (1ULL << 30)) { *msg = "need 1 <= n_rows < 2^30"; return TFRA_ERR_INVALID; }
-  if ((((uintptr_t)d.grad_out | (uintptr_t)d.param_default_row) & 15) || ((uintptr_t)d.seg & 7) || ((uintptr_t)d.weights & 3)) {
-    *msg = "grad_out / default buffers must be 16-B aligned";
-    return TFRA_ERR_UNSUPPORTED;
-  }
-  const int dt = t->opts.value_dtype, dim = t->opts.dim;
-  if (dt != TFRA_F32 && dt != TFRA_F16 && dt != TFRA_BF16) {
-    *msg = "value_dtype must be float32, float16 or bfloat16 (gradients and the default row are float32)";
-    return TFRA_ERR_UNSUPPORTED;
-  }
-  if (dim <= 0 || dim % 4 != 0 || dim > 64 * MAXCH) { *msg = "needs dim % 4 == 0 and dim <= 256"; return TFRA_ERR_UNSUPPORTED; }
-  if (d.opt->kind < 0 || d.opt->kind > TFRA_OPT_FTRL) { *msg = "unknown kind"; return TFRA_ERR_INVALID; }
-  const int need = d.opt->kind == TFRA_OPT_SGD ? 0 : (d.opt->kind == TFRA_OPT_ADAGRAD ? 1 : 2);
-  if (t->opts.aux_fields < need) { *msg = "table lacks optimizer slot fields"; return TFRA_ERR_INVALID; }
-  *active = true;
-  return TFRA_OK;
+  Check c = check_apply_combined(t, d.opt, d.plan, d.grad_out, d.seg, d.weights, d.combiner, d.n_rows, d.param_default_row, [&] {
+    if (ws->device != t->device) return refuse(TFRA_ERR_INVALID, "workspace and table live on different devices");
+    return d.plan->n == 0 ? nothing_to_do() : Check{};
+  });
+  if (c.done()) return c;
+  c = check_apply_planned(t, d.opt, d.plan, d.grad_out, d.param_default_row, [] { return Check{}; });
+  if (c.done()) return c;
+  const int dim = t->opts.dim;   // (hot_sums' classes: NCH 1..4)
+  if (dim <= 0 || dim % 4 != 0 || dim > 64 * MAXCH) return refuse(TFRA_ERR_UNSUPPORTED, "needs dim % 4 == 0 and dim <= 256");
+  return Check{};
 }
 
 }  // namespace
@@ -700,11 +686,9 @@ extern "C" int tfra_multi_apply_planned_combined(tfra_workspace_t* ws, size_t n_
   // every descriptor is checked before anything is enqueued and before any table is touched
   std::vector<size_t> act;   // the descriptors with work, in input order: record k belongs to descs[act[k]]
   for (size_t i = 0; i < n_tables; ++i) {
-    bool active = false;
-    std::string msg;
-    const int rc = check_apply_desc(descs[i], ws, &active, &msg);
-    if (rc) return set_error(rc, who + std::to_string(i) + ": " + msg);
-    if (active) act.push_back(i);
+    const Check c = check_apply_desc(descs[i], ws);
+    if (c.code) return report(who + std::to_string(i) + ": ", c);
+    if (c.active) act.push_back(i);
   }
   // two descriptors on one table would be two writers of one key inside one launch; a plan's partial sums and flags are one use's
   for (size_t i = 0; i < n_tables; ++i)
@@ -719,6 +703,8 @@ extern "C" int tfra_multi_apply_planned_combined(tfra_workspace_t* ws, size_t n_
 
   // classes: the sums by NCH (1..4), the update by (rule, storage type)
   constexpr int NHOT = 4, NAPP = 12;
+  auto ent_blocks_of = [&](size_t k) { return (unsigned)((descs[act[k]].plan->n + 255) / 256); };
+  auto den_blocks_of = [&](size_t k) { return (unsigned)((descs[act[k]].n_rows + 255) / 256); };
   std::vector<int> hot_of(n_act), app_of(n_act);
   unsigned hot_n[NHOT] = {}, app_n[NAPP] = {};
   u64 ent_blocks = 0, den_blocks = 0;
@@ -726,13 +712,12 @@ extern "C" int tfra_multi_apply_planned_combined(tfra_workspace_t* ws, size_t n_
   for (size_t k = 0; k < n_act; ++k) {
     const tfra_apply_combined_desc& d = descs[act[k]];
     const Table* t = reinterpret_cast<const Table*>(d.table);
-    const int dt = t->opts.value_dtype;
     hot_of[k] = (t->opts.dim + 63) / 64 - 1;
-    app_of[k] = d.opt->kind * 3 + (dt == TFRA_F32 ? 0 : dt == TFRA_F16 ? 1 : 2);
+    app_of[k] = d.opt->kind * 3 + st_index(t->opts.value_dtype);
     ++hot_n[hot_of[k]];
     ++app_n[app_of[k]];
-    ent_blocks += (d.plan->n + 255) / 256;
-    den_blocks += (d.n_rows + 255) / 256;
+    ent_blocks += ent_blocks_of(k);
+    den_blocks += den_blocks_of(k);
     se_ints += (2 * d.n_rows + 63) / 64 * 64;
     den_floats += (d.n_rows + 63) / 64 * 64;
     ent_recs += (d.plan->n + 15) / 16 * 16;
@@ -740,63 +725,47 @@ extern "C" int tfra_multi_apply_planned_combined(tfra_workspace_t* ws, size_t n_
   if (ent_blocks >= (1ULL << 31) || den_blocks >= (1ULL << 31))
     return set_error(TFRA_ERR_UNSUPPORTED, "multi_apply_planned_combined: too many rows in one call");
 
-  // each table locked once, in one global order (by address): two threads with overlapping lists cannot deadlock
   std::vector<Table*> tabs;
   tabs.reserve(n_act);
   for (size_t i : act) tabs.push_back(reinterpret_cast<Table*>(descs[i].table));
-  std::sort(tabs.begin(), tabs.end(), std::less<Table*>());
   std::vector<std::unique_lock<std::mutex>> locks;
-  locks.reserve(tabs.size());
-  for (Table* t : tabs) locks.emplace_back(t->mu);
-  for (Table* t : tabs) {
-    const int rc = t->enter(s);   // (also: the calling thread is on the tables' device from here on)
-    if (rc) return rc;
-  }
+  int rc = lock_and_enter(std::move(tabs), s, &locks);
+  if (rc) return rc;
   // capacity, as the single call prepares it: a table may grow here, so the views are taken afterwards
   std::vector<int> bounded(n_act, 0);
+  bool app_evict[NAPP] = {};   // a table at max_capacity in the class: the class runs its eviction phase
   for (size_t k = 0; k < n_act; ++k) {
     Table* t = reinterpret_cast<Table*>(descs[act[k]].table);
-    int rc = t->prepare_insert(descs[act[k]].plan->n, s);
+    rc = t->prepare_insert(descs[act[k]].plan->n, s);
     if (rc) return rc;
     uint8_t* bounded_now = nullptr;
     rc = t->bounded_flags(1, s, &bounded_now);
     if (rc) return rc;
     bounded[k] = bounded_now ? (t->dense ? 2 : 1) : 0;
+    app_evict[app_of[k]] = app_evict[app_of[k]] || bounded[k] != 0;
   }
 
   // device memory: [bounds of all rows | denominators | entry records | blob], the blob = [update records | bounds records |
   // entry-kernel records | unsigned pool: entry prefix, row prefix, then per class present its prefix and its record indices]
   const size_t se_bytes = se_ints * sizeof(int), den_bytes = den_floats * sizeof(float), ent_bytes = ent_recs * sizeof(CombEnt);
-  auto al16 = [](size_t x) { return (x + 15) / 16 * 16; };
-  const size_t arec_off = 0, brec_off = al16(n_act * sizeof(ApplyManyRec));
-  const size_t crec_off = al16(brec_off + n_act * sizeof(BoundsRec));
-  const size_t pool_off = al16(crec_off + n_act * sizeof(CombManyRec));
-  const size_t pool_words = 2 * (n_act + 1) + 2 * (2 * n_act + NHOT + NAPP);
-  const size_t blob_bytes = (pool_off + pool_words * sizeof(unsigned) + 255) / 256 * 256;
-  int rc = ws->ensure(se_bytes + den_bytes + ent_bytes + blob_bytes, s);
-  if (rc) return rc;
-  ManyStage* stage = many_stage_of(ws);
-  unsigned char* h = nullptr;
-  int slot = 0;
-  rc = stage->take(blob_bytes, &h, &slot);
+  Blob blob;
+  const size_t arec_off = blob.add<ApplyManyRec>(n_act), brec_off = blob.add<BoundsRec>(n_act), crec_off = blob.add<CombManyRec>(n_act);
+  const size_t pool_off = blob.add<unsigned>(2 * ClassPool::words(n_act, 1, false) + ClassPool::words(n_act, NHOT, true) +
+                                             ClassPool::words(n_act, NAPP, true));
+  ManyUpload up;
+  rc = many_begin(ws, se_bytes + den_bytes + ent_bytes, blob.bytes(), s, &up);
   if (rc) return rc;
   unsigned char* base = (unsigned char*)ws->buf;
   int* se_base = reinterpret_cast<int*>(base);
   float* den_base = reinterpret_cast<float*>(base + se_bytes);
   CombEnt* ent_base = reinterpret_cast<CombEnt*>(base + se_bytes + den_bytes);
-  unsigned char* d_blob = base + se_bytes + den_bytes + ent_bytes;
-  ApplyManyRec* arecs = reinterpret_cast<ApplyManyRec*>(h + arec_off);
-  BoundsRec* brecs = reinterpret_cast<BoundsRec*>(h + brec_off);
-  CombManyRec* crecs = reinterpret_cast<CombManyRec*>(h + crec_off);
-  unsigned* pool = reinterpret_cast<unsigned*>(h + pool_off);
-  const unsigned* d_pool = reinterpret_cast<const unsigned*>(d_blob + pool_off);
+  ApplyManyRec* arecs = section<ApplyManyRec>(up.host, arec_off);
+  BoundsRec* brecs = section<BoundsRec>(up.host, brec_off);
+  CombManyRec* crecs = section<CombManyRec>(up.host, crec_off);
 
   std::vector<unsigned> key_blocks(n_act), bin_blocks(n_act);
-  unsigned* ent_pre = pool;
-  unsigned* den_pre = pool + (n_act + 1);
   {
     size_t se_at = 0, den_at = 0, ent_at = 0;
-    unsigned eb = 0, db = 0;
     for (size_t k = 0; k < n_act; ++k) {
       const tfra_apply_combined_desc& d = descs[act[k]];
       Table* t = reinterpret_cast<Table*>(d.table);
@@ -810,85 +779,51 @@ extern "C" int tfra_multi_apply_planned_combined(tfra_workspace_t* ws, size_t n_
       ent_at += (pl->n + 15) / 16 * 16;
       brecs[k] = BoundsRec{(const i64*)d.seg, se, pl->n, d.n_rows};
       crecs[k] = CombManyRec{(const i64*)d.seg, d.weights, se, den, ent, pl->n, d.n_rows, d.combiner};
-      ent_pre[k] = eb;
-      den_pre[k] = db;
-      eb += (unsigned)((pl->n + 255) / 256);
-      db += (unsigned)((d.n_rows + 255) / 256);
       plan_grids(pl, &key_blocks[k], &bin_blocks[k]);
       key_blocks[k] = many_cap(key_blocks[k], app_n[app_of[k]]);
       bin_blocks[k] = many_cap(bin_blocks[k], hot_n[hot_of[k]]);
-      ApplyManyRec& r = arecs[k];
-      r.v = t->view_of(t->cur);   // under the lock, after the capacity preparation
-      r.o = OptP{p->kind, p->lr, p->beta1, p->beta2, p->eps, p->l1, p->l2, p->lr_power, p->d_lr};
-      r.sp = ScoreP{t->opts.strategy, t->global_epoch, bounded[k]};
-      r.ks = keys_of(pl);
-      r.grads = d.grad_out;
-      r.partial = pl->partial;
-      r.default_row = d.param_default_row;
-      r.hout = pl->out.hout;
-      r.binmap = pl->binmap;
-      r.dflag = pl->dflag;
-      r.any_deferred = pl->any_deferred;
-      r.ent = ent;
-      r.dim = pl->dim;
-      r.aux0 = t->opts.aux_init[0];
-      r.aux1 = t->opts.aux_init[1];
-      r.use_gen = ++pl->use_gen;   // one use of the plan
+      // the view: under the lock, after the capacity preparation; ++use_gen: one use of the plan
+      arecs[k] = ApplyManyRec{t->view_of(t->cur), OptP{p->kind, p->lr, p->beta1, p->beta2, p->eps, p->l1, p->l2, p->lr_power, p->d_lr},
+                              ScoreP{t->opts.strategy, t->global_epoch, bounded[k]}, keys_of(pl), d.grad_out, pl->partial,
+                              d.param_default_row, pl->out.hout, pl->binmap, pl->dflag, pl->any_deferred, ent, pl->dim,
+                              t->opts.aux_init[0], t->opts.aux_init[1], ++pl->use_gen};
     }
-    ent_pre[n_act] = eb;
-    den_pre[n_act] = db;
   }
-  // a class = [prefix (n + 1) | idx (n)] in the pool
-  struct Cls { size_t at; unsigned n, grid; bool evict; };
-  Cls hot_cls[NHOT], app_cls[NAPP];
-  size_t at = 2 * (n_act + 1);
-  auto fill = [&](Cls& c, const std::vector<int>& of, int which, const std::vector<unsigned>& blocks) {
-    c = Cls{at, 0, 0, false};
-    for (size_t k = 0; k < n_act; ++k)
-      if (of[k] == which) ++c.n;
-    if (!c.n) return;
-    unsigned* pre = pool + at;
-    unsigned* idx = pre + c.n + 1;
-    unsigned j = 0;
-    for (size_t k = 0; k < n_act; ++k) {
-      if (of[k] != which) continue;
-      pre[j] = c.grid;
-      idx[j++] = (unsigned)k;
-      c.grid += blocks[k];
-      c.evict = c.evict || bounded[k] != 0;
-    }
-    pre[j] = c.grid;
-    at += 2 * c.n + 1;
-  };
-  for (int c = 0; c < NHOT; ++c) fill(hot_cls[c], hot_of, c, bin_blocks);
-  for (int c = 0; c < NAPP; ++c) fill(app_cls[c], app_of, c, key_blocks);
+  // the pool: the entry kernels' two prefixes over all records, then the classes, which read the records through an index
+  ClassPool pool{section<unsigned>(up.host, pool_off)};
+  auto all = [](size_t) { return true; };
+  const ManyClass ent_cls = pool.put(n_act, false, all, ent_blocks_of), den_cls = pool.put(n_act, false, all, den_blocks_of);
+  ManyClass hot_cls[NHOT], app_cls[NAPP];
+  for (int c = 0; c < NHOT; ++c)
+    hot_cls[c] = pool.put(n_act, true, [&](size_t k) { return hot_of[k] == c; }, [&](size_t k) { return bin_blocks[k]; });
+  for (int c = 0; c < NAPP; ++c)
+    app_cls[c] = pool.put(n_act, true, [&](size_t k) { return app_of[k] == c; }, [&](size_t k) { return key_blocks[k]; });
 
-  if (hipMemcpyAsync(d_blob, h, blob_bytes, hipMemcpyHostToDevice, s) != hipSuccess)
-    return set_error(TFRA_ERR_HIP, "multi_apply_planned_combined: record upload");
-  rc = stage->sent(slot, s);
+  rc = many_send(up, s, "multi_apply_planned_combined: record upload", false);
   if (rc) return rc;
   if (hipMemsetAsync(se_base, 0, se_bytes, s) != hipSuccess)   // empty rows: start = end = 0
     return set_error(TFRA_ERR_HIP, "multi_apply_planned_combined: memset");
   uint32_t launches = 0;
-  rc = comb_bounds_many(s, ent_pre[n_act], reinterpret_cast<const BoundsRec*>(d_blob + brec_off), d_pool, (unsigned)n_act);
+  const unsigned* d_pool = section<const unsigned>(up.dev, pool_off);
+  rc = comb_bounds_many(s, ent_cls.grid, section<const BoundsRec>(up.dev, brec_off), d_pool + ent_cls.at, (unsigned)n_act);
   if (rc) return rc;
-  rc = comb_den_ent_many(s, den_pre[n_act], ent_pre[n_act], reinterpret_cast<const CombManyRec*>(d_blob + crec_off), d_pool + (n_act + 1),
-                         d_pool, (unsigned)n_act);
+  rc = comb_den_ent_many(s, den_cls.grid, ent_cls.grid, section<const CombManyRec>(up.dev, crec_off), d_pool + den_cls.at,
+                         d_pool + ent_cls.at, (unsigned)n_act);
   if (rc) return rc;
   launches += 3;
-  const ApplyManyRec* d_arecs = reinterpret_cast<const ApplyManyRec*>(d_blob + arec_off);
+  const ApplyManyRec* d_arecs = section<const ApplyManyRec>(up.dev, arec_off);
   for (int c = 0; c < NHOT; ++c) {
-    const Cls& k = hot_cls[c];
+    const ManyClass& k = hot_cls[c];
     if (!k.n) continue;
     launch_hot_sums_many(s, c + 1, k.grid, d_arecs, d_pool + k.at, d_pool + k.at + k.n + 1, k.n);
     ++launches;
   }
   for (int c = 0; c < NAPP; ++c) {
-    const Cls& k = app_cls[c];
+    const ManyClass& k = app_cls[c];
     if (!k.n) continue;
     launch_apply_many(s, c % 3, c / 3, false, k.grid, d_arecs, d_pool + k.at, d_pool + k.at + k.n + 1, k.n);
     ++launches;
-    if (k.evict) {   // a table at max_capacity in the class: its eviction phase
+    if (app_evict[c]) {
       launch_apply_many(s, c % 3, c / 3, true, k.grid, d_arecs, d_pool + k.at, d_pool + k.at + k.n + 1, k.n);
       ++launches;
     }

@@ -134,6 +134,27 @@ static inline void with_granule(int g, F&& f) {
   }
 }
 
+// The fused kernels' storage types as an index: 0 float32, 1 float16, 2 bfloat16 (the caller has refused every other dtype)
+static inline int st_index(int dtype) { return dtype == TFRA_F16 ? 1 : dtype == TFRA_BF16 ? 2 : 0; }
+// One launch ladder per template axis (as with_granule), for single-table and grouped launchers alike: storage type, rule
+template <class F>
+static inline void with_stored(int st, F&& f) {
+  switch (st) {
+    case 1: f(std::integral_constant<int, TFRA_F16>{}); break;
+    case 2: f(std::integral_constant<int, TFRA_BF16>{}); break;
+    default: f(std::integral_constant<int, TFRA_F32>{}); break;
+  }
+}
+template <class F>
+static inline void with_opt_kind(int kind, F&& f) {
+  switch (kind) {
+    case TFRA_OPT_SGD: f(std::integral_constant<int, TFRA_OPT_SGD>{}); break;
+    case TFRA_OPT_ADAM: f(std::integral_constant<int, TFRA_OPT_ADAM>{}); break;
+    case TFRA_OPT_ADAGRAD: f(std::integral_constant<int, TFRA_OPT_ADAGRAD>{}); break;
+    default: f(std::integral_constant<int, TFRA_OPT_FTRL>{}); break;
+  }
+}
+
 }  // namespace tfra
 
 // Scratch of the front-end ops (tfra_workspace_create): one growing device buffer per caller stream.
@@ -152,7 +173,7 @@ struct tfra_workspace {
   hipStream_t unq_stream = nullptr;
   bool unq_stream_set = false;
   hipEvent_t unq_ev = nullptr;
-  void* many = nullptr;   // pinned staging ring of tfra_multi_find_combine's descriptor records (tfra_pool.hip)
+  void* many = nullptr;   // pinned staging ring of the grouped calls' descriptor records (ManyStage, tfra_many.h)
   int ensure(size_t need, hipStream_t s) {
     if (need <= bytes) return TFRA_OK;
     if (buf) {

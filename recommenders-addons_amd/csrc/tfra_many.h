@@ -1,12 +1,18 @@
 // What the grouped calls share (tfra_multi_find_combine: tfra_pool.hip; tfra_multi_apply_planned_combined: tfra_apply.hip, with its
-// entry-record kernels in tfra_frontend.hip): the search that takes a block to its descriptor, the records of the launches that
-// run in more than one unit, and the pinned staging ring the records reach the device through.
+// entry-record kernels in tfra_frontend.hip).
+// Device side: the search that takes a block to its descriptor and the records of the launches that run in more than one unit.
+// Host side, the frame of a grouped call: the outcome of an operation's argument checks (Check: each operation's checks are ONE
+// function, which its single-table call and its grouped call both run), the tables' locks (lock_and_enter), the layout of the
+// record blob (Blob), its way to the device through a pinned staging ring (ManyStage, many_begin / many_send) and the block
+// prefixes of a launch class (ClassPool).  A grouped call is: check every descriptor, classify, lock, lay out, fill, send, launch.
 // The types live in namespace tfra (not in an anonymous one): their launchers cross translation units.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <mutex>
 #include <string>
+#include <vector>
 
 #include "../../include/tfra_mi355x.h"
 #include "tfra_combine_device.h"
@@ -110,10 +116,96 @@ struct ManyStage {
   }
 };
 
-// the workspace's ring, made on first use
-inline ManyStage* many_stage_of(tfra_workspace* ws) {
-  if (!ws->many) ws->many = new ManyStage();
-  return reinterpret_cast<ManyStage*>(ws->many);
+// The blob of one call: the workspace holds [front_bytes of the call's own scratch | blob]; `host` is the staging slot to fill,
+// `dev` where it lands.  A section sits at the same offset in both (Blob).
+struct ManyUpload {
+  unsigned char *host = nullptr, *dev = nullptr;
+  size_t bytes = 0;
+  ManyStage* stage = nullptr;
+  int slot = 0;
+};
+inline int many_begin(tfra_workspace* ws, size_t front_bytes, size_t blob_bytes, hipStream_t s, ManyUpload* u) {
+  if (int rc = ws->ensure(front_bytes + blob_bytes, s)) return rc;
+  if (!ws->many) ws->many = new ManyStage();   // the workspace's ring, made on first use
+  u->stage = reinterpret_cast<ManyStage*>(ws->many);
+  u->dev = (unsigned char*)ws->buf + front_bytes;
+  u->bytes = blob_bytes;
+  return u->stage->take(blob_bytes, &u->host, &u->slot);
 }
+// the filled slot's copy and the event behind it; a copy that fails: `what` with TFRA_ERR_HIP, or (hip_detail) as ManyStage::hip_rc
+inline int many_send(const ManyUpload& u, hipStream_t s, const char* what, bool hip_detail) {
+  const hipError_t e = hipMemcpyAsync(u.dev, u.host, u.bytes, hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) return hip_detail ? ManyStage::hip_rc(e, what) : set_error(TFRA_ERR_HIP, what);
+  return u.stage->sent(u.slot, s);
+}
+
+// Offsets of the blob's sections: each (element type, count) starts 16-byte aligned, the total is rounded to 256.
+struct Blob {
+  size_t end = 0;
+  template <class T>
+  size_t add(size_t count) {
+    const size_t at = (end + 15) / 16 * 16;
+    end = at + count * sizeof(T);
+    return at;
+  }
+  size_t bytes() const { return (end + 255) / 256 * 256; }
+};
+template <class T>
+inline T* section(unsigned char* base, size_t off) { return reinterpret_cast<T*>(base + off); }
+
+// The launch classes of a call, one after the other in a section of unsigned words: a class is [prefix (n + 1)], then [idx (n)]
+// where its kernel reads the records through an index.  put() appends the class of the k in [0, n_all) with member(k), blocks(k)
+// blocks each; a class without members takes no words.  words(): what n_all members in at most n_classes classes can take.
+struct ManyClass { size_t at = 0; unsigned n = 0, grid = 0; };
+struct ClassPool {
+  unsigned* host;
+  size_t at = 0;
+  static size_t words(size_t n_all, size_t n_classes, bool with_idx) { return (with_idx ? 2 : 1) * n_all + n_classes; }
+  template <class Member, class Blocks>
+  ManyClass put(size_t n_all, bool with_idx, Member&& member, Blocks&& blocks) {
+    ManyClass c{at, 0, 0};
+    for (size_t k = 0; k < n_all; ++k) c.n += member(k) ? 1 : 0;
+    if (!c.n) return c;
+    unsigned* pre = host + at;
+    unsigned* idx = pre + c.n + 1;
+    unsigned j = 0;
+    for (size_t k = 0; k < n_all; ++k) {
+      if (!member(k)) continue;
+      pre[j] = c.grid;
+      if (with_idx) idx[j] = (unsigned)k;
+      ++j;
+      c.grid += blocks(k);
+    }
+    pre[j] = c.grid;
+    at += c.n + 1 + (with_idx ? c.n : 0);
+    return c;
+  }
+};
+
+// Each distinct table of `tabs` locked once, in one global order (by address: two threads with overlapping lists cannot
+// deadlock), then entered on s (also: the calling thread is on the tables' device from here on).
+inline int lock_and_enter(std::vector<Table*> tabs, hipStream_t s, std::vector<std::unique_lock<std::mutex>>* locks) {
+  std::sort(tabs.begin(), tabs.end(), std::less<Table*>());
+  tabs.erase(std::unique(tabs.begin(), tabs.end()), tabs.end());
+  locks->reserve(tabs.size());
+  for (Table* t : tabs) locks->emplace_back(t->mu);
+  for (Table* t : tabs)
+    if (int rc = t->enter(s)) return rc;
+  return TFRA_OK;
+}
+
+// The outcome of an operation's argument checks: a code and the message WITHOUT the entry point's prefix (no message: the callee
+// that failed has recorded its own), or TFRA_OK and whether there is anything to do.  An operation's checks are one function in
+// the single call's order; where that call locks and enters its table the function calls `at_entry`, which the grouped call uses
+// for what only a descriptor can get wrong.
+struct Check {
+  int code = TFRA_OK;
+  std::string msg;
+  bool active = true;
+  bool done() const { return code != TFRA_OK || !active; }
+};
+inline Check refuse(int code, const char* msg) { return Check{code, msg, false}; }
+inline Check nothing_to_do() { return Check{TFRA_OK, "", false}; }
+inline int report(const std::string& who, const Check& c) { return c.msg.empty() ? c.code : set_error(c.code, who + c.msg); }
 
 }  // namespace tfra

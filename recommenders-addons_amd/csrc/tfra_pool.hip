@@ -7,10 +7,14 @@
 // entries in input order, probes the table once per entry and accumulates w * row in registers: neither tensor exists and
 // nothing is counted on the host.  The arithmetic is tfra_combine_device.h's, the code seg_combine_kernel (tfra_frontend.hip)
 // compiles, in the same order, so the result equals tfra_table_find + tfra_sparse_segment_combine bit for bit.
+// tfra_multi_find_combine is the same lookup for a list of tables; its host side stands on the grouped-call frame of tfra_many.h,
+// and both calls run ONE function for their argument checks (check_find_combine) and one launch ladder (with_pool_class).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/tfra_mi355x.h"
@@ -191,47 +195,42 @@ __global__ __launch_bounds__(256) void seg64_bounds_many_kernel(const BoundsRec*
   if (p == rec.nnz - 1 || rec.seg[p + 1] != s) rec.se[rec.n_rows + s] = (int)p + 1;
 }
 
-template <int DT>
-void launch_find_combine_many(hipStream_t s, int nch, unsigned grid, const ManyRec* recs, const unsigned* prefix, unsigned n) {
-  constexpr int U = 4;
-  if (nch == 0) find_combine_many_kernel<DT, U, 1><<<grid, 256, 0, s>>>(recs, prefix, n);
-  else if (nch == 1) find_combine_many_kernel<DT, U, 2><<<grid, 256, 0, s>>>(recs, prefix, n);
-  else find_combine_many_kernel<DT, U, 4><<<grid, 256, 0, s>>>(recs, prefix, n);
-}
-
-// (the records reach the device through the workspace's pinned staging ring: ManyStage, tfra_many.h)
-
-// the single call's checks of one descriptor, in its order and with its codes; *active: the descriptor has rows to write
-int check_desc(const tfra_find_combine_desc& d, const tfra_workspace* ws, bool* active, std::string* msg) {
-  *active = false;
-  if (d.struct_size != sizeof(tfra_find_combine_desc)) { *msg = "descriptor size mismatch"; return TFRA_ERR_INVALID; }
-  const Table* t = reinterpret_cast<const Table*>(d.table);
-  if (!t) { *msg = "null table"; return TFRA_ERR_INVALID; }
-  if (d.combiner < 0 || d.combiner > 2) { *msg = "bad argument"; return TFRA_ERR_INVALID; }
-  if (ws->device != t->device) { *msg = "workspace and table live on different devices"; return TFRA_ERR_INVALID; }
-  const int dt = t->opts.value_dtype, dim = t->opts.dim;
-  if (dt != TFRA_F32 && dt != TFRA_F16 && dt != TFRA_BF16) { *msg = "value_dtype must be float32, float16 or bfloat16"; return TFRA_ERR_UNSUPPORTED; }
-  if (dim % 4 != 0 || dim > 256) { *msg = "needs dim % 4 == 0 and dim <= 256"; return TFRA_ERR_UNSUPPORTED; }
-  if (d.nnz >= (1ULL << 31) || d.n_rows >= (1ULL << 30)) { *msg = "too large (nnz < 2^31, n_rows < 2^30)"; return TFRA_ERR_UNSUPPORTED; }
-  if ((((uintptr_t)d.out | (uintptr_t)d.default_row) & 15) || ((uintptr_t)d.ids & 7) || ((uintptr_t)d.seg & 7) || ((uintptr_t)d.weights & 3)) {
-    *msg = "misaligned buffer (out and default_row: 16 bytes)";
-    return TFRA_ERR_UNSUPPORTED;
+// NCH by the row width: 1 (dim <= 64), 2 (<= 128) or 4 column chunks; f(std::integral_constant<int, NCH>{}) for the index
+int nch_index(int dim) { return dim <= 64 ? 0 : dim <= 128 ? 1 : 2; }
+template <class F>
+void with_nch(int index, F&& f) {
+  switch (index) {
+    case 0: f(std::integral_constant<int, 1>{}); break;
+    case 1: f(std::integral_constant<int, 2>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
   }
-  if (d.n_rows == 0) return TFRA_OK;
-  if (!d.out) { *msg = "null out"; return TFRA_ERR_INVALID; }
-  if (d.nnz && (!d.ids || !d.seg || !d.default_row)) { *msg = "null buffer"; return TFRA_ERR_INVALID; }
-  *active = true;
-  return TFRA_OK;
+}
+// launch(DT, U, NCH) for a table's storage type index and NCH index: the one ladder of the single and the grouped launch
+template <class F>
+void with_pool_class(int st, int nch, F&& launch) {
+  with_stored(st, [&](auto DT) { with_nch(nch, [&](auto NCH) { launch(DT, std::integral_constant<int, 4>{}, NCH); }); });
 }
 
-template <int DT>
-void launch_find_combine(hipStream_t s, const TableView& v, size_t n_rows, int dim, const i64* ids, const float* w, const int* se,
-                         int combiner, const unsigned char* d, float* out) {
-  constexpr int U = 4;
-  const unsigned grid = (unsigned)((n_rows * 16 + 255) / 256);
-  if (dim <= 64) find_combine_kernel<DT, U, 1><<<grid, 256, 0, s>>>(v, n_rows, dim, ids, w, se, combiner, d, out);
-  else if (dim <= 128) find_combine_kernel<DT, U, 2><<<grid, 256, 0, s>>>(v, n_rows, dim, ids, w, se, combiner, d, out);
-  else find_combine_kernel<DT, U, 4><<<grid, 256, 0, s>>>(v, n_rows, dim, ids, w, se, combiner, d, out);
+// The checks of a pooled lookup, for tfra_table_find_combine and for each descriptor of tfra_multi_find_combine.
+// active: there are rows to write.
+const char* const NEEDS_DIM = "needs dim % 4 == 0 and dim <= 256";
+template <class AtEntry>
+Check check_find_combine(const Table* t, const tfra_workspace* ws, size_t nnz, const void* ids, const void* seg, const float* weights,
+                         int combiner, size_t n_rows, const void* default_row, const float* out, AtEntry&& at_entry) {
+  if (!t) return refuse(TFRA_ERR_INVALID, "null table");
+  if (!ws || combiner < 0 || combiner > 2) return refuse(TFRA_ERR_INVALID, "bad argument");
+  if (Check e = at_entry(); e.done()) return e;
+  if (ws->device != t->device) return refuse(TFRA_ERR_INVALID, "workspace and table live on different devices");
+  const int dt = t->opts.value_dtype, dim = t->opts.dim;
+  if (dt != TFRA_F32 && dt != TFRA_F16 && dt != TFRA_BF16) return refuse(TFRA_ERR_UNSUPPORTED, "value_dtype must be float32, float16 or bfloat16");
+  if (dim % 4 != 0 || dim > 256) return refuse(TFRA_ERR_UNSUPPORTED, NEEDS_DIM);
+  if (nnz >= (1ULL << 31) || n_rows >= (1ULL << 30)) return refuse(TFRA_ERR_UNSUPPORTED, "too large (nnz < 2^31, n_rows < 2^30)");
+  if ((((uintptr_t)out | (uintptr_t)default_row) & 15) || ((uintptr_t)ids & 7) || ((uintptr_t)seg & 7) || ((uintptr_t)weights & 3))
+    return refuse(TFRA_ERR_UNSUPPORTED, "misaligned buffer (out and default_row: 16 bytes)");
+  if (n_rows == 0) return nothing_to_do();
+  if (!out) return refuse(TFRA_ERR_INVALID, "null out");
+  if (nnz && (!ids || !seg || !default_row)) return refuse(TFRA_ERR_INVALID, "null buffer");
+  return Check{};
 }
 
 }  // namespace
@@ -240,40 +239,31 @@ extern "C" int tfra_table_find_combine(tfra_table_t* tp, tfra_workspace_t* ws, s
                                        const float* weights, int combiner, size_t n_rows, const void* default_row, float* out,
                                        tfra_stream_t stream) {
   Table* t = reinterpret_cast<Table*>(tp);
-  if (!t) return set_error(TFRA_ERR_INVALID, "find_combine: null table");
-  if (!ws || combiner < 0 || combiner > 2) return set_error(TFRA_ERR_INVALID, "find_combine: bad argument");
   hipStream_t s = (hipStream_t)stream;
-  std::lock_guard<std::mutex> lock(t->mu);
-  int rc = t->enter(s);
-  if (rc) return rc;
-  if (ws->device != t->device) return set_error(TFRA_ERR_INVALID, "find_combine: workspace and table live on different devices");
-  const int dt = t->opts.value_dtype, dim = t->opts.dim;
-  if (dt != TFRA_F32 && dt != TFRA_F16 && dt != TFRA_BF16)
-    return set_error(TFRA_ERR_UNSUPPORTED, "find_combine: value_dtype must be float32, float16 or bfloat16");
-  if (dim % 4 != 0 || dim > 256)
-    return set_error(TFRA_ERR_UNSUPPORTED, "find_combine: needs dim % 4 == 0 and dim <= 256 (use tfra_unique + tfra_table_find + "
-                                           "tfra_sparse_segment_combine otherwise)");
-  if (nnz >= (1ULL << 31) || n_rows >= (1ULL << 30)) return set_error(TFRA_ERR_UNSUPPORTED, "find_combine: too large (nnz < 2^31, n_rows < 2^30)");
-  if ((((uintptr_t)out | (uintptr_t)default_row) & 15) || ((uintptr_t)ids & 7) || ((uintptr_t)seg & 7) || ((uintptr_t)weights & 3))
-    return set_error(TFRA_ERR_UNSUPPORTED, "find_combine: misaligned buffer (out and default_row: 16 bytes)");
-  if (n_rows == 0) return TFRA_OK;
-  if (!out) return set_error(TFRA_ERR_INVALID, "find_combine: null out");
+  std::unique_lock<std::mutex> lock;
+  Check c = check_find_combine(t, ws, nnz, ids, seg, weights, combiner, n_rows, default_row, out, [&] {
+    lock = std::unique_lock<std::mutex>(t->mu);
+    return Check{t->enter(s)};
+  });
+  if (c.msg == NEEDS_DIM) c.msg += " (use tfra_unique + tfra_table_find + tfra_sparse_segment_combine otherwise)";
+  if (c.code) return report("find_combine: ", c);
+  if (!c.active) return TFRA_OK;
+  const int dim = t->opts.dim;
   if (nnz == 0) {
     HIP_TRY(hipMemsetAsync(out, 0, n_rows * (size_t)dim * sizeof(float), s));
     return TFRA_OK;
   }
-  if (!ids || !seg || !default_row) return set_error(TFRA_ERR_INVALID, "find_combine: null buffer");
-  rc = ws->ensure((2 * n_rows * sizeof(int) + 255) / 256 * 256, s);
+  int rc = ws->ensure((2 * n_rows * sizeof(int) + 255) / 256 * 256, s);
   if (rc) return rc;
   int* se = (int*)ws->buf;
   rc = comb_bounds(s, nnz, seg, n_rows, se);
   if (rc) return rc;
   const TableView v = t->view_of(t->cur);
-  const i64* k = (const i64*)ids;
-  const unsigned char* d = (const unsigned char*)default_row;
-  if (dt == TFRA_F32) launch_find_combine<TFRA_F32>(s, v, n_rows, dim, k, weights, se, combiner, d, out);
-  else if (dt == TFRA_F16) launch_find_combine<TFRA_F16>(s, v, n_rows, dim, k, weights, se, combiner, d, out);
-  else launch_find_combine<TFRA_BF16>(s, v, n_rows, dim, k, weights, se, combiner, d, out);
+  const unsigned grid = (unsigned)((n_rows * 16 + 255) / 256);
+  with_pool_class(st_index(t->opts.value_dtype), nch_index(dim), [&](auto DT, auto U, auto NCH) {
+    find_combine_kernel<DT, U, NCH><<<grid, 256, 0, s>>>(v, n_rows, dim, (const i64*)ids, weights, se, combiner,
+                                                               (const unsigned char*)default_row, out);
+  });
   HIP_TRY(hipGetLastError());
   return TFRA_OK;
 }
@@ -306,137 +296,96 @@ extern "C" int tfra_multi_find_combine(tfra_workspace_t* ws, size_t n_tables, co
   // every descriptor is checked before anything is enqueued: one bad descriptor and no out is written
   constexpr int NCLASS = 9;   // (float32 | float16 | bfloat16) x (NCH 1 | 2 | 4)
   std::vector<int> cls(n_tables, -1);
+  std::vector<size_t> se_off(n_tables, 0);   // a descriptor's bounds in the bounds area, in input order
   size_t n_act = 0, n_bnd = 0, total_rows = 0;
+  u64 bnd_blocks = 0;
   for (size_t i = 0; i < n_tables; ++i) {
-    bool active = false;
-    std::string msg;
-    const int rc = check_desc(descs[i], ws, &active, &msg);
-    if (rc) return set_error(rc, "multi_find_combine: descriptor " + std::to_string(i) + ": " + msg);
-    if (!active) continue;
-    const Table* t = reinterpret_cast<const Table*>(descs[i].table);
-    const int dt = t->opts.value_dtype, dim = t->opts.dim;
-    cls[i] = (dt == TFRA_F32 ? 0 : dt == TFRA_F16 ? 1 : 2) * 3 + (dim <= 64 ? 0 : dim <= 128 ? 1 : 2);
+    const tfra_find_combine_desc& d = descs[i];
+    if (d.struct_size != sizeof(tfra_find_combine_desc))
+      return set_error(TFRA_ERR_INVALID, "multi_find_combine: descriptor " + std::to_string(i) + ": descriptor size mismatch");
+    const Table* t = reinterpret_cast<const Table*>(d.table);
+    const Check c = check_find_combine(t, ws, d.nnz, d.ids, d.seg, d.weights, d.combiner, d.n_rows, d.default_row, d.out, [] { return Check{}; });
+    if (c.code) return report("multi_find_combine: descriptor " + std::to_string(i) + ": ", c);
+    if (!c.active) continue;
+    cls[i] = st_index(t->opts.value_dtype) * 3 + nch_index(t->opts.dim);
     ++n_act;
-    n_bnd += descs[i].nnz ? 1 : 0;
-    total_rows += descs[i].n_rows;
+    n_bnd += d.nnz ? 1 : 0;
+    bnd_blocks += (d.nnz + 255) / 256;
+    se_off[i] = 2 * total_rows;
+    total_rows += d.n_rows;
   }
   if (n_act == 0) return TFRA_OK;
   // the records' order: class by class, input order inside a class
+  auto row_blocks = [&](size_t i) { return (unsigned)((descs[i].n_rows * 16 + 255) / 256); };
+  auto bnd_blocks_of = [&](size_t i) { return (unsigned)((descs[i].nnz + 255) / 256); };
   std::vector<size_t> order;
   order.reserve(n_act);
   size_t cls_first[NCLASS + 1];
-  u64 cls_blocks[NCLASS], bnd_blocks = 0;
   for (int c = 0; c < NCLASS; ++c) {
     cls_first[c] = order.size();
-    cls_blocks[c] = 0;
+    u64 blocks = 0;
     for (size_t i = 0; i < n_tables; ++i)
-      if (cls[i] == c) { order.push_back(i); cls_blocks[c] += (descs[i].n_rows * 16 + 255) / 256; }
-    if (cls_blocks[c] >= (1ULL << 31)) return set_error(TFRA_ERR_UNSUPPORTED, "multi_find_combine: too many rows in one call");
+      if (cls[i] == c) { order.push_back(i); blocks += row_blocks(i); }
+    if (blocks >= (1ULL << 31)) return set_error(TFRA_ERR_UNSUPPORTED, "multi_find_combine: too many rows in one call");
   }
   cls_first[NCLASS] = order.size();
-  for (size_t i = 0; i < n_tables; ++i)
-    if (cls[i] >= 0) bnd_blocks += (descs[i].nnz + 255) / 256;
   if (bnd_blocks >= (1ULL << 31)) return set_error(TFRA_ERR_UNSUPPORTED, "multi_find_combine: too many entries in one call");
 
-  // each distinct table locked once, in one global order (by address): two threads with overlapping lists cannot deadlock
+  // (one table may stand in several descriptors: locked once)
   std::vector<Table*> tabs;
   tabs.reserve(n_act);
   for (size_t i : order) tabs.push_back(reinterpret_cast<Table*>(descs[i].table));
-  std::sort(tabs.begin(), tabs.end(), std::less<Table*>());
-  tabs.erase(std::unique(tabs.begin(), tabs.end()), tabs.end());
   std::vector<std::unique_lock<std::mutex>> locks;
-  locks.reserve(tabs.size());
-  for (Table* t : tabs) locks.emplace_back(t->mu);
-  for (Table* t : tabs) {
-    const int rc = t->enter(s);
-    if (rc) return rc;
-  }
-
-  // device memory: [bounds of all rows | records | per-class block prefixes | bounds records | their block prefix]
-  const size_t se_bytes = (2 * total_rows * sizeof(int) + 255) / 256 * 256;
-  const size_t rec_off = 0, cpre_off = (n_act * sizeof(ManyRec) + 15) / 16 * 16;
-  const size_t brec_off = (cpre_off + (n_act + NCLASS) * sizeof(unsigned) + 15) / 16 * 16;
-  const size_t bpre_off = brec_off + n_bnd * sizeof(BoundsRec);
-  const size_t blob_bytes = (bpre_off + (n_bnd + 1) * sizeof(unsigned) + 255) / 256 * 256;
-  int rc = ws->ensure(se_bytes + blob_bytes, s);
+  int rc = lock_and_enter(std::move(tabs), s, &locks);
   if (rc) return rc;
-  ManyStage* stage = many_stage_of(ws);
-  unsigned char* h = nullptr;
-  int slot = 0;
-  rc = stage->take(blob_bytes, &h, &slot);
+
+  // device memory: [bounds of all rows | blob], the blob = [records | per-class block prefixes | bounds records | their block prefix]
+  const size_t se_bytes = (2 * total_rows * sizeof(int) + 255) / 256 * 256;
+  Blob blob;
+  const size_t rec_off = blob.add<ManyRec>(n_act), cpre_off = blob.add<unsigned>(ClassPool::words(n_act, NCLASS, false));
+  const size_t brec_off = blob.add<BoundsRec>(n_bnd), bpre_off = blob.add<unsigned>(ClassPool::words(n_bnd, 1, false));
+  ManyUpload up;
+  rc = many_begin(ws, se_bytes, blob.bytes(), s, &up);
   if (rc) return rc;
   int* se_base = (int*)ws->buf;
-  unsigned char* d_blob = (unsigned char*)ws->buf + se_bytes;
-  ManyRec* recs = reinterpret_cast<ManyRec*>(h + rec_off);
-  unsigned* cpre = reinterpret_cast<unsigned*>(h + cpre_off);
-  BoundsRec* brecs = reinterpret_cast<BoundsRec*>(h + brec_off);
-  unsigned* bpre = reinterpret_cast<unsigned*>(h + bpre_off);
+  ManyRec* recs = section<ManyRec>(up.host, rec_off);
+  BoundsRec* brecs = section<BoundsRec>(up.host, brec_off);
   // the views are taken here, under the locks: a table that grew since the last call has another one
-  std::vector<size_t> se_off(n_tables, 0);
-  {
-    size_t off = 0;
-    for (size_t i = 0; i < n_tables; ++i)
-      if (cls[i] >= 0) { se_off[i] = off; off += 2 * descs[i].n_rows; }
+  for (size_t k = 0; k < n_act; ++k) {
+    const tfra_find_combine_desc& d = descs[order[k]];
+    Table* t = reinterpret_cast<Table*>(d.table);
+    recs[k] = ManyRec{t->view_of(t->cur), d.n_rows, (const i64*)d.ids, d.weights, se_base + se_off[order[k]],
+                      (const unsigned char*)d.default_row, d.out, t->opts.dim, d.combiner};
   }
-  size_t cpre_at[NCLASS];
-  {
-    size_t k = 0, pre = 0;
-    for (int c = 0; c < NCLASS; ++c) {
-      cpre_at[c] = pre;
-      if (cls_first[c] == cls_first[c + 1]) continue;
-      unsigned blocks = 0;
-      for (size_t j = cls_first[c]; j < cls_first[c + 1]; ++j, ++k) {
-        const tfra_find_combine_desc& d = descs[order[j]];
-        Table* t = reinterpret_cast<Table*>(d.table);
-        ManyRec& r = recs[k];
-        r.v = t->view_of(t->cur);
-        r.n_rows = d.n_rows;
-        r.ids = (const i64*)d.ids;
-        r.w = d.weights;
-        r.se = se_base + se_off[order[j]];
-        r.default_row = (const unsigned char*)d.default_row;
-        r.out = d.out;
-        r.dim = t->opts.dim;
-        r.combiner = d.combiner;
-        cpre[pre++] = blocks;
-        blocks += (unsigned)((d.n_rows * 16 + 255) / 256);
-      }
-      cpre[pre++] = blocks;
-    }
-  }
+  // the records stand in class order: a class is a range of them and needs no index
+  ClassPool cpool{section<unsigned>(up.host, cpre_off)};
+  ManyClass row_cls[NCLASS];
+  for (int c = 0; c < NCLASS; ++c)
+    row_cls[c] = cpool.put(n_act, false, [&](size_t k) { return k >= cls_first[c] && k < cls_first[c + 1]; },
+                           [&](size_t k) { return row_blocks(order[k]); });
+  auto bounded = [&](size_t i) { return cls[i] >= 0 && descs[i].nnz != 0; };
   {
     size_t k = 0;
-    unsigned blocks = 0;
-    for (size_t i = 0; i < n_tables; ++i) {
-      if (cls[i] < 0 || descs[i].nnz == 0) continue;
-      brecs[k].seg = (const i64*)descs[i].seg;
-      brecs[k].se = se_base + se_off[i];
-      brecs[k].nnz = descs[i].nnz;
-      brecs[k].n_rows = descs[i].n_rows;
-      bpre[k++] = blocks;
-      blocks += (unsigned)((descs[i].nnz + 255) / 256);
-    }
-    bpre[k] = blocks;
+    for (size_t i = 0; i < n_tables; ++i)
+      if (bounded(i)) brecs[k++] = BoundsRec{(const i64*)descs[i].seg, se_base + se_off[i], descs[i].nnz, descs[i].n_rows};
   }
-  HIP_TRY(hipMemcpyAsync(d_blob, h, blob_bytes, hipMemcpyHostToDevice, s));
-  rc = stage->sent(slot, s);
+  const ManyClass bnd = ClassPool{section<unsigned>(up.host, bpre_off)}.put(n_tables, false, bounded, bnd_blocks_of);
+  rc = many_send(up, s, "hipMemcpyAsync(d_blob, h, blob_bytes, hipMemcpyHostToDevice, s)", true);
   if (rc) return rc;
   HIP_TRY(hipMemsetAsync(se_base, 0, 2 * total_rows * sizeof(int), s));   // empty rows (and every row of an nnz == 0 descriptor): 0, 0
   uint32_t launches = 0;
-  if (n_bnd) {
-    seg64_bounds_many_kernel<<<(unsigned)bnd_blocks, 256, 0, s>>>(reinterpret_cast<const BoundsRec*>(d_blob + brec_off),
-                                                                  reinterpret_cast<const unsigned*>(d_blob + bpre_off), (unsigned)n_bnd);
+  if (bnd.n) {
+    seg64_bounds_many_kernel<<<bnd.grid, 256, 0, s>>>(section<const BoundsRec>(up.dev, brec_off), section<const unsigned>(up.dev, bpre_off), bnd.n);
     ++launches;
   }
   for (int c = 0; c < NCLASS; ++c) {
-    const unsigned n = (unsigned)(cls_first[c + 1] - cls_first[c]);
-    if (!n) continue;
-    const ManyRec* r = reinterpret_cast<const ManyRec*>(d_blob + rec_off) + cls_first[c];
-    const unsigned* p = reinterpret_cast<const unsigned*>(d_blob + cpre_off) + cpre_at[c];
-    const unsigned grid = (unsigned)cls_blocks[c];
-    if (c / 3 == 0) launch_find_combine_many<TFRA_F32>(s, c % 3, grid, r, p, n);
-    else if (c / 3 == 1) launch_find_combine_many<TFRA_F16>(s, c % 3, grid, r, p, n);
-    else launch_find_combine_many<TFRA_BF16>(s, c % 3, grid, r, p, n);
+    const ManyClass& k = row_cls[c];
+    if (!k.n) continue;
+    const ManyRec* r = section<const ManyRec>(up.dev, rec_off) + cls_first[c];
+    const unsigned* p = section<const unsigned>(up.dev, cpre_off) + k.at;
+    with_pool_class(c / 3, c % 3, [&](auto DT, auto U, auto NCH) {
+      find_combine_many_kernel<DT, U, NCH><<<k.grid, 256, 0, s>>>(r, p, k.n);
+    });
     ++launches;
   }
   HIP_TRY(hipGetLastError());

@@ -499,6 +499,14 @@ class SparsePlan:
       self._built.record(stream)
     return self
 
+  def _wait_built(self, stream):    # before a reader of the plan is enqueued on `stream`
+    stream.wait_event(self._built)
+
+  def _mark_used(self, stream):     # behind a reader of the plan's buffers on `stream`: the next build waits for it
+    if self._used is None:
+      self._used = torch.cuda.Event()
+    self._used.record(stream)
+
   def partition(self, num_shards, mode=0):
     """The plan's distinct ids grouped by owner (tfra_plan_partition: tfra_partition over the plan's keys, in place of
     tf.unique + dynamic_partition): owner-major ids [n], perm [n] (plan index of each owner-major row), counts
@@ -529,12 +537,10 @@ class SparsePlan:
       raise ValueError("dest must be a contiguous int32 tensor with one entry per id")
     stream = torch.cuda.current_stream(self._device)
     if sync:
-      stream.wait_event(self._built)
+      self._wait_built(stream)
     _capi.call("tfra_plan_reduce_to", self._h, _ptr(grads), _ptr(dest), _ptr(rows_out), _stream(self._device))
     if sync:
-      if self._used is None:
-        self._used = torch.cuda.Event()
-      self._used.record(stream)
+      self._mark_used(stream)
     return rows_out
 
   def read(self):
@@ -571,21 +577,17 @@ def _apply_planned(self, params, plan, grads, default_row, sync=True):
   d = default_row.to(self._device, torch.float32).contiguous()
   stream = torch.cuda.current_stream(self._device)
   if sync:
-    stream.wait_event(plan._built)
+    plan._wait_built(stream)
   _capi.call("tfra_table_apply_planned", self._h, ctypes.byref(params), plan._h, _ptr(grads), _ptr(d), _stream(self._device))
   if sync:
-    if plan._used is None:
-      plan._used = torch.cuda.Event()
-    plan._used.record(stream)
+    plan._mark_used(stream)
 
 
 _DeviceTable.apply_planned = _apply_planned
 
 
-def _apply_planned_combined(self, params, plan, grad_out, seg, weights, combiner, default_row, sync=True):
-  """apply_planned for an embedding_lookup_sparse (tfra_table_apply_planned_combined): `plan` built over the entry ids,
-  grad_out [n_rows, dim] the gradient of the combined result, seg [nnz] its row ids (ascending), weights [nnz] or None,
-  combiner 0 sum / 1 mean / 2 sqrtn.  Entry e's gradient is formed from grad_out inside the write-back kernels."""
+def _apply_combined_args(self, plan, grad_out, seg, weights, default_row):
+  """A combined write-back's grad_out, seg, weights (or None) and default row, checked and as the C calls take them."""
   if plan._dim != self._dim or plan._device != self._device:
     raise ValueError("the plan was built for dim %d on %s" % (plan._dim, plan._device))
   grad_out = grad_out.to(self._device, torch.float32).contiguous()
@@ -596,15 +598,24 @@ def _apply_planned_combined(self, params, plan, grad_out, seg, weights, combiner
     raise ValueError("seg / weights need one element per plan entry (%d)" % plan.n)
   w = None if weights is None else weights.to(self._device, torch.float32).contiguous()
   d = default_row.to(self._device, torch.float32).contiguous()
+  return grad_out, seg, w, d
+
+
+_DeviceTable._apply_combined_args = _apply_combined_args
+
+
+def _apply_planned_combined(self, params, plan, grad_out, seg, weights, combiner, default_row, sync=True):
+  """apply_planned for an embedding_lookup_sparse (tfra_table_apply_planned_combined): `plan` built over the entry ids,
+  grad_out [n_rows, dim] the gradient of the combined result, seg [nnz] its row ids (ascending), weights [nnz] or None,
+  combiner 0 sum / 1 mean / 2 sqrtn.  Entry e's gradient is formed from grad_out inside the write-back kernels."""
+  grad_out, seg, w, d = self._apply_combined_args(plan, grad_out, seg, weights, default_row)
   stream = torch.cuda.current_stream(self._device)
   if sync:
-    stream.wait_event(plan._built)
+    plan._wait_built(stream)
   _capi.call("tfra_table_apply_planned_combined", self._h, ctypes.byref(params), plan._h, _ptr(grad_out), _ptr(seg), _ptr(w),
              int(combiner), grad_out.shape[0], _ptr(d), _stream(self._device))
   if sync:
-    if plan._used is None:
-      plan._used = torch.cuda.Event()
-    plan._used.record(stream)
+    plan._mark_used(stream)
 
 
 _DeviceTable.apply_planned_combined = _apply_planned_combined
@@ -632,12 +643,10 @@ def _upsert_planned(self, plan, values, scores=None, sync=True):
     scores = scores.to(self._device, torch.int64).contiguous()
   stream = torch.cuda.current_stream(self._device)
   if sync:
-    stream.wait_event(plan._built)
+    plan._wait_built(stream)
   _capi.call("tfra_table_upsert_planned", self._h, plan._h, _ptr(values), _ptr(scores), _stream(self._device))
   if sync:
-    if plan._used is None:
-      plan._used = torch.cuda.Event()
-    plan._used.record(stream)
+    plan._mark_used(stream)
 
 
 _DeviceTable.upsert_sparse = _upsert_sparse
@@ -878,16 +887,7 @@ def apply_planned_combined_many(requests, p_list, sync=True):
       device = table._device
     elif table._device != device:
       raise ValueError("apply_planned_combined_many: all tables must live on one device (%s and %s)" % (device, table._device))
-    if plan._dim != table._dim or plan._device != table._device:
-      raise ValueError("the plan was built for dim %d on %s" % (plan._dim, plan._device))
-    grad_out = grad_out.to(table._device, torch.float32).contiguous()
-    if grad_out.dim() != 2 or grad_out.shape[1] != table._dim:
-      raise ValueError("Expected grad_out of shape [n_rows, %d], got %s" % (table._dim, list(grad_out.shape)))
-    seg = seg.to(table._device, torch.int64).contiguous()
-    if seg.numel() != plan.n or (weights is not None and weights.numel() != plan.n):
-      raise ValueError("seg / weights need one element per plan entry (%d)" % plan.n)
-    w = None if weights is None else weights.to(table._device, torch.float32).contiguous()
-    d = default_row.to(table._device, torch.float32).contiguous()
+    grad_out, seg, w, d = table._apply_combined_args(plan, grad_out, seg, weights, default_row)
     keep.append((grad_out, seg, w, d, p_list[i]))
     plans.append(plan)
     e = descs[i]
@@ -901,13 +901,11 @@ def apply_planned_combined_many(requests, p_list, sync=True):
   stream = torch.cuda.current_stream(device)
   if sync:
     for plan in plans:
-      stream.wait_event(plan._built)
+      plan._wait_built(stream)
   launches = ctypes.c_uint32(0)
   _capi.call("tfra_multi_apply_planned_combined", _workspace(device), n, ctypes.c_void_p(ctypes.addressof(descs)),
              ctypes.c_void_p(ctypes.addressof(launches)), _stream(device))
   if sync:
     for plan in plans:
-      if plan._used is None:
-        plan._used = torch.cuda.Event()
-      plan._used.record(stream)
+      plan._mark_used(stream)
   return int(launches.value)
