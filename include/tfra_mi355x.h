@@ -581,7 +581,7 @@ int tfra_multi_find_combine(tfra_workspace_t* ws, size_t n_tables, const tfra_fi
  * *launches_out (optional, host): the kernel launches enqueued =
  *   3 + (NCH classes present) + ((rule, storage type) classes present) + ((rule, storage type) classes with a table at max_capacity),
  * 0 when no descriptor has ids.  26 growing float32 tables of dims 16 / 32 / 64 / 128 with one rule: 3 + 2 + 1 = 6.
- * The plan builds (tfra_sparse_plan_build) stay per plan.  Not for stream capture. */
+ * The plans are built per plan (tfra_sparse_plan_build) or by tfra_multi_sparse_plan_build below.  Not for stream capture. */
 typedef struct {
   uint32_t struct_size;              /* = sizeof(tfra_apply_combined_desc) */
   int32_t  combiner;                 /* 0 sum | 1 mean | 2 sqrtn */
@@ -595,6 +595,30 @@ typedef struct {
 } tfra_apply_combined_desc;
 int tfra_multi_apply_planned_combined(tfra_workspace_t* ws, size_t n_tables, const tfra_apply_combined_desc* descs,
                                       uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
+
+/* The CSR plans of MANY batches in one call (a 26-table model's write-back plans are 26 tfra_sparse_plan_build calls = 78 launches
+ * otherwise): descs[i].plan ends as tfra_sparse_plan_build(plan, n, ids, dim, stream) leaves it — the same device code runs, with
+ * the same arithmetic and placement rules: the CSR's content per key (tfra_sparse_plan_read) and every write-back through the plan
+ * are bit-identical; where a key's records land inside the plan's buffers differs from run to run, as between two single builds.
+ * Every rule of that call holds per descriptor (dim % 4 == 0, dim <= 256, at most 2^18 ids, ids complete in memory in stream
+ * order, the caller orders build and use).  n == 0: the plan is left empty and takes no blocks.  n_plans == 0: TFRA_OK.
+ * All descriptors are checked BEFORE any plan is touched: if one fails, the call returns the code the single call returns for it
+ * (the message names the descriptor's index, then the single call's text), nothing is enqueued and every plan of the list still
+ * holds its previous build.  Only a descriptor can get these wrong: a wrong struct_size, a plan on another device than ws, or
+ * descs == NULL with n_plans > 0: TFRA_ERR_INVALID; dim == 0 (the assign-only plan is one kernel already): TFRA_ERR_UNSUPPORTED;
+ * the same plan in two descriptors: TFRA_ERR_INVALID, the message names both indices.
+ * Everything that can fail for memory or that synchronises comes before the first enqueue as well: a plan that outgrew its buffer
+ * is reallocated there (hipDeviceSynchronize + hipFree + hipMalloc, as in the single call), and ws takes its size.
+ * Enqueues after that, whatever n_plans: per plan that is new, was reallocated or whose number of merge buckets changed, the
+ * memsets the single call enqueues for it (none in the steady state); one upload of the plans' records (the workspace's ring of
+ * pinned, event-guarded slots, shared with the other grouped calls); one tile launch and one scatter launch over all plans' tiles
+ * (512 ids each) and one merge-bucket launch per pass size present in the list (512, or 1024 for a plan of more than 131072 ids).
+ * *launches_out (optional, host): the kernel launches enqueued = 2 + (pass sizes present): 3 for any list whose plans hold at most
+ * 131072 ids each, 0 when no descriptor has ids.  ws must be a workspace of the stream's own (the ring and the records are its
+ * state): a build on a side stream next to another grouped call on the main stream uses two workspaces.  Not for stream capture. */
+typedef struct { uint32_t struct_size; tfra_sparse_plan_t* plan; size_t n; const int64_t* ids; int dim; } tfra_plan_build_desc;
+int tfra_multi_sparse_plan_build(tfra_workspace_t* ws, size_t n_plans, const tfra_plan_build_desc* descs,
+                                 uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
 
 /* default_partition_fn(PY/dynamic_embedding_variable.py:165-197) + dynamic_partition in one
  * pass: owner[i] = mode 0: (key & 0x7fffffff) % num_shards (CUDA-build branch)

@@ -62,6 +62,7 @@
 #include "tfra_combine_device.h"
 #include "tfra_device.h"
 #include "tfra_host.h"
+#include "tfra_many.h"
 #include "tfra_optim_device.h"
 #include "tfra_plan.h"
 #include "tfra_reduce_device.h"
@@ -72,14 +73,16 @@ using namespace tfra::red;
 namespace {
 
 // ---------------------------------------------------------------------------------------------
+// The three plan kernels' bodies take `blk`, the block's index among the blocks of THIS plan: blockIdx.x in the single build's
+// kernels, blockIdx.x minus the plan's first block in the grouped build's (csr_*_many_kernel), where the duties of "block 0" fall
+// to the first block of each plan.
 // plan kernel 1: per tile of 512 ids.
-__global__ __launch_bounds__(NTA) void csr_tile_kernel(size_t n, const i64* __restrict__ ids, unsigned P, unsigned cm,
-                                                       CsrDesc ds, unsigned* err,
-                                                       unsigned* __restrict__ tile_entries,
-                                                       unsigned short* __restrict__ run_start,
-                                                       unsigned* __restrict__ tile_len, u64* counters) {
+__device__ __forceinline__ void csr_tile_body(const unsigned blk, size_t n, const i64* __restrict__ ids, unsigned P, unsigned cm,
+                                              const CsrDesc ds, unsigned* err, unsigned* __restrict__ tile_entries,
+                                              unsigned short* __restrict__ run_start, unsigned* __restrict__ tile_len,
+                                              u64* counters) {
   // the allocation counters of this build start at zero (the bucket kernel, next on the stream, uses them)
-  if (blockIdx.x == 0 && threadIdx.x <= NSH) counters[(size_t)threadIdx.x * CTR_STRIDE] = 0;
+  if (blk == 0 && threadIdx.x <= NSH) counters[(size_t)threadIdx.x * CTR_STRIDE] = 0;
   constexpr unsigned GCAP = 2048;            // group table: 4x the tile => short probe chains
   constexpr int W = TILE / 32;               // words of a position bitmask
   constexpr int GM = GCAP / W;               // multi-member groups ranked per round (mask area = s_owner)
@@ -91,7 +94,7 @@ __global__ __launch_bounds__(NTA) void csr_tile_kernel(size_t n, const i64* __re
   __shared__ unsigned short s_run[TILE];     // ... and the run (multi-member group) each list entry belongs to
   __shared__ int s_scan[NTA / 64];
   unsigned* const s_mask = s_owner;
-  const size_t tile = blockIdx.x, base = tile * TILE;
+  const size_t tile = blk, base = tile * TILE;
   const int nvalid = (int)min((size_t)TILE, n - base);
   const int p = threadIdx.x;
   const bool ok = p < nvalid;
@@ -152,10 +155,18 @@ __global__ __launch_bounds__(NTA) void csr_tile_kernel(size_t n, const i64* __re
   if (threadIdx.x == 0) tile_len[tile] = (unsigned)L;
 }
 
+__global__ __launch_bounds__(NTA) void csr_tile_kernel(size_t n, const i64* __restrict__ ids, unsigned P, unsigned cm,
+                                                       CsrDesc ds, unsigned* err,
+                                                       unsigned* __restrict__ tile_entries,
+                                                       unsigned short* __restrict__ run_start,
+                                                       unsigned* __restrict__ tile_len, u64* counters) {
+  csr_tile_body(blockIdx.x, n, ids, P, cm, ds, err, tile_entries, run_start, tile_len, counters);
+}
+
 // ---------------------------------------------------------------------------------------------
 // plan kernel 2: per merge bucket.  Dynamic LDS: cm*36 + TABW*4 bytes.
-__global__ __launch_bounds__(NT) void csr_bucket_kernel(unsigned P, unsigned ntiles, unsigned cm, CsrDesc ds,
-                                                        uint4* __restrict__ drec, CsrOut out, unsigned* err) {
+__device__ __forceinline__ void csr_bucket_body(const unsigned blk, unsigned P, unsigned ntiles, unsigned cm, const CsrDesc ds,
+                                                uint4* __restrict__ drec, const CsrOut out, unsigned* err) {
   extern __shared__ unsigned char smem[];
   i64* const e_key = reinterpret_cast<i64*>(smem);            // [cm] descriptors of the pass
   unsigned* const e_ord = reinterpret_cast<unsigned*>(e_key + cm);
@@ -171,7 +182,7 @@ __global__ __launch_bounds__(NT) void csr_bucket_kernel(unsigned P, unsigned nti
   __shared__ unsigned s_nhot, s_nshared, s_hot_ok;
   __shared__ unsigned s_cold_ok;
   __shared__ unsigned sh_ckbase, sh_hkbase, sh_pbase, sh_bbase;
-  const unsigned b = blockIdx.x;
+  const unsigned b = blk;
   const int lane = threadIdx.x & 63, sub = lane & 15, grp = threadIdx.x >> 4, wv = threadIdx.x >> 6;
   const int n_b = (int)ds.cursor[(size_t)b * CSTRIDE];
   if (n_b == 0) return;
@@ -430,6 +441,11 @@ __global__ __launch_bounds__(NT) void csr_bucket_kernel(unsigned P, unsigned nti
   }
 }
 
+__global__ __launch_bounds__(NT) void csr_bucket_kernel(unsigned P, unsigned ntiles, unsigned cm, CsrDesc ds,
+                                                        uint4* __restrict__ drec, CsrOut out, unsigned* err) {
+  csr_bucket_body(blockIdx.x, P, ntiles, cm, ds, drec, out, err);
+}
+
 // plan kernel 3 (the last one): per tile again.
 //  (a) every member of a multi-member run goes to the place csr_bucket_kernel chose for its descriptor:
 //      entry e = e0 + (rank inside the run) of its key;
@@ -438,13 +454,12 @@ __global__ __launch_bounds__(NT) void csr_bucket_kernel(unsigned P, unsigned nti
 //  (c) block 0: publishes the counts (device copy for the kernels of the other half, pinned host copy for the
 //      driver), re-arms the bucket cursors for the next build, latches the errors.
 //   d_counts: [0] keys with many occurrences [1] other keys [2] - [3] bins [4] - [5] errors of the build
-__global__ __launch_bounds__(NTA) void csr_scatter_kernel(const unsigned* __restrict__ tile_entries,
-                                                          const unsigned short* __restrict__ run_start,
-                                                          const unsigned* __restrict__ tile_len,
-                                                          const uint4* __restrict__ drec, CsrOut out,
-                                                          unsigned* __restrict__ keymap, i64* __restrict__ dkeys,
-                                                          unsigned* __restrict__ binmap, unsigned* cursors, unsigned P,
-                                                          unsigned* d_counts, unsigned* host_counts, unsigned gen) {
+__device__ __forceinline__ void csr_scatter_body(const unsigned blk, const unsigned* __restrict__ tile_entries,
+                                                 const unsigned short* __restrict__ run_start,
+                                                 const unsigned* __restrict__ tile_len, const uint4* __restrict__ drec,
+                                                 const CsrOut out, unsigned* __restrict__ keymap, i64* __restrict__ dkeys,
+                                                 unsigned* __restrict__ binmap, unsigned* cursors, unsigned P,
+                                                 unsigned* d_counts, unsigned* host_counts, unsigned gen) {
   __shared__ unsigned s_hpre[NSH + 1], s_cpre[NSH + 1], s_bpre[NSH + 1];
   if (threadIdx.x < 64) {   // wave 0: prefix sums of the shards' counts (clamped to the shard capacities)
     const unsigned sh = threadIdx.x;
@@ -466,7 +481,7 @@ __global__ __launch_bounds__(NTA) void csr_scatter_kernel(const unsigned* __rest
     for (unsigned step = NSH / 2; step > 0; step >>= 1) if (pre[lo + step] <= x) lo += step;
     return lo;
   };
-  const unsigned gid = blockIdx.x * NTA + threadIdx.x;
+  const unsigned gid = blk * NTA + threadIdx.x;
   // dkeys[g] = the key itself: the write-back kernels start the table probe from it while keymap -> record resolves
   if (gid < nhot) {
     const unsigned sh = shard_of(s_hpre, gid), r = sh * out.hr + (gid - s_hpre[sh]);
@@ -482,8 +497,8 @@ __global__ __launch_bounds__(NTA) void csr_scatter_kernel(const unsigned* __rest
     binmap[gid] = sh * out.br + (gid - s_bpre[sh]);
   }
   // (a)
-  const size_t base = (size_t)blockIdx.x * TILE;
-  const int L = (int)tile_len[blockIdx.x];
+  const size_t base = (size_t)blk * TILE;
+  const int L = (int)tile_len[blk];
   const int q = threadIdx.x;
   if (q < L) {
     const unsigned te = tile_entries[base + q];
@@ -505,7 +520,7 @@ __global__ __launch_bounds__(NTA) void csr_scatter_kernel(const unsigned* __rest
   // the finished plan on another stream waits for the build's event (tfra_table_step_prefetch: hipEventQuery on the host), or
   // is ordered behind it by the stream.  (Round 2 treated the pinned generation as "plan complete" — ADVICE r2; a per-block
   // release + ticket here cost the kernel 8 us, the event costs nothing on the critical path.)
-  if (blockIdx.x == 0) {
+  if (blk == 0) {
     __syncthreads();
     for (unsigned i = threadIdx.x; i <= P; i += NTA) cursors[(size_t)i * CSTRIDE] = 0;   // bucket cursors + overflow count
     if (threadIdx.x == 0) {
@@ -520,6 +535,64 @@ __global__ __launch_bounds__(NTA) void csr_scatter_kernel(const unsigned* __rest
       }
     }
   }
+}
+
+__global__ __launch_bounds__(NTA) void csr_scatter_kernel(const unsigned* __restrict__ tile_entries,
+                                                          const unsigned short* __restrict__ run_start,
+                                                          const unsigned* __restrict__ tile_len,
+                                                          const uint4* __restrict__ drec, CsrOut out,
+                                                          unsigned* __restrict__ keymap, i64* __restrict__ dkeys,
+                                                          unsigned* __restrict__ binmap, unsigned* cursors, unsigned P,
+                                                          unsigned* d_counts, unsigned* host_counts, unsigned gen) {
+  csr_scatter_body(blockIdx.x, tile_entries, run_start, tile_len, drec, out, keymap, dkeys, binmap, cursors, P, d_counts, host_counts,
+                   gen);
+}
+
+// ---- the grouped build (tfra_multi_sparse_plan_build): the three kernels over a LIST of plans.  What a single build's kernels take
+// as arguments is a record in device memory; a block finds its plan by many_desc_of (tfra_many.h) — blockIdx.x is wave-uniform, so
+// the search and the record are scalar loads, as kernel arguments are — and runs the single build's body with its index inside the
+// plan.  The kernels are block-per-work-item (a tile, a merge bucket, a tile) and no block waits for another, so plan d's blocks
+// are exactly the single build's blocks: ntiles, P, ntiles.  The bucket launch is one class per cm (its dynamic LDS), reading the
+// records through the class's index.
+struct PlanManyRec {
+  size_t n;
+  const i64* ids;
+  unsigned P, cm, ntiles, gen;
+  CsrDesc ds;
+  CsrOut out;
+  unsigned* err;
+  unsigned* tile_entries;
+  unsigned short* run_start;
+  unsigned* tile_len;
+  uint4* drec;
+  unsigned* keymap;
+  i64* dkeys;
+  unsigned* binmap;
+  unsigned* cursors;
+  unsigned* d_counts;
+  unsigned* host_counts;
+};
+
+__global__ __launch_bounds__(NTA) void csr_tile_many_kernel(const PlanManyRec* __restrict__ recs, const unsigned* __restrict__ prefix,
+                                                            unsigned n) {
+  const unsigned d = many_desc_of(prefix, n, blockIdx.x);
+  const PlanManyRec r = recs[d];
+  csr_tile_body(blockIdx.x - prefix[d], r.n, r.ids, r.P, r.cm, r.ds, r.err, r.tile_entries, r.run_start, r.tile_len, r.out.counters);
+}
+
+__global__ __launch_bounds__(NT) void csr_bucket_many_kernel(const PlanManyRec* __restrict__ recs, const unsigned* __restrict__ prefix,
+                                                             const unsigned* __restrict__ idx, unsigned n) {
+  const unsigned d = many_desc_of(prefix, n, blockIdx.x);
+  const PlanManyRec r = recs[idx[d]];
+  csr_bucket_body(blockIdx.x - prefix[d], r.P, r.ntiles, r.cm, r.ds, r.drec, r.out, r.err);
+}
+
+__global__ __launch_bounds__(NTA) void csr_scatter_many_kernel(const PlanManyRec* __restrict__ recs, const unsigned* __restrict__ prefix,
+                                                               unsigned n) {
+  const unsigned d = many_desc_of(prefix, n, blockIdx.x);
+  const PlanManyRec r = recs[d];
+  csr_scatter_body(blockIdx.x - prefix[d], r.tile_entries, r.run_start, r.tile_len, r.drec, r.out, r.keymap, r.dkeys, r.binmap, r.cursors,
+                   r.P, r.d_counts, r.host_counts, r.gen);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -915,78 +988,112 @@ int tfra::setplan_build(tfra_sparse_plan* pl, size_t n, const int64_t* ids, hipS
 
 void tfra::setplan_fill_empty(void* ent, size_t n, hipStream_t s) { fill_setent_kernel<<<1, 64, 0, s>>>(static_cast<SetEnt*>(ent), n); }
 
-extern "C" int tfra_sparse_plan_build(tfra_sparse_plan_t* pl, size_t n, const int64_t* ids, int dim, tfra_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!pl) return set_error(TFRA_ERR_INVALID, "sparse_plan_build: null plan");
-  const bool skip_counts = pl->skip_counts_once;   // consumed here on EVERY path (an empty batch or an error must not leak it into the next build)
-  pl->skip_counts_once = false;
-  { int cur_ = -1; if (hipGetDevice(&cur_) != hipSuccess || cur_ != pl->device) { if (hipSetDevice(pl->device) != hipSuccess) return set_error(TFRA_ERR_HIP, "sparse_plan_build: hipSetDevice"); } }
-  pl->n = 0;
-  if (n == 0) return TFRA_OK;
-  if (!ids) return set_error(TFRA_ERR_INVALID, "sparse_plan_build: null ids");
-  if (dim == 0) return setplan_build(pl, n, ids, s, !skip_counts);   // assign-only: the last position and the count of every distinct id
-  if (dim < 0 || dim % 4 != 0 || dim > 64 * MAXCH)
-    return set_error(TFRA_ERR_UNSUPPORTED, "sparse_plan_build: needs dim % 4 == 0 and dim <= 256 (dim 0: assign-only plan)");
-  if (n > MAX_IDS) return set_error(TFRA_ERR_UNSUPPORTED, "sparse_plan_build: at most 2^18 ids per plan");
-  const size_t ntiles = (n + TILE - 1) / TILE, npad = ntiles * TILE;
+// The argument checks of a plan build, for the single call and for a descriptor of the grouped one (tfra_multi_sparse_plan_build).
+// active: there are ids.  dim 0 (the SET plan) passes: the single call builds it, the grouped call refuses it at its entry.
+template <class AtEntry>
+static Check check_plan_build(const tfra_sparse_plan* pl, size_t n, const int64_t* ids, int dim, AtEntry&& at_entry) {
+  if (!pl) return refuse(TFRA_ERR_INVALID, "null plan");
+  if (Check e = at_entry(); e.done()) return e;
+  if (n == 0) return nothing_to_do();
+  if (!ids) return refuse(TFRA_ERR_INVALID, "null ids");
+  if (dim != 0 && (dim < 0 || dim % 4 != 0 || dim > 64 * MAXCH))
+    return refuse(TFRA_ERR_UNSUPPORTED, "needs dim % 4 == 0 and dim <= 256 (dim 0: assign-only plan)");
+  if (n > MAX_IDS) return refuse(TFRA_ERR_UNSUPPORTED, "at most 2^18 ids per plan");
+  return Check{};
+}
+
+// The host part of a CSR build, shared by the single and the grouped call, in three steps:
+//   plan_layout   sizes only: tiles, merge buckets, the pass size, the shards' capacities, the buffer's sections;
+//   plan_grow     the buffer, when the layout outgrew it — the ONLY step that can fail for lack of memory or synchronise (a
+//                 replaced buffer is freed behind hipDeviceSynchronize); it enqueues nothing, and a plan whose buffer was
+//                 replaced holds no build;
+//   plan_lay_out  the plan's pointers into its buffer, gen += 1, and the memsets a build needs when the plan is not armed or
+//                 its number of merge buckets changed (cursors, counters, counts) or the left-over flags moved.  In the
+//                 steady state — armed, same layout — it enqueues nothing.
+struct PlanLayout {
+  size_t n, ntiles, npad;
+  unsigned P, cm;
+  int dim;
+  unsigned cr, hr, pr, br;
+  size_t reg, head, ctr, nrec_c, nrec_h, nbin, npart, bytes;
+};
+static size_t al256(size_t x) { return (x + 255) / 256 * 256; }
+
+static PlanLayout plan_layout(size_t n, int dim) {
+  PlanLayout L{};
+  L.n = n; L.dim = dim;
+  L.ntiles = (n + TILE - 1) / TILE; L.npad = L.ntiles * TILE;
+  const size_t ntiles = L.ntiles, npad = L.npad;
   unsigned P = 64;
   while (P < 2048 && (size_t)P * 128 < n) P <<= 1;
-  const unsigned cm = ntiles <= 256 ? 512u : 1024u;   // a key present in every tile must fit one pass with room to spare
-  auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-  const size_t reg = (size_t)P * CMAX;
-  const size_t head = al((size_t)(P + 2) * CSTRIDE * 4);
-  const size_t ctr = al((size_t)(NSH + 1) * CTR_STRIDE * 8);
+  L.P = P;
+  L.cm = ntiles <= 256 ? 512u : 1024u;   // a key present in every tile must fit one pass with room to spare
+  L.reg = (size_t)P * CMAX;
+  L.head = al256((size_t)(P + 2) * CSTRIDE * 4);
+  L.ctr = al256((size_t)(NSH + 1) * CTR_STRIDE * 8);
   // per-shard capacities: twice the fair share + slack; bins / partial rows also cover ONE key holding every id
-  CsrOut& o = pl->out;
-  o.cr = (unsigned)(2 * npad / NSH + 64);
-  o.hr = (unsigned)(2 * (npad / 9) / NSH + 64);
-  o.pr = (unsigned)(npad / SEG + 2 * (npad / 9) / NSH + 64);
-  o.br = (unsigned)(npad / SEG + (npad / 16 + npad / 9) / NSH / 16 + 2 * (P / NSH + 1) + 32);
-  const size_t nrec_c = (size_t)NSH * o.cr, nrec_h = (size_t)NSH * o.hr, nbin = (size_t)NSH * o.br, npart = (size_t)NSH * o.pr;
-  size_t bytes = head + ctr + 256                                               // cursors, counters, d_counts
-                 + al(reg * 8) + al(reg * 4) + al(npad * 8) + 2 * al(npad * 4)  // descriptors + overflow list
-                 + al(npad * 4) + al(npad * 2) + al(ntiles * 4) + al(npad * 16) // tile lists, run starts, lengths, destinations
-                 + al(nrec_c * REC_WORDS * 4) + al(nrec_h * REC_WORDS * 4)      // key records
-                 + al(nbin * SEG * 4) + al(nbin * 32 * 4)                       // bins + run outputs
-                 + al(npad * 4) + al(npad * 8) + al(nbin * 4)                   // keymap, dense keys, binmap
-                 + al(npad) + al((size_t)SLOW_CAP * sizeof(OwnItem))            // deferred flags, left-over item list
-                 + al(npart * 4)                                                // partial row -> destination (route helpers)
-                 + al(npart * (size_t)dim * 4);                                 // partial rows
-  if (pl->bytes < bytes) {
-    if (pl->buf) {
-      if (hipDeviceSynchronize() != hipSuccess || hipFree(pl->buf) != hipSuccess) return set_error(TFRA_ERR_HIP, "sparse_plan_build: free");
-      pl->buf = nullptr; pl->bytes = 0;
-    }
-    hipError_t e = hipMalloc(&pl->buf, bytes);
-    if (e != hipSuccess) { pl->buf = nullptr; return set_error(e == hipErrorOutOfMemory ? TFRA_ERR_OOM : TFRA_ERR_HIP, "sparse_plan_build: hipMalloc"); }
-    pl->bytes = bytes;
-    pl->armed = false;
-    pl->dflag = nullptr;
+  L.cr = (unsigned)(2 * npad / NSH + 64);
+  L.hr = (unsigned)(2 * (npad / 9) / NSH + 64);
+  L.pr = (unsigned)(npad / SEG + 2 * (npad / 9) / NSH + 64);
+  L.br = (unsigned)(npad / SEG + (npad / 16 + npad / 9) / NSH / 16 + 2 * (P / NSH + 1) + 32);
+  L.nrec_c = (size_t)NSH * L.cr; L.nrec_h = (size_t)NSH * L.hr; L.nbin = (size_t)NSH * L.br; L.npart = (size_t)NSH * L.pr;
+  const auto al = al256;
+  L.bytes = L.head + L.ctr + 256                                                       // cursors, counters, d_counts
+            + al(L.reg * 8) + al(L.reg * 4) + al(npad * 8) + 2 * al(npad * 4)          // descriptors + overflow list
+            + al(npad * 4) + al(npad * 2) + al(ntiles * 4) + al(npad * 16)             // tile lists, run starts, lengths, destinations
+            + al(L.nrec_c * REC_WORDS * 4) + al(L.nrec_h * REC_WORDS * 4)              // key records
+            + al(L.nbin * SEG * 4) + al(L.nbin * 32 * 4)                               // bins + run outputs
+            + al(npad * 4) + al(npad * 8) + al(L.nbin * 4)                             // keymap, dense keys, binmap
+            + al(npad) + al((size_t)SLOW_CAP * sizeof(OwnItem))                        // deferred flags, left-over item list
+            + al(L.npart * 4)                                                          // partial row -> destination (route helpers)
+            + al(L.npart * (size_t)dim * 4);                                           // partial rows
+  return L;
+}
+
+static int plan_grow(tfra_sparse_plan* pl, const PlanLayout& L) {
+  if (pl->bytes >= L.bytes) return TFRA_OK;
+  if (pl->buf) {
+    if (hipDeviceSynchronize() != hipSuccess || hipFree(pl->buf) != hipSuccess) return set_error(TFRA_ERR_HIP, "sparse_plan_build: free");
+    pl->buf = nullptr; pl->bytes = 0;
+    if (pl->kind == 0) pl->n = 0;
   }
+  hipError_t e = hipMalloc(&pl->buf, L.bytes);
+  if (e != hipSuccess) { pl->buf = nullptr; return set_error(e == hipErrorOutOfMemory ? TFRA_ERR_OOM : TFRA_ERR_HIP, "sparse_plan_build: hipMalloc"); }
+  pl->bytes = L.bytes;
+  pl->armed = false;
+  pl->dflag = nullptr;
+  return TFRA_OK;
+}
+
+static int plan_lay_out(tfra_sparse_plan* pl, const PlanLayout& L, hipStream_t s) {
+  const auto al = al256;
+  const size_t npad = L.npad;
+  CsrOut& o = pl->out;
+  o.cr = L.cr; o.hr = L.hr; o.pr = L.pr; o.br = L.br;
   unsigned char* w = (unsigned char*)pl->buf;
-  pl->cursors = (unsigned*)w; w += head;
-  o.counters = (u64*)w; w += ctr;
+  pl->cursors = (unsigned*)w; w += L.head;
+  o.counters = (u64*)w; w += L.ctr;
   pl->d_counts = (unsigned*)w; w += 256;
-  const bool same_layout = pl->armed && pl->P == P;
-  if (!same_layout && hipMemsetAsync(pl->buf, 0, head + ctr + 256, s) != hipSuccess)
+  const bool same_layout = pl->armed && pl->P == L.P;
+  if (!same_layout && hipMemsetAsync(pl->buf, 0, L.head + L.ctr + 256, s) != hipSuccess)
     return set_error(TFRA_ERR_HIP, "sparse_plan_build: memset");
   CsrDesc& ds = pl->ds;
-  ds.key = (i64*)w; w += al(reg * 8);
-  ds.ord = (unsigned*)w; w += al(reg * 4);
+  ds.key = (i64*)w; w += al(L.reg * 8);
+  ds.ord = (unsigned*)w; w += al(L.reg * 4);
   ds.ovf_key = (i64*)w; w += al(npad * 8);
   ds.ovf_ord = (unsigned*)w; w += al(npad * 4);
   ds.ovf_bucket = (unsigned*)w; w += al(npad * 4);
   pl->tile_entries = (unsigned*)w; w += al(npad * 4);
   pl->run_start = (unsigned short*)w; w += al(npad * 2);
-  pl->tile_len = (unsigned*)w; w += al(ntiles * 4);
+  pl->tile_len = (unsigned*)w; w += al(L.ntiles * 4);
   pl->drec = (uint4*)w; w += al(npad * 16);
-  o.crec = (unsigned*)w; w += al(nrec_c * REC_WORDS * 4);
-  o.hrec = (unsigned*)w; w += al(nrec_h * REC_WORDS * 4);
-  o.hent = (unsigned*)w; w += al(nbin * SEG * 4);
-  o.hout = (unsigned*)w; w += al(nbin * 32 * 4);
+  o.crec = (unsigned*)w; w += al(L.nrec_c * REC_WORDS * 4);
+  o.hrec = (unsigned*)w; w += al(L.nrec_h * REC_WORDS * 4);
+  o.hent = (unsigned*)w; w += al(L.nbin * SEG * 4);
+  o.hout = (unsigned*)w; w += al(L.nbin * 32 * 4);
   pl->keymap = (unsigned*)w; w += al(npad * 4);
   pl->dkeys = (i64*)w; w += al(npad * 8);
-  pl->binmap = (unsigned*)w; w += al(nbin * 4);
+  pl->binmap = (unsigned*)w; w += al(L.nbin * 4);
   if (pl->dflag != (uint8_t*)w || pl->dflag_len != npad) {   // the left-over flags are all zero between launches (upsert_own_kernel)
     if (hipMemsetAsync(w, 0, al(npad), s) != hipSuccess) return set_error(TFRA_ERR_HIP, "sparse_plan_build: memset");
     pl->dflag_len = npad;
@@ -994,26 +1101,154 @@ extern "C" int tfra_sparse_plan_build(tfra_sparse_plan_t* pl, size_t n, const in
   pl->dflag = (uint8_t*)w; w += al(npad);
   pl->slow_items = (OwnItem*)w; w += al((size_t)SLOW_CAP * sizeof(OwnItem));
   pl->any_deferred = pl->d_counts + 8;
-  pl->prow_dest = (int*)w; w += al(npart * 4);
+  pl->prow_dest = (int*)w; w += al(L.npart * 4);
   pl->partial = (float*)w;
   pl->gen += 1;
   ds.cursor = pl->cursors;
-  ds.ovf_count = pl->cursors + (size_t)P * CSTRIDE;
+  ds.ovf_count = pl->cursors + (size_t)L.P * CSTRIDE;
   ds.ovf_cap = (unsigned)npad;
-  unsigned* err = pl->cursors + (size_t)(P + 1) * CSTRIDE;
-  csr_tile_kernel<<<dim3((unsigned)ntiles), NTA, 0, s>>>(n, (const i64*)ids, P, cm, ds, err, pl->tile_entries, pl->run_start, pl->tile_len, o.counters);
+  return TFRA_OK;
+}
+// the error counter of a plan laid out for L.P merge buckets
+static unsigned* plan_err_word(const tfra_sparse_plan* pl, unsigned P) { return pl->cursors + (size_t)(P + 1) * CSTRIDE; }
+// ... and what the object remembers of a build whose launches were enqueued
+static void plan_built(tfra_sparse_plan* pl, const PlanLayout& L) {
+  pl->n = L.n; pl->npad = L.npad; pl->ntiles = L.ntiles; pl->P = L.P; pl->cm = L.cm; pl->dim = L.dim; pl->kind = 0;
+}
+
+extern "C" int tfra_sparse_plan_build(tfra_sparse_plan_t* pl, size_t n, const int64_t* ids, int dim, tfra_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  bool skip_counts = false;
+  const Check c = check_plan_build(pl, n, ids, dim, [&] {
+    skip_counts = pl->skip_counts_once;   // consumed here on EVERY path (an empty batch or an error must not leak it into the next build)
+    pl->skip_counts_once = false;
+    { int cur_ = -1; if (hipGetDevice(&cur_) != hipSuccess || cur_ != pl->device) { if (hipSetDevice(pl->device) != hipSuccess) return refuse(TFRA_ERR_HIP, "hipSetDevice"); } }
+    pl->n = 0;
+    return Check{};
+  });
+  if (c.code) return report("sparse_plan_build: ", c);
+  if (!c.active) return TFRA_OK;
+  if (dim == 0) return setplan_build(pl, n, ids, s, !skip_counts);   // assign-only: the last position and the count of every distinct id
+  const PlanLayout L = plan_layout(n, dim);
+  int rc = plan_grow(pl, L);
+  if (rc) return rc;
+  if ((rc = plan_lay_out(pl, L, s))) return rc;
+  const CsrDesc& ds = pl->ds;
+  const CsrOut& o = pl->out;
+  unsigned* err = plan_err_word(pl, L.P);
+  csr_tile_kernel<<<dim3((unsigned)L.ntiles), NTA, 0, s>>>(n, (const i64*)ids, L.P, L.cm, ds, err, pl->tile_entries, pl->run_start, pl->tile_len, o.counters);
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(csr_bucket_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)plan_smem_bytes(1024));
     attr_set = true;
   }
-  csr_bucket_kernel<<<dim3(P), NT, plan_smem_bytes(cm), s>>>(P, (unsigned)ntiles, cm, ds, pl->drec, o, err);
-  csr_scatter_kernel<<<dim3((unsigned)ntiles), NTA, 0, s>>>(pl->tile_entries, pl->run_start, pl->tile_len, pl->drec, o, pl->keymap,
-                                                           pl->dkeys, pl->binmap, pl->cursors, P, pl->d_counts, pl->host_counts, pl->gen);
+  csr_bucket_kernel<<<dim3(L.P), NT, plan_smem_bytes(L.cm), s>>>(L.P, (unsigned)L.ntiles, L.cm, ds, pl->drec, o, err);
+  csr_scatter_kernel<<<dim3((unsigned)L.ntiles), NTA, 0, s>>>(pl->tile_entries, pl->run_start, pl->tile_len, pl->drec, o, pl->keymap,
+                                                             pl->dkeys, pl->binmap, pl->cursors, L.P, pl->d_counts, pl->host_counts, pl->gen);
   pl->armed = true;
   if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "sparse_plan_build: launch failed");
-  pl->n = n; pl->npad = npad; pl->ntiles = ntiles; pl->P = P; pl->cm = cm; pl->dim = dim; pl->kind = 0;
+  plan_built(pl, L);
+  return TFRA_OK;
+}
+
+// tfra_multi_sparse_plan_build: the CSR builds of a LIST of plans with launches that do not grow with the list (the frame of
+// tfra_many.h: check every descriptor, classify, lay out, fill one blob, send it, launch).  Everything that can fail for an
+// argument or for memory, or that synchronises — the checks of ALL descriptors, every plan's buffer (plan_grow), the workspace and
+// its staging slot (many_begin) — comes before the first enqueue.
+namespace {
+Check check_plan_desc(const tfra_plan_build_desc& d, const tfra_workspace* ws) {
+  if (d.struct_size != sizeof(tfra_plan_build_desc)) return refuse(TFRA_ERR_INVALID, "descriptor size mismatch");
+  return check_plan_build(d.plan, d.n, d.ids, d.dim, [&] {
+    if (d.plan->device != ws->device) return refuse(TFRA_ERR_INVALID, "workspace and plan live on different devices");
+    if (d.dim == 0) return refuse(TFRA_ERR_UNSUPPORTED, "the assign-only plan (dim 0) is one kernel already and is not grouped");
+    return Check{};
+  });
+}
+}  // namespace
+
+extern "C" int tfra_multi_sparse_plan_build(tfra_workspace_t* ws, size_t n_plans, const tfra_plan_build_desc* descs,
+                                            uint32_t* launches_out, tfra_stream_t stream) {
+  if (launches_out) *launches_out = 0;
+  if (n_plans == 0) return TFRA_OK;
+  if (!ws || !descs) return set_error(TFRA_ERR_INVALID, "multi_sparse_plan_build: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  const std::string who = "multi_sparse_plan_build: descriptor ";
+  // every descriptor is checked before any plan is touched
+  std::vector<size_t> act;   // the descriptors with ids, in input order: record k belongs to descs[act[k]]
+  for (size_t i = 0; i < n_plans; ++i) {
+    const Check c = check_plan_desc(descs[i], ws);
+    if (c.code) return report(who + std::to_string(i) + ": ", c);
+    if (c.active) act.push_back(i);
+  }
+  for (size_t i = 0; i < n_plans; ++i)   // a plan object holds ONE build
+    for (size_t j = i + 1; j < n_plans; ++j)
+      if (descs[i].plan == descs[j].plan)
+        return set_error(TFRA_ERR_INVALID, who + std::to_string(i) + " and descriptor " + std::to_string(j) + " name the same plan");
+  { int cur_ = -1; if (hipGetDevice(&cur_) != hipSuccess || cur_ != ws->device) { if (hipSetDevice(ws->device) != hipSuccess) return set_error(TFRA_ERR_HIP, "multi_sparse_plan_build: hipSetDevice"); } }
+  const size_t n_act = act.size();
+  std::vector<PlanLayout> lay(n_act);
+  u64 tile_blocks = 0, bucket_blocks = 0;
+  for (size_t k = 0; k < n_act; ++k) {
+    lay[k] = plan_layout(descs[act[k]].n, descs[act[k]].dim);
+    tile_blocks += lay[k].ntiles;
+    bucket_blocks += lay[k].P;
+  }
+  if (tile_blocks >= (1ULL << 31) || bucket_blocks >= (1ULL << 31))
+    return set_error(TFRA_ERR_UNSUPPORTED, "multi_sparse_plan_build: too many ids in one call");
+  int rc;
+  for (size_t k = 0; k < n_act; ++k)
+    if ((rc = plan_grow(descs[act[k]].plan, lay[k]))) return rc;
+  // the blob: [records | unsigned pool: the tiles' prefix (the tile and the scatter launch), then per cm class its prefix and its
+  // record indices]
+  Blob blob;
+  const size_t rec_off = blob.add<PlanManyRec>(n_act);
+  const size_t pool_off = blob.add<unsigned>(ClassPool::words(n_act, 1, false) + ClassPool::words(n_act, 2, true));
+  ManyUpload up;
+  if (n_act && (rc = many_begin(ws, 0, blob.bytes(), s, &up))) return rc;
+  // from here on the call enqueues.  As in the single call, a plan holds no build until its launches are enqueued, and a public
+  // build always counts
+  for (size_t i = 0; i < n_plans; ++i) { descs[i].plan->skip_counts_once = false; descs[i].plan->n = 0; }
+  if (n_act == 0) return TFRA_OK;
+  PlanManyRec* recs = section<PlanManyRec>(up.host, rec_off);
+  for (size_t k = 0; k < n_act; ++k) {
+    const tfra_plan_build_desc& d = descs[act[k]];
+    tfra_sparse_plan* pl = d.plan;
+    const PlanLayout& L = lay[k];
+    if ((rc = plan_lay_out(pl, L, s))) return rc;
+    recs[k] = PlanManyRec{L.n, (const i64*)d.ids, L.P, L.cm, (unsigned)L.ntiles, pl->gen, pl->ds, pl->out, plan_err_word(pl, L.P),
+                          pl->tile_entries, pl->run_start, pl->tile_len, pl->drec, pl->keymap, pl->dkeys, pl->binmap, pl->cursors,
+                          pl->d_counts, pl->host_counts};
+  }
+  ClassPool pool{section<unsigned>(up.host, pool_off)};
+  const ManyClass tile_cls = pool.put(n_act, false, [](size_t) { return true; }, [&](size_t k) { return (unsigned)lay[k].ntiles; });
+  ManyClass bucket_cls[2];   // cm 512 | 1024: the bucket kernel's dynamic LDS
+  for (int c = 0; c < 2; ++c)
+    bucket_cls[c] = pool.put(n_act, true, [&](size_t k) { return lay[k].cm == (c ? 1024u : 512u); }, [&](size_t k) { return lay[k].P; });
+  if ((rc = many_send(up, s, "multi_sparse_plan_build: record upload", false))) return rc;
+  const PlanManyRec* d_recs = section<const PlanManyRec>(up.dev, rec_off);
+  const unsigned* d_pool = section<const unsigned>(up.dev, pool_off);
+  uint32_t launches = 0;
+  csr_tile_many_kernel<<<tile_cls.grid, NTA, 0, s>>>(d_recs, d_pool + tile_cls.at, (unsigned)n_act);
+  ++launches;
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(csr_bucket_many_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)plan_smem_bytes(1024));
+    attr_set = true;
+  }
+  for (int c = 0; c < 2; ++c) {
+    const ManyClass& k = bucket_cls[c];
+    if (!k.n) continue;
+    csr_bucket_many_kernel<<<k.grid, NT, plan_smem_bytes(c ? 1024u : 512u), s>>>(d_recs, d_pool + k.at, d_pool + k.at + k.n + 1, k.n);
+    ++launches;
+  }
+  csr_scatter_many_kernel<<<tile_cls.grid, NTA, 0, s>>>(d_recs, d_pool + tile_cls.at, (unsigned)n_act);
+  ++launches;
+  for (size_t k = 0; k < n_act; ++k) descs[act[k]].plan->armed = true;
+  if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "multi_sparse_plan_build: launch failed");
+  for (size_t k = 0; k < n_act; ++k) plan_built(descs[act[k]].plan, lay[k]);
+  if (launches_out) *launches_out = launches;
   return TFRA_OK;
 }
 

@@ -88,6 +88,14 @@ class ApplyCombinedDesc(ctypes.Structure):
   ]
 
 
+class PlanBuildDesc(ctypes.Structure):
+  """tfra_plan_build_desc (include/tfra_mi355x.h): one plan's build in tfra_multi_sparse_plan_build."""
+  _fields_ = [
+      ("struct_size", ctypes.c_uint32), ("plan", ctypes.c_void_p), ("n", ctypes.c_size_t), ("ids", ctypes.c_void_p),
+      ("dim", ctypes.c_int),
+  ]
+
+
 class OverlapStep(ctypes.Structure):
   """tfra_overlap_step (include/tfra_mi355x.h): one step of tfra_table_steps_overlap."""
   _fields_ = [
@@ -170,6 +178,7 @@ _SIGS = {
     "tfra_table_find_combine": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, _P, _P],
     "tfra_multi_find_combine": [_P, _SZ, _P, _P, _P],
     "tfra_multi_apply_planned_combined": [_P, _SZ, _P, _P, _P],
+    "tfra_multi_sparse_plan_build": [_P, _SZ, _P, _P, _P],
     "tfra_segment_sum": [_P, _SZ, _I, _P, _P, _P, _SZ, _P, _P],
     "tfra_gather_rows": [_SZ, _SZ, _P, _P, _P, _P],
     "tfra_keys_widen_i32": [_SZ, _P, _P, _P],

@@ -315,10 +315,12 @@ class DynamicEmbeddingOptimizer:
     returns: one global step for all pairs, and every pair that takes the fused write-back there (one shard, float32 / float16 /
     bfloat16 rows, a fused rule, a plannable batch) joins the group of its device, which is written back by ONE C call
     (`table_ops.apply_planned_combined_many`: tfra_multi_apply_planned_combined, whose launch count does not grow with the list).
+    The group's pairs that arrive without a plan get theirs (pool or fresh) from ONE grouped build just before that call
+    (`table_ops.build_plans_many`: tfra_multi_sparse_plan_build); one such pair keeps the single build.
     Every other pair takes `apply_combined_gradients`' path for it.  A variable that occurs a second time closes the current
     groups first, so the order of the write-backs of one variable is the list's.  Tables and slots end bit-identical to
     `apply_combined_gradients` over the same list."""
-    from .table_ops import SparsePlan, apply_planned_combined_many
+    from .table_ops import SparsePlan, apply_planned_combined_many, build_plans_many
     from .variable import _pool_plan, _release_plan
     pairs = []
     for grad_out, tw in grads_and_vars:
@@ -331,6 +333,7 @@ class DynamicEmbeddingOptimizer:
       pairs.append((tw.check_grad_out(grad_out), tw))
     p = self.begin_step()
     groups, seen = {}, set()   # device -> [(var, plan, pooled, request)]; the variables written since the last flush
+    unbuilt = {}               # device -> [(plan, entry ids)]: the group's pairs that arrived without a plan
 
     def release(members):
       for var, plan, pooled, _ in members:
@@ -340,8 +343,13 @@ class DynamicEmbeddingOptimizer:
     def flush():
       seen.clear()
       while groups:
-        _, members = groups.popitem()
+        device, members = groups.popitem()
         try:
+          todo = unbuilt.pop(device, [])
+          if len(todo) == 1:
+            todo[0][0].build(todo[0][1])
+          elif todo:   # one grouped build in front of the grouped write-back, on the same stream
+            build_plans_many([b[0] for b in todo], [b[1] for b in todo])
           apply_planned_combined_many([m[3] for m in members], p)
         finally:
           release(members)
@@ -367,7 +375,7 @@ class DynamicEmbeddingOptimizer:
           plan = _pool_plan(var)
           if plan is None:
             plan, pooled = SparsePlan(var._primary, var.dim), False
-          plan.build(tw.entry_ids)
+          unbuilt.setdefault(var._tables[0]._device, []).append((plan, tw.entry_ids))
         t = var._tables[0]
         groups.setdefault(t._device, []).append(
             (var, plan, pooled, (t._table, plan, g, tw.seg, tw.weights, device_ops.COMBINERS[tw.combiner],
@@ -378,6 +386,7 @@ class DynamicEmbeddingOptimizer:
     finally:
       for members in groups.values():   # (only after an exception: their plans go back to their pools)
         release(members)
+      unbuilt.clear()
 
   def _apply_generic(self, var, ids, grad):
     """The reference's write-back sequence for an arbitrary rule (`Generic`)."""

@@ -909,3 +909,45 @@ def apply_planned_combined_many(requests, p_list, sync=True):
     for plan in plans:
       plan._mark_used(stream)
   return int(launches.value)
+
+
+def build_plans_many(plans, ids_list, return_launches=False):
+  """The builds of a list of `SparsePlan`s in ONE C call (tfra_multi_sparse_plan_build), on the CURRENT stream of the plans'
+  device: plan i ends as `plans[i].build(ids_list[i])` leaves it — the same CSR per key, bit-identical write-backs through it.
+  Around the call each plan gets what `SparsePlan.build` does for it: the ids as a contiguous int64 tensor kept alive on the plan,
+  the wait for the plan's last use, `record_stream`, and the `_built` event behind the call.  All plans live on one device, have a
+  dim > 0 (the assign-only plan is one kernel already) and occur once.  The call's workspace is `device_ops._workspace(device)`,
+  which is keyed by the current stream: a build on a side stream has a workspace of its own and never shares the staging ring or
+  the scratch of the main stream's grouped calls (`find_combine_many`, `apply_planned_combined_many`), which may be in flight at
+  the same time.  Returns the plans (with return_launches: also the number of kernel launches the call enqueued — it does not grow
+  with the list)."""
+  from .device_ops import _workspace
+  plans = list(plans)
+  n = len(plans)
+  if len(ids_list) != n:
+    raise ValueError("build_plans_many: %d plans but %d id tensors" % (n, len(ids_list)))
+  if n == 0:
+    return (plans, 0) if return_launches else plans
+  device = plans[0]._device
+  for plan in plans:
+    if plan._device != device:
+      raise ValueError("build_plans_many: all plans must live on one device (%s and %s)" % (device, plan._device))
+  stream = torch.cuda.current_stream(device)
+  descs = (_capi.PlanBuildDesc * n)()
+  flat = []
+  for i, (plan, ids) in enumerate(zip(plans, ids_list)):
+    ids = ids.to(device, torch.int64).contiguous().reshape(-1)
+    if plan._used is not None:
+      stream.wait_event(plan._used)     # the previous batch's sums/apply still read the plan buffers
+    ids.record_stream(stream)
+    flat.append(ids)
+    e = descs[i]
+    e.struct_size = ctypes.sizeof(_capi.PlanBuildDesc)
+    e.plan, e.n, e.ids, e.dim = plan._h.value, ids.numel(), (ids.data_ptr() if ids.numel() else None), plan._dim
+  launches = ctypes.c_uint32(0)
+  _capi.call("tfra_multi_sparse_plan_build", _workspace(device), n, ctypes.c_void_p(ctypes.addressof(descs)),
+             ctypes.c_void_p(ctypes.addressof(launches)), _stream(device))
+  for plan, ids in zip(plans, flat):
+    plan.ids, plan.n = ids, ids.numel()   # keeps the ids alive until the next build
+    plan._built.record(stream)
+  return (plans, int(launches.value)) if return_launches else plans

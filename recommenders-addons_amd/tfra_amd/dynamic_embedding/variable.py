@@ -412,10 +412,7 @@ def _plan_at_lookup(params, ids):
   keeps them in the TrainableWrapper, PY/embedding_weights.py:38-120) and the plan needs nothing else, so it builds while
   the lookup, the model's forward and backward run — no look-ahead into the next batch is needed.  Returns None when
   the write-back of this variable / batch is not the planned one."""
-  from .optimizer import DynamicEmbeddingOptimizer
-  from .table_ops import SparsePlan
-  n = ids.numel()
-  if n < PLAN_AT_LOOKUP_MIN_IDS or params.bp_v2 or not DynamicEmbeddingOptimizer.can_plan(params, n) or not ids.is_cuda:
+  if not _wants_plan_at_lookup(params, ids):
     return None
   plan = _pool_plan(params)
   if plan is None:
@@ -428,6 +425,47 @@ def _plan_at_lookup(params, ids):
   with torch.cuda.stream(side):
     plan.build(ids)
   return plan
+
+
+def _wants_plan_at_lookup(params, ids):
+  """Whether the write-back of `ids` into this variable is the planned one and the batch is worth a plan built at lookup time."""
+  from .optimizer import DynamicEmbeddingOptimizer
+  n = ids.numel()
+  return not (n < PLAN_AT_LOOKUP_MIN_IDS or params.bp_v2 or not DynamicEmbeddingOptimizer.can_plan(params, n) or not ids.is_cuda)
+
+
+_GROUP_PLAN_STREAMS = {}   # device -> the side stream of the grouped lookups' plan builds
+
+
+def _plans_at_lookup_many(device, members):
+  """`_plan_at_lookup` for the grouped members of one device (`members`: [(i, params, entry ids)]): the same eligibility rule per
+  variable, a plan from each variable's own pool, and ONE grouped build (`table_ops.build_plans_many`) on ONE side stream of the
+  device, which waits for the current stream once — instead of one side stream, one wait and three launches per variable.
+  Returns {i: plan} for the members that got a plan, or None when at most one member is eligible: a group of one keeps
+  `_plan_at_lookup` on that variable's own stream."""
+  from . import table_ops
+  want = [m for m in members if _wants_plan_at_lookup(m[1], m[2])]
+  if len(want) < 2:
+    return None
+  got = []
+  for i, params, ids in want:
+    plan = _pool_plan(params)
+    if plan is not None:   # (None: more lookups in flight than plans, this one takes the one-call write-back)
+      got.append((i, params, ids, plan))
+  if not got:
+    return {}
+  side = _GROUP_PLAN_STREAMS.get(device)
+  if side is None:
+    side = _GROUP_PLAN_STREAMS[device] = torch.cuda.Stream(device=device)
+  side.wait_stream(torch.cuda.current_stream(device))   # the ids may still be being produced
+  try:
+    with torch.cuda.stream(side):
+      table_ops.build_plans_many([g[3] for g in got], [g[2] for g in got])
+  except Exception:
+    for _, params, _, plan in got:
+      _release_plan(params, plan)
+    raise
+  return {i: plan for i, _, _, plan in got}
 
 
 def _pool_plan(params):
@@ -524,7 +562,9 @@ class SparseTrainableWrapper(TrainableWrapper):
   _LAZY = ("ids", "_idx", "_n_unique", "exists", "_values")
 
   def __init__(self, params, ids, idx, n_unique, seg, weights, combiner, n_rows, out_shape, entry_ids, entry_seg,
-               entry_weights, max_norm=None, plan_writeback=False, lookup_ids=None):
+               entry_weights, max_norm=None, plan_writeback=False, lookup_ids=None, entry_plan=None):
+    """entry_plan: a plan over `entry_ids` whose build is already enqueued (the grouped lookup starts its members' plans in one
+    call); the wrapper owns it from here on, as one made with plan_writeback."""
     if lookup_ids is None:
       super().__init__(params, ids, max_norm=max_norm)
       self._idx, self._n_unique = idx, n_unique
@@ -536,7 +576,7 @@ class SparseTrainableWrapper(TrainableWrapper):
     self.out_shape = tuple(out_shape)
     self._seg, self._weights = seg, weights   # the lookup's own entries (grad_of)
     self.entry_ids, self.seg, self.weights = entry_ids, entry_seg, entry_weights
-    self.entry_plan = _plan_at_lookup(params, entry_ids) if plan_writeback else None
+    self.entry_plan = entry_plan if entry_plan is not None else (_plan_at_lookup(params, entry_ids) if plan_writeback else None)
 
   def __getattr__(self, name):   # only reached for attributes not set yet
     if name in SparseTrainableWrapper._LAZY and self.__dict__.get("_lookup_ids") is not None:
@@ -671,7 +711,9 @@ def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None,
   the (result, SparseTrainableWrapper) pair, the wrapper built behind the pooled forward.  `combiner` and `num_rows` are scalars
   or per-table lists.  The variables the pooled forward serves (`_pooled_forward`) are read by ONE grouped call per device
   (`table_ops.find_combine_many`: tfra_multi_find_combine, whose launch count does not grow with the list); every other variable
-  takes `embedding_lookup_sparse` as it is, so no list is refused.  Where num_rows is absent, the grouped variables' row counts
+  takes `embedding_lookup_sparse` as it is, so no list is refused.  With return_trainable and plan_writeback the grouped members
+  that a single lookup would give a plan (`_plan_at_lookup`'s rule, per variable) get theirs from ONE grouped build per device on
+  one side stream (`_plans_at_lookup_many`: tfra_multi_sparse_plan_build).  Where num_rows is absent, the grouped variables' row counts
   come from one host read per device, not one per table."""
   from . import table_ops
   n_t = len(params_list)
@@ -709,15 +751,22 @@ def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None,
       t = params_list[i]._tables[0]
       reqs.append((t._table, ids.reshape(-1), seg, w, device_ops.COMBINERS[combiners[i]], rows[i], t._default_value))
     outs = table_ops.find_combine_many(reqs)
-    for (i, ids, seg, w), out in zip(members, outs):
-      if not return_trainable:
+    if not return_trainable:
+      for (i, ids, seg, w), out in zip(members, outs):
         results[i] = out
-        continue
+      continue
+    ent = {i: (entries[i] if entries[i] is not None else (ids.reshape(-1), seg, w))   # ids keep their key dtype
+           for i, ids, seg, w in members}
+    # the members' write-back plans: one grouped build on one side stream (None: at most one member takes a plan, and its wrapper
+    # starts it as the single lookup does)
+    started = _plans_at_lookup_many(device, [(i, params_list[i], ent[i][0]) for i, _, _, _ in members]) if plan_writeback else None
+    for (i, ids, seg, w), out in zip(members, outs):
       params, n = params_list[i], rows[i]
-      e_ids, e_seg, e_w = entries[i] if entries[i] is not None else (ids.reshape(-1), seg, w)   # ids keep their key dtype
+      e_ids, e_seg, e_w = ent[i]
       tw = SparseTrainableWrapper(params, None, None, None, seg, w, combiners[i], n,
                                   shapes[i] if shapes[i] is not None else (n, params.dim), e_ids, e_seg, e_w,
-                                  max_norm=max_norm, plan_writeback=plan_writeback, lookup_ids=ids)
+                                  max_norm=max_norm, plan_writeback=plan_writeback and started is None, lookup_ids=ids,
+                                  entry_plan=None if started is None else started.get(i))
       results[i] = (out, tw)
   return results
 
