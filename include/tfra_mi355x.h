@@ -558,6 +558,53 @@ typedef struct {
 int tfra_multi_find_combine(tfra_workspace_t* ws, size_t n_tables, const tfra_find_combine_desc* descs,
                             uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
 
+/* The pooled lookup over a rank-2 RaggedTensor (PY/ragged_embedding_ops.py:129-260, embedding_lookup_sparse) with the semantics of
+ * its safe form (PY/ragged_embedding_ops.py:263-442, safe_embedding_lookup_sparse) on request: row r combines the entries
+ * [row_splits[r], row_splits[r + 1]) of ids / weights, in input order, as tfra_table_find_combine combines the entries with
+ * seg == r — the same device code, so the result is bit-identical to that call on the row ids the splits stand for.
+ * row_splits: int64 [n_rows + 1] on the device, 8-byte aligned.  Its CONTENT is not validated (that would need a host read):
+ * the kernel uses b = clamp(row_splits[r], 0, nnz), e = clamp(row_splits[r + 1], b, nnz), so a negative, decreasing or too large
+ * value gives an empty or shortened row and never a read outside ids / weights.
+ * flags:
+ *   TFRA_RAGGED_PRUNE  (:414-416; ignored when weights == NULL) an entry is a member of its row only if weights[p] > 0 — a NaN
+ *                      weight is no member, as under math_ops.greater.  The weight sum and the accumulation run over the members
+ *                      only, in entry order: the bits are those of the compacted list.  Ids are never pruned.
+ *   TFRA_RAGGED_FILL   (:417-440) a row without members is the row stored under fill_id (any int64, the reserved key values
+ *                      included), default_row on a miss, up-cast to float32 and written as it is (a -0.0 survives).
+ *                      Without the flag such a row is zeros.
+ * ONE kernel launch and nothing else (no workspace, no memset, no bounds launch); nnz == 0 without FILL is one memset of out,
+ * with FILL the kernel runs and every row is the fill row.  The limits of tfra_table_find_combine hold (float32 / float16 /
+ * bfloat16, dim % 4 == 0, dim <= 256, out and default_row 16-byte aligned, nnz < 2^31, n_rows < 2^30: TFRA_ERR_UNSUPPORTED);
+ * unknown flag bits, a NULL row_splits with n_rows > 0: TFRA_ERR_INVALID.  n_rows == 0: TFRA_OK, nothing written.  Never inserts. */
+#define TFRA_RAGGED_PRUNE 1u
+#define TFRA_RAGGED_FILL  2u
+int tfra_table_find_combine_ragged(tfra_table_t* t, size_t n_rows, const int64_t* row_splits, size_t nnz,
+                                   const int64_t* ids, const float* weights, int combiner, uint32_t flags,
+                                   int64_t fill_id, const void* default_row, float* out, tfra_stream_t stream);
+
+/* The ragged pooled lookups of MANY tables in one call (the multi-hot features of a many-table model: the Keras layers call
+ * PY/ragged_embedding_ops.py:263-442 once per feature): descs[i].out is bit-identical to tfra_table_find_combine_ragged of the
+ * descriptor's fields — the same device code runs — and every rule of that call holds per descriptor.  n_rows == 0: the
+ * descriptor is skipped.  n_tables == 0: TFRA_OK.  The same table may appear in several descriptors.
+ * All descriptors are checked BEFORE anything is enqueued: if one fails, the call returns the code the single call returns for it
+ * (the message names the descriptor's index) and no out of any descriptor is written.  A wrong struct_size, a non-zero
+ * `reserved`, a table on another device than ws, or descs == NULL with n_tables > 0: TFRA_ERR_INVALID.
+ * Locks, the tables' storage and the upload are those of tfra_multi_find_combine (shared ring of pinned slots in ws).
+ * Enqueues, whatever n_tables: one upload of the descriptors' records and one launch per (value dtype, NCH, safe-or-not) class
+ * in the list — safe: the descriptor's flags change something (FILL, or PRUNE with weights) — at most 18; no memset, no bounds
+ * launch.  *launches_out (optional, host): the kernel launches enqueued.  Not for stream capture. */
+typedef struct {
+  uint32_t struct_size;      /* = sizeof(tfra_find_combine_ragged_desc) */
+  int32_t  combiner;         /* 0 sum | 1 mean | 2 sqrtn */
+  tfra_table_t* table;
+  size_t n_rows; const int64_t* row_splits;                                   /* [n_rows + 1] */
+  size_t nnz; const int64_t* ids; const float* weights;                       /* weights may be NULL */
+  uint32_t flags; uint32_t reserved;                                          /* TFRA_RAGGED_*; reserved = 0 */
+  int64_t fill_id; const void* default_row; float* out;                       /* out [n_rows, table dim] float32 */
+} tfra_find_combine_ragged_desc;
+int tfra_multi_find_combine_ragged(tfra_workspace_t* ws, size_t n_tables, const tfra_find_combine_ragged_desc* descs,
+                                   uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
+
 /* The combined write-backs of MANY tables in one call (a 26-table model's backward is 26 tfra_table_apply_planned_combined calls =
  * ~160 enqueues otherwise): table i ends bit-identical to tfra_table_apply_planned_combined(table, opt, plan, grad_out, seg,
  * weights, combiner, n_rows, param_default_row, stream) — the same device code runs — and every rule of that call holds per

@@ -36,6 +36,14 @@ __device__ __forceinline__ float comb_wsum(const float* __restrict__ w, int b, i
   return s;
 }
 
+// comb_wsum over the members that safe_embedding_lookup_sparse keeps (PY/dynamic_embedding_ops.py:374-376, `_prune_invalid_weights`:
+// weight > 0, so a NaN weight is no member), in input order: the sum comb_wsum gives for the compacted list, bit for bit.  w != NULL.
+__device__ __forceinline__ float comb_wsum_pruned(const float* __restrict__ w, int b, int e, int combiner) {
+  float s = 0.f;
+  for (int p = b; p < e; ++p) { const float x = w[p]; if (x > 0.f) s += combiner == 2 ? x * x : x; }
+  return s;
+}
+
 // den_r over the row's members [b, e)
 __device__ __forceinline__ float comb_den(const float* __restrict__ w, int b, int e, int combiner) {
   if (combiner == 0) return 1.f;

@@ -9,6 +9,9 @@
 // compiles, in the same order, so the result equals tfra_table_find + tfra_sparse_segment_combine bit for bit.
 // tfra_multi_find_combine is the same lookup for a list of tables; its host side stands on the grouped-call frame of tfra_many.h,
 // and both calls run ONE function for their argument checks (check_find_combine) and one launch ladder (with_pool_class).
+// tfra_table_find_combine_ragged / tfra_multi_find_combine_ragged are the two calls over a rank-2 RaggedTensor (PY/ragged_embedding_ops.py:
+// 129-442): the row's entry range comes from row_splits, so ONE launch serves a call, and safe_embedding_lookup_sparse's pruning by
+// weight and its default_id run inside that launch (find_combine_row's RAGGED and SAFE axes; check_find_combine_ragged, with_ragged_class).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -63,19 +66,50 @@ template <> struct PoolRow<TFRA_BF16> {
 // Accumulation is strictly in entry order.  Loads stay unconditional, as in find_wave: entries past the row's end are clamped to
 // its last entry (probed and read again, not accumulated), columns past dim to column 0.
 // The probe is find_kernel's (probe_find_word: plain loads), so a lookup that runs beside a write-back sees what tfra_table_find sees.
-// The body is one function with two callers — find_combine_kernel (one table per launch) and find_combine_many_kernel (a list of
-// tables per launch) — so that both compile the same expressions: r is the output row of this lane's group in ITS table.
-template <int DT, int U, int NCH>
+// The body is one function with four callers — find_combine_kernel (one table per launch), find_combine_many_kernel (a list of
+// tables per launch) and their ragged forms below — so that all compile the same expressions: r is the output row of this lane's
+// group in ITS table.
+// Two compile-time axes beside (DT, U, NCH):
+//   RAGGED  where [b, e) comes from: the start_end ints of the bounds launch, or an int64 row_splits[n_rows + 1] (a rank-2
+//           RaggedTensor's, PY/ragged_embedding_ops.py:129-442) clamped to 0 <= b <= e <= nnz — whatever row_splits holds, no
+//           entry outside [0, nnz) is read.
+//   SAFE    safe_embedding_lookup_sparse's semantics (PY/ragged_embedding_ops.py:414-440), by rg.flags:
+//           TFRA_RAGGED_PRUNE (with weights): only the entries with weight > 0 are members — the weight sum and the accumulation
+//           run over them, in entry order, as over the compacted list; a pruned entry is still probed and read (loads stay
+//           unconditional), like an entry past the row's end;
+//           TFRA_RAGGED_FILL: a row without members is the row of rg.fill_id (default_row on a miss), up-cast and written AS IT IS
+//           (no acc += 1 * x, no scaling: a -0.0 survives).
+// Without RAGGED and SAFE the function is the one it was: `rg` is not read.
+struct RaggedArgs {
+  const i64* row_splits;
+  int nnz;
+  unsigned flags;
+  i64 fill_id;
+};
+template <int DT, int U, int NCH, bool RAGGED = false, bool SAFE = false>
 __device__ __forceinline__ void find_combine_row(const TableView& v, size_t n_rows, int dim, const i64* __restrict__ ids,
                                                  const float* __restrict__ w, const int* __restrict__ start_end, int combiner,
-                                                 const unsigned char* __restrict__ default_row, float* __restrict__ out, size_t r) {
+                                                 const unsigned char* __restrict__ default_row, float* __restrict__ out, size_t r,
+                                                 const RaggedArgs& rg = RaggedArgs{}) {
   static_assert(U == 4, "keep_live is written for U == 4");
   typedef typename PoolRow<DT>::Raw Raw;
   constexpr unsigned EB = DT == TFRA_F32 ? 4u : 2u;   // bytes per element
   const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
   if (r >= n_rows) return;
-  const int b = start_end[r], e = start_end[n_rows + r];
-  const float wsum = combiner == 0 ? 0.f : comb_wsum(w, b, e, combiner);
+  int b, e;
+  if constexpr (RAGGED) {
+    const i64 lo = rg.row_splits[r], hi = rg.row_splits[r + 1];
+    b = (int)min(max(lo, (i64)0), (i64)rg.nnz);
+    e = (int)min(max(hi, (i64)b), (i64)rg.nnz);
+  } else {
+    b = start_end[r];
+    e = start_end[n_rows + r];
+  }
+  bool prune = false, any = false;   // (SAFE only) any: the row has a member
+  if constexpr (SAFE) prune = (rg.flags & TFRA_RAGGED_PRUNE) && w;
+  float wsum;
+  if constexpr (SAFE) wsum = combiner == 0 ? 0.f : (prune ? comb_wsum_pruned(w, b, e, combiner) : comb_wsum(w, b, e, combiner));
+  else wsum = combiner == 0 ? 0.f : comb_wsum(w, b, e, combiner);
   const float scale = comb_scale_of(wsum, combiner);
   unsigned coff[NCH];   // this lane's byte offset inside a row, per chunk
   bool cok[NCH];
@@ -132,7 +166,12 @@ __device__ __forceinline__ void find_combine_row(const TableView& v, size_t n_ro
         for (int c = 0; c < NCH; ++c) keep_live(t[c][0], t[c][1], t[c][2], t[c][3]);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-          if (p0 + q + u < e) {
+          bool member = p0 + q + u < e;
+          if constexpr (SAFE) {
+            member = member && (!prune || x[u] > 0.f);
+            any = any || member;
+          }
+          if (member) {
 #pragma unroll
             for (int c = 0; c < NCH; ++c) comb_acc4(acc[c], PoolRow<DT>::widen(t[c][u]), x[u]);
           }
@@ -141,6 +180,19 @@ __device__ __forceinline__ void find_combine_row(const TableView& v, size_t n_ro
     }
   }
   float* o = out + r * (size_t)dim;
+  if constexpr (SAFE) {
+    if ((rg.flags & TFRA_RAGGED_FILL) && !any) {   // (uniform in the group: every lane saw the same members)
+      u64 h;
+      const unsigned f0 = (unsigned)bucket0(rg.fill_id, v.nb, h);
+      const unsigned f1 = (unsigned)bucket1(h, f0, v.nb);
+      const i64 word = probe_find_word(v, rg.fill_id, f0, f1, key_line(v, f0)[sub], sub, gshift);
+      const unsigned char* src = word >= 0 ? word_row_ptr(v, (u64)word) : default_row;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c)
+        if (cok[c]) *reinterpret_cast<float4*>(o + c * 64 + sub * 4) = PoolRow<DT>::widen(*reinterpret_cast<const Raw*>(src + coff[c]));
+      return;
+    }
+  }
 #pragma unroll
   for (int c = 0; c < NCH; ++c)
     if (cok[c]) *reinterpret_cast<float4*>(o + c * 64 + sub * 4) = comb_finish4(acc[c], wsum, scale, combiner);
@@ -179,6 +231,45 @@ __global__ __launch_bounds__(256) void find_combine_many_kernel(const ManyRec* _
   const ManyRec rec = recs[d];
   find_combine_row<DT, U, NCH>(rec.v, rec.n_rows, rec.dim, rec.ids, rec.w, rec.se, rec.combiner, rec.default_row, rec.out,
                                ((size_t)(blockIdx.x - prefix[d]) * 256 + threadIdx.x) >> 4);
+}
+
+// ---- the ragged forms (tfra_table_find_combine_ragged / tfra_multi_find_combine_ragged): the bounds come with the batch -------------
+// The same launch shape — 256 threads, one 16-lane group per output row, no LDS — and no launch before it: a ragged batch carries
+// each row's entry range, which the tuple form recovers from seg with a memset and a bounds launch.  SAFE is chosen on the host:
+// a call whose flags change nothing (no FILL, and PRUNE without weights) runs the kernel that does not look at them.
+template <int DT, int U, int NCH, bool SAFE>
+__global__ __launch_bounds__(256) void find_combine_ragged_kernel(TableView v, size_t n_rows, int dim, const i64* __restrict__ ids,
+                                                                  const float* __restrict__ w, const i64* __restrict__ row_splits,
+                                                                  int nnz, int combiner, unsigned flags, i64 fill_id,
+                                                                  const unsigned char* __restrict__ default_row,
+                                                                  float* __restrict__ out) {
+  find_combine_row<DT, U, NCH, true, SAFE>(v, n_rows, dim, ids, w, nullptr, combiner, default_row, out,
+                                           ((size_t)blockIdx.x * 256 + threadIdx.x) >> 4, RaggedArgs{row_splits, nnz, flags, fill_id});
+}
+
+struct RaggedRec {
+  TableView v;
+  size_t n_rows;
+  const i64* ids;
+  const float* w;
+  const i64* row_splits;
+  const unsigned char* default_row;
+  float* out;
+  i64 fill_id;
+  int nnz;
+  int dim;
+  int combiner;
+  unsigned flags;
+};
+
+template <int DT, int U, int NCH, bool SAFE>
+__global__ __launch_bounds__(256) void find_combine_ragged_many_kernel(const RaggedRec* __restrict__ recs,
+                                                                       const unsigned* __restrict__ prefix, unsigned n) {
+  const unsigned d = many_desc_of(prefix, n, blockIdx.x);
+  const RaggedRec rec = recs[d];
+  find_combine_row<DT, U, NCH, true, SAFE>(rec.v, rec.n_rows, rec.dim, rec.ids, rec.w, nullptr, rec.combiner, rec.default_row, rec.out,
+                                           ((size_t)(blockIdx.x - prefix[d]) * 256 + threadIdx.x) >> 4,
+                                           RaggedArgs{rec.row_splits, rec.nnz, rec.flags, rec.fill_id});
 }
 
 // seg64_bounds_kernel (tfra_frontend.hip) over a list: descriptor d owns ceil(nnz / 256) blocks and p counts ITS entries, so the
@@ -231,6 +322,43 @@ Check check_find_combine(const Table* t, const tfra_workspace* ws, size_t nnz, c
   if (!out) return refuse(TFRA_ERR_INVALID, "null out");
   if (nnz && (!ids || !seg || !default_row)) return refuse(TFRA_ERR_INVALID, "null buffer");
   return Check{};
+}
+
+// The checks of a ragged pooled lookup, for tfra_table_find_combine_ragged and for each descriptor of tfra_multi_find_combine_ragged:
+// check_find_combine's codes and wording for table, dtype, dim, size and alignment, and what only the ragged form can get wrong.
+// ws: the grouped call's workspace; the single call needs none (NULL).  row_splits' CONTENT is not looked at: the kernel clamps it.
+template <class AtEntry>
+Check check_find_combine_ragged(const Table* t, const tfra_workspace* ws, size_t n_rows, const void* row_splits, size_t nnz, const void* ids,
+                                const float* weights, int combiner, uint32_t flags, uint32_t reserved, const void* default_row,
+                                const float* out, AtEntry&& at_entry) {
+  if (!t) return refuse(TFRA_ERR_INVALID, "null table");
+  if (combiner < 0 || combiner > 2) return refuse(TFRA_ERR_INVALID, "bad argument");
+  if (flags & ~(TFRA_RAGGED_PRUNE | TFRA_RAGGED_FILL)) return refuse(TFRA_ERR_INVALID, "unknown flag bits (TFRA_RAGGED_PRUNE | TFRA_RAGGED_FILL)");
+  if (reserved) return refuse(TFRA_ERR_INVALID, "reserved must be 0");
+  if (Check e = at_entry(); e.done()) return e;
+  if (ws && ws->device != t->device) return refuse(TFRA_ERR_INVALID, "workspace and table live on different devices");
+  const int dt = t->opts.value_dtype, dim = t->opts.dim;
+  if (dt != TFRA_F32 && dt != TFRA_F16 && dt != TFRA_BF16) return refuse(TFRA_ERR_UNSUPPORTED, "value_dtype must be float32, float16 or bfloat16");
+  if (dim % 4 != 0 || dim > 256) return refuse(TFRA_ERR_UNSUPPORTED, NEEDS_DIM);
+  if (nnz >= (1ULL << 31) || n_rows >= (1ULL << 30)) return refuse(TFRA_ERR_UNSUPPORTED, "too large (nnz < 2^31, n_rows < 2^30)");
+  if ((((uintptr_t)out | (uintptr_t)default_row) & 15) || ((uintptr_t)ids & 7) || ((uintptr_t)weights & 3))
+    return refuse(TFRA_ERR_UNSUPPORTED, "misaligned buffer (out and default_row: 16 bytes)");
+  if ((uintptr_t)row_splits & 7) return refuse(TFRA_ERR_UNSUPPORTED, "misaligned row_splits (8 bytes)");
+  if (n_rows == 0) return nothing_to_do();
+  if (!out) return refuse(TFRA_ERR_INVALID, "null out");
+  if (!row_splits) return refuse(TFRA_ERR_INVALID, "null row_splits");
+  if ((nnz && !ids) || ((nnz || (flags & TFRA_RAGGED_FILL)) && !default_row)) return refuse(TFRA_ERR_INVALID, "null buffer");
+  return Check{};
+}
+// whether the flags change anything: the SAFE kernels run only then
+bool ragged_safe(uint32_t flags, const float* weights) { return (flags & TFRA_RAGGED_FILL) || ((flags & TFRA_RAGGED_PRUNE) && weights); }
+// launch(DT, U, NCH, SAFE): with_pool_class with the ragged forms' fourth axis
+template <class F>
+void with_ragged_class(int st, int nch, bool safe, F&& launch) {
+  with_pool_class(st, nch, [&](auto DT, auto U, auto NCH) {
+    if (safe) launch(DT, U, NCH, std::true_type{});
+    else launch(DT, U, NCH, std::false_type{});
+  });
 }
 
 }  // namespace
@@ -385,6 +513,118 @@ extern "C" int tfra_multi_find_combine(tfra_workspace_t* ws, size_t n_tables, co
     const unsigned* p = section<const unsigned>(up.dev, cpre_off) + k.at;
     with_pool_class(c / 3, c % 3, [&](auto DT, auto U, auto NCH) {
       find_combine_many_kernel<DT, U, NCH><<<k.grid, 256, 0, s>>>(r, p, k.n);
+    });
+    ++launches;
+  }
+  HIP_TRY(hipGetLastError());
+  if (launches_out) *launches_out = launches;
+  return TFRA_OK;
+}
+
+// ---- the ragged calls ------------------------------------------------------------------------------------------------------------------
+extern "C" int tfra_table_find_combine_ragged(tfra_table_t* tp, size_t n_rows, const int64_t* row_splits, size_t nnz, const int64_t* ids,
+                                              const float* weights, int combiner, uint32_t flags, int64_t fill_id,
+                                              const void* default_row, float* out, tfra_stream_t stream) {
+  Table* t = reinterpret_cast<Table*>(tp);
+  hipStream_t s = (hipStream_t)stream;
+  std::unique_lock<std::mutex> lock;
+  Check c = check_find_combine_ragged(t, nullptr, n_rows, row_splits, nnz, ids, weights, combiner, flags, 0, default_row, out, [&] {
+    lock = std::unique_lock<std::mutex>(t->mu);
+    return Check{t->enter(s)};
+  });
+  if (c.msg == NEEDS_DIM) c.msg += " (use tfra_unique + tfra_table_find + tfra_sparse_segment_combine otherwise)";
+  if (c.code) return report("find_combine_ragged: ", c);
+  if (!c.active) return TFRA_OK;
+  const int dim = t->opts.dim;
+  if (nnz == 0 && !(flags & TFRA_RAGGED_FILL)) {
+    HIP_TRY(hipMemsetAsync(out, 0, n_rows * (size_t)dim * sizeof(float), s));
+    return TFRA_OK;
+  }
+  const TableView v = t->view_of(t->cur);
+  const unsigned grid = (unsigned)((n_rows * 16 + 255) / 256);
+  with_ragged_class(st_index(t->opts.value_dtype), nch_index(dim), ragged_safe(flags, weights), [&](auto DT, auto U, auto NCH, auto SAFE) {
+    find_combine_ragged_kernel<DT, U, NCH, SAFE><<<grid, 256, 0, s>>>(v, n_rows, dim, (const i64*)ids, weights, (const i64*)row_splits,
+                                                                           (int)nnz, combiner, flags, (i64)fill_id,
+                                                                           (const unsigned char*)default_row, out);
+  });
+  HIP_TRY(hipGetLastError());
+  return TFRA_OK;
+}
+
+extern "C" int tfra_multi_find_combine_ragged(tfra_workspace_t* ws, size_t n_tables, const tfra_find_combine_ragged_desc* descs,
+                                              uint32_t* launches_out, tfra_stream_t stream) {
+  if (launches_out) *launches_out = 0;
+  if (n_tables == 0) return TFRA_OK;
+  if (!ws || !descs) return set_error(TFRA_ERR_INVALID, "multi_find_combine_ragged: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  // every descriptor is checked before anything is enqueued: one bad descriptor and no out is written
+  constexpr int NCLASS = 18;   // (float32 | float16 | bfloat16) x (NCH 1 | 2 | 4) x (plain | safe)
+  std::vector<int> cls(n_tables, -1);
+  size_t n_act = 0;
+  for (size_t i = 0; i < n_tables; ++i) {
+    const tfra_find_combine_ragged_desc& d = descs[i];
+    if (d.struct_size != sizeof(tfra_find_combine_ragged_desc))
+      return set_error(TFRA_ERR_INVALID, "multi_find_combine_ragged: descriptor " + std::to_string(i) + ": descriptor size mismatch");
+    const Table* t = reinterpret_cast<const Table*>(d.table);
+    const Check c = check_find_combine_ragged(t, ws, d.n_rows, d.row_splits, d.nnz, d.ids, d.weights, d.combiner, d.flags, d.reserved,
+                                              d.default_row, d.out, [] { return Check{}; });
+    if (c.code) return report("multi_find_combine_ragged: descriptor " + std::to_string(i) + ": ", c);
+    if (!c.active) continue;
+    cls[i] = (st_index(t->opts.value_dtype) * 3 + nch_index(t->opts.dim)) * 2 + (ragged_safe(d.flags, d.weights) ? 1 : 0);
+    ++n_act;
+  }
+  if (n_act == 0) return TFRA_OK;
+  // the records' order: class by class, input order inside a class
+  auto row_blocks = [&](size_t i) { return (unsigned)((descs[i].n_rows * 16 + 255) / 256); };
+  std::vector<size_t> order;
+  order.reserve(n_act);
+  size_t cls_first[NCLASS + 1];
+  for (int c = 0; c < NCLASS; ++c) {
+    cls_first[c] = order.size();
+    u64 blocks = 0;
+    for (size_t i = 0; i < n_tables; ++i)
+      if (cls[i] == c) { order.push_back(i); blocks += row_blocks(i); }
+    if (blocks >= (1ULL << 31)) return set_error(TFRA_ERR_UNSUPPORTED, "multi_find_combine_ragged: too many rows in one call");
+  }
+  cls_first[NCLASS] = order.size();
+
+  // (one table may stand in several descriptors: locked once)
+  std::vector<Table*> tabs;
+  tabs.reserve(n_act);
+  for (size_t i : order) tabs.push_back(reinterpret_cast<Table*>(descs[i].table));
+  std::vector<std::unique_lock<std::mutex>> locks;
+  int rc = lock_and_enter(std::move(tabs), s, &locks);
+  if (rc) return rc;
+
+  // device memory: the blob alone = [records | per-class block prefixes]; there are no bounds to keep
+  Blob blob;
+  const size_t rec_off = blob.add<RaggedRec>(n_act), cpre_off = blob.add<unsigned>(ClassPool::words(n_act, NCLASS, false));
+  ManyUpload up;
+  rc = many_begin(ws, 0, blob.bytes(), s, &up);
+  if (rc) return rc;
+  RaggedRec* recs = section<RaggedRec>(up.host, rec_off);
+  // the views are taken here, under the locks: a table that grew since the last call has another one
+  for (size_t k = 0; k < n_act; ++k) {
+    const tfra_find_combine_ragged_desc& d = descs[order[k]];
+    Table* t = reinterpret_cast<Table*>(d.table);
+    recs[k] = RaggedRec{t->view_of(t->cur), d.n_rows, (const i64*)d.ids, d.weights, (const i64*)d.row_splits,
+                        (const unsigned char*)d.default_row, d.out, (i64)d.fill_id, (int)d.nnz, t->opts.dim, d.combiner, d.flags};
+  }
+  ClassPool cpool{section<unsigned>(up.host, cpre_off)};
+  ManyClass row_cls[NCLASS];
+  for (int c = 0; c < NCLASS; ++c)
+    row_cls[c] = cpool.put(n_act, false, [&](size_t k) { return k >= cls_first[c] && k < cls_first[c + 1]; },
+                           [&](size_t k) { return row_blocks(order[k]); });
+  rc = many_send(up, s, "hipMemcpyAsync(d_blob, h, blob_bytes, hipMemcpyHostToDevice, s)", true);
+  if (rc) return rc;
+  uint32_t launches = 0;
+  for (int c = 0; c < NCLASS; ++c) {
+    const ManyClass& k = row_cls[c];
+    if (!k.n) continue;
+    const RaggedRec* r = section<const RaggedRec>(up.dev, rec_off) + cls_first[c];
+    const unsigned* p = section<const unsigned>(up.dev, cpre_off) + k.at;
+    with_ragged_class(c / 6, (c / 2) % 3, c & 1, [&](auto DT, auto U, auto NCH, auto SAFE) {
+      find_combine_ragged_many_kernel<DT, U, NCH, SAFE><<<k.grid, 256, 0, s>>>(r, p, k.n);
     });
     ++launches;
   }

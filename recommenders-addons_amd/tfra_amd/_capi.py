@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libtfra_mi355x.so")
 TFRA_F32, TFRA_F16, TFRA_BF16, TFRA_I8, TFRA_I32, TFRA_I64, TFRA_F64 = range(7)
 FLAG_UNIQUE_KEYS = 1
 OPT_SGD, OPT_ADAM, OPT_ADAGRAD, OPT_FTRL = range(4)
+RAGGED_PRUNE, RAGGED_FILL = 1, 2   # TFRA_RAGGED_* (flags of the ragged pooled lookup)
 OPTION_CAPTURE_SAFE = 1
 OPTION_NO_OWNER_TAGS = 2
 OPTION_KEY_BYTES_ON_DISK = 3
@@ -76,6 +77,16 @@ class FindCombineDesc(ctypes.Structure):
       ("struct_size", ctypes.c_uint32), ("combiner", ctypes.c_int32), ("table", ctypes.c_void_p), ("nnz", ctypes.c_size_t),
       ("ids", ctypes.c_void_p), ("seg", ctypes.c_void_p), ("weights", ctypes.c_void_p), ("n_rows", ctypes.c_size_t),
       ("default_row", ctypes.c_void_p), ("out", ctypes.c_void_p),
+  ]
+
+
+class FindCombineRaggedDesc(ctypes.Structure):
+  """tfra_find_combine_ragged_desc (include/tfra_mi355x.h): one table's ragged pooled lookup in tfra_multi_find_combine_ragged."""
+  _fields_ = [
+      ("struct_size", ctypes.c_uint32), ("combiner", ctypes.c_int32), ("table", ctypes.c_void_p), ("n_rows", ctypes.c_size_t),
+      ("row_splits", ctypes.c_void_p), ("nnz", ctypes.c_size_t), ("ids", ctypes.c_void_p), ("weights", ctypes.c_void_p),
+      ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("fill_id", ctypes.c_int64), ("default_row", ctypes.c_void_p),
+      ("out", ctypes.c_void_p),
   ]
 
 
@@ -177,6 +188,8 @@ _SIGS = {
     "tfra_table_find_unique": [_P, _P, _SZ, _P, _P, _P, _P, _I, _P, _P, _P, _P],
     "tfra_table_find_combine": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, _P, _P],
     "tfra_multi_find_combine": [_P, _SZ, _P, _P, _P],
+    "tfra_table_find_combine_ragged": [_P, _SZ, _P, _SZ, _P, _P, _I, ctypes.c_uint32, ctypes.c_int64, _P, _P, _P],
+    "tfra_multi_find_combine_ragged": [_P, _SZ, _P, _P, _P],
     "tfra_multi_apply_planned_combined": [_P, _SZ, _P, _P, _P],
     "tfra_multi_sparse_plan_build": [_P, _SZ, _P, _P, _P],
     "tfra_segment_sum": [_P, _SZ, _I, _P, _P, _P, _SZ, _P, _P],

@@ -11,5 +11,6 @@ from .variable import (CuckooHashTableConfig, CuckooHashTableCreator, HkvHashTab
                        KVCreator, SparseTrainableWrapper, TrainableWrapper, Variable, default_partition_fn, embedding_lookup,
                        embedding_lookup_sparse, embedding_lookup_sparse_many, embedding_lookup_unique, get_variable,
                        safe_embedding_lookup_sparse, safe_embedding_lookup_sparse_many)
+from . import ragged_embedding_ops   # (after .variable: it stands on the tuple-form functions)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

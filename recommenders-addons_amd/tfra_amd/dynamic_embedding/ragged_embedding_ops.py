@@ -1,0 +1,193 @@
+"""`tfra_amd.dynamic_embedding.ragged_embedding_ops` — mirrors
+`tensorflow_recommenders_addons/dynamic_embedding/python/ops/ragged_embedding_ops.py` (PY/ragged_embedding_ops.py:129-442):
+embedding_lookup_sparse and safe_embedding_lookup_sparse over a rank-2 RaggedTensor, which the reference's Keras layers use for
+multi-hot features.
+
+A ragged batch is `sp_ids = (row_splits[n_rows + 1], values[nnz])` with `sp_weights` = weight values[nnz] or None: row r owns
+the entries [row_splits[r], row_splits[r + 1]), row_splits[0] == 0 as in a RaggedTensor.  int32 row_splits are widened; int32 keys
+go through the table's usual key handling.  The number of rows is the length of row_splits, so nothing is read on the host.
+
+The forward is ONE kernel launch (tfra_table_find_combine_ragged; `Variable.lookup_combined_ragged`): the row's entry range comes
+with the batch, so there is no bounds pass, and the safe form's pruning by weight and its default_id are done by the group that
+owns the row (flags PRUNE / FILL) — no boolean-mask indexing, no second lookup, no `torch.where`.  The result is bit-identical
+to the tuple-form functions of `tfra_amd.dynamic_embedding` on the row ids the splits stand for.
+
+A variable the pooled forward does not serve (several shards, a callable initializer, dim % 4 != 0 or dim > 256, other value
+dtypes, bp_v2) is handed to the tuple-form function with row ids derived from row_splits on the device: no input is refused.
+
+Training: return_trainable=True returns the tuple form's SparseTrainableWrapper, built behind the ragged forward.  Only the
+FORWARD of a safe trainable lookup is sync-free: the wrapper's entry list (pruned entries dropped, one entry per empty row) is
+made by the tuple form's preprocessing as it is, host syncs included."""
+import torch
+
+from . import device_ops
+from .variable import (SparseTrainableWrapper, _per_table, _plans_at_lookup_many, _pooled_forward, _safe_sparse_args)
+from . import variable as _tuple_form
+
+_COMBINERS = ("mean", "sqrtn", "sum")
+
+
+def _ragged_input(params, sp_ids, sp_weights):
+  """(row_splits int64 [n_rows + 1], values [nnz], weights float32 [nnz] or None) on the variable's device; shapes checked."""
+  if len(sp_ids) != 2:
+    raise ValueError("ragged ids are (row_splits[n_rows + 1], values[nnz])")
+  rs = torch.as_tensor(sp_ids[0], device=params._primary).reshape(-1)
+  if rs.dtype not in (torch.int32, torch.int64):
+    raise TypeError("row_splits must be int32 or int64, got %s" % rs.dtype)
+  if rs.numel() < 1:
+    raise ValueError("row_splits needs n_rows + 1 >= 1 elements")
+  ids = torch.as_tensor(sp_ids[1], device=params._primary).reshape(-1)
+  w = None
+  if sp_weights is not None:
+    w = torch.as_tensor(sp_weights, dtype=torch.float32, device=params._primary).reshape(-1)
+    if w.numel() != ids.numel():
+      raise ValueError("sp_weights must have one element per id")
+  return rs.to(torch.int64), ids, w
+
+
+def row_ids_of(row_splits, nnz):
+  """value_rowids of a ragged batch without a host read: entry p lies in the row r with row_splits[r] <= p < row_splits[r + 1]
+  (the number of splits behind the first that are <= p); an entry behind the last split gets n_rows, which no row owns."""
+  p = torch.arange(nnz, dtype=torch.int64, device=row_splits.device)
+  return torch.searchsorted(row_splits[1:].contiguous(), p, right=True)
+
+
+def _check_combiner(combiner):
+  if combiner not in _COMBINERS:
+    raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+
+
+def _safe_flags(w, combiner, default_id):
+  """(prune, fill id): PRUNE exactly when weights are given and the combiner is not "sum" (PY/ragged_embedding_ops.py:414-416),
+  FILL exactly when default_id is not None (:417-440).  Ids are never pruned."""
+  return (w is not None and combiner != "sum"), default_id
+
+
+def _plain_wrapper(params, rs, ids, w, combiner, n, plan_writeback, entry_plan=None):
+  seg = row_ids_of(rs, ids.numel())
+  return SparseTrainableWrapper(params, None, None, None, seg, w, combiner, n, (n, params.dim), ids, seg, w,
+                                plan_writeback=plan_writeback, lookup_ids=ids, entry_plan=entry_plan)
+
+
+def _safe_entries(params, rs, ids, w, combiner, default_id, n):
+  """What the tuple form's safe lookup hands its wrapper: `_safe_sparse_args` on the derived row ids, as it is (host syncs
+  included)."""
+  rows, p_ids, p_w, _, entries, out_shape, _ = _safe_sparse_args(params, (row_ids_of(rs, ids.numel()), ids), w, combiner, default_id,
+                                                                 True, n)
+  return rows, p_ids, p_w, entries, out_shape
+
+
+def _safe_wrapper(params, args, combiner, n, plan_writeback, entry_plan=None):
+  rows, p_ids, p_w, entries, out_shape = args
+  return SparseTrainableWrapper(params, None, None, None, rows, p_w, combiner, n, out_shape, entries[0], entries[1], entries[2],
+                                plan_writeback=plan_writeback, lookup_ids=p_ids, entry_plan=entry_plan)
+
+
+def embedding_lookup_sparse(params, sp_ids, sp_weights, name=None, combiner="mean", return_trainable=False, plan_writeback=False):
+  """PY/ragged_embedding_ops.py:223-324.  `sp_ids` = (row_splits[n_rows + 1], values[nnz]), `sp_weights` = weight values or None.
+  [n_rows, dim] float32: row r = sum / mean / sqrtn over its entries of weight * embedding, zeros for an empty row — bit-identical
+  to `de.embedding_lookup_sparse(params, (row ids, values), sp_weights, num_rows=n_rows)`, in one launch.
+
+  return_trainable: also returns the SparseTrainableWrapper (`DynamicEmbeddingOptimizer.apply_combined_gradients`); its entry
+  list is (values, derived row ids, weights).  plan_writeback: as the tuple form's."""
+  _check_combiner(combiner)
+  rs, ids, w = _ragged_input(params, sp_ids, sp_weights)
+  n = rs.numel() - 1
+  if not _pooled_forward(params, None):
+    return _tuple_form.embedding_lookup_sparse(params, (row_ids_of(rs, ids.numel()), ids), w, combiner=combiner,
+                                               return_trainable=return_trainable, num_rows=n, plan_writeback=plan_writeback)
+  out = params.lookup_combined_ragged(rs, ids, w, combiner)
+  if not return_trainable:
+    return out
+  return out, _plain_wrapper(params, rs, ids, w, combiner, n, plan_writeback)
+
+
+def safe_embedding_lookup_sparse(params, sparse_ids, sparse_weights=None, combiner="mean", default_id=None, name=None,
+                                 return_trainable=False, plan_writeback=False):
+  """PY/ragged_embedding_ops.py:327-442, with this project's semantics of the tuple form (`de.safe_embedding_lookup_sparse`):
+  ids are never pruned; entries whose weight is not > 0 are dropped unless combiner == "sum"; a row left without entries yields
+  zeros, or the embedding of `default_id`.  Bit-identical to the tuple form on (row ids, values), in one launch and with no
+  host synchronisation: the pruning and the default row are the kernel's.
+
+  return_trainable: also returns the SparseTrainableWrapper; its entry list comes from the tuple form's preprocessing
+  (`_safe_sparse_args`) on the derived row ids, which reads on the host — only the forward of a safe trainable lookup is
+  sync-free."""
+  _check_combiner(combiner)
+  rs, ids, w = _ragged_input(params, sparse_ids, sparse_weights)
+  n = rs.numel() - 1
+  if not _pooled_forward(params, None):
+    return _tuple_form.safe_embedding_lookup_sparse(params, (row_ids_of(rs, ids.numel()), ids), w, combiner=combiner,
+                                                    default_id=default_id, return_trainable=return_trainable, num_rows=n,
+                                                    plan_writeback=plan_writeback)
+  prune, fill = _safe_flags(w, combiner, default_id)
+  out = params.lookup_combined_ragged(rs, ids, w, combiner, prune=prune, fill_id=fill)
+  if not return_trainable:
+    return out
+  return out, _safe_wrapper(params, _safe_entries(params, rs, ids, w, combiner, default_id, n), combiner, n, plan_writeback)
+
+
+def _many(params_list, sp_ids_list, weights_list, combiner, default_id, safe, return_trainable, plan_writeback):
+  from . import table_ops
+  n_t = len(params_list)
+  if len(sp_ids_list) != n_t:
+    raise ValueError("sp_ids_list: %d entries for %d tables" % (len(sp_ids_list), n_t))
+  weights = _per_table(None if weights_list is None else list(weights_list), n_t, "sp_weights_list")
+  combiners = _per_table(combiner, n_t, "combiner")
+  default_ids = _per_table(default_id, n_t, "default_id")
+  for c in combiners:
+    _check_combiner(c)
+  single = safe_embedding_lookup_sparse if safe else embedding_lookup_sparse
+  results = [None] * n_t
+  groups = {}   # device -> [(i, row_splits, ids, w)]
+  for i, params in enumerate(params_list):
+    if not _pooled_forward(params, None):
+      kw = dict(default_id=default_ids[i]) if safe else {}
+      results[i] = single(params, sp_ids_list[i], weights[i], combiner=combiners[i], return_trainable=return_trainable,
+                          plan_writeback=plan_writeback, **kw)
+      continue
+    groups.setdefault(params._primary, []).append((i,) + _ragged_input(params, sp_ids_list[i], weights[i]))
+  for device, members in groups.items():
+    reqs = []
+    for i, rs, ids, w in members:
+      t = params_list[i]._tables[0]
+      prune, fill = _safe_flags(w, combiners[i], default_ids[i]) if safe else (False, None)
+      reqs.append((t._table, rs, ids, w, device_ops.COMBINERS[combiners[i]], prune, fill, t._default_value))
+    outs = table_ops.find_combine_ragged_many(reqs)
+    if not return_trainable:
+      for (i, _, _, _), out in zip(members, outs):
+        results[i] = out
+      continue
+    made = {}   # i -> what the member's wrapper is built from
+    for i, rs, ids, w in members:
+      n = rs.numel() - 1
+      made[i] = _safe_entries(params_list[i], rs, ids, w, combiners[i], default_ids[i], n) if safe else None
+    entry_ids = {i: (made[i][3][0] if safe else ids) for i, _, ids, _ in members}
+    # the members' write-back plans: one grouped build on one side stream (None: at most one member takes a plan, and its wrapper
+    # starts it as the single lookup does)
+    started = _plans_at_lookup_many(device, [(i, params_list[i], entry_ids[i]) for i, _, _, _ in members]) if plan_writeback else None
+    for (i, rs, ids, w), out in zip(members, outs):
+      params, n = params_list[i], rs.numel() - 1
+      pw = plan_writeback and started is None
+      plan = None if started is None else started.get(i)
+      tw = (_safe_wrapper(params, made[i], combiners[i], n, pw, plan) if safe else
+            _plain_wrapper(params, rs, ids, w, combiners[i], n, pw, plan))
+      results[i] = (out, tw)
+  return results
+
+
+def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None, combiner="mean", return_trainable=False,
+                                 plan_writeback=False):
+  """`embedding_lookup_sparse` of a LIST of variables: result i is what the single form returns for table i, bit for bit.
+  `combiner` is a scalar or a per-table list.  The variables the pooled forward serves are read by ONE grouped call per device
+  (`table_ops.find_combine_ragged_many`: tfra_multi_find_combine_ragged — one upload and one launch per class, no bounds pass);
+  every other variable takes the single form, so no list is refused."""
+  return _many(params_list, sp_ids_list, sp_weights_list, combiner, None, False, return_trainable, plan_writeback)
+
+
+def safe_embedding_lookup_sparse_many(params_list, sp_ids_list, sparse_weights_list=None, combiner="mean", default_id=None,
+                                      return_trainable=False, plan_writeback=False):
+  """`safe_embedding_lookup_sparse` of a LIST of variables: result i is what the single form returns for table i, bit for bit.
+  `combiner` and `default_id` are scalars or per-table lists.  One grouped call per device for the variables the pooled forward
+  serves, with no host synchronisation in the forward; with return_trainable the wrappers' entry lists are made per table by
+  the tuple form's preprocessing (host syncs included)."""
+  return _many(params_list, sp_ids_list, sparse_weights_list, combiner, default_id, True, return_trainable, plan_writeback)

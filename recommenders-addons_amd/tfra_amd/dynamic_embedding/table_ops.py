@@ -297,6 +297,44 @@ class _DeviceTable:
                int(n_rows), _ptr(d), _ptr(out), _stream(self._device))
     return out
 
+  def _find_combine_ragged_args(self, row_splits, ids, weights, prune, fill_id, default_row):
+    """The arguments of one ragged pooled lookup as the C calls read them: (row_splits int64 [n_rows + 1], ids, weights or None,
+    flags, fill id, default row, out), checked and on the table's device (find_combine_ragged and find_combine_ragged_many share
+    it).  Shapes only: the content of row_splits is the kernel's business (it clamps), nothing is read on the host."""
+    ids = self._keys(ids).reshape(-1)
+    nnz = ids.numel()
+    rs = torch.as_tensor(row_splits, device=self._device).reshape(-1)
+    if rs.dtype not in (torch.int32, torch.int64):
+      raise TypeError("row_splits must be int32 or int64, got %s" % rs.dtype)
+    if rs.numel() < 1:
+      raise ValueError("row_splits needs n_rows + 1 >= 1 elements")
+    rs = rs.to(torch.int64).contiguous()   # int32 splits are widened
+    w = None
+    if weights is not None:
+      w = torch.as_tensor(weights, device=self._device).reshape(-1).to(torch.float32).contiguous()
+      if w.numel() != nnz:
+        raise ValueError("weights must have one element per id")
+    d = self._default_value if default_row is None else torch.as_tensor(default_row, device=self._device)
+    if d.dtype != self._value_dtype:
+      raise TypeError("default values must be dtype %s, got %s" % (self._value_dtype, d.dtype))
+    if d.numel() != self._dim:
+      raise ValueError("default_row must be one row of dim=%d elements, got %d" % (self._dim, d.numel()))
+    d = d.contiguous()
+    flags = (_capi.RAGGED_PRUNE if prune else 0) | (_capi.RAGGED_FILL if fill_id is not None else 0)
+    out = torch.empty((rs.numel() - 1, self._dim), dtype=torch.float32, device=self._device)
+    return rs, ids, w, flags, (0 if fill_id is None else int(fill_id)), d, out
+
+  def find_combine_ragged(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, default_row=None):
+    """The pooled lookup over a ragged batch (tfra_table_find_combine_ragged): row r combines the entries
+    [row_splits[r], row_splits[r + 1]) of ids / weights as `find_combine` combines the entries with seg == r, bit for bit, in ONE
+    launch (no bounds pass).  row_splits int64 or int32 [n_rows + 1]; out-of-range or decreasing splits give empty or shortened
+    rows, never a read outside ids.  prune: only entries with weight > 0 are members (ignored without weights).  fill_id: a row
+    without members is the row of that key (`default_row` on a miss), up-cast as it is; None: zeros.  Nothing is read on the host."""
+    rs, ids, w, flags, fill, d, out = self._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row)
+    _capi.call("tfra_table_find_combine_ragged", self._h, rs.numel() - 1, _ptr(rs), ids.numel(), _ptr(ids), _ptr(w), int(combiner),
+               flags, fill, _ptr(d), _ptr(out), _stream(self._device))
+    return out
+
   def upsert(self, keys, values, scores=None, unique_keys=False, field=0):
     keys = self._keys(keys)
     values = self._values_for(keys, values)
@@ -859,6 +897,46 @@ def find_combine_many(requests, return_launches=False):
     e.n_rows, e.default_row, e.out = int(n_rows), d.data_ptr(), out.data_ptr()
   launches = ctypes.c_uint32(0)
   _capi.call("tfra_multi_find_combine", _workspace(device), n, ctypes.c_void_p(ctypes.addressof(descs)),
+             ctypes.c_void_p(ctypes.addressof(launches)), _stream(device))
+  return (outs, int(launches.value)) if return_launches else outs
+
+
+def find_combine_ragged_many(requests, return_launches=False):
+  """The ragged pooled lookups of a list of tables in ONE C call (tfra_multi_find_combine_ragged).  `requests`: a list of
+  (table, row_splits, ids, weights, combiner[, prune[, fill_id[, default_row]]]) — `table` a _DeviceTable (or a CuckooHashTable /
+  HkvHashTable, whose device table is taken), the other arguments those of `_DeviceTable.find_combine_ragged`, handled the same
+  way.  All tables live on one device; a table may occur more than once.  Returns the [n_rows, dim] float32 results in the
+  requests' order, each bit-identical to `find_combine_ragged` of its request (with return_launches: also the number of kernel
+  launches the call enqueued: one per (value dtype, row-width class, safe-or-not) class in the list)."""
+  from .device_ops import _workspace
+  n = len(requests)
+  if n == 0:
+    return ([], 0) if return_launches else []
+  descs = (_capi.FindCombineRaggedDesc * n)()
+  keep, outs, device = [], [], None
+  for i, req in enumerate(requests):
+    table, row_splits, ids, weights, combiner = req[:5]
+    prune = req[5] if len(req) > 5 else False
+    fill_id = req[6] if len(req) > 6 else None
+    default_row = req[7] if len(req) > 7 else None
+    table = getattr(table, "_table", table)
+    if device is None:
+      device = table._device
+    elif table._device != device:
+      raise ValueError("find_combine_ragged_many: all tables must live on one device (%s and %s)" % (device, table._device))
+    rs, ids, w, flags, fill, d, out = table._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row)
+    keep.append((rs, ids, w, d))
+    outs.append(out)
+    e = descs[i]
+    e.struct_size = ctypes.sizeof(_capi.FindCombineRaggedDesc)
+    e.combiner = int(combiner)
+    e.table = table._h.value
+    e.n_rows, e.row_splits = rs.numel() - 1, rs.data_ptr()
+    e.nnz, e.ids, e.weights = ids.numel(), ids.data_ptr(), (w.data_ptr() if w is not None else None)
+    e.flags, e.reserved, e.fill_id = flags, 0, fill
+    e.default_row, e.out = d.data_ptr(), out.data_ptr()
+  launches = ctypes.c_uint32(0)
+  _capi.call("tfra_multi_find_combine_ragged", _workspace(device), n, ctypes.c_void_p(ctypes.addressof(descs)),
              ctypes.c_void_p(ctypes.addressof(launches)), _stream(device))
   return (outs, int(launches.value)) if return_launches else outs
 

@@ -258,6 +258,19 @@ class Variable:
     ids = torch.as_tensor(ids, device=self._primary)
     return t._table.find_combine(ids.reshape(-1), seg, weights, device_ops.COMBINERS[combiner], n_rows, t._default_value)
 
+  def lookup_combined_ragged(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, name=None):
+    """`lookup_combined` over a ragged batch (tfra_table_find_combine_ragged): [n_rows, dim] float32, row r combining the entries
+    [row_splits[r], row_splits[r + 1]) — bit-identical to `lookup_combined` on the row ids the splits stand for, in one launch.
+    prune / fill_id: safe_embedding_lookup_sparse's pruning by weight and its default_id (`_DeviceTable.find_combine_ragged`).
+    Under `can_lookup_combined()`'s conditions.  Never inserts; nothing is read on the host."""
+    if not self.can_lookup_combined():
+      raise ValueError("lookup_combined_ragged needs one shard, a static default row, float32 / float16 / bfloat16 rows, "
+                       "dim % 4 == 0 and dim <= 256; use ragged_embedding_ops.embedding_lookup_sparse")
+    t = self._tables[0]
+    ids = torch.as_tensor(ids, device=self._primary)
+    return t._table.find_combine_ragged(row_splits, ids.reshape(-1), weights, device_ops.COMBINERS[combiner], prune=prune,
+                                        fill_id=fill_id, default_row=t._default_value)
+
   def export(self, name=None):
     """PY/dynamic_embedding_variable.py:988-1007"""
     ks, vs = [], []
