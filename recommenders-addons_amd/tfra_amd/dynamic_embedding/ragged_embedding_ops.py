@@ -21,10 +21,8 @@ made by the tuple form's preprocessing as it is, host syncs included."""
 import torch
 
 from . import device_ops
-from .variable import (SparseTrainableWrapper, _per_table, _plans_at_lookup_many, _pooled_forward, _safe_sparse_args)
+from .variable import (SparseTrainableWrapper, _check_combiner, _per_table, _pooled_forward, _safe_sparse_args, _wrap_grouped)
 from . import variable as _tuple_form
-
-_COMBINERS = ("mean", "sqrtn", "sum")
 
 
 def _ragged_input(params, sp_ids, sp_weights):
@@ -50,11 +48,6 @@ def row_ids_of(row_splits, nnz):
   (the number of splits behind the first that are <= p); an entry behind the last split gets n_rows, which no row owns."""
   p = torch.arange(nnz, dtype=torch.int64, device=row_splits.device)
   return torch.searchsorted(row_splits[1:].contiguous(), p, right=True)
-
-
-def _check_combiner(combiner):
-  if combiner not in _COMBINERS:
-    raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
 
 
 def _safe_flags(w, combiner, default_id):
@@ -158,20 +151,18 @@ def _many(params_list, sp_ids_list, weights_list, combiner, default_id, safe, re
         results[i] = out
       continue
     made = {}   # i -> what the member's wrapper is built from
-    for i, rs, ids, w in members:
-      n = rs.numel() - 1
-      made[i] = _safe_entries(params_list[i], rs, ids, w, combiners[i], default_ids[i], n) if safe else None
-    entry_ids = {i: (made[i][3][0] if safe else ids) for i, _, ids, _ in members}
-    # the members' write-back plans: one grouped build on one side stream (None: at most one member takes a plan, and its wrapper
-    # starts it as the single lookup does)
-    started = _plans_at_lookup_many(device, [(i, params_list[i], entry_ids[i]) for i, _, _, _ in members]) if plan_writeback else None
-    for (i, rs, ids, w), out in zip(members, outs):
+    if safe:
+      for i, rs, ids, w in members:
+        made[i] = _safe_entries(params_list[i], rs, ids, w, combiners[i], default_ids[i], rs.numel() - 1)
+
+    def wrapper(member, own_plan, entry_plan):
+      i, rs, ids, w = member
       params, n = params_list[i], rs.numel() - 1
-      pw = plan_writeback and started is None
-      plan = None if started is None else started.get(i)
-      tw = (_safe_wrapper(params, made[i], combiners[i], n, pw, plan) if safe else
-            _plain_wrapper(params, rs, ids, w, combiners[i], n, pw, plan))
-      results[i] = (out, tw)
+      return (_safe_wrapper(params, made[i], combiners[i], n, own_plan, entry_plan) if safe else
+              _plain_wrapper(params, rs, ids, w, combiners[i], n, own_plan, entry_plan))
+
+    _wrap_grouped(device, params_list, members, outs, {i: (made[i][3][0] if safe else ids) for i, _, ids, _ in members},
+                  plan_writeback, wrapper, results)
   return results
 
 

@@ -63,6 +63,11 @@ def _ptr(t):
   return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _workspace(device):   # device_ops imports this module: its _workspace is looked up at call time
+  from .device_ops import _workspace as workspace
+  return workspace(device)
+
+
 def _wide_keys(keys):
   """`keys` as the engine's int64 keys, for a C function that reads `const int64_t*`: int64 keys as they are, int32 keys widened on
   the device (tfra_keys_widen_i32).  Any other dtype raises TypeError before a launch."""
@@ -242,7 +247,6 @@ class _DeviceTable:
     """find(keys) and the de-duplication of the same keys in ONE launch (tfra_table_find_unique: the forward half of embedding_lookup
     as the fused TF op issues it): returns (rows [n, dim], unique [n] — the first `count` entries are the distinct keys, in no
     particular order —, idx [n] int32 with unique[idx] == keys, count: device int64 scalar[, exists]).  Nothing is read on the host."""
-    from .device_ops import _workspace
     keys = self._keys(keys).reshape(-1)
     n = keys.numel()
     d = self._default_value if dynamic_default_values is None else dynamic_default_values
@@ -263,14 +267,9 @@ class _DeviceTable:
     uniq = _narrow_keys(uniq, self._key_dtype)   # the table's key dtype, so that `unique` goes back into upsert / erase
     return (out, uniq, idx, cnt, exists) if return_exists else (out, uniq, idx, cnt)
 
-  def _find_combine_args(self, ids, seg, weights, n_rows, default_row):
-    """The arguments of one pooled lookup as the C calls read them: (ids, seg, weights or None, default row, out), checked and on
-    the table's device (find_combine and find_combine_many share it)."""
-    ids = self._keys(ids).reshape(-1)
-    nnz = ids.numel()
-    seg = torch.as_tensor(seg, device=self._device).reshape(-1).to(torch.int64).contiguous()
-    if seg.numel() != nnz:
-      raise ValueError("ids and segment_ids must have the same number of elements: %d vs %d" % (nnz, seg.numel()))
+  def _pooled_operands(self, nnz, weights, default_row):
+    """The weights (float32 [nnz], or None) and the default row (one row of the value dtype, the table's when None) of a pooled
+    lookup, checked and on the table's device: what the tuple and the ragged form share behind their own ids / rows checks."""
     w = None
     if weights is not None:
       w = torch.as_tensor(weights, device=self._device).reshape(-1).to(torch.float32).contiguous()
@@ -282,6 +281,17 @@ class _DeviceTable:
     if d.numel() != self._dim:
       raise ValueError("default_row must be one row of dim=%d elements, got %d" % (self._dim, d.numel()))
     d = d.contiguous()
+    return w, d
+
+  def _find_combine_args(self, ids, seg, weights, n_rows, default_row):
+    """The arguments of one pooled lookup as the C calls read them: (ids, seg, weights or None, default row, out), checked and on
+    the table's device (find_combine and find_combine_many share it)."""
+    ids = self._keys(ids).reshape(-1)
+    nnz = ids.numel()
+    seg = torch.as_tensor(seg, device=self._device).reshape(-1).to(torch.int64).contiguous()
+    if seg.numel() != nnz:
+      raise ValueError("ids and segment_ids must have the same number of elements: %d vs %d" % (nnz, seg.numel()))
+    w, d = self._pooled_operands(nnz, weights, default_row)
     out = torch.empty((int(n_rows), self._dim), dtype=torch.float32, device=self._device)
     return ids, seg, w, d, out
 
@@ -291,7 +301,6 @@ class _DeviceTable:
     seg ascending int64, weights float32 or None (all 1), combiner 0 sum / 1 mean / 2 sqrtn.  float32 / float16 / bfloat16 rows,
     dim % 4 == 0, dim <= 256 (TfraError UNSUPPORTED otherwise).  Bit-identical to find + device_ops.sparse_segment_combine over
     idx = arange(nnz); no unique pass, nothing read on the host."""
-    from .device_ops import _workspace
     ids, seg, w, d, out = self._find_combine_args(ids, seg, weights, n_rows, default_row)
     _capi.call("tfra_table_find_combine", self._h, _workspace(self._device), ids.numel(), _ptr(ids), _ptr(seg), _ptr(w), int(combiner),
                int(n_rows), _ptr(d), _ptr(out), _stream(self._device))
@@ -302,24 +311,13 @@ class _DeviceTable:
     flags, fill id, default row, out), checked and on the table's device (find_combine_ragged and find_combine_ragged_many share
     it).  Shapes only: the content of row_splits is the kernel's business (it clamps), nothing is read on the host."""
     ids = self._keys(ids).reshape(-1)
-    nnz = ids.numel()
     rs = torch.as_tensor(row_splits, device=self._device).reshape(-1)
     if rs.dtype not in (torch.int32, torch.int64):
       raise TypeError("row_splits must be int32 or int64, got %s" % rs.dtype)
     if rs.numel() < 1:
       raise ValueError("row_splits needs n_rows + 1 >= 1 elements")
     rs = rs.to(torch.int64).contiguous()   # int32 splits are widened
-    w = None
-    if weights is not None:
-      w = torch.as_tensor(weights, device=self._device).reshape(-1).to(torch.float32).contiguous()
-      if w.numel() != nnz:
-        raise ValueError("weights must have one element per id")
-    d = self._default_value if default_row is None else torch.as_tensor(default_row, device=self._device)
-    if d.dtype != self._value_dtype:
-      raise TypeError("default values must be dtype %s, got %s" % (self._value_dtype, d.dtype))
-    if d.numel() != self._dim:
-      raise ValueError("default_row must be one row of dim=%d elements, got %d" % (self._dim, d.numel()))
-    d = d.contiguous()
+    w, d = self._pooled_operands(ids.numel(), weights, default_row)
     flags = (_capi.RAGGED_PRUNE if prune else 0) | (_capi.RAGGED_FILL if fill_id is not None else 0)
     out = torch.empty((rs.numel() - 1, self._dim), dtype=torch.float32, device=self._device)
     return rs, ids, w, flags, (0 if fill_id is None else int(fill_id)), d, out
@@ -549,7 +547,6 @@ class SparsePlan:
     """The plan's distinct ids grouped by owner (tfra_plan_partition: tfra_partition over the plan's keys, in place of
     tf.unique + dynamic_partition): owner-major ids [n], perm [n] (plan index of each owner-major row), counts
     [num_shards] (device).  Entries past sum(counts) are unspecified.  Runs on the current stream after the build."""
-    from .device_ops import _workspace
     dev = self._device
     keys_out = torch.empty(self.n, dtype=torch.int64, device=dev)
     perm = torch.empty(self.n, dtype=torch.int32, device=dev)
@@ -865,90 +862,97 @@ class HkvHashTable(_LookupInterfaceMirror):
     return self._table.export_all(with_scores=True, values=True, split_size=split_size)
 
 
+def _device_table(x):
+  """`x` if it is a _DeviceTable, the device table of a CuckooHashTable / HkvHashTable."""
+  return getattr(x, "_table", x)
+
+
+def _grouped_call(c_name, desc_type, who, owners, fill):
+  """The frame of the grouped calls (`find_combine_many`, `find_combine_ragged_many`, `apply_planned_combined_many`,
+  `build_plans_many`): ONE C call `c_name(workspace, n, descs, &launches, stream)` over one descriptor of `desc_type` per entry of
+  `owners`, on the current stream of the one device all of them live on.  An owner is a _DeviceTable, a CuckooHashTable /
+  HkvHashTable (whose device table is taken: `_device_table`) or a SparsePlan.  Member by member, the owner's device is compared
+  with the first one's (ValueError in the name of `who`), then `fill(descs[i], i)` checks the member's arguments and sets the
+  descriptor's fields behind struct_size.  What `fill` returns — the tensors whose data_ptr() it stored — stays referenced here
+  until the C call has returned.  Returns the number of kernel launches the call enqueued."""
+  descs = (desc_type * len(owners))()
+  keep, device = [], _device_table(owners[0])._device
+  for i, owner in enumerate(owners):
+    dev = _device_table(owner)._device
+    if dev != device:
+      raise ValueError("%s: all tables must live on one device (%s and %s)" % (who, device, dev))
+    descs[i].struct_size = ctypes.sizeof(desc_type)
+    keep.append(fill(descs[i], i))
+  launches = ctypes.c_uint32(0)
+  _capi.call(c_name, _workspace(device), len(owners), ctypes.c_void_p(ctypes.addressof(descs)),
+             ctypes.c_void_p(ctypes.addressof(launches)), _stream(device))
+  return int(launches.value)
+
+
 def find_combine_many(requests, return_launches=False):
-  """The pooled lookups of a list of tables in ONE C call (tfra_multi_find_combine).  `requests`: a list of
-  (table, ids, seg, weights, combiner, n_rows[, default_row]) — `table` a _DeviceTable (or a CuckooHashTable / HkvHashTable, whose
-  device table is taken), the other arguments those of `_DeviceTable.find_combine`, handled the same way (int32 keys widened, the
-  default row falling back to the table's).  All tables live on one device.  Returns the [n_rows, dim] float32 results in the
-  requests' order, each bit-identical to `find_combine` of its request (with return_launches: also the number of kernel launches
-  the call enqueued — it does not grow with the list)."""
-  from .device_ops import _workspace
-  n = len(requests)
-  if n == 0:
+  """The pooled lookups of a list of tables in ONE C call (tfra_multi_find_combine; the frame: `_grouped_call`).  `requests`: a
+  list of (table, ids, seg, weights, combiner, n_rows[, default_row]), the arguments behind `table` those of
+  `_DeviceTable.find_combine`, handled the same way (int32 keys widened, the default row falling back to the table's).  Returns
+  the [n_rows, dim] float32 results in the requests' order, each bit-identical to `find_combine` of its request (with
+  return_launches: also the number of kernel launches the call enqueued — it does not grow with the list)."""
+  if not requests:
     return ([], 0) if return_launches else []
-  descs = (_capi.FindCombineDesc * n)()
-  keep, outs, device = [], [], None
-  for i, req in enumerate(requests):
+  outs = []
+
+  def fill(e, i):
+    req = requests[i]
     table, ids, seg, weights, combiner, n_rows = req[:6]
     default_row = req[6] if len(req) > 6 else None
-    table = getattr(table, "_table", table)
-    if device is None:
-      device = table._device
-    elif table._device != device:
-      raise ValueError("find_combine_many: all tables must live on one device (%s and %s)" % (device, table._device))
+    table = _device_table(table)
     ids, seg, w, d, out = table._find_combine_args(ids, seg, weights, n_rows, default_row)
-    keep.append((ids, seg, w, d))
     outs.append(out)
-    e = descs[i]
-    e.struct_size = ctypes.sizeof(_capi.FindCombineDesc)
-    e.combiner = int(combiner)
-    e.table = table._h.value
+    e.combiner, e.table = int(combiner), table._h.value
     e.nnz, e.ids, e.seg, e.weights = ids.numel(), ids.data_ptr(), seg.data_ptr(), (w.data_ptr() if w is not None else None)
     e.n_rows, e.default_row, e.out = int(n_rows), d.data_ptr(), out.data_ptr()
-  launches = ctypes.c_uint32(0)
-  _capi.call("tfra_multi_find_combine", _workspace(device), n, ctypes.c_void_p(ctypes.addressof(descs)),
-             ctypes.c_void_p(ctypes.addressof(launches)), _stream(device))
-  return (outs, int(launches.value)) if return_launches else outs
+    return ids, seg, w, d
+
+  launches = _grouped_call("tfra_multi_find_combine", _capi.FindCombineDesc, "find_combine_many", [r[0] for r in requests], fill)
+  return (outs, launches) if return_launches else outs
 
 
 def find_combine_ragged_many(requests, return_launches=False):
-  """The ragged pooled lookups of a list of tables in ONE C call (tfra_multi_find_combine_ragged).  `requests`: a list of
-  (table, row_splits, ids, weights, combiner[, prune[, fill_id[, default_row]]]) — `table` a _DeviceTable (or a CuckooHashTable /
-  HkvHashTable, whose device table is taken), the other arguments those of `_DeviceTable.find_combine_ragged`, handled the same
-  way.  All tables live on one device; a table may occur more than once.  Returns the [n_rows, dim] float32 results in the
-  requests' order, each bit-identical to `find_combine_ragged` of its request (with return_launches: also the number of kernel
-  launches the call enqueued: one per (value dtype, row-width class, safe-or-not) class in the list)."""
-  from .device_ops import _workspace
-  n = len(requests)
-  if n == 0:
+  """The ragged pooled lookups of a list of tables in ONE C call (tfra_multi_find_combine_ragged; the frame: `_grouped_call`).
+  `requests`: a list of (table, row_splits, ids, weights, combiner[, prune[, fill_id[, default_row]]]), the arguments behind
+  `table` those of `_DeviceTable.find_combine_ragged`, handled the same way.  A table may occur more than once.  Returns the
+  [n_rows, dim] float32 results in the requests' order, each bit-identical to `find_combine_ragged` of its request (with
+  return_launches: also the number of kernel launches the call enqueued: one per (value dtype, row-width class, safe-or-not)
+  class in the list)."""
+  if not requests:
     return ([], 0) if return_launches else []
-  descs = (_capi.FindCombineRaggedDesc * n)()
-  keep, outs, device = [], [], None
-  for i, req in enumerate(requests):
+  outs = []
+
+  def fill(e, i):
+    req = requests[i]
     table, row_splits, ids, weights, combiner = req[:5]
     prune = req[5] if len(req) > 5 else False
     fill_id = req[6] if len(req) > 6 else None
     default_row = req[7] if len(req) > 7 else None
-    table = getattr(table, "_table", table)
-    if device is None:
-      device = table._device
-    elif table._device != device:
-      raise ValueError("find_combine_ragged_many: all tables must live on one device (%s and %s)" % (device, table._device))
-    rs, ids, w, flags, fill, d, out = table._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row)
-    keep.append((rs, ids, w, d))
+    table = _device_table(table)
+    rs, ids, w, flags, fill_key, d, out = table._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row)
     outs.append(out)
-    e = descs[i]
-    e.struct_size = ctypes.sizeof(_capi.FindCombineRaggedDesc)
-    e.combiner = int(combiner)
-    e.table = table._h.value
+    e.combiner, e.table = int(combiner), table._h.value
     e.n_rows, e.row_splits = rs.numel() - 1, rs.data_ptr()
     e.nnz, e.ids, e.weights = ids.numel(), ids.data_ptr(), (w.data_ptr() if w is not None else None)
-    e.flags, e.reserved, e.fill_id = flags, 0, fill
+    e.flags, e.reserved, e.fill_id = flags, 0, fill_key
     e.default_row, e.out = d.data_ptr(), out.data_ptr()
-  launches = ctypes.c_uint32(0)
-  _capi.call("tfra_multi_find_combine_ragged", _workspace(device), n, ctypes.c_void_p(ctypes.addressof(descs)),
-             ctypes.c_void_p(ctypes.addressof(launches)), _stream(device))
-  return (outs, int(launches.value)) if return_launches else outs
+    return rs, ids, w, d
+
+  launches = _grouped_call("tfra_multi_find_combine_ragged", _capi.FindCombineRaggedDesc, "find_combine_ragged_many",
+                           [r[0] for r in requests], fill)
+  return (outs, launches) if return_launches else outs
 
 
 def apply_planned_combined_many(requests, p_list, sync=True):
-  """The combined write-backs of a list of tables in ONE C call (tfra_multi_apply_planned_combined).  `requests`: a list of
-  (table, plan, grad_out, seg, weights, combiner, default_row) — `table` a _DeviceTable (or a CuckooHashTable / HkvHashTable,
-  whose device table is taken), the other arguments those of `_DeviceTable.apply_planned_combined`, handled the same way.
-  `p_list`: the optimizer parameters (`_capi.OptParams`) of each request, or one for all.  All tables live on one device and
-  each table and each plan occurs once.  Every table ends bit-identical to `apply_planned_combined` of its request.  Returns the
-  number of kernel launches the call enqueued — it does not grow with the list."""
-  from .device_ops import _workspace
+  """The combined write-backs of a list of tables in ONE C call (tfra_multi_apply_planned_combined; the frame: `_grouped_call`).
+  `requests`: a list of (table, plan, grad_out, seg, weights, combiner, default_row), the arguments behind `table` those of
+  `_DeviceTable.apply_planned_combined`, handled the same way.  `p_list`: the optimizer parameters (`_capi.OptParams`) of each
+  request, or one for all.  Each table and each plan occurs once.  Every table ends bit-identical to `apply_planned_combined` of
+  its request.  Returns the number of kernel launches the call enqueued — it does not grow with the list."""
   n = len(requests)
   if n == 0:
     return 0
@@ -956,42 +960,34 @@ def apply_planned_combined_many(requests, p_list, sync=True):
     p_list = [p_list] * n
   if len(p_list) != n:
     raise ValueError("apply_planned_combined_many: %d requests but %d optimizer parameter sets" % (n, len(p_list)))
-  descs = (_capi.ApplyCombinedDesc * n)()
-  keep, plans, device = [], [], None
-  for i, req in enumerate(requests):
-    table, plan, grad_out, seg, weights, combiner, default_row = req
-    table = getattr(table, "_table", table)
-    if device is None:
-      device = table._device
-    elif table._device != device:
-      raise ValueError("apply_planned_combined_many: all tables must live on one device (%s and %s)" % (device, table._device))
+
+  def fill(e, i):
+    table, plan, grad_out, seg, weights, combiner, default_row = requests[i]
+    table = _device_table(table)
     grad_out, seg, w, d = table._apply_combined_args(plan, grad_out, seg, weights, default_row)
-    keep.append((grad_out, seg, w, d, p_list[i]))
-    plans.append(plan)
-    e = descs[i]
-    e.struct_size = ctypes.sizeof(_capi.ApplyCombinedDesc)
-    e.combiner = int(combiner)
-    e.table = table._h.value
-    e.opt = ctypes.addressof(p_list[i])
-    e.plan = plan._h.value
+    e.combiner, e.table = int(combiner), table._h.value
+    e.opt, e.plan = ctypes.addressof(p_list[i]), plan._h.value
     e.grad_out, e.seg, e.weights = grad_out.data_ptr(), seg.data_ptr(), (w.data_ptr() if w is not None else None)
     e.n_rows, e.param_default_row = grad_out.shape[0], d.data_ptr()
-  stream = torch.cuda.current_stream(device)
+    return grad_out, seg, w, d, p_list[i]
+
+  stream = torch.cuda.current_stream(_device_table(requests[0][0])._device)
+  plans = [req[1] for req in requests]
   if sync:
     for plan in plans:
       plan._wait_built(stream)
-  launches = ctypes.c_uint32(0)
-  _capi.call("tfra_multi_apply_planned_combined", _workspace(device), n, ctypes.c_void_p(ctypes.addressof(descs)),
-             ctypes.c_void_p(ctypes.addressof(launches)), _stream(device))
+  launches = _grouped_call("tfra_multi_apply_planned_combined", _capi.ApplyCombinedDesc, "apply_planned_combined_many",
+                           [r[0] for r in requests], fill)
   if sync:
     for plan in plans:
       plan._mark_used(stream)
-  return int(launches.value)
+  return launches
 
 
 def build_plans_many(plans, ids_list, return_launches=False):
-  """The builds of a list of `SparsePlan`s in ONE C call (tfra_multi_sparse_plan_build), on the CURRENT stream of the plans'
-  device: plan i ends as `plans[i].build(ids_list[i])` leaves it — the same CSR per key, bit-identical write-backs through it.
+  """The builds of a list of `SparsePlan`s in ONE C call (tfra_multi_sparse_plan_build; the frame: `_grouped_call`), on the CURRENT
+  stream of the plans' device: plan i ends as `plans[i].build(ids_list[i])` leaves it — the same CSR per key, bit-identical
+  write-backs through it.
   Around the call each plan gets what `SparsePlan.build` does for it: the ids as a contiguous int64 tensor kept alive on the plan,
   the wait for the plan's last use, `record_stream`, and the `_built` event behind the call.  All plans live on one device, have a
   dim > 0 (the assign-only plan is one kernel already) and occur once.  The call's workspace is `device_ops._workspace(device)`,
@@ -999,7 +995,6 @@ def build_plans_many(plans, ids_list, return_launches=False):
   the scratch of the main stream's grouped calls (`find_combine_many`, `apply_planned_combined_many`), which may be in flight at
   the same time.  Returns the plans (with return_launches: also the number of kernel launches the call enqueued — it does not grow
   with the list)."""
-  from .device_ops import _workspace
   plans = list(plans)
   n = len(plans)
   if len(ids_list) != n:
@@ -1011,21 +1006,18 @@ def build_plans_many(plans, ids_list, return_launches=False):
     if plan._device != device:
       raise ValueError("build_plans_many: all plans must live on one device (%s and %s)" % (device, plan._device))
   stream = torch.cuda.current_stream(device)
-  descs = (_capi.PlanBuildDesc * n)()
   flat = []
-  for i, (plan, ids) in enumerate(zip(plans, ids_list)):
-    ids = ids.to(device, torch.int64).contiguous().reshape(-1)
+
+  def fill(e, i):
+    plan, ids = plans[i], ids_list[i].to(device, torch.int64).contiguous().reshape(-1)
     if plan._used is not None:
       stream.wait_event(plan._used)     # the previous batch's sums/apply still read the plan buffers
     ids.record_stream(stream)
     flat.append(ids)
-    e = descs[i]
-    e.struct_size = ctypes.sizeof(_capi.PlanBuildDesc)
     e.plan, e.n, e.ids, e.dim = plan._h.value, ids.numel(), (ids.data_ptr() if ids.numel() else None), plan._dim
-  launches = ctypes.c_uint32(0)
-  _capi.call("tfra_multi_sparse_plan_build", _workspace(device), n, ctypes.c_void_p(ctypes.addressof(descs)),
-             ctypes.c_void_p(ctypes.addressof(launches)), _stream(device))
+
+  launches = _grouped_call("tfra_multi_sparse_plan_build", _capi.PlanBuildDesc, "build_plans_many", plans, fill)
   for plan, ids in zip(plans, flat):
     plan.ids, plan.n = ids, ids.numel()   # keeps the ids alive until the next build
     plan._built.record(stream)
-  return (plans, int(launches.value)) if return_launches else plans
+  return (plans, launches) if return_launches else plans

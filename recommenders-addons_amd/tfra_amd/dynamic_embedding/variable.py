@@ -672,31 +672,29 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=
   return_trainable: also returns a SparseTrainableWrapper; `DynamicEmbeddingOptimizer.apply_combined_gradients` applies the
   gradient of the result through it.  plan_writeback (with return_trainable): build the write-back plan over the entry ids
   at lookup time, on the Variable's second stream (as embedding_lookup's plan_writeback)."""
-  if combiner not in ("mean", "sqrtn", "sum"):
-    raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+  _check_combiner(combiner)
   indices, ids = sp_ids
   indices = torch.as_tensor(indices, device=params._primary)
   seg = (indices[:, 0] if indices.dim() == 2 else indices).to(torch.int64)
   ids = torch.as_tensor(ids, device=params._primary)
   w = sp_weights if sp_weights is None else torch.as_tensor(sp_weights, dtype=torch.float32, device=params._primary)
-  if _pooled_forward(params, max_norm):
-    # the pooled read: one probe + row read per entry, combined in registers — no unique pass, no [U, dim] rows, no host read of
-    # a count (the result is bit-identical to the chain below)
-    n = int(seg.max().item()) + 1 if num_rows is None else num_rows
-    out = params.lookup_combined(ids, seg, w, combiner, n)
-    if not return_trainable:
-      return out
-    e_ids, e_seg, e_w = _entries if _entries is not None else (ids.reshape(-1), seg, w)   # ids keep their key dtype
-    tw = SparseTrainableWrapper(params, None, None, None, seg, w, combiner, n,
-                                _out_shape if _out_shape is not None else (n, params.dim), e_ids, e_seg, e_w,
-                                max_norm=max_norm, plan_writeback=plan_writeback, lookup_ids=ids)
-    return out, tw
-  uniq, idx, cnt = device_ops.unique(ids)
+  pooled = _pooled_forward(params, max_norm)
+  if not pooled:
+    uniq, idx, cnt = device_ops.unique(ids)
   n = int(seg.max().item()) + 1 if num_rows is None else num_rows
   if return_trainable:
     e_ids, e_seg, e_w = _entries if _entries is not None else (ids.reshape(-1), seg, w)   # ids keep their key dtype
-    tw = SparseTrainableWrapper(params, uniq.reshape(-1), idx, cnt, seg, w, combiner, n,
-                                _out_shape if _out_shape is not None else (n, params.dim), e_ids, e_seg, e_w,
+    shape = _out_shape if _out_shape is not None else (n, params.dim)
+  if pooled:
+    # the pooled read: one probe + row read per entry, combined in registers — no unique pass, no [U, dim] rows, no host read of
+    # a count (the result is bit-identical to the chain below)
+    out = params.lookup_combined(ids, seg, w, combiner, n)
+    if not return_trainable:
+      return out
+    return out, SparseTrainableWrapper(params, None, None, None, seg, w, combiner, n, shape, e_ids, e_seg, e_w, max_norm=max_norm,
+                                       plan_writeback=plan_writeback, lookup_ids=ids)
+  if return_trainable:
+    tw = SparseTrainableWrapper(params, uniq.reshape(-1), idx, cnt, seg, w, combiner, n, shape, e_ids, e_seg, e_w,
                                 max_norm=max_norm, plan_writeback=plan_writeback)
     ue = tw.read_value()
   else:
@@ -714,6 +712,28 @@ def _per_table(value, n, what):
       raise ValueError("%s: %d entries for %d tables" % (what, len(value), n))
     return list(value)
   return [value] * n
+
+
+def _check_combiner(combiner):
+  if combiner not in ("mean", "sqrtn", "sum"):
+    raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+
+
+def _rows_in_one_read(rows, unknown):
+  """rows[i] = the highest row id + 1 for every (i, row ids) of `unknown` — members of one device, each with at least one entry —
+  from one host read for all of them."""
+  if unknown:
+    for (i, _), top in zip(unknown, torch.stack([r.max() for _, r in unknown]).tolist()):
+      rows[i] = int(top) + 1
+
+
+def _wrap_grouped(device, params_list, members, outs, entry_ids, plan_writeback, wrapper, results):
+  """results[i] = (out, SparseTrainableWrapper) behind a grouped forward, for the members (i, ...) of `device` and their `outs`.
+  The members' write-back plans over entry_ids[i]: one grouped build on one side stream (None: at most one member takes a plan,
+  and its wrapper starts it as the single lookup does: own_plan).  `wrapper(member, own_plan, entry_plan)` makes the wrapper."""
+  started = _plans_at_lookup_many(device, [(m[0], params_list[m[0]], entry_ids[m[0]]) for m in members]) if plan_writeback else None
+  for m, out in zip(members, outs):
+    results[m[0]] = (out, wrapper(m, plan_writeback and started is None, None if started is None else started.get(m[0])))
 
 
 def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None, combiner="mean", max_norm=None,
@@ -738,8 +758,7 @@ def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None,
   entries = _per_table(None if _entries_list is None else list(_entries_list), n_t, "_entries_list")
   shapes = _per_table(None if _out_shapes is None else list(_out_shapes), n_t, "_out_shapes")
   for c in combiners:
-    if c not in ("mean", "sqrtn", "sum"):
-      raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+    _check_combiner(c)
   results = [None] * n_t
   groups = {}   # device -> [(i, ids, seg, w)]
   for i, params in enumerate(params_list):
@@ -755,10 +774,7 @@ def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None,
     w = weights[i] if weights[i] is None else torch.as_tensor(weights[i], dtype=torch.float32, device=params._primary)
     groups.setdefault(params._primary, []).append((i, ids, seg, w))
   for device, members in groups.items():
-    unknown = [m for m in members if rows[m[0]] is None]
-    if unknown:   # the row counts of all of them in one host read
-      for m, top in zip(unknown, torch.stack([m[2].max() for m in unknown]).tolist()):
-        rows[m[0]] = int(top) + 1
+    _rows_in_one_read(rows, [(m[0], m[2]) for m in members if rows[m[0]] is None])
     reqs = []
     for i, ids, seg, w in members:
       t = params_list[i]._tables[0]
@@ -770,17 +786,15 @@ def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None,
       continue
     ent = {i: (entries[i] if entries[i] is not None else (ids.reshape(-1), seg, w))   # ids keep their key dtype
            for i, ids, seg, w in members}
-    # the members' write-back plans: one grouped build on one side stream (None: at most one member takes a plan, and its wrapper
-    # starts it as the single lookup does)
-    started = _plans_at_lookup_many(device, [(i, params_list[i], ent[i][0]) for i, _, _, _ in members]) if plan_writeback else None
-    for (i, ids, seg, w), out in zip(members, outs):
+
+    def wrapper(member, own_plan, entry_plan):
+      i, ids, seg, w = member
       params, n = params_list[i], rows[i]
-      e_ids, e_seg, e_w = ent[i]
-      tw = SparseTrainableWrapper(params, None, None, None, seg, w, combiners[i], n,
-                                  shapes[i] if shapes[i] is not None else (n, params.dim), e_ids, e_seg, e_w,
-                                  max_norm=max_norm, plan_writeback=plan_writeback and started is None, lookup_ids=ids,
-                                  entry_plan=None if started is None else started.get(i))
-      results[i] = (out, tw)
+      return SparseTrainableWrapper(params, None, None, None, seg, w, combiners[i], n,
+                                    shapes[i] if shapes[i] is not None else (n, params.dim), *ent[i], max_norm=max_norm,
+                                    plan_writeback=own_plan, lookup_ids=ids, entry_plan=entry_plan)
+
+    _wrap_grouped(device, params_list, members, outs, {i: e[0] for i, e in ent.items()}, plan_writeback, wrapper, results)
   return results
 
 
@@ -868,8 +882,7 @@ def safe_embedding_lookup_sparse(params, sp_ids, sparse_weights=None, combiner="
   (`_prune_invalid_weights`, :374-376); rows left without entries yield zeros, or the embedding of
   `default_id` (`sparse_fill_empty_rows`, :379-408); leading dims are flattened for the lookup and restored
   on the result (:356-367, 411-424)."""
-  if combiner not in ("mean", "sqrtn", "sum"):
-    raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+  _check_combiner(combiner)
   rows, ids, w, n, entries, out_shape, lead = _safe_sparse_args(params, sp_ids, sparse_weights, combiner, default_id,
                                                                  return_trainable, num_rows)
   out = embedding_lookup_sparse(params, (rows, ids), w, combiner=combiner, max_norm=max_norm,
@@ -894,8 +907,7 @@ def safe_embedding_lookup_sparse_many(params_list, sp_ids_list, sparse_weights_l
   default_ids = _per_table(default_id, n_t, "default_id")
   num = _per_table(num_rows, n_t, "num_rows")
   for c in combiners:
-    if c not in ("mean", "sqrtn", "sum"):
-      raise ValueError("combiner must be one of 'mean', 'sqrtn' or 'sum'")
+    _check_combiner(c)
   unknown = {}   # device -> [(i, row ids)]: rank 2, no dense_shape, no num_rows, at least one entry
   for i, params in enumerate(params_list):
     if num[i] is None and len(sp_ids_list[i]) == 2:
@@ -903,8 +915,7 @@ def safe_embedding_lookup_sparse_many(params_list, sp_ids_list, sparse_weights_l
       if indices.numel() and (indices.dim() == 1 or indices.shape[1] <= 2):
         unknown.setdefault(params._primary, []).append((i, indices[:, 0] if indices.dim() == 2 else indices))
   for members in unknown.values():
-    for (i, _), top in zip(members, torch.stack([r.max() for _, r in members]).tolist()):
-      num[i] = int(top) + 1
+    _rows_in_one_read(num, members)
   args = [_safe_sparse_args(params_list[i], sp_ids_list[i], weights[i], combiners[i], default_ids[i], return_trainable, num[i])
           for i in range(n_t)]
   outs = embedding_lookup_sparse_many(params_list, [(a[0], a[1]) for a in args], [a[2] for a in args], combiner=combiners,

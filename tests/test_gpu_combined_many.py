@@ -5,19 +5,16 @@ The reference of every case is a TWIN table driven through the single call (tfra
 Both forms run the same device functions (hot_sums_body / apply_csr_body, csrc/tfra_apply.hip; comb_den_row / comb_ent_one,
 csrc/tfra_combine_device.h), so they must agree BIT FOR BIT: every comparison is torch.equal on the bit patterns of the key-sorted
 exported rows and of every slot, after two steps (the second one updates rows the first one wrote).  No tolerance."""
-import ctypes
 
 import numpy as np
 import pytest
 
-from tests import test_gpu_pooled_lookup as H
+from tests.sparse_helpers import (COMB, N_ROWS, Calls, Case, T, _export_state, assert_twins, desc_of, grad, key_of, make_var, many,
+                                  opt_of, raw_many, writeback_batch as batch)
 
 pytestmark = pytest.mark.gpu
 
-COMB = H.COMB
 INVALID, UNSUPPORTED = -1, -6
-T, bits, Calls, _export_state = H.T, H.bits, H.Calls, H._export_state
-N_ROWS, PER_ROW, UNIVERSE, PLANTED = 256, 8, 500, 7
 
 
 @pytest.fixture(scope="module")
@@ -25,102 +22,6 @@ def env():
   import torch
   import tfra_amd.dynamic_embedding as de
   return torch, de
-
-
-def opt_of(de, name):
-  return {"sgd": lambda: de.optimizers.SGD(0.1), "adam": lambda: de.optimizers.Adam(1e-3, 0.9, 0.999, 1e-8),
-          "adagrad": lambda: de.optimizers.Adagrad(0.05, 0.1), "ftrl": lambda: de.optimizers.Ftrl(0.05)}[name]()
-
-
-def key_of(rank):
-  return rank.astype(np.int64) * 7919 - 1_000_000
-
-
-def make_var(torch, de, opt, name, dim, vdtype="float32", fill=True, **kw):
-  """A one-shard variable with the rule's slots; holds the keys of rank % 5 != 0 (the others enter from the default row)."""
-  var = de.Variable(dim=dim, name=name, initializer=0.5, value_dtype=getattr(torch, vdtype),
-                    **de.DynamicEmbeddingOptimizer.variable_kwargs(opt), **kw)
-  if fill:
-    r = np.arange(UNIVERSE)
-    keys = T(torch, key_of(r[r % 5 != 0]))
-    g = torch.Generator(device="cuda").manual_seed(dim)
-    var.upsert(keys, torch.randn((keys.numel(), dim), generator=g, device="cuda").to(var.value_dtype))
-  return var
-
-
-_BATCH = {}
-
-
-def batch(torch, seed, n_rows=N_ROWS, per_row=PER_ROW, planted=600):
-  """(ids, seg, w): Zipf(1.2) % 500 ids, so that many keys occur more than 8 times (the partial-sum route), one id planted 600
-  times (more than one 512-entry bin), ~20 % of the ids not resident, one row whose weights are all zero, three seg values
-  >= n_rows at the tail."""
-  if (seed, n_rows, per_row) not in _BATCH:
-    rng = np.random.default_rng(seed)
-    nnz = n_rows * per_row
-    rank = (rng.zipf(1.2, size=nnz) - 1) % UNIVERSE
-    if planted:
-      rank[rng.choice(nnz, size=min(planted, nnz // 3), replace=False)] = PLANTED
-    seg = np.repeat(np.arange(n_rows, dtype=np.int64), per_row)
-    seg[-3:] = [n_rows, n_rows, n_rows + 44]
-    w = rng.uniform(0.1, 2.0, size=nnz).astype(np.float32)
-    w[seg == 5] = 0.0
-    _BATCH[(seed, n_rows, per_row)] = (T(torch, key_of(rank)), T(torch, seg), T(torch, w))
-  return _BATCH[(seed, n_rows, per_row)]
-
-
-def grad(torch, seed, n_rows, dim, step=0):
-  g = torch.Generator(device="cuda").manual_seed(1000 * seed + step)
-  return torch.randn((n_rows, dim), generator=g, device="cuda") * 0.01
-
-
-class Case:
-  """One descriptor: the table of the grouped call, its twin, and the inputs both get."""
-
-  def __init__(self, torch, de, opt, name, dim, vdtype="float32", comb="mean", weighted=True, seed=1, inputs=None, n_rows=None, **kw):
-    from tfra_amd.dynamic_embedding.table_ops import SparsePlan
-    self.var, self.twin = make_var(torch, de, opt, name + "_m", dim, vdtype, **kw), make_var(torch, de, opt, name + "_t", dim, vdtype, **kw)
-    self.ids, self.seg, w = inputs if inputs is not None else batch(torch, seed)
-    self.w = w if weighted else None
-    self.comb, self.dim, self.seed = COMB[comb], dim, seed
-    self.n_rows = n_rows if n_rows is not None else N_ROWS
-    self.plan, self.plan_t = SparsePlan(self.var._primary, dim), SparsePlan(self.var._primary, dim)
-
-  def table(self, twin=False):
-    return (self.twin if twin else self.var)._tables[0]
-
-  def G(self, torch, step):
-    return grad(torch, self.seed, self.n_rows, self.dim, step)
-
-  def request(self, torch, step, build=True):
-    if build:
-      self.plan.build(self.ids)
-    t = self.table()
-    return (t._table, self.plan, self.G(torch, step), self.seg, self.w, self.comb, t._default_value.to(torch.float32))
-
-  def single(self, torch, p, step, build=True):
-    if self.ids.numel() == 0:
-      return   # (nothing to write; the single call takes no plan that was never built with ids)
-    if build:
-      self.plan_t.build(self.ids)
-    t = self.table(True)
-    t._table.apply_planned_combined(p, self.plan_t, self.G(torch, step), self.seg, self.w, self.comb, t._default_value.to(torch.float32))
-
-
-def many(reqs, p):
-  from tfra_amd.dynamic_embedding import table_ops
-  return table_ops.apply_planned_combined_many(reqs, p)
-
-
-def assert_twins(torch, de, opt, cases):
-  deo = de.DynamicEmbeddingOptimizer(opt)
-  for i, c in enumerate(cases):
-    a, b = _export_state(torch, de, deo, opt, c.var), _export_state(torch, de, deo, opt, c.twin)
-    assert len(a) == len(b) == 2 + len(opt.slots)
-    for j, (x, y) in enumerate(zip(a, b)):
-      assert torch.equal(x, y), "descriptor %d: field %d differs from the twin driven by the single call" % (i, j)
-    c.table()._table.check_errors()
-    c.table(True)._table.check_errors()
 
 
 def two_steps(torch, de, opt, cases, expect_launches=None):
@@ -195,29 +96,6 @@ def test_26_tables_6_launches_52_tables_the_same_6(env, n_tables):
 
 
 # ---- 4. one bad descriptor and nothing is written --------------------------------------------------------------------------------
-def desc_of(torch, req, p):
-  from tfra_amd import _capi
-  table, plan, G, seg, w, comb, d = req
-  e = _capi.ApplyCombinedDesc()
-  e.struct_size, e.combiner = ctypes.sizeof(_capi.ApplyCombinedDesc), int(comb)
-  e.table, e.opt, e.plan = table._h.value, ctypes.addressof(p), plan._h.value
-  e.grad_out, e.seg, e.weights = G.data_ptr(), seg.data_ptr(), (w.data_ptr() if w is not None else None)
-  e.n_rows, e.param_default_row = G.shape[0], d.data_ptr()
-  return e
-
-
-def raw_many(torch, descs):
-  from tfra_amd import _capi
-  from tfra_amd.dynamic_embedding.device_ops import _workspace
-  from tfra_amd.dynamic_embedding.table_ops import _stream
-  arr = (_capi.ApplyCombinedDesc * max(1, len(descs)))(*descs)
-  launches = ctypes.c_uint32(77)
-  dev = torch.device("cuda", torch.cuda.current_device())
-  rc = _capi.lib().tfra_multi_apply_planned_combined(_workspace(dev), len(descs), ctypes.c_void_p(ctypes.addressof(arr)),
-                                                     ctypes.c_void_p(ctypes.addressof(launches)), _stream(dev))
-  return rc, int(launches.value), _capi.lib().tfra_last_error().decode()
-
-
 BAD = ["int8_table", "misaligned_grad_out", "null_plan", "struct_size", "combiner_3", "plan_of_another_dim", "adam_without_slots",
        "same_table_twice", "same_plan_twice"]
 

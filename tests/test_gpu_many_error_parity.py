@@ -10,9 +10,7 @@ import ctypes
 
 import pytest
 
-from tests import test_gpu_combined_many as CM
-from tests import test_gpu_pooled_lookup as H
-from tests import test_gpu_pooled_many as PM
+from tests import sparse_helpers as H
 
 pytestmark = pytest.mark.gpu
 
@@ -53,11 +51,11 @@ def writeback(env):
   """Three tables of dim 64 with Adam's slots, N_ROWS rows each (the shapes of test_gpu_combined_many's bad-descriptor test), an
   int8 table and a table without slot fields."""
   torch, de = env
-  opt = CM.opt_of(de, "adam")
-  cases = [CM.Case(torch, de, opt, "ep_w%d" % i, 64, seed=60 + i) for i in range(3)]
+  opt = H.opt_of(de, "adam")
+  cases = [H.Case(torch, de, opt, "ep_w%d" % i, 64, seed=60 + i) for i in range(3)]
   t8 = de.CuckooHashTable(torch.int64, torch.int8, torch.zeros(64, dtype=torch.int8), name="ep_i8", dim=64, aux_fields=2)
   t8.insert(torch.arange(8, device="cuda"), torch.ones((8, 64), device="cuda").to(torch.int8))
-  bare = CM.make_var(torch, de, CM.opt_of(de, "sgd"), "ep_bare", 64)
+  bare = H.make_var(torch, de, H.opt_of(de, "sgd"), "ep_bare", 64)
   return opt, cases, t8, bare
 
 
@@ -84,16 +82,16 @@ def test_write_back_single_and_grouped_refuse_alike(env, writeback, what):
   p = opt.params(1)
   case = cases[WRITEBACK_FAULTS.index(what) % 3]
   req = case.request(torch, 1)
-  e = CM.desc_of(torch, req, p)
+  e = H.desc_of(torch, req, p)
   keep, want = [req], INVALID
-  sgd = CM.opt_of(de, "sgd")
+  sgd = H.opt_of(de, "sgd")
   watched = [lambda: table_state(torch, t8), lambda: H._export_state(torch, de, de.DynamicEmbeddingOptimizer(sgd), sgd, bare)]
   deo = de.DynamicEmbeddingOptimizer(opt)
   watched += [lambda c=c: H._export_state(torch, de, deo, opt, c.var) for c in cases]
   if what == "int8_table":
     e.table, want = t8._table._h.value, UNSUPPORTED
   elif what == "misaligned_grad_out":
-    G = torch.zeros(CM.N_ROWS * 64 + 4, device="cuda")[1:1 + CM.N_ROWS * 64].view(CM.N_ROWS, 64)
+    G = torch.zeros(H.N_ROWS * 64 + 4, device="cuda")[1:1 + H.N_ROWS * 64].view(H.N_ROWS, 64)
     keep.append(G)
     e.grad_out, want = G.data_ptr(), UNSUPPORTED
     assert G.data_ptr() % 16 == 4
@@ -113,7 +111,7 @@ def test_write_back_single_and_grouped_refuse_alike(env, writeback, what):
   before = [w() for w in watched]
   torch.cuda.synchronize()
   single = single_apply(torch, e)
-  rc, launches, msg = CM.raw_many(torch, [e])
+  rc, launches, msg = H.raw_many(torch, [e])
   print(what, "single:", single, "grouped:", (rc, msg))
   assert single[0] == want
   assert launches == 0
@@ -154,7 +152,7 @@ def test_lookup_single_and_grouped_refuse_alike(env, bad):
   out = torch.full((4, t._table.dim + 4), 7.0, device="cuda")
   descs = (_capi.FindCombineDesc * 1)()
   e = descs[0]
-  PM._desc(e, t, ids_t, seg_t, 4, out)
+  H._desc(e, t, ids_t, seg_t, 4, out)
   want = UNSUPPORTED
   if bad == "combiner3":
     e.combiner, want = 3, INVALID
@@ -169,7 +167,7 @@ def test_lookup_single_and_grouped_refuse_alike(env, bad):
   torch.cuda.synchronize()
   single = single_find(torch, t, e)
   launches = ctypes.c_uint32(99)
-  grouped = PM._raw(torch, descs, launches=launches)
+  grouped = H._raw(torch, descs, launches=launches)
   print(bad, "single:", single, "grouped:", grouped)
   assert single[0] == want
   assert launches.value == 0

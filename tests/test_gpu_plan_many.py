@@ -11,31 +11,12 @@ import ctypes
 import numpy as np
 import pytest
 
-from tests import test_gpu_combined_many as CM
+from tests import sparse_helpers as H
+from tests.sparse_helpers import Calls, T
 
 pytestmark = pytest.mark.gpu
 
 INVALID, UNSUPPORTED = -1, -6
-T = CM.T
-
-
-class Calls:
-  """Counts _capi.call by C function name."""
-
-  def __init__(self, monkeypatch):
-    from tfra_amd import _capi
-    self.n = {}
-    real = _capi.call
-
-    def counting(name, *args):
-      self.n[name] = self.n.get(name, 0) + 1
-      return real(name, *args)
-
-    monkeypatch.setattr(_capi, "call", counting)
-
-  def __getitem__(self, name):
-    return self.n.get(name, 0)
-
 
 @pytest.fixture(scope="module")
 def env():
@@ -204,21 +185,21 @@ def test_26_plans_take_3_launches_and_52_the_same_3(env):
 # ---- 7. the plans work -------------------------------------------------------------------------------------------------------------
 def test_tables_written_back_through_grouped_plans_equal_the_single_builds(env):
   torch, de, table_ops = env
-  adam = CM.opt_of(de, "adam")
+  adam = H.opt_of(de, "adam")
   shapes = [(32, "float32"), (64, "float32"), (128, "float32"), (64, "float16")]
-  cases = [CM.Case(torch, de, adam, "pm7_%d" % i, d, vdtype=vd, seed=70 + i) for i, (d, vd) in enumerate(shapes)]
+  cases = [H.Case(torch, de, adam, "pm7_%d" % i, d, vdtype=vd, seed=70 + i) for i, (d, vd) in enumerate(shapes)]
 
   def twin_request(c, step):
     t = c.table(True)
     return (t._table, c.plan_t, c.G(torch, step), c.seg, c.w, c.comb, t._default_value.to(torch.float32))
 
-  for step, p in ((1, adam.params(1)), (2, CM.opt_of(de, "sgd").params(2))):
+  for step, p in ((1, adam.params(1)), (2, H.opt_of(de, "sgd").params(2))):
     table_ops.build_plans_many([c.plan for c in cases], [c.ids for c in cases])   # set a: grouped
     for c in cases:
       c.plan_t.build(c.ids)                                                       # set b: one by one
-    CM.many([c.request(torch, step, build=False) for c in cases], p)
-    CM.many([twin_request(c, step) for c in cases], p)
-  CM.assert_twins(torch, de, adam, cases)
+    H.many([c.request(torch, step, build=False) for c in cases], p)
+    H.many([twin_request(c, step) for c in cases], p)
+  H.assert_twins(torch, de, adam, cases)
   # one plan of each set consumed by apply_planned on a dense [n, dim] gradient
   c = cases[1]
   table_ops.build_plans_many([cases[0].plan, c.plan], [cases[0].ids, c.ids])
@@ -228,7 +209,7 @@ def test_tables_written_back_through_grouped_plans_equal_the_single_builds(env):
   for twin, plan in ((False, c.plan), (True, c.plan_t)):
     t = c.table(twin)
     t._table.apply_planned(p, plan, g, t._default_value.to(torch.float32))
-  CM.assert_twins(torch, de, adam, cases)
+  H.assert_twins(torch, de, adam, cases)
 
 
 # ---- 8. one bad descriptor and nothing is built ----------------------------------------------------------------------------------
@@ -344,9 +325,9 @@ def test_side_stream_build_beside_grouped_lookups(env):
   share a staging ring or scratch."""
   torch, de, table_ops = env
   rng = np.random.default_rng(10)
-  sgd = CM.opt_of(de, "sgd")
+  sgd = H.opt_of(de, "sgd")
   dims = [64, 32, 128]
-  cases = [CM.Case(torch, de, sgd, "pm10_%d" % i, d, seed=100 + i) for i, d in enumerate(dims)]
+  cases = [H.Case(torch, de, sgd, "pm10_%d" % i, d, seed=100 + i) for i, d in enumerate(dims)]
   reqs = []
   for c in cases:
     t = c.table()
@@ -365,7 +346,7 @@ def test_side_stream_build_beside_grouped_lookups(env):
   torch.cuda.synchronize()
   for r in range(10):
     for o, q in zip(outs[r], quiet):
-      assert torch.equal(CM.bits(torch, o), CM.bits(torch, q)), r
+      assert torch.equal(H.bits(torch, o), H.bits(torch, q)), r
   for pl, a in zip(plans, rounds[-1]):
     assert same(canon(pl), canon_np(a)), a.size
 
@@ -376,18 +357,18 @@ ROWS = 8192   # x 1 id per row = PLAN_AT_LOOKUP_MIN_IDS entries
 
 def sparse_inputs(torch, seed, empty_row=None):
   rng = np.random.default_rng(seed)
-  rank = (rng.zipf(1.2, size=ROWS) - 1) % CM.UNIVERSE
+  rank = (rng.zipf(1.2, size=ROWS) - 1) % H.UNIVERSE
   seg = np.arange(ROWS, dtype=np.int64)
   if empty_row is not None:
     seg[empty_row] = empty_row - 1   # row `empty_row` has no entry, the row before has two
   w = rng.uniform(0.1, 2.0, size=ROWS).astype(np.float32)
-  return (T(torch, seg), T(torch, CM.key_of(rank))), T(torch, w)
+  return (T(torch, seg), T(torch, H.key_of(rank))), T(torch, w)
 
 
 def variables(torch, de, opt, tag):
   kw = de.DynamicEmbeddingOptimizer.variable_kwargs(opt)
   dev = dev_of(torch)
-  vs = [CM.make_var(torch, de, opt, "pm11%s_%d" % (tag, i), d) for i, d in enumerate((64, 32, 128))]
+  vs = [H.make_var(torch, de, opt, "pm11%s_%d" % (tag, i), d) for i, d in enumerate((64, 32, 128))]
   return vs + [de.Variable(dim=32, name="pm11%s_s" % tag, initializer=0.5, devices=[dev, dev], **kw)]
 
 
@@ -400,7 +381,7 @@ def test_python_surface_one_grouped_build_per_step(env, monkeypatch, safe):
   torch, de, table_ops = env
   from tfra_amd.dynamic_embedding import variable as V
   assert ROWS >= V.PLAN_AT_LOOKUP_MIN_IDS
-  opt = CM.opt_of(de, "adam")
+  opt = H.opt_of(de, "adam")
   tag = "s" if safe else "p"
   va, vb = variables(torch, de, opt, tag + "a"), variables(torch, de, opt, tag + "b")
   da, db = de.DynamicEmbeddingOptimizer(opt), de.DynamicEmbeddingOptimizer(opt)
@@ -409,7 +390,7 @@ def test_python_surface_one_grouped_build_per_step(env, monkeypatch, safe):
 
   def lookups(vs, plan_writeback):
     if safe:
-      res = de.safe_embedding_lookup_sparse_many(vs, sps, ws, combiner="mean", default_id=int(CM.key_of(np.array([3]))[0]),
+      res = de.safe_embedding_lookup_sparse_many(vs, sps, ws, combiner="mean", default_id=int(H.key_of(np.array([3]))[0]),
                                                  return_trainable=True, num_rows=ROWS, plan_writeback=plan_writeback)
     else:
       res = de.embedding_lookup_sparse_many(vs, sps, ws, combiner="mean", return_trainable=True, num_rows=ROWS,
@@ -417,7 +398,7 @@ def test_python_surface_one_grouped_build_per_step(env, monkeypatch, safe):
     return [tw for _, tw in res]
 
   for step, plan_writeback in ((1, True), (2, False)):
-    Gs = [CM.grad(torch, 110 + i, ROWS, v.dim, step) for i, v in enumerate(va)]
+    Gs = [H.grad(torch, 110 + i, ROWS, v.dim, step) for i, v in enumerate(va)]
     db.apply_combined_gradients(list(zip(Gs, lookups(vb, False))))
     calls = Calls(monkeypatch)
     tws = lookups(va, plan_writeback)
@@ -435,14 +416,14 @@ def test_python_surface_one_grouped_build_per_step(env, monkeypatch, safe):
     assert pools_are_full(va[:3])
   assert da.iterations == db.iterations == 2
   for a, b in zip(va, vb):
-    for x, y in zip(CM._export_state(torch, de, da, opt, a), CM._export_state(torch, de, db, opt, b)):
+    for x, y in zip(H._export_state(torch, de, da, opt, a), H._export_state(torch, de, db, opt, b)):
       assert torch.equal(x, y)
 
 
 def test_a_group_of_one_keeps_the_single_build(env, monkeypatch):
   torch, de, table_ops = env
-  opt = CM.opt_of(de, "sgd")
-  v = CM.make_var(torch, de, opt, "pm12", 64)
+  opt = H.opt_of(de, "sgd")
+  v = H.make_var(torch, de, opt, "pm12", 64)
   deo = de.DynamicEmbeddingOptimizer(opt)
   sp, w = sparse_inputs(torch, 120)
   for plan_writeback in (True, False):
@@ -450,6 +431,6 @@ def test_a_group_of_one_keeps_the_single_build(env, monkeypatch):
     (_, tw), = de.embedding_lookup_sparse_many([v], [sp], [w], combiner="sum", return_trainable=True, num_rows=ROWS,
                                                plan_writeback=plan_writeback)
     assert (tw.entry_plan is not None) == plan_writeback
-    deo.apply_combined_gradients_many([(CM.grad(torch, 120, ROWS, 64), tw)])
+    deo.apply_combined_gradients_many([(H.grad(torch, 120, ROWS, 64), tw)])
     assert calls["tfra_sparse_plan_build"] == 1 and calls["tfra_multi_sparse_plan_build"] == 0
     monkeypatch.undo()

@@ -11,11 +11,10 @@ import numpy as np
 import pytest
 
 import oracle
+from tests.sparse_helpers import COMB, Calls, T, _export_state, _raw_find_combine, batch, bits, filled_var, sparse_case, table
 
 pytestmark = pytest.mark.gpu
 
-IMIN = np.iinfo(np.int64).min
-COMB = {"sum": 0, "mean": 1, "sqrtn": 2}
 UNSUPPORTED = -6
 
 
@@ -24,82 +23,6 @@ def env():
   import torch
   import tfra_amd.dynamic_embedding as de
   return torch, de
-
-
-def T(torch, a):
-  return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def bits(torch, x):
-  return x.contiguous().view(torch.int32)
-
-
-# ---- one batch per size, shared by every case ----------------------------------------------------------------------------
-UNIVERSE = 6000          # distinct keys the ids are drawn from; every fifth one is never inserted
-
-
-def _universe():
-  rng = np.random.default_rng(1234)
-  keys = rng.permutation(np.arange(1, UNIVERSE + 1, dtype=np.int64) * 7919 - 3_000_000)   # negative keys too
-  inserted = keys[np.arange(UNIVERSE) % 5 != 0]          # rank r of the Zipf law -> keys[r]: misses at every frequency
-  return keys, np.concatenate([inserted, [IMIN]])         # INT64_MIN is resident (its side row), INT64_MIN + 1 is not
-
-
-def _batch(nnz, n_rows, long_row):
-  """(ids, seg, w): Zipf ids with ~20 % never-inserted keys and both reserved key values; seg ascending with empty rows at the
-  start, in the middle and at the end, a row of 1 entry, a row of `long_row` entries and 4 out-of-range values at the tail;
-  weights with zeros and negatives, a row whose weights are all 0 and a row whose weights cancel."""
-  rng = np.random.default_rng(nnz)
-  keys, _ = _universe()
-  counts = rng.integers(0, 24, size=n_rows)
-  special = {0: 0, 1: 0, 2: 1, 3: long_row, 4: 2, 5: 3, n_rows // 2: 0, n_rows // 2 + 1: 0, n_rows - 2: 0, n_rows - 1: 0}
-  for r, c in special.items():
-    counts[r] = c
-  free = np.setdiff1d(np.arange(n_rows), list(special))
-  deficit = nnz - 4 - int(counts.sum())
-  assert deficit >= 0
-  counts[free] += rng.multinomial(deficit, np.full(free.size, 1.0 / free.size))
-  seg = np.concatenate([np.repeat(np.arange(n_rows), counts), [n_rows, n_rows, n_rows + 5, 1 << 40]]).astype(np.int64)
-  assert seg.size == nnz and np.all(np.diff(seg) >= 0)
-  ids = keys[(rng.zipf(1.2, size=nnz) - 1) % UNIVERSE]
-  ids[5], ids[nnz // 2], ids[7], ids[nnz // 3] = IMIN, IMIN, IMIN + 1, IMIN + 1
-  w = rng.standard_normal(nnz).astype(np.float32)
-  w[rng.random(nnz) < 0.05] = 0.0
-  w[seg == 4] = [1.0, -1.0]       # mean: weight sum 0 -> zeros; sqrtn: sqrt(2)
-  w[seg == 5] = 0.0               # every combiner's weight sum is 0
-  return ids, seg, w
-
-
-_BATCHES = {}
-
-
-def batch(torch, nnz, n_rows, long_row=2000):
-  if (nnz, n_rows) not in _BATCHES:
-    ids, seg, w = _batch(nnz, n_rows, long_row)
-    _BATCHES[(nnz, n_rows)] = (ids, seg, w, T(torch, ids), T(torch, seg), T(torch, w))
-  return _BATCHES[(nnz, n_rows)]
-
-
-_TABLES = {}
-
-
-def table(torch, de, kind, vdtype, dim):
-  """A table of `kind` ("cuckoo": growing; "hkv": bounded, LRU) holding the inserted part of the universe, random rows."""
-  key = (kind, vdtype, dim)
-  if key not in _TABLES:
-    dt = getattr(torch, vdtype)
-    default = torch.full((dim,), 0.375, dtype=dt)
-    if kind == "cuckoo":
-      t = de.CuckooHashTable(torch.int64, dt, default, name="pl_c_%s_%d" % (vdtype, dim), dim=dim)
-    else:
-      t = de.HkvHashTable(torch.int64, dt, default, name="pl_h_%s_%d" % (vdtype, dim), init_capacity=8192, max_capacity=8192,
-                          max_hbm_for_values=1 << 28, evict_strategy=de.HkvEvictStrategy.LRU, dim=dim)
-    _, inserted = _universe()
-    g = torch.Generator(device="cuda").manual_seed(dim)
-    rows = torch.randn((inserted.size, dim), generator=g, device="cuda").to(dt)
-    t.insert(T(torch, inserted), rows)
-    _TABLES[key] = t
-  return _TABLES[key]
 
 
 def composition(torch, de, t, ids_t, seg_t, w_t, combiner, n_rows):
@@ -202,45 +125,10 @@ def test_find_combine_matches_oracle(env, combiner, weighted, dim):
 
 
 # ---- 3. the public path ----------------------------------------------------------------------------------------------------
-class Calls:
-  """Counts _capi.call by C function name."""
-
-  def __init__(self, monkeypatch):
-    from tfra_amd import _capi
-    self.n = {}
-    real = _capi.call
-
-    def counting(name, *args):
-      self.n[name] = self.n.get(name, 0) + 1
-      return real(name, *args)
-
-    monkeypatch.setattr(_capi, "call", counting)
-
-  def __getitem__(self, name):
-    return self.n.get(name, 0)
-
-
 def explicit_els(torch, de, var, seg_t, ids_t, w_t, combiner, n_rows):
   """The forward as the op chain: device_ops.unique -> Variable.lookup -> device_ops.sparse_segment_combine."""
   uniq, idx, _ = de.device_ops.unique(ids_t)
   return de.device_ops.sparse_segment_combine(var.lookup(uniq), idx, seg_t, w_t, combiner, n_rows)
-
-
-def filled_var(torch, de, name, dim=64, key_dtype=None, **kw):
-  var = de.Variable(dim=dim, name=name, key_dtype=key_dtype or torch.int64, **kw)
-  keys = torch.arange(0, 3000, 2, device="cuda").to(var.key_dtype)
-  g = torch.Generator(device="cuda").manual_seed(7)
-  var.upsert(keys, torch.randn((keys.numel(), dim), generator=g, device="cuda").to(var.value_dtype))
-  return var
-
-
-def sparse_case(rng, n_rows=200, weighted=True):
-  counts = rng.integers(0, 9, size=n_rows)
-  counts[[0, 7, n_rows - 1]] = 0
-  seg = np.repeat(np.arange(n_rows), counts).astype(np.int64)
-  ids = (rng.zipf(1.3, size=seg.size) % 3000).astype(np.int64)
-  w = rng.standard_normal(seg.size).astype(np.float32) if weighted else None
-  return seg, ids, w
 
 
 @pytest.mark.parametrize("vdtype", ["float32", "bfloat16"])
@@ -338,13 +226,6 @@ def test_ineligible_variables_keep_the_op_chain(env, monkeypatch, why):
 
 
 # ---- 4. training through the pooled forward ------------------------------------------------------------------------------
-def _export_state(torch, de, deo, opt, var):
-  k, v = var.export()
-  o = torch.argsort(k)
-  k = k[o]
-  return [k, bits(torch, v[o])] + [bits(torch, deo.get_slot(var, s).lookup(k)) for s in opt.slots]
-
-
 @pytest.mark.parametrize("name", ["sgd", "adam"])
 def test_training_step_never_runs_unique_and_matches_the_chain(env, monkeypatch, name):
   torch, de = env
@@ -390,15 +271,6 @@ def test_training_step_never_runs_unique_and_matches_the_chain(env, monkeypatch,
 
 
 # ---- 5. errors ---------------------------------------------------------------------------------------------------------------
-def _raw_find_combine(torch, de, t, nnz, ids_t, seg_t, n_rows, out, combiner=0):
-  from tfra_amd import _capi
-  from tfra_amd.dynamic_embedding.device_ops import _workspace
-  from tfra_amd.dynamic_embedding.table_ops import _ptr, _stream
-  dev = t._table.device
-  return _capi.lib().tfra_table_find_combine(t._table._h, _workspace(dev), nnz, _ptr(ids_t), _ptr(seg_t), None, combiner, n_rows,
-                                             _ptr(t._default_value), _ptr(out), _stream(dev))
-
-
 @pytest.mark.parametrize("dim,vdtype", [(6, "float32"), (260, "float32"), (8, "int8")])
 def test_unsupported_tables_are_refused_and_write_nothing(env, dim, vdtype):
   torch, de = env

@@ -9,13 +9,13 @@ import ctypes
 import numpy as np
 import pytest
 
-from tests import test_gpu_pooled_lookup as H
+from tests import sparse_helpers as H
 
 pytestmark = pytest.mark.gpu
 
 COMB = H.COMB
 INVALID, UNSUPPORTED = -1, -6
-T, bits = H.T, H.bits
+T, bits, _raw, _desc = H.T, H.bits, H._raw, H._desc
 
 
 @pytest.fixture(scope="module")
@@ -192,26 +192,6 @@ def test_back_to_back_calls_and_a_table_that_grew(env):
 
 
 # ---- 6. all or nothing ------------------------------------------------------------------------------------------------------------
-def _raw(torch, descs, n=None, launches=None):
-  from tfra_amd import _capi
-  from tfra_amd.dynamic_embedding.device_ops import _workspace
-  from tfra_amd.dynamic_embedding.table_ops import _stream
-  dev = torch.device("cuda", torch.cuda.current_device())
-  rc = _capi.lib().tfra_multi_find_combine(_workspace(dev), len(descs) if n is None else n,
-                                           ctypes.c_void_p(ctypes.addressof(descs)) if descs is not None else None,
-                                           ctypes.c_void_p(ctypes.addressof(launches)) if launches is not None else None, _stream(dev))
-  return rc, _capi.lib().tfra_last_error().decode()
-
-
-def _desc(e, t, ids, seg, n_rows, out, combiner=0):
-  from tfra_amd import _capi
-  e.struct_size = ctypes.sizeof(_capi.FindCombineDesc)
-  e.combiner = combiner
-  e.table = t._table._h.value if t is not None else None
-  e.nnz, e.ids, e.seg, e.weights = ids.numel(), ids.data_ptr(), seg.data_ptr(), None
-  e.n_rows, e.default_row, e.out = n_rows, (t._default_value.data_ptr() if t is not None else None), out.data_ptr()
-
-
 @pytest.mark.parametrize("bad", ["dim6", "int8", "misaligned_out", "null_table", "struct_size", "combiner3"])
 def test_one_bad_descriptor_and_nothing_is_written(env, bad):
   torch, de = env

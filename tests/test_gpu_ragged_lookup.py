@@ -11,6 +11,8 @@ import ctypes
 import numpy as np
 import pytest
 
+from tests import sparse_helpers as H
+from tests.sparse_helpers import Calls, T, _export_state, bits
 from tests.test_ragged_lookup_abi import ragged_bounds, ragged_model
 
 pytestmark = pytest.mark.gpu
@@ -26,14 +28,6 @@ def env():
   import torch
   import tfra_amd.dynamic_embedding as de
   return torch, de
-
-
-def T(torch, a):
-  return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def bits(torch, x):
-  return x.contiguous().view(torch.int32)
 
 
 # ---- shared fixtures: tables of 2 000 keys, one batch ---------------------------------------------------------------------------
@@ -246,30 +240,8 @@ def test_malformed_row_splits_are_clamped(env, dim, combiner):
 
 
 # ---- 4. launch counts ------------------------------------------------------------------------------------------------------------
-class Calls:
-  """Counts _capi.call by C function name."""
-
-  def __init__(self, monkeypatch):
-    from tfra_amd import _capi
-    self.n = {}
-    real = _capi.call
-
-    def counting(name, *args):
-      self.n[name] = self.n.get(name, 0) + 1
-      return real(name, *args)
-
-    monkeypatch.setattr(_capi, "call", counting)
-
-  def __getitem__(self, name):
-    return self.n.get(name, 0)
-
-
-def filled_var(torch, de, name, dim=64, key_dtype=None, **kw):
-  var = de.Variable(dim=dim, name=name, key_dtype=key_dtype or torch.int64, **kw)
-  keys = torch.arange(0, 3000, 2, device="cuda").to(var.key_dtype)
-  g = torch.Generator(device="cuda").manual_seed(7)
-  var.upsert(keys, (torch.randn((keys.numel(), dim), generator=g, device="cuda") * 3).to(var.value_dtype))
-  return var
+def filled_var(torch, de, name, **kw):
+  return H.filled_var(torch, de, name, scale=3, **kw)
 
 
 def sparse_case(rng, n_rows=200):
@@ -491,13 +463,6 @@ def test_ineligible_variables_take_the_tuple_form(env, monkeypatch, why):
 
 
 # ---- 7. training -----------------------------------------------------------------------------------------------------------------
-def _export_state(torch, de, deo, opt, var):
-  k, v = var.export()
-  o = torch.argsort(k)
-  k = k[o]
-  return [k, bits(torch, v[o])] + [bits(torch, deo.get_slot(var, s).lookup(k)) for s in opt.slots]
-
-
 def _train_case(torch):
   """128 rows, duplicates within and across rows, two empty rows, ~20 % of the weights not > 0."""
   rng = np.random.default_rng(31)
