@@ -170,6 +170,36 @@ int tfra_table_reserve(tfra_table_t* t, size_t min_slots, tfra_stream_t stream);
 int tfra_table_export_batch(tfra_table_t* t, size_t n, size_t offset, size_t* d_counter,
                             int64_t* keys, void* values, uint64_t* scores, tfra_stream_t stream);
 
+/* -- score-filtered scans (HierarchicalKV's export_batch_if / size_if / erase_if) for tables with a score line, i.e. every
+ *    eviction strategy but TFRA_EVICT_NONE.  pred(score, threshold): TFRA_SCORE_GE = score >= threshold, TFRA_SCORE_LT =
+ *    score < threshold, on the uint64 score export_batch reports (LRU: device clock; EPOCHLRU / EPOCHLFU: epoch << 32 | low
+ *    word; LFU: count; CUSTOMIZED: the caller's).  The two reserved keys (side rows) count as score ~0: they match every GE
+ *    and no LT.  All three calls: a table without scores returns TFRA_ERR_UNSUPPORTED, an unknown pred TFRA_ERR_INVALID, both
+ *    before anything is enqueued (no counter is touched, no file created); tfra_last_error() names the function.  Like
+ *    export_batch they are ordered against writers of the table by the caller.                                          */
+typedef enum { TFRA_SCORE_GE = 0, TFRA_SCORE_LT = 1 } tfra_score_pred;
+/* export_batch over the matching entries: n, offset, the slot numbering (reserved keys at nb*15 and nb*15+1) and the
+ * unspecified order are tfra_table_export_batch's.  *d_counter (caller zeroes it) is advanced by EVERY match of the range
+ * whatever cap is; an entry whose output position is >= cap is not written — key, row and score alike — so buffers of cap
+ * entries are never overrun.  keys == NULL: count only (values and scores must be NULL too, else TFRA_ERR_INVALID; cap is
+ * ignored, no row is read).                                                                                            */
+int tfra_table_export_batch_if(tfra_table_t* t, int pred, uint64_t threshold, size_t n, size_t offset,
+                               size_t* d_counter, size_t cap, int64_t* keys, void* values, uint64_t* scores,
+                               tfra_stream_t stream);
+/* Erases every matching entry of the whole table (one scan of the key and score lines; rows are not touched) and adds
+ * their number to *d_erased (device size_t, may be NULL).  Synchronises nothing; safe under TFRA_OPTION_CAPTURE_SAFE
+ * as tfra_table_erase is.                                                                                              */
+int tfra_table_erase_if(tfra_table_t* t, int pred, uint64_t threshold, size_t* d_erased /* may be NULL; += */,
+                        tfra_stream_t stream);
+/* tfra_table_save_field for the matching entries only: the same `<prefix>-keys` / `<prefix>-values` files, byte format,
+ * `append` and TFRA_OPTION_KEY_BYTES_ON_DISK key width, written window by window (buffer_keys slots per window, so a
+ * window never holds more than buffer_keys matches; the cap is a guard).  field == 0 is the embedding.  No `-scores` file
+ * is written: the reference's loader reads none (lookup_table_op_hkv.h:596-600), so a loaded key starts from the score its
+ * insert gives it.  The files merge over a base through tfra_table_load, which does not clear.  A delta does not record
+ * erased keys.                                                                                                         */
+int tfra_table_save_if(tfra_table_t* t, int field, int pred, uint64_t threshold, const char* prefix,
+                       size_t buffer_keys, int append, tfra_stream_t stream, size_t* n_saved);
+
 /* -- run-time options.  TFRA_OPTION_CAPTURE_SAFE = 1 makes every table entry point safe to call
  *    while `stream` is being captured into a hipGraph (no host synchronisation, no event
  *    record/query, no growth): the caller guarantees capacity (tfra_table_reserve beforehand) and

@@ -106,6 +106,9 @@ struct Table {
   int bounded_flags(size_t n, hipStream_t s, uint8_t** out);
 };
 
+// Argument check shared by the score-filtered calls (tfra_table.hip): TFRA_ERR_INVALID for a null table or an unknown predicate,
+// TFRA_ERR_UNSUPPORTED for a table without a score line; the message names `fn`.  Enqueues nothing.
+int score_filter_check(const Table* t, int pred, const char* fn);
 void destroy_own_plan(Table* t);   // tfra_csr.hip
 // insert_or_assign of UNIQUE keys as one ownership pass (tfra_own.hip); *taken = false: not applicable, run the locked kernels
 int own_upsert_unique(Table* t, hipStream_t s, size_t n, const i64* keys, const void* values, const u64* scores, bool* taken,

@@ -29,8 +29,15 @@ struct File {
 
 extern "C" {
 
+// filter (optional): {pred, threshold} of tfra_table_save_if, whose caller has checked the arguments — only entries whose score
+// matches are exported (a window of `chunk` slots holds at most `chunk` live entries, so the cap never cuts anything)
+struct ScoreFilter {
+  int pred;
+  uint64_t threshold;
+};
+
 static int save_impl(tfra_table_t* tp, int field, const char* prefix, size_t buffer_keys, int append, tfra_stream_t stream,
-                     size_t* n_saved) {
+                     size_t* n_saved, const ScoreFilter* filter = nullptr) {
   Table* t = reinterpret_cast<Table*>(tp);
   if (!t || !prefix) return set_error(TFRA_ERR_INVALID, "save: null argument");
   if (field < 0 || field > t->opts.aux_fields) return set_error(TFRA_ERR_INVALID, "save: bad field");
@@ -65,11 +72,14 @@ static int save_impl(tfra_table_t* tp, int field, const char* prefix, size_t buf
   for (size_t off = 0; off < cap; off += chunk) {
     size_t len = std::min(chunk, cap - off);
     if (hipMemsetAsync(d_cnt, 0, sizeof(size_t), s) != hipSuccess) { cleanup(); return set_error(TFRA_ERR_HIP, "save: memset"); }
-    rc = tfra_table_export_batch(tp, len, off, d_cnt, (int64_t*)d_keys, field == 0 ? d_vals : nullptr, nullptr, stream);
+    rc = filter ? tfra_table_export_batch_if(tp, filter->pred, filter->threshold, len, off, d_cnt, chunk, (int64_t*)d_keys,
+                                             field == 0 ? d_vals : nullptr, nullptr, stream)
+                : tfra_table_export_batch(tp, len, off, d_cnt, (int64_t*)d_keys, field == 0 ? d_vals : nullptr, nullptr, stream);
     if (rc) { cleanup(); return rc; }
     (void)hipMemcpyAsync(h_cnt, d_cnt, sizeof(size_t), hipMemcpyDeviceToHost, s);
     if (hipStreamSynchronize(s) != hipSuccess) { cleanup(); return set_error(TFRA_ERR_HIP, "save: sync"); }
     size_t got = *h_cnt;
+    if (filter && got > chunk) { cleanup(); return set_error(TFRA_ERR_HIP, "save_if: a window held more matches than slots"); }
     if (!got) continue;
     if (field > 0) {   // a co-located state vector (optimizer slot): read it for the exported keys, same order
       // every exported key is resident, so the default row is never used: any valid row-sized buffer will do
@@ -110,6 +120,17 @@ int tfra_table_save(tfra_table_t* tp, const char* prefix, size_t buffer_keys, in
 int tfra_table_save_field(tfra_table_t* tp, int field, const char* prefix, size_t buffer_keys, int append,
                           tfra_stream_t stream, size_t* n_saved) {
   return save_impl(tp, field, prefix, buffer_keys, append, stream, n_saved);
+}
+
+int tfra_table_save_if(tfra_table_t* tp, int field, int pred, uint64_t threshold, const char* prefix, size_t buffer_keys,
+                       int append, tfra_stream_t stream, size_t* n_saved) {
+  Table* t = reinterpret_cast<Table*>(tp);
+  int rc = score_filter_check(t, pred, "tfra_table_save_if");
+  if (rc) return rc;
+  if (!prefix) return set_error(TFRA_ERR_INVALID, "tfra_table_save_if: null prefix");
+  if (field < 0 || field > t->opts.aux_fields) return set_error(TFRA_ERR_INVALID, "tfra_table_save_if: bad field");
+  const ScoreFilter f{pred, threshold};
+  return save_impl(tp, field, prefix, buffer_keys, append, stream, n_saved, &f);
 }
 
 static int load_impl(tfra_table_t* tp, int field, const char* prefix, size_t buffer_keys, tfra_stream_t stream, size_t* n_loaded) {

@@ -17,6 +17,8 @@ RAGGED_PRUNE, RAGGED_FILL = 1, 2   # TFRA_RAGGED_* (flags of the ragged pooled l
 OPTION_CAPTURE_SAFE = 1
 OPTION_NO_OWNER_TAGS = 2
 OPTION_KEY_BYTES_ON_DISK = 3
+SCORE_GE, SCORE_LT = 0, 1   # tfra_score_pred
+ERR_UNSUPPORTED = -6
 
 
 class TfraError(RuntimeError):
@@ -153,6 +155,9 @@ _SIGS = {
     "tfra_table_slot_census": [_P, ctypes.POINTER(ctypes.c_uint64), _P],
     "tfra_table_reserve": [_P, _SZ, _P],
     "tfra_table_export_batch": [_P, _SZ, _SZ, _P, _P, _P, _P, _P],
+    "tfra_table_export_batch_if": [_P, _I, ctypes.c_uint64, _SZ, _SZ, _P, _SZ, _P, _P, _P, _P],
+    "tfra_table_erase_if": [_P, _I, ctypes.c_uint64, _P, _P],
+    "tfra_table_save_if": [_P, _I, _I, ctypes.c_uint64, ctypes.c_char_p, _SZ, _I, _P, ctypes.POINTER(_SZ)],
     "tfra_table_set_global_epoch": [_P, ctypes.c_uint64],
     "tfra_table_set_option": [_P, _I, ctypes.c_int64],
     "tfra_table_save": [_P, ctypes.c_char_p, _SZ, _I, _P, ctypes.POINTER(_SZ)],

@@ -108,6 +108,20 @@ def _driver_ids(table, ids, device, widen=True):
   return torch.as_tensor(ids, device=device).reshape(-1).to(torch.int64).contiguous()
 
 
+def _score_filter(threshold, pred):
+  """(tfra_score_pred, threshold) of a score-filtered call: `pred` is the string "ge" (score >= threshold) or "lt" (score <
+  threshold), the threshold an integer in [0, 2^64).  Anything else raises ValueError before a launch."""
+  if pred not in ("ge", "lt"):
+    raise ValueError("pred must be 'ge' or 'lt', got %r" % (pred,))
+  try:
+    thr = int(threshold)
+  except (TypeError, ValueError):
+    raise ValueError("threshold must be an integer in [0, 2^64), got %r" % (threshold,))
+  if not 0 <= thr < (1 << 64):
+    raise ValueError("threshold must be in [0, 2^64), got %r" % (threshold,))
+  return (_capi.SCORE_GE if pred == "ge" else _capi.SCORE_LT), thr
+
+
 def _as_device(device):
   if device is None or device == "" or device == []:
     device = "cuda:0"
@@ -461,6 +475,45 @@ class _DeviceTable:
     if got != n:
       raise RuntimeError("export: table changed during export (%d vs %d)" % (got, n))
     return _narrow_keys(keys, self._key_dtype), vals, scores
+
+  # ---- score-filtered scans (tables with scores: every Hkv strategy) --------------------------
+  def count_if(self, threshold, pred="ge"):
+    """Number of entries whose score matches, as a device int64 tensor of shape [1] (tfra_table_export_batch_if, count only:
+    one scan of the key and score lines, no host read)."""
+    p, thr = _score_filter(threshold, pred)
+    counter = torch.zeros(1, dtype=torch.int64, device=self._device)
+    _capi.call("tfra_table_export_batch_if", self._h, p, thr, self.capacity(), 0, _ptr(counter), 0, None, None, None,
+               _stream(self._device))
+    return counter
+
+  def export_if(self, threshold, pred="ge", with_scores=True, values=True):
+    """(keys, values, scores) of the entries whose score matches, order unspecified: a count-only pass, ONE host read of the
+    count (it sizes the tensors), then the export pass with cap = that count."""
+    p, thr = _score_filter(threshold, pred)
+    n = int(self.count_if(threshold, pred).item())
+    keys = torch.empty(n, dtype=torch.int64, device=self._device)
+    vals = torch.empty((n, self._dim), dtype=self._value_dtype, device=self._device) if values else None
+    scores = torch.empty(n, dtype=torch.int64, device=self._device) if with_scores else None
+    if n:
+      counter = torch.zeros(1, dtype=torch.int64, device=self._device)
+      _capi.call("tfra_table_export_batch_if", self._h, p, thr, self.capacity(), 0, _ptr(counter), n, _ptr(keys), _ptr(vals),
+                 _ptr(scores), _stream(self._device))
+    return _narrow_keys(keys, self._key_dtype), vals, scores
+
+  def erase_if(self, threshold, pred="lt"):
+    """Erases every entry whose score matches; the number erased as a device int64 tensor of shape [1] (no host sync)."""
+    p, thr = _score_filter(threshold, pred)
+    erased = torch.zeros(1, dtype=torch.int64, device=self._device)
+    _capi.call("tfra_table_erase_if", self._h, p, thr, _ptr(erased), _stream(self._device))
+    return erased
+
+  def save_if(self, prefix, threshold, pred="ge", buffer_size=4194304, append_to_file=False, field=0):
+    """save() of the entries whose score matches only (a delta checkpoint; load() merges it over a base)."""
+    p, thr = _score_filter(threshold, pred)
+    out = ctypes.c_size_t()
+    _capi.call("tfra_table_save_if", self._h, int(field), p, thr, prefix.encode(), int(buffer_size), int(bool(append_to_file)),
+               _stream(self._device), ctypes.byref(out))
+    return out.value
 
   def save(self, prefix, buffer_size=4194304, append_to_file=False, field=0):
     """field > 0: the co-located state vector `field` (an optimizer slot) in the same file format."""
@@ -860,6 +913,27 @@ class HkvHashTable(_LookupInterfaceMirror):
     if not (isinstance(split_size, int) and split_size > 0):
       raise ValueError("split_size must be positive integer.")
     return self._table.export_all(with_scores=True, values=True, split_size=split_size)
+
+
+  # ---- score-filtered forms (HKV export_batch_if / erase_if / size_if) ------------------------
+  def export_if(self, threshold, pred="ge", name=None):
+    """(keys, values, scores) of the entries with score >= threshold ("ge") or < threshold ("lt")."""
+    return self._table.export_if(threshold, pred)
+
+  def remove_if(self, threshold, pred="lt", name=None):
+    """Erases the matching entries; returns their number as a device int64 tensor of shape [1]."""
+    return self._table.erase_if(threshold, pred)
+
+  def size_if(self, threshold, pred="ge", name=None):
+    """Number of matching entries as a device int64 tensor of shape [1]."""
+    return self._table.count_if(threshold, pred)
+
+  def save_delta_to_file_system(self, dirpath, threshold, pred="ge", file_name=None, dirpath_env="TFRA_SAVED_KV",
+                                append_to_file=False, buffer_size=4194304, name=None):
+    """save_to_file_system of the matching entries only (same path and naming rules, same files): a delta checkpoint in the
+    format load_from_file_system reads (that call clears first; the device table's `load` merges over what is resident).
+    Erased keys are not recorded; scores are not written."""
+    return self._table.save_if(self._file_prefix(dirpath, file_name, dirpath_env), threshold, pred, buffer_size, append_to_file)
 
 
 def _device_table(x):

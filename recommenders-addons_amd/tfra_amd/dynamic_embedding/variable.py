@@ -15,7 +15,7 @@ partition -> per-shard table op -> stitch, the partition/stitch being device ker
 import torch
 
 from . import device_ops
-from .table_ops import CuckooHashTable, HkvHashTable, HkvEvictStrategy, _as_device
+from .table_ops import CuckooHashTable, HkvHashTable, HkvEvictStrategy, _as_device, _score_filter
 
 
 def default_partition_fn(keys, shard_num):
@@ -285,6 +285,48 @@ class Variable:
     if index is not None:
       return self._tables[index].size()
     return torch.stack([t.size().to(self._primary) for t in self._tables]).sum()
+
+  # ---- score-filtered forms (tables with per-key scores: HkvHashTable shards) -----------------
+  def _scored_tables(self, what):
+    """The shards, once every one of them is known to keep scores; NotImplementedError (before any table is touched) when not."""
+    for t in self._tables:
+      if not hasattr(t, "export_if"):
+        raise NotImplementedError("%s needs per-key scores; %s tables have evict strategy NONE (use an HkvHashTableCreator)"
+                                  % (what, type(t).__name__))
+    return self._tables
+
+  def export_if(self, threshold, pred="ge", name=None):
+    """(keys, values, scores) of every shard's entries whose score matches, concatenated as export does."""
+    _score_filter(threshold, pred)
+    ks, vs, ss = [], [], []
+    for t in self._scored_tables("export_if"):
+      k, v, s = t.export_if(threshold, pred)
+      ks.append(k.to(self._primary))
+      vs.append(v.to(self._primary))
+      ss.append(s.to(self._primary))
+    return torch.cat(ks, 0), torch.cat(vs, 0), torch.cat(ss, 0)
+
+  def remove_if(self, threshold, pred="lt", name=None):
+    """Erases the matching entries of every shard; their total number (device int64 scalar, as size)."""
+    _score_filter(threshold, pred)
+    return torch.stack([t.remove_if(threshold, pred).to(self._primary) for t in self._scored_tables("remove_if")]).sum()
+
+  def size_if(self, threshold, pred="ge", name=None):
+    _score_filter(threshold, pred)
+    return torch.stack([t.size_if(threshold, pred).to(self._primary) for t in self._scored_tables("size_if")]).sum()
+
+  def save_delta(self, dirpath, threshold, pred="ge", proc_size=1, proc_rank=0, buffer_size=4194304, append_to_file=False):
+    """save_to_file_system's per-shard embedding files for the matching entries only; returns the number of entries written.
+    The files have save_to_file_system's names and format.  To restore, load the base and then each shard's delta with the
+    device table's `load` (it does not clear; load_from_file_system does).  The optimizer's state vectors are not part of a
+    delta."""
+    _score_filter(threshold, pred)
+    suffix = "_rank{}_size{}".format(proc_rank, proc_size) if proc_size > 1 else ""
+    total = 0
+    for idx, t in enumerate(self._scored_tables("save_delta")):
+      total += t.save_delta_to_file_system(dirpath, threshold, pred, file_name=self._make_name(idx) + suffix, dirpath_env=None,
+                                           append_to_file=append_to_file, buffer_size=buffer_size)
+    return total
 
   def _slot_file_names(self, optimizer):
     """{field: base file name} of the co-located state vectors.  With the optimizer: the reference's slot-variable

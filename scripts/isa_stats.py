@@ -8,16 +8,21 @@ pats = sys.argv[2:]
 out = os.path.join(tempfile.gettempdir(), os.path.basename(src) + ".s")
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "--cuda-device-only",
                        "-S", src, "-o", out], stderr=subprocess.DEVNULL)
-cur, stats, regs, last_name = None, collections.OrderedDict(), {}, None
+cur, stats, regs, last_name, lds = None, collections.OrderedDict(), {}, None, None
 for line in open(out):
   m = re.match(r"^(_Z\w+):", line)
   if m:
     cur = m.group(1); stats[cur] = collections.Counter(); continue
   if line.startswith("\t.end_amdhsa_kernel") or line.startswith(".Lfunc_end"):
     cur = None
+  # a kernel's metadata lists its keys in alphabetical order: .group_segment_fixed_size comes BEFORE the .name it belongs to
+  m = re.match(r"\s+\.group_segment_fixed_size:\s+(\d+)", line)
+  if m: lds = int(m.group(1)); continue
   m = re.match(r"\s+\.name:\s+(\S+)", line)
-  if m: last_name = m.group(1)
-  m = re.match(r"\s+\.(vgpr_count|sgpr_count|vgpr_spill_count|group_segment_fixed_size|private_segment_fixed_size):\s+(\d+)", line)
+  if m:
+    last_name = m.group(1)
+    if lds is not None: regs.setdefault(last_name, {})["group_segment_fixed_size"] = lds; lds = None
+  m = re.match(r"\s+\.(vgpr_count|sgpr_count|vgpr_spill_count|private_segment_fixed_size):\s+(\d+)", line)
   if m and last_name: regs.setdefault(last_name, {})[m.group(1)] = int(m.group(2))
   if cur is None: continue
   t = line.strip().split()
