@@ -560,7 +560,7 @@ int tfra::apply_planned_impl(tfra_table_t* tp, const tfra_opt_params* p, const t
   if (comb) launch_apply(t, s, pl, p->kind, o, grads, param_default_row, key_blocks, sp, CombRows{comb});
   else launch_apply(t, s, pl, p->kind, o, grads, param_default_row, key_blocks, sp);
   if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "apply_planned: launch failed");
-  step_epoch_public(t);
+  t->step_epoch();
   return TFRA_OK;
 }
 
@@ -829,7 +829,7 @@ extern "C" int tfra_multi_apply_planned_combined(tfra_workspace_t* ws, size_t n_
     }
   }
   if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "multi_apply_planned_combined: launch failed");
-  for (size_t i : act) step_epoch_public(reinterpret_cast<Table*>(descs[i].table));
+  for (size_t i : act) reinterpret_cast<Table*>(descs[i].table)->step_epoch();
   if (launches_out) *launches_out = launches;
   return TFRA_OK;
 }
@@ -914,7 +914,7 @@ static int apply_sparse_big(Table* t, tfra_table_t* tp, tfra_sparse_plan* pl, co
       off += (size_t)c;
     }
     t->epoch_hold = false;
-    step_epoch_public(t);
+    t->step_epoch();
     return cleanup(TFRA_OK);
   }
   return cleanup(set_error(TFRA_ERR_UNSUPPORTED, "apply_sparse: could not split the batch into parts of 2^18 ids"));

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <mutex>
 #include <string>
@@ -15,6 +16,22 @@ namespace tfra {
 
 extern thread_local std::string g_last_error;
 int set_error(int code, const std::string& msg);
+
+#define HIP_TRY(expr)                                                                         \
+  do {                                                                                        \
+    hipError_t _e = (expr);                                                                   \
+    if (_e != hipSuccess)                                                                     \
+      return set_error(_e == hipErrorOutOfMemory ? TFRA_ERR_OOM : TFRA_ERR_HIP,                \
+                       std::string(#expr) + ": " + hipGetErrorString(_e));                    \
+  } while (0)
+
+// head of a C entry point of the table units (tfra_table / tfra_grow / tfra_upsert / tfra_scan .hip): handle `tp`, `stream`
+#define TABLE_ENTER()                                         \
+  Table* t = reinterpret_cast<Table*>(tp);                    \
+  if (!t) return set_error(TFRA_ERR_INVALID, "null table");   \
+  hipStream_t s = (hipStream_t)stream;                        \
+  std::lock_guard<std::mutex> lock(t->mu);                    \
+  { int _rc = t->enter(s); if (_rc) return _rc; }
 
 struct Storage {
   unsigned char* base = nullptr;  // nb bucket blocks [key line | score line | 15 rows] + 2 side rows
@@ -82,7 +99,7 @@ struct Table {
   int key_file_bytes = 8;     // TFRA_OPTION_KEY_BYTES_ON_DISK
   uint64_t global_epoch = 0;
   int64_t curr_step = 1;
-  bool epoch_hold = false;   // see step_epoch (tfra_optim.hip)
+  bool epoch_hold = false;   // see step_epoch
   int n_rehash = 0;
 
   void* dalloc(size_t bytes, hipStream_t s);
@@ -104,9 +121,22 @@ struct Table {
   int prepare_insert(size_t n, hipStream_t s);
   int poll_density(size_t n, hipStream_t s);
   int bounded_flags(size_t n, hipStream_t s, uint8_t** out);
+  void enqueue_clear(const Storage& st, bool reset_counters, hipStream_t s);   // clear_kernel <<<2048, 256>>> (tfra_table.hip)
+  void enqueue_size(i64* d_out, hipStream_t s);                                // size_kernel <<<1, SIZE_SHARDS>>> of `cur`
+  // geometry: a bucket block is [key line | score line (scored tables) | SLOTS rows]; the side rows follow the last block
+  unsigned hdr_bytes() const { return opts.strategy >= 0 ? 256u : 128u; }
+  size_t bucket_stride() const { return (size_t)hdr_bytes() + (size_t)SLOTS * row_stride; }
+  size_t storage_bytes(u64 nb) const { return nb * bucket_stride() + (size_t)NUM_RESERVED * row_stride; }
+  u64 max_nb() const { return std::max<u64>(2, opts.max_capacity / SLOTS); }   // (max_capacity == 0, unbounded: the caller's case)
+  void step_epoch() {   // one upsert, or one fused write-back, is one step of the epoch strategies (lookup_table_op_hkv.h:528-536)
+    if (epoch_hold) return;   // one logical write-back issued as several launches (apply_sparse_big): stepped once by the caller
+    if (opts.strategy != TFRA_EVICT_EPOCHLRU && opts.strategy != TFRA_EVICT_EPOCHLFU) return;
+    curr_step += 1;
+    if (opts.step_per_epoch > 0 && curr_step > opts.step_per_epoch) { global_epoch += 1; curr_step = 1; }
+  }
 };
 
-// Argument check shared by the score-filtered calls (tfra_table.hip): TFRA_ERR_INVALID for a null table or an unknown predicate,
+// Argument check shared by the score-filtered calls (tfra_scan.hip): TFRA_ERR_INVALID for a null table or an unknown predicate,
 // TFRA_ERR_UNSUPPORTED for a table without a score line; the message names `fn`.  Enqueues nothing.
 int score_filter_check(const Table* t, int pred, const char* fn);
 void destroy_own_plan(Table* t);   // tfra_csr.hip
@@ -115,7 +145,6 @@ int own_upsert_unique(Table* t, hipStream_t s, size_t n, const i64* keys, const 
                       const uint8_t* accum_exists = nullptr, const int64_t* d_n = nullptr);   // accum_exists: insert_or_accum instead of an assign
 void destroy_workspace_plan(void* plan);   // tfra_csr.hip
 void destroy_workspace_many(void* stage);  // tfra_pool.hip
-void step_epoch_public(Table* t);  // tfra_optim.hip
 
 // Copy granule of rows of `bytes` bytes between two buffers: the largest power of two <= 16 that divides the row size and both
 // addresses (a null pointer divides everything).
@@ -134,6 +163,20 @@ static inline void with_granule(int g, F&& f) {
     case 4: f(std::integral_constant<int, 4>{}); break;
     case 2: f(std::integral_constant<int, 2>{}); break;
     default: f(std::integral_constant<int, 1>{}); break;
+  }
+}
+
+// f(std::integral_constant<int, DT>{}) for the value dtype DT (tfra_dtype) that dt selects (anything else: TFRA_F64)
+template <class F>
+static inline void with_dtype(int dt, F&& f) {
+  switch (dt) {
+    case TFRA_F32: f(std::integral_constant<int, TFRA_F32>{}); break;
+    case TFRA_F16: f(std::integral_constant<int, TFRA_F16>{}); break;
+    case TFRA_BF16: f(std::integral_constant<int, TFRA_BF16>{}); break;
+    case TFRA_I8: f(std::integral_constant<int, TFRA_I8>{}); break;
+    case TFRA_I32: f(std::integral_constant<int, TFRA_I32>{}); break;
+    case TFRA_I64: f(std::integral_constant<int, TFRA_I64>{}); break;
+    default: f(std::integral_constant<int, TFRA_F64>{}); break;
   }
 }
 

@@ -191,22 +191,7 @@ void launch_apply(int dt, bool vec4, dim3 grid, hipStream_t s, TableView v, OptP
   if (deferred) apply_evict_kernel<KIND><<<grid, 256, 0, s>>>(v, o, n, k, g, d, full, dim, a0, a1, dn, sp, deferred);
 }
 
-// one fused write-back counts as one upsert for the epoch strategies (lookup_table_op_hkv.h:528-536)
-void step_epoch(Table* t) {
-  if (t->epoch_hold) return;   // one logical write-back issued as several launches (apply_sparse_big): stepped once by the caller
-  const int strat = t->opts.strategy;
-  if (strat == TFRA_EVICT_EPOCHLRU || strat == TFRA_EVICT_EPOCHLFU) {
-    t->curr_step += 1;
-    if (t->opts.step_per_epoch > 0 && t->curr_step > t->opts.step_per_epoch) { t->global_epoch += 1; t->curr_step = 1; }
-  }
-}
-
 }  // namespace
-
-namespace tfra {
-void step_epoch_public(Table* t) { step_epoch(t); }
-
-}  // namespace tfra
 
 extern "C" int tfra_table_apply_optimizer(tfra_table_t* tp, const tfra_opt_params* p, size_t n, const int64_t* keys,
                                           const float* grads, const void* param_defaults, int default_is_full,
@@ -247,7 +232,7 @@ extern "C" int tfra_table_apply_optimizer(tfra_table_t* tp, const tfra_opt_param
     case TFRA_OPT_ADAGRAD: launch_apply<TFRA_OPT_ADAGRAD>(dt, vec4, grid, s, v, o, n, k, grads, d, default_is_full, dim, a0, a1, (const i64*)d_n, sp, deferred); break;
     default: launch_apply<TFRA_OPT_FTRL>(dt, vec4, grid, s, v, o, n, k, grads, d, default_is_full, dim, a0, a1, (const i64*)d_n, sp, deferred); break;
   }
-  step_epoch(t);
+  t->step_epoch();   // one fused write-back counts as one upsert
   if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "apply_optimizer: launch failed");
   return TFRA_OK;
 }

@@ -294,7 +294,7 @@ int tfra::upsert_planned_impl(tfra_table_t* tp, const tfra_sparse_plan_t* pl, co
   if (pl->kind == 1) launch_own<SRC_SET>(s, L.g, L.simple, L.a, (size_t)L.key_blocks * 16, L.ctr, L.next_ctr, L.og, L.rem_blocks, progress, progress_val);
   else launch_own<SRC_PLAN>(s, L.g, L.simple, L.a, (size_t)L.key_blocks * 16, L.ctr, L.next_ctr, L.og, L.rem_blocks, progress, progress_val);
   if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "upsert_planned: launch failed");
-  step_epoch_public(t);
+  t->step_epoch();
   return TFRA_OK;
 }
 

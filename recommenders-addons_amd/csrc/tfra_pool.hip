@@ -28,14 +28,6 @@
 
 using namespace tfra;
 
-#define HIP_TRY(expr)                                                                         \
-  do {                                                                                        \
-    hipError_t _e = (expr);                                                                   \
-    if (_e != hipSuccess)                                                                     \
-      return set_error(_e == hipErrorOutOfMemory ? TFRA_ERR_OOM : TFRA_ERR_HIP,                \
-                       std::string(#expr) + ": " + hipGetErrorString(_e));                    \
-  } while (0)
-
 namespace {
 
 // four elements of a row as float32: a 16-B load of a float32 row, an 8-B load of a half row up-cast exactly

@@ -428,7 +428,7 @@ static int step_overlap_one(tfra_step_driver* d, size_t n, const int64_t* ids, v
     if (map_slot_new >= 0) {
       d->map_slot = (unsigned)map_slot_new; d->map_valid = true; d->map_ids = ids_next; d->map_n = n_next; d->map_plan = plan_cur; d->map_gen = plan_cur->gen;
     }
-    if (plan_prev) step_epoch_public(t);
+    if (plan_prev) t->step_epoch();
     d->n_overlapped += 1;
   }
   d->pending = n > 0;

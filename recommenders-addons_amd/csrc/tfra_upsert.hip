@@ -1,0 +1,498 @@
+// The locked upsert and accumulate of the table (tfra_table.hip): insert_or_assign[_n], insert_field, accum_or_assign.
+// (Unique keys on a table that is large for the batch take the ownership pass instead: own_upsert_unique, tfra_own.hip.)
+#include <hip/hip_runtime.h>
+
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include "tfra_host.h"
+
+using namespace tfra;
+typedef tfra::AuxInitPod AuxInit;  // elem_bytes = sizeof(V); pattern[f] = aux_init[f] as V, replicated to 32 bits
+
+// ---- aux-field initialisation for a newly claimed row --------------------------------------
+
+// WT: write-through stores (eviction path: the row must be in memory before the key is published, see publish_key)
+template <bool WT = false>
+__device__ __forceinline__ void init_aux_fields(const TableView& v, const AuxInit& ai, i64 row,
+                                                int sub, unsigned skip_field) {
+  unsigned char* r = row_ptr(v, row);
+  for (unsigned f = 0; f < v.n_fields; ++f) {
+    if (f == skip_field) continue;
+    unsigned pat = f == 0 ? 0u : ai.pattern[(f - 1) & 3];
+    unsigned char* p = r + f * v.field_bytes;
+    if ((v.field_bytes & 3) == 0) {
+      for (unsigned off = sub * 4; off < v.field_bytes; off += 64) {
+        if (WT) __hip_atomic_store(reinterpret_cast<unsigned*>(p + off), pat, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else *reinterpret_cast<unsigned*>(p + off) = pat;
+      }
+    } else {
+      for (unsigned off = sub; off < v.field_bytes; off += 16) {
+        const unsigned char b = (unsigned char)(pat >> (8 * (off % ai.elem_bytes)));
+        if (WT) __hip_atomic_store(p + off, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else p[off] = b;
+      }
+    }
+  }
+}
+
+// ---- insert_or_assign, unique-keys fast path (single pass) ---------------------------------
+template <int G, int U>
+__global__ __launch_bounds__(256) void insert_unique_kernel(TableView v, size_t n,
+                                                            const i64* __restrict__ keys,
+                                                            const unsigned char* __restrict__ vals,
+                                                            const u64* __restrict__ scores,
+                                                            unsigned field, AuxInit ai, int strategy,
+                                                            u64 epoch, int bounded, uint8_t* __restrict__ deferred) {
+  const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48, grp = lane >> 4;
+  const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  constexpr int KPW = 4 * U;
+  const size_t base = wave * KPW;
+  if (base >= n) return;
+  const size_t last = n - 1;
+  i64 kreg = keys[min(base + (size_t)(lane & (KPW - 1)), last)];
+  int fresh = 0, failed = 0;
+  i64 key[U], k0[U], k1[U];
+  u64 h[U], b0[U];
+  const bool pf1 = bounded > 1;  // table near capacity: both home buckets' lines in flight together
+#pragma unroll
+  for (int u = 0; u < U; ++u) {  // U first probes in flight (unconditional, tail clamped)
+    key[u] = shfl_i64(kreg, u * 4 + grp);
+    b0[u] = bucket0(key[u], v.nb, h[u]);
+    k0[u] = load_key_coherent(key_line(v, b0[u]) + sub);
+    k1[u] = load_key_coherent(key_line(v, pf1 ? bucket1(h[u], b0[u], v.nb) : b0[u]) + sub);  // (same line again: an L2 hit)
+  }
+  keep_live(k0[0], k0[1], k0[2], k0[3]);
+  keep_live(k1[0], k1[1], k1[2], k1[3]);
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    int j = u * 4 + grp;
+    size_t i = base + j;
+    if (i < n) {
+      bool is_new;
+      i64 row = locate_or_claim_from(v, key[u], h[u], b0[u], k0[u], sub, gshift, is_new, bounded, pf1 ? &k1[u] : nullptr);
+      if (deferred && sub == 0) deferred[i] = row == NEED_EVICT;
+      if (row >= 0) {
+        copy_bytes16<G>(row_ptr(v, row) + field * v.field_bytes,
+                        vals + i * (size_t)v.field_bytes, v.field_bytes, sub);
+        if (is_new && v.n_fields > 1) init_aux_fields(v, ai, row, sub, field);
+        update_score(v, row, is_new, strategy, scores ? scores[i] : 1, epoch, sub);
+        fresh += (is_new && sub == 0);
+      } else if (row != NEED_EVICT) {
+        failed += (sub == 0);
+      }
+    }
+  }
+  // one size update per wave
+  for (int o = 32; o > 0; o >>= 1) { fresh += __shfl_xor(fresh, o); failed += __shfl_xor(failed, o); }
+  if (lane == 0) {
+    if (fresh) size_add(v, wave, fresh);
+    if (failed) atomicAdd(v.err_count, (unsigned)failed);
+  }
+}
+
+// ---- phase 2 of a bounded-table upsert: keys that found neither themselves nor an empty slot
+// replace the minimum-score entry of their two home buckets (runs after phase 1 has completed, so
+// no row is being written by an assign while it is evicted).
+template <int G>
+__global__ __launch_bounds__(256) void insert_evict_kernel(TableView v, size_t n, const i64* __restrict__ keys,
+                                                           const unsigned char* __restrict__ vals,
+                                                           const u64* __restrict__ scores, unsigned field, AuxInit ai,
+                                                           int strategy, u64 epoch, const uint8_t* __restrict__ deferred) {
+  const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
+  const size_t i = (((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4);
+  int fresh = 0, failed = 0;
+  if (i < n && deferred[i]) {
+    const i64 key = keys[i];
+    const u64 in_score = scores ? scores[i] : 1;
+    const bool lru_like = strategy == TFRA_EVICT_LRU || strategy == TFRA_EVICT_EPOCHLRU;
+    u64 word = 0;
+    bool claimed_empty;
+    i64 row = evict_and_lock(v, key, strategy == TFRA_EVICT_EPOCHLFU ? ((epoch << 32) | in_score) : in_score, lru_like, sub,
+                             gshift, &word, claimed_empty);
+    if (row >= 0) {
+      copy_bytes16_wt<G>(row_ptr(v, row) + field * v.field_bytes, vals + i * (size_t)v.field_bytes,
+                         v.field_bytes, sub);
+      if (v.n_fields > 1) init_aux_fields<true>(v, ai, row, sub, field);
+      if (sub == 0) store_wt8(score_word(v, word), 0);  // the slot starts a new life: scores count from zero
+      update_score<true>(v, row, true, strategy, in_score, epoch, sub);
+      publish_key(v, word, key, sub);
+      fresh = (claimed_empty && sub == 0);
+    } else if (row == -3) {
+      failed = (sub == 0);
+    }  // -1: not admitted (its score is below every resident score): silently dropped, like HKV
+  }
+  for (int o = 32; o > 0; o >>= 1) { fresh += __shfl_xor(fresh, o); failed += __shfl_xor(failed, o); }
+  if (lane == 0) {
+    if (fresh) size_add(v, i >> 2, fresh);
+    if (failed) atomicAdd(v.err_count, (unsigned)failed);
+  }
+}
+
+// ---- insert_or_assign with duplicates: pass 1 locate/claim + elect the LAST index ----------
+template <int U>
+__global__ __launch_bounds__(256) void insert_locate_kernel(TableView v, size_t n,
+                                                            const i64* __restrict__ keys,
+                                                            i64* __restrict__ slot_of, unsigned field,
+                                                            AuxInit ai) {
+  const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48, grp = lane >> 4;
+  const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  constexpr int KPW = 4 * U;
+  const size_t base = wave * KPW;
+  if (base >= n) return;
+  i64 kreg = (lane < KPW && base + lane < n) ? keys[base + lane] : 0;
+  int fresh = 0, failed = 0;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    int j = u * 4 + grp;
+    size_t i = base + j;
+    i64 key = shfl_i64(kreg, j);
+    if (i < n) {
+      bool is_new;
+      i64 row = locate_or_claim(v, key, sub, gshift, is_new);
+      if (row >= 0) {
+        if (is_new && v.n_fields > 1) init_aux_fields(v, ai, row, sub, field);
+        if (sub == 0) {
+          // hot keys (Zipf) repeat thousands of times: only occurrences that can still raise the
+          // maximum pay for the contended atomic
+          if (__hip_atomic_load(&v.winner[row], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (int)i) atomicMax(&v.winner[row], (int)i);
+          slot_of[i] = row | (is_new ? (i64)1 << 62 : 0);
+        }
+        fresh += (is_new && sub == 0);
+      } else {
+        if (sub == 0) slot_of[i] = -1;
+        failed += (sub == 0);
+      }
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) { fresh += __shfl_xor(fresh, o); failed += __shfl_xor(failed, o); }
+  if (lane == 0) {
+    if (fresh) size_add(v, wave, fresh);
+    if (failed) atomicAdd(v.err_count, (unsigned)failed);
+  }
+}
+
+// pass 2: only the elected occurrence writes the row (sequential "last writer wins" of
+// LaunchTensorsInsert with one thread), then re-arms the election word.
+template <int G>
+__global__ __launch_bounds__(256) void insert_write_kernel(TableView v, size_t n,
+                                                           const unsigned char* __restrict__ vals,
+                                                           const u64* __restrict__ scores,
+                                                           const i64* __restrict__ slot_of,
+                                                           unsigned field, int strategy, u64 epoch) {
+  const int lane = threadIdx.x & 63, sub = lane & 15;
+  const size_t i = (((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4);
+  if (i >= n) return;
+  (void)lane;
+  i64 so = slot_of[i];
+  if (so < 0) return;
+  bool is_new = (so >> 62) & 1;
+  i64 row = so & (((i64)1 << 62) - 1);
+  if (v.winner[row] != (int)i) {
+    // LFU counts every upsert, also the overwritten duplicates
+    if (strategy == TFRA_EVICT_LFU) update_score(v, row, false, strategy, scores ? scores[i] : 1, epoch, sub);
+    return;
+  }
+  copy_bytes16<G>(row_ptr(v, row) + field * v.field_bytes,
+                  vals + i * (size_t)v.field_bytes, v.field_bytes, sub);
+  update_score(v, row, is_new, strategy, scores ? scores[i] : 1, epoch, sub);
+}
+
+__global__ void rearm_winner_kernel(TableView v, size_t n, const i64* __restrict__ slot_of) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  i64 so = slot_of[i];
+  if (so >= 0) v.winner[so & (((i64)1 << 62) - 1)] = -1;
+}
+
+// ---- typed accumulate: row[j] += delta[j], one add per element (ValueArray::operator+=) ----
+
+template <int DT>
+__device__ __forceinline__ void row_add(unsigned char* row, const unsigned char* delta, unsigned dim, int sub) {
+  for (unsigned j = sub; j < dim; j += 16) {
+    if (DT == TFRA_F32) reinterpret_cast<float*>(row)[j] += reinterpret_cast<const float*>(delta)[j];
+    else if (DT == TFRA_F64) reinterpret_cast<double*>(row)[j] += reinterpret_cast<const double*>(delta)[j];
+    else if (DT == TFRA_I8) reinterpret_cast<signed char*>(row)[j] = (signed char)(reinterpret_cast<signed char*>(row)[j] + reinterpret_cast<const signed char*>(delta)[j]);
+    else if (DT == TFRA_I32) reinterpret_cast<unsigned*>(row)[j] += reinterpret_cast<const unsigned*>(delta)[j];
+    else if (DT == TFRA_I64) reinterpret_cast<u64*>(row)[j] += reinterpret_cast<const u64*>(delta)[j];
+    else if (DT == TFRA_F16) {
+      _Float16 a = reinterpret_cast<_Float16*>(row)[j], b = reinterpret_cast<const _Float16*>(delta)[j];
+      reinterpret_cast<_Float16*>(row)[j] = (_Float16)((float)a + (float)b);
+    } else {
+      unsigned short* r = reinterpret_cast<unsigned short*>(row);
+      r[j] = f32_to_bf16(bf16_to_f32(r[j]) + bf16_to_f32(reinterpret_cast<const unsigned short*>(delta)[j]));
+    }
+  }
+}
+
+// ---- accum_or_assign.  ROUND >= 0: duplicate-safe mode, processes only the occurrence that is
+// currently first-in-line for its key (election word), see host loop. -------------------------
+// one (key, values-or-delta, exists) triple: absent & !exists -> insert, present & exists -> row += delta, else nothing
+template <int DT, int G>
+__device__ __forceinline__ void accum_one(const TableView& v, size_t i, const i64* __restrict__ keys,
+                                          const unsigned char* __restrict__ vod, const uint8_t* __restrict__ exists,
+                                          const u64* __restrict__ scores, unsigned dim, const AuxInit& ai, int strategy, u64 epoch,
+                                          uint8_t* __restrict__ deferred, int bounded_mode, int sub, int gshift, int& fresh,
+                                          int& failed) {
+  const i64 key = keys[i];
+  const bool ex = exists[i] != 0;
+  const unsigned char* src = vod + i * (size_t)v.field_bytes;
+  if (!ex) {
+    bool is_new;
+    i64 row;
+    if (deferred) {  // bounded table at max_capacity: keys without a free slot evict in phase 2
+      u64 h;
+      const u64 b0 = bucket0(key, v.nb, h);
+      const i64 k0 = load_key_coherent(key_line(v, b0) + sub);
+      row = locate_or_claim_from(v, key, h, b0, k0, sub, gshift, is_new, bounded_mode);
+      if (sub == 0) deferred[i] = row == NEED_EVICT;
+    } else {
+      row = locate_or_claim(v, key, sub, gshift, is_new);
+    }
+    if (row < 0) failed += (sub == 0 && row != NEED_EVICT);
+    else if (is_new) {
+      copy_bytes16<G>(row_ptr(v, row), src, v.field_bytes, sub);
+      if (v.n_fields > 1) init_aux_fields(v, ai, row, sub, 0);
+      update_score(v, row, true, strategy, scores ? scores[i] : 1, epoch, sub);
+      fresh += (sub == 0);
+    }  // present & !exists: dropped
+  } else {
+    i64 row = probe_find<true>(v, key, sub, gshift);
+    if (row >= 0) {
+      row_add<DT>(row_ptr(v, row), src, dim, sub);
+      update_score(v, row, false, strategy, scores ? scores[i] : 1, epoch, sub);
+    }  // absent & exists: dropped
+    if (deferred && sub == 0) deferred[i] = 0;
+  }
+}
+
+template <int DT, int G>
+__global__ __launch_bounds__(256) void accum_kernel(TableView v, size_t n, const i64* __restrict__ keys,
+                                                    const unsigned char* __restrict__ vod,
+                                                    const uint8_t* __restrict__ exists,
+                                                    const u64* __restrict__ scores, unsigned dim,
+                                                    AuxInit ai, int strategy, u64 epoch,
+                                                    uint8_t* __restrict__ deferred, int bounded_mode) {
+  const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
+  const size_t g = (((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4);
+  const size_t wave = g >> 2;
+  int fresh = 0, failed = 0;
+  if (g < n) accum_one<DT, G>(v, g, keys, vod, exists, scores, dim, ai, strategy, epoch, deferred, bounded_mode, sub, gshift, fresh, failed);
+  for (int o = 32; o > 0; o >>= 1) { fresh += __shfl_xor(fresh, o); failed += __shfl_xor(failed, o); }
+  if (lane == 0) {
+    if (fresh) size_add(v, wave, fresh);
+    if (failed) atomicAdd(v.err_count, (unsigned)failed);
+  }
+}
+
+// Keys that repeat within one call: the reference applies the triples one after the other in index order
+// (LaunchTensorsAccum on one thread; accumrase_fn, cuckoohash_map.hh:619-633), and the outcome of an occurrence depends
+// on the ones before it (an insert makes the key present for the next).  The (key, index) pairs arrive sorted by key
+// (stable radix sort: indices ascend within a key); the group of a key's FIRST sorted position walks the key's
+// occurrences in index order, every step through memory (a key that repeats thousands of times is one long chain —
+// exact, not fast: TFRA de-duplicates before accum, PY/dynamic_embedding_variable.py:1377-1378).
+template <int DT, int G>
+__global__ __launch_bounds__(256) void accum_segments_kernel(TableView v, size_t n, const i64* __restrict__ keys,
+                                                             const unsigned char* __restrict__ vod,
+                                                             const uint8_t* __restrict__ exists, const u64* __restrict__ scores,
+                                                             unsigned dim, AuxInit ai, int strategy, u64 epoch,
+                                                             const u64* __restrict__ sorted_keys, const unsigned* __restrict__ sorted_idx) {
+  const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
+  const size_t p = (((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4);
+  int fresh = 0, failed = 0;
+  if (p < n) {
+    const u64 k = sorted_keys[p];
+    if (p == 0 || sorted_keys[p - 1] != k) {
+      for (size_t q = p; q < n && sorted_keys[q] == k; ++q) {
+        accum_one<DT, G>(v, (size_t)sorted_idx[q], keys, vod, exists, scores, dim, ai, strategy, epoch, nullptr, 0, sub, gshift, fresh, failed);
+        __threadfence_block();   // the next occurrence reads what this one wrote (other lanes of the group, same row)
+      }
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) { fresh += __shfl_xor(fresh, o); failed += __shfl_xor(failed, o); }
+  if (lane == 0) {
+    if (fresh) size_add(v, p >> 2, fresh);
+    if (failed) atomicAdd(v.err_count, (unsigned)failed);
+  }
+}
+
+__global__ void iota_u32_kernel(unsigned* p, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = (unsigned)i;
+}
+
+static int insert_impl(Table* t, hipStream_t s, int field, size_t n, const int64_t* keys, const void* values,
+                       const uint64_t* scores, uint32_t flags) {
+  if (n == 0) return TFRA_OK;
+  if (!keys || !values) return set_error(TFRA_ERR_INVALID, "insert: null buffer");
+  if (field < 0 || field > t->opts.aux_fields) return set_error(TFRA_ERR_INVALID, "insert: bad field");
+  if (n >= (1ULL << 31)) return set_error(TFRA_ERR_INVALID, "insert: more than 2^31-1 keys per call");
+  int rc = t->prepare_insert(n, s);
+  if (rc) return rc;
+  // TableWrapper::upsert epoch stepping (lookup_table_op_hkv.h:528-536)
+  u64 epoch = t->global_epoch;
+  unsigned fo = field * t->field_bytes;
+  int g = granule_of(t->field_bytes, values, nullptr);
+  if (fo) g = std::min(g, granule_of(fo, nullptr, nullptr));
+  const i64* k = (const i64*)keys;
+  const unsigned char* vals = (const unsigned char*)values;
+  const u64* sc = (const u64*)scores;
+  int strat = t->opts.strategy;
+  constexpr int U = 4;
+  size_t waves = (n + 4 * U - 1) / (4 * U);
+  dim3 grid((unsigned)((waves + 3) / 4)), block(256);
+  // Hkv flavour at max_capacity: the table cannot grow, full home buckets evict by score (2 phases)
+  const bool bounded = t->at_max_capacity() && field == 0;
+  if (bounded && !(flags & TFRA_FLAG_UNIQUE_KEYS))
+    return set_error(TFRA_ERR_UNSUPPORTED, "insert: a bounded (Hkv) table at max_capacity needs TFRA_FLAG_UNIQUE_KEYS "
+                                           "(HKV's unique-keys contract) so that eviction is well defined");
+  if ((flags & TFRA_FLAG_UNIQUE_KEYS) && field == 0) {
+    // the single pass with bucket ownership whenever the batch is small for the table: no locks, no CAS
+    bool taken = false;
+    rc = own_upsert_unique(t, s, n, k, vals, sc, &taken);
+    if (rc) return rc;
+    if (taken) { t->step_epoch(); return TFRA_OK; }
+  }
+  if (flags & TFRA_FLAG_UNIQUE_KEYS) {
+    uint8_t* deferred = nullptr;
+    if (bounded) {
+      rc = t->ensure_scratch(n, s);
+      if (rc) return rc;
+      t->apply_P = 0;
+      deferred = (uint8_t*)t->scratch;
+    }
+    TableView v = t->view_of(t->cur);
+    const int bd = bounded ? (t->dense ? 2 : 1) : 0;
+    with_granule(g, [&](auto G) { insert_unique_kernel<G, U><<<grid, block, 0, s>>>(v, n, k, vals, sc, field, t->aux, strat, epoch, bd, deferred); });
+    if (bounded) {
+      dim3 grid2((unsigned)((n * 16 + 255) / 256));
+      with_granule(g, [&](auto G) { insert_evict_kernel<G><<<grid2, block, 0, s>>>(v, n, k, vals, sc, field, t->aux, strat, epoch, deferred); });
+    }
+  } else {
+    rc = t->ensure_winner(s);
+    if (rc) return rc;
+    rc = t->ensure_scratch(n * sizeof(i64), s);
+    if (rc) return rc;
+    t->apply_P = 0;  // scratch head is overwritten below
+    TableView v = t->view_of(t->cur);
+    i64* slot_of = (i64*)t->scratch;
+    insert_locate_kernel<U><<<grid, block, 0, s>>>(v, n, k, slot_of, field, t->aux);
+    dim3 grid2((unsigned)((n * 16 + 255) / 256));
+    with_granule(g, [&](auto G) { insert_write_kernel<G><<<grid2, block, 0, s>>>(v, n, vals, sc, slot_of, field, strat, epoch); });
+    rearm_winner_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(v, n, slot_of);
+  }
+  HIP_TRY(hipGetLastError());
+  t->step_epoch();
+  return TFRA_OK;
+}
+
+static void launch_accum(int dt, int g, dim3 grid, hipStream_t s, TableView v, size_t n, const i64* k, const unsigned char* vod,
+                         const uint8_t* ex, const u64* sc, unsigned dim, AuxInit ai, int strat, u64 epoch,
+                         const u64* sorted_keys, const unsigned* sorted_idx, uint8_t* deferred, int bmode) {
+  with_dtype(dt, [&](auto dtc) {
+    constexpr int DT = decltype(dtc)::value;
+    with_granule(g, [&](auto G) {
+      if (sorted_keys) accum_segments_kernel<DT, G><<<grid, 256, 0, s>>>(v, n, k, vod, ex, sc, dim, ai, strat, epoch, sorted_keys, sorted_idx);
+      else accum_kernel<DT, G><<<grid, 256, 0, s>>>(v, n, k, vod, ex, sc, dim, ai, strat, epoch, deferred, bmode);
+    });
+  });
+}
+
+// Unique keys, their number on the device: the ownership pass or nothing (the locked kernels size their scratch by the host's n).
+extern "C" int tfra_table_insert_or_assign_n(tfra_table_t* tp, size_t n, const int64_t* d_n, const int64_t* keys, const void* values,
+                                             const uint64_t* scores, tfra_stream_t stream) {
+  TABLE_ENTER();
+  if (n == 0) return TFRA_OK;
+  if (!d_n || !keys || !values) return set_error(TFRA_ERR_INVALID, "insert_or_assign_n: null buffer");
+  if (n >= (1ULL << 31)) return set_error(TFRA_ERR_INVALID, "insert: more than 2^31-1 keys per call");
+  int rc = t->prepare_insert(n, s);   // (n is an upper bound of the keys: a growing table may grow a call early)
+  if (rc) return rc;
+  bool taken = false;
+  rc = own_upsert_unique(t, s, n, (const i64*)keys, values, (const u64*)scores, &taken, nullptr, d_n);
+  if (rc) return rc;
+  if (!taken) return set_error(TFRA_ERR_UNSUPPORTED, "insert_or_assign_n: the single-pass write-back cannot take this call (owner tags off, "
+                                                     "a bulk load, or no scratch while capturing): read the count and call tfra_table_insert_or_assign");
+  t->step_epoch();
+  return TFRA_OK;
+}
+
+extern "C" int tfra_table_insert_or_assign(tfra_table_t* tp, size_t n, const int64_t* keys, const void* values,
+                                           const uint64_t* scores, uint32_t flags, tfra_stream_t stream) {
+  TABLE_ENTER();
+  return insert_impl(t, s, 0, n, keys, values, scores, flags);
+}
+
+extern "C" int tfra_table_insert_field(tfra_table_t* tp, int field, size_t n, const int64_t* keys, const void* values,
+                                       uint32_t flags, tfra_stream_t stream) {
+  TABLE_ENTER();
+  return insert_impl(t, s, field, n, keys, values, nullptr, flags);
+}
+
+extern "C" int tfra_table_accum_or_assign(tfra_table_t* tp, size_t n, const int64_t* keys, const void* vod,
+                                          const uint8_t* exists, const uint64_t* scores, uint32_t flags, tfra_stream_t stream) {
+  TABLE_ENTER();
+  if (n == 0) return TFRA_OK;
+  if (!keys || !vod || !exists) return set_error(TFRA_ERR_INVALID, "accum: null buffer");
+  if (n >= (1ULL << 31)) return set_error(TFRA_ERR_INVALID, "accum: more than 2^31-1 keys per call");
+  int rc = t->prepare_insert(n, s);
+  if (rc) return rc;
+  int g = granule_of(t->field_bytes, vod, nullptr);
+  TableView v = t->view_of(t->cur);
+  const i64* k = (const i64*)keys;
+  if (flags & TFRA_FLAG_UNIQUE_KEYS) {
+    // unique keys (what TFRA hands the op: PY/dynamic_embedding_variable.py:1377-1378): the single pass with bucket ownership,
+    // as tfra_table_insert_or_assign does, whenever the batch is small for the table; else the locked kernels
+    bool taken = false;
+    rc = own_upsert_unique(t, s, n, k, vod, (const u64*)scores, &taken, exists);
+    if (rc) return rc;
+    if (taken) return TFRA_OK;   // (TableWrapper::accum does not step the epoch: lookup_table_op_hkv.h:539-546)
+    dim3 grid((unsigned)((n * 16 + 255) / 256));
+    uint8_t* deferred;
+    rc = t->bounded_flags(n, s, &deferred);
+    if (rc) return rc;
+    launch_accum(t->opts.value_dtype, g, grid, s, v, n, k, (const unsigned char*)vod, exists, (const u64*)scores,
+                 (unsigned)t->opts.dim, t->aux, t->opts.strategy, t->global_epoch, nullptr, nullptr, deferred,
+                 deferred ? (t->dense ? 2 : 1) : 0);
+    if (deferred) {  // phase 2: the absent keys that found no free slot replace a minimum-score entry
+      const unsigned char* vals = (const unsigned char*)vod;
+      const u64* sc = (const u64*)scores;
+      const int strat = t->opts.strategy;
+      const u64 epoch = t->global_epoch;
+      dim3 block(256);
+      with_granule(g, [&](auto G) { insert_evict_kernel<G><<<grid, block, 0, s>>>(v, n, k, vals, sc, 0, t->aux, strat, epoch, deferred); });
+    }
+    HIP_TRY(hipGetLastError());
+    return TFRA_OK;
+  }
+  {
+    uint8_t* bounded_now;
+    rc = t->bounded_flags(1, s, &bounded_now);
+    if (rc) return rc;
+    if (bounded_now)
+      return set_error(TFRA_ERR_UNSUPPORTED, "accum: a bounded (Hkv) table at max_capacity needs TFRA_FLAG_UNIQUE_KEYS "
+                                             "(HKV's unique-keys contract) so that eviction is well defined");
+  }
+  // Duplicate-safe mode: the reference applies the triples sequentially in index order (LaunchTensorsAccum on one
+  // thread).  All on the device, no host copy and no synchronisation: a stable radix sort of (key, index) groups the
+  // occurrences of a key with their indices ascending, and accum_segments_kernel walks each group in that order.
+  {
+    size_t tmp_bytes = 0;
+    HIP_TRY(rocprim::radix_sort_pairs((void*)nullptr, tmp_bytes, (const u64*)nullptr, (u64*)nullptr, (const unsigned*)nullptr,
+                                      (unsigned*)nullptr, n, 0u, 64u, s));
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    rc = t->ensure_scratch(al(n * 8) + 2 * al(n * 4) + al(tmp_bytes), s);
+    if (rc) return rc;
+    t->apply_P = 0;  // scratch head is overwritten below
+    unsigned char* w = (unsigned char*)t->scratch;
+    u64* sorted_keys = (u64*)w; w += al(n * 8);
+    unsigned* iota = (unsigned*)w; w += al(n * 4);
+    unsigned* sorted_idx = (unsigned*)w; w += al(n * 4);
+    void* tmp = w;
+    iota_u32_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(iota, n);
+    HIP_TRY(rocprim::radix_sort_pairs(tmp, tmp_bytes, (const u64*)keys, sorted_keys, (const unsigned*)iota, sorted_idx, n, 0u, 64u, s));
+    dim3 grid((unsigned)((n * 16 + 255) / 256));
+    launch_accum(t->opts.value_dtype, g, grid, s, v, n, k, (const unsigned char*)vod, exists, (const u64*)scores,
+                 (unsigned)t->opts.dim, t->aux, t->opts.strategy, t->global_epoch, sorted_keys, sorted_idx, nullptr, 0);
+  }
+  HIP_TRY(hipGetLastError());
+  return TFRA_OK;
+}

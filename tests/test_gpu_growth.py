@@ -1,4 +1,4 @@
-"""Growth in place (tables whose storage is a mapped virtual address range: csrc/tfra_table.hip, Table::grow_in_place):
+"""Growth in place (tables whose storage is a mapped virtual address range: csrc/tfra_grow.hip, Table::grow_in_place):
 every bucket splits into its children where it is.  The table must come out exactly as the copying growth leaves it —
 same keys, rows, scores, optimizer slots, size — for cuckoo and Hkv flavours, with side rows (sentinel keys) and erased
 slots, over several doublings; and a table of more than a third of the HBM must grow where a second copy cannot exist.

@@ -376,3 +376,42 @@ def test_insert_sizes_all_dims(env, vdtype):
     assert bool((got[85 * 18:] == -1).all())
     t.clear()
     assert int(t.size()) == 0
+
+
+@pytest.mark.parametrize("max_capacity", [0, 1024], ids=["growing", "at_max_capacity"])
+def test_epoch_steps_once_per_upsert_on_every_route(env, max_capacity):
+  """Every stepping write advances the epoch counters exactly once, whichever entry point takes it: upsert of unique keys,
+  upsert with duplicates allowed, upsert_n (count on the device).  Model (TableWrapper::upsert, lookup_table_op_hkv.h:528-536):
+  curr_step starts at 1; a write scores with the current epoch, then curr_step += 1 and, when curr_step > step_per_epoch, the
+  epoch advances and curr_step = 1.  With step_per_epoch = 2 the j-th write (1-based) scores with epoch (j - 1) // 2.
+  accum_or_assign does not step (TableWrapper::accum, :539-546): the writes after it go on counting as if it had not happened.
+  A route that answers TFRA_ERR_UNSUPPORTED — its documented "not taken" reply: upsert_n when the single pass declines, duplicates
+  allowed on a bounded table at max_capacity — is replaced by upsert(unique_keys=True) for that call; the call count stands."""
+  torch, de = env
+  from tfra_amd import _capi
+  from tfra_amd.dynamic_embedding.table_ops import _DeviceTable
+  t = _DeviceTable(torch.int64, torch.int32, 0, "epoch_routes_%d" % max_capacity, "cuda:0", dim=4, init_capacity=1024,
+                   max_capacity=max_capacity, strategy=int(de.HkvEvictStrategy.EPOCHLFU), step_per_epoch=2)
+  keys = torch.arange(100, 116, device="cuda")   # 16 distinct keys in >= 1024 slots: nothing evicts
+  vals = torch.ones((16, 4), dtype=torch.int32, device="cuda")
+  count = torch.tensor([16], dtype=torch.int64, device="cuda")
+  routes = [lambda: t.upsert(keys, vals, unique_keys=True), lambda: t.upsert(keys, vals, unique_keys=False),
+            lambda: t.upsert_n(keys, count, vals)]
+
+  def write(j):   # the j-th stepping write
+    try:
+      routes[(j - 1) % 3]()
+    except _capi.TfraError as e:
+      if e.code != _capi.ERR_UNSUPPORTED:
+        raise
+      routes[0]()
+    k, _, s = t.export_all(with_scores=True, values=False)
+    assert sorted(k.tolist()) == list(range(100, 116))
+    assert (s >> 32).tolist() == [(j - 1) // 2] * 16, "write %d" % j
+
+  for j in range(1, 7):
+    write(j)
+  t.accum_or_assign(keys, vals, torch.ones(16, dtype=torch.bool, device="cuda"), unique_keys=True)
+  assert t.find(keys).tolist() == [[2] * 4] * 16   # the accumulate was applied: 1 + 1
+  write(7)
+  write(8)   # (had the accumulate stepped, this would be the ninth step and score with epoch 4)
