@@ -547,6 +547,15 @@ int tfra_sparse_segment_combine(tfra_workspace_t* ws, size_t nnz, int dim, const
 int tfra_sparse_segment_combine_backprop(tfra_workspace_t* ws, size_t nnz, int dim, const float* grad_out,
                                          const int64_t* seg, const float* weights, int combiner, size_t n_rows,
                                          float* entry_grads_out, tfra_stream_t stream);
+/* The gradient of tfra_sparse_segment_combine with respect to its WEIGHTS: dw_out[p] = d loss / d weights[p], float32 [nnz],
+ * from grad_out = d loss / d out [n_rows, dim] and x_p = rows[idx[p],:] — the formulas, conventions and evaluation order of
+ * tfra_table_find_combine_backprop_weights below (same device functions, same column-to-lane mapping: where both apply, the
+ * bits are equal).  Any dim > 0, as the forward.  seg ascending; weights NULL = all 1; an entry whose row lies outside
+ * [0, n_rows) gets 0.  Enqueues the bounds step, one memset of dw_out and one launch.  nnz == 0: TFRA_OK. */
+int tfra_sparse_segment_combine_backprop_weights(tfra_workspace_t* ws, size_t nnz, int dim, const float* rows,
+                                                 const int32_t* idx, const float* grad_out, const int64_t* seg,
+                                                 const float* weights, int combiner, size_t n_rows, float* dw_out,
+                                                 tfra_stream_t stream);
 
 /* pooled lookup = embedding_lookup_sparse's forward (PY/dynamic_embedding_ops.py:120-293) without its intermediates:
  * out[r,:] = combine over {p : seg[p] == r}, in input order, of w_p * (hit(ids[p]) ? row(ids[p]) : default_row), float32.
@@ -634,6 +643,50 @@ typedef struct {
 } tfra_find_combine_ragged_desc;
 int tfra_multi_find_combine_ragged(tfra_workspace_t* ws, size_t n_tables, const tfra_find_combine_ragged_desc* descs,
                                    uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
+
+/* The gradient of the pooled lookup with respect to its WEIGHTS (sp_weights of embedding_lookup_sparse; the reference gets it
+ * from TensorFlow's autodiff of `embeddings *= weights`, segment_sum and the divide, PY/dynamic_embedding_ops.py:233-291):
+ * dw_out[p] = d loss / d weights[p], float32 [nnz], for grad_out = d loss / d out, float32 [n_rows, dim].
+ * For row r with members p (weights w_p, rows x_p read as float32: half rows up-cast exactly, default_row on a miss, as in the
+ * forward), G = grad_out[r,:], d_p = sum_c G[c] x_p[c], s = sum_p w_p d_p and wsum = sum w (mean) | sum w^2 (sqrtn), the
+ * forward's sum:
+ *   sum    dw_p = d_p
+ *   mean   dw_p = (d_p - s / wsum) / wsum
+ *   sqrtn  dw_p = (d_p - (s / wsum) * w_p) / sqrtf(wsum)
+ * mean / sqrtn with wsum == 0: every entry of the row gets 0.  An entry with seg outside [0, n_rows) gets 0.  weights NULL = all
+ * 1; the gradient with respect to those implicit ones is still written.  seg ascending.
+ * Order (csrc/tfra_combine_device.h): lane `sub` of the row's 16-lane group holds the columns 64 c + 4 sub .. + 3; it adds its
+ * products over chunks ascending, components x, y, z, w; the group reduces by xor-shuffles with offsets 8, 4, 2, 1; columns at
+ * or beyond dim add nothing; s adds w_p * d_p in entry order.  Bit-identical to tfra_table_find(ids -> rows) followed by
+ * tfra_sparse_segment_combine_backprop_weights(float32(rows), idx = 0..nnz-1, ...).
+ * Enqueues the forward's bounds step (a memset and a launch), one memset of dw_out and one launch (one probe and one row read
+ * per entry; mean / sqrtn re-read the row's own [b, e) range of dw_out once — the table's rows are read once, the forward's out
+ * is not an input).  Never inserts, touches no score; the table's storage is read where it is at call time, behind the table's
+ * last stream.  Limits and refusals are tfra_table_find_combine's, with grad_out in the place of out: float32 / float16 /
+ * bfloat16 tables, dim % 4 == 0, dim <= 256, grad_out and default_row 16-byte aligned, nnz < 2^31, n_rows < 2^30: anything else
+ * returns TFRA_ERR_UNSUPPORTED and writes nothing; a bad combiner or a NULL buffer: TFRA_ERR_INVALID.  nnz == 0: TFRA_OK. */
+int tfra_table_find_combine_backprop_weights(tfra_table_t* t, tfra_workspace_t* ws, size_t nnz, const int64_t* ids,
+                                             const int64_t* seg, const float* weights, int combiner, size_t n_rows,
+                                             const void* default_row, const float* grad_out, float* dw_out,
+                                             tfra_stream_t stream);
+
+/* The same gradient for the ragged call (tfra_table_find_combine_ragged): row r owns the entries [b, e) with
+ * b = clamp(row_splits[r], 0, nnz), e = clamp(row_splits[r + 1], b, nnz); an entry outside that cover gets 0, and nothing
+ * outside ids / weights / dw_out [0, nnz) is read or written whatever row_splits holds.  Bit-identical to
+ * tfra_table_find_combine_backprop_weights on the row ids the splits stand for.
+ * TFRA_RAGGED_PRUNE (ignored when weights == NULL): an entry whose weight is not > 0 (NaN included) is no member: it gets
+ * exactly 0 and enters neither s nor wsum; the members' values are those of the compacted list, bit for bit.
+ * TFRA_RAGGED_FILL: a row without members yields the fill row, which does not depend on the weights: its entries get 0 (they
+ * are all pruned; fill_id is not looked up).
+ * Overlapping rows: a row_splits that decreases can make two rows claim the same entries.  Both rows' groups then write those
+ * entries of dw_out, in both passes and without ordering between them: such an entry ends as one row's value or a mix of the
+ * two.  Entries that exactly one row claims are that row's, and nothing outside [0, nnz) is touched.
+ * Enqueues one memset of dw_out and ONE launch; no workspace.  Limits and refusals are tfra_table_find_combine_ragged's, with
+ * grad_out in the place of out; unknown flag bits: TFRA_ERR_INVALID.  nnz == 0: TFRA_OK. */
+int tfra_table_find_combine_ragged_backprop_weights(tfra_table_t* t, size_t n_rows, const int64_t* row_splits, size_t nnz,
+                                                    const int64_t* ids, const float* weights, int combiner, uint32_t flags,
+                                                    int64_t fill_id, const void* default_row, const float* grad_out,
+                                                    float* dw_out, tfra_stream_t stream);
 
 /* The combined write-backs of MANY tables in one call (a 26-table model's backward is 26 tfra_table_apply_planned_combined calls =
  * ~160 enqueues otherwise): table i ends bit-identical to tfra_table_apply_planned_combined(table, opt, plan, grad_out, seg,

@@ -75,6 +75,42 @@ __device__ __forceinline__ float4 comb_grad4(float4 g, float den, float w) {
   return make_float4(comb_grad(g.x, den, w), comb_grad(g.y, den, w), comb_grad(g.z, den, w), comb_grad(g.w, den, w));
 }
 
+// ---- the gradient with respect to the WEIGHTS (sp_weights of embedding_lookup_sparse) ----------------------------------------------
+// The forward is out = A / den with A = sum_p w_p x_p over the row's members and den = 1 (sum) | W = sum w (mean) | sqrt(S),
+// S = sum w^2 (sqrtn).  With G = grad_out[r, :], d_p = sum_c G[c] x_p[c] and s = sum_p w_p d_p (members in entry order):
+//   sum    dw_p = d_p
+//   mean   dw_p = (d_p - s / W) / W
+//   sqrtn  dw_p = (d_p - (s / S) * w_p) / sqrtf(S)
+// W / S is the forward's comb_wsum / comb_wsum_pruned (the same loop); mean / sqrtn with W / S == 0 give 0 for every entry of the
+// row; an entry that is no member (pruned by weight, or in no row) gets exactly 0 and enters neither s nor W / S.
+// ONE evaluation order, for every kernel that forms dw (wgrad_*_kernel in tfra_wgrad.hip: rows straight from the table;
+// seg_combine_wgrad_kernel in tfra_frontend.hip: rows from a [U, dim] tensor), so that the routes agree bit for bit:
+//   - lane `sub` of the row's 16-lane group holds the columns 64 c + 4 sub .. + 3 of chunk c (find_combine_row's mapping);
+//   - it starts from d = 0 and adds its products G[col] * x[col] one by one, chunks ascending, components x, y, z, w inside a
+//     chunk (wgrad_dot4 / wgrad_dot1); a column at or beyond dim adds nothing (the add is skipped, not fed a zero);
+//   - the 16 partial sums are reduced by __shfl_xor with offsets 8, 4, 2, 1 (wgrad_reduce16: every lane ends with the same bits);
+//   - s starts from 0 and adds w_p * d_p per member in entry order (wgrad_s).
+// The library is built with -ffp-contract=off: every product is rounded before it is added.
+__device__ __forceinline__ void wgrad_dot1(float& d, float g, float x) { d += g * x; }
+__device__ __forceinline__ void wgrad_dot4(float& d, float4 g, float4 x) {
+  wgrad_dot1(d, g.x, x.x); wgrad_dot1(d, g.y, x.y); wgrad_dot1(d, g.z, x.z); wgrad_dot1(d, g.w, x.w);
+}
+__device__ __forceinline__ float wgrad_reduce16(float d) {
+  d += __shfl_xor(d, 8);
+  d += __shfl_xor(d, 4);
+  d += __shfl_xor(d, 2);
+  d += __shfl_xor(d, 1);
+  return d;
+}
+__device__ __forceinline__ void wgrad_s(float& s, float w, float d) { s += w * d; }
+// a member's dw from its raw d_p, its weight, the row's s and wsum (= W | S)
+__device__ __forceinline__ float wgrad_finish(float d, float w, float s, float wsum, int combiner) {
+  if (combiner == 0) return d;
+  if (!(wsum != 0.f)) return 0.f;
+  if (combiner == 1) return (d - s / wsum) / wsum;
+  return (d - (s / wsum) * w) / sqrtf(wsum);
+}
+
 // The bodies of comb_den_kernel / comb_ent_kernel (tfra_frontend.hip), one function each with two callers: the single-table kernels
 // and the grouped ones (comb_den_many_kernel / comb_ent_many_kernel), which find r / p inside THEIR descriptor
 __device__ __forceinline__ void comb_den_row(size_t r, size_t n_rows, const int* __restrict__ start_end, const float* __restrict__ w,

@@ -507,6 +507,42 @@ __global__ __launch_bounds__(256) void seg_combine_kernel(size_t n_rows, int dim
   }
 }
 
+// The gradient of seg_combine_kernel's WEIGHTS (tfra_combine_device.h: wgrad_*; the chain twin of wgrad_kernel, tfra_wgrad.hip):
+// the same 16-lane group per output row and the same column-to-lane mapping — lane `sub` adds its products over the columns
+// 64 c + 4 sub .. + 3, chunks ascending — then the group's reduction and s += w * d in entry order.  The lane (p - b) & 15 stores
+// the raw d of entry p; for mean / sqrtn the group then walks its own [b, e) of dw again, lane j re-reading what lane j wrote.
+template <bool VEC4>
+__global__ __launch_bounds__(256) void seg_combine_wgrad_kernel(size_t n_rows, int dim, const float* __restrict__ rows,
+                                                                const int* __restrict__ idx, const float* __restrict__ w,
+                                                                const int* __restrict__ start_end, int combiner,
+                                                                const float* __restrict__ grad_out, float* dw) {
+  const int sub = threadIdx.x & 15;
+  const size_t r = (((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4);
+  if (r >= n_rows) return;
+  const int b = start_end[r], e = start_end[n_rows + r];
+  if (b >= e) return;
+  const float wsum = combiner == 0 ? 0.f : comb_wsum(w, b, e, combiner);
+  const float* G = grad_out + r * (size_t)dim;
+  float s = 0.f;
+  for (int p = b; p < e; ++p) {
+    const float x = w ? w[p] : 1.f;
+    const float* row = rows + (size_t)idx[p] * dim;
+    float d = 0.f;
+    for (int c = sub * 4; c < dim; c += 64) {
+      if (VEC4) {
+        wgrad_dot4(d, *reinterpret_cast<const float4*>(G + c), *reinterpret_cast<const float4*>(row + c));
+      } else {
+        for (int k = c; k < c + 4 && k < dim; ++k) wgrad_dot1(d, G[k], row[k]);
+      }
+    }
+    d = wgrad_reduce16(d);
+    wgrad_s(s, x, d);
+    if (sub == ((p - b) & 15)) dw[p] = d;
+  }
+  if (combiner == 0) return;
+  for (int p = b + sub; p < e; p += 16) dw[p] = wgrad_finish(dw[p], w ? w[p] : 1.f, s, wsum, combiner);
+}
+
 // ------------------------------------ combiner backward (tfra_combine_device.h) -----------------
 __global__ void comb_den_kernel(size_t n_rows, const int* __restrict__ start_end, const float* __restrict__ w, int combiner,
                                 float* __restrict__ den) {
@@ -867,6 +903,32 @@ int tfra_sparse_segment_combine_backprop(tfra_workspace_t* ws, size_t nnz, int d
   const unsigned grid = (unsigned)std::min<size_t>((work + 255) / 256, 8192);
   if (vec4) comb_backprop_kernel<true><<<grid, 256, 0, s>>>(nnz, dim, grad_out, ent, entry_grads_out);
   else comb_backprop_kernel<false><<<grid, 256, 0, s>>>(nnz, dim, grad_out, ent, entry_grads_out);
+  HIP_TRY(hipGetLastError());
+  return TFRA_OK;
+}
+
+int tfra_sparse_segment_combine_backprop_weights(tfra_workspace_t* ws, size_t nnz, int dim, const float* rows, const int32_t* idx,
+                                                 const float* grad_out, const int64_t* seg, const float* weights, int combiner,
+                                                 size_t n_rows, float* dw_out, tfra_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!ws || dim <= 0 || combiner < 0 || combiner > 2) return set_error(TFRA_ERR_INVALID, "segment_combine_backprop_weights: bad argument");
+  { int cur_ = -1; if (hipGetDevice(&cur_) != hipSuccess || cur_ != ws->device) HIP_TRY(hipSetDevice(ws->device)); }
+  if (nnz == 0) return TFRA_OK;
+  if (!rows || !idx || !seg || !dw_out || (n_rows && !grad_out)) return set_error(TFRA_ERR_INVALID, "segment_combine_backprop_weights: null buffer");
+  if (nnz >= (1ULL << 31) || n_rows >= (1ULL << 30)) return set_error(TFRA_ERR_INVALID, "segment_combine_backprop_weights: too large");
+  if (((uintptr_t)seg & 7) || (((uintptr_t)weights | (uintptr_t)idx | (uintptr_t)rows | (uintptr_t)grad_out | (uintptr_t)dw_out) & 3))
+    return set_error(TFRA_ERR_UNSUPPORTED, "segment_combine_backprop_weights: misaligned buffer");
+  HIP_TRY(hipMemsetAsync(dw_out, 0, nnz * sizeof(float), s));   // entries in no row: 0
+  if (n_rows == 0) return TFRA_OK;
+  int rc = ws->ensure(align_up(2 * n_rows * sizeof(int)), s);
+  if (rc) return rc;
+  int* se = (int*)ws->buf;
+  rc = comb_bounds(s, nnz, seg, n_rows, se);
+  if (rc) return rc;
+  dim3 grid((unsigned)((n_rows * 16 + 255) / 256));
+  const bool vec4 = dim % 4 == 0 && (((uintptr_t)rows | (uintptr_t)grad_out) % 16 == 0);
+  if (vec4) seg_combine_wgrad_kernel<true><<<grid, 256, 0, s>>>(n_rows, dim, rows, idx, weights, se, combiner, grad_out, dw_out);
+  else seg_combine_wgrad_kernel<false><<<grid, 256, 0, s>>>(n_rows, dim, rows, idx, weights, se, combiner, grad_out, dw_out);
   HIP_TRY(hipGetLastError());
   return TFRA_OK;
 }

@@ -8,7 +8,8 @@
 // nothing is counted on the host.  The arithmetic is tfra_combine_device.h's, the code seg_combine_kernel (tfra_frontend.hip)
 // compiles, in the same order, so the result equals tfra_table_find + tfra_sparse_segment_combine bit for bit.
 // tfra_multi_find_combine is the same lookup for a list of tables; its host side stands on the grouped-call frame of tfra_many.h,
-// and both calls run ONE function for their argument checks (check_find_combine) and one launch ladder (with_pool_class).
+// and both calls run ONE function for their argument checks (check_find_combine) and one launch ladder (with_pool_class); those
+// live in tfra_pool.h, which the gradient of the lookup's weights (tfra_wgrad.hip) shares.
 // tfra_table_find_combine_ragged / tfra_multi_find_combine_ragged are the two calls over a rank-2 RaggedTensor (PY/ragged_embedding_ops.py:
 // 129-442): the row's entry range comes from row_splits, so ONE launch serves a call, and safe_embedding_lookup_sparse's pruning by
 // weight and its default_id run inside that launch (find_combine_row's RAGGED and SAFE axes; check_find_combine_ragged, with_ragged_class).
@@ -25,31 +26,11 @@
 #include "tfra_device.h"
 #include "tfra_host.h"
 #include "tfra_many.h"
+#include "tfra_pool.h"
 
 using namespace tfra;
 
 namespace {
-
-// four elements of a row as float32: a 16-B load of a float32 row, an 8-B load of a half row up-cast exactly
-template <int DT> struct PoolRow;
-template <> struct PoolRow<TFRA_F32> {
-  typedef float4 Raw;
-  static __device__ __forceinline__ float4 widen(float4 x) { return x; }
-};
-template <> struct PoolRow<TFRA_F16> {
-  typedef uint2 Raw;
-  static __device__ __forceinline__ float h(unsigned short b) { return (float)__builtin_bit_cast(_Float16, b); }
-  static __device__ __forceinline__ float4 widen(uint2 x) {
-    return make_float4(h((unsigned short)x.x), h((unsigned short)(x.x >> 16)), h((unsigned short)x.y), h((unsigned short)(x.y >> 16)));
-  }
-};
-template <> struct PoolRow<TFRA_BF16> {
-  typedef uint2 Raw;
-  static __device__ __forceinline__ float4 widen(uint2 x) {
-    return make_float4(bf16_to_f32((unsigned short)x.x), bf16_to_f32((unsigned short)(x.x >> 16)), bf16_to_f32((unsigned short)x.y),
-                       bf16_to_f32((unsigned short)(x.y >> 16)));
-  }
-};
 
 // One 16-lane group per output row (find_wave's and seg_combine_kernel's mapping: 4 rows per wave64).  The row's entries [b, e)
 // are taken 16 at a time — lane j of the group loads id and weight of entry p0 + j and hashes it, one instruction stream for 16
@@ -276,81 +257,6 @@ __global__ __launch_bounds__(256) void seg64_bounds_many_kernel(const BoundsRec*
   if (s < 0 || (size_t)s >= rec.n_rows) return;
   if (p == 0 || rec.seg[p - 1] != s) rec.se[s] = (int)p;
   if (p == rec.nnz - 1 || rec.seg[p + 1] != s) rec.se[rec.n_rows + s] = (int)p + 1;
-}
-
-// NCH by the row width: 1 (dim <= 64), 2 (<= 128) or 4 column chunks; f(std::integral_constant<int, NCH>{}) for the index
-int nch_index(int dim) { return dim <= 64 ? 0 : dim <= 128 ? 1 : 2; }
-template <class F>
-void with_nch(int index, F&& f) {
-  switch (index) {
-    case 0: f(std::integral_constant<int, 1>{}); break;
-    case 1: f(std::integral_constant<int, 2>{}); break;
-    default: f(std::integral_constant<int, 4>{}); break;
-  }
-}
-// launch(DT, U, NCH) for a table's storage type index and NCH index: the one ladder of the single and the grouped launch
-template <class F>
-void with_pool_class(int st, int nch, F&& launch) {
-  with_stored(st, [&](auto DT) { with_nch(nch, [&](auto NCH) { launch(DT, std::integral_constant<int, 4>{}, NCH); }); });
-}
-
-// The checks of a pooled lookup, for tfra_table_find_combine and for each descriptor of tfra_multi_find_combine.
-// active: there are rows to write.
-const char* const NEEDS_DIM = "needs dim % 4 == 0 and dim <= 256";
-template <class AtEntry>
-Check check_find_combine(const Table* t, const tfra_workspace* ws, size_t nnz, const void* ids, const void* seg, const float* weights,
-                         int combiner, size_t n_rows, const void* default_row, const float* out, AtEntry&& at_entry) {
-  if (!t) return refuse(TFRA_ERR_INVALID, "null table");
-  if (!ws || combiner < 0 || combiner > 2) return refuse(TFRA_ERR_INVALID, "bad argument");
-  if (Check e = at_entry(); e.done()) return e;
-  if (ws->device != t->device) return refuse(TFRA_ERR_INVALID, "workspace and table live on different devices");
-  const int dt = t->opts.value_dtype, dim = t->opts.dim;
-  if (dt != TFRA_F32 && dt != TFRA_F16 && dt != TFRA_BF16) return refuse(TFRA_ERR_UNSUPPORTED, "value_dtype must be float32, float16 or bfloat16");
-  if (dim % 4 != 0 || dim > 256) return refuse(TFRA_ERR_UNSUPPORTED, NEEDS_DIM);
-  if (nnz >= (1ULL << 31) || n_rows >= (1ULL << 30)) return refuse(TFRA_ERR_UNSUPPORTED, "too large (nnz < 2^31, n_rows < 2^30)");
-  if ((((uintptr_t)out | (uintptr_t)default_row) & 15) || ((uintptr_t)ids & 7) || ((uintptr_t)seg & 7) || ((uintptr_t)weights & 3))
-    return refuse(TFRA_ERR_UNSUPPORTED, "misaligned buffer (out and default_row: 16 bytes)");
-  if (n_rows == 0) return nothing_to_do();
-  if (!out) return refuse(TFRA_ERR_INVALID, "null out");
-  if (nnz && (!ids || !seg || !default_row)) return refuse(TFRA_ERR_INVALID, "null buffer");
-  return Check{};
-}
-
-// The checks of a ragged pooled lookup, for tfra_table_find_combine_ragged and for each descriptor of tfra_multi_find_combine_ragged:
-// check_find_combine's codes and wording for table, dtype, dim, size and alignment, and what only the ragged form can get wrong.
-// ws: the grouped call's workspace; the single call needs none (NULL).  row_splits' CONTENT is not looked at: the kernel clamps it.
-template <class AtEntry>
-Check check_find_combine_ragged(const Table* t, const tfra_workspace* ws, size_t n_rows, const void* row_splits, size_t nnz, const void* ids,
-                                const float* weights, int combiner, uint32_t flags, uint32_t reserved, const void* default_row,
-                                const float* out, AtEntry&& at_entry) {
-  if (!t) return refuse(TFRA_ERR_INVALID, "null table");
-  if (combiner < 0 || combiner > 2) return refuse(TFRA_ERR_INVALID, "bad argument");
-  if (flags & ~(TFRA_RAGGED_PRUNE | TFRA_RAGGED_FILL)) return refuse(TFRA_ERR_INVALID, "unknown flag bits (TFRA_RAGGED_PRUNE | TFRA_RAGGED_FILL)");
-  if (reserved) return refuse(TFRA_ERR_INVALID, "reserved must be 0");
-  if (Check e = at_entry(); e.done()) return e;
-  if (ws && ws->device != t->device) return refuse(TFRA_ERR_INVALID, "workspace and table live on different devices");
-  const int dt = t->opts.value_dtype, dim = t->opts.dim;
-  if (dt != TFRA_F32 && dt != TFRA_F16 && dt != TFRA_BF16) return refuse(TFRA_ERR_UNSUPPORTED, "value_dtype must be float32, float16 or bfloat16");
-  if (dim % 4 != 0 || dim > 256) return refuse(TFRA_ERR_UNSUPPORTED, NEEDS_DIM);
-  if (nnz >= (1ULL << 31) || n_rows >= (1ULL << 30)) return refuse(TFRA_ERR_UNSUPPORTED, "too large (nnz < 2^31, n_rows < 2^30)");
-  if ((((uintptr_t)out | (uintptr_t)default_row) & 15) || ((uintptr_t)ids & 7) || ((uintptr_t)weights & 3))
-    return refuse(TFRA_ERR_UNSUPPORTED, "misaligned buffer (out and default_row: 16 bytes)");
-  if ((uintptr_t)row_splits & 7) return refuse(TFRA_ERR_UNSUPPORTED, "misaligned row_splits (8 bytes)");
-  if (n_rows == 0) return nothing_to_do();
-  if (!out) return refuse(TFRA_ERR_INVALID, "null out");
-  if (!row_splits) return refuse(TFRA_ERR_INVALID, "null row_splits");
-  if ((nnz && !ids) || ((nnz || (flags & TFRA_RAGGED_FILL)) && !default_row)) return refuse(TFRA_ERR_INVALID, "null buffer");
-  return Check{};
-}
-// whether the flags change anything: the SAFE kernels run only then
-bool ragged_safe(uint32_t flags, const float* weights) { return (flags & TFRA_RAGGED_FILL) || ((flags & TFRA_RAGGED_PRUNE) && weights); }
-// launch(DT, U, NCH, SAFE): with_pool_class with the ragged forms' fourth axis
-template <class F>
-void with_ragged_class(int st, int nch, bool safe, F&& launch) {
-  with_pool_class(st, nch, [&](auto DT, auto U, auto NCH) {
-    if (safe) launch(DT, U, NCH, std::true_type{});
-    else launch(DT, U, NCH, std::false_type{});
-  });
 }
 
 }  // namespace

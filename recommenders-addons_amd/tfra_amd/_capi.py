@@ -195,6 +195,9 @@ _SIGS = {
     "tfra_multi_find_combine": [_P, _SZ, _P, _P, _P],
     "tfra_table_find_combine_ragged": [_P, _SZ, _P, _SZ, _P, _P, _I, ctypes.c_uint32, ctypes.c_int64, _P, _P, _P],
     "tfra_multi_find_combine_ragged": [_P, _SZ, _P, _P, _P],
+    "tfra_table_find_combine_backprop_weights": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, _P, _P, _P],
+    "tfra_table_find_combine_ragged_backprop_weights": [_P, _SZ, _P, _SZ, _P, _P, _I, ctypes.c_uint32, ctypes.c_int64, _P, _P, _P,
+                                                        _P],
     "tfra_multi_apply_planned_combined": [_P, _SZ, _P, _P, _P],
     "tfra_multi_sparse_plan_build": [_P, _SZ, _P, _P, _P],
     "tfra_segment_sum": [_P, _SZ, _I, _P, _P, _P, _SZ, _P, _P],
@@ -203,6 +206,7 @@ _SIGS = {
     "tfra_keys_narrow_i32": [_SZ, _P, _P, _P, _P],
     "tfra_sparse_segment_combine": [_P, _SZ, _I, _P, _P, _P, _P, _I, _SZ, _P, _P],
     "tfra_sparse_segment_combine_backprop": [_P, _SZ, _I, _P, _P, _P, _I, _SZ, _P, _P],
+    "tfra_sparse_segment_combine_backprop_weights": [_P, _SZ, _I, _P, _P, _P, _P, _P, _I, _SZ, _P, _P],
     "tfra_partition": [_P, _SZ, _P, _P, _I, _I, _P, _P, _P, _P],
     "tfra_partition_by_owner": [_P, _SZ, _P, _I, _P, _P, _P],
     "tfra_scatter_rows": [_SZ, _SZ, _P, _P, _P, _P],

@@ -233,6 +233,33 @@ def sparse_segment_combine(rows, idx, seg, weights, combiner, n_rows):
   return out
 
 
+def sparse_segment_combine_weight_grad(rows, idx, grad_out, seg, weights, combiner):
+  """The gradient of `sparse_segment_combine` with respect to its weights (tfra_sparse_segment_combine_backprop_weights):
+  float32 [nnz], dw[p] = d loss / d weights[p] for grad_out = d loss / d out [n_rows, dim].  With d_p = grad_out[seg[p]] . rows[idx[p]],
+  s = sum_p w_p d_p over the row and W = sum w (mean) | sum w^2 (sqrtn):  sum d_p | mean (d_p - s / W) / W |
+  sqrtn (d_p - (s / W) w_p) / sqrt(W); 0 for a row with W == 0 and for an entry whose row lies outside [0, n_rows).
+  weights None = all 1 (the gradient with respect to those ones is still returned).  seg ascending.  Bit-identical to
+  `_DeviceTable.find_combine_weight_grad` where both apply."""
+  rows = rows.to(torch.float32).contiguous()
+  dev = rows.device
+  idx = idx.to(dev, torch.int32).contiguous().reshape(-1)
+  seg = seg.to(dev, torch.int64).contiguous().reshape(-1)
+  grad_out = grad_out.to(dev, torch.float32).contiguous()
+  if rows.dim() != 2 or grad_out.dim() != 2 or grad_out.shape[1] != rows.shape[1]:
+    raise ValueError("rows must be [U, dim] and grad_out [n_rows, dim], got %s and %s" % (list(rows.shape), list(grad_out.shape)))
+  nnz = idx.numel()
+  if seg.numel() != nnz:
+    raise ValueError("indices and segment_ids must have the same number of elements: %d vs %d" % (nnz, seg.numel()))
+  if weights is not None and torch.as_tensor(weights).numel() != nnz:
+    raise ValueError("weights must have one element per index")
+  w = None if weights is None else torch.as_tensor(weights, device=dev).to(torch.float32).contiguous().reshape(-1)
+  n_rows, dim = grad_out.shape
+  out = torch.empty(nnz, dtype=torch.float32, device=dev)
+  _capi.call("tfra_sparse_segment_combine_backprop_weights", _workspace(dev), nnz, dim, _ptr(rows), _ptr(idx), _ptr(grad_out),
+             _ptr(seg), _ptr(w), COMBINERS[combiner], n_rows, _ptr(out), _stream(dev))
+  return out
+
+
 def sparse_segment_combine_backprop(grad_out, seg, weights, combiner):
   """The backward of `sparse_segment_combine` (TF's SparseSegment{Sum,Mean,SqrtN}Grad with the weights multiply):
   entry_grads[e] = (grad_out[seg[e]] / den) * weights[e], den = 1 (sum) | the row's weight sum (mean) | sqrt of the sum of

@@ -21,7 +21,8 @@ made by the tuple form's preprocessing as it is, host syncs included."""
 import torch
 
 from . import device_ops
-from .variable import (SparseTrainableWrapper, _check_combiner, _per_table, _pooled_forward, _safe_sparse_args, _wrap_grouped)
+from .variable import (SparseTrainableWrapper, _check_combiner, _note_pruned, _per_table, _pooled_forward, _safe_sparse_args,
+                       _wrap_grouped)
 from . import variable as _tuple_form
 
 
@@ -70,10 +71,12 @@ def _safe_entries(params, rs, ids, w, combiner, default_id, n):
   return rows, p_ids, p_w, entries, out_shape
 
 
-def _safe_wrapper(params, args, combiner, n, plan_writeback, entry_plan=None):
+def _safe_wrapper(params, args, combiner, n, plan_writeback, entry_plan=None, caller_weights=None):
+  """caller_weights: the weights as the caller gave them (`SparseTrainableWrapper.weights_grad` answers in their length)."""
   rows, p_ids, p_w, entries, out_shape = args
-  return SparseTrainableWrapper(params, None, None, None, rows, p_w, combiner, n, out_shape, entries[0], entries[1], entries[2],
-                                plan_writeback=plan_writeback, lookup_ids=p_ids, entry_plan=entry_plan)
+  tw = SparseTrainableWrapper(params, None, None, None, rows, p_w, combiner, n, out_shape, entries[0], entries[1], entries[2],
+                              plan_writeback=plan_writeback, lookup_ids=p_ids, entry_plan=entry_plan)
+  return _note_pruned(tw, caller_weights, combiner)
 
 
 def embedding_lookup_sparse(params, sp_ids, sp_weights, name=None, combiner="mean", return_trainable=False, plan_writeback=False):
@@ -116,7 +119,8 @@ def safe_embedding_lookup_sparse(params, sparse_ids, sparse_weights=None, combin
   out = params.lookup_combined_ragged(rs, ids, w, combiner, prune=prune, fill_id=fill)
   if not return_trainable:
     return out
-  return out, _safe_wrapper(params, _safe_entries(params, rs, ids, w, combiner, default_id, n), combiner, n, plan_writeback)
+  return out, _safe_wrapper(params, _safe_entries(params, rs, ids, w, combiner, default_id, n), combiner, n, plan_writeback,
+                            caller_weights=w)
 
 
 def _many(params_list, sp_ids_list, weights_list, combiner, default_id, safe, return_trainable, plan_writeback):
@@ -158,7 +162,7 @@ def _many(params_list, sp_ids_list, weights_list, combiner, default_id, safe, re
     def wrapper(member, own_plan, entry_plan):
       i, rs, ids, w = member
       params, n = params_list[i], rs.numel() - 1
-      return (_safe_wrapper(params, made[i], combiners[i], n, own_plan, entry_plan) if safe else
+      return (_safe_wrapper(params, made[i], combiners[i], n, own_plan, entry_plan, caller_weights=w) if safe else
               _plain_wrapper(params, rs, ids, w, combiners[i], n, own_plan, entry_plan))
 
     _wrap_grouped(device, params_list, members, outs, {i: (made[i][3][0] if safe else ids) for i, _, ids, _ in members},

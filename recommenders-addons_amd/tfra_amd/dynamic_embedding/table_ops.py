@@ -347,6 +347,41 @@ class _DeviceTable:
                flags, fill, _ptr(d), _ptr(out), _stream(self._device))
     return out
 
+  def _weight_grad_out(self, grad_out, n_rows):
+    """grad_out of a pooled lookup as the C calls read it: float32 [n_rows, dim] on the table's device, contiguous."""
+    g = torch.as_tensor(grad_out, device=self._device).to(torch.float32).contiguous()
+    if g.dim() != 2 or g.shape[1] != self._dim or (n_rows is not None and g.shape[0] != n_rows):
+      raise ValueError("grad_out must be [%s, %d] (the lookup's result), got %s" %
+                       ("n_rows" if n_rows is None else n_rows, self._dim, list(g.shape)))
+    return g
+
+  def find_combine_weight_grad(self, ids, seg, weights, combiner, grad_out, default_row=None):
+    """The gradient of `find_combine` with respect to its weights (tfra_table_find_combine_backprop_weights): float32 [nnz],
+    dw[p] = d loss / d weights[p] for grad_out = d loss / d out, float32 [n_rows, dim] — the rows read straight from the table as
+    the forward reads them (the default row on a miss), never inserted, no [nnz, dim] tensor.  weights None = all 1 (the gradient
+    with respect to those ones is still returned); an entry whose row lies outside [0, n_rows) gets 0; mean / sqrtn give 0 for a
+    row whose weight sum is 0.  The limits are `find_combine`'s.  Bit-identical to find + device_ops.sparse_segment_combine_weight_grad
+    over idx = arange(nnz)."""
+    g = self._weight_grad_out(grad_out, None)
+    ids, seg, w, d, _ = self._find_combine_args(ids, seg, weights, 0, default_row)
+    dw = torch.empty(ids.numel(), dtype=torch.float32, device=self._device)
+    _capi.call("tfra_table_find_combine_backprop_weights", self._h, _workspace(self._device), ids.numel(), _ptr(ids), _ptr(seg),
+               _ptr(w), int(combiner), g.shape[0], _ptr(d), _ptr(g), _ptr(dw), _stream(self._device))
+    return dw
+
+  def find_combine_ragged_weight_grad(self, row_splits, ids, weights, combiner, grad_out, prune=False, fill_id=None,
+                                      default_row=None):
+    """`find_combine_weight_grad` for `find_combine_ragged` (tfra_table_find_combine_ragged_backprop_weights), bit-identical to it on
+    the row ids the splits stand for, in one launch.  An entry outside the clamped cover of row_splits gets 0.  prune: an entry
+    whose weight is not > 0 gets exactly 0 and is in no sum, the members' values are those of the compacted list.  fill_id: the
+    entries of a row without members get 0 (the fill row does not depend on the weights)."""
+    rs, ids, w, flags, fill, d, _ = self._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row)
+    g = self._weight_grad_out(grad_out, rs.numel() - 1)
+    dw = torch.empty(ids.numel(), dtype=torch.float32, device=self._device)
+    _capi.call("tfra_table_find_combine_ragged_backprop_weights", self._h, rs.numel() - 1, _ptr(rs), ids.numel(), _ptr(ids),
+               _ptr(w), int(combiner), flags, fill, _ptr(d), _ptr(g), _ptr(dw), _stream(self._device))
+    return dw
+
   def upsert(self, keys, values, scores=None, unique_keys=False, field=0):
     keys = self._keys(keys)
     values = self._values_for(keys, values)

@@ -271,6 +271,30 @@ class Variable:
     return t._table.find_combine_ragged(row_splits, ids.reshape(-1), weights, device_ops.COMBINERS[combiner], prune=prune,
                                         fill_id=fill_id, default_row=t._default_value)
 
+  def lookup_combined_weight_grad(self, ids, seg, weights, combiner, grad_out, name=None):
+    """The gradient of `lookup_combined` with respect to `weights` (tfra_table_find_combine_backprop_weights): float32 [nnz] from
+    grad_out = d loss / d result, [n_rows, dim].  The rows are read from the table as they are now, as the forward reads them
+    (the default row on a miss); nothing is inserted and no [nnz, dim] tensor exists.  weights None = all 1.  Under
+    `can_lookup_combined()`'s conditions."""
+    if not self.can_lookup_combined():
+      raise ValueError("lookup_combined needs one shard, a static default row, float32 / float16 / bfloat16 rows, dim % 4 == 0 "
+                       "and dim <= 256; use embedding_lookup_sparse")
+    t = self._tables[0]
+    ids = torch.as_tensor(ids, device=self._primary)
+    return t._table.find_combine_weight_grad(ids.reshape(-1), seg, weights, device_ops.COMBINERS[combiner], grad_out, t._default_value)
+
+  def lookup_combined_ragged_weight_grad(self, row_splits, ids, weights, combiner, grad_out, prune=False, fill_id=None, name=None):
+    """`lookup_combined_weight_grad` for `lookup_combined_ragged` (tfra_table_find_combine_ragged_backprop_weights): bit-identical to
+    it on the row ids the splits stand for, in one launch.  prune: the entries the forward prunes get exactly 0; fill_id: the
+    entries of a row that takes the fill row get 0.  Under `can_lookup_combined()`'s conditions."""
+    if not self.can_lookup_combined():
+      raise ValueError("lookup_combined_ragged needs one shard, a static default row, float32 / float16 / bfloat16 rows, "
+                       "dim % 4 == 0 and dim <= 256; use ragged_embedding_ops.embedding_lookup_sparse")
+    t = self._tables[0]
+    ids = torch.as_tensor(ids, device=self._primary)
+    return t._table.find_combine_ragged_weight_grad(row_splits, ids.reshape(-1), weights, device_ops.COMBINERS[combiner], grad_out,
+                                                    prune=prune, fill_id=fill_id, default_row=t._default_value)
+
   def export(self, name=None):
     """PY/dynamic_embedding_variable.py:988-1007"""
     ks, vs = [], []
@@ -612,7 +636,11 @@ class SparseTrainableWrapper(TrainableWrapper):
   A wrapper made behind the pooled forward (`lookup_ids`: the lookup's ids as given, instead of `ids` / `idx` / `n_unique`) has
   not de-duplicated anything yet: `ids`, `_idx`, `_n_unique`, `exists` and the rows behind `read_value()` are resolved on their
   first access — tf.unique of the lookup's ids and a lookup of the unique ids, as the eager wrapper does at construction (the
-  rows are then those the table holds at that moment).  `apply_combined_gradients` needs none of them."""
+  rows are then those the table holds at that moment).  `apply_combined_gradients` needs none of them.
+
+  `weights_grad` is the gradient of the result with respect to the caller's sp_weights; for it the wrapper keeps the lookup's ids
+  as given (`_pooled_ids`, a reference that survives the lazy resolution) and, behind a safe lookup that pruned by weight, the
+  caller's weights (`_caller_weights`: `_note_pruned`), from which the pruned positions are found when the gradient is asked for."""
 
   _LAZY = ("ids", "_idx", "_n_unique", "exists", "_values")
 
@@ -625,7 +653,8 @@ class SparseTrainableWrapper(TrainableWrapper):
       self._idx, self._n_unique = idx, n_unique
     else:
       self.params, self.max_norm, self.plan = params, max_norm, None
-    self._lookup_ids = lookup_ids
+    self._lookup_ids = self._pooled_ids = lookup_ids
+    self._caller_weights = None
     self.combiner = combiner
     self.n_rows = int(n_rows)
     self.out_shape = tuple(out_shape)
@@ -670,6 +699,45 @@ class SparseTrainableWrapper(TrainableWrapper):
     eg = device_ops.sparse_segment_combine_backprop(g, self._seg, self._weights, self.combiner)
     n = self.ids.numel()
     return device_ops.segment_sum(eg, self._idx, self._n_unique, n)
+
+
+  def weights_grad(self, grad_out):
+    """The gradient of the lookup's result with respect to the VALUES of the sp_weights the caller passed: float32, the caller's
+    length and order, from grad_out = d loss / d result (the result's shape).  Entries the safe form pruned get 0; the entries
+    it adds for empty rows are not the caller's and do not appear; a row that took `default_id` contributes nothing.
+    The table's rows are read AS THEY ARE AT CALL TIME: call it before the step's write-back (`apply_combined_gradients`), or
+    the gradient is that of the updated rows.
+    A variable the pooled forward serves is read straight from the table (`Variable.lookup_combined_weight_grad`: no [nnz, dim]
+    rows); every other one — several shards, a callable initializer, bp_v2, other dims or dtypes — goes through a lookup of the
+    unique ids and `device_ops.sparse_segment_combine_weight_grad`.  The two routes give the same bits for the same rows.
+    Nothing is read on the host on the pooled route, pruned or not (the pruned positions are filled by a masked scatter).
+    ValueError for a lookup made without sp_weights, with max_norm (the clip's own gradient is not formed, as in
+    `apply_combined_gradients`), or for a grad_out of another shape."""
+    if self.max_norm is not None:
+      raise ValueError("weights_grad does not support max_norm: the clip's gradient is not formed")
+    if self._weights is None:
+      raise ValueError("weights_grad needs a lookup made with sp_weights")
+    g = self.check_grad_out(grad_out)
+    if self._pooled_ids is not None and _pooled_forward(self.params, None):
+      dw = self.params.lookup_combined_weight_grad(self._pooled_ids, self._seg, self._weights, self.combiner, g)
+    else:
+      rows = self.params.lookup(self.ids).to(torch.float32)
+      dw = device_ops.sparse_segment_combine_weight_grad(rows, self._idx, g, self._seg, self._weights, self.combiner)
+    if self._caller_weights is None:
+      return dw
+    cw = torch.as_tensor(self._caller_weights, dtype=torch.float32, device=dw.device).reshape(-1)
+    # dw holds one value per kept entry, in order: `_safe_sparse_args` kept exactly the entries with weight > 0.  masked_scatter_
+    # fills the kept positions from dw in order, on the device (no host read, unlike a boolean-mask assignment)
+    return torch.zeros(cw.numel(), dtype=torch.float32, device=dw.device).masked_scatter_(cw > 0, dw)
+
+
+def _note_pruned(tw, sparse_weights, combiner):
+  """Behind a safe lookup: the wrapper remembers the caller's weights when entries were pruned by them (weights given and the
+  combiner not "sum": `_safe_sparse_args`), so that `weights_grad` can answer in the caller's length and order.  A reference
+  only: constructing the wrapper stays as cheap as it is."""
+  if tw is not None and sparse_weights is not None and combiner != "sum":
+    tw._caller_weights = sparse_weights
+  return tw
 
 
 def embedding_lookup(params, ids, partition_strategy=None, name=None, validate_indices=None, max_norm=None,
@@ -932,7 +1000,7 @@ def safe_embedding_lookup_sparse(params, sp_ids, sparse_weights=None, combiner="
                                 _entries=entries, _out_shape=out_shape)
   res, tw = out if return_trainable else (out, None)
   res = _safe_sparse_finish(params, res, rows, n, default_id, max_norm, lead)
-  return (res, tw) if return_trainable else res
+  return (res, _note_pruned(tw, sparse_weights, combiner)) if return_trainable else res
 
 
 def safe_embedding_lookup_sparse_many(params_list, sp_ids_list, sparse_weights_list=None, combiner="mean", default_id=None,
@@ -968,5 +1036,5 @@ def safe_embedding_lookup_sparse_many(params_list, sp_ids_list, sparse_weights_l
   for i, (rows, ids, w, n, entries, out_shape, lead) in enumerate(args):
     res, tw = outs[i] if return_trainable else (outs[i], None)
     res = _safe_sparse_finish(params_list[i], res, rows, n, default_ids[i], max_norm, lead)
-    results.append((res, tw) if return_trainable else res)
+    results.append((res, _note_pruned(tw, weights[i], combiners[i])) if return_trainable else res)
   return results
