@@ -64,7 +64,7 @@ __device__ __forceinline__ void hot_sums_body(const float* __restrict__ grads, i
   if (progress && blk == 0 && threadIdx.x == 0)
     __hip_atomic_store(progress, progress_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48, g = threadIdx.x >> 4;
-  const unsigned nbins = d_counts[3];
+  const unsigned nbins = d_counts[PC_BINS];
   for (unsigned ib = blk; ib < nbins; ib += nblk) {
     const unsigned bin = binmap[ib];
     const unsigned e = hent[(size_t)bin * SEG + threadIdx.x];          // lane `sub` holds entry `sub` of the item
@@ -229,11 +229,11 @@ __device__ __forceinline__ void apply_csr_body(const TableView& v, OptP o, int d
   if (PHASE2 && *any_deferred != use_gen) return;   // phase 1 of this use deferred nothing
   constexpr int S = NSlots<KIND>::v;
   const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
-  const unsigned total = ks.d_counts[0] + ks.d_counts[1];
+  const unsigned total = ks.d_counts[PC_HOT] + ks.d_counts[PC_COLD];
   const unsigned ngroups = (nblk * blockDim.x) >> 4;
   int fresh = 0, failed = 0;
   if (o.d_lr) o.lr = *o.d_lr;
-  if (!PHASE2 && blk == 0 && threadIdx.x == 0 && ks.d_counts[5]) atomicAdd(v.err_count, ks.d_counts[5]);  // plan overflow
+  if (!PHASE2 && blk == 0 && threadIdx.x == 0 && ks.d_counts[PC_OVERFLOW]) atomicAdd(v.err_count, ks.d_counts[PC_OVERFLOW]);  // plan overflow
   // trips are uniform per wave (the batch width below is a wave-wide maximum): a group past the end re-reads the
   // last key's records and does nothing else
   for (unsigned wbase = ((blk * blockDim.x + threadIdx.x) >> 6) << 2; wbase < total; wbase += ngroups) {
@@ -437,9 +437,9 @@ __global__ __launch_bounds__(256) void gather_csr_kernel(int dim, const float* _
                                                          i64* __restrict__ keys_out, float* __restrict__ rows_out,
                                                          i64* __restrict__ d_count, const int* __restrict__ dest) {
   const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
-  const unsigned total = ks.d_counts[0] + ks.d_counts[1];
+  const unsigned total = ks.d_counts[PC_HOT] + ks.d_counts[PC_COLD];
   const unsigned ngroups = (gridDim.x * blockDim.x) >> 4;
-  if (d_count && blockIdx.x == 0 && threadIdx.x == 0) *d_count = ks.d_counts[5] ? (i64)-1 : (i64)total;
+  if (d_count && blockIdx.x == 0 && threadIdx.x == 0) *d_count = ks.d_counts[PC_OVERFLOW] ? (i64)-1 : (i64)total;
   for (unsigned wbase = ((blockIdx.x * blockDim.x + threadIdx.x) >> 6) << 2; wbase < total; wbase += ngroups) {
     const unsigned it_raw = wbase + (unsigned)(lane >> 4);
     const bool active = it_raw < total;
@@ -952,7 +952,7 @@ extern "C" int tfra_reduce_by_key(tfra_workspace_t* ws, size_t n, const int64_t*
                                   int64_t* keys_out, float* rows_out, int64_t* d_count, tfra_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
   if (!ws || !d_count) return set_error(TFRA_ERR_INVALID, "reduce_by_key: null argument");
-  { int cur_ = -1; if (hipGetDevice(&cur_) != hipSuccess || cur_ != ws->device) { if (hipSetDevice(ws->device) != hipSuccess) return set_error(TFRA_ERR_HIP, "reduce_by_key: hipSetDevice"); } }
+  if (on_device(ws->device) != hipSuccess) return set_error(TFRA_ERR_HIP, "reduce_by_key: hipSetDevice");
   if (n == 0) {
     if (hipMemsetAsync(d_count, 0, sizeof(int64_t), s) != hipSuccess) return set_error(TFRA_ERR_HIP, "reduce_by_key: memset");
     return TFRA_OK;
@@ -994,7 +994,7 @@ extern "C" int tfra_plan_reduce_to(const tfra_sparse_plan_t* pl, const float* gr
   const int dim = pl->dim;
   if (dim <= 0 || (((uintptr_t)grads | (uintptr_t)rows_out) & 15))
     return set_error(TFRA_ERR_INVALID, "plan_reduce_to: the plan must have been built with the rows' dim; buffers 16-B aligned");
-  { int cur_ = -1; if (hipGetDevice(&cur_) != hipSuccess || cur_ != pl->device) { if (hipSetDevice(pl->device) != hipSuccess) return set_error(TFRA_ERR_HIP, "plan_reduce_to: hipSetDevice"); } }
+  if (on_device(pl->device) != hipSuccess) return set_error(TFRA_ERR_HIP, "plan_reduce_to: hipSetDevice");
   unsigned key_blocks, bin_blocks;
   plan_grids(pl, &key_blocks, &bin_blocks);
   launch_hot_sums(s, pl, grads, bin_blocks, nullptr, 0);
@@ -1036,7 +1036,7 @@ static int step_prefetch_impl(tfra_table_t* tp, const tfra_opt_params* p, tfra_s
   if (plan_next) {
     if (!plan_next->host_counts) {
       if (hipHostMalloc((void**)&plan_next->host_counts, 64, hipHostMallocDefault) != hipSuccess) { plan_next->host_counts = nullptr; return set_error(TFRA_ERR_OOM, "step_prefetch: hipHostMalloc"); }
-      for (int i = 0; i < 8; ++i) plan_next->host_counts[i] = 0;
+      for (unsigned i = 0; i < HC_SHIFT + PC_PUBLISHED; ++i) plan_next->host_counts[i] = 0;
     }
     if (plan_next->last_used_step) {  // the write-back that read plan_next's buffers must be over
       const unsigned need = plan_next->last_used_step + 1;

@@ -543,7 +543,7 @@ int tfra_assign_route_feed(tfra_assign_route_t* r, size_t n, const int64_t* d_id
   if (!r) return set_error(TFRA_ERR_INVALID, "assign_route_feed: null route");
   if (r->live >= MAX_LIVE) return set_error(TFRA_ERR_INVALID, "assign_route_feed: six batches are fed ahead already");
   if (n == 0 || n > r->max_n || !d_ids) return set_error(TFRA_ERR_INVALID, "assign_route_feed: 1 <= n <= max_batch ids expected");
-  { int cur = -1; if (hipGetDevice(&cur) != hipSuccess || cur != r->device) { if (hipSetDevice(r->device) != hipSuccess) return hip_fail("hipSetDevice"); } }
+  if (tfra::on_device(r->device) != hipSuccess) return hip_fail("hipSetDevice");
   ASlot& sl = r->slots[r->tail];
   sl.wait_src = !ids_ready;   // the ids are still being produced on the caller's stream
   if (sl.wait_src && hipEventRecord(sl.src_ev, (hipStream_t)stream) != hipSuccess) return hip_fail("event record");
@@ -561,7 +561,7 @@ int tfra_assign_route_step(tfra_assign_route_t* r, void* d_rows_out, const void*
   if (fed_ahead <= 0) return set_error(TFRA_ERR_INVALID, "assign_route_step: no batch fed (tfra_assign_route_flush writes the pending batch back)");
   if (!d_rows_out || !default_row) return set_error(TFRA_ERR_INVALID, "assign_route_step: null buffer");
   if (r->pending && !values_prev) return set_error(TFRA_ERR_INVALID, "assign_route_step: the previous step's batch has not been written back: values_prev is null");
-  { int cur = -1; if (hipGetDevice(&cur) != hipSuccess || cur != r->device) { if (hipSetDevice(r->device) != hipSuccess) return hip_fail("hipSetDevice"); } }
+  if (tfra::on_device(r->device) != hipSuccess) return hip_fail("hipSetDevice");
   hipStream_t s = (hipStream_t)stream;
   ASlot& cur = r->slots[r->look];
   int rc = ensure_routed(r, cur);
@@ -605,7 +605,7 @@ int tfra_assign_route_flush(tfra_assign_route_t* r, const void* values_prev, tfr
   if (!r) return set_error(TFRA_ERR_INVALID, "assign_route_flush: null route");
   if (!r->pending) return TFRA_OK;
   if (!values_prev) return set_error(TFRA_ERR_INVALID, "assign_route_flush: null values_prev");
-  { int cur = -1; if (hipGetDevice(&cur) != hipSuccess || cur != r->device) { if (hipSetDevice(r->device) != hipSuccess) return hip_fail("hipSetDevice"); } }
+  if (tfra::on_device(r->device) != hipSuccess) return hip_fail("hipSetDevice");
   hipStream_t s = (hipStream_t)stream;
   ASlot& pv = r->slots[r->head];
   int rc = send_values(r, pv, values_prev, s);

@@ -546,7 +546,7 @@ __device__ __forceinline__ void copy_bytes16_wt(unsigned char* dst, const unsign
 }
 
 // ---- find: the work of ONE wave (16 keys: 4 per 16-lane group), shared by find_kernel (tfra_table.hip) and the launch that runs
-// the lookup next to the de-duplication of the same ids (find_unique_kernel, tfra_csr.hip) -------------------------------------
+// the lookup next to the de-duplication of the same ids (find_unique_kernel, tfra_setplan.hip) -------------------------------------
 // PF1: also put the SECOND home bucket's line of every key in flight with the first (a bounded table running
 // near capacity: most b0 lines are full and flagged, ~1/3 of the resident keys and every miss need b1, and on
 // a loaded memory round trip is ~2 us — two in flight beat two in a row).

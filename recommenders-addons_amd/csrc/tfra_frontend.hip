@@ -768,7 +768,7 @@ int tfra_unique(tfra_workspace_t* ws, size_t n, const int64_t* ids, int64_t* uni
                 int64_t* d_num_unique, tfra_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
   if (!ws || !d_num_unique) return set_error(TFRA_ERR_INVALID, "unique: null argument");
-  { int cur_ = -1; if (hipGetDevice(&cur_) != hipSuccess || cur_ != ws->device) HIP_TRY(hipSetDevice(ws->device)); }
+  HIP_TRY_AS("hipSetDevice(ws->device)", on_device(ws->device));
   if (n == 0) { HIP_TRY(hipMemsetAsync(d_num_unique, 0, sizeof(int64_t), s)); return TFRA_OK; }
   if (!ids || !unique_out || !idx_out) return set_error(TFRA_ERR_INVALID, "unique: null buffer");
   if (n >= (1ULL << 30)) return set_error(TFRA_ERR_INVALID, "unique: more than 2^30 ids per call");
@@ -824,7 +824,7 @@ int tfra_segment_sum(tfra_workspace_t* ws, size_t n, int dim, const float* in, c
                      const int64_t* d_num_segments, size_t max_segments, float* out, tfra_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
   if (!ws || !d_num_segments || !out || dim <= 0) return set_error(TFRA_ERR_INVALID, "segment_sum: bad argument");
-  { int cur_ = -1; if (hipGetDevice(&cur_) != hipSuccess || cur_ != ws->device) HIP_TRY(hipSetDevice(ws->device)); }
+  HIP_TRY_AS("hipSetDevice(ws->device)", on_device(ws->device));
   if (max_segments == 0) return TFRA_OK;
   if (n == 0) { HIP_TRY(hipMemsetAsync(out, 0, max_segments * (size_t)dim * sizeof(float), s)); return TFRA_OK; }
   if (!in || !idx) return set_error(TFRA_ERR_INVALID, "segment_sum: null buffer");
@@ -860,7 +860,7 @@ int tfra_sparse_segment_combine(tfra_workspace_t* ws, size_t nnz, int dim, const
                                 tfra_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
   if (!ws || !out || dim <= 0 || combiner < 0 || combiner > 2) return set_error(TFRA_ERR_INVALID, "segment_combine: bad argument");
-  { int cur_ = -1; if (hipGetDevice(&cur_) != hipSuccess || cur_ != ws->device) HIP_TRY(hipSetDevice(ws->device)); }
+  HIP_TRY_AS("hipSetDevice(ws->device)", on_device(ws->device));
   if (n_rows == 0) return TFRA_OK;
   if (nnz && (!rows || !idx || !seg)) return set_error(TFRA_ERR_INVALID, "segment_combine: null buffer");
   if (nnz >= (1ULL << 31) || n_rows >= (1ULL << 30)) return set_error(TFRA_ERR_INVALID, "segment_combine: too large");
@@ -882,7 +882,7 @@ int tfra_sparse_segment_combine_backprop(tfra_workspace_t* ws, size_t nnz, int d
                                          tfra_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
   if (!ws || dim <= 0 || combiner < 0 || combiner > 2) return set_error(TFRA_ERR_INVALID, "segment_combine_backprop: bad argument");
-  { int cur_ = -1; if (hipGetDevice(&cur_) != hipSuccess || cur_ != ws->device) HIP_TRY(hipSetDevice(ws->device)); }
+  HIP_TRY_AS("hipSetDevice(ws->device)", on_device(ws->device));
   if (nnz == 0) return TFRA_OK;
   if (!grad_out || !seg || !entry_grads_out) return set_error(TFRA_ERR_INVALID, "segment_combine_backprop: null buffer");
   if (n_rows == 0) return set_error(TFRA_ERR_INVALID, "segment_combine_backprop: entries but no rows");
@@ -912,7 +912,7 @@ int tfra_sparse_segment_combine_backprop_weights(tfra_workspace_t* ws, size_t nn
                                                  size_t n_rows, float* dw_out, tfra_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
   if (!ws || dim <= 0 || combiner < 0 || combiner > 2) return set_error(TFRA_ERR_INVALID, "segment_combine_backprop_weights: bad argument");
-  { int cur_ = -1; if (hipGetDevice(&cur_) != hipSuccess || cur_ != ws->device) HIP_TRY(hipSetDevice(ws->device)); }
+  HIP_TRY_AS("hipSetDevice(ws->device)", on_device(ws->device));
   if (nnz == 0) return TFRA_OK;
   if (!rows || !idx || !seg || !dw_out || (n_rows && !grad_out)) return set_error(TFRA_ERR_INVALID, "segment_combine_backprop_weights: null buffer");
   if (nnz >= (1ULL << 31) || n_rows >= (1ULL << 30)) return set_error(TFRA_ERR_INVALID, "segment_combine_backprop_weights: too large");
@@ -938,7 +938,7 @@ int tfra_partition(tfra_workspace_t* ws, size_t n, const int64_t* d_n, const int
   hipStream_t s = (hipStream_t)stream;
   if (!ws || !d_counts || num_shards <= 0 || num_shards > 2048 || mode < 0 || mode > 2)
     return set_error(TFRA_ERR_INVALID, "partition: bad argument (1 <= num_shards <= 2048, mode in 0..2)");
-  { int cur_ = -1; if (hipGetDevice(&cur_) != hipSuccess || cur_ != ws->device) HIP_TRY(hipSetDevice(ws->device)); }
+  HIP_TRY_AS("hipSetDevice(ws->device)", on_device(ws->device));
   if (n == 0) { HIP_TRY(hipMemsetAsync(d_counts, 0, num_shards * sizeof(int64_t), s)); return TFRA_OK; }
   if (!keys || !keys_out || !perm_out) return set_error(TFRA_ERR_INVALID, "partition: null buffer");
   if (n >= (1ULL << 31)) return set_error(TFRA_ERR_INVALID, "partition: too many keys");
@@ -959,7 +959,7 @@ int tfra_partition_by_owner(tfra_workspace_t* ws, size_t n, const int32_t* owner
   hipStream_t s = (hipStream_t)stream;
   if (!ws || !d_counts || num_shards <= 0 || num_shards > 2048)
     return set_error(TFRA_ERR_INVALID, "partition_by_owner: bad argument (1 <= num_shards <= 2048)");
-  { int cur_ = -1; if (hipGetDevice(&cur_) != hipSuccess || cur_ != ws->device) HIP_TRY(hipSetDevice(ws->device)); }
+  HIP_TRY_AS("hipSetDevice(ws->device)", on_device(ws->device));
   if (n == 0) { HIP_TRY(hipMemsetAsync(d_counts, 0, num_shards * sizeof(int64_t), s)); return TFRA_OK; }
   if (!owner || !perm_out) return set_error(TFRA_ERR_INVALID, "partition_by_owner: null buffer");
   if (n >= (1ULL << 31)) return set_error(TFRA_ERR_INVALID, "partition_by_owner: too many keys");
@@ -980,7 +980,7 @@ int tfra_select_lowest(tfra_workspace_t* ws, size_t n, const int64_t* keys, cons
   hipStream_t s = (hipStream_t)stream;
   if (!ws || (status_dtype != TFRA_I32 && status_dtype != TFRA_I64) || k > n)
     return set_error(TFRA_ERR_INVALID, "select_lowest: bad argument (status int32/int64, k <= n)");
-  { int cur_ = -1; if (hipGetDevice(&cur_) != hipSuccess || cur_ != ws->device) HIP_TRY(hipSetDevice(ws->device)); }
+  HIP_TRY_AS("hipSetDevice(ws->device)", on_device(ws->device));
   if (k == 0) return TFRA_OK;
   if (!keys || !status || !keys_out) return set_error(TFRA_ERR_INVALID, "select_lowest: null buffer");
   if (n >= (1ULL << 31)) return set_error(TFRA_ERR_INVALID, "select_lowest: too many keys");

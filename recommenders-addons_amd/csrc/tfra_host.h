@@ -17,13 +17,24 @@ namespace tfra {
 extern thread_local std::string g_last_error;
 int set_error(int code, const std::string& msg);
 
-#define HIP_TRY(expr)                                                                         \
+// HIP_TRY_AS: the error text names `what` instead of the expression
+#define HIP_TRY_AS(what, expr)                                                                \
   do {                                                                                        \
     hipError_t _e = (expr);                                                                   \
     if (_e != hipSuccess)                                                                     \
       return set_error(_e == hipErrorOutOfMemory ? TFRA_ERR_OOM : TFRA_ERR_HIP,                \
-                       std::string(#expr) + ": " + hipGetErrorString(_e));                    \
+                       std::string(what) + ": " + hipGetErrorString(_e));                     \
   } while (0)
+#define HIP_TRY(expr) HIP_TRY_AS(#expr, expr)
+
+// Makes `device` the calling thread's device: hipSuccess, or why it could not.  hipSetDevice costs tens of microseconds on
+// ROCm 7.2 — more than the find kernel itself — so it is only issued when the calling thread is on another device.  (The
+// destroy paths' unconditional hipSetDevice is another thing: they cannot report a failure and do not care for the cost.)
+static inline hipError_t on_device(int device) {
+  int cur = -1;
+  if (hipGetDevice(&cur) == hipSuccess && cur == device) return hipSuccess;
+  return hipSetDevice(device);
+}
 
 // head of a C entry point of the table units (tfra_table / tfra_grow / tfra_upsert / tfra_scan .hip): handle `tp`, `stream`
 #define TABLE_ENTER()                                         \
@@ -209,7 +220,7 @@ struct tfra_workspace {
   void* buf = nullptr;
   size_t bytes = 0;
   void* plan = nullptr;   // tfra_sparse_plan of tfra_reduce_by_key
-  void* uplan = nullptr;  // tfra_sparse_plan of tfra_unique_unordered
+  void* uplan = nullptr;  // tfra_sparse_plan of tfra_unique_unordered and tfra_table_find_unique (tfra::workspace_uplan)
   unsigned* h_err = nullptr;   // pinned: polls of the one-launch unique that timed out (reported by the NEXT tfra_unique_unordered call)
   // tfra_unique (up to 2^20 ids): two persistent hash sets that alternate and empty each other (no fill kernel per call)
   void* unq_buf = nullptr;
@@ -233,3 +244,17 @@ struct tfra_workspace {
     return TFRA_OK;
   }
 };
+
+namespace tfra {
+// The workspace's plan object of tfra_unique_unordered / tfra_table_find_unique, created on first use
+static inline int workspace_uplan(tfra_workspace* ws, tfra_sparse_plan_t** out) {
+  if (!ws->uplan) {
+    tfra_sparse_plan_t* pl = nullptr;
+    int rc = tfra_sparse_plan_create(ws->device, &pl);
+    if (rc) return rc;
+    ws->uplan = pl;
+  }
+  *out = reinterpret_cast<tfra_sparse_plan_t*>(ws->uplan);
+  return TFRA_OK;
+}
+}  // namespace tfra

@@ -1,4 +1,4 @@
-// ASSIGN half of a write-back (tfra_table_upsert_planned, over a CSR or SET plan of tfra_csr.hip; tfra_table_upsert_sparse; a
+// ASSIGN half of a write-back (tfra_table_upsert_planned, over a CSR plan of tfra_csr.hip or a SET plan of tfra_setplan.hip; tfra_table_upsert_sparse; a
 // caller's unique keys, own_upsert_unique): one pass with bucket ownership (upsert_own_kernel, own_batch16 of tfra_own_device.h),
 // then the keys it leaves over with the locked protocol (upsert_rest_kernel).
 #include <hip/hip_runtime.h>
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void upsert_rest_kernel(const OwnArgs a, const
     f1 = reinterpret_cast<const uint4*>(it)[1];
   }
   unsigned total = 0;
-  if (!slow_ctr) total = SRC != SRC_DIRECT ? a.ks.d_counts[0] + a.ks.d_counts[1] : direct_count(a);
+  if (!slow_ctr) total = SRC != SRC_DIRECT ? a.ks.d_counts[PC_HOT] + a.ks.d_counts[PC_COLD] : direct_count(a);
   const unsigned counted = slow_ctr ? *slow_ctr : total;
   if ((SRC == SRC_SET || SRC == SRC_DIRECT) && !ACC && slow_ctr && a.stats_host && blockIdx.x == 0 && threadIdx.x == 0) {   // the pass's sample -> the host (launch_own)
     __hip_atomic_store(a.stats_host, slow_ctr[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);       // not plain hits
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void upsert_rest_kernel(const OwnArgs a, const
   if (zero4 && blockIdx.x == 0 && threadIdx.x < 4) zero4[threadIdx.x] = 0;   // last kernel of this use: arm the next use's counters
   if (counted == 0) return;
   const bool listed = slow_ctr && counted <= a.item_cap;
-  if (slow_ctr && !listed) total = SRC != SRC_DIRECT ? a.ks.d_counts[0] + a.ks.d_counts[1] : direct_count(a);
+  if (slow_ctr && !listed) total = SRC != SRC_DIRECT ? a.ks.d_counts[PC_HOT] + a.ks.d_counts[PC_COLD] : direct_count(a);
   const unsigned n = listed ? counted : total;
   const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
   const unsigned ngroups = (gridDim.x * blockDim.x) >> 4;
@@ -117,7 +117,7 @@ template <int G, bool SIMPLE, int SRC, int U = 4, bool ACC = false, bool HF = fa
 __global__ __launch_bounds__(256) void upsert_own_kernel(const OwnArgs a, OwnCtrs* ctr, unsigned own_gen, unsigned* progress,
                                                          unsigned progress_val) {
   const int lane = threadIdx.x & 63;
-  const unsigned total = SRC != SRC_DIRECT ? a.ks.d_counts[0] + a.ks.d_counts[1] : direct_count(a);
+  const unsigned total = SRC != SRC_DIRECT ? a.ks.d_counts[PC_HOT] + a.ks.d_counts[PC_COLD] : direct_count(a);
   const unsigned nwaves = (gridDim.x * blockDim.x) >> 6;
   const unsigned wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   int fresh = 0, not_hits = 0, looked = 0;
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void upsert_own_kernel(const OwnArgs a, OwnCtr
       __hip_atomic_store(progress, progress_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       __hip_atomic_store(progress + 1, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    if (SRC == SRC_PLAN && a.ks.d_counts[5]) atomicAdd(a.v.err_count, a.ks.d_counts[5]);
+    if (SRC == SRC_PLAN && a.ks.d_counts[PC_OVERFLOW]) atomicAdd(a.v.err_count, a.ks.d_counts[PC_OVERFLOW]);
   }
   const OwnFlags fl = own_setup<SIMPLE>(a);
   for (unsigned wbase = wave * (4 * U); wbase < total; wbase += nwaves * (4 * U)) {
@@ -257,8 +257,8 @@ int tfra::own_prepare(Table* t, const tfra_sparse_plan_t* pl, const void* values
   unsigned* tags = t->ensure_own_tags(s);    // nullptr (no owner tags): every key takes the locked protocol
   L->og = tags ? next_own_gen(t) : 0;
   const unsigned par = pl->ups_uses[pl->kind == 1 ? 1 : 0]++ & 1u;   // (its own count per buffer: apply_planned uses of the plan do not touch the counters)
-  L->ctr = reinterpret_cast<OwnCtrs*>(pl->d_counts + 12) + par;
-  L->next_ctr = reinterpret_cast<OwnCtrs*>(pl->d_counts + 12) + (par ^ 1u);
+  L->ctr = reinterpret_cast<OwnCtrs*>(pl->d_counts + PC_OWN_CTRS) + par;
+  L->next_ctr = reinterpret_cast<OwnCtrs*>(pl->d_counts + PC_OWN_CTRS) + (par ^ 1u);
   // Left-over keys of the ownership pass.  Few (a big table): the remainder kernel walks their list with a handful of
   // blocks.  Many (a small table): full grid.
   const double nkeys = (double)key_blocks * 16.0;   // unique keys of the plan when its counts have arrived, else the id count

@@ -164,6 +164,7 @@ struct OwnItem {          // 32 B, written as two 16-B stores
 // Counters of one use by the ownership write-back (two sets alternate, the last kernel of use k zeroes the set of
 // use k+1: nothing of use k-1 is still running by stream order).
 struct OwnCtrs { unsigned n_a, spare[3]; };
+static_assert(2 * sizeof(OwnCtrs) == PC_OWN_CTRS_WORDS * sizeof(unsigned), "the two sets are words [PC_OWN_CTRS, + PC_OWN_CTRS_WORDS) of a plan's d_counts block");
 
 // Where the keys of a launch come from:
 //   SRC_PLAN    the unique keys of a de-duplication plan (value row = the key's LAST occurrence in the batch)

@@ -1,8 +1,9 @@
 // The write-back plan object (tfra_sparse_plan_t) and the host helpers the units of the write-back share:
-//   tfra_csr.hip    the plans: CSR (gradients) and SET (assign-only) builders, the object's life, its route helpers
-//   tfra_apply.hip  the gradient half: hot sums + the fused optimizer update
-//   tfra_own.hip    the assign half: the ownership pass + its remainder
-//   tfra_step.hip   the overlapped step's driver (its kernel: tfra_step_impl.h)
+//   tfra_csr.hip      the CSR plan (gradients): its builders, the object's life, tfra_sparse_plan_read, the route helpers
+//   tfra_setplan.hip  the SET plan (assign-only): its builders, and the unique / find+unique ops built on it
+//   tfra_apply.hip    the gradient half: hot sums + the fused optimizer update
+//   tfra_own.hip      the assign half: the ownership pass + its remainder
+//   tfra_step.hip     the overlapped step's driver (its kernel: tfra_step_impl.h)
 // The object holds types of tfra_plan_device.h (anonymous namespace): every unit includes the same definitions, so it has one
 // layout.  A helper shared across units cannot take or return such a type (its linkage would be internal): the shared ones below
 // take the plan object, pointers and scalars; keys_of, which returns one, is defined here for each unit.
@@ -34,7 +35,7 @@ struct tfra_sparse_plan {
   unsigned* keymap = nullptr;
   i64* dkeys = nullptr;
   unsigned* binmap = nullptr;
-  unsigned* d_counts = nullptr;
+  unsigned* d_counts = nullptr;     // the control words of the last build (PC_*, tfra_plan_device.h): the CSR buffer's, or set_counts
   uint8_t* dflag = nullptr;
   size_t dflag_len = 0;
   OwnItem* slow_items = nullptr;   // [SLOW_CAP] left-over keys of the ownership pass of a write-back (self-contained items)
@@ -47,7 +48,7 @@ struct tfra_sparse_plan {
   float* partial = nullptr;
   int* prow_dest = nullptr;        // [partial rows] scratch of tfra_plan_positions_to
   bool armed = false;              // cursors/counters are zero (re-armed by the last kernel of the previous build)
-  unsigned* host_counts = nullptr; // pinned: [0] generation of the last COMPLETED build, [1..6] its counts
+  unsigned* host_counts = nullptr; // pinned copy of a CSR build's published words (HC_*, tfra_plan_device.h)
   unsigned gen = 0;                // generation of the last enqueued build
   bool ev_recorded = false;        // the last build ran on a side stream (tfra_table_step_prefetch)
   unsigned last_used_step = 0;     // last step whose write-back read this plan
@@ -59,8 +60,7 @@ struct tfra_sparse_plan {
   unsigned set_m2 = 0;
   SetTab set_tab[2]{};
   unsigned set_parity = 0;         // table of the last build
-  unsigned* set_counts = nullptr;  // the d_counts block of the set buffer: [8] any_deferred [12..19] OwnCtrs x2; [64 + 8 (2 p + use & 1) ..]
-                                   // the key counts of table p's uses ({0, distinct keys, 0, 0, 0, 0}: what CsrKeys::d_counts shows)
+  unsigned* set_counts = nullptr;  // the control words of the set buffer (PC_* and SC_*, tfra_plan_device.h)
   unsigned set_use[2] = {0, 0};    // uses of each table so far
   bool built_counts = true;        // the last build counted occurrences
   bool skip_counts_once = false;   // the NEXT build need not count occurrences (set by the table's own drivers for tables whose
@@ -80,12 +80,13 @@ struct tfra_sparse_plan {
   unsigned scat_use = 0;           // scatters into this object so far (its two overflow counters alternate)
   const int64_t* scat_ids = nullptr;   // the batch whose pairs the segments hold (nullptr: none)
   size_t scat_n = 0;
-  unsigned char tab_state[2] = {0, 0}; // TAB_EMPTY / TAB_LISTED / TAB_LISTLESS: what each table holds (setplan_prepare)
+  unsigned char tab_state[2] = {0, 0}; // what each table holds (TAB_*; the build rules: setplan_prepare, tfra_setplan.hip)
 };
+enum : unsigned char { TAB_EMPTY = 0, TAB_LISTED = 1, TAB_LISTLESS = 2 };
 
 namespace tfra {
 
-// ---- tfra_csr.hip
+// ---- tfra_setplan.hip
 // The SET plan of a batch (dim 0) on stream s; counts: also the occurrences of every id (see setplan_kernel)
 int setplan_build(tfra_sparse_plan* pl, size_t n, const int64_t* ids, hipStream_t s, bool counts);
 // A build without the dense list, made by the overlapped step's launch: the scatter buffers for n ids, then the bookkeeping of
@@ -94,6 +95,8 @@ int setplan_prepare_listless(tfra_sparse_plan* pl, size_t n, hipStream_t s);
 void setplan_take_listless(tfra_sparse_plan* pl, size_t n);
 // n SET entries (SetEnt) set free, with one small launch on stream s
 void setplan_fill_empty(void* ent, size_t n, hipStream_t s);
+
+// ---- tfra_csr.hip
 void plan_grids(const tfra_sparse_plan* pl, unsigned* key_blocks, unsigned* bin_blocks);
 int own_plan(Table* t, tfra_sparse_plan** out);
 
@@ -123,8 +126,10 @@ int upsert_planned_impl(tfra_table_t* tp, const tfra_sparse_plan_t* pl, const vo
 
 static inline CsrKeys keys_of(const tfra_sparse_plan* pl) {
   if (pl->kind == 1) {
+    // a SET use block is laid out as the head of a CSR d_counts block on purpose (tfra_plan_device.h): d_counts = the block of
+    // the table's current use, in which tb.count is word SC_USE_COUNT
     const SetTab& tb = pl->set_tab[pl->set_parity];
-    return CsrKeys{nullptr, nullptr, nullptr, nullptr, nullptr, tb.count - 1, tb.ukeys, tb.uslot, tb.ent};
+    return CsrKeys{nullptr, nullptr, nullptr, nullptr, nullptr, tb.count - SC_USE_COUNT, tb.ukeys, tb.uslot, tb.ent};
   }
   return CsrKeys{pl->keymap, pl->dkeys, pl->out.crec, pl->out.hrec, pl->out.hent, pl->d_counts, nullptr, nullptr, nullptr};
 }

@@ -1,6 +1,7 @@
-// Device side of the write-back plans (tfra_csr.hip builds them): the CSR plan's layout and records, the SET plan's table and
-// its probes.  Shared by the plan kernels, the gradient half (tfra_apply.hip), the ownership pass (tfra_own_device.h) and the
-// overlapped step (tfra_step_impl.h).
+// Device side of the write-back plans (tfra_csr.hip builds the CSR plan, tfra_setplan.hip the SET plan): the CSR plan's layout and
+// records, the SET plan's table and its probes, and the control words of a plan's count blocks (host and device).  Shared by the
+// plan kernels, the gradient half (tfra_apply.hip), the ownership pass (tfra_own_device.h) and the overlapped step
+// (tfra_step_impl.h).
 //
 // Everything here stays in the anonymous namespace, as it was when one file held all of it: kernels take these types by value,
 // and a kernel's mangled name (what rocprofv3 and scripts/summarize_profile.py see) carries its parameters' namespaces.
@@ -30,6 +31,51 @@ constexpr unsigned REC_WORDS = 16;        // a key record = 64 B: [0,1] key [2] 
                                           // positions, ascending; many: [3] first partial row [4] #partials [5] entry
                                           // address of its last occurrence
 constexpr unsigned KM_MANY = 1u << 31;    // keymap: the record lives in `hrec`
+
+// ---------------------------------------------------------------------------------------------
+// The plan's CONTROL WORDS: the one map of the 32-bit words a plan object's count blocks hold, for the host and for the kernels of
+// every unit (which are compiled separately: a word that moves here moves in all of them, and none may move by accident —
+// the static_asserts below and in tfra_own_device.h).
+//   d_counts block (PC_*; PC_WORDS words): the head of whichever buffer holds the object's last build — the CSR buffer's
+//     (plan_lay_out, tfra_csr.hip) or the SET buffer's (set_counts; setplan_prepare, tfra_setplan.hip).  The last CSR plan kernel
+//     publishes words [0, PC_PUBLISHED); the write-backs keep their own words behind them.
+//   SET buffer (SC_*; SC_WORDS words, of which the first PC_WORDS are its d_counts block): each of the two tables has two USE
+//     blocks that alternate from build to build.  A use block is laid out as the head of a d_counts block ON PURPOSE — {0, distinct
+//     keys, 0, 0, 0, 0}: PC_HOT = 0, PC_COLD = the count, no bins, no overflow — so that CsrKeys::d_counts may point at it (keys_of)
+//     and every consumer of a plan's keys reads "PC_HOT + PC_COLD keys" whatever the plan's kind.
+//   pinned copy (HC_*; host_counts): the generation of the last COMPLETED CSR build, then its published words.
+enum : unsigned {
+  PC_HOT = 0,             // keys with more than DIRECT occurrences (a SET use block: always 0 — the one-launch unique counts its blocks here)
+  PC_COLD = 1,            // the other keys (a SET use block: all distinct keys)
+  PC_BINS = 3,            // hot bins of the build
+  PC_OVERFLOW = 5,        // errors of the build, latched: its keys are incomplete
+  PC_PUBLISHED = 6,       // words the last CSR plan kernel publishes, device and pinned copy (words 2 and 4: unused, zero)
+  PC_ANY_DEFERRED = 8,    // = use_gen of the last write-back that deferred a key to its eviction phase
+  PC_OWN_CTRS = 12,       // the two OwnCtrs sets of the ownership write-back (tfra_own_device.h), PC_OWN_CTRS_WORDS in all
+  PC_OWN_CTRS_WORDS = 8,
+  PC_PART_COUNT = 32,     // i64 (two words): PC_HOT + PC_COLD as tfra_partition reads a count (tfra_plan_partition)
+  PC_WORDS = 64,
+  SC_USE_BASE = 64,       // first use block: table p, use u at SC_USE_BASE + SC_TAB_STRIDE p + SC_USE_STRIDE (u & 1)
+  SC_USE_STRIDE = 8,
+  SC_TAB_STRIDE = 16,     // a table's two use blocks: what filling a table zeroes
+  SC_USE_COUNT = PC_COLD, // the count inside a use block (SetTab::count points at it)
+  SC_ZERO = 120,          // a word that is always zero: the "list length" of a table that has no list
+  SC_WORDS = 128,
+  HC_GEN = 0,             // pinned copy: the generation word ...
+  HC_SHIFT = 1,           // ... and published word k at HC_SHIFT + k
+};
+static_assert(PC_HOT == 0 && PC_COLD == 1 && PC_BINS == 3 && PC_OVERFLOW == 5 && PC_PUBLISHED == 6 && PC_ANY_DEFERRED == 8 &&
+              PC_OWN_CTRS == 12 && PC_PART_COUNT == 32 && SC_USE_BASE == 64 && SC_USE_STRIDE == 8 && SC_TAB_STRIDE == 16 &&
+              SC_USE_COUNT == 1 && SC_ZERO == 120 && HC_GEN == 0 && HC_SHIFT == 1,
+              "kernels of other units read these words: the layout does not move");
+static_assert(PC_PUBLISHED <= PC_ANY_DEFERRED && PC_ANY_DEFERRED < PC_OWN_CTRS && PC_OWN_CTRS + PC_OWN_CTRS_WORDS <= PC_PART_COUNT &&
+              PC_PART_COUNT % 2 == 0 && PC_PART_COUNT + 2 <= PC_WORDS, "the d_counts block's words do not overlap");
+static_assert(SC_USE_BASE >= PC_WORDS && SC_TAB_STRIDE == 2 * SC_USE_STRIDE && PC_PUBLISHED <= SC_USE_STRIDE &&
+              SC_USE_BASE + 2 * SC_TAB_STRIDE <= SC_ZERO && SC_ZERO < SC_WORDS, "the SET buffer's use blocks end before the always-zero word");
+// the count word of use `use` of table `table` of a SET buffer whose control words start at `base`
+__host__ inline unsigned* set_count_word(unsigned* base, unsigned table, unsigned use) {
+  return base + SC_USE_BASE + SC_TAB_STRIDE * table + SC_USE_STRIDE * (use & 1u) + SC_USE_COUNT;
+}
 
 // global descriptor store: bucket b owns [b*CMAX, b*CMAX + cm); overflow list behind it
 struct CsrDesc {

@@ -539,7 +539,7 @@ int tfra_route_feed(tfra_route_t* r, size_t n, const int64_t* d_ids, int ids_rea
   if (!r) return set_error(TFRA_ERR_INVALID, "route_feed: null route");
   if (r->fed >= NSLOTS - 1) return set_error(TFRA_ERR_INVALID, "route_feed: four batches are fed ahead already");
   if (n == 0 || n > r->max_n || !d_ids) return set_error(TFRA_ERR_INVALID, "route_feed: 1 <= n <= max_batch ids expected");
-  { int cur = -1; if (hipGetDevice(&cur) != hipSuccess || cur != r->device) { if (hipSetDevice(r->device) != hipSuccess) return hip_fail("hipSetDevice"); } }
+  if (tfra::on_device(r->device) != hipSuccess) return hip_fail("hipSetDevice");
   Slot& sl = r->slots[r->tail];
   sl.wait_src = !ids_ready;   // the ids are still being produced on the caller's stream
   if (sl.wait_src && hipEventRecord(sl.src_ev, (hipStream_t)stream) != hipSuccess) return hip_fail("event record");

@@ -1,5 +1,5 @@
 // The overlapped step's driver (tfra_step_driver_t, tfra_table_step[s]_overlap): one launch per step of the kernel in
-// tfra_step_impl.h, fed from the plan objects of tfra_csr.hip and the ownership pass's host half (tfra_own.hip).
+// tfra_step_impl.h, fed from the plan objects of tfra_csr.hip / tfra_setplan.hip and the ownership pass's host half (tfra_own.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -68,7 +68,7 @@ struct tfra_step_driver {
 extern "C" int tfra_step_driver_create(tfra_table_t* tp, tfra_step_driver_t** out) {
   Table* t = reinterpret_cast<Table*>(tp);
   if (!t || !out) return set_error(TFRA_ERR_INVALID, "step_driver_create: null argument");
-  { int cur_ = -1; if (hipGetDevice(&cur_) != hipSuccess || cur_ != t->device) { if (hipSetDevice(t->device) != hipSuccess) return set_error(TFRA_ERR_HIP, "step_driver_create: hipSetDevice"); } }
+  if (on_device(t->device) != hipSuccess) return set_error(TFRA_ERR_HIP, "step_driver_create: hipSetDevice");
   tfra_step_driver* d = new tfra_step_driver();
   d->t = t; d->tp = tp;
   for (unsigned i = 0; i < tfra_step_driver::NPL; ++i) {

@@ -163,12 +163,7 @@ TableView Table::view_of(const Storage& st) const {
 // serialise against work queued on another stream (the reference blocks on a per-table mutex and
 // a stream sync per op, R/kernels/hkv_hashtable_op_gpu.cu.cc:192-213; here: event chaining).
 int Table::enter(hipStream_t s) {
-  // hipSetDevice costs tens of microseconds on ROCm 7.2 — more than the find kernel itself — so
-  // it is only issued when the calling thread is on another device.
-  int cur = -1;
-  if (hipGetDevice(&cur) != hipSuccess || cur != device) {
-    if (hipSetDevice(device) != hipSuccess) return set_error(TFRA_ERR_HIP, "hipSetDevice failed");
-  }
+  if (on_device(device) != hipSuccess) return set_error(TFRA_ERR_HIP, "hipSetDevice failed");
   if (has_last && s != last_stream && !capture_safe) {
     HIP_TRY(hipEventRecord(chain_event, last_stream));
     HIP_TRY(hipStreamWaitEvent(s, chain_event, 0));

@@ -1,11 +1,14 @@
-"""GPU: the CSR-by-key write-back plan (csrc/tfra_csr.hip) and the kernels that consume it.
+"""GPU: the write-back plans — the CSR-by-key plan (csrc/tfra_csr.hip) and the assign-only SET plan with the unique ops built on it
+(csrc/tfra_setplan.hip) — and the kernels that consume them.
 
   * the plan itself (tfra_sparse_plan_read) against numpy: unique keys, counts, positions ascending per key;
   * tfra_table_apply_sparse at BASELINE's benchmark shape (B = 131 072 Zipf-1.2 over >= 10 M keys, 3 steps) against
     the reference's write-back sequence with SEQUENTIAL fp32 duplicate sums (what the CPU path does,
     PY/dynamic_embedding_optimizer.py:177-190): embedding values within 1e-6 (north_star tolerance);
   * tfra_table_upsert_sparse (repeats: the last occurrence wins) against the oracle table, bit-exact, every dtype,
-    unbounded and bounded-at-capacity tables.
+    unbounded and bounded-at-capacity tables;
+  * the SET plan (dim 0) against numpy: distinct keys, occurrence counts, the last position through upsert_planned; one plan
+    object rebuilt as SET and CSR in any order; tfra_unique_unordered and tfra_table_find_unique against numpy.unique.
 """
 import numpy as np
 import pytest
@@ -508,6 +511,62 @@ def test_one_plan_object_alternating_csr_and_set_builds(env):
     got = t.lookup(torch.from_numpy(uk).cuda())
     want = torch.tensor([expect[int(k)] for k in uk], device="cuda")[:, None].repeat(1, dim)
     assert torch.equal(got, want), "step %d (plan dim %d)" % (step, pdim)
+  t._table.check_errors()
+
+
+def test_set_csr_set_builds_then_upsert_on_one_plan_object(env):
+  """One plan object: regular SET build, CSR build (dim 4), regular SET build, then upsert_planned from it on a small LFU table
+  without caller scores.  The path on which the plan's control words meet: the count word of each of the SET buffer's two tables
+  (the second build walks the first table's list through that table's count word), the SET use block read as a CSR d_counts block
+  (tfra_sparse_plan_read and the write-back see the keys through keys_of), the CSR buffer's own block in between, the SET buffer's
+  OwnCtrs set selected by that buffer's use count, and the occurrence counts as the LFU scores.  n = 1500: two 1024-id blocks, the
+  smallest shape with a second block; both sentinel key values, and one key with more than 8 occurrences."""
+  torch, de, SparsePlan = env
+  dim, n = 4, 1500
+  t = de.HkvHashTable(torch.int64, torch.float32, torch.zeros(dim), init_capacity=8192, max_capacity=8192, device="cuda:0", dim=dim,
+                      evict_strategy=de.HkvEvictStrategy.LFU, name="set_csr_set")
+  plan = SparsePlan("cuda:0", 0)
+  rng = np.random.default_rng(23)
+  imin = np.iinfo(np.int64).min
+
+  def batch():
+    keys = rng.integers(1, 700, size=n).astype(np.int64) * 104729 - 3
+    keys[rng.integers(0, n, size=5)] = imin          # EMPTY_KEY as an ordinary key
+    keys[rng.integers(0, n, size=3)] = imin + 1      # LOCKED_KEY as an ordinary key
+    keys[rng.integers(0, n, size=40)] = 42           # a key with more than 8 occurrences
+    return keys
+
+  def build_and_check_set(keys):
+    plan._dim = 0
+    plan.build(torch.from_numpy(keys).cuda())
+    counts, pk, pc, ppos = plan.read()
+    uk, uc = np.unique(keys, return_counts=True)
+    assert uc[uk == 42][0] > 8 and imin in uk and imin + 1 in uk
+    assert counts["many"] == 0 and counts["few"] == uk.size and counts["errors"] == 0 and ppos is None
+    o = np.argsort(pk)
+    np.testing.assert_array_equal(pk[o], uk)
+    np.testing.assert_array_equal(pc[o], uc)
+    return uk, uc
+
+  build_and_check_set(batch())
+  plan._dim = dim               # (the C entry point takes the dim per build: the same object, the other buffer)
+  plan.build(torch.from_numpy(batch()).cuda())
+  keys = batch()
+  uk, uc = build_and_check_set(keys)
+  vals = torch.arange(n, device="cuda", dtype=torch.float32)[:, None].repeat(1, dim)   # row i = [i] * dim
+  t._table.upsert_planned(plan, vals)
+  last = {}
+  for i, k in enumerate(keys.tolist()):
+    last[k] = i
+  got = t.lookup(torch.from_numpy(uk).cuda())
+  want = torch.tensor([float(last[int(k)]) for k in uk], device="cuda")[:, None].repeat(1, dim)
+  assert torch.equal(got, want)
+  assert int(t.size().item()) == uk.size
+  ek, es = t.export_keys_and_scores(1 << 14)
+  ek, es = ek.cpu().numpy(), es.cpu().numpy()
+  np.testing.assert_array_equal(np.sort(ek), uk)
+  scored = uk > imin + 1   # (the two sentinel key values live in side rows, which keep no score)
+  np.testing.assert_array_equal(es[np.argsort(ek)][scored], uc[scored].astype(es.dtype))   # an LFU score = the occurrences the plan counted
   t._table.check_errors()
 
 

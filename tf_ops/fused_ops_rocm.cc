@@ -334,7 +334,7 @@ class EmbeddingLookupOp : public OpKernel {
     OP_REQUIRES_OK(ctx, t->Workspace(&ws));
     OP_REQUIRES(ctx, dflt.NumElements() == dim, errors::InvalidArgument("EmbeddingLookup: default_value must be one row [dim]"));
     // (no early return for an empty batch: the call zeroes num_unique, a device scalar a downstream InsertN reads)
-    // ONE launch: the lookup's blocks behind the de-duplication's (find_unique_kernel, csrc/tfra_csr.hip)
+    // ONE launch: the lookup's blocks behind the de-duplication's (find_unique_kernel, csrc/tfra_setplan.hip)
     OP_REQUIRES_OK(ctx, ToStatus(tfra_table_find_unique(t->raw(), ws, static_cast<size_t>(n), In<int64_t>(ids), Out<char>(values), nullptr,
                                                         dflt.tensor_data().data(), 0, Out<int64_t>(unique_ids), Out<int32_t>(idx),
                                                         Out<int64_t>(num), st)));
