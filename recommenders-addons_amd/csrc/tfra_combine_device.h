@@ -6,7 +6,7 @@
 // A row whose weight sum is 0 gives g_e = 0, the forward's convention (seg_combine_kernel, tfra_frontend.hip).
 //
 // Every kernel that forms g_e — tfra_sparse_segment_combine_backprop (written out) and the combined write-back of
-// tfra_table_apply_planned_combined (formed in registers from grad_out, tfra_apply.hip) — reads the same per-entry record and
+// tfra_table_apply_planned_combined (formed in registers from grad_out, tfra_apply_device.h) — reads the same per-entry record and
 // calls comb_grad4, so the two routes agree bit for bit.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -20,7 +20,7 @@
 //                            occurrences of a key fill one bin, the remainder (< 512, padded to 16) shares a bin
 //                            with other remainders, never straddling — and (key, first partial, #partials).
 //     csr_finish_kernel  publishes the counts, re-arms the cursors for the next build.
-//   GRADIENT HALF (tfra_table_apply_planned; tfra_apply.hip)
+//   GRADIENT HALF (tfra_table_apply_planned; tfra_apply.hip, the bodies in tfra_apply_device.h)
 //     hot_sums_kernel    one block per bin: 32 groups x 16 rows in flight, ordered add -> one partial row per run
 //     apply_csr_kernel   one 16-lane group per unique key (hot keys first): gathers its <= 8 gradient rows or
 //                        its partial rows IN ORDER, sums, locates/claims the table row, applies the optimizer.

@@ -11,6 +11,7 @@
 
 #include "../../include/tfra_mi355x.h"
 #include "tfra_device.h"
+#include "tfra_optim_device.h"
 
 namespace tfra {
 
@@ -147,6 +148,41 @@ struct Table {
   }
 };
 
+// The kernels' forms of a caller's optimizer parameters and of the table's score state.  at_capacity: whether Table::bounded_flags
+// handed out flag bytes (a bounded table that cannot grow any more: the write-back runs its eviction phase); 2 = such a table is
+// also dense (locate_or_claim_from).
+static inline OptP opt_of(const tfra_opt_params* p) {
+  return OptP{p->kind, p->lr, p->beta1, p->beta2, p->eps, p->l1, p->l2, p->lr_power, p->d_lr};
+}
+static inline int bounded_mode(const Table* t, bool at_capacity) { return at_capacity ? (t->dense ? 2 : 1) : 0; }
+static inline ScoreP score_of(const Table* t, const uint8_t* flags) {
+  return ScoreP{t->opts.strategy, t->global_epoch, bounded_mode(t, flags != nullptr)};
+}
+
+// Scratch of ONE call: the device and pinned allocations made through it live until the holder goes out of scope.  Its destructor
+// synchronises the call's stream once — a copy or a kernel queued there may still use the memory — and frees them, on every way
+// out of the function.  false: the allocation failed (the pointer is null, the caller reports it in its own words).
+struct Scratch {
+  hipStream_t s;
+  std::vector<std::pair<void*, bool>> held;   // (pointer, pinned)
+  explicit Scratch(hipStream_t stream) : s(stream) {}
+  Scratch(const Scratch&) = delete;
+  Scratch& operator=(const Scratch&) = delete;
+  template <class T>
+  bool take(T** p, size_t bytes, bool pinned) {
+    *p = nullptr;
+    if ((pinned ? hipHostMalloc((void**)p, bytes, hipHostMallocDefault) : hipMalloc((void**)p, bytes)) != hipSuccess) { *p = nullptr; return false; }
+    held.emplace_back(*p, pinned);
+    return true;
+  }
+  template <class T> bool device(T** p, size_t bytes) { return take(p, bytes, false); }
+  template <class T> bool pinned(T** p, size_t bytes) { return take(p, bytes, true); }
+  ~Scratch() {
+    if (!held.empty()) (void)hipStreamSynchronize(s);
+    for (auto& h : held) (void)(h.second ? hipHostFree(h.first) : hipFree(h.first));
+  }
+};
+
 // Argument check shared by the score-filtered calls (tfra_scan.hip): TFRA_ERR_INVALID for a null table or an unknown predicate,
 // TFRA_ERR_UNSUPPORTED for a table without a score line; the message names `fn`.  Enqueues nothing.
 int score_filter_check(const Table* t, int pred, const char* fn);
@@ -246,15 +282,28 @@ struct tfra_workspace {
 };
 
 namespace tfra {
-// The workspace's plan object of tfra_unique_unordered / tfra_table_find_unique, created on first use
-static inline int workspace_uplan(tfra_workspace* ws, tfra_sparse_plan_t** out) {
-  if (!ws->uplan) {
-    tfra_sparse_plan_t* pl = nullptr;
-    int rc = tfra_sparse_plan_create(ws->device, &pl);
+// The helper object an owner (a table, a workspace) keeps in a void* slot, created on `device` on first use: a workspace, a plan.
+// A create call that fails has recorded its own error; the slot stays null.
+static inline int workspace_in(void** slot, int device, tfra_workspace_t** out) {
+  if (!*slot) {
+    tfra_workspace_t* w = nullptr;
+    int rc = tfra_workspace_create(device, &w);
     if (rc) return rc;
-    ws->uplan = pl;
+    *slot = w;
   }
-  *out = reinterpret_cast<tfra_sparse_plan_t*>(ws->uplan);
+  *out = reinterpret_cast<tfra_workspace_t*>(*slot);
   return TFRA_OK;
 }
+static inline int plan_in(void** slot, int device, tfra_sparse_plan_t** out) {
+  if (!*slot) {
+    tfra_sparse_plan_t* pl = nullptr;
+    int rc = tfra_sparse_plan_create(device, &pl);
+    if (rc) return rc;
+    *slot = pl;
+  }
+  *out = reinterpret_cast<tfra_sparse_plan_t*>(*slot);
+  return TFRA_OK;
+}
+// The workspace's plan object of tfra_unique_unordered / tfra_table_find_unique
+static inline int workspace_uplan(tfra_workspace* ws, tfra_sparse_plan_t** out) { return plan_in(&ws->uplan, ws->device, out); }
 }  // namespace tfra

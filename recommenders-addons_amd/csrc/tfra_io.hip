@@ -55,55 +55,46 @@ static int save_impl(tfra_table_t* tp, int field, const char* prefix, size_t buf
   vf.f = fopen(vt.c_str(), append ? "ab" : "wb");
   if (!kf.f || !vf.f) return set_error(TFRA_ERR_IO, "save: cannot open " + kt + " / " + vt);
   size_t chunk = std::min(buffer_keys, cap);
-  i64 *d_keys = nullptr, *h_keys = nullptr;
-  unsigned char *d_vals = nullptr, *h_vals = nullptr;
-  size_t *d_cnt = nullptr, *h_cnt = nullptr;
-  auto cleanup = [&]() {
-    (void)hipFree(d_keys); (void)hipFree(d_vals); (void)hipFree(d_cnt);
-    (void)hipHostFree(h_keys); (void)hipHostFree(h_vals); (void)hipHostFree(h_cnt);
-  };
-  if (hipMalloc((void**)&d_keys, chunk * sizeof(i64)) != hipSuccess || hipMalloc((void**)&d_vals, chunk * fb) != hipSuccess ||
-      hipMalloc((void**)&d_cnt, sizeof(size_t)) != hipSuccess || hipHostMalloc((void**)&h_keys, chunk * sizeof(i64)) != hipSuccess ||
-      hipHostMalloc((void**)&h_vals, chunk * fb) != hipSuccess || hipHostMalloc((void**)&h_cnt, sizeof(size_t)) != hipSuccess) {
-    cleanup();
+  i64 *d_keys, *h_keys;
+  unsigned char *d_vals, *h_vals;
+  size_t *d_cnt, *h_cnt;
+  Scratch scratch(s);   // (freed behind a synchronisation of s, on every way out: an export or a copy may still be queued)
+  if (!scratch.device(&d_keys, chunk * sizeof(i64)) || !scratch.device(&d_vals, chunk * fb) || !scratch.device(&d_cnt, sizeof(size_t)) ||
+      !scratch.pinned(&h_keys, chunk * sizeof(i64)) || !scratch.pinned(&h_vals, chunk * fb) || !scratch.pinned(&h_cnt, sizeof(size_t)))
     return set_error(TFRA_ERR_OOM, "save: staging allocation failed");
-  }
   size_t total = 0;
   for (size_t off = 0; off < cap; off += chunk) {
     size_t len = std::min(chunk, cap - off);
-    if (hipMemsetAsync(d_cnt, 0, sizeof(size_t), s) != hipSuccess) { cleanup(); return set_error(TFRA_ERR_HIP, "save: memset"); }
+    if (hipMemsetAsync(d_cnt, 0, sizeof(size_t), s) != hipSuccess) return set_error(TFRA_ERR_HIP, "save: memset");
     rc = filter ? tfra_table_export_batch_if(tp, filter->pred, filter->threshold, len, off, d_cnt, chunk, (int64_t*)d_keys,
                                              field == 0 ? d_vals : nullptr, nullptr, stream)
                 : tfra_table_export_batch(tp, len, off, d_cnt, (int64_t*)d_keys, field == 0 ? d_vals : nullptr, nullptr, stream);
-    if (rc) { cleanup(); return rc; }
+    if (rc) return rc;
     (void)hipMemcpyAsync(h_cnt, d_cnt, sizeof(size_t), hipMemcpyDeviceToHost, s);
-    if (hipStreamSynchronize(s) != hipSuccess) { cleanup(); return set_error(TFRA_ERR_HIP, "save: sync"); }
+    if (hipStreamSynchronize(s) != hipSuccess) return set_error(TFRA_ERR_HIP, "save: sync");
     size_t got = *h_cnt;
-    if (filter && got > chunk) { cleanup(); return set_error(TFRA_ERR_HIP, "save_if: a window held more matches than slots"); }
+    if (filter && got > chunk) return set_error(TFRA_ERR_HIP, "save_if: a window held more matches than slots");
     if (!got) continue;
     if (field > 0) {   // a co-located state vector (optimizer slot): read it for the exported keys, same order
       // every exported key is resident, so the default row is never used: any valid row-sized buffer will do
       rc = tfra_table_find_field(tp, field, got, (const int64_t*)d_keys, d_vals, nullptr, d_vals, 1, stream);
-      if (rc) { cleanup(); return rc; }
+      if (rc) return rc;
     }
     (void)hipMemcpyAsync(h_keys, d_keys, got * sizeof(i64), hipMemcpyDeviceToHost, s);
     (void)hipMemcpyAsync(h_vals, d_vals, got * fb, hipMemcpyDeviceToHost, s);
-    if (hipStreamSynchronize(s) != hipSuccess) { cleanup(); return set_error(TFRA_ERR_HIP, "save: copy"); }
+    if (hipStreamSynchronize(s) != hipSuccess) return set_error(TFRA_ERR_HIP, "save: copy");
     if (t->key_file_bytes == 4) {   // int32 keys on disk: narrowed in place (the staging buffer is ours)
       int* k32 = reinterpret_cast<int*>(h_keys);
       for (size_t i = 0; i < got; ++i) {
         const i64 k = h_keys[i];
-        if ((i64)(int)k != k) { cleanup(); return set_error(TFRA_ERR_INVALID, "save: a key does not fit the table's 4-byte key files"); }
+        if ((i64)(int)k != k) return set_error(TFRA_ERR_INVALID, "save: a key does not fit the table's 4-byte key files");
         k32[i] = (int)k;
       }
     }
-    if (fwrite(h_keys, (size_t)t->key_file_bytes, got, kf.f) != got || fwrite(h_vals, fb, got, vf.f) != got) {
-      cleanup();
+    if (fwrite(h_keys, (size_t)t->key_file_bytes, got, kf.f) != got || fwrite(h_vals, fb, got, vf.f) != got)
       return set_error(TFRA_ERR_IO, "save: short write");
-    }
     total += got;
   }
-  cleanup();
   fclose(kf.f); kf.f = nullptr;
   fclose(vf.f); vf.f = nullptr;
   if (!append && (rename(kt.c_str(), kp.c_str()) != 0 || rename(vt.c_str(), vp.c_str()) != 0))
@@ -157,23 +148,17 @@ static int load_impl(tfra_table_t* tp, int field, const char* prefix, size_t buf
   if (key_bytes % kb || nkeys * fb != val_bytes)
     return set_error(TFRA_ERR_IO, "load: " + kp + " and " + vp + " sizes do not match dim");
   size_t chunk = std::max<size_t>(1, std::min(buffer_keys, nkeys));
-  i64 *d_keys = nullptr, *h_keys = nullptr;
-  unsigned char *d_vals = nullptr, *h_vals = nullptr;
-  auto cleanup = [&]() {
-    (void)hipFree(d_keys); (void)hipFree(d_vals); (void)hipHostFree(h_keys); (void)hipHostFree(h_vals);
-  };
-  if (hipMalloc((void**)&d_keys, chunk * sizeof(i64)) != hipSuccess || hipMalloc((void**)&d_vals, chunk * fb) != hipSuccess ||
-      hipHostMalloc((void**)&h_keys, chunk * sizeof(i64)) != hipSuccess || hipHostMalloc((void**)&h_vals, chunk * fb) != hipSuccess) {
-    cleanup();
+  i64 *d_keys, *h_keys;
+  unsigned char *d_vals, *h_vals;
+  Scratch scratch(s);   // (freed behind a synchronisation of s, on every way out: the copies out of the pinned buffers may still be queued)
+  if (!scratch.device(&d_keys, chunk * sizeof(i64)) || !scratch.device(&d_vals, chunk * fb) || !scratch.pinned(&h_keys, chunk * sizeof(i64)) ||
+      !scratch.pinned(&h_vals, chunk * fb))
     return set_error(TFRA_ERR_OOM, "load: staging allocation failed");
-  }
   size_t done = 0;
   while (done < nkeys) {
     size_t len = std::min(chunk, nkeys - done);
-    if (fread(h_keys, kb, len, kf.f) != len || fread(h_vals, fb, len, vf.f) != len) {
-      cleanup();
+    if (fread(h_keys, kb, len, kf.f) != len || fread(h_vals, fb, len, vf.f) != len)
       return set_error(TFRA_ERR_IO, "load: short read");
-    }
     if (kb == 4) {   // int32 keys on disk: widened in place, back to front
       const int* k32 = reinterpret_cast<const int*>(h_keys);
       for (size_t i = len; i-- > 0;) h_keys[i] = (i64)k32[i];
@@ -186,11 +171,10 @@ static int load_impl(tfra_table_t* tp, int field, const char* prefix, size_t buf
     const uint32_t flags = (t->opts.strategy >= 0 && t->opts.max_capacity) ? TFRA_FLAG_UNIQUE_KEYS : 0u;
     int rc = field == 0 ? tfra_table_insert_or_assign(tp, len, (const int64_t*)d_keys, d_vals, nullptr, flags, stream)
                         : tfra_table_insert_field(tp, field, len, (const int64_t*)d_keys, d_vals, flags, stream);
-    if (rc) { cleanup(); return rc; }
-    if (hipStreamSynchronize(s) != hipSuccess) { cleanup(); return set_error(TFRA_ERR_HIP, "load: sync"); }
+    if (rc) return rc;
+    if (hipStreamSynchronize(s) != hipSuccess) return set_error(TFRA_ERR_HIP, "load: sync");
     done += len;
   }
-  cleanup();
   if (n_loaded) *n_loaded = done;
   return TFRA_OK;
 }

@@ -1,5 +1,5 @@
-// What the grouped calls share (tfra_multi_find_combine: tfra_pool.hip; tfra_multi_apply_planned_combined: tfra_apply.hip, with its
-// entry-record kernels in tfra_frontend.hip; tfra_multi_sparse_plan_build: tfra_csr.hip).
+// What the grouped calls share (tfra_multi_find_combine: tfra_pool.hip; tfra_multi_apply_planned_combined: tfra_apply_many.hip, with
+// its entry-record kernels in tfra_frontend.hip; tfra_multi_sparse_plan_build: tfra_csr.hip).
 // Device side: the search that takes a block to its descriptor and the records of the launches that run in more than one unit.
 // Host side, the frame of a grouped call: the outcome of an operation's argument checks (Check: each operation's checks are ONE
 // function, which its single-table call and its grouped call both run), the tables' locks (lock_and_enter), the layout of the

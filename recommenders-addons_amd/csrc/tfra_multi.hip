@@ -1,5 +1,5 @@
 // Many tables per GPU (BASELINE configs[4]: 26 embedding tables of a DLRM-style model): one C call issues the training
-// step of every table — tfra_table_step_prefetch / _assign each — from a small pool of host threads, one group of tables
+// step of every table — tfra_table_step_prefetch / _assign (tfra_prefetch.hip) each — from a small pool of host threads, one group of tables
 // per thread, each table on its own pair of streams.  A step of one table is 6-8 kernel launches (~5 us of host time
 // each on ROCm 7.2): issued one table after the other from one thread, 26 tables are host-bound (1.9 ms per step measured
 // in round 1, the GPU idle most of the time); issued from W threads onto disjoint streams the launches overlap and so do

@@ -215,7 +215,7 @@ extern "C" int tfra_table_apply_optimizer(tfra_table_t* tp, const tfra_opt_param
   rc = t->prepare_insert(n, s);
   if (rc) return rc;
   TableView v = t->view_of(t->cur);
-  OptP o{p->kind, p->lr, p->beta1, p->beta2, p->eps, p->l1, p->l2, p->lr_power, p->d_lr};
+  const OptP o = opt_of(p);
   int dim = t->opts.dim;
   bool vec4 = dim % 4 == 0 && (((uintptr_t)grads | (uintptr_t)param_defaults) % 16 == 0);
   dim3 grid((unsigned)((n * 16 + 255) / 256));
@@ -225,7 +225,7 @@ extern "C" int tfra_table_apply_optimizer(tfra_table_t* tp, const tfra_opt_param
   uint8_t* deferred;
   rc = t->bounded_flags(n, s, &deferred);
   if (rc) return rc;
-  const ScoreP sp{t->opts.strategy, t->global_epoch, deferred ? (t->dense ? 2 : 1) : 0};
+  const ScoreP sp = score_of(t, deferred);
   switch (p->kind) {
     case TFRA_OPT_SGD: launch_apply<TFRA_OPT_SGD>(dt, vec4, grid, s, v, o, n, k, grads, d, default_is_full, dim, a0, a1, (const i64*)d_n, sp, deferred); break;
     case TFRA_OPT_ADAM: launch_apply<TFRA_OPT_ADAM>(dt, vec4, grid, s, v, o, n, k, grads, d, default_is_full, dim, a0, a1, (const i64*)d_n, sp, deferred); break;

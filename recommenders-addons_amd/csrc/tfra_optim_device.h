@@ -1,5 +1,5 @@
 // Optimizer update rules shared by the fused write-back kernels (tfra_optim.hip,
-// tfra_apply.hip).  TF's ResourceApply{GradientDescent,Adam,Adagrad[V2],Ftrl}, fp32, same
+// tfra_apply_device.h), and the kernels' parameter records OptP / ScoreP (formed on the host by opt_of / score_of, tfra_host.h).  TF's ResourceApply{GradientDescent,Adam,Adagrad[V2],Ftrl}, fp32, same
 // operation order as oracle/optimizers.py; compile with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -251,7 +251,7 @@ int tfra::own_prepare(Table* t, const tfra_sparse_plan_t* pl, const void* values
   uint8_t* bounded_now;
   rc = t->bounded_flags(1, s, &bounded_now);
   if (rc) return rc;
-  const ScoreP sp{t->opts.strategy, t->global_epoch, bounded_now ? (t->dense ? 2 : 1) : 0};
+  const ScoreP sp = score_of(t, bounded_now);
   const int g = granule_of(t->field_bytes, values, nullptr);
   ++pl->use_gen;
   unsigned* tags = t->ensure_own_tags(s);    // nullptr (no owner tags): every key takes the locked protocol
@@ -330,7 +330,7 @@ int own_upsert_unique(Table* t, hipStream_t s, size_t n, const i64* keys, const 
   uint8_t* bounded_now;
   int rc = t->bounded_flags(1, s, &bounded_now);
   if (rc) return rc;
-  const ScoreP sp{t->opts.strategy, t->global_epoch, bounded_now ? (t->dense ? 2 : 1) : 0};
+  const ScoreP sp = score_of(t, bounded_now);
   const int g = granule_of(t->field_bytes, values, nullptr);
   const unsigned og = next_own_gen(t);
   const unsigned par = t->own_ws_uses++ & 1u;

@@ -1,7 +1,9 @@
 // The write-back plan object (tfra_sparse_plan_t) and the host helpers the units of the write-back share:
 //   tfra_csr.hip      the CSR plan (gradients): its builders, the object's life, tfra_sparse_plan_read, the route helpers
 //   tfra_setplan.hip  the SET plan (assign-only): its builders, and the unique / find+unique ops built on it
-//   tfra_apply.hip    the gradient half: hot sums + the fused optimizer update
+//   tfra_apply.hip    the gradient half: hot sums + the fused optimizer update (device bodies: tfra_apply_device.h, checks: tfra_apply.h)
+//   tfra_apply_many.hip  the grouped combined write-back (tfra_multi_apply_planned_combined)
+//   tfra_prefetch.hip the two-stream look-ahead driver (tfra_table_step_prefetch[_assign]); no kernel of its own
 //   tfra_own.hip      the assign half: the ownership pass + its remainder
 //   tfra_step.hip     the overlapped step's driver (its kernel: tfra_step_impl.h)
 // The object holds types of tfra_plan_device.h (anonymous namespace): every unit includes the same definitions, so it has one
@@ -100,7 +102,7 @@ void setplan_fill_empty(void* ent, size_t n, hipStream_t s);
 void plan_grids(const tfra_sparse_plan* pl, unsigned* key_blocks, unsigned* bin_blocks);
 int own_plan(Table* t, tfra_sparse_plan** out);
 
-// ---- tfra_apply.hip
+// ---- tfra_apply.hip (callers: tfra_prefetch.hip, and the unit itself)
 int apply_planned_impl(tfra_table_t* tp, const tfra_opt_params* p, const tfra_sparse_plan_t* pl, const float* grads,
                        const float* param_default_row, tfra_stream_t stream, unsigned* progress, unsigned progress_val,
                        const CombEnt* comb = nullptr);

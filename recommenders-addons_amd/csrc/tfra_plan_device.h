@@ -1,6 +1,6 @@
 // Device side of the write-back plans (tfra_csr.hip builds the CSR plan, tfra_setplan.hip the SET plan): the CSR plan's layout and
 // records, the SET plan's table and its probes, and the control words of a plan's count blocks (host and device).  Shared by the
-// plan kernels, the gradient half (tfra_apply.hip), the ownership pass (tfra_own_device.h) and the overlapped step
+// plan kernels, the gradient half (tfra_apply_device.h), the ownership pass (tfra_own_device.h) and the overlapped step
 // (tfra_step_impl.h).
 //
 // Everything here stays in the anonymous namespace, as it was when one file held all of it: kernels take these types by value,

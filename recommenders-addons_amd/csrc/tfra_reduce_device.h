@@ -1,5 +1,5 @@
-// Block-level building blocks of the duplicate-id reductions (tfra_csr.hip: the CSR write-back plan; tfra_apply.hip: its
-// gradient kernels).
+// Block-level building blocks of the duplicate-id reductions (tfra_csr.hip: the CSR write-back plan; tfra_apply_device.h: its
+// gradient kernels' bodies).
 #pragma once
 #include <hip/hip_runtime.h>
 

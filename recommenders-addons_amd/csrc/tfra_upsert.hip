@@ -361,7 +361,7 @@ static int insert_impl(Table* t, hipStream_t s, int field, size_t n, const int64
       deferred = (uint8_t*)t->scratch;
     }
     TableView v = t->view_of(t->cur);
-    const int bd = bounded ? (t->dense ? 2 : 1) : 0;
+    const int bd = bounded_mode(t, bounded);
     with_granule(g, [&](auto G) { insert_unique_kernel<G, U><<<grid, block, 0, s>>>(v, n, k, vals, sc, field, t->aux, strat, epoch, bd, deferred); });
     if (bounded) {
       dim3 grid2((unsigned)((n * 16 + 255) / 256));
@@ -451,7 +451,7 @@ extern "C" int tfra_table_accum_or_assign(tfra_table_t* tp, size_t n, const int6
     if (rc) return rc;
     launch_accum(t->opts.value_dtype, g, grid, s, v, n, k, (const unsigned char*)vod, exists, (const u64*)scores,
                  (unsigned)t->opts.dim, t->aux, t->opts.strategy, t->global_epoch, nullptr, nullptr, deferred,
-                 deferred ? (t->dense ? 2 : 1) : 0);
+                 bounded_mode(t, deferred != nullptr));
     if (deferred) {  // phase 2: the absent keys that found no free slot replace a minimum-score entry
       const unsigned char* vals = (const unsigned char*)vod;
       const u64* sc = (const u64*)scores;

@@ -156,3 +156,32 @@ def test_one_global_step_for_tables_sharing_an_optimizer(env):
   deo1.apply_sparse(one, ids, g)
   for v in tabs:
     assert torch.equal(v.lookup(ids), one.lookup(ids))
+
+
+def test_save_refused_midway_leaves_table_usable(env, tmp_path):
+  """save() refused AFTER its staging buffers exist and the first window has been exported (a key that does not fit 4-byte key
+  files) is an ordinary error: it repeats, and once the option is back the same table saves, and the files load, byte for byte."""
+  torch, de = env
+  from tfra_amd import _capi
+  dim, n = 4, 40
+  keys = torch.arange(1, n + 1, dtype=torch.int64, device="cuda")
+  keys[7] = 2**31 + 5
+  vals = (keys[:, None] % 1000 * torch.ones(dim, device="cuda")).float()
+  t = de.CuckooHashTable(torch.int64, torch.float32, torch.zeros(dim), device="cuda:0", dim=dim, name="ckpt_refused")
+  t.insert(keys, vals)
+  dt = t._table
+  prefix = str(tmp_path / "refused")
+  _capi.call("tfra_table_set_option", dt._h, _capi.OPTION_KEY_BYTES_ON_DISK, 4)
+  for _ in range(2):
+    with pytest.raises(_capi.TfraError, match="does not fit the table's 4-byte key files"):
+      dt.save(prefix)
+  _capi.call("tfra_table_set_option", dt._h, _capi.OPTION_KEY_BYTES_ON_DISK, 8)
+  assert dt.save(prefix) == n
+  t2 = de.CuckooHashTable(torch.int64, torch.float32, torch.zeros(dim), device="cuda:0", dim=dim, name="ckpt_refused2")
+  assert t2._table.load(prefix) == n
+  k1, v1 = t.export()
+  k2, v2 = t2.export()
+  o1, o2 = torch.argsort(k1), torch.argsort(k2)
+  assert k1.numel() == n and torch.equal(k1[o1], k2[o2]) and torch.equal(v1[o1], v2[o2])
+  dt.check_errors()
+  t2._table.check_errors()

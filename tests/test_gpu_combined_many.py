@@ -2,7 +2,7 @@
 DynamicEmbeddingOptimizer.apply_combined_gradients_many).
 
 The reference of every case is a TWIN table driven through the single call (tfra_table_apply_planned_combined) on the same inputs.
-Both forms run the same device functions (hot_sums_body / apply_csr_body, csrc/tfra_apply.hip; comb_den_row / comb_ent_one,
+Both forms run the same device functions (hot_sums_body / apply_csr_body, csrc/tfra_apply_device.h; comb_den_row / comb_ent_one,
 csrc/tfra_combine_device.h), so they must agree BIT FOR BIT: every comparison is torch.equal on the bit patterns of the key-sorted
 exported rows and of every slot, after two steps (the second one updates rows the first one wrote).  No tolerance."""
 

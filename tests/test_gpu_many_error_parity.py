@@ -3,7 +3,7 @@
 Each case makes ONE faulty argument set and gives it to the single C entry point (tfra_table_apply_planned_combined /
 tfra_table_find_combine) and, as a lone descriptor, to the grouped one (tfra_multi_apply_planned_combined /
 tfra_multi_find_combine).  Both run one function per operation for their checks (check_apply_combined + check_apply_planned,
-csrc/tfra_apply.hip; check_find_combine, csrc/tfra_pool.hip), so: the codes are equal, the grouped text behind "descriptor 0: " is
+csrc/tfra_apply.h; check_find_combine, csrc/tfra_pool.hip), so: the codes are equal, the grouped text behind "descriptor 0: " is
 a prefix of the single text behind its "name: " (the single call may add a hint), and neither call writes anything — every input
 here is refused on the host, before any launch."""
 import ctypes
