@@ -114,7 +114,13 @@ int tfra_table_find(tfra_table_t* t, size_t n, const int64_t* keys, void* values
  *    With TFRA_FLAG_UNIQUE_KEYS (what the Insert op passes: HKV's contract) the call is ONE pass
  *    with bucket ownership over the caller's keys (the kernels of tfra_table_upsert_planned, no
  *    plan); a bulk load — so many keys for the table's size that most would collide on a home
- *    bucket — and calls without the flag take the locked kernels.  Same results either way.     */
+ *    bucket — and calls without the flag take the locked kernels.  Same results either way.
+ *    A bounded (Hkv) table at max_capacity: a key that finds neither itself nor an empty slot replaces the minimum-score
+ *    entry among the 30 slots of its two home buckets (ties: the first home bucket before the second; an empty slot before
+ *    any victim).  LFU / EPOCHLFU / CUSTOMIZED admit the key only if its compare score (the caller's score; EPOCHLFU:
+ *    epoch << 32 | score) is >= that minimum — else it is dropped, no error, nothing changes.  The replaced slot starts a new
+ *    life: the new key's LFU count is its own score, aux fields are at aux_init.  Without TFRA_FLAG_UNIQUE_KEYS the call (and
+ *    tfra_table_accum_or_assign) returns TFRA_ERR_UNSUPPORTED there and changes nothing.  (tests/test_gpu_eviction.py)      */
 int tfra_table_insert_or_assign(tfra_table_t* t, size_t n, const int64_t* keys, const void* values,
                                 const uint64_t* scores, uint32_t flags, tfra_stream_t stream);
 
@@ -269,7 +275,12 @@ typedef struct {
 } tfra_opt_params;
 /* d_n: optional DEVICE int64 scalar; when non-NULL only the first min(n, *d_n) keys are applied,
  * so a caller can chain tfra_unique -> tfra_segment_sum -> apply without reading the unique count
- * on the host (n is then the buffer length). */
+ * on the host (n is then the buffer length).
+ * Scores, here and in the sparse / planned / combined forms below: one write-back is one upsert with score 1 — LFU counts + 1,
+ * a CUSTOMIZED score BECOMES 1, EPOCHLFU epoch << 32 | (count + 1).  On a bounded table at max_capacity the keys that hit or find
+ * an empty slot are written first, then every other key replaces the minimum-score entry of its two home buckets as
+ * tfra_table_insert_or_assign does, with compare score 1 (EPOCHLFU: epoch << 32 | 1), and starts from the default row and
+ * aux_init; a key that is not admitted is dropped WITH its gradient, no error.  (tests/test_gpu_eviction.py) */
 int tfra_table_apply_optimizer(tfra_table_t* t, const tfra_opt_params* p, size_t n,
                                const int64_t* keys, const float* grads, const void* param_defaults,
                                int default_is_full, const int64_t* d_n, tfra_stream_t stream);

@@ -4,6 +4,8 @@
   craft(nb, ...)       keys with requested home buckets, filtered from a fixed-seed stream of int64 candidates
   FirstFit(nb)         a sequential table that cannot evict: first-fit placement along b0, b1, b1+1, ... (mod nb) and the two
                        monotone overflow flags, by the rule of locate_or_claim_from; erase empties the slot and keeps the flags
+  pair_scene(nb, ...)  the key sets of an eviction scene (tests/test_gpu_eviction.py): bucket pairs with 30 residents + fresh keys
+                       each, and bystanders that fill the rest of the table past 60 % without touching the pairs
 
 The GPU tests (tests/test_gpu_probe_chains.py) build overflow chains with craft() and hold the table's slot census against
 FirstFit.census().  Within one launch slots only go empty -> key and every inserter takes the first empty slot of its sequence,
@@ -89,6 +91,44 @@ def craft(nb, b0=None, b1=None, substituted=None, count=1, seed=0):
     raise ValueError("craft: the candidate stream (seed %d) holds %d keys with b0=%r b1=%r substituted=%r at nb=%d, %d wanted"
                      % (seed, got.size, b0, b1, substituted, nb, count))
   return got[:count].copy()
+
+
+def pair_scene(nb, pairs, n_pair=75, live=None, per_bucket=13, seed=0, by_seed=1):
+  """Key sets for a table of nb buckets that holds `live` keys (default: 60 % of the slots + 60) with the bucket pairs
+  `pairs` = [(b0, b1), ...] full:
+    keys[i]      n_pair keys whose homes are exactly pairs[i]: the first 30 are the residents (15 fill b0, 15 fill b1), the rest fresh
+    bystanders   live - 30 * len(pairs) keys with neither home in a pair's {b0, b1, b1 + 1, b1 + 2} (those sets must be disjoint), at
+                 most `per_bucket` (< 15) of them sharing a b0: no b0 ever fills, so every bystander sits in its b0 whatever the
+                 order of arrival, and the buckets b1 + 1 / b1 + 2 of every pair stay EMPTY (a fresh pair key that walked would land
+                 there and be seen)
+  -> (keys, bystanders)"""
+  nb = int(nb)
+  assert 0 < per_bucket < SLOTS and 30 <= n_pair
+  shut = []
+  for b0, b1 in pairs:
+    quad = [int(b0), int(b1), (int(b1) + 1) % nb, (int(b1) + 2) % nb]
+    if len(set(quad)) != 4 or set(quad) & set(shut):
+      raise ValueError("pair_scene: the buckets b0, b1, b1 + 1, b1 + 2 of the pairs %r overlap at nb=%d" % (pairs, nb))
+    shut += quad
+  keys = [craft(nb, b0=b0, b1=b1, count=n_pair, seed=seed) for b0, b1 in pairs]
+  if live is None:
+    live = int(0.6 * nb * SLOTS) + 60
+  want = live - 30 * len(pairs)
+  cand, h0, h1, _ = _stream(nb, by_seed)
+  n_look = min(cand.size, 40 * max(want, 1))
+  cand, h0, h1 = cand[:n_look], h0[:n_look], h1[:n_look]
+  ok = ~(np.isin(h0, shut) | np.isin(h1, shut))
+  occ = np.zeros(nb, np.int64)
+  by = []
+  for k, a in zip(cand[ok].tolist(), h0[ok].tolist()):
+    if len(by) == want:
+      break
+    if occ[a] < per_bucket:
+      occ[a] += 1
+      by.append(k)
+  if len(by) < want:
+    raise ValueError("pair_scene: %d bystanders wanted at nb=%d, %d found (%d buckets x %d)" % (want, nb, len(by), nb - len(shut), per_bucket))
+  return keys, np.array(by, np.int64)
 
 
 class FirstFit:

@@ -99,7 +99,8 @@ def test_overlap_step_equals_sequential_ops_dictionary_oracle(env, cap, n):
 
 
 def test_overlap_step_evictions_and_forced_conflicts(env):
-  """A table filled to capacity, a third of every batch never-seen ids (each evicts the oldest entry of its two home buckets)
+  """A table filled to capacity, a third of every batch never-seen ids (each evicts the oldest entry of its two home buckets:
+  WHICH entry that is, is pinned by tests/test_gpu_eviction.py::test_step_drivers_evict_the_oldest, not here)
   and a third the OLDEST resident keys — the likely victims: the write-back keeps meeting victims the next lookup asks for.
   Checked against the table itself after every step (module docstring), plus: exists => the row of the key's last write;
   a key of the batch just written back is present; size <= capacity; the conflict path really ran."""

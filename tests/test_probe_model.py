@@ -140,3 +140,41 @@ def test_find_needs_both_flags():
   m.ovf1[41] = True
   m.ovf0[20] = False
   assert m.find(deep) is None and m.find(keys[20]) is None
+
+
+def test_pair_scene_key_sets():
+  """30 residents fill the pair exactly, call 1 = b0 and call 2 = b1; the bystanders sit in their own b0 in any order of arrival,
+  keep clear of b0, b1, b1 + 1, b1 + 2 of every pair and carry the table past 60 %."""
+  nb = 89
+  pairs = [(5, 12), (25, 32), (45, 52), (65, 86)]          # the last pair's b1 + 2 wraps to bucket 88
+  keys, by = pm.pair_scene(nb, pairs)
+  assert np.array_equal(by, pm.pair_scene(nb, pairs)[1])
+  everything = np.concatenate(keys + [by])
+  assert np.unique(everything).size == everything.size
+  live = 30 * len(pairs) + by.size
+  assert live == int(0.6 * nb * 15) + 60 and live > 0.6 * nb * 15
+  shut = {b for b0, b1 in pairs for b in (b0, b1, (b1 + 1) % nb, (b1 + 2) % nb)}
+  h0, h1, _ = pm.homes(by, nb)
+  assert not (set(h0.tolist()) | set(h1.tolist())) & shut
+  for order in (by, by[::-1]):
+    m = pm.FirstFit(nb)
+    for (b0, b1), k in zip(pairs, keys):
+      kb0, kb1, _ = pm.homes(k, nb)
+      assert k.size == 75 and (kb0 == b0).all() and (kb1 == b1).all()
+      for x in k[:15]:
+        m.insert(x)
+      assert {m.bucket_of(x) for x in k[:15]} == {b0}
+      for x in k[15:30]:
+        m.insert(x)
+      assert {m.bucket_of(x) for x in k[15:30]} == {b1}
+    for x in order:
+      m.insert(x)
+    assert [m.bucket_of(x) for x in by] == h0.tolist()
+    for b0, b1 in pairs:
+      assert m.slots[(b1 + 1) % nb] == [None] * 15 and m.slots[(b1 + 2) % nb] == [None] * 15
+    assert m.census()["live"] == live
+    fresh = keys[0][30]                                     # a table that cannot evict would put it into b1 + 1
+    m.insert(fresh)
+    assert m.bucket_of(fresh) == pairs[0][1] + 1
+  with pytest.raises(ValueError):
+    pm.pair_scene(nb, [(5, 12), (13, 40)])                  # bucket 13 is b1 + 1 of the first pair
