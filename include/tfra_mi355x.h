@@ -136,6 +136,40 @@ int tfra_table_find_n(tfra_table_t* t, size_t n, const int64_t* d_n, const int64
 int tfra_table_insert_or_assign_n(tfra_table_t* t, size_t n, const int64_t* d_n, const int64_t* keys, const void* values,
                                   const uint64_t* scores, tfra_stream_t stream);
 
+/* -- insert_and_evict (HierarchicalKV's insert_and_evict): an insert that hands back what it displaces, for a host or SSD tier
+ *    below HBM, eviction metrics, or re-admission with the old row.
+ *    The write is tfra_table_insert_or_assign(t, n, keys, values, scores, TFRA_FLAG_UNIQUE_KEYS, stream): unique keys, the
+ *    embedding field, the same epoch stepping, the same victim and admission rule, a new life for the replaced slot; the table
+ *    ends as that call would leave it.
+ *    Reported: EVERY entry that leaves the table because of this call is appended at *d_evicted_counter as a triple
+ *    (key, row, score): the row in the table's value dtype with the bytes it held when it left, the score the uint64
+ *    tfra_table_export_batch would have reported for it at that moment.  A key that is NOT admitted (LFU / EPOCHLFU /
+ *    CUSTOMIZED, compare score below the minimum of its home buckets) is reported too, as (the key, the caller's row, its
+ *    compare score — EPOCHLFU: epoch << 32 | score): nothing the caller handed in or had resident is lost.  A key that takes
+ *    an empty slot reports nothing; a key that cannot be placed at all counts in tfra_table_check_errors as for
+ *    insert_or_assign and is not reported.  Whatever the order in which the keys of the call arrive:
+ *    {resident before} U {keys} = {resident after} + {reported}, every reported key exactly once, and a reported key that
+ *    was one of `keys` carries the row of `values`.
+ *    flags: TFRA_EVICT_WHOLE_ROWS — evicted_values rows are the whole co-located row, (1 + aux_fields) * dim elements
+ *    (embedding, then the slot vectors, as stored; a key that was not admitted has its slot vectors at aux_init); without
+ *    it rows of dim elements.  Unknown bits: TFRA_ERR_INVALID.
+ *    Counter and cap are tfra_table_export_batch_if's: *d_evicted_counter (device size_t, the caller zeroes it) is advanced
+ *    by every reported entry whatever cap is; an entry whose position is >= cap is not written — key, row and score alike;
+ *    cap = n always suffices.  evicted_keys == NULL: count only (evicted_values and evicted_scores must be NULL too, else
+ *    TFRA_ERR_INVALID).  evicted_values and evicted_scores may each be NULL.  The output order is unspecified.
+ *    A table that is not at max_capacity (still growing, or TFRA_EVICT_NONE) displaces nothing: the call IS that
+ *    insert_or_assign, the counter and the output buffers are not touched (evicted_scores may be non-NULL).
+ *    At max_capacity the call always takes the locked two-phase kernels (phase 2 captures); the single ownership pass that
+ *    insert_or_assign prefers for small batches does not capture.  Same table either way.
+ *    Refused before anything is enqueued, tfra_last_error() naming the function: a NULL table, keys, values or counter,
+ *    n >= 2^31 (TFRA_ERR_INVALID).  n == 0: TFRA_OK, nothing touched.  Synchronises nothing; usable under
+ *    TFRA_OPTION_CAPTURE_SAFE as tfra_table_insert_or_assign is.  (tests/test_gpu_insert_and_evict.py)                      */
+#define TFRA_EVICT_WHOLE_ROWS 1u
+int tfra_table_insert_and_evict(tfra_table_t* t, size_t n, const int64_t* keys, const void* values,
+                                const uint64_t* scores, uint32_t flags, size_t* d_evicted_counter, size_t cap,
+                                int64_t* evicted_keys, void* evicted_values, uint64_t* evicted_scores,
+                                tfra_stream_t stream);
+
 /* -- accum_or_assign = TableWrapper::accum (lookup_table_op_hkv.h:539-546):
  *    absent & !exists -> insert row; present & exists -> row += delta (element order 0..dim-1,
  *    one add each); otherwise no-op.  Oracle: accumrase_fn (lib/cuckoo/cuckoohash_map.hh:619). */

@@ -1,4 +1,4 @@
-// The locked upsert and accumulate of the table (tfra_table.hip): insert_or_assign[_n], insert_field, accum_or_assign.
+// The locked upsert and accumulate of the table (tfra_table.hip): insert_or_assign[_n], insert_and_evict, insert_field, accum_or_assign.
 // (Unique keys on a table that is large for the batch take the ownership pass instead: own_upsert_unique, tfra_own.hip.)
 #include <hip/hip_runtime.h>
 
@@ -93,33 +93,129 @@ __global__ __launch_bounds__(256) void insert_unique_kernel(TableView v, size_t 
 // ---- phase 2 of a bounded-table upsert: keys that found neither themselves nor an empty slot
 // replace the minimum-score entry of their two home buckets (runs after phase 1 has completed, so
 // no row is being written by an assign while it is evicted).
+
+// Where the capturing instance (tfra_table_insert_and_evict) appends what leaves the table: (key, row, score) triples at *counter.
+struct EvictOut {
+  u64* counter;         // device size_t, advanced by every reported entry whatever cap is
+  u64 cap;              // entries at positions >= cap are not written
+  i64* keys;            // null: count only
+  unsigned char* vals;  // may be null; rows of row_bytes
+  u64* scores;          // may be null
+  unsigned row_bytes;   // field_bytes, or the whole co-located row (TFRA_EVICT_WHOLE_ROWS)
+};
+
+// Row copy whose loads are agent-scope, as load_key_coherent's: the victim may have been published a moment ago by a group of
+// this launch on another XCD (write-through stores), and a plain load could be served from a line that predates them.
 template <int G>
+__device__ __forceinline__ void copy_bytes16_coherent(unsigned char* dst, const unsigned char* src, unsigned bytes, int sub) {
+  for (unsigned off = sub * G; off < bytes; off += 16 * G) {
+    if constexpr (G >= 8) {
+      const u64* p = reinterpret_cast<const u64*>(src + off);
+      u64 t[G / 8];
+#pragma unroll
+      for (int j = 0; j < G / 8; ++j) t[j] = __hip_atomic_load(p + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+      for (int j = 0; j < G / 8; ++j) reinterpret_cast<u64*>(dst + off)[j] = t[j];
+    } else {
+      typedef typename Granule<G>::T T;
+      *reinterpret_cast<T*>(dst + off) = __hip_atomic_load(reinterpret_cast<const T*>(src + off), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+// The slot `word` (row `row`) is LOCKED by this group: the new key's row, aux fields and score, then the key
+template <int G>
+__device__ __forceinline__ void replace_locked(const TableView& v, i64 row, u64 word, i64 key, const unsigned char* src, unsigned field,
+                                               const AuxInit& ai, int strategy, u64 in_score, u64 epoch, int sub) {
+  copy_bytes16_wt<G>(row_ptr(v, row) + field * v.field_bytes, src, v.field_bytes, sub);
+  if (v.n_fields > 1) init_aux_fields<true>(v, ai, row, sub, field);
+  if (sub == 0) store_wt8(score_word(v, word), 0);  // the slot starts a new life: scores count from zero
+  update_score<true>(v, row, true, strategy, in_score, epoch, sub);
+  publish_key(v, word, key, sub);
+}
+
+// CAPTURE: every entry that leaves the table, and every key that is not admitted, is appended to `eo`.
+template <int G, bool CAPTURE = false>
 __global__ __launch_bounds__(256) void insert_evict_kernel(TableView v, size_t n, const i64* __restrict__ keys,
                                                            const unsigned char* __restrict__ vals,
                                                            const u64* __restrict__ scores, unsigned field, AuxInit ai,
-                                                           int strategy, u64 epoch, const uint8_t* __restrict__ deferred) {
+                                                           int strategy, u64 epoch, const uint8_t* __restrict__ deferred, EvictOut eo) {
   const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
   const size_t i = (((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4);
   int fresh = 0, failed = 0;
-  if (i < n && deferred[i]) {
-    const i64 key = keys[i];
-    const u64 in_score = scores ? scores[i] : 1;
-    const bool lru_like = strategy == TFRA_EVICT_LRU || strategy == TFRA_EVICT_EPOCHLRU;
-    u64 word = 0;
-    bool claimed_empty;
-    i64 row = evict_and_lock(v, key, strategy == TFRA_EVICT_EPOCHLFU ? ((epoch << 32) | in_score) : in_score, lru_like, sub,
-                             gshift, &word, claimed_empty);
+  const bool lru_like = strategy == TFRA_EVICT_LRU || strategy == TFRA_EVICT_EPOCHLRU;
+  if constexpr (!CAPTURE) {
+    if (i < n && deferred[i]) {
+      const i64 key = keys[i];
+      const u64 in_score = scores ? scores[i] : 1;
+      u64 word = 0;
+      bool claimed_empty;
+      i64 row = evict_and_lock(v, key, strategy == TFRA_EVICT_EPOCHLFU ? ((epoch << 32) | in_score) : in_score, lru_like, sub,
+                               gshift, &word, claimed_empty);
+      if (row >= 0) {
+        replace_locked<G>(v, row, word, key, vals + i * (size_t)v.field_bytes, field, ai, strategy, in_score, epoch, sub);
+        fresh = (claimed_empty && sub == 0);
+      } else if (row == -3) {
+        failed = (sub == 0);
+      }  // -1: not admitted (its score is below every resident score): silently dropped, like HKV
+    }
+  } else {
+    const bool active = i < n && deferred[i];
+    i64 key = 0, victim = EMPTY_KEY, row = -3;
+    u64 in_score = 1, compare = 0, word = 0;
+    bool claimed_empty = false;
+    if (active) {
+      key = keys[i];
+      in_score = scores ? scores[i] : 1;
+      compare = strategy == TFRA_EVICT_EPOCHLFU ? ((epoch << 32) | in_score) : in_score;
+      row = evict_and_lock(v, key, compare, lru_like, sub, gshift, &word, claimed_empty, nullptr, nullptr, &victim);
+    }
+    // Output positions: ONE counter add per wave.  The wave's groups have left evict_and_lock together (they wait for each other
+    // at the end of its loop, capturing or not), so the ballot makes no lock holder wait for anything it did not wait for before.
+    const bool report = active && ((row >= 0 && !claimed_empty) || row == -1);   // a replaced entry, or a key that is not admitted
+    const u64 m = __ballot(report && sub == 0);
+    u64 pos = 0;
+    if (m) {
+      unsigned lo = 0, hi = 0;
+      if (lane == 0) {
+        const u64 b = atomicAdd(eo.counter, (u64)__popcll(m));
+        lo = (unsigned)b; hi = (unsigned)(b >> 32);
+      }
+      pos = (((u64)(unsigned)__shfl((int)hi, 0) << 32) | (unsigned)__shfl((int)lo, 0)) + (u64)__popcll(m & ((1ULL << gshift) - 1));
+    }
+    const bool wr = report && eo.keys && pos < eo.cap;
+    unsigned char* out_row = eo.vals ? eo.vals + pos * (u64)eo.row_bytes : nullptr;
     if (row >= 0) {
-      copy_bytes16_wt<G>(row_ptr(v, row) + field * v.field_bytes, vals + i * (size_t)v.field_bytes,
-                         v.field_bytes, sub);
-      if (v.n_fields > 1) init_aux_fields<true>(v, ai, row, sub, field);
-      if (sub == 0) store_wt8(score_word(v, word), 0);  // the slot starts a new life: scores count from zero
-      update_score<true>(v, row, true, strategy, in_score, epoch, sub);
-      publish_key(v, word, key, sub);
+      if (wr) {
+        // the slot is LOCKED: its row and score are stable (evict_and_lock re-read the score under the lock).  Read before write.
+        if (sub == 0) {
+          eo.keys[pos] = victim;
+          if (eo.scores) eo.scores[pos] = __hip_atomic_load(score_word(v, word), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (out_row) copy_bytes16_coherent<G>(out_row, row_ptr(v, row), eo.row_bytes, sub);
+      }
+      replace_locked<G>(v, row, word, key, vals + i * (size_t)v.field_bytes, field, ai, strategy, in_score, epoch, sub);
       fresh = (claimed_empty && sub == 0);
-    } else if (row == -3) {
+    } else if (active && row == -3) {
       failed = (sub == 0);
-    }  // -1: not admitted (its score is below every resident score): silently dropped, like HKV
+    } else if (wr) {   // -1, not admitted: the caller's own key, row and compare score; slot vectors at aux_init.  No table read.
+      if (sub == 0) {
+        eo.keys[pos] = key;
+        if (eo.scores) eo.scores[pos] = compare;
+      }
+      if (out_row) {
+        copy_bytes16<G>(out_row, vals + i * (size_t)v.field_bytes, v.field_bytes, sub);
+        for (unsigned f = 1; (f + 1) * v.field_bytes <= eo.row_bytes; ++f) {
+          const unsigned pat = ai.pattern[(f - 1) & 3];
+          unsigned char* p = out_row + f * v.field_bytes;
+          if (G >= 4 && (v.field_bytes & 3) == 0) {
+            for (unsigned off = sub * 4; off < v.field_bytes; off += 64) *reinterpret_cast<unsigned*>(p + off) = pat;
+          } else {
+            for (unsigned off = sub; off < v.field_bytes; off += 16) p[off] = (unsigned char)(pat >> (8 * (off % ai.elem_bytes)));
+          }
+        }
+      }
+    }
   }
   for (int o = 32; o > 0; o >>= 1) { fresh += __shfl_xor(fresh, o); failed += __shfl_xor(failed, o); }
   if (lane == 0) {
@@ -320,8 +416,10 @@ __global__ void iota_u32_kernel(unsigned* p, size_t n) {
   if (i < n) p[i] = (unsigned)i;
 }
 
+// eo (tfra_table_insert_and_evict): where phase 2 of a table at max_capacity reports what it replaces or does not admit; such a call
+// takes the locked kernels (the ownership pass does not capture).  Off max_capacity eo is not looked at.
 static int insert_impl(Table* t, hipStream_t s, int field, size_t n, const int64_t* keys, const void* values,
-                       const uint64_t* scores, uint32_t flags) {
+                       const uint64_t* scores, uint32_t flags, const EvictOut* eo = nullptr) {
   if (n == 0) return TFRA_OK;
   if (!keys || !values) return set_error(TFRA_ERR_INVALID, "insert: null buffer");
   if (field < 0 || field > t->opts.aux_fields) return set_error(TFRA_ERR_INVALID, "insert: bad field");
@@ -345,7 +443,7 @@ static int insert_impl(Table* t, hipStream_t s, int field, size_t n, const int64
   if (bounded && !(flags & TFRA_FLAG_UNIQUE_KEYS))
     return set_error(TFRA_ERR_UNSUPPORTED, "insert: a bounded (Hkv) table at max_capacity needs TFRA_FLAG_UNIQUE_KEYS "
                                            "(HKV's unique-keys contract) so that eviction is well defined");
-  if ((flags & TFRA_FLAG_UNIQUE_KEYS) && field == 0) {
+  if ((flags & TFRA_FLAG_UNIQUE_KEYS) && field == 0 && !(bounded && eo)) {
     // the single pass with bucket ownership whenever the batch is small for the table: no locks, no CAS
     bool taken = false;
     rc = own_upsert_unique(t, s, n, k, vals, sc, &taken);
@@ -365,7 +463,12 @@ static int insert_impl(Table* t, hipStream_t s, int field, size_t n, const int64
     with_granule(g, [&](auto G) { insert_unique_kernel<G, U><<<grid, block, 0, s>>>(v, n, k, vals, sc, field, t->aux, strat, epoch, bd, deferred); });
     if (bounded) {
       dim3 grid2((unsigned)((n * 16 + 255) / 256));
-      with_granule(g, [&](auto G) { insert_evict_kernel<G><<<grid2, block, 0, s>>>(v, n, k, vals, sc, field, t->aux, strat, epoch, deferred); });
+      if (eo) {   // one granule for the table row, the caller's rows and the output rows
+        const int gc = std::min(g, granule_of(eo->row_bytes, eo->vals, nullptr));
+        with_granule(gc, [&](auto G) { insert_evict_kernel<G, true><<<grid2, block, 0, s>>>(v, n, k, vals, sc, field, t->aux, strat, epoch, deferred, *eo); });
+      } else {
+        with_granule(g, [&](auto G) { insert_evict_kernel<G><<<grid2, block, 0, s>>>(v, n, k, vals, sc, field, t->aux, strat, epoch, deferred, EvictOut{}); });
+      }
     }
   } else {
     rc = t->ensure_winner(s);
@@ -421,6 +524,22 @@ extern "C" int tfra_table_insert_or_assign(tfra_table_t* tp, size_t n, const int
   return insert_impl(t, s, 0, n, keys, values, scores, flags);
 }
 
+extern "C" int tfra_table_insert_and_evict(tfra_table_t* tp, size_t n, const int64_t* keys, const void* values, const uint64_t* scores,
+                                           uint32_t flags, size_t* d_evicted_counter, size_t cap, int64_t* evicted_keys,
+                                           void* evicted_values, uint64_t* evicted_scores, tfra_stream_t stream) {
+  if (!tp) return set_error(TFRA_ERR_INVALID, "tfra_table_insert_and_evict: null table");
+  if (flags & ~TFRA_EVICT_WHOLE_ROWS) return set_error(TFRA_ERR_INVALID, "tfra_table_insert_and_evict: unknown flag bits");
+  if (n == 0) return TFRA_OK;
+  if (!keys || !values || !d_evicted_counter) return set_error(TFRA_ERR_INVALID, "tfra_table_insert_and_evict: null buffer");
+  if (!evicted_keys && (evicted_values || evicted_scores))
+    return set_error(TFRA_ERR_INVALID, "tfra_table_insert_and_evict: evicted_keys == NULL counts only, evicted_values and evicted_scores must be NULL too");
+  if (n >= (1ULL << 31)) return set_error(TFRA_ERR_INVALID, "tfra_table_insert_and_evict: more than 2^31-1 keys per call");
+  TABLE_ENTER();
+  const unsigned row_bytes = t->field_bytes * ((flags & TFRA_EVICT_WHOLE_ROWS) ? 1u + (unsigned)t->opts.aux_fields : 1u);
+  const EvictOut eo{(u64*)d_evicted_counter, (u64)cap, (i64*)evicted_keys, (unsigned char*)evicted_values, (u64*)evicted_scores, row_bytes};
+  return insert_impl(t, s, 0, n, keys, values, scores, TFRA_FLAG_UNIQUE_KEYS, &eo);
+}
+
 extern "C" int tfra_table_insert_field(tfra_table_t* tp, int field, size_t n, const int64_t* keys, const void* values,
                                        uint32_t flags, tfra_stream_t stream) {
   TABLE_ENTER();
@@ -458,7 +577,7 @@ extern "C" int tfra_table_accum_or_assign(tfra_table_t* tp, size_t n, const int6
       const int strat = t->opts.strategy;
       const u64 epoch = t->global_epoch;
       dim3 block(256);
-      with_granule(g, [&](auto G) { insert_evict_kernel<G><<<grid, block, 0, s>>>(v, n, k, vals, sc, 0, t->aux, strat, epoch, deferred); });
+      with_granule(g, [&](auto G) { insert_evict_kernel<G><<<grid, block, 0, s>>>(v, n, k, vals, sc, 0, t->aux, strat, epoch, deferred, EvictOut{}); });
     }
     HIP_TRY(hipGetLastError());
     return TFRA_OK;

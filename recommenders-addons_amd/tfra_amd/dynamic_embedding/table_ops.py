@@ -401,6 +401,39 @@ class _DeviceTable:
       _capi.call("tfra_table_insert_or_assign", self._h, n, _ptr(keys), _ptr(values), _ptr(scores), flags,
                  _stream(self._device))
 
+  def upsert_and_evict(self, keys, values, scores=None, whole_rows=False, cap=None, sync=True):
+    """upsert(keys, values, scores, unique_keys=True) that hands back what it displaces (tfra_table_insert_and_evict): every entry
+    that leaves a table at max_capacity because of this call, and every key the table does not admit (with the caller's row and
+    its compare score).  -> (evicted_keys, evicted_values, evicted_scores), trimmed to their count: ONE host read of the counter.
+    whole_rows: the rows are the whole co-located row, [(1 + aux_fields) * dim].  cap: room in the buffers (default: one entry
+    per key, which always suffices); the count goes on beyond it, entries beyond it are not written.
+    sync=False: (count, keys, values, scores) with `count` a device int64 tensor of shape [1] and the buffers untrimmed — no
+    host read.  A table that is not at max_capacity reports nothing."""
+    keys = self._keys(keys)
+    values = self._values_for(keys, values)
+    n = keys.numel()
+    if scores is not None and scores.numel() == 0:
+      scores = None
+    if scores is not None:
+      scores = scores.to(self._device, torch.int64).contiguous()
+      if scores.numel() != n:
+        raise ValueError("scores must have one entry per key")
+    cap = n if cap is None else int(cap)
+    if cap < 0:
+      raise ValueError("cap must be >= 0, got %d" % cap)
+    width = self._dim * (1 + self._aux_fields if whole_rows else 1)
+    counter = torch.zeros(1, dtype=torch.int64, device=self._device)
+    ek = torch.empty(cap, dtype=torch.int64, device=self._device)
+    ev = torch.empty((cap, width), dtype=self._value_dtype, device=self._device)
+    es = torch.empty(cap, dtype=torch.int64, device=self._device)
+    if n:
+      _capi.call("tfra_table_insert_and_evict", self._h, n, _ptr(keys), _ptr(values), _ptr(scores),
+                 _capi.EVICT_WHOLE_ROWS if whole_rows else 0, _ptr(counter), cap, _ptr(ek), _ptr(ev), _ptr(es), _stream(self._device))
+    if not sync:
+      return counter, ek, ev, es   # (the keys stay int64 here: narrowing the unwritten tail would read it)
+    m = min(int(counter.item()), cap)
+    return _narrow_keys(ek[:m], self._key_dtype), ev[:m], es[:m]
+
   def find_n(self, keys, count, out=None, return_exists=False):
     """find over the first `count[0]` entries of the buffer `keys`, the count read ON THE DEVICE (`count`: an int64 tensor on the
     table's device, or pinned host memory): tfra_table_find_n.  Rows beyond the count are left as they are."""
@@ -930,6 +963,12 @@ class HkvHashTable(_LookupInterfaceMirror):
     # HKV requires unique keys per call (PY/dynamic_embedding_variable.py:1377-1378); with that contract
     # a full bounded table can evict by score
     self._table.upsert(keys, values, scores=self._gen_scores(keys), unique_keys=True)
+
+  def insert_and_evict(self, keys, values, scores=None, name=None):
+    """insert that returns (evicted_keys, evicted_values, evicted_scores): what left the table because of this call and what it
+    did not admit (HierarchicalKV's insert_and_evict).  scores: as the engine takes them; None = gen_scores_fn / the strategy's."""
+    keys = torch.as_tensor(keys, device=self._device) if not torch.is_tensor(keys) else keys
+    return self._table.upsert_and_evict(keys, values, scores=self._gen_scores(keys) if scores is None else scores)
 
   def accum(self, keys, values_or_deltas, exists, name=None):
     """PY/hkv_hashtable_ops.py:369-402"""

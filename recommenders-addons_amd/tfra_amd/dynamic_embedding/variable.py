@@ -181,6 +181,23 @@ class Variable:
     for i, t in enumerate(self._tables):
       t.insert(kp[i].to(t._device), vp[i].to(t._device))
 
+  def upsert_and_evict(self, keys, values, name=None):
+    """upsert that returns (evicted_keys, evicted_values, evicted_scores) on the primary device: what every shard displaced or
+    did not admit because of this call (HkvHashTable.insert_and_evict per shard, concatenated as export does)."""
+    for t in self._tables:
+      if not hasattr(t, "insert_and_evict"):
+        raise NotImplementedError("upsert_and_evict needs bounded tables with scores; %s tables never evict (use an "
+                                  "HkvHashTableCreator)" % type(t).__name__)
+    keys = torch.as_tensor(keys, device=self._primary)
+    values = torch.as_tensor(values, device=self._primary)
+    want = tuple(keys.shape) + (self.dim,)
+    if tuple(values.shape) != want:
+      raise ValueError("Expected shape %s for values, got %s" % (list(want), list(values.shape)))
+    kp, perm, counts = self._partition(keys)
+    vp = self._split_rows(values.reshape(-1, self.dim), perm, counts)
+    out = [t.insert_and_evict(kp[i].to(t._device), vp[i].to(t._device)) for i, t in enumerate(self._tables)]
+    return tuple(torch.cat([o[j].to(self._primary) for o in out], 0) for j in range(3))
+
   def accum(self, keys, old_values, new_values, exists, name=None):
     """PY/dynamic_embedding_variable.py:806-855: where(exists, new-old, new) then per-shard accum."""
     keys = torch.as_tensor(keys, device=self._primary)
