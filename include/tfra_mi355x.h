@@ -170,6 +170,34 @@ int tfra_table_insert_and_evict(tfra_table_t* t, size_t n, const int64_t* keys, 
                                 int64_t* evicted_keys, void* evicted_values, uint64_t* evicted_scores,
                                 tfra_stream_t stream);
 
+/* -- find_or_insert (HierarchicalKV's find_or_insert): the lookup of a training step.  A key that is resident is READ; a key
+ *    that is not is admitted with the row the caller drew for it, and that row is returned.  After the call every key of the
+ *    batch that could be placed is resident with the row the caller saw, so the step's write-back only ever hits.
+ *    keys: unique within the call (HKV's contract, what TFRA_FLAG_UNIQUE_KEYS names).  d_n: NULL, or the key count as in
+ *    tfra_table_find_n (a device int64, or pinned host memory the device can read): min(n, *d_n) keys are served, entries of
+ *    values_out / found beyond the count are left as they are; a growing table sizes itself by n, the upper bound.
+ *    init_values: [n, dim] when init_is_full, else one row [dim], in the table's value dtype (tfra_table_find's defaults /
+ *    default_is_full).  scores: NULL or [n], as for tfra_table_insert_or_assign.  values_out ([n, dim]) may be NULL (admit
+ *    only); found ([n]) may be NULL.
+ *    A HIT: values_out[i] = the resident embedding row, found[i] = 1.  The row and the slot vectors are not written; the
+ *    score is touched as insert_or_assign touches it on an assign (LRU: the clock, LFU: += score, CUSTOMIZED: the caller's).
+ *    A MISS: the key is written exactly as tfra_table_insert_or_assign(.., TFRA_FLAG_UNIQUE_KEYS) would write (key, init row,
+ *    score): below max_capacity or on a growing table into an empty slot with the slot vectors at aux_init; at max_capacity
+ *    with the same victim and admission rule, the slot starting a new life.  values_out[i] = the init row and found[i] = 0,
+ *    whether the key was placed, was not admitted, or could not be placed (that one counts in tfra_table_check_errors).
+ *    The table ends as tfra_table_insert_or_assign(keys, found ? resident row : init row, scores, TFRA_FLAG_UNIQUE_KEYS) on
+ *    the locked kernels would leave it: keys, rows, slot vectors, scores; the epoch steps once per call.  A key of the batch
+ *    may be displaced by a later key of the same batch only where that call would displace it; the row returned for it is
+ *    still the one it had.
+ *    The call always takes the locked two-phase kernels (phase 1 finds or claims and copies, phase 2 — at max_capacity only —
+ *    evicts for the keys that found no empty slot); the single ownership pass does not serve it.  Every value dtype, every dim.
+ *    Refused before anything is enqueued, tfra_last_error() naming the function: a NULL table, keys or init_values,
+ *    n >= 2^31 (TFRA_ERR_INVALID).  n == 0: TFRA_OK, nothing touched.  Synchronises nothing; under TFRA_OPTION_CAPTURE_SAFE it
+ *    behaves as tfra_table_insert_or_assign does.  (tests/test_gpu_find_or_insert.py)                                        */
+int tfra_table_find_or_insert(tfra_table_t* t, size_t n, const int64_t* d_n, const int64_t* keys,
+                              const void* init_values, int init_is_full, const uint64_t* scores,
+                              void* values_out, uint8_t* found, tfra_stream_t stream);
+
 /* -- accum_or_assign = TableWrapper::accum (lookup_table_op_hkv.h:539-546):
  *    absent & !exists -> insert row; present & exists -> row += delta (element order 0..dim-1,
  *    one add each); otherwise no-op.  Oracle: accumrase_fn (lib/cuckoo/cuckoohash_map.hh:619). */

@@ -1,4 +1,5 @@
-// The locked upsert and accumulate of the table (tfra_table.hip): insert_or_assign[_n], insert_and_evict, insert_field, accum_or_assign.
+// The locked upsert and accumulate of the table (tfra_table.hip): insert_or_assign[_n], insert_and_evict, find_or_insert, insert_field,
+// accum_or_assign.
 // (Unique keys on a table that is large for the batch take the ownership pass instead: own_upsert_unique, tfra_own.hip.)
 #include <hip/hip_runtime.h>
 
@@ -35,18 +36,39 @@ __device__ __forceinline__ void init_aux_fields(const TableView& v, const AuxIni
   }
 }
 
+// What the FIND instance (tfra_table_find_or_insert) hands back and where its count and init rows come from.
+struct FindOut {
+  unsigned char* vals;   // [n, field_bytes]: the resident row of a hit, the init row of a miss; may be null
+  uint8_t* found;        // may be null
+  unsigned char* spill;  // single init row on a table at max_capacity: phase 2 reads row i of its source, so a deferred key's init row goes here
+  const long long* d_n;  // null, or the key count on the device (n = the buffers' length)
+  int full;              // init rows: one per key, or one for all (find_kernel's defaults)
+};
+
 // ---- insert_or_assign, unique-keys fast path (single pass) ---------------------------------
-template <int G, int U>
+// FIND: a hit is READ — its row goes to fo.vals, nothing of it but the score is written; a miss is written from its
+// init row `vals` as the plain instance writes it, and that row is what fo.vals gets.  Unique keys: no other group of the launch
+// writes a row that a hit reads, and the rows of earlier launches are behind a kernel boundary, so the row is loaded as find loads it.
+template <int G, int U, bool FIND = false>
 __global__ __launch_bounds__(256) void insert_unique_kernel(TableView v, size_t n,
                                                             const i64* __restrict__ keys,
                                                             const unsigned char* __restrict__ vals,
                                                             const u64* __restrict__ scores,
                                                             unsigned field, AuxInit ai, int strategy,
-                                                            u64 epoch, int bounded, uint8_t* __restrict__ deferred) {
+                                                            u64 epoch, int bounded, uint8_t* __restrict__ deferred, FindOut fo) {
   const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48, grp = lane >> 4;
   const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   constexpr int KPW = 4 * U;
   const size_t base = wave * KPW;
+  const size_t n_buf = n;
+  if constexpr (FIND) {
+    if (fo.d_n) {   // uniform load, as find_kernel's
+      const long long dn = *fo.d_n;
+      n = dn < 0 ? 0 : min(n, (size_t)dn);
+    }
+    // phase 2 walks the whole buffer: the flags of the keys beyond the count say "not deferred"
+    if (deferred && lane < KPW && base + lane >= n && base + lane < n_buf) deferred[base + lane] = 0;
+  }
   if (base >= n) return;
   const size_t last = n - 1;
   i64 kreg = keys[min(base + (size_t)(lane & (KPW - 1)), last)];
@@ -71,7 +93,29 @@ __global__ __launch_bounds__(256) void insert_unique_kernel(TableView v, size_t 
       bool is_new;
       i64 row = locate_or_claim_from(v, key[u], h[u], b0[u], k0[u], sub, gshift, is_new, bounded, pf1 ? &k1[u] : nullptr);
       if (deferred && sub == 0) deferred[i] = row == NEED_EVICT;
-      if (row >= 0) {
+      if constexpr (FIND) {
+        const unsigned char* init = vals + (fo.full ? i * (size_t)v.field_bytes : 0);
+        unsigned char* out = fo.vals ? fo.vals + i * (size_t)v.field_bytes : nullptr;
+        const bool hit = row >= 0 && !is_new;
+        if (fo.found && sub == 0) fo.found[i] = hit;
+        if (hit) {
+          if (out) copy_bytes16<G>(out, row_ptr(v, row), v.field_bytes, sub);
+        } else {
+          if (row >= 0) {
+            copy_bytes16<G>(row_ptr(v, row), init, v.field_bytes, sub);
+            if (v.n_fields > 1) init_aux_fields(v, ai, row, sub, 0);
+          } else if (row == NEED_EVICT && fo.spill) {
+            copy_bytes16<G>(fo.spill + i * (size_t)v.field_bytes, init, v.field_bytes, sub);
+          }
+          if (out) copy_bytes16<G>(out, init, v.field_bytes, sub);
+        }
+        if (row >= 0) {
+          update_score(v, row, is_new, strategy, scores ? scores[i] : 1, epoch, sub);
+          fresh += (is_new && sub == 0);
+        } else if (row != NEED_EVICT) {
+          failed += (sub == 0);
+        }
+      } else if (row >= 0) {
         copy_bytes16<G>(row_ptr(v, row) + field * v.field_bytes,
                         vals + i * (size_t)v.field_bytes, v.field_bytes, sub);
         if (is_new && v.n_fields > 1) init_aux_fields(v, ai, row, sub, field);
@@ -460,7 +504,7 @@ static int insert_impl(Table* t, hipStream_t s, int field, size_t n, const int64
     }
     TableView v = t->view_of(t->cur);
     const int bd = bounded_mode(t, bounded);
-    with_granule(g, [&](auto G) { insert_unique_kernel<G, U><<<grid, block, 0, s>>>(v, n, k, vals, sc, field, t->aux, strat, epoch, bd, deferred); });
+    with_granule(g, [&](auto G) { insert_unique_kernel<G, U><<<grid, block, 0, s>>>(v, n, k, vals, sc, field, t->aux, strat, epoch, bd, deferred, FindOut{}); });
     if (bounded) {
       dim3 grid2((unsigned)((n * 16 + 255) / 256));
       if (eo) {   // one granule for the table row, the caller's rows and the output rows
@@ -538,6 +582,53 @@ extern "C" int tfra_table_insert_and_evict(tfra_table_t* tp, size_t n, const int
   const unsigned row_bytes = t->field_bytes * ((flags & TFRA_EVICT_WHOLE_ROWS) ? 1u + (unsigned)t->opts.aux_fields : 1u);
   const EvictOut eo{(u64*)d_evicted_counter, (u64)cap, (i64*)evicted_keys, (unsigned char*)evicted_values, (u64*)evicted_scores, row_bytes};
   return insert_impl(t, s, 0, n, keys, values, scores, TFRA_FLAG_UNIQUE_KEYS, &eo);
+}
+
+// find_or_insert: always the locked two-phase route, as insert_and_evict; the ownership pass does not serve it.
+extern "C" int tfra_table_find_or_insert(tfra_table_t* tp, size_t n, const int64_t* d_n, const int64_t* keys, const void* init_values,
+                                         int init_is_full, const uint64_t* scores, void* values_out, uint8_t* found,
+                                         tfra_stream_t stream) {
+  if (!tp) return set_error(TFRA_ERR_INVALID, "tfra_table_find_or_insert: null table");
+  if (n == 0) return TFRA_OK;
+  if (!keys || !init_values) return set_error(TFRA_ERR_INVALID, "tfra_table_find_or_insert: null buffer");
+  if (n >= (1ULL << 31)) return set_error(TFRA_ERR_INVALID, "tfra_table_find_or_insert: more than 2^31-1 keys per call");
+  TABLE_ENTER();
+  int rc = t->prepare_insert(n, s);   // (n is an upper bound of the keys when d_n is given)
+  if (rc) return rc;
+  const u64 epoch = t->global_epoch;
+  const unsigned fb = t->field_bytes;
+  const int g = granule_of(fb, init_values, values_out);
+  const i64* k = (const i64*)keys;
+  const unsigned char* init = (const unsigned char*)init_values;
+  const u64* sc = (const u64*)scores;
+  const int strat = t->opts.strategy;
+  constexpr int U = 4;
+  const size_t waves = (n + 4 * U - 1) / (4 * U);
+  dim3 grid((unsigned)((waves + 3) / 4)), block(256);
+  const bool bounded = t->at_max_capacity();
+  uint8_t* deferred = nullptr;
+  FindOut fo{(unsigned char*)values_out, found, nullptr, (const long long*)d_n, init_is_full != 0};
+  const unsigned char* src2 = init;   // phase 2 reads row i of its source
+  if (bounded) {
+    const size_t flags_bytes = (n + 255) & ~(size_t)255;
+    const bool spill = !init_is_full && !values_out;
+    rc = t->ensure_scratch(flags_bytes + (spill ? n * (size_t)fb : 0), s);
+    if (rc) return rc;
+    t->apply_P = 0;
+    deferred = (uint8_t*)t->scratch;
+    if (spill) fo.spill = (unsigned char*)t->scratch + flags_bytes;
+    if (!init_is_full) src2 = spill ? fo.spill : fo.vals;   // a deferred key's init row is in values_out[i] after phase 1
+  }
+  TableView v = t->view_of(t->cur);
+  const int bd = bounded_mode(t, bounded);
+  with_granule(g, [&](auto G) { insert_unique_kernel<G, U, true><<<grid, block, 0, s>>>(v, n, k, init, sc, 0, t->aux, strat, epoch, bd, deferred, fo); });
+  if (bounded) {
+    dim3 grid2((unsigned)((n * 16 + 255) / 256));
+    with_granule(g, [&](auto G) { insert_evict_kernel<G><<<grid2, block, 0, s>>>(v, n, k, src2, sc, 0, t->aux, strat, epoch, deferred, EvictOut{}); });
+  }
+  HIP_TRY(hipGetLastError());
+  t->step_epoch();
+  return TFRA_OK;
 }
 
 extern "C" int tfra_table_insert_field(tfra_table_t* tp, int field, size_t n, const int64_t* keys, const void* values,

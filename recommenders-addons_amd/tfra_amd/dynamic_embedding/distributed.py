@@ -213,8 +213,9 @@ class RoutedPrefetchStep:
   NSLOTS = 4
 
   def __init__(self, var, optimizer, group=None, partition_mode=None, force_collectives=False):
-    from .optimizer import DynamicEmbeddingOptimizer
+    from .optimizer import DynamicEmbeddingOptimizer, _refuse_init_on_lookup
     from .table_ops import SparsePlan
+    _refuse_init_on_lookup(var, "RoutedPrefetchStep")
     if var.shard_num != 1 or not DynamicEmbeddingOptimizer.can_plan(var, 1) or var.value_dtype != torch.float32:   # (the route ships fp32 rows)
       raise ValueError("RoutedPrefetchStep needs a single-shard fp32 local Variable with dim % 4 == 0, dim <= 256")
     optimizer._check(var)
@@ -465,7 +466,8 @@ class NativeRoutedStep:
                threaded=True, share_transport_of=None):
     import ctypes
     from .. import _capi
-    from .optimizer import DynamicEmbeddingOptimizer
+    from .optimizer import DynamicEmbeddingOptimizer, _refuse_init_on_lookup
+    _refuse_init_on_lookup(var, "NativeRoutedStep")
     if var.shard_num != 1 or not DynamicEmbeddingOptimizer.can_plan(var, 1) or var.value_dtype != torch.float32:   # (the route ships fp32 rows)
       raise ValueError("NativeRoutedStep needs a single-shard fp32 local Variable with dim % 4 == 0, dim <= 256")
     optimizer._check(var)

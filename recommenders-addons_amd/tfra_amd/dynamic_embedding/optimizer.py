@@ -20,7 +20,7 @@ import torch
 from .. import _capi
 from . import device_ops
 from .table_ops import _driver_ids, _narrow_keys
-from .variable import SparseTrainableWrapper, TrainableWrapper, Variable
+from .variable import SparseTrainableWrapper, TrainableWrapper, Variable, misses_are_static
 
 
 class _Opt:
@@ -415,8 +415,10 @@ class DynamicEmbeddingOptimizer:
   @staticmethod
   def can_plan(var, n):
     """The planned / two-kernel write-back covers one shard, float32 / float16 / bfloat16 rows with dim % 4 == 0, dim <= 256
-    (gradients and the default row are float32 in every case; a half row is up-cast, updated in float32 and rounded once)."""
-    return (var.shard_num == 1 and not callable(var.initializer) and var.dim % 4 == 0 and var.dim <= 256 and
+    (gradients and the default row are float32 in every case; a half row is up-cast, updated in float32 and rounded once).
+    A miss of the write-back starts from ONE static row, so the variable's misses must be static (`variable.misses_are_static`:
+    no callable initializer, or init_on_lookup — the lookup has admitted every key with its own row already)."""
+    return (var.shard_num == 1 and misses_are_static(var) and var.dim % 4 == 0 and var.dim <= 256 and
             n <= (1 << 18) and var.value_dtype in PLANNED_VALUE_DTYPES)
 
   def plan(self, var, ids, plan=None):
@@ -452,7 +454,7 @@ class DynamicEmbeddingOptimizer:
       return
     if getattr(var, "restrict_policy", None) is not None:  # PY/embedding_weights.py:441-442
       var.restrict_policy.apply_update(ids)
-    if (var.shard_num == 1 and not callable(var.initializer) and var.dim % 4 == 0 and var.dim <= 256 and not self.exact_order and
+    if (var.shard_num == 1 and misses_are_static(var) and var.dim % 4 == 0 and var.dim <= 256 and not self.exact_order and
         var.value_dtype in PLANNED_VALUE_DTYPES):
       # whole backward half in two kernels (tile reduce + bucket apply): no host sync, deterministic.  (More than 2^18
       # ids: the library reduces chunk by chunk and applies every key once — tfra_apply.hip: apply_sparse_big.)
@@ -460,7 +462,7 @@ class DynamicEmbeddingOptimizer:
       t._table.apply_sparse(p, ids, grad, t._default_value.to(torch.float32))
       return
     if var.dim % 4 == 0 and var.dim <= 256 and n <= (1 << 18) and not self.exact_order:
-      # sharded variables / callable initializers: the same parallel, order-fixed duplicate reduction
+      # sharded variables / per-key misses (a callable initializer without init_on_lookup): the same parallel, order-fixed duplicate reduction
       # (tile reduce + bucket merge, float32 sums), then one fused update per unique key and shard — on a half / bfloat16
       # table the rule runs in float32 on the up-cast row and slots and the results are rounded to the storage type once.  (unique +
       # segment_sum walks a segment sequentially: 9 ms for a Zipf batch whose hottest id repeats 24 000 times.)
@@ -468,7 +470,7 @@ class DynamicEmbeddingOptimizer:
     else:
       uniq_buf, idx, cnt = device_ops.unique_no_sync(ids)
       gsum = device_ops.segment_sum(grad, idx, cnt, n)
-    if var.shard_num == 1 and not callable(var.initializer):
+    if var.shard_num == 1 and misses_are_static(var):
       # one shard: no partition, so the unique count never has to reach the host
       t = var._tables[0]
       t._table.apply_optimizer(p, uniq_buf, gsum, t._default_value.to(torch.float32), n_dev=cnt)
@@ -487,6 +489,14 @@ class DynamicEmbeddingOptimizer:
       t._table.apply_optimizer(p, k, gp[i].to(t._device), dd.to(torch.float32))
 
 
+def _refuse_init_on_lookup(var, who):
+  """The step drivers look their ids up inside their own C calls, which never admit: a variable whose lookups have to admit
+  (init_on_lookup) would have its never-seen keys updated from the static default row there."""
+  if var.admits_on_lookup():
+    raise ValueError("%s does not serve an init_on_lookup Variable: its lookups do not admit never-seen keys; use "
+                     "embedding_lookup(..., return_trainable=True) + apply_gradients" % who)
+
+
 class CapturedTrainStep:
   """lookup + sparse write-back of ONE single-shard Variable captured into a HIP graph.
 
@@ -501,6 +511,7 @@ class CapturedTrainStep:
   def __init__(self, var, optimizer, batch, reserve_slots=None):
     if var.shard_num != 1:
       raise ValueError("CapturedTrainStep needs a single-shard Variable")
+    _refuse_init_on_lookup(var, "CapturedTrainStep")
     self.var, self.deo, self.batch = var, optimizer, int(batch)
     self.table = var.tables[0]._table
     dev = self.table.device
@@ -567,6 +578,7 @@ class PrefetchStep:
 
   def __init__(self, var, optimizer):
     from .table_ops import SparsePlan
+    _refuse_init_on_lookup(var, "PrefetchStep")
     if var.shard_num != 1 or not DynamicEmbeddingOptimizer.can_plan(var, 1):
       raise ValueError("PrefetchStep needs a single-shard float32 / float16 / bfloat16 Variable with dim % 4 == 0, dim <= 256")
     optimizer._check(var)
@@ -641,6 +653,7 @@ class MultiTablePrefetchStep:
     from .table_ops import SparsePlan
     self.vars, self.deo, self.workers = list(variables), optimizer, int(workers)
     for v in self.vars:
+      _refuse_init_on_lookup(v, "MultiTablePrefetchStep")
       if v.shard_num != 1 or not DynamicEmbeddingOptimizer.can_plan(v, 1):
         raise ValueError("MultiTablePrefetchStep needs single-shard float32 / float16 / bfloat16 Variables with dim % 4 == 0, dim <= 256")
       optimizer._check(v)

@@ -434,6 +434,39 @@ class _DeviceTable:
     m = min(int(counter.item()), cap)
     return _narrow_keys(ek[:m], self._key_dtype), ev[:m], es[:m]
 
+  def find_or_insert(self, keys, init_values=None, scores=None, return_exists=False, count=None, out=None):
+    """The lookup that admits (tfra_table_find_or_insert): the resident row of every key that has one; a key that has none is
+    inserted with its init row — `init_values[i]` ([n, dim]), or the one row `init_values` ([dim]; None: the table's default row)
+    — as upsert(.., unique_keys=True) would insert it, and that row is returned.  `keys` are UNIQUE.  scores: as for `upsert`.
+    count: a device int64 (or pinned) count of the leading keys that are served, read on the device; rows of `out` beyond it are
+    left as they are.  out: the [n, dim] buffer to fill (default: a new one).  -> rows, or (rows, exists) — exists[i] False for
+    every key that was not resident before the call, admitted or not.  Nothing is read on the host."""
+    keys = self._keys(keys)
+    n = keys.numel()
+    d = self._default_value if init_values is None else init_values
+    d = torch.as_tensor(d, device=self._device) if not torch.is_tensor(d) else d.to(self._device)
+    if d.dtype != self._value_dtype:
+      raise TypeError("init values must be dtype %s, got %s" % (self._value_dtype, d.dtype))
+    d = d.contiguous()
+    full = int(d.numel() == n * self._dim)   # (one key: the two forms are the same row)
+    if not full and d.numel() != self._dim:
+      raise ValueError("init_values must be [n, dim] or one row of dim=%d elements, got shape %s" % (self._dim, list(d.shape)))
+    if out is None:
+      out = torch.empty(tuple(keys.shape) + (self._dim,), dtype=self._value_dtype, device=self._device)
+    elif out.dtype != self._value_dtype or out.numel() != n * self._dim or not out.is_contiguous() or out.device != self._device:
+      raise ValueError("out must be a contiguous %s tensor of %d x %d elements on %s" % (self._value_dtype, n, self._dim, self._device))
+    if scores is not None and scores.numel() == 0:
+      scores = None
+    if scores is not None:
+      scores = scores.to(self._device, torch.int64).contiguous()
+      if scores.numel() != n:
+        raise ValueError("scores must have one entry per key")
+    exists = torch.zeros(keys.shape, dtype=torch.bool, device=self._device) if return_exists else None
+    if n:
+      _capi.call("tfra_table_find_or_insert", self._h, n, _ptr(count), _ptr(keys), _ptr(d), full, _ptr(scores), _ptr(out),
+                 _ptr(exists), _stream(self._device))
+    return (out, exists) if return_exists else out
+
   def find_n(self, keys, count, out=None, return_exists=False):
     """find over the first `count[0]` entries of the buffer `keys`, the count read ON THE DEVICE (`count`: an int64 tensor on the
     table's device, or pinned host memory): tfra_table_find_n.  Rows beyond the count are left as they are."""
@@ -844,6 +877,17 @@ class _LookupInterfaceMirror:
   def lookup(self, keys, dynamic_default_values=None, return_exists=False, name=None):
     """PY/cuckoo_hashtable_ops.py:272-340"""
     return self._table.find(keys, dynamic_default_values, return_exists)
+
+  def find_or_insert(self, keys, dynamic_default_values=None, return_exists=False, name=None, count=None):
+    """HierarchicalKV's find_or_insert: `lookup` that inserts every key it does not find with the row it returns for it
+    (`dynamic_default_values[i]`, else the table's default row), as `insert` would.  Keys must be unique.  Scores follow
+    `insert`'s rule.  count: a device int64 count of the leading keys to serve (`_DeviceTable.find_or_insert`)."""
+    keys = torch.as_tensor(keys, device=self._device) if not torch.is_tensor(keys) else keys
+    return self._table.find_or_insert(keys, dynamic_default_values, scores=self._gen_scores(keys), return_exists=return_exists,
+                                      count=count)
+
+  def _gen_scores(self, keys):   # tables without scores
+    return None
 
   def export(self, name=None):
     k, v, _ = self._table.export_all()

@@ -77,14 +77,33 @@ class HkvHashTableCreator(KVCreator):
                         checkpoint=checkpoint, config=cfg, device=device, **kw)
 
 
+def misses_are_static(var):
+  """Whether a key the optimizer write-back does not find may start from the ONE static default row of `var` (a Variable, or
+  anything with its `initializer`): there is no callable initializer, or the step's lookup has admitted every key with its own
+  row already (init_on_lookup), so the write-back only hits.  The one predicate behind every fused write-back's eligibility."""
+  return not callable(var.initializer) or bool(getattr(var, "init_on_lookup", False))
+
+
 class Variable:
-  """A sharded dynamic-embedding table (PY/dynamic_embedding_variable.py:453-692)."""
+  """A sharded dynamic-embedding table (PY/dynamic_embedding_variable.py:453-692).
+
+  init_on_lookup (opt-in, default False): the lookup of a training step ADMITS.  `embedding_lookup(..., return_trainable=True)` and
+  `embedding_lookup_sparse(..., return_trainable=True)` of a non-bp_v2 variable de-duplicate their ids on the device, draw one
+  initializer row per unique id and call the table's find_or_insert (`lookup_or_insert`): a never-seen id enters the table with the
+  row the model is handed, every position of a repeated id sees that one row, and the admitting lookup reads nothing on the host.  The write-back then
+  only hits, so a variable with a callable initializer takes the planned, one-call and combined write-backs (`misses_are_static`),
+  and the row that is updated is the row the forward pass returned — with False the write-back draws a second row from the
+  initializer for every miss.  Optimizer slots start at aux_init when the lookup admits the key.
+  One limit: a key that was looked up but is not resident at write-back time — evicted in between, or not admitted by a table at
+  max_capacity under LFU / CUSTOMIZED — is updated from the static default row, as in every fused write-back.
+  Plain lookups (`lookup`, `embedding_lookup` without return_trainable, the pooled forward) never admit, with either setting."""
 
   def __init__(self, key_dtype=torch.int64, value_dtype=torch.float32, dim=1, devices=None,
                partitioner=default_partition_fn, shared_name=None, name="DynamicEmbedding_Variable", initializer=None,
                trainable=True, checkpoint=True, init_size=0, kv_creator=None, restrict_policy=None, bp_v2=False,
-               short_file_name=False, aux_fields=0, aux_init=(0.0, 0.0, 0.0, 0.0)):
+               short_file_name=False, aux_fields=0, aux_init=(0.0, 0.0, 0.0, 0.0), init_on_lookup=False):
     self.key_dtype = key_dtype
+    self.init_on_lookup = bool(init_on_lookup)
     self.value_dtype = value_dtype
     self.dim = int(dim)
     self.bp_v2 = bp_v2
@@ -255,6 +274,37 @@ class Variable:
     if return_exists:
       return v, e.reshape(keys.shape)
     return v
+
+  def misses_are_static(self):
+    """The module's `misses_are_static` of this variable."""
+    return misses_are_static(self)
+
+  def admits_on_lookup(self):
+    """Whether a training step's lookup admits never-seen keys: init_on_lookup, and a callable initializer to draw their rows
+    from (with a static default row a miss reads the row the write-back starts from anyway)."""
+    return self.init_on_lookup and callable(self.initializer)
+
+  def lookup_or_insert(self, keys, return_exists=False, name=None):
+    """`lookup` that admits (find_or_insert per shard): a key that is not resident enters its table with the row this call
+    returns for it — a row of the callable initializer (one draw of [n, dim] per shard, row j for that shard's key j), else
+    the static default row — as `upsert` would insert it.  `keys` must be UNIQUE.  exists[i] is False for every key that was
+    not resident before the call."""
+    keys = torch.as_tensor(keys, device=self._primary)
+    kp, perm, counts = self._partition(keys)
+    vals, exs = [], []
+    for i, t in enumerate(self._tables):
+      k = kp[i].to(t._device)
+      dd = self._create_default_values_by_initializer(k.numel(), t._device)
+      r, e = t.find_or_insert(k, dynamic_default_values=dd, return_exists=True)
+      vals.append(r.to(self._primary))
+      exs.append(e.to(self._primary))
+    if perm is None:
+      v, e = vals[0], exs[0]
+    else:
+      v = device_ops.scatter_rows(torch.cat(vals, 0), perm)
+      e = device_ops.scatter_rows(torch.cat(exs, 0).reshape(-1, 1).to(torch.uint8), perm).reshape(-1).to(torch.bool)
+    v = v.reshape(tuple(keys.shape) + (self.dim,))
+    return (v, e.reshape(keys.shape)) if return_exists else v
 
   def can_lookup_combined(self):
     """Whether `lookup_combined` serves this variable: one shard, a static default row (no callable initializer), float32 /
@@ -487,13 +537,13 @@ def _known_slot_layouts():
 
 def get_variable(name, key_dtype=torch.int64, value_dtype=torch.float32, dim=1, devices=None,
                  partitioner=default_partition_fn, shared_name="get_variable", initializer=None, trainable=True,
-                 checkpoint=True, init_size=0, kv_creator=None, restrict_policy=None, bp_v2=False, **kw):
-  """PY/dynamic_embedding_variable.py:1265-1359: create-or-reuse by name."""
+                 checkpoint=True, init_size=0, kv_creator=None, restrict_policy=None, bp_v2=False, init_on_lookup=False, **kw):
+  """PY/dynamic_embedding_variable.py:1265-1359: create-or-reuse by name.  init_on_lookup: see `Variable`."""
   if name in _VARIABLES:
     return _VARIABLES[name]
   v = Variable(key_dtype=key_dtype, value_dtype=value_dtype, dim=dim, devices=devices, partitioner=partitioner,
                shared_name=shared_name, name=name, initializer=initializer, trainable=trainable, checkpoint=checkpoint,
-               init_size=init_size, kv_creator=kv_creator, restrict_policy=restrict_policy, bp_v2=bp_v2, **kw)
+               init_size=init_size, kv_creator=kv_creator, restrict_policy=restrict_policy, bp_v2=bp_v2, init_on_lookup=init_on_lookup, **kw)
   _VARIABLES[name] = v
   return v
 
@@ -607,14 +657,38 @@ class TrainableWrapper:
     except Exception:
       pass
 
+  _ids_are_unique = False   # (SparseTrainableWrapper: its ids are tf.unique's output already)
+
   def prefetch_values(self):
-    """PY/embedding_weights.py:163-170"""
+    """PY/embedding_weights.py:163-170.  An init_on_lookup variable (not bp_v2) admits here: `_lookup_admitting`."""
     if self.params.bp_v2:
       r, self.exists = self.params.lookup(self.ids, return_exists=True)
+    elif self.params.admits_on_lookup() and self.ids.numel():
+      r = self._lookup_admitting()
     else:
       r = self.params.lookup(self.ids)
     self._values = self.transform(r)
     return self._values
+
+  def _lookup_admitting(self):
+    """The lookup of an init_on_lookup variable: the ids de-duplicated on the device in first-occurrence order (tfra_unique — a
+    seeded initializer then fills the table reproducibly), ONE draw initializer([n, dim]) whose row j belongs to unique id j,
+    find_or_insert over the unique buffer with the count left on the device, and the rows gathered back through the inverse
+    index: every position of an id sees one row, and the table holds it.  No host read.  (Several shards: the unique ids are
+    trimmed with one host read and go through `Variable.lookup_or_insert`.)"""
+    params, ids = self.params, self.ids
+    if params.shard_num == 1:
+      t = params._tables[0]
+      init = params._create_default_values_by_initializer(ids.numel(), t._device)
+      if self._ids_are_unique:
+        return t.find_or_insert(ids.to(t._device), dynamic_default_values=init)
+      uniq, idx, cnt = device_ops.unique_no_sync(ids.to(t._device))
+      rows = t.find_or_insert(uniq, dynamic_default_values=init, count=cnt)
+      return device_ops.gather_rows(rows, idx)   # (idx < count everywhere: rows beyond the count are never read)
+    if self._ids_are_unique:
+      return params.lookup_or_insert(ids)
+    uniq, idx, _ = device_ops.unique(ids)
+    return device_ops.gather_rows(params.lookup_or_insert(uniq), idx)
 
   def transform(self, result):
     """PY/embedding_weights.py:497-521: optional clip_by_norm over the embedding axis."""
@@ -660,6 +734,7 @@ class SparseTrainableWrapper(TrainableWrapper):
   caller's weights (`_caller_weights`: `_note_pruned`), from which the pruned positions are found when the gradient is asked for."""
 
   _LAZY = ("ids", "_idx", "_n_unique", "exists", "_values")
+  _ids_are_unique = True
 
   def __init__(self, params, ids, idx, n_unique, seg, weights, combiner, n_rows, out_shape, entry_ids, entry_seg,
                entry_weights, max_norm=None, plan_writeback=False, lookup_ids=None, entry_plan=None):
