@@ -388,6 +388,33 @@ int tfra_table_apply_planned(tfra_table_t* t, const tfra_opt_params* p, const tf
                              const float* grads, const float* param_default_row, tfra_stream_t stream);
 int tfra_table_upsert_planned(tfra_table_t* t, const tfra_sparse_plan_t* plan, const void* values,
                               const uint64_t* scores, tfra_stream_t stream);
+/* -- find_or_insert over a write-back plan: the lookup of a training step whose ids repeat, served from the plan the step's
+ *    write-back uses anyway — one de-duplication per step.
+ *    plan: a CSR plan (tfra_sparse_plan_build with the table's dim) over a batch of n ids that may repeat; n is the plan's id
+ *    count.  The keys served are the plan's distinct keys; their count stays on the device, nothing is read on the host and
+ *    nothing is synchronised.  L(k) = the last batch position of key k.
+ *    The table effect is tfra_table_find_or_insert's over the distinct keys, with the init row of k = init_values[L(k)] when
+ *    init_is_full ([n, dim], one row per batch POSITION), else the one row [dim]; score of k = scores[L(k)] (scores: NULL or
+ *    [n], per position; NULL as there).  The table ends as that call leaves it: keys, rows, slot vectors at aux_init for
+ *    admitted keys, scores touched once per KEY (not per occurrence), one epoch step, the same victim and admission rule at
+ *    max_capacity.  The result does not depend on the plan's internal key order.
+ *    rows_out [n, dim] (the table's value dtype, required), found [n] (may be NULL): for EVERY batch position p of key k,
+ *    rows_out[p] = the row tfra_table_find_or_insert returns for k and found[p] its flag — the resident row on a hit, the
+ *    init row on a miss, whether the key was placed, not admitted or unplaceable.  All positions of a key get identical bits.
+ *    Limits, as the planned write-back's: float32 / float16 / bfloat16 rows, dim % 4 == 0, dim <= 256, rows_out and
+ *    init_values 16-byte aligned.
+ *    Refused before anything is enqueued, tfra_last_error() naming the function: a NULL table, plan, init_values or rows_out,
+ *    a plan never built, a plan whose dim is not the table's (TFRA_ERR_INVALID); an assign-only plan (dim 0), a dtype, dim
+ *    or alignment outside the limits (TFRA_ERR_UNSUPPORTED).
+ *    A plan whose build latched errors adds them to the table's error counter (tfra_table_check_errors), as the planned
+ *    write-backs do; the positions of the keys the plan lost are left as they are.
+ *    The plan stays the write-back's plan: a later tfra_table_apply_planned, _apply_planned_combined or _upsert_planned of it
+ *    does what it would have done.  (The call uses plan scratch those calls overwrite anyway; records, bins, count words and
+ *    ownership counters are not written.)  Usable under TFRA_OPTION_CAPTURE_SAFE as tfra_table_find_or_insert is.
+ *    (tests/test_gpu_find_or_insert_planned.py)                                                                          */
+int tfra_table_find_or_insert_planned(tfra_table_t* t, const tfra_sparse_plan_t* plan,
+                                      const void* init_values, int init_is_full, const uint64_t* scores,
+                                      void* rows_out, uint8_t* found, tfra_stream_t stream);
 /* The write-back of an embedding_lookup_sparse (gradient with respect to its combined output): the contract of
  * tfra_table_apply_planned, with `plan` built over the ENTRY ids (the sparse input's values, repeats included) and the
  * gradient of plan position e = the combiner's backward of entry e, formed from grad_out[n_rows, dim] in registers

@@ -467,6 +467,43 @@ class _DeviceTable:
                  _ptr(exists), _stream(self._device))
     return (out, exists) if return_exists else out
 
+  def find_or_insert_planned(self, plan, init_values=None, scores=None, return_exists=False, out=None):
+    """`find_or_insert` of a batch whose ids may repeat, over the write-back plan of that batch (tfra_table_find_or_insert_planned):
+    `plan` is a built `SparsePlan` of this table's dim; the keys served are its distinct ids, and every batch position of an id
+    gets the id's row.  init_values: [n, dim] — row p belongs to batch POSITION p, an id takes the row of its last position — or
+    one row ([dim]; None: the table's default row).  scores: per position, an id takes its last position's.  out: the [n, dim]
+    buffer to fill.  -> rows [n, dim], or (rows, exists).  The plan stays usable for `apply_planned` / `upsert_planned`: the
+    batch is de-duplicated once.  Nothing is read on the host."""
+    if plan._dim != self._dim or plan._device != self._device:
+      raise ValueError("the plan was built for dim %d on %s" % (plan._dim, plan._device))
+    n = plan.n
+    d = self._default_value if init_values is None else init_values
+    d = torch.as_tensor(d, device=self._device) if not torch.is_tensor(d) else d.to(self._device)
+    if d.dtype != self._value_dtype:
+      raise TypeError("init values must be dtype %s, got %s" % (self._value_dtype, d.dtype))
+    d = d.contiguous()
+    full = int(d.numel() == n * self._dim)   # (one id: the two forms are the same row)
+    if not full and d.numel() != self._dim:
+      raise ValueError("init_values must be [n, dim] or one row of dim=%d elements, got shape %s" % (self._dim, list(d.shape)))
+    if out is None:
+      out = torch.empty((n, self._dim), dtype=self._value_dtype, device=self._device)
+    elif out.dtype != self._value_dtype or out.numel() != n * self._dim or not out.is_contiguous() or out.device != self._device:
+      raise ValueError("out must be a contiguous %s tensor of %d x %d elements on %s" % (self._value_dtype, n, self._dim, self._device))
+    if scores is not None and scores.numel() == 0:
+      scores = None
+    if scores is not None:
+      scores = scores.to(self._device, torch.int64).contiguous()
+      if scores.numel() != n:
+        raise ValueError("scores must have one entry per batch position")
+    exists = torch.zeros(n, dtype=torch.bool, device=self._device) if return_exists else None
+    if n:
+      stream = torch.cuda.current_stream(self._device)
+      plan._wait_built(stream)
+      _capi.call("tfra_table_find_or_insert_planned", self._h, plan._h, _ptr(d), full, _ptr(scores), _ptr(out), _ptr(exists),
+                 _stream(self._device))
+      plan._mark_used(stream)
+    return (out, exists) if return_exists else out
+
   def find_n(self, keys, count, out=None, return_exists=False):
     """find over the first `count[0]` entries of the buffer `keys`, the count read ON THE DEVICE (`count`: an int64 tensor on the
     table's device, or pinned host memory): tfra_table_find_n.  Rows beyond the count are left as they are."""
@@ -885,6 +922,13 @@ class _LookupInterfaceMirror:
     keys = torch.as_tensor(keys, device=self._device) if not torch.is_tensor(keys) else keys
     return self._table.find_or_insert(keys, dynamic_default_values, scores=self._gen_scores(keys), return_exists=return_exists,
                                       count=count)
+
+  def find_or_insert_planned(self, plan, dynamic_default_values=None, return_exists=False, name=None):
+    """`find_or_insert` of the batch a `SparsePlan` was built over (ids may repeat): every position gets its id's row, an id that
+    is not resident enters with the row of its LAST position (`dynamic_default_values[p]`, else the table's default row).  Scores
+    follow `insert`'s rule, evaluated per position.  The plan then serves the write-back (`_DeviceTable.find_or_insert_planned`)."""
+    return self._table.find_or_insert_planned(plan, dynamic_default_values, scores=self._gen_scores(plan.ids),
+                                              return_exists=return_exists)
 
   def _gen_scores(self, keys):   # tables without scores
     return None
