@@ -37,7 +37,7 @@ static inline hipError_t on_device(int device) {
   return hipSetDevice(device);
 }
 
-// head of a C entry point of the table units (tfra_table / tfra_grow / tfra_upsert / tfra_scan .hip): handle `tp`, `stream`
+// head of a C entry point of the table units (tfra_table / tfra_grow / tfra_upsert / tfra_find_insert / tfra_accum / tfra_scan .hip): handle `tp`, `stream`
 #define TABLE_ENTER()                                         \
   Table* t = reinterpret_cast<Table*>(tp);                    \
   if (!t) return set_error(TFRA_ERR_INVALID, "null table");   \

@@ -6,7 +6,7 @@
 //   tfra_prefetch.hip the two-stream look-ahead driver (tfra_table_step_prefetch[_assign]); no kernel of its own
 //   tfra_own.hip      the assign half: the ownership pass + its remainder
 //   tfra_step.hip     the overlapped step's driver (its kernel: tfra_step_impl.h)
-//   tfra_upsert.hip   find_or_insert over a CSR plan's keys (tfra_table_find_or_insert_planned), next to the locked kernels it shares
+//   tfra_find_insert.hip  find_or_insert over a CSR plan's keys (tfra_table_find_or_insert_planned)
 // The object holds types of tfra_plan_device.h (anonymous namespace): every unit includes the same definitions, so it has one
 // layout.  A helper shared across units cannot take or return such a type (its linkage would be internal): the shared ones below
 // take the plan object, pointers and scalars; keys_of, which returns one, is defined here for each unit.

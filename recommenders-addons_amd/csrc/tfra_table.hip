@@ -5,7 +5,7 @@
 // reference's CPU table (R/kernels/cuckoo_hashtable_op.cc, lib/cuckoo/cuckoohash_map.hh).
 // Work mapping everywhere: 16 lanes per key (one 128-B bucket line per probe, one 16-B
 // granule per lane per row step), 4 keys per wave64, U independent keys in flight per group.
-// Growth and storage: tfra_grow.hip; the locked upsert / accumulate: tfra_upsert.hip; the slot-window scans: tfra_scan.hip.
+// Growth and storage: tfra_grow.hip; the locked upsert family: tfra_upsert.hip, tfra_find_insert.hip, tfra_accum.hip; the slot-window scans: tfra_scan.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstring>

@@ -21,7 +21,8 @@ fused write-back).
 HIP events around windows of --steps calls, --windows windows per form (alternating) after --warmup calls; one JSON line per shape:
 median, min and max of the windows in us per call for both forms and their spreads.
    python scripts/mb_find_or_insert.py [--slots 8388600] [--grow-slots 16777216] [--steps 20] [--windows 5] [--warmup 5]
-                                       [--what table,train] [--out profiles/find_or_insert_mb.jsonl]"""
+                                       [--what table,train] [--lib PATH] [--tag this-tree]
+                                       [--out profiles/find_or_insert_mb.jsonl]"""
 import argparse
 import json
 import os
@@ -200,10 +201,15 @@ def main():
   ap.add_argument("--windows", type=int, default=5)
   ap.add_argument("--warmup", type=int, default=5)
   ap.add_argument("--what", default="table,train")
+  ap.add_argument("--lib", default=None)
+  ap.add_argument("--tag", default="this tree")
   ap.add_argument("--out", default=None)
   a = ap.parse_args()
   if not torch.cuda.is_available():
     raise SystemExit("mb_find_or_insert: no GPU visible; this is a measurement, it has no CPU form")
+  if a.lib:   # another build of the library (the parent commit's), as mb_insert_and_evict.py takes one
+    from tfra_amd import _capi
+    _capi.LIB_PATH = os.path.abspath(a.lib)
   lines = []
   if "table" in a.what:
     for kind in ("growing", "bounded"):
@@ -214,7 +220,7 @@ def main():
   if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "a") as f:
-      f.write("\n".join(lines) + "\n")
+      f.write("\n".join(json.dumps({"tag": a.tag, **json.loads(l)}) for l in lines) + "\n")
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
 """A field-aware row model of the table, in plain numpy: what every entry point of a table created with `aux_fields = S`
-must leave in the `1 + S` vectors of a key (include/tfra_mi355x.h; make_aux_init, csrc/tfra_table.hip; init_aux_fields, csrc/tfra_upsert.hip).
+must leave in the `1 + S` vectors of a key (include/tfra_mi355x.h; make_aux_init, csrc/tfra_table.hip; init_aux_fields, csrc/tfra_upsert_device.h).
 
 State: key -> array [1 + S, dim] of the table's STORAGE dtype.  bfloat16 has no numpy type: its rows are held as their
 uint16 bit patterns, every other dtype as itself.  All comparisons against the device are made on the rows' bytes.
