@@ -3,7 +3,7 @@
 // (1 without weights) and incoming gradient G[r,:]:
 //   g_e = (G[r] / den_r) * w_e,   den_r = 1 (sum) | sum_{seg = r} w (mean) | sqrt(sum_{seg = r} w^2) (sqrtn)
 // in fp32 and in TF's order: the divide's gradient first, then the multiply's (G / 1 == G exactly, so sum needs no branch).
-// A row whose weight sum is 0 gives g_e = 0, the forward's convention (seg_combine_kernel, tfra_frontend.hip).
+// A row whose weight sum is 0 gives g_e = 0, the forward's convention (seg_combine_kernel, tfra_combine.hip).
 //
 // Every kernel that forms g_e — tfra_sparse_segment_combine_backprop (written out) and the combined write-back of
 // tfra_table_apply_planned_combined (formed in registers from grad_out, tfra_apply_device.h) — reads the same per-entry record and
@@ -51,7 +51,7 @@ __device__ __forceinline__ float comb_den(const float* __restrict__ w, int b, in
   return combiner == 2 ? sqrtf(s) : s;
 }
 
-// ---- the forward's two steps, shared by seg_combine_kernel (tfra_frontend.hip: rows from a [U, dim] tensor) and find_combine_kernel
+// ---- the forward's two steps, shared by seg_combine_kernel (tfra_combine.hip: rows from a [U, dim] tensor) and find_combine_kernel
 // (tfra_pool.hip: rows straight from the table), so that both compile the same expressions and agree bit for bit ------------------
 // one member: acc += v * x
 __device__ __forceinline__ void comb_acc(float& acc, float v, float x) { acc += v * x; }
@@ -84,7 +84,7 @@ __device__ __forceinline__ float4 comb_grad4(float4 g, float den, float w) {
 // W / S is the forward's comb_wsum / comb_wsum_pruned (the same loop); mean / sqrtn with W / S == 0 give 0 for every entry of the
 // row; an entry that is no member (pruned by weight, or in no row) gets exactly 0 and enters neither s nor W / S.
 // ONE evaluation order, for every kernel that forms dw (wgrad_*_kernel in tfra_wgrad.hip: rows straight from the table;
-// seg_combine_wgrad_kernel in tfra_frontend.hip: rows from a [U, dim] tensor), so that the routes agree bit for bit:
+// seg_combine_wgrad_kernel in tfra_combine.hip: rows from a [U, dim] tensor), so that the routes agree bit for bit:
 //   - lane `sub` of the row's 16-lane group holds the columns 64 c + 4 sub .. + 3 of chunk c (find_combine_row's mapping);
 //   - it starts from d = 0 and adds its products G[col] * x[col] one by one, chunks ascending, components x, y, z, w inside a
 //     chunk (wgrad_dot4 / wgrad_dot1); a column at or beyond dim adds nothing (the add is skipped, not fed a zero);
@@ -111,7 +111,7 @@ __device__ __forceinline__ float wgrad_finish(float d, float w, float s, float w
   return (d - (s / wsum) * w) / sqrtf(wsum);
 }
 
-// The bodies of comb_den_kernel / comb_ent_kernel (tfra_frontend.hip), one function each with two callers: the single-table kernels
+// The bodies of comb_den_kernel / comb_ent_kernel (tfra_combine.hip), one function each with two callers: the single-table kernels
 // and the grouped ones (comb_den_many_kernel / comb_ent_many_kernel), which find r / p inside THEIR descriptor
 __device__ __forceinline__ void comb_den_row(size_t r, size_t n_rows, const int* __restrict__ start_end, const float* __restrict__ w,
                                              int combiner, float* __restrict__ den) {
@@ -125,14 +125,14 @@ __device__ __forceinline__ void comb_ent_one(size_t p, size_t nnz, const i64* __
   ent[p] = CombEnt{ok ? (unsigned)s : 0u, ok ? den[s] : 0.f, w ? w[p] : 1.f, 0u};
 }
 
-// The per-entry records of one batch (tfra_frontend.hip): ent[e] = {seg[e], den_{seg[e]}, w_e}; an entry whose row lies outside
+// The per-entry records of one batch (tfra_combine.hip): ent[e] = {seg[e], den_{seg[e]}, w_e}; an entry whose row lies outside
 // [0, n_rows) gets {0, 0, w} (gradient 0, as the forward ignores it).  seg ascending; se: scratch of 2 n_rows ints, den: of
 // n_rows floats.  n_rows >= 1.
 int comb_entries(hipStream_t s, size_t nnz, const int64_t* seg, const float* weights, int combiner, size_t n_rows, int* se,
                  float* den, CombEnt* ent);
 
 // se[r] / se[n_rows + r] = first / one-past-last entry of row r (seg ascending; entries outside [0, n_rows) are in no row; a row
-// without entries: 0, 0).  se: 2 n_rows ints.  A memset and one launch (tfra_frontend.hip).
+// without entries: 0, 0).  se: 2 n_rows ints.  A memset and one launch (tfra_combine.hip).
 int comb_bounds(hipStream_t s, size_t nnz, const int64_t* seg, size_t n_rows, int* se);
 
 }  // namespace tfra

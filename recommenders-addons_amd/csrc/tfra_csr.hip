@@ -59,6 +59,7 @@
 
 #include "../../include/tfra_mi355x.h"
 #include "tfra_device.h"
+#include "tfra_frontend.h"
 #include "tfra_host.h"
 #include "tfra_many.h"
 #include "tfra_plan.h"
@@ -648,7 +649,6 @@ struct PlanLayout {
   unsigned cr, hr, pr, br;
   size_t reg, head, ctr, nrec_c, nrec_h, nbin, npart, bytes;
 };
-static size_t al256(size_t x) { return (x + 255) / 256 * 256; }
 
 static PlanLayout plan_layout(size_t n, int dim) {
   PlanLayout L{};
@@ -660,15 +660,15 @@ static PlanLayout plan_layout(size_t n, int dim) {
   L.P = P;
   L.cm = ntiles <= 256 ? 512u : 1024u;   // a key present in every tile must fit one pass with room to spare
   L.reg = (size_t)P * CMAX;
-  L.head = al256((size_t)(P + 2) * CSTRIDE * 4);
-  L.ctr = al256((size_t)(NSH + 1) * CTR_STRIDE * 8);
+  L.head = align_up((size_t)(P + 2) * CSTRIDE * 4);
+  L.ctr = align_up((size_t)(NSH + 1) * CTR_STRIDE * 8);
   // per-shard capacities: twice the fair share + slack; bins / partial rows also cover ONE key holding every id
   L.cr = (unsigned)(2 * npad / NSH + 64);
   L.hr = (unsigned)(2 * (npad / 9) / NSH + 64);
   L.pr = (unsigned)(npad / SEG + 2 * (npad / 9) / NSH + 64);
   L.br = (unsigned)(npad / SEG + (npad / 16 + npad / 9) / NSH / 16 + 2 * (P / NSH + 1) + 32);
   L.nrec_c = (size_t)NSH * L.cr; L.nrec_h = (size_t)NSH * L.hr; L.nbin = (size_t)NSH * L.br; L.npart = (size_t)NSH * L.pr;
-  const auto al = al256;
+  const auto al = [](size_t x) { return align_up(x); };
   L.bytes = L.head + L.ctr + PC_WORDS * 4                                              // cursors, counters, d_counts
             + al(L.reg * 8) + al(L.reg * 4) + al(npad * 8) + 2 * al(npad * 4)          // descriptors + overflow list
             + al(npad * 4) + al(npad * 2) + al(ntiles * 4) + al(npad * 16)             // tile lists, run starts, lengths, destinations
@@ -697,7 +697,7 @@ static int plan_grow(tfra_sparse_plan* pl, const PlanLayout& L) {
 }
 
 static int plan_lay_out(tfra_sparse_plan* pl, const PlanLayout& L, hipStream_t s) {
-  const auto al = al256;
+  const auto al = [](size_t x) { return align_up(x); };
   const size_t npad = L.npad;
   CsrOut& o = pl->out;
   o.cr = L.cr; o.hr = L.hr; o.pr = L.pr; o.br = L.br;

@@ -1,5 +1,5 @@
 // What the grouped calls share (tfra_multi_find_combine: tfra_pool.hip; tfra_multi_apply_planned_combined: tfra_apply_many.hip, with
-// its entry-record kernels in tfra_frontend.hip; tfra_multi_sparse_plan_build: tfra_csr.hip).
+// its entry-record kernels in tfra_combine.hip; tfra_multi_sparse_plan_build: tfra_csr.hip).
 // Device side: the search that takes a block to its descriptor and the records of the launches that run in more than one unit.
 // Host side, the frame of a grouped call: the outcome of an operation's argument checks (Check: each operation's checks are ONE
 // function, which its single-table call and its grouped call both run), the tables' locks (lock_and_enter), the layout of the
@@ -43,7 +43,7 @@ struct BoundsRec {
 // grid = prefix[n]; recs / prefix in device memory
 int comb_bounds_many(hipStream_t s, unsigned grid, const BoundsRec* recs, const unsigned* prefix, unsigned n);
 
-// comb_den_many_kernel / comb_ent_many_kernel (tfra_frontend.hip): one descriptor's denominators (ceil(n_rows / 256) blocks) and
+// comb_den_many_kernel / comb_ent_many_kernel (tfra_combine.hip): one descriptor's denominators (ceil(n_rows / 256) blocks) and
 // per-entry records (ceil(nnz / 256) blocks), what comb_entries makes for one table
 struct CombManyRec {
   const i64* seg;

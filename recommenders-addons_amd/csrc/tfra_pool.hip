@@ -5,7 +5,7 @@
 //   gather(idx) * weights, segment_sum, / sum w | / sqrt(sum w^2)   :233-291   (a [nnz, dim] tensor between them)
 // A read needs no de-duplication (repeats of a hot id hit the cache), so here one 16-lane group per OUTPUT ROW walks the row's
 // entries in input order, probes the table once per entry and accumulates w * row in registers: neither tensor exists and
-// nothing is counted on the host.  The arithmetic is tfra_combine_device.h's, the code seg_combine_kernel (tfra_frontend.hip)
+// nothing is counted on the host.  The arithmetic is tfra_combine_device.h's, the code seg_combine_kernel (tfra_combine.hip)
 // compiles, in the same order, so the result equals tfra_table_find + tfra_sparse_segment_combine bit for bit.
 // tfra_multi_find_combine is the same lookup for a list of tables; its host side stands on the grouped-call frame of tfra_many.h,
 // and both calls run ONE function for their argument checks (check_find_combine) and one launch ladder (with_pool_class); those
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(256) void find_combine_ragged_many_kernel(const Rag
                                            RaggedArgs{rec.row_splits, rec.nnz, rec.flags, rec.fill_id});
 }
 
-// seg64_bounds_kernel (tfra_frontend.hip) over a list: descriptor d owns ceil(nnz / 256) blocks and p counts ITS entries, so the
+// seg64_bounds_kernel (tfra_combine.hip) over a list: descriptor d owns ceil(nnz / 256) blocks and p counts ITS entries, so the
 // neighbours p - 1 / p + 1 are never read across a descriptor's end.  se zeroed before (empty rows: 0, 0).
 __global__ __launch_bounds__(256) void seg64_bounds_many_kernel(const BoundsRec* __restrict__ recs, const unsigned* __restrict__ prefix,
                                                                 unsigned n) {

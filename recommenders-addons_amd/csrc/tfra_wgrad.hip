@@ -4,7 +4,7 @@
 // the forward's shape (find_combine_row, tfra_pool.hip): one 16-lane group per OUTPUT ROW, one probe and one row read per entry, the
 // row's incoming gradient held in registers where the forward holds its accumulator, and [nnz] floats out.
 // The arithmetic and its ONE evaluation order are tfra_combine_device.h's (wgrad_dot4, wgrad_reduce16, wgrad_s, wgrad_finish), the
-// code seg_combine_wgrad_kernel (tfra_frontend.hip: rows from a [U, dim] tensor) compiles, so the two routes agree bit for bit.
+// code seg_combine_wgrad_kernel (tfra_combine.hip: rows from a [U, dim] tensor) compiles, so the two routes agree bit for bit.
 // The argument checks and the launch ladders are the forward's (tfra_pool.h).
 #include <hip/hip_runtime.h>
 

@@ -589,6 +589,42 @@ def test_unique_many_calls_one_workspace(env):
     np.testing.assert_array_equal(want[idx.cpu().numpy()], ids)
 
 
+def _zipf_ids_hot_and_sentinel(rng, n):
+  """The stream of test_unique_many_calls_one_workspace: Zipf ids under a modulus of n // 2, int64.min (the scratch sets' sentinel
+  value, which both implementations keep in a side slot) at n // 40 positions, one hot id over [n // 3, n // 2)."""
+  ids = (rng.zipf(1.2, size=n) % max(2, n // 2)).astype(np.int64) * 7919 - 11
+  ids[rng.integers(0, n, size=n // 40)] = np.iinfo(np.int64).min
+  ids[n // 3: n // 2] = 5
+  return ids
+
+
+def _check_tf_unique(torch, de, ids):
+  from oracle import frontends as ofe
+  u, idx, cnt = de.device_ops.unique(torch.from_numpy(ids).cuda())
+  eu, eidx = ofe.unique(ids)
+  assert int(cnt.item()) == eu.size
+  np.testing.assert_array_equal(u.cpu().numpy(), eu)
+  np.testing.assert_array_equal(idx.cpu().numpy(), eidx)
+
+
+@pytest.mark.parametrize("n", [1 << 20, (1 << 20) + 1])
+def test_unique_at_the_path_switch(env, n):
+  """tfra_unique changes implementation at 2^20 ids.  2^20 is the largest call of the three-launch path: its look-back runs over
+  the largest legal grid, 1024 tiles.  2^20 + 1 is the smallest call of the six-launch path (fill, insert, count, scan, scatter,
+  idx over the workspace's scratch).  Both against tf.unique, bit for bit."""
+  torch, de, SparsePlan = env
+  _check_tf_unique(torch, de, _zipf_ids_hot_and_sentinel(np.random.default_rng(n), n))
+
+
+def test_unique_six_launch_call_between_fast_calls(env):
+  """One workspace: a three-launch call, a six-launch call (it works in the workspace's scratch, not in the two persistent sets),
+  a three-launch call again — the sets are as usable after the call in between as before it."""
+  torch, de, SparsePlan = env
+  rng = np.random.default_rng(29)
+  for n in (131_072, (1 << 20) + 1, 131_072):
+    _check_tf_unique(torch, de, _zipf_ids_hot_and_sentinel(rng, n))
+
+
 def test_unique_unordered_matches_numpy_as_a_set(env):
   """tfra_unique_unordered: the distinct ids in ANY order + a consistent inverse index (what embedding_lookup needs of tf.unique);
   a sequence of calls on one workspace with sizes going up and down, the sentinel values and a hot id."""
