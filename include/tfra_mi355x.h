@@ -198,6 +198,51 @@ int tfra_table_find_or_insert(tfra_table_t* t, size_t n, const int64_t* d_n, con
                               const void* init_values, int init_is_full, const uint64_t* scores,
                               void* values_out, uint8_t* found, tfra_stream_t stream);
 
+/* -- The read side of a tier: a table that stands in front of something slower (insert_and_evict above is its write side).
+ *    All three calls: d_n is NULL, or the key count as in tfra_table_find_n (a device int64, or pinned host memory the device
+ *    can read): min(n, *d_n) keys are served, a negative count means 0, and entries of the outputs beyond the count are left
+ *    as they are.  Refused before anything is enqueued, tfra_last_error() naming the function: a NULL table, NULL keys, NULL
+ *    exists for contains, NULL values for assign, NULL defaults with non-NULL values, n >= 2^31 (TFRA_ERR_INVALID).  n == 0:
+ *    TFRA_OK, nothing touched.  They synchronise nothing, never grow the table, and are usable under
+ *    TFRA_OPTION_CAPTURE_SAFE as tfra_table_find is.  (tests/test_gpu_find_missed.py, test_gpu_assign.py, test_gpu_tier_loop.py)
+ *
+ *    find_missed (HierarchicalKV's find(n, keys, values, missed_keys, missed_indices, missed_size, scores)): tfra_table_find that
+ *    also lists its misses.  values and exists are byte for byte what tfra_table_find writes for the same arguments (the
+ *    embedding field, duplicate keys, one default row or [n, dim] defaults, every value dtype and dim); it never inserts and
+ *    never writes the table, an LRU score is not touched.  values may be NULL: the call lists misses only, defaults is not
+ *    read.  scores_out: NULL or [n]; a hit's entry is the uint64 tfra_table_export_batch would report for that key now (a table
+ *    without scores: 0; a reserved key: ~0), a miss's is 0.
+ *    Reported: every missed batch position i is appended at *d_missed_counter as the pair (keys[i], (int32_t)i); a missing key
+ *    that repeats is reported at every one of its positions, unique keys give a unique list.  The two arrays are
+ *    index-aligned; the order is unspecified.  Counter and cap are tfra_table_export_batch_if's: the counter (device size_t,
+ *    the caller zeroes it, the call continues from its value) advances by every miss whatever cap is; a pair whose position is
+ *    >= cap is not written, key and index alike; cap = n always suffices from a zeroed counter.  missed_keys and
+ *    missed_indices may each be NULL (both: count only).  d_missed_counter == NULL requires both NULL (else TFRA_ERR_INVALID):
+ *    the call is then find plus scores.
+ *    *d_missed_counter is 8 bytes: it can be handed unchanged as d_n to tfra_table_find_n, tfra_table_insert_or_assign_n or
+ *    tfra_table_find_or_insert on another table (the lower tier), with missed_keys as their keys — no host read in between.
+ *    The counter takes ONE atomic add per block of the launch that has a miss, not one per miss.
+ *
+ *    assign (HierarchicalKV's assign): a write that only hits.  keys: unique within the call (what TFRA_FLAG_UNIQUE_KEYS names;
+ *    with repeats the row a repeated key ends with is unspecified).  A resident key gets values[i] in its embedding field, its
+ *    score is touched exactly as tfra_table_insert_or_assign touches it on an assign (scores ? scores[i] : 1), its slot vectors
+ *    are not written, found[i] = 1.  A key that is not resident changes nothing — it is not claimed, not evicted for, not
+ *    counted in tfra_table_check_errors — and found[i] = 0: the caller sends it to the tier that holds it.  The size and the
+ *    slot census are unchanged; the epoch steps once per call, as for insert_or_assign.  Both reserved keys are served.
+ *    found may be NULL.
+ *
+ *    contains (HierarchicalKV's contains): exists[i] is tfra_table_find's byte; one probe per key, no row is read, nothing is
+ *    written.                                                                                                               */
+int tfra_table_find_missed(tfra_table_t* t, size_t n, const int64_t* d_n, const int64_t* keys,
+                           void* values, uint8_t* exists, uint64_t* scores_out,
+                           const void* defaults, int default_is_full,
+                           size_t* d_missed_counter, size_t cap, int64_t* missed_keys, int32_t* missed_indices,
+                           tfra_stream_t stream);
+int tfra_table_assign(tfra_table_t* t, size_t n, const int64_t* d_n, const int64_t* keys, const void* values,
+                      const uint64_t* scores, uint8_t* found, tfra_stream_t stream);
+int tfra_table_contains(tfra_table_t* t, size_t n, const int64_t* d_n, const int64_t* keys, uint8_t* exists,
+                        tfra_stream_t stream);
+
 /* -- accum_or_assign = TableWrapper::accum (lookup_table_op_hkv.h:539-546):
  *    absent & !exists -> insert row; present & exists -> row += delta (element order 0..dim-1,
  *    one add each); otherwise no-op.  Oracle: accumrase_fn (lib/cuckoo/cuckoohash_map.hh:619). */

@@ -545,15 +545,30 @@ __device__ __forceinline__ void copy_bytes16_wt(unsigned char* dst, const unsign
   }
 }
 
-// ---- find: the work of ONE wave (16 keys: 4 per 16-lane group), shared by find_kernel (tfra_table.hip) and the launch that runs
-// the lookup next to the de-duplication of the same ids (find_unique_kernel, tfra_setplan.hip) -------------------------------------
+// ---- find: the work of ONE wave (16 keys: 4 per 16-lane group), shared by find_kernel (tfra_table.hip), the launch that runs
+// the lookup next to the de-duplication of the same ids (find_unique_kernel, tfra_setplan.hip) and the tier calls (tfra_tier.hip) --
 // PF1: also put the SECOND home bucket's line of every key in flight with the first (a bounded table running
 // near capacity: most b0 lines are full and flagged, ~1/3 of the resident keys and every miss need b1, and on
 // a loaded memory round trip is ~2 us — two in flight beat two in a row).
-template <int G, int U, bool WT, bool PF1>
+// X: what a caller wants beyond rows and exists.  FindOnly (empty; find_kernel, find_unique_kernel): nothing, and nothing of the
+// rest is compiled.  The tier calls hand in one of:
+//   TierMissed   find_missed: `out` may be null (no row is read then); x->scores_out (may be null) gets a hit's score as
+//                export_batch reports it (no score line: 0; a side row: ~0) and 0 for a miss; x->miss = the wave's misses, bit j =
+//                key base + j (positions beyond n are never set).  The caller appends them: no store of the list is in here.
+//   TierAssign   assign: the rows go the OTHER way — values[i] (`defaults`, full) into the row of a hit, nothing for a miss — and
+//                a hit's score is touched as insert_or_assign touches it on an assign.  Unique keys: plain stores.
+//   TierContains contains: the probe and the exists byte, nothing else.
+enum { FIND_ONLY = 0, TIER_MISSED = 1, TIER_ASSIGN = 2, TIER_CONTAINS = 3 };
+struct FindOnly { static constexpr int mode = FIND_ONLY; };
+struct TierMissed { static constexpr int mode = TIER_MISSED; u64* scores_out; unsigned miss; };
+struct TierAssign { static constexpr int mode = TIER_ASSIGN; const u64* scores; int strategy; u64 epoch; };
+struct TierContains { static constexpr int mode = TIER_CONTAINS; };
+
+template <int G, int U, bool WT, bool PF1, class X = FindOnly>
 __device__ __forceinline__ void find_wave(const TableView& v, size_t n, const i64* __restrict__ keys, unsigned char* __restrict__ out,
                                           uint8_t* __restrict__ exists, const unsigned char* __restrict__ defaults, int full,
-                                          unsigned field_off, const unsigned wave) {
+                                          unsigned field_off, const unsigned wave, X* x = nullptr) {
+  constexpr int M = X::mode;
   const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
   const int grp = lane >> 4;
   constexpr int KPW = 4 * U;
@@ -588,13 +603,53 @@ __device__ __forceinline__ void find_wave(const TableView& v, size_t n, const i6
   if (PF1) keep_live(k1[0], k1[1], k1[2], k1[3]);
   const unsigned char* src[U];
   unsigned char* dst[U];
+  [[maybe_unused]] i64 wd[U];   // (tier calls) the word index of key u, -1 = absent
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const i64 word = probe_find_word(v, key[u], b0[u], b1[u], k0[u], sub, gshift, PF1 ? &k1[u] : nullptr);
     if (exists && sub == 0) exists[idx[u]] = word >= 0;
-    src[u] = word >= 0 ? word_row_ptr(v, (u64)word) + field_off
-                       : defaults + (full ? (u64)idx[u] * (u64)v.field_bytes : 0);
-    dst[u] = out + (u64)idx[u] * (u64)v.field_bytes;
+    if constexpr (M == TIER_ASSIGN) {
+      src[u] = defaults + (u64)idx[u] * (u64)v.field_bytes;
+      dst[u] = word >= 0 ? word_row_ptr(v, (u64)word) + field_off : nullptr;
+    } else {
+      src[u] = word >= 0 ? word_row_ptr(v, (u64)word) + field_off
+                         : defaults + (full ? (u64)idx[u] * (u64)v.field_bytes : 0);
+      dst[u] = out + (u64)idx[u] * (u64)v.field_bytes;
+    }
+    if constexpr (M != FIND_ONLY) wd[u] = word;
+  }
+  if constexpr (M == TIER_CONTAINS) return;
+  if constexpr (M == TIER_MISSED) {
+    // the wave's miss mask: group grp's lane 0 votes for key u*4 + grp (a clamped tail position does not count)
+    unsigned miss = 0;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const u64 m = __ballot(sub == 0 && wd[u] < 0 && base + (unsigned)(u * 4 + grp) <= last);
+      miss |= ((unsigned)(m & 1) | ((unsigned)(m >> 15) & 2u) | ((unsigned)(m >> 30) & 4u) | ((unsigned)(m >> 45) & 8u)) << (u * 4);
+    }
+    x->miss = miss;
+    if (x->scores_out) {   // (uniform)  U score words in flight; a miss reads its first home bucket's, which is always there
+      i64 sc[U];
+      const bool scored = has_scores(v);
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const bool slot = wd[u] >= 0 && (u64)wd[u] < v.nb * 16;
+        sc[u] = scored ? (i64)*(slot ? score_word(v, (u64)wd[u]) : score_line(v, b0[u])) : 0;
+      }
+      keep_live(sc[0], sc[1], sc[2], sc[3]);
+#pragma unroll
+      for (int u = 0; u < U; ++u)   // clamped tail: the same value twice
+        if (sub == 0) x->scores_out[idx[u]] = wd[u] < 0 ? 0 : ((u64)wd[u] < v.nb * 16 ? (u64)sc[u] : ~0ULL);
+    }
+    if (!out) return;   // list the misses only
+  }
+  if constexpr (M == TIER_ASSIGN) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {   // a clamped tail position must not touch the score a second time
+      if (wd[u] < 0 || base + (unsigned)(u * 4 + grp) > last) continue;
+      const i64 row = (i64)(((u64)wd[u] >> 4) * SLOTS + ((u64)wd[u] & 15));   // (side rows: >= nb * 15, no score)
+      update_score(v, row, false, x->strategy, x->scores ? x->scores[idx[u]] : 1, x->epoch, sub);
+    }
   }
   typedef typename Granule<G>::T T;
   for (unsigned off = sub * G; off < v.field_bytes; off += 16 * G) {
@@ -604,6 +659,7 @@ __device__ __forceinline__ void find_wave(const TableView& v, size_t n, const i6
     keep_live(tmp[0], tmp[1], tmp[2], tmp[3]);
 #pragma unroll
     for (int u = 0; u < U; ++u) {  // clamped tail: same bytes twice
+      if constexpr (M == TIER_ASSIGN) { if (!dst[u]) continue; }
       if (G == 16 && WT) store_wt16(dst[u] + off, *reinterpret_cast<uint4*>(&tmp[u]));
       else *reinterpret_cast<T*>(dst[u] + off) = tmp[u];
     }

@@ -143,6 +143,9 @@ _SIGS = {
     "tfra_table_insert_and_evict": [_P, _SZ, _P, _P, _P, ctypes.c_uint32, _P, _SZ, _P, _P, _P, _P],
     "tfra_table_find_or_insert": [_P, _SZ, _P, _P, _P, _I, _P, _P, _P, _P],
     "tfra_table_find_or_insert_planned": [_P, _P, _P, _I, _P, _P, _P, _P],
+    "tfra_table_find_missed": [_P, _SZ, _P, _P, _P, _P, _P, _P, _I, _P, _SZ, _P, _P, _P],
+    "tfra_table_assign": [_P, _SZ, _P, _P, _P, _P, _P, _P],
+    "tfra_table_contains": [_P, _SZ, _P, _P, _P, _P],
     "tfra_table_find_n": [_P, _SZ, _P, _P, _P, _P, _P, ctypes.c_int, _P],
     "tfra_table_insert_or_assign_n": [_P, _SZ, _P, _P, _P, _P, _P],
     "tfra_table_insert_field": [_P, _I, _SZ, _P, _P, ctypes.c_uint32, _P],

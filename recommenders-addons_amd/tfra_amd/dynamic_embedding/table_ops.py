@@ -504,6 +504,73 @@ class _DeviceTable:
       plan._mark_used(stream)
     return (out, exists) if return_exists else out
 
+  # ---- the read side of a tier: find that lists its misses, a write that only hits, membership ----
+  def find_missed(self, keys, dynamic_default_values=None, return_exists=False, return_scores=False, count=None, cap=None,
+                  sync=True):
+    """`find` that also lists its misses (tfra_table_find_missed): rows (and exists) are `find`'s; every batch position whose key is
+    not resident is reported as a pair (key, position), in no particular order.  -> (rows, missed_keys, missed_indices[, exists]
+    [, scores]) with the two lists trimmed to their count: ONE host read of the counter.  missed_indices is int32; scores [n]
+    int64 holds what `export_all(with_scores=True)` reports for a hit and 0 for a miss.  count: a device int64 (or pinned) count
+    of the leading keys that are served.  cap: room in the lists (default: one pair per key, which always suffices); the count
+    goes on beyond it, pairs beyond it are not written.
+    sync=False: (rows, counter, missed_keys, missed_indices, ...) with `counter` a device int64 tensor of shape [1] and the lists
+    untrimmed (the keys stay int64) — nothing is read on the host, and `counter` can be the `count` of the next call on another
+    table: find_n, upsert_n, find_or_insert."""
+    keys = self._keys(keys)
+    n = keys.numel()
+    d = self._default_value if dynamic_default_values is None else dynamic_default_values
+    d = torch.as_tensor(d, device=self._device) if not torch.is_tensor(d) else d.to(self._device)
+    if d.dtype != self._value_dtype:
+      raise TypeError("default values must be dtype %s, got %s" % (self._value_dtype, d.dtype))
+    d = d.contiguous()
+    out = torch.empty(tuple(keys.shape) + (self._dim,), dtype=self._value_dtype, device=self._device)
+    full = int(out.numel() == d.numel())
+    if not full and d.numel() < self._dim:
+      raise ValueError("default value needs at least dim=%d elements, got %d" % (self._dim, d.numel()))
+    cap = n if cap is None else int(cap)
+    if cap < 0:
+      raise ValueError("cap must be >= 0, got %d" % cap)
+    exists = torch.zeros(keys.shape, dtype=torch.bool, device=self._device) if return_exists else None
+    scores = torch.zeros(keys.shape, dtype=torch.int64, device=self._device) if return_scores else None
+    counter = torch.zeros(1, dtype=torch.int64, device=self._device)
+    mk = torch.empty(cap, dtype=torch.int64, device=self._device)
+    mi = torch.empty(cap, dtype=torch.int32, device=self._device)
+    if n:
+      _capi.call("tfra_table_find_missed", self._h, n, _ptr(count), _ptr(keys), _ptr(out), _ptr(exists), _ptr(scores), _ptr(d), full,
+                 _ptr(counter), cap, _ptr(mk), _ptr(mi), _stream(self._device))
+    extra = ((exists,) if return_exists else ()) + ((scores,) if return_scores else ())
+    if not sync:
+      return (out, counter, mk, mi) + extra   # (the keys stay int64 here: narrowing the unwritten tail would read it)
+    m = min(int(counter.item()), cap)
+    return (out, _narrow_keys(mk[:m], self._key_dtype), mi[:m]) + extra
+
+  def assign(self, keys, values, scores=None, return_found=False, count=None):
+    """The write that only hits (tfra_table_assign): a resident key gets its row of `values` and its score is touched as `upsert`
+    touches it; a key that is not resident changes nothing — it is not inserted, nothing is evicted for it.  `keys` are UNIQUE.
+    count: a device int64 (or pinned) count of the leading keys that are served.  -> None, or found [n] bool (return_found)."""
+    keys = self._keys(keys)
+    values = self._values_for(keys, values)
+    n = keys.numel()
+    if scores is not None and scores.numel() == 0:
+      scores = None
+    if scores is not None:
+      scores = scores.to(self._device, torch.int64).contiguous()
+      if scores.numel() != n:
+        raise ValueError("scores must have one entry per key")
+    found = torch.zeros(keys.shape, dtype=torch.bool, device=self._device) if return_found else None
+    if n:
+      _capi.call("tfra_table_assign", self._h, n, _ptr(count), _ptr(keys), _ptr(values), _ptr(scores), _ptr(found),
+                 _stream(self._device))
+    return found
+
+  def contains(self, keys, count=None):
+    """exists of `find` without reading a row (tfra_table_contains) -> bool tensor shaped like keys."""
+    keys = self._keys(keys)
+    exists = torch.zeros(keys.shape, dtype=torch.bool, device=self._device)
+    if keys.numel():
+      _capi.call("tfra_table_contains", self._h, keys.numel(), _ptr(count), _ptr(keys), _ptr(exists), _stream(self._device))
+    return exists
+
   def find_n(self, keys, count, out=None, return_exists=False):
     """find over the first `count[0]` entries of the buffer `keys`, the count read ON THE DEVICE (`count`: an int64 tensor on the
     table's device, or pinned host memory): tfra_table_find_n.  Rows beyond the count are left as they are."""
@@ -930,6 +997,22 @@ class _LookupInterfaceMirror:
     return self._table.find_or_insert_planned(plan, dynamic_default_values, scores=self._gen_scores(plan.ids),
                                               return_exists=return_exists)
 
+  def lookup_missed(self, keys, dynamic_default_values=None, name=None):
+    """`lookup` that also lists its misses (HierarchicalKV's find with missed_keys / missed_indices): -> (rows, missed_keys,
+    missed_indices), the pairs (key, batch position) of the keys that are not resident, in no particular order
+    (`_DeviceTable.find_missed`).  Never inserts; an LRU score is not touched."""
+    return self._table.find_missed(keys, dynamic_default_values)
+
+  def assign(self, keys, values, name=None):
+    """HierarchicalKV's assign: `insert` for the keys that are resident, nothing for the others (they are not inserted and
+    nothing is evicted for them).  Keys must be unique.  Scores follow `insert`'s rule."""
+    keys = torch.as_tensor(keys, device=self._device) if not torch.is_tensor(keys) else keys
+    self._table.assign(keys, values, scores=self._gen_scores(keys))
+
+  def contains(self, keys, name=None):
+    """HierarchicalKV's contains: a bool tensor, True where the key is resident.  No row is read."""
+    return self._table.contains(keys)
+
   def _gen_scores(self, keys):   # tables without scores
     return None
 
@@ -1057,6 +1140,12 @@ class HkvHashTable(_LookupInterfaceMirror):
     did not admit (HierarchicalKV's insert_and_evict).  scores: as the engine takes them; None = gen_scores_fn / the strategy's."""
     keys = torch.as_tensor(keys, device=self._device) if not torch.is_tensor(keys) else keys
     return self._table.upsert_and_evict(keys, values, scores=self._gen_scores(keys) if scores is None else scores)
+
+  def assign(self, keys, values, scores=None, name=None):
+    """HierarchicalKV's assign: the resident keys get their rows and their scores are touched as `insert` touches them; the
+    others change nothing.  scores: as the engine takes them; None = gen_scores_fn / the strategy's."""
+    keys = torch.as_tensor(keys, device=self._device) if not torch.is_tensor(keys) else keys
+    self._table.assign(keys, values, scores=self._gen_scores(keys) if scores is None else scores)
 
   def accum(self, keys, values_or_deltas, exists, name=None):
     """PY/hkv_hashtable_ops.py:369-402"""

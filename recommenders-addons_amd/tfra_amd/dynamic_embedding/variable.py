@@ -320,6 +320,64 @@ class Variable:
     v = v.reshape(tuple(keys.shape) + (self.dim,))
     return (v, e.reshape(keys.shape)) if return_exists else v
 
+  # ---- the read side of a tier (tables in front of something slower) ---------------------------
+  def _scatter_flags(self, parts, perm, shape):
+    """Per-shard bool vectors (owner-major order) back in batch order, as `lookup` returns its exists."""
+    if perm is None:
+      return parts[0].reshape(shape)
+    return device_ops.scatter_rows(torch.cat(parts, 0).reshape(-1, 1).to(torch.uint8), perm).reshape(-1).to(torch.bool).reshape(shape)
+
+  def lookup_missed(self, keys, return_exists=False, name=None):
+    """`lookup` that also lists its misses (find_missed per shard) -> (rows, missed_keys, missed_positions[, exists]): the keys
+    that are not resident and their positions in the flattened batch (int64, index-aligned, in no particular order; a missing
+    key that repeats is listed at every position).  Never inserts.  A callable initializer draws the defaults per shard, as
+    `lookup` does.  A shard reports positions in its slice of the owner-major key list; they are mapped back through the
+    partition's permutation (owner_major = flat[perm])."""
+    keys = torch.as_tensor(keys, device=self._primary)
+    kp, perm, counts = self._partition(keys)
+    vals, exs, mks, mps = [], [], [], []
+    off = 0
+    for i, t in enumerate(self._tables):
+      k = kp[i].to(t._device)
+      dd = self._create_default_values_by_initializer(k.numel(), t._device)
+      r = t.resource_handle.find_missed(k, dd, return_exists=return_exists)
+      vals.append(r[0].to(self._primary))
+      mks.append(r[1].to(self._primary))
+      pos = r[2].to(self._primary).to(torch.int64)
+      mps.append(pos if perm is None else perm[off + pos].to(torch.int64))
+      if return_exists:
+        exs.append(r[3].to(self._primary))
+      off += counts[i]
+    v = vals[0] if perm is None else device_ops.scatter_rows(torch.cat(vals, 0), perm)
+    v = v.reshape(tuple(keys.shape) + (self.dim,))
+    out = (v, torch.cat(mks, 0), torch.cat(mps, 0))
+    return out + (self._scatter_flags(exs, perm, keys.shape),) if return_exists else out
+
+  def assign(self, keys, values, return_found=False, name=None):
+    """`upsert` for the keys that are resident; the others change nothing — they are not inserted and nothing is evicted for them
+    (assign per shard).  `keys` must be UNIQUE.  -> None, or found (bool, shaped like keys): False = send the row to the tier
+    that holds the key.  `size()` never changes."""
+    keys = torch.as_tensor(keys, device=self._primary)
+    values = torch.as_tensor(values, device=self._primary)
+    want = tuple(keys.shape) + (self.dim,)
+    if tuple(values.shape) != want:
+      raise ValueError("Expected shape %s for values, got %s" % (list(want), list(values.shape)))
+    kp, perm, counts = self._partition(keys)
+    vp = self._split_rows(values.reshape(-1, self.dim), perm, counts)
+    fs = []
+    for i, t in enumerate(self._tables):
+      k = kp[i].to(t._device)
+      f = t.resource_handle.assign(k, vp[i].to(t._device), scores=t._gen_scores(k), return_found=return_found)
+      if return_found:
+        fs.append(f.to(self._primary))
+    return self._scatter_flags(fs, perm, keys.shape) if return_found else None
+
+  def contains(self, keys, name=None):
+    """A bool tensor shaped like keys: True where the key is resident (contains per shard; no row is read)."""
+    keys = torch.as_tensor(keys, device=self._primary)
+    kp, perm, _ = self._partition(keys)
+    return self._scatter_flags([t.contains(kp[i].to(t._device)).to(self._primary) for i, t in enumerate(self._tables)], perm, keys.shape)
+
   def can_lookup_combined(self):
     """Whether `lookup_combined` serves this variable: one shard, a static default row (no callable initializer), float32 /
     float16 / bfloat16 rows with dim % 4 == 0 and dim <= 256 — the conditions of the planned write-back (`can_plan`)."""
