@@ -65,7 +65,7 @@ typedef struct {
   uint64_t init_capacity;         /* attr init_capacity / init_size; 0 -> 1 Mi
                                      (hkv_hashtable_op_gpu.cu.cc:53) or 8192 for cuckoo flavour */
   uint64_t max_capacity;          /* attr max_capacity; 0 = unbounded (libcuckoo flavour)   */
-  uint64_t max_hbm_for_vectors;   /* accepted for attr parity; this engine is pure-HBM       */
+  uint64_t max_hbm_for_vectors;   /* accepted for attr parity and ignored; two tiers: tfra_tier_* */
   float max_load_factor;          /* growth trigger; 0 -> 0.5 like lookup_table_op_hkv.h:449
                                      when max_capacity>0, 0.75 for the unbounded flavour     */
   int32_t strategy;               /* tfra_evict_strategy                                     */
@@ -242,6 +242,71 @@ int tfra_table_assign(tfra_table_t* t, size_t n, const int64_t* d_n, const int64
                       const uint64_t* scores, uint8_t* found, tfra_stream_t stream);
 int tfra_table_contains(tfra_table_t* t, size_t n, const int64_t* d_n, const int64_t* keys, uint8_t* exists,
                         tfra_stream_t stream);
+
+/* -- insert_and_evict_n: tfra_table_insert_and_evict with the key count on the device and, on request, whole rows in.
+ *    The contract is tfra_table_insert_and_evict's over min(n, *d_n) keys.  d_n is as in tfra_table_find_n (NULL: n; a negative
+ *    count: 0): nothing beyond the count is read as a key or written, scratch and growth are sized by n.  The call always takes
+ *    the locked two-phase kernels; off max_capacity it displaces nothing and leaves the counter alone, like its parent.
+ *    flags: TFRA_EVICT_WHOLE_ROWS as above, and TFRA_INSERT_WHOLE_ROWS — `values` rows are (1 + aux_fields) * dim elements, the
+ *    embedding, then the slot vectors, as stored.  The slot vectors are then written from the caller's row in every case (a key
+ *    that takes an empty slot, a key that replaces a victim, a key that was already resident) and aux_init is not applied; under
+ *    TFRA_EVICT_WHOLE_ROWS a key that is not admitted is reported with the caller's whole row.  Without the flag the bytes
+ *    written are exactly tfra_table_insert_and_evict's.  Unknown bits: TFRA_ERR_INVALID.
+ *    Refused before anything is enqueued, tfra_last_error() naming the function: the parent's cases.
+ *    (tests/test_gpu_insert_and_evict_n.py)                                                                                   */
+#define TFRA_INSERT_WHOLE_ROWS 2u
+int tfra_table_insert_and_evict_n(tfra_table_t* t, size_t n, const int64_t* d_n, const int64_t* keys, const void* values,
+                                  const uint64_t* scores, uint32_t flags, size_t* d_evicted_counter, size_t cap,
+                                  int64_t* evicted_keys, void* evicted_values, uint64_t* evicted_scores, tfra_stream_t stream);
+
+/* -- The tier driver: `upper`, a bounded LRU / EPOCHLRU table (a cache in HBM), in front of `lower`, a TFRA_EVICT_NONE table that
+ *    holds everything.  Every call is ONE stream-ordered chain of launches on both tables with no host read, and moves WHOLE
+ *    co-located rows between them: a key that is demoted and later promoted comes back with its slot vectors.
+ *    The invariant, after every call, for every key ever written through the tier: if upper contains it, upper holds its newest
+ *    whole row; otherwise lower holds it.  The tier is inclusive: a promoted key keeps a stale copy below, upper wins, a demotion
+ *    overwrites the stale copy.  (Writes that go to either table directly are the caller's to keep consistent with this.)
+ *    create refuses, naming itself: tables that differ in device, value dtype, dim or aux_fields, upper == lower, max_batch == 0
+ *    or >= 2^31 (TFRA_ERR_INVALID); an upper strategy other than LRU / EPOCHLRU — every key must be admitted — and a lower
+ *    strategy other than TFRA_EVICT_NONE — the bottom must not forget — (TFRA_ERR_UNSUPPORTED).  The driver owns staging for
+ *    max_batch keys; it must be destroyed before its tables (destroy waits for the device).
+ *    All calls: d_n as in tfra_table_find_n; n > max_batch, a NULL tier or a NULL required buffer: TFRA_ERR_INVALID naming the
+ *    function, nothing enqueued; n == 0: TFRA_OK, nothing touched.  Both tables are locked as the grouped calls lock several
+ *    tables (one global order), so a tier call and a plain call on either table from another thread do not deadlock.
+ *
+ *    tfra_tier_find: a read.  Duplicates are served at every position, nothing moves, nothing is written to either table, no score
+ *    is touched.  values[i] = the row upper holds, else the row lower holds, else the default (defaults / default_is_full as in
+ *    tfra_table_find); where[i] (may be NULL) = 1 (upper), 2 (lower) or 0 (neither).
+ *
+ *    tfra_tier_find_or_insert: the lookup of a training step.  keys are unique.  values_out (may be NULL) and where (may be NULL)
+ *    as for tfra_tier_find, a never-seen key's row being its init row (init_values / init_is_full as in
+ *    tfra_table_find_or_insert).  Afterwards every key of the batch is resident in upper with its whole row — a key from below
+ *    with the slot vectors it had there, a never-seen key with slot vectors at upper's aux_init — and its score is the newest:
+ *    the hits are touched before the misses are promoted, so the batch does not evict its own keys.  What the promotion
+ *    displaces goes to lower as whole rows.
+ *    The saturation limit: a batch that fills both home buckets of one of its own keys with its own keys (30 slots) cannot keep
+ *    that key in upper; its row is then below and the invariant holds, but a fused write-back of the step would not find it
+ *    resident and restart it from the default row — the same limit as a key "not resident at write-back time".  And that
+ *    write-back inserts the key into upper directly: at max_capacity it evicts another resident key OUTSIDE the tier, whose
+ *    newest whole row is not demoted and is lost (lower keeps at most a stale copy) — the invariant breaks for that victim.
+ *    It takes a batch built for the purpose; a caller that cannot rule one out checks not_resident before writing back.  With
+ *    TFRA_TIER_VERIFY the call counts the batch keys that are not resident at its end into the statistics (not_resident).
+ *
+ *    tfra_tier_insert: upsert of embedding rows (unique keys) into upper, as tfra_table_insert_and_evict writes them (a new key's
+ *    slot vectors start at aux_init); what it displaces goes to lower as whole rows.
+ *
+ *    tfra_tier_stats: out8 = {calls, missed, lower_hits, demoted, not_resident, 0, 0, 0}, cumulative, the call still pending
+ *    included.  The one call that reads on the host (it waits for the stream).
+ *    (tests/test_gpu_tier_driver.py)                                                                                          */
+typedef struct tfra_tier tfra_tier_t;
+#define TFRA_TIER_VERIFY 1u
+int tfra_tier_create(tfra_table_t* upper, tfra_table_t* lower, size_t max_batch, tfra_tier_t** out);
+int tfra_tier_destroy(tfra_tier_t* tier);
+int tfra_tier_find(tfra_tier_t* tier, size_t n, const int64_t* d_n, const int64_t* keys, void* values, uint8_t* where,
+                   const void* defaults, int default_is_full, tfra_stream_t stream);
+int tfra_tier_find_or_insert(tfra_tier_t* tier, size_t n, const int64_t* d_n, const int64_t* keys, const void* init_values,
+                             int init_is_full, void* values_out, uint8_t* where, uint32_t flags, tfra_stream_t stream);
+int tfra_tier_insert(tfra_tier_t* tier, size_t n, const int64_t* d_n, const int64_t* keys, const void* values, tfra_stream_t stream);
+int tfra_tier_stats(tfra_tier_t* tier, uint64_t* out8, tfra_stream_t stream);
 
 /* -- accum_or_assign = TableWrapper::accum (lookup_table_op_hkv.h:539-546):
  *    absent & !exists -> insert row; present & exists -> row += delta (element order 0..dim-1,

@@ -558,11 +558,19 @@ __device__ __forceinline__ void copy_bytes16_wt(unsigned char* dst, const unsign
 //   TierAssign   assign: the rows go the OTHER way — values[i] (`defaults`, full) into the row of a hit, nothing for a miss — and
 //                a hit's score is touched as insert_or_assign touches it on an assign.  Unique keys: plain stores.
 //   TierContains contains: the probe and the exists byte, nothing else.
-enum { FIND_ONLY = 0, TIER_MISSED = 1, TIER_ASSIGN = 2, TIER_CONTAINS = 3 };
+// and the tier driver (tfra_tierstep.hip) one of:
+//   TierMissedTouch  TierMissed whose hits also get their score touched as TierAssign touches it (in_score 1), out null or not.
+//   TierFetch    the lower tier's lookup of a miss list: key j of `keys` belongs to batch position x->pos_of[j], and that position
+//                is where its row (`out`, may be null), its default (full) and its byte x->where (2 = found, 0 = not; may be null) go; `exists`
+//                is not used.  x->word[u] / x->pos[u]: word index (-1 = absent) and position of key u of this lane's group, for
+//                the caller's own copies (only set by a wave that has keys).
+enum { FIND_ONLY = 0, TIER_MISSED = 1, TIER_ASSIGN = 2, TIER_CONTAINS = 3, TIER_MISSED_TOUCH = 4, TIER_FETCH = 5 };
 struct FindOnly { static constexpr int mode = FIND_ONLY; };
 struct TierMissed { static constexpr int mode = TIER_MISSED; u64* scores_out; unsigned miss; };
 struct TierAssign { static constexpr int mode = TIER_ASSIGN; const u64* scores; int strategy; u64 epoch; };
 struct TierContains { static constexpr int mode = TIER_CONTAINS; };
+struct TierMissedTouch { static constexpr int mode = TIER_MISSED_TOUCH; u64* scores_out; unsigned miss; int strategy; u64 epoch; };
+struct TierFetch { static constexpr int mode = TIER_FETCH; const int* pos_of; uint8_t* where; i64 word[4]; unsigned pos[4]; };
 
 template <int G, int U, bool WT, bool PF1, class X = FindOnly>
 __device__ __forceinline__ void find_wave(const TableView& v, size_t n, const i64* __restrict__ keys, unsigned char* __restrict__ out,
@@ -595,6 +603,7 @@ __device__ __forceinline__ void find_wave(const TableView& v, size_t n, const i6
     b0[u] = (unsigned)__shfl((int)b0reg, j);
     b1[u] = (unsigned)__shfl((int)b1reg, j);
     idx[u] = min(base + (unsigned)j, last);
+    if constexpr (M == TIER_FETCH) idx[u] = x->pos[u] = (unsigned)x->pos_of[idx[u]];   // from here on "its index" is its batch position
     k0[u] = key_line(v, b0[u])[sub];  // U probes in flight
     k1[u] = PF1 ? key_line(v, b1[u])[sub] : 0;
   }
@@ -608,6 +617,10 @@ __device__ __forceinline__ void find_wave(const TableView& v, size_t n, const i6
   for (int u = 0; u < U; ++u) {
     const i64 word = probe_find_word(v, key[u], b0[u], b1[u], k0[u], sub, gshift, PF1 ? &k1[u] : nullptr);
     if (exists && sub == 0) exists[idx[u]] = word >= 0;
+    if constexpr (M == TIER_FETCH) {
+      if (x->where && sub == 0) x->where[idx[u]] = word >= 0 ? 2 : 0;
+      x->word[u] = word;
+    }
     if constexpr (M == TIER_ASSIGN) {
       src[u] = defaults + (u64)idx[u] * (u64)v.field_bytes;
       dst[u] = word >= 0 ? word_row_ptr(v, (u64)word) + field_off : nullptr;
@@ -619,7 +632,15 @@ __device__ __forceinline__ void find_wave(const TableView& v, size_t n, const i6
     if constexpr (M != FIND_ONLY) wd[u] = word;
   }
   if constexpr (M == TIER_CONTAINS) return;
-  if constexpr (M == TIER_MISSED) {
+  if constexpr (M == TIER_FETCH) { if (!out) return; }
+  if constexpr (M == TIER_MISSED_TOUCH) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {   // TierAssign's touch, before the early way out below
+      if (wd[u] < 0 || base + (unsigned)(u * 4 + grp) > last) continue;
+      update_score(v, (i64)(((u64)wd[u] >> 4) * SLOTS + ((u64)wd[u] & 15)), false, x->strategy, 1, x->epoch, sub);
+    }
+  }
+  if constexpr (M == TIER_MISSED || M == TIER_MISSED_TOUCH) {
     // the wave's miss mask: group grp's lane 0 votes for key u*4 + grp (a clamped tail position does not count)
     unsigned miss = 0;
 #pragma unroll

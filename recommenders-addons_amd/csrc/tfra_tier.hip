@@ -1,53 +1,29 @@
 // The read side of a tier: tfra_table_find_missed — find that also lists its misses —, tfra_table_assign — a write
 // that only hits — and tfra_table_contains.  All three are find_wave (tfra_device.h: 16 lanes per key, U = 4 keys in flight per
-// group) with one of its Tier* extras; what is new here is the append of the miss list.
+// group) with one of its Tier* extras; what is new here is the append of the miss list.  The tier driver (tfra_tierstep.hip, DESIGN
+// §4.20) launches find_missed through launch_find_missed (tfra_tier.h), with the touching instance find_missed_touch_kernel.
 #include <hip/hip_runtime.h>
 
 #include "tfra_host.h"
+#include "tfra_tier.h"
 
 using namespace tfra;
-
-// 64-key tiles (four waves each) that ONE block of find_missed_kernel covers — a block of 256 * TIER_TILES threads — and so the keys
-// behind one atomicAdd on the miss counter: 64 * TIER_TILES.  Adds to one address serialise (DESIGN §4 measured ~150 M/s), so
-// B = 131 072 keys cost 2048 / TIER_TILES adds.  The tiles of a block run side by side, not one after the other: the launch has
-// find_kernel's waves in flight whatever the value.  The value kept is the one scripts/mb_find_missed.py measured best
-// (profiles/find_missed_mb.jsonl); a build with -DTFRA_TIER_TILES=N tries another.
-#ifndef TFRA_TIER_TILES
-#define TFRA_TIER_TILES 4
-#endif
-constexpr int TIER_TILES = TFRA_TIER_TILES;
-static_assert(TIER_TILES == 1 || TIER_TILES == 2 || TIER_TILES == 4, "a block has at most 1024 threads");
-
-// Where the miss list goes (tfra_table_export_batch_if's counter and cap rules).
-struct MissOut {
-  u64* counter;    // device size_t, advanced by every miss whatever cap is; null: no list
-  u64 cap;         // pairs at positions >= cap are not written
-  i64* keys;       // may be null
-  int* idx;        // may be null
-  u64* scores;     // find_missed's scores_out: may be null
-};
-
-__device__ __forceinline__ size_t served(size_t n, const long long* d_n) {   // min(n, *d_n), a negative count = 0 (find_kernel's)
-  if (!d_n) return n;
-  const long long dn = *d_n;
-  return dn < 0 ? 0 : min(n, (size_t)dn);
-}
 
 // ---- find_missed ----------------------------------------------------------------------------------------------------------------
 // A block is TILES tiles of 64 keys, one wave per 16 keys, all through find_wave at once; each wave leaves its 16-bit miss mask in
 // LDS.  Then ONE wave scans the 4 * TILES counts, ONE lane takes the block's range with ONE atomicAdd (none when the block has no
 // miss), and every wave stores its pairs at the base it was given: plain vector stores, behind every load group of the lookup.
-template <int G, int U, bool PF1, int TILES>
-__global__ __launch_bounds__(256 * TILES) void find_missed_kernel(TableView v, size_t n, const i64* __restrict__ keys, unsigned char* __restrict__ out,
-                                                                  uint8_t* __restrict__ exists, const unsigned char* __restrict__ defaults, int full,
-                                                                  const long long* __restrict__ d_n, MissOut mo) {
+// X: TierMissed, or TierMissedTouch (the tier driver's step 1) with its miss mask zeroed.
+template <int G, int U, bool PF1, int TILES, class X>
+__device__ __forceinline__ void find_missed_body(TableView v, size_t n, const i64* __restrict__ keys, unsigned char* __restrict__ out,
+                                                 uint8_t* __restrict__ exists, const unsigned char* __restrict__ defaults, int full,
+                                                 const long long* __restrict__ d_n, MissOut mo, X x) {
   constexpr int NW = 4 * TILES;   // waves per block
   __shared__ unsigned s_mask[NW];
   __shared__ u64 s_base[NW];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const unsigned wave = blockIdx.x * NW + w;
-  TierMissed x{mo.scores, 0u};
-  find_wave<G, U, G == 16, PF1, TierMissed>(v, served(n, d_n), keys, out, exists, defaults, full, 0u, wave, &x);
+  find_wave<G, U, G == 16, PF1, X>(v, served(n, d_n), keys, out, exists, defaults, full, 0u, wave, &x);
   if (!mo.counter) return;   // (uniform) find plus scores
   if (lane == 0) s_mask[w] = x.miss;
   __syncthreads();
@@ -74,6 +50,19 @@ __global__ __launch_bounds__(256 * TILES) void find_missed_kernel(TableView v, s
   if (mo.keys) mo.keys[p] = keys[i];
   if (mo.idx) mo.idx[p] = (int)i;
 }
+// The kernels of the body: find_missed_kernel under the name and with the code it had, and the touching instance.
+template <int G, int U, bool PF1, int TILES>
+__global__ __launch_bounds__(256 * TILES) void find_missed_kernel(TableView v, size_t n, const i64* __restrict__ keys, unsigned char* __restrict__ out,
+                                                                  uint8_t* __restrict__ exists, const unsigned char* __restrict__ defaults, int full,
+                                                                  const long long* __restrict__ d_n, MissOut mo) {
+  find_missed_body<G, U, PF1, TILES>(v, n, keys, out, exists, defaults, full, d_n, mo, TierMissed{mo.scores, 0u});
+}
+template <int G, int U, bool PF1, int TILES>
+__global__ __launch_bounds__(256 * TILES) void find_missed_touch_kernel(TableView v, size_t n, const i64* __restrict__ keys, unsigned char* __restrict__ out,
+                                                                        uint8_t* __restrict__ exists, const unsigned char* __restrict__ defaults, int full,
+                                                                        const long long* __restrict__ d_n, MissOut mo, int strategy, u64 epoch) {
+  find_missed_body<G, U, PF1, TILES>(v, n, keys, out, exists, defaults, full, d_n, mo, TierMissedTouch{mo.scores, 0u, strategy, epoch});
+}
 
 // ---- assign: values[i] into the row of every resident key, the score touched as on an assign; absent keys change nothing ----------
 template <int G, int U, bool PF1>
@@ -99,7 +88,27 @@ static int tier_check(const char* fn, size_t n, bool buffers) {
   if (n >= (1ULL << 31)) return set_error(TFRA_ERR_INVALID, std::string(fn) + ": more than 2^31-1 keys per call");
   return TFRA_OK;
 }
-static unsigned blocks_of(size_t n, int tiles) { return (unsigned)((n + 64 * (size_t)tiles - 1) / (64 * (size_t)tiles)); }
+
+void launch_find_missed(Table* t, hipStream_t s, size_t n, const long long* dn, const i64* k, unsigned char* o, uint8_t* exists,
+                        const unsigned char* d, int full, const MissOut& mo, bool touch) {
+  const TableView v = t->view_of(t->cur);
+  const int g = o ? granule_of(t->field_bytes, o, d) : 16;
+  constexpr int U = 4;
+  const dim3 grid(blocks_of(n, TIER_TILES)), block(256 * TIER_TILES);
+  const int strat = t->opts.strategy;
+  const u64 epoch = t->global_epoch;
+  with_granule(g, [&](auto G) {
+    if constexpr (G == 16) {   // a dense table: both home-bucket lines of a key in flight together, as find does
+      if (t->dense) {
+        if (touch) find_missed_touch_kernel<16, U, true, TIER_TILES><<<grid, block, 0, s>>>(v, n, k, o, exists, d, full, dn, mo, strat, epoch);
+        else find_missed_kernel<16, U, true, TIER_TILES><<<grid, block, 0, s>>>(v, n, k, o, exists, d, full, dn, mo);
+        return;
+      }
+    }
+    if (touch) find_missed_touch_kernel<G, U, false, TIER_TILES><<<grid, block, 0, s>>>(v, n, k, o, exists, d, full, dn, mo, strat, epoch);
+    else find_missed_kernel<G, U, false, TIER_TILES><<<grid, block, 0, s>>>(v, n, k, o, exists, d, full, dn, mo);
+  });
+}
 
 extern "C" {
 
@@ -113,21 +122,9 @@ int tfra_table_find_missed(tfra_table_t* tp, size_t n, const int64_t* d_n, const
   if (!d_missed_counter && (missed_keys || missed_indices))
     return set_error(TFRA_ERR_INVALID, std::string(fn) + ": a miss list needs its counter (d_missed_counter == NULL)");
   TABLE_ENTER();
-  const TableView v = t->view_of(t->cur);
-  const int g = values ? granule_of(t->field_bytes, values, defaults) : 16;
-  constexpr int U = 4;
-  const dim3 grid(blocks_of(n, TIER_TILES)), block(256 * TIER_TILES);
-  const i64* k = (const i64*)keys;
-  unsigned char* o = (unsigned char*)values;
-  const unsigned char* d = (const unsigned char*)defaults;
-  const long long* dn = (const long long*)d_n;
   const MissOut mo{(u64*)d_missed_counter, (u64)cap, (i64*)missed_keys, (int*)missed_indices, (u64*)scores_out};
-  with_granule(g, [&](auto G) {
-    if constexpr (G == 16) {   // a dense table: both home-bucket lines of a key in flight together, as find does
-      if (t->dense) { find_missed_kernel<16, U, true, TIER_TILES><<<grid, block, 0, s>>>(v, n, k, o, exists, d, default_is_full, dn, mo); return; }
-    }
-    find_missed_kernel<G, U, false, TIER_TILES><<<grid, block, 0, s>>>(v, n, k, o, exists, d, default_is_full, dn, mo);
-  });
+  launch_find_missed(t, s, n, (const long long*)d_n, (const i64*)keys, (unsigned char*)values, exists, (const unsigned char*)defaults,
+                     default_is_full, mo, false);
   HIP_TRY(hipGetLastError());
   return TFRA_OK;
 }

@@ -47,6 +47,14 @@ static int carve_evict_scratch(Table* t, hipStream_t s, size_t n, bool want_scor
 // Phase 2 of a bounded-table upsert, the ONE launch of insert_evict_kernel (tfra_upsert.hip): the keys whose flag in `deferred` is
 // set replace the minimum-score entry of their home buckets by row i of src_rows and scores[i] (null: 1).  g: the copy granule of
 // table row and src_rows.  eo: the capturing instance (tfra_table_insert_and_evict), one granule for the output rows too.
+// whole_in (with eo only): src_rows are whole co-located rows, written and reported as such (TFRA_INSERT_WHOLE_ROWS).
 // (Hidden: shared by the library's units, not one of its dynamic symbols.)
 __attribute__((visibility("hidden"))) void evict_phase(Table* t, hipStream_t s, const TableView& v, int g, size_t n, const i64* keys, const unsigned char* src_rows,
-                 const u64* scores, unsigned field, const uint8_t* deferred, const EvictOut* eo = nullptr);
+                 const u64* scores, unsigned field, const uint8_t* deferred, const EvictOut* eo = nullptr, bool whole_in = false);
+
+// The body of tfra_table_insert_and_evict_n behind its argument checks, for a caller that holds the table's lock and has entered it
+// on s (the call itself; the tier driver, tfra_tierstep.hip): the locked two-phase upsert of min(n, *d_n) unique keys (d_n null: n).
+// whole_in: `values` rows are whole co-located rows.  eo: looked at on a table at max_capacity only; null there: nothing is
+// reported (whole rows are only written by the capturing instance: whole_in without eo is refused there).
+__attribute__((visibility("hidden"))) int insert_counted(Table* t, hipStream_t s, size_t n, const long long* d_n, const i64* keys, const unsigned char* values,
+                   const u64* scores, bool whole_in, const EvictOut* eo);

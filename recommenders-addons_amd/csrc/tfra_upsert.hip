@@ -1,9 +1,9 @@
-// The locked upsert of the table (tfra_table.hip): insert_or_assign[_n], insert_and_evict, insert_field, and the eviction phase of
+// The locked upsert of the table (tfra_table.hip): insert_or_assign[_n], insert_and_evict[_n], insert_field, and the eviction phase of
 // every two-phase call of the family (evict_phase: insert_evict_kernel is compiled here and nowhere else).  The admitting lookups
 // are tfra_find_insert.hip, the typed accumulate tfra_accum.hip; what the three share: tfra_upsert_device.h, tfra_upsert.h.
 // (Unique keys on a table that is large for the batch take the ownership pass instead: own_upsert_unique, tfra_own.hip.)
-// Kernels instantiated here: insert_unique_kernel<G, U, false>, insert_evict_kernel<G, false | true>, insert_locate_kernel,
-// insert_write_kernel, rearm_winner_kernel.
+// Kernels instantiated here: insert_unique_kernel<G, U, false>, insert_counted_kernel<G, U, false | true>,
+// insert_evict_kernel<G, false | true>, insert_evict_rows_kernel<G>, insert_locate_kernel, insert_write_kernel, rearm_winner_kernel.
 #include <hip/hip_runtime.h>
 
 #include "tfra_host.h"
@@ -15,11 +15,13 @@ using namespace tfra;
 // ---- phase 2 of a bounded-table upsert (what it is and what it reports: tfra_upsert_device.h, at EvictOut) ----
 
 // CAPTURE: every entry that leaves the table, and every key that is not admitted, is appended to `eo`.
-template <int G, bool CAPTURE = false>
-__global__ __launch_bounds__(256) void insert_evict_kernel(TableView v, size_t n, const i64* __restrict__ keys,
-                                                           const unsigned char* __restrict__ vals,
-                                                           const u64* __restrict__ scores, unsigned field, AuxInit ai,
-                                                           int strategy, u64 epoch, const uint8_t* __restrict__ deferred, EvictOut eo) {
+// WHOLE_IN (TFRA_INSERT_WHOLE_ROWS, capturing only): `vals` rows are whole co-located rows, written and reported as such.
+template <int G, bool CAPTURE, bool WHOLE_IN>
+__device__ __forceinline__ void insert_evict_body(const TableView& v, size_t n, const i64* __restrict__ keys,
+                                                  const unsigned char* __restrict__ vals,
+                                                  const u64* __restrict__ scores, unsigned field, const AuxInit& ai,
+                                                  int strategy, u64 epoch, const uint8_t* __restrict__ deferred, const EvictOut& eo) {
+  const unsigned src_bytes = WHOLE_IN ? v.n_fields * v.field_bytes : v.field_bytes;   // one row of vals
   const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
   const size_t i = (((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4);
   int fresh = 0, failed = 0;
@@ -67,7 +69,7 @@ __global__ __launch_bounds__(256) void insert_evict_kernel(TableView v, size_t n
           if (out_row) copy_bytes16_coherent<G>(out_row, row_ptr(v, row), eo.row_bytes, sub);
         }
       }
-      replace_locked<G>(v, row, word, key, vals + i * (size_t)v.field_bytes, field, ai, strategy, in_score, epoch, sub);
+      replace_locked<G, WHOLE_IN>(v, row, word, key, vals + i * (size_t)src_bytes, field, ai, strategy, in_score, epoch, sub);
       fresh = (claimed_empty && sub == 0);
     } else if (active && row == -3) {
       failed = (sub == 0);
@@ -77,14 +79,91 @@ __global__ __launch_bounds__(256) void insert_evict_kernel(TableView v, size_t n
         if (eo.scores) eo.scores[pos] = compare;
       }
       if (out_row) {
-        copy_bytes16<G>(out_row, vals + i * (size_t)v.field_bytes, v.field_bytes, sub);
-        // (out_row is aligned to G only: words when G says so)
-        for (unsigned f = 1; (f + 1) * v.field_bytes <= eo.row_bytes; ++f)
-          fill_aux_field(out_row + f * v.field_bytes, v.field_bytes, ai.pattern[(f - 1) & 3], ai.elem_bytes, G >= 4 && (v.field_bytes & 3) == 0, sub);
+        if constexpr (WHOLE_IN) {   // the caller's row, slot vectors and all (eo.row_bytes: the field or the whole row)
+          copy_bytes16<G>(out_row, vals + i * (size_t)src_bytes, eo.row_bytes, sub);
+        } else {
+          copy_bytes16<G>(out_row, vals + i * (size_t)v.field_bytes, v.field_bytes, sub);
+          // (out_row is aligned to G only: words when G says so)
+          for (unsigned f = 1; (f + 1) * v.field_bytes <= eo.row_bytes; ++f)
+            fill_aux_field(out_row + f * v.field_bytes, v.field_bytes, ai.pattern[(f - 1) & 3], ai.elem_bytes, G >= 4 && (v.field_bytes & 3) == 0, sub);
+        }
       }
     }
   }
   wave_account(v, i >> 2, lane, fresh, failed);
+}
+
+// The kernels of the body: insert_evict_kernel under the name and with the code it had, and the whole-row capturing instance.
+template <int G, bool CAPTURE = false>
+__global__ __launch_bounds__(256) void insert_evict_kernel(TableView v, size_t n, const i64* __restrict__ keys,
+                                                           const unsigned char* __restrict__ vals,
+                                                           const u64* __restrict__ scores, unsigned field, AuxInit ai,
+                                                           int strategy, u64 epoch, const uint8_t* __restrict__ deferred, EvictOut eo) {
+  insert_evict_body<G, CAPTURE, false>(v, n, keys, vals, scores, field, ai, strategy, epoch, deferred, eo);
+}
+template <int G>
+__global__ __launch_bounds__(256) void insert_evict_rows_kernel(TableView v, size_t n, const i64* __restrict__ keys,
+                                                                const unsigned char* __restrict__ vals, const u64* __restrict__ scores,
+                                                                AuxInit ai, int strategy, u64 epoch, const uint8_t* __restrict__ deferred,
+                                                                EvictOut eo) {
+  insert_evict_body<G, true, true>(v, n, keys, vals, scores, 0u, ai, strategy, epoch, deferred, eo);
+}
+
+// ---- insert_and_evict_n, phase 1 ----
+// insert_unique_kernel's plain write of the embedding field — its probes, claim, score and accounting — over the min(n_buf, *d_n)
+// leading keys of buffers of n_buf entries (d_n null: all), the flags of the entries beyond the count cleared for phase 2 as the
+// FIND instance clears them.  A kernel of its own so that insert_unique_kernel keeps its code.
+// WHOLE (TFRA_INSERT_WHOLE_ROWS): `vals` rows are whole co-located rows; the slot vectors of a new AND of a resident key are the
+// caller's, init_aux_fields is not applied.
+template <int G, int U, bool WHOLE>
+__global__ __launch_bounds__(256) void insert_counted_kernel(TableView v, size_t n_buf, const i64* __restrict__ keys,
+                                                             const unsigned char* __restrict__ vals, const u64* __restrict__ scores,
+                                                             AuxInit ai, int strategy, u64 epoch, int bounded,
+                                                             uint8_t* __restrict__ deferred, const long long* __restrict__ d_n) {
+  const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48, grp = lane >> 4;
+  const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  constexpr int KPW = 4 * U;
+  const size_t base = wave * KPW;
+  size_t n = n_buf;
+  if (d_n) {   // uniform load, as find_kernel's
+    const long long dn = *d_n;
+    n = dn < 0 ? 0 : min(n_buf, (size_t)dn);
+  }
+  if (deferred && lane < KPW && base + lane >= n && base + lane < n_buf) deferred[base + lane] = 0;
+  if (base >= n) return;
+  const size_t last = n - 1;
+  const unsigned src_bytes = WHOLE ? v.n_fields * v.field_bytes : v.field_bytes;   // one row of vals
+  i64 kreg = keys[min(base + (size_t)(lane & (KPW - 1)), last)];
+  int fresh = 0, failed = 0;
+  i64 key[U], k0[U], k1[U];
+  u64 h[U], b0[U];
+  const bool pf1 = bounded > 1;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {  // U first probes in flight (unconditional, tail clamped)
+    key[u] = shfl_i64(kreg, u * 4 + grp);
+    b0[u] = bucket0(key[u], v.nb, h[u]);
+    k0[u] = load_key_coherent(key_line(v, b0[u]) + sub);
+    k1[u] = load_key_coherent(key_line(v, pf1 ? bucket1(h[u], b0[u], v.nb) : b0[u]) + sub);
+  }
+  keep_live(k0[0], k0[1], k0[2], k0[3]);
+  keep_live(k1[0], k1[1], k1[2], k1[3]);
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const size_t i = base + (size_t)(u * 4 + grp);
+    if (i >= n) continue;
+    bool is_new;
+    const i64 row = locate_or_claim_from(v, key[u], h[u], b0[u], k0[u], sub, gshift, is_new, bounded, pf1 ? &k1[u] : nullptr);
+    if (deferred && sub == 0) deferred[i] = row == NEED_EVICT;
+    if (row >= 0) {
+      copy_bytes16<G>(row_ptr(v, row), vals + i * (size_t)src_bytes, src_bytes, sub);
+      if constexpr (!WHOLE) { if (is_new && v.n_fields > 1) init_aux_fields(v, ai, row, sub, 0); }
+      update_score(v, row, is_new, strategy, scores ? scores[i] : 1, epoch, sub);
+      fresh += (is_new && sub == 0);
+    } else if (row != NEED_EVICT) {
+      failed += (sub == 0);
+    }
+  }
+  wave_account(v, wave, lane, fresh, failed);
 }
 
 // ---- insert_or_assign with duplicates: pass 1 locate/claim + elect the LAST index ----------
@@ -160,13 +239,14 @@ __global__ void rearm_winner_kernel(TableView v, size_t n, const i64* __restrict
 }
 
 void evict_phase(Table* t, hipStream_t s, const TableView& v, int g, size_t n, const i64* keys, const unsigned char* src_rows,
-                 const u64* scores, unsigned field, const uint8_t* deferred, const EvictOut* eo) {
+                 const u64* scores, unsigned field, const uint8_t* deferred, const EvictOut* eo, bool whole_in) {
   const dim3 grid((unsigned)((n * 16 + 255) / 256)), block(256);
   const int strat = t->opts.strategy;
   const u64 epoch = t->global_epoch;
   if (eo) {   // one granule for the table row, the caller's rows and the output rows
     const int gc = std::min(g, granule_of(eo->row_bytes, eo->vals, nullptr));
-    with_granule(gc, [&](auto G) { insert_evict_kernel<G, true><<<grid, block, 0, s>>>(v, n, keys, src_rows, scores, field, t->aux, strat, epoch, deferred, *eo); });
+    if (whole_in) with_granule(gc, [&](auto G) { insert_evict_rows_kernel<G><<<grid, block, 0, s>>>(v, n, keys, src_rows, scores, t->aux, strat, epoch, deferred, *eo); });
+    else with_granule(gc, [&](auto G) { insert_evict_kernel<G, true><<<grid, block, 0, s>>>(v, n, keys, src_rows, scores, field, t->aux, strat, epoch, deferred, *eo); });
   } else {
     with_granule(g, [&](auto G) { insert_evict_kernel<G><<<grid, block, 0, s>>>(v, n, keys, src_rows, scores, field, t->aux, strat, epoch, deferred, EvictOut{}); });
   }
@@ -275,6 +355,56 @@ extern "C" int tfra_table_insert_and_evict(tfra_table_t* tp, size_t n, const int
   const unsigned row_bytes = t->field_bytes * ((flags & TFRA_EVICT_WHOLE_ROWS) ? 1u + (unsigned)t->opts.aux_fields : 1u);
   const EvictOut eo{(u64*)d_evicted_counter, (u64)cap, (i64*)evicted_keys, (unsigned char*)evicted_values, (u64*)evicted_scores, row_bytes};
   return insert_impl(t, s, 0, n, keys, values, scores, TFRA_FLAG_UNIQUE_KEYS, &eo);
+}
+
+// ---- insert_and_evict_n: the count on the device, whole rows in ----
+int insert_counted(Table* t, hipStream_t s, size_t n, const long long* d_n, const i64* keys, const unsigned char* values,
+                   const u64* scores, bool whole_in, const EvictOut* eo) {
+  int rc = t->prepare_insert(n, s);   // (n is an upper bound of the keys: a growing table may grow a call early)
+  if (rc) return rc;
+  const u64 epoch = t->global_epoch;
+  const int strat = t->opts.strategy;
+  const int g = granule_of(t->field_bytes, values, nullptr);   // (divides the whole row too: one granule for field and row)
+  constexpr int U = 4;
+  const size_t waves = (n + 4 * U - 1) / (4 * U);
+  const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
+  const bool bounded = t->at_max_capacity();
+  if (bounded && whole_in && !eo) return set_error(TFRA_ERR_INVALID, "insert: whole rows into a table at max_capacity need the capturing phase 2");
+  EvictScratch es;
+  if (bounded) {
+    rc = carve_evict_scratch(t, s, n, false, 0, &es);
+    if (rc) return rc;
+  }
+  const TableView v = t->view_of(t->cur);
+  const int bd = bounded_mode(t, bounded);
+  with_granule(g, [&](auto G) {
+    if (whole_in) insert_counted_kernel<G, U, true><<<grid, block, 0, s>>>(v, n, keys, values, scores, t->aux, strat, epoch, bd, es.deferred, d_n);
+    else insert_counted_kernel<G, U, false><<<grid, block, 0, s>>>(v, n, keys, values, scores, t->aux, strat, epoch, bd, es.deferred, d_n);
+  });
+  if (bounded) evict_phase(t, s, v, g, n, keys, values, scores, 0, es.deferred, eo, whole_in);
+  HIP_TRY(hipGetLastError());
+  t->step_epoch();
+  return TFRA_OK;
+}
+
+extern "C" int tfra_table_insert_and_evict_n(tfra_table_t* tp, size_t n, const int64_t* d_n, const int64_t* keys, const void* values,
+                                             const uint64_t* scores, uint32_t flags, size_t* d_evicted_counter, size_t cap,
+                                             int64_t* evicted_keys, void* evicted_values, uint64_t* evicted_scores, tfra_stream_t stream) {
+  const char* who = "tfra_table_insert_and_evict_n: ";
+  if (!tp) return set_error(TFRA_ERR_INVALID, std::string(who) + "null table");
+  if (flags & ~(TFRA_EVICT_WHOLE_ROWS | TFRA_INSERT_WHOLE_ROWS)) return set_error(TFRA_ERR_INVALID, std::string(who) + "unknown flag bits");
+  if (n == 0) return TFRA_OK;
+  if (int rc = check_batch(who, n, keys && values && d_evicted_counter, [&] {
+        return !evicted_keys && (evicted_values || evicted_scores)
+                   ? set_error(TFRA_ERR_INVALID, std::string(who) + "evicted_keys == NULL counts only, evicted_values and evicted_scores must be NULL too")
+                   : TFRA_OK;
+      }))
+    return rc;
+  TABLE_ENTER();
+  const unsigned row_bytes = t->field_bytes * ((flags & TFRA_EVICT_WHOLE_ROWS) ? 1u + (unsigned)t->opts.aux_fields : 1u);
+  const EvictOut eo{(u64*)d_evicted_counter, (u64)cap, (i64*)evicted_keys, (unsigned char*)evicted_values, (u64*)evicted_scores, row_bytes};
+  return insert_counted(t, s, n, (const long long*)d_n, (const i64*)keys, (const unsigned char*)values, (const u64*)scores,
+                        (flags & TFRA_INSERT_WHOLE_ROWS) != 0, &eo);
 }
 
 extern "C" int tfra_table_insert_field(tfra_table_t* tp, int field, size_t n, const int64_t* keys, const void* values,

@@ -70,6 +70,8 @@ struct FindOut {
 // FIND: a hit is READ — its row goes to fo.vals, nothing of it but the score is written; a miss is written from its
 // init row `vals` as the plain instance writes it, and that row is what fo.vals gets.  Unique keys: no other group of the launch
 // writes a row that a hit reads, and the rows of earlier launches are behind a kernel boundary, so the row is loaded as find loads it.
+// A TWIN of the plain instance lives in tfra_upsert.hip: insert_counted_kernel (the key count on the device, whole rows in; DESIGN
+// §4.20) repeats its probes, claim, score and accounting so that this kernel keeps its code.  A fix here belongs there too.
 template <int G, int U, bool FIND = false>
 __global__ __launch_bounds__(256) void insert_unique_kernel(TableView v, size_t n,
                                                             const i64* __restrict__ keys,
@@ -184,11 +186,16 @@ __device__ __forceinline__ void copy_bytes16_coherent(unsigned char* dst, const 
 }
 
 // The slot `word` (row `row`) is LOCKED by this group: the new key's row, aux fields and score, then the key
-template <int G>
+// WHOLE: src is a whole co-located row (TFRA_INSERT_WHOLE_ROWS): the slot vectors come from it, aux_init is not applied
+template <int G, bool WHOLE = false>
 __device__ __forceinline__ void replace_locked(const TableView& v, i64 row, u64 word, i64 key, const unsigned char* src, unsigned field,
                                                const AuxInit& ai, int strategy, u64 in_score, u64 epoch, int sub) {
-  copy_bytes16_wt<G>(row_ptr(v, row) + field * v.field_bytes, src, v.field_bytes, sub);
-  if (v.n_fields > 1) init_aux_fields<true>(v, ai, row, sub, field);
+  if constexpr (WHOLE) {
+    copy_bytes16_wt<G>(row_ptr(v, row), src, v.n_fields * v.field_bytes, sub);
+  } else {
+    copy_bytes16_wt<G>(row_ptr(v, row) + field * v.field_bytes, src, v.field_bytes, sub);
+    if (v.n_fields > 1) init_aux_fields<true>(v, ai, row, sub, field);
+  }
   if (sub == 0) store_wt8(score_word(v, word), 0);  // the slot starts a new life: scores count from zero
   update_score<true>(v, row, true, strategy, in_score, epoch, sub);
   publish_key(v, word, key, sub);

@@ -13,6 +13,8 @@ LIB_PATH = os.path.join(_HERE, "lib", "libtfra_mi355x.so")
 TFRA_F32, TFRA_F16, TFRA_BF16, TFRA_I8, TFRA_I32, TFRA_I64, TFRA_F64 = range(7)
 FLAG_UNIQUE_KEYS = 1
 EVICT_WHOLE_ROWS = 1   # TFRA_EVICT_WHOLE_ROWS (flag of tfra_table_insert_and_evict)
+INSERT_WHOLE_ROWS = 2  # TFRA_INSERT_WHOLE_ROWS (flag of tfra_table_insert_and_evict_n)
+TIER_VERIFY = 1        # TFRA_TIER_VERIFY (flag of tfra_tier_find_or_insert)
 OPT_SGD, OPT_ADAM, OPT_ADAGRAD, OPT_FTRL = range(4)
 RAGGED_PRUNE, RAGGED_FILL = 1, 2   # TFRA_RAGGED_* (flags of the ragged pooled lookup)
 OPTION_CAPTURE_SAFE = 1
@@ -146,6 +148,13 @@ _SIGS = {
     "tfra_table_find_missed": [_P, _SZ, _P, _P, _P, _P, _P, _P, _I, _P, _SZ, _P, _P, _P],
     "tfra_table_assign": [_P, _SZ, _P, _P, _P, _P, _P, _P],
     "tfra_table_contains": [_P, _SZ, _P, _P, _P, _P],
+    "tfra_table_insert_and_evict_n": [_P, _SZ, _P, _P, _P, _P, ctypes.c_uint32, _P, _SZ, _P, _P, _P, _P],
+    "tfra_tier_create": [_P, _P, _SZ, ctypes.POINTER(_P)],
+    "tfra_tier_destroy": [_P],
+    "tfra_tier_find": [_P, _SZ, _P, _P, _P, _P, _P, _I, _P],
+    "tfra_tier_find_or_insert": [_P, _SZ, _P, _P, _P, _I, _P, _P, ctypes.c_uint32, _P],
+    "tfra_tier_insert": [_P, _SZ, _P, _P, _P, _P],
+    "tfra_tier_stats": [_P, ctypes.POINTER(ctypes.c_uint64), _P],
     "tfra_table_find_n": [_P, _SZ, _P, _P, _P, _P, _P, ctypes.c_int, _P],
     "tfra_table_insert_or_assign_n": [_P, _SZ, _P, _P, _P, _P, _P],
     "tfra_table_insert_field": [_P, _I, _SZ, _P, _P, ctypes.c_uint32, _P],

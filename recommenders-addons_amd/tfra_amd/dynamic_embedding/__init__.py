@@ -6,9 +6,10 @@ from .optimizer import (CapturedTrainStep, DynamicEmbeddingOptimizer, MultiTable
                         PrefetchAssignStep, PrefetchStep, assign_step_driver_for, assign_step_for)
 from .restrict_policies import FrequencyRestrictPolicy, RestrictPolicy, TimestampRestrictPolicy
 from .table_ops import (SparsePlan, CuckooHashTable, HkvEvictStrategy, HkvHashTable, KHkvHashTableInitCapacity,
-                        KHkvHashTableMaxCapacity, KHkvHashTableMaxHbmForValuesByBytes)
+                        KHkvHashTableMaxCapacity, KHkvHashTableMaxHbmForValuesByBytes, TieredHashTable)
 from .variable import (CuckooHashTableConfig, CuckooHashTableCreator, HkvHashTableConfig, HkvHashTableCreator,
-                       KVCreator, SparseTrainableWrapper, TrainableWrapper, Variable, default_partition_fn, embedding_lookup,
+                       KVCreator, SparseTrainableWrapper, TieredHashTableConfig, TieredHashTableCreator, TrainableWrapper, Variable,
+                       default_partition_fn, embedding_lookup,
                        embedding_lookup_sparse, embedding_lookup_sparse_many, embedding_lookup_unique, get_variable,
                        safe_embedding_lookup_sparse, safe_embedding_lookup_sparse_many)
 from . import ragged_embedding_ops   # (after .variable: it stands on the tuple-form functions)

@@ -401,16 +401,27 @@ class _DeviceTable:
       _capi.call("tfra_table_insert_or_assign", self._h, n, _ptr(keys), _ptr(values), _ptr(scores), flags,
                  _stream(self._device))
 
-  def upsert_and_evict(self, keys, values, scores=None, whole_rows=False, cap=None, sync=True):
+  def upsert_and_evict(self, keys, values, scores=None, whole_rows=False, cap=None, sync=True, count=None, whole_rows_in=False):
     """upsert(keys, values, scores, unique_keys=True) that hands back what it displaces (tfra_table_insert_and_evict): every entry
     that leaves a table at max_capacity because of this call, and every key the table does not admit (with the caller's row and
     its compare score).  -> (evicted_keys, evicted_values, evicted_scores), trimmed to their count: ONE host read of the counter.
     whole_rows: the rows are the whole co-located row, [(1 + aux_fields) * dim].  cap: room in the buffers (default: one entry
     per key, which always suffices); the count goes on beyond it, entries beyond it are not written.
     sync=False: (count, keys, values, scores) with `count` a device int64 tensor of shape [1] and the buffers untrimmed — no
-    host read.  A table that is not at max_capacity reports nothing."""
+    host read.  A table that is not at max_capacity reports nothing.
+    count: a device int64 (or pinned) count of the leading keys that are served, read on the device; whole_rows_in: `values`
+    rows are whole co-located rows, [(1 + aux_fields) * dim], and the slot vectors are written from them for new, replacing
+    and resident keys alike (either one: tfra_table_insert_and_evict_n)."""
     keys = self._keys(keys)
-    values = self._values_for(keys, values)
+    if whole_rows_in:
+      if not torch.is_tensor(values) or values.dtype != self._value_dtype:
+        raise TypeError("Signature mismatch. values must be a %s tensor." % self._value_dtype)
+      want = tuple(keys.shape) + (self._dim * (1 + self._aux_fields),)
+      if tuple(values.shape) != want:
+        raise ValueError("Expected shape %s for whole-row values, got %s" % (list(want), list(values.shape)))
+      values = values.to(self._device).contiguous()
+    else:
+      values = self._values_for(keys, values)
     n = keys.numel()
     if scores is not None and scores.numel() == 0:
       scores = None
@@ -426,9 +437,14 @@ class _DeviceTable:
     ek = torch.empty(cap, dtype=torch.int64, device=self._device)
     ev = torch.empty((cap, width), dtype=self._value_dtype, device=self._device)
     es = torch.empty(cap, dtype=torch.int64, device=self._device)
-    if n:
+    flags = _capi.EVICT_WHOLE_ROWS if whole_rows else 0
+    if n and (count is not None or whole_rows_in):
+      _capi.call("tfra_table_insert_and_evict_n", self._h, n, _ptr(count), _ptr(keys), _ptr(values), _ptr(scores),
+                 flags | (_capi.INSERT_WHOLE_ROWS if whole_rows_in else 0), _ptr(counter), cap, _ptr(ek), _ptr(ev), _ptr(es),
+                 _stream(self._device))
+    elif n:
       _capi.call("tfra_table_insert_and_evict", self._h, n, _ptr(keys), _ptr(values), _ptr(scores),
-                 _capi.EVICT_WHOLE_ROWS if whole_rows else 0, _ptr(counter), cap, _ptr(ek), _ptr(ev), _ptr(es), _stream(self._device))
+                 flags, _ptr(counter), cap, _ptr(ek), _ptr(ev), _ptr(es), _stream(self._device))
     if not sync:
       return counter, ek, ev, es   # (the keys stay int64 here: narrowing the unwritten tail would read it)
     m = min(int(counter.item()), cap)
@@ -761,6 +777,93 @@ def _apply_sparse(self, params, ids, grads, default_row):
 _DeviceTable.apply_sparse = _apply_sparse
 
 
+class _DeviceTier:
+  """Owns one tfra_tier_t: `upper`, a bounded LRU / EPOCHLRU _DeviceTable, in front of `lower`, a growing _DeviceTable without
+  eviction.  Whole co-located rows move between the two on the device; nothing but `stats` reads on the host.  After every call,
+  for every key ever written through the tier: upper holds its newest whole row if it contains the key, otherwise lower does."""
+
+  def __init__(self, upper, lower, max_batch):
+    self._upper, self._lower = upper, lower   # (kept alive: the driver must go before its tables)
+    self._max_batch = int(max_batch)
+    h = ctypes.c_void_p()
+    _capi.call("tfra_tier_create", upper._h, lower._h, self._max_batch, ctypes.byref(h))
+    self._h = h
+
+  def __del__(self):
+    h = getattr(self, "_h", None)
+    if h:
+      try:
+        _capi.lib().tfra_tier_destroy(h)
+      except Exception:  # interpreter shutdown
+        pass
+      self._h = None
+
+  @property
+  def max_batch(self):
+    return self._max_batch
+
+  def _rows_for(self, keys, rows, what):
+    """-> (rows on the device, is_full): [n, dim] or one row of dim elements (None: the upper table's default row)"""
+    up = self._upper
+    d = up._default_value if rows is None else rows
+    d = torch.as_tensor(d, device=up._device) if not torch.is_tensor(d) else d.to(up._device)
+    if d.dtype != up._value_dtype:
+      raise TypeError("%s must be dtype %s, got %s" % (what, up._value_dtype, d.dtype))
+    d = d.contiguous()
+    full = int(d.numel() == keys.numel() * up._dim)   # (one key: the two forms are the same row)
+    if not full and d.numel() != up._dim:
+      raise ValueError("%s must be [n, dim] or one row of dim=%d elements, got shape %s" % (what, up._dim, list(d.shape)))
+    return d, full
+
+  def _out_for(self, keys, out):
+    up = self._upper
+    n = keys.numel()
+    if out is None:
+      return torch.empty(tuple(keys.shape) + (up._dim,), dtype=up._value_dtype, device=up._device)
+    if out.dtype != up._value_dtype or out.numel() != n * up._dim or not out.is_contiguous() or out.device != up._device:
+      raise ValueError("out must be a contiguous %s tensor of %d x %d elements on %s" % (up._value_dtype, n, up._dim, up._device))
+    return out
+
+  def find(self, keys, dynamic_default_values=None, return_where=False, count=None, out=None):
+    """A read (tfra_tier_find): the row upper holds, else the row lower holds, else the default.  Keys may repeat; nothing moves and
+    neither table is written.  -> rows, or (rows, where) with where uint8: 1 = upper, 2 = lower, 0 = neither."""
+    keys = self._upper._keys(keys)
+    d, full = self._rows_for(keys, dynamic_default_values, "default values")
+    out = self._out_for(keys, out)
+    where = torch.zeros(keys.shape, dtype=torch.uint8, device=self._upper._device)
+    if keys.numel():
+      _capi.call("tfra_tier_find", self._h, keys.numel(), _ptr(count), _ptr(keys), _ptr(out), _ptr(where), _ptr(d), full,
+                 _stream(self._upper._device))
+    return (out, where) if return_where else out
+
+  def find_or_insert(self, keys, init_values=None, return_where=False, count=None, out=None, verify=False):
+    """The lookup of a training step (tfra_tier_find_or_insert): UNIQUE keys; rows as `find` returns them, a never-seen key's being
+    its init row.  Afterwards every key of the batch is resident in upper with its whole row (the slot vectors it had below, or
+    aux_init), and what that displaced is below.  verify: count the batch keys that are NOT resident at the end into
+    stats()["not_resident"] (a batch that fills both home buckets of one of its keys with its own keys)."""
+    keys = self._upper._keys(keys)
+    d, full = self._rows_for(keys, init_values, "init values")
+    out = self._out_for(keys, out)
+    where = torch.zeros(keys.shape, dtype=torch.uint8, device=self._upper._device)
+    if keys.numel():
+      _capi.call("tfra_tier_find_or_insert", self._h, keys.numel(), _ptr(count), _ptr(keys), _ptr(d), full, _ptr(out), _ptr(where),
+                 _capi.TIER_VERIFY if verify else 0, _stream(self._upper._device))
+    return (out, where) if return_where else out
+
+  def insert(self, keys, values, count=None):
+    """upsert of embedding rows (UNIQUE keys) into upper; what it displaces goes down as whole rows (tfra_tier_insert)."""
+    keys = self._upper._keys(keys)
+    values = self._upper._values_for(keys, values)
+    if keys.numel():
+      _capi.call("tfra_tier_insert", self._h, keys.numel(), _ptr(count), _ptr(keys), _ptr(values), _stream(self._upper._device))
+
+  def stats(self):
+    """-> dict(calls, missed, lower_hits, demoted, not_resident), cumulative.  The one call that reads on the host."""
+    w = (ctypes.c_uint64 * 8)()
+    _capi.call("tfra_tier_stats", self._h, w, _stream(self._upper._device))
+    return dict(zip(("calls", "missed", "lower_hits", "demoted", "not_resident"), (int(x) for x in w[:5])))
+
+
 class SparsePlan:
   """The id-only half of `apply_sparse` for one batch (tfra_sparse_plan_*): which ids repeat, the order
   their gradients are summed in, the unique keys of the step.  Build it as soon as the ids are known —
@@ -1029,24 +1132,48 @@ class _LookupInterfaceMirror:
     os.makedirs(dirpath, exist_ok=True)
     return os.path.join(dirpath, file_name if file_name else self._name)
 
+  def _checkpoint_table(self):
+    """The device table whose rows and slot vectors ARE the checkpoint: what is saved from and loaded into, here and by
+    `Variable.save_to_file_system` / `load_from_file_system`.  An accessor: it changes nothing.  (A TieredHashTable: its lower table.)"""
+    return self._table
+
+  def _checkpoint_flush(self):
+    """Called ONCE per shard before `_checkpoint_table()` is read from or has single fields written: afterwards that table alone holds
+    everything.  (A TieredHashTable copies its cache down; `save_to_file_system` calls this itself, so the slot files a Variable
+    saves behind it need no second flush.)"""
+
+  def _checkpoint_loaded(self):
+    """Called once per shard behind the loads into `_checkpoint_table()`.  (A TieredHashTable empties its cache.)"""
+
+  # the per-shard forms of Variable.lookup_missed / Variable.assign: a tiered shard answers for both of its tiers
+  def _shard_find_missed(self, keys, defaults, return_exists):
+    return self._table.find_missed(keys, defaults, return_exists=return_exists)
+
+  def _shard_assign(self, keys, values, return_found):
+    return self._table.assign(keys, values, scores=self._gen_scores(keys), return_found=return_found)
+
   def save_to_file_system(self, dirpath, file_name=None, dirpath_env="TFRA_SAVED_KV", append_to_file=False,
                           buffer_size=4194304, name=None):
-    return self._table.save(self._file_prefix(dirpath, file_name, dirpath_env), buffer_size, append_to_file)
+    self._checkpoint_flush()
+    return self._checkpoint_table().save(self._file_prefix(dirpath, file_name, dirpath_env), buffer_size, append_to_file)
 
   def load_from_file_system(self, dirpath, file_name=None, dirpath_env="TFRA_SAVED_KV", load_entire_dir=False,
                             buffer_size=4194304, name=None):
     """load_entire_dir: load every `*-keys` file of the directory (PY/cuckoo_hashtable_ops.py:482-523).
     The GPU op clears the table first (hkv_hashtable_op_gpu.cu.cc:619)."""
     prefix = self._file_prefix(dirpath, file_name, dirpath_env)
-    self._table.clear_all()
+    table = self._checkpoint_table()
+    table.clear_all()
     if load_entire_dir:
       d = os.path.dirname(prefix)
       total = 0
       for f in sorted(os.listdir(d)):
         if f.endswith("-keys"):
-          total += self._table.load(os.path.join(d, f[:-len("-keys")]), buffer_size)
-      return total
-    return self._table.load(prefix, buffer_size)
+          total += table.load(os.path.join(d, f[:-len("-keys")]), buffer_size)
+    else:
+      total = table.load(prefix, buffer_size)
+    self._checkpoint_loaded()
+    return total
 
 
 class CuckooHashTable(_LookupInterfaceMirror):
@@ -1187,8 +1314,158 @@ class HkvHashTable(_LookupInterfaceMirror):
     return self._table.save_if(self._file_prefix(dirpath, file_name, dirpath_env), threshold, pred, buffer_size, append_to_file)
 
 
+def _export_or_empty(table, values=True):
+  """(keys, rows) of a _DeviceTable's export_all; an empty table exports two empty tensors (export_batch refuses a buffer of no
+  bytes)."""
+  if table.size_host() == 0:
+    return (torch.empty(0, dtype=table._key_dtype, device=table._device),
+            torch.empty((0, table._dim), dtype=table._value_dtype, device=table._device) if values else None)
+  k, v, _ = table.export_all(values=values)
+  return k, v
+
+
+class TieredHashTable(_LookupInterfaceMirror):
+  """Two tiers behind one table interface: `_table`, a bounded LRU / EPOCHLRU _DeviceTable at max_capacity (the cache: the fused
+  write-backs, `_device_table` and the slot views act on it), in front of `_lower`, a growing _DeviceTable that holds every key
+  the cache does not, driven by `_tier` (a _DeviceTier).  Whole co-located rows move between the two, so a key that is demoted
+  and promoted again keeps its optimizer slots.  After every call that goes through this class, for every key ever written: the
+  upper table holds its newest whole row if it contains the key, otherwise the lower one does.
+  `find_or_insert` — the lookup of a training step — leaves every key of the batch resident in the upper table, so the
+  write-back of the step only hits.  One limit, next to "not resident at write-back time": a batch that fills both home buckets
+  of one of its own keys with its own keys (30 slots) cannot keep that key up; its row is below and a fused write-back restarts
+  it from the default row (`_DeviceTier.find_or_insert(verify=True)` counts such keys).
+  config: a TieredHashTableConfig (`upper`: an HkvHashTableConfig, `max_batch`: the most keys one call may carry)."""
+
+  def __init__(self, key_dtype, value_dtype, default_value, name="TieredHashTable", checkpoint=True, config=None, device="",
+               shard_saveable_object_fn=None, dim=None, aux_fields=0, aux_init=(0.0,) * 4, init_size=0):
+    if config is None:
+      raise ValueError("TieredHashTable needs a TieredHashTableConfig")
+    up = config.upper
+    self._key_dtype, self._value_dtype, self._name, self._checkpoint = key_dtype, value_dtype, name, checkpoint
+    self._evict_strategy = HkvEvictStrategy(up.evict_strategy)
+    self._table = _DeviceTable(key_dtype, value_dtype, default_value, name, device, dim=dim, aux_fields=aux_fields,
+                               init_capacity=up.init_capacity, max_capacity=up.max_capacity, max_hbm_for_values=up.max_hbm_for_values,
+                               strategy=int(self._evict_strategy), step_per_epoch=up.step_per_epoch,
+                               reserved_key_start_bit=up.reserved_key_start_bit, aux_init=aux_init)
+    self._lower = _DeviceTable(key_dtype, value_dtype, default_value, name + "_lower", device, dim=dim, aux_fields=aux_fields,
+                               init_capacity=init_size or int(os.environ.get("TF_HASHTABLE_INIT_SIZE", 8192)), max_capacity=0,
+                               strategy=-1, aux_init=aux_init)
+    self._tier = _DeviceTier(self._table, self._lower, config.max_batch)
+    self._aux_fields = aux_fields
+    self._default_value = self._table._default_value
+    self._device = self._table.device
+
+  def _chunks(self, n):
+    mb = self._tier.max_batch
+    return [(a, min(a + mb, n)) for a in range(0, n, mb)]
+
+  def size(self, name=None):
+    """The number of distinct keys of the two tiers, a scalar int64 device tensor."""
+    uk, _ = _export_or_empty(self._table, values=False)
+    below = self._lower.size_device()
+    return below + (~self._lower.contains(uk)).sum() if uk.numel() else below
+
+  def remove(self, keys, name=None):
+    self._table.erase(keys)
+    self._lower.erase(keys)
+
+  def clear(self, name=None):
+    self._table.clear_all()
+    self._lower.clear_all()
+
+  def lookup(self, keys, dynamic_default_values=None, return_exists=False, name=None):
+    """A read of both tiers (`_DeviceTier.find`): nothing moves."""
+    keys = torch.as_tensor(keys, device=self._device) if not torch.is_tensor(keys) else keys
+    flat = keys.reshape(-1)
+    n, dim = flat.numel(), self._table.dim
+    d = dynamic_default_values
+    full = d is not None and torch.is_tensor(d) and d.numel() == n * dim and n > 1
+    rows = torch.empty((n, dim), dtype=self._value_dtype, device=self._device)
+    where = torch.zeros(n, dtype=torch.uint8, device=self._device)
+    for a, b in self._chunks(n):
+      r, w = self._tier.find(flat[a:b], d.reshape(n, dim)[a:b] if full else d, return_where=True)
+      rows[a:b], where[a:b] = r, w
+    rows = rows.reshape(tuple(keys.shape) + (dim,))
+    return (rows, (where != 0).reshape(keys.shape)) if return_exists else rows
+
+  def find_or_insert(self, keys, dynamic_default_values=None, return_exists=False, name=None, count=None):
+    """The admitting lookup through both tiers (`_DeviceTier.find_or_insert`): UNIQUE keys, at most `max_batch` of them.  exists[i]
+    is False for a key neither tier held."""
+    keys = torch.as_tensor(keys, device=self._device) if not torch.is_tensor(keys) else keys
+    rows, where = self._tier.find_or_insert(keys, dynamic_default_values, return_where=True, count=count)
+    return (rows, where != 0) if return_exists else rows
+
+  def find_or_insert_planned(self, plan, dynamic_default_values=None, return_exists=False, name=None):
+    raise NotImplementedError("TieredHashTable has no planned admitting lookup: look the ids up with find_or_insert")
+
+  def lookup_missed(self, keys, dynamic_default_values=None, name=None):
+    """`lookup` plus the pairs (key, position) that NEITHER tier holds (one host read for their number)."""
+    return self._shard_find_missed(keys, dynamic_default_values, False)
+
+  def _shard_find_missed(self, keys, defaults, return_exists):
+    keys = torch.as_tensor(keys, device=self._device) if not torch.is_tensor(keys) else keys
+    rows, exists = self.lookup(keys, defaults, return_exists=True)
+    mi = torch.nonzero(~exists.reshape(-1)).reshape(-1)
+    out = (rows, keys.reshape(-1)[mi], mi.to(torch.int32))
+    return out + (exists,) if return_exists else out
+
+  def insert(self, keys, values, name=None):
+    """upsert of embedding rows (UNIQUE keys) into the cache; what that displaces goes down with its slots (`_DeviceTier.insert`)."""
+    keys = torch.as_tensor(keys, device=self._device) if not torch.is_tensor(keys) else keys
+    values = torch.as_tensor(values, device=self._device) if not torch.is_tensor(values) else values
+    flat, n = keys.reshape(-1), keys.numel()
+    vals = values.reshape(n, self._table.dim)
+    for a, b in self._chunks(n):
+      self._tier.insert(flat[a:b], vals[a:b])
+
+  def assign(self, keys, values, name=None):
+    """The write that only hits, in both tiers: a key the cache holds gets its row there, and whatever copy the lower tier has is
+    overwritten too (a stale copy of a promoted key is never read: the upper table wins)."""
+    self._shard_assign(keys, values, False)
+
+  def _shard_assign(self, keys, values, return_found):
+    keys = torch.as_tensor(keys, device=self._device) if not torch.is_tensor(keys) else keys
+    up = self._table.assign(keys, values, return_found=return_found)
+    lo = self._lower.assign(keys, values, return_found=return_found)
+    return (up | lo) if return_found else None
+
+  def accum(self, keys, values_or_deltas, exists, name=None):
+    raise NotImplementedError("TieredHashTable does not serve accum (bp_v2)")
+
+  def contains(self, keys, name=None):
+    return self._table.contains(keys) | self._lower.contains(keys)
+
+  def export(self, name=None):
+    """The lower tier's export with the upper tier's rows over it."""
+    uk, uv = _export_or_empty(self._table)
+    lk, lv = _export_or_empty(self._lower)
+    if not uk.numel() or not lk.numel():
+      return (lk, lv) if not uk.numel() else (uk, uv)
+    keep = ~self._table.contains(lk)
+    return torch.cat([uk, lk[keep]]), torch.cat([uv, lv[keep]])
+
+  def flush(self):
+    """Every key of the cache gets its whole row copied to the lower tier, field by field (export, find(field=), upsert(field=)):
+    afterwards the lower table alone holds everything.  The cache is unchanged."""
+    uk, uv = _export_or_empty(self._table)
+    if not uk.numel():
+      return
+    self._lower.upsert(uk, uv, unique_keys=True)
+    for f in range(1, self._aux_fields + 1):
+      self._lower.upsert(uk, self._table.find(uk, field=f), field=f)
+
+  def _checkpoint_table(self):
+    return self._lower
+
+  def _checkpoint_flush(self):
+    self.flush()
+
+  def _checkpoint_loaded(self):
+    self._table.clear_all()   # everything was loaded below: the cache fills again from there
+
+
 def _device_table(x):
-  """`x` if it is a _DeviceTable, the device table of a CuckooHashTable / HkvHashTable."""
+  """`x` if it is a _DeviceTable, the device table of a CuckooHashTable / HkvHashTable (a TieredHashTable: its cache)."""
   return getattr(x, "_table", x)
 
 

@@ -15,7 +15,7 @@ partition -> per-shard table op -> stitch, the partition/stitch being device ker
 import torch
 
 from . import device_ops
-from .table_ops import CuckooHashTable, HkvHashTable, HkvEvictStrategy, _as_device, _score_filter
+from .table_ops import CuckooHashTable, HkvHashTable, HkvEvictStrategy, TieredHashTable, _as_device, _score_filter
 
 
 def default_partition_fn(keys, shard_num):
@@ -77,6 +77,32 @@ class HkvHashTableCreator(KVCreator):
                         checkpoint=checkpoint, config=cfg, device=device, **kw)
 
 
+class TieredHashTableConfig:
+  """A bounded cache in front of a growing table (`TieredHashTable`).  upper: the HkvHashTableConfig of the cache — LRU or EPOCHLRU,
+  init_capacity == max_capacity so that it evicts from the start; lower: the CuckooHashTableConfig of the table below; max_batch:
+  the most keys one lookup or insert may carry (the tier driver's staging is sized by it)."""
+
+  def __init__(self, upper=None, lower=None, max_batch=1 << 18):
+    self.upper = upper if upper is not None else HkvHashTableConfig()
+    self.lower = lower if lower is not None else CuckooHashTableConfig()
+    self.max_batch = int(max_batch)
+
+
+class TieredHashTableCreator(KVCreator):
+  """Creates `TieredHashTable` shards: `Variable(kv_creator=TieredHashTableCreator(TieredHashTableConfig(...)))`."""
+
+  def create(self, key_dtype=None, value_dtype=None, default_value=None, name=None, checkpoint=None, init_size=None,
+             config=None, device=None, shard_saveable_object_fn=None, **kw):
+    cfg = config or self.config or TieredHashTableConfig()
+    return TieredHashTable(key_dtype=key_dtype, value_dtype=value_dtype, default_value=default_value, name=name,
+                           checkpoint=checkpoint, config=cfg, device=device, init_size=init_size or 0, **kw)
+
+
+def _has_tiered_shards(var):
+  """Whether `var` (a Variable, or anything with its `_tables`) keeps its rows in TieredHashTable shards."""
+  return any(isinstance(t, TieredHashTable) for t in getattr(var, "_tables", ()))
+
+
 def misses_are_static(var):
   """Whether a key the optimizer write-back does not find may start from the ONE static default row of `var` (a Variable, or
   anything with its `initializer`): there is no callable initializer, or the step's lookup has admitted every key with its own
@@ -95,7 +121,10 @@ class Variable:
   and the row that is updated is the row the forward pass returned — with False the write-back draws a second row from the
   initializer for every miss.  Optimizer slots start at aux_init when the lookup admits the key.
   One limit: a key that was looked up but is not resident at write-back time — evicted in between, or not admitted by a table at
-  max_capacity under LFU / CUSTOMIZED — is updated from the static default row, as in every fused write-back.
+  max_capacity under LFU / CUSTOMIZED — is updated from the static default row, as in every fused write-back.  Over tiered shards
+  (`TieredHashTableCreator`: a bounded cache in front of a growing table, whole rows moving between them) the lookup leaves every key
+  of the batch in the cache, and the same limit has one more case: a batch that fills both home buckets of one of its own keys with
+  its own keys (30 slots) cannot keep that key in the cache; its row is safe below, but the write-back restarts it from the default row.
   Plain lookups (`lookup`, `embedding_lookup` without return_trainable, the pooled forward) never admit, with either setting.
 
   init_on_lookup="plan": True for every predicate above, and `embedding_lookup(..., return_trainable=True)` of repeating ids on a
@@ -295,8 +324,9 @@ class Variable:
 
   def admits_on_lookup(self):
     """Whether a training step's lookup admits never-seen keys: init_on_lookup, and a callable initializer to draw their rows
-    from (with a static default row a miss reads the row the write-back starts from anyway)."""
-    return bool(self.init_on_lookup) and callable(self.initializer)
+    from (with a static default row a miss reads the row the write-back starts from anyway).  Over tiered shards the lookup
+    always admits, static default row or not: a key that is below must be promoted before the write-back, which acts on the cache."""
+    return (bool(self.init_on_lookup) and callable(self.initializer)) or _has_tiered_shards(self)
 
   def lookup_or_insert(self, keys, return_exists=False, name=None):
     """`lookup` that admits (find_or_insert per shard): a key that is not resident enters its table with the row this call
@@ -332,7 +362,7 @@ class Variable:
     that are not resident and their positions in the flattened batch (int64, index-aligned, in no particular order; a missing
     key that repeats is listed at every position).  Never inserts.  A callable initializer draws the defaults per shard, as
     `lookup` does.  A shard reports positions in its slice of the owner-major key list; they are mapped back through the
-    partition's permutation (owner_major = flat[perm])."""
+    partition's permutation (owner_major = flat[perm]).  A tiered shard lists the keys NEITHER of its tiers holds."""
     keys = torch.as_tensor(keys, device=self._primary)
     kp, perm, counts = self._partition(keys)
     vals, exs, mks, mps = [], [], [], []
@@ -340,7 +370,7 @@ class Variable:
     for i, t in enumerate(self._tables):
       k = kp[i].to(t._device)
       dd = self._create_default_values_by_initializer(k.numel(), t._device)
-      r = t.resource_handle.find_missed(k, dd, return_exists=return_exists)
+      r = t._shard_find_missed(k, dd, return_exists)
       vals.append(r[0].to(self._primary))
       mks.append(r[1].to(self._primary))
       pos = r[2].to(self._primary).to(torch.int64)
@@ -356,7 +386,7 @@ class Variable:
   def assign(self, keys, values, return_found=False, name=None):
     """`upsert` for the keys that are resident; the others change nothing — they are not inserted and nothing is evicted for them
     (assign per shard).  `keys` must be UNIQUE.  -> None, or found (bool, shaped like keys): False = send the row to the tier
-    that holds the key.  `size()` never changes."""
+    that holds the key.  `size()` never changes.  A tiered shard writes the row in both of its tiers (found: in either)."""
     keys = torch.as_tensor(keys, device=self._primary)
     values = torch.as_tensor(values, device=self._primary)
     want = tuple(keys.shape) + (self.dim,)
@@ -367,7 +397,7 @@ class Variable:
     fs = []
     for i, t in enumerate(self._tables):
       k = kp[i].to(t._device)
-      f = t.resource_handle.assign(k, vp[i].to(t._device), scores=t._gen_scores(k), return_found=return_found)
+      f = t._shard_assign(k, vp[i].to(t._device), return_found)
       if return_found:
         fs.append(f.to(self._primary))
     return self._scatter_flags(fs, perm, keys.shape) if return_found else None
@@ -512,8 +542,8 @@ class Variable:
     for idx, t in enumerate(self._tables):
       t.save_to_file_system(dirpath, file_name=self._make_name(idx) + suffix, dirpath_env=None, buffer_size=buffer_size)
       for f, base in slots.items():
-        t._table.save(os.path.join(dirpath, "{}_mht_{}of{}{}".format(base, idx + 1, self.shard_num, suffix)), buffer_size,
-                      field=f)
+        t._checkpoint_table().save(os.path.join(dirpath, "{}_mht_{}of{}{}".format(base, idx + 1, self.shard_num, suffix)), buffer_size,
+                                   field=f)
 
   def load_from_file_system(self, dirpath, proc_size=1, proc_rank=0, buffer_size=4194304, optimizer=None):
     """Reload; when the shard count changed, every `_mht_` file is re-read and re-partitioned
@@ -571,7 +601,7 @@ class Variable:
         for f, base in slots.items():
           p = os.path.join(dirpath, "{}_mht_{}of{}".format(base, idx + 1, self.shard_num))
           if os.path.exists(p + "-keys"):
-            t._table.load(p, buffer_size, field=f)
+            t._checkpoint_table().load(p, buffer_size, field=f)
       return
     self.clear()
     key_np = np.int32 if self.key_dtype == torch.int32 else np.int64   # the key files hold raw keys of the key dtype
@@ -580,6 +610,8 @@ class Variable:
       vals = torch.from_numpy(np.fromfile(os.path.join(dirpath, fn + "-values"), dtype=np.uint8)).view(
           self.value_dtype).reshape(-1, self.dim)
       self.upsert(torch.from_numpy(keys).to(self._primary), vals.to(self._primary))
+    for t in self._tables:          # once per shard: the table the state vectors go into holds every embedding row from here on
+      t._checkpoint_flush()
     for f, base in slots.items():   # re-sharded restore of the state vectors: through the same partitioner
       for fn in slot_files(base):
         keys = torch.from_numpy(np.fromfile(os.path.join(dirpath, fn + "-keys"), dtype=key_np)).to(self._primary)
@@ -589,7 +621,9 @@ class Variable:
         vp = self._split_rows(vals, perm, counts)
         for i, t in enumerate(self._tables):
           if kp[i].numel():
-            t._table.upsert(kp[i].to(t._device), vp[i].to(t._device), field=f)
+            t._checkpoint_table().upsert(kp[i].to(t._device), vp[i].to(t._device), field=f)
+    for t in self._tables:
+      t._checkpoint_loaded()
 
 
 _VARIABLES = {}
@@ -754,7 +788,8 @@ class TrainableWrapper:
     params, ids = self.params, self.ids
     if params.shard_num == 1:
       t = params._tables[0]
-      plan = self._plan_for_lookup() if params.init_on_lookup == "plan" and not self._ids_are_unique else None
+      planned = params.init_on_lookup == "plan" and not self._ids_are_unique and not _has_tiered_shards(params)   # (a tier: the True route)
+      plan = self._plan_for_lookup() if planned else None
       init = params._create_default_values_by_initializer(ids.numel(), t._device)
       if plan is not None:
         return t.find_or_insert_planned(plan, dynamic_default_values=init)
