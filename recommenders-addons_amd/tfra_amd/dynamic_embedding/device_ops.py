@@ -5,7 +5,7 @@ import ctypes
 import torch
 
 from .. import _capi
-from .table_ops import _narrow_keys, _ptr, _stream, _wide_keys
+from ._args import _narrow_keys, _ptr, _stream, _wide_keys
 
 _WS = {}
 

@@ -20,6 +20,9 @@ injectable so the routing logic can be exercised on CPU with stand-ins (tests/te
 import torch
 import torch.distributed as dist
 
+from ._args import _driver_ids, _narrow_keys, _stream
+from .table_ops import SparsePlan
+
 
 def _partition_mode(partition_mode, key_dtype):
   """An explicit partition mode as given; None = default_partition_fn's rule for the table's key dtype (mask-mod for int64 keys,
@@ -214,7 +217,6 @@ class RoutedPrefetchStep:
 
   def __init__(self, var, optimizer, group=None, partition_mode=None, force_collectives=False):
     from .optimizer import DynamicEmbeddingOptimizer, _refuse_init_on_lookup
-    from .table_ops import SparsePlan
     _refuse_init_on_lookup(var, "RoutedPrefetchStep")
     if var.shard_num != 1 or not DynamicEmbeddingOptimizer.can_plan(var, 1) or var.value_dtype != torch.float32:   # (the route ships fp32 rows)
       raise ValueError("RoutedPrefetchStep needs a single-shard fp32 local Variable with dim % 4 == 0, dim <= 256")
@@ -254,7 +256,6 @@ class RoutedPrefetchStep:
     current stream (the second stream then waits for it)."""
     if self.fed >= self.NSLOTS - 1:
       raise RuntimeError("RoutedPrefetchStep: %d batches are fed ahead already" % self.fed)
-    from .table_ops import _driver_ids
     sl = self.slots[self.tail]
     ids = _driver_ids(self.table, ids, self.dev, widen=False)   # int32-key tables: the ids stay int32 along the route
     if not ids_ready:
@@ -522,7 +523,6 @@ class NativeRoutedStep:
     return self._ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(self.dev.index or 0))
 
   def feed(self, ids, ids_ready=True):
-    from .table_ops import _driver_ids
     ids = _driver_ids(self.table, ids, self.dev)
     if self.table.key_dtype == torch.int32:
       ids_ready = False   # widened on the current stream just now: the driver's stream must wait for that
@@ -559,7 +559,6 @@ class NativeRoutedStep:
         torch.cuda.current_stream(self.dev).synchronize()   # the ids arrived on the driver's second stream
         if _hip().hipMemcpy(served.data_ptr(), ptr, nr * 8, 3) != 0:
           raise RuntimeError("NativeRoutedStep: copy of the served ids failed")
-        from .table_ops import _narrow_keys
         self.var.restrict_policy.apply_update(_narrow_keys(served, self.table.key_dtype))
     self._call("tfra_route_apply", self._h, self._ctypes.byref(p), self._ctypes.c_void_p(g.data_ptr()),
                self._ctypes.c_void_p(self.default.data_ptr()), self._stream())
@@ -697,7 +696,6 @@ class RoutedAssignStep:
     return self._ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(self.dev.index or 0))
 
   def _as_ids(self, ids):
-    from .table_ops import _driver_ids
     return _driver_ids(self.table, ids, self.dev)
 
   def feed(self, ids, ids_ready=False):
@@ -738,7 +736,6 @@ class RoutedAssignStep:
   def _identity_step(self, vp, out):
     # one rank, no route: tfra_table_step_overlap itself — the announced batches are its look-ahead (the values of a batch arrive one
     # call later, as in the routed form: the driver defers the write-back)
-    from .table_ops import _stream
     o, c = self._ovl, self._ctypes
     ids = self._fed[0]
     n = ids.numel()
@@ -756,7 +753,6 @@ class RoutedAssignStep:
       return
     vp = self._values(values_prev, self._pending[0].numel())
     if self.identity:
-      from .table_ops import _stream
       self._capi.call("tfra_table_step_overlap_flush", self._ovl._h, self._ctypes.c_void_p(vp.data_ptr()), None, _stream(self.dev))
     else:
       self._call("tfra_assign_route_flush", self._h, self._ctypes.c_void_p(vp.data_ptr()), self._stream())

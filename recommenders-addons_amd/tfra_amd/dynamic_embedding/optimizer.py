@@ -19,8 +19,9 @@ import torch
 
 from .. import _capi
 from . import device_ops
-from .table_ops import _driver_ids, _narrow_keys
-from .variable import SparseTrainableWrapper, TrainableWrapper, Variable, misses_are_static
+from ._args import _driver_ids, _narrow_keys, _ptr, _stream
+from .table_ops import SparsePlan, apply_planned_combined_many, build_plans_many
+from .variable import SparseTrainableWrapper, TrainableWrapper, Variable, _pool_plan, _release_plan, misses_are_static
 
 
 class _Opt:
@@ -260,7 +261,6 @@ class DynamicEmbeddingOptimizer:
         self.apply_sparse(tw.params, tw.ids, grad, p, plan=plan)
       finally:
         if plan is not None:
-          from .variable import _release_plan
           _release_plan(tw.params, plan)
 
   def apply_combined_gradients(self, grads_and_vars, name=None):
@@ -287,13 +287,10 @@ class DynamicEmbeddingOptimizer:
       fused = (self.opt.kind is not None and not self.exact_order and not var.bp_v2 and n > 0 and self.can_plan(var, n))
       if not fused:
         if plan is not None:
-          from .variable import _release_plan
           _release_plan(var, plan)
         eg = device_ops.sparse_segment_combine_backprop(g, tw.seg, tw.weights, tw.combiner)
         self.apply_sparse(var, tw.entry_ids, eg, p)
         continue
-      from .table_ops import SparsePlan
-      from .variable import _pool_plan, _release_plan
       pooled = True
       if plan is None:
         plan = _pool_plan(var)
@@ -320,8 +317,6 @@ class DynamicEmbeddingOptimizer:
     Every other pair takes `apply_combined_gradients`' path for it.  A variable that occurs a second time closes the current
     groups first, so the order of the write-backs of one variable is the list's.  Tables and slots end bit-identical to
     `apply_combined_gradients` over the same list."""
-    from .table_ops import SparsePlan, apply_planned_combined_many, build_plans_many
-    from .variable import _pool_plan, _release_plan
     pairs = []
     for grad_out, tw in grads_and_vars:
       if not isinstance(tw, SparseTrainableWrapper):
@@ -425,7 +420,6 @@ class DynamicEmbeddingOptimizer:
     """Build (or rebuild) the id-only half of `apply_sparse(var, ids, ...)` on the current stream; pass the
     result as `apply_sparse(..., plan=plan)`.  Call it under `torch.cuda.stream(side_stream)` to overlap it
     with the lookup of the same ids or with the previous step."""
-    from .table_ops import SparsePlan
     ids = torch.as_tensor(ids, device=var._primary).reshape(-1)
     if not self.can_plan(var, ids.numel()) or self.exact_order or self.opt.kind is None:
       raise ValueError("this variable / batch / optimizer takes the unique + segment_sum write-back, which has no plan")
@@ -577,7 +571,6 @@ class PrefetchStep:
   NPLANS = 4
 
   def __init__(self, var, optimizer):
-    from .table_ops import SparsePlan
     _refuse_init_on_lookup(var, "PrefetchStep")
     if var.shard_num != 1 or not DynamicEmbeddingOptimizer.can_plan(var, 1):
       raise ValueError("PrefetchStep needs a single-shard float32 / float16 / bfloat16 Variable with dim % 4 == 0, dim <= 256")
@@ -606,7 +599,6 @@ class PrefetchStep:
     memory when this is called (a batch staged by the input pipeline).  Pass False when it is still being produced
     on the current stream (device-side hashing, an async H2D copy): the second stream then waits for it (one
     cross-stream event per step)."""
-    from .table_ops import _ptr
     cur = self.cur
     nxt_slot = (cur + 1) % self.NPLANS
     ids = self.ids[cur]
@@ -650,7 +642,6 @@ class MultiTablePrefetchStep:
   NPLANS = 4
 
   def __init__(self, variables, optimizer, streams=4, workers=1):
-    from .table_ops import SparsePlan
     self.vars, self.deo, self.workers = list(variables), optimizer, int(workers)
     for v in self.vars:
       _refuse_init_on_lookup(v, "MultiTablePrefetchStep")
@@ -760,7 +751,6 @@ class PrefetchAssignStep:
   NPLANS = 4
 
   def __init__(self, table):
-    from .table_ops import SparsePlan
     self.t = table
     self.table = table._table if hasattr(table, "_table") else table
     self.dev = self.table.device
@@ -909,7 +899,6 @@ class OverlapAssignStep:
     """next_ids / next2_ids: the ids of the next step and of the one after it (an input pipeline knows them): with both, the
     de-duplication plan of a batch is built inside the step launches, without atomics; with next_ids only, by a launch of its
     own per step; with neither, in front of the next step."""
-    from .table_ops import _stream
     ids = self._ids
     if ids is None:
       raise RuntimeError("OverlapAssignStep.step: no batch is primed — call prime(ids) first (and again after a step that "
@@ -935,7 +924,6 @@ class OverlapAssignStep:
     return (out, ex) if return_exists else out
 
   def flush(self):
-    from .table_ops import _stream
     if self._pending is not None:
       _capi.call("tfra_table_step_overlap_flush", self._h, ctypes.c_void_p(self._pending[1].data_ptr()), None, _stream(self.dev))
       self._keep = self._pending
@@ -984,7 +972,6 @@ class OverlapAssignStep:
     the run starts (None: nothing pending); ids_after / ids_after2 = the ids of the two steps behind the run (their plans are
     built / started by the run's last launches).  The caller keeps every tensor alive and unchanged until the run has executed.
     Ids that are not already the engine's int64 ids (those of an int32-key table) are converted here, when the run is made."""
-    from .table_ops import _stream
     ids_list = [self._as_ids(x) for x in ids_list]
     ids_after = None if ids_after is None else self._as_ids(ids_after)
     ids_after2 = None if ids_after2 is None else self._as_ids(ids_after2)

@@ -20,7 +20,7 @@ FORWARD of a safe trainable lookup is sync-free: the wrapper's entry list (prune
 made by the tuple form's preprocessing as it is, host syncs included."""
 import torch
 
-from . import device_ops
+from . import device_ops, table_ops
 from .variable import (SparseTrainableWrapper, _check_combiner, _note_pruned, _per_table, _pooled_forward, _safe_sparse_args,
                        _wrap_grouped)
 from . import variable as _tuple_form
@@ -124,7 +124,6 @@ def safe_embedding_lookup_sparse(params, sparse_ids, sparse_weights=None, combin
 
 
 def _many(params_list, sp_ids_list, weights_list, combiner, default_id, safe, return_trainable, plan_writeback):
-  from . import table_ops
   n_t = len(params_list)
   if len(sp_ids_list) != n_t:
     raise ValueError("sp_ids_list: %d entries for %d tables" % (len(sp_ids_list), n_t))

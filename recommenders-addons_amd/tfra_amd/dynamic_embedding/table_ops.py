@@ -22,16 +22,9 @@ import sys
 import torch
 
 from .. import _capi
-
-_TORCH2DT = {
-    torch.float32: _capi.TFRA_F32,
-    torch.float16: _capi.TFRA_F16,
-    torch.bfloat16: _capi.TFRA_BF16,
-    torch.int8: _capi.TFRA_I8,
-    torch.int32: _capi.TFRA_I32,
-    torch.int64: _capi.TFRA_I64,
-    torch.float64: _capi.TFRA_F64,
-}
+from ._args import (_TORCH2DT, _admitted_rows, _as_device, _as_tensor, _cap_for, _check_plan, _default_rows, _driver_ids,
+                    _narrow_keys, _out_rows, _over_plans, _ptr, _score_filter, _scores_for, _stream, _trim_to_count, _wide_keys)
+from .device_ops import _workspace
 
 KHkvHashTableInitCapacity = 1024 * 1024  # PY/hkv_hashtable_ops.py:40-44
 KHkvHashTableMaxCapacity = 1024 * 1024
@@ -45,101 +38,6 @@ class HkvEvictStrategy(enum.IntEnum):
   EPOCHLRU = 2
   EPOCHLFU = 3
   CUSTOMIZED = 4
-
-
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-
-def _stream(device):
-  """The current HIP stream of `device` as a void*.  torch.cuda.current_stream() builds a Stream object through several
-  Python layers (5 us per call, 18 calls in one routed multi-GPU step): the raw getter is the same value in 0.3 us."""
-  if _raw_stream is not None:
-    idx = device.index if isinstance(device, torch.device) else torch.device(device).index
-    return ctypes.c_void_p(_raw_stream(idx if idx is not None else torch.cuda.current_device()))
-  return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _ptr(t):
-  return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _workspace(device):   # device_ops imports this module: its _workspace is looked up at call time
-  from .device_ops import _workspace as workspace
-  return workspace(device)
-
-
-def _wide_keys(keys):
-  """`keys` as the engine's int64 keys, for a C function that reads `const int64_t*`: int64 keys as they are, int32 keys widened on
-  the device (tfra_keys_widen_i32).  Any other dtype raises TypeError before a launch."""
-  if keys.dtype == torch.int64:
-    return keys.contiguous()
-  if keys.dtype != torch.int32:
-    raise TypeError("keys must be torch.int64 or torch.int32, got %s" % keys.dtype)
-  keys = keys.contiguous()
-  wide = torch.empty(keys.shape, dtype=torch.int64, device=keys.device)
-  if keys.numel():
-    _capi.call("tfra_keys_widen_i32", keys.numel(), _ptr(keys), _ptr(wide), _stream(keys.device))
-  return wide
-
-
-def _narrow_keys(keys, dtype):
-  """Engine int64 keys back in the caller's key dtype: int32 keys narrowed on the device (tfra_keys_narrow_i32), int64 as they
-  are.  Only keys that came from int32 keys are narrowed, so none can overflow."""
-  if dtype == torch.int64:
-    return keys
-  narrow = torch.empty(keys.shape, dtype=torch.int32, device=keys.device)
-  if keys.numel():
-    _capi.call("tfra_keys_narrow_i32", keys.numel(), _ptr(keys.contiguous()), _ptr(narrow), None, _stream(keys.device))
-  return narrow
-
-
-def _driver_ids(table, ids, device, widen=True):
-  """The ids of a step or route driver, as the int64 buffer its C calls read.  An int32-key table takes int32 ids only — int64 ids
-  raise TypeError before any launch, as the table's own ops do, so that no key above 2^31 can enter it — and widens them (or,
-  widen=False, keeps them as they are); an int64-key table casts whatever integer ids it is given, as it always has."""
-  if table.key_dtype == torch.int32:
-    ids = torch.as_tensor(ids, device=device) if not torch.is_tensor(ids) else ids
-    if ids.dtype != torch.int32:
-      raise TypeError("Signature mismatch. Keys must be dtype %s, got %s." % (torch.int32, ids.dtype))
-    ids = ids.to(device).reshape(-1).contiguous()
-    return _wide_keys(ids) if widen else ids
-  if torch.is_tensor(ids) and ids.dtype == torch.int64 and ids.dim() == 1 and ids.is_contiguous() and ids.device == device:
-    return ids
-  return torch.as_tensor(ids, device=device).reshape(-1).to(torch.int64).contiguous()
-
-
-def _score_filter(threshold, pred):
-  """(tfra_score_pred, threshold) of a score-filtered call: `pred` is the string "ge" (score >= threshold) or "lt" (score <
-  threshold), the threshold an integer in [0, 2^64).  Anything else raises ValueError before a launch."""
-  if pred not in ("ge", "lt"):
-    raise ValueError("pred must be 'ge' or 'lt', got %r" % (pred,))
-  try:
-    thr = int(threshold)
-  except (TypeError, ValueError):
-    raise ValueError("threshold must be an integer in [0, 2^64), got %r" % (threshold,))
-  if not 0 <= thr < (1 << 64):
-    raise ValueError("threshold must be in [0, 2^64), got %r" % (threshold,))
-  return (_capi.SCORE_GE if pred == "ge" else _capi.SCORE_LT), thr
-
-
-def _as_device(device):
-  if device is None or device == "" or device == []:
-    device = "cuda:0"
-  if isinstance(device, (list, tuple)):
-    device = device[0]
-  if isinstance(device, str):
-    d = device.strip().lower().replace("/", "")
-    # TF-style '/GPU:0' / '/device:GPU:0'
-    if "gpu" in d:
-      device = "cuda:" + d.split(":")[-1]
-  dev = torch.device(device)
-  if dev.type != "cuda":
-    raise RuntimeError(
-        "tfra_amd tables live on an MI355X (device %r requested); there is no CPU fallback" %
-        (device,))
-  if not torch.cuda.is_available():
-    raise RuntimeError("no HIP device visible: tfra_amd has no CPU fallback")
-  return torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
 
 
 class _DeviceTable:
@@ -217,13 +115,13 @@ class _DeviceTable:
     return self._value_dtype
 
   def _keys(self, keys):
-    keys = torch.as_tensor(keys, device=self._device) if not torch.is_tensor(keys) else keys
+    keys = _as_tensor(keys, self._device)
     if keys.dtype != self._key_dtype:
       raise TypeError("Signature mismatch. Keys must be dtype %s, got %s." % (self._key_dtype, keys.dtype))
     return _wide_keys(keys.to(self._device))   # the engine's keys are int64
 
   def _values_for(self, keys, values, what="values"):
-    values = torch.as_tensor(values, device=self._device) if not torch.is_tensor(values) else values
+    values = _as_tensor(values, self._device)
     if values.dtype != self._value_dtype:
       raise TypeError("Signature mismatch. %s must be dtype %s, got %s." % (what, self._value_dtype, values.dtype))
     want = tuple(keys.shape) + (self._dim,)
@@ -232,21 +130,22 @@ class _DeviceTable:
       raise ValueError("Expected shape %s for %s, got %s" % (list(want), what, list(values.shape)))
     return values.to(self._device).contiguous()
 
+  # the rows and out= operands of this table's lookups (None: the table's default row), by `_args`' rules -> (rows, is_full) / out
+  def _defaults(self, rows, n):
+    return _default_rows(self._value_dtype, self._dim, self._device, self._default_value if rows is None else rows, n * self._dim)
+
+  def _init_rows(self, rows, n, what="init values"):
+    return _admitted_rows(self._value_dtype, self._dim, self._device, self._default_value if rows is None else rows, n, what)
+
+  def _out(self, shape, out):
+    return _out_rows(self._value_dtype, self._dim, self._device, shape, out)
+
   # ---- ops ---------------------------------------------------------------------------------
   def find(self, keys, dynamic_default_values=None, return_exists=False, field=0):
     keys = self._keys(keys)
     n = keys.numel()
-    d = self._default_value if dynamic_default_values is None else dynamic_default_values
-    d = torch.as_tensor(d, device=self._device) if not torch.is_tensor(d) else d.to(self._device)
-    if d.dtype != self._value_dtype:
-      raise TypeError("default values must be dtype %s, got %s" % (self._value_dtype, d.dtype))
-    d = d.contiguous()
+    d, full = self._defaults(dynamic_default_values, n)
     out = torch.empty(tuple(keys.shape) + (self._dim,), dtype=self._value_dtype, device=self._device)
-    # is_full_default = (value_flat.size() == default_flat.size())
-    # (R/kernels/hkv_hashtable_op_gpu.cu.cc:188-190, cuckoo_hashtable_op.cc:48-50)
-    full = int(out.numel() == d.numel())
-    if not full and d.numel() < self._dim:
-      raise ValueError("default value needs at least dim=%d elements, got %d" % (self._dim, d.numel()))
     exists = torch.empty(keys.shape, dtype=torch.bool, device=self._device) if return_exists else None
     if n:
       if field:
@@ -263,15 +162,8 @@ class _DeviceTable:
     particular order —, idx [n] int32 with unique[idx] == keys, count: device int64 scalar[, exists]).  Nothing is read on the host."""
     keys = self._keys(keys).reshape(-1)
     n = keys.numel()
-    d = self._default_value if dynamic_default_values is None else dynamic_default_values
-    d = torch.as_tensor(d, device=self._device) if not torch.is_tensor(d) else d.to(self._device)
-    if d.dtype != self._value_dtype:
-      raise TypeError("default values must be dtype %s, got %s" % (self._value_dtype, d.dtype))
-    d = d.contiguous()
+    d, full = self._defaults(dynamic_default_values, n)
     out = torch.empty((n, self._dim), dtype=self._value_dtype, device=self._device)
-    full = int(out.numel() == d.numel())
-    if not full and d.numel() < self._dim:
-      raise ValueError("default value needs at least dim=%d elements, got %d" % (self._dim, d.numel()))
     exists = torch.empty(n, dtype=torch.bool, device=self._device) if return_exists else None
     uniq = torch.empty(n, dtype=torch.int64, device=self._device)
     idx = torch.empty(n, dtype=torch.int32, device=self._device)
@@ -389,12 +281,7 @@ class _DeviceTable:
     if n == 0:
       return
     flags = _capi.FLAG_UNIQUE_KEYS if unique_keys else 0
-    if scores is not None and scores.numel() == 0:
-      scores = None  # HkvHashTableInsert: empty scores tensor == no scores
-    if scores is not None:
-      scores = scores.to(self._device, torch.int64).contiguous()
-      if scores.numel() != n:
-        raise ValueError("scores must have one entry per key")
+    scores = _scores_for(scores, n, self._device)
     if field:
       _capi.call("tfra_table_insert_field", self._h, field, n, _ptr(keys), _ptr(values), flags, _stream(self._device))
     else:
@@ -423,15 +310,8 @@ class _DeviceTable:
     else:
       values = self._values_for(keys, values)
     n = keys.numel()
-    if scores is not None and scores.numel() == 0:
-      scores = None
-    if scores is not None:
-      scores = scores.to(self._device, torch.int64).contiguous()
-      if scores.numel() != n:
-        raise ValueError("scores must have one entry per key")
-    cap = n if cap is None else int(cap)
-    if cap < 0:
-      raise ValueError("cap must be >= 0, got %d" % cap)
+    scores = _scores_for(scores, n, self._device)
+    cap = _cap_for(cap, n)
     width = self._dim * (1 + self._aux_fields if whole_rows else 1)
     counter = torch.zeros(1, dtype=torch.int64, device=self._device)
     ek = torch.empty(cap, dtype=torch.int64, device=self._device)
@@ -447,8 +327,7 @@ class _DeviceTable:
                  flags, _ptr(counter), cap, _ptr(ek), _ptr(ev), _ptr(es), _stream(self._device))
     if not sync:
       return counter, ek, ev, es   # (the keys stay int64 here: narrowing the unwritten tail would read it)
-    m = min(int(counter.item()), cap)
-    return _narrow_keys(ek[:m], self._key_dtype), ev[:m], es[:m]
+    return _trim_to_count(counter, cap, ek, self._key_dtype, ev, es)
 
   def find_or_insert(self, keys, init_values=None, scores=None, return_exists=False, count=None, out=None):
     """The lookup that admits (tfra_table_find_or_insert): the resident row of every key that has one; a key that has none is
@@ -459,24 +338,9 @@ class _DeviceTable:
     every key that was not resident before the call, admitted or not.  Nothing is read on the host."""
     keys = self._keys(keys)
     n = keys.numel()
-    d = self._default_value if init_values is None else init_values
-    d = torch.as_tensor(d, device=self._device) if not torch.is_tensor(d) else d.to(self._device)
-    if d.dtype != self._value_dtype:
-      raise TypeError("init values must be dtype %s, got %s" % (self._value_dtype, d.dtype))
-    d = d.contiguous()
-    full = int(d.numel() == n * self._dim)   # (one key: the two forms are the same row)
-    if not full and d.numel() != self._dim:
-      raise ValueError("init_values must be [n, dim] or one row of dim=%d elements, got shape %s" % (self._dim, list(d.shape)))
-    if out is None:
-      out = torch.empty(tuple(keys.shape) + (self._dim,), dtype=self._value_dtype, device=self._device)
-    elif out.dtype != self._value_dtype or out.numel() != n * self._dim or not out.is_contiguous() or out.device != self._device:
-      raise ValueError("out must be a contiguous %s tensor of %d x %d elements on %s" % (self._value_dtype, n, self._dim, self._device))
-    if scores is not None and scores.numel() == 0:
-      scores = None
-    if scores is not None:
-      scores = scores.to(self._device, torch.int64).contiguous()
-      if scores.numel() != n:
-        raise ValueError("scores must have one entry per key")
+    d, full = self._init_rows(init_values, n)
+    out = self._out(keys.shape, out)
+    scores = _scores_for(scores, n, self._device)
     exists = torch.zeros(keys.shape, dtype=torch.bool, device=self._device) if return_exists else None
     if n:
       _capi.call("tfra_table_find_or_insert", self._h, n, _ptr(count), _ptr(keys), _ptr(d), full, _ptr(scores), _ptr(out),
@@ -490,34 +354,15 @@ class _DeviceTable:
     one row ([dim]; None: the table's default row).  scores: per position, an id takes its last position's.  out: the [n, dim]
     buffer to fill.  -> rows [n, dim], or (rows, exists).  The plan stays usable for `apply_planned` / `upsert_planned`: the
     batch is de-duplicated once.  Nothing is read on the host."""
-    if plan._dim != self._dim or plan._device != self._device:
-      raise ValueError("the plan was built for dim %d on %s" % (plan._dim, plan._device))
+    _check_plan(plan, self._dim, self._device)
     n = plan.n
-    d = self._default_value if init_values is None else init_values
-    d = torch.as_tensor(d, device=self._device) if not torch.is_tensor(d) else d.to(self._device)
-    if d.dtype != self._value_dtype:
-      raise TypeError("init values must be dtype %s, got %s" % (self._value_dtype, d.dtype))
-    d = d.contiguous()
-    full = int(d.numel() == n * self._dim)   # (one id: the two forms are the same row)
-    if not full and d.numel() != self._dim:
-      raise ValueError("init_values must be [n, dim] or one row of dim=%d elements, got shape %s" % (self._dim, list(d.shape)))
-    if out is None:
-      out = torch.empty((n, self._dim), dtype=self._value_dtype, device=self._device)
-    elif out.dtype != self._value_dtype or out.numel() != n * self._dim or not out.is_contiguous() or out.device != self._device:
-      raise ValueError("out must be a contiguous %s tensor of %d x %d elements on %s" % (self._value_dtype, n, self._dim, self._device))
-    if scores is not None and scores.numel() == 0:
-      scores = None
-    if scores is not None:
-      scores = scores.to(self._device, torch.int64).contiguous()
-      if scores.numel() != n:
-        raise ValueError("scores must have one entry per batch position")
+    d, full = self._init_rows(init_values, n)
+    out = self._out((n,), out)
+    scores = _scores_for(scores, n, self._device, per="batch position")
     exists = torch.zeros(n, dtype=torch.bool, device=self._device) if return_exists else None
     if n:
-      stream = torch.cuda.current_stream(self._device)
-      plan._wait_built(stream)
-      _capi.call("tfra_table_find_or_insert_planned", self._h, plan._h, _ptr(d), full, _ptr(scores), _ptr(out), _ptr(exists),
-                 _stream(self._device))
-      plan._mark_used(stream)
+      _over_plans((plan,), self._device, True, _capi.call, "tfra_table_find_or_insert_planned", self._h, plan._h, _ptr(d), full,
+                  _ptr(scores), _ptr(out), _ptr(exists), _stream(self._device))
     return (out, exists) if return_exists else out
 
   # ---- the read side of a tier: find that lists its misses, a write that only hits, membership ----
@@ -534,18 +379,9 @@ class _DeviceTable:
     table: find_n, upsert_n, find_or_insert."""
     keys = self._keys(keys)
     n = keys.numel()
-    d = self._default_value if dynamic_default_values is None else dynamic_default_values
-    d = torch.as_tensor(d, device=self._device) if not torch.is_tensor(d) else d.to(self._device)
-    if d.dtype != self._value_dtype:
-      raise TypeError("default values must be dtype %s, got %s" % (self._value_dtype, d.dtype))
-    d = d.contiguous()
+    d, full = self._defaults(dynamic_default_values, n)
     out = torch.empty(tuple(keys.shape) + (self._dim,), dtype=self._value_dtype, device=self._device)
-    full = int(out.numel() == d.numel())
-    if not full and d.numel() < self._dim:
-      raise ValueError("default value needs at least dim=%d elements, got %d" % (self._dim, d.numel()))
-    cap = n if cap is None else int(cap)
-    if cap < 0:
-      raise ValueError("cap must be >= 0, got %d" % cap)
+    cap = _cap_for(cap, n)
     exists = torch.zeros(keys.shape, dtype=torch.bool, device=self._device) if return_exists else None
     scores = torch.zeros(keys.shape, dtype=torch.int64, device=self._device) if return_scores else None
     counter = torch.zeros(1, dtype=torch.int64, device=self._device)
@@ -557,8 +393,7 @@ class _DeviceTable:
     extra = ((exists,) if return_exists else ()) + ((scores,) if return_scores else ())
     if not sync:
       return (out, counter, mk, mi) + extra   # (the keys stay int64 here: narrowing the unwritten tail would read it)
-    m = min(int(counter.item()), cap)
-    return (out, _narrow_keys(mk[:m], self._key_dtype), mi[:m]) + extra
+    return (out,) + _trim_to_count(counter, cap, mk, self._key_dtype, mi) + extra
 
   def assign(self, keys, values, scores=None, return_found=False, count=None):
     """The write that only hits (tfra_table_assign): a resident key gets its row of `values` and its score is touched as `upsert`
@@ -567,12 +402,7 @@ class _DeviceTable:
     keys = self._keys(keys)
     values = self._values_for(keys, values)
     n = keys.numel()
-    if scores is not None and scores.numel() == 0:
-      scores = None
-    if scores is not None:
-      scores = scores.to(self._device, torch.int64).contiguous()
-      if scores.numel() != n:
-        raise ValueError("scores must have one entry per key")
+    scores = _scores_for(scores, n, self._device)
     found = torch.zeros(keys.shape, dtype=torch.bool, device=self._device) if return_found else None
     if n:
       _capi.call("tfra_table_assign", self._h, n, _ptr(count), _ptr(keys), _ptr(values), _ptr(scores), _ptr(found),
@@ -605,8 +435,7 @@ class _DeviceTable:
     (tfra_table_insert_or_assign_n; raises when the single-pass write-back cannot take the call)."""
     keys = self._keys(keys)
     values = self._values_for(keys, values)
-    if scores is not None:
-      scores = scores.to(self._device, torch.int64).contiguous()
+    scores = _scores_for(scores, keys.numel(), self._device)
     if keys.numel():
       _capi.call("tfra_table_insert_or_assign_n", self._h, keys.numel(), _ptr(count), _ptr(keys), _ptr(values), _ptr(scores),
                  _stream(self._device))
@@ -623,10 +452,7 @@ class _DeviceTable:
     n = keys.numel()
     if n == 0:
       return
-    if scores is not None and scores.numel() == 0:
-      scores = None
-    if scores is not None:
-      scores = scores.to(self._device, torch.int64).contiguous()
+    scores = _scores_for(scores, n, self._device)
     _capi.call("tfra_table_accum_or_assign", self._h, n, _ptr(keys), _ptr(vod), _ptr(exists), _ptr(scores),
                _capi.FLAG_UNIQUE_KEYS if unique_keys else 0, _stream(self._device))
 
@@ -761,20 +587,67 @@ class _DeviceTable:
     _capi.call("tfra_table_apply_optimizer", self._h, ctypes.byref(params), keys.numel(), _ptr(keys), _ptr(grads), _ptr(d),
                full, _ptr(n_dev), _stream(self._device))
 
+  # ---- write-backs of a batch whose ids may repeat; `plan`: a built `SparsePlan`, the id-only half made ahead ----
+  def apply_sparse(self, params, ids, grads, default_row):
+    """ids may repeat: duplicate gradients are summed (fixed order), one fused update per unique key."""
+    ids = self._keys(ids).reshape(-1)
+    grads = grads.to(self._device, torch.float32).contiguous()
+    if grads.numel() != ids.numel() * self._dim:
+      raise ValueError("Expected shape %s for grads, got %s" % ([ids.numel(), self._dim], list(grads.shape)))
+    d = default_row.to(self._device, torch.float32).contiguous()
+    _capi.call("tfra_table_apply_sparse", self._h, ctypes.byref(params), ids.numel(), _ptr(ids), _ptr(grads), _ptr(d),
+               _stream(self._device))
 
-  # method of _DeviceTable (appended below the class body by assignment)
-def _apply_sparse(self, params, ids, grads, default_row):
-  """ids may repeat: duplicate gradients are summed (fixed order), one fused update per unique key."""
-  ids = self._keys(ids).reshape(-1)
-  grads = grads.to(self._device, torch.float32).contiguous()
-  if grads.numel() != ids.numel() * self._dim:
-    raise ValueError("Expected shape %s for grads, got %s" % ([ids.numel(), self._dim], list(grads.shape)))
-  d = default_row.to(self._device, torch.float32).contiguous()
-  _capi.call("tfra_table_apply_sparse", self._h, ctypes.byref(params), ids.numel(), _ptr(ids), _ptr(grads), _ptr(d),
-             _stream(self._device))
+  def apply_planned(self, params, plan, grads, default_row, sync=True):
+    """Gradient half of apply_sparse for a batch whose id-only half was built ahead (`SparsePlan`)."""
+    _check_plan(plan, self._dim, self._device)
+    grads = grads.to(self._device, torch.float32).contiguous()
+    if grads.numel() != plan.n * self._dim:
+      raise ValueError("Expected shape %s for grads, got %s" % ([plan.n, self._dim], list(grads.shape)))
+    d = default_row.to(self._device, torch.float32).contiguous()
+    _over_plans((plan,), self._device, sync, _capi.call, "tfra_table_apply_planned", self._h, ctypes.byref(params), plan._h,
+                _ptr(grads), _ptr(d), _stream(self._device))
 
+  def _apply_combined_args(self, plan, grad_out, seg, weights, default_row):
+    """A combined write-back's grad_out, seg, weights (or None) and default row, checked and as the C calls take them."""
+    _check_plan(plan, self._dim, self._device)
+    grad_out = grad_out.to(self._device, torch.float32).contiguous()
+    if grad_out.dim() != 2 or grad_out.shape[1] != self._dim:
+      raise ValueError("Expected grad_out of shape [n_rows, %d], got %s" % (self._dim, list(grad_out.shape)))
+    seg = seg.to(self._device, torch.int64).contiguous()
+    if seg.numel() != plan.n or (weights is not None and weights.numel() != plan.n):
+      raise ValueError("seg / weights need one element per plan entry (%d)" % plan.n)
+    w = None if weights is None else weights.to(self._device, torch.float32).contiguous()
+    d = default_row.to(self._device, torch.float32).contiguous()
+    return grad_out, seg, w, d
 
-_DeviceTable.apply_sparse = _apply_sparse
+  def apply_planned_combined(self, params, plan, grad_out, seg, weights, combiner, default_row, sync=True):
+    """apply_planned for an embedding_lookup_sparse (tfra_table_apply_planned_combined): `plan` built over the entry ids,
+    grad_out [n_rows, dim] the gradient of the combined result, seg [nnz] its row ids (ascending), weights [nnz] or None,
+    combiner 0 sum / 1 mean / 2 sqrtn.  Entry e's gradient is formed from grad_out inside the write-back kernels."""
+    grad_out, seg, w, d = self._apply_combined_args(plan, grad_out, seg, weights, default_row)
+    _over_plans((plan,), self._device, sync, _capi.call, "tfra_table_apply_planned_combined", self._h, ctypes.byref(params), plan._h,
+                _ptr(grad_out), _ptr(seg), _ptr(w), int(combiner), grad_out.shape[0], _ptr(d), _stream(self._device))
+
+  def upsert_sparse(self, ids, values, scores=None):
+    """insert_or_assign of a batch whose keys may repeat: the LAST occurrence wins (the reference's sequential
+    order), de-duplicated on the device — also on a bounded table at max_capacity."""
+    ids = self._keys(ids).reshape(-1)
+    values = self._values_for(ids, values.reshape(ids.numel(), -1))
+    scores = _scores_for(scores, ids.numel(), self._device)
+    if ids.numel():
+      _capi.call("tfra_table_upsert_sparse", self._h, ids.numel(), _ptr(ids), _ptr(values), _ptr(scores), _stream(self._device))
+
+  def upsert_planned(self, plan, values, scores=None, sync=True):
+    """Assign half of upsert_sparse for a batch whose id-only half was built ahead (`SparsePlan`)."""
+    if plan._device != self._device:   # (not `_check_plan`: an assign-only plan is built with dim 0 and serves any row width)
+      raise ValueError("the plan lives on %s" % (plan._device,))
+    values = values.to(self._device).contiguous()
+    if values.dtype != self._value_dtype or values.numel() != plan.n * self._dim:
+      raise ValueError("Expected %s values of shape %s" % (self._value_dtype, [plan.n, self._dim]))
+    scores = _scores_for(scores, plan.n, self._device, per="batch position")
+    _over_plans((plan,), self._device, sync, _capi.call, "tfra_table_upsert_planned", self._h, plan._h, _ptr(values), _ptr(scores),
+                _stream(self._device))
 
 
 class _DeviceTier:
@@ -802,34 +675,13 @@ class _DeviceTier:
   def max_batch(self):
     return self._max_batch
 
-  def _rows_for(self, keys, rows, what):
-    """-> (rows on the device, is_full): [n, dim] or one row of dim elements (None: the upper table's default row)"""
-    up = self._upper
-    d = up._default_value if rows is None else rows
-    d = torch.as_tensor(d, device=up._device) if not torch.is_tensor(d) else d.to(up._device)
-    if d.dtype != up._value_dtype:
-      raise TypeError("%s must be dtype %s, got %s" % (what, up._value_dtype, d.dtype))
-    d = d.contiguous()
-    full = int(d.numel() == keys.numel() * up._dim)   # (one key: the two forms are the same row)
-    if not full and d.numel() != up._dim:
-      raise ValueError("%s must be [n, dim] or one row of dim=%d elements, got shape %s" % (what, up._dim, list(d.shape)))
-    return d, full
-
-  def _out_for(self, keys, out):
-    up = self._upper
-    n = keys.numel()
-    if out is None:
-      return torch.empty(tuple(keys.shape) + (up._dim,), dtype=up._value_dtype, device=up._device)
-    if out.dtype != up._value_dtype or out.numel() != n * up._dim or not out.is_contiguous() or out.device != up._device:
-      raise ValueError("out must be a contiguous %s tensor of %d x %d elements on %s" % (up._value_dtype, n, up._dim, up._device))
-    return out
-
   def find(self, keys, dynamic_default_values=None, return_where=False, count=None, out=None):
     """A read (tfra_tier_find): the row upper holds, else the row lower holds, else the default.  Keys may repeat; nothing moves and
-    neither table is written.  -> rows, or (rows, where) with where uint8: 1 = upper, 2 = lower, 0 = neither."""
+    neither table is written.  -> rows, or (rows, where) with where uint8: 1 = upper, 2 = lower, 0 = neither.  The default rows
+    follow the admitting rule ([n, dim] or exactly one row), not `_DeviceTable.find`'s."""
     keys = self._upper._keys(keys)
-    d, full = self._rows_for(keys, dynamic_default_values, "default values")
-    out = self._out_for(keys, out)
+    d, full = self._upper._init_rows(dynamic_default_values, keys.numel(), "default values")
+    out = self._upper._out(keys.shape, out)
     where = torch.zeros(keys.shape, dtype=torch.uint8, device=self._upper._device)
     if keys.numel():
       _capi.call("tfra_tier_find", self._h, keys.numel(), _ptr(count), _ptr(keys), _ptr(out), _ptr(where), _ptr(d), full,
@@ -842,8 +694,8 @@ class _DeviceTier:
     aux_init), and what that displaced is below.  verify: count the batch keys that are NOT resident at the end into
     stats()["not_resident"] (a batch that fills both home buckets of one of its keys with its own keys)."""
     keys = self._upper._keys(keys)
-    d, full = self._rows_for(keys, init_values, "init values")
-    out = self._out_for(keys, out)
+    d, full = self._upper._init_rows(init_values, keys.numel())
+    out = self._upper._out(keys.shape, out)
     where = torch.zeros(keys.shape, dtype=torch.uint8, device=self._upper._device)
     if keys.numel():
       _capi.call("tfra_tier_find_or_insert", self._h, keys.numel(), _ptr(count), _ptr(keys), _ptr(d), full, _ptr(out), _ptr(where),
@@ -931,12 +783,8 @@ class SparsePlan:
       raise ValueError("Expected shape %s for grads, got %s" % ([self.n, self._dim], list(grads.shape)))
     if dest.dtype != torch.int32 or dest.numel() != self.n or not dest.is_contiguous():
       raise ValueError("dest must be a contiguous int32 tensor with one entry per id")
-    stream = torch.cuda.current_stream(self._device)
-    if sync:
-      self._wait_built(stream)
-    _capi.call("tfra_plan_reduce_to", self._h, _ptr(grads), _ptr(dest), _ptr(rows_out), _stream(self._device))
-    if sync:
-      self._mark_used(stream)
+    _over_plans((self,), self._device, sync, _capi.call, "tfra_plan_reduce_to", self._h, _ptr(grads), _ptr(dest), _ptr(rows_out),
+                _stream(self._device))
     return rows_out
 
   def read(self):
@@ -961,92 +809,6 @@ class SparsePlan:
         self._h = None
     except Exception:
       pass
-
-
-def _apply_planned(self, params, plan, grads, default_row, sync=True):
-  """Gradient half of apply_sparse for a batch whose id-only half was built ahead (`SparsePlan`)."""
-  if plan._dim != self._dim or plan._device != self._device:
-    raise ValueError("the plan was built for dim %d on %s" % (plan._dim, plan._device))
-  grads = grads.to(self._device, torch.float32).contiguous()
-  if grads.numel() != plan.n * self._dim:
-    raise ValueError("Expected shape %s for grads, got %s" % ([plan.n, self._dim], list(grads.shape)))
-  d = default_row.to(self._device, torch.float32).contiguous()
-  stream = torch.cuda.current_stream(self._device)
-  if sync:
-    plan._wait_built(stream)
-  _capi.call("tfra_table_apply_planned", self._h, ctypes.byref(params), plan._h, _ptr(grads), _ptr(d), _stream(self._device))
-  if sync:
-    plan._mark_used(stream)
-
-
-_DeviceTable.apply_planned = _apply_planned
-
-
-def _apply_combined_args(self, plan, grad_out, seg, weights, default_row):
-  """A combined write-back's grad_out, seg, weights (or None) and default row, checked and as the C calls take them."""
-  if plan._dim != self._dim or plan._device != self._device:
-    raise ValueError("the plan was built for dim %d on %s" % (plan._dim, plan._device))
-  grad_out = grad_out.to(self._device, torch.float32).contiguous()
-  if grad_out.dim() != 2 or grad_out.shape[1] != self._dim:
-    raise ValueError("Expected grad_out of shape [n_rows, %d], got %s" % (self._dim, list(grad_out.shape)))
-  seg = seg.to(self._device, torch.int64).contiguous()
-  if seg.numel() != plan.n or (weights is not None and weights.numel() != plan.n):
-    raise ValueError("seg / weights need one element per plan entry (%d)" % plan.n)
-  w = None if weights is None else weights.to(self._device, torch.float32).contiguous()
-  d = default_row.to(self._device, torch.float32).contiguous()
-  return grad_out, seg, w, d
-
-
-_DeviceTable._apply_combined_args = _apply_combined_args
-
-
-def _apply_planned_combined(self, params, plan, grad_out, seg, weights, combiner, default_row, sync=True):
-  """apply_planned for an embedding_lookup_sparse (tfra_table_apply_planned_combined): `plan` built over the entry ids,
-  grad_out [n_rows, dim] the gradient of the combined result, seg [nnz] its row ids (ascending), weights [nnz] or None,
-  combiner 0 sum / 1 mean / 2 sqrtn.  Entry e's gradient is formed from grad_out inside the write-back kernels."""
-  grad_out, seg, w, d = self._apply_combined_args(plan, grad_out, seg, weights, default_row)
-  stream = torch.cuda.current_stream(self._device)
-  if sync:
-    plan._wait_built(stream)
-  _capi.call("tfra_table_apply_planned_combined", self._h, ctypes.byref(params), plan._h, _ptr(grad_out), _ptr(seg), _ptr(w),
-             int(combiner), grad_out.shape[0], _ptr(d), _stream(self._device))
-  if sync:
-    plan._mark_used(stream)
-
-
-_DeviceTable.apply_planned_combined = _apply_planned_combined
-
-
-def _upsert_sparse(self, ids, values, scores=None):
-  """insert_or_assign of a batch whose keys may repeat: the LAST occurrence wins (the reference's sequential
-  order), de-duplicated on the device — also on a bounded table at max_capacity."""
-  ids = self._keys(ids).reshape(-1)
-  values = self._values_for(ids, values.reshape(ids.numel(), -1))
-  if scores is not None:
-    scores = scores.to(self._device, torch.int64).contiguous()
-  if ids.numel():
-    _capi.call("tfra_table_upsert_sparse", self._h, ids.numel(), _ptr(ids), _ptr(values), _ptr(scores), _stream(self._device))
-
-
-def _upsert_planned(self, plan, values, scores=None, sync=True):
-  """Assign half of upsert_sparse for a batch whose id-only half was built ahead (`SparsePlan`)."""
-  if plan._device != self._device:
-    raise ValueError("the plan lives on %s" % (plan._device,))
-  values = values.to(self._device).contiguous()
-  if values.dtype != self._value_dtype or values.numel() != plan.n * self._dim:
-    raise ValueError("Expected %s values of shape %s" % (self._value_dtype, [plan.n, self._dim]))
-  if scores is not None:
-    scores = scores.to(self._device, torch.int64).contiguous()
-  stream = torch.cuda.current_stream(self._device)
-  if sync:
-    plan._wait_built(stream)
-  _capi.call("tfra_table_upsert_planned", self._h, plan._h, _ptr(values), _ptr(scores), _stream(self._device))
-  if sync:
-    plan._mark_used(stream)
-
-
-_DeviceTable.upsert_sparse = _upsert_sparse
-_DeviceTable.upsert_planned = _upsert_planned
 
 
 class _LookupInterfaceMirror:
@@ -1089,7 +851,7 @@ class _LookupInterfaceMirror:
     """HierarchicalKV's find_or_insert: `lookup` that inserts every key it does not find with the row it returns for it
     (`dynamic_default_values[i]`, else the table's default row), as `insert` would.  Keys must be unique.  Scores follow
     `insert`'s rule.  count: a device int64 count of the leading keys to serve (`_DeviceTable.find_or_insert`)."""
-    keys = torch.as_tensor(keys, device=self._device) if not torch.is_tensor(keys) else keys
+    keys = _as_tensor(keys, self._device)
     return self._table.find_or_insert(keys, dynamic_default_values, scores=self._gen_scores(keys), return_exists=return_exists,
                                       count=count)
 
@@ -1109,7 +871,7 @@ class _LookupInterfaceMirror:
   def assign(self, keys, values, name=None):
     """HierarchicalKV's assign: `insert` for the keys that are resident, nothing for the others (they are not inserted and
     nothing is evicted for them).  Keys must be unique.  Scores follow `insert`'s rule."""
-    keys = torch.as_tensor(keys, device=self._device) if not torch.is_tensor(keys) else keys
+    keys = _as_tensor(keys, self._device)
     self._table.assign(keys, values, scores=self._gen_scores(keys))
 
   def contains(self, keys, name=None):
@@ -1265,13 +1027,13 @@ class HkvHashTable(_LookupInterfaceMirror):
   def insert_and_evict(self, keys, values, scores=None, name=None):
     """insert that returns (evicted_keys, evicted_values, evicted_scores): what left the table because of this call and what it
     did not admit (HierarchicalKV's insert_and_evict).  scores: as the engine takes them; None = gen_scores_fn / the strategy's."""
-    keys = torch.as_tensor(keys, device=self._device) if not torch.is_tensor(keys) else keys
+    keys = _as_tensor(keys, self._device)
     return self._table.upsert_and_evict(keys, values, scores=self._gen_scores(keys) if scores is None else scores)
 
   def assign(self, keys, values, scores=None, name=None):
     """HierarchicalKV's assign: the resident keys get their rows and their scores are touched as `insert` touches them; the
     others change nothing.  scores: as the engine takes them; None = gen_scores_fn / the strategy's."""
-    keys = torch.as_tensor(keys, device=self._device) if not torch.is_tensor(keys) else keys
+    keys = _as_tensor(keys, self._device)
     self._table.assign(keys, values, scores=self._gen_scores(keys) if scores is None else scores)
 
   def accum(self, keys, values_or_deltas, exists, name=None):
@@ -1281,17 +1043,17 @@ class HkvHashTable(_LookupInterfaceMirror):
 
   def export_keys_and_scores(self, split_size, name=None):
     """PY/hkv_hashtable_ops.py:421-434"""
-    if not (isinstance(split_size, int) and split_size > 0):
-      raise ValueError("split_size must be positive integer.")
-    k, _, s = self._table.export_all(with_scores=True, values=False, split_size=split_size)
+    k, _, s = self._export_split(split_size, values=False)
     return k, s
 
   def export_with_scores(self, split_size, name=None):
     """PY/hkv_hashtable_ops.py:436-450"""
+    return self._export_split(split_size, values=True)
+
+  def _export_split(self, split_size, values):
     if not (isinstance(split_size, int) and split_size > 0):
       raise ValueError("split_size must be positive integer.")
-    return self._table.export_all(with_scores=True, values=True, split_size=split_size)
-
+    return self._table.export_all(with_scores=True, values=values, split_size=split_size)
 
   # ---- score-filtered forms (HKV export_batch_if / erase_if / size_if) ------------------------
   def export_if(self, threshold, pred="ge", name=None):
@@ -1375,7 +1137,7 @@ class TieredHashTable(_LookupInterfaceMirror):
 
   def lookup(self, keys, dynamic_default_values=None, return_exists=False, name=None):
     """A read of both tiers (`_DeviceTier.find`): nothing moves."""
-    keys = torch.as_tensor(keys, device=self._device) if not torch.is_tensor(keys) else keys
+    keys = _as_tensor(keys, self._device)
     flat = keys.reshape(-1)
     n, dim = flat.numel(), self._table.dim
     d = dynamic_default_values
@@ -1391,7 +1153,7 @@ class TieredHashTable(_LookupInterfaceMirror):
   def find_or_insert(self, keys, dynamic_default_values=None, return_exists=False, name=None, count=None):
     """The admitting lookup through both tiers (`_DeviceTier.find_or_insert`): UNIQUE keys, at most `max_batch` of them.  exists[i]
     is False for a key neither tier held."""
-    keys = torch.as_tensor(keys, device=self._device) if not torch.is_tensor(keys) else keys
+    keys = _as_tensor(keys, self._device)
     rows, where = self._tier.find_or_insert(keys, dynamic_default_values, return_where=True, count=count)
     return (rows, where != 0) if return_exists else rows
 
@@ -1403,7 +1165,7 @@ class TieredHashTable(_LookupInterfaceMirror):
     return self._shard_find_missed(keys, dynamic_default_values, False)
 
   def _shard_find_missed(self, keys, defaults, return_exists):
-    keys = torch.as_tensor(keys, device=self._device) if not torch.is_tensor(keys) else keys
+    keys = _as_tensor(keys, self._device)
     rows, exists = self.lookup(keys, defaults, return_exists=True)
     mi = torch.nonzero(~exists.reshape(-1)).reshape(-1)
     out = (rows, keys.reshape(-1)[mi], mi.to(torch.int32))
@@ -1411,8 +1173,8 @@ class TieredHashTable(_LookupInterfaceMirror):
 
   def insert(self, keys, values, name=None):
     """upsert of embedding rows (UNIQUE keys) into the cache; what that displaces goes down with its slots (`_DeviceTier.insert`)."""
-    keys = torch.as_tensor(keys, device=self._device) if not torch.is_tensor(keys) else keys
-    values = torch.as_tensor(values, device=self._device) if not torch.is_tensor(values) else values
+    keys = _as_tensor(keys, self._device)
+    values = _as_tensor(values, self._device)
     flat, n = keys.reshape(-1), keys.numel()
     vals = values.reshape(n, self._table.dim)
     for a, b in self._chunks(n):
@@ -1424,7 +1186,7 @@ class TieredHashTable(_LookupInterfaceMirror):
     self._shard_assign(keys, values, False)
 
   def _shard_assign(self, keys, values, return_found):
-    keys = torch.as_tensor(keys, device=self._device) if not torch.is_tensor(keys) else keys
+    keys = _as_tensor(keys, self._device)
     up = self._table.assign(keys, values, return_found=return_found)
     lo = self._lower.assign(keys, values, return_found=return_found)
     return (up | lo) if return_found else None
@@ -1573,17 +1335,9 @@ def apply_planned_combined_many(requests, p_list, sync=True):
     e.n_rows, e.param_default_row = grad_out.shape[0], d.data_ptr()
     return grad_out, seg, w, d, p_list[i]
 
-  stream = torch.cuda.current_stream(_device_table(requests[0][0])._device)
-  plans = [req[1] for req in requests]
-  if sync:
-    for plan in plans:
-      plan._wait_built(stream)
-  launches = _grouped_call("tfra_multi_apply_planned_combined", _capi.ApplyCombinedDesc, "apply_planned_combined_many",
-                           [r[0] for r in requests], fill)
-  if sync:
-    for plan in plans:
-      plan._mark_used(stream)
-  return launches
+  return _over_plans([req[1] for req in requests], _device_table(requests[0][0])._device, sync, _grouped_call,
+                     "tfra_multi_apply_planned_combined", _capi.ApplyCombinedDesc, "apply_planned_combined_many",
+                     [r[0] for r in requests], fill)
 
 
 def build_plans_many(plans, ids_list, return_launches=False):

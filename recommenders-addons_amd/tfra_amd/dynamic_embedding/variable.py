@@ -14,8 +14,9 @@ partition -> per-shard table op -> stitch, the partition/stitch being device ker
 """
 import torch
 
-from . import device_ops
-from .table_ops import CuckooHashTable, HkvHashTable, HkvEvictStrategy, TieredHashTable, _as_device, _score_filter
+from . import device_ops, table_ops
+from ._args import _as_device, _score_filter
+from .table_ops import CuckooHashTable, HkvHashTable, HkvEvictStrategy, SparsePlan, TieredHashTable
 
 
 def default_partition_fn(keys, shard_num):
@@ -226,22 +227,49 @@ class Variable:
     return list(torch.split(owner_major, c)), perm, c
 
   def _split_rows(self, rows, perm, counts):
+    """`rows` — [n, width], or a bool vector [n] (gathered as uint8) — in owner-major order, one slice per shard."""
     if perm is None:
       return [rows]
+    if rows.dtype == torch.bool:
+      return list(torch.split(device_ops.gather_rows(rows.reshape(-1, 1).to(torch.uint8), perm).reshape(-1).to(torch.bool), counts))
     return list(torch.split(device_ops.gather_rows(rows, perm), counts))
+
+  def _fan_out(self, keys, *rows, values=None):
+    """The first half of every sharded call -> (keys, perm, counts, shards): `keys` as a tensor on the primary device, the
+    partition's permutation (None for 1 shard) and host counts, and per shard the tuple (table, its keys, its slice of each
+    operand) on the shard's device.  An operand is one of `rows` ([n, width], or a bool vector [n]), index-aligned with the
+    flattened keys; `values`, when given, is the first of them, after the check that it has one row of dim per key."""
+    keys = torch.as_tensor(keys, device=self._primary)
+    if values is not None:
+      values = torch.as_tensor(values, device=self._primary)
+      want = tuple(keys.shape) + (self.dim,)
+      if tuple(values.shape) != want:
+        raise ValueError("Expected shape %s for values, got %s" % (list(want), list(values.shape)))
+      rows = (values.reshape(-1, self.dim),) + rows
+    kp, perm, counts = self._partition(keys)
+    shards = [(t, k.to(t._device)) for t, k in zip(self._tables, kp)]
+    for r in rows:
+      shards = [s + (x.to(s[0]._device),) for s, x in zip(shards, self._split_rows(r, perm, counts))]
+    return keys, perm, counts, shards
+
+  def _stitch_rows(self, parts, perm, shape):
+    """The second half: per-shard row tensors (owner-major order) back in batch order on the primary device, [*shape, dim]."""
+    if perm is None:
+      return parts[0].to(self._primary).reshape(tuple(shape) + (self.dim,))
+    return device_ops.scatter_rows(torch.cat([p.to(self._primary) for p in parts], 0), perm).reshape(tuple(shape) + (self.dim,))
+
+  def _scatter_flags(self, parts, perm, shape):
+    """Per-shard bool vectors (owner-major order) back in batch order on the primary device, as `lookup` returns its exists."""
+    if perm is None:
+      return parts[0].to(self._primary).reshape(shape)
+    flags = torch.cat([p.to(self._primary) for p in parts], 0).reshape(-1, 1).to(torch.uint8)
+    return device_ops.scatter_rows(flags, perm).reshape(-1).to(torch.bool).reshape(shape)
 
   # ---- table ops ---------------------------------------------------------------------------
   def upsert(self, keys, values, name=None):
     """PY/dynamic_embedding_variable.py:772-804"""
-    keys = torch.as_tensor(keys, device=self._primary)
-    values = torch.as_tensor(values, device=self._primary)
-    want = tuple(keys.shape) + (self.dim,)
-    if tuple(values.shape) != want:
-      raise ValueError("Expected shape %s for values, got %s" % (list(want), list(values.shape)))
-    kp, perm, counts = self._partition(keys)
-    vp = self._split_rows(values.reshape(-1, self.dim), perm, counts)
-    for i, t in enumerate(self._tables):
-      t.insert(kp[i].to(t._device), vp[i].to(t._device))
+    for t, k, v in self._fan_out(keys, values=values)[3]:
+      t.insert(k, v)
 
   def upsert_and_evict(self, keys, values, name=None):
     """upsert that returns (evicted_keys, evicted_values, evicted_scores) on the primary device: what every shard displaced or
@@ -250,36 +278,22 @@ class Variable:
       if not hasattr(t, "insert_and_evict"):
         raise NotImplementedError("upsert_and_evict needs bounded tables with scores; %s tables never evict (use an "
                                   "HkvHashTableCreator)" % type(t).__name__)
-    keys = torch.as_tensor(keys, device=self._primary)
-    values = torch.as_tensor(values, device=self._primary)
-    want = tuple(keys.shape) + (self.dim,)
-    if tuple(values.shape) != want:
-      raise ValueError("Expected shape %s for values, got %s" % (list(want), list(values.shape)))
-    kp, perm, counts = self._partition(keys)
-    vp = self._split_rows(values.reshape(-1, self.dim), perm, counts)
-    out = [t.insert_and_evict(kp[i].to(t._device), vp[i].to(t._device)) for i, t in enumerate(self._tables)]
+    out = [t.insert_and_evict(k, v) for t, k, v in self._fan_out(keys, values=values)[3]]
     return tuple(torch.cat([o[j].to(self._primary) for o in out], 0) for j in range(3))
 
   def accum(self, keys, old_values, new_values, exists, name=None):
     """PY/dynamic_embedding_variable.py:806-855: where(exists, new-old, new) then per-shard accum."""
-    keys = torch.as_tensor(keys, device=self._primary)
     exists = torch.as_tensor(exists, device=self._primary).reshape(-1).to(torch.bool)
     old_values = old_values.reshape(-1, self.dim)
     new_values = new_values.reshape(-1, self.dim)
     vod = torch.where(exists[:, None], new_values - old_values, new_values)
-    kp, perm, counts = self._partition(keys)
-    vp = self._split_rows(vod, perm, counts)
-    ep = [exists] if perm is None else list(
-        torch.split(device_ops.gather_rows(exists.reshape(-1, 1).to(torch.uint8), perm).reshape(-1).to(torch.bool),
-                    counts))
-    for i, t in enumerate(self._tables):
-      t.accum(kp[i].to(t._device), vp[i].to(t._device), ep[i].to(t._device))
+    for t, k, v, e in self._fan_out(keys, vod, exists)[3]:
+      t.accum(k, v, e)
 
   def remove(self, keys, name=None):
     """PY/dynamic_embedding_variable.py:877-902"""
-    kp, _, _ = self._partition(torch.as_tensor(keys, device=self._primary))
-    for i, t in enumerate(self._tables):
-      t.remove(kp[i].to(t._device))
+    for t, k in self._fan_out(keys)[3]:
+      t.remove(k)
 
   def clear(self, name=None):
     for t in self._tables:
@@ -293,30 +307,24 @@ class Variable:
 
   def lookup(self, keys, return_exists=False, name=None):
     """PY/dynamic_embedding_variable.py:933-986"""
-    keys = torch.as_tensor(keys, device=self._primary)
-    kp, perm, counts = self._partition(keys)
+    return self._lookup_through("lookup", keys, return_exists, return_exists)
+
+  def _lookup_through(self, method, keys, shard_exists, return_exists):
+    """The body of `lookup` and `lookup_or_insert`: every shard's `method` ("lookup" or "find_or_insert") over the shard's keys and
+    its defaults — one draw of the callable initializer per shard, else None —, asked for exists when shard_exists, and the
+    results stitched back into batch order."""
+    keys, perm, _, shards = self._fan_out(keys)
     vals, exs = [], []
-    for i, t in enumerate(self._tables):
-      k = kp[i].to(t._device)
-      dd = self._create_default_values_by_initializer(k.numel(), t._device)
-      r = t.lookup(k, dynamic_default_values=dd, return_exists=return_exists)
-      if return_exists:
-        vals.append(r[0].to(self._primary))
-        exs.append(r[1].to(self._primary))
+    for t, k in shards:
+      r = getattr(t, method)(k, dynamic_default_values=self._create_default_values_by_initializer(k.numel(), t._device),
+                             return_exists=shard_exists)
+      if shard_exists:
+        vals.append(r[0])
+        exs.append(r[1])
       else:
-        vals.append(r.to(self._primary))
-    if perm is None:
-      v = vals[0]
-      e = exs[0] if return_exists else None
-    else:
-      v = device_ops.scatter_rows(torch.cat(vals, 0), perm)
-      e = None
-      if return_exists:
-        e = device_ops.scatter_rows(torch.cat(exs, 0).reshape(-1, 1).to(torch.uint8), perm).reshape(-1).to(torch.bool)
-    v = v.reshape(tuple(keys.shape) + (self.dim,))
-    if return_exists:
-      return v, e.reshape(keys.shape)
-    return v
+        vals.append(r)
+    v = self._stitch_rows(vals, perm, keys.shape)
+    return (v, self._scatter_flags(exs, perm, keys.shape)) if return_exists else v
 
   def misses_are_static(self):
     """The module's `misses_are_static` of this variable."""
@@ -333,80 +341,42 @@ class Variable:
     returns for it — a row of the callable initializer (one draw of [n, dim] per shard, row j for that shard's key j), else
     the static default row — as `upsert` would insert it.  `keys` must be UNIQUE.  exists[i] is False for every key that was
     not resident before the call."""
-    keys = torch.as_tensor(keys, device=self._primary)
-    kp, perm, counts = self._partition(keys)
-    vals, exs = [], []
-    for i, t in enumerate(self._tables):
-      k = kp[i].to(t._device)
-      dd = self._create_default_values_by_initializer(k.numel(), t._device)
-      r, e = t.find_or_insert(k, dynamic_default_values=dd, return_exists=True)
-      vals.append(r.to(self._primary))
-      exs.append(e.to(self._primary))
-    if perm is None:
-      v, e = vals[0], exs[0]
-    else:
-      v = device_ops.scatter_rows(torch.cat(vals, 0), perm)
-      e = device_ops.scatter_rows(torch.cat(exs, 0).reshape(-1, 1).to(torch.uint8), perm).reshape(-1).to(torch.bool)
-    v = v.reshape(tuple(keys.shape) + (self.dim,))
-    return (v, e.reshape(keys.shape)) if return_exists else v
+    return self._lookup_through("find_or_insert", keys, True, return_exists)
 
   # ---- the read side of a tier (tables in front of something slower) ---------------------------
-  def _scatter_flags(self, parts, perm, shape):
-    """Per-shard bool vectors (owner-major order) back in batch order, as `lookup` returns its exists."""
-    if perm is None:
-      return parts[0].reshape(shape)
-    return device_ops.scatter_rows(torch.cat(parts, 0).reshape(-1, 1).to(torch.uint8), perm).reshape(-1).to(torch.bool).reshape(shape)
-
   def lookup_missed(self, keys, return_exists=False, name=None):
     """`lookup` that also lists its misses (find_missed per shard) -> (rows, missed_keys, missed_positions[, exists]): the keys
     that are not resident and their positions in the flattened batch (int64, index-aligned, in no particular order; a missing
     key that repeats is listed at every position).  Never inserts.  A callable initializer draws the defaults per shard, as
     `lookup` does.  A shard reports positions in its slice of the owner-major key list; they are mapped back through the
     partition's permutation (owner_major = flat[perm]).  A tiered shard lists the keys NEITHER of its tiers holds."""
-    keys = torch.as_tensor(keys, device=self._primary)
-    kp, perm, counts = self._partition(keys)
+    keys, perm, counts, shards = self._fan_out(keys)
     vals, exs, mks, mps = [], [], [], []
     off = 0
-    for i, t in enumerate(self._tables):
-      k = kp[i].to(t._device)
-      dd = self._create_default_values_by_initializer(k.numel(), t._device)
-      r = t._shard_find_missed(k, dd, return_exists)
-      vals.append(r[0].to(self._primary))
+    for (t, k), count in zip(shards, counts):
+      r = t._shard_find_missed(k, self._create_default_values_by_initializer(k.numel(), t._device), return_exists)
+      vals.append(r[0])
       mks.append(r[1].to(self._primary))
       pos = r[2].to(self._primary).to(torch.int64)
       mps.append(pos if perm is None else perm[off + pos].to(torch.int64))
       if return_exists:
-        exs.append(r[3].to(self._primary))
-      off += counts[i]
-    v = vals[0] if perm is None else device_ops.scatter_rows(torch.cat(vals, 0), perm)
-    v = v.reshape(tuple(keys.shape) + (self.dim,))
-    out = (v, torch.cat(mks, 0), torch.cat(mps, 0))
+        exs.append(r[3])
+      off += count
+    out = (self._stitch_rows(vals, perm, keys.shape), torch.cat(mks, 0), torch.cat(mps, 0))
     return out + (self._scatter_flags(exs, perm, keys.shape),) if return_exists else out
 
   def assign(self, keys, values, return_found=False, name=None):
     """`upsert` for the keys that are resident; the others change nothing — they are not inserted and nothing is evicted for them
     (assign per shard).  `keys` must be UNIQUE.  -> None, or found (bool, shaped like keys): False = send the row to the tier
     that holds the key.  `size()` never changes.  A tiered shard writes the row in both of its tiers (found: in either)."""
-    keys = torch.as_tensor(keys, device=self._primary)
-    values = torch.as_tensor(values, device=self._primary)
-    want = tuple(keys.shape) + (self.dim,)
-    if tuple(values.shape) != want:
-      raise ValueError("Expected shape %s for values, got %s" % (list(want), list(values.shape)))
-    kp, perm, counts = self._partition(keys)
-    vp = self._split_rows(values.reshape(-1, self.dim), perm, counts)
-    fs = []
-    for i, t in enumerate(self._tables):
-      k = kp[i].to(t._device)
-      f = t._shard_assign(k, vp[i].to(t._device), return_found)
-      if return_found:
-        fs.append(f.to(self._primary))
+    keys, perm, _, shards = self._fan_out(keys, values=values)
+    fs = [t._shard_assign(k, v, return_found) for t, k, v in shards]
     return self._scatter_flags(fs, perm, keys.shape) if return_found else None
 
   def contains(self, keys, name=None):
     """A bool tensor shaped like keys: True where the key is resident (contains per shard; no row is read)."""
-    keys = torch.as_tensor(keys, device=self._primary)
-    kp, perm, _ = self._partition(keys)
-    return self._scatter_flags([t.contains(kp[i].to(t._device)).to(self._primary) for i, t in enumerate(self._tables)], perm, keys.shape)
+    keys, perm, _, shards = self._fan_out(keys)
+    return self._scatter_flags([t.contains(k) for t, k in shards], perm, keys.shape)
 
   def can_lookup_combined(self):
     """Whether `lookup_combined` serves this variable: one shard, a static default row (no callable initializer), float32 /
@@ -420,24 +390,24 @@ class Variable:
     out[r] = combiner over the entries p with seg[p] == r, in input order, of weights[p] * (row of ids[p], the default row on a
     miss).  seg ascending; weights None = all 1; combiner "sum" / "mean" / "sqrtn".  Bit-identical to
     unique -> lookup -> device_ops.sparse_segment_combine, without the unique pass and its host read.  Never inserts."""
+    t, ids = self._combined_operands(ids, ragged=False)
+    return t._table.find_combine(ids, seg, weights, device_ops.COMBINERS[combiner], n_rows, t._default_value)
+
+  def _combined_operands(self, ids, ragged):
+    """-> (the one shard, the flat ids on its device) of a pooled read; ValueError unless `can_lookup_combined()`."""
     if not self.can_lookup_combined():
-      raise ValueError("lookup_combined needs one shard, a static default row, float32 / float16 / bfloat16 rows, dim % 4 == 0 "
-                       "and dim <= 256; use embedding_lookup_sparse")
-    t = self._tables[0]
-    ids = torch.as_tensor(ids, device=self._primary)
-    return t._table.find_combine(ids.reshape(-1), seg, weights, device_ops.COMBINERS[combiner], n_rows, t._default_value)
+      raise ValueError("%s needs one shard, a static default row, float32 / float16 / bfloat16 rows, dim %% 4 == 0 and dim <= 256; "
+                       "use %s" % (("lookup_combined_ragged", "ragged_embedding_ops.embedding_lookup_sparse") if ragged else
+                                   ("lookup_combined", "embedding_lookup_sparse")))
+    return self._tables[0], torch.as_tensor(ids, device=self._primary).reshape(-1)
 
   def lookup_combined_ragged(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, name=None):
     """`lookup_combined` over a ragged batch (tfra_table_find_combine_ragged): [n_rows, dim] float32, row r combining the entries
     [row_splits[r], row_splits[r + 1]) — bit-identical to `lookup_combined` on the row ids the splits stand for, in one launch.
     prune / fill_id: safe_embedding_lookup_sparse's pruning by weight and its default_id (`_DeviceTable.find_combine_ragged`).
     Under `can_lookup_combined()`'s conditions.  Never inserts; nothing is read on the host."""
-    if not self.can_lookup_combined():
-      raise ValueError("lookup_combined_ragged needs one shard, a static default row, float32 / float16 / bfloat16 rows, "
-                       "dim % 4 == 0 and dim <= 256; use ragged_embedding_ops.embedding_lookup_sparse")
-    t = self._tables[0]
-    ids = torch.as_tensor(ids, device=self._primary)
-    return t._table.find_combine_ragged(row_splits, ids.reshape(-1), weights, device_ops.COMBINERS[combiner], prune=prune,
+    t, ids = self._combined_operands(ids, ragged=True)
+    return t._table.find_combine_ragged(row_splits, ids, weights, device_ops.COMBINERS[combiner], prune=prune,
                                         fill_id=fill_id, default_row=t._default_value)
 
   def lookup_combined_weight_grad(self, ids, seg, weights, combiner, grad_out, name=None):
@@ -445,23 +415,15 @@ class Variable:
     grad_out = d loss / d result, [n_rows, dim].  The rows are read from the table as they are now, as the forward reads them
     (the default row on a miss); nothing is inserted and no [nnz, dim] tensor exists.  weights None = all 1.  Under
     `can_lookup_combined()`'s conditions."""
-    if not self.can_lookup_combined():
-      raise ValueError("lookup_combined needs one shard, a static default row, float32 / float16 / bfloat16 rows, dim % 4 == 0 "
-                       "and dim <= 256; use embedding_lookup_sparse")
-    t = self._tables[0]
-    ids = torch.as_tensor(ids, device=self._primary)
-    return t._table.find_combine_weight_grad(ids.reshape(-1), seg, weights, device_ops.COMBINERS[combiner], grad_out, t._default_value)
+    t, ids = self._combined_operands(ids, ragged=False)
+    return t._table.find_combine_weight_grad(ids, seg, weights, device_ops.COMBINERS[combiner], grad_out, t._default_value)
 
   def lookup_combined_ragged_weight_grad(self, row_splits, ids, weights, combiner, grad_out, prune=False, fill_id=None, name=None):
     """`lookup_combined_weight_grad` for `lookup_combined_ragged` (tfra_table_find_combine_ragged_backprop_weights): bit-identical to
     it on the row ids the splits stand for, in one launch.  prune: the entries the forward prunes get exactly 0; fill_id: the
     entries of a row that takes the fill row get 0.  Under `can_lookup_combined()`'s conditions."""
-    if not self.can_lookup_combined():
-      raise ValueError("lookup_combined_ragged needs one shard, a static default row, float32 / float16 / bfloat16 rows, "
-                       "dim % 4 == 0 and dim <= 256; use ragged_embedding_ops.embedding_lookup_sparse")
-    t = self._tables[0]
-    ids = torch.as_tensor(ids, device=self._primary)
-    return t._table.find_combine_ragged_weight_grad(row_splits, ids.reshape(-1), weights, device_ops.COMBINERS[combiner], grad_out,
+    t, ids = self._combined_operands(ids, ragged=True)
+    return t._table.find_combine_ragged_weight_grad(row_splits, ids, weights, device_ops.COMBINERS[combiner], grad_out,
                                                     prune=prune, fill_id=fill_id, default_row=t._default_value)
 
   def export(self, name=None):
@@ -617,11 +579,9 @@ class Variable:
         keys = torch.from_numpy(np.fromfile(os.path.join(dirpath, fn + "-keys"), dtype=key_np)).to(self._primary)
         vals = torch.from_numpy(np.fromfile(os.path.join(dirpath, fn + "-values"), dtype=np.uint8)).view(
             self.value_dtype).reshape(-1, self.dim).to(self._primary)
-        kp, perm, counts = self._partition(keys)
-        vp = self._split_rows(vals, perm, counts)
-        for i, t in enumerate(self._tables):
-          if kp[i].numel():
-            t._checkpoint_table().upsert(kp[i].to(t._device), vp[i].to(t._device), field=f)
+        for t, k, v in self._fan_out(keys, vals)[3]:
+          if k.numel():
+            t._checkpoint_table().upsert(k, v, field=f)
     for t in self._tables:
       t._checkpoint_loaded()
 
@@ -695,7 +655,6 @@ def _plans_at_lookup_many(device, members):
   device, which waits for the current stream once — instead of one side stream, one wait and three launches per variable.
   Returns {i: plan} for the members that got a plan, or None when at most one member is eligible: a group of one keeps
   `_plan_at_lookup` on that variable's own stream."""
-  from . import table_ops
   want = [m for m in members if _wants_plan_at_lookup(m[1], m[2])]
   if len(want) < 2:
     return None
@@ -722,7 +681,6 @@ def _plans_at_lookup_many(device, members):
 
 def _pool_plan(params):
   """A free plan of the Variable's pool (a new one while fewer than PLAN_POOL_MAX exist), or None."""
-  from .table_ops import SparsePlan
   pool = params.__dict__.setdefault("_plan_pool", {"free": [], "made": 0, "stream": None})
   if pool["free"]:
     return pool["free"].pop()
@@ -1084,7 +1042,6 @@ def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None,
   that a single lookup would give a plan (`_plan_at_lookup`'s rule, per variable) get theirs from ONE grouped build per device on
   one side stream (`_plans_at_lookup_many`: tfra_multi_sparse_plan_build).  Where num_rows is absent, the grouped variables' row counts
   come from one host read per device, not one per table."""
-  from . import table_ops
   n_t = len(params_list)
   if len(sp_ids_list) != n_t:
     raise ValueError("sp_ids_list: %d entries for %d tables" % (len(sp_ids_list), n_t))

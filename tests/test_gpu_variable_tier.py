@@ -1,5 +1,6 @@
 """GPU: Variable.lookup_missed / assign / contains over 1, 2 and 3 shards (all on one device) give what one shard gives: the same
-rows, the same set of (key, batch position) pairs, the same flags; the positions index the caller's batch whatever the partition."""
+rows, the same set of (key, batch position) pairs, the same flags; the positions index the caller's batch whatever the partition.
+So do accum, remove and lookup_or_insert behind them: the same rows and flags, and the same table afterwards."""
 import numpy as np
 import pytest
 
@@ -49,8 +50,29 @@ def _run(env, shards, partitioner=None, initializer=0.5):
   assert var.assign(uniq, _rows(torch, uniq, 2)) is None
   assert [int(var.size(i)) for i in range(shards)] == size and sum(size) == N     # assign never changes size()
   after, ex_after = var.lookup(torch.cat([res, absent]), return_exists=True)
-  return dict(look=look, rows=rows, pairs=sorted(zip(mk.tolist(), mp.tolist())), mk=mk, mp=mp, ex=ex, contains=var.contains(look),
-              found=found, uniq=uniq, after=after, ex_after=ex_after, res=res)
+  out = dict(look=look, rows=rows, pairs=sorted(zip(mk.tolist(), mp.tolist())), mk=mk, mp=mp, ex=ex, contains=var.contains(look),
+             found=found, uniq=uniq, after=after, ex_after=ex_after, res=res)
+  # accum, remove and lookup_or_insert (they change size(), so they come behind everything above)
+  every = torch.cat([res, absent])
+  # accum over unique keys, resident and absent, each half claimed to exist and half not: a resident key gets new - old added
+  # (exists) or is left alone, an absent one is inserted with `new` (not exists) or ignored
+  acc = torch.cat([res[:200], absent[400:600]])[torch.from_numpy(rng.permutation(400)).cuda()]
+  claimed = torch.from_numpy(rng.integers(0, 2, size=400).astype(bool)).cuda()
+  var.accum(acc, _rows(torch, acc, 3), _rows(torch, acc, 4), claimed)
+  out["acc_rows"], out["acc_ex"] = var.lookup(every, return_exists=True)
+  out["acc_size"] = int(var.size())
+  var.remove(torch.cat([res[100:300], absent[500:700]]))
+  out["rem_rows"], out["rem_ex"] = var.lookup(every, return_exists=True)
+  out["rem_size"] = int(var.size())
+  # lookup_or_insert over unique keys, half of them never seen
+  fresh = torch.from_numpy(pool[2 * N:2 * N + 10]).cuda()
+  adm = torch.cat([res[700:710], fresh])[torch.from_numpy(rng.permutation(20)).cuda()]
+  out["adm"] = adm
+  out["adm_rows"], out["adm_ex"] = var.lookup_or_insert(adm, return_exists=True)
+  assert torch.equal(var.lookup_or_insert(adm), out["adm_rows"])     # (all resident now: the same rows, nothing new)
+  out["end_rows"], out["end_ex"] = var.lookup(torch.cat([every, fresh]), return_exists=True)
+  out["end_size"] = [int(var.size(i)) for i in range(shards)]
+  return out
 
 
 _ONE = {}
@@ -65,9 +87,11 @@ def _one(env, initializer):
 
 def _same(torch, a, b):
   assert torch.equal(a["look"], b["look"])
-  for f in ("rows", "ex", "contains", "found", "after", "ex_after"):
+  for f in ("rows", "ex", "contains", "found", "after", "ex_after", "acc_rows", "acc_ex", "rem_rows", "rem_ex", "adm", "adm_rows",
+            "adm_ex", "end_rows", "end_ex"):
     assert torch.equal(a[f], b[f]), f
   assert a["pairs"] == b["pairs"]
+  assert (a["acc_size"], a["rem_size"], sum(a["end_size"])) == (b["acc_size"], b["rem_size"], sum(b["end_size"]))
 
 
 @pytest.mark.parametrize("shards", [1, 2, 3])
@@ -83,6 +107,12 @@ def test_shards_give_the_one_shard_results(env, shards):
   assert torch.equal(r["found"], hit) and int(hit.sum()) == 400
   assert torch.equal(r["rows"][~r["ex"]], torch.full((350, DIM), 0.5, device="cuda"))
   assert int(r["ex_after"].sum()) == N             # nothing was admitted
+  # lookup_or_insert: exactly the never-seen half is reported as absent and is resident afterwards, with the rows it returned
+  seen = torch.from_numpy(np.isin(r["adm"].cpu().numpy(), r["res"].cpu().numpy())).cuda()
+  assert torch.equal(r["adm_ex"], seen) and int(seen.sum()) == 10
+  assert torch.equal(r["adm_rows"][~seen], torch.full((10, DIM), 0.5, device="cuda"))
+  assert bool(r["end_ex"][-10:].all()) and sum(r["end_size"]) == r["rem_size"] + 10
+  assert r["rem_size"] < r["acc_size"] and not bool(r["rem_ex"][100:300].any())     # remove removed
 
 
 def test_custom_partitioner(env):
