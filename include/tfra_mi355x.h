@@ -831,6 +831,27 @@ int tfra_table_find_combine_ragged(tfra_table_t* t, size_t n_rows, const int64_t
                                    const int64_t* ids, const float* weights, int combiner, uint32_t flags,
                                    int64_t fill_id, const void* default_row, float* out, tfra_stream_t stream);
 
+/* The two pooled lookups over a TIER (tfra_tier_create): tfra_table_find_combine and tfra_table_find_combine_ragged with the row of
+ * an entry taken from both tables — the row upper holds, else the row lower holds, else default_row; upper wins, as in
+ * tfra_tier_find.  The fill id of TFRA_RAGGED_FILL is looked up the same way, and the reserved key values are served in both tables.
+ * Every rule of the one-table calls holds, with their codes and wording, checked on the upper table (both tables of a tier have its
+ * value dtype, dim and device): the limits (float32 / float16 / bfloat16, dim % 4 == 0, dim <= 256, out and default_row 16-byte
+ * aligned, nnz < 2^31, n_rows < 2^30), seg ascending, row_splits clamped and never validated, PRUNE / FILL, the zero rows, and the
+ * launches — the tuple form is the bounds launch plus ONE combine launch, the ragged form ONE launch.
+ * These calls are READS: nothing moves between the tables, nothing is written to either, no score is touched and the tier's
+ * statistics do not change.  They use none of the tier's staging, so nnz is NOT limited by max_batch.  A key that is only below
+ * costs its group one more key line; a batch of U = 4 entries that all hit upper reads nothing of lower.
+ * Bit-identical to tfra_tier_find (default_is_full = 0) of ids followed by tfra_sparse_segment_combine over float32(rows) and
+ * idx = 0..nnz-1, and to tfra_table_find_combine on one table that holds the same newest rows.
+ * A NULL tier: TFRA_ERR_INVALID, nothing enqueued.  Never inserts, never promotes: a training step admits its ids first
+ * (tfra_tier_find_or_insert with values_out == NULL).                                    (tests/test_gpu_tier_pooled.py) */
+int tfra_tier_find_combine(tfra_tier_t* tier, tfra_workspace_t* ws, size_t nnz, const int64_t* ids, const int64_t* seg,
+                           const float* weights, int combiner, size_t n_rows, const void* default_row, float* out,
+                           tfra_stream_t stream);
+int tfra_tier_find_combine_ragged(tfra_tier_t* tier, size_t n_rows, const int64_t* row_splits, size_t nnz,
+                                  const int64_t* ids, const float* weights, int combiner, uint32_t flags,
+                                  int64_t fill_id, const void* default_row, float* out, tfra_stream_t stream);
+
 /* The ragged pooled lookups of MANY tables in one call (the multi-hot features of a many-table model: the Keras layers call
  * PY/ragged_embedding_ops.py:263-442 once per feature): descs[i].out is bit-identical to tfra_table_find_combine_ragged of the
  * descriptor's fields — the same device code runs — and every rule of that call holds per descriptor.  n_rows == 0: the

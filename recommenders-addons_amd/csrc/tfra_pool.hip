@@ -13,6 +13,7 @@
 // tfra_table_find_combine_ragged / tfra_multi_find_combine_ragged are the two calls over a rank-2 RaggedTensor (PY/ragged_embedding_ops.py:
 // 129-442): the row's entry range comes from row_splits, so ONE launch serves a call, and safe_embedding_lookup_sparse's pruning by
 // weight and its default_id run inside that launch (find_combine_row's RAGGED and SAFE axes; check_find_combine_ragged, with_ragged_class).
+// find_combine_row itself, the body of every kernel here, lives in tfra_pool_device.h: the tier's pooled lookup (tfra_tierpool.hip) shares it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,149 +28,11 @@
 #include "tfra_host.h"
 #include "tfra_many.h"
 #include "tfra_pool.h"
+#include "tfra_pool_device.h"
 
 using namespace tfra;
 
 namespace {
-
-// One 16-lane group per output row (find_wave's and seg_combine_kernel's mapping: 4 rows per wave64).  The row's entries [b, e)
-// are taken 16 at a time — lane j of the group loads id and weight of entry p0 + j and hashes it, one instruction stream for 16
-// keys, the next 16 loading while these are worked on — and of those U at a time: U key lines in flight before any is inspected,
-// then the U rows (NCH column chunks of 64 floats each: lane `sub` holds columns 64 c + 4 sub .. + 3) before any is accumulated.
-// Accumulation is strictly in entry order.  Loads stay unconditional, as in find_wave: entries past the row's end are clamped to
-// its last entry (probed and read again, not accumulated), columns past dim to column 0.
-// The probe is find_kernel's (probe_find_word: plain loads), so a lookup that runs beside a write-back sees what tfra_table_find sees.
-// The body is one function with four callers — find_combine_kernel (one table per launch), find_combine_many_kernel (a list of
-// tables per launch) and their ragged forms below — so that all compile the same expressions: r is the output row of this lane's
-// group in ITS table.
-// Two compile-time axes beside (DT, U, NCH):
-//   RAGGED  where [b, e) comes from: the start_end ints of the bounds launch, or an int64 row_splits[n_rows + 1] (a rank-2
-//           RaggedTensor's, PY/ragged_embedding_ops.py:129-442) clamped to 0 <= b <= e <= nnz — whatever row_splits holds, no
-//           entry outside [0, nnz) is read.
-//   SAFE    safe_embedding_lookup_sparse's semantics (PY/ragged_embedding_ops.py:414-440), by rg.flags:
-//           TFRA_RAGGED_PRUNE (with weights): only the entries with weight > 0 are members — the weight sum and the accumulation
-//           run over them, in entry order, as over the compacted list; a pruned entry is still probed and read (loads stay
-//           unconditional), like an entry past the row's end;
-//           TFRA_RAGGED_FILL: a row without members is the row of rg.fill_id (default_row on a miss), up-cast and written AS IT IS
-//           (no acc += 1 * x, no scaling: a -0.0 survives).
-// Without RAGGED and SAFE the function is the one it was: `rg` is not read.
-struct RaggedArgs {
-  const i64* row_splits;
-  int nnz;
-  unsigned flags;
-  i64 fill_id;
-};
-template <int DT, int U, int NCH, bool RAGGED = false, bool SAFE = false>
-__device__ __forceinline__ void find_combine_row(const TableView& v, size_t n_rows, int dim, const i64* __restrict__ ids,
-                                                 const float* __restrict__ w, const int* __restrict__ start_end, int combiner,
-                                                 const unsigned char* __restrict__ default_row, float* __restrict__ out, size_t r,
-                                                 const RaggedArgs& rg = RaggedArgs{}) {
-  static_assert(U == 4, "keep_live is written for U == 4");
-  typedef typename PoolRow<DT>::Raw Raw;
-  constexpr unsigned EB = DT == TFRA_F32 ? 4u : 2u;   // bytes per element
-  const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
-  if (r >= n_rows) return;
-  int b, e;
-  if constexpr (RAGGED) {
-    const i64 lo = rg.row_splits[r], hi = rg.row_splits[r + 1];
-    b = (int)min(max(lo, (i64)0), (i64)rg.nnz);
-    e = (int)min(max(hi, (i64)b), (i64)rg.nnz);
-  } else {
-    b = start_end[r];
-    e = start_end[n_rows + r];
-  }
-  bool prune = false, any = false;   // (SAFE only) any: the row has a member
-  if constexpr (SAFE) prune = (rg.flags & TFRA_RAGGED_PRUNE) && w;
-  float wsum;
-  if constexpr (SAFE) wsum = combiner == 0 ? 0.f : (prune ? comb_wsum_pruned(w, b, e, combiner) : comb_wsum(w, b, e, combiner));
-  else wsum = combiner == 0 ? 0.f : comb_wsum(w, b, e, combiner);
-  const float scale = comb_scale_of(wsum, combiner);
-  unsigned coff[NCH];   // this lane's byte offset inside a row, per chunk
-  bool cok[NCH];
-  float4 acc[NCH];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const int col = c * 64 + sub * 4;
-    cok[c] = col < dim;
-    coff[c] = cok[c] ? (unsigned)col * EB : 0u;
-    acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  if (b < e) {
-    const int last = e - 1;
-    i64 knext = ids[min(b + sub, last)];
-    float wnext = w ? w[min(b + sub, last)] : 1.f;
-    for (int p0 = b; p0 < e; p0 += 16) {
-      const i64 kreg = knext;
-      const float wreg = wnext;
-      if (p0 + 16 < e) {   // the next 16 entries, in flight behind this batch's probes and rows
-        const int pn = min(p0 + 16 + sub, last);
-        knext = ids[pn];
-        wnext = w ? w[pn] : 1.f;
-      }
-      u64 hreg;
-      const unsigned b0reg = (unsigned)bucket0(kreg, v.nb, hreg);
-      const unsigned b1reg = (unsigned)bucket1(hreg, b0reg, v.nb);
-      for (int q = 0; q < 16 && p0 + q < e; q += U) {
-        i64 key[U], k0[U];
-        unsigned b0[U], b1[U];
-        float x[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int j = gshift + q + u;
-          key[u] = shfl_i64(kreg, j);
-          b0[u] = (unsigned)__shfl((int)b0reg, j);
-          b1[u] = (unsigned)__shfl((int)b1reg, j);
-          x[u] = __shfl(wreg, j);
-          k0[u] = key_line(v, b0[u])[sub];   // U probes in flight
-        }
-        keep_live(k0[0], k0[1], k0[2], k0[3]);
-        const unsigned char* src[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const i64 word = probe_find_word(v, key[u], b0[u], b1[u], k0[u], sub, gshift);
-          src[u] = word >= 0 ? word_row_ptr(v, (u64)word) : default_row;
-        }
-        Raw t[NCH][U];
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-#pragma unroll
-          for (int u = 0; u < U; ++u) t[c][u] = *reinterpret_cast<const Raw*>(src[u] + coff[c]);   // U rows in flight
-        }
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) keep_live(t[c][0], t[c][1], t[c][2], t[c][3]);
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          bool member = p0 + q + u < e;
-          if constexpr (SAFE) {
-            member = member && (!prune || x[u] > 0.f);
-            any = any || member;
-          }
-          if (member) {
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) comb_acc4(acc[c], PoolRow<DT>::widen(t[c][u]), x[u]);
-          }
-        }
-      }
-    }
-  }
-  float* o = out + r * (size_t)dim;
-  if constexpr (SAFE) {
-    if ((rg.flags & TFRA_RAGGED_FILL) && !any) {   // (uniform in the group: every lane saw the same members)
-      u64 h;
-      const unsigned f0 = (unsigned)bucket0(rg.fill_id, v.nb, h);
-      const unsigned f1 = (unsigned)bucket1(h, f0, v.nb);
-      const i64 word = probe_find_word(v, rg.fill_id, f0, f1, key_line(v, f0)[sub], sub, gshift);
-      const unsigned char* src = word >= 0 ? word_row_ptr(v, (u64)word) : default_row;
-#pragma unroll
-      for (int c = 0; c < NCH; ++c)
-        if (cok[c]) *reinterpret_cast<float4*>(o + c * 64 + sub * 4) = PoolRow<DT>::widen(*reinterpret_cast<const Raw*>(src + coff[c]));
-      return;
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < NCH; ++c)
-    if (cok[c]) *reinterpret_cast<float4*>(o + c * 64 + sub * 4) = comb_finish4(acc[c], wsum, scale, combiner);
-}
 
 template <int DT, int U, int NCH>
 __global__ __launch_bounds__(256) void find_combine_kernel(TableView v, size_t n_rows, int dim, const i64* __restrict__ ids,

@@ -1,9 +1,14 @@
 // What the tier calls of a table (tfra_tier.hip) share with the tier driver (tfra_tierstep.hip): the block shape of
-// find_missed_kernel, the miss list it appends to, and its ONE launcher.
+// find_missed_kernel, the miss list it appends to, and its ONE launcher; and what the driver shares with the tier's pooled lookup
+// (tfra_tierpool.hip): the driver's object and the locks a call on it takes.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <mutex>
+#include <vector>
+
 #include "tfra_host.h"
+#include "tfra_many.h"
 
 // 64-key tiles (four waves each) that ONE block of find_missed_kernel covers — a block of 256 * TIER_TILES threads — and so the keys
 // behind one atomicAdd on the miss counter: 64 * TIER_TILES.  Adds to one address serialise (DESIGN §4 measured ~150 M/s), so
@@ -24,6 +29,36 @@ struct MissOut {
   int* idx;              // may be null
   tfra::u64* scores;     // find_missed's scores_out: may be null
 };
+
+// The driver's words on the device: the cumulative statistics, then the two counters of the call in flight.
+enum { TS_CALLS = 0, TS_MISSED = 1, TS_LOWER_HITS = 2, TS_DEMOTED = 3, TS_NOT_RESIDENT = 4, TS_WORDS = 8, TC_MISSED = 8, TC_DOWN = 9, TIER_WORDS = 10 };
+
+// The tier driver's object (tfra_tierstep.hip makes and drives it; the tier's pooled lookup, tfra_tierpool.hip, reads its tables).
+struct tfra_tier {
+  tfra::Table* upper = nullptr;
+  tfra::Table* lower = nullptr;
+  size_t max_batch = 0;
+  unsigned fb = 0, whole = 0;       // bytes of the embedding field and of the whole co-located row
+  unsigned char* block = nullptr;   // ONE allocation, carved below
+  tfra::u64* words = nullptr;       // [TIER_WORDS]
+  tfra::i64* miss_keys = nullptr;   // [max_batch] what the upper table missed ...
+  int* miss_idx = nullptr;          // [max_batch] ... and at which batch position
+  unsigned char* up_rows = nullptr;    // [max_batch, whole] what comes up
+  tfra::i64* down_keys = nullptr;      // [max_batch] what goes down: keys,
+  unsigned char* down_rows = nullptr;  // [max_batch, whole] whole rows
+  tfra::u64* down_scores = nullptr;    // [max_batch] and scores
+  std::mutex mu;                    // the staging belongs to one call at a time
+};
+
+// The head of every call on a tier: the driver's lock and both tables' (tfra_many.h: each once, in one global order, entered on s).
+struct TierEntry {
+  std::unique_lock<std::mutex> own;
+  std::vector<std::unique_lock<std::mutex>> tables;
+};
+static inline int tier_enter(tfra_tier* tier, hipStream_t s, TierEntry* e) {
+  e->own = std::unique_lock<std::mutex>(tier->mu);
+  return tfra::lock_and_enter({tier->upper, tier->lower}, s, &e->tables);
+}
 
 __device__ __forceinline__ size_t served(size_t n, const long long* d_n) {   // min(n, *d_n), a negative count = 0 (find_kernel's)
   if (!d_n) return n;

@@ -17,25 +17,6 @@
 
 using namespace tfra;
 
-// The driver's words on the device: the cumulative statistics, then the two counters of the call in flight.
-enum { TS_CALLS = 0, TS_MISSED = 1, TS_LOWER_HITS = 2, TS_DEMOTED = 3, TS_NOT_RESIDENT = 4, TS_WORDS = 8, TC_MISSED = 8, TC_DOWN = 9, TIER_WORDS = 10 };
-
-struct tfra_tier {
-  Table* upper = nullptr;
-  Table* lower = nullptr;
-  size_t max_batch = 0;
-  unsigned fb = 0, whole = 0;       // bytes of the embedding field and of the whole co-located row
-  unsigned char* block = nullptr;   // ONE allocation, carved below
-  u64* words = nullptr;             // [TIER_WORDS]
-  i64* miss_keys = nullptr;         // [max_batch] what the upper table missed ...
-  int* miss_idx = nullptr;          // [max_batch] ... and at which batch position
-  unsigned char* up_rows = nullptr;    // [max_batch, whole] what comes up
-  i64* down_keys = nullptr;            // [max_batch] what goes down: keys,
-  unsigned char* down_rows = nullptr;  // [max_batch, whole] whole rows
-  u64* down_scores = nullptr;          // [max_batch] and scores
-  std::mutex mu;                    // the staging belongs to one call at a time
-};
-
 // One thread, in place of a memset: the previous call's two counters go into the statistics and start from zero.
 __global__ void tier_begin_kernel(u64* w) {
   w[TS_CALLS] += 1;
@@ -120,20 +101,12 @@ static void launch_fetch(Table* lower, hipStream_t s, size_t n, const FetchIO& i
   });
 }
 
-// The head of every call on a tier: the refusals that need no device, then the driver's lock and both tables' (tfra_many.h: each
-// once, in one global order, entered on s).
-struct TierEntry {
-  std::unique_lock<std::mutex> own;
-  std::vector<std::unique_lock<std::mutex>> tables;
-};
+// The head of every call on a tier: the refusals that need no device (here), then the driver's lock and both tables' (TierEntry and
+// tier_enter: tfra_tier.h).
 static int tier_check(const char* fn, const tfra_tier* tier, size_t n, bool buffers) {
   if (!buffers) return set_error(TFRA_ERR_INVALID, std::string(fn) + ": null buffer");
   if (n > tier->max_batch) return set_error(TFRA_ERR_INVALID, std::string(fn) + ": more keys than the tier's max_batch");
   return TFRA_OK;
-}
-static int tier_enter(tfra_tier* tier, hipStream_t s, TierEntry* e) {
-  e->own = std::unique_lock<std::mutex>(tier->mu);
-  return lock_and_enter({tier->upper, tier->lower}, s, &e->tables);
 }
 
 // steps 3 and 4: `values` into the upper table, what that displaces as whole rows into the lower one

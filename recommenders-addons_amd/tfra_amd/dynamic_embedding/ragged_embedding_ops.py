@@ -21,8 +21,8 @@ made by the tuple form's preprocessing as it is, host syncs included."""
 import torch
 
 from . import device_ops, table_ops
-from .variable import (SparseTrainableWrapper, _check_combiner, _note_pruned, _per_table, _pooled_forward, _safe_sparse_args,
-                       _wrap_grouped)
+from .variable import (SparseTrainableWrapper, _check_combiner, _has_tiered_shards, _note_pruned, _per_table, _pooled_forward,
+                       _safe_sparse_args, _wrap_grouped)
 from . import variable as _tuple_form
 
 
@@ -92,6 +92,8 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights, name=None, combiner="mea
   if not _pooled_forward(params, None):
     return _tuple_form.embedding_lookup_sparse(params, (row_ids_of(rs, ids.numel()), ids), w, combiner=combiner,
                                                return_trainable=return_trainable, num_rows=n, plan_writeback=plan_writeback)
+  if return_trainable:
+    params.admit_entries(ids)   # (tiered shards: the entry ids into the cache ahead of the read; otherwise nothing)
   out = params.lookup_combined_ragged(rs, ids, w, combiner)
   if not return_trainable:
     return out
@@ -116,11 +118,12 @@ def safe_embedding_lookup_sparse(params, sparse_ids, sparse_weights=None, combin
                                                     default_id=default_id, return_trainable=return_trainable, num_rows=n,
                                                     plan_writeback=plan_writeback)
   prune, fill = _safe_flags(w, combiner, default_id)
-  out = params.lookup_combined_ragged(rs, ids, w, combiner, prune=prune, fill_id=fill)
   if not return_trainable:
-    return out
-  return out, _safe_wrapper(params, _safe_entries(params, rs, ids, w, combiner, default_id, n), combiner, n, plan_writeback,
-                            caller_weights=w)
+    return params.lookup_combined_ragged(rs, ids, w, combiner, prune=prune, fill_id=fill)
+  made = _safe_entries(params, rs, ids, w, combiner, default_id, n)
+  params.admit_entries(made[3][0])   # (tiered shards: the entry ids into the cache ahead of the read; otherwise nothing)
+  out = params.lookup_combined_ragged(rs, ids, w, combiner, prune=prune, fill_id=fill)
+  return out, _safe_wrapper(params, made, combiner, n, plan_writeback, caller_weights=w)
 
 
 def _many(params_list, sp_ids_list, weights_list, combiner, default_id, safe, return_trainable, plan_writeback):
@@ -136,7 +139,7 @@ def _many(params_list, sp_ids_list, weights_list, combiner, default_id, safe, re
   results = [None] * n_t
   groups = {}   # device -> [(i, row_splits, ids, w)]
   for i, params in enumerate(params_list):
-    if not _pooled_forward(params, None):
+    if not _pooled_forward(params, None) or _has_tiered_shards(params):   # (a tier has no grouped descriptor: the single form)
       kw = dict(default_id=default_ids[i]) if safe else {}
       results[i] = single(params, sp_ids_list[i], weights[i], combiner=combiners[i], return_trainable=return_trainable,
                           plan_writeback=plan_writeback, **kw)

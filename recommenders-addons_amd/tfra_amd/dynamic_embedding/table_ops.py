@@ -702,6 +702,38 @@ class _DeviceTier:
                  _capi.TIER_VERIFY if verify else 0, _stream(self._upper._device))
     return (out, where) if return_where else out
 
+  def admit(self, keys, init_values=None, count=None, verify=False):
+    """`find_or_insert` without its result (tfra_tier_find_or_insert with values_out and where NULL): UNIQUE keys, at most
+    max_batch; afterwards every one of them is resident in upper with its whole row, a never-seen key with its init row
+    (`init_values`: [n, dim] or one row; None: the table's default row).  count: a device int64 (or pinned) count of the leading
+    keys that are served.  No row is written back to the caller and nothing is read on the host: what a pooled training step
+    calls before `find_combine` (the write-back of the step then only hits)."""
+    keys = self._upper._keys(keys)
+    d, full = self._upper._init_rows(init_values, keys.numel())
+    if keys.numel():
+      _capi.call("tfra_tier_find_or_insert", self._h, keys.numel(), _ptr(count), _ptr(keys), _ptr(d), full, None, None,
+                 _capi.TIER_VERIFY if verify else 0, _stream(self._upper._device))
+
+  def find_combine(self, ids, seg, weights, combiner, n_rows, default_row=None):
+    """`_DeviceTable.find_combine` over both tiers (tfra_tier_find_combine): an entry's row is the one upper holds, else the one
+    lower holds, else `default_row`.  A read: nothing moves, nothing is written, `stats()` does not change; ids are not limited by
+    max_batch.  Bit-identical to `find` + device_ops.sparse_segment_combine over idx = arange(nnz)."""
+    up = self._upper
+    ids, seg, w, d, out = up._find_combine_args(ids, seg, weights, n_rows, default_row)
+    _capi.call("tfra_tier_find_combine", self._h, _workspace(up._device), ids.numel(), _ptr(ids), _ptr(seg), _ptr(w), int(combiner),
+               int(n_rows), _ptr(d), _ptr(out), _stream(up._device))
+    return out
+
+  def find_combine_ragged(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, default_row=None):
+    """`_DeviceTable.find_combine_ragged` over both tiers (tfra_tier_find_combine_ragged), in one launch: bit-identical to
+    `find_combine` on the row ids the splits stand for; the row of `fill_id` is looked up in upper, then lower, then is
+    `default_row`.  A read, as `find_combine`."""
+    up = self._upper
+    rs, ids, w, flags, fill, d, out = up._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row)
+    _capi.call("tfra_tier_find_combine_ragged", self._h, rs.numel() - 1, _ptr(rs), ids.numel(), _ptr(ids), _ptr(w), int(combiner),
+               flags, fill, _ptr(d), _ptr(out), _stream(up._device))
+    return out
+
   def insert(self, keys, values, count=None):
     """upsert of embedding rows (UNIQUE keys) into upper; what it displaces goes down as whole rows (tfra_tier_insert)."""
     keys = self._upper._keys(keys)
@@ -1159,6 +1191,19 @@ class TieredHashTable(_LookupInterfaceMirror):
 
   def find_or_insert_planned(self, plan, dynamic_default_values=None, return_exists=False, name=None):
     raise NotImplementedError("TieredHashTable has no planned admitting lookup: look the ids up with find_or_insert")
+
+  def admit(self, keys, init_values=None, count=None, verify=False):
+    """`find_or_insert` that hands no rows back (`_DeviceTier.admit`): UNIQUE keys, at most `max_batch`; afterwards each is in the
+    cache with its whole row.  What a pooled training step runs over its entry ids before `find_combine`."""
+    self._tier.admit(_as_tensor(keys, self._device), init_values, count=count, verify=verify)
+
+  def find_combine(self, ids, seg, weights, combiner, n_rows, default_row=None):
+    """The pooled lookup over both tiers (`_DeviceTier.find_combine`): a read, nothing moves."""
+    return self._tier.find_combine(ids, seg, weights, combiner, n_rows, default_row)
+
+  def find_combine_ragged(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, default_row=None):
+    """The ragged pooled lookup over both tiers (`_DeviceTier.find_combine_ragged`): a read, nothing moves."""
+    return self._tier.find_combine_ragged(row_splits, ids, weights, combiner, prune=prune, fill_id=fill_id, default_row=default_row)
 
   def lookup_missed(self, keys, dynamic_default_values=None, name=None):
     """`lookup` plus the pairs (key, position) that NEITHER tier holds (one host read for their number)."""

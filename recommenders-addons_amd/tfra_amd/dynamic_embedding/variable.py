@@ -104,6 +104,12 @@ def _has_tiered_shards(var):
   return any(isinstance(t, TieredHashTable) for t in getattr(var, "_tables", ()))
 
 
+def _pooled_reader(shard):
+  """What serves a shard's pooled read: a TieredHashTable itself — its `find_combine` / `find_combine_ragged` read both tiers —,
+  else the shard's device table."""
+  return shard if isinstance(shard, TieredHashTable) else shard._table
+
+
 def misses_are_static(var):
   """Whether a key the optimizer write-back does not find may start from the ONE static default row of `var` (a Variable, or
   anything with its `initializer`): there is no callable initializer, or the step's lookup has admitted every key with its own
@@ -391,10 +397,32 @@ class Variable:
     miss).  seg ascending; weights None = all 1; combiner "sum" / "mean" / "sqrtn".  Bit-identical to
     unique -> lookup -> device_ops.sparse_segment_combine, without the unique pass and its host read.  Never inserts."""
     t, ids = self._combined_operands(ids, ragged=False)
-    return t._table.find_combine(ids, seg, weights, device_ops.COMBINERS[combiner], n_rows, t._default_value)
+    return _pooled_reader(t).find_combine(ids, seg, weights, device_ops.COMBINERS[combiner], n_rows, t._default_value)
 
-  def _combined_operands(self, ids, ragged):
-    """-> (the one shard, the flat ids on its device) of a pooled read; ValueError unless `can_lookup_combined()`."""
+  def admit_entries(self, entry_ids):
+    """Ahead of the pooled forward of a TRAINING step over tiered shards: the entry ids — the ids the step's write-back will touch,
+    the safe form's entries for empty rows among them — de-duplicated on the device (`device_ops.unique_no_sync`) and admitted
+    into the cache with the static default row (`TieredHashTable.admit`, the count left on the device).  A key from below comes
+    up with its optimizer slots, a never-seen key enters as the write-back would have started it, so `apply_combined_gradients`
+    only hits.  Nothing is read on the host.  A variable without tiered shards: nothing to do.  More entry ids than the tier's
+    max_batch: ValueError."""
+    if not _has_tiered_shards(self):
+      return
+    t = self._tables[0]
+    ids = torch.as_tensor(entry_ids, device=t._device).reshape(-1)
+    if ids.numel() > t._tier.max_batch:
+      raise ValueError("a pooled training lookup over a tiered variable admits its entry ids in one call: %d entry ids exceed the "
+                       "tier's max_batch (%d)" % (ids.numel(), t._tier.max_batch))
+    if ids.numel():
+      uniq, _, cnt = device_ops.unique_no_sync(ids)
+      t.admit(uniq, t._default_value, count=cnt)
+
+  def _combined_operands(self, ids, ragged, one_table=False):
+    """-> (the one shard, the flat ids on its device) of a pooled read; ValueError unless `can_lookup_combined()`.  one_table: the
+    caller reads ONE device table (the weight gradients) — a tiered shard is refused, its cache alone would answer."""
+    if one_table and _has_tiered_shards(self):
+      raise ValueError("the pooled weight gradient reads one table and a tiered variable keeps rows in two: use "
+                       "SparseTrainableWrapper.weights_grad (lookup + device_ops.sparse_segment_combine_weight_grad)")
     if not self.can_lookup_combined():
       raise ValueError("%s needs one shard, a static default row, float32 / float16 / bfloat16 rows, dim %% 4 == 0 and dim <= 256; "
                        "use %s" % (("lookup_combined_ragged", "ragged_embedding_ops.embedding_lookup_sparse") if ragged else
@@ -407,22 +435,22 @@ class Variable:
     prune / fill_id: safe_embedding_lookup_sparse's pruning by weight and its default_id (`_DeviceTable.find_combine_ragged`).
     Under `can_lookup_combined()`'s conditions.  Never inserts; nothing is read on the host."""
     t, ids = self._combined_operands(ids, ragged=True)
-    return t._table.find_combine_ragged(row_splits, ids, weights, device_ops.COMBINERS[combiner], prune=prune,
-                                        fill_id=fill_id, default_row=t._default_value)
+    return _pooled_reader(t).find_combine_ragged(row_splits, ids, weights, device_ops.COMBINERS[combiner], prune=prune,
+                                                 fill_id=fill_id, default_row=t._default_value)
 
   def lookup_combined_weight_grad(self, ids, seg, weights, combiner, grad_out, name=None):
     """The gradient of `lookup_combined` with respect to `weights` (tfra_table_find_combine_backprop_weights): float32 [nnz] from
     grad_out = d loss / d result, [n_rows, dim].  The rows are read from the table as they are now, as the forward reads them
     (the default row on a miss); nothing is inserted and no [nnz, dim] tensor exists.  weights None = all 1.  Under
     `can_lookup_combined()`'s conditions."""
-    t, ids = self._combined_operands(ids, ragged=False)
+    t, ids = self._combined_operands(ids, ragged=False, one_table=True)
     return t._table.find_combine_weight_grad(ids, seg, weights, device_ops.COMBINERS[combiner], grad_out, t._default_value)
 
   def lookup_combined_ragged_weight_grad(self, row_splits, ids, weights, combiner, grad_out, prune=False, fill_id=None, name=None):
     """`lookup_combined_weight_grad` for `lookup_combined_ragged` (tfra_table_find_combine_ragged_backprop_weights): bit-identical to
     it on the row ids the splits stand for, in one launch.  prune: the entries the forward prunes get exactly 0; fill_id: the
     entries of a row that takes the fill row get 0.  Under `can_lookup_combined()`'s conditions."""
-    t, ids = self._combined_operands(ids, ragged=True)
+    t, ids = self._combined_operands(ids, ragged=True, one_table=True)
     return t._table.find_combine_ragged_weight_grad(row_splits, ids, weights, device_ops.COMBINERS[combiner], grad_out,
                                                     prune=prune, fill_id=fill_id, default_row=t._default_value)
 
@@ -892,7 +920,7 @@ class SparseTrainableWrapper(TrainableWrapper):
     The table's rows are read AS THEY ARE AT CALL TIME: call it before the step's write-back (`apply_combined_gradients`), or
     the gradient is that of the updated rows.
     A variable the pooled forward serves is read straight from the table (`Variable.lookup_combined_weight_grad`: no [nnz, dim]
-    rows); every other one — several shards, a callable initializer, bp_v2, other dims or dtypes — goes through a lookup of the
+    rows); every other one — several shards, tiered shards, a callable initializer, bp_v2, other dims or dtypes — goes through a lookup of the
     unique ids and `device_ops.sparse_segment_combine_weight_grad`.  The two routes give the same bits for the same rows.
     Nothing is read on the host on the pooled route, pruned or not (the pruned positions are filled by a masked scatter).
     ValueError for a lookup made without sp_weights, with max_norm (the clip's own gradient is not formed, as in
@@ -902,7 +930,8 @@ class SparseTrainableWrapper(TrainableWrapper):
     if self._weights is None:
       raise ValueError("weights_grad needs a lookup made with sp_weights")
     g = self.check_grad_out(grad_out)
-    if self._pooled_ids is not None and _pooled_forward(self.params, None):
+    # (tiered shards: `lookup_combined_weight_grad` would read the cache alone; the chain's `lookup` reads both tiers)
+    if self._pooled_ids is not None and _pooled_forward(self.params, None) and not _has_tiered_shards(self.params):
       dw = self.params.lookup_combined_weight_grad(self._pooled_ids, self._seg, self._weights, self.combiner, g)
     else:
       rows = self.params.lookup(self.ids).to(torch.float32)
@@ -981,7 +1010,10 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=
     shape = _out_shape if _out_shape is not None else (n, params.dim)
   if pooled:
     # the pooled read: one probe + row read per entry, combined in registers — no unique pass, no [U, dim] rows, no host read of
-    # a count (the result is bit-identical to the chain below)
+    # a count (the result is bit-identical to the chain below).  Over tiered shards a training step first brings its entry ids
+    # into the cache (`Variable.admit_entries`), and the read sees both tiers either way
+    if return_trainable:
+      params.admit_entries(e_ids)
     out = params.lookup_combined(ids, seg, w, combiner, n)
     if not return_trainable:
       return out
@@ -1038,6 +1070,7 @@ def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None,
   the (result, SparseTrainableWrapper) pair, the wrapper built behind the pooled forward.  `combiner` and `num_rows` are scalars
   or per-table lists.  The variables the pooled forward serves (`_pooled_forward`) are read by ONE grouped call per device
   (`table_ops.find_combine_many`: tfra_multi_find_combine, whose launch count does not grow with the list); every other variable
+  — a tiered one among them: its pooled read takes both tiers' views, which the grouped call's descriptors do not carry —
   takes `embedding_lookup_sparse` as it is, so no list is refused.  With return_trainable and plan_writeback the grouped members
   that a single lookup would give a plan (`_plan_at_lookup`'s rule, per variable) get theirs from ONE grouped build per device on
   one side stream (`_plans_at_lookup_many`: tfra_multi_sparse_plan_build).  Where num_rows is absent, the grouped variables' row counts
@@ -1055,7 +1088,7 @@ def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None,
   results = [None] * n_t
   groups = {}   # device -> [(i, ids, seg, w)]
   for i, params in enumerate(params_list):
-    if not _pooled_forward(params, max_norm):
+    if not _pooled_forward(params, max_norm) or _has_tiered_shards(params):   # (a tier has no grouped descriptor: the single form)
       results[i] = embedding_lookup_sparse(params, sp_ids_list[i], weights[i], combiner=combiners[i], max_norm=max_norm,
                                            return_trainable=return_trainable, num_rows=rows[i], plan_writeback=plan_writeback,
                                            _entries=entries[i], _out_shape=shapes[i])
