@@ -852,6 +852,31 @@ int tfra_tier_find_combine_ragged(tfra_tier_t* tier, size_t n_rows, const int64_
                                   const int64_t* ids, const float* weights, int combiner, uint32_t flags,
                                   int64_t fill_id, const void* default_row, float* out, tfra_stream_t stream);
 
+/* The gradient of the pooled lookup's WEIGHTS over a tier: tfra_table_find_combine_backprop_weights and
+ * tfra_table_find_combine_ragged_backprop_weights (below), with the tier in the place of the table and the row of an entry taken
+ * from both tables as in tfra_tier_find_combine.  dw_out[p] is what tfra_table_find_combine_backprop_weights gives on ONE table
+ * that holds every key's newest row: upper wins, a stale copy below a promoted key is never read, a key in neither table is
+ * default_row.  Bit-identical to that call, and to tfra_tier_find (default_is_full = 0) of ids followed by
+ * tfra_sparse_segment_combine_backprop_weights over float32(rows) and idx = 0..nnz-1.  The ragged form's PRUNE and FILL are the
+ * one-table ragged call's: a pruned entry and every entry of a row without members get exactly 0 (fill_id is not looked up, in
+ * either table); row_splits is clamped and never validated; overlapping rows as described there.
+ * Every rule of the one-table calls holds, with their codes and wording, checked on the upper table, grad_out in the place of out
+ * (16-byte aligned), dw_out 4-byte aligned and non-NULL when nnz > 0.  nnz == 0 or n_rows == 0: TFRA_OK (with nnz > 0 and no rows,
+ * dw_out is zeroed).  A NULL tier: TFRA_ERR_INVALID.  After any refusal nothing has been enqueued.
+ * These calls are READS, as the tier's pooled lookups are: nothing moves between the tables, nothing is written to either, no
+ * score is touched, tfra_tier_stats does not change, none of the tier's staging is used and nnz is NOT limited by max_batch.
+ * Enqueues what the one-table calls enqueue: the tuple form the bounds step, one memset of dw_out and ONE launch; the ragged form
+ * one memset and ONE launch.  A batch of U = 4 entries that all hit upper reads nothing of lower.
+ *                                                                                   (tests/test_gpu_tier_weight_grad.py) */
+int tfra_tier_find_combine_backprop_weights(tfra_tier_t* tier, tfra_workspace_t* ws, size_t nnz, const int64_t* ids,
+                                            const int64_t* seg, const float* weights, int combiner, size_t n_rows,
+                                            const void* default_row, const float* grad_out, float* dw_out,
+                                            tfra_stream_t stream);
+int tfra_tier_find_combine_ragged_backprop_weights(tfra_tier_t* tier, size_t n_rows, const int64_t* row_splits, size_t nnz,
+                                                   const int64_t* ids, const float* weights, int combiner, uint32_t flags,
+                                                   int64_t fill_id, const void* default_row, const float* grad_out,
+                                                   float* dw_out, tfra_stream_t stream);
+
 /* The ragged pooled lookups of MANY tables in one call (the multi-hot features of a many-table model: the Keras layers call
  * PY/ragged_embedding_ops.py:263-442 once per feature): descs[i].out is bit-identical to tfra_table_find_combine_ragged of the
  * descriptor's fields — the same device code runs — and every rule of that call holds per descriptor.  n_rows == 0: the

@@ -1,6 +1,6 @@
-// What the pooled lookup (tfra_pool.hip; over a tier: tfra_tierpool.hip) and the gradient of its weights (tfra_wgrad.hip) share, ONE copy each: the up-cast of a
+// What the pooled lookup (tfra_pool.hip; over a tier: tfra_tierpool.hip) and the gradient of its weights (tfra_wgrad.hip; over a tier: tfra_tierwgrad.hip) share, ONE copy each: the up-cast of a
 // stored row (PoolRow), the launch ladders by value dtype and row width (with_pool_class, with_ragged_class) and the argument checks
-// of the tuple and the ragged call (check_find_combine, check_find_combine_ragged).
+// of the tuple and the ragged call (check_find_combine, check_find_combine_ragged; check_dw_out for the gradient's output).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -98,6 +98,12 @@ Check check_find_combine_ragged(const Table* t, const tfra_workspace* ws, size_t
   if (!out) return refuse(TFRA_ERR_INVALID, "null out");
   if (!row_splits) return refuse(TFRA_ERR_INVALID, "null row_splits");
   if ((nnz && !ids) || ((nnz || (flags & TFRA_RAGGED_FILL)) && !default_row)) return refuse(TFRA_ERR_INVALID, "null buffer");
+  return Check{};
+}
+// what only the weight-gradient calls can get wrong, behind the forward's checks: dw_out
+Check check_dw_out(size_t nnz, const float* dw_out) {
+  if (nnz && !dw_out) return refuse(TFRA_ERR_INVALID, "null dw_out");
+  if ((uintptr_t)dw_out & 3) return refuse(TFRA_ERR_UNSUPPORTED, "misaligned dw_out (4 bytes)");
   return Check{};
 }
 // whether the flags change anything: the SAFE kernels run only then

@@ -1,6 +1,6 @@
 // What the tier calls of a table (tfra_tier.hip) share with the tier driver (tfra_tierstep.hip): the block shape of
 // find_missed_kernel, the miss list it appends to, and its ONE launcher; and what the driver shares with the tier's pooled lookup
-// (tfra_tierpool.hip): the driver's object and the locks a call on it takes.
+// (tfra_tierpool.hip) and its weight gradient (tfra_tierwgrad.hip): the driver's object and the locks a call on it takes.
 #pragma once
 #include <hip/hip_runtime.h>
 

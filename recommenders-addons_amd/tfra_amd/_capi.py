@@ -157,6 +157,9 @@ _SIGS = {
     "tfra_tier_stats": [_P, ctypes.POINTER(ctypes.c_uint64), _P],
     "tfra_tier_find_combine": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, _P, _P],
     "tfra_tier_find_combine_ragged": [_P, _SZ, _P, _SZ, _P, _P, _I, ctypes.c_uint32, ctypes.c_int64, _P, _P, _P],
+    "tfra_tier_find_combine_backprop_weights": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, _P, _P, _P],
+    "tfra_tier_find_combine_ragged_backprop_weights": [_P, _SZ, _P, _SZ, _P, _P, _I, ctypes.c_uint32, ctypes.c_int64, _P, _P, _P,
+                                                       _P],
     "tfra_table_find_n": [_P, _SZ, _P, _P, _P, _P, _P, ctypes.c_int, _P],
     "tfra_table_insert_or_assign_n": [_P, _SZ, _P, _P, _P, _P, _P],
     "tfra_table_insert_field": [_P, _I, _SZ, _P, _P, ctypes.c_uint32, _P],

@@ -734,6 +734,32 @@ class _DeviceTier:
                flags, fill, _ptr(d), _ptr(out), _stream(up._device))
     return out
 
+  def find_combine_weight_grad(self, ids, seg, weights, combiner, grad_out, default_row=None):
+    """`_DeviceTable.find_combine_weight_grad` over both tiers (tfra_tier_find_combine_backprop_weights): float32 [nnz], the rows
+    read as `find_combine` reads them — upper's, else lower's, else `default_row`.  A read: nothing moves, nothing is written,
+    `stats()` does not change; ids are not limited by max_batch.  Bit-identical to `find` +
+    device_ops.sparse_segment_combine_weight_grad over idx = arange(nnz)."""
+    up = self._upper
+    g = up._weight_grad_out(grad_out, None)
+    ids, seg, w, d, _ = up._find_combine_args(ids, seg, weights, 0, default_row)
+    dw = torch.empty(ids.numel(), dtype=torch.float32, device=up._device)
+    _capi.call("tfra_tier_find_combine_backprop_weights", self._h, _workspace(up._device), ids.numel(), _ptr(ids), _ptr(seg),
+               _ptr(w), int(combiner), g.shape[0], _ptr(d), _ptr(g), _ptr(dw), _stream(up._device))
+    return dw
+
+  def find_combine_ragged_weight_grad(self, row_splits, ids, weights, combiner, grad_out, prune=False, fill_id=None,
+                                      default_row=None):
+    """`_DeviceTable.find_combine_ragged_weight_grad` over both tiers (tfra_tier_find_combine_ragged_backprop_weights), in one
+    launch: bit-identical to `find_combine_weight_grad` on the row ids the splits stand for; prune and fill_id as there (a pruned
+    entry and the entries of a row without members get 0; the fill id is not looked up).  A read, as `find_combine_weight_grad`."""
+    up = self._upper
+    rs, ids, w, flags, fill, d, _ = up._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row)
+    g = up._weight_grad_out(grad_out, rs.numel() - 1)
+    dw = torch.empty(ids.numel(), dtype=torch.float32, device=up._device)
+    _capi.call("tfra_tier_find_combine_ragged_backprop_weights", self._h, rs.numel() - 1, _ptr(rs), ids.numel(), _ptr(ids),
+               _ptr(w), int(combiner), flags, fill, _ptr(d), _ptr(g), _ptr(dw), _stream(up._device))
+    return dw
+
   def insert(self, keys, values, count=None):
     """upsert of embedding rows (UNIQUE keys) into upper; what it displaces goes down as whole rows (tfra_tier_insert)."""
     keys = self._upper._keys(keys)
@@ -1204,6 +1230,17 @@ class TieredHashTable(_LookupInterfaceMirror):
   def find_combine_ragged(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, default_row=None):
     """The ragged pooled lookup over both tiers (`_DeviceTier.find_combine_ragged`): a read, nothing moves."""
     return self._tier.find_combine_ragged(row_splits, ids, weights, combiner, prune=prune, fill_id=fill_id, default_row=default_row)
+
+  def find_combine_weight_grad(self, ids, seg, weights, combiner, grad_out, default_row=None):
+    """The gradient of `find_combine` with respect to its weights, over both tiers (`_DeviceTier.find_combine_weight_grad`): a
+    read, nothing moves."""
+    return self._tier.find_combine_weight_grad(ids, seg, weights, combiner, grad_out, default_row)
+
+  def find_combine_ragged_weight_grad(self, row_splits, ids, weights, combiner, grad_out, prune=False, fill_id=None,
+                                      default_row=None):
+    """The same gradient for `find_combine_ragged` (`_DeviceTier.find_combine_ragged_weight_grad`): a read, nothing moves."""
+    return self._tier.find_combine_ragged_weight_grad(row_splits, ids, weights, combiner, grad_out, prune=prune, fill_id=fill_id,
+                                                      default_row=default_row)
 
   def lookup_missed(self, keys, dynamic_default_values=None, name=None):
     """`lookup` plus the pairs (key, position) that NEITHER tier holds (one host read for their number)."""

@@ -105,8 +105,8 @@ def _has_tiered_shards(var):
 
 
 def _pooled_reader(shard):
-  """What serves a shard's pooled read: a TieredHashTable itself — its `find_combine` / `find_combine_ragged` read both tiers —,
-  else the shard's device table."""
+  """What serves a shard's pooled read: a TieredHashTable itself — its `find_combine` / `find_combine_ragged` and their
+  `*_weight_grad` forms read both tiers —, else the shard's device table."""
   return shard if isinstance(shard, TieredHashTable) else shard._table
 
 
@@ -417,12 +417,9 @@ class Variable:
       uniq, _, cnt = device_ops.unique_no_sync(ids)
       t.admit(uniq, t._default_value, count=cnt)
 
-  def _combined_operands(self, ids, ragged, one_table=False):
-    """-> (the one shard, the flat ids on its device) of a pooled read; ValueError unless `can_lookup_combined()`.  one_table: the
-    caller reads ONE device table (the weight gradients) — a tiered shard is refused, its cache alone would answer."""
-    if one_table and _has_tiered_shards(self):
-      raise ValueError("the pooled weight gradient reads one table and a tiered variable keeps rows in two: use "
-                       "SparseTrainableWrapper.weights_grad (lookup + device_ops.sparse_segment_combine_weight_grad)")
+  def _combined_operands(self, ids, ragged):
+    """-> (the one shard, the flat ids on its device) of a pooled read — the forward or the weight gradient, over one table or a
+    tier (`_pooled_reader` serves the shard) —; ValueError unless `can_lookup_combined()`."""
     if not self.can_lookup_combined():
       raise ValueError("%s needs one shard, a static default row, float32 / float16 / bfloat16 rows, dim %% 4 == 0 and dim <= 256; "
                        "use %s" % (("lookup_combined_ragged", "ragged_embedding_ops.embedding_lookup_sparse") if ragged else
@@ -441,18 +438,20 @@ class Variable:
   def lookup_combined_weight_grad(self, ids, seg, weights, combiner, grad_out, name=None):
     """The gradient of `lookup_combined` with respect to `weights` (tfra_table_find_combine_backprop_weights): float32 [nnz] from
     grad_out = d loss / d result, [n_rows, dim].  The rows are read from the table as they are now, as the forward reads them
-    (the default row on a miss); nothing is inserted and no [nnz, dim] tensor exists.  weights None = all 1.  Under
+    (the default row on a miss); nothing is inserted and no [nnz, dim] tensor exists.  weights None = all 1.  A tiered shard is
+    read in both tiers (tfra_tier_find_combine_backprop_weights: the cache's row, else the lower table's), nothing moves.  Under
     `can_lookup_combined()`'s conditions."""
-    t, ids = self._combined_operands(ids, ragged=False, one_table=True)
-    return t._table.find_combine_weight_grad(ids, seg, weights, device_ops.COMBINERS[combiner], grad_out, t._default_value)
+    t, ids = self._combined_operands(ids, ragged=False)
+    return _pooled_reader(t).find_combine_weight_grad(ids, seg, weights, device_ops.COMBINERS[combiner], grad_out, t._default_value)
 
   def lookup_combined_ragged_weight_grad(self, row_splits, ids, weights, combiner, grad_out, prune=False, fill_id=None, name=None):
     """`lookup_combined_weight_grad` for `lookup_combined_ragged` (tfra_table_find_combine_ragged_backprop_weights): bit-identical to
     it on the row ids the splits stand for, in one launch.  prune: the entries the forward prunes get exactly 0; fill_id: the
-    entries of a row that takes the fill row get 0.  Under `can_lookup_combined()`'s conditions."""
-    t, ids = self._combined_operands(ids, ragged=True, one_table=True)
-    return t._table.find_combine_ragged_weight_grad(row_splits, ids, weights, device_ops.COMBINERS[combiner], grad_out,
-                                                    prune=prune, fill_id=fill_id, default_row=t._default_value)
+    entries of a row that takes the fill row get 0.  A tiered shard is read in both tiers
+    (tfra_tier_find_combine_ragged_backprop_weights).  Under `can_lookup_combined()`'s conditions."""
+    t, ids = self._combined_operands(ids, ragged=True)
+    return _pooled_reader(t).find_combine_ragged_weight_grad(row_splits, ids, weights, device_ops.COMBINERS[combiner], grad_out,
+                                                             prune=prune, fill_id=fill_id, default_row=t._default_value)
 
   def export(self, name=None):
     """PY/dynamic_embedding_variable.py:988-1007"""
@@ -919,9 +918,10 @@ class SparseTrainableWrapper(TrainableWrapper):
     it adds for empty rows are not the caller's and do not appear; a row that took `default_id` contributes nothing.
     The table's rows are read AS THEY ARE AT CALL TIME: call it before the step's write-back (`apply_combined_gradients`), or
     the gradient is that of the updated rows.
-    A variable the pooled forward serves is read straight from the table (`Variable.lookup_combined_weight_grad`: no [nnz, dim]
-    rows); every other one — several shards, tiered shards, a callable initializer, bp_v2, other dims or dtypes — goes through a lookup of the
-    unique ids and `device_ops.sparse_segment_combine_weight_grad`.  The two routes give the same bits for the same rows.
+    A variable the pooled forward serves, tiered or not, is read straight from the table (`Variable.lookup_combined_weight_grad`:
+    no [nnz, dim] rows; a tier is read in both tables); every other one — several shards, a callable initializer, bp_v2, other
+    dims or dtypes — goes through a lookup of the unique ids and `device_ops.sparse_segment_combine_weight_grad`.  The two routes
+    give the same bits for the same rows.
     Nothing is read on the host on the pooled route, pruned or not (the pruned positions are filled by a masked scatter).
     ValueError for a lookup made without sp_weights, with max_norm (the clip's own gradient is not formed, as in
     `apply_combined_gradients`), or for a grad_out of another shape."""
@@ -930,8 +930,7 @@ class SparseTrainableWrapper(TrainableWrapper):
     if self._weights is None:
       raise ValueError("weights_grad needs a lookup made with sp_weights")
     g = self.check_grad_out(grad_out)
-    # (tiered shards: `lookup_combined_weight_grad` would read the cache alone; the chain's `lookup` reads both tiers)
-    if self._pooled_ids is not None and _pooled_forward(self.params, None) and not _has_tiered_shards(self.params):
+    if self._pooled_ids is not None and _pooled_forward(self.params, None):
       dw = self.params.lookup_combined_weight_grad(self._pooled_ids, self._seg, self._weights, self.combiner, g)
     else:
       rows = self.params.lookup(self.ids).to(torch.float32)
