@@ -900,6 +900,56 @@ typedef struct {
 int tfra_multi_find_combine_ragged(tfra_workspace_t* ws, size_t n_tables, const tfra_find_combine_ragged_desc* descs,
                                    uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
 
+/* The two grouped pooled lookups over a list whose members are TIERS or plain tables (a many-table model keeps its big tables
+ * tiered and its small ones plain, and one call reads all of them): tfra_multi_find_combine / tfra_multi_find_combine_ragged with
+ * a descriptor that names exactly ONE of table / tier.  descs[i].out is bit-identical to the single call on that descriptor — the
+ * same device function runs: a descriptor that names a tier matches tfra_tier_find_combine / tfra_tier_find_combine_ragged (upper
+ * wins, else lower, else default_row; the fill id is looked up the same way), one that names a table matches
+ * tfra_table_find_combine / tfra_table_find_combine_ragged.  Every rule of the single calls holds per descriptor, with their codes
+ * and wording, checked on the table or on the tier's upper table.  n_rows == 0: the descriptor is skipped.  nnz == 0: its out is
+ * zero-filled (ragged form with FILL: the kernel runs and every row is the fill row).  n_tables == 0: TFRA_OK.
+ * All descriptors are checked BEFORE anything is enqueued: if one fails, the call returns the single call's code, the message is
+ * "multi_tier_find_combine[_ragged]: descriptor <i>: ..." and no out of any descriptor is written.  Both of table / tier set,
+ * neither of them set, a wrong struct_size, a non-zero `reserved`, a table on another device than ws, or descs == NULL with
+ * n_tables > 0: TFRA_ERR_INVALID.
+ * These calls are READS, as the single tier calls are: nothing moves between the tables, nothing is written to any of them, no
+ * score is touched, tfra_tier_stats does not change, no tier's staging is used and nnz is not limited by max_batch.  So the same
+ * tier and the same table may stand in several descriptors, and a table may be named directly in one descriptor while it is the
+ * upper or lower table of a tier in another.
+ * Locks: each distinct tier's own mutex once, in address order, before any table lock; then every distinct table of the call
+ * (plain ones, uppers, lowers) once, in the global order of tfra_multi_find_combine — the hierarchy of the single tier calls.  The
+ * tables' storage is looked at under the locks: a lower table that grew between two calls is read where it is now.
+ * Enqueues, whatever n_tables: one upload of the records (the ring of pinned, event-guarded slots in ws that
+ * tfra_multi_find_combine uses: calls may follow each other with no host wait); the tuple form then one memset of all rows'
+ * bounds, ONE bounds launch over all descriptors, tiered or not, and one combine launch per (tiered or not, value dtype, NCH)
+ * class in the list, at most 18; the ragged form one launch per (tiered or not, value dtype, NCH, safe or not) class, at most 36,
+ * no memset and no bounds launch.  The plain classes run the kernels of tfra_multi_find_combine[_ragged].  *launches_out
+ * (optional, host): the kernel launches enqueued.  Not for stream capture.  A training step still admits each tier's ids with a
+ * tfra_tier_find_or_insert of its own first: what these calls collapse is the read.       (tests/test_gpu_tier_pooled_many.py) */
+typedef struct {
+  uint32_t struct_size;      /* = sizeof(tfra_tier_find_combine_desc) */
+  int32_t  combiner;         /* 0 sum | 1 mean | 2 sqrtn */
+  tfra_table_t* table;       /* exactly ONE of table / tier is non-NULL */
+  tfra_tier_t*  tier;
+  size_t nnz; const int64_t* ids; const int64_t* seg; const float* weights;   /* weights may be NULL */
+  size_t n_rows; const void* default_row; float* out;                         /* out [n_rows, dim] float32 */
+} tfra_tier_find_combine_desc;
+int tfra_multi_tier_find_combine(tfra_workspace_t* ws, size_t n_tables, const tfra_tier_find_combine_desc* descs,
+                                 uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
+
+typedef struct {
+  uint32_t struct_size;      /* = sizeof(tfra_tier_find_combine_ragged_desc) */
+  int32_t  combiner;         /* 0 sum | 1 mean | 2 sqrtn */
+  tfra_table_t* table;       /* exactly ONE of table / tier is non-NULL */
+  tfra_tier_t*  tier;
+  size_t n_rows; const int64_t* row_splits;                                   /* [n_rows + 1] */
+  size_t nnz; const int64_t* ids; const float* weights;                       /* weights may be NULL */
+  uint32_t flags; uint32_t reserved;                                          /* TFRA_RAGGED_*; reserved = 0 */
+  int64_t fill_id; const void* default_row; float* out;                       /* out [n_rows, dim] float32 */
+} tfra_tier_find_combine_ragged_desc;
+int tfra_multi_tier_find_combine_ragged(tfra_workspace_t* ws, size_t n_tables, const tfra_tier_find_combine_ragged_desc* descs,
+                                        uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
+
 /* The gradient of the pooled lookup with respect to its WEIGHTS (sp_weights of embedding_lookup_sparse; the reference gets it
  * from TensorFlow's autodiff of `embeddings *= weights`, segment_sum and the divide, PY/dynamic_embedding_ops.py:233-291):
  * dw_out[p] = d loss / d weights[p], float32 [nnz], for grad_out = d loss / d out, float32 [n_rows, dim].

@@ -7,9 +7,10 @@
 // entries in input order, probes the table once per entry and accumulates w * row in registers: neither tensor exists and
 // nothing is counted on the host.  The arithmetic is tfra_combine_device.h's, the code seg_combine_kernel (tfra_combine.hip)
 // compiles, in the same order, so the result equals tfra_table_find + tfra_sparse_segment_combine bit for bit.
-// tfra_multi_find_combine is the same lookup for a list of tables; its host side stands on the grouped-call frame of tfra_many.h,
-// and both calls run ONE function for their argument checks (check_find_combine) and one launch ladder (with_pool_class); those
-// live in tfra_pool.h, which the gradient of the lookup's weights (tfra_wgrad.hip) shares.
+// tfra_multi_find_combine is the same lookup for a list of tables; its host side is the frame the grouped lookup over tiers shares
+// (multi_find_combine_frame, tfra_tierpool_many.hip, on the grouped-call pieces of tfra_many.h), which launches this unit's kernels
+// through launch_find_combine_many.  Both calls run ONE function for their argument checks (check_find_combine) and one launch
+// ladder (with_pool_class); those live in tfra_pool.h, which the gradient of the lookup's weights (tfra_wgrad.hip) shares.
 // tfra_table_find_combine_ragged / tfra_multi_find_combine_ragged are the two calls over a rank-2 RaggedTensor (PY/ragged_embedding_ops.py:
 // 129-442): the row's entry range comes from row_splits, so ONE launch serves a call, and safe_embedding_lookup_sparse's pruning by
 // weight and its default_id run inside that launch (find_combine_row's RAGGED and SAFE axes; check_find_combine_ragged, with_ragged_class).
@@ -29,6 +30,7 @@
 #include "tfra_many.h"
 #include "tfra_pool.h"
 #include "tfra_pool_device.h"
+#include "tfra_pool_many.h"
 
 using namespace tfra;
 
@@ -44,20 +46,8 @@ __global__ __launch_bounds__(256) void find_combine_kernel(TableView v, size_t n
 }
 
 // ---- the grouped form (tfra_multi_find_combine): the lookups of a LIST of tables in one launch per (value dtype, NCH) class ------
-// What a single-table launch takes as kernel arguments is a record in device memory here (26 tables' records do not fit the 4 KB
-// of kernel arguments: a TableView alone is 80 B).  The grid is the concatenation of the class's descriptors, descriptor d owning
-// the blocks [prefix[d], prefix[d + 1]) = ceil(n_rows * 16 / 256) blocks, so that a block never straddles two descriptors.
-struct ManyRec {
-  TableView v;
-  size_t n_rows;
-  const i64* ids;
-  const float* w;
-  const int* se;
-  const unsigned char* default_row;
-  float* out;
-  int dim;
-  int combiner;
-};
+// What a single-table launch takes as kernel arguments is a record in device memory here (ManyRec: tfra_pool_many.h, which the
+// tier's grouped kernels share).
 // (BoundsRec, the record of the bounds launch, and many_desc_of, the search that takes a block to its descriptor: tfra_many.h)
 
 template <int DT, int U, int NCH>
@@ -83,21 +73,7 @@ __global__ __launch_bounds__(256) void find_combine_ragged_kernel(TableView v, s
                                            ((size_t)blockIdx.x * 256 + threadIdx.x) >> 4, RaggedArgs{row_splits, nnz, flags, fill_id});
 }
 
-struct RaggedRec {
-  TableView v;
-  size_t n_rows;
-  const i64* ids;
-  const float* w;
-  const i64* row_splits;
-  const unsigned char* default_row;
-  float* out;
-  i64 fill_id;
-  int nnz;
-  int dim;
-  int combiner;
-  unsigned flags;
-};
-
+// (RaggedRec, the ragged record: tfra_pool_many.h)
 template <int DT, int U, int NCH, bool SAFE>
 __global__ __launch_bounds__(256) void find_combine_ragged_many_kernel(const RaggedRec* __restrict__ recs,
                                                                        const unsigned* __restrict__ prefix, unsigned n) {
@@ -164,6 +140,19 @@ int comb_bounds_many(hipStream_t s, unsigned grid, const BoundsRec* recs, const 
   return TFRA_OK;
 }
 
+// the one instantiation of the grouped one-table kernels, for the frames of tfra_tierpool_many.hip (cls: tfra_pool_many.h)
+void launch_find_combine_many(hipStream_t s, int cls, unsigned grid, const ManyRec* recs, const unsigned* prefix, unsigned n) {
+  with_pool_class(cls / 3, cls % 3, [&](auto DT, auto U, auto NCH) {
+    find_combine_many_kernel<DT, U, NCH><<<grid, 256, 0, s>>>(recs, prefix, n);
+  });
+}
+void launch_find_combine_ragged_many(hipStream_t s, int cls, bool safe, unsigned grid, const RaggedRec* recs, const unsigned* prefix,
+                                     unsigned n) {
+  with_ragged_class(cls / 3, cls % 3, safe, [&](auto DT, auto U, auto NCH, auto SAFE) {
+    find_combine_ragged_many_kernel<DT, U, NCH, SAFE><<<grid, 256, 0, s>>>(recs, prefix, n);
+  });
+}
+
 void destroy_workspace_many(void* p) {
   ManyStage* st = reinterpret_cast<ManyStage*>(p);
   if (!st) return;
@@ -176,110 +165,16 @@ void destroy_workspace_many(void* p) {
 }
 }  // namespace tfra
 
+// The grouped calls' host side is ONE frame per form (multi_find_combine_frame / multi_find_combine_ragged_frame, tfra_tierpool_many.hip),
+// over descriptors of this ABI or of the tier ABI; the launches of the one-table classes come back here (the launchers above).
+static PoolDesc plain_desc_at(const void* descs, size_t i) {
+  const tfra_find_combine_desc& d = static_cast<const tfra_find_combine_desc*>(descs)[i];
+  return PoolDesc{d.struct_size == sizeof(tfra_find_combine_desc), false, reinterpret_cast<Table*>(d.table), nullptr, d.combiner, d.nnz,
+                  d.ids, d.seg, nullptr, d.weights, d.n_rows, 0, 0, 0, d.default_row, d.out};
+}
 extern "C" int tfra_multi_find_combine(tfra_workspace_t* ws, size_t n_tables, const tfra_find_combine_desc* descs,
                                        uint32_t* launches_out, tfra_stream_t stream) {
-  if (launches_out) *launches_out = 0;
-  if (n_tables == 0) return TFRA_OK;
-  if (!ws || !descs) return set_error(TFRA_ERR_INVALID, "multi_find_combine: null argument");
-  hipStream_t s = (hipStream_t)stream;
-  // every descriptor is checked before anything is enqueued: one bad descriptor and no out is written
-  constexpr int NCLASS = 9;   // (float32 | float16 | bfloat16) x (NCH 1 | 2 | 4)
-  std::vector<int> cls(n_tables, -1);
-  std::vector<size_t> se_off(n_tables, 0);   // a descriptor's bounds in the bounds area, in input order
-  size_t n_act = 0, n_bnd = 0, total_rows = 0;
-  u64 bnd_blocks = 0;
-  for (size_t i = 0; i < n_tables; ++i) {
-    const tfra_find_combine_desc& d = descs[i];
-    if (d.struct_size != sizeof(tfra_find_combine_desc))
-      return set_error(TFRA_ERR_INVALID, "multi_find_combine: descriptor " + std::to_string(i) + ": descriptor size mismatch");
-    const Table* t = reinterpret_cast<const Table*>(d.table);
-    const Check c = check_find_combine(t, ws, d.nnz, d.ids, d.seg, d.weights, d.combiner, d.n_rows, d.default_row, d.out, [] { return Check{}; });
-    if (c.code) return report("multi_find_combine: descriptor " + std::to_string(i) + ": ", c);
-    if (!c.active) continue;
-    cls[i] = st_index(t->opts.value_dtype) * 3 + nch_index(t->opts.dim);
-    ++n_act;
-    n_bnd += d.nnz ? 1 : 0;
-    bnd_blocks += (d.nnz + 255) / 256;
-    se_off[i] = 2 * total_rows;
-    total_rows += d.n_rows;
-  }
-  if (n_act == 0) return TFRA_OK;
-  // the records' order: class by class, input order inside a class
-  auto row_blocks = [&](size_t i) { return (unsigned)((descs[i].n_rows * 16 + 255) / 256); };
-  auto bnd_blocks_of = [&](size_t i) { return (unsigned)((descs[i].nnz + 255) / 256); };
-  std::vector<size_t> order;
-  order.reserve(n_act);
-  size_t cls_first[NCLASS + 1];
-  for (int c = 0; c < NCLASS; ++c) {
-    cls_first[c] = order.size();
-    u64 blocks = 0;
-    for (size_t i = 0; i < n_tables; ++i)
-      if (cls[i] == c) { order.push_back(i); blocks += row_blocks(i); }
-    if (blocks >= (1ULL << 31)) return set_error(TFRA_ERR_UNSUPPORTED, "multi_find_combine: too many rows in one call");
-  }
-  cls_first[NCLASS] = order.size();
-  if (bnd_blocks >= (1ULL << 31)) return set_error(TFRA_ERR_UNSUPPORTED, "multi_find_combine: too many entries in one call");
-
-  // (one table may stand in several descriptors: locked once)
-  std::vector<Table*> tabs;
-  tabs.reserve(n_act);
-  for (size_t i : order) tabs.push_back(reinterpret_cast<Table*>(descs[i].table));
-  std::vector<std::unique_lock<std::mutex>> locks;
-  int rc = lock_and_enter(std::move(tabs), s, &locks);
-  if (rc) return rc;
-
-  // device memory: [bounds of all rows | blob], the blob = [records | per-class block prefixes | bounds records | their block prefix]
-  const size_t se_bytes = (2 * total_rows * sizeof(int) + 255) / 256 * 256;
-  Blob blob;
-  const size_t rec_off = blob.add<ManyRec>(n_act), cpre_off = blob.add<unsigned>(ClassPool::words(n_act, NCLASS, false));
-  const size_t brec_off = blob.add<BoundsRec>(n_bnd), bpre_off = blob.add<unsigned>(ClassPool::words(n_bnd, 1, false));
-  ManyUpload up;
-  rc = many_begin(ws, se_bytes, blob.bytes(), s, &up);
-  if (rc) return rc;
-  int* se_base = (int*)ws->buf;
-  ManyRec* recs = section<ManyRec>(up.host, rec_off);
-  BoundsRec* brecs = section<BoundsRec>(up.host, brec_off);
-  // the views are taken here, under the locks: a table that grew since the last call has another one
-  for (size_t k = 0; k < n_act; ++k) {
-    const tfra_find_combine_desc& d = descs[order[k]];
-    Table* t = reinterpret_cast<Table*>(d.table);
-    recs[k] = ManyRec{t->view_of(t->cur), d.n_rows, (const i64*)d.ids, d.weights, se_base + se_off[order[k]],
-                      (const unsigned char*)d.default_row, d.out, t->opts.dim, d.combiner};
-  }
-  // the records stand in class order: a class is a range of them and needs no index
-  ClassPool cpool{section<unsigned>(up.host, cpre_off)};
-  ManyClass row_cls[NCLASS];
-  for (int c = 0; c < NCLASS; ++c)
-    row_cls[c] = cpool.put(n_act, false, [&](size_t k) { return k >= cls_first[c] && k < cls_first[c + 1]; },
-                           [&](size_t k) { return row_blocks(order[k]); });
-  auto bounded = [&](size_t i) { return cls[i] >= 0 && descs[i].nnz != 0; };
-  {
-    size_t k = 0;
-    for (size_t i = 0; i < n_tables; ++i)
-      if (bounded(i)) brecs[k++] = BoundsRec{(const i64*)descs[i].seg, se_base + se_off[i], descs[i].nnz, descs[i].n_rows};
-  }
-  const ManyClass bnd = ClassPool{section<unsigned>(up.host, bpre_off)}.put(n_tables, false, bounded, bnd_blocks_of);
-  rc = many_send(up, s, "hipMemcpyAsync(d_blob, h, blob_bytes, hipMemcpyHostToDevice, s)", true);
-  if (rc) return rc;
-  HIP_TRY(hipMemsetAsync(se_base, 0, 2 * total_rows * sizeof(int), s));   // empty rows (and every row of an nnz == 0 descriptor): 0, 0
-  uint32_t launches = 0;
-  if (bnd.n) {
-    seg64_bounds_many_kernel<<<bnd.grid, 256, 0, s>>>(section<const BoundsRec>(up.dev, brec_off), section<const unsigned>(up.dev, bpre_off), bnd.n);
-    ++launches;
-  }
-  for (int c = 0; c < NCLASS; ++c) {
-    const ManyClass& k = row_cls[c];
-    if (!k.n) continue;
-    const ManyRec* r = section<const ManyRec>(up.dev, rec_off) + cls_first[c];
-    const unsigned* p = section<const unsigned>(up.dev, cpre_off) + k.at;
-    with_pool_class(c / 3, c % 3, [&](auto DT, auto U, auto NCH) {
-      find_combine_many_kernel<DT, U, NCH><<<k.grid, 256, 0, s>>>(r, p, k.n);
-    });
-    ++launches;
-  }
-  HIP_TRY(hipGetLastError());
-  if (launches_out) *launches_out = launches;
-  return TFRA_OK;
+  return multi_find_combine_frame("multi_find_combine", ws, n_tables, descs, plain_desc_at, launches_out, (hipStream_t)stream);
 }
 
 // ---- the ragged calls ------------------------------------------------------------------------------------------------------------------
@@ -312,84 +207,13 @@ extern "C" int tfra_table_find_combine_ragged(tfra_table_t* tp, size_t n_rows, c
   return TFRA_OK;
 }
 
+static PoolDesc plain_ragged_desc_at(const void* descs, size_t i) {
+  const tfra_find_combine_ragged_desc& d = static_cast<const tfra_find_combine_ragged_desc*>(descs)[i];
+  return PoolDesc{d.struct_size == sizeof(tfra_find_combine_ragged_desc), false, reinterpret_cast<Table*>(d.table), nullptr, d.combiner,
+                  d.nnz, d.ids, nullptr, d.row_splits, d.weights, d.n_rows, d.flags, d.reserved, d.fill_id, d.default_row, d.out};
+}
 extern "C" int tfra_multi_find_combine_ragged(tfra_workspace_t* ws, size_t n_tables, const tfra_find_combine_ragged_desc* descs,
                                               uint32_t* launches_out, tfra_stream_t stream) {
-  if (launches_out) *launches_out = 0;
-  if (n_tables == 0) return TFRA_OK;
-  if (!ws || !descs) return set_error(TFRA_ERR_INVALID, "multi_find_combine_ragged: null argument");
-  hipStream_t s = (hipStream_t)stream;
-  // every descriptor is checked before anything is enqueued: one bad descriptor and no out is written
-  constexpr int NCLASS = 18;   // (float32 | float16 | bfloat16) x (NCH 1 | 2 | 4) x (plain | safe)
-  std::vector<int> cls(n_tables, -1);
-  size_t n_act = 0;
-  for (size_t i = 0; i < n_tables; ++i) {
-    const tfra_find_combine_ragged_desc& d = descs[i];
-    if (d.struct_size != sizeof(tfra_find_combine_ragged_desc))
-      return set_error(TFRA_ERR_INVALID, "multi_find_combine_ragged: descriptor " + std::to_string(i) + ": descriptor size mismatch");
-    const Table* t = reinterpret_cast<const Table*>(d.table);
-    const Check c = check_find_combine_ragged(t, ws, d.n_rows, d.row_splits, d.nnz, d.ids, d.weights, d.combiner, d.flags, d.reserved,
-                                              d.default_row, d.out, [] { return Check{}; });
-    if (c.code) return report("multi_find_combine_ragged: descriptor " + std::to_string(i) + ": ", c);
-    if (!c.active) continue;
-    cls[i] = (st_index(t->opts.value_dtype) * 3 + nch_index(t->opts.dim)) * 2 + (ragged_safe(d.flags, d.weights) ? 1 : 0);
-    ++n_act;
-  }
-  if (n_act == 0) return TFRA_OK;
-  // the records' order: class by class, input order inside a class
-  auto row_blocks = [&](size_t i) { return (unsigned)((descs[i].n_rows * 16 + 255) / 256); };
-  std::vector<size_t> order;
-  order.reserve(n_act);
-  size_t cls_first[NCLASS + 1];
-  for (int c = 0; c < NCLASS; ++c) {
-    cls_first[c] = order.size();
-    u64 blocks = 0;
-    for (size_t i = 0; i < n_tables; ++i)
-      if (cls[i] == c) { order.push_back(i); blocks += row_blocks(i); }
-    if (blocks >= (1ULL << 31)) return set_error(TFRA_ERR_UNSUPPORTED, "multi_find_combine_ragged: too many rows in one call");
-  }
-  cls_first[NCLASS] = order.size();
-
-  // (one table may stand in several descriptors: locked once)
-  std::vector<Table*> tabs;
-  tabs.reserve(n_act);
-  for (size_t i : order) tabs.push_back(reinterpret_cast<Table*>(descs[i].table));
-  std::vector<std::unique_lock<std::mutex>> locks;
-  int rc = lock_and_enter(std::move(tabs), s, &locks);
-  if (rc) return rc;
-
-  // device memory: the blob alone = [records | per-class block prefixes]; there are no bounds to keep
-  Blob blob;
-  const size_t rec_off = blob.add<RaggedRec>(n_act), cpre_off = blob.add<unsigned>(ClassPool::words(n_act, NCLASS, false));
-  ManyUpload up;
-  rc = many_begin(ws, 0, blob.bytes(), s, &up);
-  if (rc) return rc;
-  RaggedRec* recs = section<RaggedRec>(up.host, rec_off);
-  // the views are taken here, under the locks: a table that grew since the last call has another one
-  for (size_t k = 0; k < n_act; ++k) {
-    const tfra_find_combine_ragged_desc& d = descs[order[k]];
-    Table* t = reinterpret_cast<Table*>(d.table);
-    recs[k] = RaggedRec{t->view_of(t->cur), d.n_rows, (const i64*)d.ids, d.weights, (const i64*)d.row_splits,
-                        (const unsigned char*)d.default_row, d.out, (i64)d.fill_id, (int)d.nnz, t->opts.dim, d.combiner, d.flags};
-  }
-  ClassPool cpool{section<unsigned>(up.host, cpre_off)};
-  ManyClass row_cls[NCLASS];
-  for (int c = 0; c < NCLASS; ++c)
-    row_cls[c] = cpool.put(n_act, false, [&](size_t k) { return k >= cls_first[c] && k < cls_first[c + 1]; },
-                           [&](size_t k) { return row_blocks(order[k]); });
-  rc = many_send(up, s, "hipMemcpyAsync(d_blob, h, blob_bytes, hipMemcpyHostToDevice, s)", true);
-  if (rc) return rc;
-  uint32_t launches = 0;
-  for (int c = 0; c < NCLASS; ++c) {
-    const ManyClass& k = row_cls[c];
-    if (!k.n) continue;
-    const RaggedRec* r = section<const RaggedRec>(up.dev, rec_off) + cls_first[c];
-    const unsigned* p = section<const unsigned>(up.dev, cpre_off) + k.at;
-    with_ragged_class(c / 6, (c / 2) % 3, c & 1, [&](auto DT, auto U, auto NCH, auto SAFE) {
-      find_combine_ragged_many_kernel<DT, U, NCH, SAFE><<<k.grid, 256, 0, s>>>(r, p, k.n);
-    });
-    ++launches;
-  }
-  HIP_TRY(hipGetLastError());
-  if (launches_out) *launches_out = launches;
-  return TFRA_OK;
+  return multi_find_combine_ragged_frame("multi_find_combine_ragged", ws, n_tables, descs, plain_ragged_desc_at, launches_out,
+                                         (hipStream_t)stream);
 }

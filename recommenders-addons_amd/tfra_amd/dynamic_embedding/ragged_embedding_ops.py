@@ -21,8 +21,8 @@ made by the tuple form's preprocessing as it is, host syncs included."""
 import torch
 
 from . import device_ops, table_ops
-from .variable import (SparseTrainableWrapper, _check_combiner, _has_tiered_shards, _note_pruned, _per_table, _pooled_forward,
-                       _safe_sparse_args, _wrap_grouped)
+from .variable import (SparseTrainableWrapper, _admit_entries_many, _check_combiner, _check_entries_many, _note_pruned, _per_table,
+                       _pooled_forward, _pooled_reader, _safe_sparse_args, _wrap_grouped)
 from . import variable as _tuple_form
 
 
@@ -137,29 +137,39 @@ def _many(params_list, sp_ids_list, weights_list, combiner, default_id, safe, re
     _check_combiner(c)
   single = safe_embedding_lookup_sparse if safe else embedding_lookup_sparse
   results = [None] * n_t
-  groups = {}   # device -> [(i, row_splits, ids, w)]
+  groups, singles = {}, []   # device -> [(i, row_splits, ids, w)]; the members the pooled forward does not serve
   for i, params in enumerate(params_list):
-    if not _pooled_forward(params, None) or _has_tiered_shards(params):   # (a tier has no grouped descriptor: the single form)
-      kw = dict(default_id=default_ids[i]) if safe else {}
-      results[i] = single(params, sp_ids_list[i], weights[i], combiner=combiners[i], return_trainable=return_trainable,
-                          plan_writeback=plan_writeback, **kw)
+    if not _pooled_forward(params, None):
+      singles.append(i)
       continue
     groups.setdefault(params._primary, []).append((i,) + _ragged_input(params, sp_ids_list[i], weights[i]))
+  made, entry_ids = {}, {}   # i -> what the member's safe wrapper is built from; i -> the ids its wrapper will write back
+  if return_trainable:
+    # made ahead of the reads: a tiered member admits its entry ids first, and every tiered member's max_batch is checked before
+    # anything is admitted or read
+    for members in groups.values():
+      for i, rs, ids, w in members:
+        if safe:
+          made[i] = _safe_entries(params_list[i], rs, ids, w, combiners[i], default_ids[i], rs.numel() - 1)
+        entry_ids[i] = made[i][3][0] if safe else ids
+    _check_entries_many([(params_list[i], e) for i, e in entry_ids.items()])
+  for i in singles:
+    kw = dict(default_id=default_ids[i]) if safe else {}
+    results[i] = single(params_list[i], sp_ids_list[i], weights[i], combiner=combiners[i], return_trainable=return_trainable,
+                        plan_writeback=plan_writeback, **kw)
   for device, members in groups.items():
+    if return_trainable:
+      _admit_entries_many(params_list, {m[0]: entry_ids[m[0]] for m in members})   # (tiered members; ahead of the ONE read)
     reqs = []
     for i, rs, ids, w in members:
       t = params_list[i]._tables[0]
       prune, fill = _safe_flags(w, combiners[i], default_ids[i]) if safe else (False, None)
-      reqs.append((t._table, rs, ids, w, device_ops.COMBINERS[combiners[i]], prune, fill, t._default_value))
+      reqs.append((_pooled_reader(t), rs, ids, w, device_ops.COMBINERS[combiners[i]], prune, fill, t._default_value))
     outs = table_ops.find_combine_ragged_many(reqs)
     if not return_trainable:
       for (i, _, _, _), out in zip(members, outs):
         results[i] = out
       continue
-    made = {}   # i -> what the member's wrapper is built from
-    if safe:
-      for i, rs, ids, w in members:
-        made[i] = _safe_entries(params_list[i], rs, ids, w, combiners[i], default_ids[i], rs.numel() - 1)
 
     def wrapper(member, own_plan, entry_plan):
       i, rs, ids, w = member
@@ -167,8 +177,7 @@ def _many(params_list, sp_ids_list, weights_list, combiner, default_id, safe, re
       return (_safe_wrapper(params, made[i], combiners[i], n, own_plan, entry_plan, caller_weights=w) if safe else
               _plain_wrapper(params, rs, ids, w, combiners[i], n, own_plan, entry_plan))
 
-    _wrap_grouped(device, params_list, members, outs, {i: (made[i][3][0] if safe else ids) for i, _, ids, _ in members},
-                  plan_writeback, wrapper, results)
+    _wrap_grouped(device, params_list, members, outs, {m[0]: entry_ids[m[0]] for m in members}, plan_writeback, wrapper, results)
   return results
 
 
@@ -176,8 +185,9 @@ def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None,
                                  plan_writeback=False):
   """`embedding_lookup_sparse` of a LIST of variables: result i is what the single form returns for table i, bit for bit.
   `combiner` is a scalar or a per-table list.  The variables the pooled forward serves are read by ONE grouped call per device
-  (`table_ops.find_combine_ragged_many`: tfra_multi_find_combine_ragged — one upload and one launch per class, no bounds pass);
-  every other variable takes the single form, so no list is refused."""
+  (`table_ops.find_combine_ragged_many`: tfra_multi_find_combine_ragged — one upload and one launch per class, no bounds pass; with
+  a tiered variable among them tfra_multi_tier_find_combine_ragged, which reads that member in both tiers — with return_trainable
+  behind one admission of its entry ids per tiered member); every other variable takes the single form, so no list is refused."""
   return _many(params_list, sp_ids_list, sp_weights_list, combiner, None, False, return_trainable, plan_writeback)
 
 
@@ -185,6 +195,7 @@ def safe_embedding_lookup_sparse_many(params_list, sp_ids_list, sparse_weights_l
                                       return_trainable=False, plan_writeback=False):
   """`safe_embedding_lookup_sparse` of a LIST of variables: result i is what the single form returns for table i, bit for bit.
   `combiner` and `default_id` are scalars or per-table lists.  One grouped call per device for the variables the pooled forward
-  serves, with no host synchronisation in the forward; with return_trainable the wrappers' entry lists are made per table by
-  the tuple form's preprocessing (host syncs included)."""
+  serves (tiered ones included, as in `embedding_lookup_sparse_many`), with no host synchronisation in the forward; with
+  return_trainable the wrappers' entry lists are made per table by the tuple form's preprocessing (host syncs included), ahead of
+  the grouped call: they are what a tiered member admits."""
   return _many(params_list, sp_ids_list, sparse_weights_list, combiner, default_id, True, return_trainable, plan_writeback)

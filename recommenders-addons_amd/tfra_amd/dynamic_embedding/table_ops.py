@@ -1309,22 +1309,51 @@ class TieredHashTable(_LookupInterfaceMirror):
 
 
 def _device_table(x):
-  """`x` if it is a _DeviceTable, the device table of a CuckooHashTable / HkvHashTable (a TieredHashTable: its cache)."""
+  """`x` if it is a _DeviceTable, the device table of a CuckooHashTable / HkvHashTable (a TieredHashTable: its cache, which is what
+  a write-back acts on; a pooled READ of a tiered owner goes through `_device_tier`)."""
   return getattr(x, "_table", x)
+
+
+def _device_tier(x):
+  """The _DeviceTier behind a tiered owner of a pooled read — a TieredHashTable's driver, or `x` if it is a _DeviceTier —, else
+  None: the owner is one table (`_device_table`)."""
+  if isinstance(x, _DeviceTier):
+    return x
+  return x._tier if isinstance(x, TieredHashTable) else None
+
+
+def _owner_device(x):
+  """The device of a grouped call's owner: a tier's is its upper table's (both tables of a tier live on one device)."""
+  tier = _device_tier(x)
+  return tier._upper._device if tier is not None else _device_table(x)._device
+
+
+def _pooled_owner(e, owner, tiered):
+  """Sets the owner of a pooled descriptor `e` — `tiered`: of the tier ABI (`_capi.TierFindCombineDesc` / `...RaggedDesc`), which
+  names exactly one of table / tier — and returns the _DeviceTable that prepares the operands: the owner's device table, or a
+  tier's upper table."""
+  tier = _device_tier(owner)
+  table = tier._upper if tier is not None else _device_table(owner)
+  if tiered:
+    e.table, e.tier = (None, tier._h.value) if tier is not None else (table._h.value, None)
+  else:
+    e.table = table._h.value
+  return table
 
 
 def _grouped_call(c_name, desc_type, who, owners, fill):
   """The frame of the grouped calls (`find_combine_many`, `find_combine_ragged_many`, `apply_planned_combined_many`,
   `build_plans_many`): ONE C call `c_name(workspace, n, descs, &launches, stream)` over one descriptor of `desc_type` per entry of
   `owners`, on the current stream of the one device all of them live on.  An owner is a _DeviceTable, a CuckooHashTable /
-  HkvHashTable (whose device table is taken: `_device_table`) or a SparsePlan.  Member by member, the owner's device is compared
+  HkvHashTable (whose device table is taken: `_device_table`), a TieredHashTable / _DeviceTier (the pooled reads: `_device_tier`)
+  or a SparsePlan.  Member by member, the owner's device (`_owner_device`) is compared
   with the first one's (ValueError in the name of `who`), then `fill(descs[i], i)` checks the member's arguments and sets the
   descriptor's fields behind struct_size.  What `fill` returns — the tensors whose data_ptr() it stored — stays referenced here
   until the C call has returned.  Returns the number of kernel launches the call enqueued."""
   descs = (desc_type * len(owners))()
-  keep, device = [], _device_table(owners[0])._device
+  keep, device = [], _owner_device(owners[0])
   for i, owner in enumerate(owners):
-    dev = _device_table(owner)._device
+    dev = _owner_device(owner)
     if dev != device:
       raise ValueError("%s: all tables must live on one device (%s and %s)" % (who, device, dev))
     descs[i].struct_size = ctypes.sizeof(desc_type)
@@ -1340,24 +1369,30 @@ def find_combine_many(requests, return_launches=False):
   list of (table, ids, seg, weights, combiner, n_rows[, default_row]), the arguments behind `table` those of
   `_DeviceTable.find_combine`, handled the same way (int32 keys widened, the default row falling back to the table's).  Returns
   the [n_rows, dim] float32 results in the requests' order, each bit-identical to `find_combine` of its request (with
-  return_launches: also the number of kernel launches the call enqueued — it does not grow with the list)."""
+  return_launches: also the number of kernel launches the call enqueued — it does not grow with the list).
+  `table` may be a TieredHashTable or a _DeviceTier: its request is read in BOTH tiers, bit-identical to the tier's `find_combine`
+  (the operands prepared by the upper table).  A list with a tiered owner goes through tfra_multi_tier_find_combine as a whole,
+  plain tables included — still one call; a list without one takes the call, the descriptor and the launch counts it always took."""
   if not requests:
     return ([], 0) if return_launches else []
   outs = []
+  tiered = any(_device_tier(r[0]) is not None for r in requests)
 
   def fill(e, i):
     req = requests[i]
     table, ids, seg, weights, combiner, n_rows = req[:6]
     default_row = req[6] if len(req) > 6 else None
-    table = _device_table(table)
+    table = _pooled_owner(e, table, tiered)
     ids, seg, w, d, out = table._find_combine_args(ids, seg, weights, n_rows, default_row)
     outs.append(out)
-    e.combiner, e.table = int(combiner), table._h.value
+    e.combiner = int(combiner)
     e.nnz, e.ids, e.seg, e.weights = ids.numel(), ids.data_ptr(), seg.data_ptr(), (w.data_ptr() if w is not None else None)
     e.n_rows, e.default_row, e.out = int(n_rows), d.data_ptr(), out.data_ptr()
     return ids, seg, w, d
 
-  launches = _grouped_call("tfra_multi_find_combine", _capi.FindCombineDesc, "find_combine_many", [r[0] for r in requests], fill)
+  c_name, desc_type = (("tfra_multi_tier_find_combine", _capi.TierFindCombineDesc) if tiered else
+                       ("tfra_multi_find_combine", _capi.FindCombineDesc))
+  launches = _grouped_call(c_name, desc_type, "find_combine_many", [r[0] for r in requests], fill)
   return (outs, launches) if return_launches else outs
 
 
@@ -1367,10 +1402,13 @@ def find_combine_ragged_many(requests, return_launches=False):
   `table` those of `_DeviceTable.find_combine_ragged`, handled the same way.  A table may occur more than once.  Returns the
   [n_rows, dim] float32 results in the requests' order, each bit-identical to `find_combine_ragged` of its request (with
   return_launches: also the number of kernel launches the call enqueued: one per (value dtype, row-width class, safe-or-not)
-  class in the list)."""
+  class in the list).  `table` may be a TieredHashTable or a _DeviceTier, as in `find_combine_many`: the request is read in both
+  tiers, the fill id too, and the whole list goes through tfra_multi_tier_find_combine_ragged (one launch per (tiered or not,
+  value dtype, row-width class, safe-or-not) class); a list without a tiered owner takes the call it always took."""
   if not requests:
     return ([], 0) if return_launches else []
   outs = []
+  tiered = any(_device_tier(r[0]) is not None for r in requests)
 
   def fill(e, i):
     req = requests[i]
@@ -1378,18 +1416,19 @@ def find_combine_ragged_many(requests, return_launches=False):
     prune = req[5] if len(req) > 5 else False
     fill_id = req[6] if len(req) > 6 else None
     default_row = req[7] if len(req) > 7 else None
-    table = _device_table(table)
+    table = _pooled_owner(e, table, tiered)
     rs, ids, w, flags, fill_key, d, out = table._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row)
     outs.append(out)
-    e.combiner, e.table = int(combiner), table._h.value
+    e.combiner = int(combiner)
     e.n_rows, e.row_splits = rs.numel() - 1, rs.data_ptr()
     e.nnz, e.ids, e.weights = ids.numel(), ids.data_ptr(), (w.data_ptr() if w is not None else None)
     e.flags, e.reserved, e.fill_id = flags, 0, fill_key
     e.default_row, e.out = d.data_ptr(), out.data_ptr()
     return rs, ids, w, d
 
-  launches = _grouped_call("tfra_multi_find_combine_ragged", _capi.FindCombineRaggedDesc, "find_combine_ragged_many",
-                           [r[0] for r in requests], fill)
+  c_name, desc_type = (("tfra_multi_tier_find_combine_ragged", _capi.TierFindCombineRaggedDesc) if tiered else
+                       ("tfra_multi_find_combine_ragged", _capi.FindCombineRaggedDesc))
+  launches = _grouped_call(c_name, desc_type, "find_combine_ragged_many", [r[0] for r in requests], fill)
   return (outs, launches) if return_launches else outs
 
 

@@ -406,16 +406,24 @@ class Variable:
     up with its optimizer slots, a never-seen key enters as the write-back would have started it, so `apply_combined_gradients`
     only hits.  Nothing is read on the host.  A variable without tiered shards: nothing to do.  More entry ids than the tier's
     max_batch: ValueError."""
+    ids = self._admissible_entries(entry_ids)
+    if ids is not None and ids.numel():
+      t = self._tables[0]
+      uniq, _, cnt = device_ops.unique_no_sync(ids)
+      t.admit(uniq, t._default_value, count=cnt)
+
+  def _admissible_entries(self, entry_ids):
+    """`admit_entries`' check, with nothing enqueued: the flat entry ids on the tiered shard's device (None: no tiered shards), or
+    its ValueError for more entry ids than the tier's max_batch.  The grouped forms run it for ALL their tiered members before the
+    first admission (`_check_entries_many`)."""
     if not _has_tiered_shards(self):
-      return
+      return None
     t = self._tables[0]
     ids = torch.as_tensor(entry_ids, device=t._device).reshape(-1)
     if ids.numel() > t._tier.max_batch:
       raise ValueError("a pooled training lookup over a tiered variable admits its entry ids in one call: %d entry ids exceed the "
                        "tier's max_batch (%d)" % (ids.numel(), t._tier.max_batch))
-    if ids.numel():
-      uniq, _, cnt = device_ops.unique_no_sync(ids)
-      t.admit(uniq, t._default_value, count=cnt)
+    return ids
 
   def _combined_operands(self, ids, ragged):
     """-> (the one shard, the flat ids on its device) of a pooled read — the forward or the weight gradient, over one table or a
@@ -1052,6 +1060,23 @@ def _rows_in_one_read(rows, unknown):
       rows[i] = int(top) + 1
 
 
+def _check_entries_many(members):
+  """At the head of a grouped training lookup, for its pooled `members` [(variable, entry ids)]: the max_batch ValueError of
+  `Variable.admit_entries` for ALL tiered members before the first admission is enqueued — a refused list has admitted and read
+  nothing."""
+  for params, entry_ids in members:
+    params._admissible_entries(entry_ids)
+
+
+def _admit_entries_many(params_list, entry_ids):
+  """Ahead of the ONE grouped read of a training step: `Variable.admit_entries(entry_ids[i])` for every member i of `entry_ids`
+  (index -> the entry ids its wrapper will write back; a member without tiered shards: nothing).  Admission moves rows between
+  the tiers and never changes them, so the one read behind all admissions returns what a read behind each would.  N tiered
+  members are still N admission chains: the read is what the grouped call collapses."""
+  for i, ids in entry_ids.items():
+    params_list[i].admit_entries(ids)
+
+
 def _wrap_grouped(device, params_list, members, outs, entry_ids, plan_writeback, wrapper, results):
   """results[i] = (out, SparseTrainableWrapper) behind a grouped forward, for the members (i, ...) of `device` and their `outs`.
   The members' write-back plans over entry_ids[i]: one grouped build on one side stream (None: at most one member takes a plan,
@@ -1068,8 +1093,10 @@ def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None,
   `embedding_lookup_sparse(params_list[i], sp_ids_list[i], sp_weights_list[i], ...)` returns, bit for bit — with return_trainable
   the (result, SparseTrainableWrapper) pair, the wrapper built behind the pooled forward.  `combiner` and `num_rows` are scalars
   or per-table lists.  The variables the pooled forward serves (`_pooled_forward`) are read by ONE grouped call per device
-  (`table_ops.find_combine_many`: tfra_multi_find_combine, whose launch count does not grow with the list); every other variable
-  — a tiered one among them: its pooled read takes both tiers' views, which the grouped call's descriptors do not carry —
+  (`table_ops.find_combine_many`: tfra_multi_find_combine, whose launch count does not grow with the list) — a tiered variable
+  among them: it joins its device's group with the shard itself as owner (`_pooled_reader`), the group then goes through
+  tfra_multi_tier_find_combine and the member is read in both tiers; with return_trainable its entry ids are admitted into the
+  cache first (`_admit_entries_many`: one admission per tiered member, then the one read) —; every other variable
   takes `embedding_lookup_sparse` as it is, so no list is refused.  With return_trainable and plan_writeback the grouped members
   that a single lookup would give a plan (`_plan_at_lookup`'s rule, per variable) get theirs from ONE grouped build per device on
   one side stream (`_plans_at_lookup_many`: tfra_multi_sparse_plan_build).  Where num_rows is absent, the grouped variables' row counts
@@ -1085,9 +1112,12 @@ def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None,
   for c in combiners:
     _check_combiner(c)
   results = [None] * n_t
+  if return_trainable:
+    _check_entries_many([(p, entries[i][0] if entries[i] is not None else sp_ids_list[i][1])
+                         for i, p in enumerate(params_list) if _pooled_forward(p, max_norm)])
   groups = {}   # device -> [(i, ids, seg, w)]
   for i, params in enumerate(params_list):
-    if not _pooled_forward(params, max_norm) or _has_tiered_shards(params):   # (a tier has no grouped descriptor: the single form)
+    if not _pooled_forward(params, max_norm):
       results[i] = embedding_lookup_sparse(params, sp_ids_list[i], weights[i], combiner=combiners[i], max_norm=max_norm,
                                            return_trainable=return_trainable, num_rows=rows[i], plan_writeback=plan_writeback,
                                            _entries=entries[i], _out_shape=shapes[i])
@@ -1100,17 +1130,19 @@ def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None,
     groups.setdefault(params._primary, []).append((i, ids, seg, w))
   for device, members in groups.items():
     _rows_in_one_read(rows, [(m[0], m[2]) for m in members if rows[m[0]] is None])
+    if return_trainable:
+      ent = {i: (entries[i] if entries[i] is not None else (ids.reshape(-1), seg, w))   # ids keep their key dtype
+             for i, ids, seg, w in members}
+      _admit_entries_many(params_list, {i: e[0] for i, e in ent.items()})   # (tiered members; ahead of the ONE read)
     reqs = []
     for i, ids, seg, w in members:
       t = params_list[i]._tables[0]
-      reqs.append((t._table, ids.reshape(-1), seg, w, device_ops.COMBINERS[combiners[i]], rows[i], t._default_value))
+      reqs.append((_pooled_reader(t), ids.reshape(-1), seg, w, device_ops.COMBINERS[combiners[i]], rows[i], t._default_value))
     outs = table_ops.find_combine_many(reqs)
     if not return_trainable:
       for (i, ids, seg, w), out in zip(members, outs):
         results[i] = out
       continue
-    ent = {i: (entries[i] if entries[i] is not None else (ids.reshape(-1), seg, w))   # ids keep their key dtype
-           for i, ids, seg, w in members}
 
     def wrapper(member, own_plan, entry_plan):
       i, ids, seg, w = member

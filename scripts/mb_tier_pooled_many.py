@@ -1,0 +1,172 @@
+"""The pooled forward of a many-table model whose tables are TIERED, two ways, in ONE process on one MI355X:
+  (a) the loop of tier.find_combine / find_combine_ragged (tfra_tier_find_combine[_ragged]), one call per tier — the route before
+      the grouped call took tiers;
+  (b) ONE table_ops.find_combine_many / find_combine_ragged_many over the same requests (tfra_multi_tier_find_combine[_ragged]).
+--tiers (26) float32 tiers, dims cycling 16 / 32 / 64 / 128: an upper LRU table of --slots slots at max_capacity, given
+--slots * 5 / 4 keys (the highest indices first, so it keeps the low ones), over a lower table of --lower keys that holds every
+key.  Per tier a batch of 8 192 rows x 4 Zipf-1.2 ids, combiner mean, no weights; of its entries 0 % or 10 % are drawn from keys
+the upper table was never given, the others from the low indices it kept.  The share of ENTRIES that is really only below is
+taken from tfra_tier_find's `where` and recorded (`below_pct`), not assumed.  Each form runs on tiers of its OWN (two sets,
+filled alike); the forms' windows ALTERNATE: a, b, a, b, ...  Points, each at both mixes:
+  tuple     26 tiers, the tuple form
+  ragged    26 tiers, the ragged form
+  mixed     13 tiers + 13 plain tables (the lower tables of the other 13 tiers, named directly) in one call, against
+            tfra_multi_find_combine for the plain half plus the tier loop
+  one       one tier (dim 64) alone in the list: what the grouping costs where it cannot help
+HIP events around windows of --steps steps, --windows windows per form after --warmup steps; one JSON line per point and mix
+(median, min and max of the windows in us per step, host calls included; (a) - (b) against the sum of both spreads), written to
+--out, and the table of DESIGN §4.23 on stdout.
+   python scripts/mb_tier_pooled_many.py [--tiers 26] [--slots 65534] [--lower 262144] [--steps 20] [--windows 5] [--warmup 5]
+                                         [--out profiles/tier_pooled_many_mb.jsonl]"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "recommenders-addons_amd"))
+
+N_ROWS, PER_ROW = 8192, 4
+NNZ = N_ROWS * PER_ROW
+DIMS = (16, 32, 64, 128)
+MIXES = (0, 10)
+CHUNK = 1 << 18
+
+
+def window(f, n):
+  e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+  torch.cuda.synchronize()
+  e0.record()
+  for _ in range(n):
+    f()
+  e1.record()
+  e1.synchronize()
+  return e0.elapsed_time(e1) * 1000.0 / n
+
+
+def stats(us):
+  return {"median": round(float(np.median(us)), 1), "min": round(min(us), 1), "max": round(max(us), 1), "windows": [round(x, 1) for x in us]}
+
+
+def key_of(i):
+  return i * 2654435761 + 1
+
+
+def main():
+  ap = argparse.ArgumentParser()
+  ap.add_argument("--tiers", type=int, default=26)
+  ap.add_argument("--slots", type=int, default=65534)
+  ap.add_argument("--lower", type=int, default=262144)
+  ap.add_argument("--steps", type=int, default=20)
+  ap.add_argument("--windows", type=int, default=5)
+  ap.add_argument("--warmup", type=int, default=5)
+  ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tier_pooled_many_mb.jsonl"))
+  a = ap.parse_args()
+  if not torch.cuda.is_available():
+    raise SystemExit("mb_tier_pooled_many: no GPU visible; this is a measurement, it has no CPU form")
+  from tfra_amd.dynamic_embedding import table_ops
+  from tfra_amd.dynamic_embedding.table_ops import _DeviceTable, _DeviceTier
+
+  n_up = a.slots + a.slots // 4
+  sets = {}
+  for form in "ab":                                   # each form reads tiers of its own, filled alike
+    tiers = []
+    for j in range(a.tiers):
+      dim = DIMS[j % 4]
+      up = _DeviceTable(torch.int64, torch.float32, torch.zeros(dim), "mb_tpm_%s_up%d" % (form, j), "cuda:0", dim=dim,
+                        init_capacity=a.slots, max_capacity=a.slots, strategy=0)
+      lo = _DeviceTable(torch.int64, torch.float32, torch.zeros(dim), "mb_tpm_%s_lo%d" % (form, j), "cuda:0", dim=dim,
+                        init_capacity=2 * a.lower)
+      for t, n in ((lo, a.lower), (up, n_up)):        # the upper table forgets some of the high indices, the low ones are its newest
+        for s in range(0, n, CHUNK):
+          i = torch.arange(s, min(s + CHUNK, n), dtype=torch.int64, device="cuda")
+          k = key_of(i if t is lo else n_up - 1 - i)
+          t.upsert(k, (k % 1000).to(torch.float32)[:, None].expand(-1, dim).contiguous(), unique_keys=True)
+        t.check_errors()
+      tiers.append(_DeviceTier(up, lo, NNZ))
+    sets[form] = tiers
+  seg = torch.arange(NNZ, dtype=torch.int64, device="cuda") // PER_ROW
+  splits = torch.arange(0, NNZ + 1, PER_ROW, dtype=torch.int64, device="cuda")
+  rng = np.random.default_rng(7)
+  half = a.tiers // 2
+  one = 2 % a.tiers                                   # a dim-64 tier
+  lines, table = [], []
+  for mix in MIXES:
+    ids, below = [], []
+    for j in range(a.tiers):
+      rank = rng.zipf(1.2, size=NNZ).astype(np.int64) - 1
+      cold = rng.random(NNZ) < mix / 100.0
+      # the hot keys: the low indices BOTH sets' upper tables really kept (a full bucket drops a key or two even of its newest)
+      low = key_of(torch.arange(a.slots // 2, dtype=torch.int64, device="cuda"))
+      kept = torch.nonzero(sets["a"][j]._upper.contains(low) & sets["b"][j]._upper.contains(low)).reshape(-1).cpu().numpy()
+      index = np.where(cold, n_up + rank % (a.lower - n_up), kept[rank % kept.size])
+      ids.append(key_of(torch.from_numpy(index).cuda()))
+      default_row = torch.zeros(DIMS[j % 4], device="cuda")
+      for form in "ab":
+        where = sets[form][j].find(ids[j], default_row, return_where=True)[1]
+        assert int((where == 0).sum()) == 0
+        below.append(100.0 * float((where == 2).sum()) / NNZ)
+    below_pct = [round(min(below), 2), round(float(np.mean(below)), 2), round(max(below), 2)]
+
+    def tup(owner, j):
+      return (owner, ids[j], seg, None, 1, N_ROWS)
+
+    def rag(owner, j):
+      return (owner, splits, ids[j], None, 1)
+
+    A, B = sets["a"], sets["b"]
+    points = {
+        "tuple": (lambda: [A[j].find_combine(ids[j], seg, None, 1, N_ROWS) for j in range(a.tiers)],
+                  lambda: table_ops.find_combine_many([tup(B[j], j) for j in range(a.tiers)]), a.tiers, 0),
+        "ragged": (lambda: [A[j].find_combine_ragged(splits, ids[j], None, 1) for j in range(a.tiers)],
+                   lambda: table_ops.find_combine_ragged_many([rag(B[j], j) for j in range(a.tiers)]), a.tiers, 0),
+        "mixed": (lambda: ([A[j].find_combine(ids[j], seg, None, 1, N_ROWS) for j in range(half)] +
+                           table_ops.find_combine_many([tup(A[j]._lower, j) for j in range(half, a.tiers)])),
+                  lambda: table_ops.find_combine_many([tup(B[j], j) for j in range(half)] + [tup(B[j]._lower, j) for j in range(half, a.tiers)]),
+                  half, a.tiers - half),
+        "one": (lambda: [A[one].find_combine(ids[one], seg, None, 1, N_ROWS)],
+                lambda: table_ops.find_combine_many([tup(B[one], one)]), 1, 0),
+    }
+    for name, (fa, fb, n_tiers, n_plain) in points.items():
+      run = {"a": fa, "b": fb}
+      for x, y in zip(fa(), fb()):
+        assert torch.equal(x.view(torch.int32), y.view(torch.int32)), "(a) and (b) differ at " + name
+      us = {n: [] for n in run}
+      for f in run.values():
+        for _ in range(a.warmup):
+          f()
+      for _ in range(a.windows):
+        for n, f in run.items():
+          us[n].append(window(f, a.steps))
+      for t in A + B:
+        t._upper.check_errors()
+        t._lower.check_errors()
+      out = {"what": "tier_pooled_many", "point": name, "tiers": n_tiers, "plain_tables": n_plain, "dims": list(DIMS), "dtype": "float32",
+             "n_rows": N_ROWS, "per_row": PER_ROW, "nnz_per_table": NNZ, "combiner": "mean", "zipf": 1.2, "cold_pct": mix,
+             "below_pct_min_mean_max": below_pct, "upper_slots": a.slots, "upper_given_keys": n_up, "lower_keys": a.lower,
+             "steps": a.steps, "windows": a.windows, "warmup": a.warmup, "order": "windows alternate a, b; each form on tiers of its own"}
+      for n in run:
+        out[n + "_us"] = stats(us[n])
+        out[n + "_spread_us"] = round(out[n + "_us"]["max"] - out[n + "_us"]["min"], 1)
+      out["a_minus_b_us"] = round(out["a_us"]["median"] - out["b_us"]["median"], 1)
+      out["sum_of_spreads_us"] = round(out["a_spread_us"] + out["b_spread_us"], 1)
+      out["b_below_a_by_more_than_both_spreads"] = out["a_minus_b_us"] > out["sum_of_spreads_us"]
+      print(json.dumps(out), flush=True)
+      lines.append(json.dumps(out))
+      fmt = lambda s: "%.1f [%.1f - %.1f]" % (s["median"], s["min"], s["max"])
+      table.append("| %s | %d + %d | %d %% (%.1f %%) | %s | %s | %.1f | %.1f | %s |" % (
+          name, n_tiers, n_plain, mix, below_pct[1], fmt(out["a_us"]), fmt(out["b_us"]), out["a_minus_b_us"], out["sum_of_spreads_us"],
+          "yes" if out["b_below_a_by_more_than_both_spreads"] else "no"))
+  os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+  with open(a.out, "w") as fh:
+    fh.write("\n".join(lines) + "\n")
+  print("| point | tiers + plain | cold (entries only below) | (a) loop, us | (b) grouped, us | (a) - (b) | sum of spreads | beyond it |")
+  print("|---|---|---|---|---|---|---|---|")
+  print("\n".join(table))
+
+
+if __name__ == "__main__":
+  main()
