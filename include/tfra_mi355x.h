@@ -994,6 +994,61 @@ int tfra_table_find_combine_ragged_backprop_weights(tfra_table_t* t, size_t n_ro
                                                     int64_t fill_id, const void* default_row, const float* grad_out,
                                                     float* dw_out, tfra_stream_t stream);
 
+/* The weight gradients of MANY pooled lookups in one call (a model with 26 weighted sparse features asks for 26 of them per step:
+ * ~100 enqueues for 26 small kernels otherwise).  A descriptor names exactly ONE of table / tier, as tfra_tier_find_combine_desc
+ * does; descs[i].dw_out is bit-identical to the single call on that descriptor — the same device function runs:
+ * tfra_table_find_combine[_ragged]_backprop_weights for a table, tfra_tier_find_combine[_ragged]_backprop_weights for a tier
+ * (upper wins, else lower, else default_row).  Every rule of the single calls holds per descriptor, with their codes and wording,
+ * checked on the table or on the tier's upper table: an entry in no row (tuple form) or outside the clamped cover of row_splits
+ * (ragged form) gets 0; PRUNE applies only with weights, FILL changes nothing and fill_id is not looked at.
+ * nnz == 0: nothing is written for the descriptor.  n_rows == 0 (nnz > 0): its dw_out is zero-filled.  n_tables == 0: TFRA_OK.
+ * All descriptors are checked BEFORE anything is enqueued: if one fails, the call returns the single call's code, the message is
+ * "multi_find_combine[_ragged]_backprop_weights: descriptor <i>: ..." and no dw_out of any descriptor is written.  Both of
+ * table / tier set, neither of them set, a wrong struct_size, a non-zero `reserved`, a table on another device than ws, or
+ * descs == NULL with n_tables > 0: TFRA_ERR_INVALID.
+ * These calls are READS: no table is written, no score is touched, nothing moves between tiers, tfra_tier_stats does not change,
+ * no tier's staging is used and nnz is not limited by max_batch.  So the same table or tier may stand in several descriptors, and
+ * a table may be named directly in one descriptor while it is the upper or lower table of a tier in another.  The dw_out ranges
+ * of different descriptors must NOT overlap (not checked: the descriptors' rows run side by side in one launch).
+ * Locks and storage as in tfra_multi_tier_find_combine: each distinct tier's mutex once, in address order, then every distinct
+ * table once in the global order; the views are taken under the locks.
+ * Enqueues, whatever n_tables: one upload of the records (the workspace's ring of pinned slots); the tuple form one memset of all
+ * rows' bounds; then ONE launch that zero-fills every dw_out (a descriptor owns ceil(nnz / 256) blocks of it) — in the tuple form
+ * the same launch writes all rows' bounds —; then one gradient launch per (tiered or not, value dtype, NCH) class in the list, at
+ * most 18; the ragged form per (tiered or not, value dtype, NCH, pruning or not) class, at most 36 — pruning: TFRA_RAGGED_PRUNE
+ * with weights.
+ * *launches_out (optional, host): the kernel launches enqueued =
+ *     (1 if any descriptor has nnz > 0, else 0) + (the distinct classes among the descriptors with nnz > 0 and n_rows > 0).
+ * Not for stream capture.                                                                  (tests/test_gpu_wgrad_many.py) */
+typedef struct {
+  uint32_t struct_size;      /* = sizeof(tfra_find_combine_wgrad_desc) */
+  int32_t  combiner;         /* 0 sum | 1 mean | 2 sqrtn */
+  tfra_table_t* table;       /* exactly ONE of table / tier is non-NULL */
+  tfra_tier_t*  tier;
+  size_t nnz; const int64_t* ids; const int64_t* seg; const float* weights;   /* weights may be NULL */
+  size_t n_rows; const void* default_row;
+  const float* grad_out;     /* [n_rows, dim] float32, 16-byte aligned */
+  float* dw_out;             /* [nnz] float32 */
+} tfra_find_combine_wgrad_desc;
+int tfra_multi_find_combine_backprop_weights(tfra_workspace_t* ws, size_t n_tables, const tfra_find_combine_wgrad_desc* descs,
+                                             uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
+
+typedef struct {
+  uint32_t struct_size;      /* = sizeof(tfra_find_combine_ragged_wgrad_desc) */
+  int32_t  combiner;         /* 0 sum | 1 mean | 2 sqrtn */
+  tfra_table_t* table;       /* exactly ONE of table / tier is non-NULL */
+  tfra_tier_t*  tier;
+  size_t n_rows; const int64_t* row_splits;                                   /* [n_rows + 1] */
+  size_t nnz; const int64_t* ids; const float* weights;                       /* weights may be NULL */
+  uint32_t flags; uint32_t reserved;                                          /* TFRA_RAGGED_*; reserved = 0 */
+  int64_t fill_id; const void* default_row;                                   /* fill_id is ignored */
+  const float* grad_out;     /* [n_rows, dim] float32, 16-byte aligned */
+  float* dw_out;             /* [nnz] float32 */
+} tfra_find_combine_ragged_wgrad_desc;
+int tfra_multi_find_combine_ragged_backprop_weights(tfra_workspace_t* ws, size_t n_tables,
+                                                    const tfra_find_combine_ragged_wgrad_desc* descs,
+                                                    uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
+
 /* The combined write-backs of MANY tables in one call (a 26-table model's backward is 26 tfra_table_apply_planned_combined calls =
  * ~160 enqueues otherwise): table i ends bit-identical to tfra_table_apply_planned_combined(table, opt, plan, grad_out, seg,
  * weights, combiner, n_rows, param_default_row, stream) — the same device code runs — and every rule of that call holds per

@@ -1,4 +1,4 @@
-// What the pooled lookup (tfra_pool.hip; over a tier: tfra_tierpool.hip) and the gradient of its weights (tfra_wgrad.hip; over a tier: tfra_tierwgrad.hip) share, ONE copy each: the up-cast of a
+// What the pooled lookup (tfra_pool.hip; over a tier: tfra_tierpool.hip) and the gradient of its weights (tfra_wgrad.hip; over a tier: tfra_tierwgrad.hip; over a list: tfra_wgrad_many.hip) share, ONE copy each: the up-cast of a
 // stored row (PoolRow), the launch ladders by value dtype and row width (with_pool_class, with_ragged_class) and the argument checks
 // of the tuple and the ragged call (check_find_combine, check_find_combine_ragged; check_dw_out for the gradient's output).
 #pragma once

@@ -2,13 +2,22 @@
 // tfra_multi_tier_find_combine / _ragged: tfra_tierpool_many.hip): the records of their launches, the launchers that
 // cross the units (each kernel is instantiated in ONE unit) and the host frame of each form, written once over a descriptor of
 // either ABI (PoolDesc) — check every descriptor, classify, lock, lay out, fill, send, launch (tfra_many.h).
+// The grouped weight gradients (tfra_multi_find_combine[_ragged]_backprop_weights: tfra_wgrad_many.hip) read the same
+// descriptor and take the same steps: what a frame needs for them — a descriptor's owner, its class, the records' order, the
+// locks — is at the end of this file, ONE copy for the three units.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <mutex>
+#include <string>
+#include <vector>
 
 #include "../../include/tfra_mi355x.h"
 #include "tfra_device.h"
 #include "tfra_host.h"
 #include "tfra_many.h"
+#include "tfra_pool.h"
 #include "tfra_tier.h"
 
 namespace tfra {
@@ -62,8 +71,9 @@ TFRA_HIDDEN void launch_tier_find_combine_many(hipStream_t s, int cls, unsigned 
 TFRA_HIDDEN void launch_tier_find_combine_ragged_many(hipStream_t s, int cls, bool safe, unsigned grid, const TierRaggedRec* recs,
                                                       const unsigned* prefix, unsigned n);
 
-// ---- a descriptor of any of the four calls, as the frames read it: exactly one of table / tier for the tier ABI, the table alone
-// for the one-table ABI (tier_abi false: `tier` is not looked at and a NULL table is the single call's "null table").
+// ---- a descriptor of any of the grouped pooled calls, as the frames read it: exactly one of table / tier for the tier ABI (the
+// weight gradients' too), the table alone for the one-table ABI (tier_abi false: `tier` is not looked at and a NULL table is the
+// single call's "null table").
 struct PoolDesc {
   bool size_ok;              // struct_size is the ABI's
   bool tier_abi;
@@ -79,7 +89,9 @@ struct PoolDesc {
   uint32_t flags, reserved;  // ragged form
   int64_t fill_id;           // ragged form
   const void* default_row;
-  float* out;
+  float* out;                // the lookups
+  const float* grad_out;     // the weight gradients: grad_out in the place of out, and dw_out
+  float* dw_out;
 };
 typedef PoolDesc (*PoolDescAt)(const void* descs, size_t i);
 
@@ -88,5 +100,66 @@ TFRA_HIDDEN int multi_find_combine_frame(const char* who, tfra_workspace* ws, si
                                          uint32_t* launches_out, hipStream_t s);
 TFRA_HIDDEN int multi_find_combine_ragged_frame(const char* who, tfra_workspace* ws, size_t n_tables, const void* descs, PoolDescAt at,
                                                 uint32_t* launches_out, hipStream_t s);
+
+namespace {
+
+// ---- what the frames share (host code, hidden: an anonymous namespace, as tfra_pool.h's checks) ------------------------------------
+// The table a descriptor's checks run on: its table, or its tier's upper table (tfra_tier_create has made sure that both tables of a
+// tier have its value dtype, dim and device).  What only a descriptor can get wrong is refused here, before the operation's checks.
+int desc_owner(const PoolDesc& d, Table** t, const char** why) {
+  if (!d.size_ok) { *why = "descriptor size mismatch"; return TFRA_ERR_INVALID; }
+  if (d.tier_abi && (d.table != nullptr) == (d.tier != nullptr)) {
+    *why = "exactly one of table / tier must be set";
+    return TFRA_ERR_INVALID;
+  }
+  *t = d.tier ? d.tier->upper : d.table;
+  return TFRA_OK;
+}
+int pool_class(const Table* t) { return st_index(t->opts.value_dtype) * 3 + nch_index(t->opts.dim); }
+unsigned row_blocks(const PoolDesc& d) { return (unsigned)((d.n_rows * 16 + 255) / 256); }
+
+// The records' order: class by class, input order inside a class; first[c] is where class c starts, first[n_class] the number of
+// active descriptors.  The classes of plain tables come first: they are the one-table call's, in its order.
+int order_by_class(const std::string& who, const std::vector<PoolDesc>& ds, const std::vector<int>& cls, int n_class,
+                   std::vector<size_t>* order, size_t* first) {
+  for (int c = 0; c < n_class; ++c) {
+    first[c] = order->size();
+    u64 blocks = 0;
+    for (size_t i = 0; i < ds.size(); ++i)
+      if (cls[i] == c) { order->push_back(i); blocks += row_blocks(ds[i]); }
+    if (blocks >= (1ULL << 31)) return set_error(TFRA_ERR_UNSUPPORTED, who + ": too many rows in one call");
+  }
+  first[n_class] = order->size();
+  return TFRA_OK;
+}
+
+// The locks of a call: each distinct tier's own mutex once, in address order, BEFORE any table lock — the hierarchy of the single
+// tier calls (tier_enter) — then every table of the call (plain ones, uppers and lowers: a table may be named directly in one
+// descriptor and stand in a tier of another) once, in the global order, entered on s.  (Members are released in reverse order.)
+struct PoolLocks {
+  std::vector<std::unique_lock<std::mutex>> tiers, tables;
+};
+int lock_owners(const std::vector<PoolDesc>& ds, const std::vector<size_t>& order, hipStream_t s, PoolLocks* l) {
+  std::vector<tfra_tier*> tiers;
+  std::vector<Table*> tabs;
+  tabs.reserve(2 * order.size());
+  for (size_t i : order) {
+    const PoolDesc& d = ds[i];
+    if (d.tier) {
+      tiers.push_back(d.tier);
+      tabs.push_back(d.tier->upper);
+      tabs.push_back(d.tier->lower);
+    } else {
+      tabs.push_back(d.table);
+    }
+  }
+  std::sort(tiers.begin(), tiers.end(), std::less<tfra_tier*>());
+  tiers.erase(std::unique(tiers.begin(), tiers.end()), tiers.end());
+  l->tiers.reserve(tiers.size());
+  for (tfra_tier* t : tiers) l->tiers.emplace_back(t->mu);
+  return lock_and_enter(std::move(tabs), s, &l->tables);
+}
+
+}  // namespace
 
 }  // namespace tfra

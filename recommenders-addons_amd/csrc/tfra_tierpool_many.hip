@@ -56,63 +56,6 @@ __global__ __launch_bounds__(256) void tier_find_combine_ragged_many_kernel(cons
                                                  RaggedArgs{rec.row_splits, rec.nnz, rec.flags, rec.fill_id}, &lo);
 }
 
-// ---- what the two frames share ---------------------------------------------------------------------------------------------------
-// The table a descriptor's checks run on: its table, or its tier's upper table (tfra_tier_create has made sure that both tables of a
-// tier have its value dtype, dim and device).  What only a descriptor can get wrong is refused here, before the operation's checks.
-int desc_owner(const PoolDesc& d, Table** t, const char** why) {
-  if (!d.size_ok) { *why = "descriptor size mismatch"; return TFRA_ERR_INVALID; }
-  if (d.tier_abi && (d.table != nullptr) == (d.tier != nullptr)) {
-    *why = "exactly one of table / tier must be set";
-    return TFRA_ERR_INVALID;
-  }
-  *t = d.tier ? d.tier->upper : d.table;
-  return TFRA_OK;
-}
-int pool_class(const Table* t) { return st_index(t->opts.value_dtype) * 3 + nch_index(t->opts.dim); }
-unsigned row_blocks(const PoolDesc& d) { return (unsigned)((d.n_rows * 16 + 255) / 256); }
-
-// The records' order: class by class, input order inside a class; first[c] is where class c starts, first[n_class] the number of
-// active descriptors.  The classes of plain tables come first: they are the one-table call's, in its order.
-int order_by_class(const std::string& who, const std::vector<PoolDesc>& ds, const std::vector<int>& cls, int n_class,
-                   std::vector<size_t>* order, size_t* first) {
-  for (int c = 0; c < n_class; ++c) {
-    first[c] = order->size();
-    u64 blocks = 0;
-    for (size_t i = 0; i < ds.size(); ++i)
-      if (cls[i] == c) { order->push_back(i); blocks += row_blocks(ds[i]); }
-    if (blocks >= (1ULL << 31)) return set_error(TFRA_ERR_UNSUPPORTED, who + ": too many rows in one call");
-  }
-  first[n_class] = order->size();
-  return TFRA_OK;
-}
-
-// The locks of a call: each distinct tier's own mutex once, in address order, BEFORE any table lock — the hierarchy of the single
-// tier calls (tier_enter) — then every table of the call (plain ones, uppers and lowers: a table may be named directly in one
-// descriptor and stand in a tier of another) once, in the global order, entered on s.  (Members are released in reverse order.)
-struct PoolLocks {
-  std::vector<std::unique_lock<std::mutex>> tiers, tables;
-};
-int lock_owners(const std::vector<PoolDesc>& ds, const std::vector<size_t>& order, hipStream_t s, PoolLocks* l) {
-  std::vector<tfra_tier*> tiers;
-  std::vector<Table*> tabs;
-  tabs.reserve(2 * order.size());
-  for (size_t i : order) {
-    const PoolDesc& d = ds[i];
-    if (d.tier) {
-      tiers.push_back(d.tier);
-      tabs.push_back(d.tier->upper);
-      tabs.push_back(d.tier->lower);
-    } else {
-      tabs.push_back(d.table);
-    }
-  }
-  std::sort(tiers.begin(), tiers.end(), std::less<tfra_tier*>());
-  tiers.erase(std::unique(tiers.begin(), tiers.end()), tiers.end());
-  l->tiers.reserve(tiers.size());
-  for (tfra_tier* t : tiers) l->tiers.emplace_back(t->mu);
-  return lock_and_enter(std::move(tabs), s, &l->tables);
-}
-
 }  // namespace
 
 namespace tfra {

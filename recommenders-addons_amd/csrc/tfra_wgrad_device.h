@@ -1,6 +1,7 @@
 // The body of the pooled lookup's weight gradient, ONE copy for its kernels: wgrad_kernel and wgrad_ragged_kernel (tfra_wgrad.hip)
 // read one table; tier_wgrad_kernel and tier_wgrad_ragged_kernel (tfra_tierwgrad.hip) read the two tables of a tier through the
-// same function (its TIER axis, find_combine_row's: tfra_pool_device.h).
+// same function (its TIER axis, find_combine_row's: tfra_pool_device.h); the grouped kernels (tfra_wgrad_many.hip) call it per
+// descriptor of a list.
 #pragma once
 #include <hip/hip_runtime.h>
 

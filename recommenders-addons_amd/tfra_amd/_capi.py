@@ -116,6 +116,27 @@ class TierFindCombineRaggedDesc(ctypes.Structure):
   ]
 
 
+class FindCombineWgradDesc(ctypes.Structure):
+  """tfra_find_combine_wgrad_desc (include/tfra_mi355x.h): the weight gradient of one tier's or one table's pooled lookup in
+  tfra_multi_find_combine_backprop_weights; exactly one of table / tier is set."""
+  _fields_ = [
+      ("struct_size", ctypes.c_uint32), ("combiner", ctypes.c_int32), ("table", ctypes.c_void_p), ("tier", ctypes.c_void_p),
+      ("nnz", ctypes.c_size_t), ("ids", ctypes.c_void_p), ("seg", ctypes.c_void_p), ("weights", ctypes.c_void_p),
+      ("n_rows", ctypes.c_size_t), ("default_row", ctypes.c_void_p), ("grad_out", ctypes.c_void_p), ("dw_out", ctypes.c_void_p),
+  ]
+
+
+class FindCombineRaggedWgradDesc(ctypes.Structure):
+  """tfra_find_combine_ragged_wgrad_desc (include/tfra_mi355x.h): the weight gradient of one tier's or one table's ragged pooled
+  lookup in tfra_multi_find_combine_ragged_backprop_weights; exactly one of table / tier is set."""
+  _fields_ = [
+      ("struct_size", ctypes.c_uint32), ("combiner", ctypes.c_int32), ("table", ctypes.c_void_p), ("tier", ctypes.c_void_p),
+      ("n_rows", ctypes.c_size_t), ("row_splits", ctypes.c_void_p), ("nnz", ctypes.c_size_t), ("ids", ctypes.c_void_p),
+      ("weights", ctypes.c_void_p), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("fill_id", ctypes.c_int64),
+      ("default_row", ctypes.c_void_p), ("grad_out", ctypes.c_void_p), ("dw_out", ctypes.c_void_p),
+  ]
+
+
 class ApplyCombinedDesc(ctypes.Structure):
   """tfra_apply_combined_desc (include/tfra_mi355x.h): one table's combined write-back in tfra_multi_apply_planned_combined."""
   _fields_ = [
@@ -239,6 +260,8 @@ _SIGS = {
     "tfra_multi_find_combine_ragged": [_P, _SZ, _P, _P, _P],
     "tfra_multi_tier_find_combine": [_P, _SZ, _P, _P, _P],
     "tfra_multi_tier_find_combine_ragged": [_P, _SZ, _P, _P, _P],
+    "tfra_multi_find_combine_backprop_weights": [_P, _SZ, _P, _P, _P],
+    "tfra_multi_find_combine_ragged_backprop_weights": [_P, _SZ, _P, _P, _P],
     "tfra_table_find_combine_backprop_weights": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, _P, _P, _P],
     "tfra_table_find_combine_ragged_backprop_weights": [_P, _SZ, _P, _SZ, _P, _P, _I, ctypes.c_uint32, ctypes.c_int64, _P, _P, _P,
                                                         _P],

@@ -11,7 +11,7 @@ from .variable import (CuckooHashTableConfig, CuckooHashTableCreator, HkvHashTab
                        KVCreator, SparseTrainableWrapper, TieredHashTableConfig, TieredHashTableCreator, TrainableWrapper, Variable,
                        default_partition_fn, embedding_lookup,
                        embedding_lookup_sparse, embedding_lookup_sparse_many, embedding_lookup_unique, get_variable,
-                       safe_embedding_lookup_sparse, safe_embedding_lookup_sparse_many)
+                       safe_embedding_lookup_sparse, safe_embedding_lookup_sparse_many, sparse_weights_grad_many)
 from . import ragged_embedding_ops   # (after .variable: it stands on the tuple-form functions)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -1342,8 +1342,8 @@ def _pooled_owner(e, owner, tiered):
 
 
 def _grouped_call(c_name, desc_type, who, owners, fill):
-  """The frame of the grouped calls (`find_combine_many`, `find_combine_ragged_many`, `apply_planned_combined_many`,
-  `build_plans_many`): ONE C call `c_name(workspace, n, descs, &launches, stream)` over one descriptor of `desc_type` per entry of
+  """The frame of the grouped calls (`find_combine_many`, `find_combine_ragged_many`, their `*_weight_grad_many` forms,
+  `apply_planned_combined_many`, `build_plans_many`): ONE C call `c_name(workspace, n, descs, &launches, stream)` over one descriptor of `desc_type` per entry of
   `owners`, on the current stream of the one device all of them live on.  An owner is a _DeviceTable, a CuckooHashTable /
   HkvHashTable (whose device table is taken: `_device_table`), a TieredHashTable / _DeviceTier (the pooled reads: `_device_tier`)
   or a SparsePlan.  Member by member, the owner's device (`_owner_device`) is compared
@@ -1430,6 +1430,71 @@ def find_combine_ragged_many(requests, return_launches=False):
                        ("tfra_multi_find_combine_ragged", _capi.FindCombineRaggedDesc))
   launches = _grouped_call(c_name, desc_type, "find_combine_ragged_many", [r[0] for r in requests], fill)
   return (outs, launches) if return_launches else outs
+
+
+def find_combine_weight_grad_many(requests, return_launches=False):
+  """The weight gradients of a list of pooled lookups in ONE C call (tfra_multi_find_combine_backprop_weights; the frame:
+  `_grouped_call`).  `requests`: a list of (table, ids, seg, weights, combiner, grad_out[, default_row]), the arguments behind
+  `table` those of `_DeviceTable.find_combine_weight_grad`, handled the same way (n_rows is grad_out's).  `table` is a table, a
+  TieredHashTable or a _DeviceTier (read in both tiers), in any mix; a table or tier may occur more than once.  Returns the
+  float32 [nnz] gradients in the requests' order, each bit-identical to `find_combine_weight_grad` of its request (with
+  return_launches: also the number of kernel launches the call enqueued: one that zero-fills all results and writes all rows'
+  bounds, and one per (tiered or not, value dtype, row-width class) class in the list)."""
+  if not requests:
+    return ([], 0) if return_launches else []
+  dws = []
+
+  def fill(e, i):
+    req = requests[i]
+    table, ids, seg, weights, combiner, grad_out = req[:6]
+    default_row = req[6] if len(req) > 6 else None
+    table = _pooled_owner(e, table, True)
+    g = table._weight_grad_out(grad_out, None)
+    ids, seg, w, d, _ = table._find_combine_args(ids, seg, weights, 0, default_row)
+    dw = torch.empty(ids.numel(), dtype=torch.float32, device=table._device)
+    dws.append(dw)
+    e.combiner = int(combiner)
+    e.nnz, e.ids, e.seg, e.weights = ids.numel(), ids.data_ptr(), seg.data_ptr(), (w.data_ptr() if w is not None else None)
+    e.n_rows, e.default_row, e.grad_out, e.dw_out = g.shape[0], d.data_ptr(), g.data_ptr(), dw.data_ptr()
+    return ids, seg, w, d, g
+
+  launches = _grouped_call("tfra_multi_find_combine_backprop_weights", _capi.FindCombineWgradDesc, "find_combine_weight_grad_many",
+                           [r[0] for r in requests], fill)
+  return (dws, launches) if return_launches else dws
+
+
+def find_combine_ragged_weight_grad_many(requests, return_launches=False):
+  """The weight gradients of a list of ragged pooled lookups in ONE C call (tfra_multi_find_combine_ragged_backprop_weights; the
+  frame: `_grouped_call`).  `requests`: a list of (table, row_splits, ids, weights, combiner, grad_out[, prune[, fill_id[,
+  default_row]]]), the arguments behind `table` those of `_DeviceTable.find_combine_ragged_weight_grad`, handled the same way;
+  `table` as in `find_combine_weight_grad_many`.  Returns the float32 [nnz] gradients in the requests' order, each bit-identical
+  to `find_combine_ragged_weight_grad` of its request (with return_launches: also the number of kernel launches: one that
+  zero-fills all results and one per (tiered or not, value dtype, row-width class, pruning or not) class in the list)."""
+  if not requests:
+    return ([], 0) if return_launches else []
+  dws = []
+
+  def fill(e, i):
+    req = requests[i]
+    table, row_splits, ids, weights, combiner, grad_out = req[:6]
+    prune = req[6] if len(req) > 6 else False
+    fill_id = req[7] if len(req) > 7 else None
+    default_row = req[8] if len(req) > 8 else None
+    table = _pooled_owner(e, table, True)
+    rs, ids, w, flags, fill_key, d, _ = table._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row)
+    g = table._weight_grad_out(grad_out, rs.numel() - 1)
+    dw = torch.empty(ids.numel(), dtype=torch.float32, device=table._device)
+    dws.append(dw)
+    e.combiner = int(combiner)
+    e.n_rows, e.row_splits = rs.numel() - 1, rs.data_ptr()
+    e.nnz, e.ids, e.weights = ids.numel(), ids.data_ptr(), (w.data_ptr() if w is not None else None)
+    e.flags, e.reserved, e.fill_id = flags, 0, fill_key
+    e.default_row, e.grad_out, e.dw_out = d.data_ptr(), g.data_ptr(), dw.data_ptr()
+    return rs, ids, w, d, g
+
+  launches = _grouped_call("tfra_multi_find_combine_ragged_backprop_weights", _capi.FindCombineRaggedWgradDesc,
+                           "find_combine_ragged_weight_grad_many", [r[0] for r in requests], fill)
+  return (dws, launches) if return_launches else dws
 
 
 def apply_planned_combined_many(requests, p_list, sync=True):

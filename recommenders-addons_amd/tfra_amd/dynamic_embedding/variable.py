@@ -951,6 +951,46 @@ class SparseTrainableWrapper(TrainableWrapper):
     return torch.zeros(cw.numel(), dtype=torch.float32, device=dw.device).masked_scatter_(cw > 0, dw)
 
 
+def sparse_weights_grad_many(grads_and_wrappers):
+  """`SparseTrainableWrapper.weights_grad` of a LIST of lookups (a many-table model's weighted sparse features):
+  `grads_and_wrappers` is a list of (grad_out, wrapper), and result i is what `wrapper.weights_grad(grad_out)` returns, bit for
+  bit and in the caller's length.  The wrappers on the pooled route — made behind the pooled forward, of a variable it still
+  serves (`_pooled_forward`), tiered or not — are read by ONE grouped call per device
+  (`table_ops.find_combine_weight_grad_many`: tfra_multi_find_combine_backprop_weights, whose launch count does not grow with the
+  list); what a safe lookup pruned is filled in per member afterwards, as `weights_grad` fills it.  Every other wrapper — several
+  shards, a callable initializer, bp_v2, other dims or dtypes — is served by its own `weights_grad`, so no list is refused.
+  The ValueErrors are `weights_grad`'s (no sp_weights, max_norm, a grad_out of another shape), raised for the whole list before
+  anything is enqueued.  As there, the tables' rows are read as they are at call time: call it before the step's write-back."""
+  pairs = list(grads_and_wrappers)
+  checked = []
+  for grad_out, tw in pairs:
+    if tw.max_norm is not None:
+      raise ValueError("weights_grad does not support max_norm: the clip's gradient is not formed")
+    if tw._weights is None:
+      raise ValueError("weights_grad needs a lookup made with sp_weights")
+    checked.append(tw.check_grad_out(grad_out))
+  results = [None] * len(pairs)
+  groups = {}   # device -> [i]
+  for i, (grad_out, tw) in enumerate(pairs):
+    if tw._pooled_ids is not None and _pooled_forward(tw.params, None):
+      groups.setdefault(tw.params._primary, []).append(i)
+    else:
+      results[i] = tw.weights_grad(grad_out)
+  for members in groups.values():
+    reqs = []
+    for i in members:
+      tw = pairs[i][1]
+      t, ids = tw.params._combined_operands(tw._pooled_ids, ragged=False)
+      reqs.append((_pooled_reader(t), ids, tw._seg, tw._weights, device_ops.COMBINERS[tw.combiner], checked[i], t._default_value))
+    for i, dw in zip(members, table_ops.find_combine_weight_grad_many(reqs)):
+      cw = pairs[i][1]._caller_weights
+      if cw is not None:   # (weights_grad: the kept positions are filled from dw in order, on the device)
+        cw = torch.as_tensor(cw, dtype=torch.float32, device=dw.device).reshape(-1)
+        dw = torch.zeros(cw.numel(), dtype=torch.float32, device=dw.device).masked_scatter_(cw > 0, dw)
+      results[i] = dw
+  return results
+
+
 def _note_pruned(tw, sparse_weights, combiner):
   """Behind a safe lookup: the wrapper remembers the caller's weights when entries were pruned by them (weights given and the
   combiner not "sum": `_safe_sparse_args`), so that `weights_grad` can answer in the caller's length and order.  A reference
