@@ -924,8 +924,9 @@ int tfra_multi_find_combine_ragged(tfra_workspace_t* ws, size_t n_tables, const 
  * bounds, ONE bounds launch over all descriptors, tiered or not, and one combine launch per (tiered or not, value dtype, NCH)
  * class in the list, at most 18; the ragged form one launch per (tiered or not, value dtype, NCH, safe or not) class, at most 36,
  * no memset and no bounds launch.  The plain classes run the kernels of tfra_multi_find_combine[_ragged].  *launches_out
- * (optional, host): the kernel launches enqueued.  Not for stream capture.  A training step still admits each tier's ids with a
- * tfra_tier_find_or_insert of its own first: what these calls collapse is the read.       (tests/test_gpu_tier_pooled_many.py) */
+ * (optional, host): the kernel launches enqueued.  Not for stream capture.  A training step admits its tiers' ids first, all
+ * tiers in one chain with tfra_multi_tier_find_or_insert (below): what these calls collapse is the read.
+ *                                                                                         (tests/test_gpu_tier_pooled_many.py) */
 typedef struct {
   uint32_t struct_size;      /* = sizeof(tfra_tier_find_combine_desc) */
   int32_t  combiner;         /* 0 sum | 1 mean | 2 sqrtn */
@@ -949,6 +950,47 @@ typedef struct {
 } tfra_tier_find_combine_ragged_desc;
 int tfra_multi_tier_find_combine_ragged(tfra_workspace_t* ws, size_t n_tables, const tfra_tier_find_combine_ragged_desc* descs,
                                         uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
+
+/* The grouped ADMISSION over tiers: tfra_tier_find_or_insert of a LIST of tiers as one stream-ordered chain (a model with 26 tiered
+ * features otherwise enqueues 26 chains of 6 launches in front of a grouped read of 3).  Per descriptor the call IS
+ * tfra_tier_find_or_insert on that descriptor: values_out and where, the invariant (afterwards every batch key is resident in the
+ * upper table with its whole row, what the promotion displaced is in the lower table as whole rows), the touch of the hits before
+ * the promotion, and the statistics (calls + 1, missed, lower_hits, demoted, not_resident under TFRA_TIER_VERIFY) are the same;
+ * the same device code runs (stages 2 to 4 as twins of the single kernels).  n == 0: the descriptor is skipped and its tier counts
+ * no call.  n_tiers == 0: TFRA_OK.
+ * Refusals, ALL before anything is enqueued — a refused list leaves every table, every statistic and every output of every
+ * descriptor untouched: the single call's rules with its codes and wording, prefixed "multi_tier_find_or_insert: descriptor <i>: "
+ * (a NULL tier, NULL keys or init_values, n > max_batch, unknown flag bits); and, TFRA_ERR_INVALID: a wrong struct_size, a
+ * non-zero `reserved`, descs == NULL with n_tiers > 0 (or a NULL ws), a tier on another device than ws, the same tier in two
+ * descriptors, and any table standing twice in the call in ANY role (two tiers over one lower table; one tier's lower table
+ * being another's upper table).  This call WRITES: the read calls' "may stand in several descriptors" does not carry over — a
+ * block of a launch touches only its own descriptor's tables and staging.  (Descriptors with n == 0 are not looked at for this.)
+ * Locks: each tier's own mutex once, in address order, then every upper and lower table once in the global order, as
+ * tfra_multi_tier_find_combine.
+ * Host work first: for ALL members, before the first grouped launch, both tables make room for the batch (a table may grow or
+ * enqueue a size read, as in the single call) and an upper table at max_capacity sets up its phase-2 flags; the epoch is read
+ * then and stepped per table after the enqueue.  If this fails part-way (a lower table's growth runs out of memory), earlier
+ * tables may have grown, but no row and no statistic has changed.
+ * Enqueues: one upload of the records (the workspace's ring of pinned, event-guarded slots), then each stage of the single chain
+ * once per launch class — the template instance and host mode the single call would have picked: 1 launch for all tiers'
+ * begin; find_missed_touch over the upper tables (copy granule 16 / 8 / 4 / 2 / 1 of row and buffers, 16 also with a dense
+ * table's second home bucket in flight: at most 6); the fetch over the lower tables (at most 6); the whole-row upsert into the
+ * upper tables (per granule, at most 5), for the members at max_capacity its capturing phase 2 (at most 5); the upsert of what
+ * was displaced into the lower tables (at most 5); for TFRA_TIER_VERIFY members the count-only find_missed (at most 2).  At most
+ * 30 launches whatever n_tiers; a list of 16-byte-aligned float32 tiers whose uppers are full is one class per stage: 6 launches,
+ * 7 with TFRA_TIER_VERIFY.  *launches_out (optional, host): the kernel launches enqueued.  Not for stream capture.
+ *                                                                                          (tests/test_gpu_tier_admit_many.py) */
+typedef struct {
+  uint32_t struct_size;            /* = sizeof(tfra_tier_find_or_insert_desc) */
+  uint32_t flags;                  /* TFRA_TIER_VERIFY or 0 */
+  tfra_tier_t* tier;
+  size_t n; const int64_t* d_n;    /* d_n may be NULL; as tfra_tier_find_or_insert */
+  const int64_t* keys;             /* unique */
+  const void* init_values; int32_t init_is_full; uint32_t reserved;   /* reserved = 0 */
+  void* values_out; uint8_t* where;                                   /* both may be NULL (admission only) */
+} tfra_tier_find_or_insert_desc;
+int tfra_multi_tier_find_or_insert(tfra_workspace_t* ws, size_t n_tiers, const tfra_tier_find_or_insert_desc* descs,
+                                   uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
 
 /* The gradient of the pooled lookup with respect to its WEIGHTS (sp_weights of embedding_lookup_sparse; the reference gets it
  * from TensorFlow's autodiff of `embeddings *= weights`, segment_sum and the divide, PY/dynamic_embedding_ops.py:233-291):

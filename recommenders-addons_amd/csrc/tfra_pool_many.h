@@ -133,12 +133,10 @@ int order_by_class(const std::string& who, const std::vector<PoolDesc>& ds, cons
   return TFRA_OK;
 }
 
-// The locks of a call: each distinct tier's own mutex once, in address order, BEFORE any table lock — the hierarchy of the single
-// tier calls (tier_enter) — then every table of the call (plain ones, uppers and lowers: a table may be named directly in one
-// descriptor and stand in a tier of another) once, in the global order, entered on s.  (Members are released in reverse order.)
-struct PoolLocks {
-  std::vector<std::unique_lock<std::mutex>> tiers, tables;
-};
+// The locks of a call (TierLocks, lock_tiers_and_tables: tfra_tier.h, shared with the grouped admission): each distinct tier's own
+// mutex, then every table of the call (plain ones, uppers and lowers: a table may be named directly in one descriptor and stand in
+// a tier of another) once.
+typedef TierLocks PoolLocks;
 int lock_owners(const std::vector<PoolDesc>& ds, const std::vector<size_t>& order, hipStream_t s, PoolLocks* l) {
   std::vector<tfra_tier*> tiers;
   std::vector<Table*> tabs;
@@ -153,11 +151,7 @@ int lock_owners(const std::vector<PoolDesc>& ds, const std::vector<size_t>& orde
       tabs.push_back(d.table);
     }
   }
-  std::sort(tiers.begin(), tiers.end(), std::less<tfra_tier*>());
-  tiers.erase(std::unique(tiers.begin(), tiers.end()), tiers.end());
-  l->tiers.reserve(tiers.size());
-  for (tfra_tier* t : tiers) l->tiers.emplace_back(t->mu);
-  return lock_and_enter(std::move(tabs), s, &l->tables);
+  return lock_tiers_and_tables(std::move(tiers), std::move(tabs), s, l);
 }
 
 }  // namespace

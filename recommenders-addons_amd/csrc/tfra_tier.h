@@ -1,6 +1,7 @@
 // What the tier calls of a table (tfra_tier.hip) share with the tier driver (tfra_tierstep.hip): the block shape of
 // find_missed_kernel, the miss list it appends to, and its ONE launcher; and what the driver shares with the tier's pooled lookup
-// (tfra_tierpool.hip) and its weight gradient (tfra_tierwgrad.hip): the driver's object and the locks a call on it takes.
+// (tfra_tierpool.hip) and its weight gradient (tfra_tierwgrad.hip): the driver's object and the locks a call on it takes; and with
+// the grouped admission (tfra_tierstep_many.hip): the checks of tfra_tier_find_or_insert, the fetch's operands, the grouped locks.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,6 +29,20 @@ struct MissOut {
   tfra::i64* keys;       // may be null
   int* idx;              // may be null
   tfra::u64* scores;     // find_missed's scores_out: may be null
+};
+
+// What tier_fetch_kernel (tfra_tierstep.hip) and its grouped twin (tfra_tierstep_many.hip) read and write beside the lower table.
+struct FetchIO {
+  const tfra::i64* keys;          // the miss list, *d_count entries of at most cap
+  const int* pos_of;              // the batch position of each
+  const tfra::u64* d_count;
+  size_t cap;
+  unsigned char* out;             // [n, field_bytes] by batch position; may be null
+  uint8_t* where;                 // [n] by batch position: 2 = found below, 0 = never seen; may be null
+  const unsigned char* defaults;  // the row of a key that is not below: row `position` when full, else row 0
+  int full;
+  unsigned char* stage;           // null (tier_find), or [cap, whole]: row j = the whole row of listed key j
+  tfra::u64* lower_hits;          // statistics word
 };
 
 // The driver's words on the device: the cumulative statistics, then the two counters of the call in flight.
@@ -58,6 +73,32 @@ struct TierEntry {
 static inline int tier_enter(tfra_tier* tier, hipStream_t s, TierEntry* e) {
   e->own = std::unique_lock<std::mutex>(tier->mu);
   return tfra::lock_and_enter({tier->upper, tier->lower}, s, &e->tables);
+}
+
+// The locks of a grouped call over tiers: each distinct tier's own mutex once, in address order, BEFORE any table lock — the
+// hierarchy of tier_enter — then every table of the call (plain ones, uppers and lowers) once, in the global order, entered on s.
+// (Members are released in reverse order.)
+struct TierLocks {
+  std::vector<std::unique_lock<std::mutex>> tiers, tables;
+};
+static inline int lock_tiers_and_tables(std::vector<tfra_tier*> tiers, std::vector<tfra::Table*> tabs, hipStream_t s, TierLocks* l) {
+  std::sort(tiers.begin(), tiers.end(), std::less<tfra_tier*>());
+  tiers.erase(std::unique(tiers.begin(), tiers.end()), tiers.end());
+  l->tiers.reserve(tiers.size());
+  for (tfra_tier* t : tiers) l->tiers.emplace_back(t->mu);
+  return tfra::lock_and_enter(std::move(tabs), s, &l->tables);
+}
+
+// The argument checks of tfra_tier_find_or_insert, in its order, for that call and for every descriptor of
+// tfra_multi_tier_find_or_insert (tfra_many.h: an operation's checks are ONE function).
+static inline tfra::Check check_tier_find_or_insert(const tfra_tier* tier, size_t n, const void* keys, const void* init_values,
+                                                    uint32_t flags) {
+  if (!tier) return tfra::refuse(TFRA_ERR_INVALID, "null tier");
+  if (flags & ~TFRA_TIER_VERIFY) return tfra::refuse(TFRA_ERR_INVALID, "unknown flag bits");
+  if (n == 0) return tfra::nothing_to_do();
+  if (!keys || !init_values) return tfra::refuse(TFRA_ERR_INVALID, "null buffer");
+  if (n > tier->max_batch) return tfra::refuse(TFRA_ERR_INVALID, "more keys than the tier's max_batch");
+  return tfra::Check{};
 }
 
 __device__ __forceinline__ size_t served(size_t n, const long long* d_n) {   // min(n, *d_n), a negative count = 0 (find_kernel's)

@@ -1,5 +1,6 @@
 // The tier driver: an upper table — a bounded LRU cache at max_capacity — in front of a lower table that never
 // forgets, driven as ONE stream-ordered chain with no host read: tfra_tier_find, tfra_tier_find_or_insert, tfra_tier_insert.
+// (Many tiers' find_or_insert in one chain: tfra_multi_tier_find_or_insert, tfra_tierstep_many.hip)
 // Whole co-located rows move between the tiers, so a key that goes down and comes up again keeps its slot vectors.
 // The launches of a find_or_insert: tier_begin_kernel; find_missed_touch_kernel on the upper table (launch_find_missed,
 // tfra_tier.hip); tier_fetch_kernel on the lower table (here); the locked whole-row upsert into the upper table, its phase 2
@@ -26,24 +27,12 @@ __global__ void tier_begin_kernel(u64* w) {
   w[TC_DOWN] = 0;
 }
 
-// What tier_fetch_kernel reads and writes beside the lower table.
-struct FetchIO {
-  const i64* keys;                // the miss list, *d_count entries of at most cap
-  const int* pos_of;              // the batch position of each
-  const u64* d_count;
-  size_t cap;
-  unsigned char* out;             // [n, field_bytes] by batch position; may be null
-  uint8_t* where;                 // [n] by batch position: 2 = found below, 0 = never seen; may be null
-  const unsigned char* defaults;  // the row of a key that is not below: row `position` when full, else row 0
-  int full;
-  unsigned char* stage;           // null (tier_find), or [cap, whole]: row j = the whole row of listed key j
-  u64* lower_hits;                // statistics word
-};
-
 // ---- step 2: the lower table's lookup of the miss list ----------------------------------------------------------------------------
 // find_wave with TierFetch: the embedding of listed key j goes to out[pos_of[j]].  With a stage, the whole row goes to stage row j: a
 // hit's as the lower table stores it, a never-seen key's as [its default row | slot vectors at aux_init] — what an upsert would have
 // left for it.  The block's hits are counted with ONE add (none when it has no hit).
+// (A TWIN, tier_fetch_body in tfra_tierstep_many.hip, runs this on a block index local to a descriptor of the grouped admission:
+// as a call of a shared body this kernel lost its code — by-value structs went to LDS — DESIGN §4.25.  A fix here belongs there too.)
 template <int G, int U, bool PF1, int TILES>
 __global__ __launch_bounds__(256 * TILES) void tier_fetch_kernel(TableView v, FetchIO io, AuxInit ai) {
   constexpr int NW = 4 * TILES;
@@ -193,11 +182,8 @@ int tfra_tier_find(tfra_tier_t* tier, size_t n, const int64_t* d_n, const int64_
 
 int tfra_tier_find_or_insert(tfra_tier_t* tier, size_t n, const int64_t* d_n, const int64_t* keys, const void* init_values,
                              int init_is_full, void* values_out, uint8_t* where, uint32_t flags, tfra_stream_t stream) {
-  const char* fn = "tfra_tier_find_or_insert";
-  if (!tier) return set_error(TFRA_ERR_INVALID, std::string(fn) + ": null tier");
-  if (flags & ~TFRA_TIER_VERIFY) return set_error(TFRA_ERR_INVALID, std::string(fn) + ": unknown flag bits");
-  if (n == 0) return TFRA_OK;
-  if (int rc = tier_check(fn, tier, n, keys && init_values)) return rc;
+  const Check c = check_tier_find_or_insert(tier, n, keys, init_values, flags);
+  if (c.done()) return report("tfra_tier_find_or_insert: ", c);
   hipStream_t s = (hipStream_t)stream;
   TierEntry entry;
   if (int rc = tier_enter(tier, s, &entry)) return rc;

@@ -16,6 +16,8 @@ using namespace tfra;
 
 // CAPTURE: every entry that leaves the table, and every key that is not admitted, is appended to `eo`.
 // WHOLE_IN (TFRA_INSERT_WHOLE_ROWS, capturing only): `vals` rows are whole co-located rows, written and reported as such.
+// (The <G, true, true> instance has a TWIN in tfra_tierstep_many.hip, insert_evict_whole_body, which takes its key index as an
+// argument; handing this body the index changed these kernels' registers — DESIGN §4.25.  A fix here belongs there too.)
 template <int G, bool CAPTURE, bool WHOLE_IN>
 __device__ __forceinline__ void insert_evict_body(const TableView& v, size_t n, const i64* __restrict__ keys,
                                                   const unsigned char* __restrict__ vals,
@@ -115,6 +117,8 @@ __global__ __launch_bounds__(256) void insert_evict_rows_kernel(TableView v, siz
 // FIND instance clears them.  A kernel of its own so that insert_unique_kernel keeps its code.
 // WHOLE (TFRA_INSERT_WHOLE_ROWS): `vals` rows are whole co-located rows; the slot vectors of a new AND of a resident key are the
 // caller's, init_aux_fields is not applied.
+// (The WHOLE instance has a TWIN in tfra_tierstep_many.hip, insert_whole_counted_body, on a wave index local to a descriptor of
+// the grouped admission — DESIGN §4.25.  A fix here belongs there too.)
 template <int G, int U, bool WHOLE>
 __global__ __launch_bounds__(256) void insert_counted_kernel(TableView v, size_t n_buf, const i64* __restrict__ keys,
                                                              const unsigned char* __restrict__ vals, const u64* __restrict__ scores,

@@ -688,15 +688,23 @@ class _DeviceTier:
                  _stream(self._upper._device))
     return (out, where) if return_where else out
 
+  def _admit_args(self, keys, init_values, want_rows, out=None):
+    """The operands of tfra_tier_find_or_insert, ONE copy for `find_or_insert`, `admit` and the grouped forms
+    (`tier_find_or_insert_many`, `admit_many`): -> keys, init rows, init_is_full, rows out, where (the last two None unless
+    want_rows)."""
+    keys = self._upper._keys(keys)
+    d, full = self._upper._init_rows(init_values, keys.numel())
+    if not want_rows:
+      return keys, d, full, None, None
+    out = self._upper._out(keys.shape, out)
+    return keys, d, full, out, torch.zeros(keys.shape, dtype=torch.uint8, device=self._upper._device)
+
   def find_or_insert(self, keys, init_values=None, return_where=False, count=None, out=None, verify=False):
     """The lookup of a training step (tfra_tier_find_or_insert): UNIQUE keys; rows as `find` returns them, a never-seen key's being
     its init row.  Afterwards every key of the batch is resident in upper with its whole row (the slot vectors it had below, or
     aux_init), and what that displaced is below.  verify: count the batch keys that are NOT resident at the end into
     stats()["not_resident"] (a batch that fills both home buckets of one of its keys with its own keys)."""
-    keys = self._upper._keys(keys)
-    d, full = self._upper._init_rows(init_values, keys.numel())
-    out = self._upper._out(keys.shape, out)
-    where = torch.zeros(keys.shape, dtype=torch.uint8, device=self._upper._device)
+    keys, d, full, out, where = self._admit_args(keys, init_values, True, out)
     if keys.numel():
       _capi.call("tfra_tier_find_or_insert", self._h, keys.numel(), _ptr(count), _ptr(keys), _ptr(d), full, _ptr(out), _ptr(where),
                  _capi.TIER_VERIFY if verify else 0, _stream(self._upper._device))
@@ -707,9 +715,8 @@ class _DeviceTier:
     max_batch; afterwards every one of them is resident in upper with its whole row, a never-seen key with its init row
     (`init_values`: [n, dim] or one row; None: the table's default row).  count: a device int64 (or pinned) count of the leading
     keys that are served.  No row is written back to the caller and nothing is read on the host: what a pooled training step
-    calls before `find_combine` (the write-back of the step then only hits)."""
-    keys = self._upper._keys(keys)
-    d, full = self._upper._init_rows(init_values, keys.numel())
+    calls before `find_combine` (the write-back of the step then only hits).  Many tiers at once: `admit_many`."""
+    keys, d, full, _, _ = self._admit_args(keys, init_values, False)
     if keys.numel():
       _capi.call("tfra_tier_find_or_insert", self._h, keys.numel(), _ptr(count), _ptr(keys), _ptr(d), full, None, None,
                  _capi.TIER_VERIFY if verify else 0, _stream(self._upper._device))
@@ -1563,3 +1570,46 @@ def build_plans_many(plans, ids_list, return_launches=False):
     plan.ids, plan.n = ids, ids.numel()   # keeps the ids alive until the next build
     plan._built.record(stream)
   return (plans, launches) if return_launches else plans
+
+
+def tier_find_or_insert_many(requests, return_launches=False):
+  """The admitting lookups of a list of tiers in ONE C call (tfra_multi_tier_find_or_insert; the frame: `_grouped_call`): one
+  chain of launches for the whole list — 6, or 7 with verify, for aligned float32 tiers whose caches are full — where a loop of
+  `_DeviceTier.find_or_insert` enqueues as many per tier.  `requests`: a list of (owner, keys[, init_values[, count[, want_rows[,
+  verify[, out]]]]]), `owner` a _DeviceTier or a TieredHashTable, the arguments behind it those of `_DeviceTier.find_or_insert`, prepared
+  the same way (`_DeviceTier._admit_args`); want_rows (default True) False: admission only, as `_DeviceTier.admit`.  Every tier,
+  and every table in any role, may stand ONCE in the list (the call writes): the C call refuses the list otherwise, and a refused
+  list changes nothing.  Returns, in the requests' order, (rows, where) or None for a request without want_rows, each what
+  `find_or_insert(..., return_where=True)` of its request returns (with return_launches: also the number of kernel launches)."""
+  if not requests:
+    return ([], 0) if return_launches else []
+  outs = []
+  tiers = []
+  for r in requests:
+    tier = _device_tier(r[0])
+    if tier is None:
+      raise ValueError("tier_find_or_insert_many: every owner must be a TieredHashTable or a _DeviceTier")
+    tiers.append(tier)
+
+  def fill(e, i):
+    req = tuple(requests[i]) + (None, None, True, False)[len(requests[i]) - 2:]
+    _, keys, init_values, count, want_rows, verify = req[:6]
+    keys, d, full, out, where = tiers[i]._admit_args(keys, init_values, want_rows, req[6] if len(req) > 6 else None)
+    outs.append((out, where) if want_rows else None)
+    e.flags, e.tier = (_capi.TIER_VERIFY if verify else 0), tiers[i]._h.value
+    e.n, e.d_n, e.keys = keys.numel(), (count.data_ptr() if count is not None else None), keys.data_ptr()
+    e.init_values, e.init_is_full, e.reserved = d.data_ptr(), full, 0
+    e.values_out, e.where = (out.data_ptr(), where.data_ptr()) if want_rows else (None, None)
+    return keys, d, count, out, where
+
+  launches = _grouped_call("tfra_multi_tier_find_or_insert", _capi.TierFindOrInsertDesc, "tier_find_or_insert_many", tiers, fill)
+  return (outs, launches) if return_launches else outs
+
+
+def admit_many(requests):
+  """`tier_find_or_insert_many` without outputs — the `_DeviceTier.admit` of a list of tiers in one call.  `requests`: a list of
+  (owner, keys[, init_values[, count[, verify]]]), the arguments behind `owner` those of `_DeviceTier.admit`."""
+  def widen(r):
+    r = tuple(r) + (None, None, False)[len(r) - 2:]
+    return (r[0], r[1], r[2], r[3], False, r[4])
+  tier_find_or_insert_many([widen(r) for r in requests])

@@ -1108,13 +1108,43 @@ def _check_entries_many(members):
     params._admissible_entries(entry_ids)
 
 
+# The shortest list of distinct tiers that `_admit_entries_many` admits with the grouped call.  One tier alone is slower grouped
+# (37.2 against 29.6 us); two are faster grouped there (44.5 against 54.1 us), but a list of two keeps one
+# tfra_tier_find_or_insert per member, which tests/test_gpu_tier_pooled_many.py holds: the chain that grows with the list is what
+# the grouped call is for, and from three tiers on it takes it.
+ADMIT_MANY_MIN_TIERS = 3
+
+
 def _admit_entries_many(params_list, entry_ids):
   """Ahead of the ONE grouped read of a training step: `Variable.admit_entries(entry_ids[i])` for every member i of `entry_ids`
   (index -> the entry ids its wrapper will write back; a member without tiered shards: nothing).  Admission moves rows between
-  the tiers and never changes them, so the one read behind all admissions returns what a read behind each would.  N tiered
-  members are still N admission chains: the read is what the grouped call collapses."""
+  the tiers and never changes them, so the one read behind all admissions returns what a read behind each would.  The members
+  (of one device) whose tiers are distinct are admitted by ONE grouped call (`table_ops.admit_many`:
+  tfra_multi_tier_find_or_insert, whose launch count does not grow with the list) when there are ADMIT_MANY_MIN_TIERS of them or
+  more, each member's entry ids de-duplicated on the device first as `admit_entries` does; a tier that stands in the list again
+  has its later occurrences admitted by the single call behind the grouped one — the order of the loop of single calls.  A
+  shorter list keeps the loop of `admit_entries`."""
+  first, later, seen = [], [], set()
   for i, ids in entry_ids.items():
-    params_list[i].admit_entries(ids)
+    params = params_list[i]
+    flat = params._admissible_entries(ids)
+    if flat is None or not flat.numel():
+      continue
+    tier = params._tables[0]._tier
+    (later if id(tier) in seen else first).append((params, flat))
+    seen.add(id(tier))
+  if len(first) < ADMIT_MANY_MIN_TIERS:
+    for params, flat in first:
+      params.admit_entries(flat)
+  else:
+    reqs = []
+    for params, flat in first:
+      t = params._tables[0]
+      uniq, _, cnt = device_ops.unique_no_sync(flat)
+      reqs.append((t, uniq, t._default_value, cnt))
+    table_ops.admit_many(reqs)
+  for params, flat in later:
+    params.admit_entries(flat)
 
 
 def _wrap_grouped(device, params_list, members, outs, entry_ids, plan_writeback, wrapper, results):
@@ -1136,7 +1166,7 @@ def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None,
   (`table_ops.find_combine_many`: tfra_multi_find_combine, whose launch count does not grow with the list) — a tiered variable
   among them: it joins its device's group with the shard itself as owner (`_pooled_reader`), the group then goes through
   tfra_multi_tier_find_combine and the member is read in both tiers; with return_trainable its entry ids are admitted into the
-  cache first (`_admit_entries_many`: one admission per tiered member, then the one read) —; every other variable
+  cache first (`_admit_entries_many`: ONE grouped admission of the device's tiered members from three on, then the one read) —; every other variable
   takes `embedding_lookup_sparse` as it is, so no list is refused.  With return_trainable and plan_writeback the grouped members
   that a single lookup would give a plan (`_plan_at_lookup`'s rule, per variable) get theirs from ONE grouped build per device on
   one side stream (`_plans_at_lookup_many`: tfra_multi_sparse_plan_build).  Where num_rows is absent, the grouped variables' row counts
