@@ -525,6 +525,25 @@ int tfra_table_upsert_planned(tfra_table_t* t, const tfra_sparse_plan_t* plan, c
 int tfra_table_find_or_insert_planned(tfra_table_t* t, const tfra_sparse_plan_t* plan,
                                       const void* init_values, int init_is_full, const uint64_t* scores,
                                       void* rows_out, uint8_t* found, tfra_stream_t stream);
+/* The same over a TIER (tfra_tier_create) -- tfra_tier_find_or_insert over a write-back plan: the lookup of a training step whose ids repeat, de-duplicated ONCE.  The keys
+ *    served are the DISTINCT keys of `plan`, a built CSR plan (tfra_sparse_plan_build with the tables' dim) of at most max_batch
+ *    ids; the call relates to tfra_tier_find_or_insert as tfra_table_find_or_insert_planned relates to tfra_table_find_or_insert:
+ *    a key's init row is init_values[L(k)], L(k) its LAST batch position (init_is_full == 0: row 0), and the key's row and its
+ *    `where` byte (1 = was in upper, 2 = came from lower, 0 = never seen) are written to EVERY batch position of the key.
+ *    rows_out ([plan n, dim]) and where ([plan n]) may each be NULL; both NULL is the admit-only form (nothing is handed back, the
+ *    two launches that spread rows to positions are not enqueued).  The tier carries no caller scores, so there is no `scores`.
+ *    Afterwards every distinct key of the plan is resident in upper with its whole row (a never-seen key: [init row | aux_init
+ *    slots]), what the promotion displaced is below as whole rows; the hits are touched before the promotion; the statistics move
+ *    as for tfra_tier_find_or_insert, counted per distinct key; TFRA_TIER_VERIFY counts the distinct keys not resident at the end.
+ *    The plan is left untouched and serves tfra_table_apply_planned / _apply_planned_combined / _upsert_planned on the upper table
+ *    afterwards.  Nothing is read on the host; a plan overflow word goes to the upper table's error counter.
+ *    Refused before anything is enqueued, tfra_last_error() naming the function: a NULL tier, plan or init_values, unknown flag
+ *    bits, a plan that was never built, more ids in the plan than max_batch, a plan of another dim or device (TFRA_ERR_INVALID);
+ *    an assign-only (SET) plan, a value dtype other than float32 / float16 / bfloat16, dim % 4 != 0, dim > 256, init_values or
+ *    rows_out not 16-byte aligned (TFRA_ERR_UNSUPPORTED).  The saturation limit of tfra_tier_find_or_insert holds unchanged.
+ *    (tests/test_gpu_tier_planned.py)                                                                                          */
+int tfra_tier_find_or_insert_planned(tfra_tier_t* tier, const tfra_sparse_plan_t* plan, const void* init_values,
+                                     int init_is_full, void* rows_out, uint8_t* where, uint32_t flags, tfra_stream_t stream);
 /* The write-back of an embedding_lookup_sparse (gradient with respect to its combined output): the contract of
  * tfra_table_apply_planned, with `plan` built over the ENTRY ids (the sparse input's values, repeats included) and the
  * gradient of plan position e = the combiner's backward of entry e, formed from grad_out[n_rows, dim] in registers

@@ -7,6 +7,7 @@
 //   tfra_own.hip      the assign half: the ownership pass + its remainder
 //   tfra_step.hip     the overlapped step's driver (its kernel: tfra_step_impl.h)
 //   tfra_find_insert.hip  find_or_insert over a CSR plan's keys (tfra_table_find_or_insert_planned)
+//   tfra_tierplan.hip  the same over a tier (tfra_tier_find_or_insert_planned)
 // The object holds types of tfra_plan_device.h (anonymous namespace): every unit includes the same definitions, so it has one
 // layout.  A helper shared across units cannot take or return such a type (its linkage would be internal): the shared ones below
 // take the plan object, pointers and scalars; keys_of, which returns one, is defined here for each unit.

@@ -1,7 +1,8 @@
 // What the tier calls of a table (tfra_tier.hip) share with the tier driver (tfra_tierstep.hip): the block shape of
 // find_missed_kernel, the miss list it appends to, and its ONE launcher; and what the driver shares with the tier's pooled lookup
 // (tfra_tierpool.hip) and its weight gradient (tfra_tierwgrad.hip): the driver's object and the locks a call on it takes; and with
-// the grouped admission (tfra_tierstep_many.hip): the checks of tfra_tier_find_or_insert, the fetch's operands, the grouped locks.
+// the grouped admission (tfra_tierstep_many.hip): the checks of tfra_tier_find_or_insert, the fetch's operands, the grouped locks;
+// and with the planned admission (tfra_tierplan.hip): the stages of the chain behind its own key launch.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -58,6 +59,7 @@ struct tfra_tier {
   tfra::u64* words = nullptr;       // [TIER_WORDS]
   tfra::i64* miss_keys = nullptr;   // [max_batch] what the upper table missed ...
   int* miss_idx = nullptr;          // [max_batch] ... and at which batch position
+  int* miss_rec = nullptr;          // [max_batch] the planned admission (tfra_tierplan.hip): ... and which key of the plan it is
   unsigned char* up_rows = nullptr;    // [max_batch, whole] what comes up
   tfra::i64* down_keys = nullptr;      // [max_batch] what goes down: keys,
   unsigned char* down_rows = nullptr;  // [max_batch, whole] whole rows
@@ -100,6 +102,15 @@ static inline tfra::Check check_tier_find_or_insert(const tfra_tier* tier, size_
   if (n > tier->max_batch) return tfra::refuse(TFRA_ERR_INVALID, "more keys than the tier's max_batch");
   return tfra::Check{};
 }
+
+// The stages of a tier's admitting chain that the planned admission (tfra_tierplan.hip) runs behind its own key launch, for a
+// caller that holds the tier's locks (tier_enter); defined in tfra_tierstep.hip.  tier_begin: the launch of tier_begin_kernel.
+// launch_fetch: step 2, tier_fetch_kernel over the miss list.  tier_put: steps 3 and 4, `values` into the upper table, what that
+// displaces as whole rows into the lower one.  (Hidden: shared by the library's units, not dynamic symbols.)
+__attribute__((visibility("hidden"))) void tier_begin(tfra_tier* tier, hipStream_t s);
+__attribute__((visibility("hidden"))) void launch_fetch(tfra::Table* lower, hipStream_t s, size_t n, const FetchIO& io, const tfra::AuxInitPod& ai);
+__attribute__((visibility("hidden"))) int tier_put(tfra_tier* tier, hipStream_t s, size_t n, const long long* d_n, const tfra::i64* keys,
+                                                   const unsigned char* values, bool whole_in);
 
 __device__ __forceinline__ size_t served(size_t n, const long long* d_n) {   // min(n, *d_n), a negative count = 0 (find_kernel's)
   if (!d_n) return n;

@@ -1,6 +1,7 @@
 // The tier driver: an upper table — a bounded LRU cache at max_capacity — in front of a lower table that never
 // forgets, driven as ONE stream-ordered chain with no host read: tfra_tier_find, tfra_tier_find_or_insert, tfra_tier_insert.
-// (Many tiers' find_or_insert in one chain: tfra_multi_tier_find_or_insert, tfra_tierstep_many.hip)
+// (Many tiers' find_or_insert in one chain: tfra_multi_tier_find_or_insert, tfra_tierstep_many.hip, DESIGN §4.25.  find_or_insert
+// over the distinct keys of a write-back plan: tfra_tier_find_or_insert_planned, tfra_tierplan.hip)
 // Whole co-located rows move between the tiers, so a key that goes down and comes up again keeps its slot vectors.
 // The launches of a find_or_insert: tier_begin_kernel; find_missed_touch_kernel on the upper table (launch_find_missed,
 // tfra_tier.hip); tier_fetch_kernel on the lower table (here); the locked whole-row upsert into the upper table, its phase 2
@@ -76,7 +77,9 @@ __global__ __launch_bounds__(256 * TILES) void tier_fetch_kernel(TableView v, Fe
 
 // =============================== host side ==========================================================================================
 
-static void launch_fetch(Table* lower, hipStream_t s, size_t n, const FetchIO& io, const AuxInit& ai) {
+void tier_begin(tfra_tier* tier, hipStream_t s) { tier_begin_kernel<<<1, 1, 0, s>>>(tier->words); }
+
+void launch_fetch(Table* lower, hipStream_t s, size_t n, const FetchIO& io, const AuxInit& ai) {
   const TableView v = lower->view_of(lower->cur);
   int g = granule_of(lower->field_bytes, io.out, io.defaults);
   if (io.stage) g = std::min(g, granule_of(lower->field_bytes, io.stage, nullptr));
@@ -99,7 +102,7 @@ static int tier_check(const char* fn, const tfra_tier* tier, size_t n, bool buff
 }
 
 // steps 3 and 4: `values` into the upper table, what that displaces as whole rows into the lower one
-static int tier_put(tfra_tier* tier, hipStream_t s, size_t n, const long long* d_n, const i64* keys, const unsigned char* values, bool whole_in) {
+int tier_put(tfra_tier* tier, hipStream_t s, size_t n, const long long* d_n, const i64* keys, const unsigned char* values, bool whole_in) {
   const EvictOut eo{tier->words + TC_DOWN, (u64)tier->max_batch, tier->down_keys, tier->down_rows, tier->down_scores, tier->whole};
   if (int rc = insert_counted(tier->upper, s, n, d_n, keys, values, nullptr, whole_in, &eo)) return rc;
   return insert_counted(tier->lower, s, n, (const long long*)(tier->words + TC_DOWN), tier->down_keys, tier->down_rows, nullptr, true, nullptr);
@@ -130,8 +133,8 @@ int tfra_tier_create(tfra_table_t* up, tfra_table_t* lo, size_t max_batch, tfra_
   t->fb = upper->field_bytes;
   t->whole = upper->field_bytes * (1u + (unsigned)upper->opts.aux_fields);
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t o_words = 0, o_mk = al(TIER_WORDS * 8), o_mi = o_mk + al(max_batch * 8), o_up = o_mi + al(max_batch * 4),
-               o_dk = o_up + al(max_batch * t->whole), o_dr = o_dk + al(max_batch * 8), o_ds = o_dr + al(max_batch * t->whole),
+  const size_t o_words = 0, o_mk = al(TIER_WORDS * 8), o_mi = o_mk + al(max_batch * 8), o_mr = o_mi + al(max_batch * 4),
+               o_up = o_mr + al(max_batch * 4), o_dk = o_up + al(max_batch * t->whole), o_dr = o_dk + al(max_batch * 8), o_ds = o_dr + al(max_batch * t->whole),
                total = o_ds + al(max_batch * 8);
   hipError_t e = hipMalloc((void**)&t->block, total);
   if (e == hipSuccess) e = hipMemset(t->block, 0, al(TIER_WORDS * 8));
@@ -143,6 +146,7 @@ int tfra_tier_create(tfra_table_t* up, tfra_table_t* lo, size_t max_batch, tfra_
   t->words = (u64*)(t->block + o_words);
   t->miss_keys = (i64*)(t->block + o_mk);
   t->miss_idx = (int*)(t->block + o_mi);
+  t->miss_rec = (int*)(t->block + o_mr);
   t->up_rows = t->block + o_up;
   t->down_keys = (i64*)(t->block + o_dk);
   t->down_rows = t->block + o_dr;

@@ -205,6 +205,7 @@ _SIGS = {
     "tfra_tier_destroy": [_P],
     "tfra_tier_find": [_P, _SZ, _P, _P, _P, _P, _P, _I, _P],
     "tfra_tier_find_or_insert": [_P, _SZ, _P, _P, _P, _I, _P, _P, ctypes.c_uint32, _P],
+    "tfra_tier_find_or_insert_planned": [_P, _P, _P, _I, _P, _P, ctypes.c_uint32, _P],
     "tfra_tier_insert": [_P, _SZ, _P, _P, _P, _P],
     "tfra_tier_stats": [_P, ctypes.POINTER(ctypes.c_uint64), _P],
     "tfra_tier_find_combine": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, _P, _P],

@@ -721,6 +721,41 @@ class _DeviceTier:
       _capi.call("tfra_tier_find_or_insert", self._h, keys.numel(), _ptr(count), _ptr(keys), _ptr(d), full, None, None,
                  _capi.TIER_VERIFY if verify else 0, _stream(self._upper._device))
 
+  def _planned_args(self, plan, init_values):
+    """The plan-side operands of tfra_tier_find_or_insert_planned, ONE copy for `find_or_insert_planned` and `admit_planned`: the
+    plan's checks — its dim and device, at most max_batch ids (the tier's staging) — and the init rows, [n, dim] per batch
+    POSITION or one row, by the admitting rule."""
+    up = self._upper
+    _check_plan(plan, up._dim, up._device)
+    if plan.n > self._max_batch:
+      raise ValueError("the plan holds %d ids, more than the tier's max_batch %d" % (plan.n, self._max_batch))
+    return up._init_rows(init_values, plan.n)
+
+  def find_or_insert_planned(self, plan, init_values=None, return_where=False, out=None, verify=False):
+    """`find_or_insert` of a batch whose ids may repeat, over the write-back plan of that batch (tfra_tier_find_or_insert_planned):
+    `plan` is a built `SparsePlan` of the tables' dim with at most max_batch ids; the keys served are its distinct ids, and every
+    batch position of an id gets the id's row and its `where` byte.  init_values: [n, dim] — row p belongs to batch POSITION p, an
+    id takes the row of its last position — or one row ([dim]; None: the table's default row).  out: the [n, dim] buffer to fill.
+    -> rows [n, dim], or (rows, where).  Afterwards every distinct id is resident in upper with its whole row, and the plan serves
+    `apply_planned` / `upsert_planned` on upper: the batch is de-duplicated once.  verify: as `find_or_insert`, per distinct id.
+    Nothing is read on the host."""
+    d, full = self._planned_args(plan, init_values)
+    up, n = self._upper, plan.n
+    out = up._out((n,), out)
+    where = torch.zeros(n, dtype=torch.uint8, device=up._device) if return_where else None   # (not wanted: not written)
+    if n:
+      _over_plans((plan,), up._device, True, _capi.call, "tfra_tier_find_or_insert_planned", self._h, plan._h, _ptr(d), full,
+                  _ptr(out), _ptr(where), _capi.TIER_VERIFY if verify else 0, _stream(up._device))
+    return (out, where) if return_where else out
+
+  def admit_planned(self, plan, init_values=None, verify=False):
+    """`find_or_insert_planned` without its result (rows_out and where NULL): afterwards every distinct id of the plan is resident
+    in upper with its whole row; no row is written back to the caller, and the launches that spread rows to positions do not run."""
+    d, full = self._planned_args(plan, init_values)
+    if plan.n:
+      _over_plans((plan,), self._upper._device, True, _capi.call, "tfra_tier_find_or_insert_planned", self._h, plan._h, _ptr(d), full,
+                  None, None, _capi.TIER_VERIFY if verify else 0, _stream(self._upper._device))
+
   def find_combine(self, ids, seg, weights, combiner, n_rows, default_row=None):
     """`_DeviceTable.find_combine` over both tiers (tfra_tier_find_combine): an entry's row is the one upper holds, else the one
     lower holds, else `default_row`.  A read: nothing moves, nothing is written, `stats()` does not change; ids are not limited by
@@ -1223,7 +1258,19 @@ class TieredHashTable(_LookupInterfaceMirror):
     return (rows, where != 0) if return_exists else rows
 
   def find_or_insert_planned(self, plan, dynamic_default_values=None, return_exists=False, name=None):
-    raise NotImplementedError("TieredHashTable has no planned admitting lookup: look the ids up with find_or_insert")
+    """`find_or_insert` of the batch a `SparsePlan` was built over (ids may repeat, at most `max_batch` of them), through both
+    tiers (`_DeviceTier.find_or_insert_planned`): every position gets its id's row, an id neither tier held enters with the row of
+    its LAST position (`dynamic_default_values[p]`, else the table's default row).  exists[p] is False for such an id.  The plan
+    then serves the write-back on the cache."""
+    if not return_exists:
+      return self._tier.find_or_insert_planned(plan, dynamic_default_values)
+    rows, where = self._tier.find_or_insert_planned(plan, dynamic_default_values, return_where=True)
+    return rows, where != 0
+
+  def admit_planned(self, plan, init_values=None, verify=False):
+    """`find_or_insert_planned` that hands no rows back (`_DeviceTier.admit_planned`): afterwards every distinct id of the plan is
+    in the cache with its whole row."""
+    self._tier.admit_planned(plan, init_values, verify=verify)
 
   def admit(self, keys, init_values=None, count=None, verify=False):
     """`find_or_insert` that hands no rows back (`_DeviceTier.admit`): UNIQUE keys, at most `max_batch`; afterwards each is in the

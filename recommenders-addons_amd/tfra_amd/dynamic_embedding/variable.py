@@ -140,7 +140,9 @@ class Variable:
   `apply_gradients` takes that same plan — the batch is de-duplicated once per step instead of twice.  Row p of the one draw
   initializer([n, dim]) belongs to batch position p, and a never-seen id enters with the row of its LAST position (with True: row
   j belongs to the j-th distinct id in first-occurrence order), so the two settings admit different rows for the same seed.
-  Several shards, more than 2^18 ids, no free plan, or the sparse wrapper: the True route.  Measured (Adam, 131 072 Zipf ids, 10 %
+  Several shards, more than 2^18 ids, no free plan, the sparse wrapper, or tiered shards: the True route.  (A tier has the planned
+  lookup — `TieredHashTable.find_or_insert_planned` — but a step through it was measured 13.0 us below True's 206.6 with spreads that
+  sum to 15.0, short of the margin, so the variable does not route to it: DESIGN 4.26.)  Measured (Adam, 131 072 Zipf ids, 10 %
   never seen, us per step): False 153.5, True 159.1, True with plan_writeback 158.5, "plan" 134.5."""
 
   def __init__(self, key_dtype=torch.int64, value_dtype=torch.float32, dim=1, devices=None,
@@ -775,13 +777,13 @@ class TrainableWrapper:
     find_or_insert over the unique buffer with the count left on the device, and the rows gathered back through the inverse
     index: every position of an id sees one row, and the table holds it.  No host read.  (Several shards: the unique ids are
     trimmed with one host read and go through `Variable.lookup_or_insert`.)
-    init_on_lookup="plan" (one shard, ids that may repeat, a plan to be had: `_plan_for_lookup`): no unique and no gather — the
+    init_on_lookup="plan" (one shard that is not tiered, ids that may repeat, a plan to be had: `_plan_for_lookup`): no unique and no gather — the
     ids go through their write-back plan (find_or_insert_planned), row p of the one draw belongs to batch position p and an id
     that is not resident takes the row of its last position."""
     params, ids = self.params, self.ids
     if params.shard_num == 1:
       t = params._tables[0]
-      planned = params.init_on_lookup == "plan" and not self._ids_are_unique and not _has_tiered_shards(params)   # (a tier: the True route)
+      planned = params.init_on_lookup == "plan" and not self._ids_are_unique and not _has_tiered_shards(params)   # (a tier: the True route — DESIGN 4.26)
       plan = self._plan_for_lookup() if planned else None
       init = params._create_default_values_by_initializer(ids.numel(), t._device)
       if plan is not None:
