@@ -1011,6 +1011,41 @@ typedef struct {
 int tfra_multi_tier_find_or_insert(tfra_workspace_t* ws, size_t n_tiers, const tfra_tier_find_or_insert_desc* descs,
                                    uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
 
+/* The grouped admitting lookup of PLAIN tables: tfra_table_find_or_insert of a LIST of tables as one stream-ordered chain (a model
+ * with 26 random-initializer features otherwise enqueues 26 admissions in front of a grouped read of 3).  Per descriptor the call
+ * IS tfra_table_find_or_insert on that descriptor: values_out and found are the same and the table ends the same (keys, rows,
+ * slot vectors at aux_init, scores; the epoch steps once per table), with the same victim and admission rule at max_capacity;
+ * min(n, *d_n) keys are served and outputs beyond the count are left as they are; the same device code runs (both phases as twins
+ * of the single call's kernels).  n == 0: the descriptor is skipped and its table's epoch does not step.  n_tables == 0: TFRA_OK.
+ * Refusals, ALL before anything is enqueued — a refused list leaves every table and every output of every descriptor untouched:
+ * the single call's rules with its codes and wording, prefixed "multi_find_or_insert: descriptor <i>: " (a NULL table, NULL keys
+ * or init_values, n >= 2^31); and, TFRA_ERR_INVALID: a wrong struct_size, non-zero `flags` or `reserved`, descs == NULL with
+ * n_tables > 0 or a NULL ws ("null argument": checked without a device, *launches_out = 0), a table on another device than ws,
+ * and the same table in two descriptors.  This call WRITES: a block of a launch touches only its own descriptor's table, buffers
+ * and scratch.  (Descriptors with n == 0 are not looked at for this.)
+ * Locks: every table once, in the global order of the grouped calls.
+ * Host work first: for ALL members, before the first grouped launch, the table makes room for the batch (it may grow or enqueue a
+ * size read, as in the single call) and a table at max_capacity sets up its phase-2 flags (and, for one shared init row without
+ * values_out, its spill rows); the epoch is read then and stepped per table after the enqueue.  If this fails part-way (a
+ * growth runs out of memory), earlier tables may have grown, but no row has changed.
+ * Enqueues: one upload of the records (the workspace's ring of pinned, event-guarded slots), then phase 1 once per copy-granule
+ * class (16 / 8 / 4 / 2 / 1 of row, init rows and values_out) present in the list, and phase 2 once per granule class among the
+ * members at max_capacity.  At most 10 launches whatever n_tables; a list of 16-byte-aligned float32 growing tables takes 1, with
+ * full bounded members 2.  *launches_out (optional, host): the kernel launches enqueued.  Synchronises nothing.  Not for stream
+ * capture.                                                                              (tests/test_gpu_find_or_insert_many.py) */
+typedef struct {
+  uint32_t struct_size;            /* = sizeof(tfra_find_or_insert_desc) */
+  uint32_t flags;                  /* 0 */
+  tfra_table_t* table;
+  size_t n; const int64_t* d_n;    /* d_n may be NULL; as tfra_table_find_or_insert */
+  const int64_t* keys;             /* unique */
+  const void* init_values; int32_t init_is_full; uint32_t reserved;   /* reserved = 0 */
+  const uint64_t* scores;          /* NULL or [n] */
+  void* values_out; uint8_t* found;                                   /* both may be NULL (admission only) */
+} tfra_find_or_insert_desc;
+int tfra_multi_find_or_insert(tfra_workspace_t* ws, size_t n_tables, const tfra_find_or_insert_desc* descs,
+                              uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
+
 /* The gradient of the pooled lookup with respect to its WEIGHTS (sp_weights of embedding_lookup_sparse; the reference gets it
  * from TensorFlow's autodiff of `embeddings *= weights`, segment_sum and the divide, PY/dynamic_embedding_ops.py:233-291):
  * dw_out[p] = d loss / d weights[p], float32 [nnz], for grad_out = d loss / d out, float32 [n_rows, dim].

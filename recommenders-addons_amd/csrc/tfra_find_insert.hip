@@ -5,6 +5,7 @@
 // tfra_upsert.hip's (evict_phase, tfra_upsert.h).
 #include <hip/hip_runtime.h>
 
+#include "tfra_find_insert.h"
 #include "tfra_find_insert_device.h"
 #include "tfra_host.h"
 #include "tfra_plan.h"
@@ -17,9 +18,10 @@ using namespace tfra;
 extern "C" int tfra_table_find_or_insert(tfra_table_t* tp, size_t n, const int64_t* d_n, const int64_t* keys, const void* init_values,
                                          int init_is_full, const uint64_t* scores, void* values_out, uint8_t* found,
                                          tfra_stream_t stream) {
-  if (!tp) return set_error(TFRA_ERR_INVALID, "tfra_table_find_or_insert: null table");
-  if (n == 0) return TFRA_OK;
-  if (int rc = check_batch("tfra_table_find_or_insert: ", n, keys && init_values)) return rc;
+  {   // (the grouped call, tfra_find_insert_many.hip, runs the same checks per descriptor)
+    const Check c = check_find_or_insert(tp, n, keys, init_values);
+    if (c.done()) return report("tfra_table_find_or_insert: ", c);
+  }
   TABLE_ENTER();
   int rc = t->prepare_insert(n, s);   // (n is an upper bound of the keys when d_n is given)
   if (rc) return rc;

@@ -17,7 +17,9 @@ using namespace tfra;
 // CAPTURE: every entry that leaves the table, and every key that is not admitted, is appended to `eo`.
 // WHOLE_IN (TFRA_INSERT_WHOLE_ROWS, capturing only): `vals` rows are whole co-located rows, written and reported as such.
 // (The <G, true, true> instance has a TWIN in tfra_tierstep_many.hip, insert_evict_whole_body, which takes its key index as an
-// argument; handing this body the index changed these kernels' registers — DESIGN §4.25.  A fix here belongs there too.)
+// argument; handing this body the index changed these kernels' registers — DESIGN §4.25.  A fix here belongs there too.
+// The <G, false, false> instance has one in tfra_find_insert_many.hip, find_insert_evict_body — DESIGN §4.27.  A fix in one belongs
+// in the other.)
 template <int G, bool CAPTURE, bool WHOLE_IN>
 __device__ __forceinline__ void insert_evict_body(const TableView& v, size_t n, const i64* __restrict__ keys,
                                                   const unsigned char* __restrict__ vals,

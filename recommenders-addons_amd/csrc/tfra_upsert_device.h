@@ -72,6 +72,8 @@ struct FindOut {
 // writes a row that a hit reads, and the rows of earlier launches are behind a kernel boundary, so the row is loaded as find loads it.
 // A TWIN of the plain instance lives in tfra_upsert.hip: insert_counted_kernel (the key count on the device, whole rows in; DESIGN
 // §4.20) repeats its probes, claim, score and accounting so that this kernel keeps its code.  A fix here belongs there too.
+// The FIND instance has a TWIN as well: find_insert_body (tfra_find_insert_many.hip), the same lookup with its
+// operands read from a descriptor's record and the wave index local to the descriptor.  A fix in one belongs in the other.
 template <int G, int U, bool FIND = false>
 __global__ __launch_bounds__(256) void insert_unique_kernel(TableView v, size_t n,
                                                             const i64* __restrict__ keys,

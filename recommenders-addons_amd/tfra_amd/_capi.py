@@ -126,6 +126,16 @@ class TierFindOrInsertDesc(ctypes.Structure):
   ]
 
 
+class FindOrInsertDesc(ctypes.Structure):
+  """tfra_find_or_insert_desc (include/tfra_mi355x.h): one plain table's admitting lookup in tfra_multi_find_or_insert."""
+  _fields_ = [
+      ("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("table", ctypes.c_void_p),
+      ("n", ctypes.c_size_t), ("d_n", ctypes.c_void_p), ("keys", ctypes.c_void_p),
+      ("init_values", ctypes.c_void_p), ("init_is_full", ctypes.c_int32), ("reserved", ctypes.c_uint32),
+      ("scores", ctypes.c_void_p), ("values_out", ctypes.c_void_p), ("found", ctypes.c_void_p),
+  ]
+
+
 class FindCombineWgradDesc(ctypes.Structure):
   """tfra_find_combine_wgrad_desc (include/tfra_mi355x.h): the weight gradient of one tier's or one table's pooled lookup in
   tfra_multi_find_combine_backprop_weights; exactly one of table / tier is set."""
@@ -272,6 +282,7 @@ _SIGS = {
     "tfra_multi_tier_find_combine": [_P, _SZ, _P, _P, _P],
     "tfra_multi_tier_find_combine_ragged": [_P, _SZ, _P, _P, _P],
     "tfra_multi_tier_find_or_insert": [_P, _SZ, _P, _P, _P],
+    "tfra_multi_find_or_insert": [_P, _SZ, _P, _P, _P],
     "tfra_multi_find_combine_backprop_weights": [_P, _SZ, _P, _P, _P],
     "tfra_multi_find_combine_ragged_backprop_weights": [_P, _SZ, _P, _P, _P],
     "tfra_table_find_combine_backprop_weights": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, _P, _P, _P],

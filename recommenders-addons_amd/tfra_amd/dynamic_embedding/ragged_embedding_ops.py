@@ -22,7 +22,7 @@ import torch
 
 from . import device_ops, table_ops
 from .variable import (SparseTrainableWrapper, _admit_entries_many, _check_combiner, _check_entries_many, _note_pruned, _per_table,
-                       _pooled_forward, _pooled_reader, _safe_sparse_args, _wrap_grouped)
+                       _pooled_forward, _pooled_reader, _pooled_training, _safe_sparse_args, _wrap_grouped)
 from . import variable as _tuple_form
 
 
@@ -89,11 +89,11 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights, name=None, combiner="mea
   _check_combiner(combiner)
   rs, ids, w = _ragged_input(params, sp_ids, sp_weights)
   n = rs.numel() - 1
-  if not _pooled_forward(params, None):
+  if not (_pooled_training if return_trainable else _pooled_forward)(params, None):
     return _tuple_form.embedding_lookup_sparse(params, (row_ids_of(rs, ids.numel()), ids), w, combiner=combiner,
                                                return_trainable=return_trainable, num_rows=n, plan_writeback=plan_writeback)
   if return_trainable:
-    params.admit_entries(ids)   # (tiered shards: the entry ids into the cache ahead of the read; otherwise nothing)
+    params.admit_entries(ids)   # (tiered shards: the entry ids into the cache ahead of the read; init_on_lookup="pooled": admitted with drawn rows)
   out = params.lookup_combined_ragged(rs, ids, w, combiner)
   if not return_trainable:
     return out
@@ -113,7 +113,7 @@ def safe_embedding_lookup_sparse(params, sparse_ids, sparse_weights=None, combin
   _check_combiner(combiner)
   rs, ids, w = _ragged_input(params, sparse_ids, sparse_weights)
   n = rs.numel() - 1
-  if not _pooled_forward(params, None):
+  if not (_pooled_training if return_trainable else _pooled_forward)(params, None):
     return _tuple_form.safe_embedding_lookup_sparse(params, (row_ids_of(rs, ids.numel()), ids), w, combiner=combiner,
                                                     default_id=default_id, return_trainable=return_trainable, num_rows=n,
                                                     plan_writeback=plan_writeback)
@@ -121,7 +121,7 @@ def safe_embedding_lookup_sparse(params, sparse_ids, sparse_weights=None, combin
   if not return_trainable:
     return params.lookup_combined_ragged(rs, ids, w, combiner, prune=prune, fill_id=fill)
   made = _safe_entries(params, rs, ids, w, combiner, default_id, n)
-  params.admit_entries(made[3][0])   # (tiered shards: the entry ids into the cache ahead of the read; otherwise nothing)
+  params.admit_entries(made[3][0])   # (tiered shards: the entry ids into the cache ahead of the read; init_on_lookup="pooled": admitted with drawn rows)
   out = params.lookup_combined_ragged(rs, ids, w, combiner, prune=prune, fill_id=fill)
   return out, _safe_wrapper(params, made, combiner, n, plan_writeback, caller_weights=w)
 
@@ -138,8 +138,9 @@ def _many(params_list, sp_ids_list, weights_list, combiner, default_id, safe, re
   single = safe_embedding_lookup_sparse if safe else embedding_lookup_sparse
   results = [None] * n_t
   groups, singles = {}, []   # device -> [(i, row_splits, ids, w)]; the members the pooled forward does not serve
+  pooled = _pooled_training if return_trainable else _pooled_forward
   for i, params in enumerate(params_list):
-    if not _pooled_forward(params, None):
+    if not pooled(params, None):
       singles.append(i)
       continue
     groups.setdefault(params._primary, []).append((i,) + _ragged_input(params, sp_ids_list[i], weights[i]))

@@ -347,6 +347,21 @@ class _DeviceTable:
                  _ptr(exists), _stream(self._device))
     return (out, exists) if return_exists else out
 
+  def admit(self, keys, init_values=None, scores=None, count=None):
+    """`find_or_insert` without its result (tfra_table_find_or_insert with values_out and found NULL): UNIQUE keys; afterwards every
+    one of them that could be placed is resident, a never-seen key with its init row (`init_values`: [n, dim] or one row; None: the
+    table's default row) and the slot vectors at aux_init, a resident key untouched but for its score.  scores, count: as for
+    `find_or_insert`.  No [n, dim] buffer is allocated, no row is written back to the caller and nothing is read on the host: what
+    a pooled training step of a random-initializer variable calls before `find_combine` (the write-back of the step then only
+    hits).  Many tables at once: `table_admit_many`."""
+    keys = self._keys(keys)
+    n = keys.numel()
+    d, full = self._init_rows(init_values, n)
+    scores = _scores_for(scores, n, self._device)
+    if n:
+      _capi.call("tfra_table_find_or_insert", self._h, n, _ptr(count), _ptr(keys), _ptr(d), full, _ptr(scores), None, None,
+                 _stream(self._device))
+
   def find_or_insert_planned(self, plan, init_values=None, scores=None, return_exists=False, out=None):
     """`find_or_insert` of a batch whose ids may repeat, over the write-back plan of that batch (tfra_table_find_or_insert_planned):
     `plan` is a built `SparsePlan` of this table's dim; the keys served are its distinct ids, and every batch position of an id
@@ -954,6 +969,13 @@ class _LookupInterfaceMirror:
     keys = _as_tensor(keys, self._device)
     return self._table.find_or_insert(keys, dynamic_default_values, scores=self._gen_scores(keys), return_exists=return_exists,
                                       count=count)
+
+  def admit(self, keys, dynamic_default_values=None, count=None):
+    """`find_or_insert` without its result (`_DeviceTable.admit`): the unique `keys` become resident, a never-seen key with its
+    row of `dynamic_default_values` ([n, dim] or one row; None: the table's default row); no rows are handed back.  Scores as
+    `find_or_insert` passes them (`_gen_scores`)."""
+    keys = _as_tensor(keys, self._device)
+    self._table.admit(keys, dynamic_default_values, scores=self._gen_scores(keys), count=count)
 
   def find_or_insert_planned(self, plan, dynamic_default_values=None, return_exists=False, name=None):
     """`find_or_insert` of the batch a `SparsePlan` was built over (ids may repeat): every position gets its id's row, an id that
@@ -1660,3 +1682,57 @@ def admit_many(requests):
     r = tuple(r) + (None, None, False)[len(r) - 2:]
     return (r[0], r[1], r[2], r[3], False, r[4])
   tier_find_or_insert_many([widen(r) for r in requests])
+
+
+def find_or_insert_many(requests, return_launches=False):
+  """The admitting lookups of a list of PLAIN tables in ONE C call (tfra_multi_find_or_insert; the frame: `_grouped_call`): phase 1
+  once per copy-granule class of the list and, for the members at max_capacity, phase 2 once per class among them — 1 launch for
+  aligned float32 growing tables, 2 with full bounded members — where a loop of `_DeviceTable.find_or_insert` enqueues as many per
+  table.  `requests`: a list of (owner, keys[, init_values[, count[, want_rows[, scores[, out]]]]]), `owner` a _DeviceTable or a
+  table class that wraps one (CuckooHashTable / HkvHashTable), the arguments behind it those of `_DeviceTable.find_or_insert`,
+  prepared the same way; want_rows (default True) False: admission only, as `_DeviceTable.admit`.  Every table may stand ONCE in
+  the list (the call writes): the C call refuses the list otherwise, and a refused list changes nothing.  Returns, in the
+  requests' order, (rows, exists) or None for a request without want_rows, each what `find_or_insert(..., return_exists=True)` of
+  its request returns (with return_launches: also the number of kernel launches)."""
+  if not requests:
+    return ([], 0) if return_launches else []
+  outs = []
+  tables = []
+  for r in requests:
+    if _device_tier(r[0]) is not None:
+      raise ValueError("find_or_insert_many: a tiered owner goes through tier_find_or_insert_many")
+    tables.append(_device_table(r[0]))
+
+  def fill(e, i):
+    t = tables[i]
+    req = tuple(requests[i]) + (None, None, True, None, None)[len(requests[i]) - 2:]
+    _, keys, init_values, count, want_rows, scores, out = req[:7]
+    keys = t._keys(keys)
+    n = keys.numel()
+    d, full = t._init_rows(init_values, n)
+    scores = _scores_for(scores, n, t._device)
+    exists = None
+    if want_rows:
+      out = t._out(keys.shape, out)
+      exists = torch.zeros(keys.shape, dtype=torch.bool, device=t._device)
+    else:
+      out = None
+    outs.append((out, exists) if want_rows else None)
+    e.flags, e.table = 0, t._h.value
+    e.n, e.d_n, e.keys = n, (count.data_ptr() if count is not None else None), keys.data_ptr()
+    e.init_values, e.init_is_full, e.reserved = d.data_ptr(), full, 0
+    e.scores = scores.data_ptr() if scores is not None else None
+    e.values_out, e.found = (out.data_ptr(), exists.data_ptr()) if want_rows else (None, None)
+    return keys, d, count, scores, out, exists
+
+  launches = _grouped_call("tfra_multi_find_or_insert", _capi.FindOrInsertDesc, "find_or_insert_many", tables, fill)
+  return (outs, launches) if return_launches else outs
+
+
+def table_admit_many(requests):
+  """`find_or_insert_many` without outputs — the `_DeviceTable.admit` of a list of plain tables in one call.  `requests`: a list of
+  (owner, keys[, init_values[, count[, scores]]]), the arguments behind `owner` those of `_DeviceTable.admit`."""
+  def widen(r):
+    r = tuple(r) + (None, None, None)[len(r) - 2:]
+    return (r[0], r[1], r[2], r[3], False, r[4])
+  find_or_insert_many([widen(r) for r in requests])

@@ -143,7 +143,24 @@ class Variable:
   Several shards, more than 2^18 ids, no free plan, the sparse wrapper, or tiered shards: the True route.  (A tier has the planned
   lookup — `TieredHashTable.find_or_insert_planned` — but a step through it was measured 13.0 us below True's 206.6 with spreads that
   sum to 15.0, short of the margin, so the variable does not route to it: DESIGN 4.26.)  Measured (Adam, 131 072 Zipf ids, 10 %
-  never seen, us per step): False 153.5, True 159.1, True with plan_writeback 158.5, "plan" 134.5."""
+  never seen, us per step): False 153.5, True 159.1, True with plan_writeback 158.5, "plan" 134.5.
+
+  init_on_lookup="pooled": True for every predicate above and for the dense `embedding_lookup`; the TRAINING forms of the sparse
+  lookups (`embedding_lookup_sparse`, `safe_embedding_lookup_sparse`, `ragged_embedding_ops.*` and their `*_many` forms, with
+  return_trainable=True) of a variable with a callable initializer that meets `can_lookup_combined()`'s other conditions (one
+  shard, float32 / float16 / bfloat16, dim % 4 == 0, dim <= 256; not bp_v2, no max_norm) admit first and read once
+  (`can_admit_pooled`): the entry ids de-duplicated on the device with the count left there, ONE draw
+  initializer([n_entry_ids, dim]) whose row j belongs to unique id j, `admit` (find_or_insert with no rows handed back; over a
+  tiered shard `TieredHashTable.admit` with those rows), then the pooled read — no [U, dim] rows, nothing read on the host when
+  num_rows is given, and in the `*_many` forms ONE grouped admission (tfra_multi_find_or_insert) from ADMIT_MANY_MIN_TABLES plain
+  members on.  Non-training sparse lookups keep the chain and insert nothing (a miss is drawn and stays out: `_read_rows`; with
+  True the chain's `embedding_lookup` admits there too); several shards take the True route.
+  Limits: (1) with the chain the model sees a drawn row even for a key a full LFU / CUSTOMIZED table does not admit, or one a later
+  key of the same batch displaces; with "pooled" such a key reads as the table's static default row, and the write-back restarts
+  it from there — the existing limit of every fused write-back.  (2) A seeded random initializer draws [n_entry_ids, dim] here
+  against [U, dim] with True, so the two settings admit different rows for the same seed (as "plan" does).  (3) What is admitted
+  are the ENTRY ids, the safe form's entry for empty rows (default_id, or 0) among them, where the chain admits the looked-up ids.
+  (4) More entry ids than a tier's max_batch: the existing ValueError."""
 
   def __init__(self, key_dtype=torch.int64, value_dtype=torch.float32, dim=1, devices=None,
                partitioner=default_partition_fn, shared_name=None, name="DynamicEmbedding_Variable", initializer=None,
@@ -151,11 +168,11 @@ class Variable:
                short_file_name=False, aux_fields=0, aux_init=(0.0, 0.0, 0.0, 0.0), init_on_lookup=False):
     self.key_dtype = key_dtype
     if isinstance(init_on_lookup, str) or init_on_lookup not in (False, True):
-      if init_on_lookup != "plan":
-        raise ValueError("init_on_lookup must be False, True or \"plan\", got %r" % (init_on_lookup,))
+      if init_on_lookup not in ("plan", "pooled"):
+        raise ValueError("init_on_lookup must be False, True, \"plan\" or \"pooled\", got %r" % (init_on_lookup,))
     else:
       init_on_lookup = bool(init_on_lookup)
-    self.init_on_lookup = init_on_lookup   # (False, True or "plan": truthy means "the lookup admits" for every predicate)
+    self.init_on_lookup = init_on_lookup   # (False, True, "plan" or "pooled": truthy means "the lookup admits" for every predicate)
     self.value_dtype = value_dtype
     self.dim = int(dim)
     self.bp_v2 = bp_v2
@@ -393,6 +410,14 @@ class Variable:
     return (self.shard_num == 1 and not callable(self.initializer) and self.value_dtype in PLANNED_VALUE_DTYPES and
             self.dim % 4 == 0 and self.dim <= 256)
 
+  def can_admit_pooled(self):
+    """Whether a TRAINING sparse lookup of this variable takes the pooled route by admitting first (init_on_lookup="pooled"): a
+    callable initializer to draw the admitted rows from, and `can_lookup_combined()`'s other conditions.  (Without a callable
+    initializer `can_lookup_combined()` itself holds.)"""
+    from .optimizer import PLANNED_VALUE_DTYPES
+    return (self.init_on_lookup == "pooled" and callable(self.initializer) and self.shard_num == 1 and
+            self.value_dtype in PLANNED_VALUE_DTYPES and self.dim % 4 == 0 and self.dim <= 256)
+
   def lookup_combined(self, ids, seg, weights, combiner, n_rows, name=None):
     """The forward of embedding_lookup_sparse as one pooled read (tfra_table_find_combine): [n_rows, dim] float32,
     out[r] = combiner over the entries p with seg[p] == r, in input order, of weights[p] * (row of ids[p], the default row on a
@@ -406,23 +431,32 @@ class Variable:
     the safe form's entries for empty rows among them — de-duplicated on the device (`device_ops.unique_no_sync`) and admitted
     into the cache with the static default row (`TieredHashTable.admit`, the count left on the device).  A key from below comes
     up with its optimizer slots, a never-seen key enters as the write-back would have started it, so `apply_combined_gradients`
-    only hits.  Nothing is read on the host.  A variable without tiered shards: nothing to do.  More entry ids than the tier's
-    max_batch: ValueError."""
+    only hits.  Nothing is read on the host.  More entry ids than the tier's max_batch: ValueError.
+    An init_on_lookup="pooled" variable (`can_admit_pooled`), tiered or not, admits its entry ids the same way with ONE draw
+    initializer([n_entry_ids, dim]) in the place of the static default row, row j for unique id j (`_admission_rows`).  Any
+    other variable without tiered shards: nothing to do."""
     ids = self._admissible_entries(entry_ids)
     if ids is not None and ids.numel():
       t = self._tables[0]
       uniq, _, cnt = device_ops.unique_no_sync(ids)
-      t.admit(uniq, t._default_value, count=cnt)
+      t.admit(uniq, self._admission_rows(ids.numel()), count=cnt)
+
+  def _admission_rows(self, n):
+    """The init rows `admit_entries` admits n entry ids with: one draw of the initializer, [n, dim], for an init_on_lookup="pooled"
+    variable; else the shard's static default row."""
+    t = self._tables[0]
+    return self._create_default_values_by_initializer(n, t._device) if self.can_admit_pooled() else t._default_value
 
   def _admissible_entries(self, entry_ids):
-    """`admit_entries`' check, with nothing enqueued: the flat entry ids on the tiered shard's device (None: no tiered shards), or
-    its ValueError for more entry ids than the tier's max_batch.  The grouped forms run it for ALL their tiered members before the
-    first admission (`_check_entries_many`)."""
-    if not _has_tiered_shards(self):
+    """`admit_entries`' check, with nothing enqueued: the flat entry ids on the shard's device (None: neither tiered shards nor
+    `can_admit_pooled`), or its ValueError for more entry ids than the tier's max_batch.  The grouped forms run it for ALL their
+    members before the first admission (`_check_entries_many`)."""
+    tiered = _has_tiered_shards(self)
+    if not tiered and not self.can_admit_pooled():
       return None
     t = self._tables[0]
     ids = torch.as_tensor(entry_ids, device=t._device).reshape(-1)
-    if ids.numel() > t._tier.max_batch:
+    if tiered and ids.numel() > t._tier.max_batch:
       raise ValueError("a pooled training lookup over a tiered variable admits its entry ids in one call: %d entry ids exceed the "
                        "tier's max_batch (%d)" % (ids.numel(), t._tier.max_batch))
     return ids
@@ -430,7 +464,7 @@ class Variable:
   def _combined_operands(self, ids, ragged):
     """-> (the one shard, the flat ids on its device) of a pooled read — the forward or the weight gradient, over one table or a
     tier (`_pooled_reader` serves the shard) —; ValueError unless `can_lookup_combined()`."""
-    if not self.can_lookup_combined():
+    if not (self.can_lookup_combined() or self.can_admit_pooled()):
       raise ValueError("%s needs one shard, a static default row, float32 / float16 / bfloat16 rows, dim %% 4 == 0 and dim <= 256; "
                        "use %s" % (("lookup_combined_ragged", "ragged_embedding_ops.embedding_lookup_sparse") if ragged else
                                    ("lookup_combined", "embedding_lookup_sparse")))
@@ -733,6 +767,15 @@ def _release_plan(params, plan):
     pool["free"].append(plan)   # (its next build waits for the event of its last use: SparsePlan.build)
 
 
+def _clip_rows(result, max_norm):
+  """clip_by_norm over the embedding axis (None: as it is)"""
+  if max_norm is None:
+    return result
+  norm = result.to(torch.float32).norm(dim=-1, keepdim=True)
+  scale = max_norm / torch.maximum(norm, torch.full_like(norm, max_norm))
+  return (result * scale).to(result.dtype)
+
+
 class TrainableWrapper:
   """The local [N,dim] "shadow" of the rows of one lookup (PY/embedding_weights.py:38-540):
   refilled from the table on read (`prefetch_values`), written back by `update_op`."""
@@ -821,11 +864,7 @@ class TrainableWrapper:
 
   def transform(self, result):
     """PY/embedding_weights.py:497-521: optional clip_by_norm over the embedding axis."""
-    if self.max_norm is None:
-      return result
-    norm = result.to(torch.float32).norm(dim=-1, keepdim=True)
-    scale = self.max_norm / torch.maximum(norm, torch.full_like(norm, self.max_norm))
-    return (result * scale).to(result.dtype)
+    return _clip_rows(result, self.max_norm)
 
   def read_value(self):
     return self._values
@@ -940,7 +979,7 @@ class SparseTrainableWrapper(TrainableWrapper):
     if self._weights is None:
       raise ValueError("weights_grad needs a lookup made with sp_weights")
     g = self.check_grad_out(grad_out)
-    if self._pooled_ids is not None and _pooled_forward(self.params, None):
+    if self._pooled_ids is not None and _pooled_training(self.params, None):
       dw = self.params.lookup_combined_weight_grad(self._pooled_ids, self._seg, self._weights, self.combiner, g)
     else:
       rows = self.params.lookup(self.ids).to(torch.float32)
@@ -974,7 +1013,7 @@ def sparse_weights_grad_many(grads_and_wrappers):
   results = [None] * len(pairs)
   groups = {}   # device -> [i]
   for i, (grad_out, tw) in enumerate(pairs):
-    if tw._pooled_ids is not None and _pooled_forward(tw.params, None):
+    if tw._pooled_ids is not None and _pooled_training(tw.params, None):
       groups.setdefault(tw.params._primary, []).append(i)
     else:
       results[i] = tw.weights_grad(grad_out)
@@ -1035,6 +1074,22 @@ def _pooled_forward(params, max_norm):
   return max_norm is None and not params.bp_v2 and params.can_lookup_combined()
 
 
+def _read_rows(params, ids, max_norm):
+  """The rows of `ids` for a sparse lookup that is NOT a training step's (and for the safe form's default_id row): `embedding_lookup`
+  as it is — which, through its wrapper, admits for an init_on_lookup variable —, but for init_on_lookup="pooled" a read that
+  inserts nothing: a miss is drawn and stays out (the setting's training lookups have admitted what the write-back will touch)."""
+  if params.init_on_lookup == "pooled":
+    return _clip_rows(params.lookup(ids), max_norm)
+  return embedding_lookup(params, ids, max_norm=max_norm)
+
+
+def _pooled_training(params, max_norm):
+  """`_pooled_forward` for the TRAINING forms (return_trainable) and what reads through their wrappers: also a variable that
+  reaches the pooled read by admitting its entry ids with drawn rows first (init_on_lookup="pooled": `Variable.can_admit_pooled`).
+  The one predicate of every training call site."""
+  return _pooled_forward(params, max_norm) or (max_norm is None and not params.bp_v2 and params.can_admit_pooled())
+
+
 def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=None, name="embedding_lookup_sparse",
                             combiner="mean", max_norm=None, return_trainable=False, num_rows=None, plan_writeback=False,
                             _entries=None, _out_shape=None):
@@ -1050,7 +1105,7 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=
   seg = (indices[:, 0] if indices.dim() == 2 else indices).to(torch.int64)
   ids = torch.as_tensor(ids, device=params._primary)
   w = sp_weights if sp_weights is None else torch.as_tensor(sp_weights, dtype=torch.float32, device=params._primary)
-  pooled = _pooled_forward(params, max_norm)
+  pooled = _pooled_training(params, max_norm) if return_trainable else _pooled_forward(params, max_norm)
   if not pooled:
     uniq, idx, cnt = device_ops.unique(ids)
   n = int(seg.max().item()) + 1 if num_rows is None else num_rows
@@ -1060,7 +1115,8 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=
   if pooled:
     # the pooled read: one probe + row read per entry, combined in registers — no unique pass, no [U, dim] rows, no host read of
     # a count (the result is bit-identical to the chain below).  Over tiered shards a training step first brings its entry ids
-    # into the cache (`Variable.admit_entries`), and the read sees both tiers either way
+    # into the cache (`Variable.admit_entries`), and the read sees both tiers either way; an init_on_lookup="pooled" variable
+    # admits them with drawn rows there, which is what lets it read here at all
     if return_trainable:
       params.admit_entries(e_ids)
     out = params.lookup_combined(ids, seg, w, combiner, n)
@@ -1074,7 +1130,7 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=
     ue = tw.read_value()
   else:
     tw = None
-    ue = embedding_lookup(params, uniq, max_norm=max_norm)
+    ue = _read_rows(params, uniq, max_norm)
   # gather + weights + segment combine fused in one kernel (reads the unique rows through idx)
   out = device_ops.sparse_segment_combine(ue, idx, seg, w, combiner, n)
   return (out, tw) if return_trainable else out
@@ -1115,36 +1171,48 @@ def _check_entries_many(members):
 # tfra_tier_find_or_insert per member, which tests/test_gpu_tier_pooled_many.py holds: the chain that grows with the list is what
 # the grouped call is for, and from three tiers on it takes it.
 ADMIT_MANY_MIN_TIERS = 3
+# The same for the plain init_on_lookup="pooled" members and tfra_multi_find_or_insert, measured: with no never-seen
+# id in the batch three tables are level (19.2 against 19.9 us, inside the spreads) and four are the first list the grouped call wins
+# beyond the sum of both spreads (25.5 against 23.1 us); with a tenth never seen it is ahead from two on.
+ADMIT_MANY_MIN_TABLES = 4
 
 
 def _admit_entries_many(params_list, entry_ids):
   """Ahead of the ONE grouped read of a training step: `Variable.admit_entries(entry_ids[i])` for every member i of `entry_ids`
-  (index -> the entry ids its wrapper will write back; a member without tiered shards: nothing).  Admission moves rows between
-  the tiers and never changes them, so the one read behind all admissions returns what a read behind each would.  The members
-  (of one device) whose tiers are distinct are admitted by ONE grouped call (`table_ops.admit_many`:
+  (index -> the entry ids its wrapper will write back; a member that is neither tiered nor init_on_lookup="pooled": nothing).
+  Admission moves rows between the tiers and never changes them, so the one read behind all admissions returns what a read behind
+  each would.  The members (of one device) whose tiers are distinct are admitted by ONE grouped call (`table_ops.admit_many`:
   tfra_multi_tier_find_or_insert, whose launch count does not grow with the list) when there are ADMIT_MANY_MIN_TIERS of them or
   more, each member's entry ids de-duplicated on the device first as `admit_entries` does; a tier that stands in the list again
   has its later occurrences admitted by the single call behind the grouped one — the order of the loop of single calls.  A
-  shorter list keeps the loop of `admit_entries`."""
-  first, later, seen = [], [], set()
+  shorter list keeps the loop of `admit_entries`.
+  The plain (not tiered) init_on_lookup="pooled" members go the same way through `table_ops.table_admit_many`
+  (tfra_multi_find_or_insert) from ADMIT_MANY_MIN_TABLES distinct tables on, each with its own draw (`Variable._admission_rows`);
+  the draws are made in the list's order whichever call admits them."""
+  first, later, seen = {True: [], False: []}, [], set()   # tiered -> [(params, flat)]
   for i, ids in entry_ids.items():
     params = params_list[i]
     flat = params._admissible_entries(ids)
     if flat is None or not flat.numel():
       continue
-    tier = params._tables[0]._tier
-    (later if id(tier) in seen else first).append((params, flat))
-    seen.add(id(tier))
-  if len(first) < ADMIT_MANY_MIN_TIERS:
-    for params, flat in first:
-      params.admit_entries(flat)
-  else:
+    tiered = _has_tiered_shards(params)
+    owner = params._tables[0]._tier if tiered else params._tables[0]._table
+    (later if id(owner) in seen else first[tiered]).append((params, flat))
+    seen.add(id(owner))
+  for tiered, least, many in ((True, ADMIT_MANY_MIN_TIERS, table_ops.admit_many), (False, ADMIT_MANY_MIN_TABLES, table_ops.table_admit_many)):
+    if len(first[tiered]) < least:
+      for params, flat in first[tiered]:
+        params.admit_entries(flat)
+      continue
     reqs = []
-    for params, flat in first:
+    for params, flat in first[tiered]:
       t = params._tables[0]
       uniq, _, cnt = device_ops.unique_no_sync(flat)
-      reqs.append((t, uniq, t._default_value, cnt))
-    table_ops.admit_many(reqs)
+      if tiered:
+        reqs.append((t, uniq, params._admission_rows(flat.numel()), cnt))
+      else:   # (the scores `admit` of the shard would pass: `_gen_scores`)
+        reqs.append((t, uniq, params._admission_rows(flat.numel()), cnt, t._gen_scores(uniq)))
+    many(reqs)
   for params, flat in later:
     params.admit_entries(flat)
 
@@ -1184,12 +1252,13 @@ def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None,
   for c in combiners:
     _check_combiner(c)
   results = [None] * n_t
+  pooled = _pooled_training if return_trainable else _pooled_forward
   if return_trainable:
     _check_entries_many([(p, entries[i][0] if entries[i] is not None else sp_ids_list[i][1])
-                         for i, p in enumerate(params_list) if _pooled_forward(p, max_norm)])
+                         for i, p in enumerate(params_list) if pooled(p, max_norm)])
   groups = {}   # device -> [(i, ids, seg, w)]
   for i, params in enumerate(params_list):
-    if not _pooled_forward(params, max_norm):
+    if not pooled(params, max_norm):
       results[i] = embedding_lookup_sparse(params, sp_ids_list[i], weights[i], combiner=combiners[i], max_norm=max_norm,
                                            return_trainable=return_trainable, num_rows=rows[i], plan_writeback=plan_writeback,
                                            _entries=entries[i], _out_shape=shapes[i])
@@ -1293,8 +1362,7 @@ def _safe_sparse_finish(params, res, rows, n, default_id, max_norm, lead):
   if default_id is not None and n:
     empty = torch.ones(n, dtype=torch.bool, device=res.device)
     empty[rows] = False
-    d = embedding_lookup(params, torch.tensor([default_id], dtype=params.key_dtype, device=params._primary),
-                         max_norm=max_norm).to(torch.float32)
+    d = _read_rows(params, torch.tensor([default_id], dtype=params.key_dtype, device=params._primary), max_norm).to(torch.float32)
     res = torch.where(empty[:, None], d, res)
   if lead is not None:
     res = res.reshape(tuple(lead) + (res.shape[-1],))
