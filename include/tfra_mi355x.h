@@ -709,6 +709,32 @@ int tfra_unique(tfra_workspace_t* ws, size_t n, const int64_t* ids, int64_t* uni
 int tfra_unique_unordered(tfra_workspace_t* ws, size_t n, const int64_t* ids, int64_t* unique_out,
                           int32_t* idx_out, int64_t* d_num_unique, tfra_stream_t stream);
 
+/* tfra_unique of a LIST of id lists as ONE stream-ordered chain: for descriptor d, unique_out[0 .. *d_num_unique),
+ * idx_out and *d_num_unique hold exactly what tfra_unique(ws, n, ids, unique_out, idx_out, d_num_unique, stream) writes — the
+ * distinct ids in order of first occurrence, the position of every id among them, the count on the device.  The lists are
+ * independent: an id that stands in two lists is distinct in each.  unique_out[*d_num_unique .. n) is unspecified.  Deterministic.
+ * Enqueues: one upload of the records (the workspace's ring of pinned, event-guarded slots), then one insert launch over all lists'
+ * ids, one scatter launch over all lists' tiles (it writes every list's count, 0 for a list with n == 0, whose other pointers may
+ * be NULL) and one index launch, which is left out when no descriptor has an idx_out: 3 launches, or 2, whatever n_lists.
+ * *launches_out (optional, host): the kernel launches enqueued; 0 when the call is refused or has nothing to do.
+ * Every check runs before anything is enqueued: a refused call writes nothing.  TFRA_ERR_INVALID, naming the descriptor: a
+ * struct_size other than sizeof, flags != 0, d_num_unique NULL, ids or unique_out NULL where n > 0, a list longer than 2^20 ids,
+ * lists that total more than 2^22 ids, output ranges (unique_out, idx_out, d_num_unique) of different descriptors that overlap.
+ * The same ids may stand in several descriptors.  The call keeps persistent sets of its own in the workspace, apart from
+ * tfra_unique's: the two may be interleaved freely.  Synchronises nothing.  Not for stream capture.
+ *                                                                                        (tests/test_gpu_unique_many.py) */
+typedef struct {
+  uint32_t struct_size;      /* = sizeof(tfra_unique_desc) */
+  uint32_t flags;            /* 0 */
+  size_t n;                  /* ids in this list; 0 is allowed */
+  const int64_t* ids;        /* [n] */
+  int64_t* unique_out;       /* [n] */
+  int32_t* idx_out;          /* [n], or NULL: this list's inverse index is not wanted */
+  int64_t* d_num_unique;     /* device int64 scalar */
+} tfra_unique_desc;
+int tfra_multi_unique(tfra_workspace_t* ws, size_t n_lists, const tfra_unique_desc* descs, uint32_t* launches_out /* optional, host */,
+                      tfra_stream_t stream);
+
 /* Find of all n ids AND tfra_unique_unordered of the same ids in ONE launch — the forward half of embedding_lookup as the fused TF op
  * TFRA>HkvHashTableEmbeddingLookup issues it (tf_ops/fused_ops_rocm.cc; PY/dynamic_embedding_ops.py:99-117 needs the rows of every id,
  * the distinct ids and the inverse index for the backward pass).  rows_out / exists / defaults / default_is_full as tfra_table_find,

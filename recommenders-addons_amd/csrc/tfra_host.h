@@ -266,6 +266,14 @@ struct tfra_workspace {
   hipStream_t unq_stream = nullptr;
   bool unq_stream_set = false;
   hipEvent_t unq_ev = nullptr;
+  // tfra_multi_unique (tfra_unique_many.hip): the same state once more, of its own — two sets of unqm_slots slots that the call's
+  // lists share as sub-sets, room for unqm_nmax ids and unqm_tiles scatter tiles in all; tfra_unique's sets above are not touched by it
+  void* unqm_buf = nullptr;
+  size_t unqm_slots = 0, unqm_nmax = 0, unqm_tiles = 0;
+  unsigned unqm_parity = 0, unqm_gen = 0;
+  hipStream_t unqm_stream = nullptr;
+  bool unqm_stream_set = false;
+  hipEvent_t unqm_ev = nullptr;
   void* many = nullptr;   // pinned staging ring of the grouped calls' descriptor records (ManyStage, tfra_many.h)
   int ensure(size_t need, hipStream_t s) {
     if (need <= bytes) return TFRA_OK;

@@ -136,6 +136,14 @@ class FindOrInsertDesc(ctypes.Structure):
   ]
 
 
+class UniqueDesc(ctypes.Structure):
+  """tfra_unique_desc (include/tfra_mi355x.h): one id list's de-duplication in tfra_multi_unique."""
+  _fields_ = [
+      ("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("n", ctypes.c_size_t), ("ids", ctypes.c_void_p),
+      ("unique_out", ctypes.c_void_p), ("idx_out", ctypes.c_void_p), ("d_num_unique", ctypes.c_void_p),
+  ]
+
+
 class FindCombineWgradDesc(ctypes.Structure):
   """tfra_find_combine_wgrad_desc (include/tfra_mi355x.h): the weight gradient of one tier's or one table's pooled lookup in
   tfra_multi_find_combine_backprop_weights; exactly one of table / tier is set."""
@@ -274,6 +282,7 @@ _SIGS = {
     "tfra_workspace_destroy": [_P],
     "tfra_unique": [_P, _SZ, _P, _P, _P, _P, _P],
     "tfra_unique_unordered": [_P, _SZ, _P, _P, _P, _P, _P],
+    "tfra_multi_unique": [_P, _SZ, _P, _P, _P],
     "tfra_table_find_unique": [_P, _P, _SZ, _P, _P, _P, _P, _I, _P, _P, _P, _P],
     "tfra_table_find_combine": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, _P, _P],
     "tfra_multi_find_combine": [_P, _SZ, _P, _P, _P],

@@ -55,6 +55,66 @@ def unique_no_sync(ids):
   return _narrow_keys(uniq, ids.dtype), idx, cnt
 
 
+UNIQUE_MANY_MAX_LIST = 1 << 20    # tfra_multi_unique's bounds (include/tfra_mi355x.h): ids in one list,
+UNIQUE_MANY_MAX_TOTAL = 1 << 22   # ids in all lists of a call
+
+
+def _round_up(n, to):
+  return (n + to - 1) // to * to
+
+
+def unique_many(ids_list, want_idx=True, return_launches=False):
+  """`unique_no_sync` of a LIST of id tensors in ONE C call (tfra_multi_unique: one insert, one scatter and one index launch over
+  all lists, whatever their number).  Returns the list of (uniq, idx, cnt), member i what `unique_no_sync(ids_list[i])` returns:
+  the full-length buffer of distinct ids in first-occurrence order in the dtype of the member's ids (int32 ids widened in front
+  of the call and narrowed behind it, per member), the int32 inverse index, the count as a device scalar; nothing is read on the
+  host.  The lists are independent.  want_idx=False: every `idx` is None and the index launch is left out (two launches: all
+  admission needs).  All lists must live on one device (ValueError); the workspace is the one of
+  that device's current stream.  The members' buffers are views of one allocation per kind.  A list beyond the call's limits
+  (UNIQUE_MANY_MAX_LIST ids in one member, UNIQUE_MANY_MAX_TOTAL in all) takes the loop of `unique_no_sync`.
+  return_launches: also the number of kernel launches of the de-duplication itself."""
+  n_l = len(ids_list)
+  if n_l == 0:
+    return ([], 0) if return_launches else []
+  dev = ids_list[0].device
+  for ids in ids_list:
+    if ids.device != dev:
+      raise ValueError("unique_many: all lists must live on one device (%s and %s)" % (dev, ids.device))
+  sizes = [ids.numel() for ids in ids_list]
+  if max(sizes) > UNIQUE_MANY_MAX_LIST or sum(sizes) > UNIQUE_MANY_MAX_TOTAL:
+    res = [unique_no_sync(ids) for ids in ids_list]
+    res = [(u, i if want_idx else None, c) for u, i, c in res]
+    return (res, sum(0 if n == 0 else 3 if n <= (1 << 20) else 6 for n in sizes)) if return_launches else res
+  flats = [_wide_keys(ids.reshape(-1)) for ids in ids_list]
+  # one allocation per kind; every member's view starts on a 512-byte boundary, as a tensor of its own would
+  u_at, i_at, u_end, i_end = [], [], 0, 0
+  for n in sizes:
+    u_at.append(u_end)
+    u_end += _round_up(n, 64)
+    i_at.append(i_end)
+    i_end += _round_up(n, 128) if want_idx else 0
+  uniq_all = torch.empty(u_end, dtype=torch.int64, device=dev)
+  idx_all = torch.empty(i_end, dtype=torch.int32, device=dev)
+  cnt_all = torch.empty(n_l, dtype=torch.int64, device=dev)   # (the call writes every count, 0 for an empty list)
+  descs = (_capi.UniqueDesc * n_l)()
+  res = []
+  for k, (flat, n) in enumerate(zip(flats, sizes)):
+    uniq = uniq_all[u_at[k]:u_at[k] + n]
+    idx = idx_all[i_at[k]:i_at[k] + n] if want_idx else None
+    cnt = cnt_all[k]
+    e = descs[k]
+    e.struct_size, e.flags, e.n = ctypes.sizeof(_capi.UniqueDesc), 0, n
+    e.ids, e.unique_out = (flat.data_ptr(), uniq.data_ptr()) if n else (None, None)
+    e.idx_out = idx.data_ptr() if (want_idx and n) else None
+    e.d_num_unique = cnt.data_ptr()
+    res.append((uniq, idx, cnt))
+  launches = ctypes.c_uint32(0)
+  _capi.call("tfra_multi_unique", _workspace(dev), n_l, ctypes.c_void_p(ctypes.addressof(descs)),
+             ctypes.c_void_p(ctypes.addressof(launches)), _stream(dev))
+  res = [(_narrow_keys(u, ids.dtype), i, c) for (u, i, c), ids in zip(res, ids_list)]
+  return (res, int(launches.value)) if return_launches else res
+
+
 def gather_rows(rows, idx):
   """out[i,:] = rows[idx[i],:]  (tf.gather after unique, PY/dynamic_embedding_ops.py:111)."""
   rows = rows.contiguous()

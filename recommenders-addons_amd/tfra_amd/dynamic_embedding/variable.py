@@ -1183,7 +1183,8 @@ def _admit_entries_many(params_list, entry_ids):
   Admission moves rows between the tiers and never changes them, so the one read behind all admissions returns what a read behind
   each would.  The members (of one device) whose tiers are distinct are admitted by ONE grouped call (`table_ops.admit_many`:
   tfra_multi_tier_find_or_insert, whose launch count does not grow with the list) when there are ADMIT_MANY_MIN_TIERS of them or
-  more, each member's entry ids de-duplicated on the device first as `admit_entries` does; a tier that stands in the list again
+  more, each member's entry ids de-duplicated on the device first as `admit_entries` does — for all members of the grouped
+  admissions, tiered and plain, by ONE grouped call (`device_ops.unique_many`: tfra_multi_unique) —; a tier that stands in the list again
   has its later occurrences admitted by the single call behind the grouped one — the order of the loop of single calls.  A
   shorter list keeps the loop of `admit_entries`.
   The plain (not tiered) init_on_lookup="pooled" members go the same way through `table_ops.table_admit_many`
@@ -1199,7 +1200,12 @@ def _admit_entries_many(params_list, entry_ids):
     owner = params._tables[0]._tier if tiered else params._tables[0]._table
     (later if id(owner) in seen else first[tiered]).append((params, flat))
     seen.add(id(owner))
-  for tiered, least, many in ((True, ADMIT_MANY_MIN_TIERS, table_ops.admit_many), (False, ADMIT_MANY_MIN_TABLES, table_ops.table_admit_many)):
+  kinds = ((True, ADMIT_MANY_MIN_TIERS, table_ops.admit_many), (False, ADMIT_MANY_MIN_TABLES, table_ops.table_admit_many))
+  # the unique ids of ALL members that take a grouped admission, tiered and plain together: one grouped de-duplication
+  # (tfra_multi_unique; admission has no use for the inverse index) ahead of both admissions
+  grouped = [flat for tiered, least, _ in kinds if len(first[tiered]) >= least for _, flat in first[tiered]]
+  uniques = iter(device_ops.unique_many(grouped, want_idx=False))
+  for tiered, least, many in kinds:
     if len(first[tiered]) < least:
       for params, flat in first[tiered]:
         params.admit_entries(flat)
@@ -1207,7 +1213,7 @@ def _admit_entries_many(params_list, entry_ids):
     reqs = []
     for params, flat in first[tiered]:
       t = params._tables[0]
-      uniq, _, cnt = device_ops.unique_no_sync(flat)
+      uniq, _, cnt = next(uniques)
       if tiered:
         reqs.append((t, uniq, params._admission_rows(flat.numel()), cnt))
       else:   # (the scores `admit` of the shard would pass: `_gen_scores`)
