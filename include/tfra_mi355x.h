@@ -735,6 +735,52 @@ typedef struct {
 int tfra_multi_unique(tfra_workspace_t* ws, size_t n_lists, const tfra_unique_desc* descs, uint32_t* launches_out /* optional, host */,
                       tfra_stream_t stream);
 
+/* The entry lists of a LIST of safe sparse lookups, built on the device as ONE stream-ordered chain: what the
+ * training form of safe_embedding_lookup_sparse hands its wrapper.  A descriptor is one lookup: nnz entries (ids[p], weights[p]) of
+ * n_rows rows; the row of entry p is rows[p] (ascending), or with TFRA_SAFE_RAGGED the r with rows[r] <= p < rows[r + 1]
+ * (rows = row_splits [n_rows + 1], non-decreasing).  Entry p is a MEMBER when its row lies in [0, n_rows) and — TFRA_SAFE_PRUNE
+ * with weights given — weights[p] > 0 (a NaN is no member); an entry whose row lies outside is in neither list.
+ *   kept list:  the members in input order, (ids[p], row, weights[p]); kept_weights is not written when weights == NULL.
+ *   entry list: sorted by row; a row with members contributes them in input order with weight weights ? weights[p] : 1.0f, a row
+ *               without members ONE entry (fill_id, r, 1.0f) with TFRA_SAFE_FILL, else (0, r, 0.0f).
+ *   d_counts:   the kept count and the entry count, always written (n_rows == 0: both 0; nnz == 0: the entry list is the fillers).
+ * Nothing at or beyond a count is specified, and nothing is ever written outside [0, nnz) of the kept buffers or
+ * [0, nnz + n_rows) of the entry buffers — also where rows are not ascending or splits not non-decreasing, whose lists are then
+ * unspecified.  The kept group is kept_ids and kept_rows, with kept_weights where weights are given: all or none.  The entry
+ * group is entry_ids and entry_rows, entry_weights optional.  Neither group: the counts alone.  Deterministic.
+ * Enqueues: one upload of the records (the workspace's ring of pinned, event-guarded slots), then per tile of 1024 the members'
+ * counts and their scan for the lists that prune, the rows' bounds and member-less flags, their scan (it writes d_counts) and the
+ * scatter: at most 5 launches, 3 when no list prunes, whatever n_lists; no block waits for another; scratch is the workspace's.
+ * *launches_out (optional, host): the kernel launches enqueued; 0 when the call is refused or n_lists == 0 (TFRA_OK).
+ * Every check runs before anything is enqueued: a refused call writes nothing.  TFRA_ERR_INVALID, naming the descriptor: a
+ * struct_size other than sizeof, unknown flag bits, d_counts NULL, rows NULL where n_rows > 0 and (nnz > 0 or RAGGED), ids NULL
+ * where n_rows > 0, nnz > 0 and a group is given, a half-given group, an int64 buffer that is not 8-byte or a float buffer that
+ * is not 4-byte aligned, output ranges (the groups' buffers, d_counts) that overlap; descs NULL with n_lists > 0.
+ * TFRA_ERR_UNSUPPORTED: nnz + n_rows >= 2^31 in one list, more than 2^24 entries plus rows in all lists.
+ * Synchronises nothing.                                                                 (tests/test_gpu_safe_entries.py) */
+#define TFRA_SAFE_PRUNE  1u  /* with weights: an entry is a member only if weights[p] > 0 (NaN: no member) */
+#define TFRA_SAFE_FILL   2u  /* an empty row's entry is (fill_id, weight 1); without the flag (0, weight 0) */
+#define TFRA_SAFE_RAGGED 4u  /* rows = row_splits [n_rows + 1] instead of ascending row ids [nnz] */
+typedef struct {
+  uint32_t struct_size;      /* = sizeof(tfra_safe_entries_desc) */
+  uint32_t flags;            /* TFRA_SAFE_* */
+  size_t n_rows;
+  size_t nnz;
+  const int64_t* rows;       /* [nnz] ascending row ids, or (RAGGED) row_splits [n_rows + 1] */
+  const int64_t* ids;        /* [nnz] */
+  const float* weights;      /* [nnz], or NULL */
+  int64_t fill_id;
+  int64_t* kept_ids;         /* [nnz] */
+  int64_t* kept_rows;        /* [nnz] */
+  float* kept_weights;       /* [nnz] */
+  int64_t* entry_ids;        /* [nnz + n_rows] */
+  int64_t* entry_rows;       /* [nnz + n_rows] */
+  float* entry_weights;      /* [nnz + n_rows], or NULL */
+  int64_t* d_counts;         /* device int64[2]: kept count, entry count */
+} tfra_safe_entries_desc;
+int tfra_multi_safe_entries(tfra_workspace_t* ws, size_t n_lists, const tfra_safe_entries_desc* descs,
+                            uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
+
 /* Find of all n ids AND tfra_unique_unordered of the same ids in ONE launch — the forward half of embedding_lookup as the fused TF op
  * TFRA>HkvHashTableEmbeddingLookup issues it (tf_ops/fused_ops_rocm.cc; PY/dynamic_embedding_ops.py:99-117 needs the rows of every id,
  * the distinct ids and the inverse index for the backward pass).  rows_out / exists / defaults / default_is_full as tfra_table_find,

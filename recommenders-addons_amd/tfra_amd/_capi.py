@@ -144,6 +144,20 @@ class UniqueDesc(ctypes.Structure):
   ]
 
 
+class SafeEntriesDesc(ctypes.Structure):
+  """tfra_safe_entries_desc (include/tfra_mi355x.h): one safe lookup's kept list and entry list in tfra_multi_safe_entries."""
+  _fields_ = [
+      ("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("n_rows", ctypes.c_size_t), ("nnz", ctypes.c_size_t),
+      ("rows", ctypes.c_void_p), ("ids", ctypes.c_void_p), ("weights", ctypes.c_void_p), ("fill_id", ctypes.c_int64),
+      ("kept_ids", ctypes.c_void_p), ("kept_rows", ctypes.c_void_p), ("kept_weights", ctypes.c_void_p),
+      ("entry_ids", ctypes.c_void_p), ("entry_rows", ctypes.c_void_p), ("entry_weights", ctypes.c_void_p),
+      ("d_counts", ctypes.c_void_p),
+  ]
+
+
+SAFE_PRUNE, SAFE_FILL, SAFE_RAGGED = 1, 2, 4   # TFRA_SAFE_*
+
+
 class FindCombineWgradDesc(ctypes.Structure):
   """tfra_find_combine_wgrad_desc (include/tfra_mi355x.h): the weight gradient of one tier's or one table's pooled lookup in
   tfra_multi_find_combine_backprop_weights; exactly one of table / tier is set."""
@@ -283,6 +297,7 @@ _SIGS = {
     "tfra_unique": [_P, _SZ, _P, _P, _P, _P, _P],
     "tfra_unique_unordered": [_P, _SZ, _P, _P, _P, _P, _P],
     "tfra_multi_unique": [_P, _SZ, _P, _P, _P],
+    "tfra_multi_safe_entries": [_P, _SZ, _P, _P, _P],
     "tfra_table_find_unique": [_P, _P, _SZ, _P, _P, _P, _P, _I, _P, _P, _P, _P],
     "tfra_table_find_combine": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, _P, _P],
     "tfra_multi_find_combine": [_P, _SZ, _P, _P, _P],

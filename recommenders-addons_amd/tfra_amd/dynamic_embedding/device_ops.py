@@ -115,6 +115,110 @@ def unique_many(ids_list, want_idx=True, return_launches=False):
   return (res, int(launches.value)) if return_launches else res
 
 
+SAFE_ENTRIES_MAX_LIST = 1 << 31    # tfra_multi_safe_entries' bounds (include/tfra_mi355x.h): nnz + n_rows of one list stays below,
+SAFE_ENTRIES_MAX_TOTAL = 1 << 24   # entries plus rows of all lists of a call
+
+
+def safe_entries_fit(sizes):
+  """Whether lists of these (nnz, n_rows) fit one tfra_multi_safe_entries call."""
+  return (all(nnz + n < SAFE_ENTRIES_MAX_LIST for nnz, n in sizes) and sum(nnz + n for nnz, n in sizes) <= SAFE_ENTRIES_MAX_TOTAL)
+
+
+def _read_counts(counts):
+  """The ONE host read of `safe_entries_many`: every list's two counts."""
+  return counts.cpu().tolist()
+
+
+def safe_entries_many(requests, want_kept=True, want_entries=True, return_launches=False):
+  """The kept list and the entry list of a LIST of safe sparse lookups in ONE C call (tfra_multi_safe_entries: at most five
+  launches, whatever the number of lists) and ONE host read: the `.cpu()` of the call's [n_lists, 2] counts.  A request is
+  (rows, ids, weights, n_rows, prune, fill_id, ragged): `rows` int64 ascending row ids [nnz] or — ragged — row_splits
+  [n_rows + 1]; `ids` int64 or int32 [nnz]; `weights` float32 [nnz] or None; `prune`: only entries with weight > 0 are members;
+  `fill_id`: the id of a member-less row's entry (weight 1), None: id 0 with weight 0.  All on one device (ValueError).
+  Returns per request (kept, entries), each (ids, rows, weights) trimmed to its count or None where it was not asked for:
+  kept = the members in input order (weights None where none were given), entries = the members and one entry per member-less row
+  in row order (weights None where none were given and fill_id is not None: they would all be 1).  ids come back in the dtype
+  they were given in (int32 ids widened in front of the call and narrowed behind it).  want_kept / want_entries: a bool, or one
+  per request.  Lists beyond the call's limits raise ValueError (`safe_entries_fit`).
+  return_launches: also the number of kernel launches of the builder itself."""
+  n_l = len(requests)
+  if n_l == 0:
+    return ([], 0) if return_launches else []
+  kept_of = list(want_kept) if isinstance(want_kept, (list, tuple)) else [bool(want_kept)] * n_l
+  ent_of = list(want_entries) if isinstance(want_entries, (list, tuple)) else [bool(want_entries)] * n_l
+  dev = requests[0][1].device
+  sizes = []
+  for rows, ids, w, n, prune, fill, ragged in requests:
+    for t in (rows, ids, w):
+      if t is not None and t.device != dev:
+        raise ValueError("safe_entries_many: all lists must live on one device (%s and %s)" % (dev, t.device))
+    nnz, n = ids.numel(), int(n)
+    if rows.numel() != (n + 1 if ragged else nnz) or (w is not None and w.numel() != nnz):
+      raise ValueError("safe_entries_many: rows %d, ids %d, weights %s for %d rows" %
+                       (rows.numel(), nnz, None if w is None else w.numel(), n))
+    sizes.append((nnz, n))
+  if not safe_entries_fit(sizes):
+    raise ValueError("safe_entries_many: the lists are beyond one call's limits")
+  # one allocation per kind; every member's view starts on a 512-byte boundary, as a tensor of its own would
+  i_end = f_end = 0
+  at = []
+  for k, (nnz, n) in enumerate(sizes):
+    has_w = requests[k][2] is not None
+    ent_w = ent_of[k] and (has_w or requests[k][5] is None)
+    spans = [nnz if kept_of[k] else 0] * 2 + [nnz + n if ent_of[k] else 0] * 2
+    offs = []
+    for span in spans:
+      offs.append(i_end)
+      i_end += _round_up(span, 64)
+    for span in (nnz if (kept_of[k] and has_w) else 0, nnz + n if ent_w else 0):
+      offs.append(f_end)
+      f_end += _round_up(span, 128)
+    at.append((offs, has_w, ent_w))
+  i_all = torch.empty(i_end, dtype=torch.int64, device=dev)
+  f_all = torch.empty(f_end, dtype=torch.float32, device=dev)
+  counts = torch.empty((n_l, 2), dtype=torch.int64, device=dev)   # (the call writes every count)
+  descs = (_capi.SafeEntriesDesc * n_l)()
+  hold, views = [], []
+  for k, ((rows, ids, w, _, prune, fill, ragged), (nnz, n)) in enumerate(zip(requests, sizes)):
+    offs, has_w, ent_w = at[k]
+    rows = rows.reshape(-1).to(torch.int64).contiguous()
+    flat = _wide_keys(ids.reshape(-1))
+    w = None if w is None else w.reshape(-1).contiguous()
+    hold.append((rows, flat, w))
+    e = descs[k]
+    e.struct_size, e.n_rows, e.nnz = ctypes.sizeof(_capi.SafeEntriesDesc), n, nnz
+    e.flags = ((_capi.SAFE_PRUNE if prune else 0) | (_capi.SAFE_FILL if fill is not None else 0) |
+               (_capi.SAFE_RAGGED if ragged else 0))
+    e.rows, e.ids, e.weights = rows.data_ptr() if rows.numel() else None, flat.data_ptr() if nnz else None, _ptr(w) if nnz else None
+    e.fill_id = 0 if fill is None else int(fill)
+    v = [None] * 6
+    if kept_of[k]:
+      v[0], v[1] = i_all[offs[0]:offs[0] + nnz], i_all[offs[1]:offs[1] + nnz]
+      v[4] = f_all[offs[4]:offs[4] + nnz] if has_w else None
+      # (an empty view has no address of its own: any aligned one serves a buffer of no elements)
+      e.kept_ids, e.kept_rows = i_all.data_ptr() + 8 * offs[0], i_all.data_ptr() + 8 * offs[1]
+      e.kept_weights = f_all.data_ptr() + 4 * offs[4] if (has_w and nnz) else None
+    if ent_of[k]:
+      v[2], v[3] = i_all[offs[2]:offs[2] + nnz + n], i_all[offs[3]:offs[3] + nnz + n]
+      v[5] = f_all[offs[5]:offs[5] + nnz + n] if ent_w else None
+      e.entry_ids, e.entry_rows = i_all.data_ptr() + 8 * offs[2], i_all.data_ptr() + 8 * offs[3]
+      e.entry_weights = f_all.data_ptr() + 4 * offs[5] if ent_w else None
+    e.d_counts = counts.data_ptr() + 16 * k
+    views.append(v)
+  launches = ctypes.c_uint32(0)
+  _capi.call("tfra_multi_safe_entries", _workspace(dev), n_l, ctypes.c_void_p(ctypes.addressof(descs)),
+             ctypes.c_void_p(ctypes.addressof(launches)), _stream(dev))
+  host = _read_counts(counts)
+  res = []
+  for k, v in enumerate(views):
+    nk, ne = host[k]
+    dt = requests[k][1].dtype
+    kept = (_narrow_keys(v[0][:nk], dt), v[1][:nk], None if v[4] is None else v[4][:nk]) if kept_of[k] else None
+    ent = (_narrow_keys(v[2][:ne], dt), v[3][:ne], None if v[5] is None else v[5][:ne]) if ent_of[k] else None
+    res.append((kept, ent))
+  return (res, int(launches.value)) if return_launches else res
+
+
 def gather_rows(rows, idx):
   """out[i,:] = rows[idx[i],:]  (tf.gather after unique, PY/dynamic_embedding_ops.py:111)."""
   rows = rows.contiguous()

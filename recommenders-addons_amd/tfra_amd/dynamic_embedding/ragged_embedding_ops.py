@@ -15,14 +15,15 @@ to the tuple-form functions of `tfra_amd.dynamic_embedding` on the row ids the s
 A variable the pooled forward does not serve (several shards, a callable initializer, dim % 4 != 0 or dim > 256, other value
 dtypes, bp_v2) is handed to the tuple-form function with row ids derived from row_splits on the device: no input is refused.
 
-Training: return_trainable=True returns the tuple form's SparseTrainableWrapper, built behind the ragged forward.  Only the
-FORWARD of a safe trainable lookup is sync-free: the wrapper's entry list (pruned entries dropped, one entry per empty row) is
-made by the tuple form's preprocessing as it is, host syncs included."""
+Training: return_trainable=True returns the tuple form's SparseTrainableWrapper, built behind the ragged forward.  The wrapper's
+entry list of a safe lookup (pruned entries dropped, one entry per empty row) is built on the device from row_splits as they are
+(`device_ops.safe_entries_many`: one call, and ONE host read of the lists' lengths, which the write-back plan needs on the host);
+the forward itself reads nothing."""
 import torch
 
 from . import device_ops, table_ops
 from .variable import (SparseTrainableWrapper, _admit_entries_many, _check_combiner, _check_entries_many, _note_pruned, _per_table,
-                       _pooled_forward, _pooled_reader, _pooled_training, _safe_sparse_args, _wrap_grouped)
+                       _pooled_forward, _pooled_reader, _pooled_training, _safe_sparse_args, _safe_sparse_args_many, _wrap_grouped)
 from . import variable as _tuple_form
 
 
@@ -63,12 +64,13 @@ def _plain_wrapper(params, rs, ids, w, combiner, n, plan_writeback, entry_plan=N
                                 plan_writeback=plan_writeback, lookup_ids=ids, entry_plan=entry_plan)
 
 
-def _safe_entries(params, rs, ids, w, combiner, default_id, n):
-  """What the tuple form's safe lookup hands its wrapper: `_safe_sparse_args` on the derived row ids, as it is (host syncs
-  included)."""
-  rows, p_ids, p_w, _, entries, out_shape, _ = _safe_sparse_args(params, (row_ids_of(rs, ids.numel()), ids), w, combiner, default_id,
-                                                                 True, n)
-  return rows, p_ids, p_w, entries, out_shape
+def _safe_entries_many(params_list, members, combiners, default_ids):
+  """What the tuple form's safe lookup hands its wrapper — `_safe_sparse_args` on the row ids the splits stand for — for every
+  member (i, row_splits, ids, w): one builder call and one host read per device, the splits passed as they are.  i -> the lists."""
+  made = _safe_sparse_args_many([params_list[m[0]] for m in members], [(m[1], m[2]) for m in members], [m[3] for m in members],
+                                [combiners[m[0]] for m in members], [default_ids[m[0]] for m in members], True,
+                                [m[1].numel() - 1 for m in members], ragged=True)
+  return {m[0]: (rows, p_ids, p_w, entries, out_shape) for m, (rows, p_ids, p_w, _, entries, out_shape, _) in zip(members, made)}
 
 
 def _safe_wrapper(params, args, combiner, n, plan_writeback, entry_plan=None, caller_weights=None):
@@ -107,9 +109,8 @@ def safe_embedding_lookup_sparse(params, sparse_ids, sparse_weights=None, combin
   zeros, or the embedding of `default_id`.  Bit-identical to the tuple form on (row ids, values), in one launch and with no
   host synchronisation: the pruning and the default row are the kernel's.
 
-  return_trainable: also returns the SparseTrainableWrapper; its entry list comes from the tuple form's preprocessing
-  (`_safe_sparse_args`) on the derived row ids, which reads on the host — only the forward of a safe trainable lookup is
-  sync-free."""
+  return_trainable: also returns the SparseTrainableWrapper; its entry list is what the tuple form's preprocessing
+  (`_safe_sparse_args`) makes on the derived row ids, built on the device from row_splits with one host read of its length."""
   _check_combiner(combiner)
   rs, ids, w = _ragged_input(params, sparse_ids, sparse_weights)
   n = rs.numel() - 1
@@ -120,7 +121,7 @@ def safe_embedding_lookup_sparse(params, sparse_ids, sparse_weights=None, combin
   prune, fill = _safe_flags(w, combiner, default_id)
   if not return_trainable:
     return params.lookup_combined_ragged(rs, ids, w, combiner, prune=prune, fill_id=fill)
-  made = _safe_entries(params, rs, ids, w, combiner, default_id, n)
+  made = _safe_entries_many([params], [(0, rs, ids, w)], [combiner], [default_id])[0]
   params.admit_entries(made[3][0])   # (tiered shards: the entry ids into the cache ahead of the read; init_on_lookup="pooled": admitted with drawn rows)
   out = params.lookup_combined_ragged(rs, ids, w, combiner, prune=prune, fill_id=fill)
   return out, _safe_wrapper(params, made, combiner, n, plan_writeback, caller_weights=w)
@@ -148,11 +149,11 @@ def _many(params_list, sp_ids_list, weights_list, combiner, default_id, safe, re
   if return_trainable:
     # made ahead of the reads: a tiered member admits its entry ids first, and every tiered member's max_batch is checked before
     # anything is admitted or read
-    for members in groups.values():
-      for i, rs, ids, w in members:
-        if safe:
-          made[i] = _safe_entries(params_list[i], rs, ids, w, combiners[i], default_ids[i], rs.numel() - 1)
-        entry_ids[i] = made[i][3][0] if safe else ids
+    everyone = [m for members in groups.values() for m in members]
+    if safe:
+      made = _safe_entries_many(params_list, everyone, combiners, default_ids)
+    for i, rs, ids, w in everyone:
+      entry_ids[i] = made[i][3][0] if safe else ids
     _check_entries_many([(params_list[i], e) for i, e in entry_ids.items()])
   for i in singles:
     kw = dict(default_id=default_ids[i]) if safe else {}
@@ -197,6 +198,6 @@ def safe_embedding_lookup_sparse_many(params_list, sp_ids_list, sparse_weights_l
   """`safe_embedding_lookup_sparse` of a LIST of variables: result i is what the single form returns for table i, bit for bit.
   `combiner` and `default_id` are scalars or per-table lists.  One grouped call per device for the variables the pooled forward
   serves (tiered ones included, as in `embedding_lookup_sparse_many`), with no host synchronisation in the forward; with
-  return_trainable the wrappers' entry lists are made per table by the tuple form's preprocessing (host syncs included), ahead of
-  the grouped call: they are what a tiered member admits."""
+  return_trainable the wrappers' entry lists of all tables come from one `device_ops.safe_entries_many` per device (one C call,
+  one host read of every list's length), ahead of the grouped call: they are what a tiered member admits."""
   return _many(params_list, sp_ids_list, sparse_weights_list, combiner, default_id, True, return_trainable, plan_writeback)

@@ -1302,10 +1302,9 @@ def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None,
   return results
 
 
-def _safe_sparse_args(params, sp_ids, sparse_weights, combiner, default_id, return_trainable, num_rows):
-  """The preprocessing of safe_embedding_lookup_sparse (PY/dynamic_embedding_ops.py:356-408): pruning by weight, the rank > 2
-  flattening, the number of rows and — for a trainable — the entry list with one entry per empty row.  Returns what
-  `embedding_lookup_sparse` is then called with and what `_safe_sparse_finish` needs: (rows, ids, w, n, entries, out_shape, lead)."""
+def _safe_sparse_rows(params, sp_ids, sparse_weights, num_rows):
+  """The head of safe_embedding_lookup_sparse's preprocessing (PY/dynamic_embedding_ops.py:356-367): the operands on the
+  variable's device, the rank > 2 flattening and the number of rows.  (rows, ids, w, n, lead)."""
   dense_shape = None
   if len(sp_ids) == 3:
     indices, ids, dense_shape = sp_ids
@@ -1334,9 +1333,17 @@ def _safe_sparse_args(params, sp_ids, sparse_weights, combiner, default_id, retu
     else:
       n = int(rows.max().item()) + 1 if rows.numel() else 0
   w = None
-  keep = None
   if sparse_weights is not None:
     w = torch.as_tensor(sparse_weights, dtype=torch.float32, device=params._primary)
+  return rows, ids, w, n, lead
+
+
+def _safe_sparse_lists_torch(params, rows, ids, w, n, combiner, default_id, return_trainable):
+  """The two lists of the preprocessing in torch (boolean masks, `nonzero`, a stable sort: four host reads): the kept entries
+  (rows, ids, w) and — for a trainable — the entry list.  The route of batches beyond `device_ops.safe_entries_many`'s limits
+  and of tensors that do not live on a GPU, and what the device route is tested against."""
+  keep = None
+  if w is not None:
     if combiner != "sum":
       keep = w > 0
   if keep is not None:
@@ -1358,8 +1365,75 @@ def _safe_sparse_args(params, sp_ids, sparse_weights, combiner, default_id, retu
     order = torch.sort(all_rows, stable=True).indices
     entries = (all_ids[order].contiguous(), all_rows[order].contiguous(),
                None if (w is None and default_id is not None) else all_w[order].contiguous())
+  return rows, ids, w, entries
+
+
+def _safe_sparse_args_torch(params, sp_ids, sparse_weights, combiner, default_id, return_trainable, num_rows):
+  """`_safe_sparse_args` with both lists made in torch."""
+  rows, ids, w, n, lead = _safe_sparse_rows(params, sp_ids, sparse_weights, num_rows)
+  rows, ids, w, entries = _safe_sparse_lists_torch(params, rows, ids, w, n, combiner, default_id, return_trainable)
   out_shape = (tuple(lead) if lead is not None else (n,)) + (params.dim,)
   return rows, ids, w, n, entries, out_shape, lead
+
+
+def _safe_sparse_args(params, sp_ids, sparse_weights, combiner, default_id, return_trainable, num_rows):
+  """The preprocessing of safe_embedding_lookup_sparse (PY/dynamic_embedding_ops.py:356-408): pruning by weight, the rank > 2
+  flattening, the number of rows and — for a trainable — the entry list with one entry per empty row.  Returns what
+  `embedding_lookup_sparse` is then called with and what `_safe_sparse_finish` needs: (rows, ids, w, n, entries, out_shape, lead).
+  The kept entries and the entry list are built on the device (`_safe_sparse_args_many`)."""
+  return _safe_sparse_args_many([params], [sp_ids], [sparse_weights], [combiner], [default_id], return_trainable, [num_rows])[0]
+
+
+def _safe_sparse_args_many(params_list, sp_ids_list, weights, combiners, default_ids, return_trainable, num, ragged=False):
+  """`_safe_sparse_args` of every member, bit for bit, with the kept lists and the entry lists of all members of a device from ONE
+  `device_ops.safe_entries_many` (one C call, one host read of all counts).  ragged: sp_ids_list[i] is (row_splits int64, ids)
+  with `num[i]` rows, and the member's `rows` are the row ids the splits stand for; the splits go to the builder as they are.
+  A non-training member asks for its kept list only, and for nothing where it does not prune.  A member whose lists exceed the
+  builder's limits, or whose tensors are not on a GPU, takes `_safe_sparse_lists_torch`."""
+  n_t = len(params_list)
+  heads = [(sp_ids_list[i][0], sp_ids_list[i][1], weights[i], num[i], None) if ragged else
+           _safe_sparse_rows(params_list[i], sp_ids_list[i], weights[i], num[i]) for i in range(n_t)]
+  lists = [None] * n_t   # member -> (rows, ids, w, entries)
+  groups = {}            # device -> members the builder serves
+  for i, (rows, ids, w, n, lead) in enumerate(heads):
+    prune = w is not None and combiners[i] != "sum"
+    if not (prune or return_trainable):
+      lists[i] = (rows, ids, w, None)   # nothing to build (a ragged member never gets here: its forward needs no lists)
+    elif rows.is_cuda and ids.dtype in (torch.int32, torch.int64) and device_ops.safe_entries_fit([(ids.numel(), n)]):
+      groups.setdefault(rows.device, []).append(i)
+  for members in groups.values():
+    while members:   # (as many calls as the limit on a call's total asks for: one, for any batch a step sees)
+      take, total = [], 0
+      for i in members:
+        if total + heads[i][1].numel() + heads[i][3] > device_ops.SAFE_ENTRIES_MAX_TOTAL:
+          break
+        take.append(i)
+        total += heads[i][1].numel() + heads[i][3]
+      members = members[len(take):]
+      reqs, kept = [], []
+      for i in take:
+        rows, ids, w, n, _ = heads[i]
+        prune = w is not None and combiners[i] != "sum"
+        reqs.append((rows, ids, w, n, prune, default_ids[i], ragged))
+        kept.append(prune or ragged)   # (a ragged member that keeps everything still takes its row ids from the kept list)
+      built = device_ops.safe_entries_many(reqs, want_kept=kept, want_entries=return_trainable)
+      for i, (k, ent) in zip(take, built):
+        rows, ids, w, n, _ = heads[i]
+        if w is not None and combiners[i] != "sum":
+          rows, ids, w = k[1], k[0], k[2]
+        elif ragged:
+          rows = k[1]
+        lists[i] = (rows, ids, w, ent)
+  args = []
+  for i, (rows, ids, w, n, lead) in enumerate(heads):
+    if lists[i] is None:
+      if ragged:
+        from .ragged_embedding_ops import row_ids_of
+        rows = row_ids_of(rows, ids.numel())
+      lists[i] = _safe_sparse_lists_torch(params_list[i], rows, ids, w, n, combiners[i], default_ids[i], return_trainable)
+    rows, ids, w, entries = lists[i]
+    args.append((rows, ids, w, n, entries, (tuple(lead) if lead is not None else (n,)) + (params_list[i].dim,), lead))
+  return args
 
 
 def _safe_sparse_finish(params, res, rows, n, default_id, max_norm, lead):
@@ -1400,8 +1474,8 @@ def safe_embedding_lookup_sparse_many(params_list, sp_ids_list, sparse_weights_l
                                       max_norm=None, return_trainable=False, num_rows=None, plan_writeback=False):
   """`safe_embedding_lookup_sparse` of a LIST of variables: result i is what the single form returns for table i, bit for bit.
   `combiner`, `default_id` and `num_rows` are scalars or per-table lists.  The preprocessing is the single form's
-  (`_safe_sparse_args`); the lookups go through `embedding_lookup_sparse_many`, one grouped call per device for the variables
-  the pooled forward serves.  Row counts that neither a dense_shape nor num_rows gives are read in one host read per device."""
+  (`_safe_sparse_args_many`: all tables' kept lists and entry lists from one builder call and one host read per device); the
+  lookups go through `embedding_lookup_sparse_many`, one grouped call per device for the variables the pooled forward serves.  Row counts that neither a dense_shape nor num_rows gives are read in one host read per device."""
   n_t = len(params_list)
   if len(sp_ids_list) != n_t:
     raise ValueError("sp_ids_list: %d entries for %d tables" % (len(sp_ids_list), n_t))
@@ -1419,8 +1493,7 @@ def safe_embedding_lookup_sparse_many(params_list, sp_ids_list, sparse_weights_l
         unknown.setdefault(params._primary, []).append((i, indices[:, 0] if indices.dim() == 2 else indices))
   for members in unknown.values():
     _rows_in_one_read(num, members)
-  args = [_safe_sparse_args(params_list[i], sp_ids_list[i], weights[i], combiners[i], default_ids[i], return_trainable, num[i])
-          for i in range(n_t)]
+  args = _safe_sparse_args_many(params_list, sp_ids_list, weights, combiners, default_ids, return_trainable, num)
   outs = embedding_lookup_sparse_many(params_list, [(a[0], a[1]) for a in args], [a[2] for a in args], combiner=combiners,
                                       max_norm=max_norm, return_trainable=return_trainable, num_rows=[a[3] for a in args],
                                       plan_writeback=plan_writeback, _entries_list=[a[4] for a in args],
