@@ -781,6 +781,34 @@ typedef struct {
 int tfra_multi_safe_entries(tfra_workspace_t* ws, size_t n_lists, const tfra_safe_entries_desc* descs,
                             uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
 
+/* The pooling lists of a field-wise embedding, built on the device in ONE launch: what FieldWiseEmbedding hands the
+ * ragged pooled lookup.  ids and slots are dense row-major blocks [n_rows * per_row]: sample b owns the positions
+ * [b * per_row, (b + 1) * per_row), and slots[p] in [0, nslots) is the field of ids[p].  With n = n_rows * per_row:
+ *   entry_ids  [n]: the ids ordered by (sample, slot, input position) — STABLE: within one (sample, slot) the input order is kept.
+ *   row_splits [n_rows * nslots + 1]: row_splits[b * nslots + f] = b * per_row + the number of sample b's entries with slot < f;
+ *              the last element is n.  Segment b * nslots + f owns the entries [row_splits[s], row_splits[s + 1]).
+ *   entry_pos  [n] int32, optional (NULL): the input position p of every entry.
+ *   entry_seg  [n], optional (NULL): b * nslots + slot of every entry — the ascending `seg` of the combined write-back.
+ *   d_bad      device int64, optional (NULL): += the number of slots outside [0, nslots).  Such a slot is a caller error: it is
+ *              clamped into range (below 0 to 0, else to nslots - 1) and counted, never used as an index.
+ * Nothing is ever written outside [0, n) of the entry buffers or outside row_splits' n_rows * nslots + 1 elements, whatever slots
+ * holds.  Deterministic.  n_rows == 0: TFRA_OK, nothing is looked at or written.  per_row == 0: every split is 0 (ids, slots and
+ * the entry buffers may be NULL).
+ * Enqueues ONE kernel on `stream`, on the calling thread's current device: a sample is sorted by one, two or four waves of one block
+ * (up to 64, up to 128, more entries) with the per-slot counts in LDS, the rank inside a chunk of 64 from wave64 ballots in
+ * position order; no workspace, no memset, no host read, no block waits for another, plain vector stores (d_bad: one atomic add per
+ * wave that saw a bad slot).
+ * Every check runs before anything is enqueued: a refused call writes nothing.  TFRA_ERR_INVALID: nslots == 0, row_splits NULL,
+ * ids, slots or entry_ids NULL where per_row > 0, an int64 buffer that is not 8-byte aligned or entry_pos not 4-byte aligned, an
+ * output that overlaps another output or an input (ids and slots may be one buffer).  TFRA_ERR_UNSUPPORTED:
+ * nslots > TFRA_FIELD_ENTRIES_MAX_SLOTS, n_rows * per_row >= 2^31 (or either factor).  The cap is the LDS budget: four waves' counts
+ * of 4 bytes per slot, 32 KiB at the cap — half of what a block gets without opting in, and five blocks to a CU.
+ * Synchronises nothing.                                                                 (tests/test_gpu_field_entries.py) */
+#define TFRA_FIELD_ENTRIES_MAX_SLOTS 2048u
+int tfra_field_entries(size_t n_rows, size_t per_row, size_t nslots, const int64_t* ids, const int64_t* slots, int64_t* entry_ids,
+                       int64_t* row_splits, int32_t* entry_pos /* optional */, int64_t* entry_seg /* optional */,
+                       int64_t* d_bad /* optional */, tfra_stream_t stream);
+
 /* Find of all n ids AND tfra_unique_unordered of the same ids in ONE launch — the forward half of embedding_lookup as the fused TF op
  * TFRA>HkvHashTableEmbeddingLookup issues it (tf_ops/fused_ops_rocm.cc; PY/dynamic_embedding_ops.py:99-117 needs the rows of every id,
  * the distinct ids and the inverse index for the backward pass).  rows_out / exists / defaults / default_is_full as tfra_table_find,

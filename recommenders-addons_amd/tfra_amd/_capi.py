@@ -298,6 +298,7 @@ _SIGS = {
     "tfra_unique_unordered": [_P, _SZ, _P, _P, _P, _P, _P],
     "tfra_multi_unique": [_P, _SZ, _P, _P, _P],
     "tfra_multi_safe_entries": [_P, _SZ, _P, _P, _P],
+    "tfra_field_entries": [_SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _P, _P, _P],
     "tfra_table_find_unique": [_P, _P, _SZ, _P, _P, _P, _P, _I, _P, _P, _P, _P],
     "tfra_table_find_combine": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, _P, _P],
     "tfra_multi_find_combine": [_P, _SZ, _P, _P, _P],

@@ -13,5 +13,7 @@ from .variable import (CuckooHashTableConfig, CuckooHashTableCreator, HkvHashTab
                        embedding_lookup_sparse, embedding_lookup_sparse_many, embedding_lookup_unique, get_variable,
                        safe_embedding_lookup_sparse, safe_embedding_lookup_sparse_many, sparse_weights_grad_many)
 from . import ragged_embedding_ops   # (after .variable: it stands on the tuple-form functions)
+from . import layers                 # (after ragged_embedding_ops: FieldWiseEmbedding reads through it)
+from . import keras                  # (de.keras.layers is de.layers)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -219,6 +219,79 @@ def safe_entries_many(requests, want_kept=True, want_entries=True, return_launch
   return (res, int(launches.value)) if return_launches else res
 
 
+FIELD_ENTRIES_MAX_SLOTS = 2048   # tfra_field_entries' bounds (include/tfra_mi355x.h): nslots up to here,
+FIELD_ENTRIES_MAX_N = 1 << 31    # n_rows * per_row stays below
+
+
+def field_entries_fit(n_rows, per_row, nslots):
+  """Whether a [n_rows, per_row] block over `nslots` fields fits one tfra_field_entries call."""
+  return nslots <= FIELD_ENTRIES_MAX_SLOTS and max(n_rows, per_row, n_rows * per_row) < FIELD_ENTRIES_MAX_N
+
+
+def _field_block(ids2d, slots2d, nslots, who):
+  """(ids [B, S], slots int64 [B, S], nslots) of a field-wise block, shapes checked."""
+  if ids2d.dim() != 2:
+    raise ValueError("%s: ids must be [batch, per_sample], got shape %s" % (who, list(ids2d.shape)))
+  if slots2d.numel() != ids2d.numel() or slots2d.device != ids2d.device:
+    raise ValueError("%s: slots must have one element per id, on the ids' device" % who)
+  nslots = int(nslots)
+  if nslots < 1:
+    raise ValueError("%s: nslots must be >= 1, got %d" % (who, nslots))
+  return ids2d, slots2d.reshape(ids2d.shape).to(torch.int64), nslots
+
+
+def _field_entries_torch(ids2d, slots2d, nslots, want_pos=False, want_seg=True, bad=None):
+  """`field_entries` in torch ops, on whatever device the block lives (the reference's `_pooling_by_slots`, PY/keras/layers/
+  embedding.py:491-513, with the order of ties pinned): the slots clamped into [0, nslots), the bias sample * nslots added, a STABLE
+  `torch.sort`, the ids gathered, the splits by `searchsorted`.  The route of blocks beyond the builder's limits and the tests'
+  reference."""
+  ids, slots, nslots = _field_block(ids2d, slots2d, nslots, "_field_entries_torch")
+  b, s = ids.shape
+  dev = ids.device
+  if bad is not None:
+    bad += ((slots < 0) | (slots >= nslots)).sum()
+  seg = slots.clamp(0, nslots - 1) + torch.arange(b, dtype=torch.int64, device=dev).reshape(b, 1) * nslots
+  seg, order = torch.sort(seg.reshape(-1), stable=True)
+  entry_ids = ids.reshape(-1)[order]
+  row_splits = torch.searchsorted(seg, torch.arange(b * nslots + 1, dtype=torch.int64, device=dev))
+  return entry_ids, row_splits, (order.to(torch.int32) if want_pos else None), (seg if want_seg else None)
+
+
+def field_entries(ids2d, slots2d, nslots, want_pos=False, want_seg=True, bad=None):
+  """The pooling lists of a field-wise embedding in ONE launch (tfra_field_entries; no workspace, nothing read on the host).
+  `ids2d` int64 or int32 [batch, per_sample] on a device, `slots2d` any integer dtype, one field in [0, nslots) per id.  Returns
+  (entry_ids, row_splits, entry_pos, entry_seg): the ids ordered by (sample, slot, input position) — stable — in the dtype they
+  were given in (int32 ids widened in front of the call and narrowed behind it); row_splits int64 [batch * nslots + 1], segment
+  sample * nslots + slot owning [row_splits[s], row_splits[s + 1]); entry_pos int32 [n], every entry's input position (want_pos,
+  else None); entry_seg int64 [n], every entry's segment (want_seg, else None).  `bad`: an int64 device tensor of one element
+  that receives += the number of slots outside [0, nslots); such a slot is clamped into range either way.
+  A block beyond the call's limits (`field_entries_fit`) takes `_field_entries_torch`, with the same results."""
+  ids, slots, nslots = _field_block(ids2d, slots2d, nslots, "field_entries")
+  dev = ids.device
+  if dev.type != "cuda":
+    raise ValueError("field_entries builds its lists on the device; the ids live on %s" % dev)
+  if bad is not None and (bad.dtype != torch.int64 or bad.numel() != 1 or bad.device != dev):
+    raise ValueError("field_entries: bad must be an int64 tensor of one element on the ids' device")
+  b, s = ids.shape
+  if not field_entries_fit(b, s, nslots):
+    return _field_entries_torch(ids, slots, nslots, want_pos, want_seg, bad)
+  n = b * s
+  flat = _wide_keys(ids.reshape(-1))
+  slots = slots.contiguous()
+  entry_ids = torch.empty(n, dtype=torch.int64, device=dev)
+  if b == 0:   # (the call writes nothing for no samples: the one split is the closing one)
+    row_splits = torch.zeros(1, dtype=torch.int64, device=dev)
+  else:
+    row_splits = torch.empty(b * nslots + 1, dtype=torch.int64, device=dev)
+  entry_pos = torch.empty(n, dtype=torch.int32, device=dev) if want_pos else None
+  entry_seg = torch.empty(n, dtype=torch.int64, device=dev) if want_seg else None
+  with torch.cuda.device(dev):   # (the launch goes to the calling thread's current device)
+    _capi.call("tfra_field_entries", b, s, nslots, _ptr(flat) if n else None, _ptr(slots) if n else None,
+               _ptr(entry_ids) if n else None, _ptr(row_splits), _ptr(entry_pos) if n else None, _ptr(entry_seg) if n else None,
+               _ptr(bad), _stream(dev))
+  return _narrow_keys(entry_ids, ids.dtype), row_splits, entry_pos, entry_seg
+
+
 def gather_rows(rows, idx):
   """out[i,:] = rows[idx[i],:]  (tf.gather after unique, PY/dynamic_embedding_ops.py:111)."""
   rows = rows.contiguous()

@@ -58,9 +58,11 @@ def _safe_flags(w, combiner, default_id):
   return (w is not None and combiner != "sum"), default_id
 
 
-def _plain_wrapper(params, rs, ids, w, combiner, n, plan_writeback, entry_plan=None):
-  seg = row_ids_of(rs, ids.numel())
-  return SparseTrainableWrapper(params, None, None, None, seg, w, combiner, n, (n, params.dim), ids, seg, w,
+def _plain_wrapper(params, rs, ids, w, combiner, n, plan_writeback, entry_plan=None, seg=None, out_shape=None):
+  """seg: the entries' row ids where the caller has them (else derived from the splits); out_shape: the shape the caller gives
+  the result, which the gradient then has (else [n, dim])."""
+  seg = row_ids_of(rs, ids.numel()) if seg is None else seg
+  return SparseTrainableWrapper(params, None, None, None, seg, w, combiner, n, out_shape or (n, params.dim), ids, seg, w,
                                 plan_writeback=plan_writeback, lookup_ids=ids, entry_plan=entry_plan)
 
 
@@ -81,25 +83,30 @@ def _safe_wrapper(params, args, combiner, n, plan_writeback, entry_plan=None, ca
   return _note_pruned(tw, caller_weights, combiner)
 
 
-def embedding_lookup_sparse(params, sp_ids, sp_weights, name=None, combiner="mean", return_trainable=False, plan_writeback=False):
+def embedding_lookup_sparse(params, sp_ids, sp_weights, name=None, combiner="mean", return_trainable=False, plan_writeback=False,
+                            entry_seg=None, out_shape=None):
   """PY/ragged_embedding_ops.py:223-324.  `sp_ids` = (row_splits[n_rows + 1], values[nnz]), `sp_weights` = weight values or None.
   [n_rows, dim] float32: row r = sum / mean / sqrtn over its entries of weight * embedding, zeros for an empty row — bit-identical
   to `de.embedding_lookup_sparse(params, (row ids, values), sp_weights, num_rows=n_rows)`, in one launch.
 
   return_trainable: also returns the SparseTrainableWrapper (`DynamicEmbeddingOptimizer.apply_combined_gradients`); its entry
-  list is (values, derived row ids, weights).  plan_writeback: as the tuple form's."""
+  list is (values, derived row ids, weights).  plan_writeback: as the tuple form's.
+  entry_seg: the row id of every entry (int64 [nnz], what the splits stand for) from a caller that has it — `layers.
+  FieldWiseEmbedding`, whose list builder writes it — so that it is not derived again; out_shape: the shape that caller gives the
+  result ([n_rows, dim] reshaped), which the wrapper then expects of the gradient.  Both default to today's path."""
   _check_combiner(combiner)
   rs, ids, w = _ragged_input(params, sp_ids, sp_weights)
   n = rs.numel() - 1
   if not (_pooled_training if return_trainable else _pooled_forward)(params, None):
-    return _tuple_form.embedding_lookup_sparse(params, (row_ids_of(rs, ids.numel()), ids), w, combiner=combiner,
-                                               return_trainable=return_trainable, num_rows=n, plan_writeback=plan_writeback)
+    seg = row_ids_of(rs, ids.numel()) if entry_seg is None else entry_seg
+    return _tuple_form.embedding_lookup_sparse(params, (seg, ids), w, combiner=combiner, return_trainable=return_trainable,
+                                               num_rows=n, plan_writeback=plan_writeback, _out_shape=out_shape)
   if return_trainable:
     params.admit_entries(ids)   # (tiered shards: the entry ids into the cache ahead of the read; init_on_lookup="pooled": admitted with drawn rows)
   out = params.lookup_combined_ragged(rs, ids, w, combiner)
   if not return_trainable:
     return out
-  return out, _plain_wrapper(params, rs, ids, w, combiner, n, plan_writeback)
+  return out, _plain_wrapper(params, rs, ids, w, combiner, n, plan_writeback, seg=entry_seg, out_shape=out_shape)
 
 
 def safe_embedding_lookup_sparse(params, sparse_ids, sparse_weights=None, combiner="mean", default_id=None, name=None,
