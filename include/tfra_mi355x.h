@@ -384,10 +384,30 @@ int tfra_table_save_if(tfra_table_t* t, int field, int pred, uint64_t threshold,
  *    keeps using ONE stream.  Scratch buffers must have been sized by an identical warm-up call.
  *    TFRA_OPTION_NO_OWNER_TAGS = 1 makes the planned write-backs take the general two-kernel path
  *    (the one used when the 4 B/bucket owner-tag array cannot be allocated); same results.      */
-typedef enum { TFRA_OPTION_CAPTURE_SAFE = 1, TFRA_OPTION_NO_OWNER_TAGS = 2, TFRA_OPTION_KEY_BYTES_ON_DISK = 3 } tfra_option;
+typedef enum {
+  TFRA_OPTION_CAPTURE_SAFE = 1,
+  TFRA_OPTION_NO_OWNER_TAGS = 2,
+  TFRA_OPTION_KEY_BYTES_ON_DISK = 3,
+  TFRA_OPTION_STOCHASTIC_ROUNDING = 4
+} tfra_option;
 /*    TFRA_OPTION_KEY_BYTES_ON_DISK = 4 | 8 (default 8): the width of a key in `<prefix>-keys` files.  4 = tables whose OP-LEVEL key type
  *    is int32 (the reference's (int32, float) GPU kernels, K/cuckoo_hashtable_op_gpu.cu.cc:1058: its files hold raw int32 keys): save
- *    narrows, load widens (sign-extending); a key outside the int32 range fails the save. */
+ *    narrows, load widens (sign-extending); a key outside the int32 range fails the save.
+ *    TFRA_OPTION_STOCHASTIC_ROUNDING = 0 (default, off) | a 64-bit seed: every FUSED OPTIMIZER write-back of a float16 / bfloat16 table
+ *    (tfra_table_apply_optimizer / _apply_sparse / _apply_planned / _apply_planned_combined, the prefetch steps, tfra_route_apply, and the
+ *    table's member of tfra_multi_apply_planned_combined, which is served by the single call's launches) rounds what the rule produced
+ *    — the parameter and every slot vector the rule owns — stochastically instead of to nearest even.  With lo = x rounded toward zero
+ *    onto the storage grid (continued by one step past its largest finite value, stored as infinity), hi the next grid value away
+ *    from zero and F = 65536 (|x| - |lo|) / (|hi| - |lo|), the result is hi iff 65536 - r <= F, r the element's 16 random bits; a
+ *    representable value, an infinity, a NaN and |x| at or beyond the continued step are stored as with the option off.  The bits are
+ *    a pure function of (seed, call, key, element): with mix64 the splitmix64 finalizer and GAMMA = 0x9E3779B97F4A7C15,
+ *      a = mix64(seed + call * GAMMA), b = mix64(a ^ key), e = field * dim + column, w = mix64(b + ((e >> 2) + 1) * GAMMA),
+ *      r = (w >> 16 (e & 3)) & 0xffff.
+ *    `call` is the table's count of fused write-backs that passed their checks and had work to do (one logical write-back issued in
+ *    parts is one call); setting the option, to any value, sets it to 0.  The constant aux_init fill of fields the rule does not own,
+ *    tfra_table_insert_or_accum, the upserts and every copy of a row keep nearest-even / the bits they are given.  A non-zero value on a
+ *    table of another value type, and a fused write-back on a table that also has TFRA_OPTION_CAPTURE_SAFE (a replayed graph would
+ *    reuse one call index), fail with TFRA_ERR_UNSUPPORTED before anything is enqueued.  (tests/test_gpu_stochastic_rounding.py) */
 int tfra_table_set_option(tfra_table_t* t, int option, int64_t value);
 
 /* -- set_global_epoch (lookup_table_op_hkv.h:499,507,533) --------------------------------- */
@@ -433,8 +453,9 @@ int tfra_table_load_field(tfra_table_t* t, int field, const char* prefix, size_t
  * with p = param_defaults (full [n,dim] or broadcast [dim], like find) and slots = aux_init.
  * Requires aux_fields >= the optimizer's slot count.  value_dtype F32, F16 or BF16, here and in the planned / sparse forms
  * below (gradients and defaults are float32 in every case: the rule runs in fp32 on the up-cast row and slots and the
- * results are rounded to the storage type once, to nearest even; a new row starts from the float32 default row and
- * aux_init values, not from their rounded images).                                            */
+ * results are rounded to the storage type once, to nearest even — or stochastically, on a table with
+ * TFRA_OPTION_STOCHASTIC_ROUNDING; a new row starts from the float32 default row and aux_init values, not from their
+ * rounded images).                                                                            */
 typedef enum { TFRA_OPT_SGD = 0, TFRA_OPT_ADAM = 1, TFRA_OPT_ADAGRAD = 2, TFRA_OPT_FTRL = 3 } tfra_opt_kind;
 typedef struct {
   int32_t kind;     /* tfra_opt_kind */
@@ -1268,6 +1289,9 @@ int tfra_multi_find_combine_ragged_backprop_weights(tfra_workspace_t* ws, size_t
  * *launches_out (optional, host): the kernel launches enqueued =
  *   3 + (NCH classes present) + ((rule, storage type) classes present) + ((rule, storage type) classes with a table at max_capacity),
  * 0 when no descriptor has ids.  26 growing float32 tables of dims 16 / 32 / 64 / 128 with one rule: 3 + 2 + 1 = 6.
+ * A descriptor whose table has TFRA_OPTION_STOCHASTIC_ROUNDING on is checked with the others and then served by the single call's
+ * launches, on the same stream, behind the grouped ones (the grouped kernels round to nearest even); *launches_out counts the
+ * grouped launches only.
  * The plans are built per plan (tfra_sparse_plan_build) or by tfra_multi_sparse_plan_build below.  Not for stream capture. */
 typedef struct {
   uint32_t struct_size;              /* = sizeof(tfra_apply_combined_desc) */

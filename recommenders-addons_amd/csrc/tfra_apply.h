@@ -23,12 +23,21 @@ static void with_nch(int nch, F&& f) {
   }
 }
 
+// A fused write-back of a table that rounds stochastically takes one call index of the random stream, on the host: a captured
+// graph would replay that one index.  Every fused write-back refuses the pair before it enqueues anything.
+static Check check_rounding(const Table* t) {
+  if (t->stochastic() && t->capture_safe)
+    return refuse(TFRA_ERR_UNSUPPORTED, "TFRA_OPTION_STOCHASTIC_ROUNDING and TFRA_OPTION_CAPTURE_SAFE are both set (a replayed graph would reuse one call index)");
+  return Check{};
+}
+
 // The checks of a planned write-back: apply_planned_impl's, whoever calls it, and behind check_apply_combined those of a
 // descriptor of tfra_multi_apply_planned_combined.  active: the plan holds ids.
 template <class AtEntry>
 static Check check_apply_planned(const Table* t, const tfra_opt_params* p, const tfra_sparse_plan* pl, const float* grads,
                                  const float* param_default_row, AtEntry&& at_entry) {
   if (!t || !p || !pl) return refuse(TFRA_ERR_INVALID, "null argument");
+  if (Check e = check_rounding(t); e.done()) return e;
   if (Check e = at_entry(); e.done()) return e;
   if (pl->n == 0) return nothing_to_do();
   if (!grads || !param_default_row) return refuse(TFRA_ERR_INVALID, "null buffer");
@@ -52,6 +61,7 @@ static Check check_apply_combined(const Table* t, const tfra_opt_params* p, cons
                                   AtEntry&& at_entry) {
   if (!t || !p || !pl) return refuse(TFRA_ERR_INVALID, "null argument");
   if (combiner < 0 || combiner > 2) return refuse(TFRA_ERR_INVALID, "combiner must be 0 (sum), 1 (mean) or 2 (sqrtn)");
+  if (Check e = check_rounding(t); e.done()) return e;
   if (Check e = at_entry(); e.done()) return e;
   if (pl->kind != 0 || pl->dim != t->opts.dim) return refuse(TFRA_ERR_INVALID, "the plan was built for another dim");
   if (t->opts.device != pl->device && t->opts.device >= 0) return refuse(TFRA_ERR_INVALID, "plan and table live on different devices");

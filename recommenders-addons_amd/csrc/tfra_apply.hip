@@ -117,13 +117,20 @@ static void launch_apply(Table* t, hipStream_t s, const tfra_sparse_plan* pl, in
   // rounds of dispatch plus a third of 27 blocks; 1024 blocks looping twice: configs[1] 55.2 -> 53.7 us per step (A/B on one box, twice)
   static const unsigned grid_cap = [] { const char* e = getenv("TFRA_APPLY_GRID_CAP"); return e ? (unsigned)atoi(e) : 1024u; }();
   if (grid_cap) key_blocks = std::min(key_blocks, grid_cap);
+  // xs: the caller's pack, and behind it the rounding's StochP for the half rows of a table that rounds stochastically
+  auto launch = [&](auto KIND, auto ST, const auto&... xs) {
+    apply_csr_kernel<KIND, false, ST><<<key_blocks, 256, 0, s>>>(v, o, pl->dim, grads, pl->partial, keys_of(pl), default_row, a0, a1, sp,
+                                                                 pl->dflag, pl->any_deferred, gen, xs...);
+    if (sp.bounded)
+      apply_csr_kernel<KIND, true, ST><<<key_blocks, 256, 0, s>>>(v, o, pl->dim, grads, pl->partial, keys_of(pl), default_row, a0, a1, sp,
+                                                                  pl->dflag, pl->any_deferred, gen, xs...);
+  };
   with_opt_kind(kind, [&](auto KIND) {
     with_stored(st_index(t->opts.value_dtype), [&](auto ST) {
-      apply_csr_kernel<KIND, false, ST><<<key_blocks, 256, 0, s>>>(v, o, pl->dim, grads, pl->partial, keys_of(pl), default_row, a0, a1, sp,
-                                                                   pl->dflag, pl->any_deferred, gen, cs...);
-      if (sp.bounded)
-        apply_csr_kernel<KIND, true, ST><<<key_blocks, 256, 0, s>>>(v, o, pl->dim, grads, pl->partial, keys_of(pl), default_row, a0, a1, sp,
-                                                                    pl->dflag, pl->any_deferred, gen, cs...);
+      if constexpr (decltype(ST)::value != TFRA_F32) {
+        if (t->stochastic()) { launch(KIND, ST, cs..., t->stoch_of()); return; }
+      }
+      launch(KIND, ST, cs...);
     });
   });
 }
@@ -152,7 +159,7 @@ int tfra::apply_planned_impl(tfra_table_t* tp, const tfra_opt_params* p, const t
   if (comb) launch_apply(t, s, pl, p->kind, o, grads, param_default_row, key_blocks, sp, CombRows{comb});
   else launch_apply(t, s, pl, p->kind, o, grads, param_default_row, key_blocks, sp);
   if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "apply_planned: launch failed");
-  t->step_epoch();
+  t->step_writeback();
   return TFRA_OK;
 }
 
@@ -265,7 +272,7 @@ static int apply_sparse_big(Table* t, tfra_table_t* tp, tfra_sparse_plan* pl, co
       off += (size_t)c;
     }
     t->epoch_hold = false;
-    t->step_epoch();
+    t->step_writeback();
     return TFRA_OK;
   }
   return set_error(TFRA_ERR_UNSUPPORTED, "apply_sparse: could not split the batch into parts of 2^18 ids");
@@ -286,6 +293,7 @@ extern "C" int tfra_table_apply_sparse(tfra_table_t* tp, const tfra_opt_params* 
                                            "(use tfra_unique + tfra_segment_sum + tfra_table_apply_optimizer otherwise)");
   tfra_sparse_plan* pl;
   std::lock_guard<std::mutex> lock(t->mu);
+  if (const Check c = check_rounding(t); c.code) return report("apply_sparse: ", c);   // (before the plan build is enqueued)
   int rc = t->enter((hipStream_t)stream);   // orders the rebuild of the table's own plan behind its previous use
   if (rc) return rc;
   rc = own_plan(t, &pl);

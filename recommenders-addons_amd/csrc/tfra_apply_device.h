@@ -5,6 +5,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "../../include/tfra_mi355x.h"
 #include "tfra_combine_device.h"
 #include "tfra_device.h"
@@ -29,7 +31,8 @@ namespace {
 template <class... CS>
 __device__ __forceinline__ const CombEnt* comb_ent(const CS&... cs) {
   const CombEnt* p = nullptr;
-  ((p = cs.ent), ...);
+  auto take = [&](const auto& x) { if constexpr (std::is_same<std::decay_t<decltype(x)>, CombRows>::value) p = x.ent; };
+  (take(cs), ...);   // (the pack of the update kernels may also hold the rounding's StochP)
   return p;
 }
 
@@ -193,6 +196,9 @@ __device__ __forceinline__ float4 sum_rows(const float* __restrict__ grads, cons
 // rounded to the storage type once (to_stored) and written back as one 8-byte write-through store per field.  A new row starts
 // from the FLOAT default row and aux_init values, not from their rounded images (as apply_kernel / apply_evict_kernel do).
 // Gradients and partial sums are fp32 for every ST.  The float instantiations compile the code they always did (if constexpr).
+// A StochP in the pack (half rows of a table with TFRA_OPTION_STOCHASTIC_ROUNDING): the parameter and the slots the rule owns are
+// rounded by to_stored4_sr, one hash word per lane, field and granule, formed between the rule and the store; the constant fill
+// of the other fields stays nearest-even.  Without one the pack's kernels compile the code they always did.
 // The body is one function with two callers — apply_csr_kernel (one table per launch) and apply_csr_many_kernel (a list of tables
 // per launch): blk = this block's index among the nblk blocks that work on THIS table's plan; they stand where the block index and
 // the grid size of the launch stood, and nothing else differs.
@@ -202,7 +208,9 @@ __device__ __forceinline__ void apply_csr_body(const TableView& v, OptP o, int d
                                                const float* __restrict__ default_row, float aux0, float aux1,
                                                const ScoreP& sp, uint8_t* __restrict__ dflag, unsigned* any_deferred,
                                                unsigned use_gen, unsigned blk, unsigned nblk, const CS... cs) {
-  constexpr bool COMB = sizeof...(CS) > 0;
+  constexpr bool COMB = (false || ... || std::is_same<CS, CombRows>::value);
+  constexpr bool STOCH = HasStoch<CS...>::v;
+  static_assert(!STOCH || ST != TFRA_F32, "stochastic rounding is of half rows");
   if (PHASE2 && *any_deferred != use_gen) return;   // phase 1 of this use deferred nothing
   constexpr int S = NSlots<KIND>::v;
   const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
@@ -289,10 +297,19 @@ __device__ __forceinline__ void apply_csr_body(const TableView& v, OptP o, int d
         apply_one<KIND>(o, gg.z, p.z, s1.z, s2.z);
         apply_one<KIND>(o, gg.w, p.w, s1.w, s2.w);
         // write-through, one rounding per element (PHASE2: in memory before publish_key)
+        if constexpr (STOCH) {
+          const u64 kb = sr_key(stoch_in(cs...), key);
+          if (col) {
+            store_wt8(sr + c, to_stored4_sr<ST>(p, sr_word(kb, (unsigned)c)));
+            if (S >= 1) store_wt8(sr + dim + c, to_stored4_sr<ST>(s1, sr_word(kb, (unsigned)(dim + c))));
+            if (S >= 2) store_wt8(sr + 2 * dim + c, to_stored4_sr<ST>(s2, sr_word(kb, (unsigned)(2 * dim + c))));
+          }
+        } else {
         if (col) {
           store_wt8(sr + c, to_stored4<ST>(p));
           if (S >= 1) store_wt8(sr + dim + c, to_stored4<ST>(s1));
           if (S >= 2) store_wt8(sr + 2 * dim + c, to_stored4<ST>(s2));
+        }
         }
       }
       // aux fields the optimizer does not own (table created with more slots than it uses)

@@ -100,6 +100,9 @@ Slices slices_of(const tfra_apply_combined_desc& d) {
   return Slices{(2 * d.n_rows + 63) / 64 * 64, (d.n_rows + 63) / 64 * 64, (d.plan->n + 15) / 16 * 16};
 }
 
+int apply_grouped(tfra_workspace_t* ws, const tfra_apply_combined_desc* descs, const std::vector<size_t>& act, uint32_t* launches_out,
+                  hipStream_t s);
+
 }  // namespace
 
 extern "C" int tfra_multi_apply_planned_combined(tfra_workspace_t* ws, size_t n_tables, const tfra_apply_combined_desc* descs,
@@ -124,8 +127,29 @@ extern "C" int tfra_multi_apply_planned_combined(tfra_workspace_t* ws, size_t n_
       if (descs[i].plan == descs[j].plan)
         return set_error(TFRA_ERR_INVALID, who + std::to_string(i) + " and descriptor " + std::to_string(j) + " name the same plan");
     }
+  // members whose table rounds stochastically (TFRA_OPTION_STOCHASTIC_ROUNDING): the grouped kernels have no rounding axis, so the
+  // single call's launches serve them, on the same stream, behind the grouped ones (whose table locks are released by then)
+  std::vector<size_t> grouped, single;
+  for (size_t i : act) (reinterpret_cast<const Table*>(descs[i].table)->stochastic() ? single : grouped).push_back(i);
+  if (!grouped.empty()) {
+    const int rc = apply_grouped(ws, descs, grouped, launches_out, s);
+    if (rc) return rc;
+  }
+  for (size_t i : single) {
+    const tfra_apply_combined_desc& d = descs[i];
+    const int rc = tfra_table_apply_planned_combined(d.table, d.opt, d.plan, d.grad_out, d.seg, d.weights, d.combiner, d.n_rows,
+                                                     d.param_default_row, stream);
+    if (rc) return rc;
+  }
+  return TFRA_OK;
+}
+
+namespace {
+
+// the grouped launches over act, the checked descriptors with work whose tables round to nearest even
+int apply_grouped(tfra_workspace_t* ws, const tfra_apply_combined_desc* descs, const std::vector<size_t>& act, uint32_t* launches_out,
+                  hipStream_t s) {
   const size_t n_act = act.size();
-  if (n_act == 0) return TFRA_OK;
 
   // classes: the sums by NCH (1..4), the update by (rule, storage type)
   constexpr int NHOT = 4, NAPP = 12;
@@ -255,8 +279,10 @@ extern "C" int tfra_multi_apply_planned_combined(tfra_workspace_t* ws, size_t n_
     }
   }
   if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "multi_apply_planned_combined: launch failed");
-  for (size_t i : act) reinterpret_cast<Table*>(descs[i].table)->step_epoch();
+  for (size_t i : act) reinterpret_cast<Table*>(descs[i].table)->step_writeback();
   if (launches_out) *launches_out = launches;
   return TFRA_OK;
 }
+
+}  // namespace
 

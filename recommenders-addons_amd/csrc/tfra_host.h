@@ -112,6 +112,8 @@ struct Table {
   uint64_t global_epoch = 0;
   int64_t curr_step = 1;
   bool epoch_hold = false;   // see step_epoch
+  uint64_t sr_seed = 0;      // TFRA_OPTION_STOCHASTIC_ROUNDING: 0 = off (nearest even), else the seed of the half rows' rounding bits
+  uint64_t sr_call = 0;      // fused write-backs since the option was set (step_writeback): the call index of the next one
   int n_rehash = 0;
 
   void* dalloc(size_t bytes, hipStream_t s);
@@ -146,6 +148,14 @@ struct Table {
     curr_step += 1;
     if (opts.step_per_epoch > 0 && curr_step > opts.step_per_epoch) { global_epoch += 1; curr_step = 1; }
   }
+  // behind a FUSED OPTIMIZER write-back that passed its checks and had work to do: step_epoch, and one call of the stochastic
+  // rounding's random stream (held like the epoch while one logical write-back is issued in parts)
+  void step_writeback() {
+    step_epoch();
+    if (!epoch_hold) sr_call += 1;
+  }
+  bool stochastic() const { return sr_seed != 0; }
+  StochP stoch_of() const { return StochP{sr_mix64(sr_seed + sr_call * SR_GAMMA)}; }   // `a` of this call (tfra_optim_device.h)
 };
 
 // The kernels' forms of a caller's optimizer parameters and of the table's score state.  at_capacity: whether Table::bounded_flags

@@ -26,13 +26,18 @@ namespace {
 // 16 lanes per key; lane `sub` owns elements sub*4..sub*4+3 (+64 per step): float4 everywhere
 // when dim % 4 == 0 (VEC4), scalar otherwise.
 // ST: storage type of the rows (tfra_dtype F32 / F16 / BF16); VEC4 only with float rows.
-template <int KIND, bool VEC4, int ST = TFRA_F32>
+// SR = StochP (half rows of a table with TFRA_OPTION_STOCHASTIC_ROUNDING): the parameter and the slots the rule owns are rounded by
+// to_stored_sr with the element's 16 bits of its granule's hash word — the bits the planned kernels store for the same (seed, call,
+// key); the constant fill of the other fields stays nearest-even.  None: the code the kernels always compiled to.
+template <int KIND, bool VEC4, int ST = TFRA_F32, class... SR>
 __global__ __launch_bounds__(256) void apply_kernel(TableView v, OptP o, size_t n, const i64* __restrict__ keys,
                                                     const float* __restrict__ grads,
                                                     const float* __restrict__ defaults, int full, int dim,
                                                     float aux0, float aux1, const i64* __restrict__ d_n,
-                                                    ScoreP sp, uint8_t* __restrict__ deferred) {
+                                                    ScoreP sp, uint8_t* __restrict__ deferred, const SR... sr) {
   constexpr int S = NSlots<KIND>::v;
+  constexpr bool STOCH = HasStoch<SR...>::v;
+  static_assert(!STOCH || ST != TFRA_F32, "stochastic rounding is of half rows");
   const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
   const size_t g = (((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4);
   int fresh = 0, failed = 0;
@@ -80,25 +85,33 @@ __global__ __launch_bounds__(256) void apply_kernel(TableView v, OptP o, size_t 
         }
       } else {
         typedef typename Stored<ST>::T V;
-        V* sr = reinterpret_cast<V*>(row_ptr(v, row));
+        V* row_s = reinterpret_cast<V*>(row_ptr(v, row));
         for (int c = sub; c < dim; c += 16) {
           float p, s1 = aux0, s2 = aux1;
           if (is_new) {
             p = df[c];
           } else {
-            p = load_stored<ST>(sr + c);
-            if (S >= 1) s1 = load_stored<ST>(sr + dim + c);
-            if (S >= 2) s2 = load_stored<ST>(sr + 2 * dim + c);
+            p = load_stored<ST>(row_s + c);
+            if (S >= 1) s1 = load_stored<ST>(row_s + dim + c);
+            if (S >= 2) s2 = load_stored<ST>(row_s + 2 * dim + c);
           }
           apply_one<KIND>(o, gr[c], p, s1, s2);
-          sr[c] = to_stored<ST>(p);
-          if (S >= 1) sr[dim + c] = to_stored<ST>(s1);
-          if (S >= 2) sr[2 * dim + c] = to_stored<ST>(s2);
+          if constexpr (STOCH) {
+            const u64 kb = sr_key(stoch_in(sr...), key);
+            const unsigned e0 = (unsigned)c, e1 = (unsigned)(dim + c), e2 = (unsigned)(2 * dim + c);
+            row_s[c] = to_stored_sr<ST>(p, sr_bits(sr_word(kb, e0), e0));
+            if (S >= 1) row_s[dim + c] = to_stored_sr<ST>(s1, sr_bits(sr_word(kb, e1), e1));
+            if (S >= 2) row_s[2 * dim + c] = to_stored_sr<ST>(s2, sr_bits(sr_word(kb, e2), e2));
+          } else {
+          row_s[c] = to_stored<ST>(p);
+          if (S >= 1) row_s[dim + c] = to_stored<ST>(s1);
+          if (S >= 2) row_s[2 * dim + c] = to_stored<ST>(s2);
+          }
         }
         // aux fields the optimizer does not own (table created with more slots than it uses)
         if (is_new && (int)v.n_fields - 1 > S) {
           for (int f = S + 1; f < (int)v.n_fields; ++f)
-            for (int c = sub; c < dim; c += 16) sr[f * dim + c] = to_stored<ST>(f == 1 ? aux0 : aux1);
+            for (int c = sub; c < dim; c += 16) row_s[f * dim + c] = to_stored<ST>(f == 1 ? aux0 : aux1);
         }
       }
       // aux fields the optimizer does not own (table created with more slots than it uses)
@@ -123,13 +136,15 @@ __global__ __launch_bounds__(256) void apply_kernel(TableView v, OptP o, size_t 
 // minimum-score entry of its two home buckets and starts from the default row / initial slot values —
 // what find (miss -> default) + dense apply + upsert (evicting) give in the reference
 // (PY/dynamic_embedding_optimizer.py:165-204 on an HkvHashTable, lookup_table_op_hkv.h:522-537).
-template <int KIND, int ST = TFRA_F32>
+template <int KIND, int ST = TFRA_F32, class... SR>
 __global__ __launch_bounds__(256) void apply_evict_kernel(TableView v, OptP o, size_t n, const i64* __restrict__ keys,
                                                           const float* __restrict__ grads,
                                                           const float* __restrict__ defaults, int full, int dim,
                                                           float aux0, float aux1, const i64* __restrict__ d_n,
-                                                          ScoreP sp, const uint8_t* __restrict__ deferred) {
+                                                          ScoreP sp, const uint8_t* __restrict__ deferred, const SR... sr) {
   constexpr int S = NSlots<KIND>::v;
+  constexpr bool STOCH = HasStoch<SR...>::v;
+  static_assert(!STOCH || ST != TFRA_F32, "stochastic rounding is of half rows");
   const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
   const size_t g = (((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4);
   int fresh = 0, failed = 0;
@@ -152,9 +167,20 @@ __global__ __launch_bounds__(256) void apply_evict_kernel(TableView v, OptP o, s
       for (int c = sub; c < dim; c += 16) {
         float p = df[c], s1 = aux0, s2 = aux1;
         apply_one<KIND>(o, gr[c], p, s1, s2);
+        if constexpr (STOCH) {
+          const u64 kb = sr_key(stoch_in(sr...), key);
+          auto st_sr = [&](int f, float x) {
+            const unsigned e = (unsigned)(f * dim + c);
+            __hip_atomic_store(pr + e, to_stored_sr<ST>(x, sr_bits(sr_word(kb, e), e)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          };
+          st_sr(0, p);
+          if (S >= 1) st_sr(1, s1);
+          if (S >= 2) st_sr(2, s2);
+        } else {
         st(pr + c, p);
         if (S >= 1) st(pr + dim + c, s1);
         if (S >= 2) st(pr + 2 * dim + c, s2);
+        }
       }
       for (int f = S + 1; f < (int)v.n_fields; ++f)
         for (int c = sub; c < dim; c += 16) st(pr + f * dim + c, (f == 1 ? aux0 : aux1));
@@ -175,15 +201,20 @@ __global__ __launch_bounds__(256) void apply_evict_kernel(TableView v, OptP o, s
 
 template <int KIND>
 void launch_apply(int dt, bool vec4, dim3 grid, hipStream_t s, TableView v, OptP o, size_t n, const i64* k, const float* g,
-                  const float* d, int full, int dim, float a0, float a1, const i64* dn, ScoreP sp, uint8_t* deferred) {
-  if (dt == TFRA_F16) {
-    apply_kernel<KIND, false, TFRA_F16><<<grid, 256, 0, s>>>(v, o, n, k, g, d, full, dim, a0, a1, dn, sp, deferred);
-    if (deferred) apply_evict_kernel<KIND, TFRA_F16><<<grid, 256, 0, s>>>(v, o, n, k, g, d, full, dim, a0, a1, dn, sp, deferred);
-    return;
-  }
-  if (dt == TFRA_BF16) {
-    apply_kernel<KIND, false, TFRA_BF16><<<grid, 256, 0, s>>>(v, o, n, k, g, d, full, dim, a0, a1, dn, sp, deferred);
-    if (deferred) apply_evict_kernel<KIND, TFRA_BF16><<<grid, 256, 0, s>>>(v, o, n, k, g, d, full, dim, a0, a1, dn, sp, deferred);
+                  const float* d, int full, int dim, float a0, float a1, const i64* dn, ScoreP sp, uint8_t* deferred,
+                  const StochP* sr) {   // sr: null = nearest even
+  // half rows; xs: nothing, or the StochP of a table that rounds stochastically
+  auto half = [&](auto ST, const auto&... xs) {
+    apply_kernel<KIND, false, ST><<<grid, 256, 0, s>>>(v, o, n, k, g, d, full, dim, a0, a1, dn, sp, deferred, xs...);
+    if (deferred) apply_evict_kernel<KIND, ST><<<grid, 256, 0, s>>>(v, o, n, k, g, d, full, dim, a0, a1, dn, sp, deferred, xs...);
+  };
+  if (dt == TFRA_F16 || dt == TFRA_BF16) {
+    with_stored(st_index(dt), [&](auto ST) {
+      if constexpr (decltype(ST)::value != TFRA_F32) {
+        if (sr) half(ST, *sr);
+        else half(ST);
+      }
+    });
     return;
   }
   if (vec4) apply_kernel<KIND, true><<<grid, 256, 0, s>>>(v, o, n, k, g, d, full, dim, a0, a1, dn, sp, deferred);
@@ -200,6 +231,9 @@ extern "C" int tfra_table_apply_optimizer(tfra_table_t* tp, const tfra_opt_param
   if (!t || !p) return set_error(TFRA_ERR_INVALID, "apply_optimizer: null argument");
   hipStream_t s = (hipStream_t)stream;
   std::lock_guard<std::mutex> lock(t->mu);
+  if (t->stochastic() && t->capture_safe)
+    return set_error(TFRA_ERR_UNSUPPORTED, "apply_optimizer: TFRA_OPTION_STOCHASTIC_ROUNDING and TFRA_OPTION_CAPTURE_SAFE are both set "
+                                           "(a replayed graph would reuse one call index)");
   int rc = t->enter(s);
   if (rc) return rc;
   if (n == 0) return TFRA_OK;
@@ -226,13 +260,15 @@ extern "C" int tfra_table_apply_optimizer(tfra_table_t* tp, const tfra_opt_param
   rc = t->bounded_flags(n, s, &deferred);
   if (rc) return rc;
   const ScoreP sp = score_of(t, deferred);
+  const StochP sr_now = t->stoch_of();
+  const StochP* sr = t->stochastic() ? &sr_now : nullptr;
   switch (p->kind) {
-    case TFRA_OPT_SGD: launch_apply<TFRA_OPT_SGD>(dt, vec4, grid, s, v, o, n, k, grads, d, default_is_full, dim, a0, a1, (const i64*)d_n, sp, deferred); break;
-    case TFRA_OPT_ADAM: launch_apply<TFRA_OPT_ADAM>(dt, vec4, grid, s, v, o, n, k, grads, d, default_is_full, dim, a0, a1, (const i64*)d_n, sp, deferred); break;
-    case TFRA_OPT_ADAGRAD: launch_apply<TFRA_OPT_ADAGRAD>(dt, vec4, grid, s, v, o, n, k, grads, d, default_is_full, dim, a0, a1, (const i64*)d_n, sp, deferred); break;
-    default: launch_apply<TFRA_OPT_FTRL>(dt, vec4, grid, s, v, o, n, k, grads, d, default_is_full, dim, a0, a1, (const i64*)d_n, sp, deferred); break;
+    case TFRA_OPT_SGD: launch_apply<TFRA_OPT_SGD>(dt, vec4, grid, s, v, o, n, k, grads, d, default_is_full, dim, a0, a1, (const i64*)d_n, sp, deferred, sr); break;
+    case TFRA_OPT_ADAM: launch_apply<TFRA_OPT_ADAM>(dt, vec4, grid, s, v, o, n, k, grads, d, default_is_full, dim, a0, a1, (const i64*)d_n, sp, deferred, sr); break;
+    case TFRA_OPT_ADAGRAD: launch_apply<TFRA_OPT_ADAGRAD>(dt, vec4, grid, s, v, o, n, k, grads, d, default_is_full, dim, a0, a1, (const i64*)d_n, sp, deferred, sr); break;
+    default: launch_apply<TFRA_OPT_FTRL>(dt, vec4, grid, s, v, o, n, k, grads, d, default_is_full, dim, a0, a1, (const i64*)d_n, sp, deferred, sr); break;
   }
-  t->step_epoch();   // one fused write-back counts as one upsert
+  t->step_writeback();   // one fused write-back counts as one upsert, and as one call of the rounding's random stream
   if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "apply_optimizer: launch failed");
   return TFRA_OK;
 }

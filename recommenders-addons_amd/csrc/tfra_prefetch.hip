@@ -46,6 +46,9 @@ static int step_prefetch_impl(tfra_table_t* tp, const tfra_opt_params* p, tfra_s
   if (plan_next == plan_cur) return set_error(TFRA_ERR_INVALID, "step_prefetch: plan_next must differ from plan_cur");
   std::lock_guard<std::mutex> step_lock(t->step_mu);   // one driver call at a time per table
   int rc = TFRA_OK;
+  if (p && t->stochastic() && t->capture_safe)   // the write-back would refuse it (check_rounding) behind the lookup: refuse in front
+    return set_error(TFRA_ERR_UNSUPPORTED, "step_prefetch: TFRA_OPTION_STOCHASTIC_ROUNDING and TFRA_OPTION_CAPTURE_SAFE are both set "
+                                           "(a replayed graph would reuse one call index)");
   if (!pinned_on_first_use(&t->progress_host, 64)) return set_error(TFRA_ERR_OOM, "step_prefetch: hipHostMalloc");
   const unsigned step = ++t->step_gen;
   if (plan_next) {

@@ -429,6 +429,13 @@ int tfra_table_set_option(tfra_table_t* tp, int option, int64_t value) {
     t->key_file_bytes = (int)value;
     return TFRA_OK;
   }
+  if (option == TFRA_OPTION_STOCHASTIC_ROUNDING) {
+    if (value != 0 && t->opts.value_dtype != TFRA_F16 && t->opts.value_dtype != TFRA_BF16)
+      return set_error(TFRA_ERR_UNSUPPORTED, "set_option: TFRA_OPTION_STOCHASTIC_ROUNDING needs a float16 or bfloat16 table");
+    t->sr_seed = (uint64_t)value;
+    t->sr_call = 0;
+    return TFRA_OK;
+  }
   return set_error(TFRA_ERR_INVALID, "unknown option");
 }
 

@@ -20,6 +20,7 @@ RAGGED_PRUNE, RAGGED_FILL = 1, 2   # TFRA_RAGGED_* (flags of the ragged pooled l
 OPTION_CAPTURE_SAFE = 1
 OPTION_NO_OWNER_TAGS = 2
 OPTION_KEY_BYTES_ON_DISK = 3
+OPTION_STOCHASTIC_ROUNDING = 4
 SCORE_GE, SCORE_LT = 0, 1   # tfra_score_pred
 ERR_UNSUPPORTED = -6
 

@@ -506,6 +506,9 @@ class CapturedTrainStep:
     if var.shard_num != 1:
       raise ValueError("CapturedTrainStep needs a single-shard Variable")
     _refuse_init_on_lookup(var, "CapturedTrainStep")
+    if getattr(var, "stochastic_rounding", None):
+      raise ValueError("CapturedTrainStep does not serve a Variable with stochastic_rounding: the rounding's call index advances "
+                       "on the host, a replayed graph would reuse one set of random bits")
     self.var, self.deo, self.batch = var, optimizer, int(batch)
     self.table = var.tables[0]._table
     dev = self.table.device

@@ -57,6 +57,7 @@ class _DeviceTable:
     self._value_dtype = value_dtype
     self._device = _as_device(device)
     self._name = name
+    self.stochastic_rounding = 0   # the seed of set_stochastic_rounding (0: off)
     dv = torch.as_tensor(default_value, dtype=value_dtype).reshape(-1)
     if dim is None:
       dim = dv.numel()
@@ -514,6 +515,15 @@ class _DeviceTable:
     """While True every op on this table can be captured into a HIP graph (no host sync, no growth)."""
     _capi.call("tfra_table_set_option", self._h, _capi.OPTION_CAPTURE_SAFE, int(bool(on)))
 
+  def set_stochastic_rounding(self, seed):
+    """seed: None or 0 = off (the default: nearest even); any other 64-bit value: the fused optimizer write-backs of this float16 /
+    bfloat16 table round the parameter and the slots the rule owns stochastically, with random bits that are a pure function of
+    (seed, write-backs since this call, key, element) — TFRA_OPTION_STOCHASTIC_ROUNDING.  Every call restarts the count at 0.
+    Upserts, insert_or_accum, the constant fill of fields the rule does not own and the Generic optimizers keep nearest even."""
+    seed = 0 if seed is None else int(seed) & ((1 << 64) - 1)
+    _capi.call("tfra_table_set_option", self._h, _capi.OPTION_STOCHASTIC_ROUNDING, seed - (1 << 64) if seed >> 63 else seed)
+    self.stochastic_rounding = seed
+
   def set_owner_tags(self, on):
     """False: planned write-backs take the general two-kernel path (what runs when the tag array cannot be allocated)."""
     _capi.call("tfra_table_set_option", self._h, _capi.OPTION_NO_OWNER_TAGS, int(not on))
@@ -957,6 +967,12 @@ class _LookupInterfaceMirror:
 
   def clear(self, name=None):
     self._table.clear_all()
+
+  def set_stochastic_rounding(self, seed):
+    """Stochastic rounding of the fused optimizer write-backs of a float16 / bfloat16 table (`_DeviceTable.set_stochastic_rounding`):
+    seed None or 0 = off.  A tiered table sets its cache table, where the write-backs land; rows that move between the tiers
+    are copied, not rounded."""
+    self._table.set_stochastic_rounding(seed)
 
   def lookup(self, keys, dynamic_default_values=None, return_exists=False, name=None):
     """PY/cuckoo_hashtable_ops.py:272-340"""

@@ -165,7 +165,8 @@ class Variable:
   def __init__(self, key_dtype=torch.int64, value_dtype=torch.float32, dim=1, devices=None,
                partitioner=default_partition_fn, shared_name=None, name="DynamicEmbedding_Variable", initializer=None,
                trainable=True, checkpoint=True, init_size=0, kv_creator=None, restrict_policy=None, bp_v2=False,
-               short_file_name=False, aux_fields=0, aux_init=(0.0, 0.0, 0.0, 0.0), init_on_lookup=False):
+               short_file_name=False, aux_fields=0, aux_init=(0.0, 0.0, 0.0, 0.0), init_on_lookup=False,
+               stochastic_rounding=None):
     self.key_dtype = key_dtype
     if isinstance(init_on_lookup, str) or init_on_lookup not in (False, True):
       if init_on_lookup not in ("plan", "pooled"):
@@ -202,6 +203,9 @@ class Variable:
                                  name=self._make_name(idx), checkpoint=checkpoint, init_size=self.init_size, device=dev,
                                  dim=self.dim, aux_fields=aux_fields, aux_init=aux_init))
     self._primary = _as_device(self.devices[0])
+    self.stochastic_rounding = None
+    if stochastic_rounding:
+      self.set_stochastic_rounding(stochastic_rounding)
     # PY/dynamic_embedding_variable.py:604-611: the policy CLASS is passed, instantiated on this variable
     if restrict_policy is not None:
       from .restrict_policies import RestrictPolicy
@@ -323,6 +327,17 @@ class Variable:
   def clear(self, name=None):
     for t in self._tables:
       t.clear()
+
+  def set_stochastic_rounding(self, seed):
+    """seed None or 0: off (the default).  Otherwise the fused optimizer write-backs (SGD, Adam, Adagrad, Ftrl) of this float16 /
+    bfloat16 variable round the parameter and the slots stochastically instead of to nearest even, so that updates below half a
+    storage ulp are kept in the mean; shard i takes seed + i.  The stored bits are a pure function of (seed, write-backs since
+    this call, key, element).  Not for CapturedTrainStep (a replayed graph would reuse one set of random bits); the Generic
+    optimizers ignore it."""
+    seed = 0 if seed is None else int(seed)
+    for i, t in enumerate(self._tables):
+      t.set_stochastic_rounding((seed + i) & ((1 << 64) - 1) if seed else 0)
+    self.stochastic_rounding = seed or None
 
   def _create_default_values_by_initializer(self, n, device):
     """PY/dynamic_embedding_variable.py:919-931: full-size [n,dim] defaults from the initializer."""
