@@ -456,11 +456,23 @@ int tfra_table_load_field(tfra_table_t* t, int field, const char* prefix, size_t
  * results are rounded to the storage type once, to nearest even — or stochastically, on a table with
  * TFRA_OPTION_STOCHASTIC_ROUNDING; a new row starts from the float32 default row and aux_init values, not from their
  * rounded images).                                                                            */
-typedef enum { TFRA_OPT_SGD = 0, TFRA_OPT_ADAM = 1, TFRA_OPT_ADAGRAD = 2, TFRA_OPT_FTRL = 3 } tfra_opt_kind;
+typedef enum {
+  TFRA_OPT_SGD = 0, TFRA_OPT_ADAM = 1, TFRA_OPT_ADAGRAD = 2, TFRA_OPT_FTRL = 3,
+  TFRA_OPT_MOMENTUM = 4, TFRA_OPT_NESTEROV = 5, TFRA_OPT_RMSPROP = 6
+} tfra_opt_kind;
+/* The three later kinds use the fields the struct already has (it has no size field, so it does not grow; ABI version 1):
+ *   MOMENTUM / NESTEROV (ResourceApplyMomentum, use_nesterov = false / true): lr, beta1 = momentum.  One slot: field 1 = accum,
+ *     aux_init[0] = 0.   accum = accum * beta1 + g;  p -= accum * lr   |   p -= g * lr + accum * (beta1 * lr)
+ *   RMSPROP (ResourceApplyRMSProp, non-centered): lr, beta1 = momentum, eps, and beta2 = 1 - rho — ALREADY SUBTRACTED by the
+ *     caller, in double, and rounded to float once: (float)(1.0 - rho).  That is the constant TF's kernel and the oracle multiply
+ *     by; 1.f - (float)rho is another float for rho = 0.9.  Two slots: field 1 = ms (aux_init[0] = initial_rms), field 2 = mom
+ *     (aux_init[1] = 0).   ms += (g * g - ms) * beta2;  mom = mom * beta1 + (g * lr) / sqrt(ms + eps);  p -= mom
+ * d_lr overrides lr for these as for the others (Nesterov's beta1 * lr is formed in the kernel, from the lr in force).
+ * Every call below that takes a tfra_opt_params accepts all seven kinds on all of its paths and refuses any other value. */
 typedef struct {
   int32_t kind;     /* tfra_opt_kind */
   float lr;         /* Adam: pass lr_t = lr*sqrt(1-b2^t)/(1-b1^t) computed by the host (global step) */
-  float beta1, beta2, eps;          /* Adam; Adagrad: eps<0 -> TF1 rule (no eps)             */
+  float beta1, beta2, eps;          /* Adam; Adagrad: eps<0 -> TF1 rule (no eps); Momentum / Nesterov / RMSProp: see above */
   float l1, l2, lr_power;           /* FTRL                                                  */
   const float* d_lr;                /* optional DEVICE scalar overriding `lr` (read by the kernel):
                                        lets a captured hipGraph follow a learning-rate schedule /

@@ -44,8 +44,8 @@ static Check check_apply_planned(const Table* t, const tfra_opt_params* p, const
   const int dt = t->opts.value_dtype;
   if (dt != TFRA_F32 && dt != TFRA_F16 && dt != TFRA_BF16)
     return refuse(TFRA_ERR_UNSUPPORTED, "value_dtype must be float32, float16 or bfloat16 (gradients and the default row are float32)");
-  if (p->kind < 0 || p->kind > TFRA_OPT_FTRL) return refuse(TFRA_ERR_INVALID, "unknown kind");
-  const int need = p->kind == TFRA_OPT_SGD ? 0 : (p->kind == TFRA_OPT_ADAGRAD ? 1 : 2);
+  if (p->kind < 0 || p->kind > TFRA_OPT_RMSPROP) return refuse(TFRA_ERR_INVALID, "unknown kind");
+  const int need = opt_slots(p->kind);
   if (t->opts.aux_fields < need) return refuse(TFRA_ERR_INVALID, "table lacks optimizer slot fields");
   if (t->opts.dim != pl->dim) return refuse(TFRA_ERR_INVALID, "the plan was built for another dim");
   if (t->opts.device != pl->device && t->opts.device >= 0) return refuse(TFRA_ERR_INVALID, "plan and table live on different devices");

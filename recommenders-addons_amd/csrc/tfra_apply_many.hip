@@ -152,7 +152,7 @@ int apply_grouped(tfra_workspace_t* ws, const tfra_apply_combined_desc* descs, c
   const size_t n_act = act.size();
 
   // classes: the sums by NCH (1..4), the update by (rule, storage type)
-  constexpr int NHOT = 4, NAPP = 12;
+  constexpr int NHOT = 4, NAPP = (TFRA_OPT_RMSPROP + 1) * 3;   // (check_apply_planned has refused every other kind)
   auto ent_blocks_of = [&](size_t k) { return (unsigned)((descs[act[k]].plan->n + 255) / 256); };
   auto den_blocks_of = [&](size_t k) { return (unsigned)((descs[act[k]].n_rows + 255) / 256); };
   std::vector<int> hot_of(n_act), app_of(n_act);

@@ -254,7 +254,10 @@ static inline void with_opt_kind(int kind, F&& f) {
     case TFRA_OPT_SGD: f(std::integral_constant<int, TFRA_OPT_SGD>{}); break;
     case TFRA_OPT_ADAM: f(std::integral_constant<int, TFRA_OPT_ADAM>{}); break;
     case TFRA_OPT_ADAGRAD: f(std::integral_constant<int, TFRA_OPT_ADAGRAD>{}); break;
-    default: f(std::integral_constant<int, TFRA_OPT_FTRL>{}); break;
+    case TFRA_OPT_MOMENTUM: f(std::integral_constant<int, TFRA_OPT_MOMENTUM>{}); break;
+    case TFRA_OPT_NESTEROV: f(std::integral_constant<int, TFRA_OPT_NESTEROV>{}); break;
+    case TFRA_OPT_RMSPROP: f(std::integral_constant<int, TFRA_OPT_RMSPROP>{}); break;
+    default: f(std::integral_constant<int, TFRA_OPT_FTRL>{}); break;   // (the callers have refused every kind that is not one of the seven)
   }
 }
 

@@ -241,8 +241,8 @@ extern "C" int tfra_table_apply_optimizer(tfra_table_t* tp, const tfra_opt_param
   const int dt = t->opts.value_dtype;
   if (dt != TFRA_F32 && dt != TFRA_F16 && dt != TFRA_BF16)
     return set_error(TFRA_ERR_UNSUPPORTED, "apply_optimizer: value_dtype must be float32, float16 or bfloat16 (gradients and defaults are float32)");
-  int need = p->kind == TFRA_OPT_SGD ? 0 : (p->kind == TFRA_OPT_ADAGRAD ? 1 : 2);
-  if (p->kind < 0 || p->kind > TFRA_OPT_FTRL) return set_error(TFRA_ERR_INVALID, "apply_optimizer: unknown kind");
+  if (p->kind < 0 || p->kind > TFRA_OPT_RMSPROP) return set_error(TFRA_ERR_INVALID, "apply_optimizer: unknown kind");
+  const int need = opt_slots(p->kind);
   if (t->opts.aux_fields < need)
     return set_error(TFRA_ERR_INVALID, "apply_optimizer: table has " + std::to_string(t->opts.aux_fields) +
                                            " aux fields, optimizer needs " + std::to_string(need));
@@ -266,6 +266,9 @@ extern "C" int tfra_table_apply_optimizer(tfra_table_t* tp, const tfra_opt_param
     case TFRA_OPT_SGD: launch_apply<TFRA_OPT_SGD>(dt, vec4, grid, s, v, o, n, k, grads, d, default_is_full, dim, a0, a1, (const i64*)d_n, sp, deferred, sr); break;
     case TFRA_OPT_ADAM: launch_apply<TFRA_OPT_ADAM>(dt, vec4, grid, s, v, o, n, k, grads, d, default_is_full, dim, a0, a1, (const i64*)d_n, sp, deferred, sr); break;
     case TFRA_OPT_ADAGRAD: launch_apply<TFRA_OPT_ADAGRAD>(dt, vec4, grid, s, v, o, n, k, grads, d, default_is_full, dim, a0, a1, (const i64*)d_n, sp, deferred, sr); break;
+    case TFRA_OPT_MOMENTUM: launch_apply<TFRA_OPT_MOMENTUM>(dt, vec4, grid, s, v, o, n, k, grads, d, default_is_full, dim, a0, a1, (const i64*)d_n, sp, deferred, sr); break;
+    case TFRA_OPT_NESTEROV: launch_apply<TFRA_OPT_NESTEROV>(dt, vec4, grid, s, v, o, n, k, grads, d, default_is_full, dim, a0, a1, (const i64*)d_n, sp, deferred, sr); break;
+    case TFRA_OPT_RMSPROP: launch_apply<TFRA_OPT_RMSPROP>(dt, vec4, grid, s, v, o, n, k, grads, d, default_is_full, dim, a0, a1, (const i64*)d_n, sp, deferred, sr); break;
     default: launch_apply<TFRA_OPT_FTRL>(dt, vec4, grid, s, v, o, n, k, grads, d, default_is_full, dim, a0, a1, (const i64*)d_n, sp, deferred, sr); break;
   }
   t->step_writeback();   // one fused write-back counts as one upsert, and as one call of the rounding's random stream

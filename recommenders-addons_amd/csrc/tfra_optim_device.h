@@ -1,5 +1,5 @@
 // Optimizer update rules shared by the fused write-back kernels (tfra_optim.hip,
-// tfra_apply_device.h), and the kernels' parameter records OptP / ScoreP (formed on the host by opt_of / score_of, tfra_host.h).  TF's ResourceApply{GradientDescent,Adam,Adagrad[V2],Ftrl}, fp32, same
+// tfra_apply_device.h), and the kernels' parameter records OptP / ScoreP (formed on the host by opt_of / score_of, tfra_host.h).  TF's ResourceApply{GradientDescent,Adam,Adagrad[V2],Ftrl,Momentum,RMSProp}, fp32, same
 // operation order as oracle/optimizers.py; compile with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -21,6 +21,7 @@ __device__ __forceinline__ float sgnf(float z) { return (z > 0.f) ? 1.f : ((z < 
 
 template <int KIND>
 __device__ __forceinline__ void apply_one(const OptP& o, float g, float& p, float& s1, float& s2) {
+  static_assert(KIND >= TFRA_OPT_SGD && KIND <= TFRA_OPT_RMSPROP, "apply_one: a kind without a rule (the last branch is FTRL's alone)");
   if (KIND == TFRA_OPT_SGD) {
     p = p - o.lr * g;
   } else if (KIND == TFRA_OPT_ADAM) {
@@ -32,6 +33,16 @@ __device__ __forceinline__ void apply_one(const OptP& o, float g, float& p, floa
     s1 = s1 + g * g;
     if (o.eps < 0.f) p = p - o.lr * g / sqrtf(s1);
     else p = p - o.lr * g / (sqrtf(s1) + o.eps);
+  } else if (KIND == TFRA_OPT_MOMENTUM) {   // ResourceApplyMomentum: s1 = accum
+    s1 = s1 * o.beta1 + g;
+    p = p - s1 * o.lr;
+  } else if (KIND == TFRA_OPT_NESTEROV) {   // ... with use_nesterov; beta1 * lr is rounded once, from the lr in force (d_lr)
+    s1 = s1 * o.beta1 + g;
+    p = p - (g * o.lr + s1 * (o.beta1 * o.lr));
+  } else if (KIND == TFRA_OPT_RMSPROP) {    // ResourceApplyRMSProp: s1 = ms, s2 = mom; beta2 carries 1 - rho (tfra_mi355x.h)
+    s1 = s1 + (g * g - s1) * o.beta2;
+    s2 = s2 * o.beta1 + (g * o.lr) / sqrtf(s1 + o.eps);
+    p = p - s2;
   } else {  // FTRL: s1 = accum, s2 = linear
     float a_new = s1 + g * g;
     float pa_new, pa;
@@ -147,7 +158,11 @@ __device__ __forceinline__ StochP stoch_in(const XS&... xs) {
 // score strategy of the table + its current epoch (update_score)
 struct ScoreP { int strategy; u64 epoch; int bounded; };  // bounded: 0 / 1 / 2 (dense), see locate_or_claim_from
 
-template <int KIND> struct NSlots { static constexpr int v = KIND == TFRA_OPT_SGD ? 0 : (KIND == TFRA_OPT_ADAGRAD ? 1 : 2); };
+// Slot fields a rule owns — the ONE place: the kernels (NSlots) and the hosts' argument checks both read it
+constexpr int opt_slots(int kind) {
+  return kind == TFRA_OPT_SGD ? 0 : (kind == TFRA_OPT_ADAGRAD || kind == TFRA_OPT_MOMENTUM || kind == TFRA_OPT_NESTEROV) ? 1 : 2;
+}
+template <int KIND> struct NSlots { static constexpr int v = opt_slots(KIND); };
 
 
 }  // namespace tfra

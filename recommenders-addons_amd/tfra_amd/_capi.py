@@ -15,7 +15,7 @@ FLAG_UNIQUE_KEYS = 1
 EVICT_WHOLE_ROWS = 1   # TFRA_EVICT_WHOLE_ROWS (flag of tfra_table_insert_and_evict)
 INSERT_WHOLE_ROWS = 2  # TFRA_INSERT_WHOLE_ROWS (flag of tfra_table_insert_and_evict_n)
 TIER_VERIFY = 1        # TFRA_TIER_VERIFY (flag of tfra_tier_find_or_insert)
-OPT_SGD, OPT_ADAM, OPT_ADAGRAD, OPT_FTRL = range(4)
+OPT_SGD, OPT_ADAM, OPT_ADAGRAD, OPT_FTRL, OPT_MOMENTUM, OPT_NESTEROV, OPT_RMSPROP = range(7)   # tfra_opt_kind
 RAGGED_PRUNE, RAGGED_FILL = 1, 2   # TFRA_RAGGED_* (flags of the ragged pooled lookup)
 OPTION_CAPTURE_SAFE = 1
 OPTION_NO_OWNER_TAGS = 2

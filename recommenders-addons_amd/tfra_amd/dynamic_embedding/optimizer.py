@@ -123,7 +123,7 @@ class Generic(_Opt):
   sum the gradients of repeated ids, (1+S) table finds, the rule on the dense [U, dim] tensors — host-framework
   math, as TF's ResourceApply* kernels are for the reference — and (1+S) table upserts.  Subclass and implement
   `update(step, p, g, *slots) -> (p_new, *slots_new)` (fp32 torch tensors), or pass `update=`.  The four rules
-  with a fused HIP kernel (SGD, Adam, Adagrad, Ftrl) do not take this path."""
+  with a fused HIP kernel (SGD, Adam, Adagrad, Ftrl) do not take this path, nor do Momentum / RMSProp created with fused=True."""
   kind = None
 
   def __init__(self, slots=(), slot_init=(), update=None):
@@ -146,11 +146,23 @@ class Generic(_Opt):
 
 class Momentum(Generic):
   """tf.train.MomentumOptimizer (ResourceApplyMomentum / Keras SGD with momentum): accum = momentum*accum + g;
-  p -= lr*accum, or with use_nesterov: p -= lr*g + lr*momentum*accum."""
+  p -= lr*accum, or with use_nesterov: p -= lr*g + lr*momentum*accum.
+  fused=False (the default): the `Generic` route, `update` on dense tensors.  fused=True: the fused HIP write-backs
+  (TFRA_OPT_MOMENTUM / TFRA_OPT_NESTEROV), as for SGD, Adam, Adagrad and Ftrl — same slots, same rows, so a variable trained
+  through one form continues through the other."""
 
-  def __init__(self, learning_rate=0.01, momentum=0.9, use_nesterov=False):
+  def __init__(self, learning_rate=0.01, momentum=0.9, use_nesterov=False, fused=False):
     super().__init__(slots=("momentum",), slot_init=(0.0,))
     self.lr, self.momentum, self.nesterov = learning_rate, momentum, use_nesterov
+    if fused:
+      self.kind = _capi.OPT_NESTEROV if use_nesterov else _capi.OPT_MOMENTUM
+
+  def params(self, step):
+    if self.kind is None:
+      return None
+    p = _capi.OptParams()
+    p.kind, p.lr, p.beta1 = self.kind, self.lr, self.momentum
+    return p
 
   def update(self, step, p, g, accum):
     accum = accum * self.momentum + g
@@ -163,11 +175,23 @@ class Momentum(Generic):
 
 class RMSProp(Generic):
   """tf.train.RMSPropOptimizer (ResourceApplyRMSProp, non-centered): ms = rho*ms + (1-rho)*g^2;
-  mom = momentum*mom + lr*g/sqrt(ms + eps); p -= mom.  `rms` starts at 1 (TF1) — pass initial_rms=0 for Keras."""
+  mom = momentum*mom + lr*g/sqrt(ms + eps); p -= mom.  `rms` starts at 1 (TF1) — pass initial_rms=0 for Keras.
+  fused=False (the default): the `Generic` route.  fused=True: the fused HIP write-backs (TFRA_OPT_RMSPROP); same slots and rows."""
 
-  def __init__(self, learning_rate=0.001, decay=0.9, momentum=0.0, epsilon=1e-10, initial_rms=1.0):
+  def __init__(self, learning_rate=0.001, decay=0.9, momentum=0.0, epsilon=1e-10, initial_rms=1.0, fused=False):
     super().__init__(slots=("rms", "momentum"), slot_init=(initial_rms, 0.0))
     self.lr, self.rho, self.momentum, self.eps = learning_rate, decay, momentum, epsilon
+    if fused:
+      self.kind = _capi.OPT_RMSPROP
+
+  def params(self, step):
+    if self.kind is None:
+      return None
+    p = _capi.OptParams()
+    # beta2 carries 1 - rho, subtracted HERE in double and rounded to float once by the c_float (include/tfra_mi355x.h): the
+    # constant ResourceApplyRMSProp multiplies by.  float32(1) - float32(rho) is another number for rho = 0.9.
+    p.kind, p.lr, p.beta1, p.beta2, p.eps = self.kind, self.lr, self.momentum, 1.0 - self.rho, self.eps
+    return p
 
   def update(self, step, p, g, ms, mom):
     ms = ms + (g * g - ms) * (1.0 - self.rho)

@@ -519,7 +519,8 @@ class _DeviceTable:
     """seed: None or 0 = off (the default: nearest even); any other 64-bit value: the fused optimizer write-backs of this float16 /
     bfloat16 table round the parameter and the slots the rule owns stochastically, with random bits that are a pure function of
     (seed, write-backs since this call, key, element) — TFRA_OPTION_STOCHASTIC_ROUNDING.  Every call restarts the count at 0.
-    Upserts, insert_or_accum, the constant fill of fields the rule does not own and the Generic optimizers keep nearest even."""
+    Upserts, insert_or_accum, the constant fill of fields the rule does not own and the Generic optimizers
+    (Momentum / RMSProp without fused=True among them) keep nearest even."""
     seed = 0 if seed is None else int(seed) & ((1 << 64) - 1)
     _capi.call("tfra_table_set_option", self._h, _capi.OPTION_STOCHASTIC_ROUNDING, seed - (1 << 64) if seed >> 63 else seed)
     self.stochastic_rounding = seed

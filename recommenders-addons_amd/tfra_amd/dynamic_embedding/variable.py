@@ -333,7 +333,7 @@ class Variable:
     bfloat16 variable round the parameter and the slots stochastically instead of to nearest even, so that updates below half a
     storage ulp are kept in the mean; shard i takes seed + i.  The stored bits are a pure function of (seed, write-backs since
     this call, key, element).  Not for CapturedTrainStep (a replayed graph would reuse one set of random bits); the Generic
-    optimizers ignore it."""
+    optimizers ignore it (Momentum / RMSProp without fused=True among them; with fused=True they round this way too)."""
     seed = 0 if seed is None else int(seed)
     for i, t in enumerate(self._tables):
       t.set_stochastic_rounding((seed + i) & ((1 << 64) - 1) if seed else 0)
