@@ -452,7 +452,7 @@ int tfra_table_load_field(tfra_table_t* t, int field, const char* prefix, size_t
  * keys [n] UNIQUE (use tfra_segment_sum first), grads [n,dim] fp32.  Missing keys are inserted
  * with p = param_defaults (full [n,dim] or broadcast [dim], like find) and slots = aux_init.
  * Requires aux_fields >= the optimizer's slot count.  value_dtype F32, F16 or BF16, here and in the planned / sparse forms
- * below (gradients and defaults are float32 in every case: the rule runs in fp32 on the up-cast row and slots and the
+ * below (gradients and defaults are float32 — half gradients: the *_typed calls — and the rule runs in fp32 on the up-cast row and slots and the
  * results are rounded to the storage type once, to nearest even — or stochastically, on a table with
  * TFRA_OPTION_STOCHASTIC_ROUNDING; a new row starts from the float32 default row and aux_init values, not from their
  * rounded images).                                                                            */
@@ -865,6 +865,38 @@ int tfra_segment_sum(tfra_workspace_t* ws, size_t n, int dim, const float* in, c
  * (pathological hash skew).  Unlike tfra_segment_sum the cost does not grow with the multiplicity of the hottest id. */
 int tfra_reduce_by_key(tfra_workspace_t* ws, size_t n, const int64_t* ids, int dim, const float* in,
                        int64_t* keys_out, float* rows_out, int64_t* d_count, tfra_stream_t stream);
+
+/* -- Half-precision gradients: the three calls that read an [n, dim] gradient matrix, taking it as the dense part
+ *    of a bfloat16 / float16 model hands it back, with the loss scale undone on the way.  Additive; ABI version 1.
+ *    Contract: each call equals its untyped twin (tfra_table_apply_sparse, tfra_table_apply_planned, tfra_reduce_by_key) given
+ *    the float32 matrix  G32[e] = f32(grads[e]) * s.
+ *      f32() is the exact up-cast: subnormals are kept, a NaN stays a NaN.
+ *      s = *d_scale, read by the kernels on the stream (a GradScaler's inverse scale; nothing is read on the host).  The product
+ *      is ONE float32 multiplication, rounded on its own (the library is built with -ffp-contract=off).  d_scale == NULL: the
+ *      result equals s = 1.
+ *    Everything behind G32 is the twin's: the summation order of repeated ids, partial sums in float32, the rule and the rounding
+ *    (stochastic included), scores, phase 2 on a full bounded table, the epoch step, the plan's error latch, capture-safety.
+ *    tfra_table_apply_sparse_typed beyond 2^18 ids takes the twin's slower path; its first stage is the typed reduce, chunk by
+ *    chunk, and the rest is unchanged, the sums being float32.
+ *    dtype == TFRA_F32 with d_scale == NULL forwards to the untyped function: the same code, the same launches.
+ *    Refused before anything is enqueued (tfra_last_error() names the function):
+ *      TFRA_ERR_INVALID      a NULL g or g->grads; reserved != 0; a dtype other than the three
+ *      TFRA_ERR_UNSUPPORTED  half gradients that are not 8-byte aligned; a float32 matrix with a scale (loss scaling belongs to
+ *                            float16)
+ *      and everything the twin checks, with the twin's codes.
+ *    Not typed: the combined write-backs (grad_out is the small stream), tfra_table_apply_optimizer, the step drivers. */
+typedef struct {
+  const void*  grads;    /* [n, dim] row-major in `dtype`; float32: 16-byte aligned, halves: 8-byte aligned */
+  int32_t      dtype;    /* TFRA_F32 | TFRA_F16 | TFRA_BF16 */
+  int32_t      reserved; /* must be 0 */
+  const float* d_scale;  /* optional DEVICE float scalar, read by the kernels; NULL = no scaling */
+} tfra_grads;            /* 24 bytes */
+int tfra_table_apply_sparse_typed(tfra_table_t* t, const tfra_opt_params* p, size_t n, const int64_t* ids,
+                                  const tfra_grads* g, const float* param_default_row, tfra_stream_t stream);
+int tfra_table_apply_planned_typed(tfra_table_t* t, const tfra_opt_params* p, const tfra_sparse_plan_t* plan,
+                                   const tfra_grads* g, const float* param_default_row, tfra_stream_t stream);
+int tfra_reduce_by_key_typed(tfra_workspace_t* ws, size_t n, const int64_t* ids, int dim, const tfra_grads* g,
+                             int64_t* keys_out, float* rows_out, int64_t* d_count, tfra_stream_t stream);
 
 /* The reduction half of tfra_reduce_by_key for a batch whose plan was built AHEAD (tfra_sparse_plan_build with dim = the
  * rows' dim, any stream): rows_out[dest[p], :] = sum of the rows of `grads` whose id equals ids[p] (same summation tree,

@@ -32,10 +32,11 @@ static Check check_rounding(const Table* t) {
 }
 
 // The checks of a planned write-back: apply_planned_impl's, whoever calls it, and behind check_apply_combined those of a
-// descriptor of tfra_multi_apply_planned_combined.  active: the plan holds ids.
+// descriptor of tfra_multi_apply_planned_combined.  active: the plan holds ids.  grad_mask: 15 for a float gradient matrix, 7 for
+// the float16 / bfloat16 one of the *_typed calls.
 template <class AtEntry>
-static Check check_apply_planned(const Table* t, const tfra_opt_params* p, const tfra_sparse_plan* pl, const float* grads,
-                                 const float* param_default_row, AtEntry&& at_entry) {
+static Check check_apply_planned(const Table* t, const tfra_opt_params* p, const tfra_sparse_plan* pl, const void* grads,
+                                 const float* param_default_row, AtEntry&& at_entry, unsigned grad_mask = 15u) {
   if (!t || !p || !pl) return refuse(TFRA_ERR_INVALID, "null argument");
   if (Check e = check_rounding(t); e.done()) return e;
   if (Check e = at_entry(); e.done()) return e;
@@ -43,13 +44,15 @@ static Check check_apply_planned(const Table* t, const tfra_opt_params* p, const
   if (!grads || !param_default_row) return refuse(TFRA_ERR_INVALID, "null buffer");
   const int dt = t->opts.value_dtype;
   if (dt != TFRA_F32 && dt != TFRA_F16 && dt != TFRA_BF16)
-    return refuse(TFRA_ERR_UNSUPPORTED, "value_dtype must be float32, float16 or bfloat16 (gradients and the default row are float32)");
+    return refuse(TFRA_ERR_UNSUPPORTED, "value_dtype must be float32, float16 or bfloat16 (the default row is float32)");
   if (p->kind < 0 || p->kind > TFRA_OPT_RMSPROP) return refuse(TFRA_ERR_INVALID, "unknown kind");
   const int need = opt_slots(p->kind);
   if (t->opts.aux_fields < need) return refuse(TFRA_ERR_INVALID, "table lacks optimizer slot fields");
   if (t->opts.dim != pl->dim) return refuse(TFRA_ERR_INVALID, "the plan was built for another dim");
   if (t->opts.device != pl->device && t->opts.device >= 0) return refuse(TFRA_ERR_INVALID, "plan and table live on different devices");
-  if ((((uintptr_t)grads | (uintptr_t)param_default_row) & 15)) return refuse(TFRA_ERR_UNSUPPORTED, "gradient / default buffers must be 16-B aligned");
+  if (((uintptr_t)grads & grad_mask) || ((uintptr_t)param_default_row & 15))
+    return refuse(TFRA_ERR_UNSUPPORTED, grad_mask == 15u ? "gradient / default buffers must be 16-B aligned"
+                                                         : "half gradients must be 8-B aligned, the default row 16-B");
   return Check{};
 }
 

@@ -1,7 +1,8 @@
 // GRADIENT HALF of a write-back whose ids may repeat (tfra_table_apply_planned, over a CSR plan of tfra_csr.hip): the hot sums,
 // then one fused optimizer update per unique key (their bodies: tfra_apply_device.h); the same sums written out instead
 // (tfra_reduce_by_key, tfra_plan_reduce_to); the combined form (tfra_table_apply_planned_combined) and the one-call form
-// (tfra_table_apply_sparse).  The grouped combined write-back is tfra_apply_many.hip, the two-stream look-ahead driver
+// (tfra_table_apply_sparse); the *_typed forms of the three calls that read an [n, dim] gradient matrix, for float16 / bfloat16
+// gradients (GradHalf in the kernels' pack).  The grouped combined write-back is tfra_apply_many.hip, the two-stream look-ahead driver
 // tfra_prefetch.hip.  A write-back's argument checks exist once (tfra_apply.h); the launch ladders are the dispatchers of
 // tfra_host.h (with_opt_kind, with_stored) and with_nch.
 #include <hip/hip_runtime.h>
@@ -56,10 +57,15 @@ __global__ __launch_bounds__(256) void apply_csr_kernel(TableView v, OptP o, int
 // dest != nullptr (tfra_plan_reduce_to): the sum of a key goes to row dest[p], p = the key's last batch position — the
 // caller's map from batch positions to output rows (equal for all positions of a key), e.g. position -> owner-major
 // index of the multi-GPU gradient route; keys_out / d_count are not written then.
+// CS = GradHalf (tfra_reduce_by_key_typed): the gradient matrix is float16 / bfloat16, read through sum_rows as the update reads
+// it; `grads` is not read then.
+template <class... CS>
 __global__ __launch_bounds__(256) void gather_csr_kernel(int dim, const float* __restrict__ grads,
                                                          const float* __restrict__ partial, CsrKeys ks,
                                                          i64* __restrict__ keys_out, float* __restrict__ rows_out,
-                                                         i64* __restrict__ d_count, const int* __restrict__ dest) {
+                                                         i64* __restrict__ d_count, const int* __restrict__ dest, const CS... cs) {
+  constexpr bool GH = HasGradHalf<CS...>::v;
+  const GradHalfSrc gh = grad_half_in(cs...);
   const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
   const unsigned total = ks.d_counts[PC_HOT] + ks.d_counts[PC_COLD];
   const unsigned ngroups = (gridDim.x * blockDim.x) >> 4;
@@ -87,7 +93,7 @@ __global__ __launch_bounds__(256) void gather_csr_kernel(int dim, const float* _
     for (int c0 = 0; c0 < dim; c0 += 64) {   // (every lane takes every trip: see apply_csr_kernel)
       const bool col = c0 + sub * 4 < dim;
       const int c = col ? c0 + sub * 4 : 0;
-      const float4 gg = sum_rows(grads, partial, hot, w, first, nsrc, wmax, dim, c, gshift);
+      const float4 gg = sum_rows<false, GH>(grads, partial, hot, w, first, nsrc, wmax, dim, c, gshift, 0.f, 0.f, gh);
       if (col) *reinterpret_cast<float4*>(rows_out + orow * dim + c) = gg;
     }
     if (keys_out && sub == 0) keys_out[g] = key;
@@ -135,21 +141,27 @@ static void launch_apply(Table* t, hipStream_t s, const tfra_sparse_plan* pl, in
   });
 }
 
+// the kernels' pack member of a half gradient matrix (hg: checked by check_typed)
+static GradHalf half_of(const tfra_grads* hg) { return GradHalf{hg->grads, hg->d_scale, hg->dtype == TFRA_BF16}; }
+
 // comb != nullptr (tfra_table_apply_planned_combined): grads is grad_out, position e's gradient is formed from comb[e]
+// hg != nullptr (the *_typed calls): the gradient matrix is hg's, float16 or bfloat16; grads is not read
 int tfra::apply_planned_impl(tfra_table_t* tp, const tfra_opt_params* p, const tfra_sparse_plan_t* pl, const float* grads,
                               const float* param_default_row, tfra_stream_t stream, unsigned* progress, unsigned progress_val,
-                             const CombEnt* comb) {
+                             const CombEnt* comb, const tfra_grads* hg) {
   // caller holds t->mu
   Table* t = reinterpret_cast<Table*>(tp);
   hipStream_t s = (hipStream_t)stream;
-  const Check c = check_apply_planned(t, p, pl, grads, param_default_row, [&] { return Check{t->enter(s)}; });
-  if (c.code) return report("apply_planned: ", c);
+  const Check c = check_apply_planned(t, p, pl, hg ? hg->grads : (const void*)grads, param_default_row,
+                                      [&] { return Check{t->enter(s)}; }, hg ? 7u : 15u);
+  if (c.code) return report(hg ? "apply_planned_typed: " : "apply_planned: ", c);
   if (!c.active) return TFRA_OK;
   int rc = t->prepare_insert(pl->n, s);
   if (rc) return rc;
   unsigned key_blocks, bin_blocks;
   plan_grids(pl, &key_blocks, &bin_blocks);
   if (comb) launch_hot_sums(s, pl, grads, bin_blocks, progress, progress_val, CombRows{comb});
+  else if (hg) launch_hot_sums(s, pl, nullptr, bin_blocks, progress, progress_val, half_of(hg));
   else launch_hot_sums(s, pl, grads, bin_blocks, progress, progress_val);
   uint8_t* bounded_now;
   rc = t->bounded_flags(1, s, &bounded_now);
@@ -157,6 +169,7 @@ int tfra::apply_planned_impl(tfra_table_t* tp, const tfra_opt_params* p, const t
   const ScoreP sp = score_of(t, bounded_now);
   const OptP o = opt_of(p);
   if (comb) launch_apply(t, s, pl, p->kind, o, grads, param_default_row, key_blocks, sp, CombRows{comb});
+  else if (hg) launch_apply(t, s, pl, p->kind, o, nullptr, param_default_row, key_blocks, sp, half_of(hg));
   else launch_apply(t, s, pl, p->kind, o, grads, param_default_row, key_blocks, sp);
   if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "apply_planned: launch failed");
   t->step_writeback();
@@ -169,6 +182,35 @@ extern "C" int tfra_table_apply_planned(tfra_table_t* tp, const tfra_opt_params*
   if (!t) return set_error(TFRA_ERR_INVALID, "apply_planned: null table");
   std::lock_guard<std::mutex> lock(t->mu);
   return apply_planned_impl(tp, p, pl, grads, param_default_row, stream, nullptr, 0);
+}
+
+// ---- the *_typed calls: the gradient matrix as the caller's dense part left it (tfra_grads).  A typed call equals its untyped
+// twin on G32[e] = f32(grads[e]) * *d_scale; the kernels form G32 in registers (GradHalf, tfra_apply_device.h).
+// What a tfra_grads itself must satisfy, before anything is enqueued.  forward: float32 without a scale — the untyped call, as it is.
+static Check check_typed(const tfra_grads* g, bool* forward) {
+  *forward = false;
+  if (!g || !g->grads) return refuse(TFRA_ERR_INVALID, "null gradients");
+  if (g->reserved != 0) return refuse(TFRA_ERR_INVALID, "tfra_grads.reserved must be 0");
+  if (g->dtype != TFRA_F32 && g->dtype != TFRA_F16 && g->dtype != TFRA_BF16)
+    return refuse(TFRA_ERR_INVALID, "tfra_grads.dtype must be float32, float16 or bfloat16");
+  if (g->dtype == TFRA_F32) {
+    if (g->d_scale) return refuse(TFRA_ERR_UNSUPPORTED, "float32 gradients take no scale (loss scaling belongs to float16)");
+    *forward = true;
+  } else if ((uintptr_t)g->grads & 7) {
+    return refuse(TFRA_ERR_UNSUPPORTED, "half gradients must be 8-B aligned");
+  }
+  return Check{};
+}
+
+extern "C" int tfra_table_apply_planned_typed(tfra_table_t* tp, const tfra_opt_params* p, const tfra_sparse_plan_t* pl,
+                                              const tfra_grads* g, const float* param_default_row, tfra_stream_t stream) {
+  Table* t = reinterpret_cast<Table*>(tp);
+  if (!t) return set_error(TFRA_ERR_INVALID, "apply_planned_typed: null table");
+  bool forward;
+  if (const Check c = check_typed(g, &forward); c.code) return report("apply_planned_typed: ", c);
+  if (forward) return tfra_table_apply_planned(tp, p, pl, (const float*)g->grads, param_default_row, stream);
+  std::lock_guard<std::mutex> lock(t->mu);
+  return apply_planned_impl(tp, p, pl, nullptr, param_default_row, stream, nullptr, 0, nullptr, g);
 }
 
 // The write-back of an embedding_lookup_sparse: plan over the entry ids, gradient of position e = the combiner's backward
@@ -210,8 +252,11 @@ extern "C" int tfra_table_apply_planned_combined(tfra_table_t* tp, const tfra_op
 //      the parts are disjoint key sets — and each part is written back on its own.
 // A slow path (host reads of the counts, scratch allocated per call); results are deterministic, the association of the
 // sums is (within chunk) + (across chunks in order).
+// hg != nullptr (tfra_table_apply_sparse_typed): stage 1 is the typed reduce; the sums are float, the rest is unchanged.
+static int reduce_by_key_impl(tfra_workspace_t* ws, size_t n, const int64_t* ids, int dim, const float* grads, const tfra_grads* hg,
+                              int64_t* keys_out, float* rows_out, int64_t* d_count, tfra_stream_t stream);
 static int apply_sparse_big(Table* t, tfra_table_t* tp, tfra_sparse_plan* pl, const tfra_opt_params* p, size_t n, const int64_t* ids,
-                            const float* grads, const float* param_default_row, tfra_stream_t stream) {
+                            const float* grads, const tfra_grads* hg, const float* param_default_row, tfra_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
   const int dim = t->opts.dim;
   tfra_workspace_t* ws;
@@ -227,8 +272,10 @@ static int apply_sparse_big(Table* t, tfra_table_t* tp, tfra_sparse_plan* pl, co
   size_t T = 0;
   for (size_t off = 0; off < n; off += MAX_IDS) {
     const size_t m = std::min<size_t>(MAX_IDS, n - off);
-    int rc = tfra_reduce_by_key(ws, m, ids + off, dim, grads + off * (size_t)dim, (int64_t*)keys_cat + T, sums_cat + T * (size_t)dim,
-                                (int64_t*)d_cnt, stream);
+    tfra_grads part;   // (rows of dim % 4 == 0 halves: a chunk's matrix is 8-B aligned as the whole is)
+    if (hg) { part = *hg; part.grads = (const unsigned short*)hg->grads + off * (size_t)dim; }
+    int rc = reduce_by_key_impl(ws, m, ids + off, dim, hg ? nullptr : grads + off * (size_t)dim, hg ? &part : nullptr,
+                                (int64_t*)keys_cat + T, sums_cat + T * (size_t)dim, (int64_t*)d_cnt, stream);
     if (rc) return rc;
     i64 c = 0;
     if (hipMemcpyAsync(&c, d_cnt, sizeof(i64), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
@@ -278,49 +325,69 @@ static int apply_sparse_big(Table* t, tfra_table_t* tp, tfra_sparse_plan* pl, co
   return set_error(TFRA_ERR_UNSUPPORTED, "apply_sparse: could not split the batch into parts of 2^18 ids");
 }
 
-extern "C" int tfra_table_apply_sparse(tfra_table_t* tp, const tfra_opt_params* p, size_t n, const int64_t* ids,
-                                       const float* grads, const float* param_default_row, tfra_stream_t stream) {
+// tfra_table_apply_sparse (hg == nullptr) and tfra_table_apply_sparse_typed on half gradients (hg, checked by check_typed; grads
+// is not read then): one function, `who` names the caller in the refusals
+static int apply_sparse_impl(const char* who, tfra_table_t* tp, const tfra_opt_params* p, size_t n, const int64_t* ids, const float* grads,
+                             const tfra_grads* hg, const float* param_default_row, tfra_stream_t stream) {
   Table* t = reinterpret_cast<Table*>(tp);
-  if (!t || !p) return set_error(TFRA_ERR_INVALID, "apply_sparse: null argument");
+  const std::string pre = std::string(who) + ": ";
+  if (!t || !p) return set_error(TFRA_ERR_INVALID, (pre + "null argument").c_str());
   if (n == 0) return TFRA_OK;
-  if (!ids || !grads || !param_default_row) return set_error(TFRA_ERR_INVALID, "apply_sparse: null buffer");
+  const void* gsrc = hg ? hg->grads : (const void*)grads;
+  if (!ids || !gsrc || !param_default_row) return set_error(TFRA_ERR_INVALID, (pre + "null buffer").c_str());
   const int dt = t->opts.value_dtype;
   if (dt != TFRA_F32 && dt != TFRA_F16 && dt != TFRA_BF16)
-    return set_error(TFRA_ERR_UNSUPPORTED, "apply_sparse: value_dtype must be float32, float16 or bfloat16 (gradients and the default row are float32)");
+    return set_error(TFRA_ERR_UNSUPPORTED, (pre + "value_dtype must be float32, float16 or bfloat16 (the default row is float32)").c_str());
   const int dim = t->opts.dim;
-  if (dim % 4 != 0 || dim > 64 * MAXCH || (((uintptr_t)grads | (uintptr_t)param_default_row) & 15))
-    return set_error(TFRA_ERR_UNSUPPORTED, "apply_sparse: needs dim % 4 == 0, dim <= 256 and 16-B aligned buffers "
-                                           "(use tfra_unique + tfra_segment_sum + tfra_table_apply_optimizer otherwise)");
+  if (dim % 4 != 0 || dim > 64 * MAXCH || ((uintptr_t)gsrc & (hg ? 7 : 15)) || ((uintptr_t)param_default_row & 15))
+    return set_error(TFRA_ERR_UNSUPPORTED, (pre + "needs dim % 4 == 0, dim <= 256 and 16-B aligned buffers (half gradients: 8-B) "
+                                                  "(use tfra_unique + tfra_segment_sum + tfra_table_apply_optimizer otherwise)").c_str());
   tfra_sparse_plan* pl;
   std::lock_guard<std::mutex> lock(t->mu);
-  if (const Check c = check_rounding(t); c.code) return report("apply_sparse: ", c);   // (before the plan build is enqueued)
+  if (const Check c = check_rounding(t); c.code) return report(pre.c_str(), c);   // (before the plan build is enqueued)
   int rc = t->enter((hipStream_t)stream);   // orders the rebuild of the table's own plan behind its previous use
   if (rc) return rc;
   rc = own_plan(t, &pl);
   if (rc) return rc;
-  if (n > MAX_IDS) return apply_sparse_big(t, tp, pl, p, n, ids, grads, param_default_row, stream);
+  if (n > MAX_IDS) return apply_sparse_big(t, tp, pl, p, n, ids, grads, hg, param_default_row, stream);
   rc = tfra_sparse_plan_build(pl, n, ids, dim, stream);
   if (rc) return rc;
-  return apply_planned_impl(tp, p, pl, grads, param_default_row, stream, nullptr, 0);
+  return apply_planned_impl(tp, p, pl, grads, param_default_row, stream, nullptr, 0, nullptr, hg);
+}
+
+extern "C" int tfra_table_apply_sparse(tfra_table_t* tp, const tfra_opt_params* p, size_t n, const int64_t* ids,
+                                       const float* grads, const float* param_default_row, tfra_stream_t stream) {
+  return apply_sparse_impl("apply_sparse", tp, p, n, ids, grads, nullptr, param_default_row, stream);
+}
+
+extern "C" int tfra_table_apply_sparse_typed(tfra_table_t* tp, const tfra_opt_params* p, size_t n, const int64_t* ids,
+                                             const tfra_grads* g, const float* param_default_row, tfra_stream_t stream) {
+  bool forward;
+  if (const Check c = check_typed(g, &forward); c.code) return report("apply_sparse_typed: ", c);
+  if (forward) return tfra_table_apply_sparse(tp, p, n, ids, (const float*)g->grads, param_default_row, stream);
+  return apply_sparse_impl("apply_sparse_typed", tp, p, n, ids, nullptr, g, param_default_row, stream);
 }
 
 // unique + unsorted_segment_sum in one call = the plan + the hot sums + a gather (the reduction half of
 // tfra_table_apply_sparse with the same summation tree, so routing the sums elsewhere — multi-GPU gradient
 // alltoall — and applying them there gives the same bits as applying them here).
-extern "C" int tfra_reduce_by_key(tfra_workspace_t* ws, size_t n, const int64_t* ids, int dim, const float* grads,
-                                  int64_t* keys_out, float* rows_out, int64_t* d_count, tfra_stream_t stream) {
+// (hg != nullptr: tfra_reduce_by_key_typed on half gradients, checked by check_typed; grads is not read then)
+static int reduce_by_key_impl(tfra_workspace_t* ws, size_t n, const int64_t* ids, int dim, const float* grads, const tfra_grads* hg,
+                              int64_t* keys_out, float* rows_out, int64_t* d_count, tfra_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (!ws || !d_count) return set_error(TFRA_ERR_INVALID, "reduce_by_key: null argument");
-  if (on_device(ws->device) != hipSuccess) return set_error(TFRA_ERR_HIP, "reduce_by_key: hipSetDevice");
+  const std::string pre = hg ? "reduce_by_key_typed: " : "reduce_by_key: ";
+  if (!ws || !d_count) return set_error(TFRA_ERR_INVALID, (pre + "null argument").c_str());
+  if (on_device(ws->device) != hipSuccess) return set_error(TFRA_ERR_HIP, (pre + "hipSetDevice").c_str());
   if (n == 0) {
-    if (hipMemsetAsync(d_count, 0, sizeof(int64_t), s) != hipSuccess) return set_error(TFRA_ERR_HIP, "reduce_by_key: memset");
+    if (hipMemsetAsync(d_count, 0, sizeof(int64_t), s) != hipSuccess) return set_error(TFRA_ERR_HIP, (pre + "memset").c_str());
     return TFRA_OK;
   }
-  if (!ids || !grads || !keys_out || !rows_out) return set_error(TFRA_ERR_INVALID, "reduce_by_key: null buffer");
-  if (dim <= 0 || dim % 4 != 0 || dim > 64 * MAXCH || (((uintptr_t)grads | (uintptr_t)rows_out) & 15))
-    return set_error(TFRA_ERR_UNSUPPORTED, "reduce_by_key: needs dim % 4 == 0, dim <= 256 and 16-B aligned buffers "
-                                           "(use tfra_unique + tfra_segment_sum otherwise)");
-  if (n > MAX_IDS) return set_error(TFRA_ERR_UNSUPPORTED, "reduce_by_key: at most 2^18 ids per call");
+  const void* gsrc = hg ? hg->grads : (const void*)grads;
+  if (!ids || !gsrc || !keys_out || !rows_out) return set_error(TFRA_ERR_INVALID, (pre + "null buffer").c_str());
+  if (dim <= 0 || dim % 4 != 0 || dim > 64 * MAXCH || ((uintptr_t)gsrc & (hg ? 7 : 15)) || ((uintptr_t)rows_out & 15))
+    return set_error(TFRA_ERR_UNSUPPORTED, (pre + "needs dim % 4 == 0, dim <= 256 and 16-B aligned buffers (half gradients: 8-B) "
+                                                  "(use tfra_unique + tfra_segment_sum otherwise)").c_str());
+  if (n > MAX_IDS) return set_error(TFRA_ERR_UNSUPPORTED, (pre + "at most 2^18 ids per call").c_str());
   tfra_sparse_plan* pl;
   int rc = plan_in(&ws->plan, ws->device, &pl);
   if (rc) return rc;
@@ -328,10 +395,29 @@ extern "C" int tfra_reduce_by_key(tfra_workspace_t* ws, size_t n, const int64_t*
   if (rc) return rc;
   unsigned key_blocks, bin_blocks;
   plan_grids(pl, &key_blocks, &bin_blocks);
-  launch_hot_sums(s, pl, grads, bin_blocks, nullptr, 0);   // (pl->dim == dim)
-  gather_csr_kernel<<<key_blocks, 256, 0, s>>>(dim, grads, pl->partial, keys_of(pl), (i64*)keys_out, rows_out, (i64*)d_count, nullptr);
-  if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "reduce_by_key: launch failed");
+  if (hg) {
+    launch_hot_sums(s, pl, nullptr, bin_blocks, nullptr, 0, half_of(hg));
+    gather_csr_kernel<<<key_blocks, 256, 0, s>>>(dim, nullptr, pl->partial, keys_of(pl), (i64*)keys_out, rows_out, (i64*)d_count, nullptr,
+                                                 half_of(hg));
+  } else {
+    launch_hot_sums(s, pl, grads, bin_blocks, nullptr, 0);   // (pl->dim == dim)
+    gather_csr_kernel<<<key_blocks, 256, 0, s>>>(dim, grads, pl->partial, keys_of(pl), (i64*)keys_out, rows_out, (i64*)d_count, nullptr);
+  }
+  if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, (pre + "launch failed").c_str());
   return TFRA_OK;
+}
+
+extern "C" int tfra_reduce_by_key(tfra_workspace_t* ws, size_t n, const int64_t* ids, int dim, const float* grads,
+                                  int64_t* keys_out, float* rows_out, int64_t* d_count, tfra_stream_t stream) {
+  return reduce_by_key_impl(ws, n, ids, dim, grads, nullptr, keys_out, rows_out, d_count, stream);
+}
+
+extern "C" int tfra_reduce_by_key_typed(tfra_workspace_t* ws, size_t n, const int64_t* ids, int dim, const tfra_grads* g,
+                                        int64_t* keys_out, float* rows_out, int64_t* d_count, tfra_stream_t stream) {
+  bool forward;
+  if (const Check c = check_typed(g, &forward); c.code) return report("reduce_by_key_typed: ", c);
+  if (forward) return tfra_reduce_by_key(ws, n, ids, dim, (const float*)g->grads, keys_out, rows_out, d_count, stream);
+  return reduce_by_key_impl(ws, n, ids, dim, nullptr, g, keys_out, rows_out, d_count, stream);
 }
 
 // The per-key gradient sums of a batch whose plan was built ahead (tfra_sparse_plan_build with the table's dim, on any

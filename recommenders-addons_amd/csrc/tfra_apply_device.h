@@ -36,6 +36,48 @@ __device__ __forceinline__ const CombEnt* comb_ent(const CS&... cs) {
   return p;
 }
 
+// CS = GradHalf (the *_typed write-backs and tfra_reduce_by_key_typed): the [n, dim] gradient matrix is float16 or bfloat16 and is
+// read where the float one is read — a lane's four elements are ONE 8-byte load (the group's 16 lanes = one 128-byte line per 64
+// columns), up-cast exactly and multiplied by the scale (one fp32 multiplication, rounded on its own: -ffp-contract=off) before
+// any add, so everything behind the load sees the float matrix G32[e] = f32(g[e]) * s of the untyped call.  ONE pack type for both
+// formats: is_bf16 is wave-uniform (a kernel argument), the conversion a shift or v_cvt_f32_f16 chosen by it.  *d_scale is a scalar
+// load, once per wave (nullptr: 1.0f — x * 1.0f is exact, no second variant).  The `grads` argument of the kernels is unused then.
+// Without one in the pack the kernels compile the code they always did (if constexpr).
+struct GradHalf { const void* g; const float* d_scale; int is_bf16; };
+struct GradHalfSrc { const unsigned short* g; float s; int is_bf16; };   // in the kernel: the scale already read
+template <class... CS> struct HasGradHalf { static constexpr bool v = (false || ... || std::is_same<CS, GradHalf>::value); };
+template <class... CS>
+__device__ __forceinline__ GradHalfSrc grad_half_in(const CS&... cs) {
+  GradHalfSrc r{nullptr, 1.f, 0};
+  auto take = [&](const auto& x) {
+    if constexpr (std::is_same<std::decay_t<decltype(x)>, GradHalf>::value) {
+      r.g = reinterpret_cast<const unsigned short*>(x.g);
+      r.s = x.d_scale ? *x.d_scale : 1.f;
+      r.is_bf16 = x.is_bf16;
+    }
+  };
+  (take(cs), ...);
+  return r;
+}
+// acc += the rows of G32 that N granules of four stored gradient elements hold, in order, those that `take(j)` names: each is up-cast
+// and scaled when its turn comes (never N float rows held at once).  The format's branch is wave-uniform and outside the loop.
+template <int ST>
+__device__ __forceinline__ void grad_half_add1(float4& acc, const uint2& r, float s) {
+  float4 x = load_stored4<ST>(r);
+  x.x *= s; x.y *= s; x.z *= s; x.w *= s;
+  acc.x += x.x; acc.y += x.y; acc.z += x.z; acc.w += x.w;
+}
+template <int N, class Take>
+__device__ __forceinline__ void grad_half_add(float4& acc, const uint2 (&r)[N], const GradHalfSrc& gh, Take&& take) {
+  if (gh.is_bf16) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) if (take(j)) grad_half_add1<TFRA_BF16>(acc, r[j], gh.s);
+  } else {
+#pragma unroll
+    for (int j = 0; j < N; ++j) if (take(j)) grad_half_add1<TFRA_F16>(acc, r[j], gh.s);
+  }
+}
+
 // The body is one function with two callers — hot_sums_kernel (one plan per launch) and hot_sums_many_kernel (a list of plans per
 // launch) — so that both compile the same expressions: blk = this block's index among the nblk blocks that work on THIS plan.
 template <int NCH, class... CS>
@@ -44,8 +86,11 @@ __device__ __forceinline__ void hot_sums_body(const float* __restrict__ grads, i
                                               const unsigned* __restrict__ binmap,
                                               const unsigned* __restrict__ d_counts, float* __restrict__ partial,
                                               unsigned* progress, unsigned progress_val, unsigned blk, unsigned nblk, const CS... cs) {
-  constexpr bool COMB = sizeof...(CS) > 0;
+  constexpr bool COMB = (false || ... || std::is_same<CS, CombRows>::value);
+  constexpr bool GH = HasGradHalf<CS...>::v;
+  static_assert(!(COMB && GH), "the combined write-back takes float grad_out");
   constexpr int NG = NTA / 16;
+  const GradHalfSrc gh = grad_half_in(cs...);
   __shared__ float s_sum[NG][64];
   __shared__ unsigned char s_kind[NG + 1];   // 0 = item continues the run of the item before, 1 = first item of a run, 2 = empty item
   // tfra_table_step_prefetch: host-visible progress counter (pinned memory) — this kernel running means the
@@ -88,6 +133,13 @@ __device__ __forceinline__ void hot_sums_body(const float* __restrict__ grads, i
       // cost more: 10.0 -> 9.2 us under rocprofv3, configs[1]'s step 56.7-57.3 -> 55.6-55.7 us (A/B on one box, twice).  Same adds, same order.
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
+        if constexpr (GH) {
+          uint2 r[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) r[j] = *reinterpret_cast<const uint2*>(gh.g + rows[h * 8 + j] + cc);
+          keep_live(r[0], r[1], r[2], r[3]); keep_live(r[4], r[5], r[6], r[7]);
+          grad_half_add(acc, r, gh, [&](int j) { return ((live >> (h * 8 + j)) & 1u) != 0; });
+        } else {
         float4 x[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) x[j] = *reinterpret_cast<const float4*>(grads + rows[h * 8 + j] + cc);
@@ -99,7 +151,15 @@ __device__ __forceinline__ void hot_sums_body(const float* __restrict__ grads, i
 #pragma unroll
         for (int j = 0; j < 8; ++j)
           if ((live >> (h * 8 + j)) & 1u) { acc.x += x[j].x; acc.y += x[j].y; acc.z += x[j].z; acc.w += x[j].w; }
+        }
       }
+      } else if constexpr (GH) {
+      uint2 r[16];
+#pragma unroll
+      for (int j = 0; j < 16; ++j) r[j] = *reinterpret_cast<const uint2*>(gh.g + rows[j] + cc);   // 16 rows in flight
+      keep_live(r[0], r[1], r[2], r[3]); keep_live(r[4], r[5], r[6], r[7]);
+      keep_live(r[8], r[9], r[10], r[11]); keep_live(r[12], r[13], r[14], r[15]);
+      grad_half_add(acc, r, gh, [&](int j) { return ((live >> j) & 1u) != 0; });
       } else {
       float4 x[16];
 #pragma unroll
@@ -137,10 +197,38 @@ __device__ __forceinline__ void hot_sums_body(const float* __restrict__ grads, i
 // 8 rows held per lane the update kernel needed 145 registers (3 waves per SIMD); this form needs 125 (Adam) / 109 (SGD).
 // COMB (combined write-back): lanes 4.. of a key with few occurrences hold grad_out rows instead of batch positions, and the
 // denominator / weight of their entry in cden / cw; each gradient row is scaled by comb_grad4 before it is added.
-template <int NB, bool COMB = false>
+// GH (half gradients): the `grads` arm loads 8-byte granules from gh and forms G32 from them; the `partial` arm is the float one.
+// Hot keys come first in the key list, so but for one wave the branch is wave-uniform; each arm has its NB loads in flight.
+template <int NB, bool COMB = false, bool GH = false>
 __device__ __forceinline__ void add_rows(float4& acc, const float* __restrict__ grads, const float* __restrict__ partial, bool hot,
                                          unsigned w, unsigned first, unsigned nsrc, unsigned j0, int dim, int c, int gshift,
-                                         float cden = 0.f, float cw = 0.f) {
+                                         float cden = 0.f, float cw = 0.f, const GradHalfSrc gh = GradHalfSrc{nullptr, 1.f, 0}) {
+  if constexpr (GH) {
+    // (each arm adds for itself, in list order: the granules are up-cast one at a time, never NB float rows held at once)
+    // (hot is the group's: the shuffles of the `grads` arm find every lane of their group in it)
+    // (both arms address with 32-bit element offsets from a scalar base — fewer than 2^18 rows of at most 256 elements, as rows[]
+    // of the sums: with 64-bit addresses the update kernels needed 129 - 139 registers, one waves-per-SIMD class below their twins)
+    if (hot) {
+      float4 x[NB];
+#pragma unroll
+      for (int j = 0; j < NB; ++j)
+        x[j] = *reinterpret_cast<const float4*>(partial + ((first + min(j0 + (unsigned)j, nsrc - 1)) * (unsigned)dim + (unsigned)c));
+      if (NB == 4) keep_live(x[0], x[1], x[2], x[3]);
+#pragma unroll
+      for (int j = 0; j < NB; ++j)
+        if (j0 + (unsigned)j < nsrc) { acc.x += x[j].x; acc.y += x[j].y; acc.z += x[j].z; acc.w += x[j].w; }
+    } else {
+      uint2 r[NB];
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        const unsigned position = (unsigned)__shfl((int)w, gshift + 4 + (int)min(min(j0 + (unsigned)j, nsrc - 1), 7u));
+        r[j] = *reinterpret_cast<const uint2*>(gh.g + (position * (unsigned)dim + (unsigned)c));
+      }
+      if (NB == 4) keep_live(r[0], r[1], r[2], r[3]);
+      grad_half_add(acc, r, gh, [&](int j) { return j0 + (unsigned)j < nsrc; });
+    }
+    return;
+  }
   float4 x[NB];
 #pragma unroll
   for (int j = 0; j < NB; ++j) {
@@ -164,18 +252,18 @@ __device__ __forceinline__ void add_rows(float4& acc, const float* __restrict__ 
 
 // the whole sum of a key; wmax = the largest list length (capped at 8) among the wave's four keys: the trip count of the
 // common part is uniform across the wave, the few keys with more than 8 partial rows go on alone
-template <bool COMB = false>
+template <bool COMB = false, bool GH = false>
 __device__ __forceinline__ float4 sum_rows(const float* __restrict__ grads, const float* __restrict__ partial, bool hot, unsigned w,
                                            unsigned first, unsigned nsrc, unsigned wmax, int dim, int c, int gshift,
-                                           float cden = 0.f, float cw = 0.f) {
+                                           float cden = 0.f, float cw = 0.f, const GradHalfSrc gh = GradHalfSrc{nullptr, 1.f, 0}) {
   float4 gg = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (wmax <= 1) add_rows<1, COMB>(gg, grads, partial, hot, w, first, nsrc, 0, dim, c, gshift, cden, cw);
-  else if (wmax <= 2) add_rows<2, COMB>(gg, grads, partial, hot, w, first, nsrc, 0, dim, c, gshift, cden, cw);
+  if (wmax <= 1) add_rows<1, COMB, GH>(gg, grads, partial, hot, w, first, nsrc, 0, dim, c, gshift, cden, cw, gh);
+  else if (wmax <= 2) add_rows<2, COMB, GH>(gg, grads, partial, hot, w, first, nsrc, 0, dim, c, gshift, cden, cw, gh);
   else {
-    add_rows<4, COMB>(gg, grads, partial, hot, w, first, nsrc, 0, dim, c, gshift, cden, cw);
-    if (wmax > 4) add_rows<4, COMB>(gg, grads, partial, hot, w, first, nsrc, 4, dim, c, gshift, cden, cw);
+    add_rows<4, COMB, GH>(gg, grads, partial, hot, w, first, nsrc, 0, dim, c, gshift, cden, cw, gh);
+    if (wmax > 4) add_rows<4, COMB, GH>(gg, grads, partial, hot, w, first, nsrc, 4, dim, c, gshift, cden, cw, gh);
   }
-  for (unsigned j0 = 8; j0 < nsrc; j0 += 4) add_rows<4, COMB>(gg, grads, partial, hot, w, first, nsrc, j0, dim, c, gshift, cden, cw);
+  for (unsigned j0 = 8; j0 < nsrc; j0 += 4) add_rows<4, COMB, GH>(gg, grads, partial, hot, w, first, nsrc, j0, dim, c, gshift, cden, cw, gh);
   return gg;
 }
 
@@ -195,7 +283,8 @@ __device__ __forceinline__ float4 sum_rows(const float* __restrict__ grads, cons
 // and field (4 stored elements; the group's 16 lanes = one 128-byte line), up-cast, updated in fp32 exactly like a float row,
 // rounded to the storage type once (to_stored) and written back as one 8-byte write-through store per field.  A new row starts
 // from the FLOAT default row and aux_init values, not from their rounded images (as apply_kernel / apply_evict_kernel do).
-// Gradients and partial sums are fp32 for every ST.  The float instantiations compile the code they always did (if constexpr).
+// Partial sums are fp32 for every ST, gradients fp32 unless the pack holds a GradHalf (above).  The float instantiations compile
+// the code they always did (if constexpr).
 // A StochP in the pack (half rows of a table with TFRA_OPTION_STOCHASTIC_ROUNDING): the parameter and the slots the rule owns are
 // rounded by to_stored4_sr, one hash word per lane, field and granule, formed between the rule and the store; the constant fill
 // of the other fields stays nearest-even.  Without one the pack's kernels compile the code they always did.
@@ -210,7 +299,10 @@ __device__ __forceinline__ void apply_csr_body(const TableView& v, OptP o, int d
                                                unsigned use_gen, unsigned blk, unsigned nblk, const CS... cs) {
   constexpr bool COMB = (false || ... || std::is_same<CS, CombRows>::value);
   constexpr bool STOCH = HasStoch<CS...>::v;
+  constexpr bool GH = HasGradHalf<CS...>::v;
   static_assert(!STOCH || ST != TFRA_F32, "stochastic rounding is of half rows");
+  static_assert(!(COMB && GH), "the combined write-back takes float grad_out");
+  const GradHalfSrc gh = grad_half_in(cs...);
   if (PHASE2 && *any_deferred != use_gen) return;   // phase 1 of this use deferred nothing
   constexpr int S = NSlots<KIND>::v;
   const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
@@ -286,7 +378,7 @@ __device__ __forceinline__ void apply_csr_body(const TableView& v, OptP o, int d
         uint2 r1 = *reinterpret_cast<const uint2*>(sr + (S >= 1 ? dim : 0) + c);
         uint2 r2 = *reinterpret_cast<const uint2*>(sr + (S >= 2 ? 2 * dim : 0) + c);
         const float4 dflt = *reinterpret_cast<const float4*>(default_row + c);
-        float4 gg = sum_rows<COMB>(grads, partial, hot, COMB ? wsrc : w, first, nsrc, wmax, dim, c, gshift, cden, cw);
+        float4 gg = sum_rows<COMB, GH>(grads, partial, hot, COMB ? wsrc : w, first, nsrc, wmax, dim, c, gshift, cden, cw, gh);
         uint2 dummy = rp;
         keep_live(dummy, rp, r1, r2);
         float4 p = is_new ? dflt : load_stored4<ST>(rp);
@@ -327,7 +419,7 @@ __device__ __forceinline__ void apply_csr_body(const TableView& v, OptP o, int d
       float4 p = *reinterpret_cast<const float4*>((is_new ? default_row : pr) + c);
       float4 s1 = *reinterpret_cast<const float4*>(pr + (S >= 1 ? dim : 0) + c);
       float4 s2 = *reinterpret_cast<const float4*>(pr + (S >= 2 ? 2 * dim : 0) + c);
-      float4 gg = sum_rows<COMB>(grads, partial, hot, COMB ? wsrc : w, first, nsrc, wmax, dim, c, gshift, cden, cw);
+      float4 gg = sum_rows<COMB, GH>(grads, partial, hot, COMB ? wsrc : w, first, nsrc, wmax, dim, c, gshift, cden, cw, gh);
       float4 dummy = p;
       keep_live(dummy, p, s1, s2);
       if (is_new || S < 1) s1 = make_float4(aux0, aux0, aux0, aux0);

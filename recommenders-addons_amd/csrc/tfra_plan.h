@@ -107,7 +107,7 @@ int own_plan(Table* t, tfra_sparse_plan** out);
 // ---- tfra_apply.hip (callers: tfra_prefetch.hip, and the unit itself)
 int apply_planned_impl(tfra_table_t* tp, const tfra_opt_params* p, const tfra_sparse_plan_t* pl, const float* grads,
                        const float* param_default_row, tfra_stream_t stream, unsigned* progress, unsigned progress_val,
-                       const CombEnt* comb = nullptr);
+                       const CombEnt* comb = nullptr, const tfra_grads* hg = nullptr);
 
 // ---- tfra_own.hip
 // Host half of an ownership write-back of a plan's keys: everything but the launches (upsert_planned_impl launches the pair

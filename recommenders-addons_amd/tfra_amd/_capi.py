@@ -66,6 +66,11 @@ class OptParams(ctypes.Structure):
 _P = ctypes.c_void_p
 
 
+class Grads(ctypes.Structure):
+  """tfra_grads (include/tfra_mi355x.h): a gradient matrix in its own dtype and an optional device scale, for the *_typed calls."""
+  _fields_ = [("grads", ctypes.c_void_p), ("dtype", ctypes.c_int32), ("reserved", ctypes.c_int32), ("d_scale", ctypes.c_void_p)]
+
+
 class StepDesc(ctypes.Structure):
   """tfra_step_desc (include/tfra_mi355x.h): one table's step in tfra_multi_step_prefetch."""
   _fields_ = [
@@ -273,6 +278,9 @@ _SIGS = {
     "tfra_table_load_field": [_P, _I, ctypes.c_char_p, _SZ, _P, ctypes.POINTER(_SZ)],
     "tfra_table_apply_optimizer": [_P, ctypes.POINTER(OptParams), _SZ, _P, _P, _P, _I, _P, _P],
     "tfra_table_apply_sparse": [_P, ctypes.POINTER(OptParams), _SZ, _P, _P, _P, _P],
+    "tfra_table_apply_sparse_typed": [_P, ctypes.POINTER(OptParams), _SZ, _P, ctypes.POINTER(Grads), _P, _P],
+    "tfra_table_apply_planned_typed": [_P, ctypes.POINTER(OptParams), _P, ctypes.POINTER(Grads), _P, _P],
+    "tfra_reduce_by_key_typed": [_P, _SZ, _P, _I, ctypes.POINTER(Grads), _P, _P, _P, _P],
     "tfra_sparse_plan_create": [_I, _P],
     "tfra_sparse_plan_destroy": [_P],
     "tfra_sparse_plan_build": [_P, _SZ, _P, _I, _P],

@@ -36,6 +36,26 @@ def _ptr(t):
   return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _grads_arg(grads, device, dim, grad_scale=None):
+  """A gradient matrix as a write-back takes it: (tfra_grads, tensor) when it goes down as it is — a contiguous float16 / bfloat16
+  matrix on `device`, inside the typed calls' limits (dim % 4 == 0, 8-byte aligned), with `grad_scale` (a one-element float32
+  device tensor, e.g. a GradScaler's inverse scale) read by the kernels — else (None, tensor) with the float32 up-cast, times
+  grad_scale where there is one: by the typed calls' definition the same bits.  The tensor is what the call reads: keep it
+  alive across the call.  No host read either way."""
+  if grad_scale is not None:
+    grad_scale = torch.as_tensor(grad_scale)
+    if grad_scale.numel() != 1:
+      raise ValueError("grad_scale must hold one element, got shape %s" % list(grad_scale.shape))
+  scale_down = grad_scale is None or (grad_scale.dtype == torch.float32 and grad_scale.device == device)
+  if (grads.dtype in (torch.float16, torch.bfloat16) and grads.device == device and grads.is_contiguous() and grads.numel() and
+      dim % 4 == 0 and grads.data_ptr() % 8 == 0 and scale_down):
+    return _capi.Grads(grads.data_ptr(), _TORCH2DT[grads.dtype], 0, None if grad_scale is None else grad_scale.data_ptr()), grads
+  g = grads.to(device, torch.float32)
+  if grad_scale is not None:
+    g = g * grad_scale.to(device=device, dtype=torch.float32).reshape(())
+  return None, g.contiguous()
+
+
 def _wide_keys(keys):
   """`keys` as the engine's int64 keys, for a C function that reads `const int64_t*`: int64 keys as they are, int32 keys widened on
   the device (tfra_keys_widen_i32).  Any other dtype raises TypeError before a launch."""

@@ -5,7 +5,7 @@ import ctypes
 import torch
 
 from .. import _capi
-from ._args import _narrow_keys, _ptr, _stream, _wide_keys
+from ._args import _grads_arg, _narrow_keys, _ptr, _stream, _wide_keys
 
 _WS = {}
 
@@ -328,19 +328,25 @@ def segment_sum(grads, idx, num_segments_dev, max_segments):
   return out
 
 
-def reduce_by_key(ids, rows):
+def reduce_by_key(ids, rows, grad_scale=None):
   """unique + unsorted_segment_sum, parallel per key (hot ids do not serialise) and bit-reproducible.
   Returns (keys[n] buffer in the dtype of `ids`, sums[n,dim] buffer, count device scalar): the first `count` entries are valid,
-  in a deterministic but unspecified key order."""
+  in a deterministic but unspecified key order.  The sums are float32.  Contiguous float16 / bfloat16 rows on the ids' device go
+  down as they are (tfra_reduce_by_key_typed: the same bits as their float32 up-cast gives), grad_scale — a one-element float32
+  device tensor the rows are multiplied by — with them."""
   wide = _wide_keys(ids.reshape(-1))
-  rows = rows.to(torch.float32).contiguous()
-  n, dim = wide.numel(), rows.shape[-1]
   dev = wide.device
+  n, dim = wide.numel(), rows.shape[-1]
+  typed, rows = _grads_arg(rows, dev, dim if 0 < n <= (1 << 18) and dim <= 256 else 1, grad_scale)
   keys = torch.empty(n, dtype=torch.int64, device=dev)
   sums = torch.empty((n, dim), dtype=torch.float32, device=dev)
   cnt = torch.zeros((), dtype=torch.int64, device=dev)
-  _capi.call("tfra_reduce_by_key", _workspace(dev), n, _ptr(wide), dim, _ptr(rows), _ptr(keys), _ptr(sums), _ptr(cnt),
-             _stream(dev))
+  if typed is not None:
+    _capi.call("tfra_reduce_by_key_typed", _workspace(dev), n, _ptr(wide), dim, ctypes.byref(typed), _ptr(keys), _ptr(sums), _ptr(cnt),
+               _stream(dev))
+  else:
+    _capi.call("tfra_reduce_by_key", _workspace(dev), n, _ptr(wide), dim, _ptr(rows), _ptr(keys), _ptr(sums), _ptr(cnt),
+               _stream(dev))
   return _narrow_keys(keys, ids.dtype), sums, cnt
 
 

@@ -274,15 +274,15 @@ class DynamicEmbeddingOptimizer:
     self.iterations += 1
     return self.opt.params(self.iterations)
 
-  def apply_gradients(self, grads_and_vars, name=None):
-    """grads_and_vars: iterable of (grad[N,dim], TrainableWrapper) — one global step for all pairs."""
+  def apply_gradients(self, grads_and_vars, name=None, grad_scale=None):
+    """grads_and_vars: iterable of (grad[N,dim], TrainableWrapper) — one global step for all pairs.  grad_scale: see apply_sparse."""
     p = self.begin_step()
     for grad, tw in grads_and_vars:
       if not isinstance(tw, TrainableWrapper):
         raise TypeError("expected the TrainableWrapper returned by embedding_lookup(..., return_trainable=True)")
       plan = tw.take_plan() if (self.opt.kind is not None and not self.exact_order) else None
       try:
-        self.apply_sparse(tw.params, tw.ids, grad, p, plan=plan)
+        self.apply_sparse(tw.params, tw.ids, grad, p, plan=plan, grad_scale=grad_scale)
       finally:
         if plan is not None:
           _release_plan(tw.params, plan)
@@ -407,10 +407,18 @@ class DynamicEmbeddingOptimizer:
         release(members)
       unbuilt.clear()
 
-  def _apply_generic(self, var, ids, grad):
+  @staticmethod
+  def _upcast(grad, dim, grad_scale):
+    """grad as the float32 matrix [n, dim] a route without a typed call reads: the up-cast, times grad_scale where there is one."""
+    grad = grad.reshape(-1, dim).to(torch.float32)
+    if grad_scale is not None:
+      grad = grad * torch.as_tensor(grad_scale).to(device=grad.device, dtype=torch.float32).reshape(())
+    return grad
+
+  def _apply_generic(self, var, ids, grad, grad_scale=None):
     """The reference's write-back sequence for an arbitrary rule (`Generic`)."""
     ids = torch.as_tensor(ids, device=var._primary).reshape(-1)
-    grad = grad.reshape(-1, var.dim).to(torch.float32)
+    grad = self._upcast(grad, var.dim, grad_scale)
     n = ids.numel()
     if n == 0:
       return
@@ -434,7 +442,7 @@ class DynamicEmbeddingOptimizer:
   @staticmethod
   def can_plan(var, n):
     """The planned / two-kernel write-back covers one shard, float32 / float16 / bfloat16 rows with dim % 4 == 0, dim <= 256
-    (gradients and the default row are float32 in every case; a half row is up-cast, updated in float32 and rounded once).
+    (the default row is float32, the gradients float32, float16 or bfloat16; a half row is up-cast, updated in float32 and rounded once).
     A miss of the write-back starts from ONE static row, so the variable's misses must be static (`variable.misses_are_static`:
     no callable initializer, or init_on_lookup — the lookup has admitted every key with its own row already)."""
     return (var.shard_num == 1 and misses_are_static(var) and var.dim % 4 == 0 and var.dim <= 256 and
@@ -451,22 +459,27 @@ class DynamicEmbeddingOptimizer:
       plan = SparsePlan(var._tables[0]._device, var.dim)
     return plan.build(ids)
 
-  def apply_sparse(self, var, ids, grad, p=None, plan=None):
+  def apply_sparse(self, var, ids, grad, p=None, plan=None, grad_scale=None):
     """Sum gradients of duplicate ids, then one fused update per unique key and shard.  p: the step's parameters from
-    `begin_step()`; None = this call IS the step (one variable per optimizer): the global step advances here."""
+    `begin_step()`; None = this call IS the step (one variable per optimizer): the global step advances here.
+    grad: float32, or float16 / bfloat16 as a half-precision dense part hands it back — the planned, the one-call and the
+    reduce_by_key routes read a contiguous half matrix as it is (the *_typed calls), every other route up-casts it first; the bits
+    are the same.  grad_scale: an optional one-element float32 device tensor the gradients are multiplied by (a GradScaler's
+    inverse scale), in the kernels where the matrix goes down as it is, as `grad.float() * grad_scale` elsewhere; it is never read
+    on the host.  A non-finite gradient propagates as it does in float32: callers check found_inf as they do now."""
     if p is None:
       p = self.begin_step()
     self._check(var)
     if self.opt.kind is None:
-      return self._apply_generic(var, ids, grad)
+      return self._apply_generic(var, ids, grad, grad_scale)
     if plan is not None:
       if getattr(var, "restrict_policy", None) is not None:
         var.restrict_policy.apply_update(plan.ids if ids is None else ids)   # (plan.ids are int64: the caller's keep the key dtype)
       t = var._tables[0]
-      t._table.apply_planned(p, plan, grad.reshape(-1, var.dim), t._default_value.to(torch.float32))
+      t._table.apply_planned(p, plan, grad.reshape(-1, var.dim), t._default_value.to(torch.float32), grad_scale=grad_scale)
       return
     ids = torch.as_tensor(ids, device=var._primary).reshape(-1)
-    grad = grad.reshape(-1, var.dim).to(torch.float32)
+    grad = grad.reshape(-1, var.dim)
     n = ids.numel()
     if n == 0:
       return
@@ -477,17 +490,17 @@ class DynamicEmbeddingOptimizer:
       # whole backward half in two kernels (tile reduce + bucket apply): no host sync, deterministic.  (More than 2^18
       # ids: the library reduces chunk by chunk and applies every key once — tfra_apply.hip: apply_sparse_big.)
       t = var._tables[0]
-      t._table.apply_sparse(p, ids, grad, t._default_value.to(torch.float32))
+      t._table.apply_sparse(p, ids, grad, t._default_value.to(torch.float32), grad_scale=grad_scale)
       return
     if var.dim % 4 == 0 and var.dim <= 256 and n <= (1 << 18) and not self.exact_order:
       # sharded variables / per-key misses (a callable initializer without init_on_lookup): the same parallel, order-fixed duplicate reduction
       # (tile reduce + bucket merge, float32 sums), then one fused update per unique key and shard — on a half / bfloat16
       # table the rule runs in float32 on the up-cast row and slots and the results are rounded to the storage type once.  (unique +
       # segment_sum walks a segment sequentially: 9 ms for a Zipf batch whose hottest id repeats 24 000 times.)
-      uniq_buf, gsum, cnt = device_ops.reduce_by_key(ids, grad)
+      uniq_buf, gsum, cnt = device_ops.reduce_by_key(ids, grad, grad_scale=grad_scale)
     else:
       uniq_buf, idx, cnt = device_ops.unique_no_sync(ids)
-      gsum = device_ops.segment_sum(grad, idx, cnt, n)
+      gsum = device_ops.segment_sum(self._upcast(grad, var.dim, grad_scale), idx, cnt, n)
     if var.shard_num == 1 and misses_are_static(var):
       # one shard: no partition, so the unique count never has to reach the host
       t = var._tables[0]

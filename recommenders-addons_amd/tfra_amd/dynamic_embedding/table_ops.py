@@ -22,7 +22,7 @@ import sys
 import torch
 
 from .. import _capi
-from ._args import (_TORCH2DT, _admitted_rows, _as_device, _as_tensor, _cap_for, _check_plan, _default_rows, _driver_ids,
+from ._args import (_TORCH2DT, _admitted_rows, _as_device, _as_tensor, _cap_for, _check_plan, _default_rows, _driver_ids, _grads_arg,
                     _narrow_keys, _out_rows, _over_plans, _ptr, _score_filter, _scores_for, _stream, _trim_to_count, _wide_keys)
 from .device_ops import _workspace
 
@@ -614,23 +614,34 @@ class _DeviceTable:
                full, _ptr(n_dev), _stream(self._device))
 
   # ---- write-backs of a batch whose ids may repeat; `plan`: a built `SparsePlan`, the id-only half made ahead ----
-  def apply_sparse(self, params, ids, grads, default_row):
-    """ids may repeat: duplicate gradients are summed (fixed order), one fused update per unique key."""
+  def apply_sparse(self, params, ids, grads, default_row, grad_scale=None):
+    """ids may repeat: duplicate gradients are summed (fixed order), one fused update per unique key.  A contiguous float16 /
+    bfloat16 gradient matrix on the table's device goes down as it is (tfra_table_apply_sparse_typed: the same bits as its
+    float32 up-cast gives), grad_scale — a one-element float32 device tensor the gradients are multiplied by — with it."""
     ids = self._keys(ids).reshape(-1)
-    grads = grads.to(self._device, torch.float32).contiguous()
+    typed, grads = _grads_arg(grads, self._device, self._dim, grad_scale)
     if grads.numel() != ids.numel() * self._dim:
       raise ValueError("Expected shape %s for grads, got %s" % ([ids.numel(), self._dim], list(grads.shape)))
     d = default_row.to(self._device, torch.float32).contiguous()
+    if typed is not None:
+      _capi.call("tfra_table_apply_sparse_typed", self._h, ctypes.byref(params), ids.numel(), _ptr(ids), ctypes.byref(typed), _ptr(d),
+                 _stream(self._device))
+      return
     _capi.call("tfra_table_apply_sparse", self._h, ctypes.byref(params), ids.numel(), _ptr(ids), _ptr(grads), _ptr(d),
                _stream(self._device))
 
-  def apply_planned(self, params, plan, grads, default_row, sync=True):
-    """Gradient half of apply_sparse for a batch whose id-only half was built ahead (`SparsePlan`)."""
+  def apply_planned(self, params, plan, grads, default_row, sync=True, grad_scale=None):
+    """Gradient half of apply_sparse for a batch whose id-only half was built ahead (`SparsePlan`); half gradients and
+    grad_scale as in apply_sparse (tfra_table_apply_planned_typed)."""
     _check_plan(plan, self._dim, self._device)
-    grads = grads.to(self._device, torch.float32).contiguous()
+    typed, grads = _grads_arg(grads, self._device, self._dim, grad_scale)
     if grads.numel() != plan.n * self._dim:
       raise ValueError("Expected shape %s for grads, got %s" % ([plan.n, self._dim], list(grads.shape)))
     d = default_row.to(self._device, torch.float32).contiguous()
+    if typed is not None:
+      _over_plans((plan,), self._device, sync, _capi.call, "tfra_table_apply_planned_typed", self._h, ctypes.byref(params), plan._h,
+                  ctypes.byref(typed), _ptr(d), _stream(self._device))
+      return
     _over_plans((plan,), self._device, sync, _capi.call, "tfra_table_apply_planned", self._h, ctypes.byref(params), plan._h,
                 _ptr(grads), _ptr(d), _stream(self._device))
 
