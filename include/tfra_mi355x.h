@@ -898,6 +898,61 @@ int tfra_table_apply_planned_typed(tfra_table_t* t, const tfra_opt_params* p, co
 int tfra_reduce_by_key_typed(tfra_workspace_t* ws, size_t n, const int64_t* ids, int dim, const tfra_grads* g,
                              int64_t* keys_out, float* rows_out, int64_t* d_count, tfra_stream_t stream);
 
+/* -- Whole rows out and back: the two table calls of a dense rule that has no fused write-back
+ *    (optimizers.Generic with whole_rows=True).  The rows are co-located [p | slot 1 | ..]: a key's whole row is read with one
+ *    probe and written with one probe.  Additive; ABI version 1. */
+typedef struct {
+  uint32_t struct_size;   /* = sizeof(tfra_row_fields) = 48 */
+  int32_t  n_fields;      /* must equal 1 + the table's aux_fields (1..5) */
+  float*   field[5];      /* field[f]: [n, dim] float32, row-major, 16-byte aligned, or NULL; entries >= n_fields must be NULL */
+} tfra_row_fields;
+
+/* tfra_table_fetch_planned: a READ over a built CSR plan of the table's dim (tfra_sparse_plan_build); U = its distinct keys.
+ *      *d_count      = U, or -1 when the plan overflowed, exactly as tfra_reduce_by_key reports it
+ *      keys_out[j]   j < U: the plan's distinct keys in the plan's key order — the order tfra_reduce_by_key over the same ids
+ *                    writes; unspecified, but the same j indexes every output of this call
+ *      gsum_out[j,:] bit for bit the row tfra_reduce_by_key_typed(ids, g) writes for that key (the same hot sums, the same
+ *                    summation tree).  g: the record of the typed calls.  g == NULL requires gsum_out == NULL: the call then
+ *                    fetches rows only and enqueues no sums launch
+ *      rows_out->field[f][j,:] = the exact float32 up-cast of what tfra_table_find_field(t, f, key, defaults, 0) returns, where
+ *                    defaults is `default_row` for f == 0 (ONE row in the table's value dtype, as tfra_table_find takes it) and
+ *                    the table's stored image of aux_init[f - 1] for f >= 1: a resident key gives its stored fields, a key that
+ *                    is not resident [default_row | aux_init ..].  A NULL field[f] is not read and not written
+ *    Rows at or beyond U are left as they are.  The call never inserts, touches no score, changes no size and counts no error:
+ *    find's probe (plain loads; both reserved key values are served), one probe per key, one read per wanted field.
+ *    Launches: the hot-sums launch when g is given, then ONE fetch launch; nothing is read on the host.
+ *    Limits: float32 / float16 / bfloat16 tables; dim % 4 == 0, dim <= 256; default_row, gsum_out and every field 16-byte aligned
+ *    (a half default_row: 8-byte); a plan of at most 2^18 ids.
+ *    Refused before anything is enqueued (tfra_last_error() names the function):
+ *      TFRA_ERR_INVALID      a NULL t, plan, keys_out, rows_out, d_count or default_row; a wrong struct_size or n_fields, a
+ *                            non-NULL entry beyond n_fields; a plan never built, or of another dim or device; gsum_out without g
+ *                            or g without gsum_out; whatever the typed calls refuse for g, with their codes
+ *      TFRA_ERR_UNSUPPORTED  an assign-only (SET) plan, another value dtype, the dim limits, a misaligned buffer
+ *    A plan of 0 ids sets *d_count = 0 and does nothing else. */
+int tfra_table_fetch_planned(tfra_table_t* t, const tfra_sparse_plan_t* plan, const tfra_grads* g,
+                             const void* default_row, int64_t* keys_out, const tfra_row_fields* rows_out,
+                             float* gsum_out, int64_t* d_count, tfra_stream_t stream);
+
+/* tfra_table_store_rows: the write that goes with it — a unique-keys upsert of whole rows given as float32 fields.
+ *    keys are UNIQUE within the call; d_n as in tfra_table_find_n (NULL: n; a negative count: 0).  field[0] must be non-NULL.
+ *    Every element is rounded to the table's value dtype ONCE, to nearest even: a NaN stays a NaN, overflow goes to infinity.
+ *    Nearest even also on a table with TFRA_OPTION_STOCHASTIC_ROUNDING (upserts keep nearest-even).
+ *      a resident key: every field with a non-NULL pointer is replaced, a NULL field keeps its bytes
+ *      a key that takes an empty slot or replaces a victim: non-NULL fields from the caller, NULL fields at aux_init
+ *    The table ends with the keys and field bytes this sequence leaves, wherever that sequence places every key:
+ *      tfra_table_insert_or_assign(keys, to_dtype(field[0]), NULL, TFRA_FLAG_UNIQUE_KEYS), then
+ *      tfra_table_insert_field(f, keys, to_dtype(field[f]), TFRA_FLAG_UNIQUE_KEYS) for each non-NULL f >= 1
+ *    with two differences:
+ *      - scores and the epoch move as for ONE insert_or_assign with scores == NULL, not 1 + S times
+ *      - on a bounded table at max_capacity the victim and admission rule is insert_or_assign's, applied once: a key that is
+ *        not admitted is dropped with its whole row and no error, where the sequence's field inserts would count one
+ *    One probe per key.  At most two launches: phase 1, and phase 2 only at max_capacity (the locked two-phase route of
+ *    tfra_table_insert_and_evict_n, without capture).  Under TFRA_OPTION_CAPTURE_SAFE it behaves as insert_or_assign does.
+ *    Limits and refusals as the fetch's: value dtypes, dim, alignment (TFRA_ERR_UNSUPPORTED); n < 2^31, a NULL t / keys / rows /
+ *    field[0], the record's checks (TFRA_ERR_INVALID).  n == 0 returns TFRA_OK and touches nothing. */
+int tfra_table_store_rows(tfra_table_t* t, size_t n, const int64_t* d_n, const int64_t* keys,
+                          const tfra_row_fields* rows, tfra_stream_t stream);
+
 /* The reduction half of tfra_reduce_by_key for a batch whose plan was built AHEAD (tfra_sparse_plan_build with dim = the
  * rows' dim, any stream): rows_out[dest[p], :] = sum of the rows of `grads` whose id equals ids[p] (same summation tree,
  * bit-reproducible).  dest [n] int32 maps batch positions to output rows and must be equal for all positions of one id —

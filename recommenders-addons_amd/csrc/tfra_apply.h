@@ -1,6 +1,7 @@
 // What the single-table write-backs (tfra_apply.hip) and the grouped one (tfra_apply_many.hip) share on the host, ONE copy each:
 // the sums' launch ladder by row width (with_nch) and the argument checks of a planned and of a combined write-back
-// (check_apply_planned, check_apply_combined), which the single call and every descriptor of the grouped call run.
+// (check_apply_planned, check_apply_combined), which the single call and every descriptor of the grouped call run; and what a
+// tfra_grads record must satisfy (check_typed), for the *_typed calls and for tfra_table_fetch_planned (tfra_rows.hip).
 // File-local in each unit (static), as keys_of of tfra_plan.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -28,6 +29,22 @@ static void with_nch(int nch, F&& f) {
 static Check check_rounding(const Table* t) {
   if (t->stochastic() && t->capture_safe)
     return refuse(TFRA_ERR_UNSUPPORTED, "TFRA_OPTION_STOCHASTIC_ROUNDING and TFRA_OPTION_CAPTURE_SAFE are both set (a replayed graph would reuse one call index)");
+  return Check{};
+}
+
+// What a tfra_grads itself must satisfy, before anything is enqueued.  forward: float32 without a scale — the untyped call, as it is.
+static Check check_typed(const tfra_grads* g, bool* forward) {
+  *forward = false;
+  if (!g || !g->grads) return refuse(TFRA_ERR_INVALID, "null gradients");
+  if (g->reserved != 0) return refuse(TFRA_ERR_INVALID, "tfra_grads.reserved must be 0");
+  if (g->dtype != TFRA_F32 && g->dtype != TFRA_F16 && g->dtype != TFRA_BF16)
+    return refuse(TFRA_ERR_INVALID, "tfra_grads.dtype must be float32, float16 or bfloat16");
+  if (g->dtype == TFRA_F32) {
+    if (g->d_scale) return refuse(TFRA_ERR_UNSUPPORTED, "float32 gradients take no scale (loss scaling belongs to float16)");
+    *forward = true;
+  } else if ((uintptr_t)g->grads & 7) {
+    return refuse(TFRA_ERR_UNSUPPORTED, "half gradients must be 8-B aligned");
+  }
   return Check{};
 }
 

@@ -186,21 +186,7 @@ extern "C" int tfra_table_apply_planned(tfra_table_t* tp, const tfra_opt_params*
 
 // ---- the *_typed calls: the gradient matrix as the caller's dense part left it (tfra_grads).  A typed call equals its untyped
 // twin on G32[e] = f32(grads[e]) * *d_scale; the kernels form G32 in registers (GradHalf, tfra_apply_device.h).
-// What a tfra_grads itself must satisfy, before anything is enqueued.  forward: float32 without a scale — the untyped call, as it is.
-static Check check_typed(const tfra_grads* g, bool* forward) {
-  *forward = false;
-  if (!g || !g->grads) return refuse(TFRA_ERR_INVALID, "null gradients");
-  if (g->reserved != 0) return refuse(TFRA_ERR_INVALID, "tfra_grads.reserved must be 0");
-  if (g->dtype != TFRA_F32 && g->dtype != TFRA_F16 && g->dtype != TFRA_BF16)
-    return refuse(TFRA_ERR_INVALID, "tfra_grads.dtype must be float32, float16 or bfloat16");
-  if (g->dtype == TFRA_F32) {
-    if (g->d_scale) return refuse(TFRA_ERR_UNSUPPORTED, "float32 gradients take no scale (loss scaling belongs to float16)");
-    *forward = true;
-  } else if ((uintptr_t)g->grads & 7) {
-    return refuse(TFRA_ERR_UNSUPPORTED, "half gradients must be 8-B aligned");
-  }
-  return Check{};
-}
+// (What a tfra_grads itself must satisfy, before anything is enqueued: check_typed, tfra_apply.h.)
 
 extern "C" int tfra_table_apply_planned_typed(tfra_table_t* tp, const tfra_opt_params* p, const tfra_sparse_plan_t* pl,
                                               const tfra_grads* g, const float* param_default_row, tfra_stream_t stream) {
@@ -444,3 +430,9 @@ extern "C" int tfra_plan_reduce_to(const tfra_sparse_plan_t* pl, const float* gr
   return TFRA_OK;
 }
 
+// The hot sums of a plan for a unit that has no sums kernel of its own (tfra_rows.hip): the launch tfra_reduce_by_key makes, over
+// the float matrix `grads` or, hg != nullptr (checked by check_typed), over hg's half matrix.
+void tfra::hot_sums_launch(hipStream_t s, const tfra_sparse_plan_t* pl, const float* grads, const tfra_grads* hg, unsigned bin_blocks) {
+  if (hg) launch_hot_sums(s, pl, nullptr, bin_blocks, nullptr, 0, half_of(hg));
+  else launch_hot_sums(s, pl, grads, bin_blocks, nullptr, 0);
+}

@@ -755,6 +755,7 @@ extern "C" int tfra_sparse_plan_build(tfra_sparse_plan_t* pl, size_t n, const in
     pl->skip_counts_once = false;
     if (on_device(pl->device) != hipSuccess) return refuse(TFRA_ERR_HIP, "hipSetDevice");
     pl->n = 0;
+    pl->ever_built = true;
     return Check{};
   });
   if (c.code) return report("sparse_plan_build: ", c);
@@ -839,7 +840,7 @@ extern "C" int tfra_multi_sparse_plan_build(tfra_workspace_t* ws, size_t n_plans
   if (n_act && (rc = many_begin(ws, 0, blob.bytes(), s, &up))) return rc;
   // from here on the call enqueues.  As in the single call, a plan holds no build until its launches are enqueued, and a public
   // build always counts
-  for (size_t i = 0; i < n_plans; ++i) { descs[i].plan->skip_counts_once = false; descs[i].plan->n = 0; }
+  for (size_t i = 0; i < n_plans; ++i) { descs[i].plan->skip_counts_once = false; descs[i].plan->n = 0; descs[i].plan->ever_built = true; }
   if (n_act == 0) return TFRA_OK;
   PlanManyRec* recs = section<PlanManyRec>(up.host, rec_off);
   for (size_t k = 0; k < n_act; ++k) {

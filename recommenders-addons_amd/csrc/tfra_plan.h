@@ -8,6 +8,7 @@
 //   tfra_step.hip     the overlapped step's driver (its kernel: tfra_step_impl.h)
 //   tfra_find_insert.hip  find_or_insert over a CSR plan's keys (tfra_table_find_or_insert_planned)
 //   tfra_tierplan.hip  the same over a tier (tfra_tier_find_or_insert_planned)
+//   tfra_rows.hip     whole rows and gradient sums of a CSR plan's keys (tfra_table_fetch_planned)
 // The object holds types of tfra_plan_device.h (anonymous namespace): every unit includes the same definitions, so it has one
 // layout.  A helper shared across units cannot take or return such a type (its linkage would be internal): the shared ones below
 // take the plan object, pointers and scalars; keys_of, which returns one, is defined here for each unit.
@@ -85,6 +86,7 @@ struct tfra_sparse_plan {
   const int64_t* scat_ids = nullptr;   // the batch whose pairs the segments hold (nullptr: none)
   size_t scat_n = 0;
   unsigned char tab_state[2] = {0, 0}; // what each table holds (TAB_*; the build rules: setplan_prepare, tfra_setplan.hip)
+  bool ever_built = false;         // a build call has reached this object (n == 0 since: a batch of 0 ids, not "never built")
 };
 enum : unsigned char { TAB_EMPTY = 0, TAB_LISTED = 1, TAB_LISTLESS = 2 };
 
@@ -108,6 +110,8 @@ int own_plan(Table* t, tfra_sparse_plan** out);
 int apply_planned_impl(tfra_table_t* tp, const tfra_opt_params* p, const tfra_sparse_plan_t* pl, const float* grads,
                        const float* param_default_row, tfra_stream_t stream, unsigned* progress, unsigned progress_val,
                        const CombEnt* comb = nullptr, const tfra_grads* hg = nullptr);
+// the hot sums of a plan, as tfra_reduce_by_key launches them (hg: a checked half matrix, else `grads`); caller: tfra_rows.hip
+void hot_sums_launch(hipStream_t s, const tfra_sparse_plan_t* pl, const float* grads, const tfra_grads* hg, unsigned bin_blocks);
 
 // ---- tfra_own.hip
 // Host half of an ownership write-back of a plan's keys: everything but the launches (upsert_planned_impl launches the pair

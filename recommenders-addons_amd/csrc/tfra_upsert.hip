@@ -19,7 +19,8 @@ using namespace tfra;
 // (The <G, true, true> instance has a TWIN in tfra_tierstep_many.hip, insert_evict_whole_body, which takes its key index as an
 // argument; handing this body the index changed these kernels' registers — DESIGN §4.25.  A fix here belongs there too.
 // The <G, false, false> instance has one in tfra_find_insert_many.hip, find_insert_evict_body — DESIGN §4.27.  A fix in one belongs
-// in the other.)
+// in the other.  The <G, false, false> instance has a second one in tfra_rows.hip, store_rows_evict_kernel, whose row comes from
+// float32 fields — DESIGN §4.34.)
 template <int G, bool CAPTURE, bool WHOLE_IN>
 __device__ __forceinline__ void insert_evict_body(const TableView& v, size_t n, const i64* __restrict__ keys,
                                                   const unsigned char* __restrict__ vals,
@@ -120,7 +121,8 @@ __global__ __launch_bounds__(256) void insert_evict_rows_kernel(TableView v, siz
 // WHOLE (TFRA_INSERT_WHOLE_ROWS): `vals` rows are whole co-located rows; the slot vectors of a new AND of a resident key are the
 // caller's, init_aux_fields is not applied.
 // (The WHOLE instance has a TWIN in tfra_tierstep_many.hip, insert_whole_counted_body, on a wave index local to a descriptor of
-// the grouped admission — DESIGN §4.25.  A fix here belongs there too.)
+// the grouped admission — DESIGN §4.25.  A fix here belongs there too.  A second one is store_rows_kernel, tfra_rows.hip, whose
+// rows come from float32 fields — DESIGN §4.34.)
 template <int G, int U, bool WHOLE>
 __global__ __launch_bounds__(256) void insert_counted_kernel(TableView v, size_t n_buf, const i64* __restrict__ keys,
                                                              const unsigned char* __restrict__ vals, const u64* __restrict__ scores,

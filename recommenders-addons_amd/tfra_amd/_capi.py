@@ -71,6 +71,11 @@ class Grads(ctypes.Structure):
   _fields_ = [("grads", ctypes.c_void_p), ("dtype", ctypes.c_int32), ("reserved", ctypes.c_int32), ("d_scale", ctypes.c_void_p)]
 
 
+class RowFields(ctypes.Structure):
+  """tfra_row_fields (include/tfra_mi355x.h): the float32 field tensors of tfra_table_fetch_planned / tfra_table_store_rows."""
+  _fields_ = [("struct_size", ctypes.c_uint32), ("n_fields", ctypes.c_int32), ("field", ctypes.c_void_p * 5)]
+
+
 class StepDesc(ctypes.Structure):
   """tfra_step_desc (include/tfra_mi355x.h): one table's step in tfra_multi_step_prefetch."""
   _fields_ = [
@@ -281,6 +286,8 @@ _SIGS = {
     "tfra_table_apply_sparse_typed": [_P, ctypes.POINTER(OptParams), _SZ, _P, ctypes.POINTER(Grads), _P, _P],
     "tfra_table_apply_planned_typed": [_P, ctypes.POINTER(OptParams), _P, ctypes.POINTER(Grads), _P, _P],
     "tfra_reduce_by_key_typed": [_P, _SZ, _P, _I, ctypes.POINTER(Grads), _P, _P, _P, _P],
+    "tfra_table_fetch_planned": [_P, _P, ctypes.POINTER(Grads), _P, _P, ctypes.POINTER(RowFields), _P, _P, _P],
+    "tfra_table_store_rows": [_P, _SZ, _P, _P, ctypes.POINTER(RowFields), _P],
     "tfra_sparse_plan_create": [_I, _P],
     "tfra_sparse_plan_destroy": [_P],
     "tfra_sparse_plan_build": [_P, _SZ, _P, _I, _P],

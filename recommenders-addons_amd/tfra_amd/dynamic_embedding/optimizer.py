@@ -20,8 +20,9 @@ import torch
 from .. import _capi
 from . import device_ops
 from ._args import _driver_ids, _narrow_keys, _ptr, _stream
-from .table_ops import SparsePlan, apply_planned_combined_many, build_plans_many
-from .variable import SparseTrainableWrapper, TrainableWrapper, Variable, _pool_plan, _release_plan, misses_are_static
+from .table_ops import HkvEvictStrategy, SparsePlan, apply_planned_combined_many, build_plans_many
+from .variable import (SparseTrainableWrapper, TrainableWrapper, Variable, _has_tiered_shards, _pool_plan, _release_plan,
+                       misses_are_static)
 
 
 class _Opt:
@@ -123,10 +124,20 @@ class Generic(_Opt):
   sum the gradients of repeated ids, (1+S) table finds, the rule on the dense [U, dim] tensors — host-framework
   math, as TF's ResourceApply* kernels are for the reference — and (1+S) table upserts.  Subclass and implement
   `update(step, p, g, *slots) -> (p_new, *slots_new)` (fp32 torch tensors), or pass `update=`.  The four rules
-  with a fused HIP kernel (SGD, Adam, Adagrad, Ftrl) do not take this path, nor do Momentum / RMSProp created with fused=True."""
-  kind = None
+  with a fused HIP kernel (SGD, Adam, Adagrad, Ftrl) do not take this path, nor do Momentum / RMSProp created with fused=True.
 
-  def __init__(self, slots=(), slot_init=(), update=None):
+  whole_rows=True (opt-in): the same rule on the same tensors, with the table work done by TWO planned calls instead
+  of a reduction, 1 + S finds and 1 + S upserts: `fetch_planned` reads every distinct key's whole co-located row [p | slots] with
+  one probe and sums the gradients of repeated ids next to it (a float16 / bfloat16 gradient matrix goes down as it is),
+  `store_rows` writes the whole row back with one probe, rounding each element to the row type once.  The rows and slots end
+  bit-identical to the default route.  Taken for one shard that is not tiered, float32 / float16 / bfloat16 rows with
+  dim % 4 == 0 and dim <= 256, at most 2^18 ids, static misses, and neither bp_v2 nor exact_order; everything else keeps the
+  default route.  On a bounded table the scores move as for ONE upsert per step, not 1 + S."""
+  kind = None
+  whole_rows = False
+
+  def __init__(self, slots=(), slot_init=(), update=None, whole_rows=False):
+    self.whole_rows = bool(whole_rows)
     self.slots = tuple(slots)
     self._slot_init = tuple(float(x) for x in slot_init) + (0.0,) * (4 - len(slot_init))
     if len(self.slots) > 4:
@@ -151,8 +162,10 @@ class Momentum(Generic):
   (TFRA_OPT_MOMENTUM / TFRA_OPT_NESTEROV), as for SGD, Adam, Adagrad and Ftrl — same slots, same rows, so a variable trained
   through one form continues through the other."""
 
-  def __init__(self, learning_rate=0.01, momentum=0.9, use_nesterov=False, fused=False):
-    super().__init__(slots=("momentum",), slot_init=(0.0,))
+  def __init__(self, learning_rate=0.01, momentum=0.9, use_nesterov=False, fused=False, whole_rows=False):
+    if fused and whole_rows:
+      raise ValueError("fused=True and whole_rows=True exclude each other: whole_rows is a form of the Generic route")
+    super().__init__(slots=("momentum",), slot_init=(0.0,), whole_rows=whole_rows)
     self.lr, self.momentum, self.nesterov = learning_rate, momentum, use_nesterov
     if fused:
       self.kind = _capi.OPT_NESTEROV if use_nesterov else _capi.OPT_MOMENTUM
@@ -178,8 +191,10 @@ class RMSProp(Generic):
   mom = momentum*mom + lr*g/sqrt(ms + eps); p -= mom.  `rms` starts at 1 (TF1) — pass initial_rms=0 for Keras.
   fused=False (the default): the `Generic` route.  fused=True: the fused HIP write-backs (TFRA_OPT_RMSPROP); same slots and rows."""
 
-  def __init__(self, learning_rate=0.001, decay=0.9, momentum=0.0, epsilon=1e-10, initial_rms=1.0, fused=False):
-    super().__init__(slots=("rms", "momentum"), slot_init=(initial_rms, 0.0))
+  def __init__(self, learning_rate=0.001, decay=0.9, momentum=0.0, epsilon=1e-10, initial_rms=1.0, fused=False, whole_rows=False):
+    if fused and whole_rows:
+      raise ValueError("fused=True and whole_rows=True exclude each other: whole_rows is a form of the Generic route")
+    super().__init__(slots=("rms", "momentum"), slot_init=(initial_rms, 0.0), whole_rows=whole_rows)
     self.lr, self.rho, self.momentum, self.eps = learning_rate, decay, momentum, epsilon
     if fused:
       self.kind = _capi.OPT_RMSPROP
@@ -280,7 +295,7 @@ class DynamicEmbeddingOptimizer:
     for grad, tw in grads_and_vars:
       if not isinstance(tw, TrainableWrapper):
         raise TypeError("expected the TrainableWrapper returned by embedding_lookup(..., return_trainable=True)")
-      plan = tw.take_plan() if (self.opt.kind is not None and not self.exact_order) else None
+      plan = tw.take_plan() if ((self.opt.kind is not None or getattr(self.opt, "whole_rows", False)) and not self.exact_order) else None
       try:
         self.apply_sparse(tw.params, tw.ids, grad, p, plan=plan, grad_scale=grad_scale)
       finally:
@@ -439,6 +454,45 @@ class DynamicEmbeddingOptimizer:
     for v, s_new in zip(views, new[1:]):
       v.upsert(uniq, s_new.to(var.value_dtype))
 
+  def _takes_whole_rows(self, var, n):
+    """Whether a `Generic` rule's step over n ids of `var` takes `_apply_generic_rows`: asked for (whole_rows=True), a plannable
+    batch, and none of what keeps the default route (exact_order, bp_v2, a tiered shard; a CUSTOMIZED table, whose upserts carry
+    the caller's scores)."""
+    if not getattr(self.opt, "whole_rows", False) or self.exact_order or var.bp_v2 or _has_tiered_shards(var):
+      return False
+    if n == 0 or not self.can_plan(var, n):
+      return False
+    t = var._tables[0]
+    return hasattr(t, "fetch_planned") and getattr(t, "_evict_strategy", None) != HkvEvictStrategy.CUSTOMIZED
+
+  def _apply_generic_rows(self, var, ids, grad, plan=None, grad_scale=None):
+    """`_apply_generic` with the table work in two planned calls: every distinct key's whole row out with the
+    gradient sums (`fetch_planned`), ONE host read of the count, the rule on the first u rows, the whole rows back
+    (`store_rows`).  plan: the batch's built plan (the wrapper's, `plan_writeback=True`); None: a pooled or fresh one is built."""
+    if plan is None:
+      ids = torch.as_tensor(ids, device=var._primary).reshape(-1)
+    if getattr(var, "restrict_policy", None) is not None:
+      var.restrict_policy.apply_update(plan.ids if ids is None else ids)
+    t = var._tables[0]
+    own = pooled = False
+    if plan is None:
+      own, pooled, plan = True, True, _pool_plan(var)
+      if plan is None:
+        plan, pooled = SparsePlan(var._primary, var.dim), False
+      plan.build(t._table._keys(ids).reshape(-1))
+    try:
+      S = len(self.opt.slots)
+      want = [True] * (1 + S) + [False] * (var.aux_fields - S)   # fields the rule does not own are neither read nor written
+      keys, fields, gsum, cnt = t._table.fetch_planned(plan, grads=grad.reshape(-1, var.dim), grad_scale=grad_scale, fields=want)
+    finally:
+      if own and pooled:
+        _release_plan(var, plan)
+    u = int(cnt.item())
+    if u < 0:
+      raise RuntimeError("the write-back plan of %r overflowed" % var.name)
+    new = self.opt.update(self.iterations, fields[0][:u], gsum[:u], *[f[:u] for f in fields[1:1 + S]])
+    t._table.store_rows(keys[:u], list(new[:1 + S]) + [None] * (var.aux_fields - S))
+
   @staticmethod
   def can_plan(var, n):
     """The planned / two-kernel write-back covers one shard, float32 / float16 / bfloat16 rows with dim % 4 == 0, dim <= 256
@@ -471,7 +525,9 @@ class DynamicEmbeddingOptimizer:
       p = self.begin_step()
     self._check(var)
     if self.opt.kind is None:
-      return self._apply_generic(var, ids, grad, grad_scale)
+      if self._takes_whole_rows(var, plan.n if plan is not None else torch.as_tensor(ids).numel()):
+        return self._apply_generic_rows(var, ids, grad, plan, grad_scale)
+      return self._apply_generic(var, plan.ids if ids is None else ids, grad, grad_scale)
     if plan is not None:
       if getattr(var, "restrict_policy", None) is not None:
         var.restrict_policy.apply_update(plan.ids if ids is None else ids)   # (plan.ids are int64: the caller's keep the key dtype)

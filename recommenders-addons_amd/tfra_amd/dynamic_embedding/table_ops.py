@@ -23,7 +23,8 @@ import torch
 
 from .. import _capi
 from ._args import (_TORCH2DT, _admitted_rows, _as_device, _as_tensor, _cap_for, _check_plan, _default_rows, _driver_ids, _grads_arg,
-                    _narrow_keys, _out_rows, _over_plans, _ptr, _score_filter, _scores_for, _stream, _trim_to_count, _wide_keys)
+                    _narrow_keys, _out_rows, _over_plans, _ptr, _rows_on, _score_filter, _scores_for, _stream, _trim_to_count,
+                    _wide_keys)
 from .device_ops import _workspace
 
 KHkvHashTableInitCapacity = 1024 * 1024  # PY/hkv_hashtable_ops.py:40-44
@@ -686,6 +687,78 @@ class _DeviceTable:
     _over_plans((plan,), self._device, sync, _capi.call, "tfra_table_upsert_planned", self._h, plan._h, _ptr(values), _ptr(scores),
                 _stream(self._device))
 
+  # ---- whole rows out and back: the two calls of a dense rule without a fused write-back (optimizers.Generic, whole_rows=True) ----
+  def _row_fields(self, tensors):
+    """A tfra_row_fields over `tensors` (one per field, None = NULL)."""
+    rf = _capi.RowFields()
+    rf.struct_size, rf.n_fields = ctypes.sizeof(_capi.RowFields), 1 + self._aux_fields
+    for f, x in enumerate(tensors):
+      rf.field[f] = None if x is None else x.data_ptr()
+    return rf
+
+  def fetch_planned(self, plan, grads=None, grad_scale=None, fields=None, default_row=None):
+    """The rows of a batch's distinct keys, whole, and the per-key sums of its gradients (tfra_table_fetch_planned): `plan` is a
+    built `SparsePlan` of this table's dim.  -> (keys [n] int64, [field tensors], gsum, count): row j < count of every output
+    belongs to keys[j]; field tensor f is [n, dim] float32 — the exact up-cast of the stored field of a resident key, of
+    `default_row` (None: the table's; one row in the table's value dtype) for field 0 and of aux_init for the slot vectors of a
+    key that is not resident — or None where `fields[f]` is false (fields None: all of them); gsum [n, dim] float32 the sums
+    `device_ops.reduce_by_key` gives for the same ids and `grads` (float32, or float16 / bfloat16 as they are; grad_scale as in
+    `apply_sparse`), None without `grads`; count a one-element int64 DEVICE tensor (-1: the plan overflowed).  Rows at or beyond
+    count are not written.  A read: nothing is inserted, no score is touched, nothing is read on the host."""
+    _check_plan(plan, self._dim, self._device)
+    n, nf = plan.n, 1 + self._aux_fields
+    want = [True] * nf if fields is None else [bool(x) for x in fields]
+    if len(want) != nf:
+      raise ValueError("fields must have one entry per field of the row (%d), got %d" % (nf, len(want)))
+    typed = g = None
+    if grads is not None:
+      typed, g = _grads_arg(grads, self._device, self._dim, grad_scale)
+      if g.numel() != n * self._dim:
+        raise ValueError("Expected shape %s for grads, got %s" % ([n, self._dim], list(g.shape)))
+      if typed is None:
+        typed = _capi.Grads(g.data_ptr(), _capi.TFRA_F32, 0, None)
+    d = _rows_on(self._value_dtype, self._device, self._default_value if default_row is None else default_row, "default row")
+    if d.numel() < self._dim:
+      raise ValueError("default row needs dim=%d elements, got %d" % (self._dim, d.numel()))
+    keys = torch.empty(n, dtype=torch.int64, device=self._device)
+    outs = [torch.empty((n, self._dim), dtype=torch.float32, device=self._device) if w else None for w in want]
+    gsum = torch.empty((n, self._dim), dtype=torch.float32, device=self._device) if g is not None and n else None
+    count = torch.zeros(1, dtype=torch.int64, device=self._device)
+    if n:
+      rf = self._row_fields(outs)
+      _over_plans((plan,), self._device, True, _capi.call, "tfra_table_fetch_planned", self._h, plan._h,
+                  ctypes.byref(typed) if gsum is not None else None, _ptr(d), _ptr(keys), ctypes.byref(rf), _ptr(gsum), _ptr(count),
+                  _stream(self._device))
+    return keys, outs, gsum, count
+
+  def store_rows(self, keys, fields, count=None):
+    """The write that goes with `fetch_planned` (tfra_table_store_rows): a unique-keys upsert of whole rows given as float32
+    field tensors.  keys [n] int64, UNIQUE; fields: one [n, dim] float32 tensor per field of the row, or None for a field that
+    is not written (a resident key keeps its bytes there, a new key starts at aux_init); fields[0] is required.  Every element
+    is rounded to the table's value dtype once, to nearest even.  count: a device int64 count of the leading keys that are
+    written (None: all).  Scores and the epoch move as for ONE upsert(unique_keys=True) without scores."""
+    keys = _as_tensor(keys, self._device)
+    if keys.dtype != torch.int64:
+      raise TypeError("store_rows takes the engine's int64 keys (as fetch_planned returns them), got %s" % keys.dtype)
+    keys = keys.to(self._device).contiguous().reshape(-1)
+    n, nf = keys.numel(), 1 + self._aux_fields
+    fields = list(fields)
+    if len(fields) != nf:
+      raise ValueError("fields must have one entry per field of the row (%d), got %d" % (nf, len(fields)))
+    if fields[0] is None:
+      raise ValueError("fields[0], the embedding, is required")
+    rows = []
+    for f, x in enumerate(fields):
+      if x is not None:
+        x = x.to(self._device, torch.float32).contiguous()
+        if x.numel() != n * self._dim:
+          raise ValueError("Expected shape %s for field %d, got %s" % ([n, self._dim], f, list(x.shape)))
+      rows.append(x)
+    if n == 0:
+      return
+    rf = self._row_fields(rows)
+    _capi.call("tfra_table_store_rows", self._h, n, _ptr(count), _ptr(keys), ctypes.byref(rf), _stream(self._device))
+
 
 class _DeviceTier:
   """Owns one tfra_tier_t: `upper`, a bounded LRU / EPOCHLRU _DeviceTable, in front of `lower`, a growing _DeviceTable without
@@ -1088,7 +1161,17 @@ class _LookupInterfaceMirror:
     return total
 
 
-class CuckooHashTable(_LookupInterfaceMirror):
+class _WholeRows:
+  """`fetch_planned` / `store_rows` of a plain table's device table (`_DeviceTable`'s: DESIGN 4.34)."""
+
+  def fetch_planned(self, plan, grads=None, grad_scale=None, fields=None):
+    return self._table.fetch_planned(plan, grads=grads, grad_scale=grad_scale, fields=fields)
+
+  def store_rows(self, keys, fields, count=None):
+    return self._table.store_rows(keys, fields, count=count)
+
+
+class CuckooHashTable(_LookupInterfaceMirror, _WholeRows):
   """PY/cuckoo_hashtable_ops.py:45-145.  Growing, never-evicting table (libcuckoo semantics)."""
 
   def __init__(self, key_dtype, value_dtype, default_value, name="CuckooHashTable", checkpoint=True, init_size=0,
@@ -1116,7 +1199,7 @@ class CuckooHashTable(_LookupInterfaceMirror):
     self._table.accum_or_assign(keys, values_or_deltas, exists)
 
 
-class HkvHashTable(_LookupInterfaceMirror):
+class HkvHashTable(_LookupInterfaceMirror, _WholeRows):
   """PY/hkv_hashtable_ops.py:47-175.  Bounded table with per-key scores and in-bucket eviction."""
 
   def __init__(self, key_dtype, value_dtype, default_value, name="HkvHashTable", checkpoint=True,
