@@ -884,7 +884,18 @@ int tfra_reduce_by_key(tfra_workspace_t* ws, size_t n, const int64_t* ids, int d
  *      TFRA_ERR_UNSUPPORTED  half gradients that are not 8-byte aligned; a float32 matrix with a scale (loss scaling belongs to
  *                            float16)
  *      and everything the twin checks, with the twin's codes.
- *    Not typed: the combined write-backs (grad_out is the small stream), tfra_table_apply_optimizer, the step drivers. */
+ *    The combined write-backs are typed too: tfra_table_apply_planned_combined_typed below and
+ *    tfra_multi_apply_planned_combined_typed (with the grouped calls).  Their contract is the same sentence over grad_out:
+ *      A typed combined call equals its untyped twin given the float32 matrix  GO32[r] = f32(grad_out[r]) * s,  bit for bit.
+ *    The product is formed BEFORE the combiner's backward: entry e's gradient is ((f32(g) * s) / den) * w, in that order, each
+ *    step rounded on its own.  Everything behind GO32 is the twin's: the entry records, the denominators, the summation order of
+ *    repeated ids, float32 partial sums, the rule and the rounding (stochastic included), scores, phase 2, the epoch step, the
+ *    plan's error latch.  The refusals are those above, raised before anything is enqueued, and what the twin checks (half grad_out
+ *    8-byte aligned instead of 16).  Addressing: the kernels address a half grad_out with 32-bit ELEMENT offsets, so a typed call
+ *    on halves refuses n_rows * dim >= 2^32 with TFRA_ERR_UNSUPPORTED (the twin's n_rows < 2^30 holds besides); it does not widen
+ *    the addresses.
+ *    Not typed: tfra_table_apply_optimizer, the step drivers, the weight-gradient calls (the *_backprop_weights family)
+ *    and tfra_sparse_segment_combine_backprop: they take float32. */
 typedef struct {
   const void*  grads;    /* [n, dim] row-major in `dtype`; float32: 16-byte aligned, halves: 8-byte aligned */
   int32_t      dtype;    /* TFRA_F32 | TFRA_F16 | TFRA_BF16 */
@@ -897,6 +908,10 @@ int tfra_table_apply_planned_typed(tfra_table_t* t, const tfra_opt_params* p, co
                                    const tfra_grads* g, const float* param_default_row, tfra_stream_t stream);
 int tfra_reduce_by_key_typed(tfra_workspace_t* ws, size_t n, const int64_t* ids, int dim, const tfra_grads* g,
                              int64_t* keys_out, float* rows_out, int64_t* d_count, tfra_stream_t stream);
+/* tfra_table_apply_planned_combined with grad_out [n_rows, dim] as a tfra_grads.  TFRA_F32 with a NULL scale forwards to it. */
+int tfra_table_apply_planned_combined_typed(tfra_table_t* t, const tfra_opt_params* p, const tfra_sparse_plan_t* plan,
+                                            const tfra_grads* grad_out, const int64_t* seg, const float* weights /* may be NULL */,
+                                            int combiner, size_t n_rows, const float* param_default_row, tfra_stream_t stream);
 
 /* -- Whole rows out and back: the two table calls of a dense rule that has no fused write-back
  *    (optimizers.Generic with whole_rows=True).  The rows are co-located [p | slot 1 | ..]: a key's whole row is read with one
@@ -1405,6 +1420,32 @@ typedef struct {
 } tfra_apply_combined_desc;
 int tfra_multi_apply_planned_combined(tfra_workspace_t* ws, size_t n_tables, const tfra_apply_combined_desc* descs,
                                       uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
+
+/* The same with each descriptor's grad_out as a tfra_grads record — half-precision gradients, above: table i ends bit-identical to
+ * tfra_table_apply_planned_combined_typed on its descriptor.  Descriptors of all three formats, with and without a scale, may
+ * stand in one list; each is checked as the single typed call checks it, all of them before anything is enqueued, and a refused
+ * list writes nothing (the message names the descriptor's index).  Everything else is tfra_multi_apply_planned_combined's.
+ * The format is one more axis of the launch classes, with two values — float32, or half (float16 and bfloat16 share a launch:
+ * the format is a wave-uniform value in the descriptor's record).
+ * *launches_out (optional, host): the kernel launches enqueued =
+ *   3 + ((NCH, float-or-half) classes present) + ((rule, storage type, float-or-half) classes present)
+ *     + ((rule, storage type, float-or-half) classes with a table at max_capacity),
+ * 0 when no descriptor has ids.  A list that is all half or all float has the untyped call's count (26 growing float32 tables of
+ * dims 16 / 32 / 64 / 128 with one rule: 6); with one float32 descriptor of dim 16 among 25 bfloat16 ones: 3 + 3 + 2 = 8.
+ * A descriptor whose table rounds stochastically is served by tfra_table_apply_planned_combined_typed behind the grouped launches. */
+typedef struct {
+  uint32_t struct_size;              /* = sizeof(tfra_apply_combined_typed_desc) */
+  int32_t  combiner;                 /* 0 sum | 1 mean | 2 sqrtn */
+  tfra_table_t* table;
+  const tfra_opt_params* opt;
+  const tfra_sparse_plan_t* plan;
+  tfra_grads grad_out;               /* [n_rows, dim] in grad_out.dtype, with its optional device scale */
+  const int64_t* seg; const float* weights;   /* weights may be NULL */
+  size_t n_rows;
+  const float* param_default_row;    /* [dim] float32 */
+} tfra_apply_combined_typed_desc;    /* 88 bytes */
+int tfra_multi_apply_planned_combined_typed(tfra_workspace_t* ws, size_t n_tables, const tfra_apply_combined_typed_desc* descs,
+                                            uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
 
 /* The CSR plans of MANY batches in one call (a 26-table model's write-back plans are 26 tfra_sparse_plan_build calls = 78 launches
  * otherwise): descs[i].plan ends as tfra_sparse_plan_build(plan, n, ids, dim, stream) leaves it — the same device code runs, with

@@ -74,11 +74,12 @@ static Check check_apply_planned(const Table* t, const tfra_opt_params* p, const
 }
 
 // The checks tfra_table_apply_planned_combined makes before it forms the entry records (apply_planned_impl's follow behind them),
-// also the first half of a descriptor's.  active: the plan holds ids.
+// also the first half of a descriptor's.  active: the plan holds ids.  grad_mask: 15 for a float grad_out, 7 for the float16 /
+// bfloat16 one of the *_combined_typed calls, whose kernels address grad_out with 32-bit element offsets: n_rows * dim < 2^32 then.
 template <class AtEntry>
-static Check check_apply_combined(const Table* t, const tfra_opt_params* p, const tfra_sparse_plan* pl, const float* grad_out,
+static Check check_apply_combined(const Table* t, const tfra_opt_params* p, const tfra_sparse_plan* pl, const void* grad_out,
                                   const int64_t* seg, const float* weights, int combiner, size_t n_rows, const float* param_default_row,
-                                  AtEntry&& at_entry) {
+                                  AtEntry&& at_entry, unsigned grad_mask = 15u) {
   if (!t || !p || !pl) return refuse(TFRA_ERR_INVALID, "null argument");
   if (combiner < 0 || combiner > 2) return refuse(TFRA_ERR_INVALID, "combiner must be 0 (sum), 1 (mean) or 2 (sqrtn)");
   if (Check e = check_rounding(t); e.done()) return e;
@@ -88,7 +89,10 @@ static Check check_apply_combined(const Table* t, const tfra_opt_params* p, cons
   if (pl->n == 0) return nothing_to_do();
   if (!grad_out || !seg || !param_default_row) return refuse(TFRA_ERR_INVALID, "null buffer");
   if (n_rows == 0 || n_rows >= (1ULL << 30)) return refuse(TFRA_ERR_INVALID, "need 1 <= n_rows < 2^30");
-  if ((((uintptr_t)grad_out | (uintptr_t)param_default_row) & 15) || ((uintptr_t)seg & 7) || ((uintptr_t)weights & 3))
-    return refuse(TFRA_ERR_UNSUPPORTED, "grad_out / default buffers must be 16-B aligned");
+  if (grad_mask != 15u && (unsigned long long)n_rows * (unsigned long long)t->opts.dim >= (1ULL << 32))
+    return refuse(TFRA_ERR_UNSUPPORTED, "half grad_out is addressed with 32-bit element offsets: need n_rows * dim < 2^32");
+  if (((uintptr_t)grad_out & grad_mask) || ((uintptr_t)param_default_row & 15) || ((uintptr_t)seg & 7) || ((uintptr_t)weights & 3))
+    return refuse(TFRA_ERR_UNSUPPORTED, grad_mask == 15u ? "grad_out / default buffers must be 16-B aligned"
+                                                         : "half grad_out must be 8-B aligned, the default row 16-B");
   return Check{};
 }

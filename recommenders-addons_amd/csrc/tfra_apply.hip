@@ -1,7 +1,7 @@
 // GRADIENT HALF of a write-back whose ids may repeat (tfra_table_apply_planned, over a CSR plan of tfra_csr.hip): the hot sums,
 // then one fused optimizer update per unique key (their bodies: tfra_apply_device.h); the same sums written out instead
 // (tfra_reduce_by_key, tfra_plan_reduce_to); the combined form (tfra_table_apply_planned_combined) and the one-call form
-// (tfra_table_apply_sparse); the *_typed forms of the three calls that read an [n, dim] gradient matrix, for float16 / bfloat16
+// (tfra_table_apply_sparse); the *_typed forms of the calls that read an [n, dim] gradient matrix or grad_out, for float16 / bfloat16
 // gradients (GradHalf in the kernels' pack).  The grouped combined write-back is tfra_apply_many.hip, the two-stream look-ahead driver
 // tfra_prefetch.hip.  A write-back's argument checks exist once (tfra_apply.h); the launch ladders are the dispatchers of
 // tfra_host.h (with_opt_kind, with_stored) and with_nch.
@@ -146,6 +146,7 @@ static GradHalf half_of(const tfra_grads* hg) { return GradHalf{hg->grads, hg->d
 
 // comb != nullptr (tfra_table_apply_planned_combined): grads is grad_out, position e's gradient is formed from comb[e]
 // hg != nullptr (the *_typed calls): the gradient matrix is hg's, float16 or bfloat16; grads is not read
+// both (tfra_table_apply_planned_combined_typed): hg is grad_out, a row of it is up-cast and scaled before comb[e] is applied
 int tfra::apply_planned_impl(tfra_table_t* tp, const tfra_opt_params* p, const tfra_sparse_plan_t* pl, const float* grads,
                               const float* param_default_row, tfra_stream_t stream, unsigned* progress, unsigned progress_val,
                              const CombEnt* comb, const tfra_grads* hg) {
@@ -154,13 +155,14 @@ int tfra::apply_planned_impl(tfra_table_t* tp, const tfra_opt_params* p, const t
   hipStream_t s = (hipStream_t)stream;
   const Check c = check_apply_planned(t, p, pl, hg ? hg->grads : (const void*)grads, param_default_row,
                                       [&] { return Check{t->enter(s)}; }, hg ? 7u : 15u);
-  if (c.code) return report(hg ? "apply_planned_typed: " : "apply_planned: ", c);
+  if (c.code) return report(hg ? (comb ? "apply_planned_combined_typed: " : "apply_planned_typed: ") : "apply_planned: ", c);
   if (!c.active) return TFRA_OK;
   int rc = t->prepare_insert(pl->n, s);
   if (rc) return rc;
   unsigned key_blocks, bin_blocks;
   plan_grids(pl, &key_blocks, &bin_blocks);
-  if (comb) launch_hot_sums(s, pl, grads, bin_blocks, progress, progress_val, CombRows{comb});
+  if (comb && hg) launch_hot_sums(s, pl, nullptr, bin_blocks, progress, progress_val, CombRows{comb}, half_of(hg));
+  else if (comb) launch_hot_sums(s, pl, grads, bin_blocks, progress, progress_val, CombRows{comb});
   else if (hg) launch_hot_sums(s, pl, nullptr, bin_blocks, progress, progress_val, half_of(hg));
   else launch_hot_sums(s, pl, grads, bin_blocks, progress, progress_val);
   uint8_t* bounded_now;
@@ -168,7 +170,8 @@ int tfra::apply_planned_impl(tfra_table_t* tp, const tfra_opt_params* p, const t
   if (rc) return rc;
   const ScoreP sp = score_of(t, bounded_now);
   const OptP o = opt_of(p);
-  if (comb) launch_apply(t, s, pl, p->kind, o, grads, param_default_row, key_blocks, sp, CombRows{comb});
+  if (comb && hg) launch_apply(t, s, pl, p->kind, o, nullptr, param_default_row, key_blocks, sp, CombRows{comb}, half_of(hg));
+  else if (comb) launch_apply(t, s, pl, p->kind, o, grads, param_default_row, key_blocks, sp, CombRows{comb});
   else if (hg) launch_apply(t, s, pl, p->kind, o, nullptr, param_default_row, key_blocks, sp, half_of(hg));
   else launch_apply(t, s, pl, p->kind, o, grads, param_default_row, key_blocks, sp);
   if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "apply_planned: launch failed");
@@ -202,17 +205,18 @@ extern "C" int tfra_table_apply_planned_typed(tfra_table_t* tp, const tfra_opt_p
 // The write-back of an embedding_lookup_sparse: plan over the entry ids, gradient of position e = the combiner's backward
 // (tfra_combine_device.h) formed from grad_out in registers — apply_planned's kernels, reading grad_out through one more
 // indirection instead of an expanded [nnz, dim] gradient.
-extern "C" int tfra_table_apply_planned_combined(tfra_table_t* tp, const tfra_opt_params* p, const tfra_sparse_plan_t* pl,
-                                                 const float* grad_out, const int64_t* seg, const float* weights, int combiner,
-                                                 size_t n_rows, const float* param_default_row, tfra_stream_t stream) {
+// (hg != nullptr: tfra_table_apply_planned_combined_typed on a half grad_out, checked by check_typed; grad_out is not read then)
+static int apply_combined_impl(const char* who, tfra_table_t* tp, const tfra_opt_params* p, const tfra_sparse_plan_t* pl,
+                               const float* grad_out, const tfra_grads* hg, const int64_t* seg, const float* weights, int combiner,
+                               size_t n_rows, const float* param_default_row, tfra_stream_t stream) {
   Table* t = reinterpret_cast<Table*>(tp);
   hipStream_t s = (hipStream_t)stream;
   std::unique_lock<std::mutex> lock;
-  const Check c = check_apply_combined(t, p, pl, grad_out, seg, weights, combiner, n_rows, param_default_row, [&] {
+  const Check c = check_apply_combined(t, p, pl, hg ? hg->grads : (const void*)grad_out, seg, weights, combiner, n_rows, param_default_row, [&] {
     lock = std::unique_lock<std::mutex>(t->mu);
     return Check{t->enter(s)};   // the scratch below was last used on the table's previous stream
-  });
-  if (c.code) return report("apply_planned_combined: ", c);
+  }, hg ? 7u : 15u);
+  if (c.code) return report(who, c);
   if (!c.active) return TFRA_OK;
   const size_t nnz = pl->n;
   tfra_workspace_t* ws;
@@ -226,7 +230,29 @@ extern "C" int tfra_table_apply_planned_combined(tfra_table_t* tp, const tfra_op
   CombEnt* ent = reinterpret_cast<CombEnt*>(b + se_b + den_b);
   rc = comb_entries(s, nnz, seg, weights, combiner, n_rows, reinterpret_cast<int*>(b), reinterpret_cast<float*>(b + se_b), ent);
   if (rc) return rc;
-  return apply_planned_impl(tp, p, pl, grad_out, param_default_row, stream, nullptr, 0, ent);
+  return apply_planned_impl(tp, p, pl, grad_out, param_default_row, stream, nullptr, 0, ent, hg);
+}
+
+extern "C" int tfra_table_apply_planned_combined(tfra_table_t* tp, const tfra_opt_params* p, const tfra_sparse_plan_t* pl,
+                                                 const float* grad_out, const int64_t* seg, const float* weights, int combiner,
+                                                 size_t n_rows, const float* param_default_row, tfra_stream_t stream) {
+  return apply_combined_impl("apply_planned_combined: ", tp, p, pl, grad_out, nullptr, seg, weights, combiner, n_rows, param_default_row,
+                             stream);
+}
+
+// The typed form: grad_out as the dense part left it.  Equals the untyped call on GO32[r] = f32(grad_out[r]) * *d_scale; the kernels
+// form GO32 in registers, in front of comb_grad4 (CombRows and GradHalf in one pack).
+extern "C" int tfra_table_apply_planned_combined_typed(tfra_table_t* tp, const tfra_opt_params* p, const tfra_sparse_plan_t* pl,
+                                                       const tfra_grads* grad_out, const int64_t* seg, const float* weights,
+                                                       int combiner, size_t n_rows, const float* param_default_row,
+                                                       tfra_stream_t stream) {
+  bool forward;
+  if (const Check c = check_typed(grad_out, &forward); c.code) return report("apply_planned_combined_typed: ", c);
+  if (forward)
+    return tfra_table_apply_planned_combined(tp, p, pl, (const float*)grad_out->grads, seg, weights, combiner, n_rows, param_default_row,
+                                             stream);
+  return apply_combined_impl("apply_planned_combined_typed: ", tp, p, pl, nullptr, grad_out, seg, weights, combiner, n_rows,
+                             param_default_row, stream);
 }
 
 // tfra_table_apply_sparse for more ids than a plan holds (2^18).  Equal ids must still meet in ONE update, whatever

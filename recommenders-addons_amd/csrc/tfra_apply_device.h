@@ -78,6 +78,24 @@ __device__ __forceinline__ void grad_half_add(float4& acc, const uint2 (&r)[N], 
   }
 }
 
+// The same over grad_out rows of a combined write-back (CombRows and GradHalf in one pack): granule j becomes a row of
+// GO32 = f32(g) * s, THEN the entry's gradient comb_grad4(GO32 row, den, w) — ((f32(g) * s) / den) * w, each step rounded on its own —
+// and is added where the float COMB arm adds it.  ent(j, den, w) shuffles entry j's denominator and weight: every lane calls it.
+// ONE loop with the format selected per granule (is_bf16 is wave-uniform), not grad_half_add's two loops under a branch: with the
+// combiner's divisions in it the doubled loop cost the update kernels 11 registers, and 18 of them a waves-per-SIMD class.
+template <int N, class Take, class Ent>
+__device__ __forceinline__ void grad_half_add_comb(float4& acc, const uint2 (&r)[N], const GradHalfSrc& gh, Take&& take, Ent&& ent) {
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    float den, w;
+    ent(j, den, w);
+    float4 x = gh.is_bf16 ? load_stored4<TFRA_BF16>(r[j]) : load_stored4<TFRA_F16>(r[j]);
+    x.x *= gh.s; x.y *= gh.s; x.z *= gh.s; x.w *= gh.s;
+    x = comb_grad4(x, den, w);
+    if (take(j)) { acc.x += x.x; acc.y += x.y; acc.z += x.z; acc.w += x.w; }
+  }
+}
+
 // The body is one function with two callers — hot_sums_kernel (one plan per launch) and hot_sums_many_kernel (a list of plans per
 // launch) — so that both compile the same expressions: blk = this block's index among the nblk blocks that work on THIS plan.
 template <int NCH, class... CS>
@@ -88,7 +106,6 @@ __device__ __forceinline__ void hot_sums_body(const float* __restrict__ grads, i
                                               unsigned* progress, unsigned progress_val, unsigned blk, unsigned nblk, const CS... cs) {
   constexpr bool COMB = (false || ... || std::is_same<CS, CombRows>::value);
   constexpr bool GH = HasGradHalf<CS...>::v;
-  static_assert(!(COMB && GH), "the combined write-back takes float grad_out");
   constexpr int NG = NTA / 16;
   const GradHalfSrc gh = grad_half_in(cs...);
   __shared__ float s_sum[NG][64];
@@ -108,7 +125,7 @@ __device__ __forceinline__ void hot_sums_body(const float* __restrict__ grads, i
     const unsigned live = (unsigned)(__ballot(!(e & E_SKIP)) >> gshift) & 0xffffu;   // entries of the item that exist
     if (sub == 0) s_kind[g] = empty ? 2 : (first ? 1 : 0);
     if (threadIdx.x == 0) s_kind[NG] = 1;
-    unsigned rows[16];   // element offset of each row (< 2^18 * 256)
+    unsigned rows[16];   // element offset of each row (< 2^18 * 256; COMB and GH: < 2^32, checked on the host)
     float cden = 0.f, cw = 0.f;   // COMB: denominator and weight of this lane's entry
     if constexpr (COMB) {
       const CombEnt ce = comb_ent(cs...)[((e & E_SKIP) ? e0 : e) & E_POS];   // (padding: the item's first row, as below)
@@ -138,6 +155,10 @@ __device__ __forceinline__ void hot_sums_body(const float* __restrict__ grads, i
 #pragma unroll
           for (int j = 0; j < 8; ++j) r[j] = *reinterpret_cast<const uint2*>(gh.g + rows[h * 8 + j] + cc);
           keep_live(r[0], r[1], r[2], r[3]); keep_live(r[4], r[5], r[6], r[7]);
+          if constexpr (COMB)
+            grad_half_add_comb(acc, r, gh, [&](int j) { return ((live >> (h * 8 + j)) & 1u) != 0; },
+                               [&](int j, float& den, float& w) { den = __shfl(cden, gshift + h * 8 + j); w = __shfl(cw, gshift + h * 8 + j); });
+          else
           grad_half_add(acc, r, gh, [&](int j) { return ((live >> (h * 8 + j)) & 1u) != 0; });
         } else {
         float4 x[8];
@@ -159,6 +180,10 @@ __device__ __forceinline__ void hot_sums_body(const float* __restrict__ grads, i
       for (int j = 0; j < 16; ++j) r[j] = *reinterpret_cast<const uint2*>(gh.g + rows[j] + cc);   // 16 rows in flight
       keep_live(r[0], r[1], r[2], r[3]); keep_live(r[4], r[5], r[6], r[7]);
       keep_live(r[8], r[9], r[10], r[11]); keep_live(r[12], r[13], r[14], r[15]);
+      if constexpr (COMB)
+        grad_half_add_comb(acc, r, gh, [&](int j) { return ((live >> j) & 1u) != 0; },
+                           [&](int j, float& den, float& w) { den = __shfl(cden, gshift + j); w = __shfl(cw, gshift + j); });
+      else
       grad_half_add(acc, r, gh, [&](int j) { return ((live >> j) & 1u) != 0; });
       } else {
       float4 x[16];
@@ -198,6 +223,7 @@ __device__ __forceinline__ void hot_sums_body(const float* __restrict__ grads, i
 // COMB (combined write-back): lanes 4.. of a key with few occurrences hold grad_out rows instead of batch positions, and the
 // denominator / weight of their entry in cden / cw; each gradient row is scaled by comb_grad4 before it is added.
 // GH (half gradients): the `grads` arm loads 8-byte granules from gh and forms G32 from them; the `partial` arm is the float one.
+// COMB and GH (the typed combined write-back): the granule is a grad_out row's; it is up-cast and scaled, then goes through comb_grad4.
 // Hot keys come first in the key list, so but for one wave the branch is wave-uniform; each arm has its NB loads in flight.
 template <int NB, bool COMB = false, bool GH = false>
 __device__ __forceinline__ void add_rows(float4& acc, const float* __restrict__ grads, const float* __restrict__ partial, bool hot,
@@ -225,6 +251,12 @@ __device__ __forceinline__ void add_rows(float4& acc, const float* __restrict__ 
         r[j] = *reinterpret_cast<const uint2*>(gh.g + (position * (unsigned)dim + (unsigned)c));
       }
       if (NB == 4) keep_live(r[0], r[1], r[2], r[3]);
+      if constexpr (COMB)   // (position = the entry's grad_out row; element offsets below 2^32: the typed call refuses n_rows * dim beyond)
+        grad_half_add_comb(acc, r, gh, [&](int j) { return j0 + (unsigned)j < nsrc; }, [&](int j, float& den, float& w) {
+          const int src = gshift + 4 + (int)min(min(j0 + (unsigned)j, nsrc - 1), 7u);
+          den = __shfl(cden, src); w = __shfl(cw, src);
+        });
+      else
       grad_half_add(acc, r, gh, [&](int j) { return j0 + (unsigned)j < nsrc; });
     }
     return;
@@ -301,7 +333,6 @@ __device__ __forceinline__ void apply_csr_body(const TableView& v, OptP o, int d
   constexpr bool STOCH = HasStoch<CS...>::v;
   constexpr bool GH = HasGradHalf<CS...>::v;
   static_assert(!STOCH || ST != TFRA_F32, "stochastic rounding is of half rows");
-  static_assert(!(COMB && GH), "the combined write-back takes float grad_out");
   const GradHalfSrc gh = grad_half_in(cs...);
   if (PHASE2 && *any_deferred != use_gen) return;   // phase 1 of this use deferred nothing
   constexpr int S = NSlots<KIND>::v;
@@ -479,6 +510,13 @@ struct ApplyManyRec {
   int dim;
   float aux0, aux1;
   unsigned use_gen;
+};
+// tfra_multi_apply_planned_combined_typed: what a descriptor with a float16 / bfloat16 grad_out adds to its ApplyManyRec, in an array
+// beside the records (same index) that only the half classes' kernels read; `grads` of the record holds the half matrix's address then.
+// (A record of its own: ApplyManyRec keeps its size, the float classes' kernels the code they had.)
+struct GradHalfRec {
+  const float* d_scale;
+  int is_bf16;
 };
 
 }  // namespace

@@ -199,6 +199,16 @@ class ApplyCombinedDesc(ctypes.Structure):
   ]
 
 
+class ApplyCombinedTypedDesc(ctypes.Structure):
+  """tfra_apply_combined_typed_desc (include/tfra_mi355x.h): ApplyCombinedDesc with grad_out as a tfra_grads, for
+  tfra_multi_apply_planned_combined_typed."""
+  _fields_ = [
+      ("struct_size", ctypes.c_uint32), ("combiner", ctypes.c_int32), ("table", ctypes.c_void_p), ("opt", ctypes.c_void_p),
+      ("plan", ctypes.c_void_p), ("grad_out", Grads), ("seg", ctypes.c_void_p), ("weights", ctypes.c_void_p),
+      ("n_rows", ctypes.c_size_t), ("param_default_row", ctypes.c_void_p),
+  ]
+
+
 class PlanBuildDesc(ctypes.Structure):
   """tfra_plan_build_desc (include/tfra_mi355x.h): one plan's build in tfra_multi_sparse_plan_build."""
   _fields_ = [
@@ -293,6 +303,7 @@ _SIGS = {
     "tfra_sparse_plan_build": [_P, _SZ, _P, _I, _P],
     "tfra_table_apply_planned": [_P, ctypes.POINTER(OptParams), _P, _P, _P, _P],
     "tfra_table_apply_planned_combined": [_P, ctypes.POINTER(OptParams), _P, _P, _P, _P, _I, _SZ, _P, _P],
+    "tfra_table_apply_planned_combined_typed": [_P, ctypes.POINTER(OptParams), _P, ctypes.POINTER(Grads), _P, _P, _I, _SZ, _P, _P],
     "tfra_table_step_prefetch": [_P, ctypes.POINTER(OptParams), _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P],
     "tfra_table_step_prefetch_assign": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _P],
     "tfra_step_driver_create": [_P, ctypes.POINTER(_P)],
@@ -330,6 +341,7 @@ _SIGS = {
     "tfra_table_find_combine_ragged_backprop_weights": [_P, _SZ, _P, _SZ, _P, _P, _I, ctypes.c_uint32, ctypes.c_int64, _P, _P, _P,
                                                         _P],
     "tfra_multi_apply_planned_combined": [_P, _SZ, _P, _P, _P],
+    "tfra_multi_apply_planned_combined_typed": [_P, _SZ, _P, _P, _P],
     "tfra_multi_sparse_plan_build": [_P, _SZ, _P, _P, _P],
     "tfra_segment_sum": [_P, _SZ, _I, _P, _P, _P, _SZ, _P, _P],
     "tfra_gather_rows": [_SZ, _SZ, _P, _P, _P, _P],

@@ -36,19 +36,20 @@ def _ptr(t):
   return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
-def _grads_arg(grads, device, dim, grad_scale=None):
+def _grads_arg(grads, device, dim, grad_scale=None, max_elements=None):
   """A gradient matrix as a write-back takes it: (tfra_grads, tensor) when it goes down as it is — a contiguous float16 / bfloat16
   matrix on `device`, inside the typed calls' limits (dim % 4 == 0, 8-byte aligned), with `grad_scale` (a one-element float32
   device tensor, e.g. a GradScaler's inverse scale) read by the kernels — else (None, tensor) with the float32 up-cast, times
   grad_scale where there is one: by the typed calls' definition the same bits.  The tensor is what the call reads: keep it
-  alive across the call.  No host read either way."""
+  alive across the call.  No host read either way.  max_elements: a matrix of that many elements or more does not go down as it is (the
+  combined typed calls address grad_out with 32-bit element offsets)."""
   if grad_scale is not None:
     grad_scale = torch.as_tensor(grad_scale)
     if grad_scale.numel() != 1:
       raise ValueError("grad_scale must hold one element, got shape %s" % list(grad_scale.shape))
   scale_down = grad_scale is None or (grad_scale.dtype == torch.float32 and grad_scale.device == device)
   if (grads.dtype in (torch.float16, torch.bfloat16) and grads.device == device and grads.is_contiguous() and grads.numel() and
-      dim % 4 == 0 and grads.data_ptr() % 8 == 0 and scale_down):
+      dim % 4 == 0 and grads.data_ptr() % 8 == 0 and scale_down and (max_elements is None or grads.numel() < max_elements)):
     return _capi.Grads(grads.data_ptr(), _TORCH2DT[grads.dtype], 0, None if grad_scale is None else grad_scale.data_ptr()), grads
   g = grads.to(device, torch.float32)
   if grad_scale is not None:

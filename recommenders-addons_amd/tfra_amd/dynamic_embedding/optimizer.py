@@ -302,12 +302,15 @@ class DynamicEmbeddingOptimizer:
         if plan is not None:
           _release_plan(tw.params, plan)
 
-  def apply_combined_gradients(self, grads_and_vars, name=None):
+  def apply_combined_gradients(self, grads_and_vars, name=None, grad_scale=None):
     """grads_and_vars: iterable of (grad_out, SparseTrainableWrapper) — grad_out is the gradient of the RESULT of
     embedding_lookup_sparse / safe_embedding_lookup_sparse (its shape, leading dims included); one global step for all
     pairs.  One shard, float32 / float16 / bfloat16 rows, a fused rule and a plannable batch: the write-back forms every entry's gradient from
     grad_out inside its kernels (tfra_table_apply_planned_combined, with the plan built at lookup time when there is one);
-    otherwise the entry gradients are written out (device_ops.sparse_segment_combine_backprop) and go through apply_sparse."""
+    otherwise the entry gradients are written out (device_ops.sparse_segment_combine_backprop) and go through apply_sparse.
+    A float16 / bfloat16 grad_out and grad_scale (a one-element float32 device tensor, as in apply_sparse) go down as they are on
+    the fused route (tfra_table_apply_planned_combined_typed); every other route reads their float32 up-cast times the scale,
+    by the typed call's definition the same bits.  No host read either way."""
     pairs = []
     for grad_out, tw in grads_and_vars:
       if not isinstance(tw, SparseTrainableWrapper):
@@ -316,7 +319,7 @@ class DynamicEmbeddingOptimizer:
       if tw.max_norm is not None:
         raise ValueError("apply_combined_gradients: lookups with max_norm are not supported (the gradient through the clip "
                          "by norm is not implemented)")
-      pairs.append((tw.check_grad_out(grad_out), tw))
+      pairs.append((tw.check_grad_out(grad_out, keep_half=True), tw))
     p = self.begin_step()
     for g, tw in pairs:
       var = tw.params
@@ -327,7 +330,7 @@ class DynamicEmbeddingOptimizer:
       if not fused:
         if plan is not None:
           _release_plan(var, plan)
-        eg = device_ops.sparse_segment_combine_backprop(g, tw.seg, tw.weights, tw.combiner)
+        eg = device_ops.sparse_segment_combine_backprop(self._upcast(g, var.dim, grad_scale).contiguous(), tw.seg, tw.weights, tw.combiner)
         self.apply_sparse(var, tw.entry_ids, eg, p)
         continue
       pooled = True
@@ -341,12 +344,12 @@ class DynamicEmbeddingOptimizer:
           var.restrict_policy.apply_update(tw.entry_ids)
         t = var._tables[0]
         t._table.apply_planned_combined(p, plan, g, tw.seg, tw.weights, device_ops.COMBINERS[tw.combiner],
-                                        t._default_value.to(torch.float32))
+                                        t._default_value.to(torch.float32), grad_scale=grad_scale)
       finally:
         if pooled:
           _release_plan(var, plan)
 
-  def apply_combined_gradients_many(self, grads_and_vars, name=None):
+  def apply_combined_gradients_many(self, grads_and_vars, name=None, grad_scale=None):
     """`apply_combined_gradients` for a many-table model — the wrappers `embedding_lookup_sparse_many(..., return_trainable=True)`
     returns: one global step for all pairs, and every pair that takes the fused write-back there (one shard, float32 / float16 /
     bfloat16 rows, a fused rule, a plannable batch) joins the group of its device, which is written back by ONE C call
@@ -355,7 +358,8 @@ class DynamicEmbeddingOptimizer:
     (`table_ops.build_plans_many`: tfra_multi_sparse_plan_build); one such pair keeps the single build.
     Every other pair takes `apply_combined_gradients`' path for it.  A variable that occurs a second time closes the current
     groups first, so the order of the write-backs of one variable is the list's.  Tables and slots end bit-identical to
-    `apply_combined_gradients` over the same list."""
+    `apply_combined_gradients` over the same list.  Half gradients and grad_scale as there: a group with a half member is ONE
+    tfra_multi_apply_planned_combined_typed call."""
     pairs = []
     for grad_out, tw in grads_and_vars:
       if not isinstance(tw, SparseTrainableWrapper):
@@ -364,7 +368,7 @@ class DynamicEmbeddingOptimizer:
       if tw.max_norm is not None:
         raise ValueError("apply_combined_gradients_many: lookups with max_norm are not supported (the gradient through the clip "
                          "by norm is not implemented)")
-      pairs.append((tw.check_grad_out(grad_out), tw))
+      pairs.append((tw.check_grad_out(grad_out, keep_half=True), tw))
     p = self.begin_step()
     groups, seen = {}, set()   # device -> [(var, plan, pooled, request)]; the variables written since the last flush
     unbuilt = {}               # device -> [(plan, entry ids)]: the group's pairs that arrived without a plan
@@ -384,7 +388,7 @@ class DynamicEmbeddingOptimizer:
             todo[0][0].build(todo[0][1])
           elif todo:   # one grouped build in front of the grouped write-back, on the same stream
             build_plans_many([b[0] for b in todo], [b[1] for b in todo])
-          apply_planned_combined_many([m[3] for m in members], p)
+          apply_planned_combined_many([m[3] for m in members], p, grad_scale=grad_scale)
         finally:
           release(members)
 
@@ -401,7 +405,8 @@ class DynamicEmbeddingOptimizer:
         if not fused:
           if plan is not None:
             _release_plan(var, plan)
-          eg = device_ops.sparse_segment_combine_backprop(g, tw.seg, tw.weights, tw.combiner)
+          eg = device_ops.sparse_segment_combine_backprop(self._upcast(g, var.dim, grad_scale).contiguous(), tw.seg, tw.weights,
+                                                          tw.combiner)
           self.apply_sparse(var, tw.entry_ids, eg, p)
           continue
         pooled = True

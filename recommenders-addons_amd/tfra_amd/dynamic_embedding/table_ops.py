@@ -646,12 +646,14 @@ class _DeviceTable:
     _over_plans((plan,), self._device, sync, _capi.call, "tfra_table_apply_planned", self._h, ctypes.byref(params), plan._h,
                 _ptr(grads), _ptr(d), _stream(self._device))
 
-  def _apply_combined_args(self, plan, grad_out, seg, weights, default_row):
-    """A combined write-back's grad_out, seg, weights (or None) and default row, checked and as the C calls take them."""
+  def _apply_combined_args(self, plan, grad_out, seg, weights, default_row, grad_scale=None):
+    """A combined write-back's grad_out, seg, weights (or None) and default row, checked and as the C calls take them.  grad_out
+    comes back as `_grads_arg` gives it: (tfra_grads, tensor) for a contiguous half matrix inside the typed calls' limits (8-byte
+    aligned, n_rows * dim < 2^32), else (None, the float32 up-cast times grad_scale)."""
     _check_plan(plan, self._dim, self._device)
-    grad_out = grad_out.to(self._device, torch.float32).contiguous()
     if grad_out.dim() != 2 or grad_out.shape[1] != self._dim:
       raise ValueError("Expected grad_out of shape [n_rows, %d], got %s" % (self._dim, list(grad_out.shape)))
+    grad_out = _grads_arg(grad_out, self._device, self._dim, grad_scale, max_elements=1 << 32)
     seg = seg.to(self._device, torch.int64).contiguous()
     if seg.numel() != plan.n or (weights is not None and weights.numel() != plan.n):
       raise ValueError("seg / weights need one element per plan entry (%d)" % plan.n)
@@ -659,11 +661,17 @@ class _DeviceTable:
     d = default_row.to(self._device, torch.float32).contiguous()
     return grad_out, seg, w, d
 
-  def apply_planned_combined(self, params, plan, grad_out, seg, weights, combiner, default_row, sync=True):
+  def apply_planned_combined(self, params, plan, grad_out, seg, weights, combiner, default_row, sync=True, grad_scale=None):
     """apply_planned for an embedding_lookup_sparse (tfra_table_apply_planned_combined): `plan` built over the entry ids,
     grad_out [n_rows, dim] the gradient of the combined result, seg [nnz] its row ids (ascending), weights [nnz] or None,
-    combiner 0 sum / 1 mean / 2 sqrtn.  Entry e's gradient is formed from grad_out inside the write-back kernels."""
-    grad_out, seg, w, d = self._apply_combined_args(plan, grad_out, seg, weights, default_row)
+    combiner 0 sum / 1 mean / 2 sqrtn.  Entry e's gradient is formed from grad_out inside the write-back kernels.  A contiguous
+    float16 / bfloat16 grad_out goes down as it is, grad_scale (as in apply_sparse) with it (tfra_table_apply_planned_combined_typed:
+    the same bits as the float32 up-cast times the scale gives)."""
+    (typed, grad_out), seg, w, d = self._apply_combined_args(plan, grad_out, seg, weights, default_row, grad_scale)
+    if typed is not None:
+      _over_plans((plan,), self._device, sync, _capi.call, "tfra_table_apply_planned_combined_typed", self._h, ctypes.byref(params),
+                  plan._h, ctypes.byref(typed), _ptr(seg), _ptr(w), int(combiner), grad_out.shape[0], _ptr(d), _stream(self._device))
+      return
     _over_plans((plan,), self._device, sync, _capi.call, "tfra_table_apply_planned_combined", self._h, ctypes.byref(params), plan._h,
                 _ptr(grad_out), _ptr(seg), _ptr(w), int(combiner), grad_out.shape[0], _ptr(d), _stream(self._device))
 
@@ -1684,8 +1692,11 @@ def find_combine_ragged_weight_grad_many(requests, return_launches=False):
   return (dws, launches) if return_launches else dws
 
 
-def apply_planned_combined_many(requests, p_list, sync=True):
+def apply_planned_combined_many(requests, p_list, sync=True, grad_scale=None):
   """The combined write-backs of a list of tables in ONE C call (tfra_multi_apply_planned_combined; the frame: `_grouped_call`).
+  grad_scale: one scale for all requests, or a list with one (or None) per request, as in `apply_planned_combined`.  When a
+  request's grad_out goes down as a half matrix, the call is tfra_multi_apply_planned_combined_typed (float32 members ride along as
+  float32 descriptors); otherwise it is the untyped call, as always.
   `requests`: a list of (table, plan, grad_out, seg, weights, combiner, default_row), the arguments behind `table` those of
   `_DeviceTable.apply_planned_combined`, handled the same way.  `p_list`: the optimizer parameters (`_capi.OptParams`) of each
   request, or one for all.  Each table and each plan occurs once.  Every table ends bit-identical to `apply_planned_combined` of
@@ -1697,20 +1708,32 @@ def apply_planned_combined_many(requests, p_list, sync=True):
     p_list = [p_list] * n
   if len(p_list) != n:
     raise ValueError("apply_planned_combined_many: %d requests but %d optimizer parameter sets" % (n, len(p_list)))
+  scales = list(grad_scale) if isinstance(grad_scale, (list, tuple)) else [grad_scale] * n
+  if len(scales) != n:
+    raise ValueError("apply_planned_combined_many: %d requests but %d gradient scales" % (n, len(scales)))
+  # the arguments first: which call it is depends on how the gradients go down
+  args = []
+  for (table, plan, grad_out, seg, weights, combiner, default_row), scale in zip(requests, scales):
+    args.append(_device_table(table)._apply_combined_args(plan, grad_out, seg, weights, default_row, scale))
+  any_typed = any(a[0][0] is not None for a in args)
 
   def fill(e, i):
-    table, plan, grad_out, seg, weights, combiner, default_row = requests[i]
-    table = _device_table(table)
-    grad_out, seg, w, d = table._apply_combined_args(plan, grad_out, seg, weights, default_row)
+    table, plan, combiner = _device_table(requests[i][0]), requests[i][1], requests[i][5]
+    (typed, grad_out), seg, w, d = args[i]
     e.combiner, e.table = int(combiner), table._h.value
     e.opt, e.plan = ctypes.addressof(p_list[i]), plan._h.value
-    e.grad_out, e.seg, e.weights = grad_out.data_ptr(), seg.data_ptr(), (w.data_ptr() if w is not None else None)
+    if any_typed:
+      e.grad_out = typed if typed is not None else _capi.Grads(grad_out.data_ptr(), _capi.TFRA_F32, 0, None)
+    else:
+      e.grad_out = grad_out.data_ptr()
+    e.seg, e.weights = seg.data_ptr(), (w.data_ptr() if w is not None else None)
     e.n_rows, e.param_default_row = grad_out.shape[0], d.data_ptr()
     return grad_out, seg, w, d, p_list[i]
 
+  c_name, desc_type = (("tfra_multi_apply_planned_combined_typed", _capi.ApplyCombinedTypedDesc) if any_typed else
+                       ("tfra_multi_apply_planned_combined", _capi.ApplyCombinedDesc))
   return _over_plans([req[1] for req in requests], _device_table(requests[0][0])._device, sync, _grouped_call,
-                     "tfra_multi_apply_planned_combined", _capi.ApplyCombinedDesc, "apply_planned_combined_many",
-                     [r[0] for r in requests], fill)
+                     c_name, desc_type, "apply_planned_combined_many", [r[0] for r in requests], fill)
 
 
 def build_plans_many(plans, ids_list, return_launches=False):

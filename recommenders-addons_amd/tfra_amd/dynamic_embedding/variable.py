@@ -958,12 +958,15 @@ class SparseTrainableWrapper(TrainableWrapper):
       pass
     super().__del__()
 
-  def check_grad_out(self, grad_out):
-    """grad_out as [n_rows, dim] float32; ValueError unless it has the shape of the lookup's result."""
+  def check_grad_out(self, grad_out, keep_half=False):
+    """grad_out as [n_rows, dim] float32; ValueError unless it has the shape of the lookup's result.  keep_half: a float16 /
+    bfloat16 gradient keeps its dtype (for the typed combined write-back): the same check, reshaped, and no copy in another dtype."""
     grad_out = torch.as_tensor(grad_out, device=self.params._primary)
     if tuple(grad_out.shape) != self.out_shape:
       raise ValueError("the gradient of a sparse lookup must have the shape of its result %s, got %s" %
                        (list(self.out_shape), list(grad_out.shape)))
+    if keep_half and grad_out.dtype in (torch.float16, torch.bfloat16):
+      return grad_out.reshape(self.n_rows, self.params.dim)
     return grad_out.reshape(self.n_rows, self.params.dim).to(torch.float32).contiguous()
 
   def grad_of(self, grad_out):
