@@ -1590,6 +1590,74 @@ int tfra_assign_route_stats(const tfra_assign_route_t* r, uint64_t* out6);
 int tfra_assign_route_time_kernels(tfra_assign_route_t* r, size_t steps);
 int tfra_assign_route_kernel_times(tfra_assign_route_t* r, double* step_kernel_us, size_t* steps);
 
+/* -- Half-precision OUTPUTS of the lookups: the forward counterpart of tfra_grads.  A bfloat16 / float16 model over
+ *    a float32 master table gets its activations in its own type from the lookup's kernel, and a half table feeding a float32 model
+ *    gets float32, with no conversion pass behind the call.  Additive; ABI version 1.
+ *    Contract: a typed call equals its untyped twin (tfra_table_find / tfra_table_find_n, tfra_table_find_combine,
+ *    tfra_table_find_combine_ragged, tfra_multi_find_combine, tfra_multi_find_combine_ragged) followed by the elementwise
+ *    conversion of the twin's output to `dtype`, bit for bit.
+ *      f32() of a half value is the exact up-cast: subnormals are kept, a NaN stays a NaN.
+ *      float32 -> float16 / bfloat16 is round to nearest even: ties go to even, the result is infinity beyond the largest finite
+ *      value, results in the subnormal range are kept, a NaN stays a NaN.  bfloat16 is the library's f32_to_bf16 (a NaN keeps its
+ *      upper 16 bits and gets bit 6 set); float16 is the hardware conversion (the _Float16 cast).
+ *      A half table read out in the OTHER half type goes through float32: exact up-cast, then the rounding above.
+ *      defaults / default_row stay in the TABLE's value dtype, as in the twins, and are converted the same way.
+ *    Everything in front of the conversion is the twin's: the probe (plain loads, reserved keys), exists, the clamping of
+ *    row_splits, PRUNE / FILL (the fill row is converted as it is: a -0.0 survives), entries in no row, zero rows, the accumulation
+ *    order, float32 accumulators, nnz == 0, and the launches: a typed call enqueues what its twin enqueues.
+ *    tfra_table_find_typed with dtype == the table's value dtype forwards to tfra_table_find / tfra_table_find_n, and a pooled call
+ *    with dtype == TFRA_F32 forwards to its twin: the same code, the same launches.
+ *    Limits: the pooled calls keep their twins' (float32 / float16 / bfloat16 tables, dim % 4 == 0, dim <= 256).  tfra_table_find_typed
+ *    takes on the same limits (its conversion works on 4-element granules) and serves field 0 only; d_n may be NULL (the count is n).
+ *    A half output is addressed with the twin's size_t row offsets: no new size limit.
+ *    Refused before anything is enqueued (tfra_last_error() names the function and, in the grouped calls, the descriptor's index;
+ *    nothing is written to any output):
+ *      TFRA_ERR_INVALID      a NULL record, or NULL rows with rows to write; reserved != 0; a dtype other than the three; a wrong
+ *                            struct_size
+ *      TFRA_ERR_UNSUPPORTED  rows misaligned (float32: 16 bytes, halves: 8 bytes); the dim / value dtype limits
+ *      and everything the twin checks, with the twin's codes and wording (a find's defaults must be aligned as its rows are read:
+ *      float32 tables 16 bytes, half tables 8).
+ *    Not typed: the tier calls (tfra_tier_*), tfra_table_find_field, tfra_table_find_unique, the find_or_insert family, the step
+ *    drivers and the routes: they write the table's value dtype (the pooled ones float32). */
+typedef struct {
+  void*   rows;      /* [n, dim] row-major in `dtype`; float32: 16-byte aligned, halves: 8-byte aligned */
+  int32_t dtype;     /* TFRA_F32 | TFRA_F16 | TFRA_BF16 */
+  int32_t reserved;  /* must be 0 */
+} tfra_rows_out;     /* 16 bytes */
+int tfra_table_find_typed(tfra_table_t* t, size_t n, const int64_t* d_n /* may be NULL */, const int64_t* keys,
+                          const tfra_rows_out* out, uint8_t* exists, const void* defaults, int default_is_full,
+                          tfra_stream_t stream);
+int tfra_table_find_combine_typed(tfra_table_t* t, tfra_workspace_t* ws, size_t nnz, const int64_t* ids, const int64_t* seg,
+                                  const float* weights, int combiner, size_t n_rows, const void* default_row,
+                                  const tfra_rows_out* out, tfra_stream_t stream);
+int tfra_table_find_combine_ragged_typed(tfra_table_t* t, size_t n_rows, const int64_t* row_splits, size_t nnz,
+                                         const int64_t* ids, const float* weights, int combiner, uint32_t flags,
+                                         int64_t fill_id, const void* default_row, const tfra_rows_out* out,
+                                         tfra_stream_t stream);
+/* The grouped forms: tfra_multi_find_combine / tfra_multi_find_combine_ragged over plain tables, each descriptor with an output
+ * record of its own.  The output type is one more launch-class axis — (value dtype, NCH, out dtype[, safe or not]) — so a list
+ * with ONE output type keeps the twin's launch count. */
+typedef struct {
+  uint32_t struct_size;      /* = sizeof(tfra_find_combine_typed_desc) */
+  int32_t  combiner;         /* 0 sum | 1 mean | 2 sqrtn */
+  tfra_table_t* table;
+  size_t nnz; const int64_t* ids; const int64_t* seg; const float* weights;   /* weights may be NULL */
+  size_t n_rows; const void* default_row; tfra_rows_out out;                  /* out.rows [n_rows, table dim] in out.dtype */
+} tfra_find_combine_typed_desc;
+int tfra_multi_find_combine_typed(tfra_workspace_t* ws, size_t n_tables, const tfra_find_combine_typed_desc* descs,
+                                  uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
+typedef struct {
+  uint32_t struct_size;      /* = sizeof(tfra_find_combine_ragged_typed_desc) */
+  int32_t  combiner;         /* 0 sum | 1 mean | 2 sqrtn */
+  tfra_table_t* table;
+  size_t n_rows; const int64_t* row_splits;                                   /* [n_rows + 1] */
+  size_t nnz; const int64_t* ids; const float* weights;                       /* weights may be NULL */
+  uint32_t flags; uint32_t reserved;                                          /* TFRA_RAGGED_*; reserved = 0 */
+  int64_t fill_id; const void* default_row; tfra_rows_out out;                /* out.rows [n_rows, table dim] in out.dtype */
+} tfra_find_combine_ragged_typed_desc;
+int tfra_multi_find_combine_ragged_typed(tfra_workspace_t* ws, size_t n_tables, const tfra_find_combine_ragged_typed_desc* descs,
+                                         uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,29 @@ template <> struct PoolRow<TFRA_BF16> {
   }
 };
 
+// four float32 as an output row's elements (the typed lookups): themselves, or rounded to nearest even to a half
+// type and packed into 8 B — float16 by the _Float16 cast add2_f16 uses, bfloat16 by f32_to_bf16 (tfra_device.h)
+template <int OT> struct PoolOut;
+template <> struct PoolOut<TFRA_F32> {
+  typedef float Elem;
+  typedef float4 Vec;
+  static __device__ __forceinline__ float4 narrow(float4 x) { return x; }
+};
+template <> struct PoolOut<TFRA_F16> {
+  typedef unsigned short Elem;
+  typedef uint2 Vec;
+  static __device__ __forceinline__ unsigned h(float f) { return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)f); }
+  static __device__ __forceinline__ uint2 narrow(float4 x) { return make_uint2(h(x.x) | (h(x.y) << 16), h(x.z) | (h(x.w) << 16)); }
+};
+template <> struct PoolOut<TFRA_BF16> {
+  typedef unsigned short Elem;
+  typedef uint2 Vec;
+  static __device__ __forceinline__ uint2 narrow(float4 x) {
+    return make_uint2((unsigned)f32_to_bf16(x.x) | ((unsigned)f32_to_bf16(x.y) << 16),
+                      (unsigned)f32_to_bf16(x.z) | ((unsigned)f32_to_bf16(x.w) << 16));
+  }
+};
+
 // NCH by the row width: 1 (dim <= 64), 2 (<= 128) or 4 column chunks; f(std::integral_constant<int, NCH>{}) for the index
 int nch_index(int dim) { return dim <= 64 ? 0 : dim <= 128 ? 1 : 2; }
 template <class F>
@@ -106,6 +129,19 @@ Check check_dw_out(size_t nnz, const float* dw_out) {
   if ((uintptr_t)dw_out & 3) return refuse(TFRA_ERR_UNSUPPORTED, "misaligned dw_out (4 bytes)");
   return Check{};
 }
+// what only a typed lookup can get wrong (tfra_rows_out), in front of its twin's checks.  NULL rows are left to the twin ("null
+// out", behind its n_rows == 0): out_for_twin() is what the twin's checks look at in the place of its float* out — a half matrix
+// needs 8 bytes where the twin asks 16, and that has been decided here.
+Check check_rows_out(const tfra_rows_out* o) {
+  if (!o) return refuse(TFRA_ERR_INVALID, "null out record");
+  if (o->reserved) return refuse(TFRA_ERR_INVALID, "out.reserved must be 0");
+  if (o->dtype != TFRA_F32 && o->dtype != TFRA_F16 && o->dtype != TFRA_BF16)
+    return refuse(TFRA_ERR_INVALID, "out.dtype must be TFRA_F32, TFRA_F16 or TFRA_BF16");
+  if ((uintptr_t)o->rows & (o->dtype == TFRA_F32 ? 15 : 7))
+    return refuse(TFRA_ERR_UNSUPPORTED, "misaligned out.rows (float32: 16 bytes, halves: 8 bytes)");
+  return Check{};
+}
+const float* out_for_twin(const tfra_rows_out& o) { return reinterpret_cast<const float*>((uintptr_t)o.rows & ~(uintptr_t)15); }
 // whether the flags change anything: the SAFE kernels run only then
 bool ragged_safe(uint32_t flags, const float* weights) { return (flags & TFRA_RAGGED_FILL) || ((flags & TFRA_RAGGED_PRUNE) && weights); }
 // launch(DT, U, NCH, SAFE): with_pool_class with the ragged forms' fourth axis

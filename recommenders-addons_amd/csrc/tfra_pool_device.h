@@ -38,20 +38,26 @@ namespace {
 //           probe's word is uniform in the group, so the branch is — and all U of them at once; only the entries that missed v
 //           are probed there.  The fill id goes the same way.  Both probes are probe_find_word: reserved keys take its own path
 //           in each view.
-// Without RAGGED and SAFE the function is the one it was: `rg` is not read.  Without TIER `lo` is not read.
+//   OT      the type of the output row (the typed lookups): float32, or a half type — `out` then points to 2-byte
+//           elements, and the function's two stores (the FILL row, the finished accumulator) narrow their float4 to 8 B first
+//           (PoolOut<OT>::narrow: round to nearest even).  Nothing in front of the two stores knows OT.
+// Without RAGGED and SAFE the function is the one it was: `rg` is not read.  Without TIER `lo` is not read.  With OT float32 the
+// stores are the float4 stores they were, chunk by chunk.
 struct RaggedArgs {
   const i64* row_splits;
   int nnz;
   unsigned flags;
   i64 fill_id;
 };
-template <int DT, int U, int NCH, bool RAGGED = false, bool SAFE = false, bool TIER = false>
+template <int DT, int U, int NCH, bool RAGGED = false, bool SAFE = false, bool TIER = false, int OT = TFRA_F32>
 __device__ __forceinline__ void find_combine_row(const TableView& v, size_t n_rows, int dim, const i64* __restrict__ ids,
                                                  const float* __restrict__ w, const int* __restrict__ start_end, int combiner,
                                                  const unsigned char* __restrict__ default_row, float* __restrict__ out, size_t r,
                                                  const RaggedArgs& rg = RaggedArgs{}, const TableView* lo = nullptr) {
   static_assert(U == 4, "keep_live is written for U == 4");
   typedef typename PoolRow<DT>::Raw Raw;
+  typedef typename PoolOut<OT>::Elem OutElem;
+  typedef typename PoolOut<OT>::Vec OutVec;
   constexpr unsigned EB = DT == TFRA_F32 ? 4u : 2u;   // bytes per element
   const int lane = threadIdx.x & 63, sub = lane & 15, gshift = lane & 48;
   if (r >= n_rows) return;
@@ -172,7 +178,7 @@ __device__ __forceinline__ void find_combine_row(const TableView& v, size_t n_ro
       }
     }
   }
-  float* o = out + r * (size_t)dim;
+  OutElem* o = reinterpret_cast<OutElem*>(out) + r * (size_t)dim;
   if constexpr (SAFE) {
     if ((rg.flags & TFRA_RAGGED_FILL) && !any) {   // (uniform in the group: every lane saw the same members)
       u64 h;
@@ -190,13 +196,25 @@ __device__ __forceinline__ void find_combine_row(const TableView& v, size_t n_ro
       }
 #pragma unroll
       for (int c = 0; c < NCH; ++c)
-        if (cok[c]) *reinterpret_cast<float4*>(o + c * 64 + sub * 4) = PoolRow<DT>::widen(*reinterpret_cast<const Raw*>(src + coff[c]));
+        if (cok[c])
+          *reinterpret_cast<OutVec*>(o + c * 64 + sub * 4) = PoolOut<OT>::narrow(PoolRow<DT>::widen(*reinterpret_cast<const Raw*>(src + coff[c])));
       return;
     }
   }
+  if constexpr (OT == TFRA_F32) {
 #pragma unroll
-  for (int c = 0; c < NCH; ++c)
-    if (cok[c]) *reinterpret_cast<float4*>(o + c * 64 + sub * 4) = comb_finish4(acc[c], wsum, scale, combiner);
+    for (int c = 0; c < NCH; ++c)
+      if (cok[c]) *reinterpret_cast<float4*>(o + c * 64 + sub * 4) = comb_finish4(acc[c], wsum, scale, combiner);
+  } else {
+    // every chunk finished and packed before the first store: narrowing chunk by chunk between the stores took the safe ragged
+    // NCH = 2 kernels from the twins' 79 VGPRs to 81, 6 to 5 waves per SIMD (profiles/typed_lookup_isa_stats.txt)
+    OutVec fin[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) fin[c] = PoolOut<OT>::narrow(comb_finish4(acc[c], wsum, scale, combiner));
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+      if (cok[c]) *reinterpret_cast<OutVec*>(o + c * 64 + sub * 4) = fin[c];
+  }
 }
 
 }  // namespace

@@ -66,6 +66,11 @@ struct TierRaggedRec {
 TFRA_HIDDEN void launch_find_combine_many(hipStream_t s, int cls, unsigned grid, const ManyRec* recs, const unsigned* prefix, unsigned n);
 TFRA_HIDDEN void launch_find_combine_ragged_many(hipStream_t s, int cls, bool safe, unsigned grid, const RaggedRec* recs,
                                                  const unsigned* prefix, unsigned n);
+// the typed lookups' kernels (tfra_pool_typed.hip): cls = (output type index - 1) * 9 + the class above — float16, then bfloat16 rows
+TFRA_HIDDEN void launch_find_combine_many_typed(hipStream_t s, int cls, unsigned grid, const ManyRec* recs, const unsigned* prefix,
+                                                unsigned n);
+TFRA_HIDDEN void launch_find_combine_ragged_many_typed(hipStream_t s, int cls, bool safe, unsigned grid, const RaggedRec* recs,
+                                                       const unsigned* prefix, unsigned n);
 TFRA_HIDDEN void launch_tier_find_combine_many(hipStream_t s, int cls, unsigned grid, const TierManyRec* recs, const unsigned* prefix,
                                                unsigned n);
 TFRA_HIDDEN void launch_tier_find_combine_ragged_many(hipStream_t s, int cls, bool safe, unsigned grid, const TierRaggedRec* recs,
@@ -92,6 +97,7 @@ struct PoolDesc {
   float* out;                // the lookups
   const float* grad_out;     // the weight gradients: grad_out in the place of out, and dw_out
   float* dw_out;
+  const tfra_rows_out* typed;   // the typed lookups (plain tables only): the output record in the place of out; NULL otherwise
 };
 typedef PoolDesc (*PoolDescAt)(const void* descs, size_t i);
 
@@ -116,6 +122,11 @@ int desc_owner(const PoolDesc& d, Table** t, const char** why) {
   return TFRA_OK;
 }
 int pool_class(const Table* t) { return st_index(t->opts.value_dtype) * 3 + nch_index(t->opts.dim); }
+// A typed descriptor's output: its type is one more class axis of the plain classes — index 0, float32, runs the
+// untyped kernels — and its rows stand in the record where out stands (the kernels of a half class address 2-byte elements).
+int out_index(const PoolDesc& d) { return d.typed ? st_index(d.typed->dtype) : 0; }
+const float* out_checked(const PoolDesc& d) { return d.typed ? out_for_twin(*d.typed) : d.out; }   // what the twin's checks look at
+float* out_rows(const PoolDesc& d) { return d.typed ? static_cast<float*>(d.typed->rows) : d.out; }
 unsigned row_blocks(const PoolDesc& d) { return (unsigned)((d.n_rows * 16 + 255) / 256); }
 
 // The records' order: class by class, input order inside a class; first[c] is where class c starts, first[n_class] the number of

@@ -80,7 +80,9 @@ int multi_find_combine_frame(const char* who_c, tfra_workspace* ws, size_t n_tab
   if (n_tables == 0) return TFRA_OK;
   if (!ws || !descs) return set_error(TFRA_ERR_INVALID, who + ": null argument");
   // every descriptor is checked before anything is enqueued: one bad descriptor and no out is written
-  constexpr int NPLAIN = 9, NCLASS = 18;   // (plain | tiered) x (float32 | float16 | bfloat16) x (NCH 1 | 2 | 4)
+  // plain: (out float32 | float16 | bfloat16) x (float32 | float16 | bfloat16) x (NCH 1 | 2 | 4), out float32 first: the untyped
+  // calls' classes in their order; tiered: (float32 | float16 | bfloat16) x NCH
+  constexpr int NUNTYPED = 9, NPLAIN = 27, NCLASS = 36;
   std::vector<PoolDesc> ds(n_tables);
   std::vector<int> cls(n_tables, -1);
   std::vector<size_t> se_off(n_tables, 0);   // a descriptor's bounds in the bounds area, in input order
@@ -92,10 +94,13 @@ int multi_find_combine_frame(const char* who_c, tfra_workspace* ws, size_t n_tab
     Table* t = nullptr;
     const char* why = nullptr;
     if (int rc = desc_owner(d, &t, &why)) return set_error(rc, at_i() + why);
-    const Check c = check_find_combine(t, ws, d.nnz, d.ids, d.seg, d.weights, d.combiner, d.n_rows, d.default_row, d.out, [] { return Check{}; });
+    if (d.typed)
+      if (const Check c = check_rows_out(d.typed); c.code) return report(at_i(), c);
+    const Check c = check_find_combine(t, ws, d.nnz, d.ids, d.seg, d.weights, d.combiner, d.n_rows, d.default_row, out_checked(d),
+                                       [] { return Check{}; });
     if (c.code) return report(at_i(), c);
     if (!c.active) continue;
-    cls[i] = (d.tier ? NPLAIN : 0) + pool_class(t);
+    cls[i] = (d.tier ? NPLAIN : out_index(d) * NUNTYPED) + pool_class(t);
     n_bnd += d.nnz ? 1 : 0;
     bnd_blocks += (d.nnz + 255) / 256;
     se_off[i] = 2 * total_rows;
@@ -131,7 +136,7 @@ int multi_find_combine_frame(const char* who_c, tfra_workspace* ws, size_t n_tab
     const PoolDesc& d = ds[order[k]];
     Table* t = d.tier ? d.tier->upper : d.table;
     const ManyRec r{t->view_of(t->cur), d.n_rows, (const i64*)d.ids, d.weights, se_base + se_off[order[k]],
-                    (const unsigned char*)d.default_row, d.out, t->opts.dim, d.combiner};
+                    (const unsigned char*)d.default_row, out_rows(d), t->opts.dim, d.combiner};
     if (d.tier) trecs[k - n_plain] = TierManyRec{r, d.tier->lower->view_of(d.tier->lower->cur)};
     else recs[k] = r;
   }
@@ -162,7 +167,8 @@ int multi_find_combine_frame(const char* who_c, tfra_workspace* ws, size_t n_tab
     const ManyClass& k = row_cls[c];
     if (!k.n) continue;
     const unsigned* p = section<const unsigned>(up.dev, cpre_off) + k.at;
-    if (c < NPLAIN) launch_find_combine_many(s, c, k.grid, section<const ManyRec>(up.dev, rec_off) + first[c], p, k.n);
+    if (c < NUNTYPED) launch_find_combine_many(s, c, k.grid, section<const ManyRec>(up.dev, rec_off) + first[c], p, k.n);
+    else if (c < NPLAIN) launch_find_combine_many_typed(s, c - NUNTYPED, k.grid, section<const ManyRec>(up.dev, rec_off) + first[c], p, k.n);
     else launch_tier_find_combine_many(s, c - NPLAIN, k.grid, section<const TierManyRec>(up.dev, trec_off) + (first[c] - n_plain), p, k.n);
     ++launches;
   }
@@ -179,7 +185,9 @@ int multi_find_combine_ragged_frame(const char* who_c, tfra_workspace* ws, size_
   if (n_tables == 0) return TFRA_OK;
   if (!ws || !descs) return set_error(TFRA_ERR_INVALID, who + ": null argument");
   // every descriptor is checked before anything is enqueued: one bad descriptor and no out is written
-  constexpr int NPLAIN = 18, NCLASS = 36;   // (plain | tiered) x (float32 | float16 | bfloat16) x (NCH 1 | 2 | 4) x (plain | safe)
+  // plain: (out float32 | float16 | bfloat16) x (float32 | float16 | bfloat16) x (NCH 1 | 2 | 4) x (plain | safe), out float32
+  // first: the untyped calls' classes in their order; tiered: (float32 | float16 | bfloat16) x NCH x (plain | safe)
+  constexpr int NUNTYPED = 18, NPLAIN = 54, NCLASS = 72;
   std::vector<PoolDesc> ds(n_tables);
   std::vector<int> cls(n_tables, -1);
   for (size_t i = 0; i < n_tables; ++i) {
@@ -188,11 +196,13 @@ int multi_find_combine_ragged_frame(const char* who_c, tfra_workspace* ws, size_
     Table* t = nullptr;
     const char* why = nullptr;
     if (int rc = desc_owner(d, &t, &why)) return set_error(rc, at_i() + why);
+    if (d.typed)
+      if (const Check c = check_rows_out(d.typed); c.code) return report(at_i(), c);
     const Check c = check_find_combine_ragged(t, ws, d.n_rows, d.row_splits, d.nnz, d.ids, d.weights, d.combiner, d.flags, d.reserved,
-                                              d.default_row, d.out, [] { return Check{}; });
+                                              d.default_row, out_checked(d), [] { return Check{}; });
     if (c.code) return report(at_i(), c);
     if (!c.active) continue;
-    cls[i] = (d.tier ? NPLAIN : 0) + pool_class(t) * 2 + (ragged_safe(d.flags, d.weights) ? 1 : 0);
+    cls[i] = (d.tier ? NPLAIN : out_index(d) * NUNTYPED) + pool_class(t) * 2 + (ragged_safe(d.flags, d.weights) ? 1 : 0);
   }
   std::vector<size_t> order;
   size_t first[NCLASS + 1];
@@ -218,7 +228,7 @@ int multi_find_combine_ragged_frame(const char* who_c, tfra_workspace* ws, size_
     const PoolDesc& d = ds[order[k]];
     Table* t = d.tier ? d.tier->upper : d.table;
     const RaggedRec r{t->view_of(t->cur), d.n_rows, (const i64*)d.ids, d.weights, (const i64*)d.row_splits,
-                      (const unsigned char*)d.default_row, d.out, (i64)d.fill_id, (int)d.nnz, t->opts.dim, d.combiner, d.flags};
+                      (const unsigned char*)d.default_row, out_rows(d), (i64)d.fill_id, (int)d.nnz, t->opts.dim, d.combiner, d.flags};
     if (d.tier) trecs[k - n_plain] = TierRaggedRec{r, d.tier->lower->view_of(d.tier->lower->cur)};
     else recs[k] = r;
   }
@@ -234,7 +244,9 @@ int multi_find_combine_ragged_frame(const char* who_c, tfra_workspace* ws, size_
     const ManyClass& k = row_cls[c];
     if (!k.n) continue;
     const unsigned* p = section<const unsigned>(up.dev, cpre_off) + k.at;
-    if (c < NPLAIN) launch_find_combine_ragged_many(s, c / 2, c & 1, k.grid, section<const RaggedRec>(up.dev, rec_off) + first[c], p, k.n);
+    if (c < NUNTYPED) launch_find_combine_ragged_many(s, c / 2, c & 1, k.grid, section<const RaggedRec>(up.dev, rec_off) + first[c], p, k.n);
+    else if (c < NPLAIN)
+      launch_find_combine_ragged_many_typed(s, (c - NUNTYPED) / 2, c & 1, k.grid, section<const RaggedRec>(up.dev, rec_off) + first[c], p, k.n);
     else launch_tier_find_combine_ragged_many(s, (c - NPLAIN) / 2, c & 1, k.grid,
                                               section<const TierRaggedRec>(up.dev, trec_off) + (first[c] - n_plain), p, k.n);
     ++launches;

@@ -71,6 +71,11 @@ class Grads(ctypes.Structure):
   _fields_ = [("grads", ctypes.c_void_p), ("dtype", ctypes.c_int32), ("reserved", ctypes.c_int32), ("d_scale", ctypes.c_void_p)]
 
 
+class RowsOut(ctypes.Structure):
+  """tfra_rows_out (include/tfra_mi355x.h): a lookup's output matrix in a dtype of its own, for the typed lookups."""
+  _fields_ = [("rows", ctypes.c_void_p), ("dtype", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 class RowFields(ctypes.Structure):
   """tfra_row_fields (include/tfra_mi355x.h): the float32 field tensors of tfra_table_fetch_planned / tfra_table_store_rows."""
   _fields_ = [("struct_size", ctypes.c_uint32), ("n_fields", ctypes.c_int32), ("field", ctypes.c_void_p * 5)]
@@ -103,6 +108,27 @@ class FindCombineRaggedDesc(ctypes.Structure):
       ("row_splits", ctypes.c_void_p), ("nnz", ctypes.c_size_t), ("ids", ctypes.c_void_p), ("weights", ctypes.c_void_p),
       ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("fill_id", ctypes.c_int64), ("default_row", ctypes.c_void_p),
       ("out", ctypes.c_void_p),
+  ]
+
+
+class FindCombineTypedDesc(ctypes.Structure):
+  """tfra_find_combine_typed_desc (include/tfra_mi355x.h): FindCombineDesc with out as a tfra_rows_out, for
+  tfra_multi_find_combine_typed."""
+  _fields_ = [
+      ("struct_size", ctypes.c_uint32), ("combiner", ctypes.c_int32), ("table", ctypes.c_void_p), ("nnz", ctypes.c_size_t),
+      ("ids", ctypes.c_void_p), ("seg", ctypes.c_void_p), ("weights", ctypes.c_void_p), ("n_rows", ctypes.c_size_t),
+      ("default_row", ctypes.c_void_p), ("out", RowsOut),
+  ]
+
+
+class FindCombineRaggedTypedDesc(ctypes.Structure):
+  """tfra_find_combine_ragged_typed_desc (include/tfra_mi355x.h): FindCombineRaggedDesc with out as a tfra_rows_out, for
+  tfra_multi_find_combine_ragged_typed."""
+  _fields_ = [
+      ("struct_size", ctypes.c_uint32), ("combiner", ctypes.c_int32), ("table", ctypes.c_void_p), ("n_rows", ctypes.c_size_t),
+      ("row_splits", ctypes.c_void_p), ("nnz", ctypes.c_size_t), ("ids", ctypes.c_void_p), ("weights", ctypes.c_void_p),
+      ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("fill_id", ctypes.c_int64), ("default_row", ctypes.c_void_p),
+      ("out", RowsOut),
   ]
 
 
@@ -331,6 +357,12 @@ _SIGS = {
     "tfra_multi_find_combine": [_P, _SZ, _P, _P, _P],
     "tfra_table_find_combine_ragged": [_P, _SZ, _P, _SZ, _P, _P, _I, ctypes.c_uint32, ctypes.c_int64, _P, _P, _P],
     "tfra_multi_find_combine_ragged": [_P, _SZ, _P, _P, _P],
+    "tfra_table_find_typed": [_P, _SZ, _P, _P, ctypes.POINTER(RowsOut), _P, _P, _I, _P],
+    "tfra_table_find_combine_typed": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, ctypes.POINTER(RowsOut), _P],
+    "tfra_table_find_combine_ragged_typed": [_P, _SZ, _P, _SZ, _P, _P, _I, ctypes.c_uint32, ctypes.c_int64, _P,
+                                             ctypes.POINTER(RowsOut), _P],
+    "tfra_multi_find_combine_typed": [_P, _SZ, _P, _P, _P],
+    "tfra_multi_find_combine_ragged_typed": [_P, _SZ, _P, _P, _P],
     "tfra_multi_tier_find_combine": [_P, _SZ, _P, _P, _P],
     "tfra_multi_tier_find_combine_ragged": [_P, _SZ, _P, _P, _P],
     "tfra_multi_tier_find_or_insert": [_P, _SZ, _P, _P, _P],

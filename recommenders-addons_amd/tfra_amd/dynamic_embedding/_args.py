@@ -57,6 +57,22 @@ def _grads_arg(grads, device, dim, grad_scale=None, max_elements=None):
   return None, g.contiguous()
 
 
+_OUT_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def _out_dtype(out_dtype):
+  """The `out_dtype=` of a lookup: None (the call's own output type: today's path) or one of float32 / float16 / bfloat16, the
+  types the typed lookups write (tfra_rows_out); anything else raises TypeError before a launch."""
+  if out_dtype is not None and out_dtype not in _OUT_DTYPES:
+    raise TypeError("out_dtype must be torch.float32, torch.float16 or torch.bfloat16, got %s" % (out_dtype,))
+  return out_dtype
+
+
+def _rows_out(out):
+  """A lookup's output tensor as the typed calls take it (tfra_rows_out).  Keep the tensor alive across the call."""
+  return _capi.RowsOut(out.data_ptr(), _TORCH2DT[out.dtype], 0)
+
+
 def _wide_keys(keys):
   """`keys` as the engine's int64 keys, for a C function that reads `const int64_t*`: int64 keys as they are, int32 keys widened on
   the device (tfra_keys_widen_i32).  Any other dtype raises TypeError before a launch."""

@@ -22,6 +22,7 @@ the forward itself reads nothing."""
 import torch
 
 from . import device_ops, table_ops
+from ._args import _out_dtype
 from .variable import (SparseTrainableWrapper, _admit_entries_many, _check_combiner, _check_entries_many, _note_pruned, _per_table,
                        _pooled_forward, _pooled_reader, _pooled_training, _safe_sparse_args, _safe_sparse_args_many, _wrap_grouped)
 from . import variable as _tuple_form
@@ -83,8 +84,13 @@ def _safe_wrapper(params, args, combiner, n, plan_writeback, entry_plan=None, ca
   return _note_pruned(tw, caller_weights, combiner)
 
 
+def _typed(out_dtype):
+  """The keyword of a typed lookup behind this module's calls: nothing for None, so that today's calls stay as they are."""
+  return {} if _out_dtype(out_dtype) is None else {"out_dtype": out_dtype}
+
+
 def embedding_lookup_sparse(params, sp_ids, sp_weights, name=None, combiner="mean", return_trainable=False, plan_writeback=False,
-                            entry_seg=None, out_shape=None):
+                            entry_seg=None, out_shape=None, out_dtype=None):
   """PY/ragged_embedding_ops.py:223-324.  `sp_ids` = (row_splits[n_rows + 1], values[nnz]), `sp_weights` = weight values or None.
   [n_rows, dim] float32: row r = sum / mean / sqrtn over its entries of weight * embedding, zeros for an empty row — bit-identical
   to `de.embedding_lookup_sparse(params, (row ids, values), sp_weights, num_rows=n_rows)`, in one launch.
@@ -93,48 +99,54 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights, name=None, combiner="mea
   list is (values, derived row ids, weights).  plan_writeback: as the tuple form's.
   entry_seg: the row id of every entry (int64 [nnz], what the splits stand for) from a caller that has it — `layers.
   FieldWiseEmbedding`, whose list builder writes it — so that it is not derived again; out_shape: the shape that caller gives the
-  result ([n_rows, dim] reshaped), which the wrapper then expects of the gradient.  Both default to today's path."""
+  result ([n_rows, dim] reshaped), which the wrapper then expects of the gradient.  Both default to today's path.
+  out_dtype: the result in float32 / float16 / bfloat16, bit for bit `embedding_lookup_sparse(...).to(out_dtype)`, rounded in the
+  lookup's kernel where the pooled read serves the variable (tfra_table_find_combine_ragged_typed), converted otherwise."""
   _check_combiner(combiner)
+  typed = _typed(out_dtype)
   rs, ids, w = _ragged_input(params, sp_ids, sp_weights)
   n = rs.numel() - 1
   if not (_pooled_training if return_trainable else _pooled_forward)(params, None):
     seg = row_ids_of(rs, ids.numel()) if entry_seg is None else entry_seg
     return _tuple_form.embedding_lookup_sparse(params, (seg, ids), w, combiner=combiner, return_trainable=return_trainable,
-                                               num_rows=n, plan_writeback=plan_writeback, _out_shape=out_shape)
+                                               num_rows=n, plan_writeback=plan_writeback, _out_shape=out_shape, **typed)
   if return_trainable:
     params.admit_entries(ids)   # (tiered shards: the entry ids into the cache ahead of the read; init_on_lookup="pooled": admitted with drawn rows)
-  out = params.lookup_combined_ragged(rs, ids, w, combiner)
+  out = params.lookup_combined_ragged(rs, ids, w, combiner, **typed)
   if not return_trainable:
     return out
   return out, _plain_wrapper(params, rs, ids, w, combiner, n, plan_writeback, seg=entry_seg, out_shape=out_shape)
 
 
 def safe_embedding_lookup_sparse(params, sparse_ids, sparse_weights=None, combiner="mean", default_id=None, name=None,
-                                 return_trainable=False, plan_writeback=False):
+                                 return_trainable=False, plan_writeback=False, out_dtype=None):
   """PY/ragged_embedding_ops.py:327-442, with this project's semantics of the tuple form (`de.safe_embedding_lookup_sparse`):
   ids are never pruned; entries whose weight is not > 0 are dropped unless combiner == "sum"; a row left without entries yields
   zeros, or the embedding of `default_id`.  Bit-identical to the tuple form on (row ids, values), in one launch and with no
   host synchronisation: the pruning and the default row are the kernel's.
 
   return_trainable: also returns the SparseTrainableWrapper; its entry list is what the tuple form's preprocessing
-  (`_safe_sparse_args`) makes on the derived row ids, built on the device from row_splits with one host read of its length."""
+  (`_safe_sparse_args`) makes on the derived row ids, built on the device from row_splits with one host read of its length.
+  out_dtype: as `embedding_lookup_sparse`'s; the row of default_id is converted as it is."""
   _check_combiner(combiner)
+  typed = _typed(out_dtype)
   rs, ids, w = _ragged_input(params, sparse_ids, sparse_weights)
   n = rs.numel() - 1
   if not (_pooled_training if return_trainable else _pooled_forward)(params, None):
     return _tuple_form.safe_embedding_lookup_sparse(params, (row_ids_of(rs, ids.numel()), ids), w, combiner=combiner,
                                                     default_id=default_id, return_trainable=return_trainable, num_rows=n,
-                                                    plan_writeback=plan_writeback)
+                                                    plan_writeback=plan_writeback, **typed)
   prune, fill = _safe_flags(w, combiner, default_id)
   if not return_trainable:
-    return params.lookup_combined_ragged(rs, ids, w, combiner, prune=prune, fill_id=fill)
+    return params.lookup_combined_ragged(rs, ids, w, combiner, prune=prune, fill_id=fill, **typed)
   made = _safe_entries_many([params], [(0, rs, ids, w)], [combiner], [default_id])[0]
   params.admit_entries(made[3][0])   # (tiered shards: the entry ids into the cache ahead of the read; init_on_lookup="pooled": admitted with drawn rows)
-  out = params.lookup_combined_ragged(rs, ids, w, combiner, prune=prune, fill_id=fill)
+  out = params.lookup_combined_ragged(rs, ids, w, combiner, prune=prune, fill_id=fill, **typed)
   return out, _safe_wrapper(params, made, combiner, n, plan_writeback, caller_weights=w)
 
 
-def _many(params_list, sp_ids_list, weights_list, combiner, default_id, safe, return_trainable, plan_writeback):
+def _many(params_list, sp_ids_list, weights_list, combiner, default_id, safe, return_trainable, plan_writeback, out_dtype=None):
+  typed = _typed(out_dtype)
   n_t = len(params_list)
   if len(sp_ids_list) != n_t:
     raise ValueError("sp_ids_list: %d entries for %d tables" % (len(sp_ids_list), n_t))
@@ -165,7 +177,7 @@ def _many(params_list, sp_ids_list, weights_list, combiner, default_id, safe, re
   for i in singles:
     kw = dict(default_id=default_ids[i]) if safe else {}
     results[i] = single(params_list[i], sp_ids_list[i], weights[i], combiner=combiners[i], return_trainable=return_trainable,
-                        plan_writeback=plan_writeback, **kw)
+                        plan_writeback=plan_writeback, **kw, **typed)
   for device, members in groups.items():
     if return_trainable:
       _admit_entries_many(params_list, {m[0]: entry_ids[m[0]] for m in members})   # (tiered members; ahead of the ONE read)
@@ -174,7 +186,7 @@ def _many(params_list, sp_ids_list, weights_list, combiner, default_id, safe, re
       t = params_list[i]._tables[0]
       prune, fill = _safe_flags(w, combiners[i], default_ids[i]) if safe else (False, None)
       reqs.append((_pooled_reader(t), rs, ids, w, device_ops.COMBINERS[combiners[i]], prune, fill, t._default_value))
-    outs = table_ops.find_combine_ragged_many(reqs)
+    outs = table_ops.find_combine_ragged_many(reqs, **typed)
     if not return_trainable:
       for (i, _, _, _), out in zip(members, outs):
         results[i] = out
@@ -191,20 +203,22 @@ def _many(params_list, sp_ids_list, weights_list, combiner, default_id, safe, re
 
 
 def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None, combiner="mean", return_trainable=False,
-                                 plan_writeback=False):
+                                 plan_writeback=False, out_dtype=None):
   """`embedding_lookup_sparse` of a LIST of variables: result i is what the single form returns for table i, bit for bit.
   `combiner` is a scalar or a per-table list.  The variables the pooled forward serves are read by ONE grouped call per device
   (`table_ops.find_combine_ragged_many`: tfra_multi_find_combine_ragged — one upload and one launch per class, no bounds pass; with
   a tiered variable among them tfra_multi_tier_find_combine_ragged, which reads that member in both tiers — with return_trainable
-  behind one admission of its entry ids per tiered member); every other variable takes the single form, so no list is refused."""
-  return _many(params_list, sp_ids_list, sp_weights_list, combiner, None, False, return_trainable, plan_writeback)
+  behind one admission of its entry ids per tiered member); every other variable takes the single form, so no list is refused.
+  out_dtype: one of float32 / float16 / bfloat16 for every result, as the single form's (tfra_multi_find_combine_ragged_typed: the
+  same launch count; a group with a tiered member is converted)."""
+  return _many(params_list, sp_ids_list, sp_weights_list, combiner, None, False, return_trainable, plan_writeback, out_dtype)
 
 
 def safe_embedding_lookup_sparse_many(params_list, sp_ids_list, sparse_weights_list=None, combiner="mean", default_id=None,
-                                      return_trainable=False, plan_writeback=False):
+                                      return_trainable=False, plan_writeback=False, out_dtype=None):
   """`safe_embedding_lookup_sparse` of a LIST of variables: result i is what the single form returns for table i, bit for bit.
   `combiner` and `default_id` are scalars or per-table lists.  One grouped call per device for the variables the pooled forward
   serves (tiered ones included, as in `embedding_lookup_sparse_many`), with no host synchronisation in the forward; with
   return_trainable the wrappers' entry lists of all tables come from one `device_ops.safe_entries_many` per device (one C call,
   one host read of every list's length), ahead of the grouped call: they are what a tiered member admits."""
-  return _many(params_list, sp_ids_list, sparse_weights_list, combiner, default_id, True, return_trainable, plan_writeback)
+  return _many(params_list, sp_ids_list, sparse_weights_list, combiner, default_id, True, return_trainable, plan_writeback, out_dtype)

@@ -23,8 +23,8 @@ import torch
 
 from .. import _capi
 from ._args import (_TORCH2DT, _admitted_rows, _as_device, _as_tensor, _cap_for, _check_plan, _default_rows, _driver_ids, _grads_arg,
-                    _narrow_keys, _out_rows, _over_plans, _ptr, _rows_on, _score_filter, _scores_for, _stream, _trim_to_count,
-                    _wide_keys)
+                    _narrow_keys, _out_dtype, _out_rows, _over_plans, _ptr, _rows_on, _rows_out, _score_filter, _scores_for, _stream,
+                    _trim_to_count, _wide_keys)
 from .device_ops import _workspace
 
 KHkvHashTableInitCapacity = 1024 * 1024  # PY/hkv_hashtable_ops.py:40-44
@@ -143,14 +143,22 @@ class _DeviceTable:
     return _out_rows(self._value_dtype, self._dim, self._device, shape, out)
 
   # ---- ops ---------------------------------------------------------------------------------
-  def find(self, keys, dynamic_default_values=None, return_exists=False, field=0):
+  def find(self, keys, dynamic_default_values=None, return_exists=False, field=0, out_dtype=None):
+    """out_dtype (field 0 only): the rows in float32 / float16 / bfloat16 instead of the value dtype, converted in the lookup's
+    kernel (tfra_table_find_typed): bit for bit `find(...).to(out_dtype)`.  The default rows stay in the value dtype."""
     keys = self._keys(keys)
     n = keys.numel()
     d, full = self._defaults(dynamic_default_values, n)
-    out = torch.empty(tuple(keys.shape) + (self._dim,), dtype=self._value_dtype, device=self._device)
+    if _out_dtype(out_dtype) is not None and field:
+      raise ValueError("out_dtype serves field 0 only")
+    out = torch.empty(tuple(keys.shape) + (self._dim,), dtype=out_dtype or self._value_dtype, device=self._device)
     exists = torch.empty(keys.shape, dtype=torch.bool, device=self._device) if return_exists else None
     if n:
-      if field:
+      if out_dtype is not None:
+        ro = _rows_out(out)
+        _capi.call("tfra_table_find_typed", self._h, n, None, _ptr(keys), ctypes.byref(ro), _ptr(exists), _ptr(d), full,
+                   _stream(self._device))
+      elif field:
         _capi.call("tfra_table_find_field", self._h, field, n, _ptr(keys), _ptr(out), _ptr(exists), _ptr(d), full,
                    _stream(self._device))
       else:
@@ -191,30 +199,41 @@ class _DeviceTable:
     d = d.contiguous()
     return w, d
 
-  def _find_combine_args(self, ids, seg, weights, n_rows, default_row):
+  def _find_combine_args(self, ids, seg, weights, n_rows, default_row, out_dtype=None):
     """The arguments of one pooled lookup as the C calls read them: (ids, seg, weights or None, default row, out), checked and on
-    the table's device (find_combine and find_combine_many share it)."""
+    the table's device (find_combine and find_combine_many share it).  out: float32, or `out_dtype` (the typed calls)."""
     ids = self._keys(ids).reshape(-1)
     nnz = ids.numel()
     seg = torch.as_tensor(seg, device=self._device).reshape(-1).to(torch.int64).contiguous()
     if seg.numel() != nnz:
       raise ValueError("ids and segment_ids must have the same number of elements: %d vs %d" % (nnz, seg.numel()))
     w, d = self._pooled_operands(nnz, weights, default_row)
-    out = torch.empty((int(n_rows), self._dim), dtype=torch.float32, device=self._device)
+    out = torch.empty((int(n_rows), self._dim), dtype=_out_dtype(out_dtype) or torch.float32, device=self._device)
     return ids, seg, w, d, out
 
   def find_combine(self, ids, seg, weights, combiner, n_rows, default_row=None):
+    """`find_combine_typed` with the call's own output type, float32 (tfra_table_find_combine)."""
+    return self.find_combine_typed(ids, seg, weights, combiner, n_rows, default_row)
+
+  def find_combine_typed(self, ids, seg, weights, combiner, n_rows, default_row=None, out_dtype=None):
     """The pooled lookup (tfra_table_find_combine): out[r] = combine over {p: seg[p] == r}, in input order, of weights[p] * (the row
     of ids[p], or `default_row` — one row of the value dtype, the table's default when None — on a miss), float32 [n_rows, dim].
     seg ascending int64, weights float32 or None (all 1), combiner 0 sum / 1 mean / 2 sqrtn.  float32 / float16 / bfloat16 rows,
     dim % 4 == 0, dim <= 256 (TfraError UNSUPPORTED otherwise).  Bit-identical to find + device_ops.sparse_segment_combine over
-    idx = arange(nnz); no unique pass, nothing read on the host."""
-    ids, seg, w, d, out = self._find_combine_args(ids, seg, weights, n_rows, default_row)
+    idx = arange(nnz); no unique pass, nothing read on the host.  out_dtype: the result in float32 / float16 / bfloat16, rounded
+    in the lookup's kernel (tfra_table_find_combine_typed): bit for bit `find_combine(...).to(out_dtype)`; None: `find_combine`.
+    (A method beside `find_combine`, whose parameter list the tiered owners mirror and stays as it is.)"""
+    ids, seg, w, d, out = self._find_combine_args(ids, seg, weights, n_rows, default_row, out_dtype)
+    if out_dtype is not None:
+      ro = _rows_out(out)
+      _capi.call("tfra_table_find_combine_typed", self._h, _workspace(self._device), ids.numel(), _ptr(ids), _ptr(seg), _ptr(w),
+                 int(combiner), int(n_rows), _ptr(d), ctypes.byref(ro), _stream(self._device))
+      return out
     _capi.call("tfra_table_find_combine", self._h, _workspace(self._device), ids.numel(), _ptr(ids), _ptr(seg), _ptr(w), int(combiner),
                int(n_rows), _ptr(d), _ptr(out), _stream(self._device))
     return out
 
-  def _find_combine_ragged_args(self, row_splits, ids, weights, prune, fill_id, default_row):
+  def _find_combine_ragged_args(self, row_splits, ids, weights, prune, fill_id, default_row, out_dtype=None):
     """The arguments of one ragged pooled lookup as the C calls read them: (row_splits int64 [n_rows + 1], ids, weights or None,
     flags, fill id, default row, out), checked and on the table's device (find_combine_ragged and find_combine_ragged_many share
     it).  Shapes only: the content of row_splits is the kernel's business (it clamps), nothing is read on the host."""
@@ -227,16 +246,22 @@ class _DeviceTable:
     rs = rs.to(torch.int64).contiguous()   # int32 splits are widened
     w, d = self._pooled_operands(ids.numel(), weights, default_row)
     flags = (_capi.RAGGED_PRUNE if prune else 0) | (_capi.RAGGED_FILL if fill_id is not None else 0)
-    out = torch.empty((rs.numel() - 1, self._dim), dtype=torch.float32, device=self._device)
+    out = torch.empty((rs.numel() - 1, self._dim), dtype=_out_dtype(out_dtype) or torch.float32, device=self._device)
     return rs, ids, w, flags, (0 if fill_id is None else int(fill_id)), d, out
 
-  def find_combine_ragged(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, default_row=None):
+  def find_combine_ragged(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, default_row=None, out_dtype=None):
     """The pooled lookup over a ragged batch (tfra_table_find_combine_ragged): row r combines the entries
     [row_splits[r], row_splits[r + 1]) of ids / weights as `find_combine` combines the entries with seg == r, bit for bit, in ONE
     launch (no bounds pass).  row_splits int64 or int32 [n_rows + 1]; out-of-range or decreasing splits give empty or shortened
     rows, never a read outside ids.  prune: only entries with weight > 0 are members (ignored without weights).  fill_id: a row
-    without members is the row of that key (`default_row` on a miss), up-cast as it is; None: zeros.  Nothing is read on the host."""
-    rs, ids, w, flags, fill, d, out = self._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row)
+    without members is the row of that key (`default_row` on a miss), up-cast as it is; None: zeros.  Nothing is read on the host.
+    out_dtype: as `find_combine`'s (tfra_table_find_combine_ragged_typed)."""
+    rs, ids, w, flags, fill, d, out = self._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row, out_dtype)
+    if out_dtype is not None:
+      ro = _rows_out(out)
+      _capi.call("tfra_table_find_combine_ragged_typed", self._h, rs.numel() - 1, _ptr(rs), ids.numel(), _ptr(ids), _ptr(w),
+                 int(combiner), flags, fill, _ptr(d), ctypes.byref(ro), _stream(self._device))
+      return out
     _capi.call("tfra_table_find_combine_ragged", self._h, rs.numel() - 1, _ptr(rs), ids.numel(), _ptr(ids), _ptr(w), int(combiner),
                flags, fill, _ptr(d), _ptr(out), _stream(self._device))
     return out
@@ -793,10 +818,14 @@ class _DeviceTier:
   def max_batch(self):
     return self._max_batch
 
-  def find(self, keys, dynamic_default_values=None, return_where=False, count=None, out=None):
+  def find(self, keys, dynamic_default_values=None, return_where=False, count=None, out=None, out_dtype=None):
     """A read (tfra_tier_find): the row upper holds, else the row lower holds, else the default.  Keys may repeat; nothing moves and
     neither table is written.  -> rows, or (rows, where) with where uint8: 1 = upper, 2 = lower, 0 = neither.  The default rows
-    follow the admitting rule ([n, dim] or exactly one row), not `_DeviceTable.find`'s."""
+    follow the admitting rule ([n, dim] or exactly one row), not `_DeviceTable.find`'s.  out_dtype: the tier calls are not typed —
+    the rows are converted behind the call."""
+    if _out_dtype(out_dtype) is not None:
+      r = self.find(keys, dynamic_default_values, return_where, count, out)
+      return (r[0].to(out_dtype), r[1]) if return_where else r.to(out_dtype)
     keys = self._upper._keys(keys)
     d, full = self._upper._init_rows(dynamic_default_values, keys.numel(), "default values")
     out = self._upper._out(keys.shape, out)
@@ -874,6 +903,12 @@ class _DeviceTier:
       _over_plans((plan,), self._upper._device, True, _capi.call, "tfra_tier_find_or_insert_planned", self._h, plan._h, _ptr(d), full,
                   None, None, _capi.TIER_VERIFY if verify else 0, _stream(self._upper._device))
 
+  def find_combine_typed(self, ids, seg, weights, combiner, n_rows, default_row=None, out_dtype=None):
+    """`find_combine` with `_DeviceTable.find_combine_typed`'s out_dtype: the tier calls are not typed — the float32 result is
+    converted."""
+    out = self.find_combine(ids, seg, weights, combiner, n_rows, default_row)
+    return out if _out_dtype(out_dtype) is None else out.to(out_dtype)
+
   def find_combine(self, ids, seg, weights, combiner, n_rows, default_row=None):
     """`_DeviceTable.find_combine` over both tiers (tfra_tier_find_combine): an entry's row is the one upper holds, else the one
     lower holds, else `default_row`.  A read: nothing moves, nothing is written, `stats()` does not change; ids are not limited by
@@ -884,10 +919,12 @@ class _DeviceTier:
                int(n_rows), _ptr(d), _ptr(out), _stream(up._device))
     return out
 
-  def find_combine_ragged(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, default_row=None):
+  def find_combine_ragged(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, default_row=None, out_dtype=None):
     """`_DeviceTable.find_combine_ragged` over both tiers (tfra_tier_find_combine_ragged), in one launch: bit-identical to
     `find_combine` on the row ids the splits stand for; the row of `fill_id` is looked up in upper, then lower, then is
-    `default_row`.  A read, as `find_combine`."""
+    `default_row`.  A read, as `find_combine`; out_dtype as there."""
+    if _out_dtype(out_dtype) is not None:
+      return self.find_combine_ragged(row_splits, ids, weights, combiner, prune, fill_id, default_row).to(out_dtype)
     up = self._upper
     rs, ids, w, flags, fill, d, out = up._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row)
     _capi.call("tfra_tier_find_combine_ragged", self._h, rs.numel() - 1, _ptr(rs), ids.numel(), _ptr(ids), _ptr(w), int(combiner),
@@ -1067,9 +1104,9 @@ class _LookupInterfaceMirror:
     are copied, not rounded."""
     self._table.set_stochastic_rounding(seed)
 
-  def lookup(self, keys, dynamic_default_values=None, return_exists=False, name=None):
-    """PY/cuckoo_hashtable_ops.py:272-340"""
-    return self._table.find(keys, dynamic_default_values, return_exists)
+  def lookup(self, keys, dynamic_default_values=None, return_exists=False, name=None, out_dtype=None):
+    """PY/cuckoo_hashtable_ops.py:272-340.  out_dtype: `_DeviceTable.find`'s."""
+    return self._table.find(keys, dynamic_default_values, return_exists, out_dtype=out_dtype)
 
   def find_or_insert(self, keys, dynamic_default_values=None, return_exists=False, name=None, count=None):
     """HierarchicalKV's find_or_insert: `lookup` that inserts every key it does not find with the row it returns for it
@@ -1377,7 +1414,8 @@ class TieredHashTable(_LookupInterfaceMirror):
     self._lower.clear_all()
 
   def lookup(self, keys, dynamic_default_values=None, return_exists=False, name=None):
-    """A read of both tiers (`_DeviceTier.find`): nothing moves."""
+    """A read of both tiers (`_DeviceTier.find`): nothing moves.  (No out_dtype here: the tier calls are not typed, and
+    `Variable.lookup` converts a tiered shard's rows behind this call.)"""
     keys = _as_tensor(keys, self._device)
     flat = keys.reshape(-1)
     n, dim = flat.numel(), self._table.dim
@@ -1422,9 +1460,14 @@ class TieredHashTable(_LookupInterfaceMirror):
     """The pooled lookup over both tiers (`_DeviceTier.find_combine`): a read, nothing moves."""
     return self._tier.find_combine(ids, seg, weights, combiner, n_rows, default_row)
 
-  def find_combine_ragged(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, default_row=None):
+  def find_combine_typed(self, ids, seg, weights, combiner, n_rows, default_row=None, out_dtype=None):
+    """`find_combine` converted to out_dtype (`_DeviceTier.find_combine_typed`)."""
+    return self._tier.find_combine_typed(ids, seg, weights, combiner, n_rows, default_row, out_dtype=out_dtype)
+
+  def find_combine_ragged(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, default_row=None, out_dtype=None):
     """The ragged pooled lookup over both tiers (`_DeviceTier.find_combine_ragged`): a read, nothing moves."""
-    return self._tier.find_combine_ragged(row_splits, ids, weights, combiner, prune=prune, fill_id=fill_id, default_row=default_row)
+    return self._tier.find_combine_ragged(row_splits, ids, weights, combiner, prune=prune, fill_id=fill_id, default_row=default_row,
+                                          out_dtype=out_dtype)
 
   def find_combine_weight_grad(self, ids, seg, weights, combiner, grad_out, default_row=None):
     """The gradient of `find_combine` with respect to its weights, over both tiers (`_DeviceTier.find_combine_weight_grad`): a
@@ -1559,7 +1602,24 @@ def _grouped_call(c_name, desc_type, who, owners, fill):
   return int(launches.value)
 
 
-def find_combine_many(requests, return_launches=False):
+def _out_dtypes(out_dtype, n):
+  """The `out_dtype=` of a grouped lookup as one entry per request: one dtype for the list, or a list of n (None: float32, the
+  request's own type).  None when every entry is None: today's call."""
+  dts = list(out_dtype) if isinstance(out_dtype, (list, tuple)) else [out_dtype] * n
+  if len(dts) != n:
+    raise ValueError("out_dtype must be one dtype or one per request: %d for %d requests" % (len(dts), n))
+  dts = [_out_dtype(d) for d in dts]
+  return None if all(d is None for d in dts) else dts
+
+
+def _converted(result, dts, return_launches):
+  """The results of an untyped grouped lookup, each converted to its request's out_dtype (a list with a tiered member)."""
+  outs = result[0] if return_launches else result
+  outs = [o if d is None else o.to(d) for o, d in zip(outs, dts)]
+  return (outs, result[1]) if return_launches else outs
+
+
+def find_combine_many(requests, return_launches=False, out_dtype=None):
   """The pooled lookups of a list of tables in ONE C call (tfra_multi_find_combine; the frame: `_grouped_call`).  `requests`: a
   list of (table, ids, seg, weights, combiner, n_rows[, default_row]), the arguments behind `table` those of
   `_DeviceTable.find_combine`, handled the same way (int32 keys widened, the default row falling back to the table's).  Returns
@@ -1567,31 +1627,39 @@ def find_combine_many(requests, return_launches=False):
   return_launches: also the number of kernel launches the call enqueued — it does not grow with the list).
   `table` may be a TieredHashTable or a _DeviceTier: its request is read in BOTH tiers, bit-identical to the tier's `find_combine`
   (the operands prepared by the upper table).  A list with a tiered owner goes through tfra_multi_tier_find_combine as a whole,
-  plain tables included — still one call; a list without one takes the call, the descriptor and the launch counts it always took."""
+  plain tables included — still one call; a list without one takes the call, the descriptor and the launch counts it always took.
+  out_dtype: one of float32 / float16 / bfloat16 for the list, or one per request (None: float32): each result in that type,
+  rounded in the lookup's kernel (tfra_multi_find_combine_typed), bit for bit `result.to(out_dtype)`; the output type is one more
+  launch-class axis, so a list with one output type keeps its launch count.  The tier calls are not typed: a list with a tiered
+  member runs untyped as a whole and each result is converted."""
   if not requests:
     return ([], 0) if return_launches else []
   outs = []
   tiered = any(_device_tier(r[0]) is not None for r in requests)
+  dts = _out_dtypes(out_dtype, len(requests))
+  if dts is not None and tiered:
+    return _converted(find_combine_many(requests, return_launches), dts, return_launches)
 
   def fill(e, i):
     req = requests[i]
     table, ids, seg, weights, combiner, n_rows = req[:6]
     default_row = req[6] if len(req) > 6 else None
     table = _pooled_owner(e, table, tiered)
-    ids, seg, w, d, out = table._find_combine_args(ids, seg, weights, n_rows, default_row)
+    ids, seg, w, d, out = table._find_combine_args(ids, seg, weights, n_rows, default_row, dts[i] if dts else None)
     outs.append(out)
     e.combiner = int(combiner)
     e.nnz, e.ids, e.seg, e.weights = ids.numel(), ids.data_ptr(), seg.data_ptr(), (w.data_ptr() if w is not None else None)
-    e.n_rows, e.default_row, e.out = int(n_rows), d.data_ptr(), out.data_ptr()
+    e.n_rows, e.default_row, e.out = int(n_rows), d.data_ptr(), (_rows_out(out) if dts else out.data_ptr())
     return ids, seg, w, d
 
   c_name, desc_type = (("tfra_multi_tier_find_combine", _capi.TierFindCombineDesc) if tiered else
+                       ("tfra_multi_find_combine_typed", _capi.FindCombineTypedDesc) if dts else
                        ("tfra_multi_find_combine", _capi.FindCombineDesc))
   launches = _grouped_call(c_name, desc_type, "find_combine_many", [r[0] for r in requests], fill)
   return (outs, launches) if return_launches else outs
 
 
-def find_combine_ragged_many(requests, return_launches=False):
+def find_combine_ragged_many(requests, return_launches=False, out_dtype=None):
   """The ragged pooled lookups of a list of tables in ONE C call (tfra_multi_find_combine_ragged; the frame: `_grouped_call`).
   `requests`: a list of (table, row_splits, ids, weights, combiner[, prune[, fill_id[, default_row]]]), the arguments behind
   `table` those of `_DeviceTable.find_combine_ragged`, handled the same way.  A table may occur more than once.  Returns the
@@ -1599,11 +1667,15 @@ def find_combine_ragged_many(requests, return_launches=False):
   return_launches: also the number of kernel launches the call enqueued: one per (value dtype, row-width class, safe-or-not)
   class in the list).  `table` may be a TieredHashTable or a _DeviceTier, as in `find_combine_many`: the request is read in both
   tiers, the fill id too, and the whole list goes through tfra_multi_tier_find_combine_ragged (one launch per (tiered or not,
-  value dtype, row-width class, safe-or-not) class); a list without a tiered owner takes the call it always took."""
+  value dtype, row-width class, safe-or-not) class); a list without a tiered owner takes the call it always took.
+  out_dtype: as `find_combine_many`'s (tfra_multi_find_combine_ragged_typed)."""
   if not requests:
     return ([], 0) if return_launches else []
   outs = []
   tiered = any(_device_tier(r[0]) is not None for r in requests)
+  dts = _out_dtypes(out_dtype, len(requests))
+  if dts is not None and tiered:
+    return _converted(find_combine_ragged_many(requests, return_launches), dts, return_launches)
 
   def fill(e, i):
     req = requests[i]
@@ -1612,16 +1684,18 @@ def find_combine_ragged_many(requests, return_launches=False):
     fill_id = req[6] if len(req) > 6 else None
     default_row = req[7] if len(req) > 7 else None
     table = _pooled_owner(e, table, tiered)
-    rs, ids, w, flags, fill_key, d, out = table._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row)
+    rs, ids, w, flags, fill_key, d, out = table._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row,
+                                                                          dts[i] if dts else None)
     outs.append(out)
     e.combiner = int(combiner)
     e.n_rows, e.row_splits = rs.numel() - 1, rs.data_ptr()
     e.nnz, e.ids, e.weights = ids.numel(), ids.data_ptr(), (w.data_ptr() if w is not None else None)
     e.flags, e.reserved, e.fill_id = flags, 0, fill_key
-    e.default_row, e.out = d.data_ptr(), out.data_ptr()
+    e.default_row, e.out = d.data_ptr(), (_rows_out(out) if dts else out.data_ptr())
     return rs, ids, w, d
 
   c_name, desc_type = (("tfra_multi_tier_find_combine_ragged", _capi.TierFindCombineRaggedDesc) if tiered else
+                       ("tfra_multi_find_combine_ragged_typed", _capi.FindCombineRaggedTypedDesc) if dts else
                        ("tfra_multi_find_combine_ragged", _capi.FindCombineRaggedDesc))
   launches = _grouped_call(c_name, desc_type, "find_combine_ragged_many", [r[0] for r in requests], fill)
   return (outs, launches) if return_launches else outs

@@ -15,7 +15,7 @@ partition -> per-shard table op -> stitch, the partition/stitch being device ker
 import torch
 
 from . import device_ops, table_ops
-from ._args import _as_device, _score_filter
+from ._args import _as_device, _out_dtype, _score_filter
 from .table_ops import CuckooHashTable, HkvHashTable, HkvEvictStrategy, SparsePlan, TieredHashTable
 
 
@@ -345,19 +345,25 @@ class Variable:
       return None
     return self.initializer([n, self.dim]).to(device=device, dtype=self.value_dtype)
 
-  def lookup(self, keys, return_exists=False, name=None):
-    """PY/dynamic_embedding_variable.py:933-986"""
-    return self._lookup_through("lookup", keys, return_exists, return_exists)
+  def lookup(self, keys, return_exists=False, name=None, out_dtype=None):
+    """PY/dynamic_embedding_variable.py:933-986.  out_dtype: the rows in float32 / float16 / bfloat16 instead of the value dtype,
+    bit for bit `lookup(...).to(out_dtype)`: every plain shard converts in its lookup's kernel (tfra_table_find_typed; the
+    conversion commutes with the stitching), a tiered shard's rows are converted behind its call.  The defaults stay in the value dtype."""
+    return self._lookup_through("lookup", keys, return_exists, return_exists, _out_dtype(out_dtype))
 
-  def _lookup_through(self, method, keys, shard_exists, return_exists):
+  def _lookup_through(self, method, keys, shard_exists, return_exists, out_dtype=None):
     """The body of `lookup` and `lookup_or_insert`: every shard's `method` ("lookup" or "find_or_insert") over the shard's keys and
     its defaults — one draw of the callable initializer per shard, else None —, asked for exists when shard_exists, and the
     results stitched back into batch order."""
     keys, perm, _, shards = self._fan_out(keys)
     vals, exs = [], []
     for t, k in shards:
+      typed = out_dtype is not None and not isinstance(t, TieredHashTable)   # (the typed lookups: `lookup` on a plain shard)
+      kw = {"out_dtype": out_dtype} if typed else {}
       r = getattr(t, method)(k, dynamic_default_values=self._create_default_values_by_initializer(k.numel(), t._device),
-                             return_exists=shard_exists)
+                             return_exists=shard_exists, **kw)
+      if out_dtype is not None and not typed:   # a tiered shard: its calls are not typed, the rows are converted
+        r = (r[0].to(out_dtype), r[1]) if shard_exists else r.to(out_dtype)
       if shard_exists:
         vals.append(r[0])
         exs.append(r[1])
@@ -433,12 +439,17 @@ class Variable:
     return (self.init_on_lookup == "pooled" and callable(self.initializer) and self.shard_num == 1 and
             self.value_dtype in PLANNED_VALUE_DTYPES and self.dim % 4 == 0 and self.dim <= 256)
 
-  def lookup_combined(self, ids, seg, weights, combiner, n_rows, name=None):
+  def lookup_combined(self, ids, seg, weights, combiner, n_rows, name=None, out_dtype=None):
     """The forward of embedding_lookup_sparse as one pooled read (tfra_table_find_combine): [n_rows, dim] float32,
     out[r] = combiner over the entries p with seg[p] == r, in input order, of weights[p] * (row of ids[p], the default row on a
     miss).  seg ascending; weights None = all 1; combiner "sum" / "mean" / "sqrtn".  Bit-identical to
-    unique -> lookup -> device_ops.sparse_segment_combine, without the unique pass and its host read.  Never inserts."""
+    unique -> lookup -> device_ops.sparse_segment_combine, without the unique pass and its host read.  Never inserts.
+    out_dtype: the result in float32 / float16 / bfloat16, rounded in the lookup's kernel (tfra_table_find_combine_typed; a tier
+    converts behind its call): bit for bit `lookup_combined(...).to(out_dtype)`."""
     t, ids = self._combined_operands(ids, ragged=False)
+    if _out_dtype(out_dtype) is not None:
+      return _pooled_reader(t).find_combine_typed(ids, seg, weights, device_ops.COMBINERS[combiner], n_rows, t._default_value,
+                                                  out_dtype=out_dtype)
     return _pooled_reader(t).find_combine(ids, seg, weights, device_ops.COMBINERS[combiner], n_rows, t._default_value)
 
   def admit_entries(self, entry_ids):
@@ -485,12 +496,15 @@ class Variable:
                                    ("lookup_combined", "embedding_lookup_sparse")))
     return self._tables[0], torch.as_tensor(ids, device=self._primary).reshape(-1)
 
-  def lookup_combined_ragged(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, name=None):
+  def lookup_combined_ragged(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, name=None, out_dtype=None):
     """`lookup_combined` over a ragged batch (tfra_table_find_combine_ragged): [n_rows, dim] float32, row r combining the entries
     [row_splits[r], row_splits[r + 1]) — bit-identical to `lookup_combined` on the row ids the splits stand for, in one launch.
     prune / fill_id: safe_embedding_lookup_sparse's pruning by weight and its default_id (`_DeviceTable.find_combine_ragged`).
-    Under `can_lookup_combined()`'s conditions.  Never inserts; nothing is read on the host."""
+    Under `can_lookup_combined()`'s conditions.  Never inserts; nothing is read on the host.  out_dtype: as `lookup_combined`'s."""
     t, ids = self._combined_operands(ids, ragged=True)
+    if _out_dtype(out_dtype) is not None:
+      return _pooled_reader(t).find_combine_ragged(row_splits, ids, weights, device_ops.COMBINERS[combiner], prune=prune,
+                                                   fill_id=fill_id, default_row=t._default_value, out_dtype=out_dtype)
     return _pooled_reader(t).find_combine_ragged(row_splits, ids, weights, device_ops.COMBINERS[combiner], prune=prune,
                                                  fill_id=fill_id, default_row=t._default_value)
 
@@ -795,10 +809,12 @@ class TrainableWrapper:
   """The local [N,dim] "shadow" of the rows of one lookup (PY/embedding_weights.py:38-540):
   refilled from the table on read (`prefetch_values`), written back by `update_op`."""
 
-  def __init__(self, params, ids, max_norm=None, plan_writeback=False):
+  def __init__(self, params, ids, max_norm=None, plan_writeback=False, out_dtype=None):
+    """out_dtype: the first read goes through the typed lookup where the route has one (`prefetch_values`)."""
     self.params = params
     self.ids = ids
     self.max_norm = max_norm
+    self._out_dtype = out_dtype
     self._values = None
     self.exists = None
     self.plan = _plan_at_lookup(params, ids) if plan_writeback else None
@@ -825,7 +841,10 @@ class TrainableWrapper:
     elif self.params.admits_on_lookup() and self.ids.numel():
       r = self._lookup_admitting()
     else:
-      r = self.params.lookup(self.ids)
+      # (the typed lookup, embedding_lookup's out_dtype: only this route has one, and only unclipped — max_norm clips the value
+      # dtype's rows, bp_v2 keeps them for accum, an admitting lookup returns what it inserts; those are converted by the caller)
+      typed = self.__dict__.get("_out_dtype") if self.max_norm is None else None
+      r = self.params.lookup(self.ids) if typed is None else self.params.lookup(self.ids, out_dtype=typed)
     self._values = self.transform(r)
     return self._values
 
@@ -1059,8 +1078,13 @@ def _note_pruned(tw, sparse_weights, combiner):
   return tw
 
 
+def _as_out_dtype(result, out_dtype):
+  """A lookup's result in the caller's out_dtype (None: as it is): the conversion of the routes that have no typed lookup."""
+  return result if out_dtype is None or result.dtype == out_dtype else result.to(out_dtype)
+
+
 def embedding_lookup(params, ids, partition_strategy=None, name=None, validate_indices=None, max_norm=None,
-                     return_trainable=False, plan_writeback=False):
+                     return_trainable=False, plan_writeback=False, out_dtype=None):
   """PY/dynamic_embedding_variable.py:1362-1530.  A miss returns the initializer row and does NOT
   insert (keys enter the table on the optimizer write-back).
 
@@ -1068,19 +1092,26 @@ def embedding_lookup(params, ids, partition_strategy=None, name=None, validate_i
   Variable's second stream, so that it builds while the model's forward and backward run and `apply_gradients` finds it
   ready (no look-ahead into the next batch needed).  Opt-in: it pays when there is work between lookup and
   apply_gradients; back to back (bench shape, 131 072 ids) the extra Python — a stream context and three events — costs
-  more than the overlap gains: 96 us per step against 75 us for lookup + one-call apply_sparse."""
+  more than the overlap gains: 96 us per step against 75 us for lookup + one-call apply_sparse.
+
+  out_dtype: the embeddings in float32 / float16 / bfloat16 instead of the value dtype (a bfloat16 model over a float32 table),
+  bit for bit `embedding_lookup(...).to(out_dtype)`.  The plain lookup converts in its kernel (`Variable.lookup`); max_norm, bp_v2
+  and an admitting lookup (init_on_lookup) run as they do and their result is converted.  The wrapper, its plan and the
+  write-back are today's: the typed write-backs take the half gradient that comes back."""
   ids = torch.as_tensor(ids, device=params._primary)
-  tw = TrainableWrapper(params, ids.reshape(-1), max_norm=max_norm, plan_writeback=return_trainable and plan_writeback)
-  emb = tw.read_value().reshape(tuple(ids.shape) + (params.dim,))
+  tw = TrainableWrapper(params, ids.reshape(-1), max_norm=max_norm, plan_writeback=return_trainable and plan_writeback,
+                        out_dtype=_out_dtype(out_dtype))
+  emb = _as_out_dtype(tw.read_value(), out_dtype).reshape(tuple(ids.shape) + (params.dim,))
   return (emb, tw) if return_trainable else emb
 
 
 def embedding_lookup_unique(params, ids, partition_strategy=None, name=None, validate_indices=None, max_norm=None,
-                            return_trainable=False):
-  """PY/dynamic_embedding_ops.py:64-117: unique -> lookup -> gather."""
+                            return_trainable=False, out_dtype=None):
+  """PY/dynamic_embedding_ops.py:64-117: unique -> lookup -> gather.  out_dtype: `embedding_lookup`'s, on the unique rows (the
+  gather copies them)."""
   ids = torch.as_tensor(ids, device=params._primary)
   uniq, idx, _ = device_ops.unique(ids)
-  r = embedding_lookup(params, uniq, max_norm=max_norm, return_trainable=return_trainable)
+  r = embedding_lookup(params, uniq, max_norm=max_norm, return_trainable=return_trainable, out_dtype=out_dtype)
   ue, tw = r if return_trainable else (r, None)
   emb = device_ops.gather_rows(ue, idx).reshape(tuple(ids.shape) + (params.dim,))
   return (emb, tw) if return_trainable else emb
@@ -1110,14 +1141,18 @@ def _pooled_training(params, max_norm):
 
 def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=None, name="embedding_lookup_sparse",
                             combiner="mean", max_norm=None, return_trainable=False, num_rows=None, plan_writeback=False,
-                            _entries=None, _out_shape=None):
+                            _entries=None, _out_shape=None, out_dtype=None):
   """PY/dynamic_embedding_ops.py:120-293.  `sp_ids` = (indices[nnz,2] or row_ids[nnz], values[nnz]);
   `sp_weights` = matching weight values or None.  Segment combine sum / mean / sqrtn over rows.
 
   return_trainable: also returns a SparseTrainableWrapper; `DynamicEmbeddingOptimizer.apply_combined_gradients` applies the
   gradient of the result through it.  plan_writeback (with return_trainable): build the write-back plan over the entry ids
-  at lookup time, on the Variable's second stream (as embedding_lookup's plan_writeback)."""
+  at lookup time, on the Variable's second stream (as embedding_lookup's plan_writeback).
+
+  out_dtype: the result in float32 / float16 / bfloat16, bit for bit `embedding_lookup_sparse(...).to(out_dtype)`: the pooled
+  read rounds in its kernel (`Variable.lookup_combined`), the op chain's float32 result is converted.  The wrapper is today's."""
   _check_combiner(combiner)
+  _out_dtype(out_dtype)
   indices, ids = sp_ids
   indices = torch.as_tensor(indices, device=params._primary)
   seg = (indices[:, 0] if indices.dim() == 2 else indices).to(torch.int64)
@@ -1137,7 +1172,8 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=
     # admits them with drawn rows there, which is what lets it read here at all
     if return_trainable:
       params.admit_entries(e_ids)
-    out = params.lookup_combined(ids, seg, w, combiner, n)
+    out = params.lookup_combined(ids, seg, w, combiner, n) if out_dtype is None else params.lookup_combined(
+        ids, seg, w, combiner, n, out_dtype=out_dtype)
     if not return_trainable:
       return out
     return out, SparseTrainableWrapper(params, None, None, None, seg, w, combiner, n, shape, e_ids, e_seg, e_w, max_norm=max_norm,
@@ -1150,7 +1186,7 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=
     tw = None
     ue = _read_rows(params, uniq, max_norm)
   # gather + weights + segment combine fused in one kernel (reads the unique rows through idx)
-  out = device_ops.sparse_segment_combine(ue, idx, seg, w, combiner, n)
+  out = _as_out_dtype(device_ops.sparse_segment_combine(ue, idx, seg, w, combiner, n), out_dtype)
   return (out, tw) if return_trainable else out
 
 
@@ -1252,7 +1288,7 @@ def _wrap_grouped(device, params_list, members, outs, entry_ids, plan_writeback,
 
 def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None, combiner="mean", max_norm=None,
                                  return_trainable=False, num_rows=None, plan_writeback=False, _entries_list=None,
-                                 _out_shapes=None):
+                                 _out_shapes=None, out_dtype=None):
   """`embedding_lookup_sparse` of a LIST of variables (a many-table model's sparse features): result i is what
   `embedding_lookup_sparse(params_list[i], sp_ids_list[i], sp_weights_list[i], ...)` returns, bit for bit — with return_trainable
   the (result, SparseTrainableWrapper) pair, the wrapper built behind the pooled forward.  `combiner` and `num_rows` are scalars
@@ -1264,7 +1300,10 @@ def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None,
   takes `embedding_lookup_sparse` as it is, so no list is refused.  With return_trainable and plan_writeback the grouped members
   that a single lookup would give a plan (`_plan_at_lookup`'s rule, per variable) get theirs from ONE grouped build per device on
   one side stream (`_plans_at_lookup_many`: tfra_multi_sparse_plan_build).  Where num_rows is absent, the grouped variables' row counts
-  come from one host read per device, not one per table."""
+  come from one host read per device, not one per table.  out_dtype: one of float32 / float16 / bfloat16 for every result, as the
+  single form's: a group of plain tables is rounded in the grouped call's kernels (tfra_multi_find_combine_typed, the same launch
+  count), a group with a tiered member and every single-form member are converted."""
+  _out_dtype(out_dtype)
   n_t = len(params_list)
   if len(sp_ids_list) != n_t:
     raise ValueError("sp_ids_list: %d entries for %d tables" % (len(sp_ids_list), n_t))
@@ -1285,7 +1324,7 @@ def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None,
     if not pooled(params, max_norm):
       results[i] = embedding_lookup_sparse(params, sp_ids_list[i], weights[i], combiner=combiners[i], max_norm=max_norm,
                                            return_trainable=return_trainable, num_rows=rows[i], plan_writeback=plan_writeback,
-                                           _entries=entries[i], _out_shape=shapes[i])
+                                           _entries=entries[i], _out_shape=shapes[i], out_dtype=out_dtype)
       continue
     indices, ids = sp_ids_list[i]
     indices = torch.as_tensor(indices, device=params._primary)
@@ -1303,7 +1342,7 @@ def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None,
     for i, ids, seg, w in members:
       t = params_list[i]._tables[0]
       reqs.append((_pooled_reader(t), ids.reshape(-1), seg, w, device_ops.COMBINERS[combiners[i]], rows[i], t._default_value))
-    outs = table_ops.find_combine_many(reqs)
+    outs = table_ops.find_combine_many(reqs) if out_dtype is None else table_ops.find_combine_many(reqs, out_dtype=out_dtype)
     if not return_trainable:
       for (i, ids, seg, w), out in zip(members, outs):
         results[i] = out
@@ -1461,7 +1500,7 @@ def _safe_sparse_finish(params, res, rows, n, default_id, max_norm, lead):
     empty = torch.ones(n, dtype=torch.bool, device=res.device)
     empty[rows] = False
     d = _read_rows(params, torch.tensor([default_id], dtype=params.key_dtype, device=params._primary), max_norm).to(torch.float32)
-    res = torch.where(empty[:, None], d, res)
+    res = torch.where(empty[:, None], d.to(res.dtype), res)   # (res: float32, or the caller's out_dtype — the select commutes with it)
   if lead is not None:
     res = res.reshape(tuple(lead) + (res.shape[-1],))
   return res
@@ -1469,28 +1508,30 @@ def _safe_sparse_finish(params, res, rows, n, default_id, max_norm, lead):
 
 def safe_embedding_lookup_sparse(params, sp_ids, sparse_weights=None, combiner="mean", default_id=None,
                                  name="safe_embedding_lookup_sparse", partition_strategy=None, max_norm=None,
-                                 return_trainable=False, num_rows=None, plan_writeback=False):
+                                 return_trainable=False, num_rows=None, plan_writeback=False, out_dtype=None):
   """PY/dynamic_embedding_ops.py:296-430.  `sp_ids` = (indices[nnz, R], values[nnz][, dense_shape[R]]) — a
   SparseTensor of rank R >= 2 (or row ids [nnz] for rank 2).  Semantics of the reference, NOT of
   `tf.nn.safe_embedding_lookup_sparse`: ids are never pruned (any int64 is a legal key, negative ones too,
   T/dynamic_embedding_ops_test.py:1007-1050); entries with weight <= 0 are dropped unless combiner == "sum"
   (`_prune_invalid_weights`, :374-376); rows left without entries yield zeros, or the embedding of
   `default_id` (`sparse_fill_empty_rows`, :379-408); leading dims are flattened for the lookup and restored
-  on the result (:356-367, 411-424)."""
+  on the result (:356-367, 411-424).  out_dtype: `embedding_lookup_sparse`'s; the default_id row is converted the same way."""
   _check_combiner(combiner)
+  _out_dtype(out_dtype)
   rows, ids, w, n, entries, out_shape, lead = _safe_sparse_args(params, sp_ids, sparse_weights, combiner, default_id,
                                                                  return_trainable, num_rows)
   out = embedding_lookup_sparse(params, (rows, ids), w, combiner=combiner, max_norm=max_norm,
                                 return_trainable=return_trainable, num_rows=n, plan_writeback=plan_writeback,
-                                _entries=entries, _out_shape=out_shape)
+                                _entries=entries, _out_shape=out_shape, out_dtype=out_dtype)
   res, tw = out if return_trainable else (out, None)
   res = _safe_sparse_finish(params, res, rows, n, default_id, max_norm, lead)
   return (res, _note_pruned(tw, sparse_weights, combiner)) if return_trainable else res
 
 
 def safe_embedding_lookup_sparse_many(params_list, sp_ids_list, sparse_weights_list=None, combiner="mean", default_id=None,
-                                      max_norm=None, return_trainable=False, num_rows=None, plan_writeback=False):
-  """`safe_embedding_lookup_sparse` of a LIST of variables: result i is what the single form returns for table i, bit for bit.
+                                      max_norm=None, return_trainable=False, num_rows=None, plan_writeback=False, out_dtype=None):
+  """`safe_embedding_lookup_sparse` of a LIST of variables: result i is what the single form returns for table i, bit for bit
+  (out_dtype: one for every result, as `embedding_lookup_sparse_many`'s).
   `combiner`, `default_id` and `num_rows` are scalars or per-table lists.  The preprocessing is the single form's
   (`_safe_sparse_args_many`: all tables' kept lists and entry lists from one builder call and one host read per device); the
   lookups go through `embedding_lookup_sparse_many`, one grouped call per device for the variables the pooled forward serves.  Row counts that neither a dense_shape nor num_rows gives are read in one host read per device."""
@@ -1515,7 +1556,7 @@ def safe_embedding_lookup_sparse_many(params_list, sp_ids_list, sparse_weights_l
   outs = embedding_lookup_sparse_many(params_list, [(a[0], a[1]) for a in args], [a[2] for a in args], combiner=combiners,
                                       max_norm=max_norm, return_trainable=return_trainable, num_rows=[a[3] for a in args],
                                       plan_writeback=plan_writeback, _entries_list=[a[4] for a in args],
-                                      _out_shapes=[a[5] for a in args])
+                                      _out_shapes=[a[5] for a in args], out_dtype=out_dtype)
   results = []
   for i, (rows, ids, w, n, entries, out_shape, lead) in enumerate(args):
     res, tw = outs[i] if return_trainable else (outs[i], None)
