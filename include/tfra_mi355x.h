@@ -725,7 +725,14 @@ int tfra_step_driver_lookups_listed(const tfra_step_driver_t* d, uint64_t* out);
 
 /* -- front-end helpers (N1/N3 rows of SURVEY.md §8f) ------------------------------------- */
 
-/* Scratch for unique/partition; grows on demand, reusable across calls on one stream. */
+/* Scratch for unique/partition; grows on demand, reusable across calls on one stream.
+ * A workspace serves ONE call at a time and ONE stream: it is not internally locked (unlike a table), growing it frees the
+ * buffer the previous call's kernels were given (after a synchronise of the CURRENT call's stream only), and the persistent
+ * sets of tfra_unique / tfra_multi_unique alternate by a parity that a call flips on the host.  Two host threads must therefore
+ * never be inside the library with the same workspace — a caller with several threads keeps one workspace per thread and stream,
+ * or a lock of its own around every call it hands the workspace to (the table calls that take one included: the table's lock
+ * does not cover the workspace).  tfra_unique and tfra_multi_unique alone tolerate a change of stream between two calls (they
+ * chain the new stream behind the previous one with an event); every other workspace call assumes the stream of the last one. */
 typedef struct tfra_workspace tfra_workspace_t;
 int tfra_workspace_create(int device, tfra_workspace_t** out);
 int tfra_workspace_destroy(tfra_workspace_t* ws);

@@ -1,25 +1,49 @@
 """Device front-end ops that bracket the table calls (N1/N3 of SURVEY.md §8f), as torch-tensor
 functions over the C ABI: unique, gather, segment_sum, partition (+stitch)."""
 import ctypes
+import sys
+import threading
 
 import torch
 
 from .. import _capi
 from ._args import _grads_arg, _narrow_keys, _ptr, _stream, _wide_keys
 
-_WS = {}
+class _Workspaces(dict):
+  """One thread's workspaces, {(device index, stream): handle}; destroyed when the thread's storage goes (tfra_workspace_destroy
+  synchronises the device first, so kernels the thread left queued have finished with the scratch)."""
+
+  def __del__(self):
+    if sys.is_finalizing():   # at interpreter exit the workspaces go with the process, as they always did
+      return
+    for h in self.values():
+      try:
+        _capi.lib().tfra_workspace_destroy(h)
+      except Exception:
+        pass
+
+
+_WS = threading.local()   # .handles: the calling thread's _Workspaces
 
 
 def _workspace(device):
-  """One scratch workspace per (device, CURRENT STREAM): a workspace holds state that persists from call to call (tfra_unique's
-  two self-emptying hash sets, their parity and generation), so two streams must never share one — calls on different
-  streams are not ordered with each other."""
+  """One scratch workspace per (HOST THREAD, device, CURRENT STREAM).  A tfra_workspace serves one call at a time and one stream
+  (include/tfra_mi355x.h, tfra_workspace_create): it has no lock of its own, a call that needs more scratch frees the buffer
+  after synchronising its OWN stream only, and the persistent sets of tfra_unique / tfra_multi_unique alternate by a parity that
+  a call flips on the host.  ctypes releases the GIL for the length of a C call, so two Python threads on one stream (the
+  default stream, say) would otherwise be inside the library with the same handle: hence the thread in the key.  Per stream,
+  because a workspace's scratch and staging ring are reused from call to call without any event: only the stream's own order
+  keeps the next call's kernels behind the previous call's.  (tfra_unique and tfra_multi_unique alone do chain a change of stream
+  with an event; nothing here relies on it.)"""
+  ws = getattr(_WS, "handles", None)
+  if ws is None:
+    ws = _WS.handles = _Workspaces()
   key = (device.index, _stream(device).value)
-  if key not in _WS:
+  if key not in ws:
     h = ctypes.c_void_p()
     _capi.call("tfra_workspace_create", device.index, ctypes.byref(h))
-    _WS[key] = h
-  return _WS[key]
+    ws[key] = h
+  return ws[key]
 
 
 def unique(ids, ordered=True):

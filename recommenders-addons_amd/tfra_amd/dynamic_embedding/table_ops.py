@@ -1817,7 +1817,7 @@ def build_plans_many(plans, ids_list, return_launches=False):
   Around the call each plan gets what `SparsePlan.build` does for it: the ids as a contiguous int64 tensor kept alive on the plan,
   the wait for the plan's last use, `record_stream`, and the `_built` event behind the call.  All plans live on one device, have a
   dim > 0 (the assign-only plan is one kernel already) and occur once.  The call's workspace is `device_ops._workspace(device)`,
-  which is keyed by the current stream: a build on a side stream has a workspace of its own and never shares the staging ring or
+  which is keyed by the calling thread and the current stream: a build on a side stream has a workspace of its own and never shares the staging ring or
   the scratch of the main stream's grouped calls (`find_combine_many`, `apply_planned_combined_many`), which may be in flight at
   the same time.  Returns the plans (with return_launches: also the number of kernel launches the call enqueued — it does not grow
   with the list)."""

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import oracle
+from tests.test_gpu_int32_surface import SLEEP_CYCLES
 
 pytestmark = pytest.mark.gpu
 DIM = 8
@@ -25,7 +26,8 @@ def _table(de, torch, name, **kw):
 
 
 def test_two_streams_are_chained_by_the_library(env):
-  """insert on stream A, find on stream B, no caller-side synchronisation: the find sees the insert."""
+  """insert on stream A, find on stream B, no caller-side synchronisation: the find sees the insert.  Every other round a long
+  kernel holds stream A back in front of its call, so that a missing wait shows even when the kernels are short."""
   torch, de = env
   t = _table(de, torch, "conc_streams")
   sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
@@ -35,10 +37,14 @@ def test_two_streams_are_chained_by_the_library(env):
   torch.cuda.synchronize()
   for rep in range(5):
     with torch.cuda.stream(sa):
+      if rep % 2:
+        torch.cuda._sleep(SLEEP_CYCLES)
       t.insert(keys, vals + rep)
     with torch.cuda.stream(sb):
       got, ex = t.lookup(keys, return_exists=True)
     with torch.cuda.stream(sa):
+      if rep % 2:
+        torch.cuda._sleep(SLEEP_CYCLES)
       t.remove(keys[: n // 2])
     with torch.cuda.stream(sb):
       got2, ex2 = t.lookup(keys, return_exists=True)
