@@ -901,8 +901,10 @@ int tfra_reduce_by_key(tfra_workspace_t* ws, size_t n, const int64_t* ids, int d
  *    8-byte aligned instead of 16).  Addressing: the kernels address a half grad_out with 32-bit ELEMENT offsets, so a typed call
  *    on halves refuses n_rows * dim >= 2^32 with TFRA_ERR_UNSUPPORTED (the twin's n_rows < 2^30 holds besides); it does not widen
  *    the addresses.
- *    Not typed: tfra_table_apply_optimizer, the step drivers, the weight-gradient calls (the *_backprop_weights family)
- *    and tfra_sparse_segment_combine_backprop: they take float32. */
+ *    The weight-gradient calls are typed too: the seven *_backprop_weights_typed calls, declared behind their
+ *    twins below.  Their contract is the same sentence over grad_out, with GO32[r, c] = f32(grad_out[r, c]) * s formed BEFORE the
+ *    dot product d_p = sum_c GO32[r, c] * x_p[c]; dw_out stays float32.
+ *    Not typed: tfra_table_apply_optimizer, the step drivers and tfra_sparse_segment_combine_backprop: they take float32. */
 typedef struct {
   const void*  grads;    /* [n, dim] row-major in `dtype`; float32: 16-byte aligned, halves: 8-byte aligned */
   int32_t      dtype;    /* TFRA_F32 | TFRA_F16 | TFRA_BF16 */
@@ -1386,6 +1388,95 @@ typedef struct {
 int tfra_multi_find_combine_ragged_backprop_weights(tfra_workspace_t* ws, size_t n_tables,
                                                     const tfra_find_combine_ragged_wgrad_desc* descs,
                                                     uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
+
+/* -- Half-precision grad_out in the weight gradients: the seven calls above that read grad_out [n_rows, dim], taking
+ *    it as a tfra_grads record (with the half-precision gradients, above) — the float16 / bfloat16 matrix a half model hands to
+ *    tfra_table_apply_planned_combined_typed serves the weight gradient as it is, with no conversion pass.  Additive; ABI version 1.
+ *    Contract: a typed weight-gradient call equals its untyped twin, bit for bit, given the float32 matrix
+ *        GO32[r, c] = f32(grad_out[r, c]) * s
+ *    with f32() and s as defined for tfra_grads: the up-cast is exact (subnormals kept, a NaN stays a NaN), s = *d_scale is read by
+ *    the kernel on the stream, the product is ONE float32 multiplication rounded on its own, d_scale == NULL equals s = 1.  The
+ *    product is formed BEFORE the dot product: d_p = sum_c GO32[r, c] * x_p[c], in the column order documented for the twin.
+ *    Everything behind GO32 is the twin's: the probe, default_row on a miss, the tier's row source, PRUNE / FILL, the clamping of
+ *    row_splits, the second pass of mean / sqrtn, the memsets and the bounds step, the locks, the launches' shapes and number.
+ *    dw_out stays float32 [nnz].
+ *    dtype == TFRA_F32 with d_scale == NULL forwards to the untyped function: the same code, the same launches.
+ *    Refused before anything is enqueued and before the table or tier handle is looked at, dw_out untouched (tfra_last_error()
+ *    begins as the twin's messages begin, with _typed appended to the name):
+ *      TFRA_ERR_INVALID      a NULL grad_out or grad_out->grads; reserved != 0; a dtype other than the three
+ *      TFRA_ERR_UNSUPPORTED  half gradients that are not 8-byte aligned; a float32 matrix with a scale
+ *    then everything the twin checks, with the twin's codes and wording; a half grad_out needs 8-byte alignment where the float
+ *    one needs 16 (with dim % 4 == 0 every row then is 8-byte aligned, odd rows at dim 4 included).
+ *    Size limits: none beyond the twin's.  The row base grad_out + r * dim is formed in 64 bits, as the float one is: the
+ *    n_rows * dim < 2^32 rule of the typed combined write-backs does NOT apply here.
+ *    tfra_sparse_segment_combine_backprop_weights_typed keeps "any dim > 0": its vector arm runs when dim % 4 == 0 and rows is
+ *    16-byte aligned (the half matrix is 8-byte aligned by the record's check), its element-wise arm otherwise (rows of the half
+ *    matrix then start at 2-byte multiples); both give the twin's bits, and the bits of the pooled calls where both apply.
+ *                                                         (tests/test_wgrad_half_abi.py, tests/test_gpu_wgrad_half.py) */
+int tfra_table_find_combine_backprop_weights_typed(tfra_table_t* t, tfra_workspace_t* ws, size_t nnz, const int64_t* ids,
+                                                   const int64_t* seg, const float* weights, int combiner, size_t n_rows,
+                                                   const void* default_row, const tfra_grads* grad_out, float* dw_out,
+                                                   tfra_stream_t stream);
+int tfra_table_find_combine_ragged_backprop_weights_typed(tfra_table_t* t, size_t n_rows, const int64_t* row_splits, size_t nnz,
+                                                          const int64_t* ids, const float* weights, int combiner, uint32_t flags,
+                                                          int64_t fill_id, const void* default_row, const tfra_grads* grad_out,
+                                                          float* dw_out, tfra_stream_t stream);
+int tfra_tier_find_combine_backprop_weights_typed(tfra_tier_t* tier, tfra_workspace_t* ws, size_t nnz, const int64_t* ids,
+                                                  const int64_t* seg, const float* weights, int combiner, size_t n_rows,
+                                                  const void* default_row, const tfra_grads* grad_out, float* dw_out,
+                                                  tfra_stream_t stream);
+int tfra_tier_find_combine_ragged_backprop_weights_typed(tfra_tier_t* tier, size_t n_rows, const int64_t* row_splits, size_t nnz,
+                                                         const int64_t* ids, const float* weights, int combiner, uint32_t flags,
+                                                         int64_t fill_id, const void* default_row, const tfra_grads* grad_out,
+                                                         float* dw_out, tfra_stream_t stream);
+int tfra_sparse_segment_combine_backprop_weights_typed(tfra_workspace_t* ws, size_t nnz, int dim, const float* rows,
+                                                       const int32_t* idx, const tfra_grads* grad_out, const int64_t* seg,
+                                                       const float* weights, int combiner, size_t n_rows, float* dw_out,
+                                                       tfra_stream_t stream);
+/* The grouped forms: tfra_multi_find_combine[_ragged]_backprop_weights with each descriptor's grad_out as a tfra_grads record.
+ * descs[i].dw_out is bit-identical to the single typed call on the descriptor.  Descriptors of all three formats, with and without
+ * a scale, may stand in one list; each record is checked as the single typed call checks it, before the descriptor's table or tier
+ * is looked at, every descriptor before anything is enqueued; a refused list writes nothing and the message names the
+ * descriptor's index ("multi_find_combine[_ragged]_backprop_weights_typed: descriptor <i>: ...").  A list whose descriptors are
+ * all float32 without a scale runs the untyped call's code and launches — with ONE difference in what it accepts: a record's
+ * `grads` must not be NULL, whatever n_rows is (the single typed calls' "null gradients"), where the untyped grouped call takes
+ * a NULL grad_out for a descriptor without rows.  Everything else is the untyped grouped call's; the zero-fill / bounds launch
+ * is unchanged.
+ * Float-or-half is one more axis of the launch classes (float16 and bfloat16 share a launch: the format is a wave-uniform value
+ * beside the descriptor's record).  *launches_out (optional, host): the kernel launches enqueued =
+ *     (1 if any descriptor has nnz > 0, else 0)
+ *     + (the distinct (tiered or not, value dtype, NCH[, pruning or not], float-or-half) classes among the descriptors with
+ *        nnz > 0 and n_rows > 0):  at most 36 in the tuple form, 72 in the ragged form.
+ * A list that is all half or all float has the untyped call's count.                      (tests/test_gpu_wgrad_half_many.py) */
+typedef struct {
+  uint32_t struct_size;      /* = sizeof(tfra_find_combine_wgrad_typed_desc) */
+  int32_t  combiner;         /* 0 sum | 1 mean | 2 sqrtn */
+  tfra_table_t* table;       /* exactly ONE of table / tier is non-NULL */
+  tfra_tier_t*  tier;
+  size_t nnz; const int64_t* ids; const int64_t* seg; const float* weights;   /* weights may be NULL */
+  size_t n_rows; const void* default_row;
+  tfra_grads grad_out;       /* [n_rows, dim] in grad_out.dtype, with its optional device scale */
+  float* dw_out;             /* [nnz] float32 */
+} tfra_find_combine_wgrad_typed_desc;
+int tfra_multi_find_combine_backprop_weights_typed(tfra_workspace_t* ws, size_t n_tables,
+                                                   const tfra_find_combine_wgrad_typed_desc* descs,
+                                                   uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
+
+typedef struct {
+  uint32_t struct_size;      /* = sizeof(tfra_find_combine_ragged_wgrad_typed_desc) */
+  int32_t  combiner;         /* 0 sum | 1 mean | 2 sqrtn */
+  tfra_table_t* table;       /* exactly ONE of table / tier is non-NULL */
+  tfra_tier_t*  tier;
+  size_t n_rows; const int64_t* row_splits;                                   /* [n_rows + 1] */
+  size_t nnz; const int64_t* ids; const float* weights;                       /* weights may be NULL */
+  uint32_t flags; uint32_t reserved;                                          /* TFRA_RAGGED_*; reserved = 0 */
+  int64_t fill_id; const void* default_row;                                   /* fill_id is ignored */
+  tfra_grads grad_out;       /* [n_rows, dim] in grad_out.dtype, with its optional device scale */
+  float* dw_out;             /* [nnz] float32 */
+} tfra_find_combine_ragged_wgrad_typed_desc;
+int tfra_multi_find_combine_ragged_backprop_weights_typed(tfra_workspace_t* ws, size_t n_tables,
+                                                          const tfra_find_combine_ragged_wgrad_typed_desc* descs,
+                                                          uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
 
 /* The combined write-backs of MANY tables in one call (a 26-table model's backward is 26 tfra_table_apply_planned_combined calls =
  * ~160 enqueues otherwise): table i ends bit-identical to tfra_table_apply_planned_combined(table, opt, plan, grad_out, seg,

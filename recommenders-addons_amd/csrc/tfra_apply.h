@@ -1,7 +1,6 @@
 // What the single-table write-backs (tfra_apply.hip) and the grouped one (tfra_apply_many.hip) share on the host, ONE copy each:
 // the sums' launch ladder by row width (with_nch) and the argument checks of a planned and of a combined write-back
-// (check_apply_planned, check_apply_combined), which the single call and every descriptor of the grouped call run; and what a
-// tfra_grads record must satisfy (check_typed), for the *_typed calls and for tfra_table_fetch_planned (tfra_rows.hip).
+// (check_apply_planned, check_apply_combined), which the single call and every descriptor of the grouped call run.
 // File-local in each unit (static), as keys_of of tfra_plan.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -32,21 +31,7 @@ static Check check_rounding(const Table* t) {
   return Check{};
 }
 
-// What a tfra_grads itself must satisfy, before anything is enqueued.  forward: float32 without a scale — the untyped call, as it is.
-static Check check_typed(const tfra_grads* g, bool* forward) {
-  *forward = false;
-  if (!g || !g->grads) return refuse(TFRA_ERR_INVALID, "null gradients");
-  if (g->reserved != 0) return refuse(TFRA_ERR_INVALID, "tfra_grads.reserved must be 0");
-  if (g->dtype != TFRA_F32 && g->dtype != TFRA_F16 && g->dtype != TFRA_BF16)
-    return refuse(TFRA_ERR_INVALID, "tfra_grads.dtype must be float32, float16 or bfloat16");
-  if (g->dtype == TFRA_F32) {
-    if (g->d_scale) return refuse(TFRA_ERR_UNSUPPORTED, "float32 gradients take no scale (loss scaling belongs to float16)");
-    *forward = true;
-  } else if ((uintptr_t)g->grads & 7) {
-    return refuse(TFRA_ERR_UNSUPPORTED, "half gradients must be 8-B aligned");
-  }
-  return Check{};
-}
+// (What a tfra_grads itself must satisfy, check_typed, stands in tfra_many.h beside Check: the typed weight gradients use it too.)
 
 // The checks of a planned write-back: apply_planned_impl's, whoever calls it, and behind check_apply_combined those of a
 // descriptor of tfra_multi_apply_planned_combined.  active: the plan holds ids.  grad_mask: 15 for a float gradient matrix, 7 for

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <string>
 
 #include "../../include/tfra_mi355x.h"
 #include "tfra_combine_device.h"
@@ -12,6 +13,7 @@
 #include "tfra_frontend.h"
 #include "tfra_host.h"
 #include "tfra_many.h"
+#include "tfra_optim_device.h"
 
 using namespace tfra;
 
@@ -85,6 +87,51 @@ __global__ __launch_bounds__(256) void seg_combine_wgrad_kernel(size_t n_rows, i
         wgrad_dot4(d, *reinterpret_cast<const float4*>(G + c), *reinterpret_cast<const float4*>(row + c));
       } else {
         for (int k = c; k < c + 4 && k < dim; ++k) wgrad_dot1(d, G[k], row[k]);
+      }
+    }
+    d = wgrad_reduce16(d);
+    wgrad_s(s, x, d);
+    if (sub == ((p - b) & 15)) dw[p] = d;
+  }
+  if (combiner == 0) return;
+  for (int p = b + sub; p < e; p += 16) dw[p] = wgrad_finish(dw[p], w ? w[p] : 1.f, s, wsum, combiner);
+}
+
+// The same over a float16 / bfloat16 grad_out (tfra_sparse_segment_combine_backprop_weights_typed): the body above
+// with GO32[r, c] = f32(grad_out[r, c]) * s formed at its load of G and nothing else changed — a second kernel and not a template
+// axis of the first, whose name and code stay as they are.  VEC4: one 8-byte load per lane and chunk, up-cast by load_stored4 (the
+// helpers GradHalf uses); otherwise element by element (load_stored), any dim and 2-byte aligned rows.  is_bf16 is a kernel
+// argument (wave-uniform), *d_scale is read once per group at a uniform address; nullptr: 1.0f.
+template <bool VEC4>
+__global__ __launch_bounds__(256) void seg_combine_wgrad_half_kernel(size_t n_rows, int dim, const float* __restrict__ rows,
+                                                                     const int* __restrict__ idx, const float* __restrict__ w,
+                                                                     const int* __restrict__ start_end, int combiner,
+                                                                     const unsigned short* __restrict__ grad_out, float* dw,
+                                                                     const float* __restrict__ d_scale, int is_bf16) {
+  const int sub = threadIdx.x & 15;
+  const size_t r = (((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4);
+  if (r >= n_rows) return;
+  const int b = start_end[r], e = start_end[n_rows + r];
+  if (b >= e) return;
+  const float wsum = combiner == 0 ? 0.f : comb_wsum(w, b, e, combiner);
+  const float gs = d_scale ? *d_scale : 1.f;
+  const unsigned short* G = grad_out + r * (size_t)dim;
+  float s = 0.f;
+  for (int p = b; p < e; ++p) {
+    const float x = w ? w[p] : 1.f;
+    const float* row = rows + (size_t)idx[p] * dim;
+    float d = 0.f;
+    for (int c = sub * 4; c < dim; c += 64) {
+      if (VEC4) {
+        const uint2 raw = *reinterpret_cast<const uint2*>(G + c);
+        float4 g = is_bf16 ? load_stored4<TFRA_BF16>(raw) : load_stored4<TFRA_F16>(raw);
+        g.x *= gs; g.y *= gs; g.z *= gs; g.w *= gs;
+        wgrad_dot4(d, g, *reinterpret_cast<const float4*>(row + c));
+      } else {
+        for (int k = c; k < c + 4 && k < dim; ++k) {
+          const float g = (is_bf16 ? bits_to_float<TFRA_BF16>(G[k]) : bits_to_float<TFRA_F16>(G[k])) * gs;
+          wgrad_dot1(d, g, row[k]);
+        }
       }
     }
     d = wgrad_reduce16(d);
@@ -204,28 +251,59 @@ int tfra_sparse_segment_combine_backprop(tfra_workspace_t* ws, size_t nnz, int d
   return TFRA_OK;
 }
 
-int tfra_sparse_segment_combine_backprop_weights(tfra_workspace_t* ws, size_t nnz, int dim, const float* rows, const int32_t* idx,
-                                                 const float* grad_out, const int64_t* seg, const float* weights, int combiner,
-                                                 size_t n_rows, float* dw_out, tfra_stream_t stream) {
+// tfra_sparse_segment_combine_backprop_weights (hg == nullptr) and its typed twin over a half grad_out (hg, checked by
+// check_typed: not NULL, 8-byte aligned; grad_out is not read then): one function, `who` names the caller in the refusals
+static int seg_combine_wgrad_impl(const std::string& who, tfra_workspace_t* ws, size_t nnz, int dim, const float* rows, const int32_t* idx,
+                                  const float* grad_out, const tfra_grads* hg, const int64_t* seg, const float* weights, int combiner,
+                                  size_t n_rows, float* dw_out, tfra_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (!ws || dim <= 0 || combiner < 0 || combiner > 2) return set_error(TFRA_ERR_INVALID, "segment_combine_backprop_weights: bad argument");
+  if (!ws || dim <= 0 || combiner < 0 || combiner > 2) return set_error(TFRA_ERR_INVALID, who + ": bad argument");
   HIP_TRY_AS("hipSetDevice(ws->device)", on_device(ws->device));
   if (nnz == 0) return TFRA_OK;
-  if (!rows || !idx || !seg || !dw_out || (n_rows && !grad_out)) return set_error(TFRA_ERR_INVALID, "segment_combine_backprop_weights: null buffer");
-  if (nnz >= (1ULL << 31) || n_rows >= (1ULL << 30)) return set_error(TFRA_ERR_INVALID, "segment_combine_backprop_weights: too large");
+  if (!rows || !idx || !seg || !dw_out || (n_rows && !grad_out && !hg)) return set_error(TFRA_ERR_INVALID, who + ": null buffer");
+  if (nnz >= (1ULL << 31) || n_rows >= (1ULL << 30)) return set_error(TFRA_ERR_INVALID, who + ": too large");
   if (((uintptr_t)seg & 7) || (((uintptr_t)weights | (uintptr_t)idx | (uintptr_t)rows | (uintptr_t)grad_out | (uintptr_t)dw_out) & 3))
-    return set_error(TFRA_ERR_UNSUPPORTED, "segment_combine_backprop_weights: misaligned buffer");
+    return set_error(TFRA_ERR_UNSUPPORTED, who + ": misaligned buffer");
   HIP_TRY(hipMemsetAsync(dw_out, 0, nnz * sizeof(float), s));   // entries in no row: 0
   if (n_rows == 0) return TFRA_OK;
   int* se;
   dim3 grid;
   int rc = comb_rows_head(ws, s, nnz, seg, n_rows, se, grid);
   if (rc) return rc;
+  if (hg) {   // the vector arm: rows as the twin wants them, the half matrix 8-byte aligned (check_typed) and dim % 4 == 0
+    const unsigned short* g = (const unsigned short*)hg->grads;
+    const int bf = hg->dtype == TFRA_BF16;
+    if (dim % 4 == 0 && (uintptr_t)rows % 16 == 0)
+      seg_combine_wgrad_half_kernel<true><<<grid, 256, 0, s>>>(n_rows, dim, rows, idx, weights, se, combiner, g, dw_out, hg->d_scale, bf);
+    else
+      seg_combine_wgrad_half_kernel<false><<<grid, 256, 0, s>>>(n_rows, dim, rows, idx, weights, se, combiner, g, dw_out, hg->d_scale, bf);
+    HIP_TRY(hipGetLastError());
+    return TFRA_OK;
+  }
   const bool vec4 = dim % 4 == 0 && (((uintptr_t)rows | (uintptr_t)grad_out) % 16 == 0);
   if (vec4) seg_combine_wgrad_kernel<true><<<grid, 256, 0, s>>>(n_rows, dim, rows, idx, weights, se, combiner, grad_out, dw_out);
   else seg_combine_wgrad_kernel<false><<<grid, 256, 0, s>>>(n_rows, dim, rows, idx, weights, se, combiner, grad_out, dw_out);
   HIP_TRY(hipGetLastError());
   return TFRA_OK;
+}
+
+int tfra_sparse_segment_combine_backprop_weights(tfra_workspace_t* ws, size_t nnz, int dim, const float* rows, const int32_t* idx,
+                                                 const float* grad_out, const int64_t* seg, const float* weights, int combiner,
+                                                 size_t n_rows, float* dw_out, tfra_stream_t stream) {
+  return seg_combine_wgrad_impl("segment_combine_backprop_weights", ws, nnz, dim, rows, idx, grad_out, nullptr, seg, weights, combiner,
+                                n_rows, dw_out, stream);
+}
+
+int tfra_sparse_segment_combine_backprop_weights_typed(tfra_workspace_t* ws, size_t nnz, int dim, const float* rows, const int32_t* idx,
+                                                       const tfra_grads* grad_out, const int64_t* seg, const float* weights,
+                                                       int combiner, size_t n_rows, float* dw_out, tfra_stream_t stream) {
+  bool forward;
+  if (const Check c = check_typed(grad_out, &forward); c.code) return report("segment_combine_backprop_weights_typed: ", c);
+  if (forward)
+    return tfra_sparse_segment_combine_backprop_weights(ws, nnz, dim, rows, idx, (const float*)grad_out->grads, seg, weights, combiner,
+                                                        n_rows, dw_out, stream);
+  return seg_combine_wgrad_impl("segment_combine_backprop_weights_typed", ws, nnz, dim, rows, idx, nullptr, grad_out, seg, weights,
+                                combiner, n_rows, dw_out, stream);
 }
 
 }  // extern "C"

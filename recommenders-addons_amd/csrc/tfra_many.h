@@ -208,4 +208,22 @@ inline Check refuse(int code, const char* msg) { return Check{code, msg, false};
 inline Check nothing_to_do() { return Check{TFRA_OK, "", false}; }
 inline int report(const std::string& who, const Check& c) { return c.msg.empty() ? c.code : set_error(c.code, who + c.msg); }
 
+// What a tfra_grads itself must satisfy, before anything is enqueued: ONE copy for the typed write-backs (tfra_apply.hip,
+// tfra_apply_many.hip), tfra_table_fetch_planned (tfra_rows.hip) and the typed weight gradients (tfra_wgrad*.hip, tfra_tierwgrad.hip,
+// tfra_combine.hip).  forward: float32 without a scale — the untyped call, as it is.
+inline Check check_typed(const tfra_grads* g, bool* forward) {
+  *forward = false;
+  if (!g || !g->grads) return refuse(TFRA_ERR_INVALID, "null gradients");
+  if (g->reserved != 0) return refuse(TFRA_ERR_INVALID, "tfra_grads.reserved must be 0");
+  if (g->dtype != TFRA_F32 && g->dtype != TFRA_F16 && g->dtype != TFRA_BF16)
+    return refuse(TFRA_ERR_INVALID, "tfra_grads.dtype must be float32, float16 or bfloat16");
+  if (g->dtype == TFRA_F32) {
+    if (g->d_scale) return refuse(TFRA_ERR_UNSUPPORTED, "float32 gradients take no scale (loss scaling belongs to float16)");
+    *forward = true;
+  } else if ((uintptr_t)g->grads & 7) {
+    return refuse(TFRA_ERR_UNSUPPORTED, "half gradients must be 8-B aligned");
+  }
+  return Check{};
+}
+
 }  // namespace tfra

@@ -142,6 +142,9 @@ Check check_rows_out(const tfra_rows_out* o) {
   return Check{};
 }
 const float* out_for_twin(const tfra_rows_out& o) { return reinterpret_cast<const float*>((uintptr_t)o.rows & ~(uintptr_t)15); }
+// The same for a half grad_out of the typed weight gradients (tfra_grads, checked by check_typed: 8-byte aligned, not NULL): what the
+// twin's checks look at in the place of its float* grad_out.
+const float* grads_for_twin(const tfra_grads& g) { return reinterpret_cast<const float*>((uintptr_t)g.grads & ~(uintptr_t)15); }
 // whether the flags change anything: the SAFE kernels run only then
 bool ragged_safe(uint32_t flags, const float* weights) { return (flags & TFRA_RAGGED_FILL) || ((flags & TFRA_RAGGED_PRUNE) && weights); }
 // launch(DT, U, NCH, SAFE): with_pool_class with the ragged forms' fourth axis

@@ -98,6 +98,7 @@ struct PoolDesc {
   const float* grad_out;     // the weight gradients: grad_out in the place of out, and dw_out
   float* dw_out;
   const tfra_rows_out* typed;   // the typed lookups (plain tables only): the output record in the place of out; NULL otherwise
+  const tfra_grads* hgrads;     // the typed weight gradients: the record in the place of grad_out; NULL otherwise
 };
 typedef PoolDesc (*PoolDescAt)(const void* descs, size_t i);
 

@@ -8,6 +8,7 @@
 #include "../../include/tfra_mi355x.h"
 #include "tfra_combine_device.h"
 #include "tfra_device.h"
+#include "tfra_optim_device.h"
 #include "tfra_pool.h"
 
 namespace tfra {
@@ -32,14 +33,22 @@ namespace {
 //           branch is — and all U of them at once; only the entries that missed v are probed there.  (Two copies of that block,
 //           not one helper: as a __forceinline__ function it changed the code of existing kernels)  Everything
 //           behind src[u] is the one-table code.
+//   GHALF   grad_out is float16 or bfloat16 (the *_typed calls): the ONE difference is the load of g[NCH] — a lane's
+//           four elements are one 8-byte load (the group's 16 lanes: one 128-byte line per chunk), up-cast exactly by the helpers
+//           GradHalf uses (load_stored4, tfra_optim_device.h) and multiplied by the scale, one fp32 multiplication rounded on its
+//           own, so that everything behind g[NCH] sees GO32[r, c] = f32(grad_out[r, c]) * s of the untyped call.  is_bf16 is
+//           wave-uniform (a kernel argument or a field of the descriptor's record): ONE class for both formats.  *d_scale is read
+//           once per group, before the entry loop, at a uniform address (a scalar load); nullptr: 1.0f, x * 1.0f being exact.
+//           The row base is formed in 64 bits, as the float one is.  Without GHALF neither argument is read.
 // An entry in no row is never visited: the memset before the launch is its 0.  (TFRA_RAGGED_FILL needs no code: a row without
 // members has only pruned entries.)  Without TIER `lo` is not read.
-template <int DT, int U, int NCH, bool RAGGED, bool PRUNE, bool TIER = false>
+template <int DT, int U, int NCH, bool RAGGED, bool PRUNE, bool TIER = false, bool GHALF = false>
 __device__ __forceinline__ void wgrad_row(const TableView& v, size_t n_rows, int dim, const i64* __restrict__ ids,
                                           const float* __restrict__ w, const int* __restrict__ start_end,
                                           const i64* __restrict__ row_splits, int nnz, int combiner,
                                           const unsigned char* __restrict__ default_row, const float* __restrict__ grad_out,
-                                          float* dw, size_t r, const TableView* lo = nullptr) {
+                                          float* dw, size_t r, const TableView* lo = nullptr, const float* d_scale = nullptr,
+                                          int is_bf16 = 0) {
   static_assert(U == 4, "keep_live is written for U == 4");
   typedef typename PoolRow<DT>::Raw Raw;
   constexpr unsigned EB = DT == TFRA_F32 ? 4u : 2u;   // bytes per element
@@ -61,13 +70,34 @@ __device__ __forceinline__ void wgrad_row(const TableView& v, size_t n_rows, int
   unsigned coff[NCH];   // this lane's byte offset inside a row, per chunk
   bool cok[NCH];
   float4 g[NCH];
-  const float* G = grad_out + r * (size_t)dim;
+  if constexpr (GHALF) {
+    typedef float v4f_t __attribute__((ext_vector_type(4)));
+    const float gs = d_scale ? *d_scale : 1.f;
+    const unsigned short* G = reinterpret_cast<const unsigned short*>(grad_out) + r * (size_t)dim;
 #pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const int col = c * 64 + sub * 4;
-    cok[c] = col < dim;
-    coff[c] = cok[c] ? (unsigned)col * EB : 0u;
-    g[c] = *reinterpret_cast<const float4*>(G + (cok[c] ? col : 0));
+    for (int c = 0; c < NCH; ++c) {
+      const int col = c * 64 + sub * 4;
+      cok[c] = col < dim;
+      coff[c] = cok[c] ? (unsigned)col * EB : 0u;
+      const uint2 raw = *reinterpret_cast<const uint2*>(G + (cok[c] ? col : 0));
+      float4 x = is_bf16 ? load_stored4<TFRA_BF16>(raw) : load_stored4<TFRA_F16>(raw);
+      x.x *= gs; x.y *= gs; x.z *= gs; x.w *= gs;
+      // The float arm's g[c] is a 16-byte load's result: four consecutive registers.  The products are placed the same way (an
+      // empty asm over a 4-vector): left to itself the register allocator gave float32-row kernels up to 7 VGPRs more than their
+      // float twins, three of them a waves-per-SIMD class lower (profiles/wgrad_half_isa_stats.txt).
+      v4f_t q = {x.x, x.y, x.z, x.w};
+      asm volatile("" : "+v"(q));
+      g[c] = make_float4(q.x, q.y, q.z, q.w);
+    }
+  } else {
+    const float* G = grad_out + r * (size_t)dim;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int col = c * 64 + sub * 4;
+      cok[c] = col < dim;
+      coff[c] = cok[c] ? (unsigned)col * EB : 0u;
+      g[c] = *reinterpret_cast<const float4*>(G + (cok[c] ? col : 0));
+    }
   }
   float s = 0.f;
   const int last = e - 1;

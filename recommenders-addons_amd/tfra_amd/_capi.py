@@ -216,6 +216,27 @@ class FindCombineRaggedWgradDesc(ctypes.Structure):
   ]
 
 
+class FindCombineWgradTypedDesc(ctypes.Structure):
+  """tfra_find_combine_wgrad_typed_desc (include/tfra_mi355x.h): FindCombineWgradDesc with grad_out as a tfra_grads, for
+  tfra_multi_find_combine_backprop_weights_typed."""
+  _fields_ = [
+      ("struct_size", ctypes.c_uint32), ("combiner", ctypes.c_int32), ("table", ctypes.c_void_p), ("tier", ctypes.c_void_p),
+      ("nnz", ctypes.c_size_t), ("ids", ctypes.c_void_p), ("seg", ctypes.c_void_p), ("weights", ctypes.c_void_p),
+      ("n_rows", ctypes.c_size_t), ("default_row", ctypes.c_void_p), ("grad_out", Grads), ("dw_out", ctypes.c_void_p),
+  ]
+
+
+class FindCombineRaggedWgradTypedDesc(ctypes.Structure):
+  """tfra_find_combine_ragged_wgrad_typed_desc (include/tfra_mi355x.h): FindCombineRaggedWgradDesc with grad_out as a tfra_grads,
+  for tfra_multi_find_combine_ragged_backprop_weights_typed."""
+  _fields_ = [
+      ("struct_size", ctypes.c_uint32), ("combiner", ctypes.c_int32), ("table", ctypes.c_void_p), ("tier", ctypes.c_void_p),
+      ("n_rows", ctypes.c_size_t), ("row_splits", ctypes.c_void_p), ("nnz", ctypes.c_size_t), ("ids", ctypes.c_void_p),
+      ("weights", ctypes.c_void_p), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("fill_id", ctypes.c_int64),
+      ("default_row", ctypes.c_void_p), ("grad_out", Grads), ("dw_out", ctypes.c_void_p),
+  ]
+
+
 class ApplyCombinedDesc(ctypes.Structure):
   """tfra_apply_combined_desc (include/tfra_mi355x.h): one table's combined write-back in tfra_multi_apply_planned_combined."""
   _fields_ = [
@@ -372,6 +393,15 @@ _SIGS = {
     "tfra_table_find_combine_backprop_weights": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, _P, _P, _P],
     "tfra_table_find_combine_ragged_backprop_weights": [_P, _SZ, _P, _SZ, _P, _P, _I, ctypes.c_uint32, ctypes.c_int64, _P, _P, _P,
                                                         _P],
+    "tfra_table_find_combine_backprop_weights_typed": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, ctypes.POINTER(Grads), _P, _P],
+    "tfra_table_find_combine_ragged_backprop_weights_typed": [_P, _SZ, _P, _SZ, _P, _P, _I, ctypes.c_uint32, ctypes.c_int64, _P,
+                                                              ctypes.POINTER(Grads), _P, _P],
+    "tfra_tier_find_combine_backprop_weights_typed": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, ctypes.POINTER(Grads), _P, _P],
+    "tfra_tier_find_combine_ragged_backprop_weights_typed": [_P, _SZ, _P, _SZ, _P, _P, _I, ctypes.c_uint32, ctypes.c_int64, _P,
+                                                             ctypes.POINTER(Grads), _P, _P],
+    "tfra_multi_find_combine_backprop_weights_typed": [_P, _SZ, _P, _P, _P],
+    "tfra_multi_find_combine_ragged_backprop_weights_typed": [_P, _SZ, _P, _P, _P],
+    "tfra_sparse_segment_combine_backprop_weights_typed": [_P, _SZ, _I, _P, _P, ctypes.POINTER(Grads), _P, _P, _I, _SZ, _P, _P],
     "tfra_multi_apply_planned_combined": [_P, _SZ, _P, _P, _P],
     "tfra_multi_apply_planned_combined_typed": [_P, _SZ, _P, _P, _P],
     "tfra_multi_sparse_plan_build": [_P, _SZ, _P, _P, _P],

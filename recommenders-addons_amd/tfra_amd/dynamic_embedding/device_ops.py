@@ -500,18 +500,22 @@ def sparse_segment_combine(rows, idx, seg, weights, combiner, n_rows):
   return out
 
 
-def sparse_segment_combine_weight_grad(rows, idx, grad_out, seg, weights, combiner):
+def sparse_segment_combine_weight_grad(rows, idx, grad_out, seg, weights, combiner, grad_scale=None):
   """The gradient of `sparse_segment_combine` with respect to its weights (tfra_sparse_segment_combine_backprop_weights):
   float32 [nnz], dw[p] = d loss / d weights[p] for grad_out = d loss / d out [n_rows, dim].  With d_p = grad_out[seg[p]] . rows[idx[p]],
   s = sum_p w_p d_p over the row and W = sum w (mean) | sum w^2 (sqrtn):  sum d_p | mean (d_p - s / W) / W |
   sqrtn (d_p - (s / W) w_p) / sqrt(W); 0 for a row with W == 0 and for an entry whose row lies outside [0, n_rows).
   weights None = all 1 (the gradient with respect to those ones is still returned).  seg ascending.  Bit-identical to
-  `_DeviceTable.find_combine_weight_grad` where both apply."""
+  `_DeviceTable.find_combine_weight_grad` where both apply.
+  A contiguous float16 / bfloat16 grad_out goes down as it is, grad_scale — a one-element float32 device tensor the gradient is
+  multiplied by, read by the kernel — with it (tfra_sparse_segment_combine_backprop_weights_typed): bit for bit the result for
+  grad_out.float() * grad_scale.  Every other grad_out is up-cast, multiplied in torch where a scale is given, and takes the
+  untyped call."""
   rows = rows.to(torch.float32).contiguous()
   dev = rows.device
   idx = idx.to(dev, torch.int32).contiguous().reshape(-1)
   seg = seg.to(dev, torch.int64).contiguous().reshape(-1)
-  grad_out = grad_out.to(dev, torch.float32).contiguous()
+  typed, grad_out = _grads_arg(torch.as_tensor(grad_out), dev, 0, grad_scale)   # (dim 0: the chain call takes halves at any dim)
   if rows.dim() != 2 or grad_out.dim() != 2 or grad_out.shape[1] != rows.shape[1]:
     raise ValueError("rows must be [U, dim] and grad_out [n_rows, dim], got %s and %s" % (list(rows.shape), list(grad_out.shape)))
   nnz = idx.numel()
@@ -522,6 +526,10 @@ def sparse_segment_combine_weight_grad(rows, idx, grad_out, seg, weights, combin
   w = None if weights is None else torch.as_tensor(weights, device=dev).to(torch.float32).contiguous().reshape(-1)
   n_rows, dim = grad_out.shape
   out = torch.empty(nnz, dtype=torch.float32, device=dev)
+  if typed is not None:
+    _capi.call("tfra_sparse_segment_combine_backprop_weights_typed", _workspace(dev), nnz, dim, _ptr(rows), _ptr(idx),
+               ctypes.byref(typed), _ptr(seg), _ptr(w), COMBINERS[combiner], n_rows, _ptr(out), _stream(dev))
+    return out
   _capi.call("tfra_sparse_segment_combine_backprop_weights", _workspace(dev), nnz, dim, _ptr(rows), _ptr(idx), _ptr(grad_out),
              _ptr(seg), _ptr(w), COMBINERS[combiner], n_rows, _ptr(out), _stream(dev))
   return out

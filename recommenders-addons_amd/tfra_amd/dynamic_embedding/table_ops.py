@@ -266,13 +266,17 @@ class _DeviceTable:
                flags, fill, _ptr(d), _ptr(out), _stream(self._device))
     return out
 
-  def _weight_grad_out(self, grad_out, n_rows):
-    """grad_out of a pooled lookup as the C calls read it: float32 [n_rows, dim] on the table's device, contiguous."""
-    g = torch.as_tensor(grad_out, device=self._device).to(torch.float32).contiguous()
+  def _weight_grad_out(self, grad_out, n_rows, keep_half=False, grad_scale=None):
+    """grad_out of a pooled lookup as the C calls read it: float32 [n_rows, dim] on the table's device, contiguous.
+    keep_half (the *_typed calls): returns (tfra_grads, tensor) for a contiguous float16 / bfloat16 matrix, which goes down as it
+    is with grad_scale beside it, else (None, the float32 up-cast times grad_scale) — `_grads_arg`, as the write-backs take it."""
+    g = torch.as_tensor(grad_out, device=self._device)
     if g.dim() != 2 or g.shape[1] != self._dim or (n_rows is not None and g.shape[0] != n_rows):
       raise ValueError("grad_out must be [%s, %d] (the lookup's result), got %s" %
                        ("n_rows" if n_rows is None else n_rows, self._dim, list(g.shape)))
-    return g
+    if keep_half:
+      return _grads_arg(g, self._device, self._dim, grad_scale)
+    return g.to(torch.float32).contiguous()
 
   def find_combine_weight_grad(self, ids, seg, weights, combiner, grad_out, default_row=None):
     """The gradient of `find_combine` with respect to its weights (tfra_table_find_combine_backprop_weights): float32 [nnz],
@@ -300,6 +304,23 @@ class _DeviceTable:
     _capi.call("tfra_table_find_combine_ragged_backprop_weights", self._h, rs.numel() - 1, _ptr(rs), ids.numel(), _ptr(ids),
                _ptr(w), int(combiner), flags, fill, _ptr(d), _ptr(g), _ptr(dw), _stream(self._device))
     return dw
+
+  def find_combine_weight_grad_typed(self, ids, seg, weights, combiner, grad_out, default_row=None, grad_scale=None):
+    """`find_combine_weight_grad` that takes grad_out as the dense part of a half model hands it back: a contiguous float16 /
+    bfloat16 [n_rows, dim] matrix goes down as it is (tfra_table_find_combine_backprop_weights_typed: no conversion pass, no
+    float32 temporary), grad_scale — a one-element float32 device tensor the gradient is multiplied by, read by the kernel — with
+    it.  The result is bit for bit `find_combine_weight_grad(grad_out.float() * grad_scale)`.  Any other grad_out (float32, or a
+    half one that is not contiguous) is up-cast, multiplied in torch where a scale is given, and takes the untyped call.
+    (A method beside `find_combine_weight_grad`, whose parameter list the tiered owners mirror and stays as it is.)"""
+    return _wgrad_typed(self, self, "tfra_table_find_combine_backprop_weights", ids, seg, weights, combiner, grad_out, default_row,
+                        grad_scale)
+
+  def find_combine_ragged_weight_grad_typed(self, row_splits, ids, weights, combiner, grad_out, prune=False, fill_id=None,
+                                            default_row=None, grad_scale=None):
+    """`find_combine_ragged_weight_grad` with grad_out and grad_scale as `find_combine_weight_grad_typed` takes them
+    (tfra_table_find_combine_ragged_backprop_weights_typed)."""
+    return _wgrad_ragged_typed(self, self, "tfra_table_find_combine_ragged_backprop_weights", row_splits, ids, weights, combiner,
+                               grad_out, prune, fill_id, default_row, grad_scale)
 
   def upsert(self, keys, values, scores=None, unique_keys=False, field=0):
     keys = self._keys(keys)
@@ -957,6 +978,18 @@ class _DeviceTier:
                _ptr(w), int(combiner), flags, fill, _ptr(d), _ptr(g), _ptr(dw), _stream(up._device))
     return dw
 
+  def find_combine_weight_grad_typed(self, ids, seg, weights, combiner, grad_out, default_row=None, grad_scale=None):
+    """`_DeviceTable.find_combine_weight_grad_typed` over both tiers (tfra_tier_find_combine_backprop_weights_typed): a contiguous
+    float16 / bfloat16 grad_out goes down as it is, grad_scale with it.  A read, as `find_combine_weight_grad`."""
+    return _wgrad_typed(self, self._upper, "tfra_tier_find_combine_backprop_weights", ids, seg, weights, combiner, grad_out,
+                        default_row, grad_scale)
+
+  def find_combine_ragged_weight_grad_typed(self, row_splits, ids, weights, combiner, grad_out, prune=False, fill_id=None,
+                                            default_row=None, grad_scale=None):
+    """`_DeviceTable.find_combine_ragged_weight_grad_typed` over both tiers (tfra_tier_find_combine_ragged_backprop_weights_typed)."""
+    return _wgrad_ragged_typed(self, self._upper, "tfra_tier_find_combine_ragged_backprop_weights", row_splits, ids, weights,
+                               combiner, grad_out, prune, fill_id, default_row, grad_scale)
+
   def insert(self, keys, values, count=None):
     """upsert of embedding rows (UNIQUE keys) into upper; what it displaces goes down as whole rows (tfra_tier_insert)."""
     keys = self._upper._keys(keys)
@@ -1480,6 +1513,16 @@ class TieredHashTable(_LookupInterfaceMirror):
     return self._tier.find_combine_ragged_weight_grad(row_splits, ids, weights, combiner, grad_out, prune=prune, fill_id=fill_id,
                                                       default_row=default_row)
 
+  def find_combine_weight_grad_typed(self, ids, seg, weights, combiner, grad_out, default_row=None, grad_scale=None):
+    """`find_combine_weight_grad` with a half grad_out as it is (`_DeviceTier.find_combine_weight_grad_typed`): a read."""
+    return self._tier.find_combine_weight_grad_typed(ids, seg, weights, combiner, grad_out, default_row, grad_scale=grad_scale)
+
+  def find_combine_ragged_weight_grad_typed(self, row_splits, ids, weights, combiner, grad_out, prune=False, fill_id=None,
+                                            default_row=None, grad_scale=None):
+    """The same for `find_combine_ragged` (`_DeviceTier.find_combine_ragged_weight_grad_typed`): a read."""
+    return self._tier.find_combine_ragged_weight_grad_typed(row_splits, ids, weights, combiner, grad_out, prune=prune,
+                                                            fill_id=fill_id, default_row=default_row, grad_scale=grad_scale)
+
   def lookup_missed(self, keys, dynamic_default_values=None, name=None):
     """`lookup` plus the pairs (key, position) that NEITHER tier holds (one host read for their number)."""
     return self._shard_find_missed(keys, dynamic_default_values, False)
@@ -1544,6 +1587,29 @@ class TieredHashTable(_LookupInterfaceMirror):
 
   def _checkpoint_loaded(self):
     self._table.clear_all()   # everything was loaded below: the cache fills again from there
+
+
+def _wgrad_typed(owner, table, c_name, ids, seg, weights, combiner, grad_out, default_row, grad_scale):
+  """The frame of `find_combine_weight_grad_typed` for a table (owner is table) and a tier (table: its upper table, which prepares
+  the operands): `c_name`_typed when grad_out goes down as a half matrix, `c_name` on the float32 up-cast otherwise."""
+  typed, g = table._weight_grad_out(grad_out, None, keep_half=True, grad_scale=grad_scale)
+  ids, seg, w, d, _ = table._find_combine_args(ids, seg, weights, 0, default_row)
+  dw = torch.empty(ids.numel(), dtype=torch.float32, device=table._device)
+  _capi.call(c_name + ("_typed" if typed is not None else ""), owner._h, _workspace(table._device), ids.numel(), _ptr(ids), _ptr(seg),
+             _ptr(w), int(combiner), g.shape[0], _ptr(d), (ctypes.byref(typed) if typed is not None else _ptr(g)), _ptr(dw),
+             _stream(table._device))
+  return dw
+
+
+def _wgrad_ragged_typed(owner, table, c_name, row_splits, ids, weights, combiner, grad_out, prune, fill_id, default_row, grad_scale):
+  """`_wgrad_typed` for the ragged calls."""
+  rs, ids, w, flags, fill, d, _ = table._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row)
+  typed, g = table._weight_grad_out(grad_out, rs.numel() - 1, keep_half=True, grad_scale=grad_scale)
+  dw = torch.empty(ids.numel(), dtype=torch.float32, device=table._device)
+  _capi.call(c_name + ("_typed" if typed is not None else ""), owner._h, rs.numel() - 1, _ptr(rs), ids.numel(), _ptr(ids), _ptr(w),
+             int(combiner), flags, fill, _ptr(d), (ctypes.byref(typed) if typed is not None else _ptr(g)), _ptr(dw),
+             _stream(table._device))
+  return dw
 
 
 def _device_table(x):
@@ -1701,68 +1767,121 @@ def find_combine_ragged_many(requests, return_launches=False, out_dtype=None):
   return (outs, launches) if return_launches else outs
 
 
-def find_combine_weight_grad_many(requests, return_launches=False):
+def _request_scales(who, grad_scale, n):
+  """grad_scale of a grouped call as one entry per request: one scale for all, or a list with one (or None) per request."""
+  scales = list(grad_scale) if isinstance(grad_scale, (list, tuple)) else [grad_scale] * n
+  if len(scales) != n:
+    raise ValueError("%s: %d requests but %d gradient scales" % (who, n, len(scales)))
+  return scales
+
+
+def _pooled_table(owner):
+  """The _DeviceTable that prepares a pooled request's operands: the owner's device table, or a tier's upper table."""
+  tier = _device_tier(owner)
+  return tier._upper if tier is not None else _device_table(owner)
+
+
+def _request_grads(who, requests, grad_scale, n_rows_of):
+  """What the grouped weight gradients decide before the descriptors exist, because which C call it is depends on it: each
+  request's gradient as `_weight_grad_out(..., keep_half=True)` prepares it — (tfra_grads or None, tensor), n_rows_of(request) the
+  row count it must have (None: its own) — and whether any of them goes down as a half matrix.  The owners are looked at first, in
+  the order and with the error `_grouped_call` has for them: a bad owner fails as it did before the gradients were prepared here."""
+  scales = _request_scales(who, grad_scale, len(requests))
+  device = _owner_device(requests[0][0])
+  for r in requests:
+    dev = _owner_device(r[0])
+    if dev != device:
+      raise ValueError("%s: all tables must live on one device (%s and %s)" % (who, device, dev))
+  grads = [_pooled_table(r[0])._weight_grad_out(r[5], n_rows_of(r), keep_half=True, grad_scale=sc) for r, sc in zip(requests, scales)]
+  return grads, any(t is not None for t, _ in grads)
+
+
+def _splits_rows(row_splits):
+  """n_rows of a ragged request, from the shape of its row_splits alone (None where `_find_combine_ragged_args` will refuse it)."""
+  n = torch.as_tensor(row_splits).numel()
+  return n - 1 if n >= 1 else None
+
+
+def find_combine_weight_grad_many(requests, return_launches=False, grad_scale=None):
   """The weight gradients of a list of pooled lookups in ONE C call (tfra_multi_find_combine_backprop_weights; the frame:
   `_grouped_call`).  `requests`: a list of (table, ids, seg, weights, combiner, grad_out[, default_row]), the arguments behind
   `table` those of `_DeviceTable.find_combine_weight_grad`, handled the same way (n_rows is grad_out's).  `table` is a table, a
   TieredHashTable or a _DeviceTier (read in both tiers), in any mix; a table or tier may occur more than once.  Returns the
   float32 [nnz] gradients in the requests' order, each bit-identical to `find_combine_weight_grad` of its request (with
   return_launches: also the number of kernel launches the call enqueued: one that zero-fills all results and writes all rows'
-  bounds, and one per (tiered or not, value dtype, row-width class) class in the list)."""
+  bounds, and one per (tiered or not, value dtype, row-width class) class in the list).
+  grad_scale: one scale for all requests, or a list with one (or None) per request, as `find_combine_weight_grad_typed` takes it.
+  As soon as one request's grad_out goes down as a half matrix (contiguous float16 / bfloat16), the call is
+  tfra_multi_find_combine_backprop_weights_typed — float32 members ride along as float32 descriptors, float-or-half being one
+  more launch-class axis —; otherwise it is the untyped call, as always."""
   if not requests:
     return ([], 0) if return_launches else []
   dws = []
+  grads, any_typed = _request_grads("find_combine_weight_grad_many", requests, grad_scale, lambda r: None)
 
   def fill(e, i):
     req = requests[i]
-    table, ids, seg, weights, combiner, grad_out = req[:6]
+    table, ids, seg, weights, combiner = req[:5]
     default_row = req[6] if len(req) > 6 else None
     table = _pooled_owner(e, table, True)
-    g = table._weight_grad_out(grad_out, None)
+    typed, g = grads[i]
     ids, seg, w, d, _ = table._find_combine_args(ids, seg, weights, 0, default_row)
     dw = torch.empty(ids.numel(), dtype=torch.float32, device=table._device)
     dws.append(dw)
     e.combiner = int(combiner)
     e.nnz, e.ids, e.seg, e.weights = ids.numel(), ids.data_ptr(), seg.data_ptr(), (w.data_ptr() if w is not None else None)
-    e.n_rows, e.default_row, e.grad_out, e.dw_out = g.shape[0], d.data_ptr(), g.data_ptr(), dw.data_ptr()
+    e.n_rows, e.default_row, e.dw_out = g.shape[0], d.data_ptr(), dw.data_ptr()
+    e.grad_out = _grads_field(typed, g, any_typed)
     return ids, seg, w, d, g
 
-  launches = _grouped_call("tfra_multi_find_combine_backprop_weights", _capi.FindCombineWgradDesc, "find_combine_weight_grad_many",
-                           [r[0] for r in requests], fill)
+  c_name, desc_type = (("tfra_multi_find_combine_backprop_weights_typed", _capi.FindCombineWgradTypedDesc) if any_typed else
+                       ("tfra_multi_find_combine_backprop_weights", _capi.FindCombineWgradDesc))
+  launches = _grouped_call(c_name, desc_type, "find_combine_weight_grad_many", [r[0] for r in requests], fill)
   return (dws, launches) if return_launches else dws
 
 
-def find_combine_ragged_weight_grad_many(requests, return_launches=False):
+def _grads_field(typed, g, any_typed):
+  """A descriptor's grad_out: the tensor's address in an untyped list; in a typed one its tfra_grads, a float32 member's formed here."""
+  if not any_typed:
+    return g.data_ptr()
+  return typed if typed is not None else _capi.Grads(g.data_ptr(), _capi.TFRA_F32, 0, None)
+
+
+def find_combine_ragged_weight_grad_many(requests, return_launches=False, grad_scale=None):
   """The weight gradients of a list of ragged pooled lookups in ONE C call (tfra_multi_find_combine_ragged_backprop_weights; the
   frame: `_grouped_call`).  `requests`: a list of (table, row_splits, ids, weights, combiner, grad_out[, prune[, fill_id[,
   default_row]]]), the arguments behind `table` those of `_DeviceTable.find_combine_ragged_weight_grad`, handled the same way;
   `table` as in `find_combine_weight_grad_many`.  Returns the float32 [nnz] gradients in the requests' order, each bit-identical
   to `find_combine_ragged_weight_grad` of its request (with return_launches: also the number of kernel launches: one that
-  zero-fills all results and one per (tiered or not, value dtype, row-width class, pruning or not) class in the list)."""
+  zero-fills all results and one per (tiered or not, value dtype, row-width class, pruning or not) class in the list).
+  grad_scale and half gradients as in `find_combine_weight_grad_many` (tfra_multi_find_combine_ragged_backprop_weights_typed)."""
   if not requests:
     return ([], 0) if return_launches else []
   dws = []
+  grads, any_typed = _request_grads("find_combine_ragged_weight_grad_many", requests, grad_scale, lambda r: _splits_rows(r[1]))
 
   def fill(e, i):
     req = requests[i]
-    table, row_splits, ids, weights, combiner, grad_out = req[:6]
+    table, row_splits, ids, weights, combiner = req[:5]
     prune = req[6] if len(req) > 6 else False
     fill_id = req[7] if len(req) > 7 else None
     default_row = req[8] if len(req) > 8 else None
     table = _pooled_owner(e, table, True)
     rs, ids, w, flags, fill_key, d, _ = table._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row)
-    g = table._weight_grad_out(grad_out, rs.numel() - 1)
+    typed, g = grads[i]
     dw = torch.empty(ids.numel(), dtype=torch.float32, device=table._device)
     dws.append(dw)
     e.combiner = int(combiner)
     e.n_rows, e.row_splits = rs.numel() - 1, rs.data_ptr()
     e.nnz, e.ids, e.weights = ids.numel(), ids.data_ptr(), (w.data_ptr() if w is not None else None)
     e.flags, e.reserved, e.fill_id = flags, 0, fill_key
-    e.default_row, e.grad_out, e.dw_out = d.data_ptr(), g.data_ptr(), dw.data_ptr()
+    e.default_row, e.dw_out = d.data_ptr(), dw.data_ptr()
+    e.grad_out = _grads_field(typed, g, any_typed)
     return rs, ids, w, d, g
 
-  launches = _grouped_call("tfra_multi_find_combine_ragged_backprop_weights", _capi.FindCombineRaggedWgradDesc,
-                           "find_combine_ragged_weight_grad_many", [r[0] for r in requests], fill)
+  c_name, desc_type = (("tfra_multi_find_combine_ragged_backprop_weights_typed", _capi.FindCombineRaggedWgradTypedDesc) if any_typed
+                       else ("tfra_multi_find_combine_ragged_backprop_weights", _capi.FindCombineRaggedWgradDesc))
+  launches = _grouped_call(c_name, desc_type, "find_combine_ragged_weight_grad_many", [r[0] for r in requests], fill)
   return (dws, launches) if return_launches else dws
 
 

@@ -526,6 +526,25 @@ class Variable:
     return _pooled_reader(t).find_combine_ragged_weight_grad(row_splits, ids, weights, device_ops.COMBINERS[combiner], grad_out,
                                                              prune=prune, fill_id=fill_id, default_row=t._default_value)
 
+  def lookup_combined_weight_grad_typed(self, ids, seg, weights, combiner, grad_out, grad_scale=None, name=None):
+    """`lookup_combined_weight_grad` that takes grad_out as a half model's dense part hands it back: a contiguous float16 /
+    bfloat16 grad_out and grad_scale (a one-element float32 device tensor the gradient is multiplied by) go down as they are
+    (tfra_table_find_combine_backprop_weights_typed; a tiered shard: tfra_tier_find_combine_backprop_weights_typed), bit for bit
+    the result for grad_out.float() * grad_scale.  Every other grad_out is up-cast, multiplied in torch where a scale is given,
+    and takes `lookup_combined_weight_grad`'s call.  (A method beside it, whose parameter list stays as it is.)"""
+    t, ids = self._combined_operands(ids, ragged=False)
+    return _pooled_reader(t).find_combine_weight_grad_typed(ids, seg, weights, device_ops.COMBINERS[combiner], grad_out,
+                                                            t._default_value, grad_scale=grad_scale)
+
+  def lookup_combined_ragged_weight_grad_typed(self, row_splits, ids, weights, combiner, grad_out, prune=False, fill_id=None,
+                                               grad_scale=None, name=None):
+    """`lookup_combined_ragged_weight_grad` with grad_out and grad_scale as `lookup_combined_weight_grad_typed` takes them
+    (tfra_table_find_combine_ragged_backprop_weights_typed; a tiered shard: the tier's typed call)."""
+    t, ids = self._combined_operands(ids, ragged=True)
+    return _pooled_reader(t).find_combine_ragged_weight_grad_typed(row_splits, ids, weights, device_ops.COMBINERS[combiner], grad_out,
+                                                                   prune=prune, fill_id=fill_id, default_row=t._default_value,
+                                                                   grad_scale=grad_scale)
+
   def export(self, name=None):
     """PY/dynamic_embedding_variable.py:988-1007"""
     ks, vs = [], []
@@ -998,7 +1017,7 @@ class SparseTrainableWrapper(TrainableWrapper):
     return device_ops.segment_sum(eg, self._idx, self._n_unique, n)
 
 
-  def weights_grad(self, grad_out):
+  def weights_grad(self, grad_out, grad_scale=None):
     """The gradient of the lookup's result with respect to the VALUES of the sp_weights the caller passed: float32, the caller's
     length and order, from grad_out = d loss / d result (the result's shape).  Entries the safe form pruned get 0; the entries
     it adds for empty rows are not the caller's and do not appear; a row that took `default_id` contributes nothing.
@@ -1009,18 +1028,28 @@ class SparseTrainableWrapper(TrainableWrapper):
     dims or dtypes — goes through a lookup of the unique ids and `device_ops.sparse_segment_combine_weight_grad`.  The two routes
     give the same bits for the same rows.
     Nothing is read on the host on the pooled route, pruned or not (the pruned positions are filled by a masked scatter).
+    A float16 / bfloat16 grad_out and grad_scale (a one-element float32 device tensor, as in `apply_combined_gradients`) go down
+    as they are on both routes (tfra_table_find_combine_backprop_weights_typed, a tier's typed call, or
+    tfra_sparse_segment_combine_backprop_weights_typed): the SAME half gradient serves the write-back and this call with no
+    conversion pass.  Every other gradient — float32, or a half one that is not contiguous — is read as its float32 up-cast times
+    the scale, by the typed calls' definition the same bits.  No host read either way.
     ValueError for a lookup made without sp_weights, with max_norm (the clip's own gradient is not formed, as in
     `apply_combined_gradients`), or for a grad_out of another shape."""
     if self.max_norm is not None:
       raise ValueError("weights_grad does not support max_norm: the clip's gradient is not formed")
     if self._weights is None:
       raise ValueError("weights_grad needs a lookup made with sp_weights")
-    g = self.check_grad_out(grad_out)
+    g = self.check_grad_out(grad_out, keep_half=True)
     if self._pooled_ids is not None and _pooled_training(self.params, None):
-      dw = self.params.lookup_combined_weight_grad(self._pooled_ids, self._seg, self._weights, self.combiner, g)
+      if g.dtype == torch.float32 and grad_scale is None:   # the method it always took
+        dw = self.params.lookup_combined_weight_grad(self._pooled_ids, self._seg, self._weights, self.combiner, g)
+      else:
+        dw = self.params.lookup_combined_weight_grad_typed(self._pooled_ids, self._seg, self._weights, self.combiner, g,
+                                                           grad_scale=grad_scale)
     else:
       rows = self.params.lookup(self.ids).to(torch.float32)
-      dw = device_ops.sparse_segment_combine_weight_grad(rows, self._idx, g, self._seg, self._weights, self.combiner)
+      dw = device_ops.sparse_segment_combine_weight_grad(rows, self._idx, g, self._seg, self._weights, self.combiner,
+                                                         grad_scale=grad_scale)
     if self._caller_weights is None:
       return dw
     cw = torch.as_tensor(self._caller_weights, dtype=torch.float32, device=dw.device).reshape(-1)
@@ -1029,7 +1058,7 @@ class SparseTrainableWrapper(TrainableWrapper):
     return torch.zeros(cw.numel(), dtype=torch.float32, device=dw.device).masked_scatter_(cw > 0, dw)
 
 
-def sparse_weights_grad_many(grads_and_wrappers):
+def sparse_weights_grad_many(grads_and_wrappers, grad_scale=None):
   """`SparseTrainableWrapper.weights_grad` of a LIST of lookups (a many-table model's weighted sparse features):
   `grads_and_wrappers` is a list of (grad_out, wrapper), and result i is what `wrapper.weights_grad(grad_out)` returns, bit for
   bit and in the caller's length.  The wrappers on the pooled route — made behind the pooled forward, of a variable it still
@@ -1038,7 +1067,9 @@ def sparse_weights_grad_many(grads_and_wrappers):
   list); what a safe lookup pruned is filled in per member afterwards, as `weights_grad` fills it.  Every other wrapper — several
   shards, a callable initializer, bp_v2, other dims or dtypes — is served by its own `weights_grad`, so no list is refused.
   The ValueErrors are `weights_grad`'s (no sp_weights, max_norm, a grad_out of another shape), raised for the whole list before
-  anything is enqueued.  As there, the tables' rows are read as they are at call time: call it before the step's write-back."""
+  anything is enqueued.  As there, the tables' rows are read as they are at call time: call it before the step's write-back.
+  Half gradients and grad_scale as in `weights_grad`: a group with a half member is ONE
+  tfra_multi_find_combine_backprop_weights_typed call (float32 members ride along); a group without one takes the untyped call."""
   pairs = list(grads_and_wrappers)
   checked = []
   for grad_out, tw in pairs:
@@ -1046,21 +1077,21 @@ def sparse_weights_grad_many(grads_and_wrappers):
       raise ValueError("weights_grad does not support max_norm: the clip's gradient is not formed")
     if tw._weights is None:
       raise ValueError("weights_grad needs a lookup made with sp_weights")
-    checked.append(tw.check_grad_out(grad_out))
+    checked.append(tw.check_grad_out(grad_out, keep_half=True))
   results = [None] * len(pairs)
   groups = {}   # device -> [i]
   for i, (grad_out, tw) in enumerate(pairs):
     if tw._pooled_ids is not None and _pooled_training(tw.params, None):
       groups.setdefault(tw.params._primary, []).append(i)
     else:
-      results[i] = tw.weights_grad(grad_out)
+      results[i] = tw.weights_grad(grad_out, grad_scale=grad_scale)
   for members in groups.values():
     reqs = []
     for i in members:
       tw = pairs[i][1]
       t, ids = tw.params._combined_operands(tw._pooled_ids, ragged=False)
       reqs.append((_pooled_reader(t), ids, tw._seg, tw._weights, device_ops.COMBINERS[tw.combiner], checked[i], t._default_value))
-    for i, dw in zip(members, table_ops.find_combine_weight_grad_many(reqs)):
+    for i, dw in zip(members, table_ops.find_combine_weight_grad_many(reqs, grad_scale=grad_scale)):
       cw = pairs[i][1]._caller_weights
       if cw is not None:   # (weights_grad: the kept positions are filled from dw in order, on the device)
         cw = torch.as_tensor(cw, dtype=torch.float32, device=dw.device).reshape(-1)
