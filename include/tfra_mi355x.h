@@ -1334,6 +1334,30 @@ int tfra_table_find_combine_ragged_backprop_weights(tfra_table_t* t, size_t n_ro
                                                     int64_t fill_id, const void* default_row, const float* grad_out,
                                                     float* dw_out, tfra_stream_t stream);
 
+/* The four calls above for LONG rows — a sequence feature, a few hundred ids per row pooled by sum or mean —: the argument lists,
+ * checks, refusals, locking and nnz == 0 behaviour of tfra_table_find_combine, tfra_table_find_combine_ragged and their
+ * *_backprop_weights forms, and their results BIT FOR BIT (the adds run in entry order with the same expressions).  What differs is
+ * the launch: ONE 256-thread block per output row probes and reads the row's entries in parallel, where the twins give a row to one
+ * 16-lane group that walks it serially.  Short rows (a categorical feature's 1 - 30 ids) are the twins' ground: a block per row
+ * wastes most of its lanes there.  The tuple forms enqueue what their twins enqueue (memset, bounds launch, one launch); the ragged
+ * forward is one launch, the ragged gradient a memset and one launch.  In the ragged gradient, entries that two overlapping rows
+ * claim end as one row's value or a mix, as in the twin.
+ * Not provided in this form: typed outputs (tfra_rows_out), a half grad_out (tfra_grads), tiers, and the grouped *_many calls. */
+int tfra_table_find_combine_long(tfra_table_t* t, tfra_workspace_t* ws, size_t nnz, const int64_t* ids, const int64_t* seg,
+                                 const float* weights, int combiner, size_t n_rows, const void* default_row, float* out,
+                                 tfra_stream_t stream);
+int tfra_table_find_combine_ragged_long(tfra_table_t* t, size_t n_rows, const int64_t* row_splits, size_t nnz,
+                                        const int64_t* ids, const float* weights, int combiner, uint32_t flags,
+                                        int64_t fill_id, const void* default_row, float* out, tfra_stream_t stream);
+int tfra_table_find_combine_backprop_weights_long(tfra_table_t* t, tfra_workspace_t* ws, size_t nnz, const int64_t* ids,
+                                                  const int64_t* seg, const float* weights, int combiner, size_t n_rows,
+                                                  const void* default_row, const float* grad_out, float* dw_out,
+                                                  tfra_stream_t stream);
+int tfra_table_find_combine_ragged_backprop_weights_long(tfra_table_t* t, size_t n_rows, const int64_t* row_splits, size_t nnz,
+                                                         const int64_t* ids, const float* weights, int combiner, uint32_t flags,
+                                                         int64_t fill_id, const void* default_row, const float* grad_out,
+                                                         float* dw_out, tfra_stream_t stream);
+
 /* The weight gradients of MANY pooled lookups in one call (a model with 26 weighted sparse features asks for 26 of them per step:
  * ~100 enqueues for 26 small kernels otherwise).  A descriptor names exactly ONE of table / tier, as tfra_tier_find_combine_desc
  * does; descs[i].dw_out is bit-identical to the single call on that descriptor — the same device function runs:

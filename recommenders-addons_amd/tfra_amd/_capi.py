@@ -393,6 +393,12 @@ _SIGS = {
     "tfra_table_find_combine_backprop_weights": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, _P, _P, _P],
     "tfra_table_find_combine_ragged_backprop_weights": [_P, _SZ, _P, _SZ, _P, _P, _I, ctypes.c_uint32, ctypes.c_int64, _P, _P, _P,
                                                         _P],
+    # the long-row forms (one block per output row): their twins' argument lists
+    "tfra_table_find_combine_long": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, _P, _P],
+    "tfra_table_find_combine_ragged_long": [_P, _SZ, _P, _SZ, _P, _P, _I, ctypes.c_uint32, ctypes.c_int64, _P, _P, _P],
+    "tfra_table_find_combine_backprop_weights_long": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, _P, _P, _P],
+    "tfra_table_find_combine_ragged_backprop_weights_long": [_P, _SZ, _P, _SZ, _P, _P, _I, ctypes.c_uint32, ctypes.c_int64, _P, _P,
+                                                             _P, _P],
     "tfra_table_find_combine_backprop_weights_typed": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, ctypes.POINTER(Grads), _P, _P],
     "tfra_table_find_combine_ragged_backprop_weights_typed": [_P, _SZ, _P, _SZ, _P, _P, _I, ctypes.c_uint32, ctypes.c_int64, _P,
                                                               ctypes.POINTER(Grads), _P, _P],

@@ -305,6 +305,41 @@ class _DeviceTable:
                _ptr(w), int(combiner), flags, fill, _ptr(d), _ptr(g), _ptr(dw), _stream(self._device))
     return dw
 
+  # ---- the long-row forms: one 256-thread block per output row (tfra_pool_long.hip), the twins' bits ---------------------------
+  def find_combine_long(self, ids, seg, weights, combiner, n_rows, default_row=None):
+    """`find_combine` for rows of a few hundred entries (tfra_table_find_combine_long): the same arguments, limits and result, bit
+    for bit; a block per output row reads the row's entries in parallel.  Short rows are `find_combine`'s ground.  float32 out."""
+    ids, seg, w, d, out = self._find_combine_args(ids, seg, weights, n_rows, default_row)
+    _capi.call("tfra_table_find_combine_long", self._h, _workspace(self._device), ids.numel(), _ptr(ids), _ptr(seg), _ptr(w),
+               int(combiner), int(n_rows), _ptr(d), _ptr(out), _stream(self._device))
+    return out
+
+  def find_combine_ragged_long(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, default_row=None):
+    """`find_combine_ragged` for long rows (tfra_table_find_combine_ragged_long), bit for bit, in one launch.  float32 out."""
+    rs, ids, w, flags, fill, d, out = self._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row)
+    _capi.call("tfra_table_find_combine_ragged_long", self._h, rs.numel() - 1, _ptr(rs), ids.numel(), _ptr(ids), _ptr(w),
+               int(combiner), flags, fill, _ptr(d), _ptr(out), _stream(self._device))
+    return out
+
+  def find_combine_weight_grad_long(self, ids, seg, weights, combiner, grad_out, default_row=None):
+    """`find_combine_weight_grad` for long rows (tfra_table_find_combine_backprop_weights_long), bit for bit.  float32 grad_out."""
+    g = self._weight_grad_out(grad_out, None)
+    ids, seg, w, d, _ = self._find_combine_args(ids, seg, weights, 0, default_row)
+    dw = torch.empty(ids.numel(), dtype=torch.float32, device=self._device)
+    _capi.call("tfra_table_find_combine_backprop_weights_long", self._h, _workspace(self._device), ids.numel(), _ptr(ids), _ptr(seg),
+               _ptr(w), int(combiner), g.shape[0], _ptr(d), _ptr(g), _ptr(dw), _stream(self._device))
+    return dw
+
+  def find_combine_ragged_weight_grad_long(self, row_splits, ids, weights, combiner, grad_out, prune=False, fill_id=None,
+                                           default_row=None):
+    """`find_combine_ragged_weight_grad` for long rows (tfra_table_find_combine_ragged_backprop_weights_long), bit for bit."""
+    rs, ids, w, flags, fill, d, _ = self._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row)
+    g = self._weight_grad_out(grad_out, rs.numel() - 1)
+    dw = torch.empty(ids.numel(), dtype=torch.float32, device=self._device)
+    _capi.call("tfra_table_find_combine_ragged_backprop_weights_long", self._h, rs.numel() - 1, _ptr(rs), ids.numel(), _ptr(ids),
+               _ptr(w), int(combiner), flags, fill, _ptr(d), _ptr(g), _ptr(dw), _stream(self._device))
+    return dw
+
   def find_combine_weight_grad_typed(self, ids, seg, weights, combiner, grad_out, default_row=None, grad_scale=None):
     """`find_combine_weight_grad` that takes grad_out as the dense part of a half model hands it back: a contiguous float16 /
     bfloat16 [n_rows, dim] matrix goes down as it is (tfra_table_find_combine_backprop_weights_typed: no conversion pass, no
@@ -1249,7 +1284,26 @@ class _WholeRows:
     return self._table.store_rows(keys, fields, count=count)
 
 
-class CuckooHashTable(_LookupInterfaceMirror, _WholeRows):
+class _LongRows:
+  """The long-row pooled reads of a plain table's device table (`_DeviceTable.find_combine_long` and its three siblings)."""
+
+  def find_combine_long(self, ids, seg, weights, combiner, n_rows, default_row=None):
+    return self._table.find_combine_long(ids, seg, weights, combiner, n_rows, default_row)
+
+  def find_combine_ragged_long(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, default_row=None):
+    return self._table.find_combine_ragged_long(row_splits, ids, weights, combiner, prune=prune, fill_id=fill_id,
+                                                default_row=default_row)
+
+  def find_combine_weight_grad_long(self, ids, seg, weights, combiner, grad_out, default_row=None):
+    return self._table.find_combine_weight_grad_long(ids, seg, weights, combiner, grad_out, default_row)
+
+  def find_combine_ragged_weight_grad_long(self, row_splits, ids, weights, combiner, grad_out, prune=False, fill_id=None,
+                                           default_row=None):
+    return self._table.find_combine_ragged_weight_grad_long(row_splits, ids, weights, combiner, grad_out, prune=prune,
+                                                            fill_id=fill_id, default_row=default_row)
+
+
+class CuckooHashTable(_LookupInterfaceMirror, _WholeRows, _LongRows):
   """PY/cuckoo_hashtable_ops.py:45-145.  Growing, never-evicting table (libcuckoo semantics)."""
 
   def __init__(self, key_dtype, value_dtype, default_value, name="CuckooHashTable", checkpoint=True, init_size=0,
@@ -1277,7 +1331,7 @@ class CuckooHashTable(_LookupInterfaceMirror, _WholeRows):
     self._table.accum_or_assign(keys, values_or_deltas, exists)
 
 
-class HkvHashTable(_LookupInterfaceMirror, _WholeRows):
+class HkvHashTable(_LookupInterfaceMirror, _WholeRows, _LongRows):
   """PY/hkv_hashtable_ops.py:47-175.  Bounded table with per-key scores and in-bucket eviction."""
 
   def __init__(self, key_dtype, value_dtype, default_value, name="HkvHashTable", checkpoint=True,
