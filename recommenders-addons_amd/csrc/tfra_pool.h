@@ -1,9 +1,13 @@
-// What the pooled lookup (tfra_pool.hip; over a tier: tfra_tierpool.hip) and the gradient of its weights (tfra_wgrad.hip; over a tier: tfra_tierwgrad.hip; over a list: tfra_wgrad_many.hip) share, ONE copy each: the up-cast of a
-// stored row (PoolRow), the launch ladders by value dtype and row width (with_pool_class, with_ragged_class) and the argument checks
-// of the tuple and the ragged call (check_find_combine, check_find_combine_ragged; check_dw_out for the gradient's output).
+// What the pooled lookups (tfra_pool.hip; typed: tfra_pool_typed.hip; long rows: tfra_pool_long.hip; over a tier: tfra_tierpool.hip)
+// and the gradients of their weights (tfra_wgrad.hip; over a tier: tfra_tierwgrad.hip; over a list: tfra_wgrad_many.hip) share, ONE
+// copy each: the up-cast of a stored row (PoolRow), the launch ladders by value dtype and row width (with_pool_class,
+// with_ragged_class), the argument checks of the tuple and the ragged call (check_find_combine, check_find_combine_ragged;
+// check_dw_out for the gradient's output) and, at the end, the host frame of every SINGLE call: four function templates (forward
+// and weight gradient, tuple and ragged) over an owner (TableOwner here, TierOwner in tfra_tier.h) and the unit's launch.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <mutex>
 #include <string>
 #include <type_traits>
 
@@ -13,6 +17,8 @@
 #include "tfra_many.h"
 
 namespace tfra {
+int comb_bounds(hipStream_t s, size_t nnz, const int64_t* seg, size_t n_rows, int* se);   // tfra_combine.hip (tfra_combine_device.h)
+
 namespace {
 
 // four elements of a row as float32: a 16-B load of a float32 row, an 8-B load of a half row up-cast exactly
@@ -155,6 +161,130 @@ void with_ragged_class(int st, int nch, bool safe, F&& launch) {
     else launch(DT, U, NCH, std::false_type{});
   });
 }
+
+// ---- the host frames of the SINGLE pooled calls -------------------------------------------------------------------------------------
+// A call is: refuse a missing owner, run the form's checks (which enter the owner where the single call locks), append the owner's
+// hint to NEEDS_DIM, report behind the entry point's name, take the early returns, (tuple forms) lay the rows' bounds into the
+// workspace, launch, hipGetLastError.  That is written here once per form; an entry point names itself, its owner and its operands
+// and writes its launch.  The launch runs after the owner is entered and takes the table views itself: a table that grew since
+// the last call has another one.  What differs between the callers comes in through the owner and the launch alone.
+//
+// An owner is what a call enters and whose table the checks run on.  It holds its locks for as long as the frame runs and carries:
+//   present()      a refusal in the owner's words where there is nothing to enter, in front of everything else;
+//   table()        the table the checks run on;
+//   enter(s)       lock and enter on s;
+//   FORWARD_HINT, GRADIENT_HINT   what NEEDS_DIM advises instead;
+//   OUT_IS_GRAD    behind the entry point's name, the prefix of the forward's checks where grad_out stands in the place of out.
+struct TableOwner {
+  static constexpr const char* FORWARD_HINT = " (use tfra_unique + tfra_table_find + tfra_sparse_segment_combine otherwise)";
+  static constexpr const char* GRADIENT_HINT = " (use tfra_table_find + tfra_sparse_segment_combine_backprop_weights otherwise)";
+  static constexpr const char* OUT_IS_GRAD = " (out = grad_out): ";
+  Table* t;
+  std::unique_lock<std::mutex> lock;
+  explicit TableOwner(tfra_table_t* tp) : t(reinterpret_cast<Table*>(tp)) {}
+  Check present() const { return Check{}; }   // a NULL table is the checks' "null table"
+  Table* table() const { return t; }
+  int enter(hipStream_t s) {
+    lock = std::unique_lock<std::mutex>(t->mu);
+    return t->enter(s);
+  }
+};
+
+// the bounds of a tuple call's rows, [2 * n_rows] ints at the head of the workspace (comb_bounds: a memset and one launch)
+int pooled_bounds(tfra_workspace* ws, hipStream_t s, size_t nnz, const int64_t* seg, size_t n_rows, int** se) {
+  if (int rc = ws->ensure((2 * n_rows * sizeof(int) + 255) / 256 * 256, s)) return rc;
+  *se = (int*)ws->buf;
+  return comb_bounds(s, nnz, seg, n_rows, *se);
+}
+
+// The forward frames.  out_checked: what the twin's checks look at (out, or out_for_twin(*out)); out and elem: the address the
+// nnz == 0 shortcut zeroes and the bytes of an output element (4, or 2 for half outputs: +0.0 is all-zero bits in every type).
+// launch(se) / launch(): the unit's kernel over the rows' bounds / over row_splits.
+template <class Owner, class Launch>
+int find_combine_call(const char* who, Owner owner, tfra_workspace* ws, size_t nnz, const int64_t* ids, const int64_t* seg,
+                      const float* weights, int combiner, size_t n_rows, const void* default_row, const float* out_checked, void* out,
+                      size_t elem, hipStream_t s, Launch&& launch) {
+  if (const Check e = owner.present(); e.code) return report(std::string(who) + ": ", e);
+  Check c = check_find_combine(owner.table(), ws, nnz, ids, seg, weights, combiner, n_rows, default_row, out_checked,
+                               [&] { return Check{owner.enter(s)}; });
+  if (c.msg == NEEDS_DIM) c.msg += Owner::FORWARD_HINT;
+  if (c.code) return report(std::string(who) + ": ", c);
+  if (!c.active) return TFRA_OK;
+  if (nnz == 0) {
+    const int dim = owner.table()->opts.dim;
+    HIP_TRY(hipMemsetAsync(out, 0, n_rows * (size_t)dim * elem, s));
+    return TFRA_OK;
+  }
+  int* se;
+  if (int rc = pooled_bounds(ws, s, nnz, seg, n_rows, &se)) return rc;
+  launch(se);
+  HIP_TRY(hipGetLastError());
+  return TFRA_OK;
+}
+
+template <class Owner, class Launch>
+int find_combine_ragged_call(const char* who, Owner owner, size_t n_rows, const int64_t* row_splits, size_t nnz, const int64_t* ids,
+                             const float* weights, int combiner, uint32_t flags, const void* default_row, const float* out_checked,
+                             void* out, size_t elem, hipStream_t s, Launch&& launch) {
+  if (const Check e = owner.present(); e.code) return report(std::string(who) + ": ", e);
+  Check c = check_find_combine_ragged(owner.table(), nullptr, n_rows, row_splits, nnz, ids, weights, combiner, flags, 0, default_row,
+                                      out_checked, [&] { return Check{owner.enter(s)}; });
+  if (c.msg == NEEDS_DIM) c.msg += Owner::FORWARD_HINT;
+  if (c.code) return report(std::string(who) + ": ", c);
+  if (!c.active) return TFRA_OK;
+  if (nnz == 0 && !(flags & TFRA_RAGGED_FILL)) {
+    const int dim = owner.table()->opts.dim;
+    HIP_TRY(hipMemsetAsync(out, 0, n_rows * (size_t)dim * elem, s));
+    return TFRA_OK;
+  }
+  launch();
+  HIP_TRY(hipGetLastError());
+  return TFRA_OK;
+}
+
+// The weight-gradient frames: the forward's checks with grad_checked (grad_out, or grads_for_twin(*hg)) in the place of out, then
+// dw_out.  No entry: nothing is written.  Otherwise dw_out is zeroed FIRST — an entry in no row, or outside the clamped cover of
+// row_splits, gets 0 — and a call without rows ends there.
+template <class Owner, class Launch>
+int find_combine_wgrad_call(const char* who, Owner owner, tfra_workspace* ws, size_t nnz, const int64_t* ids, const int64_t* seg,
+                            const float* weights, int combiner, size_t n_rows, const void* default_row, const float* grad_checked,
+                            float* dw_out, hipStream_t s, Launch&& launch) {
+  if (const Check e = owner.present(); e.code) return report(std::string(who) + ": ", e);
+  Check c = check_find_combine(owner.table(), ws, nnz, ids, seg, weights, combiner, n_rows, default_row, grad_checked,
+                               [&] { return Check{owner.enter(s)}; });
+  if (c.msg == NEEDS_DIM) c.msg += Owner::GRADIENT_HINT;
+  if (c.code) return report(std::string(who) + Owner::OUT_IS_GRAD, c);
+  if (const Check d = check_dw_out(nnz, dw_out); d.code) return report(std::string(who) + ": ", d);
+  if (nnz == 0) return TFRA_OK;
+  HIP_TRY(hipMemsetAsync(dw_out, 0, nnz * sizeof(float), s));
+  if (!c.active) return TFRA_OK;
+  int* se;
+  if (int rc = pooled_bounds(ws, s, nnz, seg, n_rows, &se)) return rc;
+  launch(se);
+  HIP_TRY(hipGetLastError());
+  return TFRA_OK;
+}
+
+template <class Owner, class Launch>
+int find_combine_ragged_wgrad_call(const char* who, Owner owner, size_t n_rows, const int64_t* row_splits, size_t nnz,
+                                   const int64_t* ids, const float* weights, int combiner, uint32_t flags, const void* default_row,
+                                   const float* grad_checked, float* dw_out, hipStream_t s, Launch&& launch) {
+  if (const Check e = owner.present(); e.code) return report(std::string(who) + ": ", e);
+  Check c = check_find_combine_ragged(owner.table(), nullptr, n_rows, row_splits, nnz, ids, weights, combiner, flags, 0, default_row,
+                                      grad_checked, [&] { return Check{owner.enter(s)}; });
+  if (c.msg == NEEDS_DIM) c.msg += Owner::GRADIENT_HINT;
+  if (c.code) return report(std::string(who) + Owner::OUT_IS_GRAD, c);
+  if (const Check d = check_dw_out(nnz, dw_out); d.code) return report(std::string(who) + ": ", d);
+  if (nnz == 0) return TFRA_OK;
+  HIP_TRY(hipMemsetAsync(dw_out, 0, nnz * sizeof(float), s));
+  if (!c.active) return TFRA_OK;
+  launch();
+  HIP_TRY(hipGetLastError());
+  return TFRA_OK;
+}
+// what the weight gradients' ragged ladder takes as its fourth axis: PRUNE.  FILL changes nothing (a row that takes the fill row has
+// no members: its entries are 0 whatever fill_id holds), and PRUNE without weights neither.
+bool wgrad_prune(uint32_t flags, const float* weights) { return (flags & TFRA_RAGGED_PRUNE) && weights; }
 
 }  // namespace
 }  // namespace tfra

@@ -10,7 +10,9 @@
 // tfra_multi_find_combine is the same lookup for a list of tables; its host side is the frame the grouped lookup over tiers shares
 // (multi_find_combine_frame, tfra_tierpool_many.hip, on the grouped-call pieces of tfra_many.h), which launches this unit's kernels
 // through launch_find_combine_many.  Both calls run ONE function for their argument checks (check_find_combine) and one launch
-// ladder (with_pool_class); those live in tfra_pool.h, which the gradient of the lookup's weights (tfra_wgrad.hip) shares.
+// ladder (with_pool_class); those live in tfra_pool.h, which the gradient of the lookup's weights (tfra_wgrad.hip) shares.  The host
+// side of the two SINGLE calls is tfra_pool.h's too (find_combine_call, find_combine_ragged_call over a TableOwner): an entry point
+// here names itself and its operands and writes its launch.
 // tfra_table_find_combine_ragged / tfra_multi_find_combine_ragged are the two calls over a rank-2 RaggedTensor (PY/ragged_embedding_ops.py:
 // 129-442): the row's entry range comes from row_splits, so ONE launch serves a call, and safe_embedding_lookup_sparse's pruning by
 // weight and its default_id run inside that launch (find_combine_row's RAGGED and SAFE axes; check_find_combine_ragged, with_ragged_class).
@@ -105,32 +107,16 @@ extern "C" int tfra_table_find_combine(tfra_table_t* tp, tfra_workspace_t* ws, s
                                        tfra_stream_t stream) {
   Table* t = reinterpret_cast<Table*>(tp);
   hipStream_t s = (hipStream_t)stream;
-  std::unique_lock<std::mutex> lock;
-  Check c = check_find_combine(t, ws, nnz, ids, seg, weights, combiner, n_rows, default_row, out, [&] {
-    lock = std::unique_lock<std::mutex>(t->mu);
-    return Check{t->enter(s)};
+  return find_combine_call("find_combine", TableOwner(tp), ws, nnz, ids, seg, weights, combiner, n_rows, default_row, out, out,
+                           sizeof(float), s, [&](const int* se) {
+    const int dim = t->opts.dim;
+    const TableView v = t->view_of(t->cur);
+    const unsigned grid = (unsigned)((n_rows * 16 + 255) / 256);
+    with_pool_class(st_index(t->opts.value_dtype), nch_index(dim), [&](auto DT, auto U, auto NCH) {
+      find_combine_kernel<DT, U, NCH><<<grid, 256, 0, s>>>(v, n_rows, dim, (const i64*)ids, weights, se, combiner,
+                                                                 (const unsigned char*)default_row, out);
+    });
   });
-  if (c.msg == NEEDS_DIM) c.msg += " (use tfra_unique + tfra_table_find + tfra_sparse_segment_combine otherwise)";
-  if (c.code) return report("find_combine: ", c);
-  if (!c.active) return TFRA_OK;
-  const int dim = t->opts.dim;
-  if (nnz == 0) {
-    HIP_TRY(hipMemsetAsync(out, 0, n_rows * (size_t)dim * sizeof(float), s));
-    return TFRA_OK;
-  }
-  int rc = ws->ensure((2 * n_rows * sizeof(int) + 255) / 256 * 256, s);
-  if (rc) return rc;
-  int* se = (int*)ws->buf;
-  rc = comb_bounds(s, nnz, seg, n_rows, se);
-  if (rc) return rc;
-  const TableView v = t->view_of(t->cur);
-  const unsigned grid = (unsigned)((n_rows * 16 + 255) / 256);
-  with_pool_class(st_index(t->opts.value_dtype), nch_index(dim), [&](auto DT, auto U, auto NCH) {
-    find_combine_kernel<DT, U, NCH><<<grid, 256, 0, s>>>(v, n_rows, dim, (const i64*)ids, weights, se, combiner,
-                                                               (const unsigned char*)default_row, out);
-  });
-  HIP_TRY(hipGetLastError());
-  return TFRA_OK;
 }
 
 namespace tfra {
@@ -183,28 +169,17 @@ extern "C" int tfra_table_find_combine_ragged(tfra_table_t* tp, size_t n_rows, c
                                               const void* default_row, float* out, tfra_stream_t stream) {
   Table* t = reinterpret_cast<Table*>(tp);
   hipStream_t s = (hipStream_t)stream;
-  std::unique_lock<std::mutex> lock;
-  Check c = check_find_combine_ragged(t, nullptr, n_rows, row_splits, nnz, ids, weights, combiner, flags, 0, default_row, out, [&] {
-    lock = std::unique_lock<std::mutex>(t->mu);
-    return Check{t->enter(s)};
+  return find_combine_ragged_call("find_combine_ragged", TableOwner(tp), n_rows, row_splits, nnz, ids, weights, combiner, flags,
+                                  default_row, out, out, sizeof(float), s, [&] {
+    const int dim = t->opts.dim;
+    const TableView v = t->view_of(t->cur);
+    const unsigned grid = (unsigned)((n_rows * 16 + 255) / 256);
+    with_ragged_class(st_index(t->opts.value_dtype), nch_index(dim), ragged_safe(flags, weights), [&](auto DT, auto U, auto NCH, auto SAFE) {
+      find_combine_ragged_kernel<DT, U, NCH, SAFE><<<grid, 256, 0, s>>>(v, n_rows, dim, (const i64*)ids, weights, (const i64*)row_splits,
+                                                                             (int)nnz, combiner, flags, (i64)fill_id,
+                                                                             (const unsigned char*)default_row, out);
+    });
   });
-  if (c.msg == NEEDS_DIM) c.msg += " (use tfra_unique + tfra_table_find + tfra_sparse_segment_combine otherwise)";
-  if (c.code) return report("find_combine_ragged: ", c);
-  if (!c.active) return TFRA_OK;
-  const int dim = t->opts.dim;
-  if (nnz == 0 && !(flags & TFRA_RAGGED_FILL)) {
-    HIP_TRY(hipMemsetAsync(out, 0, n_rows * (size_t)dim * sizeof(float), s));
-    return TFRA_OK;
-  }
-  const TableView v = t->view_of(t->cur);
-  const unsigned grid = (unsigned)((n_rows * 16 + 255) / 256);
-  with_ragged_class(st_index(t->opts.value_dtype), nch_index(dim), ragged_safe(flags, weights), [&](auto DT, auto U, auto NCH, auto SAFE) {
-    find_combine_ragged_kernel<DT, U, NCH, SAFE><<<grid, 256, 0, s>>>(v, n_rows, dim, (const i64*)ids, weights, (const i64*)row_splits,
-                                                                           (int)nnz, combiner, flags, (i64)fill_id,
-                                                                           (const unsigned char*)default_row, out);
-  });
-  HIP_TRY(hipGetLastError());
-  return TFRA_OK;
 }
 
 static PoolDesc plain_ragged_desc_at(const void* descs, size_t i) {

@@ -4,9 +4,9 @@
 // ids pooled by sum or mean — leaves a handful of waves walking their rows one latency after the other.  Here ONE 256-thread block
 // owns an output row: its 16 groups probe and read the row's entries in parallel, window by window, and the adds alone stay serial,
 // in entry order and with the twins' expressions (the bodies and why the bits are the twins': tfra_pool_long_device.h).
-// The calls take their twins' argument lists and run their twins' checks (check_find_combine, check_find_combine_ragged,
-// check_dw_out: tfra_pool.h), lock and nnz == 0 shortcut; the tuple forms keep the memset and the bounds launch, the ragged forward
-// is one launch.  float32 out and grad_out only: no typed, tiered or grouped forms.
+// The calls take their twins' argument lists and run their twins' host frames (the four *_call templates of tfra_pool.h over a
+// TableOwner: checks, lock, early returns, the tuple forms' memset and bounds launch); what stands here is each call's launch.  The
+// ragged forward is one launch.  float32 out and grad_out only: no typed, tiered or grouped forms.
 #include <hip/hip_runtime.h>
 
 #include <mutex>
@@ -50,31 +50,15 @@ extern "C" int tfra_table_find_combine_long(tfra_table_t* tp, tfra_workspace_t* 
                                             tfra_stream_t stream) {
   Table* t = reinterpret_cast<Table*>(tp);
   hipStream_t s = (hipStream_t)stream;
-  std::unique_lock<std::mutex> lock;
-  Check c = check_find_combine(t, ws, nnz, ids, seg, weights, combiner, n_rows, default_row, out, [&] {
-    lock = std::unique_lock<std::mutex>(t->mu);
-    return Check{t->enter(s)};
+  return find_combine_call("find_combine_long", TableOwner(tp), ws, nnz, ids, seg, weights, combiner, n_rows, default_row, out, out,
+                           sizeof(float), s, [&](const int* se) {
+    const int dim = t->opts.dim;
+    const TableView v = t->view_of(t->cur);
+    with_pool_class(st_index(t->opts.value_dtype), nch_index(dim), [&](auto DT, auto, auto NCH) {
+      find_combine_long_kernel<DT, NCH, false, false><<<(unsigned)n_rows, LONG_THREADS, 0, s>>>(
+          v, n_rows, dim, (const i64*)ids, weights, se, RaggedArgs{}, combiner, (const unsigned char*)default_row, out);
+    });
   });
-  if (c.msg == NEEDS_DIM) c.msg += " (use tfra_unique + tfra_table_find + tfra_sparse_segment_combine otherwise)";
-  if (c.code) return report("find_combine_long: ", c);
-  if (!c.active) return TFRA_OK;
-  const int dim = t->opts.dim;
-  if (nnz == 0) {
-    HIP_TRY(hipMemsetAsync(out, 0, n_rows * (size_t)dim * sizeof(float), s));
-    return TFRA_OK;
-  }
-  int rc = ws->ensure((2 * n_rows * sizeof(int) + 255) / 256 * 256, s);
-  if (rc) return rc;
-  int* se = (int*)ws->buf;
-  rc = comb_bounds(s, nnz, seg, n_rows, se);
-  if (rc) return rc;
-  const TableView v = t->view_of(t->cur);
-  with_pool_class(st_index(t->opts.value_dtype), nch_index(dim), [&](auto DT, auto, auto NCH) {
-    find_combine_long_kernel<DT, NCH, false, false><<<(unsigned)n_rows, LONG_THREADS, 0, s>>>(
-        v, n_rows, dim, (const i64*)ids, weights, se, RaggedArgs{}, combiner, (const unsigned char*)default_row, out);
-  });
-  HIP_TRY(hipGetLastError());
-  return TFRA_OK;
 }
 
 extern "C" int tfra_table_find_combine_ragged_long(tfra_table_t* tp, size_t n_rows, const int64_t* row_splits, size_t nnz,
@@ -82,89 +66,49 @@ extern "C" int tfra_table_find_combine_ragged_long(tfra_table_t* tp, size_t n_ro
                                                    int64_t fill_id, const void* default_row, float* out, tfra_stream_t stream) {
   Table* t = reinterpret_cast<Table*>(tp);
   hipStream_t s = (hipStream_t)stream;
-  std::unique_lock<std::mutex> lock;
-  Check c = check_find_combine_ragged(t, nullptr, n_rows, row_splits, nnz, ids, weights, combiner, flags, 0, default_row, out, [&] {
-    lock = std::unique_lock<std::mutex>(t->mu);
-    return Check{t->enter(s)};
+  return find_combine_ragged_call("find_combine_ragged_long", TableOwner(tp), n_rows, row_splits, nnz, ids, weights, combiner, flags,
+                                  default_row, out, out, sizeof(float), s, [&] {
+    const int dim = t->opts.dim;
+    const TableView v = t->view_of(t->cur);
+    const RaggedArgs rg{(const i64*)row_splits, (int)nnz, flags, (i64)fill_id};
+    with_ragged_class(st_index(t->opts.value_dtype), nch_index(dim), ragged_safe(flags, weights), [&](auto DT, auto, auto NCH, auto SAFE) {
+      find_combine_long_kernel<DT, NCH, true, SAFE><<<(unsigned)n_rows, LONG_THREADS, 0, s>>>(
+          v, n_rows, dim, (const i64*)ids, weights, nullptr, rg, combiner, (const unsigned char*)default_row, out);
+    });
   });
-  if (c.msg == NEEDS_DIM) c.msg += " (use tfra_unique + tfra_table_find + tfra_sparse_segment_combine otherwise)";
-  if (c.code) return report("find_combine_ragged_long: ", c);
-  if (!c.active) return TFRA_OK;
-  const int dim = t->opts.dim;
-  if (nnz == 0 && !(flags & TFRA_RAGGED_FILL)) {
-    HIP_TRY(hipMemsetAsync(out, 0, n_rows * (size_t)dim * sizeof(float), s));
-    return TFRA_OK;
-  }
-  const TableView v = t->view_of(t->cur);
-  const RaggedArgs rg{(const i64*)row_splits, (int)nnz, flags, (i64)fill_id};
-  with_ragged_class(st_index(t->opts.value_dtype), nch_index(dim), ragged_safe(flags, weights), [&](auto DT, auto, auto NCH, auto SAFE) {
-    find_combine_long_kernel<DT, NCH, true, SAFE><<<(unsigned)n_rows, LONG_THREADS, 0, s>>>(
-        v, n_rows, dim, (const i64*)ids, weights, nullptr, rg, combiner, (const unsigned char*)default_row, out);
-  });
-  HIP_TRY(hipGetLastError());
-  return TFRA_OK;
 }
 
 extern "C" int tfra_table_find_combine_backprop_weights_long(tfra_table_t* tp, tfra_workspace_t* ws, size_t nnz, const int64_t* ids,
                                                              const int64_t* seg, const float* weights, int combiner, size_t n_rows,
                                                              const void* default_row, const float* grad_out, float* dw_out,
                                                              tfra_stream_t stream) {
-  const std::string who = "find_combine_backprop_weights_long";
   Table* t = reinterpret_cast<Table*>(tp);
   hipStream_t s = (hipStream_t)stream;
-  std::unique_lock<std::mutex> lock;
-  Check c = check_find_combine(t, ws, nnz, ids, seg, weights, combiner, n_rows, default_row, grad_out, [&] {
-    lock = std::unique_lock<std::mutex>(t->mu);
-    return Check{t->enter(s)};
+  return find_combine_wgrad_call("find_combine_backprop_weights_long", TableOwner(tp), ws, nnz, ids, seg, weights, combiner, n_rows,
+                                 default_row, grad_out, dw_out, s, [&](const int* se) {
+    const int dim = t->opts.dim;
+    const TableView v = t->view_of(t->cur);
+    with_pool_class(st_index(t->opts.value_dtype), nch_index(dim), [&](auto DT, auto, auto NCH) {
+      wgrad_long_kernel<DT, NCH, false, false><<<(unsigned)n_rows, LONG_THREADS, 0, s>>>(
+          v, n_rows, dim, (const i64*)ids, weights, se, RaggedArgs{}, combiner, (const unsigned char*)default_row, grad_out, dw_out);
+    });
   });
-  if (c.msg == NEEDS_DIM) c.msg += " (use tfra_table_find + tfra_sparse_segment_combine_backprop_weights otherwise)";
-  if (c.code) return report(who + " (out = grad_out): ", c);
-  if (Check d = check_dw_out(nnz, dw_out); d.code) return report(who + ": ", d);
-  if (nnz == 0) return TFRA_OK;
-  HIP_TRY(hipMemsetAsync(dw_out, 0, nnz * sizeof(float), s));   // entries in no row: 0
-  if (!c.active) return TFRA_OK;                                // (no rows)
-  const int dim = t->opts.dim;
-  int rc = ws->ensure((2 * n_rows * sizeof(int) + 255) / 256 * 256, s);
-  if (rc) return rc;
-  int* se = (int*)ws->buf;
-  rc = comb_bounds(s, nnz, seg, n_rows, se);
-  if (rc) return rc;
-  const TableView v = t->view_of(t->cur);
-  with_pool_class(st_index(t->opts.value_dtype), nch_index(dim), [&](auto DT, auto, auto NCH) {
-    wgrad_long_kernel<DT, NCH, false, false><<<(unsigned)n_rows, LONG_THREADS, 0, s>>>(
-        v, n_rows, dim, (const i64*)ids, weights, se, RaggedArgs{}, combiner, (const unsigned char*)default_row, grad_out, dw_out);
-  });
-  HIP_TRY(hipGetLastError());
-  return TFRA_OK;
 }
 
 extern "C" int tfra_table_find_combine_ragged_backprop_weights_long(tfra_table_t* tp, size_t n_rows, const int64_t* row_splits,
                                                                     size_t nnz, const int64_t* ids, const float* weights, int combiner,
                                                                     uint32_t flags, int64_t fill_id, const void* default_row,
                                                                     const float* grad_out, float* dw_out, tfra_stream_t stream) {
-  const std::string who = "find_combine_ragged_backprop_weights_long";
   Table* t = reinterpret_cast<Table*>(tp);
   hipStream_t s = (hipStream_t)stream;
-  std::unique_lock<std::mutex> lock;
-  Check c = check_find_combine_ragged(t, nullptr, n_rows, row_splits, nnz, ids, weights, combiner, flags, 0, default_row, grad_out, [&] {
-    lock = std::unique_lock<std::mutex>(t->mu);
-    return Check{t->enter(s)};
+  return find_combine_ragged_wgrad_call("find_combine_ragged_backprop_weights_long", TableOwner(tp), n_rows, row_splits, nnz, ids,
+                                        weights, combiner, flags, default_row, grad_out, dw_out, s, [&] {
+    const int dim = t->opts.dim;
+    const TableView v = t->view_of(t->cur);
+    const RaggedArgs rg{(const i64*)row_splits, (int)nnz, flags, (i64)fill_id};   // (fill_id is not looked up: a filled row has no members)
+    with_ragged_class(st_index(t->opts.value_dtype), nch_index(dim), wgrad_prune(flags, weights), [&](auto DT, auto, auto NCH, auto PRUNE) {
+      wgrad_long_kernel<DT, NCH, true, PRUNE><<<(unsigned)n_rows, LONG_THREADS, 0, s>>>(
+          v, n_rows, dim, (const i64*)ids, weights, nullptr, rg, combiner, (const unsigned char*)default_row, grad_out, dw_out);
+    });
   });
-  if (c.msg == NEEDS_DIM) c.msg += " (use tfra_table_find + tfra_sparse_segment_combine_backprop_weights otherwise)";
-  if (c.code) return report(who + " (out = grad_out): ", c);
-  if (Check d = check_dw_out(nnz, dw_out); d.code) return report(who + ": ", d);
-  if (nnz == 0) return TFRA_OK;
-  HIP_TRY(hipMemsetAsync(dw_out, 0, nnz * sizeof(float), s));   // entries outside the clamped cover: 0
-  if (!c.active) return TFRA_OK;                                // (no rows)
-  const int dim = t->opts.dim;
-  const TableView v = t->view_of(t->cur);
-  const RaggedArgs rg{(const i64*)row_splits, (int)nnz, flags, (i64)fill_id};   // (fill_id is not looked up: a filled row has no members)
-  // the ladder's fourth axis is PRUNE here, as in the twin: FILL changes nothing, and PRUNE without weights neither
-  with_ragged_class(st_index(t->opts.value_dtype), nch_index(dim), (flags & TFRA_RAGGED_PRUNE) && weights,
-                    [&](auto DT, auto, auto NCH, auto PRUNE) {
-    wgrad_long_kernel<DT, NCH, true, PRUNE><<<(unsigned)n_rows, LONG_THREADS, 0, s>>>(
-        v, n_rows, dim, (const i64*)ids, weights, nullptr, rg, combiner, (const unsigned char*)default_row, grad_out, dw_out);
-  });
-  HIP_TRY(hipGetLastError());
-  return TFRA_OK;
 }

@@ -4,7 +4,8 @@
 // either ABI (PoolDesc) — check every descriptor, classify, lock, lay out, fill, send, launch (tfra_many.h).
 // The grouped weight gradients (tfra_multi_find_combine[_ragged]_backprop_weights: tfra_wgrad_many.hip) read the same
 // descriptor and take the same steps: what a frame needs for them — a descriptor's owner, its class, the records' order, the
-// locks — is at the end of this file, ONE copy for the three units.
+// classes' block prefixes (put_classes), the locks — is at the end of this file, ONE copy for the three units.
+// (The SINGLE calls' frames are tfra_pool.h's.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -143,6 +144,14 @@ int order_by_class(const std::string& who, const std::vector<PoolDesc>& ds, cons
   }
   first[n_class] = order->size();
   return TFRA_OK;
+}
+// The classes' block prefixes for records that stand in that order: class c is the range [first[c], first[c + 1]) of them and needs
+// no index; record k owns row_blocks(ds[order[k]]) blocks.
+void put_classes(ClassPool& pool, const std::vector<PoolDesc>& ds, const std::vector<size_t>& order, const size_t* first, int n_class,
+                 ManyClass* row_cls) {
+  for (int c = 0; c < n_class; ++c)
+    row_cls[c] = pool.put(order.size(), false, [&](size_t k) { return k >= first[c] && k < first[c + 1]; },
+                          [&](size_t k) { return row_blocks(ds[order[k]]); });
 }
 
 // The locks of a call (TierLocks, lock_tiers_and_tables: tfra_tier.h, shared with the grouped admission): each distinct tier's own

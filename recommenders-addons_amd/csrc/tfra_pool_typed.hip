@@ -4,8 +4,9 @@
 // with its OT axis, which narrows the float4 at the function's two stores and nowhere else.  A float32 output forwards to the twin.
 // The four kernels are tfra_pool.hip's with that axis.  They are instantiated HERE, under names of their own, for the two half
 // outputs only: the untyped kernels keep their names, their unit and their code (profiles/typed_lookup_isa_stats.txt).
-// Host side: the single calls run the twins' checks (check_find_combine / check_find_combine_ragged, tfra_pool.h) behind the check
-// of the output record (check_rows_out) and the twins' launch ladders with the output type in front; the grouped calls are the
+// Host side: the single calls run the twins' frames (find_combine_call / find_combine_ragged_call, tfra_pool.h: out_for_twin(*out)
+// for the checks, 2-byte elements for the zeros) behind the check of the output record (check_rows_out) and the float32 shortcut,
+// and launch through the twins' ladders with the output type in front; the grouped calls are the
 // twins' frames (tfra_pool_many.h), where the output type is one more launch-class axis.
 #include <hip/hip_runtime.h>
 
@@ -114,32 +115,16 @@ extern "C" int tfra_table_find_combine_typed(tfra_table_t* tp, tfra_workspace_t*
     return tfra_table_find_combine(tp, ws, nnz, ids, seg, weights, combiner, n_rows, default_row, static_cast<float*>(out->rows), stream);
   Table* t = reinterpret_cast<Table*>(tp);
   hipStream_t s = (hipStream_t)stream;
-  std::unique_lock<std::mutex> lock;
-  Check c = check_find_combine(t, ws, nnz, ids, seg, weights, combiner, n_rows, default_row, out_for_twin(*out), [&] {
-    lock = std::unique_lock<std::mutex>(t->mu);
-    return Check{t->enter(s)};
+  return find_combine_call("find_combine_typed", TableOwner(tp), ws, nnz, ids, seg, weights, combiner, n_rows, default_row,
+                           out_for_twin(*out), out->rows, 2, s, [&](const int* se) {
+    const int dim = t->opts.dim;
+    const TableView v = t->view_of(t->cur);
+    const unsigned grid = (unsigned)((n_rows * 16 + 255) / 256);
+    with_pool_out_class(st_index(out->dtype), st_index(t->opts.value_dtype), nch_index(dim), [&](auto DT, auto U, auto NCH, auto OT) {
+      find_combine_typed_kernel<DT, U, NCH, OT><<<grid, 256, 0, s>>>(v, n_rows, dim, (const i64*)ids, weights, se, combiner,
+                                                                       (const unsigned char*)default_row, static_cast<float*>(out->rows));
+    });
   });
-  if (c.msg == NEEDS_DIM) c.msg += " (use tfra_unique + tfra_table_find + tfra_sparse_segment_combine otherwise)";
-  if (c.code) return report("find_combine_typed: ", c);
-  if (!c.active) return TFRA_OK;
-  const int dim = t->opts.dim;
-  if (nnz == 0) {   // the twin's zeros: +0.0 is all-zero bits in every type
-    HIP_TRY(hipMemsetAsync(out->rows, 0, n_rows * (size_t)dim * 2, s));
-    return TFRA_OK;
-  }
-  int rc = ws->ensure((2 * n_rows * sizeof(int) + 255) / 256 * 256, s);
-  if (rc) return rc;
-  int* se = (int*)ws->buf;
-  rc = comb_bounds(s, nnz, seg, n_rows, se);
-  if (rc) return rc;
-  const TableView v = t->view_of(t->cur);
-  const unsigned grid = (unsigned)((n_rows * 16 + 255) / 256);
-  with_pool_out_class(st_index(out->dtype), st_index(t->opts.value_dtype), nch_index(dim), [&](auto DT, auto U, auto NCH, auto OT) {
-    find_combine_typed_kernel<DT, U, NCH, OT><<<grid, 256, 0, s>>>(v, n_rows, dim, (const i64*)ids, weights, se, combiner,
-                                                                     (const unsigned char*)default_row, static_cast<float*>(out->rows));
-  });
-  HIP_TRY(hipGetLastError());
-  return TFRA_OK;
 }
 
 extern "C" int tfra_table_find_combine_ragged_typed(tfra_table_t* tp, size_t n_rows, const int64_t* row_splits, size_t nnz,
@@ -152,31 +137,19 @@ extern "C" int tfra_table_find_combine_ragged_typed(tfra_table_t* tp, size_t n_r
                                           static_cast<float*>(out->rows), stream);
   Table* t = reinterpret_cast<Table*>(tp);
   hipStream_t s = (hipStream_t)stream;
-  std::unique_lock<std::mutex> lock;
-  Check c = check_find_combine_ragged(t, nullptr, n_rows, row_splits, nnz, ids, weights, combiner, flags, 0, default_row,
-                                      out_for_twin(*out), [&] {
-    lock = std::unique_lock<std::mutex>(t->mu);
-    return Check{t->enter(s)};
+  return find_combine_ragged_call("find_combine_ragged_typed", TableOwner(tp), n_rows, row_splits, nnz, ids, weights, combiner, flags,
+                                  default_row, out_for_twin(*out), out->rows, 2, s, [&] {
+    const int dim = t->opts.dim;
+    const TableView v = t->view_of(t->cur);
+    const unsigned grid = (unsigned)((n_rows * 16 + 255) / 256);
+    with_ragged_out_class(st_index(out->dtype), st_index(t->opts.value_dtype), nch_index(dim), ragged_safe(flags, weights),
+                          [&](auto DT, auto U, auto NCH, auto SAFE, auto OT) {
+      find_combine_ragged_typed_kernel<DT, U, NCH, SAFE, OT><<<grid, 256, 0, s>>>(v, n_rows, dim, (const i64*)ids, weights,
+                                                                                    (const i64*)row_splits, (int)nnz, combiner, flags,
+                                                                                    (i64)fill_id, (const unsigned char*)default_row,
+                                                                                    static_cast<float*>(out->rows));
+    });
   });
-  if (c.msg == NEEDS_DIM) c.msg += " (use tfra_unique + tfra_table_find + tfra_sparse_segment_combine otherwise)";
-  if (c.code) return report("find_combine_ragged_typed: ", c);
-  if (!c.active) return TFRA_OK;
-  const int dim = t->opts.dim;
-  if (nnz == 0 && !(flags & TFRA_RAGGED_FILL)) {
-    HIP_TRY(hipMemsetAsync(out->rows, 0, n_rows * (size_t)dim * 2, s));
-    return TFRA_OK;
-  }
-  const TableView v = t->view_of(t->cur);
-  const unsigned grid = (unsigned)((n_rows * 16 + 255) / 256);
-  with_ragged_out_class(st_index(out->dtype), st_index(t->opts.value_dtype), nch_index(dim), ragged_safe(flags, weights),
-                        [&](auto DT, auto U, auto NCH, auto SAFE, auto OT) {
-    find_combine_ragged_typed_kernel<DT, U, NCH, SAFE, OT><<<grid, 256, 0, s>>>(v, n_rows, dim, (const i64*)ids, weights,
-                                                                                  (const i64*)row_splits, (int)nnz, combiner, flags,
-                                                                                  (i64)fill_id, (const unsigned char*)default_row,
-                                                                                  static_cast<float*>(out->rows));
-  });
-  HIP_TRY(hipGetLastError());
-  return TFRA_OK;
 }
 
 // ---- the grouped calls: the twins' frames over descriptors that carry an output record ------------------------------------------------

@@ -1,6 +1,7 @@
 // What the tier calls of a table (tfra_tier.hip) share with the tier driver (tfra_tierstep.hip): the block shape of
 // find_missed_kernel, the miss list it appends to, and its ONE launcher; and what the driver shares with the tier's pooled lookup
-// (tfra_tierpool.hip) and its weight gradient (tfra_tierwgrad.hip): the driver's object and the locks a call on it takes; and with
+// (tfra_tierpool.hip) and its weight gradient (tfra_tierwgrad.hip): the driver's object, the locks a call on it takes and the tier as
+// the owner of a single pooled call (TierOwner, for the frames of tfra_pool.h); and with
 // the grouped admission (tfra_tierstep_many.hip): the checks of tfra_tier_find_or_insert, the fetch's operands, the grouped locks;
 // and with the planned admission (tfra_tierplan.hip): the stages of the chain behind its own key launch.
 #pragma once
@@ -76,6 +77,21 @@ static inline int tier_enter(tfra_tier* tier, hipStream_t s, TierEntry* e) {
   e->own = std::unique_lock<std::mutex>(tier->mu);
   return tfra::lock_and_enter({tier->upper, tier->lower}, s, &e->tables);
 }
+
+// A tier as the owner of a single pooled call, for the frames of tfra_pool.h (what TableOwner is for one table): the checks run on the
+// upper table — tfra_tier_create has made sure that both tables have its value dtype, dim and device — and the call holds the
+// driver's lock and both tables'.  A NULL tier is refused in front of everything else.  (Hidden, as TableOwner is.)
+struct __attribute__((visibility("hidden"))) TierOwner {
+  static constexpr const char* FORWARD_HINT = " (use tfra_unique + tfra_tier_find + tfra_sparse_segment_combine otherwise)";
+  static constexpr const char* GRADIENT_HINT = " (use tfra_unique + tfra_tier_find + tfra_sparse_segment_combine_backprop_weights otherwise)";
+  static constexpr const char* OUT_IS_GRAD = ": (out = grad_out) ";
+  tfra_tier* tier;
+  TierEntry entry;
+  explicit TierOwner(tfra_tier* t) : tier(t) {}
+  tfra::Check present() const { return tier ? tfra::Check{} : tfra::refuse(TFRA_ERR_INVALID, "null tier"); }
+  tfra::Table* table() const { return tier->upper; }
+  int enter(hipStream_t s) { return tier_enter(tier, s, &entry); }
+};
 
 // The locks of a grouped call over tiers: each distinct tier's own mutex once, in address order, BEFORE any table lock — the
 // hierarchy of tier_enter — then every table of the call (plain ones, uppers and lowers) once, in the global order, entered on s.

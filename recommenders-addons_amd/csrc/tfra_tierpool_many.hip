@@ -7,6 +7,7 @@
 // plain members of a list run the kernels of tfra_pool.hip through its launchers (one instantiation of each kernel in the library).
 // The host side of all four grouped pooled calls is here, ONE frame per form over a descriptor of either ABI (PoolDesc,
 // tfra_pool_many.h): tfra_multi_find_combine / _ragged (tfra_pool.hip) call the same two functions with descriptors that name no tier.
+// (The frames of the SINGLE calls, grouped or not in their units, are tfra_pool.h's.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -140,12 +141,9 @@ int multi_find_combine_frame(const char* who_c, tfra_workspace* ws, size_t n_tab
     if (d.tier) trecs[k - n_plain] = TierManyRec{r, d.tier->lower->view_of(d.tier->lower->cur)};
     else recs[k] = r;
   }
-  // the records stand in class order: a class is a range of them and needs no index
   ClassPool cpool{section<unsigned>(up.host, cpre_off)};
   ManyClass row_cls[NCLASS];
-  for (int c = 0; c < NCLASS; ++c)
-    row_cls[c] = cpool.put(n_act, false, [&](size_t k) { return k >= first[c] && k < first[c + 1]; },
-                           [&](size_t k) { return row_blocks(ds[order[k]]); });
+  put_classes(cpool, ds, order, first, NCLASS, row_cls);
   auto bounded = [&](size_t i) { return cls[i] >= 0 && ds[i].nnz != 0; };
   {
     size_t k = 0;
@@ -234,9 +232,7 @@ int multi_find_combine_ragged_frame(const char* who_c, tfra_workspace* ws, size_
   }
   ClassPool cpool{section<unsigned>(up.host, cpre_off)};
   ManyClass row_cls[NCLASS];
-  for (int c = 0; c < NCLASS; ++c)
-    row_cls[c] = cpool.put(n_act, false, [&](size_t k) { return k >= first[c] && k < first[c + 1]; },
-                           [&](size_t k) { return row_blocks(ds[order[k]]); });
+  put_classes(cpool, ds, order, first, NCLASS, row_cls);
   rc = many_send(up, s, "hipMemcpyAsync(d_blob, h, blob_bytes, hipMemcpyHostToDevice, s)", true);
   if (rc) return rc;
   uint32_t launches = 0;

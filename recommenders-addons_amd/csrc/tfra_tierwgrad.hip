@@ -6,8 +6,8 @@
 // staging, so the batch is not limited by max_batch.
 // The kernels are wgrad_row (tfra_wgrad_device.h) with its TIER axis: the mapping, the entry batching and the arithmetic of the
 // one-table kernels, in the same order, so the result equals tfra_tier_find + tfra_sparse_segment_combine_backprop_weights, and
-// tfra_table_find_combine_backprop_weights on one table that holds the same newest rows, bit for bit.  The host frames are those of
-// tfra_tier_find_combine* (tfra_tierpool.hip) with the one-table gradient's dw_out check, memset and early returns.
+// tfra_table_find_combine_backprop_weights on one table that holds the same newest rows, bit for bit.  The host frames are the one-table
+// gradient's (find_combine_wgrad_call, find_combine_ragged_wgrad_call: tfra_pool.h) over a TierOwner (tfra_tier.h).
 // The *_typed calls are tfra_wgrad.hip's over a tier: the same frames, wgrad_row's GHALF axis in kernels of their own
 // names for a float16 / bfloat16 grad_out, float32 without a scale forwarded to the untyped call.
 #include <hip/hip_runtime.h>
@@ -72,80 +72,53 @@ __global__ __launch_bounds__(256) void tier_wgrad_ragged_half_kernel(TableView u
 }
 
 // The two calls, untyped (hg == nullptr) and over a half grad_out (hg, checked by check_typed; grad_out is what the twin's checks
-// look at then): one function each, fn names the caller in the refusals.
-int tier_wgrad_impl(const std::string& fn, tfra_tier_t* tier, tfra_workspace_t* ws, size_t nnz, const int64_t* ids, const int64_t* seg,
+// look at then): one function each, `who` names the caller in the refusals.
+int tier_wgrad_impl(const char* who, tfra_tier_t* tier, tfra_workspace_t* ws, size_t nnz, const int64_t* ids, const int64_t* seg,
                     const float* weights, int combiner, size_t n_rows, const void* default_row, const float* grad_out,
                     const tfra_grads* hg, float* dw_out, tfra_stream_t stream) {
-  if (!tier) return set_error(TFRA_ERR_INVALID, fn + "null tier");
-  Table* t = tier->upper;
   hipStream_t s = (hipStream_t)stream;
-  TierEntry entry;
-  Check c = check_find_combine(t, ws, nnz, ids, seg, weights, combiner, n_rows, default_row, grad_out,
-                               [&] { return Check{tier_enter(tier, s, &entry)}; });
-  if (c.msg == NEEDS_DIM)
-    c.msg += " (use tfra_unique + tfra_tier_find + tfra_sparse_segment_combine_backprop_weights otherwise)";
-  if (c.code) return report(fn + "(out = grad_out) ", c);
-  if (Check d = check_dw_out(nnz, dw_out); d.code) return report(fn, d);
-  if (nnz == 0) return TFRA_OK;
-  HIP_TRY(hipMemsetAsync(dw_out, 0, nnz * sizeof(float), s));   // entries in no row: 0
-  if (!c.active) return TFRA_OK;                                // (no rows)
-  const int dim = t->opts.dim;
-  int rc = ws->ensure((2 * n_rows * sizeof(int) + 255) / 256 * 256, s);
-  if (rc) return rc;
-  int* se = (int*)ws->buf;
-  rc = comb_bounds(s, nnz, seg, n_rows, se);
-  if (rc) return rc;
-  // the views are taken here, under the locks: a lower table that grew since the last call has another one
-  const TableView up = t->view_of(t->cur), lo = tier->lower->view_of(tier->lower->cur);
-  const unsigned grid = (unsigned)((n_rows * 16 + 255) / 256);
-  with_pool_class(st_index(t->opts.value_dtype), nch_index(dim), [&](auto DT, auto U, auto NCH) {
-    if (hg)
-      tier_wgrad_half_kernel<DT, U, NCH><<<grid, 256, 0, s>>>(up, lo, n_rows, dim, (const i64*)ids, weights, se, combiner,
-                                                              (const unsigned char*)default_row, (const float*)hg->grads, dw_out,
-                                                              hg->d_scale, hg->dtype == TFRA_BF16);
-    else
-      tier_wgrad_kernel<DT, U, NCH><<<grid, 256, 0, s>>>(up, lo, n_rows, dim, (const i64*)ids, weights, se, combiner,
-                                                             (const unsigned char*)default_row, grad_out, dw_out);
+  return find_combine_wgrad_call(who, TierOwner(tier), ws, nnz, ids, seg, weights, combiner, n_rows, default_row, grad_out, dw_out, s,
+                                 [&](const int* se) {
+    Table* t = tier->upper;
+    const int dim = t->opts.dim;
+    // the views are taken here, under the locks: a lower table that grew since the last call has another one
+    const TableView up = t->view_of(t->cur), lo = tier->lower->view_of(tier->lower->cur);
+    const unsigned grid = (unsigned)((n_rows * 16 + 255) / 256);
+    with_pool_class(st_index(t->opts.value_dtype), nch_index(dim), [&](auto DT, auto U, auto NCH) {
+      if (hg)
+        tier_wgrad_half_kernel<DT, U, NCH><<<grid, 256, 0, s>>>(up, lo, n_rows, dim, (const i64*)ids, weights, se, combiner,
+                                                                (const unsigned char*)default_row, (const float*)hg->grads, dw_out,
+                                                                hg->d_scale, hg->dtype == TFRA_BF16);
+      else
+        tier_wgrad_kernel<DT, U, NCH><<<grid, 256, 0, s>>>(up, lo, n_rows, dim, (const i64*)ids, weights, se, combiner,
+                                                               (const unsigned char*)default_row, grad_out, dw_out);
+    });
   });
-  HIP_TRY(hipGetLastError());
-  return TFRA_OK;
 }
 
-int tier_wgrad_ragged_impl(const std::string& fn, tfra_tier_t* tier, size_t n_rows, const int64_t* row_splits, size_t nnz,
-                           const int64_t* ids, const float* weights, int combiner, uint32_t flags, int64_t fill_id,
-                           const void* default_row, const float* grad_out, const tfra_grads* hg, float* dw_out, tfra_stream_t stream) {
-  if (!tier) return set_error(TFRA_ERR_INVALID, fn + "null tier");
-  Table* t = tier->upper;
+// (fill_id is not looked at, in either table: wgrad_prune, tfra_pool.h)
+int tier_wgrad_ragged_impl(const char* who, tfra_tier_t* tier, size_t n_rows, const int64_t* row_splits, size_t nnz, const int64_t* ids,
+                           const float* weights, int combiner, uint32_t flags, int64_t, const void* default_row, const float* grad_out,
+                           const tfra_grads* hg, float* dw_out, tfra_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
-  TierEntry entry;
-  Check c = check_find_combine_ragged(t, nullptr, n_rows, row_splits, nnz, ids, weights, combiner, flags, 0, default_row, grad_out,
-                                      [&] { return Check{tier_enter(tier, s, &entry)}; });
-  if (c.msg == NEEDS_DIM)
-    c.msg += " (use tfra_unique + tfra_tier_find + tfra_sparse_segment_combine_backprop_weights otherwise)";
-  if (c.code) return report(fn + "(out = grad_out) ", c);
-  if (Check d = check_dw_out(nnz, dw_out); d.code) return report(fn, d);
-  (void)fill_id;   // a row that takes the fill row has no members: its entries are 0 whatever fill_id holds, in either table
-  if (nnz == 0) return TFRA_OK;
-  HIP_TRY(hipMemsetAsync(dw_out, 0, nnz * sizeof(float), s));   // entries outside the clamped cover: 0
-  if (!c.active) return TFRA_OK;                                // (no rows)
-  const int dim = t->opts.dim;
-  const TableView up = t->view_of(t->cur), lo = tier->lower->view_of(tier->lower->cur);
-  const unsigned grid = (unsigned)((n_rows * 16 + 255) / 256);
-  // the ladder's fourth axis is PRUNE here, as in the one-table call: FILL changes nothing, and PRUNE without weights neither
-  with_ragged_class(st_index(t->opts.value_dtype), nch_index(dim), (flags & TFRA_RAGGED_PRUNE) && weights,
-                    [&](auto DT, auto U, auto NCH, auto PRUNE) {
-    if (hg)
-      tier_wgrad_ragged_half_kernel<DT, U, NCH, PRUNE><<<grid, 256, 0, s>>>(up, lo, n_rows, dim, (const i64*)ids, weights,
-                                                                            (const i64*)row_splits, (int)nnz, combiner,
-                                                                            (const unsigned char*)default_row, (const float*)hg->grads,
-                                                                            dw_out, hg->d_scale, hg->dtype == TFRA_BF16);
-    else
-      tier_wgrad_ragged_kernel<DT, U, NCH, PRUNE><<<grid, 256, 0, s>>>(up, lo, n_rows, dim, (const i64*)ids, weights,
-                                                                           (const i64*)row_splits, (int)nnz, combiner,
-                                                                           (const unsigned char*)default_row, grad_out, dw_out);
+  return find_combine_ragged_wgrad_call(who, TierOwner(tier), n_rows, row_splits, nnz, ids, weights, combiner, flags, default_row,
+                                        grad_out, dw_out, s, [&] {
+    Table* t = tier->upper;
+    const int dim = t->opts.dim;
+    const TableView up = t->view_of(t->cur), lo = tier->lower->view_of(tier->lower->cur);
+    const unsigned grid = (unsigned)((n_rows * 16 + 255) / 256);
+    with_ragged_class(st_index(t->opts.value_dtype), nch_index(dim), wgrad_prune(flags, weights), [&](auto DT, auto U, auto NCH, auto PRUNE) {
+      if (hg)
+        tier_wgrad_ragged_half_kernel<DT, U, NCH, PRUNE><<<grid, 256, 0, s>>>(up, lo, n_rows, dim, (const i64*)ids, weights,
+                                                                              (const i64*)row_splits, (int)nnz, combiner,
+                                                                              (const unsigned char*)default_row, (const float*)hg->grads,
+                                                                              dw_out, hg->d_scale, hg->dtype == TFRA_BF16);
+      else
+        tier_wgrad_ragged_kernel<DT, U, NCH, PRUNE><<<grid, 256, 0, s>>>(up, lo, n_rows, dim, (const i64*)ids, weights,
+                                                                             (const i64*)row_splits, (int)nnz, combiner,
+                                                                             (const unsigned char*)default_row, grad_out, dw_out);
+    });
   });
-  HIP_TRY(hipGetLastError());
-  return TFRA_OK;
 }
 
 }  // namespace
@@ -154,7 +127,7 @@ extern "C" int tfra_tier_find_combine_backprop_weights(tfra_tier_t* tier, tfra_w
                                                        const int64_t* seg, const float* weights, int combiner, size_t n_rows,
                                                        const void* default_row, const float* grad_out, float* dw_out,
                                                        tfra_stream_t stream) {
-  return tier_wgrad_impl("tfra_tier_find_combine_backprop_weights: ", tier, ws, nnz, ids, seg, weights, combiner, n_rows, default_row,
+  return tier_wgrad_impl("tfra_tier_find_combine_backprop_weights", tier, ws, nnz, ids, seg, weights, combiner, n_rows, default_row,
                          grad_out, nullptr, dw_out, stream);
 }
 
@@ -162,7 +135,7 @@ extern "C" int tfra_tier_find_combine_ragged_backprop_weights(tfra_tier_t* tier,
                                                               const int64_t* ids, const float* weights, int combiner, uint32_t flags,
                                                               int64_t fill_id, const void* default_row, const float* grad_out,
                                                               float* dw_out, tfra_stream_t stream) {
-  return tier_wgrad_ragged_impl("tfra_tier_find_combine_ragged_backprop_weights: ", tier, n_rows, row_splits, nnz, ids, weights, combiner,
+  return tier_wgrad_ragged_impl("tfra_tier_find_combine_ragged_backprop_weights", tier, n_rows, row_splits, nnz, ids, weights, combiner,
                                 flags, fill_id, default_row, grad_out, nullptr, dw_out, stream);
 }
 
@@ -171,13 +144,13 @@ extern "C" int tfra_tier_find_combine_backprop_weights_typed(tfra_tier_t* tier, 
                                                              const int64_t* seg, const float* weights, int combiner, size_t n_rows,
                                                              const void* default_row, const tfra_grads* grad_out, float* dw_out,
                                                              tfra_stream_t stream) {
-  const std::string fn = "tfra_tier_find_combine_backprop_weights_typed: ";
+  const char* who = "tfra_tier_find_combine_backprop_weights_typed";
   bool forward;
-  if (const Check c = check_typed(grad_out, &forward); c.code) return report(fn, c);
+  if (const Check c = check_typed(grad_out, &forward); c.code) return report(std::string(who) + ": ", c);
   if (forward)
     return tfra_tier_find_combine_backprop_weights(tier, ws, nnz, ids, seg, weights, combiner, n_rows, default_row,
                                                    (const float*)grad_out->grads, dw_out, stream);
-  return tier_wgrad_impl(fn, tier, ws, nnz, ids, seg, weights, combiner, n_rows, default_row, grads_for_twin(*grad_out), grad_out, dw_out,
+  return tier_wgrad_impl(who, tier, ws, nnz, ids, seg, weights, combiner, n_rows, default_row, grads_for_twin(*grad_out), grad_out, dw_out,
                          stream);
 }
 
@@ -185,12 +158,12 @@ extern "C" int tfra_tier_find_combine_ragged_backprop_weights_typed(tfra_tier_t*
                                                                     const int64_t* ids, const float* weights, int combiner,
                                                                     uint32_t flags, int64_t fill_id, const void* default_row,
                                                                     const tfra_grads* grad_out, float* dw_out, tfra_stream_t stream) {
-  const std::string fn = "tfra_tier_find_combine_ragged_backprop_weights_typed: ";
+  const char* who = "tfra_tier_find_combine_ragged_backprop_weights_typed";
   bool forward;
-  if (const Check c = check_typed(grad_out, &forward); c.code) return report(fn, c);
+  if (const Check c = check_typed(grad_out, &forward); c.code) return report(std::string(who) + ": ", c);
   if (forward)
     return tfra_tier_find_combine_ragged_backprop_weights(tier, n_rows, row_splits, nnz, ids, weights, combiner, flags, fill_id,
                                                           default_row, (const float*)grad_out->grads, dw_out, stream);
-  return tier_wgrad_ragged_impl(fn, tier, n_rows, row_splits, nnz, ids, weights, combiner, flags, fill_id, default_row,
+  return tier_wgrad_ragged_impl(who, tier, n_rows, row_splits, nnz, ids, weights, combiner, flags, fill_id, default_row,
                                 grads_for_twin(*grad_out), grad_out, dw_out, stream);
 }

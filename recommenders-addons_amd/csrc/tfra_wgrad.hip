@@ -5,7 +5,8 @@
 // row's incoming gradient held in registers where the forward holds its accumulator, and [nnz] floats out.
 // The arithmetic and its ONE evaluation order are tfra_combine_device.h's (wgrad_dot4, wgrad_reduce16, wgrad_s, wgrad_finish), the
 // code seg_combine_wgrad_kernel (tfra_combine.hip: rows from a [U, dim] tensor) compiles, so the two routes agree bit for bit.
-// The argument checks and the launch ladders are the forward's (tfra_pool.h); the kernels' body, wgrad_row, is in
+// The launch ladders are the forward's and the host frame of the two calls stands beside the forward's (find_combine_wgrad_call,
+// find_combine_ragged_wgrad_call over a TableOwner: tfra_pool.h); the kernels' body, wgrad_row, is in
 // tfra_wgrad_device.h, where the tier's kernels (tfra_tierwgrad.hip) find it too.
 // The *_typed calls take grad_out as a tfra_grads: float32 without a scale forwards to the untyped call; a float16 /
 // bfloat16 matrix runs the same host frame and wgrad_row with its GHALF axis, in kernels of their own names (wgrad_half_kernel,
@@ -70,77 +71,51 @@ __global__ __launch_bounds__(256) void wgrad_ragged_half_kernel(TableView v, siz
 
 // The two calls, untyped (hg == nullptr) and over a half grad_out (hg, checked by check_typed; grad_out is what the twin's checks
 // look at then): one function each, `who` names the caller in the refusals.
-int wgrad_impl(const std::string& who, tfra_table_t* tp, tfra_workspace_t* ws, size_t nnz, const int64_t* ids, const int64_t* seg,
+int wgrad_impl(const char* who, tfra_table_t* tp, tfra_workspace_t* ws, size_t nnz, const int64_t* ids, const int64_t* seg,
                const float* weights, int combiner, size_t n_rows, const void* default_row, const float* grad_out, const tfra_grads* hg,
                float* dw_out, tfra_stream_t stream) {
   Table* t = reinterpret_cast<Table*>(tp);
   hipStream_t s = (hipStream_t)stream;
-  std::unique_lock<std::mutex> lock;
-  Check c = check_find_combine(t, ws, nnz, ids, seg, weights, combiner, n_rows, default_row, grad_out, [&] {
-    lock = std::unique_lock<std::mutex>(t->mu);
-    return Check{t->enter(s)};
+  return find_combine_wgrad_call(who, TableOwner(tp), ws, nnz, ids, seg, weights, combiner, n_rows, default_row, grad_out, dw_out, s,
+                                 [&](const int* se) {
+    const int dim = t->opts.dim;
+    const TableView v = t->view_of(t->cur);
+    const unsigned grid = (unsigned)((n_rows * 16 + 255) / 256);
+    with_pool_class(st_index(t->opts.value_dtype), nch_index(dim), [&](auto DT, auto U, auto NCH) {
+      if (hg)
+        wgrad_half_kernel<DT, U, NCH><<<grid, 256, 0, s>>>(v, n_rows, dim, (const i64*)ids, weights, se, combiner,
+                                                           (const unsigned char*)default_row, (const float*)hg->grads, dw_out,
+                                                           hg->d_scale, hg->dtype == TFRA_BF16);
+      else
+        wgrad_kernel<DT, U, NCH><<<grid, 256, 0, s>>>(v, n_rows, dim, (const i64*)ids, weights, se, combiner,
+                                                          (const unsigned char*)default_row, grad_out, dw_out);
+    });
   });
-  if (c.msg == NEEDS_DIM) c.msg += " (use tfra_table_find + tfra_sparse_segment_combine_backprop_weights otherwise)";
-  if (c.code) return report(who + " (out = grad_out): ", c);
-  if (Check d = check_dw_out(nnz, dw_out); d.code) return report(who + ": ", d);
-  if (nnz == 0) return TFRA_OK;
-  HIP_TRY(hipMemsetAsync(dw_out, 0, nnz * sizeof(float), s));   // entries in no row: 0
-  if (!c.active) return TFRA_OK;                                // (no rows)
-  const int dim = t->opts.dim;
-  int rc = ws->ensure((2 * n_rows * sizeof(int) + 255) / 256 * 256, s);
-  if (rc) return rc;
-  int* se = (int*)ws->buf;
-  rc = comb_bounds(s, nnz, seg, n_rows, se);
-  if (rc) return rc;
-  const TableView v = t->view_of(t->cur);
-  const unsigned grid = (unsigned)((n_rows * 16 + 255) / 256);
-  with_pool_class(st_index(t->opts.value_dtype), nch_index(dim), [&](auto DT, auto U, auto NCH) {
-    if (hg)
-      wgrad_half_kernel<DT, U, NCH><<<grid, 256, 0, s>>>(v, n_rows, dim, (const i64*)ids, weights, se, combiner,
-                                                         (const unsigned char*)default_row, (const float*)hg->grads, dw_out,
-                                                         hg->d_scale, hg->dtype == TFRA_BF16);
-    else
-      wgrad_kernel<DT, U, NCH><<<grid, 256, 0, s>>>(v, n_rows, dim, (const i64*)ids, weights, se, combiner,
-                                                        (const unsigned char*)default_row, grad_out, dw_out);
-  });
-  HIP_TRY(hipGetLastError());
-  return TFRA_OK;
 }
 
-int wgrad_ragged_impl(const std::string& who, tfra_table_t* tp, size_t n_rows, const int64_t* row_splits, size_t nnz, const int64_t* ids,
-                      const float* weights, int combiner, uint32_t flags, int64_t fill_id, const void* default_row,
-                      const float* grad_out, const tfra_grads* hg, float* dw_out, tfra_stream_t stream) {
+// (fill_id is not looked at: wgrad_prune, tfra_pool.h)
+int wgrad_ragged_impl(const char* who, tfra_table_t* tp, size_t n_rows, const int64_t* row_splits, size_t nnz, const int64_t* ids,
+                      const float* weights, int combiner, uint32_t flags, int64_t, const void* default_row, const float* grad_out,
+                      const tfra_grads* hg, float* dw_out, tfra_stream_t stream) {
   Table* t = reinterpret_cast<Table*>(tp);
   hipStream_t s = (hipStream_t)stream;
-  std::unique_lock<std::mutex> lock;
-  Check c = check_find_combine_ragged(t, nullptr, n_rows, row_splits, nnz, ids, weights, combiner, flags, 0, default_row, grad_out, [&] {
-    lock = std::unique_lock<std::mutex>(t->mu);
-    return Check{t->enter(s)};
+  return find_combine_ragged_wgrad_call(who, TableOwner(tp), n_rows, row_splits, nnz, ids, weights, combiner, flags, default_row,
+                                        grad_out, dw_out, s, [&] {
+    const int dim = t->opts.dim;
+    const TableView v = t->view_of(t->cur);
+    const unsigned grid = (unsigned)((n_rows * 16 + 255) / 256);
+    with_ragged_class(st_index(t->opts.value_dtype), nch_index(dim), wgrad_prune(flags, weights), [&](auto DT, auto U, auto NCH, auto PRUNE) {
+      if (hg)
+        wgrad_ragged_half_kernel<DT, U, NCH, PRUNE><<<grid, 256, 0, s>>>(v, n_rows, dim, (const i64*)ids, weights, (const i64*)row_splits,
+                                                                         (int)nnz, combiner, (const unsigned char*)default_row,
+                                                                         (const float*)hg->grads, dw_out, hg->d_scale,
+                                                                         hg->dtype == TFRA_BF16);
+      else
+        wgrad_ragged_kernel<DT, U, NCH, PRUNE><<<grid, 256, 0, s>>>(v, n_rows, dim, (const i64*)ids, weights, (const i64*)row_splits,
+                                                                      (int)nnz, combiner, (const unsigned char*)default_row, grad_out,
+                                                                      dw_out);
+    });
   });
-  if (c.msg == NEEDS_DIM) c.msg += " (use tfra_table_find + tfra_sparse_segment_combine_backprop_weights otherwise)";
-  if (c.code) return report(who + " (out = grad_out): ", c);
-  if (Check d = check_dw_out(nnz, dw_out); d.code) return report(who + ": ", d);
-  (void)fill_id;   // a row that takes the fill row has no members: its entries are 0 whatever fill_id holds
-  if (nnz == 0) return TFRA_OK;
-  HIP_TRY(hipMemsetAsync(dw_out, 0, nnz * sizeof(float), s));   // entries outside the clamped cover: 0
-  if (!c.active) return TFRA_OK;                                // (no rows)
-  const int dim = t->opts.dim;
-  const TableView v = t->view_of(t->cur);
-  const unsigned grid = (unsigned)((n_rows * 16 + 255) / 256);
-  // the ladder's fourth axis is PRUNE here: FILL changes nothing, and PRUNE without weights neither
-  with_ragged_class(st_index(t->opts.value_dtype), nch_index(dim), (flags & TFRA_RAGGED_PRUNE) && weights,
-                    [&](auto DT, auto U, auto NCH, auto PRUNE) {
-    if (hg)
-      wgrad_ragged_half_kernel<DT, U, NCH, PRUNE><<<grid, 256, 0, s>>>(v, n_rows, dim, (const i64*)ids, weights, (const i64*)row_splits,
-                                                                       (int)nnz, combiner, (const unsigned char*)default_row,
-                                                                       (const float*)hg->grads, dw_out, hg->d_scale,
-                                                                       hg->dtype == TFRA_BF16);
-    else
-      wgrad_ragged_kernel<DT, U, NCH, PRUNE><<<grid, 256, 0, s>>>(v, n_rows, dim, (const i64*)ids, weights, (const i64*)row_splits, (int)nnz,
-                                                                    combiner, (const unsigned char*)default_row, grad_out, dw_out);
-  });
-  HIP_TRY(hipGetLastError());
-  return TFRA_OK;
 }
 
 }  // namespace

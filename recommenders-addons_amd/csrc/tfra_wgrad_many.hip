@@ -6,6 +6,8 @@
 // statistics and staging are left alone.
 // The kernels are wgrad_row (tfra_wgrad_device.h), unchanged, in the launch shape of find_combine_many_kernel; the host side is one
 // frame per form in the steps of multi_find_combine_frame: check every descriptor, classify, lock, lay out, fill, send, launch.
+// What the two frames share stands once in front of them: the descriptor's checks (with the owners' hints: TableOwner, tfra_pool.h;
+// TierOwner, tfra_tier.h) and the zero-fill step (ZeroFill); the classes' block prefixes are put_classes (tfra_pool_many.h).
 // The *_typed calls run the same frames over descriptors that carry a tfra_grads: float-or-half is one more axis of
 // the launch classes.  A float32 descriptor runs the kernels it always ran; a float16 / bfloat16 one runs wgrad_row's GHALF axis
 // in kernels of their own names, its scale's address and format in a record beside the descriptor's (WgradHalf: the float
@@ -200,18 +202,50 @@ __global__ __launch_bounds__(256) void wgrad_zero_many_kernel(const ZeroRec* __r
 }
 
 // ---- what the two frames share ---------------------------------------------------------------------------------------------------
-const char* const HINT_TABLE = " (use tfra_table_find + tfra_sparse_segment_combine_backprop_weights otherwise)";
-const char* const HINT_TIER = " (use tfra_unique + tfra_tier_find + tfra_sparse_segment_combine_backprop_weights otherwise)";
-
-// The checks of the single call behind `c`, the forward's checks with grad_out in the place of out: its NEEDS_DIM hint, then
-// dw_out.  TFRA_OK, or the code with the message recorded behind `at` ("<who>: descriptor <i>: ").
+// The checks of the single call behind `c`, the forward's checks with grad_out in the place of out: its NEEDS_DIM hint (the
+// owners': tfra_pool.h, tfra_tier.h), then dw_out.  TFRA_OK, or the code with the message recorded behind `at`
+// ("<who>: descriptor <i>: ").
 int check_wgrad_desc(const std::string& at, const PoolDesc& d, Check c) {
-  if (c.msg == NEEDS_DIM) c.msg += d.tier ? HINT_TIER : HINT_TABLE;
+  if (c.msg == NEEDS_DIM) c.msg += d.tier ? TierOwner::GRADIENT_HINT : TableOwner::GRADIENT_HINT;
   if (c.code) return report(at + "(out = grad_out) ", c);
   if (Check w = check_dw_out(d.nnz, d.dw_out); w.code) return report(at, w);
   return TFRA_OK;
 }
 unsigned zero_blocks(const PoolDesc& d) { return (unsigned)((d.nnz + 255) / 256); }
+
+// The zero-fill of a call: the descriptors with nnz > 0, in input order — their dw_out is written, with rows or without —, the
+// blocks they own (ceil(nnz / 256) each), and their records and block prefix in the blob.  The two forms differ in the record
+// alone: with the rows' bounds, or without.
+struct ZeroFill {
+  std::vector<size_t> zeroed;
+  u64 blocks = 0;
+  size_t rec_off = 0, pre_off = 0;
+  void add(size_t i, const PoolDesc& d) {
+    zeroed.push_back(i);
+    blocks += zero_blocks(d);
+  }
+  int check(const std::string& who) const {
+    return blocks >= (1ULL << 31) ? set_error(TFRA_ERR_UNSUPPORTED, who + ": too many entries in one call") : TFRA_OK;
+  }
+  void lay_out(Blob* blob) {
+    rec_off = blob->add<ZeroRec>(zeroed.size());
+    pre_off = blob->add<unsigned>(ClassPool::words(zeroed.size(), 1, false));
+  }
+  // rec(i): descriptor i's record
+  template <class Rec>
+  ManyClass fill(const ManyUpload& up, const std::vector<PoolDesc>& ds, Rec&& rec) const {
+    ZeroRec* zrecs = section<ZeroRec>(up.host, rec_off);
+    for (size_t k = 0; k < zeroed.size(); ++k) zrecs[k] = rec(zeroed[k]);
+    return ClassPool{section<unsigned>(up.host, pre_off)}.put(zeroed.size(), false, [](size_t) { return true; },
+                                                             [&](size_t k) { return zero_blocks(ds[zeroed[k]]); });
+  }
+  // ONE launch: every dw_out zeroed (BOUNDS: and all rows' bounds)
+  template <bool BOUNDS>
+  void launch(const ManyUpload& up, const ManyClass& zero, hipStream_t s) const {
+    wgrad_zero_many_kernel<BOUNDS><<<zero.grid, 256, 0, s>>>(section<const ZeroRec>(up.dev, rec_off),
+                                                             section<const unsigned>(up.dev, pre_off), zero.n);
+  }
+};
 
 // A typed descriptor's record (tfra_grads): checked as the single typed call checks it, BEFORE any descriptor's table or tier is
 // looked at.  TFRA_OK, or the code with the message recorded behind `at`.
@@ -245,9 +279,8 @@ int multi_wgrad_frame(const std::string& who, tfra_workspace* ws, size_t n_table
   std::vector<PoolDesc> ds(n_tables);
   std::vector<int> cls(n_tables, -1);
   std::vector<size_t> se_off(n_tables, 0);   // a descriptor's bounds in the bounds area, in input order
-  std::vector<size_t> zeroed;                // the descriptors with nnz > 0: their dw_out is written, with rows or without
+  ZeroFill zf;
   size_t total_rows = 0;
-  u64 z_blocks = 0;
   // (typed lists) every record first: no table or tier handle is looked at before all of them have passed
   for (size_t i = 0; i < n_tables; ++i)
     if (int rc = check_desc_grads(who + ": descriptor " + std::to_string(i) + ": ", at(descs, i))) return rc;
@@ -261,23 +294,22 @@ int multi_wgrad_frame(const std::string& who, tfra_workspace* ws, size_t n_table
                                        [] { return Check{}; });
     if (int rc = check_wgrad_desc(at_i, d, c)) return rc;
     if (d.nnz == 0) continue;   // nothing to write
-    zeroed.push_back(i);
-    z_blocks += zero_blocks(d);
+    zf.add(i, d);
     if (!c.active) continue;    // no rows: zeros alone
     cls[i] = (d.tier ? NPLAIN : 0) + (desc_half(d) ? NBASE : 0) + pool_class(t);
     any_half = any_half || desc_half(d);
     se_off[i] = 2 * total_rows;
     total_rows += d.n_rows;
   }
-  if (zeroed.empty()) return TFRA_OK;
+  if (zf.zeroed.empty()) return TFRA_OK;
   std::vector<size_t> order;
   size_t first[NCLASS + 1];
   if (int rc = order_by_class(who, ds, cls, NCLASS, &order, first)) return rc;
-  const size_t n_act = order.size(), n_plain = first[NPLAIN], n_zero = zeroed.size();
-  if (z_blocks >= (1ULL << 31)) return set_error(TFRA_ERR_UNSUPPORTED, who + ": too many entries in one call");
+  const size_t n_act = order.size(), n_plain = first[NPLAIN];
+  if (int rc = zf.check(who)) return rc;
 
   PoolLocks locks;   // of every descriptor that is written, as the single call enters its table before its memset
-  int rc = lock_owners(ds, zeroed, s, &locks);
+  int rc = lock_owners(ds, zf.zeroed, s, &locks);
   if (rc) return rc;
 
   // device memory: [bounds of all rows | blob], the blob = [one-table records | tier records | per-class block prefixes | zero-fill
@@ -287,14 +319,13 @@ int multi_wgrad_frame(const std::string& who, tfra_workspace* ws, size_t n_table
   const size_t rec_off = blob.add<WgradRec>(n_plain), trec_off = blob.add<TierWgradRec>(n_act - n_plain);
   const size_t hrec_off = blob.add<WgradHalf>(any_half ? n_act : 0);   // at the records' positions k, plain and tier alike
   const size_t cpre_off = blob.add<unsigned>(ClassPool::words(n_act, NCLASS, false));
-  const size_t zrec_off = blob.add<ZeroRec>(n_zero), zpre_off = blob.add<unsigned>(ClassPool::words(n_zero, 1, false));
+  zf.lay_out(&blob);
   ManyUpload up;
   rc = many_begin(ws, se_bytes, blob.bytes(), s, &up);
   if (rc) return rc;
   int* se_base = (int*)ws->buf;
   WgradRec* recs = section<WgradRec>(up.host, rec_off);
   TierWgradRec* trecs = section<TierWgradRec>(up.host, trec_off);
-  ZeroRec* zrecs = section<ZeroRec>(up.host, zrec_off);
   WgradHalf* hrecs = section<WgradHalf>(up.host, hrec_off);
   // the views are taken here, under the locks: a table that grew since the last call has another one
   for (size_t k = 0; k < n_act; ++k) {
@@ -306,24 +337,16 @@ int multi_wgrad_frame(const std::string& who, tfra_workspace* ws, size_t n_table
     else recs[k] = r;
     if (any_half) hrecs[k] = half_rec(d);
   }
-  // the records stand in class order: a class is a range of them and needs no index
   ClassPool cpool{section<unsigned>(up.host, cpre_off)};
   ManyClass row_cls[NCLASS];
-  for (int c = 0; c < NCLASS; ++c)
-    row_cls[c] = cpool.put(n_act, false, [&](size_t k) { return k >= first[c] && k < first[c + 1]; },
-                           [&](size_t k) { return row_blocks(ds[order[k]]); });
-  for (size_t k = 0; k < n_zero; ++k) {
-    const PoolDesc& d = ds[zeroed[k]];
-    zrecs[k] = ZeroRec{(const i64*)d.seg, se_base + se_off[zeroed[k]], d.dw_out, d.nnz, d.n_rows};
-  }
-  const ManyClass zero = ClassPool{section<unsigned>(up.host, zpre_off)}.put(n_zero, false, [](size_t) { return true; },
-                                                                           [&](size_t k) { return zero_blocks(ds[zeroed[k]]); });
+  put_classes(cpool, ds, order, first, NCLASS, row_cls);
+  const ManyClass zero = zf.fill(up, ds, [&](size_t i) {
+    return ZeroRec{(const i64*)ds[i].seg, se_base + se_off[i], ds[i].dw_out, ds[i].nnz, ds[i].n_rows};
+  });
   rc = many_send(up, s, "hipMemcpyAsync(d_blob, h, blob_bytes, hipMemcpyHostToDevice, s)", true);
   if (rc) return rc;
   if (total_rows) HIP_TRY(hipMemsetAsync(se_base, 0, 2 * total_rows * sizeof(int), s));   // empty rows: 0, 0
-  // ONE launch: every dw_out zeroed and all rows' bounds
-  wgrad_zero_many_kernel<true><<<zero.grid, 256, 0, s>>>(section<const ZeroRec>(up.dev, zrec_off),
-                                                         section<const unsigned>(up.dev, zpre_off), zero.n);
+  zf.launch<true>(up, zero, s);   // every dw_out zeroed and all rows' bounds
   uint32_t launches = 1;
   for (int c = 0; c < NCLASS; ++c) {
     const ManyClass& k = row_cls[c];
@@ -362,8 +385,7 @@ int multi_wgrad_ragged_frame(const std::string& who, tfra_workspace* ws, size_t 
   bool any_half = false;
   std::vector<PoolDesc> ds(n_tables);
   std::vector<int> cls(n_tables, -1);
-  std::vector<size_t> zeroed;   // the descriptors with nnz > 0: their dw_out is written, with rows or without
-  u64 z_blocks = 0;
+  ZeroFill zf;
   // (typed lists) every record first: no table or tier handle is looked at before all of them have passed
   for (size_t i = 0; i < n_tables; ++i)
     if (int rc = check_desc_grads(who + ": descriptor " + std::to_string(i) + ": ", at(descs, i))) return rc;
@@ -377,22 +399,21 @@ int multi_wgrad_ragged_frame(const std::string& who, tfra_workspace* ws, size_t 
                                               d.default_row, grad_checked(d), [] { return Check{}; });
     if (int rc = check_wgrad_desc(at_i, d, c)) return rc;
     if (d.nnz == 0) continue;   // nothing to write
-    zeroed.push_back(i);
-    z_blocks += zero_blocks(d);
+    zf.add(i, d);
     if (!c.active) continue;    // no rows: zeros alone
     // the fourth axis is PRUNE, as in the single calls: FILL changes nothing, and PRUNE without weights neither
     cls[i] = (d.tier ? NPLAIN : 0) + (desc_half(d) ? NBASE : 0) + pool_class(t) * 2 + (((d.flags & TFRA_RAGGED_PRUNE) && d.weights) ? 1 : 0);
     any_half = any_half || desc_half(d);
   }
-  if (zeroed.empty()) return TFRA_OK;
+  if (zf.zeroed.empty()) return TFRA_OK;
   std::vector<size_t> order;
   size_t first[NCLASS + 1];
   if (int rc = order_by_class(who, ds, cls, NCLASS, &order, first)) return rc;
-  const size_t n_act = order.size(), n_plain = first[NPLAIN], n_zero = zeroed.size();
-  if (z_blocks >= (1ULL << 31)) return set_error(TFRA_ERR_UNSUPPORTED, who + ": too many entries in one call");
+  const size_t n_act = order.size(), n_plain = first[NPLAIN];
+  if (int rc = zf.check(who)) return rc;
 
   PoolLocks locks;   // of every descriptor that is written, as the single call enters its table before its memset
-  int rc = lock_owners(ds, zeroed, s, &locks);
+  int rc = lock_owners(ds, zf.zeroed, s, &locks);
   if (rc) return rc;
 
   // device memory: the blob alone = [one-table records | tier records | per-class block prefixes | zero-fill records | their block
@@ -401,13 +422,12 @@ int multi_wgrad_ragged_frame(const std::string& who, tfra_workspace* ws, size_t 
   const size_t rec_off = blob.add<WgradRaggedRec>(n_plain), trec_off = blob.add<TierWgradRaggedRec>(n_act - n_plain);
   const size_t hrec_off = blob.add<WgradHalf>(any_half ? n_act : 0);   // at the records' positions k, plain and tier alike
   const size_t cpre_off = blob.add<unsigned>(ClassPool::words(n_act, NCLASS, false));
-  const size_t zrec_off = blob.add<ZeroRec>(n_zero), zpre_off = blob.add<unsigned>(ClassPool::words(n_zero, 1, false));
+  zf.lay_out(&blob);
   ManyUpload up;
   rc = many_begin(ws, 0, blob.bytes(), s, &up);
   if (rc) return rc;
   WgradRaggedRec* recs = section<WgradRaggedRec>(up.host, rec_off);
   TierWgradRaggedRec* trecs = section<TierWgradRaggedRec>(up.host, trec_off);
-  ZeroRec* zrecs = section<ZeroRec>(up.host, zrec_off);
   WgradHalf* hrecs = section<WgradHalf>(up.host, hrec_off);
   // the views are taken here, under the locks: a table that grew since the last call has another one
   for (size_t k = 0; k < n_act; ++k) {
@@ -421,17 +441,11 @@ int multi_wgrad_ragged_frame(const std::string& who, tfra_workspace* ws, size_t 
   }
   ClassPool cpool{section<unsigned>(up.host, cpre_off)};
   ManyClass row_cls[NCLASS];
-  for (int c = 0; c < NCLASS; ++c)
-    row_cls[c] = cpool.put(n_act, false, [&](size_t k) { return k >= first[c] && k < first[c + 1]; },
-                           [&](size_t k) { return row_blocks(ds[order[k]]); });
-  for (size_t k = 0; k < n_zero; ++k) zrecs[k] = ZeroRec{nullptr, nullptr, ds[zeroed[k]].dw_out, ds[zeroed[k]].nnz, 0};
-  const ManyClass zero = ClassPool{section<unsigned>(up.host, zpre_off)}.put(n_zero, false, [](size_t) { return true; },
-                                                                           [&](size_t k) { return zero_blocks(ds[zeroed[k]]); });
+  put_classes(cpool, ds, order, first, NCLASS, row_cls);
+  const ManyClass zero = zf.fill(up, ds, [&](size_t i) { return ZeroRec{nullptr, nullptr, ds[i].dw_out, ds[i].nnz, 0}; });
   rc = many_send(up, s, "hipMemcpyAsync(d_blob, h, blob_bytes, hipMemcpyHostToDevice, s)", true);
   if (rc) return rc;
-  // ONE launch: every dw_out zeroed (entries outside the clamped cover: 0)
-  wgrad_zero_many_kernel<false><<<zero.grid, 256, 0, s>>>(section<const ZeroRec>(up.dev, zrec_off),
-                                                          section<const unsigned>(up.dev, zpre_off), zero.n);
+  zf.launch<false>(up, zero, s);   // every dw_out zeroed (entries outside the clamped cover: 0)
   uint32_t launches = 1;
   for (int c = 0; c < NCLASS; ++c) {
     const ManyClass& k = row_cls[c];

@@ -1,21 +1,31 @@
 """Host cost of the Python table layer, per call, with kernels that take no time: a 64 K-slot table and 256-id batches — what is
 left is the calling thread's work (the argument checks, the marshalling, the launches).  Per-table calls: `_DeviceTable.find`,
 `upsert`, `find_or_insert`, `find_missed(sync=False)`, `assign`, and `apply_planned` over a prebuilt plan; per-variable calls:
-`Variable.lookup` and `Variable.upsert` at 1 and 2 shards (both on one device).  One JSON line per call.
-  python scripts/mb_table_host.py [--package DIR] [--tag NAME] [--run N]
+`Variable.lookup` and `Variable.upsert` at 1 and 2 shards (both on one device); and the single pooled calls of the C library as
+ctypes reaches them, operands made once (`pooled.*`: tfra_table_find_combine, its ragged, weight-gradient and long forms and
+tfra_tier_find_combine, 256 entries in 64 rows).  One JSON line per call.
+  python scripts/mb_table_host.py [--package DIR] [--lib FILE] [--only PREFIX] [--tag NAME] [--run N]
 --package: the directory that holds the `tfra_amd` package to measure (default: this tree's), so that two versions of the Python
-layer can be run alternately against one built library."""
+layer can be run alternately against one built library.  --lib: the built library to load instead of the package's own, so that
+two builds of the C side can be run alternately under one Python layer.  --only: the calls whose name starts with PREFIX."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ap = argparse.ArgumentParser()
 ap.add_argument("--package", default=os.path.join(ROOT, "recommenders-addons_amd"))
+ap.add_argument("--lib", default=None)
+ap.add_argument("--only", default="")
 ap.add_argument("--tag", default="tree")
 ap.add_argument("--run", type=int, default=0)
 ap.add_argument("--calls", type=int, default=2000)
 args = ap.parse_args()
 sys.path.insert(0, os.path.abspath(args.package))
 import torch
+from tfra_amd import _capi
+if args.lib:
+  _capi.LIB_PATH = os.path.abspath(args.lib)   # (the library is loaded on first use)
 import tfra_amd.dynamic_embedding as de
+from tfra_amd.dynamic_embedding.device_ops import _workspace
+from tfra_amd.dynamic_embedding.table_ops import _DeviceTable, _DeviceTier, _ptr, _stream
 from tfra_amd.dynamic_embedding.table_ops import SparsePlan
 
 dev = torch.device("cuda", 0)
@@ -46,7 +56,37 @@ for n, var in variables.items():
   CALLS.append(("variable.lookup_%dshard" % n, lambda i, var=var: var.lookup(ids[i % 64])))
   CALLS.append(("variable.upsert_%dshard" % n, lambda i, var=var: var.upsert(ids[i % 64], vals)))
 
+# the pooled single calls, straight through ctypes: every operand is made once, what is timed is the C side's host frame
+lib, ws, st = _capi.lib(), _workspace(dev), _stream(dev)
+n_rows = 64
+seg = (torch.arange(B, device=dev) // (B // n_rows)).to(torch.int64).contiguous()
+splits = torch.arange(0, B + 1, B // n_rows, device=dev, dtype=torch.int64).contiguous()
+pool_out = torch.empty((n_rows, dim), device=dev)
+pool_dw = torch.empty(B, device=dev)
+upper = _DeviceTable(torch.int64, torch.float32, torch.zeros(dim), "mb_pool_up", "cuda:0", dim=dim, init_capacity=1 << 16,
+                     max_capacity=1 << 16, strategy=0)
+lower = _DeviceTable(torch.int64, torch.float32, torch.zeros(dim), "mb_pool_lo", "cuda:0", dim=dim, init_capacity=1 << 16)
+tier = _DeviceTier(upper, lower, 4096)
+h, d, o, g, dw = table._h, _ptr(default_row), _ptr(pool_out), _ptr(vals), _ptr(pool_dw)
+id_ptrs = [_ptr(t) for t in ids]
+CALLS += [
+    ("pooled.tfra_table_find_combine",
+     lambda i: lib.tfra_table_find_combine(h, ws, B, id_ptrs[i % 64], _ptr(seg), None, 1, n_rows, d, o, st)),
+    ("pooled.tfra_table_find_combine_ragged",
+     lambda i: lib.tfra_table_find_combine_ragged(h, n_rows, _ptr(splits), B, id_ptrs[i % 64], None, 1, 0, 0, d, o, st)),
+    ("pooled.tfra_table_find_combine_backprop_weights",
+     lambda i: lib.tfra_table_find_combine_backprop_weights(h, ws, B, id_ptrs[i % 64], _ptr(seg), None, 1, n_rows, d, g, dw, st)),
+    ("pooled.tfra_tier_find_combine",
+     lambda i: lib.tfra_tier_find_combine(tier._h, ws, B, id_ptrs[i % 64], _ptr(seg), None, 1, n_rows, d, o, st)),
+    ("pooled.tfra_table_find_combine_long",
+     lambda i: lib.tfra_table_find_combine_long(h, ws, B, id_ptrs[i % 64], _ptr(seg), None, 1, n_rows, d, o, st)),
+]
+
 for name, call in CALLS:
+  if not name.startswith(args.only):
+    continue
+  if name.startswith("pooled."):
+    assert call(0) == 0, (name, lib.tfra_last_error())
   for i in range(200):
     call(i)
   torch.cuda.synchronize()
@@ -56,5 +96,5 @@ for name, call in CALLS:
   host = time.perf_counter() - t0
   torch.cuda.synchronize()
   total = time.perf_counter() - t0
-  print(json.dumps({"bench": "mb_table_host", "package": args.tag, "run": args.run, "call": name, "calls": K,
+  print(json.dumps({"bench": "mb_table_host", "package": args.tag, "lib": os.path.basename(args.lib) if args.lib else "package", "run": args.run, "call": name, "calls": K,
                     "host_us_per_call": round(host / K * 1e6, 3), "total_us_per_call": round(total / K * 1e6, 3)}), flush=True)
