@@ -1358,6 +1358,32 @@ int tfra_table_find_combine_ragged_backprop_weights_long(tfra_table_t* t, size_t
                                                          int64_t fill_id, const void* default_row, const float* grad_out,
                                                          float* dw_out, tfra_stream_t stream);
 
+/* The same four calls for MIXED row lengths — a heavy-tailed sequence feature: most rows a handful of ids, a few of them hundreds,
+ * in one batch —: the twins' argument lists plus long_from directly before stream, their checks, refusals, locking and nnz == 0
+ * behaviour, and their results BIT FOR BIT.  One 256-thread block owns 16 consecutive output rows: a row with fewer than long_from
+ * entries is walked by one 16-lane group as in the twins, a row with long_from entries or more (counted before pruning: e - b of
+ * its bounds) is done by the whole block as in the *_long forms, the block's long rows one after the other.  long_from never
+ * changes a result, only who computes it; 0 means TFRA_MIXED_LONG_FROM_DEFAULT; a value above every row's length makes every row a
+ * group's.  The launches enqueued are the twins' (tuple forms: memset, bounds launch, one launch; ragged forward: one launch;
+ * ragged gradient: a memset and one launch), and overlapping rows of a ragged gradient end as in the twin.
+ * Not provided in this form: typed outputs (tfra_rows_out), a half grad_out (tfra_grads), tiers, and the grouped *_many calls. */
+#define TFRA_MIXED_LONG_FROM_DEFAULT 64
+int tfra_table_find_combine_mixed(tfra_table_t* t, tfra_workspace_t* ws, size_t nnz, const int64_t* ids, const int64_t* seg,
+                                  const float* weights, int combiner, size_t n_rows, const void* default_row, float* out,
+                                  uint32_t long_from, tfra_stream_t stream);
+int tfra_table_find_combine_ragged_mixed(tfra_table_t* t, size_t n_rows, const int64_t* row_splits, size_t nnz,
+                                         const int64_t* ids, const float* weights, int combiner, uint32_t flags,
+                                         int64_t fill_id, const void* default_row, float* out, uint32_t long_from,
+                                         tfra_stream_t stream);
+int tfra_table_find_combine_backprop_weights_mixed(tfra_table_t* t, tfra_workspace_t* ws, size_t nnz, const int64_t* ids,
+                                                   const int64_t* seg, const float* weights, int combiner, size_t n_rows,
+                                                   const void* default_row, const float* grad_out, float* dw_out,
+                                                   uint32_t long_from, tfra_stream_t stream);
+int tfra_table_find_combine_ragged_backprop_weights_mixed(tfra_table_t* t, size_t n_rows, const int64_t* row_splits, size_t nnz,
+                                                          const int64_t* ids, const float* weights, int combiner, uint32_t flags,
+                                                          int64_t fill_id, const void* default_row, const float* grad_out,
+                                                          float* dw_out, uint32_t long_from, tfra_stream_t stream);
+
 /* The weight gradients of MANY pooled lookups in one call (a model with 26 weighted sparse features asks for 26 of them per step:
  * ~100 enqueues for 26 small kernels otherwise).  A descriptor names exactly ONE of table / tier, as tfra_tier_find_combine_desc
  * does; descs[i].dw_out is bit-identical to the single call on that descriptor — the same device function runs:

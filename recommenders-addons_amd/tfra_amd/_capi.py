@@ -444,6 +444,17 @@ _SIGS = {
     "tfra_assign_route_time_kernels": [_P, _SZ],
     "tfra_assign_route_kernel_times": [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_SZ)],
 }
+# The mixed-row forms of the single pooled calls (16 rows per block, long rows by the block): their twins' lists plus long_from
+# before the stream.  A table of its own, bound with _SIGS: tests/test_pooled_refusals_abi.py holds the single find_combine names
+# of _SIGS to the family whose refusals it lists.
+_SIGS_MIXED = {
+    "tfra_table_find_combine_mixed": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, _P, ctypes.c_uint32, _P],
+    "tfra_table_find_combine_ragged_mixed": [_P, _SZ, _P, _SZ, _P, _P, _I, ctypes.c_uint32, ctypes.c_int64, _P, _P, ctypes.c_uint32,
+                                             _P],
+    "tfra_table_find_combine_backprop_weights_mixed": [_P, _P, _SZ, _P, _P, _P, _I, _SZ, _P, _P, _P, ctypes.c_uint32, _P],
+    "tfra_table_find_combine_ragged_backprop_weights_mixed": [_P, _SZ, _P, _SZ, _P, _P, _I, ctypes.c_uint32, ctypes.c_int64, _P, _P,
+                                                              _P, ctypes.c_uint32, _P],
+}
 
 _lib = None
 
@@ -457,7 +468,7 @@ def lib():
           "%s not found: run `python recommenders-addons_amd/build.py` (hipcc, gfx950). "
           "There is no CPU fallback." % LIB_PATH)
     l = ctypes.CDLL(LIB_PATH)
-    for name, args in _SIGS.items():
+    for name, args in list(_SIGS.items()) + list(_SIGS_MIXED.items()):
       f = getattr(l, name)
       f.argtypes = args
       f.restype = ctypes.c_int

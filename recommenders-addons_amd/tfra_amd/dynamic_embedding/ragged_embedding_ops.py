@@ -59,12 +59,14 @@ def _safe_flags(w, combiner, default_id):
   return (w is not None and combiner != "sum"), default_id
 
 
-def _plain_wrapper(params, rs, ids, w, combiner, n, plan_writeback, entry_plan=None, seg=None, out_shape=None, long_rows=False):
+def _plain_wrapper(params, rs, ids, w, combiner, n, plan_writeback, entry_plan=None, seg=None, out_shape=None, long_rows=False,
+                   mixed_rows=False):
   """seg: the entries' row ids where the caller has them (else derived from the splits); out_shape: the shape the caller gives
   the result, which the gradient then has (else [n, dim])."""
   seg = row_ids_of(rs, ids.numel()) if seg is None else seg
   return SparseTrainableWrapper(params, None, None, None, seg, w, combiner, n, out_shape or (n, params.dim), ids, seg, w,
-                                plan_writeback=plan_writeback, lookup_ids=ids, entry_plan=entry_plan, long_rows=long_rows)
+                                plan_writeback=plan_writeback, lookup_ids=ids, entry_plan=entry_plan, long_rows=long_rows,
+                                mixed_rows=mixed_rows)
 
 
 def _safe_entries_many(params_list, members, combiners, default_ids):
@@ -76,11 +78,12 @@ def _safe_entries_many(params_list, members, combiners, default_ids):
   return {m[0]: (rows, p_ids, p_w, entries, out_shape) for m, (rows, p_ids, p_w, _, entries, out_shape, _) in zip(members, made)}
 
 
-def _safe_wrapper(params, args, combiner, n, plan_writeback, entry_plan=None, caller_weights=None, long_rows=False):
+def _safe_wrapper(params, args, combiner, n, plan_writeback, entry_plan=None, caller_weights=None, long_rows=False, mixed_rows=False):
   """caller_weights: the weights as the caller gave them (`SparseTrainableWrapper.weights_grad` answers in their length)."""
   rows, p_ids, p_w, entries, out_shape = args
   tw = SparseTrainableWrapper(params, None, None, None, rows, p_w, combiner, n, out_shape, entries[0], entries[1], entries[2],
-                              plan_writeback=plan_writeback, lookup_ids=p_ids, entry_plan=entry_plan, long_rows=long_rows)
+                              plan_writeback=plan_writeback, lookup_ids=p_ids, entry_plan=entry_plan, long_rows=long_rows,
+                              mixed_rows=mixed_rows)
   return _note_pruned(tw, caller_weights, combiner)
 
 
@@ -89,14 +92,18 @@ def _typed(out_dtype):
   return {} if _out_dtype(out_dtype) is None else {"out_dtype": out_dtype}
 
 
-def _long(long_rows, out_dtype):
-  """The keyword of a long-row lookup behind this module's calls: nothing without it, so that today's calls stay as they are, and
-  nothing beside an out_dtype, which has no long-row form."""
-  return {"long_rows": True} if long_rows and _out_dtype(out_dtype) is None else {}
+def _long(long_rows, out_dtype, mixed_rows=False):
+  """The keyword of a long-row or mixed-row lookup behind this module's calls: nothing without it, so that today's calls stay as
+  they are, and nothing beside an out_dtype, which has neither form.  Both keywords at once: ValueError."""
+  if long_rows and mixed_rows:
+    raise ValueError("long_rows=True and mixed_rows=True exclude each other: mixed_rows serves long rows as well")
+  if _out_dtype(out_dtype) is not None:
+    return {}
+  return {"long_rows": True} if long_rows else {"mixed_rows": True} if mixed_rows else {}
 
 
 def embedding_lookup_sparse(params, sp_ids, sp_weights, name=None, combiner="mean", return_trainable=False, plan_writeback=False,
-                            entry_seg=None, out_shape=None, out_dtype=None, long_rows=False):
+                            entry_seg=None, out_shape=None, out_dtype=None, long_rows=False, mixed_rows=False):
   """PY/ragged_embedding_ops.py:223-324.  `sp_ids` = (row_splits[n_rows + 1], values[nnz]), `sp_weights` = weight values or None.
   [n_rows, dim] float32: row r = sum / mean / sqrtn over its entries of weight * embedding, zeros for an empty row — bit-identical
   to `de.embedding_lookup_sparse(params, (row ids, values), sp_weights, num_rows=n_rows)`, in one launch.
@@ -110,9 +117,12 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights, name=None, combiner="mea
   lookup's kernel where the pooled read serves the variable (tfra_table_find_combine_ragged_typed), converted otherwise.
   long_rows: rows of a few hundred ids (a sequence feature) — the pooled read takes tfra_table_find_combine_ragged_long, one block
   per output row, and the wrapper's `weights_grad` its long-row call: the same bits.  Where the plain pooled read does not apply
-  (several shards, tiers, bp_v2, other dims or dtypes, out_dtype) the keyword changes nothing."""
+  (several shards, tiers, bp_v2, other dims or dtypes, out_dtype) the keyword changes nothing.
+  mixed_rows: rows of mixed lengths (a heavy-tailed sequence feature) — tfra_table_find_combine_ragged_mixed, 16 rows per block and
+  a long row by the whole block, and the wrapper's `weights_grad` its mixed-row call: the same bits, and nothing changes where
+  long_rows changes nothing.  long_rows=True together with mixed_rows=True: ValueError."""
   _check_combiner(combiner)
-  typed = dict(_typed(out_dtype), **_long(long_rows, out_dtype))
+  typed = dict(_typed(out_dtype), **_long(long_rows, out_dtype, mixed_rows))
   rs, ids, w = _ragged_input(params, sp_ids, sp_weights)
   n = rs.numel() - 1
   if not (_pooled_training if return_trainable else _pooled_forward)(params, None):
@@ -125,11 +135,11 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights, name=None, combiner="mea
   if not return_trainable:
     return out
   return out, _plain_wrapper(params, rs, ids, w, combiner, n, plan_writeback, seg=entry_seg, out_shape=out_shape,
-                             **_long(long_rows, None))
+                             **_long(long_rows, None, mixed_rows))
 
 
 def safe_embedding_lookup_sparse(params, sparse_ids, sparse_weights=None, combiner="mean", default_id=None, name=None,
-                                 return_trainable=False, plan_writeback=False, out_dtype=None, long_rows=False):
+                                 return_trainable=False, plan_writeback=False, out_dtype=None, long_rows=False, mixed_rows=False):
   """PY/ragged_embedding_ops.py:327-442, with this project's semantics of the tuple form (`de.safe_embedding_lookup_sparse`):
   ids are never pruned; entries whose weight is not > 0 are dropped unless combiner == "sum"; a row left without entries yields
   zeros, or the embedding of `default_id`.  Bit-identical to the tuple form on (row ids, values), in one launch and with no
@@ -137,9 +147,9 @@ def safe_embedding_lookup_sparse(params, sparse_ids, sparse_weights=None, combin
 
   return_trainable: also returns the SparseTrainableWrapper; its entry list is what the tuple form's preprocessing
   (`_safe_sparse_args`) makes on the derived row ids, built on the device from row_splits with one host read of its length.
-  out_dtype: as `embedding_lookup_sparse`'s; the row of default_id is converted as it is.  long_rows: as there."""
+  out_dtype: as `embedding_lookup_sparse`'s; the row of default_id is converted as it is.  long_rows, mixed_rows: as there."""
   _check_combiner(combiner)
-  typed = dict(_typed(out_dtype), **_long(long_rows, out_dtype))
+  typed = dict(_typed(out_dtype), **_long(long_rows, out_dtype, mixed_rows))
   rs, ids, w = _ragged_input(params, sparse_ids, sparse_weights)
   n = rs.numel() - 1
   if not (_pooled_training if return_trainable else _pooled_forward)(params, None):
@@ -152,7 +162,7 @@ def safe_embedding_lookup_sparse(params, sparse_ids, sparse_weights=None, combin
   made = _safe_entries_many([params], [(0, rs, ids, w)], [combiner], [default_id])[0]
   params.admit_entries(made[3][0])   # (tiered shards: the entry ids into the cache ahead of the read; init_on_lookup="pooled": admitted with drawn rows)
   out = params.lookup_combined_ragged(rs, ids, w, combiner, prune=prune, fill_id=fill, **typed)
-  return out, _safe_wrapper(params, made, combiner, n, plan_writeback, caller_weights=w, **_long(long_rows, None))
+  return out, _safe_wrapper(params, made, combiner, n, plan_writeback, caller_weights=w, **_long(long_rows, None, mixed_rows))
 
 
 def _many(params_list, sp_ids_list, weights_list, combiner, default_id, safe, return_trainable, plan_writeback, out_dtype=None):

@@ -340,6 +340,44 @@ class _DeviceTable:
                _ptr(w), int(combiner), flags, fill, _ptr(d), _ptr(g), _ptr(dw), _stream(self._device))
     return dw
 
+  # ---- the mixed-row forms: 16 rows per block, a row of long_from entries or more by the whole block (tfra_pool_mixed.hip) ------
+  def find_combine_mixed(self, ids, seg, weights, combiner, n_rows, default_row=None, long_from=0):
+    """`find_combine` for a batch whose rows mix a handful of entries with hundreds (tfra_table_find_combine_mixed): the same
+    arguments, limits and result, bit for bit.  A row of at least `long_from` entries is read by a whole block, a shorter one by
+    one group; long_from changes no result; 0: the library's default (TFRA_MIXED_LONG_FROM_DEFAULT).  float32 out."""
+    ids, seg, w, d, out = self._find_combine_args(ids, seg, weights, n_rows, default_row)
+    _capi.call("tfra_table_find_combine_mixed", self._h, _workspace(self._device), ids.numel(), _ptr(ids), _ptr(seg), _ptr(w),
+               int(combiner), int(n_rows), _ptr(d), _ptr(out), int(long_from), _stream(self._device))
+    return out
+
+  def find_combine_ragged_mixed(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, default_row=None, long_from=0):
+    """`find_combine_ragged` for mixed row lengths (tfra_table_find_combine_ragged_mixed), bit for bit, in one launch; a row's
+    length counts before pruning.  float32 out."""
+    rs, ids, w, flags, fill, d, out = self._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row)
+    _capi.call("tfra_table_find_combine_ragged_mixed", self._h, rs.numel() - 1, _ptr(rs), ids.numel(), _ptr(ids), _ptr(w),
+               int(combiner), flags, fill, _ptr(d), _ptr(out), int(long_from), _stream(self._device))
+    return out
+
+  def find_combine_weight_grad_mixed(self, ids, seg, weights, combiner, grad_out, default_row=None, long_from=0):
+    """`find_combine_weight_grad` for mixed row lengths (tfra_table_find_combine_backprop_weights_mixed), bit for bit.  float32
+    grad_out."""
+    g = self._weight_grad_out(grad_out, None)
+    ids, seg, w, d, _ = self._find_combine_args(ids, seg, weights, 0, default_row)
+    dw = torch.empty(ids.numel(), dtype=torch.float32, device=self._device)
+    _capi.call("tfra_table_find_combine_backprop_weights_mixed", self._h, _workspace(self._device), ids.numel(), _ptr(ids), _ptr(seg),
+               _ptr(w), int(combiner), g.shape[0], _ptr(d), _ptr(g), _ptr(dw), int(long_from), _stream(self._device))
+    return dw
+
+  def find_combine_ragged_weight_grad_mixed(self, row_splits, ids, weights, combiner, grad_out, prune=False, fill_id=None,
+                                            default_row=None, long_from=0):
+    """`find_combine_ragged_weight_grad` for mixed row lengths (tfra_table_find_combine_ragged_backprop_weights_mixed), bit for bit."""
+    rs, ids, w, flags, fill, d, _ = self._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row)
+    g = self._weight_grad_out(grad_out, rs.numel() - 1)
+    dw = torch.empty(ids.numel(), dtype=torch.float32, device=self._device)
+    _capi.call("tfra_table_find_combine_ragged_backprop_weights_mixed", self._h, rs.numel() - 1, _ptr(rs), ids.numel(), _ptr(ids),
+               _ptr(w), int(combiner), flags, fill, _ptr(d), _ptr(g), _ptr(dw), int(long_from), _stream(self._device))
+    return dw
+
   def find_combine_weight_grad_typed(self, ids, seg, weights, combiner, grad_out, default_row=None, grad_scale=None):
     """`find_combine_weight_grad` that takes grad_out as the dense part of a half model hands it back: a contiguous float16 /
     bfloat16 [n_rows, dim] matrix goes down as it is (tfra_table_find_combine_backprop_weights_typed: no conversion pass, no
@@ -1303,7 +1341,26 @@ class _LongRows:
                                                             fill_id=fill_id, default_row=default_row)
 
 
-class CuckooHashTable(_LookupInterfaceMirror, _WholeRows, _LongRows):
+class _MixedRows:
+  """The mixed-row pooled reads of a plain table's device table (`_DeviceTable.find_combine_mixed` and its three siblings)."""
+
+  def find_combine_mixed(self, ids, seg, weights, combiner, n_rows, default_row=None, long_from=0):
+    return self._table.find_combine_mixed(ids, seg, weights, combiner, n_rows, default_row, long_from=long_from)
+
+  def find_combine_ragged_mixed(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, default_row=None, long_from=0):
+    return self._table.find_combine_ragged_mixed(row_splits, ids, weights, combiner, prune=prune, fill_id=fill_id,
+                                                 default_row=default_row, long_from=long_from)
+
+  def find_combine_weight_grad_mixed(self, ids, seg, weights, combiner, grad_out, default_row=None, long_from=0):
+    return self._table.find_combine_weight_grad_mixed(ids, seg, weights, combiner, grad_out, default_row, long_from=long_from)
+
+  def find_combine_ragged_weight_grad_mixed(self, row_splits, ids, weights, combiner, grad_out, prune=False, fill_id=None,
+                                            default_row=None, long_from=0):
+    return self._table.find_combine_ragged_weight_grad_mixed(row_splits, ids, weights, combiner, grad_out, prune=prune,
+                                                             fill_id=fill_id, default_row=default_row, long_from=long_from)
+
+
+class CuckooHashTable(_LookupInterfaceMirror, _WholeRows, _LongRows, _MixedRows):
   """PY/cuckoo_hashtable_ops.py:45-145.  Growing, never-evicting table (libcuckoo semantics)."""
 
   def __init__(self, key_dtype, value_dtype, default_value, name="CuckooHashTable", checkpoint=True, init_size=0,
@@ -1331,7 +1388,7 @@ class CuckooHashTable(_LookupInterfaceMirror, _WholeRows, _LongRows):
     self._table.accum_or_assign(keys, values_or_deltas, exists)
 
 
-class HkvHashTable(_LookupInterfaceMirror, _WholeRows, _LongRows):
+class HkvHashTable(_LookupInterfaceMirror, _WholeRows, _LongRows, _MixedRows):
   """PY/hkv_hashtable_ops.py:47-175.  Bounded table with per-key scores and in-bucket eviction."""
 
   def __init__(self, key_dtype, value_dtype, default_value, name="HkvHashTable", checkpoint=True,

@@ -116,6 +116,12 @@ def _long_reader(shard, out_dtype):
   return not isinstance(shard, TieredHashTable) and _out_dtype(out_dtype) is None
 
 
+def _not_both(long_rows, mixed_rows):
+  """long_rows and mixed_rows name two launch shapes of the same read: a call takes one of them."""
+  if long_rows and mixed_rows:
+    raise ValueError("long_rows=True and mixed_rows=True exclude each other: mixed_rows serves long rows as well")
+
+
 def misses_are_static(var):
   """Whether a key the optimizer write-back does not find may start from the ONE static default row of `var` (a Variable, or
   anything with its `initializer`): there is no callable initializer, or the step's lookup has admitted every key with its own
@@ -445,7 +451,7 @@ class Variable:
     return (self.init_on_lookup == "pooled" and callable(self.initializer) and self.shard_num == 1 and
             self.value_dtype in PLANNED_VALUE_DTYPES and self.dim % 4 == 0 and self.dim <= 256)
 
-  def lookup_combined(self, ids, seg, weights, combiner, n_rows, name=None, out_dtype=None, long_rows=False):
+  def lookup_combined(self, ids, seg, weights, combiner, n_rows, name=None, out_dtype=None, long_rows=False, mixed_rows=False):
     """The forward of embedding_lookup_sparse as one pooled read (tfra_table_find_combine): [n_rows, dim] float32,
     out[r] = combiner over the entries p with seg[p] == r, in input order, of weights[p] * (row of ids[p], the default row on a
     miss).  seg ascending; weights None = all 1; combiner "sum" / "mean" / "sqrtn".  Bit-identical to
@@ -453,10 +459,16 @@ class Variable:
     out_dtype: the result in float32 / float16 / bfloat16, rounded in the lookup's kernel (tfra_table_find_combine_typed; a tier
     converts behind its call): bit for bit `lookup_combined(...).to(out_dtype)`.
     long_rows: rows of a few hundred entries (a sequence feature) — the read takes tfra_table_find_combine_long, one block per
-    output row, the same bits.  A tiered shard and an out_dtype have no such form and take the call they take without it."""
+    output row, the same bits.  A tiered shard and an out_dtype have no such form and take the call they take without it.
+    mixed_rows: rows of mixed lengths (a heavy-tailed sequence feature: most rows a handful of entries, a few of them hundreds) —
+    the read takes tfra_table_find_combine_mixed, 16 rows per block and a long row by the whole block, the same bits; where
+    long_rows changes nothing, this does not either.  Both keywords together: ValueError."""
+    _not_both(long_rows, mixed_rows)
     t, ids = self._combined_operands(ids, ragged=False)
     if long_rows and _long_reader(t, out_dtype):
       return t._table.find_combine_long(ids, seg, weights, device_ops.COMBINERS[combiner], n_rows, t._default_value)
+    if mixed_rows and _long_reader(t, out_dtype):
+      return t._table.find_combine_mixed(ids, seg, weights, device_ops.COMBINERS[combiner], n_rows, t._default_value)
     if _out_dtype(out_dtype) is not None:
       return _pooled_reader(t).find_combine_typed(ids, seg, weights, device_ops.COMBINERS[combiner], n_rows, t._default_value,
                                                   out_dtype=out_dtype)
@@ -507,16 +519,20 @@ class Variable:
     return self._tables[0], torch.as_tensor(ids, device=self._primary).reshape(-1)
 
   def lookup_combined_ragged(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, name=None, out_dtype=None,
-                             long_rows=False):
+                             long_rows=False, mixed_rows=False):
     """`lookup_combined` over a ragged batch (tfra_table_find_combine_ragged): [n_rows, dim] float32, row r combining the entries
     [row_splits[r], row_splits[r + 1]) — bit-identical to `lookup_combined` on the row ids the splits stand for, in one launch.
     prune / fill_id: safe_embedding_lookup_sparse's pruning by weight and its default_id (`_DeviceTable.find_combine_ragged`).
     Under `can_lookup_combined()`'s conditions.  Never inserts; nothing is read on the host.  out_dtype and long_rows
-    (tfra_table_find_combine_ragged_long): as `lookup_combined`'s."""
+    (tfra_table_find_combine_ragged_long) and mixed_rows (tfra_table_find_combine_ragged_mixed): as `lookup_combined`'s."""
+    _not_both(long_rows, mixed_rows)
     t, ids = self._combined_operands(ids, ragged=True)
     if long_rows and _long_reader(t, out_dtype):
       return t._table.find_combine_ragged_long(row_splits, ids, weights, device_ops.COMBINERS[combiner], prune=prune, fill_id=fill_id,
                                                default_row=t._default_value)
+    if mixed_rows and _long_reader(t, out_dtype):
+      return t._table.find_combine_ragged_mixed(row_splits, ids, weights, device_ops.COMBINERS[combiner], prune=prune, fill_id=fill_id,
+                                                default_row=t._default_value)
     if _out_dtype(out_dtype) is not None:
       return _pooled_reader(t).find_combine_ragged(row_splits, ids, weights, device_ops.COMBINERS[combiner], prune=prune,
                                                    fill_id=fill_id, default_row=t._default_value, out_dtype=out_dtype)
@@ -558,6 +574,24 @@ class Variable:
       return self.lookup_combined_ragged_weight_grad(row_splits, ids, weights, combiner, grad_out, prune=prune, fill_id=fill_id)
     return t._table.find_combine_ragged_weight_grad_long(row_splits, ids, weights, device_ops.COMBINERS[combiner], grad_out,
                                                          prune=prune, fill_id=fill_id, default_row=t._default_value)
+
+  def lookup_combined_weight_grad_mixed(self, ids, seg, weights, combiner, grad_out, name=None):
+    """`lookup_combined_weight_grad` behind `lookup_combined(..., mixed_rows=True)` (tfra_table_find_combine_backprop_weights_mixed:
+    16 rows per block, a long row by the whole block), the same bits.  A tiered shard has no such form and takes
+    `lookup_combined_weight_grad`'s call.  (A method beside it, as `lookup_combined_weight_grad_long` is.)"""
+    t, ids = self._combined_operands(ids, ragged=False)
+    if not _long_reader(t, None):
+      return self.lookup_combined_weight_grad(ids, seg, weights, combiner, grad_out)
+    return t._table.find_combine_weight_grad_mixed(ids, seg, weights, device_ops.COMBINERS[combiner], grad_out, t._default_value)
+
+  def lookup_combined_ragged_weight_grad_mixed(self, row_splits, ids, weights, combiner, grad_out, prune=False, fill_id=None, name=None):
+    """`lookup_combined_ragged_weight_grad` behind `lookup_combined_ragged(..., mixed_rows=True)`
+    (tfra_table_find_combine_ragged_backprop_weights_mixed), the same bits; a tiered shard takes the call it takes without it."""
+    t, ids = self._combined_operands(ids, ragged=True)
+    if not _long_reader(t, None):
+      return self.lookup_combined_ragged_weight_grad(row_splits, ids, weights, combiner, grad_out, prune=prune, fill_id=fill_id)
+    return t._table.find_combine_ragged_weight_grad_mixed(row_splits, ids, weights, device_ops.COMBINERS[combiner], grad_out,
+                                                          prune=prune, fill_id=fill_id, default_row=t._default_value)
 
   def lookup_combined_weight_grad_typed(self, ids, seg, weights, combiner, grad_out, grad_scale=None, name=None):
     """`lookup_combined_weight_grad` that takes grad_out as a half model's dense part hands it back: a contiguous float16 /
@@ -991,11 +1025,14 @@ class SparseTrainableWrapper(TrainableWrapper):
   _ids_are_unique = True
 
   def __init__(self, params, ids, idx, n_unique, seg, weights, combiner, n_rows, out_shape, entry_ids, entry_seg,
-               entry_weights, max_norm=None, plan_writeback=False, lookup_ids=None, entry_plan=None, long_rows=False):
+               entry_weights, max_norm=None, plan_writeback=False, lookup_ids=None, entry_plan=None, long_rows=False,
+               mixed_rows=False):
     """entry_plan: a plan over `entry_ids` whose build is already enqueued (the grouped lookup starts its members' plans in one
-    call); the wrapper owns it from here on, as one made with plan_writeback.  long_rows: the lookup's keyword, which
+    call); the wrapper owns it from here on, as one made with plan_writeback.  long_rows / mixed_rows: the lookup's keyword, which
     `weights_grad` passes on to its pooled read."""
+    _not_both(long_rows, mixed_rows)
     self._long_rows = bool(long_rows)
+    self._mixed_rows = bool(mixed_rows)
     if lookup_ids is None:
       super().__init__(params, ids, max_norm=max_norm)
       self._idx, self._n_unique = idx, n_unique
@@ -1077,7 +1114,8 @@ class SparseTrainableWrapper(TrainableWrapper):
     g = self.check_grad_out(grad_out, keep_half=True)
     if self._pooled_ids is not None and _pooled_training(self.params, None):
       if g.dtype == torch.float32 and grad_scale is None:   # the method it always took
-        grad_of_weights = self.params.lookup_combined_weight_grad_long if self._long_rows else self.params.lookup_combined_weight_grad
+        grad_of_weights = (self.params.lookup_combined_weight_grad_long if self._long_rows else
+                           self.params.lookup_combined_weight_grad_mixed if self._mixed_rows else self.params.lookup_combined_weight_grad)
         dw = grad_of_weights(self._pooled_ids, self._seg, self._weights, self.combiner, g)
       else:
         dw = self.params.lookup_combined_weight_grad_typed(self._pooled_ids, self._seg, self._weights, self.combiner, g,
@@ -1208,7 +1246,7 @@ def _pooled_training(params, max_norm):
 
 def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=None, name="embedding_lookup_sparse",
                             combiner="mean", max_norm=None, return_trainable=False, num_rows=None, plan_writeback=False,
-                            _entries=None, _out_shape=None, out_dtype=None, long_rows=False):
+                            _entries=None, _out_shape=None, out_dtype=None, long_rows=False, mixed_rows=False):
   """PY/dynamic_embedding_ops.py:120-293.  `sp_ids` = (indices[nnz,2] or row_ids[nnz], values[nnz]);
   `sp_weights` = matching weight values or None.  Segment combine sum / mean / sqrtn over rows.
 
@@ -1222,8 +1260,14 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=
   long_rows: the rows hold a few hundred ids each (a sequence feature: a click or watch history).  The pooled read and, through
   the wrapper, `weights_grad` then take the long-row calls (tfra_table_find_combine_long / ..._backprop_weights_long: one block
   per output row), the same bits.  Wherever the plain pooled read does not apply — several shards, tiers, max_norm, bp_v2, other
-  dims or dtypes, out_dtype, a half grad_out — the keyword changes nothing.  Short rows are slower this way (README)."""
+  dims or dtypes, out_dtype, a half grad_out — the keyword changes nothing.  Short rows are slower this way (README).
+
+  mixed_rows: the rows' lengths are mixed (a heavy-tailed history: most rows a handful of ids, a few of them hundreds).  The pooled
+  read and `weights_grad` take the mixed-row calls (tfra_table_find_combine_mixed / ..._backprop_weights_mixed: 16 rows per block, a
+  row of TFRA_MIXED_LONG_FROM_DEFAULT entries or more by the whole block), the same bits; it changes nothing wherever long_rows
+  changes nothing.  long_rows=True together with mixed_rows=True: ValueError.  What it costs and gains: README."""
   _check_combiner(combiner)
+  _not_both(long_rows, mixed_rows)
   _out_dtype(out_dtype)
   indices, ids = sp_ids
   indices = torch.as_tensor(indices, device=params._primary)
@@ -1246,13 +1290,15 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=
       params.admit_entries(e_ids)
     if long_rows and out_dtype is None:
       out = params.lookup_combined(ids, seg, w, combiner, n, long_rows=True)
+    elif mixed_rows and out_dtype is None:
+      out = params.lookup_combined(ids, seg, w, combiner, n, mixed_rows=True)
     else:
       out = params.lookup_combined(ids, seg, w, combiner, n) if out_dtype is None else params.lookup_combined(
           ids, seg, w, combiner, n, out_dtype=out_dtype)
     if not return_trainable:
       return out
     return out, SparseTrainableWrapper(params, None, None, None, seg, w, combiner, n, shape, e_ids, e_seg, e_w, max_norm=max_norm,
-                                       plan_writeback=plan_writeback, lookup_ids=ids, long_rows=long_rows)
+                                       plan_writeback=plan_writeback, lookup_ids=ids, long_rows=long_rows, mixed_rows=mixed_rows)
   if return_trainable:
     tw = SparseTrainableWrapper(params, uniq.reshape(-1), idx, cnt, seg, w, combiner, n, shape, e_ids, e_seg, e_w,
                                 max_norm=max_norm, plan_writeback=plan_writeback)
@@ -1583,7 +1629,8 @@ def _safe_sparse_finish(params, res, rows, n, default_id, max_norm, lead):
 
 def safe_embedding_lookup_sparse(params, sp_ids, sparse_weights=None, combiner="mean", default_id=None,
                                  name="safe_embedding_lookup_sparse", partition_strategy=None, max_norm=None,
-                                 return_trainable=False, num_rows=None, plan_writeback=False, out_dtype=None, long_rows=False):
+                                 return_trainable=False, num_rows=None, plan_writeback=False, out_dtype=None, long_rows=False,
+                                 mixed_rows=False):
   """PY/dynamic_embedding_ops.py:296-430.  `sp_ids` = (indices[nnz, R], values[nnz][, dense_shape[R]]) — a
   SparseTensor of rank R >= 2 (or row ids [nnz] for rank 2).  Semantics of the reference, NOT of
   `tf.nn.safe_embedding_lookup_sparse`: ids are never pruned (any int64 is a legal key, negative ones too,
@@ -1591,15 +1638,16 @@ def safe_embedding_lookup_sparse(params, sp_ids, sparse_weights=None, combiner="
   (`_prune_invalid_weights`, :374-376); rows left without entries yield zeros, or the embedding of
   `default_id` (`sparse_fill_empty_rows`, :379-408); leading dims are flattened for the lookup and restored
   on the result (:356-367, 411-424).  out_dtype: `embedding_lookup_sparse`'s; the default_id row is converted the same way.
-  long_rows: `embedding_lookup_sparse`'s, for the lookup over the kept entries."""
+  long_rows, mixed_rows: `embedding_lookup_sparse`'s, for the lookup over the kept entries."""
   _check_combiner(combiner)
+  _not_both(long_rows, mixed_rows)
   _out_dtype(out_dtype)
   rows, ids, w, n, entries, out_shape, lead = _safe_sparse_args(params, sp_ids, sparse_weights, combiner, default_id,
                                                                  return_trainable, num_rows)
   out = embedding_lookup_sparse(params, (rows, ids), w, combiner=combiner, max_norm=max_norm,
                                 return_trainable=return_trainable, num_rows=n, plan_writeback=plan_writeback,
                                 _entries=entries, _out_shape=out_shape, out_dtype=out_dtype,
-                                **({"long_rows": True} if long_rows else {}))
+                                **({"long_rows": True} if long_rows else {"mixed_rows": True} if mixed_rows else {}))
   res, tw = out if return_trainable else (out, None)
   res = _safe_sparse_finish(params, res, rows, n, default_id, max_norm, lead)
   return (res, _note_pruned(tw, sparse_weights, combiner)) if return_trainable else res
