@@ -1342,7 +1342,8 @@ int tfra_table_find_combine_ragged_backprop_weights(tfra_table_t* t, size_t n_ro
  * wastes most of its lanes there.  The tuple forms enqueue what their twins enqueue (memset, bounds launch, one launch); the ragged
  * forward is one launch, the ragged gradient a memset and one launch.  In the ragged gradient, entries that two overlapping rows
  * claim end as one row's value or a mix, as in the twin.
- * Not provided in this form: typed outputs (tfra_rows_out), a half grad_out (tfra_grads), tiers, and the grouped *_many calls. */
+ * Not provided in this form: typed outputs (tfra_rows_out), a half grad_out (tfra_grads) and tiers.  The grouped forms:
+ * tfra_multi_find_combine_long and its siblings, below. */
 int tfra_table_find_combine_long(tfra_table_t* t, tfra_workspace_t* ws, size_t nnz, const int64_t* ids, const int64_t* seg,
                                  const float* weights, int combiner, size_t n_rows, const void* default_row, float* out,
                                  tfra_stream_t stream);
@@ -1438,6 +1439,35 @@ typedef struct {
 int tfra_multi_find_combine_ragged_backprop_weights(tfra_workspace_t* ws, size_t n_tables,
                                                     const tfra_find_combine_ragged_wgrad_desc* descs,
                                                     uint32_t* launches_out /* optional, host */, tfra_stream_t stream);
+
+/* The grouped pooled calls with LONG members — a model with some twenty categorical features and a handful of
+ * histories, all in one list —: tfra_multi_find_combine, tfra_multi_find_combine_ragged and the two grouped weight gradients above,
+ * with one more argument directly before stream.  long_rows is a HOST array of n_tables bytes: a non-zero byte means that member's
+ * rows are done ONE 256-thread block per row, as tfra_table_find_combine*_long does them; a zero byte leaves the member in the
+ * twin's launch classes and kernels.  NULL: every member is long.  "Long or not" is one more launch-class axis: a long class's
+ * grid is the concatenation of its members' rows, and the launch count depends on the classes present, not on the list's length.
+ * Each member's result is the single call's on its descriptor BIT FOR BIT, flagged or not.  A list with no byte set takes the twin's
+ * launches.  The argument lists, descriptor structs, checks, codes and wording ("multi_find_combine_long: descriptor <i>: ..."),
+ * locks, upload, (tuple forms) memset and bounds launch, the gradients' one zero-fill launch and *launches_out are the twins';
+ * every descriptor is checked before anything is enqueued, and a refused list writes nothing.
+ * The descriptors are read in their plain-table sense: a gradient descriptor that names a tier is refused (TFRA_ERR_UNSUPPORTED).
+ * The gradients also refuse overlapping dw_out ranges among the descriptors with nnz > 0 (TFRA_ERR_INVALID, the message names both
+ * indices), which the twins leave to the caller: a long row of more than 2048 entries parks partial results in its own dw_out.
+ * Not provided in the long classes: typed outputs (tfra_rows_out), a half grad_out (tfra_grads), tiers.  Additive; ABI version 1.
+ *                                                                                          (tests/test_gpu_long_many.py) */
+int tfra_multi_find_combine_long(tfra_workspace_t* ws, size_t n_tables, const tfra_find_combine_desc* descs,
+                                 uint32_t* launches_out /* optional, host */, const uint8_t* long_rows /* host, or NULL */,
+                                 tfra_stream_t stream);
+int tfra_multi_find_combine_ragged_long(tfra_workspace_t* ws, size_t n_tables, const tfra_find_combine_ragged_desc* descs,
+                                        uint32_t* launches_out /* optional, host */, const uint8_t* long_rows /* host, or NULL */,
+                                        tfra_stream_t stream);
+int tfra_multi_find_combine_backprop_weights_long(tfra_workspace_t* ws, size_t n_tables, const tfra_find_combine_wgrad_desc* descs,
+                                                  uint32_t* launches_out /* optional, host */,
+                                                  const uint8_t* long_rows /* host, or NULL */, tfra_stream_t stream);
+int tfra_multi_find_combine_ragged_backprop_weights_long(tfra_workspace_t* ws, size_t n_tables,
+                                                         const tfra_find_combine_ragged_wgrad_desc* descs,
+                                                         uint32_t* launches_out /* optional, host */,
+                                                         const uint8_t* long_rows /* host, or NULL */, tfra_stream_t stream);
 
 /* -- Half-precision grad_out in the weight gradients: the seven calls above that read grad_out [n_rows, dim], taking
  *    it as a tfra_grads record (with the half-precision gradients, above) — the float16 / bfloat16 matrix a half model hands to

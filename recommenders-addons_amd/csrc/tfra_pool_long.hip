@@ -6,7 +6,7 @@
 // in entry order and with the twins' expressions (the bodies and why the bits are the twins': tfra_pool_long_device.h).
 // The calls take their twins' argument lists and run their twins' host frames (the four *_call templates of tfra_pool.h over a
 // TableOwner: checks, lock, early returns, the tuple forms' memset and bounds launch); what stands here is each call's launch.  The
-// ragged forward is one launch.  float32 out and grad_out only: no typed, tiered or grouped forms.
+// ragged forward is one launch.  float32 out and grad_out only: no typed or tiered forms (the grouped forms: tfra_pool_long_many.hip).
 #include <hip/hip_runtime.h>
 
 #include <mutex>

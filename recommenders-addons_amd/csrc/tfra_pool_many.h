@@ -100,6 +100,10 @@ struct PoolDesc {
   float* dw_out;
   const tfra_rows_out* typed;   // the typed lookups (plain tables only): the output record in the place of out; NULL otherwise
   const tfra_grads* hgrads;     // the typed weight gradients: the record in the place of grad_out; NULL otherwise
+  // the *_long calls (tfra_pool_long_many.h): the descriptor came through one of them (plain tables, float32 out and grad_out
+  // only), and its rows are done one block per row (its flag byte)
+  bool long_abi = false;
+  bool long_rows = false;
 };
 typedef PoolDesc (*PoolDescAt)(const void* descs, size_t i);
 
@@ -129,7 +133,10 @@ int pool_class(const Table* t) { return st_index(t->opts.value_dtype) * 3 + nch_
 int out_index(const PoolDesc& d) { return d.typed ? st_index(d.typed->dtype) : 0; }
 const float* out_checked(const PoolDesc& d) { return d.typed ? out_for_twin(*d.typed) : d.out; }   // what the twin's checks look at
 float* out_rows(const PoolDesc& d) { return d.typed ? static_cast<float*>(d.typed->rows) : d.out; }
-unsigned row_blocks(const PoolDesc& d) { return (unsigned)((d.n_rows * 16 + 255) / 256); }
+// the blocks a descriptor owns in its class's grid: 16 rows per block, or (a long member) one block per row — n_rows < 2^30
+unsigned row_blocks(const PoolDesc& d) { return d.long_rows ? (unsigned)d.n_rows : (unsigned)((d.n_rows * 16 + 255) / 256); }
+// what only a descriptor of the *_long calls can get wrong: they take plain tables alone
+const char* const LONG_NO_TIER = "the long calls take plain tables only (tier must be NULL)";
 
 // The records' order: class by class, input order inside a class; first[c] is where class c starts, first[n_class] the number of
 // active descriptors.  The classes of plain tables come first: they are the one-table call's, in its order.

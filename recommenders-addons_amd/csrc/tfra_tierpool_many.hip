@@ -22,6 +22,7 @@
 #include "tfra_many.h"
 #include "tfra_pool.h"
 #include "tfra_pool_device.h"
+#include "tfra_pool_long_many.h"
 #include "tfra_pool_many.h"
 #include "tfra_tier.h"
 
@@ -82,8 +83,9 @@ int multi_find_combine_frame(const char* who_c, tfra_workspace* ws, size_t n_tab
   if (!ws || !descs) return set_error(TFRA_ERR_INVALID, who + ": null argument");
   // every descriptor is checked before anything is enqueued: one bad descriptor and no out is written
   // plain: (out float32 | float16 | bfloat16) x (float32 | float16 | bfloat16) x (NCH 1 | 2 | 4), out float32 first: the untyped
-  // calls' classes in their order; tiered: (float32 | float16 | bfloat16) x NCH
-  constexpr int NUNTYPED = 9, NPLAIN = 27, NCLASS = 36;
+  // calls' classes in their order; tiered: (float32 | float16 | bfloat16) x NCH; long (the *_long call's flagged members, plain
+  // and untyped): (float32 | float16 | bfloat16) x NCH, one block per row
+  constexpr int NUNTYPED = 9, NPLAIN = 27, NSHORT = 36, NCLASS = 45;
   std::vector<PoolDesc> ds(n_tables);
   std::vector<int> cls(n_tables, -1);
   std::vector<size_t> se_off(n_tables, 0);   // a descriptor's bounds in the bounds area, in input order
@@ -101,7 +103,7 @@ int multi_find_combine_frame(const char* who_c, tfra_workspace* ws, size_t n_tab
                                        [] { return Check{}; });
     if (c.code) return report(at_i(), c);
     if (!c.active) continue;
-    cls[i] = (d.tier ? NPLAIN : out_index(d) * NUNTYPED) + pool_class(t);
+    cls[i] = (d.long_rows ? NSHORT : d.tier ? NPLAIN : out_index(d) * NUNTYPED) + pool_class(t);
     n_bnd += d.nnz ? 1 : 0;
     bnd_blocks += (d.nnz + 255) / 256;
     se_off[i] = 2 * total_rows;
@@ -110,7 +112,7 @@ int multi_find_combine_frame(const char* who_c, tfra_workspace* ws, size_t n_tab
   std::vector<size_t> order;
   size_t first[NCLASS + 1];
   if (int rc = order_by_class(who, ds, cls, NCLASS, &order, first)) return rc;
-  const size_t n_act = order.size(), n_plain = first[NPLAIN];
+  const size_t n_act = order.size(), n_plain = first[NPLAIN], n_short = first[NSHORT];
   if (n_act == 0) return TFRA_OK;
   if (bnd_blocks >= (1ULL << 31)) return set_error(TFRA_ERR_UNSUPPORTED, who + ": too many entries in one call");
 
@@ -118,11 +120,12 @@ int multi_find_combine_frame(const char* who_c, tfra_workspace* ws, size_t n_tab
   int rc = lock_owners(ds, order, s, &locks);
   if (rc) return rc;
 
-  // device memory: [bounds of all rows | blob], the blob = [one-table records | tier records | per-class block prefixes | bounds
-  // records | their block prefix]
+  // device memory: [bounds of all rows | blob], the blob = [one-table records | tier records | long members' records | per-class
+  // block prefixes | bounds records | their block prefix]
   const size_t se_bytes = (2 * total_rows * sizeof(int) + 255) / 256 * 256;
   Blob blob;
-  const size_t rec_off = blob.add<ManyRec>(n_plain), trec_off = blob.add<TierManyRec>(n_act - n_plain);
+  const size_t rec_off = blob.add<ManyRec>(n_plain), trec_off = blob.add<TierManyRec>(n_short - n_plain);
+  const size_t lrec_off = blob.add<ManyRec>(n_act - n_short);
   const size_t cpre_off = blob.add<unsigned>(ClassPool::words(n_act, NCLASS, false));
   const size_t brec_off = blob.add<BoundsRec>(n_bnd), bpre_off = blob.add<unsigned>(ClassPool::words(n_bnd, 1, false));
   ManyUpload up;
@@ -131,6 +134,7 @@ int multi_find_combine_frame(const char* who_c, tfra_workspace* ws, size_t n_tab
   int* se_base = (int*)ws->buf;
   ManyRec* recs = section<ManyRec>(up.host, rec_off);
   TierManyRec* trecs = section<TierManyRec>(up.host, trec_off);
+  ManyRec* lrecs = section<ManyRec>(up.host, lrec_off);
   BoundsRec* brecs = section<BoundsRec>(up.host, brec_off);
   // the views are taken here, under the locks: a table that grew since the last call has another one
   for (size_t k = 0; k < n_act; ++k) {
@@ -138,7 +142,8 @@ int multi_find_combine_frame(const char* who_c, tfra_workspace* ws, size_t n_tab
     Table* t = d.tier ? d.tier->upper : d.table;
     const ManyRec r{t->view_of(t->cur), d.n_rows, (const i64*)d.ids, d.weights, se_base + se_off[order[k]],
                     (const unsigned char*)d.default_row, out_rows(d), t->opts.dim, d.combiner};
-    if (d.tier) trecs[k - n_plain] = TierManyRec{r, d.tier->lower->view_of(d.tier->lower->cur)};
+    if (d.long_rows) lrecs[k - n_short] = r;
+    else if (d.tier) trecs[k - n_plain] = TierManyRec{r, d.tier->lower->view_of(d.tier->lower->cur)};
     else recs[k] = r;
   }
   ClassPool cpool{section<unsigned>(up.host, cpre_off)};
@@ -167,7 +172,9 @@ int multi_find_combine_frame(const char* who_c, tfra_workspace* ws, size_t n_tab
     const unsigned* p = section<const unsigned>(up.dev, cpre_off) + k.at;
     if (c < NUNTYPED) launch_find_combine_many(s, c, k.grid, section<const ManyRec>(up.dev, rec_off) + first[c], p, k.n);
     else if (c < NPLAIN) launch_find_combine_many_typed(s, c - NUNTYPED, k.grid, section<const ManyRec>(up.dev, rec_off) + first[c], p, k.n);
-    else launch_tier_find_combine_many(s, c - NPLAIN, k.grid, section<const TierManyRec>(up.dev, trec_off) + (first[c] - n_plain), p, k.n);
+    else if (c < NSHORT)
+      launch_tier_find_combine_many(s, c - NPLAIN, k.grid, section<const TierManyRec>(up.dev, trec_off) + (first[c] - n_plain), p, k.n);
+    else launch_find_combine_long_many(s, c - NSHORT, k.grid, section<const ManyRec>(up.dev, lrec_off) + (first[c] - n_short), p, k.n);
     ++launches;
   }
   HIP_TRY(hipGetLastError());
@@ -184,8 +191,9 @@ int multi_find_combine_ragged_frame(const char* who_c, tfra_workspace* ws, size_
   if (!ws || !descs) return set_error(TFRA_ERR_INVALID, who + ": null argument");
   // every descriptor is checked before anything is enqueued: one bad descriptor and no out is written
   // plain: (out float32 | float16 | bfloat16) x (float32 | float16 | bfloat16) x (NCH 1 | 2 | 4) x (plain | safe), out float32
-  // first: the untyped calls' classes in their order; tiered: (float32 | float16 | bfloat16) x NCH x (plain | safe)
-  constexpr int NUNTYPED = 18, NPLAIN = 54, NCLASS = 72;
+  // first: the untyped calls' classes in their order; tiered: (float32 | float16 | bfloat16) x NCH x (plain | safe); long (the
+  // *_long call's flagged members, plain and untyped): (float32 | float16 | bfloat16) x NCH x (plain | safe), one block per row
+  constexpr int NUNTYPED = 18, NPLAIN = 54, NSHORT = 72, NCLASS = 90;
   std::vector<PoolDesc> ds(n_tables);
   std::vector<int> cls(n_tables, -1);
   for (size_t i = 0; i < n_tables; ++i) {
@@ -200,34 +208,38 @@ int multi_find_combine_ragged_frame(const char* who_c, tfra_workspace* ws, size_
                                               d.default_row, out_checked(d), [] { return Check{}; });
     if (c.code) return report(at_i(), c);
     if (!c.active) continue;
-    cls[i] = (d.tier ? NPLAIN : out_index(d) * NUNTYPED) + pool_class(t) * 2 + (ragged_safe(d.flags, d.weights) ? 1 : 0);
+    cls[i] = (d.long_rows ? NSHORT : d.tier ? NPLAIN : out_index(d) * NUNTYPED) + pool_class(t) * 2 + (ragged_safe(d.flags, d.weights) ? 1 : 0);
   }
   std::vector<size_t> order;
   size_t first[NCLASS + 1];
   if (int rc = order_by_class(who, ds, cls, NCLASS, &order, first)) return rc;
-  const size_t n_act = order.size(), n_plain = first[NPLAIN];
+  const size_t n_act = order.size(), n_plain = first[NPLAIN], n_short = first[NSHORT];
   if (n_act == 0) return TFRA_OK;
 
   PoolLocks locks;
   int rc = lock_owners(ds, order, s, &locks);
   if (rc) return rc;
 
-  // device memory: the blob alone = [one-table records | tier records | per-class block prefixes]; there are no bounds to keep
+  // device memory: the blob alone = [one-table records | tier records | long members' records | per-class block prefixes]; there
+  // are no bounds to keep
   Blob blob;
-  const size_t rec_off = blob.add<RaggedRec>(n_plain), trec_off = blob.add<TierRaggedRec>(n_act - n_plain);
+  const size_t rec_off = blob.add<RaggedRec>(n_plain), trec_off = blob.add<TierRaggedRec>(n_short - n_plain);
+  const size_t lrec_off = blob.add<RaggedRec>(n_act - n_short);
   const size_t cpre_off = blob.add<unsigned>(ClassPool::words(n_act, NCLASS, false));
   ManyUpload up;
   rc = many_begin(ws, 0, blob.bytes(), s, &up);
   if (rc) return rc;
   RaggedRec* recs = section<RaggedRec>(up.host, rec_off);
   TierRaggedRec* trecs = section<TierRaggedRec>(up.host, trec_off);
+  RaggedRec* lrecs = section<RaggedRec>(up.host, lrec_off);
   // the views are taken here, under the locks: a table that grew since the last call has another one
   for (size_t k = 0; k < n_act; ++k) {
     const PoolDesc& d = ds[order[k]];
     Table* t = d.tier ? d.tier->upper : d.table;
     const RaggedRec r{t->view_of(t->cur), d.n_rows, (const i64*)d.ids, d.weights, (const i64*)d.row_splits,
                       (const unsigned char*)d.default_row, out_rows(d), (i64)d.fill_id, (int)d.nnz, t->opts.dim, d.combiner, d.flags};
-    if (d.tier) trecs[k - n_plain] = TierRaggedRec{r, d.tier->lower->view_of(d.tier->lower->cur)};
+    if (d.long_rows) lrecs[k - n_short] = r;
+    else if (d.tier) trecs[k - n_plain] = TierRaggedRec{r, d.tier->lower->view_of(d.tier->lower->cur)};
     else recs[k] = r;
   }
   ClassPool cpool{section<unsigned>(up.host, cpre_off)};
@@ -243,8 +255,11 @@ int multi_find_combine_ragged_frame(const char* who_c, tfra_workspace* ws, size_
     if (c < NUNTYPED) launch_find_combine_ragged_many(s, c / 2, c & 1, k.grid, section<const RaggedRec>(up.dev, rec_off) + first[c], p, k.n);
     else if (c < NPLAIN)
       launch_find_combine_ragged_many_typed(s, (c - NUNTYPED) / 2, c & 1, k.grid, section<const RaggedRec>(up.dev, rec_off) + first[c], p, k.n);
-    else launch_tier_find_combine_ragged_many(s, (c - NPLAIN) / 2, c & 1, k.grid,
-                                              section<const TierRaggedRec>(up.dev, trec_off) + (first[c] - n_plain), p, k.n);
+    else if (c < NSHORT)
+      launch_tier_find_combine_ragged_many(s, (c - NPLAIN) / 2, c & 1, k.grid,
+                                           section<const TierRaggedRec>(up.dev, trec_off) + (first[c] - n_plain), p, k.n);
+    else launch_find_combine_ragged_long_many(s, (c - NSHORT) / 2, c & 1, k.grid,
+                                              section<const RaggedRec>(up.dev, lrec_off) + (first[c] - n_short), p, k.n);
     ++launches;
   }
   HIP_TRY(hipGetLastError());

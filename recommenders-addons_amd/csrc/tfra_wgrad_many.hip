@@ -23,6 +23,7 @@
 #include "tfra_host.h"
 #include "tfra_many.h"
 #include "tfra_pool.h"
+#include "tfra_pool_long_many.h"
 #include "tfra_pool_many.h"
 #include "tfra_tier.h"
 #include "tfra_wgrad_device.h"
@@ -266,6 +267,26 @@ WgradHalf half_rec(const PoolDesc& d) {
   return desc_half(d) ? WgradHalf{d.hgrads->d_scale, d.hgrads->dtype == TFRA_BF16, 0} : WgradHalf{nullptr, 0, 0};
 }
 
+// What only a list of the *_long calls can get wrong.  They take plain tables alone; and the dw_out ranges of their
+// written descriptors must be disjoint, which the twins leave to the caller: a long row past LONG_PARK entries parks its d_p in its
+// own dw_out range and reads it back, so another member's writes there would change VALUES, not only which of two results stays.
+int check_long_owner(const std::string& at, const PoolDesc& d) {
+  return d.long_abi && d.tier ? set_error(TFRA_ERR_UNSUPPORTED, at + LONG_NO_TIER) : TFRA_OK;
+}
+int check_long_disjoint(const std::string& who, const std::vector<PoolDesc>& ds, const std::vector<size_t>& written) {
+  if (written.empty() || !ds[written[0]].long_abi) return TFRA_OK;
+  std::vector<size_t> by_addr(written);
+  std::sort(by_addr.begin(), by_addr.end(), [&](size_t a, size_t b) { return std::less<const float*>()(ds[a].dw_out, ds[b].dw_out); });
+  for (size_t k = 1; k < by_addr.size(); ++k) {
+    const PoolDesc &lo = ds[by_addr[k - 1]], &hi = ds[by_addr[k]];
+    if ((uintptr_t)hi.dw_out < (uintptr_t)lo.dw_out + lo.nnz * sizeof(float))
+      return set_error(TFRA_ERR_INVALID, who + ": descriptor " + std::to_string(std::max(by_addr[k - 1], by_addr[k])) +
+                                             ": dw_out overlaps the dw_out of descriptor " +
+                                             std::to_string(std::min(by_addr[k - 1], by_addr[k])));
+  }
+  return TFRA_OK;
+}
+
 // ---- the tuple form ----------------------------------------------------------------------------------------------------------------
 int multi_wgrad_frame(const std::string& who, tfra_workspace* ws, size_t n_tables, const void* descs, PoolDescAt at,
                       uint32_t* launches_out, hipStream_t s) {
@@ -273,8 +294,9 @@ int multi_wgrad_frame(const std::string& who, tfra_workspace* ws, size_t n_table
   if (n_tables == 0) return TFRA_OK;
   if (!ws || !descs) return set_error(TFRA_ERR_INVALID, who + ": null argument");
   // every descriptor is checked before anything is enqueued: one bad descriptor and no dw_out is written
-  // (plain | tiered) x (float | half grad_out) x (float32 | float16 | bfloat16 rows) x (NCH 1 | 2 | 4)
-  constexpr int NBASE = 9, NPLAIN = 2 * NBASE, NCLASS = 2 * NPLAIN;
+  // (plain | tiered) x (float | half grad_out) x (float32 | float16 | bfloat16 rows) x (NCH 1 | 2 | 4); then the long classes (the
+  // *_long call's flagged members: plain tables, float grad_out): (float32 | float16 | bfloat16 rows) x NCH, one block per row
+  constexpr int NBASE = 9, NPLAIN = 2 * NBASE, NSHORT = 2 * NPLAIN, NCLASS = NSHORT + NBASE;
   bool any_half = false;
   std::vector<PoolDesc> ds(n_tables);
   std::vector<int> cls(n_tables, -1);
@@ -290,22 +312,24 @@ int multi_wgrad_frame(const std::string& who, tfra_workspace* ws, size_t n_table
     Table* t = nullptr;
     const char* why = nullptr;
     if (int rc = desc_owner(d, &t, &why)) return set_error(rc, at_i + why);
+    if (int rc = check_long_owner(at_i, d)) return rc;
     const Check c = check_find_combine(t, ws, d.nnz, d.ids, d.seg, d.weights, d.combiner, d.n_rows, d.default_row, grad_checked(d),
                                        [] { return Check{}; });
     if (int rc = check_wgrad_desc(at_i, d, c)) return rc;
     if (d.nnz == 0) continue;   // nothing to write
     zf.add(i, d);
     if (!c.active) continue;    // no rows: zeros alone
-    cls[i] = (d.tier ? NPLAIN : 0) + (desc_half(d) ? NBASE : 0) + pool_class(t);
+    cls[i] = d.long_rows ? NSHORT + pool_class(t) : (d.tier ? NPLAIN : 0) + (desc_half(d) ? NBASE : 0) + pool_class(t);
     any_half = any_half || desc_half(d);
     se_off[i] = 2 * total_rows;
     total_rows += d.n_rows;
   }
   if (zf.zeroed.empty()) return TFRA_OK;
+  if (int rc = check_long_disjoint(who, ds, zf.zeroed)) return rc;
   std::vector<size_t> order;
   size_t first[NCLASS + 1];
   if (int rc = order_by_class(who, ds, cls, NCLASS, &order, first)) return rc;
-  const size_t n_act = order.size(), n_plain = first[NPLAIN];
+  const size_t n_act = order.size(), n_plain = first[NPLAIN], n_short = first[NSHORT];
   if (int rc = zf.check(who)) return rc;
 
   PoolLocks locks;   // of every descriptor that is written, as the single call enters its table before its memset
@@ -316,7 +340,8 @@ int multi_wgrad_frame(const std::string& who, tfra_workspace* ws, size_t n_table
   // records | their block prefix]
   const size_t se_bytes = (2 * total_rows * sizeof(int) + 255) / 256 * 256;
   Blob blob;
-  const size_t rec_off = blob.add<WgradRec>(n_plain), trec_off = blob.add<TierWgradRec>(n_act - n_plain);
+  const size_t rec_off = blob.add<WgradRec>(n_plain), trec_off = blob.add<TierWgradRec>(n_short - n_plain);
+  const size_t lrec_off = blob.add<LongWgradRec>(n_act - n_short);   // the long members' records
   const size_t hrec_off = blob.add<WgradHalf>(any_half ? n_act : 0);   // at the records' positions k, plain and tier alike
   const size_t cpre_off = blob.add<unsigned>(ClassPool::words(n_act, NCLASS, false));
   zf.lay_out(&blob);
@@ -326,6 +351,7 @@ int multi_wgrad_frame(const std::string& who, tfra_workspace* ws, size_t n_table
   int* se_base = (int*)ws->buf;
   WgradRec* recs = section<WgradRec>(up.host, rec_off);
   TierWgradRec* trecs = section<TierWgradRec>(up.host, trec_off);
+  LongWgradRec* lrecs = section<LongWgradRec>(up.host, lrec_off);
   WgradHalf* hrecs = section<WgradHalf>(up.host, hrec_off);
   // the views are taken here, under the locks: a table that grew since the last call has another one
   for (size_t k = 0; k < n_act; ++k) {
@@ -333,7 +359,9 @@ int multi_wgrad_frame(const std::string& who, tfra_workspace* ws, size_t n_table
     Table* t = d.tier ? d.tier->upper : d.table;
     const WgradRec r{t->view_of(t->cur), d.n_rows, (const i64*)d.ids, d.weights, se_base + se_off[order[k]],
                      (const unsigned char*)d.default_row, grad_rows(d), d.dw_out, t->opts.dim, d.combiner};
-    if (d.tier) trecs[k - n_plain] = TierWgradRec{r, d.tier->lower->view_of(d.tier->lower->cur)};
+    if (d.long_rows)
+      lrecs[k - n_short] = LongWgradRec{r.v, r.n_rows, r.ids, r.w, r.se, r.default_row, r.grad_out, r.dw, r.dim, r.combiner};
+    else if (d.tier) trecs[k - n_plain] = TierWgradRec{r, d.tier->lower->view_of(d.tier->lower->cur)};
     else recs[k] = r;
     if (any_half) hrecs[k] = half_rec(d);
   }
@@ -352,6 +380,11 @@ int multi_wgrad_frame(const std::string& who, tfra_workspace* ws, size_t n_table
     const ManyClass& k = row_cls[c];
     if (!k.n) continue;
     const unsigned* p = section<const unsigned>(up.dev, cpre_off) + k.at;
+    ++launches;
+    if (c >= NSHORT) {   // one block per row (tfra_pool_long_many.hip)
+      launch_wgrad_long_many(s, c - NSHORT, k.grid, section<const LongWgradRec>(up.dev, lrec_off) + (first[c] - n_short), p, k.n);
+      continue;
+    }
     const bool half = (c % NPLAIN) >= NBASE;
     // a half class's scales and formats stand at its records' positions (any_half holds then)
     const WgradHalf* hr = half ? section<const WgradHalf>(up.dev, hrec_off) + first[c] : nullptr;
@@ -366,7 +399,6 @@ int multi_wgrad_frame(const std::string& who, tfra_workspace* ws, size_t n_table
         else tier_wgrad_many_kernel<DT, U, NCH><<<k.grid, 256, 0, s>>>(tr, p, k.n);
       }
     });
-    ++launches;
   }
   HIP_TRY(hipGetLastError());
   if (launches_out) *launches_out = launches;
@@ -380,8 +412,9 @@ int multi_wgrad_ragged_frame(const std::string& who, tfra_workspace* ws, size_t 
   if (n_tables == 0) return TFRA_OK;
   if (!ws || !descs) return set_error(TFRA_ERR_INVALID, who + ": null argument");
   // every descriptor is checked before anything is enqueued: one bad descriptor and no dw_out is written
-  // (plain | tiered) x (float | half grad_out) x (float32 | float16 | bfloat16 rows) x (NCH 1 | 2 | 4) x (plain | pruning)
-  constexpr int NBASE = 18, NPLAIN = 2 * NBASE, NCLASS = 2 * NPLAIN;
+  // (plain | tiered) x (float | half grad_out) x (float32 | float16 | bfloat16 rows) x (NCH 1 | 2 | 4) x (plain | pruning); then
+  // the long classes (the *_long call's flagged members): (float32 | float16 | bfloat16 rows) x NCH x (plain | pruning)
+  constexpr int NBASE = 18, NPLAIN = 2 * NBASE, NSHORT = 2 * NPLAIN, NCLASS = NSHORT + NBASE;
   bool any_half = false;
   std::vector<PoolDesc> ds(n_tables);
   std::vector<int> cls(n_tables, -1);
@@ -395,6 +428,7 @@ int multi_wgrad_ragged_frame(const std::string& who, tfra_workspace* ws, size_t 
     Table* t = nullptr;
     const char* why = nullptr;
     if (int rc = desc_owner(d, &t, &why)) return set_error(rc, at_i + why);
+    if (int rc = check_long_owner(at_i, d)) return rc;
     const Check c = check_find_combine_ragged(t, ws, d.n_rows, d.row_splits, d.nnz, d.ids, d.weights, d.combiner, d.flags, d.reserved,
                                               d.default_row, grad_checked(d), [] { return Check{}; });
     if (int rc = check_wgrad_desc(at_i, d, c)) return rc;
@@ -402,14 +436,16 @@ int multi_wgrad_ragged_frame(const std::string& who, tfra_workspace* ws, size_t 
     zf.add(i, d);
     if (!c.active) continue;    // no rows: zeros alone
     // the fourth axis is PRUNE, as in the single calls: FILL changes nothing, and PRUNE without weights neither
-    cls[i] = (d.tier ? NPLAIN : 0) + (desc_half(d) ? NBASE : 0) + pool_class(t) * 2 + (((d.flags & TFRA_RAGGED_PRUNE) && d.weights) ? 1 : 0);
+    cls[i] = (d.long_rows ? NSHORT : (d.tier ? NPLAIN : 0) + (desc_half(d) ? NBASE : 0)) + pool_class(t) * 2 +
+             (((d.flags & TFRA_RAGGED_PRUNE) && d.weights) ? 1 : 0);
     any_half = any_half || desc_half(d);
   }
   if (zf.zeroed.empty()) return TFRA_OK;
+  if (int rc = check_long_disjoint(who, ds, zf.zeroed)) return rc;
   std::vector<size_t> order;
   size_t first[NCLASS + 1];
   if (int rc = order_by_class(who, ds, cls, NCLASS, &order, first)) return rc;
-  const size_t n_act = order.size(), n_plain = first[NPLAIN];
+  const size_t n_act = order.size(), n_plain = first[NPLAIN], n_short = first[NSHORT];
   if (int rc = zf.check(who)) return rc;
 
   PoolLocks locks;   // of every descriptor that is written, as the single call enters its table before its memset
@@ -419,7 +455,8 @@ int multi_wgrad_ragged_frame(const std::string& who, tfra_workspace* ws, size_t 
   // device memory: the blob alone = [one-table records | tier records | per-class block prefixes | zero-fill records | their block
   // prefix]; there are no bounds to keep
   Blob blob;
-  const size_t rec_off = blob.add<WgradRaggedRec>(n_plain), trec_off = blob.add<TierWgradRaggedRec>(n_act - n_plain);
+  const size_t rec_off = blob.add<WgradRaggedRec>(n_plain), trec_off = blob.add<TierWgradRaggedRec>(n_short - n_plain);
+  const size_t lrec_off = blob.add<LongWgradRaggedRec>(n_act - n_short);   // the long members' records
   const size_t hrec_off = blob.add<WgradHalf>(any_half ? n_act : 0);   // at the records' positions k, plain and tier alike
   const size_t cpre_off = blob.add<unsigned>(ClassPool::words(n_act, NCLASS, false));
   zf.lay_out(&blob);
@@ -428,6 +465,7 @@ int multi_wgrad_ragged_frame(const std::string& who, tfra_workspace* ws, size_t 
   if (rc) return rc;
   WgradRaggedRec* recs = section<WgradRaggedRec>(up.host, rec_off);
   TierWgradRaggedRec* trecs = section<TierWgradRaggedRec>(up.host, trec_off);
+  LongWgradRaggedRec* lrecs = section<LongWgradRaggedRec>(up.host, lrec_off);
   WgradHalf* hrecs = section<WgradHalf>(up.host, hrec_off);
   // the views are taken here, under the locks: a table that grew since the last call has another one
   for (size_t k = 0; k < n_act; ++k) {
@@ -435,7 +473,9 @@ int multi_wgrad_ragged_frame(const std::string& who, tfra_workspace* ws, size_t 
     Table* t = d.tier ? d.tier->upper : d.table;
     const WgradRaggedRec r{t->view_of(t->cur), d.n_rows, (const i64*)d.ids, d.weights, (const i64*)d.row_splits,
                            (const unsigned char*)d.default_row, grad_rows(d), d.dw_out, (int)d.nnz, t->opts.dim, d.combiner};
-    if (d.tier) trecs[k - n_plain] = TierWgradRaggedRec{r, d.tier->lower->view_of(d.tier->lower->cur)};
+    if (d.long_rows)
+      lrecs[k - n_short] = LongWgradRaggedRec{r.v, r.n_rows, r.ids, r.w, r.row_splits, r.default_row, r.grad_out, r.dw, r.nnz, r.dim, r.combiner};
+    else if (d.tier) trecs[k - n_plain] = TierWgradRaggedRec{r, d.tier->lower->view_of(d.tier->lower->cur)};
     else recs[k] = r;
     if (any_half) hrecs[k] = half_rec(d);
   }
@@ -451,6 +491,12 @@ int multi_wgrad_ragged_frame(const std::string& who, tfra_workspace* ws, size_t 
     const ManyClass& k = row_cls[c];
     if (!k.n) continue;
     const unsigned* p = section<const unsigned>(up.dev, cpre_off) + k.at;
+    if (c >= NSHORT) {   // one block per row (tfra_pool_long_many.hip)
+      launch_wgrad_ragged_long_many(s, (c - NSHORT) / 2, c & 1, k.grid,
+                                    section<const LongWgradRaggedRec>(up.dev, lrec_off) + (first[c] - n_short), p, k.n);
+      ++launches;
+      continue;
+    }
     const int pc = (c % NBASE) / 2;
     const bool half = (c % NPLAIN) >= NBASE;
     const WgradHalf* hr = half ? section<const WgradHalf>(up.dev, hrec_off) + first[c] : nullptr;
@@ -501,9 +547,42 @@ PoolDesc wgrad_ragged_typed_desc_at(const void* descs, size_t i) {
   return p;
 }
 
+// the *_long calls: the untyped descriptors, each with its flag beside it (LongDescs)
+PoolDesc wgrad_long_desc_at(const void* descs, size_t i) {
+  const LongDescs& l = *static_cast<const LongDescs*>(descs);
+  PoolDesc p = wgrad_desc_at(l.descs, i);
+  p.long_abi = true;
+  p.long_rows = l.flagged(i);
+  return p;
+}
+PoolDesc wgrad_ragged_long_desc_at(const void* descs, size_t i) {
+  const LongDescs& l = *static_cast<const LongDescs*>(descs);
+  PoolDesc p = wgrad_ragged_desc_at(l.descs, i);
+  p.long_abi = true;
+  p.long_rows = l.flagged(i);
+  return p;
+}
+
 }  // namespace
 
 // ---- the entry points ----------------------------------------------------------------------------------------------------------------
+extern "C" int tfra_multi_find_combine_backprop_weights_long(tfra_workspace_t* ws, size_t n_tables,
+                                                             const tfra_find_combine_wgrad_desc* descs, uint32_t* launches_out,
+                                                             const uint8_t* long_rows, tfra_stream_t stream) {
+  const LongDescs l{descs, long_rows};
+  return multi_wgrad_frame("multi_find_combine_backprop_weights_long", ws, n_tables, descs ? &l : nullptr, wgrad_long_desc_at,
+                           launches_out, (hipStream_t)stream);
+}
+
+extern "C" int tfra_multi_find_combine_ragged_backprop_weights_long(tfra_workspace_t* ws, size_t n_tables,
+                                                                    const tfra_find_combine_ragged_wgrad_desc* descs,
+                                                                    uint32_t* launches_out, const uint8_t* long_rows,
+                                                                    tfra_stream_t stream) {
+  const LongDescs l{descs, long_rows};
+  return multi_wgrad_ragged_frame("multi_find_combine_ragged_backprop_weights_long", ws, n_tables, descs ? &l : nullptr,
+                                  wgrad_ragged_long_desc_at, launches_out, (hipStream_t)stream);
+}
+
 extern "C" int tfra_multi_find_combine_backprop_weights(tfra_workspace_t* ws, size_t n_tables, const tfra_find_combine_wgrad_desc* descs,
                                                         uint32_t* launches_out, tfra_stream_t stream) {
   return multi_wgrad_frame("multi_find_combine_backprop_weights", ws, n_tables, descs, wgrad_desc_at, launches_out, (hipStream_t)stream);

@@ -455,6 +455,14 @@ _SIGS_MIXED = {
     "tfra_table_find_combine_ragged_backprop_weights_mixed": [_P, _SZ, _P, _SZ, _P, _P, _I, ctypes.c_uint32, ctypes.c_int64, _P, _P,
                                                               _P, ctypes.c_uint32, _P],
 }
+# The grouped pooled calls with long members (one block per row for the flagged ones): their twins' lists plus the host array of
+# flag bytes before the stream.  A table of its own for the same reason.
+_SIGS_LONG_MANY = {
+    "tfra_multi_find_combine_long": [_P, _SZ, _P, _P, _P, _P],
+    "tfra_multi_find_combine_ragged_long": [_P, _SZ, _P, _P, _P, _P],
+    "tfra_multi_find_combine_backprop_weights_long": [_P, _SZ, _P, _P, _P, _P],
+    "tfra_multi_find_combine_ragged_backprop_weights_long": [_P, _SZ, _P, _P, _P, _P],
+}
 
 _lib = None
 
@@ -468,7 +476,7 @@ def lib():
           "%s not found: run `python recommenders-addons_amd/build.py` (hipcc, gfx950). "
           "There is no CPU fallback." % LIB_PATH)
     l = ctypes.CDLL(LIB_PATH)
-    for name, args in list(_SIGS.items()) + list(_SIGS_MIXED.items()):
+    for name, args in list(_SIGS.items()) + list(_SIGS_MIXED.items()) + list(_SIGS_LONG_MANY.items()):
       f = getattr(l, name)
       f.argtypes = args
       f.restype = ctypes.c_int

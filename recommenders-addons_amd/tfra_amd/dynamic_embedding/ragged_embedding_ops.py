@@ -165,9 +165,11 @@ def safe_embedding_lookup_sparse(params, sparse_ids, sparse_weights=None, combin
   return out, _safe_wrapper(params, made, combiner, n, plan_writeback, caller_weights=w, **_long(long_rows, None, mixed_rows))
 
 
-def _many(params_list, sp_ids_list, weights_list, combiner, default_id, safe, return_trainable, plan_writeback, out_dtype=None):
+def _many(params_list, sp_ids_list, weights_list, combiner, default_id, safe, return_trainable, plan_writeback, out_dtype=None,
+          long_rows=False):
   typed = _typed(out_dtype)
   n_t = len(params_list)
+  longs = [bool(x) for x in _per_table(long_rows, n_t, "long_rows")]
   if len(sp_ids_list) != n_t:
     raise ValueError("sp_ids_list: %d entries for %d tables" % (len(sp_ids_list), n_t))
   weights = _per_table(None if weights_list is None else list(weights_list), n_t, "sp_weights_list")
@@ -197,7 +199,7 @@ def _many(params_list, sp_ids_list, weights_list, combiner, default_id, safe, re
   for i in singles:
     kw = dict(default_id=default_ids[i]) if safe else {}
     results[i] = single(params_list[i], sp_ids_list[i], weights[i], combiner=combiners[i], return_trainable=return_trainable,
-                        plan_writeback=plan_writeback, **kw, **typed)
+                        plan_writeback=plan_writeback, **kw, **typed, **({"long_rows": True} if longs[i] else {}))
   for device, members in groups.items():
     if return_trainable:
       _admit_entries_many(params_list, {m[0]: entry_ids[m[0]] for m in members})   # (tiered members; ahead of the ONE read)
@@ -206,7 +208,8 @@ def _many(params_list, sp_ids_list, weights_list, combiner, default_id, safe, re
       t = params_list[i]._tables[0]
       prune, fill = _safe_flags(w, combiners[i], default_ids[i]) if safe else (False, None)
       reqs.append((_pooled_reader(t), rs, ids, w, device_ops.COMBINERS[combiners[i]], prune, fill, t._default_value))
-    outs = table_ops.find_combine_ragged_many(reqs, **typed)
+    flagged = {"long_rows": [longs[m[0]] for m in members]} if any(longs[m[0]] for m in members) else {}
+    outs = table_ops.find_combine_ragged_many(reqs, **typed, **flagged)
     if not return_trainable:
       for (i, _, _, _), out in zip(members, outs):
         results[i] = out
@@ -215,30 +218,35 @@ def _many(params_list, sp_ids_list, weights_list, combiner, default_id, safe, re
     def wrapper(member, own_plan, entry_plan):
       i, rs, ids, w = member
       params, n = params_list[i], rs.numel() - 1
-      return (_safe_wrapper(params, made[i], combiners[i], n, own_plan, entry_plan, caller_weights=w) if safe else
-              _plain_wrapper(params, rs, ids, w, combiners[i], n, own_plan, entry_plan))
+      return (_safe_wrapper(params, made[i], combiners[i], n, own_plan, entry_plan, caller_weights=w, long_rows=longs[i]) if safe
+              else _plain_wrapper(params, rs, ids, w, combiners[i], n, own_plan, entry_plan, long_rows=longs[i]))
 
     _wrap_grouped(device, params_list, members, outs, {m[0]: entry_ids[m[0]] for m in members}, plan_writeback, wrapper, results)
   return results
 
 
 def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None, combiner="mean", return_trainable=False,
-                                 plan_writeback=False, out_dtype=None):
+                                 plan_writeback=False, out_dtype=None, long_rows=False):
   """`embedding_lookup_sparse` of a LIST of variables: result i is what the single form returns for table i, bit for bit.
   `combiner` is a scalar or a per-table list.  The variables the pooled forward serves are read by ONE grouped call per device
   (`table_ops.find_combine_ragged_many`: tfra_multi_find_combine_ragged — one upload and one launch per class, no bounds pass; with
   a tiered variable among them tfra_multi_tier_find_combine_ragged, which reads that member in both tiers — with return_trainable
   behind one admission of its entry ids per tiered member); every other variable takes the single form, so no list is refused.
   out_dtype: one of float32 / float16 / bfloat16 for every result, as the single form's (tfra_multi_find_combine_ragged_typed: the
-  same launch count; a group with a tiered member is converted)."""
-  return _many(params_list, sp_ids_list, sp_weights_list, combiner, None, False, return_trainable, plan_writeback, out_dtype)
+  same launch count; a group with a tiered member is converted).
+  long_rows: one bool or one per table, the single form's keyword per member: a group with a flagged member is read by
+  tfra_multi_find_combine_ragged_long (the flagged members' rows one block per row, the same bits) and each wrapper remembers its
+  flag for `de.sparse_weights_grad_many`; tiered members and an out_dtype keep today's grouped call."""
+  return _many(params_list, sp_ids_list, sp_weights_list, combiner, None, False, return_trainable, plan_writeback, out_dtype, long_rows)
 
 
 def safe_embedding_lookup_sparse_many(params_list, sp_ids_list, sparse_weights_list=None, combiner="mean", default_id=None,
-                                      return_trainable=False, plan_writeback=False, out_dtype=None):
+                                      return_trainable=False, plan_writeback=False, out_dtype=None, long_rows=False):
   """`safe_embedding_lookup_sparse` of a LIST of variables: result i is what the single form returns for table i, bit for bit.
   `combiner` and `default_id` are scalars or per-table lists.  One grouped call per device for the variables the pooled forward
   serves (tiered ones included, as in `embedding_lookup_sparse_many`), with no host synchronisation in the forward; with
   return_trainable the wrappers' entry lists of all tables come from one `device_ops.safe_entries_many` per device (one C call,
-  one host read of every list's length), ahead of the grouped call: they are what a tiered member admits."""
-  return _many(params_list, sp_ids_list, sparse_weights_list, combiner, default_id, True, return_trainable, plan_writeback, out_dtype)
+  one host read of every list's length), ahead of the grouped call: they are what a tiered member admits.
+  long_rows: as `embedding_lookup_sparse_many`'s."""
+  return _many(params_list, sp_ids_list, sparse_weights_list, combiner, default_id, True, return_trainable, plan_writeback, out_dtype,
+               long_rows)

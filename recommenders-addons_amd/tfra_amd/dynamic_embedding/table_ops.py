@@ -1756,7 +1756,7 @@ def _pooled_owner(e, owner, tiered):
   return table
 
 
-def _grouped_call(c_name, desc_type, who, owners, fill):
+def _grouped_call(c_name, desc_type, who, owners, fill, long_flags=None):
   """The frame of the grouped calls (`find_combine_many`, `find_combine_ragged_many`, their `*_weight_grad_many` forms,
   `apply_planned_combined_many`, `build_plans_many`): ONE C call `c_name(workspace, n, descs, &launches, stream)` over one descriptor of `desc_type` per entry of
   `owners`, on the current stream of the one device all of them live on.  An owner is a _DeviceTable, a CuckooHashTable /
@@ -1764,7 +1764,9 @@ def _grouped_call(c_name, desc_type, who, owners, fill):
   or a SparsePlan.  Member by member, the owner's device (`_owner_device`) is compared
   with the first one's (ValueError in the name of `who`), then `fill(descs[i], i)` checks the member's arguments and sets the
   descriptor's fields behind struct_size.  What `fill` returns — the tensors whose data_ptr() it stored — stays referenced here
-  until the C call has returned.  Returns the number of kernel launches the call enqueued."""
+  until the C call has returned.  Returns the number of kernel launches the call enqueued.
+  long_flags (the tfra_multi_find_combine*_long calls): one bool per owner, handed down as the host array of flag bytes that
+  those calls take in front of the stream."""
   descs = (desc_type * len(owners))()
   keep, device = [], _owner_device(owners[0])
   for i, owner in enumerate(owners):
@@ -1774,9 +1776,40 @@ def _grouped_call(c_name, desc_type, who, owners, fill):
     descs[i].struct_size = ctypes.sizeof(desc_type)
     keep.append(fill(descs[i], i))
   launches = ctypes.c_uint32(0)
+  extra = ()
+  if long_flags is not None:
+    flag_bytes = (ctypes.c_uint8 * len(owners))(*[1 if f else 0 for f in long_flags])
+    extra = (ctypes.c_void_p(ctypes.addressof(flag_bytes)),)
   _capi.call(c_name, _workspace(device), len(owners), ctypes.c_void_p(ctypes.addressof(descs)),
-             ctypes.c_void_p(ctypes.addressof(launches)), _stream(device))
+             ctypes.c_void_p(ctypes.addressof(launches)), *(extra + (_stream(device),)))
   return int(launches.value)
+
+
+def _long_routes(who, fn, requests, long_rows, stays, return_launches, **per_request):
+  """`long_rows=` of a grouped pooled call `fn`: one bool for the list or one per request.  The requests that the long classes do
+  not serve (`stays(i)`: a tiered owner, a typed output, a half grad_out) keep today's grouped call, their flag ignored; the
+  remaining ones go to the tfra_multi_find_combine*_long call (`fn(..., _long=their flags)`) when at least one of them is flagged.
+  Returns None when nothing is flagged among them — the caller goes on as it always did —, else the merged results in the
+  requests' order (with return_launches: and the launches of both calls).  per_request: keywords of `fn` that may hold one entry
+  per request, split with the requests."""
+  n = len(requests)
+  flags = list(long_rows) if isinstance(long_rows, (list, tuple)) else [long_rows] * n
+  if len(flags) != n:
+    raise ValueError("%s: long_rows must be one bool or one per request: %d for %d requests" % (who, len(flags), n))
+  rest = [i for i in range(n) if not stays(i)]
+  if not any(flags[i] for i in rest):
+    return None
+  kept = [i for i in range(n) if stays(i)]
+  results, launches = [None] * n, 0
+  for idx, lng in ((kept, None), (rest, [bool(flags[i]) for i in rest])):
+    if not idx:
+      continue
+    kw = {k: ([v[i] for i in idx] if isinstance(v, (list, tuple)) else v) for k, v in per_request.items()}
+    outs, l = fn([requests[i] for i in idx], True, _long=lng, **kw)
+    for i, o in zip(idx, outs):
+      results[i] = o
+    launches += l
+  return (results, launches) if return_launches else results
 
 
 def _out_dtypes(out_dtype, n):
@@ -1796,7 +1829,7 @@ def _converted(result, dts, return_launches):
   return (outs, result[1]) if return_launches else outs
 
 
-def find_combine_many(requests, return_launches=False, out_dtype=None):
+def find_combine_many(requests, return_launches=False, out_dtype=None, long_rows=None, _long=None):
   """The pooled lookups of a list of tables in ONE C call (tfra_multi_find_combine; the frame: `_grouped_call`).  `requests`: a
   list of (table, ids, seg, weights, combiner, n_rows[, default_row]), the arguments behind `table` those of
   `_DeviceTable.find_combine`, handled the same way (int32 keys widened, the default row falling back to the table's).  Returns
@@ -1808,12 +1841,22 @@ def find_combine_many(requests, return_launches=False, out_dtype=None):
   out_dtype: one of float32 / float16 / bfloat16 for the list, or one per request (None: float32): each result in that type,
   rounded in the lookup's kernel (tfra_multi_find_combine_typed), bit for bit `result.to(out_dtype)`; the output type is one more
   launch-class axis, so a list with one output type keeps its launch count.  The tier calls are not typed: a list with a tiered
-  member runs untyped as a whole and each result is converted."""
+  member runs untyped as a whole and each result is converted.
+  long_rows: one bool for the list or one per request — the request's rows hold a few hundred ids each (a sequence feature) and
+  are done one block per row (tfra_multi_find_combine_long: "long or not" is one more launch-class axis), the same bits.  None or
+  all false: today's call, call for call.  The long classes serve plain tables and float32 results: a request with a tiered owner
+  or an out_dtype keeps today's grouped call, its flag ignored (`_long_routes`); the others go to the new call together."""
   if not requests:
     return ([], 0) if return_launches else []
   outs = []
   tiered = any(_device_tier(r[0]) is not None for r in requests)
   dts = _out_dtypes(out_dtype, len(requests))
+  if long_rows is not None:
+    routed = _long_routes("find_combine_many", find_combine_many, requests, long_rows,
+                          lambda i: _device_tier(requests[i][0]) is not None or (dts is not None and dts[i] is not None),
+                          return_launches, out_dtype=dts)
+    if routed is not None:
+      return routed
   if dts is not None and tiered:
     return _converted(find_combine_many(requests, return_launches), dts, return_launches)
 
@@ -1831,12 +1874,13 @@ def find_combine_many(requests, return_launches=False, out_dtype=None):
 
   c_name, desc_type = (("tfra_multi_tier_find_combine", _capi.TierFindCombineDesc) if tiered else
                        ("tfra_multi_find_combine_typed", _capi.FindCombineTypedDesc) if dts else
+                       ("tfra_multi_find_combine_long", _capi.FindCombineDesc) if _long else
                        ("tfra_multi_find_combine", _capi.FindCombineDesc))
-  launches = _grouped_call(c_name, desc_type, "find_combine_many", [r[0] for r in requests], fill)
+  launches = _grouped_call(c_name, desc_type, "find_combine_many", [r[0] for r in requests], fill, _long)
   return (outs, launches) if return_launches else outs
 
 
-def find_combine_ragged_many(requests, return_launches=False, out_dtype=None):
+def find_combine_ragged_many(requests, return_launches=False, out_dtype=None, long_rows=None, _long=None):
   """The ragged pooled lookups of a list of tables in ONE C call (tfra_multi_find_combine_ragged; the frame: `_grouped_call`).
   `requests`: a list of (table, row_splits, ids, weights, combiner[, prune[, fill_id[, default_row]]]), the arguments behind
   `table` those of `_DeviceTable.find_combine_ragged`, handled the same way.  A table may occur more than once.  Returns the
@@ -1845,12 +1889,19 @@ def find_combine_ragged_many(requests, return_launches=False, out_dtype=None):
   class in the list).  `table` may be a TieredHashTable or a _DeviceTier, as in `find_combine_many`: the request is read in both
   tiers, the fill id too, and the whole list goes through tfra_multi_tier_find_combine_ragged (one launch per (tiered or not,
   value dtype, row-width class, safe-or-not) class); a list without a tiered owner takes the call it always took.
-  out_dtype: as `find_combine_many`'s (tfra_multi_find_combine_ragged_typed)."""
+  out_dtype: as `find_combine_many`'s (tfra_multi_find_combine_ragged_typed).  long_rows: as `find_combine_many`'s
+  (tfra_multi_find_combine_ragged_long)."""
   if not requests:
     return ([], 0) if return_launches else []
   outs = []
   tiered = any(_device_tier(r[0]) is not None for r in requests)
   dts = _out_dtypes(out_dtype, len(requests))
+  if long_rows is not None:
+    routed = _long_routes("find_combine_ragged_many", find_combine_ragged_many, requests, long_rows,
+                          lambda i: _device_tier(requests[i][0]) is not None or (dts is not None and dts[i] is not None),
+                          return_launches, out_dtype=dts)
+    if routed is not None:
+      return routed
   if dts is not None and tiered:
     return _converted(find_combine_ragged_many(requests, return_launches), dts, return_launches)
 
@@ -1873,8 +1924,9 @@ def find_combine_ragged_many(requests, return_launches=False, out_dtype=None):
 
   c_name, desc_type = (("tfra_multi_tier_find_combine_ragged", _capi.TierFindCombineRaggedDesc) if tiered else
                        ("tfra_multi_find_combine_ragged_typed", _capi.FindCombineRaggedTypedDesc) if dts else
+                       ("tfra_multi_find_combine_ragged_long", _capi.FindCombineRaggedDesc) if _long else
                        ("tfra_multi_find_combine_ragged", _capi.FindCombineRaggedDesc))
-  launches = _grouped_call(c_name, desc_type, "find_combine_ragged_many", [r[0] for r in requests], fill)
+  launches = _grouped_call(c_name, desc_type, "find_combine_ragged_many", [r[0] for r in requests], fill, _long)
   return (outs, launches) if return_launches else outs
 
 
@@ -1914,6 +1966,12 @@ def _splits_rows(row_splits):
 
 
 def find_combine_weight_grad_many(requests, return_launches=False, grad_scale=None):
+  """`find_combine_weight_grad_many_long` without flags: today's call.  (Its parameter list is pinned; the gradient's `long_rows`
+  stands on the function below, whose documentation is this one's.)"""
+  return find_combine_weight_grad_many_long(requests, return_launches, grad_scale)
+
+
+def find_combine_weight_grad_many_long(requests, return_launches=False, grad_scale=None, long_rows=None, _long=None):
   """The weight gradients of a list of pooled lookups in ONE C call (tfra_multi_find_combine_backprop_weights; the frame:
   `_grouped_call`).  `requests`: a list of (table, ids, seg, weights, combiner, grad_out[, default_row]), the arguments behind
   `table` those of `_DeviceTable.find_combine_weight_grad`, handled the same way (n_rows is grad_out's).  `table` is a table, a
@@ -1924,11 +1982,19 @@ def find_combine_weight_grad_many(requests, return_launches=False, grad_scale=No
   grad_scale: one scale for all requests, or a list with one (or None) per request, as `find_combine_weight_grad_typed` takes it.
   As soon as one request's grad_out goes down as a half matrix (contiguous float16 / bfloat16), the call is
   tfra_multi_find_combine_backprop_weights_typed — float32 members ride along as float32 descriptors, float-or-half being one
-  more launch-class axis —; otherwise it is the untyped call, as always."""
+  more launch-class axis —; otherwise it is the untyped call, as always.
+  long_rows: as `find_combine_many`'s, for the gradient (tfra_multi_find_combine_backprop_weights_long): give a request the flag
+  its forward had.  A request with a tiered owner or a half grad_out keeps today's grouped call, its flag ignored."""
   if not requests:
     return ([], 0) if return_launches else []
   dws = []
   grads, any_typed = _request_grads("find_combine_weight_grad_many", requests, grad_scale, lambda r: None)
+  if long_rows is not None:
+    routed = _long_routes("find_combine_weight_grad_many", find_combine_weight_grad_many_long, requests, long_rows,
+                          lambda i: _device_tier(requests[i][0]) is not None or grads[i][0] is not None, return_launches,
+                          grad_scale=grad_scale)
+    if routed is not None:
+      return routed
 
   def fill(e, i):
     req = requests[i]
@@ -1946,8 +2012,9 @@ def find_combine_weight_grad_many(requests, return_launches=False, grad_scale=No
     return ids, seg, w, d, g
 
   c_name, desc_type = (("tfra_multi_find_combine_backprop_weights_typed", _capi.FindCombineWgradTypedDesc) if any_typed else
+                       ("tfra_multi_find_combine_backprop_weights_long", _capi.FindCombineWgradDesc) if _long else
                        ("tfra_multi_find_combine_backprop_weights", _capi.FindCombineWgradDesc))
-  launches = _grouped_call(c_name, desc_type, "find_combine_weight_grad_many", [r[0] for r in requests], fill)
+  launches = _grouped_call(c_name, desc_type, "find_combine_weight_grad_many", [r[0] for r in requests], fill, _long)
   return (dws, launches) if return_launches else dws
 
 
@@ -1959,17 +2026,29 @@ def _grads_field(typed, g, any_typed):
 
 
 def find_combine_ragged_weight_grad_many(requests, return_launches=False, grad_scale=None):
+  """`find_combine_ragged_weight_grad_many_long` without flags: today's call (a pinned parameter list, as above)."""
+  return find_combine_ragged_weight_grad_many_long(requests, return_launches, grad_scale)
+
+
+def find_combine_ragged_weight_grad_many_long(requests, return_launches=False, grad_scale=None, long_rows=None, _long=None):
   """The weight gradients of a list of ragged pooled lookups in ONE C call (tfra_multi_find_combine_ragged_backprop_weights; the
   frame: `_grouped_call`).  `requests`: a list of (table, row_splits, ids, weights, combiner, grad_out[, prune[, fill_id[,
   default_row]]]), the arguments behind `table` those of `_DeviceTable.find_combine_ragged_weight_grad`, handled the same way;
   `table` as in `find_combine_weight_grad_many`.  Returns the float32 [nnz] gradients in the requests' order, each bit-identical
   to `find_combine_ragged_weight_grad` of its request (with return_launches: also the number of kernel launches: one that
   zero-fills all results and one per (tiered or not, value dtype, row-width class, pruning or not) class in the list).
-  grad_scale and half gradients as in `find_combine_weight_grad_many` (tfra_multi_find_combine_ragged_backprop_weights_typed)."""
+  grad_scale and half gradients as in `find_combine_weight_grad_many` (tfra_multi_find_combine_ragged_backprop_weights_typed);
+  long_rows as there (tfra_multi_find_combine_ragged_backprop_weights_long)."""
   if not requests:
     return ([], 0) if return_launches else []
   dws = []
   grads, any_typed = _request_grads("find_combine_ragged_weight_grad_many", requests, grad_scale, lambda r: _splits_rows(r[1]))
+  if long_rows is not None:
+    routed = _long_routes("find_combine_ragged_weight_grad_many", find_combine_ragged_weight_grad_many_long, requests, long_rows,
+                          lambda i: _device_tier(requests[i][0]) is not None or grads[i][0] is not None, return_launches,
+                          grad_scale=grad_scale)
+    if routed is not None:
+      return routed
 
   def fill(e, i):
     req = requests[i]
@@ -1991,8 +2070,9 @@ def find_combine_ragged_weight_grad_many(requests, return_launches=False, grad_s
     return rs, ids, w, d, g
 
   c_name, desc_type = (("tfra_multi_find_combine_ragged_backprop_weights_typed", _capi.FindCombineRaggedWgradTypedDesc) if any_typed
+                       else ("tfra_multi_find_combine_ragged_backprop_weights_long", _capi.FindCombineRaggedWgradDesc) if _long
                        else ("tfra_multi_find_combine_ragged_backprop_weights", _capi.FindCombineRaggedWgradDesc))
-  launches = _grouped_call(c_name, desc_type, "find_combine_ragged_weight_grad_many", [r[0] for r in requests], fill)
+  launches = _grouped_call(c_name, desc_type, "find_combine_ragged_weight_grad_many", [r[0] for r in requests], fill, _long)
   return (dws, launches) if return_launches else dws
 
 

@@ -1165,7 +1165,11 @@ def sparse_weights_grad_many(grads_and_wrappers, grad_scale=None):
       tw = pairs[i][1]
       t, ids = tw.params._combined_operands(tw._pooled_ids, ragged=False)
       reqs.append((_pooled_reader(t), ids, tw._seg, tw._weights, device_ops.COMBINERS[tw.combiner], checked[i], t._default_value))
-    for i, dw in zip(members, table_ops.find_combine_weight_grad_many(reqs, grad_scale=grad_scale)):
+    # the flags the forwards had (`embedding_lookup_sparse[_many](..., long_rows=)`): the same route for the gradient
+    flags = [pairs[i][1]._long_rows for i in members]
+    dws = (table_ops.find_combine_weight_grad_many_long(reqs, grad_scale=grad_scale, long_rows=flags) if any(flags) else
+           table_ops.find_combine_weight_grad_many(reqs, grad_scale=grad_scale))
+    for i, dw in zip(members, dws):
       cw = pairs[i][1]._caller_weights
       if cw is not None:   # (weights_grad: the kept positions are filled from dw in order, on the device)
         cw = torch.as_tensor(cw, dtype=torch.float32, device=dw.device).reshape(-1)
@@ -1409,7 +1413,7 @@ def _wrap_grouped(device, params_list, members, outs, entry_ids, plan_writeback,
 
 def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None, combiner="mean", max_norm=None,
                                  return_trainable=False, num_rows=None, plan_writeback=False, _entries_list=None,
-                                 _out_shapes=None, out_dtype=None):
+                                 _out_shapes=None, out_dtype=None, long_rows=False):
   """`embedding_lookup_sparse` of a LIST of variables (a many-table model's sparse features): result i is what
   `embedding_lookup_sparse(params_list[i], sp_ids_list[i], sp_weights_list[i], ...)` returns, bit for bit — with return_trainable
   the (result, SparseTrainableWrapper) pair, the wrapper built behind the pooled forward.  `combiner` and `num_rows` are scalars
@@ -1423,12 +1427,18 @@ def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None,
   one side stream (`_plans_at_lookup_many`: tfra_multi_sparse_plan_build).  Where num_rows is absent, the grouped variables' row counts
   come from one host read per device, not one per table.  out_dtype: one of float32 / float16 / bfloat16 for every result, as the
   single form's: a group of plain tables is rounded in the grouped call's kernels (tfra_multi_find_combine_typed, the same launch
-  count), a group with a tiered member and every single-form member are converted."""
+  count), a group with a tiered member and every single-form member are converted.
+  long_rows: one bool or one per table, `embedding_lookup_sparse`'s keyword per member — a model's histories beside its
+  categorical features in ONE list.  A group with a flagged member is read by tfra_multi_find_combine_long (the flagged members'
+  rows one block per row: one more launch class, the same bits); each wrapper remembers its flag, and
+  `sparse_weights_grad_many` hands the flags down, so that forward and weight gradient take the same route.  Tiered members and
+  an out_dtype keep today's grouped call; members off the pooled route are served as today."""
   _out_dtype(out_dtype)
   n_t = len(params_list)
   if len(sp_ids_list) != n_t:
     raise ValueError("sp_ids_list: %d entries for %d tables" % (len(sp_ids_list), n_t))
   weights = _per_table(None if sp_weights_list is None else list(sp_weights_list), n_t, "sp_weights_list")
+  longs = [bool(x) for x in _per_table(long_rows, n_t, "long_rows")]
   combiners = _per_table(combiner, n_t, "combiner")
   rows = _per_table(num_rows, n_t, "num_rows")
   entries = _per_table(None if _entries_list is None else list(_entries_list), n_t, "_entries_list")
@@ -1445,7 +1455,8 @@ def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None,
     if not pooled(params, max_norm):
       results[i] = embedding_lookup_sparse(params, sp_ids_list[i], weights[i], combiner=combiners[i], max_norm=max_norm,
                                            return_trainable=return_trainable, num_rows=rows[i], plan_writeback=plan_writeback,
-                                           _entries=entries[i], _out_shape=shapes[i], out_dtype=out_dtype)
+                                           _entries=entries[i], _out_shape=shapes[i], out_dtype=out_dtype,
+                                           **({"long_rows": True} if longs[i] else {}))
       continue
     indices, ids = sp_ids_list[i]
     indices = torch.as_tensor(indices, device=params._primary)
@@ -1463,7 +1474,9 @@ def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None,
     for i, ids, seg, w in members:
       t = params_list[i]._tables[0]
       reqs.append((_pooled_reader(t), ids.reshape(-1), seg, w, device_ops.COMBINERS[combiners[i]], rows[i], t._default_value))
-    outs = table_ops.find_combine_many(reqs) if out_dtype is None else table_ops.find_combine_many(reqs, out_dtype=out_dtype)
+    flagged = {"long_rows": [longs[m[0]] for m in members]} if any(longs[m[0]] for m in members) else {}
+    outs = (table_ops.find_combine_many(reqs, **flagged) if out_dtype is None else
+            table_ops.find_combine_many(reqs, out_dtype=out_dtype, **flagged))
     if not return_trainable:
       for (i, ids, seg, w), out in zip(members, outs):
         results[i] = out
@@ -1474,7 +1487,7 @@ def embedding_lookup_sparse_many(params_list, sp_ids_list, sp_weights_list=None,
       params, n = params_list[i], rows[i]
       return SparseTrainableWrapper(params, None, None, None, seg, w, combiners[i], n,
                                     shapes[i] if shapes[i] is not None else (n, params.dim), *ent[i], max_norm=max_norm,
-                                    plan_writeback=own_plan, lookup_ids=ids, entry_plan=entry_plan)
+                                    plan_writeback=own_plan, lookup_ids=ids, entry_plan=entry_plan, long_rows=longs[i])
 
     _wrap_grouped(device, params_list, members, outs, {i: e[0] for i, e in ent.items()}, plan_writeback, wrapper, results)
   return results
@@ -1654,9 +1667,10 @@ def safe_embedding_lookup_sparse(params, sp_ids, sparse_weights=None, combiner="
 
 
 def safe_embedding_lookup_sparse_many(params_list, sp_ids_list, sparse_weights_list=None, combiner="mean", default_id=None,
-                                      max_norm=None, return_trainable=False, num_rows=None, plan_writeback=False, out_dtype=None):
+                                      max_norm=None, return_trainable=False, num_rows=None, plan_writeback=False, out_dtype=None,
+                                      long_rows=False):
   """`safe_embedding_lookup_sparse` of a LIST of variables: result i is what the single form returns for table i, bit for bit
-  (out_dtype: one for every result, as `embedding_lookup_sparse_many`'s).
+  (out_dtype: one for every result, as `embedding_lookup_sparse_many`'s; long_rows: one bool or one per table, as there).
   `combiner`, `default_id` and `num_rows` are scalars or per-table lists.  The preprocessing is the single form's
   (`_safe_sparse_args_many`: all tables' kept lists and entry lists from one builder call and one host read per device); the
   lookups go through `embedding_lookup_sparse_many`, one grouped call per device for the variables the pooled forward serves.  Row counts that neither a dense_shape nor num_rows gives are read in one host read per device."""
@@ -1681,7 +1695,7 @@ def safe_embedding_lookup_sparse_many(params_list, sp_ids_list, sparse_weights_l
   outs = embedding_lookup_sparse_many(params_list, [(a[0], a[1]) for a in args], [a[2] for a in args], combiner=combiners,
                                       max_norm=max_norm, return_trainable=return_trainable, num_rows=[a[3] for a in args],
                                       plan_writeback=plan_writeback, _entries_list=[a[4] for a in args],
-                                      _out_shapes=[a[5] for a in args], out_dtype=out_dtype)
+                                      _out_shapes=[a[5] for a in args], out_dtype=out_dtype, long_rows=long_rows)
   results = []
   for i, (rows, ids, w, n, entries, out_shape, lead) in enumerate(args):
     res, tw = outs[i] if return_trainable else (outs[i], None)
