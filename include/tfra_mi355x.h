@@ -1385,6 +1385,34 @@ int tfra_table_find_combine_ragged_backprop_weights_mixed(tfra_table_t* t, size_
                                                           int64_t fill_id, const void* default_row, const float* grad_out,
                                                           float* dw_out, uint32_t long_from, tfra_stream_t stream);
 
+/* The same four calls for WIDE rows — a table of 384, 512, 768 or 1024 columns: pretrained text or image embeddings,
+ * a wide user tower —: the argument lists, checks, refusals (in the twins' words behind the call's own name), locking and
+ * nnz == 0 behaviour of tfra_table_find_combine, tfra_table_find_combine_ragged and their *_backprop_weights forms, and what they
+ * enqueue (tuple forms: memset, bounds launch, one launch; ragged forward: one launch; ragged gradient: a memset and one launch).
+ * The one difference is the width: float32, float16 and bfloat16 tables with dim % 4 == 0 and 256 < dim <= 1024; every other dim
+ * is TFRA_ERR_UNSUPPORTED, and the message names the twins for dim <= 256.  ONE wave64 owns an output row, four rows per block:
+ * the forward deals the row's columns out over the 64 lanes, the gradient its entries over the four 16-lane groups.
+ * Results: the forward is BIT FOR BIT tfra_unique, tfra_table_find, then tfra_sparse_segment_combine at that dim (PRUNE and FILL as
+ * in the ragged twin, a FILL row written as it is); the gradient BIT FOR BIT tfra_sparse_segment_combine_backprop_weights on the
+ * looked-up rows.  Overlapping rows of a ragged gradient end as in the twin.
+ * Not provided in this form: typed outputs (tfra_rows_out), a half grad_out (tfra_grads), tiers, the grouped *_many calls,
+ * long-row blocks at wide dims, and the planned write-back beyond dim 256.  Additive; ABI version 1.
+ *                                                                             (tests/test_wide_rows_abi.py, tests/test_gpu_wide_rows.py) */
+int tfra_table_find_combine_wide(tfra_table_t* t, tfra_workspace_t* ws, size_t nnz, const int64_t* ids, const int64_t* seg,
+                                 const float* weights, int combiner, size_t n_rows, const void* default_row, float* out,
+                                 tfra_stream_t stream);
+int tfra_table_find_combine_ragged_wide(tfra_table_t* t, size_t n_rows, const int64_t* row_splits, size_t nnz,
+                                        const int64_t* ids, const float* weights, int combiner, uint32_t flags,
+                                        int64_t fill_id, const void* default_row, float* out, tfra_stream_t stream);
+int tfra_table_find_combine_backprop_weights_wide(tfra_table_t* t, tfra_workspace_t* ws, size_t nnz, const int64_t* ids,
+                                                  const int64_t* seg, const float* weights, int combiner, size_t n_rows,
+                                                  const void* default_row, const float* grad_out, float* dw_out,
+                                                  tfra_stream_t stream);
+int tfra_table_find_combine_ragged_backprop_weights_wide(tfra_table_t* t, size_t n_rows, const int64_t* row_splits, size_t nnz,
+                                                         const int64_t* ids, const float* weights, int combiner, uint32_t flags,
+                                                         int64_t fill_id, const void* default_row, const float* grad_out,
+                                                         float* dw_out, tfra_stream_t stream);
+
 /* The weight gradients of MANY pooled lookups in one call (a model with 26 weighted sparse features asks for 26 of them per step:
  * ~100 enqueues for 26 small kernels otherwise).  A descriptor names exactly ONE of table / tier, as tfra_tier_find_combine_desc
  * does; descs[i].dw_out is bit-identical to the single call on that descriptor — the same device function runs:

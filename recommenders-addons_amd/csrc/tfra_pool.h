@@ -1,4 +1,5 @@
-// What the pooled lookups (tfra_pool.hip; typed: tfra_pool_typed.hip; long rows: tfra_pool_long.hip; over a tier: tfra_tierpool.hip)
+// What the pooled lookups (tfra_pool.hip; typed: tfra_pool_typed.hip; long rows: tfra_pool_long.hip; wide rows, with their weight
+// gradients: tfra_pool_wide.hip; over a tier: tfra_tierpool.hip)
 // and the gradients of their weights (tfra_wgrad.hip; over a tier: tfra_tierwgrad.hip; over a list: tfra_wgrad_many.hip) share, ONE
 // copy each: the up-cast of a stored row (PoolRow), the launch ladders by value dtype and row width (with_pool_class,
 // with_ragged_class), the argument checks of the tuple and the ragged call (check_find_combine, check_find_combine_ragged;
@@ -84,16 +85,26 @@ void with_pool_class(int st, int nch, F&& launch) {
 // The checks of a pooled lookup, for tfra_table_find_combine and for each descriptor of tfra_multi_find_combine.
 // active: there are rows to write.
 const char* const NEEDS_DIM = "needs dim % 4 == 0 and dim <= 256";
+// The row widths a pooled call serves, as a rule: its refusal's words, or nullptr.  narrow_dims is the rule of every call but the
+// wide-row ones (tfra_pool_wide.hip), which bring wide_dims; an owner names another rule than narrow_dims as Owner::DIMS (dims_of).
+typedef const char* (*DimRule)(int dim);
+const char* narrow_dims(int dim) { return dim % 4 != 0 || dim > 256 ? NEEDS_DIM : nullptr; }
+const char* const NEEDS_WIDE_DIM =
+    "needs dim % 4 == 0 and 256 < dim <= 1024 (dim <= 256: tfra_table_find_combine, its ragged form and their *_backprop_weights forms)";
+const char* wide_dims(int dim) { return dim % 4 != 0 || dim <= 256 || dim > 1024 ? NEEDS_WIDE_DIM : nullptr; }
+template <class Owner> constexpr auto dims_of(int) -> decltype(Owner::DIMS) { return Owner::DIMS; }
+template <class Owner> constexpr DimRule dims_of(long) { return narrow_dims; }
 template <class AtEntry>
 Check check_find_combine(const Table* t, const tfra_workspace* ws, size_t nnz, const void* ids, const void* seg, const float* weights,
-                         int combiner, size_t n_rows, const void* default_row, const float* out, AtEntry&& at_entry) {
+                         int combiner, size_t n_rows, const void* default_row, const float* out, AtEntry&& at_entry,
+                         DimRule dims = narrow_dims) {
   if (!t) return refuse(TFRA_ERR_INVALID, "null table");
   if (!ws || combiner < 0 || combiner > 2) return refuse(TFRA_ERR_INVALID, "bad argument");
   if (Check e = at_entry(); e.done()) return e;
   if (ws->device != t->device) return refuse(TFRA_ERR_INVALID, "workspace and table live on different devices");
   const int dt = t->opts.value_dtype, dim = t->opts.dim;
   if (dt != TFRA_F32 && dt != TFRA_F16 && dt != TFRA_BF16) return refuse(TFRA_ERR_UNSUPPORTED, "value_dtype must be float32, float16 or bfloat16");
-  if (dim % 4 != 0 || dim > 256) return refuse(TFRA_ERR_UNSUPPORTED, NEEDS_DIM);
+  if (const char* m = dims(dim)) return refuse(TFRA_ERR_UNSUPPORTED, m);
   if (nnz >= (1ULL << 31) || n_rows >= (1ULL << 30)) return refuse(TFRA_ERR_UNSUPPORTED, "too large (nnz < 2^31, n_rows < 2^30)");
   if ((((uintptr_t)out | (uintptr_t)default_row) & 15) || ((uintptr_t)ids & 7) || ((uintptr_t)seg & 7) || ((uintptr_t)weights & 3))
     return refuse(TFRA_ERR_UNSUPPORTED, "misaligned buffer (out and default_row: 16 bytes)");
@@ -109,7 +120,7 @@ Check check_find_combine(const Table* t, const tfra_workspace* ws, size_t nnz, c
 template <class AtEntry>
 Check check_find_combine_ragged(const Table* t, const tfra_workspace* ws, size_t n_rows, const void* row_splits, size_t nnz, const void* ids,
                                 const float* weights, int combiner, uint32_t flags, uint32_t reserved, const void* default_row,
-                                const float* out, AtEntry&& at_entry) {
+                                const float* out, AtEntry&& at_entry, DimRule dims = narrow_dims) {
   if (!t) return refuse(TFRA_ERR_INVALID, "null table");
   if (combiner < 0 || combiner > 2) return refuse(TFRA_ERR_INVALID, "bad argument");
   if (flags & ~(TFRA_RAGGED_PRUNE | TFRA_RAGGED_FILL)) return refuse(TFRA_ERR_INVALID, "unknown flag bits (TFRA_RAGGED_PRUNE | TFRA_RAGGED_FILL)");
@@ -118,7 +129,7 @@ Check check_find_combine_ragged(const Table* t, const tfra_workspace* ws, size_t
   if (ws && ws->device != t->device) return refuse(TFRA_ERR_INVALID, "workspace and table live on different devices");
   const int dt = t->opts.value_dtype, dim = t->opts.dim;
   if (dt != TFRA_F32 && dt != TFRA_F16 && dt != TFRA_BF16) return refuse(TFRA_ERR_UNSUPPORTED, "value_dtype must be float32, float16 or bfloat16");
-  if (dim % 4 != 0 || dim > 256) return refuse(TFRA_ERR_UNSUPPORTED, NEEDS_DIM);
+  if (const char* m = dims(dim)) return refuse(TFRA_ERR_UNSUPPORTED, m);
   if (nnz >= (1ULL << 31) || n_rows >= (1ULL << 30)) return refuse(TFRA_ERR_UNSUPPORTED, "too large (nnz < 2^31, n_rows < 2^30)");
   if ((((uintptr_t)out | (uintptr_t)default_row) & 15) || ((uintptr_t)ids & 7) || ((uintptr_t)weights & 3))
     return refuse(TFRA_ERR_UNSUPPORTED, "misaligned buffer (out and default_row: 16 bytes)");
@@ -174,6 +185,7 @@ void with_ragged_class(int st, int nch, bool safe, F&& launch) {
 //   table()        the table the checks run on;
 //   enter(s)       lock and enter on s;
 //   FORWARD_HINT, GRADIENT_HINT   what NEEDS_DIM advises instead;
+//   DIMS           (optional) the row widths its calls serve, where not narrow_dims: WideOwner, whose refusal carries its own advice;
 //   OUT_IS_GRAD    behind the entry point's name, the prefix of the forward's checks where grad_out stands in the place of out.
 struct TableOwner {
   static constexpr const char* FORWARD_HINT = " (use tfra_unique + tfra_table_find + tfra_sparse_segment_combine otherwise)";
@@ -188,6 +200,12 @@ struct TableOwner {
     lock = std::unique_lock<std::mutex>(t->mu);
     return t->enter(s);
   }
+};
+
+// the owner of the wide-row calls (tfra_pool_wide.hip): a table, entered as TableOwner enters it, with 256 < dim <= 1024
+struct WideOwner : TableOwner {
+  static constexpr DimRule DIMS = wide_dims;
+  using TableOwner::TableOwner;
 };
 
 // the bounds of a tuple call's rows, [2 * n_rows] ints at the head of the workspace (comb_bounds: a memset and one launch)
@@ -206,7 +224,7 @@ int find_combine_call(const char* who, Owner owner, tfra_workspace* ws, size_t n
                       size_t elem, hipStream_t s, Launch&& launch) {
   if (const Check e = owner.present(); e.code) return report(std::string(who) + ": ", e);
   Check c = check_find_combine(owner.table(), ws, nnz, ids, seg, weights, combiner, n_rows, default_row, out_checked,
-                               [&] { return Check{owner.enter(s)}; });
+                               [&] { return Check{owner.enter(s)}; }, dims_of<Owner>(0));
   if (c.msg == NEEDS_DIM) c.msg += Owner::FORWARD_HINT;
   if (c.code) return report(std::string(who) + ": ", c);
   if (!c.active) return TFRA_OK;
@@ -228,7 +246,7 @@ int find_combine_ragged_call(const char* who, Owner owner, size_t n_rows, const 
                              void* out, size_t elem, hipStream_t s, Launch&& launch) {
   if (const Check e = owner.present(); e.code) return report(std::string(who) + ": ", e);
   Check c = check_find_combine_ragged(owner.table(), nullptr, n_rows, row_splits, nnz, ids, weights, combiner, flags, 0, default_row,
-                                      out_checked, [&] { return Check{owner.enter(s)}; });
+                                      out_checked, [&] { return Check{owner.enter(s)}; }, dims_of<Owner>(0));
   if (c.msg == NEEDS_DIM) c.msg += Owner::FORWARD_HINT;
   if (c.code) return report(std::string(who) + ": ", c);
   if (!c.active) return TFRA_OK;
@@ -251,7 +269,7 @@ int find_combine_wgrad_call(const char* who, Owner owner, tfra_workspace* ws, si
                             float* dw_out, hipStream_t s, Launch&& launch) {
   if (const Check e = owner.present(); e.code) return report(std::string(who) + ": ", e);
   Check c = check_find_combine(owner.table(), ws, nnz, ids, seg, weights, combiner, n_rows, default_row, grad_checked,
-                               [&] { return Check{owner.enter(s)}; });
+                               [&] { return Check{owner.enter(s)}; }, dims_of<Owner>(0));
   if (c.msg == NEEDS_DIM) c.msg += Owner::GRADIENT_HINT;
   if (c.code) return report(std::string(who) + Owner::OUT_IS_GRAD, c);
   if (const Check d = check_dw_out(nnz, dw_out); d.code) return report(std::string(who) + ": ", d);
@@ -271,7 +289,7 @@ int find_combine_ragged_wgrad_call(const char* who, Owner owner, size_t n_rows, 
                                    const float* grad_checked, float* dw_out, hipStream_t s, Launch&& launch) {
   if (const Check e = owner.present(); e.code) return report(std::string(who) + ": ", e);
   Check c = check_find_combine_ragged(owner.table(), nullptr, n_rows, row_splits, nnz, ids, weights, combiner, flags, 0, default_row,
-                                      grad_checked, [&] { return Check{owner.enter(s)}; });
+                                      grad_checked, [&] { return Check{owner.enter(s)}; }, dims_of<Owner>(0));
   if (c.msg == NEEDS_DIM) c.msg += Owner::GRADIENT_HINT;
   if (c.code) return report(std::string(who) + Owner::OUT_IS_GRAD, c);
   if (const Check d = check_dw_out(nnz, dw_out); d.code) return report(std::string(who) + ": ", d);

@@ -463,6 +463,14 @@ _SIGS_LONG_MANY = {
     "tfra_multi_find_combine_backprop_weights_long": [_P, _SZ, _P, _P, _P, _P],
     "tfra_multi_find_combine_ragged_backprop_weights_long": [_P, _SZ, _P, _P, _P, _P],
 }
+# The wide-row forms of the single pooled calls (256 < dim <= 1024, one wave per output row): their twins' argument lists.  A table
+# of its own for the same reason.
+_SIGS_WIDE = {
+    "tfra_table_find_combine_wide": _SIGS["tfra_table_find_combine"],
+    "tfra_table_find_combine_ragged_wide": _SIGS["tfra_table_find_combine_ragged"],
+    "tfra_table_find_combine_backprop_weights_wide": _SIGS["tfra_table_find_combine_backprop_weights"],
+    "tfra_table_find_combine_ragged_backprop_weights_wide": _SIGS["tfra_table_find_combine_ragged_backprop_weights"],
+}
 
 _lib = None
 
@@ -476,7 +484,7 @@ def lib():
           "%s not found: run `python recommenders-addons_amd/build.py` (hipcc, gfx950). "
           "There is no CPU fallback." % LIB_PATH)
     l = ctypes.CDLL(LIB_PATH)
-    for name, args in list(_SIGS.items()) + list(_SIGS_MIXED.items()) + list(_SIGS_LONG_MANY.items()):
+    for name, args in list(_SIGS.items()) + list(_SIGS_MIXED.items()) + list(_SIGS_LONG_MANY.items()) + list(_SIGS_WIDE.items()):
       f = getattr(l, name)
       f.argtypes = args
       f.restype = ctypes.c_int

@@ -23,8 +23,9 @@ import torch
 
 from . import device_ops, table_ops
 from ._args import _out_dtype
-from .variable import (SparseTrainableWrapper, _admit_entries_many, _check_combiner, _check_entries_many, _note_pruned, _per_table,
-                       _pooled_forward, _pooled_reader, _pooled_training, _safe_sparse_args, _safe_sparse_args_many, _wrap_grouped)
+from .variable import (SparseTrainableWrapper, _admit_entries_many, _check_combiner, _check_entries_many, _not_wide_and, _note_pruned,
+                       _per_table, _pooled_forward, _pooled_reader, _pooled_training, _safe_sparse_args, _safe_sparse_args_many,
+                       _wide_forward, _wrap_grouped)
 from . import variable as _tuple_form
 
 
@@ -102,8 +103,15 @@ def _long(long_rows, out_dtype, mixed_rows=False):
   return {"long_rows": True} if long_rows else {"mixed_rows": True} if mixed_rows else {}
 
 
+def _wide(wide_rows, long_rows, mixed_rows):
+  """The keyword of a wide-row lookup behind this module's calls to the tuple form: nothing without it.  With long_rows or
+  mixed_rows: ValueError."""
+  _not_wide_and(wide_rows, long_rows, mixed_rows)
+  return {"wide_rows": True} if wide_rows else {}
+
+
 def embedding_lookup_sparse(params, sp_ids, sp_weights, name=None, combiner="mean", return_trainable=False, plan_writeback=False,
-                            entry_seg=None, out_shape=None, out_dtype=None, long_rows=False, mixed_rows=False):
+                            entry_seg=None, out_shape=None, out_dtype=None, long_rows=False, wide_rows=False, mixed_rows=False):
   """PY/ragged_embedding_ops.py:223-324.  `sp_ids` = (row_splits[n_rows + 1], values[nnz]), `sp_weights` = weight values or None.
   [n_rows, dim] float32: row r = sum / mean / sqrtn over its entries of weight * embedding, zeros for an empty row — bit-identical
   to `de.embedding_lookup_sparse(params, (row ids, values), sp_weights, num_rows=n_rows)`, in one launch.
@@ -120,15 +128,22 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights, name=None, combiner="mea
   (several shards, tiers, bp_v2, other dims or dtypes, out_dtype) the keyword changes nothing.
   mixed_rows: rows of mixed lengths (a heavy-tailed sequence feature) — tfra_table_find_combine_ragged_mixed, 16 rows per block and
   a long row by the whole block, and the wrapper's `weights_grad` its mixed-row call: the same bits, and nothing changes where
-  long_rows changes nothing.  long_rows=True together with mixed_rows=True: ValueError."""
+  long_rows changes nothing.  long_rows=True together with mixed_rows=True: ValueError.
+  wide_rows: a variable of 256 < dim <= 1024 — a lookup that is not a training step's takes tfra_table_find_combine_ragged_wide (one
+  wave per output row, one launch, nothing read on the host) under the tuple form's conditions (`de.embedding_lookup_sparse`), the
+  same bits; a training lookup keeps the tuple form's chain, whose wrapper remembers the keyword for `weights_grad`.  Everywhere
+  else it changes nothing.  With long_rows or mixed_rows: ValueError."""
   _check_combiner(combiner)
-  typed = dict(_typed(out_dtype), **_long(long_rows, out_dtype, mixed_rows))
+  typed = dict(_typed(out_dtype), **_long(long_rows, out_dtype, mixed_rows), **_wide(wide_rows, long_rows, mixed_rows))
   rs, ids, w = _ragged_input(params, sp_ids, sp_weights)
   n = rs.numel() - 1
   if not (_pooled_training if return_trainable else _pooled_forward)(params, None):
+    if not return_trainable and _wide_forward(params, None, out_dtype, wide_rows):
+      return params.lookup_combined_ragged_wide(rs, ids, w, combiner)
     seg = row_ids_of(rs, ids.numel()) if entry_seg is None else entry_seg
     return _tuple_form.embedding_lookup_sparse(params, (seg, ids), w, combiner=combiner, return_trainable=return_trainable,
                                                num_rows=n, plan_writeback=plan_writeback, _out_shape=out_shape, **typed)
+  typed.pop("wide_rows", None)   # (the pooled read below serves dim <= 256: the keyword changes nothing)
   if return_trainable:
     params.admit_entries(ids)   # (tiered shards: the entry ids into the cache ahead of the read; init_on_lookup="pooled": admitted with drawn rows)
   out = params.lookup_combined_ragged(rs, ids, w, combiner, **typed)
@@ -139,7 +154,8 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights, name=None, combiner="mea
 
 
 def safe_embedding_lookup_sparse(params, sparse_ids, sparse_weights=None, combiner="mean", default_id=None, name=None,
-                                 return_trainable=False, plan_writeback=False, out_dtype=None, long_rows=False, mixed_rows=False):
+                                 return_trainable=False, plan_writeback=False, out_dtype=None, long_rows=False, wide_rows=False,
+                                 mixed_rows=False):
   """PY/ragged_embedding_ops.py:327-442, with this project's semantics of the tuple form (`de.safe_embedding_lookup_sparse`):
   ids are never pruned; entries whose weight is not > 0 are dropped unless combiner == "sum"; a row left without entries yields
   zeros, or the embedding of `default_id`.  Bit-identical to the tuple form on (row ids, values), in one launch and with no
@@ -147,15 +163,20 @@ def safe_embedding_lookup_sparse(params, sparse_ids, sparse_weights=None, combin
 
   return_trainable: also returns the SparseTrainableWrapper; its entry list is what the tuple form's preprocessing
   (`_safe_sparse_args`) makes on the derived row ids, built on the device from row_splits with one host read of its length.
-  out_dtype: as `embedding_lookup_sparse`'s; the row of default_id is converted as it is.  long_rows, mixed_rows: as there."""
+  out_dtype: as `embedding_lookup_sparse`'s; the row of default_id is converted as it is.  long_rows, mixed_rows: as there.
+  wide_rows: as there, the pruning and the default row being the wide kernel's (flags PRUNE / FILL)."""
   _check_combiner(combiner)
-  typed = dict(_typed(out_dtype), **_long(long_rows, out_dtype, mixed_rows))
+  typed = dict(_typed(out_dtype), **_long(long_rows, out_dtype, mixed_rows), **_wide(wide_rows, long_rows, mixed_rows))
   rs, ids, w = _ragged_input(params, sparse_ids, sparse_weights)
   n = rs.numel() - 1
   if not (_pooled_training if return_trainable else _pooled_forward)(params, None):
+    if not return_trainable and _wide_forward(params, None, out_dtype, wide_rows):
+      prune, fill = _safe_flags(w, combiner, default_id)
+      return params.lookup_combined_ragged_wide(rs, ids, w, combiner, prune=prune, fill_id=fill)
     return _tuple_form.safe_embedding_lookup_sparse(params, (row_ids_of(rs, ids.numel()), ids), w, combiner=combiner,
                                                     default_id=default_id, return_trainable=return_trainable, num_rows=n,
                                                     plan_writeback=plan_writeback, **typed)
+  typed.pop("wide_rows", None)   # (the pooled read below serves dim <= 256: the keyword changes nothing)
   prune, fill = _safe_flags(w, combiner, default_id)
   if not return_trainable:
     return params.lookup_combined_ragged(rs, ids, w, combiner, prune=prune, fill_id=fill, **typed)

@@ -340,6 +340,42 @@ class _DeviceTable:
                _ptr(w), int(combiner), flags, fill, _ptr(d), _ptr(g), _ptr(dw), _stream(self._device))
     return dw
 
+  # ---- the wide-row forms: 256 < dim <= 1024, one wave per output row (tfra_pool_wide.hip), the op chain's bits -----------------
+  def find_combine_wide(self, ids, seg, weights, combiner, n_rows, default_row=None):
+    """`find_combine` for a table of 256 < dim <= 1024 (tfra_table_find_combine_wide): the same arguments and result — bit for bit
+    unique -> find -> device_ops.sparse_segment_combine, which is all such a table had.  float32 out."""
+    ids, seg, w, d, out = self._find_combine_args(ids, seg, weights, n_rows, default_row)
+    _capi.call("tfra_table_find_combine_wide", self._h, _workspace(self._device), ids.numel(), _ptr(ids), _ptr(seg), _ptr(w),
+               int(combiner), int(n_rows), _ptr(d), _ptr(out), _stream(self._device))
+    return out
+
+  def find_combine_ragged_wide(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, default_row=None):
+    """`find_combine_ragged` for 256 < dim <= 1024 (tfra_table_find_combine_ragged_wide), in one launch.  float32 out."""
+    rs, ids, w, flags, fill, d, out = self._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row)
+    _capi.call("tfra_table_find_combine_ragged_wide", self._h, rs.numel() - 1, _ptr(rs), ids.numel(), _ptr(ids), _ptr(w),
+               int(combiner), flags, fill, _ptr(d), _ptr(out), _stream(self._device))
+    return out
+
+  def find_combine_weight_grad_wide(self, ids, seg, weights, combiner, grad_out, default_row=None):
+    """`find_combine_weight_grad` for 256 < dim <= 1024 (tfra_table_find_combine_backprop_weights_wide): bit for bit find +
+    device_ops.sparse_segment_combine_weight_grad.  float32 grad_out."""
+    g = self._weight_grad_out(grad_out, None)
+    ids, seg, w, d, _ = self._find_combine_args(ids, seg, weights, 0, default_row)
+    dw = torch.empty(ids.numel(), dtype=torch.float32, device=self._device)
+    _capi.call("tfra_table_find_combine_backprop_weights_wide", self._h, _workspace(self._device), ids.numel(), _ptr(ids), _ptr(seg),
+               _ptr(w), int(combiner), g.shape[0], _ptr(d), _ptr(g), _ptr(dw), _stream(self._device))
+    return dw
+
+  def find_combine_ragged_weight_grad_wide(self, row_splits, ids, weights, combiner, grad_out, prune=False, fill_id=None,
+                                           default_row=None):
+    """`find_combine_ragged_weight_grad` for 256 < dim <= 1024 (tfra_table_find_combine_ragged_backprop_weights_wide)."""
+    rs, ids, w, flags, fill, d, _ = self._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row)
+    g = self._weight_grad_out(grad_out, rs.numel() - 1)
+    dw = torch.empty(ids.numel(), dtype=torch.float32, device=self._device)
+    _capi.call("tfra_table_find_combine_ragged_backprop_weights_wide", self._h, rs.numel() - 1, _ptr(rs), ids.numel(), _ptr(ids),
+               _ptr(w), int(combiner), flags, fill, _ptr(d), _ptr(g), _ptr(dw), _stream(self._device))
+    return dw
+
   # ---- the mixed-row forms: 16 rows per block, a row of long_from entries or more by the whole block (tfra_pool_mixed.hip) ------
   def find_combine_mixed(self, ids, seg, weights, combiner, n_rows, default_row=None, long_from=0):
     """`find_combine` for a batch whose rows mix a handful of entries with hundreds (tfra_table_find_combine_mixed): the same
@@ -1341,6 +1377,25 @@ class _LongRows:
                                                             fill_id=fill_id, default_row=default_row)
 
 
+class _WideRows:
+  """The wide-row pooled reads of a plain table's device table (`_DeviceTable.find_combine_wide` and its three siblings)."""
+
+  def find_combine_wide(self, ids, seg, weights, combiner, n_rows, default_row=None):
+    return self._table.find_combine_wide(ids, seg, weights, combiner, n_rows, default_row)
+
+  def find_combine_ragged_wide(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, default_row=None):
+    return self._table.find_combine_ragged_wide(row_splits, ids, weights, combiner, prune=prune, fill_id=fill_id,
+                                                default_row=default_row)
+
+  def find_combine_weight_grad_wide(self, ids, seg, weights, combiner, grad_out, default_row=None):
+    return self._table.find_combine_weight_grad_wide(ids, seg, weights, combiner, grad_out, default_row)
+
+  def find_combine_ragged_weight_grad_wide(self, row_splits, ids, weights, combiner, grad_out, prune=False, fill_id=None,
+                                           default_row=None):
+    return self._table.find_combine_ragged_weight_grad_wide(row_splits, ids, weights, combiner, grad_out, prune=prune,
+                                                            fill_id=fill_id, default_row=default_row)
+
+
 class _MixedRows:
   """The mixed-row pooled reads of a plain table's device table (`_DeviceTable.find_combine_mixed` and its three siblings)."""
 
@@ -1360,7 +1415,7 @@ class _MixedRows:
                                                              fill_id=fill_id, default_row=default_row, long_from=long_from)
 
 
-class CuckooHashTable(_LookupInterfaceMirror, _WholeRows, _LongRows, _MixedRows):
+class CuckooHashTable(_LookupInterfaceMirror, _WholeRows, _LongRows, _MixedRows, _WideRows):
   """PY/cuckoo_hashtable_ops.py:45-145.  Growing, never-evicting table (libcuckoo semantics)."""
 
   def __init__(self, key_dtype, value_dtype, default_value, name="CuckooHashTable", checkpoint=True, init_size=0,
@@ -1388,7 +1443,7 @@ class CuckooHashTable(_LookupInterfaceMirror, _WholeRows, _LongRows, _MixedRows)
     self._table.accum_or_assign(keys, values_or_deltas, exists)
 
 
-class HkvHashTable(_LookupInterfaceMirror, _WholeRows, _LongRows, _MixedRows):
+class HkvHashTable(_LookupInterfaceMirror, _WholeRows, _LongRows, _MixedRows, _WideRows):
   """PY/hkv_hashtable_ops.py:47-175.  Bounded table with per-key scores and in-bucket eviction."""
 
   def __init__(self, key_dtype, value_dtype, default_value, name="HkvHashTable", checkpoint=True,

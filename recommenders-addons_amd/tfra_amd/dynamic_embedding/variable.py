@@ -122,6 +122,18 @@ def _not_both(long_rows, mixed_rows):
     raise ValueError("long_rows=True and mixed_rows=True exclude each other: mixed_rows serves long rows as well")
 
 
+def _not_wide_and(wide_rows, long_rows, mixed_rows):
+  """wide_rows names a launch shape of its own (one wave per row of 256 < dim <= 1024): the long and mixed shapes stop at dim 256."""
+  if wide_rows and (long_rows or mixed_rows):
+    raise ValueError("wide_rows=True excludes long_rows and mixed_rows: their calls serve dim <= 256")
+
+
+def _wide_forward(params, max_norm, out_dtype, wide_rows):
+  """Whether a sparse lookup that is NOT a training step's reads through the wide-row calls (`Variable.lookup_combined_wide`): the
+  keyword, nothing clipped, a float32 result, no bp_v2 and a variable they serve."""
+  return bool(wide_rows) and max_norm is None and _out_dtype(out_dtype) is None and not params.bp_v2 and params.can_lookup_combined_wide()
+
+
 def misses_are_static(var):
   """Whether a key the optimizer write-back does not find may start from the ONE static default row of `var` (a Variable, or
   anything with its `initializer`): there is no callable initializer, or the step's lookup has admitted every key with its own
@@ -593,6 +605,46 @@ class Variable:
     return t._table.find_combine_ragged_weight_grad_mixed(row_splits, ids, weights, device_ops.COMBINERS[combiner], grad_out,
                                                           prune=prune, fill_id=fill_id, default_row=t._default_value)
 
+  # ---- wide rows: 256 < dim <= 1024, one wave per output row (tfra_pool_wide.hip) ---------------------------------------------
+  def can_lookup_combined_wide(self):
+    """Whether the wide-row pooled reads serve this variable: `can_lookup_combined()`'s conditions with 256 < dim <= 1024 in the
+    place of dim <= 256, and no tiered shard.  (The planned write-backs stop at dim 256: a training lookup keeps the op chain.)"""
+    from .optimizer import PLANNED_VALUE_DTYPES
+    return (self.shard_num == 1 and not callable(self.initializer) and self.value_dtype in PLANNED_VALUE_DTYPES and
+            self.dim % 4 == 0 and 256 < self.dim <= 1024 and not _has_tiered_shards(self))
+
+  def _wide_operands(self, ids, who):
+    """`_combined_operands` of the wide-row reads; ValueError unless `can_lookup_combined_wide()`."""
+    if not self.can_lookup_combined_wide():
+      raise ValueError("%s needs one plain shard, a static default row, float32 / float16 / bfloat16 rows, dim %% 4 == 0 and "
+                       "256 < dim <= 1024" % who)
+    return self._tables[0], torch.as_tensor(ids, device=self._primary).reshape(-1)
+
+  def lookup_combined_wide(self, ids, seg, weights, combiner, n_rows, name=None):
+    """`lookup_combined` for a variable of 256 < dim <= 1024 (tfra_table_find_combine_wide): [n_rows, dim] float32, bit-identical to
+    unique -> lookup -> device_ops.sparse_segment_combine, without the unique pass, its host read and the [U, dim] rows.  Under
+    `can_lookup_combined_wide()`'s conditions.  Never inserts."""
+    t, ids = self._wide_operands(ids, "lookup_combined_wide")
+    return t._table.find_combine_wide(ids, seg, weights, device_ops.COMBINERS[combiner], n_rows, t._default_value)
+
+  def lookup_combined_ragged_wide(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, name=None):
+    """`lookup_combined_ragged` for 256 < dim <= 1024 (tfra_table_find_combine_ragged_wide), in one launch; prune / fill_id as there."""
+    t, ids = self._wide_operands(ids, "lookup_combined_ragged_wide")
+    return t._table.find_combine_ragged_wide(row_splits, ids, weights, device_ops.COMBINERS[combiner], prune=prune, fill_id=fill_id,
+                                             default_row=t._default_value)
+
+  def lookup_combined_weight_grad_wide(self, ids, seg, weights, combiner, grad_out, name=None):
+    """`lookup_combined_weight_grad` for 256 < dim <= 1024 (tfra_table_find_combine_backprop_weights_wide): bit-identical to a lookup
+    of the rows and `device_ops.sparse_segment_combine_weight_grad`, with no [nnz, dim] or [U, dim] rows.  float32 grad_out."""
+    t, ids = self._wide_operands(ids, "lookup_combined_weight_grad_wide")
+    return t._table.find_combine_weight_grad_wide(ids, seg, weights, device_ops.COMBINERS[combiner], grad_out, t._default_value)
+
+  def lookup_combined_ragged_weight_grad_wide(self, row_splits, ids, weights, combiner, grad_out, prune=False, fill_id=None, name=None):
+    """`lookup_combined_ragged_weight_grad` for 256 < dim <= 1024 (tfra_table_find_combine_ragged_backprop_weights_wide)."""
+    t, ids = self._wide_operands(ids, "lookup_combined_ragged_weight_grad_wide")
+    return t._table.find_combine_ragged_weight_grad_wide(row_splits, ids, weights, device_ops.COMBINERS[combiner], grad_out,
+                                                         prune=prune, fill_id=fill_id, default_row=t._default_value)
+
   def lookup_combined_weight_grad_typed(self, ids, seg, weights, combiner, grad_out, grad_scale=None, name=None):
     """`lookup_combined_weight_grad` that takes grad_out as a half model's dense part hands it back: a contiguous float16 /
     bfloat16 grad_out and grad_scale (a one-element float32 device tensor the gradient is multiplied by) go down as they are
@@ -1026,11 +1078,14 @@ class SparseTrainableWrapper(TrainableWrapper):
 
   def __init__(self, params, ids, idx, n_unique, seg, weights, combiner, n_rows, out_shape, entry_ids, entry_seg,
                entry_weights, max_norm=None, plan_writeback=False, lookup_ids=None, entry_plan=None, long_rows=False,
-               mixed_rows=False):
+               mixed_rows=False, wide_rows=False, wide_ids=None):
     """entry_plan: a plan over `entry_ids` whose build is already enqueued (the grouped lookup starts its members' plans in one
     call); the wrapper owns it from here on, as one made with plan_writeback.  long_rows / mixed_rows: the lookup's keyword, which
-    `weights_grad` passes on to its pooled read."""
+    `weights_grad` passes on to its pooled read.  wide_rows / wide_ids: the keyword of a lookup over 256 < dim <= 1024 and its flat
+    ids as given; the wrapper is the op chain's (`_pooled_ids` stays None) and only `weights_grad` reads them."""
     _not_both(long_rows, mixed_rows)
+    _not_wide_and(wide_rows, long_rows, mixed_rows)
+    self._wide_rows, self._wide_ids = bool(wide_rows), wide_ids
     self._long_rows = bool(long_rows)
     self._mixed_rows = bool(mixed_rows)
     if lookup_ids is None:
@@ -1120,6 +1175,10 @@ class SparseTrainableWrapper(TrainableWrapper):
       else:
         dw = self.params.lookup_combined_weight_grad_typed(self._pooled_ids, self._seg, self._weights, self.combiner, g,
                                                            grad_scale=grad_scale)
+    elif (self._wide_rows and self._wide_ids is not None and g.dtype == torch.float32 and grad_scale is None and
+          self.params.can_lookup_combined_wide()):
+      # a wide-row lookup's wrapper: the rows straight from the table, the bits of the route below
+      dw = self.params.lookup_combined_weight_grad_wide(self._wide_ids, self._seg, self._weights, self.combiner, g)
     else:
       rows = self.params.lookup(self.ids).to(torch.float32)
       dw = device_ops.sparse_segment_combine_weight_grad(rows, self._idx, g, self._seg, self._weights, self.combiner,
@@ -1250,7 +1309,7 @@ def _pooled_training(params, max_norm):
 
 def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=None, name="embedding_lookup_sparse",
                             combiner="mean", max_norm=None, return_trainable=False, num_rows=None, plan_writeback=False,
-                            _entries=None, _out_shape=None, out_dtype=None, long_rows=False, mixed_rows=False):
+                            _entries=None, _out_shape=None, out_dtype=None, long_rows=False, wide_rows=False, mixed_rows=False):
   """PY/dynamic_embedding_ops.py:120-293.  `sp_ids` = (indices[nnz,2] or row_ids[nnz], values[nnz]);
   `sp_weights` = matching weight values or None.  Segment combine sum / mean / sqrtn over rows.
 
@@ -1269,9 +1328,19 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=
   mixed_rows: the rows' lengths are mixed (a heavy-tailed history: most rows a handful of ids, a few of them hundreds).  The pooled
   read and `weights_grad` take the mixed-row calls (tfra_table_find_combine_mixed / ..._backprop_weights_mixed: 16 rows per block, a
   row of TFRA_MIXED_LONG_FROM_DEFAULT entries or more by the whole block), the same bits; it changes nothing wherever long_rows
-  changes nothing.  long_rows=True together with mixed_rows=True: ValueError.  What it costs and gains: README."""
+  changes nothing.  long_rows=True together with mixed_rows=True: ValueError.  What it costs and gains: README.
+
+  wide_rows: the variable's rows are 256 < dim <= 1024 wide (pretrained text or image embeddings, a wide tower), which the pooled
+  read above does not serve.  A lookup that is not a training step's (return_trainable=False) then takes
+  tfra_table_find_combine_wide — one wave per output row, the op chain's bits, no unique pass and no host read — when max_norm and
+  out_dtype are None, the variable is not bp_v2 and `Variable.can_lookup_combined_wide()` holds; every other call reaches exactly
+  the calls it reaches without the keyword.  A training lookup keeps the chain and its wrapper (the planned write-backs stop at dim
+  256); the wrapper remembers the keyword, and its `weights_grad` reads the rows straight from the table
+  (tfra_table_find_combine_backprop_weights_wide) for a float32 grad_out without grad_scale: the same bits.  Together with
+  long_rows or mixed_rows: ValueError.  What it costs and gains: README."""
   _check_combiner(combiner)
   _not_both(long_rows, mixed_rows)
+  _not_wide_and(wide_rows, long_rows, mixed_rows)
   _out_dtype(out_dtype)
   indices, ids = sp_ids
   indices = torch.as_tensor(indices, device=params._primary)
@@ -1279,6 +1348,9 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=
   ids = torch.as_tensor(ids, device=params._primary)
   w = sp_weights if sp_weights is None else torch.as_tensor(sp_weights, dtype=torch.float32, device=params._primary)
   pooled = _pooled_training(params, max_norm) if return_trainable else _pooled_forward(params, max_norm)
+  if not pooled and not return_trainable and _wide_forward(params, max_norm, out_dtype, wide_rows):
+    n = int(seg.max().item()) + 1 if num_rows is None else num_rows
+    return params.lookup_combined_wide(ids, seg, w, combiner, n)
   if not pooled:
     uniq, idx, cnt = device_ops.unique(ids)
   n = int(seg.max().item()) + 1 if num_rows is None else num_rows
@@ -1305,7 +1377,8 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=
                                        plan_writeback=plan_writeback, lookup_ids=ids, long_rows=long_rows, mixed_rows=mixed_rows)
   if return_trainable:
     tw = SparseTrainableWrapper(params, uniq.reshape(-1), idx, cnt, seg, w, combiner, n, shape, e_ids, e_seg, e_w,
-                                max_norm=max_norm, plan_writeback=plan_writeback)
+                                max_norm=max_norm, plan_writeback=plan_writeback,
+                                **({"wide_rows": True, "wide_ids": ids.reshape(-1)} if wide_rows else {}))
     ue = tw.read_value()
   else:
     tw = None
@@ -1643,7 +1716,7 @@ def _safe_sparse_finish(params, res, rows, n, default_id, max_norm, lead):
 def safe_embedding_lookup_sparse(params, sp_ids, sparse_weights=None, combiner="mean", default_id=None,
                                  name="safe_embedding_lookup_sparse", partition_strategy=None, max_norm=None,
                                  return_trainable=False, num_rows=None, plan_writeback=False, out_dtype=None, long_rows=False,
-                                 mixed_rows=False):
+                                 wide_rows=False, mixed_rows=False):
   """PY/dynamic_embedding_ops.py:296-430.  `sp_ids` = (indices[nnz, R], values[nnz][, dense_shape[R]]) — a
   SparseTensor of rank R >= 2 (or row ids [nnz] for rank 2).  Semantics of the reference, NOT of
   `tf.nn.safe_embedding_lookup_sparse`: ids are never pruned (any int64 is a legal key, negative ones too,
@@ -1651,16 +1724,18 @@ def safe_embedding_lookup_sparse(params, sp_ids, sparse_weights=None, combiner="
   (`_prune_invalid_weights`, :374-376); rows left without entries yield zeros, or the embedding of
   `default_id` (`sparse_fill_empty_rows`, :379-408); leading dims are flattened for the lookup and restored
   on the result (:356-367, 411-424).  out_dtype: `embedding_lookup_sparse`'s; the default_id row is converted the same way.
-  long_rows, mixed_rows: `embedding_lookup_sparse`'s, for the lookup over the kept entries."""
+  long_rows, mixed_rows, wide_rows: `embedding_lookup_sparse`'s, for the lookup over the kept entries."""
   _check_combiner(combiner)
   _not_both(long_rows, mixed_rows)
+  _not_wide_and(wide_rows, long_rows, mixed_rows)
   _out_dtype(out_dtype)
   rows, ids, w, n, entries, out_shape, lead = _safe_sparse_args(params, sp_ids, sparse_weights, combiner, default_id,
                                                                  return_trainable, num_rows)
   out = embedding_lookup_sparse(params, (rows, ids), w, combiner=combiner, max_norm=max_norm,
                                 return_trainable=return_trainable, num_rows=n, plan_writeback=plan_writeback,
                                 _entries=entries, _out_shape=out_shape, out_dtype=out_dtype,
-                                **({"long_rows": True} if long_rows else {"mixed_rows": True} if mixed_rows else {}))
+                                **({"long_rows": True} if long_rows else {"mixed_rows": True} if mixed_rows else
+                                   {"wide_rows": True} if wide_rows else {}))
   res, tw = out if return_trainable else (out, None)
   res = _safe_sparse_finish(params, res, rows, n, default_id, max_norm, lead)
   return (res, _note_pruned(tw, sparse_weights, combiner)) if return_trainable else res
