@@ -1413,6 +1413,32 @@ int tfra_table_find_combine_ragged_backprop_weights_wide(tfra_table_t* t, size_t
                                                          int64_t fill_id, const void* default_row, const float* grad_out,
                                                          float* dw_out, tfra_stream_t stream);
 
+/* The planned sparse write-back for WIDE rows: the plan build, the planned, the combined and the one-call
+ * write-back of a float32, float16 or bfloat16 table with dim % 4 == 0 and 256 < dim <= 1024, float32 gradients.  Each takes its
+ * twin's argument list (tfra_sparse_plan_build, tfra_table_apply_planned, tfra_table_apply_planned_combined,
+ * tfra_table_apply_sparse), runs its twin's checks in its twin's order with the width rule exchanged, enqueues in the twin's shape
+ * (sums launch, update launch, a second update launch on a bounded table) and refuses before anything is enqueued.
+ * TFRA_ERR_UNSUPPORTED: any other width (the message holds "256 < dim <= 1024" and names the twin); a table with
+ * TFRA_OPTION_STOCHASTIC_ROUNDING (wide write-backs round to nearest even); n > 2^18 in tfra_table_apply_sparse_wide;
+ * n_rows * dim >= 2^32 in the combined call (32-bit element offsets into grad_out).
+ * The plan object, its builders and its layout are the narrow build's: the summation tree is a function of the ids alone.  A plan
+ * built wide serves the wide write-backs only; the narrow ones, tfra_plan_reduce_to and the *_planned row calls refuse it.
+ * All seven fused rules; a bounded table at max_capacity takes the second (eviction) launch as its twin does.
+ * ONE wave64 updates a key's row — a lane owns columns k * 256 + 4 * lane — four keys per wave and trip, located by its four 16-lane
+ * groups first; the sums walk a bin's items with all 64 lanes on 256 columns.  Every addition is per column and in the twin's
+ * order, so columns [a, b) of the result are BIT FOR BIT what the narrow calls write on a table of those columns.
+ * Not provided in this form: half gradients and grad_scale (tfra_grads), stochastic rounding, tfra_reduce_by_key,
+ * tfra_table_fetch_planned / tfra_table_store_rows, the grouped *_many write-back and plan build, more than 2^18 ids, the step
+ * drivers, tiers.  Additive; ABI version 1.          (tests/test_wide_writeback_abi.py, tests/test_gpu_wide_writeback.py) */
+int tfra_sparse_plan_build_wide(tfra_sparse_plan_t* plan, size_t n, const int64_t* ids, int dim, tfra_stream_t stream);
+int tfra_table_apply_planned_wide(tfra_table_t* t, const tfra_opt_params* p, const tfra_sparse_plan_t* plan,
+                                  const float* grads, const float* param_default_row, tfra_stream_t stream);
+int tfra_table_apply_planned_combined_wide(tfra_table_t* t, const tfra_opt_params* p, const tfra_sparse_plan_t* plan,
+                                           const float* grad_out, const int64_t* seg, const float* weights, int combiner,
+                                           size_t n_rows, const float* param_default_row, tfra_stream_t stream);
+int tfra_table_apply_sparse_wide(tfra_table_t* t, const tfra_opt_params* p, size_t n, const int64_t* ids,
+                                 const float* grads, const float* param_default_row, tfra_stream_t stream);
+
 /* The weight gradients of MANY pooled lookups in one call (a model with 26 weighted sparse features asks for 26 of them per step:
  * ~100 enqueues for 26 small kernels otherwise).  A descriptor names exactly ONE of table / tier, as tfra_tier_find_combine_desc
  * does; descs[i].dw_out is bit-identical to the single call on that descriptor — the same device function runs:

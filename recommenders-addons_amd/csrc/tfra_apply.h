@@ -5,12 +5,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <string>
 #include <type_traits>
 
 #include "../../include/tfra_mi355x.h"
 #include "tfra_host.h"
 #include "tfra_many.h"
 #include "tfra_plan.h"
+#include "tfra_reduce_device.h"
 
 // NCH of the sums, the row's chunks of 64 floats: f(std::integral_constant<int, NCH>{}) for nch in 1..4
 template <class F>
@@ -25,22 +27,34 @@ static void with_nch(int nch, F&& f) {
 
 // A fused write-back of a table that rounds stochastically takes one call index of the random stream, on the host: a captured
 // graph would replay that one index.  Every fused write-back refuses the pair before it enqueues anything.
-static Check check_rounding(const Table* t) {
+// wide (the *_wide write-backs, tfra_apply_wide.hip): their kernels round to nearest even only, so such a table is refused here.
+static Check check_rounding(const Table* t, bool wide = false) {
+  if (wide && t->stochastic())
+    return refuse(TFRA_ERR_UNSUPPORTED, "wide write-backs round to nearest even (TFRA_OPTION_STOCHASTIC_ROUNDING: dim <= 256 only)");
   if (t->stochastic() && t->capture_safe)
     return refuse(TFRA_ERR_UNSUPPORTED, "TFRA_OPTION_STOCHASTIC_ROUNDING and TFRA_OPTION_CAPTURE_SAFE are both set (a replayed graph would reuse one call index)");
   return Check{};
+}
+
+// The row widths of the *_wide write-backs, as the wide pooled calls word theirs (tfra_pool.h): the refusal names the twin to use.
+inline bool wide_apply_dim(int dim) { return dim % 4 == 0 && dim > 64 * tfra::red::MAXCH && dim <= 1024; }
+inline Check refuse_wide_dim(const char* twin) {
+  return refuse(TFRA_ERR_UNSUPPORTED, (std::string("needs dim % 4 == 0 and 256 < dim <= 1024 (dim <= 256: ") + twin + ")").c_str());
 }
 
 // (What a tfra_grads itself must satisfy, check_typed, stands in tfra_many.h beside Check: the typed weight gradients use it too.)
 
 // The checks of a planned write-back: apply_planned_impl's, whoever calls it, and behind check_apply_combined those of a
 // descriptor of tfra_multi_apply_planned_combined.  active: the plan holds ids.  grad_mask: 15 for a float gradient matrix, 7 for
-// the float16 / bfloat16 one of the *_typed calls.
+// the float16 / bfloat16 one of the *_typed calls.  wide_twin != nullptr: the checks of the *_wide twin (tfra_apply_wide.hip), the
+// same in the same order with the width rule exchanged; it names the narrow call.  A plan of a wide dim belongs to the wide calls
+// alone: the narrow ones refuse it as built for another dim, whatever the table's.
 template <class AtEntry>
 static Check check_apply_planned(const Table* t, const tfra_opt_params* p, const tfra_sparse_plan* pl, const void* grads,
-                                 const float* param_default_row, AtEntry&& at_entry, unsigned grad_mask = 15u) {
+                                 const float* param_default_row, AtEntry&& at_entry, unsigned grad_mask = 15u,
+                                 const char* wide_twin = nullptr) {
   if (!t || !p || !pl) return refuse(TFRA_ERR_INVALID, "null argument");
-  if (Check e = check_rounding(t); e.done()) return e;
+  if (Check e = check_rounding(t, wide_twin != nullptr); e.done()) return e;
   if (Check e = at_entry(); e.done()) return e;
   if (pl->n == 0) return nothing_to_do();
   if (!grads || !param_default_row) return refuse(TFRA_ERR_INVALID, "null buffer");
@@ -50,7 +64,9 @@ static Check check_apply_planned(const Table* t, const tfra_opt_params* p, const
   if (p->kind < 0 || p->kind > TFRA_OPT_RMSPROP) return refuse(TFRA_ERR_INVALID, "unknown kind");
   const int need = opt_slots(p->kind);
   if (t->opts.aux_fields < need) return refuse(TFRA_ERR_INVALID, "table lacks optimizer slot fields");
-  if (t->opts.dim != pl->dim) return refuse(TFRA_ERR_INVALID, "the plan was built for another dim");
+  if (wide_twin && !wide_apply_dim(t->opts.dim)) return refuse_wide_dim(wide_twin);
+  if (t->opts.dim != pl->dim || (!wide_twin && pl->dim > 64 * tfra::red::MAXCH))
+    return refuse(TFRA_ERR_INVALID, "the plan was built for another dim");
   if (t->opts.device != pl->device && t->opts.device >= 0) return refuse(TFRA_ERR_INVALID, "plan and table live on different devices");
   if (((uintptr_t)grads & grad_mask) || ((uintptr_t)param_default_row & 15))
     return refuse(TFRA_ERR_UNSUPPORTED, grad_mask == 15u ? "gradient / default buffers must be 16-B aligned"
@@ -64,18 +80,21 @@ static Check check_apply_planned(const Table* t, const tfra_opt_params* p, const
 template <class AtEntry>
 static Check check_apply_combined(const Table* t, const tfra_opt_params* p, const tfra_sparse_plan* pl, const void* grad_out,
                                   const int64_t* seg, const float* weights, int combiner, size_t n_rows, const float* param_default_row,
-                                  AtEntry&& at_entry, unsigned grad_mask = 15u) {
+                                  AtEntry&& at_entry, unsigned grad_mask = 15u, const char* wide_twin = nullptr) {
   if (!t || !p || !pl) return refuse(TFRA_ERR_INVALID, "null argument");
   if (combiner < 0 || combiner > 2) return refuse(TFRA_ERR_INVALID, "combiner must be 0 (sum), 1 (mean) or 2 (sqrtn)");
-  if (Check e = check_rounding(t); e.done()) return e;
+  if (Check e = check_rounding(t, wide_twin != nullptr); e.done()) return e;
   if (Check e = at_entry(); e.done()) return e;
-  if (pl->kind != 0 || pl->dim != t->opts.dim) return refuse(TFRA_ERR_INVALID, "the plan was built for another dim");
+  if (wide_twin && !wide_apply_dim(t->opts.dim)) return refuse_wide_dim(wide_twin);
+  if (pl->kind != 0 || pl->dim != t->opts.dim || (!wide_twin && pl->dim > 64 * tfra::red::MAXCH))
+    return refuse(TFRA_ERR_INVALID, "the plan was built for another dim");
   if (t->opts.device != pl->device && t->opts.device >= 0) return refuse(TFRA_ERR_INVALID, "plan and table live on different devices");
   if (pl->n == 0) return nothing_to_do();
   if (!grad_out || !seg || !param_default_row) return refuse(TFRA_ERR_INVALID, "null buffer");
   if (n_rows == 0 || n_rows >= (1ULL << 30)) return refuse(TFRA_ERR_INVALID, "need 1 <= n_rows < 2^30");
-  if (grad_mask != 15u && (unsigned long long)n_rows * (unsigned long long)t->opts.dim >= (1ULL << 32))
-    return refuse(TFRA_ERR_UNSUPPORTED, "half grad_out is addressed with 32-bit element offsets: need n_rows * dim < 2^32");
+  if ((grad_mask != 15u || wide_twin) && (unsigned long long)n_rows * (unsigned long long)t->opts.dim >= (1ULL << 32))
+    return refuse(TFRA_ERR_UNSUPPORTED, wide_twin ? "wide grad_out is addressed with 32-bit element offsets: need n_rows * dim < 2^32"
+                                                  : "half grad_out is addressed with 32-bit element offsets: need n_rows * dim < 2^32");
   if (((uintptr_t)grad_out & grad_mask) || ((uintptr_t)param_default_row & 15) || ((uintptr_t)seg & 7) || ((uintptr_t)weights & 3))
     return refuse(TFRA_ERR_UNSUPPORTED, grad_mask == 15u ? "grad_out / default buffers must be 16-B aligned"
                                                          : "half grad_out must be 8-B aligned, the default row 16-B");

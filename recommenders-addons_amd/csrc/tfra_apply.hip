@@ -445,6 +445,7 @@ extern "C" int tfra_plan_reduce_to(const tfra_sparse_plan_t* pl, const float* gr
   if (pl->n == 0) return TFRA_OK;
   if (!grads || !dest || !rows_out) return set_error(TFRA_ERR_INVALID, "plan_reduce_to: null buffer");
   const int dim = pl->dim;
+  if (dim > 64 * MAXCH) return set_error(TFRA_ERR_UNSUPPORTED, "plan_reduce_to: a plan built wide serves the *_wide write-backs only");
   if (dim <= 0 || (((uintptr_t)grads | (uintptr_t)rows_out) & 15))
     return set_error(TFRA_ERR_INVALID, "plan_reduce_to: the plan must have been built with the rows' dim; buffers 16-B aligned");
   if (on_device(pl->device) != hipSuccess) return set_error(TFRA_ERR_HIP, "plan_reduce_to: hipSetDevice");

@@ -622,13 +622,17 @@ static size_t plan_smem_bytes(unsigned cm) { return (size_t)cm * 36 + (size_t)TA
 
 // The argument checks of a plan build, for the single call and for a descriptor of the grouped one (tfra_multi_sparse_plan_build).
 // active: there are ids.  dim 0 (the SET plan) passes: the single call builds it, the grouped call refuses it at its entry.
+// wide (tfra_sparse_plan_build_wide): the same checks with the width rule of the wide write-backs (tfra_apply_wide.hip) — nothing
+// else of a build looks at dim but the size of the partial rows.
 template <class AtEntry>
-static Check check_plan_build(const tfra_sparse_plan* pl, size_t n, const int64_t* ids, int dim, AtEntry&& at_entry) {
+static Check check_plan_build(const tfra_sparse_plan* pl, size_t n, const int64_t* ids, int dim, AtEntry&& at_entry, bool wide = false) {
   if (!pl) return refuse(TFRA_ERR_INVALID, "null plan");
   if (Check e = at_entry(); e.done()) return e;
   if (n == 0) return nothing_to_do();
   if (!ids) return refuse(TFRA_ERR_INVALID, "null ids");
-  if (dim != 0 && (dim < 0 || dim % 4 != 0 || dim > 64 * MAXCH))
+  if (wide && (dim % 4 != 0 || dim <= 64 * MAXCH || dim > 1024))
+    return refuse(TFRA_ERR_UNSUPPORTED, "needs dim % 4 == 0 and 256 < dim <= 1024 (dim <= 256: tfra_sparse_plan_build)");
+  if (!wide && dim != 0 && (dim < 0 || dim % 4 != 0 || dim > 64 * MAXCH))
     return refuse(TFRA_ERR_UNSUPPORTED, "needs dim % 4 == 0 and dim <= 256 (dim 0: assign-only plan)");
   if (n > MAX_IDS) return refuse(TFRA_ERR_UNSUPPORTED, "at most 2^18 ids per plan");
   return Check{};
@@ -747,7 +751,8 @@ static void plan_built(tfra_sparse_plan* pl, const PlanLayout& L) {
   pl->n = L.n; pl->npad = L.npad; pl->ntiles = L.ntiles; pl->P = L.P; pl->cm = L.cm; pl->dim = L.dim; pl->kind = 0;
 }
 
-extern "C" int tfra_sparse_plan_build(tfra_sparse_plan_t* pl, size_t n, const int64_t* ids, int dim, tfra_stream_t stream) {
+// tfra_sparse_plan_build and its wide twin: one host part, the width rule its parameter
+static int plan_build_call(const char* who, tfra_sparse_plan_t* pl, size_t n, const int64_t* ids, int dim, tfra_stream_t stream, bool wide) {
   hipStream_t s = (hipStream_t)stream;
   bool skip_counts = false;
   const Check c = check_plan_build(pl, n, ids, dim, [&] {
@@ -757,8 +762,8 @@ extern "C" int tfra_sparse_plan_build(tfra_sparse_plan_t* pl, size_t n, const in
     pl->n = 0;
     pl->ever_built = true;
     return Check{};
-  });
-  if (c.code) return report("sparse_plan_build: ", c);
+  }, wide);
+  if (c.code) return report(who, c);
   if (!c.active) return TFRA_OK;
   if (dim == 0) return setplan_build(pl, n, ids, s, !skip_counts);   // assign-only: the last position and the count of every distinct id
   const PlanLayout L = plan_layout(n, dim);
@@ -782,6 +787,15 @@ extern "C" int tfra_sparse_plan_build(tfra_sparse_plan_t* pl, size_t n, const in
   if (hipGetLastError() != hipSuccess) return set_error(TFRA_ERR_HIP, "sparse_plan_build: launch failed");
   plan_built(pl, L);
   return TFRA_OK;
+}
+
+extern "C" int tfra_sparse_plan_build(tfra_sparse_plan_t* pl, size_t n, const int64_t* ids, int dim, tfra_stream_t stream) {
+  return plan_build_call("sparse_plan_build: ", pl, n, ids, dim, stream, false);
+}
+
+// The plan of a wide write-back (tfra_apply_wide.hip): the same object, builders and layout for 256 < dim <= 1024.
+extern "C" int tfra_sparse_plan_build_wide(tfra_sparse_plan_t* pl, size_t n, const int64_t* ids, int dim, tfra_stream_t stream) {
+  return plan_build_call("sparse_plan_build_wide: ", pl, n, ids, dim, stream, true);
 }
 
 // tfra_multi_sparse_plan_build: the CSR builds of a LIST of plans with launches that do not grow with the list (the frame of

@@ -470,6 +470,11 @@ _SIGS_WIDE = {
     "tfra_table_find_combine_ragged_wide": _SIGS["tfra_table_find_combine_ragged"],
     "tfra_table_find_combine_backprop_weights_wide": _SIGS["tfra_table_find_combine_backprop_weights"],
     "tfra_table_find_combine_ragged_backprop_weights_wide": _SIGS["tfra_table_find_combine_ragged_backprop_weights"],
+    # the planned write-back of such a table (one wave per key): the plan build and the three write-backs, their twins' lists
+    "tfra_sparse_plan_build_wide": _SIGS["tfra_sparse_plan_build"],
+    "tfra_table_apply_planned_wide": _SIGS["tfra_table_apply_planned"],
+    "tfra_table_apply_planned_combined_wide": _SIGS["tfra_table_apply_planned_combined"],
+    "tfra_table_apply_sparse_wide": _SIGS["tfra_table_apply_sparse"],
 }
 
 _lib = None

@@ -252,16 +252,23 @@ PLANNED_VALUE_DTYPES = (torch.float32, torch.float16, torch.bfloat16)   # row ty
 class DynamicEmbeddingOptimizer:
   """`de.DynamicEmbeddingOptimizer(opt)` (PY/dynamic_embedding_optimizer.py:807-867)."""
 
-  def __init__(self, opt, bp_v2=None, synchronous=False, exact_order=False):
+  def __init__(self, opt, bp_v2=None, synchronous=False, exact_order=False, wide_rows=False):
     """exact_order=True sums duplicate gradients strictly in input order (bit-exact vs a sequential
     CPU unsorted_segment_sum) through unique + segment_sum + apply; the default uses the fused
-    two-kernel path whose fixed summation tree is deterministic but not the sequential order."""
+    two-kernel path whose fixed summation tree is deterministic but not the sequential order.
+    wide_rows=True gives a variable of 256 < dim <= 1024 that fused path too (the *_wide write-backs: `can_plan_wide`); it is
+    opt-in because such a variable takes unique + segment_sum today, whose sequential sums round differently from the tree's."""
     if not isinstance(opt, _Opt):
       raise TypeError("optimizer must be one of tfra_amd.dynamic_embedding.optimizers.{SGD,Adam,Adagrad,Ftrl} or a "
                       "subclass of optimizers.Generic")
     self.opt = opt
     self.iterations = 0
     self.exact_order = exact_order
+    self.wide_rows = wide_rows
+
+  def _takes_wide(self, var, n):
+    """Whether a write-back of n ids of `var` takes the wide calls: asked for, a fused rule, not exact_order, `can_plan_wide`."""
+    return self.wide_rows and self.opt.kind is not None and not self.exact_order and n > 0 and self.can_plan_wide(var, n)
 
   @staticmethod
   def variable_kwargs(opt):
@@ -326,7 +333,8 @@ class DynamicEmbeddingOptimizer:
       self._check(var)
       n = tw.entry_ids.numel()
       plan = tw.take_entry_plan()
-      fused = (self.opt.kind is not None and not self.exact_order and not var.bp_v2 and n > 0 and self.can_plan(var, n))
+      wide = not var.bp_v2 and self._takes_wide(var, n)
+      fused = wide or (self.opt.kind is not None and not self.exact_order and not var.bp_v2 and n > 0 and self.can_plan(var, n))
       if not fused:
         if plan is not None:
           _release_plan(var, plan)
@@ -343,8 +351,12 @@ class DynamicEmbeddingOptimizer:
         if getattr(var, "restrict_policy", None) is not None:
           var.restrict_policy.apply_update(tw.entry_ids)
         t = var._tables[0]
-        t._table.apply_planned_combined(p, plan, g, tw.seg, tw.weights, device_ops.COMBINERS[tw.combiner],
-                                        t._default_value.to(torch.float32), grad_scale=grad_scale)
+        if wide:   # (float32 grad_out only: a half one or a scale is up-cast first, as on every untyped route)
+          t._table.apply_planned_combined_wide(p, plan, self._upcast(g, var.dim, grad_scale).contiguous(), tw.seg, tw.weights,
+                                               device_ops.COMBINERS[tw.combiner], t._default_value.to(torch.float32))
+        else:
+          t._table.apply_planned_combined(p, plan, g, tw.seg, tw.weights, device_ops.COMBINERS[tw.combiner],
+                                          t._default_value.to(torch.float32), grad_scale=grad_scale)
       finally:
         if pooled:
           _release_plan(var, plan)
@@ -401,6 +413,23 @@ class DynamicEmbeddingOptimizer:
         seen.add(id(var))
         n = tw.entry_ids.numel()
         plan = tw.take_entry_plan()
+        if not var.bp_v2 and self._takes_wide(var, n):   # the wide write-back is not grouped: the single call, in list order
+          pooled = plan is None
+          if plan is None:
+            plan = _pool_plan(var)
+            if plan is None:
+              plan, pooled = SparsePlan(var._primary, var.dim), False
+            plan.build(tw.entry_ids)
+          try:
+            if getattr(var, "restrict_policy", None) is not None:
+              var.restrict_policy.apply_update(tw.entry_ids)
+            t = var._tables[0]
+            t._table.apply_planned_combined_wide(p, plan, self._upcast(g, var.dim, grad_scale).contiguous(), tw.seg, tw.weights,
+                                                 device_ops.COMBINERS[tw.combiner], t._default_value.to(torch.float32))
+          finally:
+            if pooled:
+              _release_plan(var, plan)
+          continue
         fused = (self.opt.kind is not None and not self.exact_order and not var.bp_v2 and n > 0 and self.can_plan(var, n))
         if not fused:
           if plan is not None:
@@ -507,12 +536,20 @@ class DynamicEmbeddingOptimizer:
     return (var.shard_num == 1 and misses_are_static(var) and var.dim % 4 == 0 and var.dim <= 256 and
             n <= (1 << 18) and var.value_dtype in PLANNED_VALUE_DTYPES)
 
+  @staticmethod
+  def can_plan_wide(var, n):
+    """`can_plan` for the wide write-backs (the *_wide calls): the same conditions with 256 < dim <= 1024, and no stochastic
+    rounding (their kernels round to nearest even)."""
+    return (var.shard_num == 1 and misses_are_static(var) and var.dim % 4 == 0 and 256 < var.dim <= 1024 and
+            n <= (1 << 18) and var.value_dtype in PLANNED_VALUE_DTYPES and not getattr(var, "stochastic_rounding", None))
+
   def plan(self, var, ids, plan=None):
     """Build (or rebuild) the id-only half of `apply_sparse(var, ids, ...)` on the current stream; pass the
     result as `apply_sparse(..., plan=plan)`.  Call it under `torch.cuda.stream(side_stream)` to overlap it
-    with the lookup of the same ids or with the previous step."""
+    with the lookup of the same ids or with the previous step.  (wide_rows=True: also for a `can_plan_wide` variable.)"""
     ids = torch.as_tensor(ids, device=var._primary).reshape(-1)
-    if not self.can_plan(var, ids.numel()) or self.exact_order or self.opt.kind is None:
+    if (not (self.can_plan(var, ids.numel()) or (self.wide_rows and self.can_plan_wide(var, ids.numel()))) or self.exact_order or
+        self.opt.kind is None):
       raise ValueError("this variable / batch / optimizer takes the unique + segment_sum write-back, which has no plan")
     if plan is None:
       plan = SparsePlan(var._tables[0]._device, var.dim)
@@ -537,6 +574,9 @@ class DynamicEmbeddingOptimizer:
       if getattr(var, "restrict_policy", None) is not None:
         var.restrict_policy.apply_update(plan.ids if ids is None else ids)   # (plan.ids are int64: the caller's keep the key dtype)
       t = var._tables[0]
+      if self._takes_wide(var, plan.n):
+        t._table.apply_planned_wide(p, plan, self._upcast(grad, var.dim, grad_scale), t._default_value.to(torch.float32))
+        return
       t._table.apply_planned(p, plan, grad.reshape(-1, var.dim), t._default_value.to(torch.float32), grad_scale=grad_scale)
       return
     ids = torch.as_tensor(ids, device=var._primary).reshape(-1)
@@ -546,6 +586,11 @@ class DynamicEmbeddingOptimizer:
       return
     if getattr(var, "restrict_policy", None) is not None:  # PY/embedding_weights.py:441-442
       var.restrict_policy.apply_update(ids)
+    if self._takes_wide(var, n):
+      # 256 < dim <= 1024, opted in: the same two kernels' work, one wave per key (tfra_apply_wide.hip)
+      t = var._tables[0]
+      t._table.apply_sparse_wide(p, ids, self._upcast(grad, var.dim, grad_scale), t._default_value.to(torch.float32))
+      return
     if (var.shard_num == 1 and misses_are_static(var) and var.dim % 4 == 0 and var.dim <= 256 and not self.exact_order and
         var.value_dtype in PLANNED_VALUE_DTYPES):
       # whole backward half in two kernels (tile reduce + bucket apply): no host sync, deterministic.  (More than 2^18

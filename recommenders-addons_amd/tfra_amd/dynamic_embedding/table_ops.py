@@ -830,6 +830,34 @@ class _DeviceTable:
     _over_plans((plan,), self._device, sync, _capi.call, "tfra_table_apply_planned_combined", self._h, ctypes.byref(params), plan._h,
                 _ptr(grad_out), _ptr(seg), _ptr(w), int(combiner), grad_out.shape[0], _ptr(d), _stream(self._device))
 
+  # ---- the same three for wide rows: 256 < dim <= 1024, one wave per key (tfra_apply_wide.hip); float32 gradients, no grad_scale ----
+  def apply_sparse_wide(self, params, ids, grads, default_row):
+    """apply_sparse for a table of 256 < dim <= 1024 (tfra_table_apply_sparse_wide): at most 2^18 ids, float32 gradients."""
+    ids = self._keys(ids).reshape(-1)
+    grads = grads.to(self._device, torch.float32).contiguous()
+    if grads.numel() != ids.numel() * self._dim:
+      raise ValueError("Expected shape %s for grads, got %s" % ([ids.numel(), self._dim], list(grads.shape)))
+    d = default_row.to(self._device, torch.float32).contiguous()
+    _capi.call("tfra_table_apply_sparse_wide", self._h, ctypes.byref(params), ids.numel(), _ptr(ids), _ptr(grads), _ptr(d),
+               _stream(self._device))
+
+  def apply_planned_wide(self, params, plan, grads, default_row, sync=True):
+    """apply_planned for a table of 256 < dim <= 1024 (tfra_table_apply_planned_wide); `plan`: a `SparsePlan` of that dim."""
+    _check_plan(plan, self._dim, self._device)
+    grads = grads.to(self._device, torch.float32).contiguous()
+    if grads.numel() != plan.n * self._dim:
+      raise ValueError("Expected shape %s for grads, got %s" % ([plan.n, self._dim], list(grads.shape)))
+    d = default_row.to(self._device, torch.float32).contiguous()
+    _over_plans((plan,), self._device, sync, _capi.call, "tfra_table_apply_planned_wide", self._h, ctypes.byref(params), plan._h,
+                _ptr(grads), _ptr(d), _stream(self._device))
+
+  def apply_planned_combined_wide(self, params, plan, grad_out, seg, weights, combiner, default_row, sync=True):
+    """apply_planned_combined for a table of 256 < dim <= 1024 (tfra_table_apply_planned_combined_wide): float32 grad_out with
+    n_rows * dim < 2^32; the expanded [nnz, dim] entry gradient is never formed."""
+    (_, grad_out), seg, w, d = self._apply_combined_args(plan, grad_out.to(torch.float32), seg, weights, default_row)
+    _over_plans((plan,), self._device, sync, _capi.call, "tfra_table_apply_planned_combined_wide", self._h, ctypes.byref(params),
+                plan._h, _ptr(grad_out), _ptr(seg), _ptr(w), int(combiner), grad_out.shape[0], _ptr(d), _stream(self._device))
+
   def upsert_sparse(self, ids, values, scores=None):
     """insert_or_assign of a batch whose keys may repeat: the LAST occurrence wins (the reference's sequential
     order), de-duplicated on the device — also on a bounded table at max_capacity."""
@@ -1140,7 +1168,9 @@ class SparsePlan:
         stream.wait_event(self._used)     # the previous batch's sums/apply still read the plan buffers
       ids.record_stream(stream)
     self.ids, self.n = ids, ids.numel()   # keeps the ids alive until the next build
-    _capi.call("tfra_sparse_plan_build", self._h, self.n, _ptr(ids), self._dim, _stream(self._device))
+    # (a dim of the wide write-backs, 256 < dim <= 1024, takes their build: the same plan object, builders and layout)
+    _capi.call("tfra_sparse_plan_build_wide" if 256 < self._dim <= 1024 else "tfra_sparse_plan_build", self._h, self.n, _ptr(ids),
+               self._dim, _stream(self._device))
     if sync:
       self._built.record(stream)
     return self
@@ -1394,6 +1424,16 @@ class _WideRows:
                                            default_row=None):
     return self._table.find_combine_ragged_weight_grad_wide(row_splits, ids, weights, combiner, grad_out, prune=prune,
                                                             fill_id=fill_id, default_row=default_row)
+
+  # the wide write-backs (`_DeviceTable.apply_sparse_wide` and its two planned siblings)
+  def apply_sparse_wide(self, params, ids, grads, default_row):
+    return self._table.apply_sparse_wide(params, ids, grads, default_row)
+
+  def apply_planned_wide(self, params, plan, grads, default_row, sync=True):
+    return self._table.apply_planned_wide(params, plan, grads, default_row, sync=sync)
+
+  def apply_planned_combined_wide(self, params, plan, grad_out, seg, weights, combiner, default_row, sync=True):
+    return self._table.apply_planned_combined_wide(params, plan, grad_out, seg, weights, combiner, default_row, sync=sync)
 
 
 class _MixedRows:
