@@ -1413,6 +1413,30 @@ int tfra_table_find_combine_ragged_backprop_weights_wide(tfra_table_t* t, size_t
                                                          int64_t fill_id, const void* default_row, const float* grad_out,
                                                          float* dw_out, tfra_stream_t stream);
 
+/* The four wide calls for LONG rows — a click or watch history of a few hundred items, each a 512 to 1024 column
+ * content embedding —: the argument lists, host frames (checks, refusals behind the call's own name, locking, nnz == 0 behaviour,
+ * what is enqueued), widths and storage types of the *_wide calls above, and their results BIT FOR BIT.  ONE block owns an output
+ * row, grid = n_rows: the forward runs 64 ceil(dim / 256) threads, a wave per 256 columns and 4 ceil(dim / 256) probes in flight;
+ * the gradient 256 threads, a 16-lane group per entry.  The only LDS is what the groups resolved, 256 / 128 bytes per block.
+ * A block per row of one entry idles most of its groups: categorical features keep the *_wide calls (what was measured, and from
+ * which row length on this form is the choice: README).
+ * Not provided in this form: typed outputs, a half grad_out, tiers, the grouped *_many calls, a mixed short / long dispatch at
+ * wide dims.  Additive; ABI version 1.                                   (tests/test_wide_long_abi.py, tests/test_gpu_wide_long.py) */
+int tfra_table_find_combine_wide_long(tfra_table_t* t, tfra_workspace_t* ws, size_t nnz, const int64_t* ids, const int64_t* seg,
+                                      const float* weights, int combiner, size_t n_rows, const void* default_row, float* out,
+                                      tfra_stream_t stream);
+int tfra_table_find_combine_ragged_wide_long(tfra_table_t* t, size_t n_rows, const int64_t* row_splits, size_t nnz,
+                                             const int64_t* ids, const float* weights, int combiner, uint32_t flags,
+                                             int64_t fill_id, const void* default_row, float* out, tfra_stream_t stream);
+int tfra_table_find_combine_backprop_weights_wide_long(tfra_table_t* t, tfra_workspace_t* ws, size_t nnz, const int64_t* ids,
+                                                       const int64_t* seg, const float* weights, int combiner, size_t n_rows,
+                                                       const void* default_row, const float* grad_out, float* dw_out,
+                                                       tfra_stream_t stream);
+int tfra_table_find_combine_ragged_backprop_weights_wide_long(tfra_table_t* t, size_t n_rows, const int64_t* row_splits, size_t nnz,
+                                                              const int64_t* ids, const float* weights, int combiner,
+                                                              uint32_t flags, int64_t fill_id, const void* default_row,
+                                                              const float* grad_out, float* dw_out, tfra_stream_t stream);
+
 /* The planned sparse write-back for WIDE rows: the plan build, the planned, the combined and the one-call
  * write-back of a float32, float16 or bfloat16 table with dim % 4 == 0 and 256 < dim <= 1024, float32 gradients.  Each takes its
  * twin's argument list (tfra_sparse_plan_build, tfra_table_apply_planned, tfra_table_apply_planned_combined,

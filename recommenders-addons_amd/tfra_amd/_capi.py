@@ -475,6 +475,11 @@ _SIGS_WIDE = {
     "tfra_table_apply_planned_wide": _SIGS["tfra_table_apply_planned"],
     "tfra_table_apply_planned_combined_wide": _SIGS["tfra_table_apply_planned_combined"],
     "tfra_table_apply_sparse_wide": _SIGS["tfra_table_apply_sparse"],
+    # the pooled reads of such a table for LONG rows (one block per output row, tfra_pool_wide_long.hip): the same lists
+    "tfra_table_find_combine_wide_long": _SIGS["tfra_table_find_combine"],
+    "tfra_table_find_combine_ragged_wide_long": _SIGS["tfra_table_find_combine_ragged"],
+    "tfra_table_find_combine_backprop_weights_wide_long": _SIGS["tfra_table_find_combine_backprop_weights"],
+    "tfra_table_find_combine_ragged_backprop_weights_wide_long": _SIGS["tfra_table_find_combine_ragged_backprop_weights"],
 }
 
 _lib = None

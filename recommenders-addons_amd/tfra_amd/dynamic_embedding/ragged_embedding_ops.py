@@ -107,7 +107,12 @@ def _wide(wide_rows, long_rows, mixed_rows):
   """The keyword of a wide-row lookup behind this module's calls to the tuple form: nothing without it.  With long_rows or
   mixed_rows: ValueError."""
   _not_wide_and(wide_rows, long_rows, mixed_rows)
-  return {"wide_rows": True} if wide_rows else {}
+  return {"wide_rows": wide_rows} if wide_rows else {}
+
+
+def _wide_ragged(params, wide_rows):
+  """The ragged wide read the keyword's value names: "block" — one block per output row —, or the wave form."""
+  return params.lookup_combined_ragged_wide_long if wide_rows == "block" else params.lookup_combined_ragged_wide
 
 
 def embedding_lookup_sparse(params, sp_ids, sp_weights, name=None, combiner="mean", return_trainable=False, plan_writeback=False,
@@ -132,14 +137,15 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights, name=None, combiner="mea
   wide_rows: a variable of 256 < dim <= 1024 — a lookup that is not a training step's takes tfra_table_find_combine_ragged_wide (one
   wave per output row, one launch, nothing read on the host) under the tuple form's conditions (`de.embedding_lookup_sparse`), the
   same bits; a training lookup keeps the tuple form's chain, whose wrapper remembers the keyword for `weights_grad`.  Everywhere
-  else it changes nothing.  With long_rows or mixed_rows: ValueError."""
+  else it changes nothing.  With long_rows or mixed_rows: ValueError.  wide_rows="block": tfra_table_find_combine_ragged_wide_long
+  (one block per output row, for long rows) in the wave call's place, the same bits; any other truthy value: ValueError."""
   _check_combiner(combiner)
   typed = dict(_typed(out_dtype), **_long(long_rows, out_dtype, mixed_rows), **_wide(wide_rows, long_rows, mixed_rows))
   rs, ids, w = _ragged_input(params, sp_ids, sp_weights)
   n = rs.numel() - 1
   if not (_pooled_training if return_trainable else _pooled_forward)(params, None):
     if not return_trainable and _wide_forward(params, None, out_dtype, wide_rows):
-      return params.lookup_combined_ragged_wide(rs, ids, w, combiner)
+      return _wide_ragged(params, wide_rows)(rs, ids, w, combiner)
     seg = row_ids_of(rs, ids.numel()) if entry_seg is None else entry_seg
     return _tuple_form.embedding_lookup_sparse(params, (seg, ids), w, combiner=combiner, return_trainable=return_trainable,
                                                num_rows=n, plan_writeback=plan_writeback, _out_shape=out_shape, **typed)
@@ -172,7 +178,7 @@ def safe_embedding_lookup_sparse(params, sparse_ids, sparse_weights=None, combin
   if not (_pooled_training if return_trainable else _pooled_forward)(params, None):
     if not return_trainable and _wide_forward(params, None, out_dtype, wide_rows):
       prune, fill = _safe_flags(w, combiner, default_id)
-      return params.lookup_combined_ragged_wide(rs, ids, w, combiner, prune=prune, fill_id=fill)
+      return _wide_ragged(params, wide_rows)(rs, ids, w, combiner, prune=prune, fill_id=fill)
     return _tuple_form.safe_embedding_lookup_sparse(params, (row_ids_of(rs, ids.numel()), ids), w, combiner=combiner,
                                                     default_id=default_id, return_trainable=return_trainable, num_rows=n,
                                                     plan_writeback=plan_writeback, **typed)

@@ -340,41 +340,75 @@ class _DeviceTable:
                _ptr(w), int(combiner), flags, fill, _ptr(d), _ptr(g), _ptr(dw), _stream(self._device))
     return dw
 
-  # ---- the wide-row forms: 256 < dim <= 1024, one wave per output row (tfra_pool_wide.hip), the op chain's bits -----------------
-  def find_combine_wide(self, ids, seg, weights, combiner, n_rows, default_row=None):
-    """`find_combine` for a table of 256 < dim <= 1024 (tfra_table_find_combine_wide): the same arguments and result — bit for bit
-    unique -> find -> device_ops.sparse_segment_combine, which is all such a table had.  float32 out."""
+  # ---- the wide-row forms: 256 < dim <= 1024, the op chain's bits.  `form`: "_wide", one wave per output row (tfra_pool_wide.hip),
+  # or "_wide_long", one block per output row (tfra_pool_wide_long.hip): the same argument lists, checks and results ---------------
+  def _find_combine_wide(self, form, ids, seg, weights, combiner, n_rows, default_row):
     ids, seg, w, d, out = self._find_combine_args(ids, seg, weights, n_rows, default_row)
-    _capi.call("tfra_table_find_combine_wide", self._h, _workspace(self._device), ids.numel(), _ptr(ids), _ptr(seg), _ptr(w),
+    _capi.call("tfra_table_find_combine" + form, self._h, _workspace(self._device), ids.numel(), _ptr(ids), _ptr(seg), _ptr(w),
                int(combiner), int(n_rows), _ptr(d), _ptr(out), _stream(self._device))
     return out
 
-  def find_combine_ragged_wide(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, default_row=None):
-    """`find_combine_ragged` for 256 < dim <= 1024 (tfra_table_find_combine_ragged_wide), in one launch.  float32 out."""
+  def _find_combine_ragged_wide(self, form, row_splits, ids, weights, combiner, prune, fill_id, default_row):
     rs, ids, w, flags, fill, d, out = self._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row)
-    _capi.call("tfra_table_find_combine_ragged_wide", self._h, rs.numel() - 1, _ptr(rs), ids.numel(), _ptr(ids), _ptr(w),
+    _capi.call("tfra_table_find_combine_ragged" + form, self._h, rs.numel() - 1, _ptr(rs), ids.numel(), _ptr(ids), _ptr(w),
                int(combiner), flags, fill, _ptr(d), _ptr(out), _stream(self._device))
     return out
+
+  def _find_combine_weight_grad_wide(self, form, ids, seg, weights, combiner, grad_out, default_row):
+    g = self._weight_grad_out(grad_out, None)
+    ids, seg, w, d, _ = self._find_combine_args(ids, seg, weights, 0, default_row)
+    dw = torch.empty(ids.numel(), dtype=torch.float32, device=self._device)
+    _capi.call("tfra_table_find_combine_backprop_weights" + form, self._h, _workspace(self._device), ids.numel(), _ptr(ids), _ptr(seg),
+               _ptr(w), int(combiner), g.shape[0], _ptr(d), _ptr(g), _ptr(dw), _stream(self._device))
+    return dw
+
+  def _find_combine_ragged_weight_grad_wide(self, form, row_splits, ids, weights, combiner, grad_out, prune, fill_id, default_row):
+    rs, ids, w, flags, fill, d, _ = self._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row)
+    g = self._weight_grad_out(grad_out, rs.numel() - 1)
+    dw = torch.empty(ids.numel(), dtype=torch.float32, device=self._device)
+    _capi.call("tfra_table_find_combine_ragged_backprop_weights" + form, self._h, rs.numel() - 1, _ptr(rs), ids.numel(), _ptr(ids),
+               _ptr(w), int(combiner), flags, fill, _ptr(d), _ptr(g), _ptr(dw), _stream(self._device))
+    return dw
+
+  def find_combine_wide(self, ids, seg, weights, combiner, n_rows, default_row=None):
+    """`find_combine` for a table of 256 < dim <= 1024 (tfra_table_find_combine_wide): the same arguments and result — bit for bit
+    unique -> find -> device_ops.sparse_segment_combine, which is all such a table had.  float32 out."""
+    return self._find_combine_wide("_wide", ids, seg, weights, combiner, n_rows, default_row)
+
+  def find_combine_ragged_wide(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, default_row=None):
+    """`find_combine_ragged` for 256 < dim <= 1024 (tfra_table_find_combine_ragged_wide), in one launch.  float32 out."""
+    return self._find_combine_ragged_wide("_wide", row_splits, ids, weights, combiner, prune, fill_id, default_row)
 
   def find_combine_weight_grad_wide(self, ids, seg, weights, combiner, grad_out, default_row=None):
     """`find_combine_weight_grad` for 256 < dim <= 1024 (tfra_table_find_combine_backprop_weights_wide): bit for bit find +
     device_ops.sparse_segment_combine_weight_grad.  float32 grad_out."""
-    g = self._weight_grad_out(grad_out, None)
-    ids, seg, w, d, _ = self._find_combine_args(ids, seg, weights, 0, default_row)
-    dw = torch.empty(ids.numel(), dtype=torch.float32, device=self._device)
-    _capi.call("tfra_table_find_combine_backprop_weights_wide", self._h, _workspace(self._device), ids.numel(), _ptr(ids), _ptr(seg),
-               _ptr(w), int(combiner), g.shape[0], _ptr(d), _ptr(g), _ptr(dw), _stream(self._device))
-    return dw
+    return self._find_combine_weight_grad_wide("_wide", ids, seg, weights, combiner, grad_out, default_row)
 
   def find_combine_ragged_weight_grad_wide(self, row_splits, ids, weights, combiner, grad_out, prune=False, fill_id=None,
                                            default_row=None):
     """`find_combine_ragged_weight_grad` for 256 < dim <= 1024 (tfra_table_find_combine_ragged_backprop_weights_wide)."""
-    rs, ids, w, flags, fill, d, _ = self._find_combine_ragged_args(row_splits, ids, weights, prune, fill_id, default_row)
-    g = self._weight_grad_out(grad_out, rs.numel() - 1)
-    dw = torch.empty(ids.numel(), dtype=torch.float32, device=self._device)
-    _capi.call("tfra_table_find_combine_ragged_backprop_weights_wide", self._h, rs.numel() - 1, _ptr(rs), ids.numel(), _ptr(ids),
-               _ptr(w), int(combiner), flags, fill, _ptr(d), _ptr(g), _ptr(dw), _stream(self._device))
-    return dw
+    return self._find_combine_ragged_weight_grad_wide("_wide", row_splits, ids, weights, combiner, grad_out, prune, fill_id,
+                                                      default_row)
+
+  def find_combine_wide_long(self, ids, seg, weights, combiner, n_rows, default_row=None):
+    """`find_combine_wide` for LONG rows — a few hundred entries each — (tfra_table_find_combine_wide_long): one block per output
+    row, a wave per 256 columns.  The same arguments and the same bits."""
+    return self._find_combine_wide("_wide_long", ids, seg, weights, combiner, n_rows, default_row)
+
+  def find_combine_ragged_wide_long(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, default_row=None):
+    """`find_combine_ragged_wide` for long rows (tfra_table_find_combine_ragged_wide_long), in one launch: the same bits."""
+    return self._find_combine_ragged_wide("_wide_long", row_splits, ids, weights, combiner, prune, fill_id, default_row)
+
+  def find_combine_weight_grad_wide_long(self, ids, seg, weights, combiner, grad_out, default_row=None):
+    """`find_combine_weight_grad_wide` for long rows (tfra_table_find_combine_backprop_weights_wide_long): one block per row, a
+    16-lane group per entry.  The same bits; float32 grad_out."""
+    return self._find_combine_weight_grad_wide("_wide_long", ids, seg, weights, combiner, grad_out, default_row)
+
+  def find_combine_ragged_weight_grad_wide_long(self, row_splits, ids, weights, combiner, grad_out, prune=False, fill_id=None,
+                                                default_row=None):
+    """`find_combine_ragged_weight_grad_wide` for long rows (tfra_table_find_combine_ragged_backprop_weights_wide_long)."""
+    return self._find_combine_ragged_weight_grad_wide("_wide_long", row_splits, ids, weights, combiner, grad_out, prune, fill_id,
+                                                      default_row)
 
   # ---- the mixed-row forms: 16 rows per block, a row of long_from entries or more by the whole block (tfra_pool_mixed.hip) ------
   def find_combine_mixed(self, ids, seg, weights, combiner, n_rows, default_row=None, long_from=0):
@@ -1424,6 +1458,22 @@ class _WideRows:
                                            default_row=None):
     return self._table.find_combine_ragged_weight_grad_wide(row_splits, ids, weights, combiner, grad_out, prune=prune,
                                                             fill_id=fill_id, default_row=default_row)
+
+  # the same four for long rows, one block per output row (`_DeviceTable.find_combine_wide_long` and its three siblings)
+  def find_combine_wide_long(self, ids, seg, weights, combiner, n_rows, default_row=None):
+    return self._table.find_combine_wide_long(ids, seg, weights, combiner, n_rows, default_row)
+
+  def find_combine_ragged_wide_long(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, default_row=None):
+    return self._table.find_combine_ragged_wide_long(row_splits, ids, weights, combiner, prune=prune, fill_id=fill_id,
+                                                     default_row=default_row)
+
+  def find_combine_weight_grad_wide_long(self, ids, seg, weights, combiner, grad_out, default_row=None):
+    return self._table.find_combine_weight_grad_wide_long(ids, seg, weights, combiner, grad_out, default_row)
+
+  def find_combine_ragged_weight_grad_wide_long(self, row_splits, ids, weights, combiner, grad_out, prune=False, fill_id=None,
+                                                default_row=None):
+    return self._table.find_combine_ragged_weight_grad_wide_long(row_splits, ids, weights, combiner, grad_out, prune=prune,
+                                                                 fill_id=fill_id, default_row=default_row)
 
   # the wide write-backs (`_DeviceTable.apply_sparse_wide` and its two planned siblings)
   def apply_sparse_wide(self, params, ids, grads, default_row):

@@ -123,7 +123,10 @@ def _not_both(long_rows, mixed_rows):
 
 
 def _not_wide_and(wide_rows, long_rows, mixed_rows):
-  """wide_rows names a launch shape of its own (one wave per row of 256 < dim <= 1024): the long and mixed shapes stop at dim 256."""
+  """wide_rows names a launch shape of its own, True (one wave per row of 256 < dim <= 1024) or "block" (one block per row: long
+  rows at those widths); the long and mixed shapes stop at dim 256."""
+  if wide_rows and wide_rows not in (True, "block"):
+    raise ValueError('wide_rows is False, True (one wave per output row) or "block" (one block per output row), not %r' % (wide_rows,))
   if wide_rows and (long_rows or mixed_rows):
     raise ValueError("wide_rows=True excludes long_rows and mixed_rows: their calls serve dim <= 256")
 
@@ -627,6 +630,31 @@ class Variable:
     t, ids = self._wide_operands(ids, "lookup_combined_wide")
     return t._table.find_combine_wide(ids, seg, weights, device_ops.COMBINERS[combiner], n_rows, t._default_value)
 
+  # the same four for LONG rows at those widths — a history of a few hundred ids per row —: one block per output row
+  # (tfra_pool_wide_long.hip), the wide methods' parameter lists, conditions and bits
+  def lookup_combined_wide_long(self, ids, seg, weights, combiner, n_rows, name=None):
+    """`lookup_combined_wide` from one block per output row (tfra_table_find_combine_wide_long): the same bits."""
+    t, ids = self._wide_operands(ids, "lookup_combined_wide_long")
+    return t._table.find_combine_wide_long(ids, seg, weights, device_ops.COMBINERS[combiner], n_rows, t._default_value)
+
+  def lookup_combined_ragged_wide_long(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, name=None):
+    """`lookup_combined_ragged_wide` from one block per output row (tfra_table_find_combine_ragged_wide_long): the same bits."""
+    t, ids = self._wide_operands(ids, "lookup_combined_ragged_wide_long")
+    return t._table.find_combine_ragged_wide_long(row_splits, ids, weights, device_ops.COMBINERS[combiner], prune=prune,
+                                                  fill_id=fill_id, default_row=t._default_value)
+
+  def lookup_combined_weight_grad_wide_long(self, ids, seg, weights, combiner, grad_out, name=None):
+    """`lookup_combined_weight_grad_wide` from one block per row (tfra_table_find_combine_backprop_weights_wide_long): the same bits."""
+    t, ids = self._wide_operands(ids, "lookup_combined_weight_grad_wide_long")
+    return t._table.find_combine_weight_grad_wide_long(ids, seg, weights, device_ops.COMBINERS[combiner], grad_out, t._default_value)
+
+  def lookup_combined_ragged_weight_grad_wide_long(self, row_splits, ids, weights, combiner, grad_out, prune=False, fill_id=None,
+                                                   name=None):
+    """`lookup_combined_ragged_weight_grad_wide` from one block per row (tfra_table_find_combine_ragged_backprop_weights_wide_long)."""
+    t, ids = self._wide_operands(ids, "lookup_combined_ragged_weight_grad_wide_long")
+    return t._table.find_combine_ragged_weight_grad_wide_long(row_splits, ids, weights, device_ops.COMBINERS[combiner], grad_out,
+                                                              prune=prune, fill_id=fill_id, default_row=t._default_value)
+
   def lookup_combined_ragged_wide(self, row_splits, ids, weights, combiner, prune=False, fill_id=None, name=None):
     """`lookup_combined_ragged` for 256 < dim <= 1024 (tfra_table_find_combine_ragged_wide), in one launch; prune / fill_id as there."""
     t, ids = self._wide_operands(ids, "lookup_combined_ragged_wide")
@@ -1082,10 +1110,11 @@ class SparseTrainableWrapper(TrainableWrapper):
     """entry_plan: a plan over `entry_ids` whose build is already enqueued (the grouped lookup starts its members' plans in one
     call); the wrapper owns it from here on, as one made with plan_writeback.  long_rows / mixed_rows: the lookup's keyword, which
     `weights_grad` passes on to its pooled read.  wide_rows / wide_ids: the keyword of a lookup over 256 < dim <= 1024 and its flat
-    ids as given; the wrapper is the op chain's (`_pooled_ids` stays None) and only `weights_grad` reads them."""
+    ids as given (the keyword's VALUE is kept: True, or "block" for the block-per-row gradient); the wrapper is the op chain's
+    (`_pooled_ids` stays None) and only `weights_grad` reads them."""
     _not_both(long_rows, mixed_rows)
     _not_wide_and(wide_rows, long_rows, mixed_rows)
-    self._wide_rows, self._wide_ids = bool(wide_rows), wide_ids
+    self._wide_rows, self._wide_ids = wide_rows, wide_ids
     self._long_rows = bool(long_rows)
     self._mixed_rows = bool(mixed_rows)
     if lookup_ids is None:
@@ -1178,7 +1207,9 @@ class SparseTrainableWrapper(TrainableWrapper):
     elif (self._wide_rows and self._wide_ids is not None and g.dtype == torch.float32 and grad_scale is None and
           self.params.can_lookup_combined_wide()):
       # a wide-row lookup's wrapper: the rows straight from the table, the bits of the route below
-      dw = self.params.lookup_combined_weight_grad_wide(self._wide_ids, self._seg, self._weights, self.combiner, g)
+      grad = (self.params.lookup_combined_weight_grad_wide_long if self._wide_rows == "block" else
+              self.params.lookup_combined_weight_grad_wide)
+      dw = grad(self._wide_ids, self._seg, self._weights, self.combiner, g)
     else:
       rows = self.params.lookup(self.ids).to(torch.float32)
       dw = device_ops.sparse_segment_combine_weight_grad(rows, self._idx, g, self._seg, self._weights, self.combiner,
@@ -1337,7 +1368,10 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=
   the calls it reaches without the keyword.  A training lookup keeps the chain and its wrapper (the planned write-backs stop at dim
   256); the wrapper remembers the keyword, and its `weights_grad` reads the rows straight from the table
   (tfra_table_find_combine_backprop_weights_wide) for a float32 grad_out without grad_scale: the same bits.  Together with
-  long_rows or mixed_rows: ValueError.  What it costs and gains: README."""
+  long_rows or mixed_rows: ValueError.  What it costs and gains: README.
+  wide_rows="block": such a variable's rows are LONG as well (a history of a few hundred items, each a wide content embedding).
+  Exactly where True takes the wave calls, "block" takes tfra_table_find_combine_wide_long / ..._backprop_weights_wide_long — one
+  block per output row —, the same bits; any other truthy value: ValueError.  From which row length on it pays: README."""
   _check_combiner(combiner)
   _not_both(long_rows, mixed_rows)
   _not_wide_and(wide_rows, long_rows, mixed_rows)
@@ -1350,7 +1384,7 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=
   pooled = _pooled_training(params, max_norm) if return_trainable else _pooled_forward(params, max_norm)
   if not pooled and not return_trainable and _wide_forward(params, max_norm, out_dtype, wide_rows):
     n = int(seg.max().item()) + 1 if num_rows is None else num_rows
-    return params.lookup_combined_wide(ids, seg, w, combiner, n)
+    return (params.lookup_combined_wide_long if wide_rows == "block" else params.lookup_combined_wide)(ids, seg, w, combiner, n)
   if not pooled:
     uniq, idx, cnt = device_ops.unique(ids)
   n = int(seg.max().item()) + 1 if num_rows is None else num_rows
@@ -1378,7 +1412,7 @@ def embedding_lookup_sparse(params, sp_ids, sp_weights=None, partition_strategy=
   if return_trainable:
     tw = SparseTrainableWrapper(params, uniq.reshape(-1), idx, cnt, seg, w, combiner, n, shape, e_ids, e_seg, e_w,
                                 max_norm=max_norm, plan_writeback=plan_writeback,
-                                **({"wide_rows": True, "wide_ids": ids.reshape(-1)} if wide_rows else {}))
+                                **({"wide_rows": wide_rows, "wide_ids": ids.reshape(-1)} if wide_rows else {}))
     ue = tw.read_value()
   else:
     tw = None
@@ -1735,7 +1769,7 @@ def safe_embedding_lookup_sparse(params, sp_ids, sparse_weights=None, combiner="
                                 return_trainable=return_trainable, num_rows=n, plan_writeback=plan_writeback,
                                 _entries=entries, _out_shape=out_shape, out_dtype=out_dtype,
                                 **({"long_rows": True} if long_rows else {"mixed_rows": True} if mixed_rows else
-                                   {"wide_rows": True} if wide_rows else {}))
+                                   {"wide_rows": wide_rows} if wide_rows else {}))
   res, tw = out if return_trainable else (out, None)
   res = _safe_sparse_finish(params, res, rows, n, default_id, max_norm, lead)
   return (res, _note_pruned(tw, sparse_weights, combiner)) if return_trainable else res
