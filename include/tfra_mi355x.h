@@ -1451,9 +1451,10 @@ int tfra_table_find_combine_ragged_backprop_weights_wide_long(tfra_table_t* t, s
  * ONE wave64 updates a key's row — a lane owns columns k * 256 + 4 * lane — four keys per wave and trip, located by its four 16-lane
  * groups first; the sums walk a bin's items with all 64 lanes on 256 columns.  Every addition is per column and in the twin's
  * order, so columns [a, b) of the result are BIT FOR BIT what the narrow calls write on a table of those columns.
- * Not provided in this form: half gradients and grad_scale (tfra_grads), stochastic rounding, tfra_reduce_by_key,
- * tfra_table_fetch_planned / tfra_table_store_rows, the grouped *_many write-back and plan build, more than 2^18 ids, the step
- * drivers, tiers.  Additive; ABI version 1.          (tests/test_wide_writeback_abi.py, tests/test_gpu_wide_writeback.py) */
+ * Not provided in this form: half gradients and grad_scale (tfra_grads), stochastic rounding, tfra_reduce_by_key, the grouped
+ * *_many write-back and plan build, more than 2^18 ids, the step drivers, tiers.  (Whole rows out and back at these widths:
+ * tfra_table_fetch_planned_wide / tfra_table_store_rows_wide below.)
+ * Additive; ABI version 1.                           (tests/test_wide_writeback_abi.py, tests/test_gpu_wide_writeback.py) */
 int tfra_sparse_plan_build_wide(tfra_sparse_plan_t* plan, size_t n, const int64_t* ids, int dim, tfra_stream_t stream);
 int tfra_table_apply_planned_wide(tfra_table_t* t, const tfra_opt_params* p, const tfra_sparse_plan_t* plan,
                                   const float* grads, const float* param_default_row, tfra_stream_t stream);
@@ -1462,6 +1463,34 @@ int tfra_table_apply_planned_combined_wide(tfra_table_t* t, const tfra_opt_param
                                            size_t n_rows, const float* param_default_row, tfra_stream_t stream);
 int tfra_table_apply_sparse_wide(tfra_table_t* t, const tfra_opt_params* p, size_t n, const int64_t* ids,
                                  const float* grads, const float* param_default_row, tfra_stream_t stream);
+
+/* Whole rows out and back for WIDE rows: tfra_table_fetch_planned and tfra_table_store_rows for a float32, float16
+ * or bfloat16 table with dim % 4 == 0 and 256 < dim <= 1024 — the two table calls of a dense rule without a fused write-back
+ * (optimizers.Generic with whole_rows=True under DynamicEmbeddingOptimizer(wide_rows=True)).  Each takes its twin's argument
+ * list and keeps its twin's contract word for word, the plan being one built by tfra_sparse_plan_build_wide:
+ *   fetch  a READ over the plan's distinct keys: one probe per key, nothing claimed, no score touched; row j < *d_count of every
+ *          output belongs to keys_out[j], in the plan's key order; a wanted field is the exact up-cast of the stored field, a key
+ *          that is not resident gives default_row for field 0 and the stored image of aux_init for the slot vectors; a NULL
+ *          field is neither read nor written; *d_count = -1 on a plan overflow; rows at or beyond the count are not written; a
+ *          built plan of 0 ids gives count 0.  Launches: the sums launch when g is given, then ONE fetch launch.
+ *   store  a unique-keys upsert of whole rows from float32 fields: each element rounded to the row type once, to nearest even; a
+ *          NULL field keeps its bytes on a resident key and starts at aux_init on a claimed one; d_n clamps the count; scores,
+ *          epoch, size and error accounting are those of ONE insert_or_assign(TFRA_FLAG_UNIQUE_KEYS) without scores; on a table
+ *          at max_capacity the eviction phase is its own second launch.
+ * g is float32 without a scale: the twin's checks of the record come first, with their codes, then a half g or one with a scale is
+ * TFRA_ERR_UNSUPPORTED (half gradients are up-cast by the caller).  gsum_out follows the plan's summation tree per column: columns
+ * [a, b) of it are BIT FOR BIT what tfra_table_fetch_planned writes for the same ids and the gradient columns [a, b).
+ * Every check is the twin's, in the twin's order, with the twin's code; the width rule is exchanged (TFRA_ERR_UNSUPPORTED, the
+ * message holds "256 < dim <= 1024" and names the twin).  A plan of at most 2^18 ids.
+ * ONE wave64 moves a key's row — a lane owns columns k * 256 + 4 * lane of every field — four keys per wave and trip, probed or
+ * claimed by its four 16-lane groups first; all fields' loads of a chunk are in flight together.  No LDS in the row kernels.
+ * Not provided in this form: half gradients and grad_scale, tfra_reduce_by_key at these widths, tiers, the grouped forms.
+ * Additive; ABI version 1.                      (tests/test_generic_rows_wide_abi.py, tests/test_gpu_generic_rows_wide.py) */
+int tfra_table_fetch_planned_wide(tfra_table_t* t, const tfra_sparse_plan_t* plan, const tfra_grads* g, const void* default_row,
+                                  int64_t* keys_out, const tfra_row_fields* rows_out, float* gsum_out, int64_t* d_count,
+                                  tfra_stream_t stream);
+int tfra_table_store_rows_wide(tfra_table_t* t, size_t n, const int64_t* d_n, const int64_t* keys, const tfra_row_fields* rows,
+                               tfra_stream_t stream);
 
 /* The weight gradients of MANY pooled lookups in one call (a model with 26 weighted sparse features asks for 26 of them per step:
  * ~100 enqueues for 26 small kernels otherwise).  A descriptor names exactly ONE of table / tier, as tfra_tier_find_combine_desc

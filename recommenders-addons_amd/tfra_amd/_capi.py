@@ -480,6 +480,9 @@ _SIGS_WIDE = {
     "tfra_table_find_combine_ragged_wide_long": _SIGS["tfra_table_find_combine_ragged"],
     "tfra_table_find_combine_backprop_weights_wide_long": _SIGS["tfra_table_find_combine_backprop_weights"],
     "tfra_table_find_combine_ragged_backprop_weights_wide_long": _SIGS["tfra_table_find_combine_ragged_backprop_weights"],
+    # whole rows out and back of such a table (one wave per key, tfra_rows_wide.hip): the two calls of a rule without a fused write-back
+    "tfra_table_fetch_planned_wide": _SIGS["tfra_table_fetch_planned"],
+    "tfra_table_store_rows_wide": _SIGS["tfra_table_store_rows"],
 }
 
 _lib = None

@@ -132,7 +132,10 @@ class Generic(_Opt):
   `store_rows` writes the whole row back with one probe, rounding each element to the row type once.  The rows and slots end
   bit-identical to the default route.  Taken for one shard that is not tiered, float32 / float16 / bfloat16 rows with
   dim % 4 == 0 and dim <= 256, at most 2^18 ids, static misses, and neither bp_v2 nor exact_order; everything else keeps the
-  default route.  On a bounded table the scores move as for ONE upsert per step, not 1 + S."""
+  default route.  On a bounded table the scores move as for ONE upsert per step, not 1 + S.
+  Under `DynamicEmbeddingOptimizer(opt, wide_rows=True)` also for 256 < dim <= 1024 (`fetch_planned_wide` / `store_rows_wide`,
+  DESIGN 4.44; a half gradient or a scale is up-cast first).  Such a variable's default route sums repeated ids sequentially, the
+  plan in its tree: there the two routes agree within rounding, bit for bit on exactly summable gradients."""
   kind = None
   whole_rows = False
 
@@ -491,10 +494,10 @@ class DynamicEmbeddingOptimizer:
   def _takes_whole_rows(self, var, n):
     """Whether a `Generic` rule's step over n ids of `var` takes `_apply_generic_rows`: asked for (whole_rows=True), a plannable
     batch, and none of what keeps the default route (exact_order, bp_v2, a tiered shard; a CUSTOMIZED table, whose upserts carry
-    the caller's scores)."""
+    the caller's scores).  wide_rows=True: also for a `can_plan_wide` variable (the *_wide table calls)."""
     if not getattr(self.opt, "whole_rows", False) or self.exact_order or var.bp_v2 or _has_tiered_shards(var):
       return False
-    if n == 0 or not self.can_plan(var, n):
+    if n == 0 or not (self.can_plan(var, n) or (self.wide_rows and self.can_plan_wide(var, n))):
       return False
     t = var._tables[0]
     return hasattr(t, "fetch_planned") and getattr(t, "_evict_strategy", None) != HkvEvictStrategy.CUSTOMIZED
@@ -517,7 +520,11 @@ class DynamicEmbeddingOptimizer:
     try:
       S = len(self.opt.slots)
       want = [True] * (1 + S) + [False] * (var.aux_fields - S)   # fields the rule does not own are neither read nor written
-      keys, fields, gsum, cnt = t._table.fetch_planned(plan, grads=grad.reshape(-1, var.dim), grad_scale=grad_scale, fields=want)
+      wide = var.dim > 256   # (`_takes_whole_rows` held: a `can_plan_wide` variable — float32 gradients only, up-cast here)
+      if wide:
+        keys, fields, gsum, cnt = t._table.fetch_planned_wide(plan, grads=self._upcast(grad, var.dim, grad_scale), fields=want)
+      else:
+        keys, fields, gsum, cnt = t._table.fetch_planned(plan, grads=grad.reshape(-1, var.dim), grad_scale=grad_scale, fields=want)
     finally:
       if own and pooled:
         _release_plan(var, plan)
@@ -525,7 +532,7 @@ class DynamicEmbeddingOptimizer:
     if u < 0:
       raise RuntimeError("the write-back plan of %r overflowed" % var.name)
     new = self.opt.update(self.iterations, fields[0][:u], gsum[:u], *[f[:u] for f in fields[1:1 + S]])
-    t._table.store_rows(keys[:u], list(new[:1 + S]) + [None] * (var.aux_fields - S))
+    (t._table.store_rows_wide if wide else t._table.store_rows)(keys[:u], list(new[:1 + S]) + [None] * (var.aux_fields - S))
 
   @staticmethod
   def can_plan(var, n):

@@ -930,6 +930,10 @@ class _DeviceTable:
     `device_ops.reduce_by_key` gives for the same ids and `grads` (float32, or float16 / bfloat16 as they are; grad_scale as in
     `apply_sparse`), None without `grads`; count a one-element int64 DEVICE tensor (-1: the plan overflowed).  Rows at or beyond
     count are not written.  A read: nothing is inserted, no score is touched, nothing is read on the host."""
+    return self._fetch_rows("tfra_table_fetch_planned", plan, grads, grad_scale, fields, default_row)
+
+  def _fetch_rows(self, call, plan, grads, grad_scale, fields, default_row):
+    """`fetch_planned` through the C call `call` (the narrow one or its wide twin: one argument list)."""
     _check_plan(plan, self._dim, self._device)
     n, nf = plan.n, 1 + self._aux_fields
     want = [True] * nf if fields is None else [bool(x) for x in fields]
@@ -951,7 +955,7 @@ class _DeviceTable:
     count = torch.zeros(1, dtype=torch.int64, device=self._device)
     if n:
       rf = self._row_fields(outs)
-      _over_plans((plan,), self._device, True, _capi.call, "tfra_table_fetch_planned", self._h, plan._h,
+      _over_plans((plan,), self._device, True, _capi.call, call, self._h, plan._h,
                   ctypes.byref(typed) if gsum is not None else None, _ptr(d), _ptr(keys), ctypes.byref(rf), _ptr(gsum), _ptr(count),
                   _stream(self._device))
     return keys, outs, gsum, count
@@ -962,6 +966,10 @@ class _DeviceTable:
     is not written (a resident key keeps its bytes there, a new key starts at aux_init); fields[0] is required.  Every element
     is rounded to the table's value dtype once, to nearest even.  count: a device int64 count of the leading keys that are
     written (None: all).  Scores and the epoch move as for ONE upsert(unique_keys=True) without scores."""
+    self._store_rows("tfra_table_store_rows", keys, fields, count)
+
+  def _store_rows(self, call, keys, fields, count):
+    """`store_rows` through the C call `call` (the narrow one or its wide twin: one argument list)."""
     keys = _as_tensor(keys, self._device)
     if keys.dtype != torch.int64:
       raise TypeError("store_rows takes the engine's int64 keys (as fetch_planned returns them), got %s" % keys.dtype)
@@ -982,7 +990,19 @@ class _DeviceTable:
     if n == 0:
       return
     rf = self._row_fields(rows)
-    _capi.call("tfra_table_store_rows", self._h, n, _ptr(count), _ptr(keys), ctypes.byref(rf), _stream(self._device))
+    _capi.call(call, self._h, n, _ptr(count), _ptr(keys), ctypes.byref(rf), _stream(self._device))
+
+  # ---- the same two for wide rows: 256 < dim <= 1024, one wave per key (tfra_rows_wide.hip); float32 gradients, no grad_scale ----
+  def fetch_planned_wide(self, plan, grads=None, fields=None, default_row=None):
+    """`fetch_planned` for a table of 256 < dim <= 1024 (tfra_table_fetch_planned_wide); `plan`: a `SparsePlan` of that dim.
+    grads: float32 (a half matrix or a scale is up-cast by the caller); gsum's columns [a, b) are bit for bit the narrow call's."""
+    if grads is not None:
+      grads = grads.to(self._device, torch.float32)
+    return self._fetch_rows("tfra_table_fetch_planned_wide", plan, grads, None, fields, default_row)
+
+  def store_rows_wide(self, keys, fields, count=None):
+    """`store_rows` for a table of 256 < dim <= 1024 (tfra_table_store_rows_wide)."""
+    self._store_rows("tfra_table_store_rows_wide", keys, fields, count)
 
 
 class _DeviceTier:
@@ -1484,6 +1504,13 @@ class _WideRows:
 
   def apply_planned_combined_wide(self, params, plan, grad_out, seg, weights, combiner, default_row, sync=True):
     return self._table.apply_planned_combined_wide(params, plan, grad_out, seg, weights, combiner, default_row, sync=sync)
+
+  # whole rows out and back of a wide table (`_DeviceTable.fetch_planned_wide` / `store_rows_wide`)
+  def fetch_planned_wide(self, plan, grads=None, fields=None):
+    return self._table.fetch_planned_wide(plan, grads=grads, fields=fields)
+
+  def store_rows_wide(self, keys, fields, count=None):
+    return self._table.store_rows_wide(keys, fields, count=count)
 
 
 class _MixedRows:
